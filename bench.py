@@ -13,7 +13,15 @@ already resident in HBM.  With N > 1 every rank vocodes its own batch of 8 utter
 no data-path collective, weak scaling); the timed region is bracketed by barrier + synchronize and the MAX over ranks
 is reported.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run does only what the headline figure needs: set up, warm up, time the steps, print the line.  `ms_per_step` is
+the wall time of one timed step.  `--dump-outputs DIR` writes the audio the last timed step returned as DIR/audio.npy
+(float32 [batch, frames * 256]; rank r > 0 writes DIR/audio_rank<r>.npy; an output beyond its share of 64 MB is written as
+the flat values at a fixed, seeded sample of positions); the inputs and weights are seeded, so two builds
+given the same arguments can be compared output for output.  `--full` adds everything below, measured as before: HIP-event
+timing of the in-layer GEMM during the timed steps (the roofline), the box probe, the BASELINE config-4 job, the secondary
+metrics and the CPU baseline.  A plain run leaves those objects null.
+
+Extra objects in the line (`--full`):
   roofline     -- dominant kernel = the WN in-layer implicit GEMM (K = 3*512 + 640, N = 1024).  `achieved` = algorithmic
                   FLOPs per launch / average launch duration measured with HIP events on the engine's stream.
   cpu_baseline -- CPU restatements of the reference algorithm (the numpy oracle and the torch.nn.functional one -- NOT the
@@ -45,6 +53,7 @@ SAMPLE_RATE = 22050
 EXCHANGE_HOP_US_MICROBENCH = 1.2       # constant (microbenchmark result, scripts/micro/xcd_exchange.cpp), used by one derived key
 DECODER_STEP_BYTES_F32 = 72.73e6       # all decoder-step weights once (enc 512; SURVEY.md section 8d / BASELINE.md section 2)
 DECODER_STEP_BYTES_F16W = 72.73e6 - 0.5 * (29.36e6 + 41.94e6)   # the two LSTM matrices in fp16, the rest fp32
+DUMP_BYTES_MAX = 64 * 2 ** 20          # --dump-outputs: bytes written over all ranks
 
 
 K_EXECUTED = 3 * 512 + 4 * 80      # dilated k3 conv taps + conditioning folded onto 4 mel frames
@@ -558,10 +567,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--batch', type=int, default=BATCH)
     ap.add_argument('--frames', type=int, default=FRAMES)
-    ap.add_argument('--cpu-frames', type=int, default=160, help='mel frames of the CPU-baseline WaveGlow sample (0 = skip)')
-    ap.add_argument('--no-kernel-timing', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the secondary (untimed-region) metrics')
-    ap.add_argument('--no-config4', action='store_true', help='skip the BASELINE config-4 scatter / synthesize / gather job')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: kernel timing + roofline, box probe, config-4 job, '
+                         'secondary metrics, CPU baseline (each can be dropped with the options below)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's audio as DIR/audio.npy (float32)")
+    ap.add_argument('--cpu-frames', type=int, default=160,
+                    help='with --full: mel frames of the CPU-baseline WaveGlow sample (0 = skip)')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='with --full: no HIP-event timing (no roofline)')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the secondary (untimed-region) metrics')
+    ap.add_argument('--no-config4', action='store_true',
+                    help='with --full: skip the BASELINE config-4 scatter / synthesize / gather job')
     ap.add_argument('--precision', default='f32', choices=('f32', 'f16x3', 'f16'),
                     help="arithmetic of the timed path: f32 = exact fp32 MFMA (default, the contract's config); "
                          "f16x3 = split fp16, fp32-class accuracy; f16 = fp16 operands")
@@ -571,6 +587,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -581,9 +599,9 @@ def main():
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     if args.gpus != world:
         raise SystemExit(f'--gpus {args.gpus} does not match WORLD_SIZE {world}')
-    # The process group is always created (world 1 included): the config-4 job below runs its scatter / gather through RCCL
-    # at every N, so that the N = 1 line and the N = 1 point of a scaling run are the same code.
-    distributed = True
+    # With --full the process group is created at world 1 too: the config-4 job below runs its scatter / gather through RCCL
+    # at every N, so that the N = 1 line and the N = 1 point of a scaling run are the same code.  A plain world-1 run needs none.
+    distributed = world > 1 or args.full
     if args.dry_run:
         return dry_run(args, world, rank)
     if not torch.cuda.is_available():
@@ -632,7 +650,8 @@ def main():
 
     for _ in range(args.warmup):
         eng.waveglow_infer(mel, z=z, sigma=1.0, precision=args.precision)
-    if not args.no_kernel_timing:
+    kernel_timing = args.full and not args.no_kernel_timing
+    if kernel_timing:
         eng.kernel_timing(True)
     barrier()
     t0 = time.perf_counter()
@@ -645,11 +664,19 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     assert bool(torch.isfinite(out).all())
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = 'audio.npy' if rank == 0 else f'audio_rank{rank}.npy'
+        audio = out.cpu().numpy().astype(np.float32)
+        cap = DUMP_BYTES_MAX // 4 // world                 # the dumps of all ranks together stay within DUMP_BYTES_MAX
+        if audio.size > cap:                               # larger than the default workload: a fixed, seeded sample
+            audio = audio.ravel()[np.sort(np.random.default_rng(0).choice(audio.size, cap, replace=False))]
+        np.save(os.path.join(args.dump_outputs, name), audio)
 
-    avg_us, launches = (0.0, 0) if args.no_kernel_timing else eng.kernel_time_us(KERNEL_WN_IN)
+    avg_us, launches = eng.kernel_time_us(KERNEL_WN_IN) if kernel_timing else (0.0, 0)
     eng.kernel_timing(False)
     probe = None
-    if rank == 0 and args.precision == 'f32':
+    if args.full and rank == 0 and args.precision == 'f32':
         try:
             probe = eng.probe_mfma_f32()              # right after the timed region: the box in the state the steps left it in
         except Exception:
@@ -671,7 +698,7 @@ def main():
         sys.stderr.write(f'[bench rank {rank}] config-4 job hung: no result after {CONFIG4_TIMEOUT_S} s; exiting with status 3\n')
         sys.stderr.flush()
         os._exit(3)
-    if not args.no_config4:
+    if args.full and not args.no_config4:
         import threading
         if rank == 0:
             headline['result'] = headline_result(args, world, B, T, dt, avg_us, launches, distributed, form, probe)
@@ -685,10 +712,10 @@ def main():
             config4 = {'error': f'{type(exc).__name__}: {exc}'} if rank == 0 else None
         watchdog.cancel()
     # secondary metrics and the CPU leg only at N = 1 (the other ranks would idle at the final barrier)
-    extra = secondary_metrics(eng, dev, rank) if (rank == 0 and world == 1 and not args.no_extra) else None
+    extra = secondary_metrics(eng, dev, rank) if (args.full and rank == 0 and world == 1 and not args.no_extra) else None
     if rank == 0:
         result = headline_result(args, world, B, T, dt, avg_us, launches, distributed, form, probe)
-        if args.cpu_frames > 0 and world == 1:
+        if args.full and args.cpu_frames > 0 and world == 1:
             result['cpu_baseline'] = cpu_baseline(w, cfg, args.cpu_frames)
         result['config4_sharded_job'] = config4
         result['extra'] = extra

@@ -14,7 +14,7 @@ PMC3="SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_LDS
 # 1. kernel trace + stats of the bench command (fp32 headline), then its PMC passes (separate runs, no trace flags;
 #    FETCH_SIZE and WRITE_SIZE do not fit one pass: "Request exceeds the capabilities of the hardware to collect")
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o bench -- \
-    python3 "$B" --steps 2 --warmup 1 --cpu-frames 0 --no-extra --no-config4 > "$out/bench_under_rocprof.json" 2> "$out/stats.log"
+    python3 "$B" --full --steps 2 --warmup 1 --cpu-frames 0 --no-extra --no-config4 > "$out/bench_under_rocprof.json" 2> "$out/stats.log"
 for pmc in "FETCH_SIZE" "WRITE_SIZE" "$PMC3"; do
     name="${pmc%% *}"
     timeout -k 10 400 rocprofv3 --pmc $pmc --output-format csv -d "$out/pmc_$name" -o bench -- \
