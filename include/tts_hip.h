@@ -195,6 +195,25 @@ int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int 
  * audio [B, N] (N >= 1024) -> mel [B, N/256 + 1, 80]                                                                */
 int tts_hip_mel_stft(tts_hip_engine* e, const float* audio, int B, int N, float* mel, int mem);
 
+/* ---- waveform clean-up (csrc/audio_proc.hip; DFT bases built on first use, no weights needed)
+ * reduce_noise: utils/audio/noisereducev1.py:175-290 with the defaults utils/audio/audio_processing.py:65-83 uses.
+ *   audio [B, N] -> out [B, N]; row b has lengths[b] (1 <= lengths[b] <= N) samples, lengths NULL = N for every row, and
+ *   out[b, lengths[b]:] = 0.  noise NULL = each row's first min(noise_len, lengths[b]) samples (audio_processing.py:71-75),
+ *   else an explicit clip [B, noise_len].  renormalize != 0: then normalize_audio(max_val=1.) over each row's own samples.
+ *   `lengths` is host memory in every mode (read during the call); audio, noise and out follow `mem` / live on the device
+ *   for the _async form.  All three calls share one workspace per handle: an _async call must have finished on its stream
+ *   (or be ordered before the next call, e.g. same stream) before the next reduce_noise / trim_silence on the handle.
+ * trim_silence: audio_processing.py:274-370 (method 'window': power 2, triangular window of window_length samples,
+ *   adaptive thresholds, max_trim_factor 5); mode 0 start_end, 1 start, 2 end; start / end int32 [B] (follow `mem`) with
+ *   trimmed row b = audio[b, start[b]:end[b]].  add_start, add_end >= 0 (margins in window lengths).                     */
+int tts_hip_reduce_noise(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const float* noise,
+                         int noise_len, int renormalize, float* out, int mem);
+int tts_hip_reduce_noise_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths,
+                               const float* noise, int noise_len, int renormalize, float* out, void* stream);
+int tts_hip_trim_silence(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int window_length,
+                         double threshold, double add_start, double add_end, int mode, int32_t* start, int32_t* end,
+                         int mem);
+
 /* ---- measurement hooks (used by bench.py; no effect on results) -------------------------------------------------
  * Average duration in microseconds of the dominant kernel's launches (HIP events on the engine's stream) since the
  * last reset, and how many launches were timed.  kind: 0 = WaveGlow WN in-layer GEMM (layers 1..7 of a flow: K = 2176),

@@ -61,6 +61,11 @@ SIGNATURES = {
     'tts_hip_probe_mfma_f32': (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
     'tts_hip_kernel_time_us': (c_int, [c_void_p, c_int, POINTER(c_double), POINTER(c_int64)]),
     'tts_hip_synchronize': (c_int, [c_void_p]),
+    'tts_hip_reduce_noise': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]),
+    'tts_hip_reduce_noise_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                           c_void_p]),
+    'tts_hip_trim_silence': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_double, c_double, c_double, c_int,
+                                     c_void_p, c_void_p, c_int]),
 }
 
 _lib = None

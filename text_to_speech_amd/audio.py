@@ -1,0 +1,86 @@
+"""Audio input path: wav reading, normalization and the device-side clean-up the reference applies while loading.
+
+Mirrors utils/audio/audio_io.py:100-144 (`load_audio`, `load_mel`) and :186-270 (`read_audio`): normalize ->
+reduce_noise -> normalize again -> trim_silence, in that order.  Normalization is host numpy (as in the reference, on the
+raw int16 samples); noise reduction and the trim indices run on the GPU (HipEngine.reduce_noise / trim_silence,
+csrc/audio_proc.hip).  Resampling and the trim methods other than 'window' are not provided: asking for them raises.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+_RN_KEYS = ('noise', 'noise_length')
+_TRIM_KEYS = ('threshold', 'window_length', 'add_start', 'add_end', 'mode')
+
+
+def read_wav(filename):
+    """(rate, samples) of a .wav file (audio_io.py:272-275: scipy.io.wavfile.read)."""
+    from scipy.io import wavfile
+    return wavfile.read(filename)
+
+
+def normalize_audio(audio, max_val=32767, dtype=np.int16):
+    """audio_processing.py:50-62: zero mean, peak `max_val`; max_val <= 1 gives float32 in [-1, 1]."""
+    if max_val <= 1.:
+        dtype = np.float32
+    audio = audio - np.mean(audio)
+    max_audio_val = np.max(np.abs(audio))
+    if max_audio_val <= 1e-9:
+        return audio.astype(dtype)
+    return (audio * (max_val / max_audio_val)).astype(dtype)
+
+
+def load_audio(data, rate=None, *, engine, normalize=True, reduce_noise=False, trim_silence=False, method='window', **kwargs):
+    """A filename or raw samples -> float32 [n] (audio_io.py:100-127 + :186-268).  `rate`: the rate the caller wants; a
+    file at another rate raises (no resampling).  Raw samples need `rate`.  kwargs: `noise`, `noise_length` for
+    reduce_noise; `threshold`, `window_length`, `add_start`, `add_end`, `mode` for trim_silence."""
+    if trim_silence and method != 'window':
+        raise ValueError(f"trim_silence: only method='window' is implemented (got {method!r})")
+    unknown = set(kwargs) - set(_RN_KEYS) - set(_TRIM_KEYS)
+    if unknown:
+        raise ValueError(f'load_audio: unknown arguments {sorted(unknown)}')
+    if isinstance(data, dict):
+        if 'rate' in data and rate is None:
+            rate = data['rate']
+        data = data['audio'] if 'audio' in data else data.get('filename', data.get('audio_filename'))
+    if isinstance(data, bytes):
+        data = data.decode()
+    if isinstance(data, str):
+        file_rate, audio = read_wav(data)
+        if rate is not None and int(rate) != int(file_rate):
+            raise ValueError(f'{data} is sampled at {file_rate} Hz, {rate} Hz requested: resampling is not supported')
+        rate = int(file_rate)
+    else:
+        if rate is None:
+            raise ValueError('load_audio: raw audio needs `rate`')
+        audio = data.detach().cpu().numpy() if hasattr(data, 'detach') else np.asarray(data)
+    if audio.ndim != 1:
+        raise ValueError(f'load_audio: expected mono audio [n], got shape {audio.shape}')
+
+    if normalize:
+        if normalize is True:
+            audio = normalize_audio(audio, max_val=1.)
+        elif normalize > 1 and np.issubdtype(audio.dtype, np.integer):
+            audio = (audio / normalize).astype(np.float32)
+    if reduce_noise:
+        rn = {k: kwargs[k] for k in _RN_KEYS if k in kwargs}
+        audio = engine.reduce_noise(np.asarray(audio, np.float32), rate, renormalize=normalize is True, **rn)
+    if trim_silence:
+        tr = {k: kwargs[k] for k in _TRIM_KEYS if k in kwargs}
+        start, end = engine.trim_silence(np.asarray(audio, np.float32), rate, **tr)
+        audio = audio[start:end]
+    return audio
+
+
+MEL_RATE = 22050                    # TacotronSTFT's sampling rate (engine.mel_stft's filterbank)
+
+
+def load_mel(data, rate=MEL_RATE, *, engine, **kwargs):
+    """audio_io.py:129-144 with TacotronSTFT (engine.mel_stft): load_audio(data, stft_fn.rate, ...) -> mel [T, 80].  Like the
+    reference, the audio is loaded at the STFT's rate: a file at another rate raises (no resampling)."""
+    if isinstance(data, dict) and 'mel' in data:
+        return data['mel']
+    if rate != MEL_RATE:
+        raise ValueError(f'load_mel: the mel-STFT runs at {MEL_RATE} Hz, got rate={rate}')
+    audio = load_audio(data, rate, engine=engine, **kwargs)
+    return engine.mel_stft(np.asarray(audio, np.float32))[0]

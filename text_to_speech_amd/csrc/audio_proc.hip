@@ -1,0 +1,641 @@
+// audio_proc.hip -- waveform clean-up on gfx950: spectral-gating noise reduction and window-method silence trimming.
+//
+// reduce_noise replaces utils/audio/noisereducev1.py:175-290 with the defaults utils/audio/audio_processing.py:65-83 uses
+// (n_fft = win = 2048, hop 512, n_grad_freq 2, n_grad_time 4, n_std_thresh 1.5, prop_decrease 1, pad_clipping on, librosa
+// centre padding with zeros).  Both DFTs are dense products on the fp32 MFMA GEMM (gemm_f32.h), like mel_stft.hip: the
+// frames are overlapping rows (stride = hop) of the padded signal and are never materialised; the inverse basis carries the
+// irfft scaling and the synthesis window, and the overlap-add is a gather (<= 4 frames per sample, no atomics).
+// trim_silence replaces audio_processing.py:274-370 (method 'window': power 2, triangular window, adaptive thresholds,
+// max_trim_factor 5): np.convolve(x^2, window, 'valid') as a direct fp64 sum, then the thresholds and indices per row.
+//
+// Every row b has its own length L_b <= N; nothing reads across a row's end, and a row's result equals a one-row call on
+// audio[b, :L_b].
+#include "engine.h"
+#include "gemm_f32.h"
+
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+
+using namespace ttsgemm;
+
+namespace {
+
+constexpr int NFFT = 2048, HOP = 512, HALF = NFFT / 2, NBIN = NFFT / 2 + 1;
+constexpr int NK = 2080;                     // 2 * 1025 DFT rows (real, imaginary) padded to a multiple of 32
+constexpr int TRIM_OUT = 1024;               // conv outputs per block of the trim convolution (256 threads x 4)
+constexpr int TRIM_JC = 1024;                // window taps staged in LDS per pass
+
+// per-row facts shared by the kernels: [0] L_b, [1] F_b signal frames, [2] noise clip length, [3] noise frames
+struct RowInfo {
+    const int* p;
+    int B;
+    __device__ int len(int b) const { return p[b]; }
+    __device__ int frames(int b) const { return p[B + b]; }
+    __device__ int nlen(int b) const { return p[2 * B + b]; }
+    __device__ int nframes(int b) const { return p[3 * B + b]; }
+};
+
+// dst[b][p] = src[b][p - 1024] for p - 1024 in [0, len_b), else 0; rows of dst are NPd floats apart and the `total`
+// extent covers B * NPd plus the slack read by the last frames
+__global__ void audio_pad_rows_kernel(const float* __restrict__ src, long long src_ld, const int* __restrict__ lens,
+                                      float* __restrict__ dst, int NPd, int B, long long total) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int b = (int)(idx / NPd), p = (int)(idx % NPd);
+    float v = 0.f;
+    if (b < B) {
+        const int s = p - HALF;
+        if (s >= 0 && s < lens[b]) v = src[b * src_ld + s];
+    }
+    dst[idx] = v;
+}
+
+// pmax[b] = max |X|^2 over the row's frames f < F_b (fp32 bit patterns of non-negative values order as unsigned)
+__global__ void audio_power_max_kernel(const float* __restrict__ S, int Fr, const int* __restrict__ fcount,
+                                       unsigned* __restrict__ pmax) {
+    const int b = blockIdx.y;
+    const long long n = (long long)fcount[b] * NBIN;
+    float m = 0.f;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long f = i / NBIN, k = i % NBIN;
+        const float* row = S + ((long long)b * Fr + f) * NK;
+        const float re = row[k], im = row[NBIN + k];
+        m = fmaxf(m, re * re + im * im);
+    }
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    __shared__ float wm[4];
+    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = fmaxf(m, wm[w]);
+        m = fmaxf(m, wm[0]);
+        atomicMax(pmax + b, __float_as_uint(m));
+    }
+}
+
+// librosa.amplitude_to_db(|X|, ref=1, amin=1e-20, top_db=80) (noisereducev1.py:66-67): 10 log10(max(p, 1e-40)) clamped in
+// the log domain (1e-40 is an fp32 denormal that flushes to zero), then max(v, rowmax - 80)
+__device__ __forceinline__ float power_db(float p) { return fmaxf(10.f * log10f(p), -400.f); }
+
+// thresh[b][k] = mean + 1.5 std (population) of the noise clip's dB over its frames (noisereducev1.py:244-247), fp64 sums
+__global__ void audio_noise_thresh_kernel(const float* __restrict__ Sn, int Frn, RowInfo info,
+                                          const unsigned* __restrict__ pmax_n, float* __restrict__ thresh) {
+    const int b = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= NBIN) return;
+    const int F = info.nframes(b);
+    const float floor_db = power_db(__uint_as_float(pmax_n[b])) - 80.f;
+    const float* base = Sn + (long long)b * Frn * NK;
+    double s = 0.0;
+    for (int f = 0; f < F; ++f) {
+        const float re = base[(long long)f * NK + k], im = base[(long long)f * NK + NBIN + k];
+        s += (double)fmaxf(power_db(re * re + im * im), floor_db);
+    }
+    const double mean = s / F;
+    double q = 0.0;
+    for (int f = 0; f < F; ++f) {
+        const float re = base[(long long)f * NK + k], im = base[(long long)f * NK + NBIN + k];
+        const double d = (double)fmaxf(power_db(re * re + im * im), floor_db) - mean;
+        q += d * d;
+    }
+    thresh[b * NBIN + k] = (float)(mean + 1.5 * sqrt(q / F));
+}
+
+// mask[b][f][k] = dB(X) < thresh[b][k] for f < F_b, else 0 (noisereducev1.py:252-259)
+__global__ void audio_gate_mask_kernel(const float* __restrict__ S, int Fr, RowInfo info, const unsigned* __restrict__ pmax,
+                                       const float* __restrict__ thresh, uint8_t* __restrict__ mask) {
+    const int b = blockIdx.z, f = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= NBIN) return;
+    uint8_t v = 0;
+    if (f < info.frames(b)) {
+        const float* row = S + ((long long)b * Fr + f) * NK;
+        const float re = row[k], im = row[NBIN + k];
+        const float db = fmaxf(power_db(re * re + im * im), power_db(__uint_as_float(pmax[b])) - 80.f);
+        v = db < thresh[b * NBIN + k] ? 1 : 0;
+    }
+    mask[((long long)b * Fr + f) * NBIN + k] = v;
+}
+
+// X *= 1 - smooth(mask): the 5 x 9 filter outer([1,2,3,2,1]/3, [1,2,3,4,5,4,3,2,1]/5)/15 (noisereducev1.py:81-106) as an
+// integer stencil over 225, zero outside bins 0..1024 and frames 0..F_b-1 (fftconvolve 'same', :142); frames >= F_b -> 0
+__global__ void audio_gate_apply_kernel(float* __restrict__ S, int Fr, RowInfo info, const uint8_t* __restrict__ mask) {
+    const int b = blockIdx.z, f = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= NBIN) return;
+    const int F = info.frames(b);
+    float* row = S + ((long long)b * Fr + f) * NK;
+    if (f >= F) {
+        row[k] = 0.f;
+        row[NBIN + k] = 0.f;
+        return;
+    }
+    const int wf[5] = {1, 2, 3, 2, 1};
+    const int wt[9] = {1, 2, 3, 4, 5, 4, 3, 2, 1};
+    int acc = 0;
+    for (int dt = -4; dt <= 4; ++dt) {
+        const int ff = f + dt;
+        if (ff < 0 || ff >= F) continue;
+        const uint8_t* mr = mask + ((long long)b * Fr + ff) * NBIN;
+        int s = 0;
+        for (int df = -2; df <= 2; ++df) {
+            const int kk = k + df;
+            if (kk >= 0 && kk < NBIN) s += wf[df + 2] * mr[kk];
+        }
+        acc += wt[dt + 4] * s;
+    }
+    const float g = (float)(225 - acc) / 225.f;
+    row[k] *= g;
+    row[NBIN + k] *= g;
+}
+
+// out[b][t] = sum_f frames[f][p - 512 f] / wss(p), p = t + 1024 (librosa.istft centre trim + fix_length(L_b)), over the
+// row's frames f < F_b; t >= L_b -> 0
+__global__ void audio_overlap_add_kernel(const float* __restrict__ T, int Fr, RowInfo info, const double* __restrict__ win2,
+                                         float* __restrict__ out, int N) {
+    const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= N) return;
+    float v = 0.f;
+    if (t < info.len(b)) {
+        const int p = t + HALF, F = info.frames(b);
+        const int f_lo = p >= NFFT ? (p - NFFT) / HOP + 1 : 0;
+        const int f_hi = min(p / HOP, F - 1);
+        double y = 0.0, w = 0.0;
+        for (int f = f_lo; f <= f_hi; ++f) {
+            const int n = p - f * HOP;
+            y += (double)T[((long long)b * Fr + f) * NFFT + n];
+            w += win2[n];
+        }
+        v = (float)(w > (double)FLT_MIN ? y / w : y);
+    }
+    out[(long long)b * N + t] = v;
+}
+
+__device__ double block_sum_d(double v, double* sh) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[w] = v;
+    __syncthreads();
+    double s = 0.0;
+    for (int i = 0; i < nw; ++i) s += sh[i];
+    return s;
+}
+
+// normalize_audio(x, max_val=1.) (audio_processing.py:50-62) over the row's own L_b samples: x - mean, / max|x| unless <= 1e-9
+__global__ __launch_bounds__(1024) void audio_renormalize_kernel(float* __restrict__ x, int N, RowInfo info) {
+    __shared__ double sh[16];
+    const int b = blockIdx.x, L = info.len(b);
+    float* r = x + (long long)b * N;
+    double s = 0.0;
+    for (int t = threadIdx.x; t < L; t += blockDim.x) s += r[t];
+    const float mean = (float)(block_sum_d(s, sh) / L);
+    float m = 0.f;
+    for (int t = threadIdx.x; t < L; t += blockDim.x) m = fmaxf(m, fabsf(r[t] - mean));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    __shared__ float shm[16];
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) m = fmaxf(m, shm[i]);
+    const bool scale = m > 1e-9f;
+    const float sc = scale ? 1.f / m : 1.f;
+    for (int t = threadIdx.x; t < L; t += blockDim.x) r[t] = scale ? (r[t] - mean) * sc : r[t] - mean;
+}
+
+// conv[b][k] = sum_j x[k + j]^2 * w[W - 1 - j], k <= L_b - W (np.convolve 'valid' with L_b >= W; squares rounded to fp32
+// like np.power on float32, products and sums in fp64).  256 threads x 4 consecutive outputs; the squared samples and the
+// reversed window pass through LDS in chunks of TRIM_JC taps, one b128 operand read per 4 taps.
+__global__ __launch_bounds__(256) void audio_trim_conv_kernel(const float* __restrict__ x, int N, RowInfo info,
+                                                              const double* __restrict__ wrev, int W, int Wp,
+                                                              double* __restrict__ conv, int Cst) {
+    __shared__ __attribute__((aligned(16))) float xs[TRIM_OUT + TRIM_JC + 4];
+    __shared__ double ws[TRIM_JC];
+    const int b = blockIdx.y, L = info.len(b);
+    if (L < W) return;
+    const int nout = L - W + 1, k0 = blockIdx.x * TRIM_OUT;
+    if (k0 >= nout) return;
+    const float* r = x + (long long)b * N;
+    const int t = threadIdx.x;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int j0 = 0; j0 < Wp; j0 += TRIM_JC) {
+        __syncthreads();
+        for (int i = t; i < TRIM_OUT + TRIM_JC + 4; i += 256) {
+            const long long s = (long long)k0 + j0 + i;
+            const float v = s < L ? r[s] : 0.f;
+            xs[i] = v * v;
+        }
+        for (int i = t; i < TRIM_JC; i += 256) ws[i] = j0 + i < Wp ? wrev[j0 + i] : 0.0;
+        __syncthreads();
+        const int jn = min(TRIM_JC, Wp - j0);             // multiple of 4
+        f32x4 c = *(const f32x4*)&xs[4 * t];
+        double cur[4] = {c[0], c[1], c[2], c[3]};
+        for (int jj = 0; jj < jn; jj += 4) {
+            const f32x4 q = *(const f32x4*)&xs[4 * t + jj + 4];
+            const double nx[4] = {q[0], q[1], q[2], q[3]};
+            const double v[4] = {ws[jj], ws[jj + 1], ws[jj + 2], ws[jj + 3]};
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int o = 0; o < 4; ++o) {
+                    const int i = o + u;
+                    acc[o] = fma(i < 4 ? cur[i] : nx[i - 4], v[u], acc[o]);
+                }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cur[i] = nx[i];
+        }
+    }
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+        const int k = k0 + 4 * t + o;
+        if (k < nout) conv[(long long)b * Cst + k] = acc[o];
+    }
+}
+
+// rows shorter than the window: np.convolve swaps the operands, conv[k] = sum_m x[m]^2 w[k + L - 1 - m], k <= W - L
+__global__ void audio_trim_conv_short_kernel(const float* __restrict__ x, int N, RowInfo info, const double* __restrict__ w,
+                                             int W, double* __restrict__ conv, int Cst) {
+    const int b = blockIdx.y, L = info.len(b);
+    if (L >= W) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > W - L) return;
+    const float* r = x + (long long)b * N;
+    double s = 0.0;
+    for (int m = 0; m < L; ++m) {
+        const float v = r[m] * r[m];
+        s = fma((double)v, w[k + L - 1 - m], s);
+    }
+    conv[(long long)b * Cst + k] = s;
+}
+
+struct TrimParams {
+    int W;              // window taps (2 * (wl // 2))
+    int wl;             // window_length (mean spans and margins)
+    double threshold, add_start, add_end;
+    int mode;           // 0 start_end, 1 start, 2 end
+};
+
+// thresholds and indices of trim_silence_window (audio_processing.py:340-370), one block per row
+__global__ __launch_bounds__(1024) void audio_trim_bounds_kernel(const double* __restrict__ conv, int Cst, RowInfo info,
+                                                                 TrimParams P, int* __restrict__ start, int* __restrict__ end) {
+    __shared__ double sh[16];
+    __shared__ int shi[2][16];
+    const int b = blockIdx.x, L = info.len(b);
+    const int nc = L >= P.W ? L - P.W + 1 : P.W - L + 1;
+    const double* c = conv + (long long)b * Cst;
+    const bool do_end = P.mode != 1, do_start = P.mode != 2;
+    // np.mean(conv[-wl:]), np.mean(conv[:wl])
+    const int e0 = max(0, nc - P.wl), s1 = min(P.wl, nc);
+    double se = 0.0, ss = 0.0;
+    for (int i = threadIdx.x; i < nc; i += blockDim.x) {
+        if (i >= e0) se += c[i];
+        if (i < s1) ss += c[i];
+    }
+    se = block_sum_d(se, sh);
+    ss = block_sum_d(ss, sh);
+    const double th_end = fmin(P.threshold, fmax(se / (nc - e0) * 5.0, P.threshold / 50.0));
+    const double th_start = fmin(P.threshold, fmax(ss / s1 * 5.0, P.threshold / 50.0));
+    int last = -1, first = 0x7fffffff;
+    for (int i = threadIdx.x; i < nc; i += blockDim.x) {
+        const double v = c[i];
+        if (v > th_end) last = max(last, i);
+        if (v > th_start) first = min(first, i);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        last = max(last, __shfl_xor(last, o));
+        first = min(first, __shfl_xor(first, o));
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        shi[0][threadIdx.x >> 6] = last;
+        shi[1][threadIdx.x >> 6] = first;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) {
+        last = max(last, shi[0][i]);
+        first = min(first, shi[1][i]);
+    }
+    long long s = 0, e = L;
+    if (do_end && last >= 0) e = std::min<long long>(L, (long long)last + (long long)((double)P.wl * P.add_end));
+    if (do_start && first != 0x7fffffff) s = std::max<long long>(0, (long long)first - (long long)((double)P.wl * P.add_start));
+    if (!(std::max<long long>(0, e - s) > L / 5)) {     // max_trim_factor 5: keep the whole row
+        s = 0;
+        e = L;
+    }
+    start[b] = (int)s;
+    end[b] = (int)e;
+}
+
+// np.linspace(start, stop, num) element i (numpy: i * step + start, last element = stop)
+double np_linspace(double a, double z, int num, int i) {
+    if (num == 1) return a;
+    if (i == num - 1) return z;
+    const double step = (z - a) / (num - 1);
+    const double y = (double)i * step;
+    return y + a;
+}
+
+constexpr long long LIM = (1ll << 31) - 65536;    // byte extent of any buffer a kernel or GEMM descriptor addresses
+
+}  // namespace
+
+void audioproc_free(tts_hip_engine* e) {
+    AudioProcDev& a = e->aproc;
+    for (void* p : a.allocs) (void)hipFree(p);
+    a.allocs.clear();
+    a.fwd_Bt = a.inv_Bt = nullptr;
+    a.win2 = nullptr;
+    a.ws.release();
+    a.io.release();
+    a.trim_win.release();
+    a.trim_wl = -1;
+}
+
+namespace {
+
+// DFT bases (built once, on first use, in fp64 with exact phase reduction): forward rows 0..1024 = cos * hann, 1025..2049 =
+// -sin * hann, 2050..2079 = 0 ([NK][2048]); inverse [2048][NK] = the irfft terms (1/2048, x2 for bins 1..1023, imaginary
+// parts of bins 0 and 1024 dropped) times the synthesis window; win2 = hann^2 (librosa window_sumsquare)
+int audioproc_bases(tts_hip_engine* e) {
+    AudioProcDev& a = e->aproc;
+    if (a.fwd_Bt) return TTS_HIP_OK;
+    std::vector<double> win(NFFT), c(NFFT), s(NFFT);
+    for (int n = 0; n < NFFT; ++n) {
+        win[n] = 0.5 - 0.5 * std::cos(2.0 * M_PI * n / NFFT);     // scipy.signal.get_window('hann', 2048, fftbins=True)
+        c[n] = std::cos(2.0 * M_PI * n / NFFT);
+        s[n] = std::sin(2.0 * M_PI * n / NFFT);
+    }
+    std::vector<float> fwd((size_t)NK * NFFT, 0.f), inv((size_t)NFFT * NK, 0.f);
+    for (int k = 0; k < NBIN; ++k) {
+        const double ck = (k == 0 || k == NFFT / 2) ? 1.0 : 2.0;
+        for (int n = 0; n < NFFT; ++n) {
+            const int kn = (int)(((long long)k * n) % NFFT);          // exact phase reduction
+            fwd[(size_t)k * NFFT + n] = (float)(c[kn] * win[n]);
+            fwd[(size_t)(NBIN + k) * NFFT + n] = (float)(-s[kn] * win[n]);
+            inv[(size_t)n * NK + k] = (float)(ck * c[kn] * win[n] / NFFT);
+            if (k != 0 && k != NFFT / 2) inv[(size_t)n * NK + NBIN + k] = (float)(-ck * s[kn] * win[n] / NFFT);
+        }
+    }
+    std::vector<double> w2(NFFT);
+    for (int n = 0; n < NFFT; ++n) w2[n] = win[n] * win[n];
+    float* p = nullptr;
+    int rc = upload(e, fwd.data(), fwd.size(), &p, a.allocs);
+    if (rc) return rc;
+    a.fwd_Bt = p;
+    rc = upload(e, inv.data(), inv.size(), &p, a.allocs);
+    if (rc) return rc;
+    a.inv_Bt = p;
+    rc = upload(e, (const float*)w2.data(), w2.size() * 2, &p, a.allocs);
+    if (rc) return rc;
+    a.win2 = (double*)p;
+    return TTS_HIP_OK;
+}
+
+size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+struct RnGeom {
+    int Fr, NP, Frn, NQ;
+    size_t off_info, off_pmax, off_thr, off_P, off_Q, off_S, off_Sn, off_T, off_mask, total;
+};
+
+RnGeom rn_geom(int B, int N, int noise_len) {
+    RnGeom g{};
+    g.Fr = (N + 2560 + HOP - 1) / HOP;          // >= F_b = 1 + (L_b + 512) // 512 for every row; NP = Fr * 512 >= N + 2560
+    g.NP = g.Fr * HOP;
+    g.Frn = (noise_len + NFFT + HOP - 1) / HOP; // >= 1 + noise_len // 512
+    g.NQ = g.Frn * HOP;
+    size_t o = 0;
+    g.off_info = o; o += al256((size_t)4 * B * 4);
+    g.off_pmax = o; o += al256((size_t)2 * B * 4);
+    g.off_thr = o; o += al256((size_t)B * NBIN * 4);
+    g.off_P = o; o += al256(((size_t)B * g.NP + NFFT) * 4);
+    g.off_Q = o; o += al256(((size_t)B * g.NQ + NFFT) * 4);
+    g.off_S = o; o += al256((size_t)B * g.Fr * NK * 4);
+    g.off_Sn = o; o += al256((size_t)B * g.Frn * NK * 4);
+    g.off_T = o; o += al256((size_t)B * g.Fr * NFFT * 4);
+    g.off_mask = o; o += al256((size_t)B * g.Fr * NBIN);
+    g.total = o;
+    return g;
+}
+
+hipError_t dft_gemm(const float* A, long long lda, int K, const float* Bt, int Nout, int M, float* out, hipStream_t st) {
+    GemmArgs g{};
+    g.M = M;
+    g.N = Nout;
+    g.L = M;
+    g.nseg = 1;
+    g.seg[0] = ASeg{A, lda, 0, K, K};
+    g.Bt = Bt;
+    g.ldb = K;
+    g.mode = EPI_LINEAR;
+    g.split = Nout;
+    g.out0 = out;
+    g.ld0 = Nout;
+    return gemm_big(g, 1, st);
+}
+
+unsigned blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
+
+// device pointers only; `lengths` / `noise_lens` already validated on the host
+int reduce_noise_run(tts_hip_engine* e, const float* d_audio, int B, int N, const std::vector<int>& lens,
+                     const float* d_noise, int noise_len, int renorm, float* d_out) {
+    AudioProcDev& a = e->aproc;
+    int rc = audioproc_bases(e);
+    if (rc) return rc;
+    const RnGeom g = rn_geom(B, N, noise_len);
+    hipStream_t st = e->stream;
+    HIPCHK(e, a.ws.ensure(g.total));
+    char* base = (char*)a.ws.p;
+    int* d_info = (int*)(base + g.off_info);
+    unsigned* pmax = (unsigned*)(base + g.off_pmax);
+    float* thr = (float*)(base + g.off_thr);
+    float* P = (float*)(base + g.off_P);
+    float* Q = (float*)(base + g.off_Q);
+    float* S = (float*)(base + g.off_S);
+    float* Sn = (float*)(base + g.off_Sn);
+    float* T = (float*)(base + g.off_T);
+    uint8_t* mask = (uint8_t*)(base + g.off_mask);
+    // row facts: L_b, F_b, noise clip length, noise frames (the default clip is audio[b, :min(noise_len, L_b)])
+    a.info_h.assign((size_t)4 * B, 0);
+    for (int b = 0; b < B; ++b) {
+        const int L = lens[b], nl = d_noise ? noise_len : std::min(noise_len, L);
+        a.info_h[b] = L;
+        a.info_h[B + b] = 1 + (L + HOP) / HOP;
+        a.info_h[2 * B + b] = nl;
+        a.info_h[3 * B + b] = 1 + nl / HOP;
+    }
+    HIPCHK(e, hipMemcpyAsync(d_info, a.info_h.data(), a.info_h.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemsetAsync(pmax, 0, (size_t)2 * B * 4, st));
+    const RowInfo info{d_info, B};
+    {
+        const long long n = (long long)B * g.NP + NFFT;
+        hipLaunchKernelGGL(audio_pad_rows_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, d_audio, (long long)N, d_info, P,
+                           g.NP, B, n);
+        HIPCHK(e, hipGetLastError());
+        const long long nq = (long long)B * g.NQ + NFFT;
+        hipLaunchKernelGGL(audio_pad_rows_kernel, dim3(blocks(nq, 256)), dim3(256), 0, st, d_noise ? d_noise : d_audio,
+                           (long long)(d_noise ? noise_len : N), d_info + 2 * B, Q, g.NQ, B, nq);
+        HIPCHK(e, hipGetLastError());
+    }
+    // forward DFTs: frame (b, f) is row b * Fr + f of the hop-strided view of the padded rows
+    HIPCHK(e, dft_gemm(P, HOP, NFFT, a.fwd_Bt, NK, B * g.Fr, S, st));
+    HIPCHK(e, dft_gemm(Q, HOP, NFFT, a.fwd_Bt, NK, B * g.Frn, Sn, st));
+    hipLaunchKernelGGL(audio_power_max_kernel, dim3(64, B), dim3(256), 0, st, S, g.Fr, d_info + B, pmax);
+    HIPCHK(e, hipGetLastError());
+    hipLaunchKernelGGL(audio_power_max_kernel, dim3(8, B), dim3(256), 0, st, Sn, g.Frn, d_info + 3 * B, pmax + B);
+    HIPCHK(e, hipGetLastError());
+    hipLaunchKernelGGL(audio_noise_thresh_kernel, dim3(blocks(NBIN, 256), B), dim3(256), 0, st, Sn, g.Frn, info, pmax + B, thr);
+    HIPCHK(e, hipGetLastError());
+    hipLaunchKernelGGL(audio_gate_mask_kernel, dim3(blocks(NBIN, 256), g.Fr, B), dim3(256), 0, st, S, g.Fr, info, pmax, thr, mask);
+    HIPCHK(e, hipGetLastError());
+    hipLaunchKernelGGL(audio_gate_apply_kernel, dim3(blocks(NBIN, 256), g.Fr, B), dim3(256), 0, st, S, g.Fr, info, mask);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, dft_gemm(S, NK, NK, a.inv_Bt, NFFT, B * g.Fr, T, st));
+    hipLaunchKernelGGL(audio_overlap_add_kernel, dim3(blocks(N, 256), B), dim3(256), 0, st, T, g.Fr, info, a.win2, d_out, N);
+    HIPCHK(e, hipGetLastError());
+    if (renorm) {
+        hipLaunchKernelGGL(audio_renormalize_kernel, dim3(B), dim3(1024), 0, st, d_out, N, info);
+        HIPCHK(e, hipGetLastError());
+    }
+    return TTS_HIP_OK;
+}
+
+// host-side validation shared by both entry points; fills `lens`
+int rn_check(tts_hip_engine* e, const char* what, const float* audio, int B, int N, const int32_t* lengths, int noise_len,
+             const float* out, std::vector<int>& lens) {
+    if (!audio || !out || B <= 0 || N <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", what);
+    if (noise_len < 1) return set_err(e, TTS_HIP_EINVAL, "%s: noise_len = %d < 1", what, noise_len);
+    lens.assign(B, N);
+    if (lengths)
+        for (int b = 0; b < B; ++b) {
+            if (lengths[b] < 1 || lengths[b] > N)
+                return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d outside [1, N = %d]", what, b, lengths[b], N);
+            lens[b] = lengths[b];
+        }
+    const RnGeom g = rn_geom(B, N, noise_len);
+    const long long biggest = std::max({(long long)B * g.Fr * NK * 4, (long long)B * g.NP * 4 + NFFT * 4,
+                                        (long long)B * g.Frn * NK * 4, (long long)B * g.NQ * 4 + NFFT * 4,
+                                        (long long)B * N * 4, (long long)B * noise_len * 4});
+    if (biggest >= LIM || g.Fr > 65535)
+        return set_err(e, TTS_HIP_EINVAL, "%s: B = %d x N = %d (noise_len %d) too large for 31-bit offsets", what, B, N, noise_len);
+    return TTS_HIP_OK;
+}
+
+}  // namespace
+
+int tts_hip_reduce_noise_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths,
+                               const float* noise, int noise_len, int renormalize, float* out, void* stream) {
+    if (!e) return TTS_HIP_EINVAL;
+    std::vector<int> lens;
+    if (int rc = rn_check(e, "reduce_noise_async", audio, B, N, lengths, noise_len, out, lens)) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    StreamScope scope(e, stream);
+    return reduce_noise_run(e, audio, B, N, lens, noise, noise_len, renormalize, out);
+}
+
+int tts_hip_reduce_noise(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const float* noise,
+                         int noise_len, int renormalize, float* out, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    std::vector<int> lens;
+    if (int rc = rn_check(e, "reduce_noise", audio, B, N, lengths, noise_len, out, lens)) return rc;
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "reduce_noise: bad mem kind %d", mem);
+    HIPCHK(e, hipSetDevice(e->device));
+    AudioProcDev& a = e->aproc;
+    const size_t n = (size_t)B * N, nn = noise ? (size_t)B * noise_len : 0;
+    const float* d_in = audio;
+    const float* d_noise = noise;
+    float* d_out = out;
+    if (mem == TTS_HIP_MEM_HOST) {
+        HIPCHK(e, a.io.ensure(al256(n * 4) * 2 + nn * 4));
+        float* io = a.io.f();
+        float* io_out = (float*)((char*)a.io.p + al256(n * 4));
+        float* io_noise = (float*)((char*)a.io.p + 2 * al256(n * 4));
+        HIPCHK(e, hipMemcpyAsync(io, audio, n * 4, hipMemcpyHostToDevice, e->stream));
+        if (noise) HIPCHK(e, hipMemcpyAsync(io_noise, noise, nn * 4, hipMemcpyHostToDevice, e->stream));
+        d_in = io;
+        d_noise = noise ? io_noise : nullptr;
+        d_out = io_out;
+    }
+    int rc = reduce_noise_run(e, d_in, B, N, lens, d_noise, noise_len, renormalize, d_out);
+    if (rc) return rc;
+    if (mem == TTS_HIP_MEM_HOST) HIPCHK(e, hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return TTS_HIP_OK;
+}
+
+int tts_hip_trim_silence(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int window_length,
+                         double threshold, double add_start, double add_end, int mode, int32_t* start, int32_t* end, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (!audio || !start || !end || B <= 0 || N <= 0) return set_err(e, TTS_HIP_EINVAL, "trim_silence: bad argument");
+    if (window_length < 2) return set_err(e, TTS_HIP_EINVAL, "trim_silence: window_length = %d < 2", window_length);
+    if (mode < 0 || mode > 2) return set_err(e, TTS_HIP_EINVAL, "trim_silence: mode %d not 0 (start_end), 1 (start) or 2 (end)", mode);
+    if (!std::isfinite(threshold) || !std::isfinite(add_start) || !std::isfinite(add_end) ||
+        add_start < 0 || add_end < 0 || (double)window_length * add_start > 1e9 || (double)window_length * add_end > 1e9)
+        return set_err(e, TTS_HIP_EINVAL, "trim_silence: threshold / margins must be finite, margins >= 0 and not oversized");
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "trim_silence: bad mem kind %d", mem);
+    const int h = window_length / 2, W = 2 * h, Wp = (W + 3) / 4 * 4;
+    std::vector<int> lens(B, N);
+    int min_len = N;
+    if (lengths)
+        for (int b = 0; b < B; ++b) {
+            if (lengths[b] < 1 || lengths[b] > N)
+                return set_err(e, TTS_HIP_EINVAL, "trim_silence: lengths[%d] = %d outside [1, N = %d]", b, lengths[b], N);
+            lens[b] = lengths[b];
+            min_len = std::min(min_len, lengths[b]);
+        }
+    const int Cst = std::max(N, W) + 1;
+    if ((long long)B * Cst * 8 >= LIM || (long long)B * N * 4 >= LIM)
+        return set_err(e, TTS_HIP_EINVAL, "trim_silence: B = %d x N = %d too large for 31-bit offsets", B, N);
+    HIPCHK(e, hipSetDevice(e->device));
+    AudioProcDev& a = e->aproc;
+    hipStream_t st = e->stream;
+    // window: concat(linspace(0, 1, h), linspace(1, 0, h)) / h, uploaded with its reversal (+ zero taps up to Wp)
+    if (a.trim_wl != window_length) {
+        std::vector<double> w(W), hw((size_t)W + Wp, 0.0);
+        for (int i = 0; i < h; ++i) {
+            w[i] = np_linspace(0.0, 1.0, h, i) / h;
+            w[h + i] = np_linspace(1.0, 0.0, h, i) / h;
+        }
+        for (int i = 0; i < W; ++i) {
+            hw[i] = w[i];
+            hw[W + i] = w[W - 1 - i];
+        }
+        HIPCHK(e, a.trim_win.ensure(hw.size() * 8));
+        HIPCHK(e, hipMemcpyAsync(a.trim_win.p, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        a.trim_wl = window_length;
+    }
+    const double* d_w = (const double*)a.trim_win.p;
+    const size_t off_conv = 0, off_info = al256((size_t)B * Cst * 8), off_se = off_info + al256((size_t)B * 4),
+                 off_in = off_se + al256((size_t)2 * B * 4), total = off_in + (mem == TTS_HIP_MEM_HOST ? (size_t)B * N * 4 : 0);
+    HIPCHK(e, a.ws.ensure(total));
+    char* base = (char*)a.ws.p;
+    double* conv = (double*)(base + off_conv);
+    int* d_info = (int*)(base + off_info);
+    int* d_se = (int*)(base + off_se);
+    const float* d_in = audio;
+    if (mem == TTS_HIP_MEM_HOST) {
+        HIPCHK(e, hipMemcpyAsync(base + off_in, audio, (size_t)B * N * 4, hipMemcpyHostToDevice, st));
+        d_in = (const float*)(base + off_in);
+    }
+    a.info_h.assign(lens.begin(), lens.end());
+    HIPCHK(e, hipMemcpyAsync(d_info, a.info_h.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    const RowInfo info{d_info, B};
+    if (N >= W) {
+        hipLaunchKernelGGL(audio_trim_conv_kernel, dim3(blocks(N - W + 1, TRIM_OUT), B), dim3(256), 0, st, d_in, N, info,
+                           d_w + W, W, Wp, conv, Cst);
+        HIPCHK(e, hipGetLastError());
+    }
+    if (min_len < W) {
+        hipLaunchKernelGGL(audio_trim_conv_short_kernel, dim3(blocks(W - min_len + 1, 256), B), dim3(256), 0, st, d_in, N, info,
+                           d_w, W, conv, Cst);
+        HIPCHK(e, hipGetLastError());
+    }
+    const TrimParams P{W, window_length, threshold, add_start, add_end, mode};
+    hipLaunchKernelGGL(audio_trim_bounds_kernel, dim3(B), dim3(1024), 0, st, conv, Cst, info, P, d_se, d_se + B);
+    HIPCHK(e, hipGetLastError());
+    const hipMemcpyKind kind = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    HIPCHK(e, hipMemcpyAsync(start, d_se, (size_t)B * 4, kind, st));
+    HIPCHK(e, hipMemcpyAsync(end, d_se + B, (size_t)B * 4, kind, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    return TTS_HIP_OK;
+}

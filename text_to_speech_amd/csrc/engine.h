@@ -157,6 +157,17 @@ struct MelStftDev {
     DevBuf frames, mag, io_in, io_out;
 };
 
+// Waveform clean-up (audio_proc.hip): DFT bases built on first use, no weights
+struct AudioProcDev {
+    float* fwd_Bt = nullptr;            // [2080][2048] windowed cos / -sin rows
+    float* inv_Bt = nullptr;            // [2048][2080] irfft terms x synthesis window
+    double* win2 = nullptr;             // [2048] hann^2
+    std::vector<void*> allocs;
+    DevBuf ws, io, trim_win;            // workspace, host staging, trim window (+ its reversal) for window length trim_wl
+    int trim_wl = -1;
+    std::vector<int> info_h;            // per-row facts staged to the device
+};
+
 struct TimedLaunch {
     hipEvent_t a, b;
     int kind;
@@ -171,6 +182,7 @@ struct tts_hip_engine {
     WaveGlowDev wg;
     Tacotron2Dev taco;
     MelStftDev stft;
+    AudioProcDev aproc;
     // timing hooks
     bool timing = false;
     std::vector<TimedLaunch> timed;
@@ -221,6 +233,7 @@ void tacotron2_free(tts_hip_engine* e);
 int melstft_finalize(tts_hip_engine* e);
 int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_mel);
 void melstft_free(tts_hip_engine* e);
+void audioproc_free(tts_hip_engine* e);
 
 // shared helpers
 // n floats of device-side samples into `out` on `st` (engine.hip: Philox4x32-10; kind = TTS_HIP_RANDOM_*)

@@ -211,6 +211,7 @@ int tts_hip_destroy(tts_hip_engine* e) {
     waveglow_free(e);
     tacotron2_free(e);
     melstft_free(e);
+    audioproc_free(e);
     (void)hipStreamDestroy(e->stream);
     delete e;
     return TTS_HIP_OK;

@@ -508,6 +508,133 @@ class HipEngine:
                                                out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'mel_stft')
         return out
 
+    # ------------------------------------------------------------------ waveform clean-up (csrc/audio_proc.hip)
+    _TRIM_MODES = {'start_end': 0, 'start': 1, 'end': 2}
+
+    @staticmethod
+    def _audio_rows(audio, lengths, what):
+        """(B, N, int32 lengths or None) of a [N] / [B, N] input; every length in [1, N].  Raises before any GPU call."""
+        if len(audio.shape) not in (1, 2):
+            raise ValueError(f'{what}: audio must be [N] or [B, N], got shape {tuple(audio.shape)}')
+        B, N = (1, int(audio.shape[0])) if len(audio.shape) == 1 else (int(audio.shape[0]), int(audio.shape[1]))
+        if B < 1 or N < 1:
+            raise ValueError(f'{what}: empty audio {tuple(audio.shape)}')
+        if lengths is None:
+            return B, N, None
+        if hasattr(lengths, 'detach'):
+            lengths = lengths.detach().cpu().numpy()
+        lens = np.ascontiguousarray(np.atleast_1d(np.asarray(lengths)).astype(np.int64))
+        if lens.shape != (B,):
+            raise ValueError(f'{what}: lengths must have shape ({B},), got {lens.shape}')
+        if lens.min() < 1 or lens.max() > N:
+            raise ValueError(f'{what}: lengths must lie in [1, {N}]')
+        return B, N, lens.astype(np.int32)
+
+    @staticmethod
+    def _samples(value, rate, what):
+        """seconds (float, times `rate`) or samples (int) -> samples, as the reference does (int(value * rate))."""
+        if isinstance(value, (float, np.floating)):
+            if rate is None:
+                raise ValueError(f'{what} in seconds needs `rate`')
+            return int(value * rate)
+        return int(value)
+
+    def reduce_noise(self, audio, rate=None, lengths=None, noise=None, noise_length=0.2, renormalize=False, stream=None):
+        """Spectral-gating noise reduction (utils/audio/audio_processing.py:65-83 -> noisereducev1.py:175-290, v1 defaults).
+        audio [N] or [B, N]; row b holds lengths[b] samples (default N) and its result is what a one-row call on
+        audio[b, :lengths[b]] gives, zero beyond.  noise=None: each row's first `noise_length` (seconds with `rate`, or
+        samples) samples are the noise clip; else noise [noise_len] / [B, noise_len].  renormalize: then
+        normalize_audio(max_val=1.) per row, as load_audio does after reduce_noise.  numpy in -> numpy out; a CUDA tensor
+        in -> a CUDA tensor out; `stream` (torch.cuda.Stream, device tensors only): enqueue there and return without waiting
+        (the clean-up calls share one workspace per engine: the next reduce_noise / trim_silence must be ordered after it)."""
+        B, N, lens = self._audio_rows(audio, lengths, 'reduce_noise')
+        if noise is not None:
+            if len(noise.shape) not in (1, 2) or (len(noise.shape) == 2 and int(noise.shape[0]) != B) or \
+                    (len(noise.shape) == 1 and B != 1):
+                raise ValueError(f'reduce_noise: noise must be [noise_len] (one row) or [{B}, noise_len], got {tuple(noise.shape)}')
+            noise_len = int(noise.shape[-1])
+        else:
+            noise_len = self._samples(noise_length, rate, 'reduce_noise: noise_length')
+        if noise_len < 1:
+            raise ValueError(f'reduce_noise: the noise clip must hold at least one sample (got {noise_len})')
+        lens_p = lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None
+        one_row = len(audio.shape) == 1
+        if _is_torch_cuda(audio):
+            torch = self._torch()
+            if noise is not None and not _is_torch_cuda(noise):
+                noise = torch.as_tensor(np.asarray(noise, np.float32), device=audio.device)
+            self._check_device(audio, noise)
+
+            def prepared():
+                a_ = audio.to(torch.float32).reshape(B, N).contiguous()
+                n_ = noise.to(torch.float32).reshape(B, noise_len).contiguous() if noise is not None else None
+                return a_, n_, torch.empty((B, N), dtype=torch.float32, device=a_.device)
+
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+            if stream is not None:
+                with self._enter_stream(stream):
+                    a, n, out = prepared()
+                self._used_on(stream, audio, a, n, out)
+                self._check(self._lib.tts_hip_reduce_noise_async(self._h, ptr(a), B, N, lens_p, ptr(n), noise_len,
+                                                                 int(bool(renormalize)), ptr(out),
+                                                                 self._order_after_torch(stream)), 'reduce_noise_async')
+            else:
+                a, n, out = prepared()
+                self._order_after_torch()
+                self._check(self._lib.tts_hip_reduce_noise(self._h, ptr(a), B, N, lens_p, ptr(n), noise_len,
+                                                           int(bool(renormalize)), ptr(out), MEM_DEVICE), 'reduce_noise')
+            return out[0] if one_row else out
+        if stream is not None:
+            raise ValueError('stream= needs device tensors')
+        a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
+        n = None
+        if noise is not None:
+            n = np.ascontiguousarray(np.asarray(noise.detach().cpu() if hasattr(noise, 'detach') else noise,
+                                                dtype=np.float32).reshape(B, noise_len))
+        out = np.empty((B, N), dtype=np.float32)
+        self._check(self._lib.tts_hip_reduce_noise(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens_p,
+                                                   n.ctypes.data_as(ctypes.c_void_p) if n is not None else None, noise_len,
+                                                   int(bool(renormalize)), out.ctypes.data_as(ctypes.c_void_p), MEM_HOST),
+                    'reduce_noise')
+        return out[0] if one_row else out
+
+    def trim_silence(self, audio, rate=None, lengths=None, threshold=0.1, window_length=0.2, add_start=0, add_end=1.5,
+                     mode='start_end'):
+        """Window-method silence trimming (utils/audio/audio_processing.py:274-370: power 2, triangular window, adaptive
+        thresholds, max_trim_factor 5).  audio [N] -> (start, end) ints; [B, N] -> (start, end) int32 arrays [B]; the
+        trimmed row b is audio[b, start[b]:end[b]] (of its first lengths[b] samples).  `window_length` in seconds (float,
+        with `rate`) or samples (int); `add_start` / `add_end` are margins in window lengths."""
+        B, N, lens = self._audio_rows(audio, lengths, 'trim_silence')
+        if mode not in self._TRIM_MODES:
+            raise ValueError(f'trim_silence: invalid mode {mode!r} (start, end or start_end)')
+        wl = self._samples(window_length, rate, 'trim_silence: window_length')
+        if wl < 2:
+            raise ValueError(f'trim_silence: window_length must be >= 2 samples (got {wl})')
+        if not (np.isfinite(threshold) and np.isfinite(add_start) and np.isfinite(add_end)) or add_start < 0 or add_end < 0:
+            raise ValueError('trim_silence: threshold and margins must be finite, margins >= 0')
+        lens_p = lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None
+        start, end = np.empty(B, np.int32), np.empty(B, np.int32)
+        args = (wl, float(threshold), float(add_start), float(add_end), self._TRIM_MODES[mode])
+        if _is_torch_cuda(audio):
+            torch = self._torch()
+            self._check_device(audio)
+            a = audio.to(torch.float32).reshape(B, N).contiguous()
+            st = torch.empty((2, B), dtype=torch.int32, device=a.device)
+            self._order_after_torch()
+            self._check(self._lib.tts_hip_trim_silence(self._h, ctypes.c_void_p(a.data_ptr()), B, N, lens_p, *args,
+                                                       ctypes.c_void_p(st.data_ptr()), ctypes.c_void_p(st[1].data_ptr()),
+                                                       MEM_DEVICE), 'trim_silence')
+            st = st.cpu().numpy()
+            start[:], end[:] = st[0], st[1]
+        else:
+            a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
+            self._check(self._lib.tts_hip_trim_silence(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens_p, *args,
+                                                       start.ctypes.data_as(ctypes.c_void_p),
+                                                       end.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'trim_silence')
+        if len(audio.shape) == 1:
+            return int(start[0]), int(end[0])
+        return start, end
+
     # ------------------------------------------------------------------ measurement hooks
     def kernel_timing(self, enable: bool) -> None:
         self._check(self._lib.tts_hip_kernel_timing(self._h, 1 if enable else 0), 'kernel_timing')

@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 PAD_MEL_VALUE = -11.0
+RATE = 22050                        # WaveGlow's output rate (the reference's Tacotron2.rate)
 
 
 class TTSPipeline:
@@ -30,10 +31,16 @@ class TTSPipeline:
         self._offset = 0                                # running block offset in the engine's device-side Philox stream
 
     def synthesize_tokens(self, tokens, speaker=None, max_length=10.0, deterministic=False, prenet_masks=None, z=None,
-                          sigma=1.0, early_stopping=True, round_frames_to=8, on_device=False):
+                          sigma=1.0, early_stopping=True, round_frames_to=8, on_device=False, reduce_noise=False,
+                          trim_silence=False):
         """tokens int32 [B, Tin] (0 = pad) -> (list of B float32 waveforms, lengths [B] in frames, steps run).
         `on_device`: nothing is copied to the host -- returns (audio [B, S] float32 device tensor, zero beyond each row's
-        samples, sample counts [B] int64 device tensor, steps run)."""
+        samples, sample counts [B] int64 device tensor, steps run).
+        `reduce_noise` / `trim_silence`: the reference's waveform clean-up (audio_processing.reduce_noise, trim_silence with
+        method 'window') on the device, each row with its own sample count as its length, at RATE Hz; trimming changes the
+        lengths, so it needs host output (on_device=False)."""
+        if on_device and trim_silence:
+            raise ValueError('trim_silence=True needs on_device=False (trimmed rows have new lengths)')
         import torch
         eng = self.engine
         dev = torch.device('cuda', eng.device)
@@ -74,12 +81,21 @@ class TTSPipeline:
             if z is not None:
                 z = as_dev(z, torch.float32)[:, :T * 32]
             audio = eng.waveglow_infer(mel.contiguous(), z=z, sigma=sigma, precision=self.vocoder_precision)
+        if reduce_noise or trim_silence:
+            n_samp = np.maximum(lengths.cpu().numpy().astype(np.int64) * 256, 1)      # a row needs >= 1 sample
+            if reduce_noise:
+                audio = eng.reduce_noise(audio, RATE, lengths=n_samp)
+            if trim_silence:
+                start, end = eng.trim_silence(audio, RATE, lengths=n_samp)
         if on_device:
             counts = lengths.to(torch.int64) * 256
             keep = torch.arange(T * 256, device=dev)[None, :] < counts[:, None]
             return torch.where(keep, audio, torch.zeros_like(audio)), counts, steps
         audio_h = audio.cpu().numpy()
         n = lengths.cpu().numpy()
+        if trim_silence:
+            return [audio_h[b, int(start[b]):int(end[b])].copy() if n[b] > 0 else np.zeros((0,), np.float32)
+                    for b in range(B)], n, steps
         return [audio_h[b, :int(n[b]) * 256].copy() for b in range(B)], n, steps
 
     def shard_fn(self, **kwargs):

@@ -47,7 +47,7 @@ class Tacotron2:
 
     def infer(self, text, *, embeddings=None, callbacks=None, predicted=None, overwrite=False, return_output=True,
               max_length=10., max_text_length=-1, max_trial=5, min_fpt_ratio=2., max_fpt_ratio=10., vocoder=None,
-              silence_time=0.15, vocoder_config={}, **kwargs):
+              silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, **kwargs):
         if isinstance(text, dict):                                   # get_text_from_paragraph (tacotron2.py:369-370)
             text = text['text' if 'text' in text else 'content']
         callbacks = _as_callbacks(callbacks)
@@ -59,7 +59,7 @@ class Tacotron2:
                                 max_trial=max_trial, min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, **kwargs)
         return self._vocode_and_finish(part, callbacks=callbacks, predicted=predicted, return_output=return_output,
                                        vocoder=vocoder, silence_time=silence_time, vocoder_config=vocoder_config,
-                                       **kwargs)
+                                       reduce_noise=reduce_noise, trim_silence=trim_silence, **kwargs)
 
     # `infer` = `_synthesize` (text -> mels; the autoregressive, latency-bound half) followed by `_vocode_and_finish`
     # (mels -> audio, callbacks; the throughput-bound half).  They are separate so that `stream(overlap=True)` can run
@@ -102,8 +102,24 @@ class Tacotron2:
         return {'text': text, 'cleaned': cleaned, 'splitted': splitted, 'mel': mels, 'attention': attention_weights,
                 'synth_time': time.time() - t0}
 
+    def _clean_waveform(self, audio, vocoder, reduce_noise, trim_silence):
+        """The reference's waveform clean-up (audio_processing.reduce_noise, trim_silence(method='window')) at self.rate, on
+        the engine of the vocoder that produced `audio` (the synthesizer's only when the vocoder has none).  With
+        `predict(..., overlap=True)` the synthesizer's handle is busy in the producer thread, and calls on one handle must
+        be serialised, so the clean-up has to stay on the vocoder's handle, in the thread that vocodes."""
+        eng = getattr(getattr(vocoder, 'compiled_infer', None), 'engine', None) or getattr(self.compiled_infer, 'engine', None)
+        if eng is None or not hasattr(eng, 'reduce_noise'):
+            raise ValueError('reduce_noise / trim_silence need a HIP engine behind the model')
+        audio = np.asarray(audio, np.float32)
+        if reduce_noise:
+            audio = eng.reduce_noise(audio, self.rate)
+        if trim_silence:
+            start, end = eng.trim_silence(audio, self.rate)
+            audio = audio[start:end]
+        return audio
+
     def _vocode_and_finish(self, part, *, callbacks=None, predicted=None, return_output=True, vocoder=None,
-                           silence_time=0.15, vocoder_config={}, **kwargs):
+                           silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, **kwargs):
         text, synth_time = part['text'], part.get('synth_time', 0.)
         audio_infos = {}
         if vocoder is not None:
@@ -118,6 +134,8 @@ class Tacotron2:
             vocoder_time = time.time() - t1
             if len(audios) > 0:
                 audios = audios[0] if len(audios) == 1 else np.concatenate(audios, axis=0)
+                if (reduce_noise or trim_silence) and len(audios) > 0:
+                    audios = self._clean_waveform(audios, vocoder, reduce_noise, trim_silence)
                 audio_infos = {'audio': audios, 'rate': self.rate, 'time': len(audios) / self.rate}
                 logger.info('%.2f s generated in %.3f s (%.3f synthesizer + %.3f vocoder)', audio_infos['time'],
                             synth_time + vocoder_time, synth_time, vocoder_time)
@@ -234,7 +252,8 @@ class Tacotron2:
                     if predicted and not overwrite and text in predicted:
                         q.put((inp, text, None, None))
                         continue
-                    extra = {k: v for k, v in voc_kw.items() if k not in ('vocoder', 'silence_time', 'vocoder_config')}
+                    extra = {k: v for k, v in voc_kw.items() if k not in ('vocoder', 'silence_time', 'vocoder_config',
+                                                                             'reduce_noise', 'trim_silence')}
                     q.put((inp, text, self._synthesize(text, **synth_kw, **extra), None))
             except BaseException as exc:                              # noqa: BLE001 -- re-raised in the consumer
                 q.put((None, None, None, exc))
