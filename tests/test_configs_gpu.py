@@ -18,7 +18,7 @@ from stop_script import script_stop_tokens
 pytestmark = pytest.mark.gpu
 
 MEL_TOL, WAVE_RMS_TOL = 1e-3, 1e-4                  # fp32 (north_star)
-MEL_TOL_F16, WAVE_RMS_TOL_F16 = 5e-3, 1e-3          # fp16 modes: measured 4e-4 / 2e-4, see the module docstring
+MEL_TOL_F16, WAVE_RMS_TOL_F16 = 1e-3, 1e-3          # fp16 modes: measured 3.3e-4 mel / 2e-4, see the module docstring
 CONFIG3_TOKENS = [50, 70, 90, 110, 130, 150, 170, 200]
 
 
