@@ -190,6 +190,20 @@ int tts_hip_last_waveglow_form(const tts_hip_engine* e);
  * `end` convolutions attenuate an error, to `acts` [B, T*32, 512] in the reference's position order.  B*T <= 31744.       */
 int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int flow,
                                 int layer, float* acts, int mem);
+/* Test hook, any precision (used by tests/ only; no effect on later calls): runs tts_hip_waveglow_infer in `precision`
+ * (0 f32 in the form tts_hip_set_waveglow_form selects, 1 f16, 2 f16x3) up to a stop point of flow `flow` (11 .. 0):
+ *   what 0: the gated activations of WN layer `layer` (0 .. 7), as tts_hip_waveglow_probe_acts, to `out` [B, T*32, 512] fp32
+ *           (f16: the fp16 activations widened; f16x3: hi + lo summed in fp32);
+ *   what 1: the flow state right after the flow (affine coupling, inverse 1x1 conv, and the early output that flows 8 and 4
+ *           prepend), to `out` [B, T*32, n] with n = 4, 6 (flow 8), 6, 8 (flow 4), 8 for flows 11-9, 8, 7-5, 4, 3-0 --
+ *           the channel order of the reference's audio after that flow (waveglow_arch.py:284-304); `layer` is not used.
+ * B*T <= 31744.                                                                                                            */
+int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int precision,
+                           int flow, int what, int layer, float* out, int mem);
+/* WN GEMM tile family the last tts_hip_waveglow_infer* (or probe) call on this handle used for its in-layer (direct form) and
+ * residual GEMMs: 3 64-row tiles (64 x 128), 2 128 x 64 tiles, 1 128-row tiles, 0 256-row tiles (fp16: 256 x 256), -1 before
+ * the first call.  Split fp16 (f16x3) has two families only: 3 and 0.                                                    */
+int tts_hip_last_waveglow_tiles(const tts_hip_engine* e);
 
 /* ---- TacotronSTFT.mel_spectrogram  (utils/audio/stft.py:242-274,306-314)
  * audio [B, N] (N >= 1024) -> mel [B, N/256 + 1, 80]                                                                */

@@ -1,0 +1,231 @@
+"""CPU half of the WaveGlow-variant matrix (tests/waveglow_cases.py): the case table reaches every WN GEMM instantiation and
+every Winograd kernel kind that `waveglow_run` can launch, `pick_variant` restates the dispatch rules at their edges, and
+every bound of test_waveglow_variants_gpu.py could fail -- oracle-only controls showing that a tap leaking across an
+utterance end, a conditioning frame off by one, an ignored fp16 flag and a small error in the `end` conv would be caught."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import waveglow_cases as wc
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'text_to_speech_amd', 'csrc')
+
+
+def _src(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def _reached():
+    """{kernel name} over every case x (precision, form) of the table."""
+    got = set()
+    for c in wc.CASES:
+        for p, f in wc.runs(c):
+            got |= wc.pick_variant(c.B, c.T, p, f).kernels
+    return got
+
+
+# ---- coverage ----------------------------------------------------------------------------------------------------------
+def test_cases_reach_every_wn_gemm_wrapper_and_instantiation():
+    """Every `gemm_wn_*` wrapper of gemm_f32.h (both values of a bool argument that picks the instantiation: split fp16's
+    `small`, fp16's `t128`) is reached by some case, and every call site in waveglow.hip / wn_wino.hip names one of them:
+    a new wrapper or call site fails here until the table covers it."""
+    wrappers = re.findall(r'inline hipError_t (gemm_wn_\w+)\(const GemmArgs& \w+, (?:bool (\w+), )?(?:int \w+, )?hipStream_t',
+                          _src('gemm_f32.h'))
+    assert len(wrappers) >= 20, wrappers
+    expected = set()
+    for name, flag in wrappers:
+        expected |= {f'{name}({flag}=True)', f'{name}({flag}=False)'} if flag else {name}
+    got = {k.split('/')[0] for k in _reached()}
+    assert expected <= got, sorted(expected - got)
+    names = {n for n, _ in wrappers}
+    for src in ('waveglow.hip', 'wn_wino.hip'):
+        called = set(re.findall(r'\b(gemm_wn_\w+)\(', _src(src)))
+        assert called and called <= names, sorted(called - names)
+        assert called <= {k.split('(')[0] for k in got}, sorted(called - {k.split('(')[0] for k in got})
+
+
+def test_cases_reach_every_winograd_kernel_kind_and_end_fold_instantiation():
+    got = _reached()
+    wino = _src('wn_wino.hip')
+    # the three in-layer kernels of the Winograd forms and the combine pass of form 2, launched in waveglow_wino_layer
+    assert 'launch_wino_fused2(b, st)' in wino and 'launch_wino_fused<2, 2, 3, 2>(a, st)' in wino
+    assert 'hipLaunchKernelGGL(wino4_combine_kernel' in wino
+    for kernel in ('fused2', 'fused_prepass'):
+        assert {f'{kernel}/{g}' for g in wc.WINO_KINDS} <= got, kernel
+    assert {'gemm_wn_wino/phases', 'gemm_wn_wino_128/phases', 'gemm_wn_wino_128/mixed', 'gemm_wn_wino_128/frames',
+            'combine'} <= got
+    folds = set(re.findall(r'\((wn_end_fold_kernel<\w+, \w+>)\)', _src('waveglow.hip')))
+    assert len(folds) == 3 and folds <= got, sorted(folds - got)
+
+
+def test_cases_reach_every_tile_family_in_every_form_and_the_edges():
+    seen = {(p, f, v.tiles, v.wino) for c in wc.CASES for p, f in wc.runs(c) for v in [wc.pick_variant(c.B, c.T, p, f)]}
+    for fam in ('64-row', '128x64', '128-row', '256-row'):
+        assert ('f32', 'winograd', fam, False) in seen or fam != '128x64' and ('f32', 'direct', fam, False) in seen, fam
+        assert ('f16', 'winograd', fam, False) in seen, fam
+    for fam in ('64-row', '128-row', '256-row'):
+        for form in ('winograd', 'winograd-prepass'):
+            assert ('f32', form, fam, True) in seen, (form, fam)
+    assert ('f32', 'winograd-3pass', '256-row', True) in seen and ('f32', 'winograd-3pass', '128-row', True) in seen
+    assert ('f32', 'winograd-3pass', '64-row', False) in seen            # form 2 keeps 64-row tiles: the direct form
+    assert {('f16x3', 'winograd', fam, False) for fam in ('64-row', '256-row')} <= seen
+    bts = {c.BT for c in wc.CASES}
+    assert {143, 144, 192, 193, 255, 256, 383, 384 + 1, 512, 513} <= bts
+    assert {c.T for c in wc.CASES if c.B > 1} >= {1, 2, 3}
+    assert any(c.T % 2 and c.T % 16 for c in wc.CASES if c.BT >= wc.WINO_MIN_FRAMES)
+    pads = {(wc.pick_variant(c.B, c.T, p, f).PR - c.BT, wc.pick_variant(c.B, c.T, p, f).tiles)
+            for c in wc.CASES for p, f in wc.runs(c)}
+    assert {(1, '256-row'), (1, '128-row'), (63, '64-row'), (127, '128-row')} <= pads
+    assert set(wc.LATER_FLOW_CASES) <= set(wc.CASE_BY_NAME) and set(wc.STATE_CASES) <= set(wc.CASE_BY_NAME)
+
+
+# ---- dispatch edges ----------------------------------------------------------------------------------------------------
+def _v(BT, precision='f32', form='winograd', T=None):
+    T = BT if T is None else T
+    return wc.pick_variant(BT // T, T, precision, form)
+
+
+def test_pick_variant_restates_the_dispatch_rules_at_their_edges():
+    # the Winograd start (fp32 only, forms >= 1)
+    assert not _v(143).wino and _v(144).wino and not _v(144, form='direct').wino
+    assert not _v(144, 'f16').wino and not _v(1024, 'f16x3').wino
+    # fp32 64-row tiles: pr64 < pr_big and B*T <= 512
+    assert _v(64).tiles == '64-row' and _v(65).tiles == '128x64' and _v(128).tiles == '128x64'
+    assert _v(129).tiles == '64-row' and _v(192).tiles == '64-row' and _v(193).tiles == '256-row'
+    assert _v(448).tiles == '64-row' and _v(449).tiles == '256-row'
+    assert _v(512).tiles == '256-row' and _v(513).tiles == '128-row' and _v(513).PR == 640     # 576 < 640 but above the limit
+    # 128-row tiles: pr128 * 1.05 < pr256
+    assert _v(383).tiles == '128-row' and _v(256).tiles == '256-row' and _v(1024, T=128).tiles == '256-row'
+    assert _v(2432, T=128).tiles == '128-row' and _v(2560 + 128, T=128).tiles == '256-row'    # 2688 * 1.05 > 2816
+    # 128 x 64 tiles: (M / 128) * 8 < 768, i.e. fewer than 384 rows per phase
+    assert _v(100).tiles == '128x64' and _v(100).PR == 128
+    assert _v(383, form='direct').tiles == '128-row' and _v(383).PR * 32 // 128 * 8 == 768
+    # fp16: the 64-row tiles pay from -25 % rows (pr64 * 4 <= pr_big * 3)
+    assert _v(64, 'f16').tiles == '64-row' and _v(65, 'f16').tiles == '128x64'
+    assert _v(192, 'f16').tiles == '64-row' and _v(193, 'f16').tiles == '256-row'              # 768 <= 768, 1024 > 768
+    assert _v(257, 'f16').tiles == '128-row' and _v(257, 'f16').PR == 384                      # 1280 > 1152
+    assert 'gemm_wn_in_h(t128=True)' in _v(257, 'f16').kernels
+    assert 'gemm_wn_in_h(t128=False)' in _v(256, 'f16').kernels
+    # split fp16: 64 x 128 while pr64 * 1.25 < pr256, 256 x 256 otherwise; no row-64 limit, no 128-row family
+    assert _v(192, 'f16x3').tiles == '64-row' and _v(193, 'f16x3').tiles == '256-row'
+    assert _v(384, 'f16x3').tiles == '64-row' and _v(385, 'f16x3').tiles == '256-row'
+    assert _v(513, 'f16x3').tiles == '64-row' and _v(100, 'f16x3').tiles == '64-row'
+    assert 'gemm_wn_in0_x3(small=False)' in _v(256, 'f16x3').kernels
+    # form 2: PR % 256 picks the phase-group GEMM; the row-64 rescue (pr128 * 1120 * 1.35 < pr64 * 1856) or the direct form
+    assert 'gemm_wn_wino/phases' in _v(256, form='winograd-3pass').kernels
+    assert 'gemm_wn_wino_128/phases' in _v(513, form='winograd-3pass').kernels
+    r = _v(300, form='winograd-3pass', T=75)
+    assert r.wino and r.tiles == '128-row' and r.PR == 384 and 'gemm_wn_wino_128/phases' in r.kernels
+    assert _v(300, form='winograd', T=75).tiles == '64-row'                                   # no rescue outside form 2
+    d = _v(144, form='winograd-3pass', T=9)
+    assert not d.wino and d.tiles == '64-row' and 'gemm_wn_in_r64' in d.kernels               # 256 / 192 > 1.2275
+    # group rows: frame groups 4 ceil(T / 16) and mixed groups ceil(T / 2) per utterance, padded to 64 (form 2: 128)
+    assert wc.group_rows(16, 9, 1) == (64, 128) and wc.group_rows(150, 1, 1) == (640, 192)
+    assert wc.group_rows(4, 75, 2) == (128, 256) and wc.group_rows(3, 171, 1) == (192, 320)
+
+
+# ---- oracle-only controls ----------------------------------------------------------------------------------------------
+CTRL = wc.CASE_BY_NAME['t3_b4']
+
+
+def _ctrl_inputs(case=CTRL):
+    mel, z = wc.inputs(case)
+    return mel, z, wc.spect_of(mel, wc.weights64())
+
+
+@pytest.fixture(scope='module')
+def ctrl_ref():
+    return wc.flow11_acts(CTRL)
+
+
+def test_control_a_tap_leaking_across_an_utterance_end_breaks_the_edge_bound(ctrl_ref, monkeypatch):
+    """One position read across the start of every utterance (the previous utterance's last position instead of the zero
+    padding), in one layer at a time: the edge-window error of that layer is at least 10x the bound of every precision
+    but fp16, and still above fp16's (max abs error too)."""
+    from oracle import waveglow_ref
+    mel, z, spect = _ctrl_inputs()
+    conv = waveglow_ref.conv1d_dilated_same
+    L = CTRL.T * wc.NPH
+    for leak in range(wc.N_LAYERS):
+        d = 1 << leak
+        if d > L:                           # no tap of a d > L layer reaches the position before an utterance
+            continue
+
+        def leaky(x, kernel, bias, dilation, _d=d):
+            out = conv(x, kernel, bias, dilation)
+            if dilation == _d:              # output position d - 1 reads x[-1] through its first tap
+                prev = np.roll(x[:, -1], 1, axis=0)
+                out[:, _d - 1] += prev @ kernel[0]
+            return out
+
+        monkeypatch.setattr(waveglow_ref, 'conv1d_dilated_same', leaky)
+        acts = wc.flow_acts(z[:, :, :2], spect, 11, stop_after=leak)
+        monkeypatch.setattr(waveglow_ref, 'conv1d_dilated_same', conv)
+        e = wc.act_errors(acts[leak], ctrl_ref[leak], CTRL.T, d)
+        print(f'leak at layer {leak}: edge {e["edge"]:.2e} rel {e["rel"]:.2e} abs {e["abs"]:.2e}')
+        for p in ('f32', 'f16x3'):
+            assert e['edge'] >= 10 * wc.ACTS_EDGE_REL[p] and e['abs'] >= 10 * wc.ACTS_ABS[p], (leak, p)
+        assert e['edge'] > wc.ACTS_EDGE_REL['f16'] and e['abs'] > wc.ACTS_ABS['f16'], leak
+
+
+def test_control_a_conditioning_frame_off_by_one_breaks_every_bound(ctrl_ref):
+    """The mel frames shifted by one inside every utterance (frame t conditioned on t - 1, zeros before the start)."""
+    mel, z, _ = _ctrl_inputs()
+    shifted = np.zeros_like(mel)
+    shifted[:, 1:] = mel[:, :-1]
+    acts = wc.flow_acts(z[:, :, :2], wc.spect_of(shifted, wc.weights64()), 11)
+    for i in range(wc.N_LAYERS):
+        e = wc.act_errors(acts[i], ctrl_ref[i], CTRL.T, 1 << i)
+        print(f'mel off by one, layer {i}: rel {e["rel"]:.2e} edge {e["edge"]:.2e} abs {e["abs"]:.2e}')
+        for k, bound in (('rel', wc.ACTS_REL), ('edge', wc.ACTS_EDGE_REL), ('abs', wc.ACTS_ABS)):
+            assert e[k] >= 10 * max(bound['f32'], bound['f16x3']) and e[k] > bound['f16'], (i, k)
+
+
+def test_control_fp16_operands_are_far_from_fp32(ctrl_ref, monkeypatch):
+    """Every GEMM operand rounded to fp16 (residual stream, first-layer input, weights, mel): the activations move at least
+    3x F16_FLOOR from the fp32 oracle, and the fp32 bound sits 10x below that floor -- so an fp16 call that ignored its
+    flag (fp32 arithmetic, within the fp32 bound) fails the floor of test_waveglow_variants_gpu.py."""
+    from oracle import waveglow_ref
+    assert 10 * max(wc.ACTS_REL['f32'], wc.ACTS_REL['f16x3']) <= wc.F16_FLOOR < wc.ACTS_REL['f16']
+    r16 = lambda a: np.asarray(a).astype(np.float16).astype(np.float64)
+    mel, z, _ = _ctrl_inputs()
+    w16 = {k: (r16(v) if '/kernel' in k else v) for k, v in wc.weights64().items()}
+    conv = waveglow_ref.conv1d_dilated_same
+    monkeypatch.setattr(waveglow_ref, 'conv1d_dilated_same', lambda x, k, b, d: conv(r16(x), k, b, d))
+    acts = wc.flow_acts(r16(z[:, :, :2]), r16(wc.spect_of(r16(mel), wc.weights64())), 11, w=w16)
+    for i in range(wc.N_LAYERS):
+        e = wc.act_errors(acts[i], ctrl_ref[i], CTRL.T, 1 << i)
+        print(f'fp16 operands, layer {i}: rel {e["rel"]:.2e} edge {e["edge"]:.2e} abs {e["abs"]:.2e}')
+        assert e['rel'] >= 3 * wc.F16_FLOOR, i
+
+
+def test_control_an_end_conv_error_of_1e4_moves_the_post_flow_state_beyond_its_bound():
+    """Every `end` conv output scaled by 1 + 1e-4 (weights with end_scale 0.2): the flow state after flows 11, 8, 4 and 0
+    moves beyond the fp32 / f16x3 bounds."""
+    from oracle import waveglow_ref
+    case = wc.CASE_BY_NAME[wc.STATE_CASES[0]]
+    ref = wc.states(case)
+    w = dict(wc.weights(wc.STATE_END_SCALE))
+    for k in range(12):
+        for part in ('kernel', 'bias'):
+            name = f'waveglow/block-{k}/end_conv/{part}'
+            w[name] = np.asarray(w[name], np.float64) * (1 + 1e-4)
+    mel, z = wc.inputs(case)
+    _, inter = waveglow_ref.infer(mel.astype(np.float64), w, wc.config(), z=z.astype(np.float64), sigma=1.0,
+                                  dtype=np.float64, return_intermediates=True)
+    for k in (11, 8, 4, 0):
+        e = wc.state_errors(inter[f'audio_after_flow_{k}'], ref[k])
+        print(f'end conv x (1 + 1e-4): state after flow {k}: rel {e["rel"]:.2e} max_rel {e["max_rel"]:.2e}')
+        for p in ('f32', 'f16x3'):
+            assert e['rel'] > wc.STATE_REL[p] and e['max_rel'] > wc.STATE_MAX_REL[p], (k, p)
+
+
+def test_edge_windows_and_state_widths():
+    m = wc.edge_mask(3, 64)
+    assert m.sum() == 96 and wc.edge_mask(3, 1).sum() == 2 and wc.edge_mask(3, 4)[[0, 3, 4, 91, 92, 95]].tolist() == \
+        [True, True, False, False, True, True]
+    ref = wc.states(wc.CASE_BY_NAME[wc.STATE_CASES[0]])
+    assert {k: v.shape[2] for k, v in ref.items()} == {11: 4, 8: 6, 4: 8, 0: 8}

@@ -47,6 +47,9 @@ SIGNATURES = {
     'tts_hip_set_waveglow_form': (c_int, [c_void_p, c_int]),
     'tts_hip_last_waveglow_form': (c_int, [c_void_p]),
     'tts_hip_waveglow_probe_acts': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_void_p, c_int]),
+    'tts_hip_waveglow_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_void_p,
+                                       c_int]),
+    'tts_hip_last_waveglow_tiles': (c_int, [c_void_p]),
     'tts_hip_mel_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]),
     'tts_hip_waveglow_infer_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p]),
     'tts_hip_mel_stft_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -69,8 +69,10 @@ struct WaveGlowDev {
     bool f16_ready = false, x3_ready = false;
     DevBuf x16, acts16, a0p16, mel16;        // fp16 path: shadow of x, activations, first-layer operand, mel
     int form_mode = 1, last_form = -1;       // tts_hip_set_waveglow_form / tts_hip_last_waveglow_form
-    int probe_flow = -1, probe_layer = -1;   // tts_hip_waveglow_probe_acts (test hook): stop after this layer and copy
-    float* probe_out = nullptr;              //   its gated activations to this device buffer [B][T * 32][512]
+    int last_tiles = -1;                     // tts_hip_last_waveglow_tiles: WN GEMM tile family of the last call
+    int probe_flow = -1, probe_layer = -1;   // tts_hip_waveglow_probe (test hook): stop after this layer (what 0) or flow
+    int probe_what = 0;                      //   (what 1) and copy its gated activations [B][T * 32][512] or the flow
+    float* probe_out = nullptr;              //   state [B][T * 32][n] to this device buffer
     bool wino_ready = false;                 // Winograd form of the fp32 in-layer GEMM (wn_wino.hip)
     bool wino_legacy_ready = false;          //   ... and the three-pass form's extra weight copies
     DevBuf wino_U, wino_P, wino_mel;         // mel planes; forms 2 / 3 only: transformed inputs [6][M/4][512], products [6][M/4][1024]

@@ -353,16 +353,20 @@ int tts_hip_waveglow_infer_f16x3(tts_hip_engine* e, const float* mel, int B, int
     return waveglow_infer_impl(e, mel, B, T, z, sigma, audio, mem, 2);
 }
 
-// Test hook: the gated activations of one WN layer (before the res/skip and `end` convolutions), natural position order.
-int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int flow,
-                                int layer, float* acts, int mem) {
+// Test hook: the gated activations of one WN layer (before the res/skip and `end` convolutions) or the flow state after one
+// flow, natural position order, in any precision.
+int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int precision,
+                           int flow, int what, int layer, float* out, int mem) {
     if (!e) return TTS_HIP_EINVAL;
     if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
-    if (!mel || !acts || B <= 0 || T <= 0 || flow < 0 || flow > 11 || layer < 0 || layer > 7 || (long long)B * T > 31744)
-        return set_err(e, TTS_HIP_EINVAL, "waveglow_probe_acts: bad argument");
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "waveglow_probe_acts: bad mem kind %d", mem);
+    if (!mel || !out || B <= 0 || T <= 0 || precision < 0 || precision > 2 || flow < 0 || flow > 11 || what < 0 || what > 1 ||
+        layer < 0 || layer > 7 || (long long)B * T > 31744)
+        return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: bad argument");
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: bad mem kind %d", mem);
     HIPCHK(e, hipSetDevice(e->device));
-    const size_t n_mel = (size_t)B * T * 80, n_z = (size_t)B * T * 32 * 8, n_acts = (size_t)B * T * 32 * 512;
+    // what 1: the flow's 2 * n_half channels, preceded by the early output that flows 8 and 4 append
+    const int width = what == 0 ? 512 : e->wg.flow[flow].n_rem + (flow % 4 == 0 && flow > 0 ? 2 : 0);
+    const size_t n_mel = (size_t)B * T * 80, n_z = (size_t)B * T * 32 * 8, n_out = (size_t)B * T * 32 * width;
     const float* d_mel = mel;
     const float* d_z = z;
     struct Scratch : DevBuf {                                   // (DevBuf has no destructor: the engine's buffers live with the handle)
@@ -377,22 +381,29 @@ int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int 
             HIPCHK(e, hipMemcpyAsync(e->wg.io_z.p, z, n_z * 4, hipMemcpyHostToDevice, e->stream));
             d_z = e->wg.io_z.f();
         }
-        HIPCHK(e, tmp.ensure(n_acts * 4));
+        HIPCHK(e, tmp.ensure(n_out * 4));
     }
-    HIPCHK(e, e->wg.io_out.ensure((size_t)B * T * 256 * 4));      // the run's audio argument (not reached before the stop)
+    HIPCHK(e, e->wg.io_out.ensure((size_t)B * T * 256 * 4));      // the run's audio argument (flow 0's state)
     e->wg.probe_flow = flow;
     e->wg.probe_layer = layer;
-    e->wg.probe_out = mem == TTS_HIP_MEM_HOST ? tmp.f() : acts;
-    int rc = waveglow_run(e, d_mel, B, T, d_z, sigma, e->wg.io_out.f(), 0);
+    e->wg.probe_what = what;
+    e->wg.probe_out = mem == TTS_HIP_MEM_HOST ? tmp.f() : out;
+    int rc = waveglow_run(e, d_mel, B, T, d_z, sigma, e->wg.io_out.f(), precision);
     e->wg.probe_out = nullptr;
     e->wg.probe_flow = e->wg.probe_layer = -1;
+    e->wg.probe_what = 0;
     hipError_t herr = hipSuccess;
-    if (!rc && mem == TTS_HIP_MEM_HOST) herr = hipMemcpyAsync(acts, tmp.p, n_acts * 4, hipMemcpyDeviceToHost, e->stream);
+    if (!rc && mem == TTS_HIP_MEM_HOST) herr = hipMemcpyAsync(out, tmp.p, n_out * 4, hipMemcpyDeviceToHost, e->stream);
     const hipError_t serr = hipStreamSynchronize(e->stream);
     if (rc) return rc;
     HIPCHK(e, herr);
     HIPCHK(e, serr);
     return TTS_HIP_OK;
+}
+
+int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int flow,
+                                int layer, float* acts, int mem) {
+    return tts_hip_waveglow_probe(e, mel, B, T, z, sigma, 0, flow, 0, layer, acts, mem);
 }
 
 int tts_hip_random_fill(tts_hip_engine* e, int kind, uint64_t seed, uint64_t offset, float* out, int64_t n, void* stream) {
@@ -519,6 +530,8 @@ int tts_hip_set_waveglow_form(tts_hip_engine* e, int form) {
 }
 
 int tts_hip_last_waveglow_form(const tts_hip_engine* e) { return e ? e->wg.last_form : -1; }
+
+int tts_hip_last_waveglow_tiles(const tts_hip_engine* e) { return e ? e->wg.last_tiles : -1; }
 
 int tts_hip_probe_mfma_f32(tts_hip_engine* e, double* tflops, double* shader_clock_ghz) {
     if (!e) return TTS_HIP_EINVAL;

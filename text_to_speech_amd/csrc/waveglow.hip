@@ -144,7 +144,7 @@ __global__ void mel_window_kernel(const float* __restrict__ mel, _Float16* __res
     put_split(dst, lo, i, t - q >= 0 ? mel[(long long)(f - q) * 80 + j] : 0.f);
 }
 
-// test hook (tts_hip_waveglow_probe_acts): phase-major rows m' = p * PR + b * T + t of one layer's gated activations ->
+// test hook (tts_hip_waveglow_probe): phase-major rows m' = p * PR + b * T + t of one layer's gated activations ->
 // natural order [B][T * 32][512] (position l = 32 t + p)
 __global__ void probe_acts_kernel(const float* __restrict__ acts, float* __restrict__ out, int PR, int BT, int T) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // one float4 of one position
@@ -154,6 +154,27 @@ __global__ void probe_acts_kernel(const float* __restrict__ acts, float* __restr
     const int p = (int)(pos % NPH);
     const long long f = pos / NPH;                     // b * T + t
     *reinterpret_cast<f32x4*>(out + pos * C + c) = *reinterpret_cast<const f32x4*>(acts + ((long long)p * PR + f) * C + c);
+}
+// the same for the fp16 activation planes, widened to fp32; `lo` (split-fp16 mode, may be null): value = hi + lo
+__global__ void probe_acts16_kernel(const _Float16* __restrict__ acts, const _Float16* __restrict__ lo, float* __restrict__ out,
+                                    int PR, int BT, int T) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)BT * NPH * (C / 4)) return;
+    const int c = (int)(idx % (C / 4)) * 4;
+    const long long pos = idx / (C / 4);
+    const int p = (int)(pos % NPH);
+    const long long src = ((long long)p * PR + pos / NPH) * C + c;
+    f32x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (float)acts[src + j] + (lo ? (float)lo[src + j] : 0.f);
+    *reinterpret_cast<f32x4*>(out + pos * C + c) = v;
+}
+// test hook: the flow state after one flow ([M'][8] phase-major, or [BT * 32][8] natural after flow 0) -> [B][T * 32][n]
+__global__ void probe_state_kernel(const float* __restrict__ audio, int natural, float* __restrict__ out, int n, int PR, int BT) {
+    const long long pos = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >= (long long)BT * NPH) return;
+    const long long row = natural ? pos : (pos % NPH) * PR + pos / NPH;
+    for (int j = 0; j < n; ++j) out[pos * n + j] = audio[row * 8 + j];
 }
 
 // audio[m'][0..3] = sigma * z[natural m][0..3]  (z null => zeros); m' = p * PR + f  <->  m = f * 32 + p
@@ -805,6 +826,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         }
     }
     wg.last_form = wino ? 1 : 0;
+    wg.last_tiles = row64 ? 3 : x3 ? 0 : tile64 ? 2 : tile128 ? 1 : 0;     // codes: include/tts_hip.h
     _Float16* x16 = (_Float16*)wg.x16.p;
     _Float16* acts16 = (_Float16*)wg.acts16.p;
     _Float16* mel16 = (_Float16*)wg.mel16.p;
@@ -875,7 +897,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
                     else HIPCHK(e, row64 ? gemm_wn_in_r64(g, st) : tile64 ? gemm_wn_in_64(g, st) : tile128 ? gemm_wn_in_128(g, st) : gemm_wn_in(g, st));
                     timing_end(e);
                 }
-                if (wg.probe_out && wg.probe_flow == k && wg.probe_layer == i) {        // test hook: stop here
+                if (wg.probe_out && wg.probe_what == 0 && wg.probe_flow == k && wg.probe_layer == i) {   // test hook: stop here
                     const long long n4 = (long long)BT * NPH * (C / 4);
                     hipLaunchKernelGGL(probe_acts_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, acts_i,
                                        wg.probe_out, PR, BT, T);
@@ -943,6 +965,13 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
                 else if (tile64) HIPCHK(e, i == 0 ? gemm_wn_in0_64h(g, st) : gemm_wn_in_64h(g, st));
                 else HIPCHK(e, i == 0 ? gemm_wn_in0_h(g, tile128, st) : gemm_wn_in_h(g, tile128, st));
                 timing_end(e);
+                if (wg.probe_out && wg.probe_what == 0 && wg.probe_flow == k && wg.probe_layer == i) {   // test hook: stop here
+                    const long long n4 = (long long)BT * NPH * (C / 4);
+                    hipLaunchKernelGGL(probe_acts16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, acts_i,
+                                       x3 ? acts_i + M * C : (const _Float16*)nullptr, wg.probe_out, PR, BT, T);
+                    HIPCHK(e, hipGetLastError());
+                    return TTS_HIP_OK;
+                }
                 if (i < 7) {
                     GemmArgs r{};
                     r.M = (int)M;
@@ -988,6 +1017,13 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
                                (long long)M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
                                zoff, early ? 2 : 0, sigma, M, h, PR, BT);
         HIPCHK(e, hipGetLastError());
+        if (wg.probe_out && wg.probe_what == 1 && wg.probe_flow == k) {          // test hook: the state after this flow
+            const long long n = (long long)BT * NPH;
+            hipLaunchKernelGGL(probe_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)dst,
+                               k == 0 ? 1 : 0, wg.probe_out, 2 * h + (early ? 2 : 0), PR, BT);
+            HIPCHK(e, hipGetLastError());
+            return TTS_HIP_OK;
+        }
         if (early) zoff += 2;
     }
     return TTS_HIP_OK;

@@ -443,6 +443,38 @@ class HipEngine:
         """'winograd' or 'direct' for the last `waveglow_infer` call on this handle ('none' before the first)."""
         return {1: 'winograd', 0: 'direct'}.get(self._lib.tts_hip_last_waveglow_form(self._h), 'none')
 
+    @property
+    def last_waveglow_tiles(self) -> str:
+        """WN GEMM tile family of the last `waveglow_infer` (or probe) call: '64-row', '128x64', '128-row' or '256-row'
+        ('none' before the first)."""
+        return {3: '64-row', 2: '128x64', 1: '128-row', 0: '256-row'}.get(self._lib.tts_hip_last_waveglow_tiles(self._h), 'none')
+
+    def waveglow_probe(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', flow: int = 11, what: str = 'acts',
+                       layer: int = 0):
+        """Test hook (tts_hip_waveglow_probe): run `waveglow_infer` in `precision` up to flow `flow` and return either the gated
+        activations [B, T*32, 512] of its WN layer `layer` (what='acts') or the flow state [B, T*32, n] right after the flow,
+        early output included (what='state'; the reference's audio after that flow)."""
+        precs = {'f32': 0, 'f16': 1, 'f16x3': 2}
+        whats = {'acts': 0, 'state': 1}
+        if precision not in precs or what not in whats:
+            raise ValueError(f'precision must be one of {tuple(precs)} and what one of {tuple(whats)}')
+        mel = np.ascontiguousarray(mel, dtype=np.float32)
+        if mel.ndim != 3 or mel.shape[2] != 80:
+            raise ValueError(f'mel must be [B, T, 80], got {mel.shape}')
+        B, T = mel.shape[:2]
+        zp = None
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.float32)
+            if z.shape != (B, T * 32, 8):
+                raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {z.shape}')
+            zp = z.ctypes.data_as(ctypes.c_void_p)
+        width = 512 if what == 'acts' else (4 if flow >= 8 else 6 if flow >= 4 else 8) + (2 if flow in (4, 8) else 0)
+        out = np.empty((B, T * 32, width), dtype=np.float32)
+        self._check(self._lib.tts_hip_waveglow_probe(
+            self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, zp, float(sigma), precs[precision], int(flow), whats[what],
+            int(layer), out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'waveglow_probe')
+        return out
+
     def waveglow_probe_acts(self, mel, z=None, sigma: float = 1.0, flow: int = 11, layer: int = 1):
         """Test hook (tts_hip_waveglow_probe_acts): the gated activations [B, T*32, 512] of WN layer `layer` of flow `flow` on
         the fp32 path, in the form `set_waveglow_form` selects -- the values before the res/skip and `end` convolutions."""
