@@ -47,7 +47,8 @@ struct WgLayerDev {
     _Float16* rs_Bt_x3 = nullptr;
     float* wino_G = nullptr;    // Winograd form (wn_wino.hip; built on first use): [6][1024][512] tap combinations and the
     float* wino_V = nullptr;    //   conditioning planes of the phase / mixed groups ([8][6][1024][224] / [16][4][1024][320])
-    float* wino_Vf = nullptr;   //   three-pass form only: column-selected copies for the frame groups [32][6][1024][224]
+                                //   and of the frame groups of dilations 32, 64 ([32][5][1024][160], F(4, 2) along frames)
+    float* wino_Vf = nullptr;   //   three-pass form only: column-selected copies for the dilation-128 frame groups [32][6][1024][224]
     float* rs_Bt = nullptr;     // [512][512] residual half of res_skip (layers 0..6)
     float* rs_bias = nullptr;   // [512]
     int rs_n = 0;

@@ -806,12 +806,12 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
     // fp32 path, 128- / 256-row tiles: layers 1 .. 7 of a flow run in their Winograd form (wn_wino.hip)
     bool wino = wino_size && (!row64 || wg.form_mode != 2);               // (PR is a multiple of 64; form 2: of 128)
     if (wino) {
-        // its operands (3.6 GB of weight planes on first use, 0.7 GB of workspace at config 2) are extra: when the device cannot
+        // its operands (6.2 GB of weight planes on first use, 0.7 GB of workspace at config 2) are extra: when the device cannot
         // hold them -- and only then: any other error is the call's error -- this handle keeps the direct form from now on
         const bool three_pass = wg.form_mode == 2;
         size_t free_b = 0, total_b = 0;
         HIPCHK(e, hipMemGetInfo(&free_b, &total_b));
-        const size_t need = wg.wino_ready && (!three_pass || wg.wino_legacy_ready) ? 0 : (size_t)(three_pass ? 11 : 4) << 30;
+        const size_t need = wg.wino_ready && (!three_pass || wg.wino_legacy_ready) ? 0 : (size_t)(three_pass ? 10 : 7) << 30;
         int rc = free_b < need ? TTS_HIP_ENOMEM : waveglow_build_wino(e, three_pass);
         bool oom = rc == TTS_HIP_ENOMEM;
         if (!rc) {

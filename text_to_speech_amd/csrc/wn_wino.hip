@@ -29,6 +29,8 @@
 // B = [112, 208), C = [208, 320), each carried by a product subset whose columns of the output transform AT have rank 4 --
 // {0, 1, 2, 5}, {0, 3, 4, 5}, {1, 2, 3, 4} -- and combined with the inverse of those columns: K = 512 + 208 for products
 // 0, 3, 4, 5 and 512 + 224 for products 1, 2 (the fused kernels skip the all-zero padding chunk of the 208-column products).
+// Dilations 32 and 64 instead run the conditioning as a second Winograd transform along frames (F(4, 2), below
+// wino4_mel_planes_frames_kernel): K = 512 + 160 for products 0 .. 4 and 512 for product 5 -- 50 conditioning chunks instead of 80.
 //
 // Groups.  Dilation d <= 8 (sample groups): four PHASES p0 + j d of one frame, 8 group phases p0 = (gp / d) 4d + gp % d; the
 // outputs share their mel rows and differ in the per-phase conditioning weights, so the slice combinations are WEIGHT
@@ -261,8 +263,57 @@ __global__ void wino4_cond_weights_frames_kernel(const float* __restrict__ cond_
     V[idx] = col >= 0 ? cond_Bt[((long long)p * 2 * C + n) * KMEL + col] : 0.f;
 }
 
+// Frame groups with s = 1, 2 (dilations 32, 64): the four outputs' mel windows overlap, so the conditioning is itself a short
+// FIR along frames, cond_j = sum_q V_q mel[t0 + j s - q].  Its four taps split into two halves of two taps s frames apart --
+// s = 1: q in {0, 1} and {2, 3}; s = 2: q in {0, 2} and {1, 3} -- and half (qa, qb = qa + s) is a 2-tap correlation of the five
+// frames z_i = mel[t0 - qb + i s]: cond_j = V_qb z_j + V_qa z_{j+1}, i.e. an F(4, 2) problem.  Its evaluation points are five of
+// the six points of the tap transform -- 0, 1, -1, 2, -2 (whose output-transform columns are those of products 0 .. 4) -- so
+// each F(4, 2) product is ADDED INTO THE TAP PRODUCT OF THE SAME POINT: product k carries K = 2 halves x 80 = 160 conditioning
+// columns (weights V_qb + x_k V_qa, mel sum_i FIR_BT[k][i] z_i), product 5 (infinity) none: 50 chunks of 16 instead of 80.
+// (Point sets of five of the six, fp32 model with fp32 operands rounded once: {0, +-1, +-2} 2.5e-7 relative RMS of the
+//  conditioning for i.i.d. mel frames, {0, +-1, 2 or -2, infinity} 2.9e-7, the direct K = 320 sum 2.3e-7.)
+constexpr int KF = 160;                                    // conditioning K of a product (s = 1, 2)
+__constant__ double FIR_X[5] = {0, 1, -1, 2, -2};
+__constant__ double FIR_BT[5][5] = {{1, 0, -5. / 4, 0, 1. / 4},
+                                    {0, 2. / 3, 2. / 3, -1. / 6, -1. / 6},
+                                    {0, -2. / 3, 2. / 3, 1. / 6, -1. / 6},
+                                    {0, -1. / 12, -1. / 24, 1. / 12, 1. / 24},
+                                    {0, 1. / 12, -1. / 24, -1. / 12, 1. / 24}};
+__host__ __device__ __forceinline__ int fir_qb(int s, int half) { return s == 1 ? 2 * half + 1 : half + 2; }   // older tap
+
+// V[32][5][1024][160]: product k, column kk = half * 80 + c: V_qb + x_k V_qa (fp64, rounded once)
+__global__ void wino4_cond_weights_fir_kernel(const float* __restrict__ cond_Bt, float* __restrict__ V, int s) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)NPH * 5 * 2 * C * KF) return;
+    const int kk = (int)(idx % KF), n = (int)((idx / KF) % (2 * C)), k = (int)((idx / ((long long)KF * 2 * C)) % 5),
+              p = (int)(idx / ((long long)KF * 2 * C * 5));
+    const int qb = fir_qb(s, kk / 80), c = kk % 80;
+    const float* row = cond_Bt + ((long long)p * 2 * C + n) * KMEL + c;
+    V[idx] = (float)((double)row[qb * 80] + FIR_X[k] * (double)row[(qb - s) * 80]);
+}
+
+// mel planes [5][rows][160] for s = 1, 2: group row gf <-> frames t0 + j s of its utterance (frame_group); frames outside the
+// utterance read as zero (the frames past its end meet only outputs that are not written)
+__global__ void wino4_mel_planes_fir_kernel(const float* __restrict__ mel, float* __restrict__ P, int s, int rows, int BT, int T) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)5 * rows * KF) return;
+    const int kk = (int)(idx % KF), k = (int)(idx / ((long long)rows * KF));
+    int b, t0;
+    const bool ok = frame_group((idx / KF) % rows, s, BT, T, b, t0);
+    const int qb = fir_qb(s, kk / 80), c = kk % 80;
+    double acc = 0.0;
+    if (ok) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int t = t0 - qb + i * s;
+            if (t >= 0 && t < T) acc += FIR_BT[k][i] * (double)mel[((long long)b * T + t) * 80 + c];
+        }
+    }
+    P[idx] = (float)acc;
+}
+
 // mel planes [6][rows][224] for s = d / 32: group row gf <-> frames t0 + j s of its utterance (frame_group); product k, slice
-// column: sum_j coef[k][j] melwin(f_j) over the frames inside the utterance
+// column: sum_j coef[k][j] melwin(f_j) over the frames inside the utterance (s = 4 only: its windows do not overlap)
 __global__ void wino4_mel_planes_frames_kernel(const float* __restrict__ mel, float* __restrict__ P, int s, int rows, int BT, int T) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long long)6 * rows * K4) return;
@@ -387,9 +438,10 @@ __global__ void wino4_combine_kernel(const float* __restrict__ P, const float* _
 // (1.26 GB written and read per layer at config 2), no combine launch.  Same products in the same k order as the three-pass
 // form, so the two agree to the last bit of the fp32 sums (the output transform is written identically).
 // The conditioning chunks of a product are a chunk range of its mel plane against one or two chunk ranges of the weight rows:
-// for the frame groups (dilations >= 32) the products' weights are column selections of cond_Bt itself -- A = chunks 0 .. 6,
+// for the frame groups of dilation 128 the products' weights are column selections of cond_Bt itself -- A = chunks 0 .. 6,
 // B = 7 .. 12, C = 13 .. 19 of its 320 columns -- so no per-product copies exist, and the all-zero padding chunk of the
-// 208-column products is skipped (45 K steps instead of 46 for four of the six products).
+// 208-column products is skipped (45 K steps instead of 46 for four of the six products).  Dilations 32 / 64: ten chunks of
+// the F(4, 2) planes for products 0 .. 4, none for product 5.
 struct WinoFusedArgs {
     const float* U;   long long uplane;                       // transformed inputs [6][Mq][512]
     const float* G;   long long gplane;                       // tap combinations [6][1024][512]
@@ -1004,10 +1056,11 @@ static inline int mixed_group_rows(int BT, int T, int form) {
 }
 
 // Per-layer operands (on the first call that takes this path): G for layers 1 .. 7 of every flow; V for the phase groups
-// (dilations 2 - 8: weight combinations over the group's four phases) and the mixed groups (dilation 16).  The frame groups
-// (dilations >= 32) need none in the fused form -- their products' conditioning weights are chunk ranges of cond_Bt itself --
-// and six column-selected copies per phase ([32][6][1024][224], 176 MB per layer) in the three-pass form, built only when that
-// form is asked for (`legacy_frames`).  3.6 GB in all (three-pass: + 6.3 GB).  A failed allocation frees what this call built.
+// (dilations 2 - 8: weight combinations over the group's four phases), the mixed groups (dilation 16) and the frame groups of
+// dilations 32 and 64 (the F(4, 2) weight planes, [32][5][1024][160]: 105 MB per layer, the same for every form).  Dilation 128
+// needs none in the fused forms -- its products' conditioning weights are chunk ranges of cond_Bt itself -- and six
+// column-selected copies per phase ([32][6][1024][224], 176 MB per layer) in the three-pass form, built only when that form is
+// asked for (`legacy_frames`).  6.2 GB in all (three-pass: + 2.1 GB).  A failed allocation frees what this call built.
 int waveglow_build_wino(tts_hip_engine* e, bool legacy_frames) {
     WaveGlowDev& wg = e->wg;
     if (wg.wino_ready && (!legacy_frames || wg.wino_legacy_ready)) return TTS_HIP_OK;
@@ -1040,9 +1093,14 @@ int waveglow_build_wino(tts_hip_engine* e, bool legacy_frames) {
                     if ((rc = dev_alloc(e, (size_t)(NPH / 4) * 6 * 2 * C * K4, &ly.wino_V, fresh, false))) return fail(rc);
                     hipLaunchKernelGGL(wino4_cond_weights_kernel, dim3(blocks_for((long long)(NPH / 4) * 6 * 2 * C * K4)), dim3(256),
                                        0, st, ly.cond_Bt, ly.wino_V, d);
+                } else if (d < 4 * NPH) {                  // frame groups, s = 1, 2: F(4, 2) along frames
+                    const long long n = (long long)NPH * 5 * 2 * C * KF;
+                    if ((rc = dev_alloc(e, (size_t)n, &ly.wino_V, fresh, false))) return fail(rc);
+                    hipLaunchKernelGGL(wino4_cond_weights_fir_kernel, dim3(blocks_for(n)), dim3(256), 0, st, ly.cond_Bt, ly.wino_V,
+                                       d / NPH);
                 }
             }
-            if (legacy_frames && !wg.wino_legacy_ready && d >= NPH) {
+            if (legacy_frames && !wg.wino_legacy_ready && d == 4 * NPH) {
                 if ((rc = dev_alloc(e, (size_t)NPH * 6 * 2 * C * K4, &ly.wino_Vf, fresh, false))) return fail(rc);
                 hipLaunchKernelGGL(wino4_cond_weights_frames_kernel, dim3(blocks_for((long long)NPH * 6 * 2 * C * K4)), dim3(256), 0,
                                    st, ly.cond_Bt, ly.wino_Vf);
@@ -1058,15 +1116,16 @@ int waveglow_build_wino(tts_hip_engine* e, bool legacy_frames) {
     return TTS_HIP_OK;
 }
 
-// Layout of the per-call mel planes (floats): [phase groups: 6][PR][224] | 3 x [frame groups: 6][PRq][224] | [mixed: 4][PRm][320]
+// Layout of the per-call mel planes (floats): [phase groups: 6][PR][224] | 2 x [frame groups, s = 1, 2: 5][PRq][160] |
+// [frame groups, s = 4: 6][PRq][224] | [mixed: 4][PRm][320]
 struct MelPlanes {
     size_t phases, frames[3], mixed, total;
     MelPlanes(int PR, int BT, int T, int form) {
         const size_t PRq = (size_t)frame_group_rows(BT, T, form), PRm = (size_t)mixed_group_rows(BT, T, form);
         phases = 0;
         frames[0] = (size_t)6 * PR * K4;
-        frames[1] = frames[0] + 6 * PRq * K4;
-        frames[2] = frames[1] + 6 * PRq * K4;
+        frames[1] = frames[0] + 5 * PRq * KF;
+        frames[2] = frames[1] + 5 * PRq * KF;
         mixed = frames[2] + 6 * PRq * K4;
         total = mixed + 4 * PRm * KMEL;
     }
@@ -1094,9 +1153,11 @@ int waveglow_wino_begin(tts_hip_engine* e, const float* d_mel, int PR, int BT, i
     if ((rc = room(wg.wino_mel, mp.total * 4))) return rc;
     float* base = wg.wino_mel.f();
     hipLaunchKernelGGL(wino4_mel_planes_kernel, dim3(blocks_for((long long)PR * K4)), dim3(256), 0, st, d_mel, base + mp.phases, PR, BT, T);
-    for (int si = 0; si < 3; ++si)
-        hipLaunchKernelGGL(wino4_mel_planes_frames_kernel, dim3(blocks_for((long long)6 * PRq * K4)), dim3(256), 0, st, d_mel,
+    for (int si = 0; si < 2; ++si)
+        hipLaunchKernelGGL(wino4_mel_planes_fir_kernel, dim3(blocks_for((long long)5 * PRq * KF)), dim3(256), 0, st, d_mel,
                            base + mp.frames[si], 1 << si, PRq, BT, T);
+    hipLaunchKernelGGL(wino4_mel_planes_frames_kernel, dim3(blocks_for((long long)6 * PRq * K4)), dim3(256), 0, st, d_mel,
+                       base + mp.frames[2], 4, PRq, BT, T);
     hipLaunchKernelGGL(wino4_mel_planes_mixed_kernel, dim3(blocks_for((long long)PRm * KMEL)), dim3(256), 0, st, d_mel,
                        base + mp.mixed, PRm, BT, T);
     HIPCHK(e, hipGetLastError());
@@ -1112,7 +1173,7 @@ int waveglow_wino_layer(tts_hip_engine* e, const WgLayerDev& ly, int i, const fl
     float* P = wg.wino_P.f();
     const MelPlanes mp(PR, BT, T, wg.form_mode);
     const int PRq = frame_group_rows(BT, T, wg.form_mode), PRm = mixed_group_rows(BT, T, wg.form_mode);
-    const bool phases = d <= 8, mixed = d == 16;
+    const bool phases = d <= 8, mixed = d == 16, fir = d == NPH || d == 2 * NPH;
     const long long Mq = phases ? (long long)(NPH / 4) * PR : mixed ? (long long)16 * PRm : (long long)NPH * PRq;
     const bool no_prepass = wg.form_mode == 1;             // form 1 (default): input transform inside the GEMM's operand reads
     if (!no_prepass) hipLaunchKernelGGL(wino4_prepass_kernel, dim3(blocks_for(Mq * (C / 4))), dim3(256), 0, st, x, U, d, PR, BT, T, Mq);
@@ -1152,7 +1213,16 @@ int waveglow_wino_layer(tts_hip_engine* e, const WgLayerDev& ly, int i, const fl
             a.ldv = KMEL;
             a.pofs = 1;
             for (int p = 1; p < 5; ++p) ccfg[p] = cc(KMEL / 16, 0);
-        } else {                                           // frame groups: chunk ranges of cond_Bt [32 phases][1024][320]
+        } else if (fir) {                                  // frame groups, s = 1, 2: products 0 .. 4, K = 160 against V [32][5][1024][160]
+            a.mel = wg.wino_mel.f() + mp.frames[i - 5];
+            a.mplane = (long long)PRq * KF;
+            a.ldm = KF;
+            a.V = ly.wino_V;
+            a.vplane = (long long)2 * C * KF;
+            a.strideVp = 5 * a.vplane;
+            a.ldv = KF;
+            for (int p = 0; p < 5; ++p) ccfg[p] = cc(KF / 16, 0);
+        } else {                                           // frame groups, s = 4: chunk ranges of cond_Bt [32 phases][1024][320]
             a.mel = wg.wino_mel.f() + mp.frames[i - 5];
             a.mplane = (long long)PRq * K4;
             a.ldm = K4;
@@ -1201,7 +1271,33 @@ int waveglow_wino_layer(tts_hip_engine* e, const WgLayerDev& ly, int i, const fl
     g.ld0 = 2 * C;
     g.wide_epi = 1;
     const long long uplane = Mq * C, gplane = (long long)2 * C * C, pplane = Mq * 2 * C;
-    if (!mixed) {                                          // six slices of K = 512 + 224
+    if (fir) {
+        // products 0 .. 4: K = 512 + 160 (the F(4, 2) conditioning products) ...
+        g.nseg = 2;
+        g.seg[0] = ASeg{U, C, 0, C, C, SEG_ROWS_Z, 0, Mq, 1};
+        g.seg[1] = ASeg{wg.wino_mel.f() + mp.frames[i - 5], KF, 0, KF, KF, SEG_FRAME_Z, 0, (long long)PRq, 0};
+        g.Bt = ly.wino_G;
+        g.strideBz = gplane;
+        g.Bt2 = ly.wino_V;
+        g.ldb2 = KF;
+        g.strideB2p = (long long)5 * 2 * C * KF;
+        g.strideB2z = (long long)2 * C * KF;
+        g.out0 = P;
+        g.strideOutZ = pplane;
+        timing_begin(e, 0);
+        HIPCHK(e, gemm_wn_wino_128(g, 5, st));
+        timing_end(e);
+        // ... product 5: K = 512
+        GemmArgs h = g;
+        h.nseg = 1;
+        h.seg[0] = ASeg{U + 5 * uplane, C, 0, C, C, SEG_ROWS_Z, 0, Mq, 0};
+        h.Bt = ly.wino_G + 5 * gplane;
+        h.Bt2 = nullptr;
+        h.out0 = P + 5 * pplane;
+        timing_begin(e, 0);
+        HIPCHK(e, gemm_wn_wino_128(h, 1, st));
+        timing_end(e);
+    } else if (!mixed) {                                   // six slices of K = 512 + 224
         g.nseg = 2;
         g.seg[0] = ASeg{U, C, 0, C, C, SEG_ROWS_Z, 0, Mq, 1};
         g.seg[1] = ASeg{wg.wino_mel.f() + (phases ? mp.phases : mp.frames[i - 5]), K4, 0, K4, K4, SEG_FRAME_Z, 0, (long long)g.phase_rows, 0};
