@@ -228,6 +228,20 @@ int tts_hip_trim_silence(tts_hip_engine* e, const float* audio, int B, int N, co
                          double threshold, double add_start, double add_end, int mode, int32_t* start, int32_t* end,
                          int mem);
 
+/* ---- resampling (csrc/resample.hip; no weights needed)
+ * scipy.signal.resample(x, int(n / rate * target_rate)) per row (utils/audio/audio_processing.py:30-35), window=None, in
+ * fp32 (scipy returns float64).  audio [B, N] -> out [B, M]; M must be (int)((double)N / rate * target_rate) >= 1.  Row b
+ * holds lengths[b] (1 <= lengths[b] <= N) samples, lengths NULL = N for every row; out row b holds
+ * (int)((double)lengths[b] / rate * target_rate) samples, then zeros, and equals a one-row call on audio[b, :lengths[b]].
+ * At most 2^24 samples per row in and out, B * N * 4 and B * M * 4 below 2^31.  rate == target_rate copies the rows and
+ * launches nothing.  `lengths` is host memory in every mode; audio and out follow `mem` / live on the device for the _async
+ * form.  One workspace per handle: an _async call must have finished on its stream (or be ordered before the next call)
+ * before the next resample on the handle.                                                                               */
+int tts_hip_resample(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate, int target_rate,
+                     float* out, int M, int mem);
+int tts_hip_resample_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate,
+                           int target_rate, float* out, int M, void* stream);
+
 /* ---- measurement hooks (used by bench.py; no effect on results) -------------------------------------------------
  * Average duration in microseconds of the dominant kernel's launches (HIP events on the engine's stream) since the
  * last reset, and how many launches were timed.  kind: 0 = WaveGlow WN in-layer GEMM (layers 1..7 of a flow: K = 2176),

@@ -1,9 +1,12 @@
 """Audio input path: wav reading, normalization and the device-side clean-up the reference applies while loading.
 
-Mirrors utils/audio/audio_io.py:100-144 (`load_audio`, `load_mel`) and :186-270 (`read_audio`): normalize ->
-reduce_noise -> normalize again -> trim_silence, in that order.  Normalization is host numpy (as in the reference, on the
-raw int16 samples); noise reduction and the trim indices run on the GPU (HipEngine.reduce_noise / trim_silence,
-csrc/audio_proc.hip).  Resampling and the trim methods other than 'window' are not provided: asking for them raises.
+Mirrors utils/audio/audio_io.py:100-144 (`load_audio`, `load_mel`) and :186-270 (`read_audio`): resample -> normalize ->
+reduce_noise -> normalize again -> trim_silence, in that order.  Normalization is host numpy (as in the reference);
+resampling, noise reduction and the trim indices run on the GPU (HipEngine.resample / reduce_noise / trim_silence,
+csrc/resample.hip, csrc/audio_proc.hip).  Resampling is opt-in (`resample=True`): by default a file at another rate
+raises, as before.  It differs from the reference in one way: the reference resamples the raw int16 samples in float64
+(scipy.signal.resample), here they become float32 (exactly) and are resampled in fp32 on the device.  The trim methods
+other than 'window' are not provided: asking for them raises.
 """
 from __future__ import annotations
 
@@ -30,16 +33,33 @@ def normalize_audio(audio, max_val=32767, dtype=np.int16):
     return (audio * (max_val / max_audio_val)).astype(dtype)
 
 
-def load_audio(data, rate=None, *, engine, normalize=True, reduce_noise=False, trim_silence=False, method='window', **kwargs):
-    """A filename or raw samples -> float32 [n] (audio_io.py:100-127 + :186-268).  `rate`: the rate the caller wants; a
-    file at another rate raises (no resampling).  Raw samples need `rate`.  kwargs: `noise`, `noise_length` for
-    reduce_noise; `threshold`, `window_length`, `add_start`, `add_end`, `mode` for trim_silence."""
+def resampled_length(n, rate, target_rate):
+    """Samples after resampling n samples from `rate` to `target_rate`: int(n / rate * target_rate), evaluated in this
+    order in IEEE double as utils/audio/audio_processing.py:33 does (not n * target_rate // rate: for 11 200 samples at
+    16 000 -> 22 050 Hz the two give 15 434 and 15 435).  csrc/resample.hip uses the same expression."""
+    if rate <= 0 or target_rate <= 0:
+        raise ValueError(f'resample: rates must be > 0 (got {rate}, {target_rate})')
+    m = int(int(n) / rate * target_rate)
+    if m < 1:
+        raise ValueError(f'resample: {n} samples at {rate} -> {target_rate} Hz give {m} < 1 samples')
+    return m
+
+
+def load_audio(data, rate=None, *, engine, normalize=True, reduce_noise=False, trim_silence=False, method='window',
+               resample=False, source_rate=None, **kwargs):
+    """A filename or raw samples -> float32 [n] (audio_io.py:100-127 + :186-268).  `rate`: the rate the caller wants.
+    resample=False: a file at another rate raises.  resample=True: audio at another rate (the file's header, a dict's
+    'rate' entry, or `source_rate=` for raw samples) is resampled to `rate` on `engine` before normalization, as the
+    reference does.  Raw samples need `rate`.  kwargs: `noise`, `noise_length` for reduce_noise; `threshold`,
+    `window_length`, `add_start`, `add_end`, `mode` for trim_silence."""
     if trim_silence and method != 'window':
         raise ValueError(f"trim_silence: only method='window' is implemented (got {method!r})")
     unknown = set(kwargs) - set(_RN_KEYS) - set(_TRIM_KEYS)
     if unknown:
         raise ValueError(f'load_audio: unknown arguments {sorted(unknown)}')
     if isinstance(data, dict):
+        if 'rate' in data and resample and source_rate is None:
+            source_rate = data['rate']
         if 'rate' in data and rate is None:
             rate = data['rate']
         data = data['audio'] if 'audio' in data else data.get('filename', data.get('audio_filename'))
@@ -47,15 +67,20 @@ def load_audio(data, rate=None, *, engine, normalize=True, reduce_noise=False, t
         data = data.decode()
     if isinstance(data, str):
         file_rate, audio = read_wav(data)
-        if rate is not None and int(rate) != int(file_rate):
-            raise ValueError(f'{data} is sampled at {file_rate} Hz, {rate} Hz requested: resampling is not supported')
-        rate = int(file_rate)
+        if rate is not None and int(rate) != int(file_rate) and not resample:
+            raise ValueError(f'{data} is sampled at {file_rate} Hz, {rate} Hz requested: resampling is off '
+                             f'(pass resample=True)')
+        source_rate = int(file_rate)
+        rate = int(file_rate) if rate is None else rate
     else:
         if rate is None:
             raise ValueError('load_audio: raw audio needs `rate`')
         audio = data.detach().cpu().numpy() if hasattr(data, 'detach') else np.asarray(data)
     if audio.ndim != 1:
         raise ValueError(f'load_audio: expected mono audio [n], got shape {audio.shape}')
+
+    if resample and source_rate is not None and int(source_rate) != int(rate):
+        audio = engine.resample(np.asarray(audio, np.float32), int(source_rate), int(rate))
 
     if normalize:
         if normalize is True:
@@ -75,12 +100,13 @@ def load_audio(data, rate=None, *, engine, normalize=True, reduce_noise=False, t
 MEL_RATE = 22050                    # TacotronSTFT's sampling rate (engine.mel_stft's filterbank)
 
 
-def load_mel(data, rate=MEL_RATE, *, engine, **kwargs):
+def load_mel(data, rate=MEL_RATE, *, engine, resample=False, **kwargs):
     """audio_io.py:129-144 with TacotronSTFT (engine.mel_stft): load_audio(data, stft_fn.rate, ...) -> mel [T, 80].  Like the
-    reference, the audio is loaded at the STFT's rate: a file at another rate raises (no resampling)."""
+    reference, the audio is loaded at the STFT's rate: a file at another rate raises unless resample=True, which resamples
+    it on `engine` first."""
     if isinstance(data, dict) and 'mel' in data:
         return data['mel']
     if rate != MEL_RATE:
         raise ValueError(f'load_mel: the mel-STFT runs at {MEL_RATE} Hz, got rate={rate}')
-    audio = load_audio(data, rate, engine=engine, **kwargs)
+    audio = load_audio(data, rate, engine=engine, resample=resample, **kwargs)
     return engine.mel_stft(np.asarray(audio, np.float32))[0]

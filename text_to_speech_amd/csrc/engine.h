@@ -171,6 +171,13 @@ struct AudioProcDev {
     std::vector<int> info_h;            // per-row facts staged to the device
 };
 
+// Resampling (resample.hip): the W_8192 twiddle table built on first use; the workspace holds, per row, the stage lines
+// (signal and filter: 16 * max(L_fwd, L_inv) bytes) and the kept rfft bins (8 * (N_b // 2 + 1) bytes)
+struct ResampleDev {
+    DevBuf tw, ws, io;                  // twiddles, workspace, host staging
+    std::vector<int> info_h;            // per-row facts staged to the device
+};
+
 struct TimedLaunch {
     hipEvent_t a, b;
     int kind;
@@ -186,6 +193,7 @@ struct tts_hip_engine {
     Tacotron2Dev taco;
     MelStftDev stft;
     AudioProcDev aproc;
+    ResampleDev resamp;
     // timing hooks
     bool timing = false;
     std::vector<TimedLaunch> timed;
@@ -237,6 +245,7 @@ int melstft_finalize(tts_hip_engine* e);
 int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_mel);
 void melstft_free(tts_hip_engine* e);
 void audioproc_free(tts_hip_engine* e);
+void resample_free(tts_hip_engine* e);
 
 // shared helpers
 // n floats of device-side samples into `out` on `st` (engine.hip: Philox4x32-10; kind = TTS_HIP_RANDOM_*)

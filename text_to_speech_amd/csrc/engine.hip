@@ -212,6 +212,7 @@ int tts_hip_destroy(tts_hip_engine* e) {
     tacotron2_free(e);
     melstft_free(e);
     audioproc_free(e);
+    resample_free(e);
     (void)hipStreamDestroy(e->stream);
     delete e;
     return TTS_HIP_OK;

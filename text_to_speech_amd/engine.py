@@ -630,6 +630,62 @@ class HipEngine:
                     'reduce_noise')
         return out[0] if one_row else out
 
+    _RESAMPLE_MAX = 1 << 24         # samples per row, in and out (csrc/resample.hip)
+
+    def resample(self, audio, rate, target_rate, lengths=None, stream=None):
+        """scipy.signal.resample(x, int(N / rate * target_rate)) per row (utils/audio/audio_processing.py:30-35), in fp32 on
+        the GPU (csrc/resample.hip).  audio [N] or [B, N]; row b holds lengths[b] samples (default N) and its result is what
+        a one-row call on audio[b, :lengths[b]] gives: resampled_length(lengths[b]) samples, then zeros up to
+        M = resampled_length(N).  rate == target_rate returns the input as float32 and launches nothing.  numpy in -> numpy
+        out; a CUDA tensor in -> a CUDA tensor out; `stream` (torch.cuda.Stream, device tensors only): enqueue there and
+        return without waiting (the next resample on this engine must be ordered after it)."""
+        from .audio import resampled_length
+        B, N, lens = self._audio_rows(audio, lengths, 'resample')
+        if int(rate) != rate or int(target_rate) != target_rate or rate <= 0 or target_rate <= 0:
+            raise ValueError(f'resample: rates must be positive integers (got {rate}, {target_rate})')
+        rate, target_rate = int(rate), int(target_rate)
+        if N > self._RESAMPLE_MAX:
+            raise ValueError(f'resample: rows of {N} samples; at most 2^24 are supported')
+        M = resampled_length(N, rate, target_rate)          # raises for M < 1
+        if M > self._RESAMPLE_MAX:
+            raise ValueError(f'resample: {N} samples at {rate} -> {target_rate} Hz give {M}; at most 2^24 are supported')
+        if lens is not None:
+            for n in np.unique(lens):
+                resampled_length(int(n), rate, target_rate)
+        if B * max(N, M) * 4 >= 1 << 31:
+            raise ValueError(f'resample: B = {B} x N = {N} (M {M}) too large for 31-bit offsets')
+        one_row = len(audio.shape) == 1
+        lens_p = lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None
+        if _is_torch_cuda(audio):
+            torch = self._torch()
+            self._check_device(audio)
+            if rate == target_rate and lens is None:
+                return audio.to(torch.float32)
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+            if stream is not None:
+                with self._enter_stream(stream):
+                    a = audio.to(torch.float32).reshape(B, N).contiguous()
+                    out = torch.empty((B, M), dtype=torch.float32, device=a.device)
+                self._used_on(stream, audio, a, out)
+                self._check(self._lib.tts_hip_resample_async(self._h, ptr(a), B, N, lens_p, rate, target_rate, ptr(out), M,
+                                                             self._order_after_torch(stream)), 'resample_async')
+            else:
+                a = audio.to(torch.float32).reshape(B, N).contiguous()
+                out = torch.empty((B, M), dtype=torch.float32, device=a.device)
+                self._order_after_torch()
+                self._check(self._lib.tts_hip_resample(self._h, ptr(a), B, N, lens_p, rate, target_rate, ptr(out), M,
+                                                       MEM_DEVICE), 'resample')
+            return out[0] if one_row else out
+        if stream is not None:
+            raise ValueError('stream= needs device tensors')
+        a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
+        if rate == target_rate and lens is None:
+            return a[0] if one_row else a
+        out = np.empty((B, M), dtype=np.float32)
+        self._check(self._lib.tts_hip_resample(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens_p, rate, target_rate,
+                                               out.ctypes.data_as(ctypes.c_void_p), M, MEM_HOST), 'resample')
+        return out[0] if one_row else out
+
     def trim_silence(self, audio, rate=None, lengths=None, threshold=0.1, window_length=0.2, add_start=0, add_end=1.5,
                      mode='start_end'):
         """Window-method silence trimming (utils/audio/audio_processing.py:274-370: power 2, triangular window, adaptive
