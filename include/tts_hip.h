@@ -171,6 +171,26 @@ int tts_hip_set_decoder_mode(tts_hip_engine* e, int mode);
  * (also after a fallback), -1 before the first call.                                                                          */
 int tts_hip_last_decoder_mode(const tts_hip_engine* e);
 
+/* Test hooks of the encoder and postnet convolutions (used by tests/ only; no effect on later calls).  Both run the code of
+ * tts_hip_tacotron2_infer, not a copy, up to a stop point and copy what it computed there to `out` (fp32):
+ * probe_encoder: the encoder of `tokens` [B, Tin] (+ speaker, as tts_hip_tacotron2_encode; B <= 1024, Tin <= 4096) --
+ *   what 0 .. 2: output of encoder conv 1 .. 3 (MaskedConv1D -> BN -> relu), [B, Tin, 512], padded positions stored as 0;
+ *   what 3: memory [B, Tin, enc] (BiLSTM output, then the speaker columns at 512 .. enc); what 4: processed memory
+ *   [B, Tin, 128] (memory @ memory_layer).
+ * probe_postnet: the postnet + residual on caller `frames` [B, T, 80] (in place of the decoder output) with `lengths` [B]
+ *   (int32, HOST memory in every mode; mask t <= lengths[b], as after the decoder loop; B <= 1024, B * T <= 2^18) --
+ *   what 0 .. 3: output of postnet conv 1 .. 4 (tanh), [B, T, 512], masked positions stored as 0; what 4: conv 5 (the
+ *   residual, no activation), [B, T, 80], masked positions BN(0); what 5: mel = frames + residual, [B, T, 80].          */
+int tts_hip_tacotron2_probe_encoder(tts_hip_engine* e, const int32_t* tokens, int B, int Tin, const float* speaker, int what,
+                                    float* out, int mem);
+int tts_hip_tacotron2_probe_postnet(tts_hip_engine* e, const float* frames, int B, int T, const int32_t* lengths, int what,
+                                    float* out, int mem);
+/* How each k = 5 conv + folded batch-norm last ran on this handle (encode, decode or probe): bit i set = one GEMM over the five
+ * shifted segments with bias, row mask and activation in its epilogue ("single pass", 512 output tiles of 64 x 64 or more),
+ * clear = one GEMM per tap into a scratch buffer plus a reduction pass ("split").  Bits 0 - 2: encoder convs 1 - 3, bits
+ * 3 - 7: postnet convs 1 - 5; a conv that has not run yet reads 0.  -1 before the first conv.                             */
+int tts_hip_last_conv_paths(const tts_hip_engine* e);
+
 /* How the fp32 WaveGlow path evaluates the k = 3 dilated convolution of WN layers 1 .. 7 (waveglow_arch.py:117-127).
  * form 1 (default): Winograd minimal filtering along the tap axis for calls of 144 frames or more (any utterance length;
  * csrc/wn_wino.hip) -- F(4,3), six products per four outputs: K per output ~800 + 320 instead of 1536 + 320, fp32 operands

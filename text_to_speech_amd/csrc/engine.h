@@ -138,6 +138,8 @@ struct Tacotron2Dev {
     int persist_mode = 3;               // tts_hip_set_decoder_mode: 0 per-step graph only, 1 persistent kernel when allowed, 2 fused
                                         // two-kernel step when allowed, 3 auto (persistent for 1 - 2 rows, fused above)
     int last_path = -1;                 // how the last call ran its loop: 2 fused step, 1 persistent kernel, 0 per-step graph
+    int last_conv_paths = -1;           // how each k = 5 conv last ran (conv_gemm): bit i set = single pass; bits 0-2 encoder
+                                        // convs 1-3, bits 3-7 postnet convs 1-5; -1 before the first conv
     bool persist_timed = true;          // persistent kernel: timed optimistic polls on (switched off if they mostly miss)
     int fused_backoff = 0;              // calls to keep off the fused step after one of its exchanges timed out (shared GPU)
     int fused_fail_streak = 0;

@@ -865,9 +865,12 @@ __global__ void conv_reduce_kernel(const float* __restrict__ part, long long zst
 // (an utterance's encoder or postnet: M = 100..800 rows) leave most CUs idle and make the K = 5 * 512 MFMA chain of one
 // 32 x 32 tile the critical path (1280 x 64 cycles = 34 us), so small problems run one K slice per tap (blockIdx.z = tap:
 // 5x the blocks, 1/5 of the chain) into `scratch` [5][M][cout] and a vectorised pass adds the slices, bias, mask and
-// activation.  Large ones (>= 512 tiles) keep the single-pass kernel with the fused epilogue.
+// activation.  Large ones (>= 512 tiles) keep the single-pass kernel with the fused epilogue.  `path_bit` is this conv's bit
+// of Tacotron2Dev::last_conv_paths (tts_hip_last_conv_paths): set when it runs single pass, cleared when split.
 int conv_gemm(tts_hip_engine* e, const ConvBnDev& cv, const float* x, int ldx, float* out, int M, int L,
-              const uint8_t* rowmask, int act, int mask_out, float* scratch, size_t scratch_floats) {
+              const uint8_t* rowmask, int act, int mask_out, float* scratch, size_t scratch_floats, int path_bit) {
+    int& paths = e->taco.last_conv_paths;
+    if (paths < 0) paths = 0;
     GemmArgs g{};
     g.M = M;
     g.N = cv.cout;
@@ -892,6 +895,7 @@ int conv_gemm(tts_hip_engine* e, const ConvBnDev& cv, const float* x, int ldx, f
         hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, e->stream, scratch,
                            (long long)M * cv.cout, 5, cv.bias, cv.altbias, rowmask, mask_out, act, out, cv.cout, total4);
         HIPCHK(e, hipGetLastError());
+        paths &= ~(1 << path_bit);
         return TTS_HIP_OK;
     }
     g.nseg = 5;
@@ -903,6 +907,7 @@ int conv_gemm(tts_hip_engine* e, const ConvBnDev& cv, const float* x, int ldx, f
     g.altbias = cv.altbias;
     g.mask_out = mask_out;
     HIPCHK(e, gemm_small(g, 1, e->stream));
+    paths |= 1 << path_bit;
     return TTS_HIP_OK;
 }
 
@@ -1174,8 +1179,10 @@ void tacotron2_graphs_clear(tts_hip_engine* e) {
 // ---------------------------------------------------------------------------------------------------------- encoder
 // tokens -> (mask, lengths, memory, processed memory) in `out` (its own device buffer, so several encoded utterances can
 // be alive); temporaries live in the engine workspace.  Everything is enqueued on e->stream; nothing is synchronized.
+// Test hook (tts_hip_tacotron2_probe_encoder): stop_conv = i (0 .. 2) returns right after encoder conv i with *stop_out
+// pointing at its output [B * Tin][512] in the workspace; -1 runs the whole encoder.
 static int tacotron2_encode_impl(tts_hip_engine* e, const int32_t* tokens, int B, int Tin, const float* speaker, int mem,
-                                 tts_hip_encoded* out) {
+                                 tts_hip_encoded* out, int stop_conv = -1, const float** stop_out = nullptr) {
     Tacotron2Dev& tc = e->taco;
     if (!tc.ready) return set_err(e, TTS_HIP_ENOTREADY, "tacotron2 weights not finalized");
     if (!tokens || !out || B <= 0 || Tin <= 0 || Tin > 4096 || B > 1024)
@@ -1251,8 +1258,12 @@ static int tacotron2_encode_impl(tts_hip_engine* e, const int32_t* tokens, int B
     float* xout = d_x1;
     for (int i = 0; i < 3; ++i) {
         // MaskedConv1D -> BN -> relu; rows at padded tokens are stored as zeros (they are only ever consumed masked)
-        if ((rc = conv_gemm(e, tc.enc_conv[i], xin, 512, xout, (int)R, Tin, d_mask, ACT_RELU, 1, d_convtmp, convtmp_n))) return rc;
+        if ((rc = conv_gemm(e, tc.enc_conv[i], xin, 512, xout, (int)R, Tin, d_mask, ACT_RELU, 1, d_convtmp, convtmp_n, i))) return rc;
         std::swap(xin, xout);
+        if (i == stop_conv) {
+            *stop_out = xin;
+            return TTS_HIP_OK;
+        }
     }
     {
         GemmArgs g{};
@@ -1300,6 +1311,51 @@ static int tacotron2_encode_impl(tts_hip_engine* e, const int32_t* tokens, int B
 static std::mutex& whole_gpu_mutex(int device) {
     static std::mutex m[PerDeviceOnce::kMaxDevices];
     return m[device >= 0 && device < PerDeviceOnce::kMaxDevices ? device : 0];
+}
+
+// ---------------------------------------------------------------------------------------------------------- postnet
+struct PostnetBufs {
+    uint8_t* dmask;                     // [B * T]
+    float* xm;                          // [B * T][80]  masked decoder output
+    float* pa;                          // [B * T][512] x 2: ping-pong of the tanh convs
+    float* pb;
+    float* post;                        // [B * T][80]  residual
+    float* mel;                         // [B * T][80]
+    float* convtmp;                     // split-path scratch of conv_gemm
+    size_t convtmp_n;
+};
+
+// Postnet + residual on e->stream (tacotron2_arch.py:214-232, 915-917): mask t <= lengths[b] (:745, per row), five masked
+// k = 5 convs + folded batch-norm -- tanh on the first four, whose padded rows are stored as 0 (only ever read masked), the
+// last one's padded rows are BN(0) as in the reference -- then mel = decoder output + residual.  Test hook
+// (tts_hip_tacotron2_probe_postnet): stop_conv = i (0 .. 4) returns right after conv i with *stop_out pointing at its output.
+static int postnet_residual(tts_hip_engine* e, const int* d_lengths, const float* d_decout, int B, int max_len,
+                            const PostnetBufs& pb, int stop_conv = -1, const float** stop_out = nullptr) {
+    Tacotron2Dev& tc = e->taco;
+    hipStream_t st = e->stream;
+    const long long RD = (long long)B * max_len;
+    const long long n = RD * NMEL;
+    hipLaunchKernelGGL(dec_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_lengths, d_decout, pb.dmask,
+                       pb.xm, max_len, RD);
+    HIPCHK(e, hipGetLastError());
+    float* const outs[5] = {pb.pa, pb.pb, pb.pa, pb.pb, pb.post};
+    const float* x = pb.xm;
+    int ldx = NMEL;
+    for (int i = 0; i < 5; ++i) {
+        const bool last = i == 4;
+        if (int rc = conv_gemm(e, tc.post_conv[i], x, ldx, outs[i], (int)RD, max_len, pb.dmask, last ? ACT_NONE : ACT_TANH,
+                               last ? 0 : 1, pb.convtmp, pb.convtmp_n, 3 + i))
+            return rc;
+        if (i == stop_conv) {
+            *stop_out = outs[i];
+            return TTS_HIP_OK;
+        }
+        x = outs[i];
+        ldx = 512;
+    }
+    hipLaunchKernelGGL(add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_decout, pb.post, pb.mel, n);
+    HIPCHK(e, hipGetLastError());
+    return TTS_HIP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------- decoder
@@ -1737,19 +1793,8 @@ static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, i
     }
 
     // ---------------- postnet + residual
-    {
-        const long long n = RD * NMEL;
-        hipLaunchKernelGGL(dec_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_lengths, d_decout,
-                           d_dmask, d_xm, max_len, RD);
-        HIPCHK(e, hipGetLastError());
-        if ((rc = conv_gemm(e, tc.post_conv[0], d_xm, NMEL, d_pa, (int)RD, max_len, d_dmask, ACT_TANH, 1, d_convtmp, convtmp_n))) return rc;
-        if ((rc = conv_gemm(e, tc.post_conv[1], d_pa, 512, d_pb, (int)RD, max_len, d_dmask, ACT_TANH, 1, d_convtmp, convtmp_n))) return rc;
-        if ((rc = conv_gemm(e, tc.post_conv[2], d_pb, 512, d_pa, (int)RD, max_len, d_dmask, ACT_TANH, 1, d_convtmp, convtmp_n))) return rc;
-        if ((rc = conv_gemm(e, tc.post_conv[3], d_pa, 512, d_pb, (int)RD, max_len, d_dmask, ACT_TANH, 1, d_convtmp, convtmp_n))) return rc;
-        if ((rc = conv_gemm(e, tc.post_conv[4], d_pb, 512, d_post, (int)RD, max_len, d_dmask, ACT_NONE, 0, d_convtmp, convtmp_n))) return rc;
-        hipLaunchKernelGGL(add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_decout, d_post, d_mel, n);
-        HIPCHK(e, hipGetLastError());
-    }
+    const PostnetBufs pbufs{d_dmask, d_xm, d_pa, d_pb, d_post, d_mel, d_convtmp, convtmp_n};
+    if ((rc = postnet_residual(e, d_lengths, d_decout, B, max_len, pbufs))) return rc;
 
     // ---------------- outputs
     const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
@@ -1870,5 +1915,82 @@ extern "C" int tts_hip_encoded_free(tts_hip_engine* e, tts_hip_encoded* encoded)
     tacotron2_graphs_drop(e, encoded->buf.p);          // only the cached graphs that point into this buffer
     encoded->buf.release();                            // hipFree waits for work that still uses it
     delete encoded;
+    return TTS_HIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------- test hooks
+// Encoder up to a stop point, into the handle's own encoded batch (the one tts_hip_tacotron2_infer* re-encodes into on
+// every call): what 0 .. 2 encoder conv 1 .. 3 [B * Tin][512], 3 memory [B * Tin][enc], 4 processed memory [B * Tin][128].
+extern "C" int tts_hip_tacotron2_probe_encoder(tts_hip_engine* e, const int32_t* tokens, int B, int Tin, const float* speaker,
+                                               int what, float* out, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (!out || what < 0 || what > 4) return set_err(e, TTS_HIP_EINVAL, "tacotron2_probe_encoder: bad argument");
+    Tacotron2Dev& tc = e->taco;
+    if (!tc.enc_cache) tc.enc_cache = new (std::nothrow) tts_hip_encoded();
+    if (!tc.enc_cache) return set_err(e, TTS_HIP_ENOMEM, "out of host memory");
+    const float* src = nullptr;
+    const int rc = tacotron2_encode_impl(e, tokens, B, Tin, speaker, mem, tc.enc_cache, what <= 2 ? what : -1, &src);
+    if (rc) return rc;
+    const tts_hip_encoded* en = tc.enc_cache;
+    const int width = what <= 2 ? 512 : what == 3 ? en->enc : ATT;
+    if (what == 3) src = en->memory;
+    if (what == 4) src = en->pm;
+    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    int bl_err = 0;
+    HIPCHK(e, hipMemcpyAsync(out, src, (size_t)B * Tin * width * 4, kout, e->stream));
+    if (what >= 3) HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (bl_err) return set_err(e, TTS_HIP_EHIP, "tacotron2 encoder: BiLSTM block exchange timed out");
+    return TTS_HIP_OK;
+}
+
+// Postnet of tacotron2_decode_impl on caller frames [B][T][80] with host lengths[B] (mask t <= lengths[b]): what 0 .. 4
+// postnet conv 1 .. 5 ([B * T][512], the last [B * T][80]), 5 mel = frames + residual [B * T][80].
+extern "C" int tts_hip_tacotron2_probe_postnet(tts_hip_engine* e, const float* frames, int B, int T, const int32_t* lengths,
+                                               int what, float* out, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    Tacotron2Dev& tc = e->taco;
+    if (!tc.ready) return set_err(e, TTS_HIP_ENOTREADY, "tacotron2 weights not finalized");
+    if (!frames || !lengths || !out || B <= 0 || B > 1024 || T <= 0 || (long long)B * T > (1 << 18) || what < 0 || what > 5)
+        return set_err(e, TTS_HIP_EINVAL, "tacotron2_probe_postnet: bad argument");
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "bad mem kind %d", mem);
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const long long RD = (long long)B * T;
+    const size_t conv_rows = (size_t)std::min<long long>(RD, 32768);
+    size_t need = 0;
+    auto sz = [&](size_t n, size_t el) { need = (need + 255) / 256 * 256 + n * el; };
+    sz(B, 4); sz(RD * NMEL, 4); sz(RD, 1); sz(RD * NMEL, 4); sz(RD * 512, 4); sz(RD * 512, 4); sz(RD * NMEL, 4);
+    sz(RD * NMEL, 4); sz(5 * conv_rows * 512, 4);
+    need += 4096;
+    {
+        const void* before = tc.ws.p;
+        HIPCHK(e, tc.ws.ensure(need));
+        if (tc.ws.p != before) tacotron2_graphs_clear(e);      // cached step graphs hold pointers into the workspace
+    }
+    Arena A;
+    A.base = (char*)tc.ws.p;
+    A.cap = tc.ws.bytes;
+    int* d_lengths = A.take<int>(B);
+    float* d_frames = A.take<float>(RD * NMEL);
+    PostnetBufs pb{};
+    pb.dmask = A.take<uint8_t>(RD);
+    pb.xm = A.take<float>(RD * NMEL);
+    pb.pa = A.take<float>(RD * 512);
+    pb.pb = A.take<float>(RD * 512);
+    pb.post = A.take<float>(RD * NMEL);
+    pb.mel = A.take<float>(RD * NMEL);
+    pb.convtmp = A.take<float>(5 * conv_rows * 512);
+    pb.convtmp_n = 5 * conv_rows * 512;
+    if (A.off > A.cap) return set_err(e, TTS_HIP_ENOMEM, "tacotron2 workspace accounting error");
+    const hipMemcpyKind kin = mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    HIPCHK(e, hipMemcpyAsync(d_lengths, lengths, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(d_frames, frames, (size_t)RD * NMEL * 4, kin, st));
+    const float* src = pb.mel;
+    if (int rc = postnet_residual(e, d_lengths, d_frames, B, T, pb, what <= 4 ? what : -1, &src)) return rc;
+    const int width = what <= 3 ? 512 : NMEL;
+    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    HIPCHK(e, hipMemcpyAsync(out, src, (size_t)RD * width * 4, kout, st));
+    HIPCHK(e, hipStreamSynchronize(st));
     return TTS_HIP_OK;
 }

@@ -428,6 +428,52 @@ class HipEngine:
         """How the last `tacotron2_infer` call ran its loop: 'fused', 'persistent', 'graph', or 'none' before the first call."""
         return {2: 'fused', 1: 'persistent', 0: 'graph'}.get(self._lib.tts_hip_last_decoder_mode(self._h), 'none')
 
+    def tacotron2_probe_encoder(self, tokens, speaker=None, what: str = 'memory'):
+        """Test hook (tts_hip_tacotron2_probe_encoder): run the encoder of `tacotron2_infer` on tokens [B, Tin] up to a stop
+        point and return what it computed there: what='conv1' / 'conv2' / 'conv3' an encoder conv's output [B, Tin, 512]
+        (padded positions stored as 0), 'memory' [B, Tin, enc], 'processed_memory' [B, Tin, 128]."""
+        whats = {'conv1': 0, 'conv2': 1, 'conv3': 2, 'memory': 3, 'processed_memory': 4}
+        if what not in whats:
+            raise ValueError(f'what must be one of {tuple(whats)}, got {what!r}')
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        if tok.ndim != 2:
+            raise ValueError(f'tokens must be [B, Tin], got {tok.shape}')
+        B, Tin = tok.shape
+        spk = None if speaker is None else np.ascontiguousarray(speaker, dtype=np.float32)
+        width = 512 if whats[what] <= 2 else 128 if what == 'processed_memory' else 512 + (0 if spk is None else spk.shape[1])
+        out = np.empty((B, Tin, width), dtype=np.float32)
+        self._check(self._lib.tts_hip_tacotron2_probe_encoder(
+            self._h, tok.ctypes.data_as(ctypes.c_void_p), B, Tin, None if spk is None else spk.ctypes.data_as(ctypes.c_void_p),
+            whats[what], out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'tacotron2_probe_encoder')
+        return out
+
+    def tacotron2_probe_postnet(self, frames, lengths, what: str = 'mel'):
+        """Test hook (tts_hip_tacotron2_probe_postnet): run the postnet of `tacotron2_infer` on frames [B, T, 80] in place of
+        the decoder output, masked as after a loop that produced `lengths` [B] (t <= lengths[b]), up to a stop point:
+        what='conv1' .. 'conv4' [B, T, 512] (masked positions stored as 0), 'conv5' (the residual) [B, T, 80], 'mel'
+        frames + residual [B, T, 80]."""
+        whats = {'conv1': 0, 'conv2': 1, 'conv3': 2, 'conv4': 3, 'conv5': 4, 'mel': 5}
+        if what not in whats:
+            raise ValueError(f'what must be one of {tuple(whats)}, got {what!r}')
+        x = np.ascontiguousarray(frames, dtype=np.float32)
+        if x.ndim != 3 or x.shape[2] != 80:
+            raise ValueError(f'frames must be [B, T, 80], got {x.shape}')
+        B, T = x.shape[:2]
+        lens = np.ascontiguousarray(lengths, dtype=np.int32)
+        if lens.shape != (B,):
+            raise ValueError(f'lengths must be [B] = ({B},), got {lens.shape}')
+        out = np.empty((B, T, 512 if whats[what] <= 3 else 80), dtype=np.float32)
+        self._check(self._lib.tts_hip_tacotron2_probe_postnet(
+            self._h, x.ctypes.data_as(ctypes.c_void_p), B, T, lens.ctypes.data_as(ctypes.c_void_p), whats[what],
+            out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'tacotron2_probe_postnet')
+        return out
+
+    @property
+    def last_conv_paths(self) -> int:
+        """Bitmask of how each k = 5 conv last ran on this handle (tts_hip_last_conv_paths): bit i set = single pass, clear =
+        split per tap; bits 0 - 2 encoder convs 1 - 3, bits 3 - 7 postnet convs 1 - 5; -1 before the first conv."""
+        return int(self._lib.tts_hip_last_conv_paths(self._h))
+
     def set_waveglow_form(self, form: str) -> None:
         """How the fp32 vocoder evaluates the dilated convolutions of WN layers 1 - 7: 'winograd' (default: minimal filtering
         along the tap axis, F(4,3), for calls of 144 frames or more) or 'direct' (always three taps).  Both are fp32; they differ by rounding only."""
