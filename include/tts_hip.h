@@ -171,7 +171,8 @@ int tts_hip_set_decoder_mode(tts_hip_engine* e, int mode);
  * (also after a fallback), -1 before the first call.                                                                          */
 int tts_hip_last_decoder_mode(const tts_hip_engine* e);
 
-/* Test hooks of the encoder and postnet convolutions (used by tests/ only; no effect on later calls).  Both run the code of
+/* Test hooks of the encoder and postnet convolutions (no effect on later calls; used by tests/, and probe_postnet what 5 by
+ * `predict(batch_backlog=...)` to give a row cut at its own frame cap the postnet of its own frames).  Both run the code of
  * tts_hip_tacotron2_infer, not a copy, up to a stop point and copy what it computed there to `out` (fp32):
  * probe_encoder: the encoder of `tokens` [B, Tin] (+ speaker, as tts_hip_tacotron2_encode; B <= 1024, Tin <= 4096) --
  *   what 0 .. 2: output of encoder conv 1 .. 3 (MaskedConv1D -> BN -> relu), [B, Tin, 512], padded positions stored as 0;
@@ -224,6 +225,25 @@ int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, co
  * residual GEMMs: 3 64-row tiles (64 x 128), 2 128 x 64 tiles, 1 128-row tiles, 0 256-row tiles (fp16: 256 x 256), -1 before
  * the first call.  Split fp16 (f16x3) has two families only: 3 and 0.                                                    */
 int tts_hip_last_waveglow_tiles(const tts_hip_engine* e);
+
+/* ---- WaveGlow.infer on a batch of unequal rows
+ * mel [B, T, 80], z NULL or [B, T*32, 8], audio [B, T*256] as above; row b holds lengths[b] (0 <= lengths[b] <= T) real
+ * frames, lengths NULL = T for every row: then the call IS tts_hip_waveglow_infer* / _async (same kernels, same launches,
+ * bit-equal audio).  With lengths, in every precision (0 f32 in the form tts_hip_set_waveglow_form selects, 1 f16, 2 f16x3)
+ * and every tile family:
+ *   - audio[b, :lengths[b]*256] is what a one-row call on mel[b, :lengths[b]], z[b, :lengths[b]*32] returns, up to the fp32
+ *     re-association that already separates tile families and forms (a padded row of the calls above is NOT: its WN
+ *     convolutions read the padding where the row alone reads zeros, 3e-2 .. 5e-2 RMS on the row's samples);
+ *   - audio[b, lengths[b]*256:] = 0 exactly;
+ *   - nothing read beyond a row's length: mel[b, lengths[b]:] and z[b, lengths[b]*32:] may hold anything, NaN and Inf
+ *     included (e.g. uninitialised padding), and two calls that differ only there return bit-equal audio.
+ * `lengths` is host memory in every mode (read during the call); mel, z and audio follow `mem` / live on the device for
+ * the _async form, which enqueues on `stream` and returns without synchronizing like tts_hip_waveglow_infer_async.  The
+ * B * T limits of the calls above hold (T is what counts, not the lengths: tail frames still occupy rows of the GEMMs).  */
+int tts_hip_waveglow_infer_ragged(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths, const float* z,
+                                  float sigma, float* audio, int precision, int mem);
+int tts_hip_waveglow_infer_ragged_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
+                                        const float* z, float sigma, float* audio, int precision, void* stream);
 
 /* ---- TacotronSTFT.mel_spectrogram  (utils/audio/stft.py:242-274,306-314)
  * audio [B, N] (N >= 1024) -> mel [B, N/256 + 1, 80]                                                                */

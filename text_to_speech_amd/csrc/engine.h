@@ -76,6 +76,8 @@ struct WaveGlowDev {
     float* probe_out = nullptr;              //   state [B][T * 32][n] to this device buffer
     bool wino_ready = false;                 // Winograd form of the fp32 in-layer GEMM (wn_wino.hip)
     bool wino_legacy_ready = false;          //   ... and the three-pass form's extra weight copies
+    DevBuf mel_ragged, ragged_info;          // ragged calls: mel copy with cleared tails; [lengths | tail frame list] int32
+    std::vector<int> ragged_info_h;          //   ... and its host image (staged to the device once per call)
     DevBuf wino_U, wino_P, wino_mel;         // mel planes; forms 2 / 3 only: transformed inputs [6][M/4][512], products [6][M/4][1024]
 };
 
@@ -236,8 +238,9 @@ void timing_collect(tts_hip_engine* e);
 
 // model entry points (device pointers only)
 int waveglow_finalize(tts_hip_engine* e);
+// d_lens (device int32 [B], null = every row holds T frames), d_tail / n_tail: the frames beyond the rows' lengths
 int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const float* d_z, float sigma, float* d_audio,
-                 int precision);
+                 int precision, const int* d_lens = nullptr, const int* d_tail = nullptr, int n_tail = 0);
 void waveglow_free(tts_hip_engine* e);
 
 int tacotron2_finalize(tts_hip_engine* e);

@@ -294,8 +294,53 @@ int tts_hip_has_model(const tts_hip_engine* e, const char* model) {
     return 0;
 }
 
+constexpr int kMaxFramesPerRun = 31744;      // one waveglow_run addresses its activations with 31-bit byte offsets
+
+// Ragged calls: checks `lengths` (host int32 [B], each in [0, T]) and stages [lengths | tail frames] to the device on the
+// current stream, once per call.  The tail frames (b - b0) * T + t, t >= lengths[b], are listed run by run (b0 = first row
+// of the run of `chunkB` rows that holds row b), so that each run finds its own as one contiguous slice.
+static int stage_ragged(tts_hip_engine* e, int B, int T, const int32_t* lengths, int chunkB, const char* who) {
+    long long n_tail = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths[b] < 0 || lengths[b] > T)
+            return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d is outside [0, T = %d]", who, b, (int)lengths[b], T);
+        n_tail += T - lengths[b];
+    }
+    std::vector<int>& h = e->wg.ragged_info_h;
+    h.resize((size_t)B + (size_t)n_tail);
+    size_t at = (size_t)B;
+    for (int b = 0; b < B; ++b) {
+        h[b] = lengths[b];
+        for (int t = lengths[b]; t < T; ++t) h[at++] = (b % chunkB) * T + t;
+    }
+    HIPCHK(e, e->wg.ragged_info.ensure(h.size() * sizeof(int)));
+    // (pageable source: the copy has left `h` when the call returns, so the next call may rebuild it)
+    HIPCHK(e, hipMemcpyAsync(e->wg.ragged_info.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    return TTS_HIP_OK;
+}
+
+// runs of whole utterances, each within kMaxFramesPerRun frames; lengths != NULL: staged by stage_ragged with the same chunkB
+static int waveglow_run_chunks(tts_hip_engine* e, const float* d_mel, int B, int T, const int32_t* lengths, const float* d_z,
+                               float sigma, float* d_out, int precision) {
+    const int chunkB = kMaxFramesPerRun / T;
+    const int* d_info = (const int*)e->wg.ragged_info.p;
+    size_t tail_at = (size_t)B;
+    for (int b0 = 0; b0 < B; b0 += chunkB) {
+        const int nb = B - b0 < chunkB ? B - b0 : chunkB;
+        int n_tail = 0;
+        if (lengths)
+            for (int b = b0; b < b0 + nb; ++b) n_tail += T - lengths[b];
+        int rc = waveglow_run(e, d_mel + (size_t)b0 * T * 80, nb, T, d_z ? d_z + (size_t)b0 * T * 32 * 8 : nullptr, sigma,
+                              d_out + (size_t)b0 * T * 256, precision, lengths ? d_info + b0 : nullptr,
+                              lengths ? d_info + tail_at : nullptr, n_tail);
+        if (rc) return rc;
+        tail_at += (size_t)n_tail;
+    }
+    return TTS_HIP_OK;
+}
+
 static int waveglow_infer_impl(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
-                               float* audio, int mem, int precision) {
+                               float* audio, int mem, int precision, const int32_t* lengths = nullptr) {
     if (!e) return TTS_HIP_EINVAL;
     if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
     if (!mel || !audio || B <= 0 || T <= 0) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: bad argument");
@@ -322,17 +367,14 @@ static int waveglow_infer_impl(tts_hip_engine* e, const float* mel, int B, int T
     // One run addresses its activations with 31-bit byte offsets (<= ~32 k frames).  Utterances are independent, so a
     // larger batch is processed in slices of whole utterances; a single utterance above the limit is refused (the Python
     // wrapper's windowed inference, models/tts/waveglow.py:114-142, is the reference's own answer to long mels).
-    constexpr int kMaxFramesPerRun = 31744;
     if (T > kMaxFramesPerRun)
         return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: T = %d frames exceeds one run's limit (%d); use windowed inference",
                        T, kMaxFramesPerRun);
-    const int chunkB = kMaxFramesPerRun / T;
-    for (int b0 = 0; b0 < B; b0 += chunkB) {
-        const int nb = B - b0 < chunkB ? B - b0 : chunkB;
-        int rc = waveglow_run(e, d_mel + (size_t)b0 * T * 80, nb, T, d_z ? d_z + (size_t)b0 * T * 32 * 8 : nullptr, sigma,
-                              d_out + (size_t)b0 * T * 256, precision);
+    if (lengths) {
+        int rc = stage_ragged(e, B, T, lengths, kMaxFramesPerRun / T, "waveglow_infer_ragged");
         if (rc) return rc;
     }
+    if (int rc = waveglow_run_chunks(e, d_mel, B, T, lengths, d_z, sigma, d_out, precision)) return rc;
     if (mem == TTS_HIP_MEM_HOST)
         HIPCHK(e, hipMemcpyAsync(audio, d_out, n_out * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -443,24 +485,34 @@ int tts_hip_waveglow_infer_seeded(tts_hip_engine* e, const float* mel, int B, in
 // Device-pointer variants on a caller stream: enqueue and return (no synchronization).  Same arithmetic as the calls above.
 int tts_hip_waveglow_infer_async(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
                                  float* audio, int precision, void* stream) {
+    return tts_hip_waveglow_infer_ragged_async(e, mel, B, T, nullptr, z, sigma, audio, precision, stream);
+}
+
+// WaveGlow.infer on a batch of unequal rows: lengths[b] frames of row b are real (NULL: the calls above, launch for launch).
+int tts_hip_waveglow_infer_ragged(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths, const float* z,
+                                  float sigma, float* audio, int precision, int mem) {
     if (!e) return TTS_HIP_EINVAL;
-    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_async: precision must be 0 (f32), 1 (f16) or 2 (f16x3)");
+    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_ragged: precision must be 0 (f32), 1 (f16) or 2 (f16x3)");
+    return waveglow_infer_impl(e, mel, B, T, z, sigma, audio, mem, precision, lengths);
+}
+
+int tts_hip_waveglow_infer_ragged_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
+                                        const float* z, float sigma, float* audio, int precision, void* stream) {
+    const char* who = lengths ? "waveglow_infer_ragged_async" : "waveglow_infer_async";
+    if (!e) return TTS_HIP_EINVAL;
+    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "%s: precision must be 0 (f32), 1 (f16) or 2 (f16x3)", who);
     if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
-    if (!mel || !audio || B <= 0 || T <= 0) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_async: bad argument");
-    constexpr int kMaxFramesPerRun = 31744;
+    if (!mel || !audio || B <= 0 || T <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", who);
     if (T > kMaxFramesPerRun)
-        return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_async: T = %d frames exceeds one run's limit (%d); use windowed inference",
-                       T, kMaxFramesPerRun);
+        return set_err(e, TTS_HIP_EINVAL, "%s: T = %d frames exceeds one run's limit (%d); use windowed inference", who, T,
+                       kMaxFramesPerRun);
     HIPCHK(e, hipSetDevice(e->device));
     StreamScope scope(e, stream);
-    const int chunkB = kMaxFramesPerRun / T;
-    for (int b0 = 0; b0 < B; b0 += chunkB) {
-        const int nb = B - b0 < chunkB ? B - b0 : chunkB;
-        int rc = waveglow_run(e, mel + (size_t)b0 * T * 80, nb, T, z ? z + (size_t)b0 * T * 32 * 8 : nullptr, sigma,
-                              audio + (size_t)b0 * T * 256, precision);
+    if (lengths) {
+        int rc = stage_ragged(e, B, T, lengths, kMaxFramesPerRun / T, who);
         if (rc) return rc;
     }
-    return TTS_HIP_OK;
+    return waveglow_run_chunks(e, mel, B, T, lengths, z, sigma, audio, precision);
 }
 
 int tts_hip_mel_stft_async(tts_hip_engine* e, const float* audio, int B, int N, float* mel, void* stream) {

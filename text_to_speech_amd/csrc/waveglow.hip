@@ -177,13 +177,21 @@ __global__ void probe_state_kernel(const float* __restrict__ audio, int natural,
     for (int j = 0; j < n; ++j) out[pos * n + j] = audio[row * 8 + j];
 }
 
+// Ragged calls (tts_hip_waveglow_infer_ragged): row b = f / T holds lens[b] real frames; frame f is real when f % T < lens[b]
+__device__ __forceinline__ bool frame_is_real(const int* __restrict__ lens, int f, int T) { return f % T < lens[f / T]; }
+
 // audio[m'][0..3] = sigma * z[natural m][0..3]  (z null => zeros); m' = p * PR + f  <->  m = f * 32 + p
-__global__ void init_audio_kernel(const float* __restrict__ z, float sigma, float* __restrict__ audio, int PR, int BT) {
+// RAGGED: frames beyond their row's length start at 0 whatever the caller's z holds there (it is not read)
+template <bool RAGGED = false>
+__global__ void init_audio_kernel(const float* __restrict__ z, float sigma, float* __restrict__ audio, int PR, int BT,
+                                  const int* __restrict__ lens = nullptr, int T = 1) {
     const long long mp = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (mp >= (long long)NPH * PR) return;
     const int p = (int)(mp / PR), f = (int)(mp % PR);
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (z && f < BT) {
+    bool real = z && f < BT;
+    if constexpr (RAGGED) real = real && frame_is_real(lens, f, T);
+    if (real) {
         v = *reinterpret_cast<const f32x4*>(z + ((long long)f * NPH + p) * 8);
         v *= sigma;
     }
@@ -192,12 +200,53 @@ __global__ void init_audio_kernel(const float* __restrict__ z, float sigma, floa
     *reinterpret_cast<f32x4*>(audio + mp * 8 + 4) = zero;
 }
 
+// Ragged calls: private copy of the mel with every frame beyond its row's length cleared.  Every later reader (the direct
+// form's conditioning segments, the Winograd mel planes, the fp16 mel windows) takes this copy, so no caller tail value --
+// NaN included -- enters a kernel that combines neighbouring frames.  One float4 per thread; tail frames are not read.
+__global__ void mel_ragged_copy_kernel(const float* __restrict__ mel, float* __restrict__ dst, const int* __restrict__ lens,
+                                       int BT, int T) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)BT * 20) return;
+    const int f = (int)(i / 20);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (frame_is_real(lens, f, T)) v = *reinterpret_cast<const f32x4*>(mel + i * 4);
+    *reinterpret_cast<f32x4*>(dst + i * 4) = v;
+}
+
+// Ragged calls: stores 0 over the rows of the residual stream that lie beyond their utterance's length -- after the start
+// conv (then also the a0p rows, constant-1 column included: a tail row must look like the zero padding a run of the row
+// alone has there) and after every residual GEMM.  `tail` lists the n_tail frames f = b * T + t with t >= lens[b]; their
+// 32 phase rows are p * PR + f.  One float4 of one row per thread: only tail bytes are touched.
+// x16 (fp16 modes, else null): the shadow of x, `planes` planes M * C halfs apart; a0p (null after a residual GEMM):
+// 16 floats per row, or `planes` planes of 32 halfs per row when x16 is given.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+__global__ void wn_zero_tail_kernel(const int* __restrict__ tail, int n_tail, int PR, long long M, float* __restrict__ x,
+                                    _Float16* __restrict__ x16, int planes, void* __restrict__ a0p) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long r = idx / (C / 4);
+    if (r >= (long long)NPH * n_tail) return;
+    const int c = (int)(idx % (C / 4)) * 4;
+    const long long m = (r / n_tail) * PR + tail[r % n_tail];
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const f16x4 zeroh = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+    *reinterpret_cast<f32x4*>(x + m * C + c) = zero;
+    if (x16)
+        for (int pl = 0; pl < planes; ++pl) *reinterpret_cast<f16x4*>(x16 + pl * M * C + m * C + c) = zeroh;
+    if (a0p) {
+        if (x16) {
+            if (c < 32)
+                for (int pl = 0; pl < planes; ++pl) *reinterpret_cast<f16x4*>((_Float16*)a0p + pl * M * 32 + m * 32 + c) = zeroh;
+        } else if (c < 16) {
+            *reinterpret_cast<f32x4*>((float*)a0p + m * 16 + c) = zero;
+        }
+    }
+}
+
 // x[m][c] = sum_{j < h} audio[m][j] * w[j][c] + b[c]      (start 1x1 conv, waveglow_arch.py:108)
 // Also writes a0p[m][..] = [audio_0 (h values) | 1 | 0 ...]: the operand of the first WN layer, whose dilated conv is
 // composed with the start conv at load time (the constant 1 carries the start bias through the zero padding).
 // HALF: x stays fp32 (master copy for the residual accumulation) and additionally gets an fp16 shadow x16 (the GEMM
 // operand); a0p is written as 32 halfs per row.
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 template <bool HALF>
 __global__ void wn_start_kernel(const float* __restrict__ audio, const float* __restrict__ w,
                                 const float* __restrict__ b, float* __restrict__ x, void* __restrict__ a0p_v,
@@ -254,7 +303,9 @@ __global__ void wn_start_kernel(const float* __restrict__ audio, const float* __
 // Lane l owns channels 4l..4l+3 and 256+4l..256+4l+3 (every wave-level load is one contiguous 1 KiB run); per layer
 // the lane's 8x8 slice of wfold sits in registers and is reused for the RPW rows; the RPW*8 partial sums are reduced with the lane-halving exchange (63 shuffles for 64 values).
 constexpr int RPW = 8;
-template <bool HALF, bool SPLIT = false>
+// RAGGED: positions beyond their row's length store 0 -- the flow state stays 0 there from flow to flow and the last flow
+// gives the zero tail of the output -- and the caller's z is not read there.
+template <bool HALF, bool SPLIT = false, bool RAGGED = false>
 __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict__ acts_v, long long layer_stride,
                                                           const float* __restrict__ wfold,
                                                           const float* __restrict__ bfold,
@@ -262,7 +313,8 @@ __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict
                                                           float* __restrict__ audio_out, int out_natural,
                                                           const float* __restrict__ z, int zoff, int n_early,
                                                           float sigma, long long M, int h, int PR, int BT,
-                                                          long long lo_plane = 0) {
+                                                          long long lo_plane = 0,
+                                                          const int* __restrict__ lens = nullptr, int T = 1) {
     // lo_plane != 0 (split-fp16 mode): activation = hi + lo, lo at + lo_plane halfs
     // fp16 variants: the folded weights of a layer ([8 outputs][512]: 16 KB, the same for every wave) are staged in LDS once
     // per block and layer (double buffered; the next layer's rows are requested before this layer's arithmetic).  With
@@ -376,6 +428,13 @@ __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict
     const int ph = (int)(m / PR), fr = (int)(m % PR);          // phase-major row -> (phase, frame)
     const long long mnat = (long long)fr * NPH + ph;           // natural position index b * L + t * 32 + p
     if ((lane & 7) == 0 && m < M && fr < BT) {
+        if constexpr (RAGGED) {
+            if (!frame_is_real(lens, fr, T)) {
+                float* dst = audio_out + (out_natural ? mnat : m) * 8;
+                for (int j = 0; j < n_early + cch; ++j) dst[j] = 0.f;
+                return;
+            }
+        }
         float a[8], y[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) a[j] = j < cch ? audio_io[m * 8 + j] : 0.f;
@@ -432,6 +491,8 @@ void waveglow_free(tts_hip_engine* e) {
     e->wg.io_mel.release();
     e->wg.io_z.release();
     e->wg.io_out.release();
+    e->wg.mel_ragged.release();
+    e->wg.ragged_info.release();
     e->wg.ready = false;
 }
 
@@ -749,9 +810,15 @@ static int waveglow_build_x3(tts_hip_engine* e) {
 // accumulation and fp32 epilogue math, fp32 master copy of the residual stream and of the flow state.  precision 2: split
 // fp16 -- every GEMM operand is a pair of fp16 planes (hi, lo), three MFMAs per product (hi*hi + hi*lo + lo*hi), fp32
 // accumulation: ~22 operand bits, i.e. fp32-class results at 3/16 of the fp32 MFMA cost.
+// Ragged calls (d_lens != null): d_lens [B] frames of each row are real, d_tail lists the n_tail frames b * T + t beyond them.
+// x is kept at 0 on those rows wherever it is written; the transposed-conv upsampling is causal (a sample only sees mel
+// frames at or before its own), so the residual stream is the only way a row's tail could reach its real positions, and
+// a row then computes what a call on its own frames computes.  d_lens == null: the launches below
+// are exactly those of a call without lengths.
 int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const float* d_z, float sigma, float* d_audio,
-                 int precision) {
+                 int precision, const int* d_lens, const int* d_tail, int n_tail) {
     WaveGlowDev& wg = e->wg;
+    const bool ragged = d_lens != nullptr;
     const bool half = precision == 1;
     const bool x3 = precision == 2;
     if (half) {
@@ -803,6 +870,25 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         HIPCHK(e, wg.a0p.ensure((size_t)M * 16 * 4));
     }
     hipStream_t st = e->stream;
+    if (ragged) {                                                // every reader below takes the copy with cleared tails
+        HIPCHK(e, wg.mel_ragged.ensure((size_t)BT * 80 * 4));
+        const long long n4 = (long long)BT * 20;
+        hipLaunchKernelGGL(mel_ragged_copy_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, d_mel,
+                           wg.mel_ragged.f(), d_lens, BT, T);
+        HIPCHK(e, hipGetLastError());
+        d_mel = wg.mel_ragged.f();
+    }
+    // x (and its fp16 shadow; after the start conv also the a0p rows) = 0 on the tail rows: store-only, tail bytes only
+    auto zero_tail = [&](bool with_a0p) -> int {
+        if (!ragged || n_tail == 0) return TTS_HIP_OK;
+        const long long n4 = (long long)NPH * n_tail * (C / 4);
+        const bool h16 = precision != 0;
+        hipLaunchKernelGGL(wn_zero_tail_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, d_tail, n_tail, PR, M,
+                           wg.x.f(), h16 ? (_Float16*)wg.x16.p : (_Float16*)nullptr, precision == 2 ? 2 : 1,
+                           with_a0p ? (h16 ? wg.a0p16.p : wg.a0p.p) : nullptr);
+        HIPCHK(e, hipGetLastError());
+        return TTS_HIP_OK;
+    };
     // fp32 path, 128- / 256-row tiles: layers 1 .. 7 of a flow run in their Winograd form (wn_wino.hip)
     bool wino = wino_size && (!row64 || wg.form_mode != 2);               // (PR is a multiple of 64; form 2: of 128)
     if (wino) {
@@ -832,7 +918,10 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
     _Float16* mel16 = (_Float16*)wg.mel16.p;
 
     const unsigned mb = (unsigned)((M + 255) / 256);
-    hipLaunchKernelGGL(init_audio_kernel, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT);
+    if (ragged)
+        hipLaunchKernelGGL(init_audio_kernel<true>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, d_lens, T);
+    else
+        hipLaunchKernelGGL(init_audio_kernel<false>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, (const int*)nullptr, 1);
     if (half || x3) {
         const long long n = (long long)BT * KMEL;
         hipLaunchKernelGGL(mel_window_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_mel, mel16,
@@ -854,6 +943,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
                 hipLaunchKernelGGL(wn_start_kernel<false>, grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
                                    wg.x.f(), wg.a0p.p, (_Float16*)nullptr, M, h);
             HIPCHK(e, hipGetLastError());
+            if (int rc = zero_tail(true)) return rc;
         }
         for (int i = 0; i < 8; ++i) {
             const WgLayerDev& ly = fl.layer[i];
@@ -924,6 +1014,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
                     timing_begin(e, 1);
                     HIPCHK(e, row64 ? gemm_wn_res_r64(r, st) : tile64 ? gemm_wn_res_64(r, st) : gemm_wn_res_skip(r, st));
                     timing_end(e);
+                    if (int rc = zero_tail(false)) return rc;
                 }
             } else {
                 // fp16 operands, described in float units (one unit = 2 halfs): ld / k / kpad / ldb are halved.  Split mode:
@@ -997,6 +1088,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
                     if (x3) HIPCHK(e, gemm_wn_res_x3(r, row64, st));
                     else HIPCHK(e, row64 ? gemm_wn_res_r64h(r, st) : tile64 ? gemm_wn_res_64h(r, st) : gemm_wn_res_h(r, st));
                     timing_end(e);
+                    if (int rc = zero_tail(false)) return rc;
                 }
             }
         }
@@ -1004,7 +1096,20 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         float* dst = (k == 0) ? d_audio : wg.audio.f();
         const long long waves = (M + RPW - 1) / RPW;
         const dim3 grid((unsigned)((waves + 3) / 4));
-        if (x3)
+        if (ragged) {
+            if (x3)
+                hipLaunchKernelGGL((wn_end_fold_kernel<true, true, true>), grid, dim3(256), 0, st, (const void*)acts16,
+                                   (long long)NP * M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
+                                   zoff, early ? 2 : 0, sigma, M, h, PR, BT, (long long)M * C, d_lens, T);
+            else if (half)
+                hipLaunchKernelGGL((wn_end_fold_kernel<true, false, true>), grid, dim3(256), 0, st, (const void*)acts16,
+                                   (long long)M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
+                                   zoff, early ? 2 : 0, sigma, M, h, PR, BT, 0ll, d_lens, T);
+            else
+                hipLaunchKernelGGL((wn_end_fold_kernel<false, false, true>), grid, dim3(256), 0, st, (const void*)wg.acts.p,
+                                   (long long)M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
+                                   zoff, early ? 2 : 0, sigma, M, h, PR, BT, 0ll, d_lens, T);
+        } else if (x3)
             hipLaunchKernelGGL((wn_end_fold_kernel<true, true>), grid, dim3(256), 0, st, (const void*)acts16,
                                (long long)NP * M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
                                zoff, early ? 2 : 0, sigma, M, h, PR, BT, (long long)M * C);

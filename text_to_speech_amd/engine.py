@@ -164,13 +164,32 @@ class HipEngine:
         return bool(self._lib.tts_hip_has_model(self._h, model.encode()))
 
     # ------------------------------------------------------------------ WaveGlow
-    def waveglow_infer(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', stream=None, seed=None, offset: int = 0):
+    @staticmethod
+    def _frame_lengths(lengths, B, T):
+        """`lengths` (any int sequence / array / tensor) as a contiguous host int32 [B] with every entry in [0, T]."""
+        if hasattr(lengths, 'detach'):
+            lengths = lengths.detach().cpu().numpy()
+        arr = np.asarray(lengths)
+        if arr.shape != (B,):
+            raise ValueError(f'lengths must hold one frame count per row, shape ({B},), got {arr.shape}')
+        if arr.dtype.kind not in 'iu':
+            raise ValueError(f'lengths must be integers, got dtype {arr.dtype}')
+        if arr.size and (int(arr.min()) < 0 or int(arr.max()) > T):
+            raise ValueError(f'lengths must lie in [0, T = {T}], got {arr.tolist()}')
+        return np.ascontiguousarray(arr, dtype=np.int32)
+
+    def waveglow_infer(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', stream=None, seed=None, offset: int = 0,
+                       lengths=None):
         """mel [B, T, 80] (+ optional z [B, T*32, 8]) -> audio [B, T*256].  precision: 'f32' (exact fp32 MFMA), 'f16x3'
         (split fp16: fp32-class accuracy, ~3x faster) or 'f16' (fp16 operands).  `seed` (with z=None): the noise is drawn
         on the device from (seed, offset) -- the reference's default `z=None, deterministic=False`
         (waveglow_arch.py:272-274,299-302) without a host-made tensor crossing PCIe; z=None and seed=None: zeros
         (`deterministic=True`).  `stream` (a torch.cuda.Stream, device tensors only): enqueue on that stream and return
-        without waiting (tts_hip_waveglow_infer_async)."""
+        without waiting (tts_hip_waveglow_infer_async).
+        `lengths` [B] (ints in [0, T]; brought to host int32): a batch of unequal rows (tts_hip_waveglow_infer_ragged) --
+        audio[b, :lengths[b] * 256] is what row b's own frames give in a call of their own, audio[b, lengths[b] * 256:] is 0,
+        and mel / z beyond a row's length are never read (they may be uninitialised).  With `seed` the noise is drawn in the
+        batch layout [B, T*32, 8] as without lengths."""
         fns = {'f32': self._lib.tts_hip_waveglow_infer, 'f16': self._lib.tts_hip_waveglow_infer_f16,
                'f16x3': self._lib.tts_hip_waveglow_infer_f16x3}
         if precision not in fns:
@@ -188,6 +207,8 @@ class HipEngine:
             if z is not None and tuple(z.shape) != (B, T * 32, 8):
                 raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {tuple(z.shape)}')
             self._check_device(mel, z)
+            lens = None if lengths is None else self._frame_lengths(lengths, B, T)
+            lens_p = None if lens is None else lens.ctypes.data_as(ctypes.c_void_p)
 
             def prepared():
                 m = mel.to(torch.float32).contiguous()
@@ -203,13 +224,29 @@ class HipEngine:
                                                                   ctypes.c_void_p(zz.data_ptr()), zz.numel(),
                                                                   ctypes.c_void_p(int(stream.cuda_stream))), 'random_fill')
                 self._used_on(stream, mel, z, m, zz, out)
+                if lens is not None:
+                    self._check(self._lib.tts_hip_waveglow_infer_ragged_async(
+                        self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p,
+                        None if zz is None else ctypes.c_void_p(zz.data_ptr()), float(sigma), ctypes.c_void_p(out.data_ptr()),
+                        pcode, ctypes.c_void_p(int(stream.cuda_stream))), 'waveglow_infer_ragged_async')
+                    return out
                 self._check(self._lib.tts_hip_waveglow_infer_async(
                     self._h, ctypes.c_void_p(m.data_ptr()), B, T, None if zz is None else ctypes.c_void_p(zz.data_ptr()),
                     float(sigma), ctypes.c_void_p(out.data_ptr()), pcode, ctypes.c_void_p(int(stream.cuda_stream))),
                     'waveglow_infer_async')
                 return out
             m, zz, out = prepared()
+            if lens is not None and zz is None and seed is not None:
+                zz = torch.empty((B, T * 32, 8), dtype=torch.float32, device=mel.device)
             self._order_after_torch()
+            if lens is not None:
+                if z is None and seed is not None:       # drawn on the engine's stream, ahead of the call that reads it
+                    self._check(self._lib.tts_hip_random_fill(self._h, 0, u64(seed), u64(offset),
+                                                              ctypes.c_void_p(zz.data_ptr()), zz.numel(), None), 'random_fill')
+                self._check(self._lib.tts_hip_waveglow_infer_ragged(
+                    self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p, None if zz is None else ctypes.c_void_p(zz.data_ptr()),
+                    float(sigma), ctypes.c_void_p(out.data_ptr()), pcode, MEM_DEVICE), 'waveglow_infer_ragged')
+                return out
             if zz is None and seed is not None:
                 self._check(self._lib.tts_hip_waveglow_infer_seeded(
                     self._h, ctypes.c_void_p(m.data_ptr()), B, T, u64(seed), u64(offset), float(sigma),
@@ -224,13 +261,25 @@ class HipEngine:
         if mel.ndim != 3 or mel.shape[2] != 80:
             raise ValueError(f'mel must be [B, T, 80], got {mel.shape}')
         B, T = mel.shape[:2]
+        lens = None if lengths is None else self._frame_lengths(lengths, B, T)
         zp = None
         if z is not None:
             z = np.ascontiguousarray(z, dtype=np.float32)
             if z.shape != (B, T * 32, 8):
                 raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {z.shape}')
             zp = z.ctypes.data_as(ctypes.c_void_p)
+        if lens is not None and zp is None and seed is not None:
+            # the noise lives on the device: the mel joins it there (80 floats a frame against the noise's 256)
+            torch = self._torch()
+            dmel = torch.as_tensor(mel, device=torch.device('cuda', self.device))
+            return self.waveglow_infer(dmel, sigma=sigma, precision=precision, seed=seed, offset=offset,
+                                       lengths=lens).cpu().numpy()
         out = np.empty((B, T * 256), dtype=np.float32)
+        if lens is not None:
+            self._check(self._lib.tts_hip_waveglow_infer_ragged(
+                self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, lens.ctypes.data_as(ctypes.c_void_p), zp, float(sigma),
+                out.ctypes.data_as(ctypes.c_void_p), pcode, MEM_HOST), 'waveglow_infer_ragged')
+            return out
         if zp is None and seed is not None:
             self._check(self._lib.tts_hip_waveglow_infer_seeded(
                 self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, u64(seed), u64(offset), float(sigma),
@@ -467,6 +516,12 @@ class HipEngine:
             self._h, x.ctypes.data_as(ctypes.c_void_p), B, T, lens.ctypes.data_as(ctypes.c_void_p), whats[what],
             out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'tacotron2_probe_postnet')
         return out
+
+    def tacotron2_postnet(self, frames, lengths):
+        """Postnet + residual of `tacotron2_infer` on decoder frames [B, T, 80] whose rows end at index lengths[b] (mask
+        t <= lengths[b]) -> mel [B, T, 80].  `predict(batch_backlog=...)` uses it for a row of a token batch that is cut at the
+        frame cap it would have had alone: the batch's own postnet saw the frames behind the cut."""
+        return self.tacotron2_probe_postnet(frames, lengths, what='mel')
 
     @property
     def last_conv_paths(self) -> int:

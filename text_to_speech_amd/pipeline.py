@@ -32,8 +32,11 @@ class TTSPipeline:
 
     def synthesize_tokens(self, tokens, speaker=None, max_length=10.0, deterministic=False, prenet_masks=None, z=None,
                           sigma=1.0, early_stopping=True, round_frames_to=8, on_device=False, reduce_noise=False,
-                          trim_silence=False):
+                          trim_silence=False, ragged=False):
         """tokens int32 [B, Tin] (0 = pad) -> (list of B float32 waveforms, lengths [B] in frames, steps run).
+        `ragged`: the decoder's lengths go to the vocoder (HipEngine.waveglow_infer(lengths=...)) instead of a -11 fill, so
+        every waveform is what its sentence gives when vocoded alone; False (default): the reference's batched path, where
+        the rows shorter than the longest hear the padding in their last ~96 frames.
         `on_device`: nothing is copied to the host -- returns (audio [B, S] float32 device tensor, zero beyond each row's
         samples, sample counts [B] int64 device tensor, steps run).
         `reduce_noise` / `trim_silence`: the reference's waveform clean-up (audio_processing.reduce_noise, trim_silence with
@@ -71,16 +74,20 @@ class TTSPipeline:
         if round_frames_to > 1:                         # keeps the WaveGlow workspace sizes (and M tiles) stable
             T = min(max_len, (T + round_frames_to - 1) // round_frames_to * round_frames_to)
         mel = out.mel[:, :T].clone()
-        valid = torch.arange(T, device=dev)[None, :] < lengths[:, None]
-        mel = torch.where(valid[:, :, None], mel, torch.full_like(mel, PAD_MEL_VALUE))
+        voc = {}
+        if ragged:                                      # frames beyond a row's length are never read: no fill
+            voc['lengths'] = lengths.to(torch.int32).cpu().numpy()
+        else:
+            valid = torch.arange(T, device=dev)[None, :] < lengths[:, None]
+            mel = torch.where(valid[:, :, None], mel, torch.full_like(mel, PAD_MEL_VALUE))
         if z is None and not deterministic:
             audio = eng.waveglow_infer(mel.contiguous(), sigma=sigma, precision=self.vocoder_precision, seed=self._seed,
-                                       offset=self._offset)
+                                       offset=self._offset, **voc)
             self._offset += (B * T * 256 + 3) // 4
         else:
             if z is not None:
                 z = as_dev(z, torch.float32)[:, :T * 32]
-            audio = eng.waveglow_infer(mel.contiguous(), z=z, sigma=sigma, precision=self.vocoder_precision)
+            audio = eng.waveglow_infer(mel.contiguous(), z=z, sigma=sigma, precision=self.vocoder_precision, **voc)
         if reduce_noise or trim_silence:
             n_samp = np.maximum(lengths.cpu().numpy().astype(np.int64) * 256, 1)      # a row needs >= 1 sample
             if reduce_noise:

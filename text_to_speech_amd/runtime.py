@@ -256,13 +256,17 @@ class HipRuntime(Runtime):
                 self._encoded = None
 
     # ------------------------------------------------------------------ WaveGlow.infer (waveglow_arch.py:244-306)
-    def waveglow_infer(self, mel, z=None, sigma=1.0, deterministic=False, seed=None, precision=None, **_ignored):
+    def waveglow_infer(self, mel, z=None, sigma=1.0, deterministic=False, seed=None, precision=None, lengths=None,
+                       **_ignored):
+        """`lengths` [B] (frames of each row that are real): a batch of unequal rows -- every row's audio is that of its own
+        frames, zeros behind it (HipEngine.waveglow_infer); the noise is drawn in the batch layout either way."""
         dev = _is_torch_cuda(mel)
         if not dev:
             mel = np.asarray(mel, dtype=np.float32)
         if mel.ndim == 2:
             mel = mel[None]
         B, T = int(mel.shape[0]), int(mel.shape[1])
+        ragged = {} if lengths is None else {'lengths': lengths}
         if z is None and not deterministic:
             if seed is not None:
                 zs, zo = (int(seed) ^ NOISE_STREAM) & _U64, 0
@@ -270,8 +274,8 @@ class HipRuntime(Runtime):
                 zs, zo = (self._seed ^ NOISE_STREAM) & _U64, self._offset
                 self._offset += (B * T * 256 + 3) // 4
             return self.engine.waveglow_infer(mel, sigma=float(sigma), precision=precision or self.vocoder_precision,
-                                              seed=zs, offset=zo)
-        return self.engine.waveglow_infer(mel, z=z, sigma=float(sigma), precision=precision or self.vocoder_precision)
+                                              seed=zs, offset=zo, **ragged)
+        return self.engine.waveglow_infer(mel, z=z, sigma=float(sigma), precision=precision or self.vocoder_precision, **ragged)
 
 
 _runtimes = {'hip': HipRuntime}

@@ -120,8 +120,7 @@ class Tacotron2:
 
     def _vocode_and_finish(self, part, *, callbacks=None, predicted=None, return_output=True, vocoder=None,
                            silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, **kwargs):
-        text, synth_time = part['text'], part.get('synth_time', 0.)
-        audio_infos = {}
+        audios, vocoder_time = None, 0.
         if vocoder is not None:
             t1 = time.time()
             audios = []
@@ -132,6 +131,16 @@ class Tacotron2:
                         audio = audio[0]
                     audios.append(_to_numpy(audio))
             vocoder_time = time.time() - t1
+        return self._finish(part, audios, vocoder_time, callbacks=callbacks, predicted=predicted, return_output=return_output,
+                            vocoder=vocoder, silence_time=silence_time, reduce_noise=reduce_noise, trim_silence=trim_silence)
+
+    def _finish(self, part, audios, vocoder_time, *, callbacks=None, predicted=None, return_output=True, vocoder=None,
+                silence_time=0.15, reduce_noise=False, trim_silence=False):
+        """The finishing half of `_vocode_and_finish`: `audios` (the waveforms of the non-empty parts, in order; None without
+        a vocoder) -> concatenation, clean-up, result dict, `predicted` entry, callbacks, return value."""
+        text, synth_time = part['text'], part.get('synth_time', 0.)
+        audio_infos = {}
+        if vocoder is not None:
             if len(audios) > 0:
                 audios = audios[0] if len(audios) == 1 else np.concatenate(audios, axis=0)
                 if (reduce_noise or trim_silence) and len(audios) > 0:
@@ -199,12 +208,26 @@ class Tacotron2:
                         'audio_filename', 'post_processing')
 
     def predict(self, inputs, *, predicted=None, callbacks=None, return_results=True, return_output=None,
-                overlap=False, **kwargs):
+                overlap=False, batch_backlog=None, **kwargs):
         """BaseModel.predict (base_model.py:676-711): builds the callbacks unless the caller brings its own `predicted`
         map, then runs `infer` sequentially; returns the result dicts (or the `predicted` entries when a JSON saver is
-        active and `return_output` was not forced)."""
+        active and `return_output` was not forced).
+        `batch_backlog=k` (k >= 2): inputs that are already waiting are synthesized together -- the next input plus up to
+        k - 1 more that a `queue.Queue` holds right now (a list / iterator: its next items) are decoded as the rows of one
+        token batch and vocoded in one call with per-row lengths (`_infer_backlog`); a lone input takes the batch-1 path, so
+        nothing waits for a batch to fill.  Results, callbacks and the `predicted` map see the inputs in their order, as in
+        the sequential loop.  With `deterministic=True` the audio is the sequential loop's up to fp32 re-association in the
+        decoder; otherwise dropout masks and noise are drawn from the runtime's stream in the batch's layout: the same
+        distribution, another realisation than the sequential loop's.  Not combined with `overlap=True`."""
+        backlog = batch_backlog is not None and int(batch_backlog) >= 2
+        if batch_backlog is not None and int(batch_backlog) < 1:
+            raise ValueError(f'batch_backlog must be None or >= 1, got {batch_backlog!r}')
+        if backlog and overlap:
+            raise ValueError('batch_backlog and overlap=True cannot be combined')
         if isinstance(inputs, (str, dict)):
             inputs = [inputs]
+        elif isinstance(inputs, _queue.Queue) and not backlog:
+            inputs = _iterate(inputs)
         join_callbacks = predicted is None
         if predicted is None:
             predicted, built = self.get_inference_callbacks(**kwargs)
@@ -215,7 +238,10 @@ class Tacotron2:
             return_output = not any(isinstance(cb, JSONSaver) for cb in callbacks)
         kwargs = {k: v for k, v in kwargs.items() if k not in self._callback_kwargs}
         results = []
-        if overlap and kwargs.get('vocoder') is not None:
+        if backlog:
+            outputs = self._infer_backlog(inputs, int(batch_backlog), predicted=predicted, callbacks=callbacks,
+                                          return_output=return_output, **kwargs)
+        elif overlap and kwargs.get('vocoder') is not None:
             outputs = self._infer_overlapped(inputs, predicted=predicted, callbacks=callbacks,
                                              return_output=return_output, **kwargs)
         else:
@@ -285,6 +311,127 @@ class Tacotron2:
                     pass
             th.join()
 
+    def _infer_backlog(self, inputs, k, *, predicted, callbacks, return_output, overwrite=False, embeddings=None,
+                       max_length=10., max_text_length=-1, max_trial=5, min_fpt_ratio=2., max_fpt_ratio=10., vocoder=None,
+                       silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, **kwargs):
+        """`predict(batch_backlog=k)`: yields (input, result) in input order.  Per group of waiting inputs (`_backlog_groups`):
+        the parts of all its texts are the rows of 0-padded token batches of at most k rows, one `compiled_infer` call each;
+        every row keeps the frame cap, the frame / token ratio test and the retries it would have had alone (rows that fail
+        are decoded again together); ONE vocoder call per group with `lengths` = the rows' frame counts, so every waveform is
+        that of its own frames; then each text is finished (`_finish`) in input order."""
+        one = dict(predicted=predicted, callbacks=callbacks, return_output=return_output, overwrite=overwrite,
+                   embeddings=embeddings, max_length=max_length, max_text_length=max_text_length, max_trial=max_trial,
+                   min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, vocoder=vocoder, silence_time=silence_time,
+                   vocoder_config=vocoder_config, reduce_noise=reduce_noise, trim_silence=trim_silence, **kwargs)
+        finish = dict(callbacks=callbacks, predicted=predicted, return_output=return_output, vocoder=vocoder,
+                      silence_time=silence_time, reduce_noise=reduce_noise, trim_silence=trim_silence)
+        is_cached = lambda text: bool(predicted) and not overwrite and text in predicted
+        for group in _backlog_groups(inputs, k, is_cached):
+            fresh = [(inp, text) for inp, text in group if not is_cached(text)]
+            if len(fresh) <= 1:                                   # no backlog: the sequential path, cache replays included
+                for inp, _ in group:
+                    yield inp, Tacotron2.infer(self, inp, **one)
+                continue
+            t0 = time.time()
+            parts = [self._prepare_text(text, max_text_length, **kwargs) for _, text in fresh]
+            rows = [(ti, enc) for ti, part in enumerate(parts) for enc in part.pop('encoded')]
+            decoded = [None] * len(rows)
+            for r0 in range(0, len(rows), k):
+                chunk = list(range(r0, min(r0 + k, len(rows))))
+                self._decode_rows(rows, chunk, decoded, embeddings=embeddings, max_length=max_length, max_trial=max_trial,
+                                  min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, **kwargs)
+            synth_time = time.time() - t0
+            for (ti, _), (mel, attn) in zip(rows, decoded):
+                parts[ti]['mel'].append(mel)
+                parts[ti]['attention'].append(attn)
+            audios, vocoder_time = [None] * len(parts), 0.
+            if vocoder is not None:
+                t1 = time.time()
+                audios = [[] for _ in parts]
+                voiced = [(ti, _to_numpy(mel)) for (ti, _), (mel, _) in zip(rows, decoded) if mel.shape[0] > 0]
+                if voiced:
+                    n_frames = np.asarray([m.shape[0] for _, m in voiced], np.int32)
+                    batch = np.zeros((len(voiced), int(n_frames.max()), voiced[0][1].shape[1]), np.float32)
+                    for r, (_, m) in enumerate(voiced):
+                        batch[r, :m.shape[0]] = m
+                    audio = _to_numpy(vocoder(batch, lengths=n_frames, **{**kwargs, **vocoder_config}))
+                    for r, (ti, m) in enumerate(voiced):
+                        audios[ti].append(audio[r, :m.shape[0] * 256].copy())
+                vocoder_time = time.time() - t1
+            done = {}
+            for (_, text), part, aud in zip(fresh, parts, audios):
+                part['synth_time'] = synth_time / len(fresh)
+                done[text] = (part, aud)
+            for inp, text in group:                               # input order: cache replays between the fresh texts
+                if text in done:
+                    part, aud = done[text]
+                    yield inp, self._finish(part, aud, vocoder_time / len(fresh), **finish)
+                else:
+                    yield inp, Tacotron2.infer(self, inp, **one)
+
+    def _prepare_text(self, text, max_text_length, **kwargs):
+        """The host half of `_synthesize` before the decoder: split / clean / encode -> a result-dict stub with `encoded`."""
+        if max_text_length == -1:
+            splitted = [text]
+        elif max_text_length == -2:
+            splitted = split_sentences(text)
+        else:
+            splitted = split_text(text, max_text_length)
+        splitted = [self.clean_text(sent, **kwargs) for sent in splitted]
+        splitted = [s for s in splitted if any(c.isalnum() for c in s)]
+        if not splitted:
+            splitted = ['']
+        cleaned = '\n\n'.join(splitted) if len(splitted) > 1 else splitted[0]
+        encoded = [self.encode_text(t, cleaned=True) for t in splitted]
+        splitted = [splitted[i] for i in range(len(splitted)) if len(encoded[i]) > 0]
+        encoded = [np.asarray(enc) for enc in encoded if len(enc) > 0]
+        return {'text': text, 'cleaned': cleaned, 'splitted': splitted, 'mel': [], 'attention': [], 'encoded': encoded}
+
+    def _decode_rows(self, rows, chunk, decoded, *, embeddings, max_length, max_trial, min_fpt_ratio, max_fpt_ratio, **kwargs):
+        """Decodes rows[i] for i in `chunk` as one token batch; decoded[i] = (mel [n_i, 80], attention [n_i, Tin]).  Row i
+        ends at min(its length, the cap int(float32(tokens_i) * float32(max_length)) it would have had alone): the runtime
+        sizes the loop by the longest row (and the mel of a row cut that way gets the postnet of its own frames, on a HIP
+        engine).  Rows outside the frame / token window are decoded again together, up to
+        `max_trial` times in all, and keep their last result, as a sentence alone does."""
+        pending = list(chunk)
+        for trial in range(max_trial):
+            n_tok = [len(rows[i][1]) for i in pending]
+            tok = np.zeros((len(pending), max(n_tok)), dtype=rows[pending[0]][1].dtype)
+            for r, i in enumerate(pending):
+                tok[r, :n_tok[r]] = rows[i][1]
+            inputs = tok if embeddings is None else (tok, np.repeat(np.asarray(embeddings)[None], len(pending), axis=0))
+            outputs = self.compiled_infer(inputs, max_length=max_length, **kwargs)
+            lengths = _to_numpy(outputs.lengths)
+            frames = [int(n) for n in lengths]
+            if isinstance(max_length, float):
+                frames = [min(n, max(1, int(np.float32(t) * np.float32(max_length)))) for n, t in zip(frames, n_tok)]
+            elif max_length is not None:
+                frames = [min(n, max(1, int(max_length))) for n in frames]
+            mels = {r: outputs.mel[r, :frames[r]] for r in range(len(pending))}
+            # A row cut by its cap: the postnet (five k = 5 convs) of the batch saw the frames the longer loop produced behind
+            # the cut, where the row alone ends.  Its last ~10 frames are computed again from the decoder output, masked there.
+            cut = [r for r in range(len(pending)) if frames[r] < int(lengths[r])]
+            engine = getattr(self.compiled_infer, 'engine', None)
+            if cut and hasattr(engine, 'tacotron2_postnet'):
+                t_cut = max(frames[r] for r in cut)
+                dec = _to_numpy(outputs.decoder_output)[cut, :t_cut]
+                redo = engine.tacotron2_postnet(dec, [frames[r] - 1 for r in cut])
+                for j, r in enumerate(cut):
+                    mels[r] = redo[j, :frames[r]]
+            failed = []
+            for r, i in enumerate(pending):
+                n_frames = frames[r]
+                decoded[i] = (mels[r], outputs.attention_weights[r, :n_frames, :n_tok[r]])
+                ratio = n_frames / n_tok[r]
+                if not min_fpt_ratio < ratio < max_fpt_ratio:
+                    failed.append(i)
+                    logger.info('Inference failed (lengths : %s, frame/token ratio : %.2f) !', lengths[r:r + 1], ratio)
+            pending = failed
+            if not pending:
+                return
+        for _ in pending:
+            logger.warning('Inference failed too much time ! Result is probably not perfect')
+
     def precompile_for_stream(self, **kwargs):
         for m in (64, 128):                                    # tacotron2.py:354-356 (warm-up of both shape buckets)
             self.infer('hello {}'.format(m), max_trial=1, padding_multiple=m, **kwargs)
@@ -293,10 +440,12 @@ class Tacotron2:
         """`predict(return_output=False, return_results=False)` over an iterable or a `queue.Queue` (None ends it);
         results leave through the callbacks (tacotron2.py:363-367, base_model.py:713)."""
         self.precompile_for_stream(vocoder=vocoder, **{k: v for k, v in kwargs.items()
-                                                       if k not in self._callback_kwargs + ('callbacks', 'predicted', 'overlap')})
+                                                       if k not in self._callback_kwargs + ('callbacks', 'predicted', 'overlap',
+                                                                                            'batch_backlog')})
         kwargs.setdefault('return_output', False)
         kwargs.setdefault('return_results', False)
-        return self.predict(_iterate(stream), vocoder=vocoder, **kwargs)
+        # batch_backlog looks at what the queue holds right now, so `predict` gets the queue itself
+        return self.predict(stream, vocoder=vocoder, **kwargs)
 
 
 # ---- multi-speaker wrapper (models/tts/sv2tts_tacotron2.py:18-128, utils/embeddings.py:249-286) --------------------------
@@ -384,6 +533,11 @@ class SV2TTSTacotron2(Tacotron2):
             embeddings = self.select_embedding(embeddings)
         return super()._infer_overlapped(inputs, embeddings=embeddings, **kwargs)
 
+    def _infer_backlog(self, inputs, k, *, embeddings=0, **kwargs):
+        if embeddings is None or isinstance(embeddings, (int, str, dict)):       # one selection per call, as above
+            embeddings = self.select_embedding(embeddings)
+        return super()._infer_backlog(inputs, k, embeddings=embeddings, **kwargs)
+
 
 def _as_callbacks(callbacks):
     """Accepts Callback instances, plain callables (called with the merged entry + result as keyword arguments, like the
@@ -412,6 +566,55 @@ def _iterate(stream):
             yield item
     else:
         yield from stream
+
+
+def _input_text(inp):
+    return inp['text' if 'text' in inp else 'content'] if isinstance(inp, dict) else inp
+
+
+def _backlog_groups(source, k, is_cached=lambda text: False):
+    """Groups of [(input, text)] for `predict(batch_backlog=k)`: the next input (a `queue.Queue` is waited on, None ends
+    it), then more that are waiting right now (`get_nowait`; a list / iterator: its next items) until the group holds k
+    texts to synthesize.  Cached texts ride along in their place without counting; a text that already sits in the group
+    closes it and opens the next one, so a repeat finds the entry its first occurrence left in the cache."""
+    is_queue = isinstance(source, _queue.Queue)
+    it = None if is_queue else iter(source)
+    END = object()
+
+    def take(block):
+        if is_queue:
+            try:
+                item = source.get() if block else source.get_nowait()
+            except _queue.Empty:
+                return None
+            return END if item is None else item
+        return next(it, END)
+
+    held = None
+    while True:
+        first = held if held is not None else take(True)
+        held = None
+        if first is END:
+            return
+        group, texts, n_fresh, ended = [(first, _input_text(first))], {_input_text(first)}, 0, False
+        n_fresh += not is_cached(group[0][1])
+        while n_fresh < k:
+            item = take(False)
+            if item is None:
+                break
+            if item is END:
+                ended = True
+                break
+            text = _input_text(item)
+            if text in texts:
+                held = item
+                break
+            group.append((item, text))
+            texts.add(text)
+            n_fresh += not is_cached(text)
+        yield group
+        if ended:
+            return
 
 
 _models = {}

@@ -82,7 +82,8 @@ class WaveGlow:
     the reference's `models.tts.WaveGlow.infer` (models/tts/waveglow.py:61-142).
 
     mel: a `.npy` path, [T, 80] or [B, T, 80] -> audio [B, T * 256] (windowed single-utterance mode: [T * 256]).
-    Without `win_len` the whole mel is vocoded in one call.  With it (frames; a float means "a multiple of": rounded up,
+    Without `win_len` the whole mel is vocoded in one call; a batch of unequal utterances then takes `lengths=[...]` (frames
+    of each row that are real): row b's audio[:lengths[b] * 256] is that of its own frames, zeros behind it.  With it (frames; a float means "a multiple of": rounded up,
     or down with `use_slice`; capped by `max_win_len`):
       * a mel that fits one window is vocoded directly -- padded to the window with -11 first only if `force_pad`
         (default: only for the keras runtime, i.e. never here), the result cut back to T * 256 samples;
