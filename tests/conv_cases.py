@@ -38,7 +38,7 @@ BOUNDS = {
 # ---- the dispatch rule -------------------------------------------------------------------------------------------------
 TILE_M, TILE_N = 64, 64     # gemm_small = launch_gemm<2, 2, 1, 1, 32, ...>: BM = WR * RT * 32, BN = WC * CT * 32 (gemm_f32.h)
 SPLIT_BELOW_TILES = 512     # conv_gemm: `tiles < 512` -> split
-SCRATCH_ROWS = 32768        # tacotron2.hip: conv_rows = min(rows, 32768), scratch = 5 * conv_rows * 512 floats
+SCRATCH_ROWS = 32768        # taco_decode.h conv_scratch_floats: 5 * min(rows, 32768) * 512 floats
 
 
 def pick_conv_path(M, cout):

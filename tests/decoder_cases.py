@@ -10,7 +10,7 @@ References come from the numpy oracle, once per case and weight rounding (`refer
 - 'f16': the four decoder-LSTM tensors (attention / decoder LSTM kernel and recurrent_kernel) rounded to fp16 with RNE, as
   `cvt_w16_kernel` does -- the exact-arithmetic reference of the fp16 mode of the fused step and the per-step graph;
 - 'f16_ctx32': the same, but the context rows of both LSTM kernels stay fp32.  The persistent kernel folds those rows
-  into the per-utterance PM table from the fp32 weights (tacotron2.hip, `parts` of the persistent section) and streams
+  into the per-utterance PM table from the fp32 weights (tacotron2.hip, `parts` of run_persistent) and streams
   only the prenet / h_att / h_dec rows in fp16.
 """
 import functools
@@ -52,7 +52,7 @@ def _persist_lds_bytes(NBT, KT, Tin):
 
 
 def _persist(B, Tin, enc, hw):
-    # taco_persist.hip:889-905 (pick_shape, persist_applicable) and the dispatch_persist switch above them
+    # taco_persist.hip pick_shape, persist_applicable and the dispatch_persist switch above them
     if B < 1 or B > 4 or Tin < 1 or Tin > 512:
         return None
     NBT = 1 if B <= 1 else 2 if B <= 2 else 4
@@ -65,7 +65,7 @@ def _persist(B, Tin, enc, hw):
 
 
 def _fused(B, Tin, enc, hw):
-    # taco_fused.hip:1302-1318 (pick_shape, fused_applicable), lds_x / lds_y (:1258-1261), the chunk_t switch (:1347-1356)
+    # taco_fused.hip pick_shape, fused_applicable, lds_x / lds_y, and the chunk_t switch of fused_enqueue_chunk
     if B < 1 or B > 8 or Tin < 2 or Tin > 256 or enc not in (512, 768):
         return None
     NBT = 4 if B <= 4 else 8
@@ -74,13 +74,13 @@ def _fused(B, Tin, enc, hw):
     lds_y = (NBT * (2 * 1024 + enc) + 2 * 31 * 128 + 4 * KT * 128 * 9 + 16) * 4
     if lds_x > 160 * 1024 or lds_y > 160 * 1024:
         return None
-    # taco_fused.hip:731 NPOS = (NBT * KT * 128 + 1023) / 1024 and :819 two_pairs = NPOS > 1 && HW && B * Tin > 4 * NBLK
+    # taco_fused.hip fused_y_kernel: NPOS = (NBT * KT * 128 + 1023) / 1024 and two_pairs = NPOS > 1 && HW && B * Tin > 4 * NBLK
     npos = (NBT * KT * 128 + 1023) // 1024
     return Variant('fused', (NBT, enc, KT, hw), two_pairs=npos > 1 and hw and B * Tin > 4 * N_CU)
 
 
 def _graph(B, enc, hw):
-    # tacotron2.hip:922-954: lstm_dispatch_p switches on KS = (n0 + n1 + units) / 256 -- attention LSTM
+    # tacotron2.hip lstm_dispatch_p switches on KS = (n0 + n1 + units) / 256 -- attention LSTM
     # [p2 256 | ctx enc | h_att 1024], decoder LSTM [h_att 1024 | ctx enc | h_dec 1024] -- and lstm_by_batch launches
     # one kernel per chunk of <= 8 rows, NBT 1 / 2 / 4 / 8 by the chunk's row count
     ks = ((256 + enc + 1024) // 256, (1024 + enc + 1024) // 256)
@@ -93,8 +93,8 @@ def _graph(B, enc, hw):
 
 def pick_variant(machine, B, Tin, enc, precision) -> Optional[Variant]:
     """The instantiation a call takes under decoder mode `machine`, or None when that machine does not accept the call
-    (it then falls back to the graph).  'auto' restates tacotron2.hip:1340-1345: persistent for 1 - 2 rows, fused above,
-    whichever applies otherwise, the graph when neither does."""
+    (it then falls back to the graph).  'auto' restates choose_decoder_machine (tacotron2.hip): persistent for 1 - 2 rows,
+    fused above, whichever applies otherwise, the graph when neither does."""
     hw = precision == 'f16'
     if machine == 'persistent':
         return _persist(B, Tin, enc, hw)

@@ -23,7 +23,7 @@ def _src(name):
 
 # ---- the rule against the source ---------------------------------------------------------------------------------------
 def test_source_constants_of_the_rule():
-    taco, gemm = _src('tacotron2.hip'), _src('gemm_f32.h')
+    taco, gemm, plan = _src('tacotron2.hip'), _src('gemm_f32.h'), _src('taco_decode.h')
     body = taco[taco.index('int conv_gemm('):]
     body = body[:body.index('\n}\n')]
     assert 'const long long tiles = (long long)((M + 63) / 64) * ((cv.cout + 63) / 64);' in body
@@ -35,15 +35,24 @@ def test_source_constants_of_the_rule():
                      r'return launch_gemm<2, 2, 1, 1, 32, 1, TAG_GENERIC>\(g, bz, s\); \}', gemm)
     assert 'constexpr int BM = WR * RT * 32;' in gemm and 'constexpr int BN = WC * CT * 32;' in gemm
     assert cc.TILE_M == 2 * 1 * 32 and cc.TILE_N == 2 * 1 * 32 and cc.SPLIT_BELOW_TILES == 512
-    # the scratch both callers size: 5 x min(rows, 32768) x 512 floats
-    assert taco.count('std::min<long long>(R, 32768)') == 1 and taco.count('std::min<long long>(RD, 32768)') == 2
-    assert taco.count('5 * conv_rows * 512') >= 5
+    # the scratch every caller sizes: 5 x min(rows, 32768) x 512 floats, written in one function ...
+    sizing = 'inline size_t conv_scratch_floats(long long rows) { return (size_t)5 * std::min<long long>(rows, 32768) * 512; }'
+    assert plan.count(sizing) == 1 and plan.count('32768') == 1 and '32768' not in taco
+    assert plan.count('conv_scratch_floats(') == 1
+    # ... that sizes the conv scratch of all three plans: the encoder's over its R rows, and the postnet's over its RD rows,
+    # which the decode plan and the postnet probe both take from postnet_layout
+    assert taco.count('conv_scratch_floats(') == 2
+    assert 't.convtmp_n = conv_scratch_floats(R);\n    t.convtmp = A.take<float>(t.convtmp_n);' in taco
+    assert 'p.convtmp_n = conv_scratch_floats(RD);\n    p.convtmp = A.take<float>(p.convtmp_n);' in taco
+    assert taco.count('postnet_layout(') == 3               # its definition, decoder_layout, the probe's plan
+    assert 'w.post = postnet_layout(A, (long long)B * max_len);' in taco and 'pb = postnet_layout(A, RD);' in taco
+    assert taco.count('encoder_tmp_layout(') == 2 and 'convtmp_n = 5' not in taco
 
 
 def test_source_masks_and_activations_of_the_convs():
     taco = _src('tacotron2.hip')
     # encoder: relu, padded rows stored as 0 (mask_out 1); postnet: tanh + 0 on convs 1-4, no activation + BN(0) on conv 5
-    assert 'conv_gemm(e, tc.enc_conv[i], xin, 512, xout, (int)R, Tin, d_mask, ACT_RELU, 1, d_convtmp, convtmp_n, i)' in taco
+    assert 'conv_gemm(e, tc.enc_conv[i], xin, 512, xout, (int)R, Tin, out->mask, ACT_RELU, 1, t.convtmp, t.convtmp_n, i)' in taco
     assert 'last ? ACT_NONE : ACT_TANH' in taco and 'last ? 0 : 1, pb.convtmp, pb.convtmp_n, 3 + i' in taco
     assert 'const bool on = t <= lengths[b];' in taco                  # dec_mask_kernel
     assert cc.LAYERS['encoder'] == [(512, 'relu', 'zero')] * 3

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
@@ -106,15 +107,35 @@ struct tts_hip_encoded {
     float* pm = nullptr;                // [B * Tin][128]  processed memory
 };
 
+// The three machines that can run the decoder loop; the values are what tts_hip_last_decoder_mode reports.
+enum DecMachine { DEC_STEP_GRAPH = 0, DEC_PERSISTENT = 1, DEC_FUSED = 2 };
+
 // Identity of an instantiated decoder-chunk hipGraph: every pointer and scalar its 225 kernel nodes have baked in.
+// ws_layout says which exchange areas the workspace plan sized in (the offset of every later buffer depends on it).
 struct DecGraphKey {
     const void* ws;
     const void* enc_buf;
-    int B, Tin, max_len_bucket, masks, win_len, win_off, half_w, persist_layout;
-    bool operator<(const DecGraphKey& o) const {
-        return std::tie(ws, enc_buf, B, Tin, max_len_bucket, masks, win_len, win_off, half_w, persist_layout) <
-               std::tie(o.ws, o.enc_buf, o.B, o.Tin, o.max_len_bucket, o.masks, o.win_len, o.win_off, o.half_w, o.persist_layout);
-    }
+    int B, Tin, max_len_bucket, masks, win_len, win_off, half_w, ws_layout;
+    DecMachine machine;
+    auto tied() const { return std::tie(ws, enc_buf, B, Tin, max_len_bucket, masks, win_len, win_off, half_w, ws_layout, machine); }
+    bool operator<(const DecGraphKey& o) const { return tied() < o.tied(); }
+};
+
+// Instantiated decoder-chunk graphs, replayed by every later call with the same key: the workspace and the encoded batch
+// are stable allocations, so the kernel nodes hold valid pointers.  At most kCapacity graphs; the oldest is evicted first.
+class DecGraphCache {
+public:
+    // captures what `enqueue` puts on `st` and instantiates it; nothing is left behind when any step fails
+    static int capture(tts_hip_engine* e, hipStream_t st, const std::function<int()>& enqueue, hipGraphExec_t* out);
+    int get_or_capture(tts_hip_engine* e, const DecGraphKey& key, hipStream_t st, const std::function<int()>& enqueue,
+                       hipGraphExec_t* out);
+    void drop_if(const void* enc_buf);      // the graphs whose kernel nodes point into this encoded batch
+    void clear();
+
+private:
+    static constexpr size_t kCapacity = 16;
+    std::map<DecGraphKey, hipGraphExec_t> graphs;
+    std::vector<DecGraphKey> order;         // insertion order
 };
 
 struct Tacotron2Dev {
@@ -150,8 +171,7 @@ struct Tacotron2Dev {
     DevBuf ws;                          // per-call workspace arena
     DevBuf io;                          // staging for host callers
     tts_hip_encoded* enc_cache = nullptr;                 // encoder output of tts_hip_tacotron2_infer* calls (reused: stable pointers)
-    std::map<DecGraphKey, hipGraphExec_t> graphs;         // instantiated decoder-chunk graphs, replayed across calls
-    std::vector<DecGraphKey> graph_order;                 // insertion order (oldest evicted first)
+    DecGraphCache graphs;                                 // instantiated decoder-chunk graphs, replayed across calls
     void* pinned = nullptr;                               // pinned host ring for the decoder loop's chunk reports (2 x 64 bytes)
     hipEvent_t chunk_ev[2] = {nullptr, nullptr};
 };
@@ -218,7 +238,6 @@ struct StreamScope {
     }
     ~StreamScope() { e->stream = saved; }
 };
-void tacotron2_graphs_clear(tts_hip_engine* e);
 
 #define HIPCHK(e, call)                                                                                         \
     do {                                                                                                        \

@@ -1317,13 +1317,13 @@ bool fused_applicable(const tts_hip_engine* e, int B, int Tin) {
     return lds_y(NBT, enc, KT) <= 160 * 1024 && lds_x(NBT, enc) <= 160 * 1024;
 }
 
-int fused_init(tts_hip_engine* e, hipStream_t st, const FusedCall& c) {
-    hipLaunchKernelGGL(fused_init_kernel, dim3(1), dim3(1), 0, st, c.state, c.B, c.max_len, c.early_stop);
+int fused_init(tts_hip_engine* e, hipStream_t st, const DecodeCall& c) {
+    hipLaunchKernelGGL(fused_init_kernel, dim3(1), dim3(1), 0, st, c.ws.fstate, c.B, c.max_len, c.early_stop);
     HIPCHK(e, hipGetLastError());
     return TTS_HIP_OK;
 }
 
-int fused_enqueue_chunk(tts_hip_engine* e, hipStream_t st, const FusedCall& c) {
+int fused_enqueue_chunk(tts_hip_engine* e, hipStream_t st, const DecodeCall& c) {
     Tacotron2Dev& tc = e->taco;
     const int enc = tc.enc_dim;
     FusedArgs a{};
@@ -1336,10 +1336,11 @@ int fused_enqueue_chunk(tts_hip_engine* e, hipStream_t st, const FusedCall& c) {
     a.Pw = tc.proj_w; a.Pb = tc.proj_b;
     a.Wq = tc.query_w; a.wloc = tc.loc_dense; a.vw = tc.value_w;
     a.memory = c.memory; a.pm = c.pm; a.mask = c.mask; a.enc_len = c.enc_len; a.masks = c.masks;
-    a.xch = c.xch; a.flags = c.flags; a.st = c.state;
-    a.hatt = c.hatt; a.hdec = c.hdec; a.catt = c.catt; a.cdec = c.cdec; a.ctx = c.ctx;
-    a.wprev = c.wprev; a.wcum = c.wcum; a.mainatt = c.mainatt;
-    a.dec_out = c.dec_out; a.stop_out = c.stop_out; a.attn_hist = c.attn_hist; a.lengths = c.lengths; a.finished = c.finished;
+    const DecoderWs& w = c.ws;
+    a.xch = w.xch; a.flags = w.pflags; a.st = w.fstate;
+    a.hatt = w.hatt; a.hdec = w.hdec; a.catt = w.catt; a.cdec = w.cdec; a.ctx = w.ctx;
+    a.wprev = w.wprev; a.wcum = w.wcum; a.mainatt = w.mainatt;
+    a.dec_out = w.dec_out; a.stop_out = w.stop_out; a.attn_hist = w.attn_hist; a.lengths = w.lengths; a.finished = w.finished;
     a.trace = c.trace;
     // first look at a hop this long after the block's own producer published (10-ns ticks): the latency of a tagged publish
     // next to the (pausing) weight stream.  Found per kernel shape with scripts/fused_sweep.py on the debug build (round 4: the
@@ -1360,14 +1361,14 @@ int fused_enqueue_chunk(tts_hip_engine* e, hipStream_t st, const FusedCall& c) {
     hipError_t er;
     const int key = (NBT == 8 ? 4 : 0) | (enc == 768 ? 2 : 0) | (c.half_w ? 1 : 0);
     switch (key) {
-        case 0: er = chunk_t<4, 512, false>(st, a, KT, c.bl_err, c.report); break;
-        case 1: er = chunk_t<4, 512, true>(st, a, KT, c.bl_err, c.report); break;
-        case 2: er = chunk_t<4, 768, false>(st, a, KT, c.bl_err, c.report); break;
-        case 3: er = chunk_t<4, 768, true>(st, a, KT, c.bl_err, c.report); break;
-        case 4: er = chunk_t<8, 512, false>(st, a, KT, c.bl_err, c.report); break;
-        case 5: er = chunk_t<8, 512, true>(st, a, KT, c.bl_err, c.report); break;
-        case 6: er = chunk_t<8, 768, false>(st, a, KT, c.bl_err, c.report); break;
-        default: er = chunk_t<8, 768, true>(st, a, KT, c.bl_err, c.report); break;
+        case 0: er = chunk_t<4, 512, false>(st, a, KT, c.bl_err, w.freport); break;
+        case 1: er = chunk_t<4, 512, true>(st, a, KT, c.bl_err, w.freport); break;
+        case 2: er = chunk_t<4, 768, false>(st, a, KT, c.bl_err, w.freport); break;
+        case 3: er = chunk_t<4, 768, true>(st, a, KT, c.bl_err, w.freport); break;
+        case 4: er = chunk_t<8, 512, false>(st, a, KT, c.bl_err, w.freport); break;
+        case 5: er = chunk_t<8, 512, true>(st, a, KT, c.bl_err, w.freport); break;
+        case 6: er = chunk_t<8, 768, false>(st, a, KT, c.bl_err, w.freport); break;
+        default: er = chunk_t<8, 768, true>(st, a, KT, c.bl_err, w.freport); break;
     }
     HIPCHK(e, er);
     return TTS_HIP_OK;

@@ -924,7 +924,7 @@ int persist_finalize(tts_hip_engine* e, const HostTensor* prenet0, const HostTen
     return upload(e, fb.data(), fb.size(), &e->taco.pfold_b, allocs);
 }
 
-int persist_decode(tts_hip_engine* e, hipStream_t st, const PersistCall& c, int* steps_run) {
+int persist_decode(tts_hip_engine* e, hipStream_t st, const DecodeCall& c, int* steps_run) {
     Tacotron2Dev& tc = e->taco;
     const int enc = tc.enc_dim;
     int NBT, KT;
@@ -940,10 +940,11 @@ int persist_decode(tts_hip_engine* e, hipStream_t st, const PersistCall& c, int*
     a.W1t = tc.prenet_w1;
     a.Pw = tc.proj_w; a.Pb = tc.proj_b;
     a.Wq = tc.query_w; a.wloc = tc.loc_dense; a.vw = tc.value_w;
-    a.PM = c.pm_fold; a.pm = c.pm; a.mask = c.mask; a.enc_len = c.enc_len; a.masks = c.masks;
-    a.xch = c.xch; a.flags = c.flags;
-    a.dec_out = c.dec_out; a.stop_out = c.stop_out; a.attn_hist = c.attn_hist;
-    a.lengths = c.lengths; a.finished = c.finished;
+    const DecoderWs& w = c.ws;
+    a.PM = w.pm_fold; a.pm = c.pm; a.mask = c.mask; a.enc_len = c.enc_len; a.masks = c.masks;
+    a.xch = w.xch; a.flags = w.pflags;
+    a.dec_out = w.dec_out; a.stop_out = w.stop_out; a.attn_hist = w.attn_hist;
+    a.lengths = w.lengths; a.finished = w.finished;
     // First-poll delays (10-ns ticks after the hop's anchor; hops A..F), found with scripts/persist_sweep.py on 100-token
     // utterances: batch 1 10.7 -> 9.3 us / step, batch 2 14.1 -> 12.8.  The two all-to-all LSTM hops (A, D) stay on the
     // sentinel path (their 1024 values only become visible ~0.9 us after the publish: a timed full poll cannot beat sentinel +
@@ -974,12 +975,12 @@ int persist_decode(tts_hip_engine* e, hipStream_t st, const PersistCall& c, int*
     hipError_t er = c.half_w ? dispatch_persist<true>(st, a, NBT, KT, lds) : dispatch_persist<false>(st, a, NBT, KT, lds);
     if (er == hipErrorCooperativeLaunchTooLarge || er == hipErrorInvalidConfiguration) {
         (void)hipGetLastError();
-        return 1;                                    // this device cannot hold the grid: per-step graph instead
+        return DEC_FALL_BACK;                        // this device cannot hold the grid: per-step graph instead
     }
     HIPCHK(e, er);
     if (e->timing) HIPCHK(e, hipEventRecord(ev1, st));
     int h[5] = {0, 0, 0, 0, 0};
-    HIPCHK(e, hipMemcpyAsync(h, c.flags, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(h, w.pflags, sizeof h, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
     if (h[3] >= 64 && h[4] * 4 > h[3]) e->taco.persist_timed = false;     // more than a quarter missed: not worth it here
     if (e->timing) {
@@ -1002,12 +1003,12 @@ int persist_decode(tts_hip_engine* e, hipStream_t st, const PersistCall& c, int*
         }
     }
 #endif
-    if (h[0] == ABORT_RENDEZVOUS) return 1;
+    if (h[0] == ABORT_RENDEZVOUS) return DEC_FALL_BACK;
     if (h[0] != 0) {
         // a hop timed out in mid-loop (never seen; e.g. a block lost its CU for a second): the outputs are partial -- the
         // caller clears them and runs the per-step graph instead
         set_err(e, TTS_HIP_EHIP, "tacotron2 persistent decoder: exchange timed out at a hop (code %d); fell back to the per-step graph", h[0]);
-        return 2;
+        return DEC_FALL_BACK;
     }
     *steps_run = h[2];
     return TTS_HIP_OK;

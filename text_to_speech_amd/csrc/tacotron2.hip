@@ -786,17 +786,21 @@ __global__ void add_kernel(const float* __restrict__ a, const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ host helpers
-struct Arena {
-    char* base = nullptr;
-    size_t off = 0, cap = 0;
-    template <class T>
-    T* take(size_t n) {
-        off = (off + 255) / 256 * 256;
-        T* p = (T*)(base + off);
-        off += n * sizeof(T);
-        return p;
-    }
-};
+// Lays a workspace out in `buf`: `layout(Arena&)` names the buffers once.  It runs against a null base to learn the size, the
+// buffer grows if it has to (a moved buffer clears the cached graphs: their kernel nodes hold pointers into it), and it runs
+// again for the pointers -- so the size and the pointers cannot disagree.
+template <class F>
+int plan_workspace(tts_hip_engine* e, DevBuf& buf, size_t slack, F&& layout) {
+    Arena sizing;
+    layout(sizing);
+    const void* before = buf.p;
+    HIPCHK(e, buf.ensure(sizing.off + slack));
+    if (buf.p != before) e->taco.graphs.clear();
+    Arena A;
+    A.base = (char*)buf.p;
+    layout(A);
+    return TTS_HIP_OK;
+}
 
 int fold_conv_bn(tts_hip_engine* e, const std::string& conv, const std::string& norm, int cin, int cout, ConvBnDev* out,
                  std::vector<void*>& allocs) {
@@ -977,7 +981,7 @@ void tacotron2_free(tts_hip_engine* e) {
     e->taco.dec.W16 = nullptr;
     e->taco.pfold_w = nullptr;
     e->taco.pfold_b = nullptr;
-    tacotron2_graphs_clear(e);
+    e->taco.graphs.clear();
     if (e->taco.pinned) {
         (void)hipHostFree(e->taco.pinned);
         e->taco.pinned = nullptr;
@@ -1170,13 +1174,95 @@ static int tacotron2_build_f16(tts_hip_engine* e) {
     return TTS_HIP_OK;
 }
 
-void tacotron2_graphs_clear(tts_hip_engine* e) {
-    for (auto& kv : e->taco.graphs) (void)hipGraphExecDestroy(kv.second);
-    e->taco.graphs.clear();
-    e->taco.graph_order.clear();
+int DecGraphCache::capture(tts_hip_engine* e, hipStream_t st, const std::function<int()>& enqueue, hipGraphExec_t* out) {
+    hipGraph_t graph = nullptr;
+    HIPCHK(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const int crc = enqueue();
+    const hipError_t ce = hipStreamEndCapture(st, &graph);
+    if (crc != TTS_HIP_OK || ce != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        if (crc != TTS_HIP_OK) return crc;
+        HIPCHK(e, ce);
+    }
+    const hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);             // the executable graph is self-contained
+    HIPCHK(e, ie);
+    return TTS_HIP_OK;
+}
+
+int DecGraphCache::get_or_capture(tts_hip_engine* e, const DecGraphKey& key, hipStream_t st,
+                                  const std::function<int()>& enqueue, hipGraphExec_t* out) {
+    auto it = graphs.find(key);
+    if (it != graphs.end()) {
+        *out = it->second;
+        return TTS_HIP_OK;
+    }
+    if (int rc = capture(e, st, enqueue, out)) return rc;
+    if (order.size() >= kCapacity) {
+        (void)hipGraphExecDestroy(graphs[order.front()]);
+        graphs.erase(order.front());
+        order.erase(order.begin());
+    }
+    graphs[key] = *out;
+    order.push_back(key);
+    return TTS_HIP_OK;
+}
+
+void DecGraphCache::drop_if(const void* enc_buf) {
+    auto keep = order.begin();
+    for (const DecGraphKey& k : order) {
+        if (k.enc_buf != enc_buf) {
+            *keep++ = k;
+        } else {
+            (void)hipGraphExecDestroy(graphs[k]);
+            graphs.erase(k);
+        }
+    }
+    order.erase(keep, order.end());
+}
+
+void DecGraphCache::clear() {
+    for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
+    graphs.clear();
+    order.clear();
+}
+
+static int check_bilstm_status(const tts_hip_engine* e, int bl_err) {
+    return bl_err ? set_err(e, TTS_HIP_EHIP, "tacotron2 encoder: BiLSTM block exchange timed out") : TTS_HIP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------- encoder
+struct EncoderTmp {                     // temporaries of one encoder call, in the engine workspace
+    int* tok;                           // [B * Tin]
+    float* x0;                          // [B * Tin][512] x 2: ping-pong of the convs
+    float* x1;
+    float* xproj;                       // [B * Tin][2048]  BiLSTM input projections, both directions
+    float* spk;                         // [B][spk_dim]
+    unsigned long long* blh;            // BiLSTM exchange buffers
+    float* convtmp;                     // split-path scratch of conv_gemm
+    size_t convtmp_n;
+};
+static size_t blh_u64(int B) { return (size_t)2 * B * 2 * 256; }
+static EncoderTmp encoder_tmp_layout(Arena& A, long long R, int B, int spk_dim) {
+    EncoderTmp t{};
+    t.tok = A.take<int>(R);
+    t.x0 = A.take<float>(R * 512);
+    t.x1 = A.take<float>(R * 512);
+    t.xproj = A.take<float>(R * 2048);
+    t.spk = A.take<float>((size_t)B * spk_dim + 1);
+    t.blh = A.take<unsigned long long>(blh_u64(B));
+    t.convtmp_n = conv_scratch_floats(R);
+    t.convtmp = A.take<float>(t.convtmp_n);
+    return t;
+}
+static void encoded_layout(Arena& A, tts_hip_encoded* o, long long R, int B, int enc) {      // the result buffer
+    o->mask = A.take<uint8_t>(R);
+    o->enc_len = A.take<int>(B);
+    o->bl_err = A.take<int>(16);
+    o->memory = A.take<float>(R * enc);
+    o->pm = A.take<float>(R * ATT);
+}
+
 // tokens -> (mask, lengths, memory, processed memory) in `out` (its own device buffer, so several encoded utterances can
 // be alive); temporaries live in the engine workspace.  Everything is enqueued on e->stream; nothing is synchronized.
 // Test hook (tts_hip_tacotron2_probe_encoder): stop_conv = i (0 .. 2) returns right after encoder conv i with *stop_out
@@ -1194,71 +1280,29 @@ static int tacotron2_encode_impl(tts_hip_engine* e, const int32_t* tokens, int B
     const int enc = tc.enc_dim;
     const long long R = (long long)B * Tin;
 
-    // result buffer
-    {
-        size_t need = 0;
-        auto sz = [&](size_t n, size_t el) { need = (need + 255) / 256 * 256 + n * el; };
-        sz(R, 1); sz(B, 4); sz(16, 4); sz(R * enc, 4); sz(R * ATT, 4);
-        need += 1024;
-        const void* before = out->buf.p;
-        HIPCHK(e, out->buf.ensure(need));
-        if (out->buf.p != before) tacotron2_graphs_clear(e);      // captured graphs hold pointers into this buffer
-        Arena A;
-        A.base = (char*)out->buf.p;
-        A.cap = out->buf.bytes;
-        out->mask = A.take<uint8_t>(R);
-        out->enc_len = A.take<int>(B);
-        out->bl_err = A.take<int>(16);
-        out->memory = A.take<float>(R * enc);
-        out->pm = A.take<float>(R * ATT);
-        out->B = B;
-        out->Tin = Tin;
-        out->enc = enc;
-    }
-    // temporaries
-    size_t need = 0;
-    auto sz = [&](size_t n, size_t el) { need = (need + 255) / 256 * 256 + n * el; };
-    sz(R, 4); sz(R * 512, 4); sz(R * 512, 4); sz(R * 2048, 4); sz((size_t)B * tc.spk_dim + 1, 4); sz((size_t)2 * B * 2 * 256, 8);
-    const size_t conv_rows = (size_t)std::min<long long>(R, 32768);
-    sz(5 * conv_rows * 512, 4);
-    need += 4096;
-    {
-        const void* before = tc.ws.p;
-        HIPCHK(e, tc.ws.ensure(need));
-        if (tc.ws.p != before) tacotron2_graphs_clear(e);
-    }
-    Arena A;
-    A.base = (char*)tc.ws.p;
-    A.cap = tc.ws.bytes;
-    int* d_tok = A.take<int>(R);
-    float* d_x0 = A.take<float>(R * 512);
-    float* d_x1 = A.take<float>(R * 512);
-    float* d_xproj = A.take<float>(R * 2048);
-    float* d_spk = A.take<float>((size_t)B * tc.spk_dim + 1);
-    unsigned long long* d_blh = A.take<unsigned long long>((size_t)2 * B * 2 * 256);
-    float* d_convtmp = A.take<float>(5 * conv_rows * 512);
-    const size_t convtmp_n = 5 * conv_rows * 512;
-    if (A.off > A.cap) return set_err(e, TTS_HIP_ENOMEM, "tacotron2 workspace accounting error");
-    uint8_t* d_mask = out->mask;
-    int* d_enc_len = out->enc_len;
-    float* d_memory = out->memory;
-    float* d_pm = out->pm;
+    int rc;
+    // result buffer (captured graphs hold pointers into it) and temporaries
+    if ((rc = plan_workspace(e, out->buf, 1024, [&](Arena& A) { encoded_layout(A, out, R, B, enc); }))) return rc;
+    out->B = B;
+    out->Tin = Tin;
+    out->enc = enc;
+    EncoderTmp t{};
+    if ((rc = plan_workspace(e, tc.ws, 4096, [&](Arena& A) { t = encoder_tmp_layout(A, R, B, tc.spk_dim); }))) return rc;
 
     const hipMemcpyKind kin = mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    HIPCHK(e, hipMemcpyAsync(d_tok, tokens, R * 4, kin, st));
-    if (tc.spk_dim) HIPCHK(e, hipMemcpyAsync(d_spk, speaker, (size_t)B * tc.spk_dim * 4, kin, st));
-    HIPCHK(e, hipMemsetAsync(d_blh, 0, (size_t)2 * B * 2 * 256 * 8, st));
+    HIPCHK(e, hipMemcpyAsync(t.tok, tokens, R * 4, kin, st));
+    if (tc.spk_dim) HIPCHK(e, hipMemcpyAsync(t.spk, speaker, (size_t)B * tc.spk_dim * 4, kin, st));
+    HIPCHK(e, hipMemsetAsync(t.blh, 0, blh_u64(B) * 8, st));
     HIPCHK(e, hipMemsetAsync(out->bl_err, 0, 16 * 4, st));
 
-    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)R), dim3(128), 0, st, d_tok, tc.embeddings, d_x0, d_mask, (int)R, tc.vocab);
+    hipLaunchKernelGGL(embed_kernel, dim3((unsigned)R), dim3(128), 0, st, t.tok, tc.embeddings, t.x0, out->mask, (int)R, tc.vocab);
     HIPCHK(e, hipGetLastError());
-    hipLaunchKernelGGL(enc_len_kernel, dim3(B), dim3(64), 0, st, d_mask, d_enc_len, Tin);
-    int rc;
-    float* xin = d_x0;
-    float* xout = d_x1;
+    hipLaunchKernelGGL(enc_len_kernel, dim3(B), dim3(64), 0, st, out->mask, out->enc_len, Tin);
+    float* xin = t.x0;
+    float* xout = t.x1;
     for (int i = 0; i < 3; ++i) {
         // MaskedConv1D -> BN -> relu; rows at padded tokens are stored as zeros (they are only ever consumed masked)
-        if ((rc = conv_gemm(e, tc.enc_conv[i], xin, 512, xout, (int)R, Tin, d_mask, ACT_RELU, 1, d_convtmp, convtmp_n, i))) return rc;
+        if ((rc = conv_gemm(e, tc.enc_conv[i], xin, 512, xout, (int)R, Tin, out->mask, ACT_RELU, 1, t.convtmp, t.convtmp_n, i))) return rc;
         std::swap(xin, xout);
         if (i == stop_conv) {
             *stop_out = xin;
@@ -1277,17 +1321,17 @@ static int tacotron2_encode_impl(tts_hip_engine* e, const int32_t* tokens, int B
         g.bias = tc.bl_in_b[0];
         g.mode = EPI_LINEAR;
         g.split = 2048;
-        g.out0 = d_xproj;
+        g.out0 = t.xproj;
         g.ld0 = 2048;
         HIPCHK(e, gemm_small(g, 1, st));
     }
-    hipLaunchKernelGGL(bilstm_kernel, dim3(BL_Q, 2, B), dim3(1024), 0, st, d_xproj, tc.bl_rec[0], tc.bl_rec[1], d_mask,
-                       d_memory, d_blh, out->bl_err, Tin, enc);
+    hipLaunchKernelGGL(bilstm_kernel, dim3(BL_Q, 2, B), dim3(1024), 0, st, t.xproj, tc.bl_rec[0], tc.bl_rec[1], out->mask,
+                       out->memory, t.blh, out->bl_err, Tin, enc);
     HIPCHK(e, hipGetLastError());
     if (tc.spk_dim) {
         const long long n = R * tc.spk_dim;
-        hipLaunchKernelGGL(speaker_concat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_spk, d_mask,
-                           d_memory, Tin, enc, tc.spk_dim, R);
+        hipLaunchKernelGGL(speaker_concat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t.spk, out->mask,
+                           out->memory, Tin, enc, tc.spk_dim, R);
         HIPCHK(e, hipGetLastError());
     }
     {   // processed_memory = memory(masked) @ memory_layer   (location_sensitive_attention.py:96-102)
@@ -1296,12 +1340,12 @@ static int tacotron2_encode_impl(tts_hip_engine* e, const int32_t* tokens, int B
         g.N = ATT;
         g.L = (int)R;
         g.nseg = 1;
-        g.seg[0] = ASeg{d_memory, enc, 0, enc, enc};
+        g.seg[0] = ASeg{out->memory, enc, 0, enc, enc};
         g.Bt = tc.memory_Bt;
         g.ldb = enc;
         g.mode = EPI_LINEAR;
         g.split = ATT;
-        g.out0 = d_pm;
+        g.out0 = out->pm;
         g.ld0 = ATT;
         HIPCHK(e, gemm_small(g, 1, st));
     }
@@ -1314,17 +1358,6 @@ static std::mutex& whole_gpu_mutex(int device) {
 }
 
 // ---------------------------------------------------------------------------------------------------------- postnet
-struct PostnetBufs {
-    uint8_t* dmask;                     // [B * T]
-    float* xm;                          // [B * T][80]  masked decoder output
-    float* pa;                          // [B * T][512] x 2: ping-pong of the tanh convs
-    float* pb;
-    float* post;                        // [B * T][80]  residual
-    float* mel;                         // [B * T][80]
-    float* convtmp;                     // split-path scratch of conv_gemm
-    size_t convtmp_n;
-};
-
 // Postnet + residual on e->stream (tacotron2_arch.py:214-232, 915-917): mask t <= lengths[b] (:745, per row), five masked
 // k = 5 convs + folded batch-norm -- tanh on the first four, whose padded rows are stored as 0 (only ever read masked), the
 // last one's padded rows are BN(0) as in the reference -- then mel = decoder output + residual.  Test hook
@@ -1359,6 +1392,334 @@ static int postnet_residual(tts_hip_engine* e, const int* d_lengths, const float
 }
 
 // ---------------------------------------------------------------------------------------------------------- decoder
+static PostnetBufs postnet_layout(Arena& A, long long RD) {
+    PostnetBufs p{};
+    p.dmask = A.take<uint8_t>(RD);
+    p.xm = A.take<float>(RD * NMEL);
+    p.pa = A.take<float>(RD * 512);
+    p.pb = A.take<float>(RD * 512);
+    p.post = A.take<float>(RD * NMEL);
+    p.mel = A.take<float>(RD * NMEL);
+    p.convtmp_n = conv_scratch_floats(RD);
+    p.convtmp = A.take<float>(p.convtmp_n);
+    return p;
+}
+
+// Buffers the step kernels address are sized for max_len rounded up to a bucket, so that every call of a bucket has
+// the same workspace layout and can replay the same instantiated hipGraph (rows are indexed with the real max_len,
+// which the kernels read from the device-side loop state).
+static int max_len_bucket(int max_len) { return (max_len + 255) / 256 * 256; }
+
+// The workspace of a decode call whose shape rule picked `machine` (it decides which exchange area is sized in).
+static DecoderWs decoder_layout(Arena& A, const tts_hip_engine* e, DecMachine machine, int B, int Tin, int max_len,
+                                bool with_masks) {
+    const int enc = e->taco.enc_dim;
+    const size_t R = (size_t)B * Tin, RB = (size_t)B * max_len_bucket(max_len);
+    const bool persist = machine == DEC_PERSISTENT, fused = machine == DEC_FUSED;
+    DecoderWs w{};
+    w.layout_id = (persist ? 1 : 0) | (fused ? 2 : 0);
+    w.masks = A.take<float>(with_masks ? RB * 2 * PRE : 1);
+    w.pm_fold = A.take<float>(persist ? R * PERSIST_NPM : 1);
+    w.zero_begin = A.mark();
+    w.state = A.take<DecState>(1);
+    w.fstate = A.take<FusedState>(1);
+    w.freport = A.take<int>(16);
+    w.xch = A.take<unsigned long long>((persist ? persist_xch_u64(B, Tin) : fused ? fused_xch_u64(B, Tin, enc) : 0) + 2);
+    w.pflags = A.take<int>(16);
+    w.hatt = A.take<float>(2 * B * ARNN);
+    w.catt = A.take<float>(B * ARNN);
+    w.hdec = A.take<float>(2 * B * DRNN);
+    w.cdec = A.take<float>(B * DRNN);
+    w.ctx = A.take<float>(B * enc);
+    w.p2 = A.take<float>(B * PRE);
+    w.q = A.take<float>(B * ATT);
+    w.frame = A.take<float>(B * NMEL);
+    w.energy = A.take<float>(R);
+    w.wprev = A.take<float>(R);
+    w.wcum = A.take<float>(R);
+    w.finished = A.take<int>(B);
+    w.lengths = A.take<int>(B);
+    w.mainatt = A.take<int>(2 * B);
+    w.zero_end = A.mark();
+    w.dec_out = A.take<float>(RB * NMEL);
+    w.stop_out = A.take<float>(RB);
+    w.attn_hist = A.take<float>(RB * Tin);
+    w.post = postnet_layout(A, (long long)B * max_len);
+    return w;
+}
+
+// Which machine runs the loop (tts_hip_set_decoder_mode): 0 = the 7-kernel per-step graph only, 1 = persistent kernel when its
+// shape rule allows, 2 = fused two-kernel step when its shape rule allows (never with kernel timing on: its steps cannot be
+// timed one by one), 3 (default) = persistent for 1 - 2 rows, fused above, whichever is applicable otherwise.  The per-step
+// graph is the fallback of both.  *backed_off: the rule gave the fused step (and the workspace is laid out for it), but a
+// recent call timed out (the GPU is shared), so this call stays on the per-step graph.
+static DecMachine choose_decoder_machine(tts_hip_engine* e, int B, int Tin, bool* backed_off) {
+    Tacotron2Dev& tc = e->taco;
+    const bool persist_ok = (tc.persist_mode == 1 || tc.persist_mode == 3) && persist_applicable(e, B, Tin);
+    const bool fused_ok = (tc.persist_mode == 2 || tc.persist_mode == 3) && !e->timing && fused_applicable(e, B, Tin);
+    *backed_off = false;
+    if (persist_ok && (!fused_ok || B <= 2)) return DEC_PERSISTENT;
+    if (!fused_ok) return DEC_STEP_GRAPH;
+    if (tc.fused_backoff > 0) {
+        --tc.fused_backoff;
+        *backed_off = true;
+    }
+    return DEC_FUSED;
+}
+
+static DecGraphKey graph_key(const tts_hip_engine* e, const DecodeCall& c, DecMachine machine) {
+    return DecGraphKey{e->taco.ws.p, c.enc_buf, c.B, c.Tin, max_len_bucket(c.max_len), c.masks ? 1 : 0, c.win_len, c.win_off,
+                       c.half_w ? 1 : 0, c.ws.layout_id, machine};
+}
+
+// All recurrent state, loop state, exchange area, histories and outputs of the real rows start at zero, and the per-step
+// graph's loop state is set: at the start of every call, and again before the per-step graph takes over from a machine
+// that gave up in mid-loop.
+static int reset_loop_state(tts_hip_engine* e, const DecodeCall& c) {
+    const DecoderWs& w = c.ws;
+    hipStream_t st = e->stream;
+    const size_t RD = (size_t)c.B * c.max_len;
+    HIPCHK(e, hipMemsetAsync(w.zero_begin, 0, w.zero_end - w.zero_begin, st));
+    HIPCHK(e, hipMemsetAsync(w.dec_out, 0, RD * NMEL * 4, st));
+    HIPCHK(e, hipMemsetAsync(w.stop_out, 0, RD * 4, st));
+    HIPCHK(e, hipMemsetAsync(w.attn_hist, 0, RD * c.Tin * 4, st));
+    hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, st, (DecState*)w.state, c.B, c.max_len, c.early_stop);
+    HIPCHK(e, hipGetLastError());
+    return TTS_HIP_OK;
+}
+
+// The seven launches of step j of a chunk of the per-step graph.
+// Measurement hook (results are garbage when set): TTS_HIP_DEBUG_ONLY_KERNEL=k launches only step kernel k (0 prenet,
+// 1 attention LSTM, 2 query, 3 energies, 4 softmax_ctx, 5 decoder LSTM, 6 project) seven times per step, which gives
+// that kernel's cost inside the graph without the other six around it (scripts/run_taco.py prints the step time).
+// Only exists in a build made with -DTTS_DEBUG_HOOKS (csrc/build.sh never passes it).
+static int enqueue_step(tts_hip_engine* e, const DecodeCall& c, int j) {
+    const Tacotron2Dev& tc = e->taco;
+    const DecoderWs& w = c.ws;
+    hipStream_t st = e->stream;
+    DecState* state = (DecState*)w.state;
+    const int B = c.B, Tin = c.Tin, enc = tc.enc_dim;
+#ifdef TTS_DEBUG_HOOKS
+    const char* only_env = getenv("TTS_HIP_DEBUG_ONLY_KERNEL");
+    const int only = only_env ? atoi(only_env) : -1;
+#else
+    constexpr int only = -1;
+#endif
+    const int par = j & 1;                       // CHUNK is even, so the parity of t equals the parity of j
+    float* hatt_old = w.hatt + (size_t)par * B * ARNN;
+    float* hatt_new = w.hatt + (size_t)(par ^ 1) * B * ARNN;
+    float* hdec_old = w.hdec + (size_t)par * B * DRNN;
+    float* hdec_new = w.hdec + (size_t)(par ^ 1) * B * DRNN;
+    timing_begin(e, 2);
+    for (int k = 0; k < 7; ++k) {
+        switch (only >= 0 ? only : k) {
+            case 0:
+                hipLaunchKernelGGL(prenet_kernel, dim3(B, 8), dim3(256), 0, st, state, j, w.frame, tc.prenet_w0, tc.prenet_w1,
+                                   c.masks, w.p2);
+                break;
+            case 1:
+                HIPCHK(e, lstm_dispatch(st, state, j, tc.att, w.p2, PRE, w.ctx, enc, hatt_old, hatt_new, w.catt, B, c.half_w));
+                break;
+            case 2:
+                hipLaunchKernelGGL(query_kernel, dim3(ATT / 2), dim3(256), 0, st, state, j, hatt_new, tc.query_w, w.q, B);
+                break;
+            case 3:
+                hipLaunchKernelGGL(energies_kernel, dim3(B, (Tin + EPB - 1) / EPB), dim3(256), 0, st, state, j, w.q, tc.loc_dense,
+                                   tc.value_w, c.pm, w.wprev, w.wcum, w.energy, Tin);
+                break;
+            case 4:
+                hipLaunchKernelGGL(softmax_ctx_kernel, dim3(B, enc / 32), dim3(256), (size_t)Tin * sizeof(float), st, state, j,
+                                   w.energy, c.mask, c.enc_len, c.win_len, c.win_off, w.mainatt + par * B,
+                                   w.mainatt + (par ^ 1) * B, c.memory, w.wprev, w.wcum, w.ctx, w.attn_hist, Tin, enc);
+                break;
+            case 5:
+                HIPCHK(e, lstm_dispatch(st, state, j, tc.dec, hatt_new, ARNN, w.ctx, enc, hdec_old, hdec_new, w.cdec, B, c.half_w));
+                break;
+            default:
+                if (enc == 512)
+                    hipLaunchKernelGGL(project_kernel<6>, dim3(21), dim3(256), 0, st, state, j, hdec_new, w.ctx, tc.proj_w,
+                                       tc.proj_b, w.frame, w.dec_out, w.stop_out, w.finished, w.lengths, B);
+                else
+                    hipLaunchKernelGGL(project_kernel<7>, dim3(21), dim3(256), 0, st, state, j, hdec_new, w.ctx, tc.proj_w,
+                                       tc.proj_b, w.frame, w.dec_out, w.stop_out, w.finished, w.lengths, B);
+                break;
+        }
+        HIPCHK(e, hipGetLastError());
+    }
+    timing_end(e);
+    return TTS_HIP_OK;
+}
+
+static int enqueue_step_chunk(tts_hip_engine* e, const DecodeCall& c) {
+    for (int j = 0; j < CHUNK; ++j)
+        if (int rc = enqueue_step(e, c, j)) return rc;
+    hipLaunchKernelGGL(advance_chunk_kernel, dim3(1), dim3(1), 0, e->stream, (DecState*)c.ws.state);
+    return TTS_HIP_OK;
+}
+
+// Each machine runs the loop from a freshly reset loop state and returns TTS_HIP_OK with *steps (and records itself in
+// last_path), DEC_FALL_BACK, or a negative error code.  The BiLSTM status is read at the machine's first synchronisation.
+//
+// Per-step graph: chunks of CHUNK steps, one hipGraph per shape bucket; after each chunk the host reads the loop state (one
+// 32-byte copy).  It never falls back.
+static int run_step_graph(tts_hip_engine* e, const DecodeCall& c, int* steps) {
+    Tacotron2Dev& tc = e->taco;
+    hipStream_t st = e->stream;
+    tc.last_path = DEC_STEP_GRAPH;
+    bool use_graph = !e->timing;                 // per-step HIP events (tts_hip_kernel_timing) cannot be captured
+#ifdef TTS_DEBUG_HOOKS
+    use_graph = use_graph && getenv("TTS_HIP_NO_GRAPH") == nullptr;
+#endif
+    hipGraphExec_t gexec = nullptr;
+    if (use_graph)
+        if (int rc = tc.graphs.get_or_capture(e, graph_key(e, c, DEC_STEP_GRAPH), st, [&] { return enqueue_step_chunk(e, c); }, &gexec))
+            return rc;
+    DecState h{};
+    int bl_err = 0;
+    for (int t0 = 0; t0 < c.max_len; t0 += CHUNK) {
+        if (use_graph) HIPCHK(e, hipGraphLaunch(gexec, st));
+        else if (int rc = enqueue_step_chunk(e, c)) return rc;
+        HIPCHK(e, hipMemcpyAsync(&h, c.ws.state, sizeof h, hipMemcpyDeviceToHost, st));
+        if (t0 == 0) HIPCHK(e, hipMemcpyAsync(&bl_err, c.bl_err, sizeof bl_err, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        if (int rc = check_bilstm_status(e, bl_err)) return rc;
+        *steps = h.steps_run;
+        if (c.early_stop && h.n_fin[0] >= c.B) break;      // the last step of a chunk (odd j) wrote slot 0
+    }
+    return TTS_HIP_OK;
+}
+
+// Persistent weight-stationary loop (taco_persist.hip): the attention context is folded through the four linear maps
+// that consume it -- PM = memory x [W_att[:, ctx] | W_dec[:, ctx] | F[:, ctx] | P[:, ctx]] -- once per utterance.
+// (Its one synchronisation does not read the BiLSTM status: the caller does, with the outputs.)
+static int run_persistent(tts_hip_engine* e, const DecodeCall& c, int* steps) {
+    Tacotron2Dev& tc = e->taco;
+    const int enc = tc.enc_dim;
+    struct Part { const float* Bt; long long ldb; int N, col; };
+    const Part parts[4] = {{tc.att.W + PRE, (long long)PRE + enc + ARNN, 4 * ARNN, PERSIST_COL_ATT},
+                           {tc.dec.W + ARNN, (long long)ARNN + enc + DRNN, 4 * DRNN, PERSIST_COL_DEC},
+                           {tc.pfold_w + DRNN, (long long)DRNN + enc, PRE, PERSIST_COL_F},
+                           {tc.proj_w + DRNN, (long long)DRNN + enc, NMEL + 1, PERSIST_COL_P}};
+    for (const Part& p : parts) {
+        GemmArgs g{};
+        g.M = c.B * c.Tin;
+        g.N = p.N;
+        g.L = g.M;
+        g.nseg = 1;
+        g.seg[0] = ASeg{c.memory, enc, 0, enc, enc};
+        g.Bt = p.Bt;
+        g.ldb = p.ldb;
+        g.mode = EPI_LINEAR;
+        g.split = p.N;
+        g.out0 = c.ws.pm_fold + p.col;
+        g.ld0 = PERSIST_NPM;
+        HIPCHK(e, gemm_small(g, 1, e->stream));
+    }
+    int rc;
+    {
+        // The persistent kernel and the fused step each need every CU of the device at once: two of them from two handles of
+        // one process would hold half the CUs each and wait for the other half (until their bounded waits give up).  One at a
+        // time per device; the work is the same, and nothing deadlocks.  (Another process is handled by the timeouts.)
+        std::lock_guard<std::mutex> whole_gpu(whole_gpu_mutex(e->device));
+        rc = persist_decode(e, e->stream, c, steps);
+    }
+    if (rc == TTS_HIP_OK) tc.last_path = DEC_PERSISTENT;
+    return rc;
+}
+
+struct ChunkReport { FusedState st; int abort_code; int bl_err; int pad[6]; };
+static_assert(sizeof(ChunkReport) == 64, "one report per 64-byte slot");
+
+// Fused two-kernel step (taco_fused.hip): chunks of FUSED_CHUNK steps, one hipGraph per shape bucket; after each chunk the
+// host reads the loop state (32 bytes), the abort flag and the BiLSTM status.  (The call is taken by value: a debug build
+// attaches its trace buffer.)
+static int run_fused(tts_hip_engine* e, DecodeCall c, int* steps) {
+    Tacotron2Dev& tc = e->taco;
+    hipStream_t st = e->stream;
+    std::lock_guard<std::mutex> whole_gpu(whole_gpu_mutex(e->device));      // see run_persistent
+    int rc;
+    if ((rc = fused_init(e, st, c))) return rc;
+    const auto enqueue_chunk = [&] { return fused_enqueue_chunk(e, st, c); };
+    hipGraphExec_t gexec = nullptr;
+    bool fgraph = true, own_graph = false;
+#ifdef TTS_DEBUG_HOOKS
+    fgraph = getenv("TTS_HIP_NO_GRAPH") == nullptr;
+    const char* trace_file = getenv("TTS_FUSED_TRACE_FILE");       // phase timestamps of the first 128 steps (scripts/fused_trace.py)
+    const size_t trace_n = (size_t)128 * 2 * 4 * 16;
+    own_graph = trace_file || getenv("TTS_FUSED_DELAYS");          // (the delays are kernel arguments of the cached graph)
+    if (trace_file) {
+        HIPCHK(e, hipMalloc((void**)&c.trace, trace_n * sizeof(long long)));
+        HIPCHK(e, hipMemsetAsync(c.trace, 0, trace_n * sizeof(long long), st));
+    }
+    // a graph of its own, outside the cache: the trace pointer / delays are baked in
+    if (own_graph && (rc = DecGraphCache::capture(e, st, enqueue_chunk, &gexec))) return rc;
+#endif
+    if (fgraph && !own_graph && (rc = tc.graphs.get_or_capture(e, graph_key(e, c, DEC_FUSED), st, enqueue_chunk, &gexec))) return rc;
+    // Chunk k + 1 is enqueued BEFORE the host looks at chunk k's loop state, so the GPU never waits for the host between
+    // chunks (a sync + relaunch per 32 steps cost ~1.2 us per step); the state travels through a pinned ring.  When chunk k
+    // turns out to have ended the loop, chunk k + 1 is 66 kernels that return at once (~0.1 ms, once per call).
+    if (!tc.pinned) {
+        HIPCHK(e, hipHostMalloc(&tc.pinned, 2 * sizeof(ChunkReport), hipHostMallocDefault));
+        for (auto& ev : tc.chunk_ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    ChunkReport* rep = (ChunkReport*)tc.pinned;
+    const int n_chunks = (c.max_len + FUSED_CHUNK - 1) / FUSED_CHUNK;
+    auto enqueue = [&](int k) -> int {
+        if (fgraph) HIPCHK(e, hipGraphLaunch(gexec, st));
+        else if (int rc2 = enqueue_chunk()) return rc2;
+        HIPCHK(e, hipMemcpyAsync(rep + (k & 1), c.ws.freport, sizeof(ChunkReport), hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipEventRecord(tc.chunk_ev[k & 1], st));
+        return TTS_HIP_OK;
+    };
+    if ((rc = enqueue(0))) return rc;
+    bool aborted = false;
+    int bl_err = 0;
+    for (int k = 0; k < n_chunks; ++k) {
+        if (k + 1 < n_chunks && (rc = enqueue(k + 1))) return rc;
+        HIPCHK(e, hipEventSynchronize(tc.chunk_ev[k & 1]));
+        const ChunkReport h = rep[k & 1];
+        bl_err = h.bl_err;
+        bool stop = false;
+        if (bl_err) {
+            stop = true;
+        } else if (h.abort_code != 0) {             // an exchange timed out (e.g. the GPU was shared and a block lost its CU):
+            aborted = true;                         // start over on the per-step graph
+            stop = true;
+        } else {
+            *steps = h.st.steps_run;
+            if (h.st.steps_run < std::min((k + 1) * FUSED_CHUNK, c.max_len)) stop = true;     // the loop ended inside this chunk
+            if (c.early_stop && h.st.n_fin >= c.B) stop = true;                              // ... or with the stop tokens of its last step
+        }
+        if (stop) {
+            if (k + 1 < n_chunks) HIPCHK(e, hipEventSynchronize(tc.chunk_ev[(k + 1) & 1]));     // the chunk already in flight (it does nothing)
+            break;
+        }
+    }
+    if ((rc = check_bilstm_status(e, bl_err))) return rc;
+    if (!aborted) {
+        tc.fused_fail_streak = 0;
+        tc.last_path = DEC_FUSED;
+    } else {
+        // back off exponentially (1, 2, 4 ... 64 calls on the per-step graph) while another tenant keeps the CUs busy
+        tc.fused_fail_streak = std::min(tc.fused_fail_streak + 1, 7);
+        tc.fused_backoff = 1 << (tc.fused_fail_streak - 1);
+        set_err(e, TTS_HIP_EHIP, "tacotron2 fused decoder: an exchange timed out; fell back to the per-step graph");
+    }
+#ifdef TTS_DEBUG_HOOKS
+    if (own_graph) (void)hipGraphExecDestroy(gexec);
+    if (c.trace) {
+        std::vector<long long> ht(trace_n);
+        (void)hipMemcpy(ht.data(), c.trace, trace_n * sizeof(long long), hipMemcpyDeviceToHost);
+        (void)hipFree(c.trace);
+        if (FILE* f = fopen(trace_file, "wb")) {
+            fwrite(ht.data(), sizeof(long long), trace_n, f);
+            fclose(f);
+        }
+    }
+#endif
+    return aborted ? DEC_FALL_BACK : TTS_HIP_OK;
+}
+
 // Autoregressive loop + postnet from an encoded batch.  Enqueued on e->stream; synchronizes it before returning (the
 // loop's exit is data dependent and `steps_run` / the BiLSTM status are host values).
 static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, int max_len, int early_stop,
@@ -1370,442 +1731,57 @@ static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, i
     if (!en || !en->buf.p || en->B <= 0 || max_len <= 0) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode: bad argument");
     if (en->enc != tc.enc_dim) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode: encoded batch belongs to other weights");
     if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "bad mem kind %d", mem);
-    if (half_w) {
-        int rc16 = tacotron2_build_f16(e);
-        if (rc16) return rc16;
-    }
+    int rc;
+    if (half_w && (rc = tacotron2_build_f16(e))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    const int B = en->B, Tin = en->Tin, enc = tc.enc_dim;
-    const long long R = (long long)B * Tin;          // encoder rows
-    const long long RD = (long long)B * max_len;     // decoder rows
-    // Buffers the step kernels address are sized for max_len rounded up to a bucket, so that every call of a bucket has
-    // the same workspace layout and can replay the same instantiated hipGraph (rows are indexed with the real max_len,
-    // which the kernels read from the device-side loop state).
-    const long long max_len_b = (max_len + 255) / 256 * 256;
-    const long long RB = (long long)B * max_len_b;
-    uint8_t* d_mask = en->mask;
-    int* d_enc_len = en->enc_len;
-    float* d_memory = en->memory;
-    float* d_pm = en->pm;
+    const int B = en->B, Tin = en->Tin;
+    const size_t RD = (size_t)B * max_len;           // decoder rows
 
-    // ---------------- workspace arena
-    // Which machine runs the loop (tts_hip_set_decoder_mode): 0 = the 7-kernel per-step graph only, 1 = persistent kernel when its
-    // shape rule allows, 2 = fused two-kernel step when its shape rule allows, 3 (default) = persistent for 1 - 2 rows, fused
-    // above, whichever is applicable otherwise.  The per-step graph is the fallback of both.
-    bool try_persist = (tc.persist_mode == 1 || tc.persist_mode == 3) && persist_applicable(e, B, Tin);
-    bool try_fused = (tc.persist_mode == 2 || tc.persist_mode == 3) && !e->timing && fused_applicable(e, B, Tin);
-    if (try_persist && try_fused) {
-        if (B <= 2) try_fused = false;
-        else try_persist = false;
-    }
-    const size_t n_xch = std::max(try_persist ? persist_xch_u64(B, Tin) : (size_t)0, try_fused ? fused_xch_u64(B, Tin, enc) : (size_t)0);
+    bool backed_off = false;
+    const DecMachine planned = choose_decoder_machine(e, B, Tin, &backed_off);
     const bool with_masks = prenet_masks != nullptr || mask_seed != nullptr;
-    const size_t n_masks = with_masks ? (size_t)RB * 2 * PRE : 1;
-    const size_t conv_rows = (size_t)std::min<long long>(RD, 32768);     // 512 tiles x 64 rows at most
-    size_t need = 0;
-    auto sz = [&](size_t n, size_t el) { need = (need + 255) / 256 * 256 + n * el; };
-    sz(n_masks, 4); sz(try_persist ? (size_t)R * PERSIST_NPM : 1, 4);
-    sz(64, 4); sz(8, 4); sz(16, 4); sz(n_xch + 2, 8); sz(16, 4);
-    sz(2 * B * ARNN, 4); sz(B * ARNN, 4); sz(2 * B * DRNN, 4); sz(B * DRNN, 4); sz(B * enc, 4); sz(B * PRE, 4); sz(B * ATT, 4);
-    sz(B * NMEL, 4); sz(R, 4); sz(R, 4); sz(R, 4); sz(B, 4); sz(B, 4); sz(2 * B, 4);
-    sz(RB * NMEL, 4); sz(RB, 4); sz(RB * Tin, 4); sz(RD, 1); sz(RD * NMEL, 4); sz(RD * 512, 4); sz(RD * 512, 4);
-    sz(RD * NMEL, 4); sz(RD * NMEL, 4); sz(5 * conv_rows * 512, 4);
-    need += 4096;
-    {
-        const void* before = tc.ws.p;
-        HIPCHK(e, tc.ws.ensure(need));
-        if (tc.ws.p != before) tacotron2_graphs_clear(e);
-    }
-    Arena A;
-    A.base = (char*)tc.ws.p;
-    A.cap = tc.ws.bytes;
-    float* d_masks = A.take<float>(n_masks);
-    float* d_pmfold = A.take<float>(try_persist ? (size_t)R * PERSIST_NPM : 1);
-    DecState* d_state = A.take<DecState>(1);
-    FusedState* d_fstate = A.take<FusedState>(1);
-    int* d_freport = A.take<int>(16);
-    unsigned long long* d_xch = A.take<unsigned long long>(n_xch + 2);
-    int* d_pflags = A.take<int>(16);
-    float* d_hatt = A.take<float>(2 * B * ARNN);
-    float* d_catt = A.take<float>(B * ARNN);
-    float* d_hdec = A.take<float>(2 * B * DRNN);
-    float* d_cdec = A.take<float>(B * DRNN);
-    float* d_ctx = A.take<float>(B * enc);
-    float* d_p2 = A.take<float>(B * PRE);
-    float* d_q = A.take<float>(B * ATT);
-    float* d_frame = A.take<float>(B * NMEL);
-    float* d_energy = A.take<float>(R);
-    float* d_wprev = A.take<float>(R);
-    float* d_wcum = A.take<float>(R);
-    int* d_finished = A.take<int>(B);
-    int* d_lengths = A.take<int>(B);
-    int* d_mainatt = A.take<int>(2 * B);
-    float* d_decout = A.take<float>(RB * NMEL);
-    float* d_stop = A.take<float>(RB);
-    float* d_attn = A.take<float>(RB * Tin);
-    uint8_t* d_dmask = A.take<uint8_t>(RD);
-    float* d_xm = A.take<float>(RD * NMEL);
-    float* d_pa = A.take<float>(RD * 512);
-    float* d_pb = A.take<float>(RD * 512);
-    float* d_post = A.take<float>(RD * NMEL);
-    float* d_mel = A.take<float>(RD * NMEL);
-    float* d_convtmp = A.take<float>(5 * conv_rows * 512);
-    const size_t convtmp_n = 5 * conv_rows * 512;
-    if (A.off > A.cap) return set_err(e, TTS_HIP_ENOMEM, "tacotron2 workspace accounting error");
-    // all recurrent state, loop state, exchange area, histories and outputs of the real rows start at zero
-    const size_t zero_from = (char*)d_state - A.base, zero_mid = (char*)d_decout - A.base;
-    auto zero_state = [&]() -> int {
-        HIPCHK(e, hipMemsetAsync(A.base + zero_from, 0, zero_mid - zero_from, st));
-        HIPCHK(e, hipMemsetAsync(d_decout, 0, (size_t)RD * NMEL * 4, st));
-        HIPCHK(e, hipMemsetAsync(d_stop, 0, (size_t)RD * 4, st));
-        HIPCHK(e, hipMemsetAsync(d_attn, 0, (size_t)RD * Tin * 4, st));
-        return TTS_HIP_OK;
-    };
-    int rc;
-    if ((rc = zero_state())) return rc;
+    DecoderWs ws{};
+    if ((rc = plan_workspace(e, tc.ws, 4096, [&](Arena& A) { ws = decoder_layout(A, e, planned, B, Tin, max_len, with_masks); })))
+        return rc;
+    const DecodeCall call{B, Tin, max_len, early_stop ? 1 : 0, win_len, win_offset, half_w, en->buf.p, en->memory, en->pm,
+                          en->mask, en->enc_len, en->bl_err, with_masks ? ws.masks : nullptr, ws};
 
     // prenet dropout masks always travel through the workspace: a captured graph must not hold a caller's pointer
     const hipMemcpyKind kin = mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    const float* masks_dev = nullptr;
     if (prenet_masks) {
-        HIPCHK(e, hipMemcpyAsync(d_masks, prenet_masks, (size_t)RD * 2 * PRE * 4, kin, st));
-        masks_dev = d_masks;
+        HIPCHK(e, hipMemcpyAsync(ws.masks, prenet_masks, RD * 2 * PRE * 4, kin, st));
     } else if (mask_seed) {                                 // drawn on the device, straight into the workspace
-        if ((rc = philox_fill(e, d_masks, (long long)RD * 2 * PRE, mask_seed[0], mask_seed[1], TTS_HIP_RANDOM_PRENET_MASK, st))) return rc;
-        masks_dev = d_masks;
+        if ((rc = philox_fill(e, ws.masks, (long long)RD * 2 * PRE, mask_seed[0], mask_seed[1], TTS_HIP_RANDOM_PRENET_MASK, st))) return rc;
     }
 
-    // ---------------- decoder loop
-    hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, st, d_state, B, max_len, early_stop ? 1 : 0);
-    HIPCHK(e, hipGetLastError());
-    const size_t sm_lds = (size_t)Tin * sizeof(float);
-    // Measurement hook (results are garbage when set): TTS_HIP_DEBUG_ONLY_KERNEL=k launches only step kernel k (0 prenet,
-    // 1 attention LSTM, 2 query, 3 energies, 4 softmax_ctx, 5 decoder LSTM, 6 project) seven times per step, which gives
-    // that kernel's cost inside the graph without the other six around it (scripts/run_taco.py prints the step time).
-    // Only exists in a build made with -DTTS_DEBUG_HOOKS (csrc/build.sh never passes it).
-#ifdef TTS_DEBUG_HOOKS
-    const char* only_env = getenv("TTS_HIP_DEBUG_ONLY_KERNEL");
-    const int only = only_env ? atoi(only_env) : -1;
-#else
-    constexpr int only = -1;
-#endif
-    auto enqueue_step = [&](int j) -> int {
-        const int par = j & 1;                       // CHUNK is even, so the parity of t equals the parity of j
-        float* hatt_old = d_hatt + (size_t)par * B * ARNN;
-        float* hatt_new = d_hatt + (size_t)(par ^ 1) * B * ARNN;
-        float* hdec_old = d_hdec + (size_t)par * B * DRNN;
-        float* hdec_new = d_hdec + (size_t)(par ^ 1) * B * DRNN;
-        timing_begin(e, 2);
-        auto k_prenet = [&]() -> int {
-            hipLaunchKernelGGL(prenet_kernel, dim3(B, 8), dim3(256), 0, st, d_state, j, d_frame, tc.prenet_w0,
-                               tc.prenet_w1, masks_dev, d_p2);
-            HIPCHK(e, hipGetLastError());
-            return TTS_HIP_OK;
-        };
-        auto k_att = [&]() -> int {
-            HIPCHK(e, lstm_dispatch(st, d_state, j, tc.att, d_p2, PRE, d_ctx, enc, hatt_old, hatt_new, d_catt, B, half_w));
-            return TTS_HIP_OK;
-        };
-        auto k_query = [&]() -> int {
-            hipLaunchKernelGGL(query_kernel, dim3(ATT / 2), dim3(256), 0, st, d_state, j, hatt_new, tc.query_w, d_q, B);
-            HIPCHK(e, hipGetLastError());
-            return TTS_HIP_OK;
-        };
-        auto k_energies = [&]() -> int {
-            hipLaunchKernelGGL(energies_kernel, dim3(B, (Tin + EPB - 1) / EPB), dim3(256), 0, st, d_state, j, d_q, tc.loc_dense,
-                               tc.value_w, d_pm, d_wprev, d_wcum, d_energy, Tin);
-            HIPCHK(e, hipGetLastError());
-            return TTS_HIP_OK;
-        };
-        auto k_softmax = [&]() -> int {
-            hipLaunchKernelGGL(softmax_ctx_kernel, dim3(B, enc / 32), dim3(256), sm_lds, st, d_state, j, d_energy, d_mask,
-                               d_enc_len, win_len, win_offset, d_mainatt + par * B, d_mainatt + (par ^ 1) * B, d_memory,
-                               d_wprev, d_wcum, d_ctx, d_attn, Tin, enc);
-            HIPCHK(e, hipGetLastError());
-            return TTS_HIP_OK;
-        };
-        auto k_dec = [&]() -> int {
-            HIPCHK(e, lstm_dispatch(st, d_state, j, tc.dec, hatt_new, ARNN, d_ctx, enc, hdec_old, hdec_new, d_cdec, B, half_w));
-            return TTS_HIP_OK;
-        };
-        auto k_project = [&]() -> int {
-            if (enc == 512)
-                hipLaunchKernelGGL(project_kernel<6>, dim3(21), dim3(256), 0, st, d_state, j, hdec_new, d_ctx, tc.proj_w,
-                                   tc.proj_b, d_frame, d_decout, d_stop, d_finished, d_lengths, B);
-            else
-                hipLaunchKernelGGL(project_kernel<7>, dim3(21), dim3(256), 0, st, d_state, j, hdec_new, d_ctx, tc.proj_w,
-                                   tc.proj_b, d_frame, d_decout, d_stop, d_finished, d_lengths, B);
-            HIPCHK(e, hipGetLastError());
-            return TTS_HIP_OK;
-        };
-        int rcs = TTS_HIP_OK;
-        for (int k = 0; k < 7 && rcs == TTS_HIP_OK; ++k) {
-            switch (only >= 0 ? only : k) {
-                case 0: rcs = k_prenet(); break;
-                case 1: rcs = k_att(); break;
-                case 2: rcs = k_query(); break;
-                case 3: rcs = k_energies(); break;
-                case 4: rcs = k_softmax(); break;
-                case 5: rcs = k_dec(); break;
-                default: rcs = k_project(); break;
-            }
-        }
-        if (rcs) return rcs;
-        timing_end(e);
-        return TTS_HIP_OK;
-    };
+    // ---------------- decoder loop: the chosen machine, and the per-step graph from the start when that one gives up
+    if ((rc = reset_loop_state(e, call))) return rc;
     int host_steps = 0;
-    bool persisted = false, fused = false;
-    // the workspace layout (and with it every pointer a captured graph holds) depends on which exchange areas were sized in
-    const int layout_id = (try_persist ? 1 : 0) | (try_fused ? 2 : 0);
-    // instantiated chunk graphs are kept and replayed by every later call with the same shape bucket: the workspace and the
-    // encoded batch are stable allocations, so the kernel nodes hold valid pointers
-    auto cached_graph = [&](const DecGraphKey& key, auto&& enqueue, hipGraphExec_t* out) -> int {
-        auto it = tc.graphs.find(key);
-        if (it != tc.graphs.end()) {
-            *out = it->second;
-            return TTS_HIP_OK;
-        }
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t gexec = nullptr;
-        HIPCHK(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        const int crc = enqueue();
-        hipError_t ce = hipStreamEndCapture(st, &graph);
-        if (crc != TTS_HIP_OK || ce != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            if (crc != TTS_HIP_OK) return crc;
-            HIPCHK(e, ce);
-        }
-        hipError_t ie = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);             // the executable graph is self-contained
-        HIPCHK(e, ie);
-        constexpr size_t kMaxGraphs = 16;
-        if (tc.graph_order.size() >= kMaxGraphs) {
-            auto old = tc.graphs.find(tc.graph_order.front());
-            if (old != tc.graphs.end()) {
-                (void)hipGraphExecDestroy(old->second);
-                tc.graphs.erase(old);
-            }
-            tc.graph_order.erase(tc.graph_order.begin());
-        }
-        tc.graphs[key] = gexec;
-        tc.graph_order.push_back(key);
-        *out = gexec;
-        return TTS_HIP_OK;
-    };
-    int bl_err = 0;
-    bool bl_checked = false;
-    bool try_fused_now = try_fused;
-    if (try_persist) {
-        // Persistent weight-stationary loop (taco_persist.hip): the attention context is folded through the four linear maps
-        // that consume it -- PM = memory x [W_att[:, ctx] | W_dec[:, ctx] | F[:, ctx] | P[:, ctx]] -- once per utterance.
-        struct Part { const float* Bt; long long ldb; int N, col; };
-        const Part parts[4] = {{tc.att.W + PRE, (long long)PRE + enc + ARNN, 4 * ARNN, PERSIST_COL_ATT},
-                               {tc.dec.W + ARNN, (long long)ARNN + enc + DRNN, 4 * DRNN, PERSIST_COL_DEC},
-                               {tc.pfold_w + DRNN, (long long)DRNN + enc, PRE, PERSIST_COL_F},
-                               {tc.proj_w + DRNN, (long long)DRNN + enc, NMEL + 1, PERSIST_COL_P}};
-        for (const Part& p : parts) {
-            GemmArgs g{};
-            g.M = (int)R;
-            g.N = p.N;
-            g.L = (int)R;
-            g.nseg = 1;
-            g.seg[0] = ASeg{d_memory, enc, 0, enc, enc};
-            g.Bt = p.Bt;
-            g.ldb = p.ldb;
-            g.mode = EPI_LINEAR;
-            g.split = p.N;
-            g.out0 = d_pmfold + p.col;
-            g.ld0 = PERSIST_NPM;
-            HIPCHK(e, gemm_small(g, 1, st));
-        }
-        PersistCall pc{};
-        pc.B = B; pc.Tin = Tin; pc.max_len = max_len; pc.early_stop = early_stop ? 1 : 0;
-        pc.win_len = win_len; pc.win_off = win_offset; pc.half_w = half_w;
-        pc.memory = d_memory; pc.pm = d_pm; pc.mask = d_mask; pc.enc_len = d_enc_len; pc.masks = masks_dev;
-        pc.pm_fold = d_pmfold; pc.xch = d_xch; pc.flags = d_pflags;
-        pc.dec_out = d_decout; pc.stop_out = d_stop; pc.attn_hist = d_attn; pc.lengths = d_lengths; pc.finished = d_finished;
-        // The persistent kernel and the fused step each need every CU of the device at once: two of them from two handles of
-        // one process would hold half the CUs each and wait for the other half (until their bounded waits give up).  One at a
-        // time per device; the work is the same, and nothing deadlocks.  (Another process is handled by the timeouts.)
-        std::unique_lock<std::mutex> whole_gpu(whole_gpu_mutex(e->device));
-        const int prc = persist_decode(e, st, pc, &host_steps);
-        whole_gpu.unlock();
-        if (prc < 0) return prc;
-        persisted = prc == TTS_HIP_OK;                  // 1: the grid could not become resident -> per-step graph below
-        if (prc == 2) {                                 // gave up in mid-loop: start over on the per-step graph
-            if ((rc = zero_state())) return rc;
-            hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, st, d_state, B, max_len, early_stop ? 1 : 0);
-            HIPCHK(e, hipGetLastError());
-        }
+    const DecMachine machine = backed_off ? DEC_STEP_GRAPH : planned;
+    rc = machine == DEC_PERSISTENT ? run_persistent(e, call, &host_steps)
+         : machine == DEC_FUSED    ? run_fused(e, call, &host_steps)
+                                   : run_step_graph(e, call, &host_steps);
+    if (rc == DEC_FALL_BACK) {
+        if ((rc = reset_loop_state(e, call))) return rc;
+        rc = run_step_graph(e, call, &host_steps);
     }
-    if (try_fused && tc.fused_backoff > 0) {
-        --tc.fused_backoff;                              // a recent call timed out (the GPU is shared): not this time
-        try_fused_now = false;
-    }
-    if (try_fused_now) {
-        std::unique_lock<std::mutex> whole_gpu(whole_gpu_mutex(e->device));      // see the persistent section above
-        // Fused two-kernel step (taco_fused.hip): chunks of FUSED_CHUNK steps, one hipGraph per shape bucket; after each chunk
-        // the host reads the loop state (32 bytes) and the abort flag.
-        FusedCall fc{};
-        fc.B = B; fc.Tin = Tin; fc.max_len = max_len; fc.early_stop = early_stop ? 1 : 0;
-        fc.win_len = win_len; fc.win_off = win_offset; fc.half_w = half_w;
-        fc.memory = d_memory; fc.pm = d_pm; fc.mask = d_mask; fc.enc_len = d_enc_len; fc.masks = masks_dev;
-        fc.xch = d_xch; fc.flags = d_pflags; fc.state = d_fstate; fc.bl_err = en->bl_err; fc.report = d_freport;
-        fc.hatt = d_hatt; fc.hdec = d_hdec; fc.catt = d_catt; fc.cdec = d_cdec; fc.ctx = d_ctx;
-        fc.wprev = d_wprev; fc.wcum = d_wcum; fc.mainatt = d_mainatt;
-        fc.dec_out = d_decout; fc.stop_out = d_stop; fc.attn_hist = d_attn; fc.lengths = d_lengths; fc.finished = d_finished;
-        if ((rc = fused_init(e, st, fc))) return rc;
-        hipGraphExec_t gexec = nullptr;
-#ifdef TTS_DEBUG_HOOKS
-        const bool fgraph = getenv("TTS_HIP_NO_GRAPH") == nullptr;
-        const char* trace_file = getenv("TTS_FUSED_TRACE_FILE");       // phase timestamps of the first 128 steps (scripts/fused_trace.py)
-        const size_t trace_n = (size_t)128 * 2 * 4 * 16;
-        const bool own_graph = trace_file || getenv("TTS_FUSED_DELAYS");   // (the delays are kernel arguments of the cached graph)
-        if (own_graph) {
-            if (trace_file) {
-                HIPCHK(e, hipMalloc((void**)&fc.trace, trace_n * sizeof(long long)));
-                HIPCHK(e, hipMemsetAsync(fc.trace, 0, trace_n * sizeof(long long), st));
-            }
-            hipGraph_t graph = nullptr;                                 // a graph of its own: the trace pointer / delays are baked in
-            HIPCHK(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            const int crc = fused_enqueue_chunk(e, st, fc);
-            HIPCHK(e, hipStreamEndCapture(st, &graph));
-            if (crc) return crc;
-            HIPCHK(e, hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-        }
-#else
-        constexpr bool fgraph = true;
-        constexpr bool own_graph = false;
-#endif
-        if (fgraph && !own_graph) {
-            const DecGraphKey key{tc.ws.p, en->buf.p, B, Tin, (int)max_len_b, with_masks ? 1 : 0, win_len, win_offset,
-                                  half_w ? 1 : 0, layout_id | 4};
-            if ((rc = cached_graph(key, [&]() { return fused_enqueue_chunk(e, st, fc); }, &gexec))) return rc;
-        }
-        // Chunk k + 1 is enqueued BEFORE the host looks at chunk k's loop state, so the GPU never waits for the host between
-        // chunks (a sync + relaunch per 32 steps cost ~1.2 us per step); the state travels through a pinned ring.  When chunk k
-        // turns out to have ended the loop, chunk k + 1 is 66 kernels that return at once (~0.1 ms, once per call).
-        struct ChunkReport { FusedState st; int abort_code; int bl_err; int pad[6]; };
-        static_assert(sizeof(ChunkReport) == 64, "one report per 64-byte slot");
-        if (!tc.pinned) {
-            HIPCHK(e, hipHostMalloc(&tc.pinned, 2 * sizeof(ChunkReport), hipHostMallocDefault));
-            for (auto& ev : tc.chunk_ev) HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        }
-        ChunkReport* rep = (ChunkReport*)tc.pinned;
-        fused = true;
-        const int n_chunks = (max_len + FUSED_CHUNK - 1) / FUSED_CHUNK;
-        auto enqueue = [&](int k) -> int {
-            if (fgraph) HIPCHK(e, hipGraphLaunch(gexec, st));
-            else if (int rc2 = fused_enqueue_chunk(e, st, fc)) return rc2;
-            HIPCHK(e, hipMemcpyAsync(rep + (k & 1), d_freport, sizeof(ChunkReport), hipMemcpyDeviceToHost, st));
-            HIPCHK(e, hipEventRecord(tc.chunk_ev[k & 1], st));
-            return TTS_HIP_OK;
-        };
-        if ((rc = enqueue(0))) return rc;
-        for (int k = 0; k < n_chunks; ++k) {
-            if (k + 1 < n_chunks && (rc = enqueue(k + 1))) return rc;
-            HIPCHK(e, hipEventSynchronize(tc.chunk_ev[k & 1]));
-            const ChunkReport h = rep[k & 1];
-            bl_checked = true;
-            bl_err = h.bl_err;
-            bool stop = false;
-            if (bl_err) {
-                stop = true;
-            } else if (h.abort_code != 0) {             // an exchange timed out (e.g. the GPU was shared and a block lost its CU):
-                fused = false;                          // start over on the per-step graph
-                stop = true;
-            } else {
-                host_steps = h.st.steps_run;
-                if (h.st.steps_run < std::min((k + 1) * FUSED_CHUNK, max_len)) stop = true;      // the loop ended inside this chunk
-                if (early_stop && h.st.n_fin >= B) stop = true;                                  // ... or with the stop tokens of its last step
-            }
-            if (stop) {
-                if (k + 1 < n_chunks) HIPCHK(e, hipEventSynchronize(tc.chunk_ev[(k + 1) & 1]));     // the chunk already in flight (it does nothing)
-                break;
-            }
-        }
-        if (bl_err) return set_err(e, TTS_HIP_EHIP, "tacotron2 encoder: BiLSTM block exchange timed out");
-        if (fused) {
-            tc.fused_fail_streak = 0;
-        } else {
-            // back off exponentially (1, 2, 4 ... 64 calls on the per-step graph) while another tenant keeps the CUs busy
-            tc.fused_fail_streak = std::min(tc.fused_fail_streak + 1, 7);
-            tc.fused_backoff = 1 << (tc.fused_fail_streak - 1);
-            set_err(e, TTS_HIP_EHIP, "tacotron2 fused decoder: an exchange timed out; fell back to the per-step graph");
-            if ((rc = zero_state())) return rc;
-            hipLaunchKernelGGL(init_state_kernel, dim3(1), dim3(1), 0, st, d_state, B, max_len, early_stop ? 1 : 0);
-            HIPCHK(e, hipGetLastError());
-        }
-#ifdef TTS_DEBUG_HOOKS
-        if (own_graph && !fc.trace) (void)hipGraphExecDestroy(gexec);
-        if (fc.trace) {
-            std::vector<long long> ht(trace_n);
-            (void)hipMemcpy(ht.data(), fc.trace, trace_n * sizeof(long long), hipMemcpyDeviceToHost);
-            (void)hipFree(fc.trace);
-            (void)hipGraphExecDestroy(gexec);
-            if (FILE* f = fopen(trace_file, "wb")) {
-                fwrite(ht.data(), sizeof(long long), trace_n, f);
-                fclose(f);
-            }
-        }
-#endif
-    }
-    tc.last_path = persisted ? 1 : fused ? 2 : 0;
-    if (!persisted && !fused) {
-        // chunks of CHUNK steps; after each chunk the host reads the loop state (one 32-byte copy)
-        DecState h{};
-#ifdef TTS_DEBUG_HOOKS
-        const bool use_graph = !e->timing && getenv("TTS_HIP_NO_GRAPH") == nullptr;
-#else
-        const bool use_graph = !e->timing;           // per-step HIP events (tts_hip_kernel_timing) cannot be captured
-#endif
-        hipGraphExec_t gexec = nullptr;
-        if (use_graph) {
-            const DecGraphKey key{tc.ws.p, en->buf.p, B, Tin, (int)max_len_b, with_masks ? 1 : 0, win_len, win_offset,
-                                  half_w ? 1 : 0, layout_id};
-            auto enqueue = [&]() -> int {
-                int crc = TTS_HIP_OK;
-                for (int j = 0; j < CHUNK && crc == TTS_HIP_OK; ++j) crc = enqueue_step(j);
-                if (crc == TTS_HIP_OK) hipLaunchKernelGGL(advance_chunk_kernel, dim3(1), dim3(1), 0, st, d_state);
-                return crc;
-            };
-            if ((rc = cached_graph(key, enqueue, &gexec))) return rc;
-        }
-        for (int t0 = 0; t0 < max_len; t0 += CHUNK) {
-            if (use_graph) {
-                HIPCHK(e, hipGraphLaunch(gexec, st));
-            } else {
-                for (int j = 0; j < CHUNK; ++j)
-                    if ((rc = enqueue_step(j))) return rc;
-                hipLaunchKernelGGL(advance_chunk_kernel, dim3(1), dim3(1), 0, st, d_state);
-            }
-            HIPCHK(e, hipMemcpyAsync(&h, d_state, sizeof h, hipMemcpyDeviceToHost, st));
-            if (t0 == 0) HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, st));
-            HIPCHK(e, hipStreamSynchronize(st));
-            bl_checked = true;
-            if (bl_err) return set_err(e, TTS_HIP_EHIP, "tacotron2 encoder: BiLSTM block exchange timed out");
-            host_steps = h.steps_run;
-            if (early_stop && h.n_fin[0] >= B) break;      // the last step of a chunk (odd j) wrote slot 0
-        }
-    }
+    if (rc) return rc;
 
     // ---------------- postnet + residual
-    const PostnetBufs pbufs{d_dmask, d_xm, d_pa, d_pb, d_post, d_mel, d_convtmp, convtmp_n};
-    if ((rc = postnet_residual(e, d_lengths, d_decout, B, max_len, pbufs))) return rc;
+    if ((rc = postnet_residual(e, ws.lengths, ws.dec_out, B, max_len, ws.post))) return rc;
 
     // ---------------- outputs
     const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (mel) HIPCHK(e, hipMemcpyAsync(mel, d_mel, RD * NMEL * 4, kout, st));
-    if (decoder_output) HIPCHK(e, hipMemcpyAsync(decoder_output, d_decout, RD * NMEL * 4, kout, st));
-    if (stop_tokens) HIPCHK(e, hipMemcpyAsync(stop_tokens, d_stop, RD * 4, kout, st));
-    if (attention) HIPCHK(e, hipMemcpyAsync(attention, d_attn, RD * Tin * 4, kout, st));
-    if (lengths) HIPCHK(e, hipMemcpyAsync(lengths, d_lengths, (size_t)B * 4, kout, st));
-    if (!bl_checked) HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, st));
+    if (mel) HIPCHK(e, hipMemcpyAsync(mel, ws.post.mel, RD * NMEL * 4, kout, st));
+    if (decoder_output) HIPCHK(e, hipMemcpyAsync(decoder_output, ws.dec_out, RD * NMEL * 4, kout, st));
+    if (stop_tokens) HIPCHK(e, hipMemcpyAsync(stop_tokens, ws.stop_out, RD * 4, kout, st));
+    if (attention) HIPCHK(e, hipMemcpyAsync(attention, ws.attn_hist, RD * Tin * 4, kout, st));
+    if (lengths) HIPCHK(e, hipMemcpyAsync(lengths, ws.lengths, (size_t)B * 4, kout, st));
+    int bl_err = 0;                                  // the persistent kernel's own synchronisation did not read it
+    if (tc.last_path == DEC_PERSISTENT) HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
-    if (bl_err) return set_err(e, TTS_HIP_EHIP, "tacotron2 encoder: BiLSTM block exchange timed out");
+    if ((rc = check_bilstm_status(e, bl_err))) return rc;
     if (steps_run) *steps_run = host_steps;
     return TTS_HIP_OK;
 }
@@ -1882,37 +1858,19 @@ extern "C" int tts_hip_tacotron2_decode_seeded(tts_hip_engine* e, const tts_hip_
                                  attention, lengths, steps_run, mem, precision == 1, ms);
 }
 
-// cached decoder graphs whose kernel nodes point into `buf` (the graphs of other encoded batches stay valid)
-static void tacotron2_graphs_drop(tts_hip_engine* e, const void* buf) {
-    auto& tc = e->taco;
-    for (auto it = tc.graphs.begin(); it != tc.graphs.end();) {
-        if (it->first.enc_buf == buf) {
-            (void)hipGraphExecDestroy(it->second);
-            for (auto o = tc.graph_order.begin(); o != tc.graph_order.end();)
-                o = (!(*o < it->first) && !(it->first < *o)) ? tc.graph_order.erase(o) : std::next(o);
-            it = tc.graphs.erase(it);
-        } else {
-            ++it;
-        }
-    }
-}
-
 extern "C" int tts_hip_tacotron2_reencode(tts_hip_engine* e, tts_hip_encoded* encoded, const int32_t* tokens, int B, int Tin,
                                           const float* speaker, int mem, void* stream) {
     if (!e || !encoded) return TTS_HIP_EINVAL;
     StreamScope scope(e, stream);
-    const void* before = encoded->buf.p;
     // (the encoder itself drops every cached graph if the buffer has to grow; a buffer that stays keeps its graphs: the next
     // sentence of the same shape bucket replays them)
-    const int rc = tacotron2_encode_impl(e, tokens, B, Tin, speaker, mem, encoded);
-    (void)before;
-    return rc;
+    return tacotron2_encode_impl(e, tokens, B, Tin, speaker, mem, encoded);
 }
 
 extern "C" int tts_hip_encoded_free(tts_hip_engine* e, tts_hip_encoded* encoded) {
     if (!e || !encoded) return TTS_HIP_EINVAL;
     (void)hipSetDevice(e->device);
-    tacotron2_graphs_drop(e, encoded->buf.p);          // only the cached graphs that point into this buffer
+    e->taco.graphs.drop_if(encoded->buf.p);          // only the cached graphs that point into this buffer
     encoded->buf.release();                            // hipFree waits for work that still uses it
     delete encoded;
     return TTS_HIP_OK;
@@ -1940,8 +1898,7 @@ extern "C" int tts_hip_tacotron2_probe_encoder(tts_hip_engine* e, const int32_t*
     HIPCHK(e, hipMemcpyAsync(out, src, (size_t)B * Tin * width * 4, kout, e->stream));
     if (what >= 3) HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    if (bl_err) return set_err(e, TTS_HIP_EHIP, "tacotron2 encoder: BiLSTM block exchange timed out");
-    return TTS_HIP_OK;
+    return check_bilstm_status(e, bl_err);
 }
 
 // Postnet of tacotron2_decode_impl on caller frames [B][T][80] with host lengths[B] (mask t <= lengths[b]): what 0 .. 4
@@ -1957,32 +1914,15 @@ extern "C" int tts_hip_tacotron2_probe_postnet(tts_hip_engine* e, const float* f
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = e->stream;
     const long long RD = (long long)B * T;
-    const size_t conv_rows = (size_t)std::min<long long>(RD, 32768);
-    size_t need = 0;
-    auto sz = [&](size_t n, size_t el) { need = (need + 255) / 256 * 256 + n * el; };
-    sz(B, 4); sz(RD * NMEL, 4); sz(RD, 1); sz(RD * NMEL, 4); sz(RD * 512, 4); sz(RD * 512, 4); sz(RD * NMEL, 4);
-    sz(RD * NMEL, 4); sz(5 * conv_rows * 512, 4);
-    need += 4096;
-    {
-        const void* before = tc.ws.p;
-        HIPCHK(e, tc.ws.ensure(need));
-        if (tc.ws.p != before) tacotron2_graphs_clear(e);      // cached step graphs hold pointers into the workspace
-    }
-    Arena A;
-    A.base = (char*)tc.ws.p;
-    A.cap = tc.ws.bytes;
-    int* d_lengths = A.take<int>(B);
-    float* d_frames = A.take<float>(RD * NMEL);
+    int* d_lengths = nullptr;
+    float* d_frames = nullptr;
     PostnetBufs pb{};
-    pb.dmask = A.take<uint8_t>(RD);
-    pb.xm = A.take<float>(RD * NMEL);
-    pb.pa = A.take<float>(RD * 512);
-    pb.pb = A.take<float>(RD * 512);
-    pb.post = A.take<float>(RD * NMEL);
-    pb.mel = A.take<float>(RD * NMEL);
-    pb.convtmp = A.take<float>(5 * conv_rows * 512);
-    pb.convtmp_n = 5 * conv_rows * 512;
-    if (A.off > A.cap) return set_err(e, TTS_HIP_ENOMEM, "tacotron2 workspace accounting error");
+    if (int rc = plan_workspace(e, tc.ws, 4096, [&](Arena& A) {
+            d_lengths = A.take<int>(B);
+            d_frames = A.take<float>(RD * NMEL);
+            pb = postnet_layout(A, RD);
+        }))
+        return rc;
     const hipMemcpyKind kin = mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     HIPCHK(e, hipMemcpyAsync(d_lengths, lengths, (size_t)B * 4, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(d_frames, frames, (size_t)RD * NMEL * 4, kin, st));
