@@ -245,6 +245,31 @@ int tts_hip_waveglow_infer_ragged(tts_hip_engine* e, const float* mel, int B, in
 int tts_hip_waveglow_infer_ragged_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
                                         const float* z, float sigma, float* audio, int precision, void* stream);
 
+/* ---- the same contract, computed as ONE packed row
+ * Arguments, memory kinds and results as tts_hip_waveglow_infer_ragged[_async] (lengths must not be NULL): audio[b,
+ * :lengths[b]*256] is what a one-row call on the row's own frames returns, audio[b, lengths[b]*256:] = 0 exactly, nothing
+ * beyond a row's length is read.  Only the way it is computed differs: the real frames of all rows are laid one after
+ * another in one row of F = sum(lengths) + TTS_HIP_WG_GAP_FRAMES * (rows with frames - 1) frames, separated by runs of zero
+ * "gap" frames that are marked as not real (rows of length 0 take no space and no gap), and that row runs as an ordinary
+ * one-row call -- the work follows the frames that exist, not B * max(lengths).  A gather builds the packed mel / z from
+ * the batch layout and a scatter writes every sample of `audio` (zero tails included) from the packed result.
+ * tts_hip_last_waveglow_form / _tiles then describe the packed run (B = 1, T = F).  The packed row is one run: F above
+ * 31744 frames is TTS_HIP_EINVAL (the message names F and the limit; nothing is launched, and there is no fall-back to the
+ * ragged call), while T alone is not limited.
+ *
+ * The gap length follows from the model.  A frame that is not real is held at 0 in the WN residual stream (after the start
+ * conv and after every residual sum), in the first-layer operand, in the flow state and in the mel, so to its neighbours
+ * it looks like the zero padding a run of the row alone has there.  One WN layer reaches at most 2^7 positions = 4 frames
+ * to either side (kernel 3, dilation 2^i, i <= 7, 32 positions per frame) and the residual stream is re-zeroed after every
+ * layer, so nothing travels further than that; the folded conditioning reads mel frames t-3 .. t.  With 4 gap frames no
+ * tap of a real position lands on another row's frame; with 3 the dilation-128 taps do (numpy oracle, segments of 6, 1
+ * and 5 frames: RMS against the solo runs 2.6e-7 with 4 gap frames, 1.2e-2 .. 5.5e-2 with 3; tests/test_waveglow_packed.py). */
+#define TTS_HIP_WG_GAP_FRAMES 4
+int tts_hip_waveglow_infer_packed(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths, const float* z,
+                                  float sigma, float* audio, int precision, int mem);
+int tts_hip_waveglow_infer_packed_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
+                                        const float* z, float sigma, float* audio, int precision, void* stream);
+
 /* ---- TacotronSTFT.mel_spectrogram  (utils/audio/stft.py:242-274,306-314)
  * audio [B, N] (N >= 1024) -> mel [B, N/256 + 1, 80]                                                                */
 int tts_hip_mel_stft(tts_hip_engine* e, const float* audio, int B, int N, float* mel, int mem);

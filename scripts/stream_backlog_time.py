@@ -1,10 +1,11 @@
 """Timing: `predict()` over a backlog of sentences -- sequential (every sentence alone at batch 1) against `batch_backlog=8`
-(waiting sentences decoded as one token batch on the fused step and vocoded in one ragged WaveGlow call).  The workload of
+(waiting sentences decoded as one token batch on the fused step and vocoded in one ragged WaveGlow call) and against the same
+with `pack_vocoder=True` (that one vocoder call computed as one packed row; mode `packed`, with `--mode all`).  The workload of
 bench.py's config 5: 64 sentences, token counts cycling 50 .. 200, fp16 modes of both models, max_length=4., deterministic.
 Reports x real time (audio seconds per wall second) and the time to the first sentence's audio for each mode; the modes
 alternate, each run ends with its last callback (host arrays: every device call has finished).
 
-  python scripts/stream_backlog_time.py [--root DIR] [--mode both|sequential|backlog] [--k 8] [--reps 3]
+  python scripts/stream_backlog_time.py [--root DIR] [--mode both|all|sequential|backlog|packed] [--k 8] [--reps 3]
 
 --root: the tree whose `text_to_speech_amd` is imported (default: this one) -- `--root <checkout of an older commit> --mode
 sequential` times that commit's stream for comparison.  Prints one JSON line."""
@@ -13,7 +14,7 @@ import numpy as np
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ap.add_argument('--mode', default='both', choices=('both', 'sequential', 'backlog'))
+ap.add_argument('--mode', default='both', choices=('both', 'all', 'sequential', 'backlog', 'packed'))
 ap.add_argument('--k', type=int, default=8)
 ap.add_argument('--reps', type=int, default=3)
 args = ap.parse_args()
@@ -36,8 +37,8 @@ letters = np.array(list('abcdefghijklmnopqrstuvwxyz     '))
 lens = [50, 70, 90, 110, 130, 150, 170, 200]
 texts = [''.join(rng.choice(letters, lens[i % 8])).strip() + f' {i}.' for i in range(64)]
 kw = dict(vocoder=voc, max_length=4., deterministic=True, save=False, return_results=False)
-extra = {'sequential': {}, 'backlog': {'batch_backlog': args.k}}
-modes = ('sequential', 'backlog') if args.mode == 'both' else (args.mode,)
+extra = {'sequential': {}, 'backlog': {'batch_backlog': args.k}, 'packed': {'batch_backlog': args.k, 'pack_vocoder': True}}
+modes = {'both': ('sequential', 'backlog'), 'all': ('sequential', 'backlog', 'packed')}.get(args.mode, (args.mode,))
 
 
 def run(mode, items):
@@ -69,7 +70,9 @@ for m in modes:
     out[f'{m}_first_audio_ms_median'] = float(np.median([r[2] for r in res[m]])) * 1e3
     out[f'{m}_decoder_path'] = res[m][-1][3]
 out['audio_seconds'] = res[modes[0]][0][1]
-if len(modes) == 2:
+if 'sequential' in modes and 'backlog' in modes:
     out['backlog_over_sequential'] = out['backlog_x_realtime'] / out['sequential_x_realtime']
+if 'packed' in modes and 'backlog' in modes:
+    out['packed_over_backlog'] = out['packed_x_realtime'] / out['backlog_x_realtime']
 eng.close()
 print(json.dumps(out))

@@ -58,6 +58,9 @@ SIGNATURES = {
     'tts_hip_waveglow_infer_ragged': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int]),
     'tts_hip_waveglow_infer_ragged_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int,
                                                     c_void_p]),
+    'tts_hip_waveglow_infer_packed': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int]),
+    'tts_hip_waveglow_infer_packed_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int,
+                                                    c_void_p]),
     'tts_hip_mel_stft_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'tts_hip_tacotron2_encode': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     'tts_hip_tacotron2_decode': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,

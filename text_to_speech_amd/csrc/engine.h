@@ -79,6 +79,8 @@ struct WaveGlowDev {
     bool wino_legacy_ready = false;          //   ... and the three-pass form's extra weight copies
     DevBuf mel_ragged, ragged_info;          // ragged calls: mel copy with cleared tails; [lengths | tail frame list] int32
     std::vector<int> ragged_info_h;          //   ... and its host image (staged to the device once per call)
+    DevBuf packed_z, packed_out;             // packed calls: noise and audio of the one packed row (its mel is mel_ragged, its
+                                             //   [segment table | frame flags | gap frames] goes through ragged_info)
     DevBuf wino_U, wino_P, wino_mel;         // mel planes; forms 2 / 3 only: transformed inputs [6][M/4][512], products [6][M/4][1024]
 };
 
@@ -259,7 +261,11 @@ void timing_collect(tts_hip_engine* e);
 int waveglow_finalize(tts_hip_engine* e);
 // d_lens (device int32 [B], null = every row holds T frames), d_tail / n_tail: the frames beyond the rows' lengths
 int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const float* d_z, float sigma, float* d_audio,
-                 int precision, const int* d_lens = nullptr, const int* d_tail = nullptr, int n_tail = 0);
+                 int precision, const int* d_lens = nullptr, const int* d_tail = nullptr, int n_tail = 0,
+                 const int* d_flags = nullptr);
+// packed call: mel / z / audio in the batch layout, d_info = [start[B] | len[B] | flags[F] | gap frames[n_gap]] (waveglow.hip)
+int waveglow_run_packed(tts_hip_engine* e, const float* d_mel, int B, int T, const float* d_z, float sigma, float* d_audio,
+                        int precision, const int* d_info, int F, int n_gap);
 void waveglow_free(tts_hip_engine* e);
 
 int tacotron2_finalize(tts_hip_engine* e);

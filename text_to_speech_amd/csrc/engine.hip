@@ -319,6 +319,52 @@ static int stage_ragged(tts_hip_engine* e, int B, int T, const int32_t* lengths,
     return TTS_HIP_OK;
 }
 
+// Packed calls: checks `lengths` like stage_ragged, plans the packed row -- the rows that hold frames one after another,
+// TTS_HIP_WG_GAP_FRAMES gap frames between two of them, rows of length 0 take no space and no gap -- and stages
+// [start[B] | len[B] | flags[F] | gap frames] once per call.  flags[f] = 1 + b * T + t on the packed frame that holds frame
+// t of row b (non-zero = real, and the gather's source index), 0 on a gap frame.  The packed row is ONE waveglow_run, so
+// its F frames must fit one run: no slicing, and no silent fall-back to the ragged path.
+static int stage_packed(tts_hip_engine* e, int B, int T, const int32_t* lengths, const char* who, int* F_out, int* n_gap_out) {
+    long long F = 0;
+    int rows = 0;
+    for (int b = 0; b < B; ++b) {
+        if (lengths[b] < 0 || lengths[b] > T)
+            return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d is outside [0, T = %d]", who, b, (int)lengths[b], T);
+        if (lengths[b] > 0) {
+            F += lengths[b];
+            ++rows;
+        }
+    }
+    const long long n_gap = rows > 1 ? (long long)TTS_HIP_WG_GAP_FRAMES * (rows - 1) : 0;
+    F += n_gap;
+    if (F > kMaxFramesPerRun)
+        return set_err(e, TTS_HIP_EINVAL,
+                       "%s: the packed row holds F = %lld frames (%d rows with frames, %d gap frames between two), above one "
+                       "run's limit (%d); split the batch or use the ragged call",
+                       who, F, rows, TTS_HIP_WG_GAP_FRAMES, kMaxFramesPerRun);
+    std::vector<int>& h = e->wg.ragged_info_h;
+    h.assign((size_t)2 * B + (size_t)F + (size_t)n_gap, 0);
+    int* flags = h.data() + 2 * (size_t)B;
+    int* gaps = flags + F;
+    int pos = 0, g = 0;
+    bool first = true;
+    for (int b = 0; b < B; ++b) {
+        h[(size_t)B + b] = lengths[b];
+        if (lengths[b] == 0) continue;                           // (start stays 0: the scatter reads nothing of such a row)
+        if (!first)
+            for (int j = 0; j < TTS_HIP_WG_GAP_FRAMES; ++j) gaps[g++] = pos++;
+        first = false;
+        h[b] = pos;
+        for (int t = 0; t < lengths[b]; ++t) flags[pos++] = 1 + b * T + t;
+    }
+    HIPCHK(e, e->wg.ragged_info.ensure(h.size() * sizeof(int)));
+    // (pageable source: the copy has left `h` when the call returns, so the next call may rebuild it)
+    HIPCHK(e, hipMemcpyAsync(e->wg.ragged_info.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    *F_out = (int)F;
+    *n_gap_out = (int)n_gap;
+    return TTS_HIP_OK;
+}
+
 // runs of whole utterances, each within kMaxFramesPerRun frames; lengths != NULL: staged by stage_ragged with the same chunkB
 static int waveglow_run_chunks(tts_hip_engine* e, const float* d_mel, int B, int T, const int32_t* lengths, const float* d_z,
                                float sigma, float* d_out, int precision) {
@@ -340,12 +386,19 @@ static int waveglow_run_chunks(tts_hip_engine* e, const float* d_mel, int B, int
 }
 
 static int waveglow_infer_impl(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
-                               float* audio, int mem, int precision, const int32_t* lengths = nullptr) {
+                               float* audio, int mem, int precision, const int32_t* lengths = nullptr, bool packed = false) {
     if (!e) return TTS_HIP_EINVAL;
     if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
     if (!mel || !audio || B <= 0 || T <= 0) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: bad argument");
     if ((long long)B * T * 32 > (1ll << 30)) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: B*T too large");
+    if (packed && !lengths) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_packed: lengths is NULL");
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: bad mem kind %d", mem);
     HIPCHK(e, hipSetDevice(e->device));
+    int F = 0, n_gap = 0;
+    if (packed) {                                                // planned and checked before anything is copied or launched
+        int rc = stage_packed(e, B, T, lengths, "waveglow_infer_packed", &F, &n_gap);
+        if (rc) return rc;
+    }
     const size_t n_mel = (size_t)B * T * 80, n_z = (size_t)B * T * 32 * 8, n_out = (size_t)B * T * 256;
     const float* d_mel = mel;
     const float* d_z = z;
@@ -367,14 +420,20 @@ static int waveglow_infer_impl(tts_hip_engine* e, const float* mel, int B, int T
     // One run addresses its activations with 31-bit byte offsets (<= ~32 k frames).  Utterances are independent, so a
     // larger batch is processed in slices of whole utterances; a single utterance above the limit is refused (the Python
     // wrapper's windowed inference, models/tts/waveglow.py:114-142, is the reference's own answer to long mels).
-    if (T > kMaxFramesPerRun)
+    // (a packed call is bounded by its F, checked by stage_packed above)
+    if (!packed && T > kMaxFramesPerRun)
         return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: T = %d frames exceeds one run's limit (%d); use windowed inference",
                        T, kMaxFramesPerRun);
-    if (lengths) {
-        int rc = stage_ragged(e, B, T, lengths, kMaxFramesPerRun / T, "waveglow_infer_ragged");
-        if (rc) return rc;
+    if (packed) {
+        if (int rc = waveglow_run_packed(e, d_mel, B, T, d_z, sigma, d_out, precision, (const int*)e->wg.ragged_info.p, F, n_gap))
+            return rc;
+    } else {
+        if (lengths) {
+            int rc = stage_ragged(e, B, T, lengths, kMaxFramesPerRun / T, "waveglow_infer_ragged");
+            if (rc) return rc;
+        }
+        if (int rc = waveglow_run_chunks(e, d_mel, B, T, lengths, d_z, sigma, d_out, precision)) return rc;
     }
-    if (int rc = waveglow_run_chunks(e, d_mel, B, T, lengths, d_z, sigma, d_out, precision)) return rc;
     if (mem == TTS_HIP_MEM_HOST)
         HIPCHK(e, hipMemcpyAsync(audio, d_out, n_out * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -513,6 +572,31 @@ int tts_hip_waveglow_infer_ragged_async(tts_hip_engine* e, const float* mel, int
         if (rc) return rc;
     }
     return waveglow_run_chunks(e, mel, B, T, lengths, z, sigma, audio, precision);
+}
+
+// WaveGlow.infer on a batch of unequal rows, computed as ONE packed row (the contract of the ragged calls above)
+int tts_hip_waveglow_infer_packed(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths, const float* z,
+                                  float sigma, float* audio, int precision, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_packed: precision must be 0 (f32), 1 (f16) or 2 (f16x3)");
+    if (!lengths) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_packed: lengths is NULL");
+    return waveglow_infer_impl(e, mel, B, T, z, sigma, audio, mem, precision, lengths, true);
+}
+
+int tts_hip_waveglow_infer_packed_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
+                                        const float* z, float sigma, float* audio, int precision, void* stream) {
+    const char* who = "waveglow_infer_packed_async";
+    if (!e) return TTS_HIP_EINVAL;
+    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "%s: precision must be 0 (f32), 1 (f16) or 2 (f16x3)", who);
+    if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
+    if (!mel || !audio || !lengths || B <= 0 || T <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", who);
+    if ((long long)B * T * 32 > (1ll << 30)) return set_err(e, TTS_HIP_EINVAL, "%s: B*T too large", who);
+    HIPCHK(e, hipSetDevice(e->device));
+    StreamScope scope(e, stream);
+    int F = 0, n_gap = 0;
+    int rc = stage_packed(e, B, T, lengths, who, &F, &n_gap);
+    if (rc) return rc;
+    return waveglow_run_packed(e, mel, B, T, z, sigma, audio, precision, (const int*)e->wg.ragged_info.p, F, n_gap);
 }
 
 int tts_hip_mel_stft_async(tts_hip_engine* e, const float* audio, int B, int N, float* mel, void* stream) {

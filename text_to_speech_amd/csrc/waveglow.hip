@@ -179,10 +179,19 @@ __global__ void probe_state_kernel(const float* __restrict__ audio, int natural,
 
 // Ragged calls (tts_hip_waveglow_infer_ragged): row b = f / T holds lens[b] real frames; frame f is real when f % T < lens[b]
 __device__ __forceinline__ bool frame_is_real(const int* __restrict__ lens, int f, int T) { return f % T < lens[f / T]; }
+// Which frames of a call are real (MASK template argument of the kernels below): every frame, the first lens[b] of each row
+// (ragged calls), or those with a non-zero entry in a per-frame flag array (packed calls: the `lens` argument then IS that
+// array, one int per frame of the packed row, 0 on gap frames)
+enum { MASK_NONE = 0, MASK_LENS = 1, MASK_FLAGS = 2 };
+template <int MASK>
+__device__ __forceinline__ bool frame_masked_real(const int* __restrict__ info, int f, int T) {
+    if constexpr (MASK == MASK_FLAGS) return info[f] != 0;
+    else return frame_is_real(info, f, T);
+}
 
 // audio[m'][0..3] = sigma * z[natural m][0..3]  (z null => zeros); m' = p * PR + f  <->  m = f * 32 + p
-// RAGGED: frames beyond their row's length start at 0 whatever the caller's z holds there (it is not read)
-template <bool RAGGED = false>
+// MASK != MASK_NONE: frames that are not real start at 0 whatever z holds there (it is not read)
+template <int MASK = MASK_NONE>
 __global__ void init_audio_kernel(const float* __restrict__ z, float sigma, float* __restrict__ audio, int PR, int BT,
                                   const int* __restrict__ lens = nullptr, int T = 1) {
     const long long mp = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -190,7 +199,7 @@ __global__ void init_audio_kernel(const float* __restrict__ z, float sigma, floa
     const int p = (int)(mp / PR), f = (int)(mp % PR);
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     bool real = z && f < BT;
-    if constexpr (RAGGED) real = real && frame_is_real(lens, f, T);
+    if constexpr (MASK != MASK_NONE) real = real && frame_masked_real<MASK>(lens, f, T);
     if (real) {
         v = *reinterpret_cast<const f32x4*>(z + ((long long)f * NPH + p) * 8);
         v *= sigma;
@@ -240,6 +249,35 @@ __global__ void wn_zero_tail_kernel(const int* __restrict__ tail, int n_tail, in
             *reinterpret_cast<f32x4*>((float*)a0p + m * 16 + c) = zero;
         }
     }
+}
+
+// Packed calls (tts_hip_waveglow_infer_packed): the real frames of all rows laid one after another in ONE row of F frames,
+// TTS_HIP_WG_GAP_FRAMES zero frames between two rows.  flags[f] = 1 + (b * T + t) for the packed frame f that holds frame t
+// of row b, 0 for a gap frame: "is real" for the kernels above and the source index of the gather in one int.
+// Gather: dst[f][..] = src[flags[f] - 1][..] (q4 float4 per frame: 20 for the mel, 64 for z), 0 on gap frames.  One float4
+// per thread, consecutive threads take consecutive float4 of both sides; caller frames beyond a row's length are not read.
+__global__ void packed_gather_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ flags,
+                                     int F, int q4) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)F * q4) return;
+    const int f = (int)(i / q4), r = (int)(i % q4);
+    const int s = flags[f];
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (s) v = *reinterpret_cast<const f32x4*>(src + ((long long)(s - 1) * q4 + r) * 4);
+    *reinterpret_cast<f32x4*>(dst + i * 4) = v;
+}
+// Scatter: audio[b][t * 256 ..] = packed[(start[b] + t) * 256 ..] for t < len[b], 0 behind it -- every float of the caller's
+// [B][T * 256] is written once, so the output needs no clear.  seg = [start[B] | len[B]]; 64 float4 per frame.
+__global__ void packed_scatter_kernel(const float* __restrict__ packed, const int* __restrict__ seg, float* __restrict__ audio,
+                                      int B, int T) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)B * T * 64) return;
+    const int r = (int)(i % 64);
+    const long long fr = i / 64;
+    const int b = (int)(fr / T), t = (int)(fr % T);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (t < seg[B + b]) v = *reinterpret_cast<const f32x4*>(packed + ((long long)(seg[b] + t) * 64 + r) * 4);
+    *reinterpret_cast<f32x4*>(audio + i * 4) = v;
 }
 
 // x[m][c] = sum_{j < h} audio[m][j] * w[j][c] + b[c]      (start 1x1 conv, waveglow_arch.py:108)
@@ -303,9 +341,10 @@ __global__ void wn_start_kernel(const float* __restrict__ audio, const float* __
 // Lane l owns channels 4l..4l+3 and 256+4l..256+4l+3 (every wave-level load is one contiguous 1 KiB run); per layer
 // the lane's 8x8 slice of wfold sits in registers and is reused for the RPW rows; the RPW*8 partial sums are reduced with the lane-halving exchange (63 shuffles for 64 values).
 constexpr int RPW = 8;
-// RAGGED: positions beyond their row's length store 0 -- the flow state stays 0 there from flow to flow and the last flow
-// gives the zero tail of the output -- and the caller's z is not read there.
-template <bool HALF, bool SPLIT = false, bool RAGGED = false>
+// MASK != MASK_NONE: positions of frames that are not real (beyond their row's length; gap frames of a packed call) store
+// 0 -- the flow state stays 0 there from flow to flow and the last flow gives the zero tail of the output -- and z is not
+// read there.
+template <bool HALF, bool SPLIT = false, int MASK = MASK_NONE>
 __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict__ acts_v, long long layer_stride,
                                                           const float* __restrict__ wfold,
                                                           const float* __restrict__ bfold,
@@ -428,8 +467,8 @@ __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict
     const int ph = (int)(m / PR), fr = (int)(m % PR);          // phase-major row -> (phase, frame)
     const long long mnat = (long long)fr * NPH + ph;           // natural position index b * L + t * 32 + p
     if ((lane & 7) == 0 && m < M && fr < BT) {
-        if constexpr (RAGGED) {
-            if (!frame_is_real(lens, fr, T)) {
+        if constexpr (MASK != MASK_NONE) {
+            if (!frame_masked_real<MASK>(lens, fr, T)) {
                 float* dst = audio_out + (out_natural ? mnat : m) * 8;
                 for (int j = 0; j < n_early + cch; ++j) dst[j] = 0.f;
                 return;
@@ -493,6 +532,8 @@ void waveglow_free(tts_hip_engine* e) {
     e->wg.io_out.release();
     e->wg.mel_ragged.release();
     e->wg.ragged_info.release();
+    e->wg.packed_z.release();
+    e->wg.packed_out.release();
     e->wg.ready = false;
 }
 
@@ -815,10 +856,15 @@ static int waveglow_build_x3(tts_hip_engine* e) {
 // frames at or before its own), so the residual stream is the only way a row's tail could reach its real positions, and
 // a row then computes what a call on its own frames computes.  d_lens == null: the launches below
 // are exactly those of a call without lengths.
+// Packed calls (d_flags != null, B = 1, d_lens null): d_flags [T] is non-zero on the real frames of the one row, d_tail lists
+// its n_tail gap frames, and d_mel is already a private copy with zero gap frames (waveglow_run_packed below).  The same
+// argument holds with "gap frame" for "tail frame": nothing in it needs the zero frames to be at the end of a row.
 int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const float* d_z, float sigma, float* d_audio,
-                 int precision, const int* d_lens, const int* d_tail, int n_tail) {
+                 int precision, const int* d_lens, const int* d_tail, int n_tail, const int* d_flags) {
     WaveGlowDev& wg = e->wg;
-    const bool ragged = d_lens != nullptr;
+    const bool packed = d_flags != nullptr;
+    const bool ragged = d_lens != nullptr || packed;             // some frames are not real
+    if (packed && (B != 1 || d_lens)) return set_err(e, TTS_HIP_EINVAL, "waveglow_run: a packed run is one row without lengths");
     const bool half = precision == 1;
     const bool x3 = precision == 2;
     if (half) {
@@ -870,7 +916,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         HIPCHK(e, wg.a0p.ensure((size_t)M * 16 * 4));
     }
     hipStream_t st = e->stream;
-    if (ragged) {                                                // every reader below takes the copy with cleared tails
+    if (ragged && !packed) {                                     // every reader below takes the copy with cleared tails
         HIPCHK(e, wg.mel_ragged.ensure((size_t)BT * 80 * 4));
         const long long n4 = (long long)BT * 20;
         hipLaunchKernelGGL(mel_ragged_copy_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, d_mel,
@@ -918,10 +964,12 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
     _Float16* mel16 = (_Float16*)wg.mel16.p;
 
     const unsigned mb = (unsigned)((M + 255) / 256);
-    if (ragged)
-        hipLaunchKernelGGL(init_audio_kernel<true>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, d_lens, T);
+    if (packed)
+        hipLaunchKernelGGL(init_audio_kernel<MASK_FLAGS>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, d_flags, T);
+    else if (ragged)
+        hipLaunchKernelGGL(init_audio_kernel<MASK_LENS>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, d_lens, T);
     else
-        hipLaunchKernelGGL(init_audio_kernel<false>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, (const int*)nullptr, 1);
+        hipLaunchKernelGGL(init_audio_kernel<MASK_NONE>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, (const int*)nullptr, 1);
     if (half || x3) {
         const long long n = (long long)BT * KMEL;
         hipLaunchKernelGGL(mel_window_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_mel, mel16,
@@ -1096,19 +1144,18 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         float* dst = (k == 0) ? d_audio : wg.audio.f();
         const long long waves = (M + RPW - 1) / RPW;
         const dim3 grid((unsigned)((waves + 3) / 4));
-        if (ragged) {
-            if (x3)
-                hipLaunchKernelGGL((wn_end_fold_kernel<true, true, true>), grid, dim3(256), 0, st, (const void*)acts16,
-                                   (long long)NP * M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
-                                   zoff, early ? 2 : 0, sigma, M, h, PR, BT, (long long)M * C, d_lens, T);
-            else if (half)
-                hipLaunchKernelGGL((wn_end_fold_kernel<true, false, true>), grid, dim3(256), 0, st, (const void*)acts16,
-                                   (long long)M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
-                                   zoff, early ? 2 : 0, sigma, M, h, PR, BT, 0ll, d_lens, T);
-            else
-                hipLaunchKernelGGL((wn_end_fold_kernel<false, false, true>), grid, dim3(256), 0, st, (const void*)wg.acts.p,
-                                   (long long)M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
-                                   zoff, early ? 2 : 0, sigma, M, h, PR, BT, 0ll, d_lens, T);
+#define TTS_END_FOLD(HALF_, SPLIT_, MASK_, acts_, stride_, lo_, info_)                                                     \
+    hipLaunchKernelGGL((wn_end_fold_kernel<HALF_, SPLIT_, MASK_>), grid, dim3(256), 0, st, (const void*)(acts_),          \
+                       (long long)(stride_), fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z, zoff,    \
+                       early ? 2 : 0, sigma, M, h, PR, BT, (long long)(lo_), info_, T)
+        if (packed) {
+            if (x3) TTS_END_FOLD(true, true, MASK_FLAGS, acts16, NP * M * C, M * C, d_flags);
+            else if (half) TTS_END_FOLD(true, false, MASK_FLAGS, acts16, M * C, 0, d_flags);
+            else TTS_END_FOLD(false, false, MASK_FLAGS, wg.acts.p, M * C, 0, d_flags);
+        } else if (ragged) {
+            if (x3) TTS_END_FOLD(true, true, MASK_LENS, acts16, NP * M * C, M * C, d_lens);
+            else if (half) TTS_END_FOLD(true, false, MASK_LENS, acts16, M * C, 0, d_lens);
+            else TTS_END_FOLD(false, false, MASK_LENS, wg.acts.p, M * C, 0, d_lens);
         } else if (x3)
             hipLaunchKernelGGL((wn_end_fold_kernel<true, true>), grid, dim3(256), 0, st, (const void*)acts16,
                                (long long)NP * M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
@@ -1121,6 +1168,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
             hipLaunchKernelGGL((wn_end_fold_kernel<false, false>), grid, dim3(256), 0, st, (const void*)wg.acts.p,
                                (long long)M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
                                zoff, early ? 2 : 0, sigma, M, h, PR, BT);
+#undef TTS_END_FOLD
         HIPCHK(e, hipGetLastError());
         if (wg.probe_out && wg.probe_what == 1 && wg.probe_flow == k) {          // test hook: the state after this flow
             const long long n = (long long)BT * NPH;
@@ -1131,5 +1179,35 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         }
         if (early) zoff += 2;
     }
+    return TTS_HIP_OK;
+}
+
+// Packed call: gather the real frames of mel / z [B, T, ..] into one row of F frames (mel_ragged / packed_z), run that row as
+// an ordinary one-row call whose gap frames are not real, scatter the row's audio back to [B, T * 256] with zero tails.
+// d_info = [start[B] | len[B] | flags[F] | gap frames[n_gap]] (staged by the caller once per call, csrc/engine.hip).
+int waveglow_run_packed(tts_hip_engine* e, const float* d_mel, int B, int T, const float* d_z, float sigma, float* d_audio,
+                        int precision, const int* d_info, int F, int n_gap) {
+    WaveGlowDev& wg = e->wg;
+    hipStream_t st = e->stream;
+    const int* d_flags = d_info + 2 * (size_t)B;
+    if (F > 0) {
+        HIPCHK(e, wg.mel_ragged.ensure((size_t)F * 80 * 4));
+        HIPCHK(e, wg.packed_out.ensure((size_t)F * 256 * 4));
+        if (d_z) HIPCHK(e, wg.packed_z.ensure((size_t)F * 256 * 4));
+        hipLaunchKernelGGL(packed_gather_kernel, dim3((unsigned)(((long long)F * 20 + 255) / 256)), dim3(256), 0, st, d_mel,
+                           wg.mel_ragged.f(), d_flags, F, 20);
+        if (d_z)
+            hipLaunchKernelGGL(packed_gather_kernel, dim3((unsigned)(((long long)F * 64 + 255) / 256)), dim3(256), 0, st, d_z,
+                               wg.packed_z.f(), d_flags, F, 64);
+        HIPCHK(e, hipGetLastError());
+        int rc = waveglow_run(e, wg.mel_ragged.f(), 1, F, d_z ? wg.packed_z.f() : nullptr, sigma, wg.packed_out.f(), precision,
+                              nullptr, d_flags + F, n_gap, d_flags);
+        if (rc) return rc;
+    }
+    // (no real frame at all: the scatter reads nothing of `packed` and stores the zeros)
+    const long long n4 = (long long)B * T * 64;
+    hipLaunchKernelGGL(packed_scatter_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
+                       (const float*)wg.packed_out.p, d_info, d_audio, B, T);
+    HIPCHK(e, hipGetLastError());
     return TTS_HIP_OK;
 }

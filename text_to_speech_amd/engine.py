@@ -179,7 +179,7 @@ class HipEngine:
         return np.ascontiguousarray(arr, dtype=np.int32)
 
     def waveglow_infer(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', stream=None, seed=None, offset: int = 0,
-                       lengths=None):
+                       lengths=None, packed: bool = False):
         """mel [B, T, 80] (+ optional z [B, T*32, 8]) -> audio [B, T*256].  precision: 'f32' (exact fp32 MFMA), 'f16x3'
         (split fp16: fp32-class accuracy, ~3x faster) or 'f16' (fp16 operands).  `seed` (with z=None): the noise is drawn
         on the device from (seed, offset) -- the reference's default `z=None, deterministic=False`
@@ -189,7 +189,16 @@ class HipEngine:
         `lengths` [B] (ints in [0, T]; brought to host int32): a batch of unequal rows (tts_hip_waveglow_infer_ragged) --
         audio[b, :lengths[b] * 256] is what row b's own frames give in a call of their own, audio[b, lengths[b] * 256:] is 0,
         and mel / z beyond a row's length are never read (they may be uninitialised).  With `seed` the noise is drawn in the
-        batch layout [B, T*32, 8] as without lengths."""
+        batch layout [B, T*32, 8] as without lengths.
+        `packed=True` (needs `lengths`): the same results computed as ONE packed row (tts_hip_waveglow_infer_packed) -- the real
+        frames of all rows one after another, 4 zero gap frames between two rows -- so the work follows sum(lengths), not
+        B * T.  The noise of `seed` is still drawn in the batch layout: a row gets the values the ragged call gives it."""
+        if packed and lengths is None:
+            raise ValueError('packed=True needs lengths (one frame count per row)')
+        rag = self._lib.tts_hip_waveglow_infer_packed if packed else self._lib.tts_hip_waveglow_infer_ragged
+        rag_async = (self._lib.tts_hip_waveglow_infer_packed_async if packed
+                     else self._lib.tts_hip_waveglow_infer_ragged_async)
+        rag_name = 'waveglow_infer_packed' if packed else 'waveglow_infer_ragged'
         fns = {'f32': self._lib.tts_hip_waveglow_infer, 'f16': self._lib.tts_hip_waveglow_infer_f16,
                'f16x3': self._lib.tts_hip_waveglow_infer_f16x3}
         if precision not in fns:
@@ -225,10 +234,10 @@ class HipEngine:
                                                                   ctypes.c_void_p(int(stream.cuda_stream))), 'random_fill')
                 self._used_on(stream, mel, z, m, zz, out)
                 if lens is not None:
-                    self._check(self._lib.tts_hip_waveglow_infer_ragged_async(
+                    self._check(rag_async(
                         self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p,
                         None if zz is None else ctypes.c_void_p(zz.data_ptr()), float(sigma), ctypes.c_void_p(out.data_ptr()),
-                        pcode, ctypes.c_void_p(int(stream.cuda_stream))), 'waveglow_infer_ragged_async')
+                        pcode, ctypes.c_void_p(int(stream.cuda_stream))), rag_name + '_async')
                     return out
                 self._check(self._lib.tts_hip_waveglow_infer_async(
                     self._h, ctypes.c_void_p(m.data_ptr()), B, T, None if zz is None else ctypes.c_void_p(zz.data_ptr()),
@@ -243,9 +252,9 @@ class HipEngine:
                 if z is None and seed is not None:       # drawn on the engine's stream, ahead of the call that reads it
                     self._check(self._lib.tts_hip_random_fill(self._h, 0, u64(seed), u64(offset),
                                                               ctypes.c_void_p(zz.data_ptr()), zz.numel(), None), 'random_fill')
-                self._check(self._lib.tts_hip_waveglow_infer_ragged(
+                self._check(rag(
                     self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p, None if zz is None else ctypes.c_void_p(zz.data_ptr()),
-                    float(sigma), ctypes.c_void_p(out.data_ptr()), pcode, MEM_DEVICE), 'waveglow_infer_ragged')
+                    float(sigma), ctypes.c_void_p(out.data_ptr()), pcode, MEM_DEVICE), rag_name)
                 return out
             if zz is None and seed is not None:
                 self._check(self._lib.tts_hip_waveglow_infer_seeded(
@@ -273,12 +282,12 @@ class HipEngine:
             torch = self._torch()
             dmel = torch.as_tensor(mel, device=torch.device('cuda', self.device))
             return self.waveglow_infer(dmel, sigma=sigma, precision=precision, seed=seed, offset=offset,
-                                       lengths=lens).cpu().numpy()
+                                       lengths=lens, packed=packed).cpu().numpy()
         out = np.empty((B, T * 256), dtype=np.float32)
         if lens is not None:
-            self._check(self._lib.tts_hip_waveglow_infer_ragged(
+            self._check(rag(
                 self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, lens.ctypes.data_as(ctypes.c_void_p), zp, float(sigma),
-                out.ctypes.data_as(ctypes.c_void_p), pcode, MEM_HOST), 'waveglow_infer_ragged')
+                out.ctypes.data_as(ctypes.c_void_p), pcode, MEM_HOST), rag_name)
             return out
         if zp is None and seed is not None:
             self._check(self._lib.tts_hip_waveglow_infer_seeded(

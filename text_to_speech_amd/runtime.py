@@ -257,16 +257,20 @@ class HipRuntime(Runtime):
 
     # ------------------------------------------------------------------ WaveGlow.infer (waveglow_arch.py:244-306)
     def waveglow_infer(self, mel, z=None, sigma=1.0, deterministic=False, seed=None, precision=None, lengths=None,
-                       **_ignored):
+                       packed=False, **_ignored):
         """`lengths` [B] (frames of each row that are real): a batch of unequal rows -- every row's audio is that of its own
-        frames, zeros behind it (HipEngine.waveglow_infer); the noise is drawn in the batch layout either way."""
+        frames, zeros behind it (HipEngine.waveglow_infer); the noise is drawn in the batch layout either way.
+        `packed=True` (with `lengths`): the same call computed as one packed row; noise values and the running offset are
+        those of the call without it."""
+        if packed and lengths is None:
+            raise ValueError('packed=True needs lengths (one frame count per row)')
         dev = _is_torch_cuda(mel)
         if not dev:
             mel = np.asarray(mel, dtype=np.float32)
         if mel.ndim == 2:
             mel = mel[None]
         B, T = int(mel.shape[0]), int(mel.shape[1])
-        ragged = {} if lengths is None else {'lengths': lengths}
+        ragged = {} if lengths is None else {'lengths': lengths, 'packed': True} if packed else {'lengths': lengths}
         if z is None and not deterministic:
             if seed is not None:
                 zs, zo = (int(seed) ^ NOISE_STREAM) & _U64, 0

@@ -119,7 +119,8 @@ class Tacotron2:
         return audio
 
     def _vocode_and_finish(self, part, *, callbacks=None, predicted=None, return_output=True, vocoder=None,
-                           silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, **kwargs):
+                           silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, pack_vocoder=False,
+                       **kwargs):
         audios, vocoder_time = None, 0.
         if vocoder is not None:
             t1 = time.time()
@@ -208,7 +209,7 @@ class Tacotron2:
                         'audio_filename', 'post_processing')
 
     def predict(self, inputs, *, predicted=None, callbacks=None, return_results=True, return_output=None,
-                overlap=False, batch_backlog=None, **kwargs):
+                overlap=False, batch_backlog=None, pack_vocoder=False, **kwargs):
         """BaseModel.predict (base_model.py:676-711): builds the callbacks unless the caller brings its own `predicted`
         map, then runs `infer` sequentially; returns the result dicts (or the `predicted` entries when a JSON saver is
         active and `return_output` was not forced).
@@ -218,8 +219,12 @@ class Tacotron2:
         nothing waits for a batch to fill.  Results, callbacks and the `predicted` map see the inputs in their order, as in
         the sequential loop.  With `deterministic=True` the audio is the sequential loop's up to fp32 re-association in the
         decoder; otherwise dropout masks and noise are drawn from the runtime's stream in the batch's layout: the same
-        distribution, another realisation than the sequential loop's.  Not combined with `overlap=True`."""
+        distribution, another realisation than the sequential loop's.  Not combined with `overlap=True`.
+        `pack_vocoder=True` (needs `batch_backlog >= 2`): the group's one vocoder call gets `packed=True` -- the same audio,
+        computed on the frames that exist instead of rows x longest row (HipEngine.waveglow_infer)."""
         backlog = batch_backlog is not None and int(batch_backlog) >= 2
+        if pack_vocoder and not backlog:
+            raise ValueError('pack_vocoder=True needs batch_backlog >= 2 (it packs the vocoder call of a backlog group)')
         if batch_backlog is not None and int(batch_backlog) < 1:
             raise ValueError(f'batch_backlog must be None or >= 1, got {batch_backlog!r}')
         if backlog and overlap:
@@ -240,7 +245,7 @@ class Tacotron2:
         results = []
         if backlog:
             outputs = self._infer_backlog(inputs, int(batch_backlog), predicted=predicted, callbacks=callbacks,
-                                          return_output=return_output, **kwargs)
+                                          return_output=return_output, pack_vocoder=bool(pack_vocoder), **kwargs)
         elif overlap and kwargs.get('vocoder') is not None:
             outputs = self._infer_overlapped(inputs, predicted=predicted, callbacks=callbacks,
                                              return_output=return_output, **kwargs)
@@ -313,12 +318,14 @@ class Tacotron2:
 
     def _infer_backlog(self, inputs, k, *, predicted, callbacks, return_output, overwrite=False, embeddings=None,
                        max_length=10., max_text_length=-1, max_trial=5, min_fpt_ratio=2., max_fpt_ratio=10., vocoder=None,
-                       silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, **kwargs):
+                       silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, pack_vocoder=False,
+                       **kwargs):
         """`predict(batch_backlog=k)`: yields (input, result) in input order.  Per group of waiting inputs (`_backlog_groups`):
         the parts of all its texts are the rows of 0-padded token batches of at most k rows, one `compiled_infer` call each;
         every row keeps the frame cap, the frame / token ratio test and the retries it would have had alone (rows that fail
         are decoded again together); ONE vocoder call per group with `lengths` = the rows' frame counts, so every waveform is
-        that of its own frames; then each text is finished (`_finish`) in input order."""
+        that of its own frames (`pack_vocoder`: that call also gets `packed=True`); then each text is finished (`_finish`) in
+        input order."""
         one = dict(predicted=predicted, callbacks=callbacks, return_output=return_output, overwrite=overwrite,
                    embeddings=embeddings, max_length=max_length, max_text_length=max_text_length, max_trial=max_trial,
                    min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, vocoder=vocoder, silence_time=silence_time,
@@ -354,7 +361,8 @@ class Tacotron2:
                     batch = np.zeros((len(voiced), int(n_frames.max()), voiced[0][1].shape[1]), np.float32)
                     for r, (_, m) in enumerate(voiced):
                         batch[r, :m.shape[0]] = m
-                    audio = _to_numpy(vocoder(batch, lengths=n_frames, **{**kwargs, **vocoder_config}))
+                    packed = {'packed': True} if pack_vocoder else {}
+                    audio = _to_numpy(vocoder(batch, lengths=n_frames, **packed, **{**kwargs, **vocoder_config}))
                     for r, (ti, m) in enumerate(voiced):
                         audios[ti].append(audio[r, :m.shape[0] * 256].copy())
                 vocoder_time = time.time() - t1
@@ -441,7 +449,7 @@ class Tacotron2:
         results leave through the callbacks (tacotron2.py:363-367, base_model.py:713)."""
         self.precompile_for_stream(vocoder=vocoder, **{k: v for k, v in kwargs.items()
                                                        if k not in self._callback_kwargs + ('callbacks', 'predicted', 'overlap',
-                                                                                            'batch_backlog')})
+                                                                                            'batch_backlog', 'pack_vocoder')})
         kwargs.setdefault('return_output', False)
         kwargs.setdefault('return_results', False)
         # batch_backlog looks at what the queue holds right now, so `predict` gets the queue itself

@@ -83,7 +83,8 @@ class WaveGlow:
 
     mel: a `.npy` path, [T, 80] or [B, T, 80] -> audio [B, T * 256] (windowed single-utterance mode: [T * 256]).
     Without `win_len` the whole mel is vocoded in one call; a batch of unequal utterances then takes `lengths=[...]` (frames
-    of each row that are real): row b's audio[:lengths[b] * 256] is that of its own frames, zeros behind it.  With it (frames; a float means "a multiple of": rounded up,
+    of each row that are real): row b's audio[:lengths[b] * 256] is that of its own frames, zeros behind it (`packed=True` next
+    to it: the same audio computed as one packed row, work proportional to sum(lengths)).  With it (frames; a float means "a multiple of": rounded up,
     or down with `use_slice`; capped by `max_win_len`):
       * a mel that fits one window is vocoded directly -- padded to the window with -11 first only if `force_pad`
         (default: only for the keras runtime, i.e. never here), the result cut back to T * 256 samples;
