@@ -217,7 +217,11 @@ int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int 
  *           (f16: the fp16 activations widened; f16x3: hi + lo summed in fp32);
  *   what 1: the flow state right after the flow (affine coupling, inverse 1x1 conv, and the early output that flows 8 and 4
  *           prepend), to `out` [B, T*32, n] with n = 4, 6 (flow 8), 6, 8 (flow 4), 8 for flows 11-9, 8, 7-5, 4, 3-0 --
- *           the channel order of the reference's audio after that flow (waveglow_arch.py:284-304); `layer` is not used.
+ *           the channel order of the reference's audio after that flow (waveglow_arch.py:284-304); `layer` is not used;
+ *   what 2: (precision 0 only) the conditioning plane that the Winograd form builds for WN layer `layer` (1 .. 7) -- the
+ *           layer's conditioning term plus its in-layer bias, columns in the engine's gate-interleaved order (64 j + c: tanh
+ *           channel 32 j + c, 64 j + 32 + c: its sigmoid channel) -- to `out` [B, T*32, 1024]; an error when the call does
+ *           not take the Winograd form (fewer than 144 frames, form 0).
  * B*T <= 31744.                                                                                                            */
 int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int precision,
                            int flow, int what, int layer, float* out, int mem);

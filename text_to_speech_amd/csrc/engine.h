@@ -47,9 +47,7 @@ struct WgLayerDev {
     _Float16* cond_Bt_x3 = nullptr;
     _Float16* rs_Bt_x3 = nullptr;
     float* wino_G = nullptr;    // Winograd form (wn_wino.hip; built on first use): [6][1024][512] tap combinations and the
-    float* wino_V = nullptr;    //   conditioning planes of the phase / mixed groups ([8][6][1024][224] / [16][4][1024][320])
-                                //   and of the frame groups of dilations 32, 64 ([32][5][1024][160], F(4, 2) along frames)
-    float* wino_Vf = nullptr;   //   three-pass form only: column-selected copies for the dilation-128 frame groups [32][6][1024][224]
+    float* wino_W = nullptr;    //   conditioning weight planes [32][7][1024][80] (F(4, 4) along frames)
     float* rs_Bt = nullptr;     // [512][512] residual half of res_skip (layers 0..6)
     float* rs_bias = nullptr;   // [512]
     int rs_n = 0;
@@ -72,16 +70,17 @@ struct WaveGlowDev {
     DevBuf x16, acts16, a0p16, mel16;        // fp16 path: shadow of x, activations, first-layer operand, mel
     int form_mode = 1, last_form = -1;       // tts_hip_set_waveglow_form / tts_hip_last_waveglow_form
     int last_tiles = -1;                     // tts_hip_last_waveglow_tiles: WN GEMM tile family of the last call
-    int probe_flow = -1, probe_layer = -1;   // tts_hip_waveglow_probe (test hook): stop after this layer (what 0) or flow
-    int probe_what = 0;                      //   (what 1) and copy its gated activations [B][T * 32][512] or the flow
-    float* probe_out = nullptr;              //   state [B][T * 32][n] to this device buffer
+    int probe_flow = -1, probe_layer = -1;   // tts_hip_waveglow_probe (test hook): stop after this layer (what 0, 2) or flow
+    int probe_what = 0;                      //   (what 1) and copy its gated activations [B][T * 32][512], the flow state
+    float* probe_out = nullptr;              //   [B][T * 32][n] or the layer's conditioning plane [B][T * 32][1024] (what 2;
+                                             //   Winograd form only) to this device buffer
     bool wino_ready = false;                 // Winograd form of the fp32 in-layer GEMM (wn_wino.hip)
-    bool wino_legacy_ready = false;          //   ... and the three-pass form's extra weight copies
     DevBuf mel_ragged, ragged_info;          // ragged calls: mel copy with cleared tails; [lengths | tail frame list] int32
     std::vector<int> ragged_info_h;          //   ... and its host image (staged to the device once per call)
     DevBuf packed_z, packed_out;             // packed calls: noise and audio of the one packed row (its mel is mel_ragged, its
                                              //   [segment table | frame flags | gap frames] goes through ragged_info)
     DevBuf wino_U, wino_P, wino_mel;         // mel planes; forms 2 / 3 only: transformed inputs [6][M/4][512], products [6][M/4][1024]
+    DevBuf wino_cond;                        // conditioning plane of the current layer [32 PR][1024]
 };
 
 // ---------------------------------------------------------------- Tacotron2
@@ -249,7 +248,7 @@ struct StreamScope {
     } while (0)
 
 // Winograd form of the WN in-layer GEMM (wn_wino.hip)
-int waveglow_build_wino(tts_hip_engine* e, bool legacy_frames);
+int waveglow_build_wino(tts_hip_engine* e);
 int waveglow_wino_begin(tts_hip_engine* e, const float* d_mel, int PR, int BT, int T, int form);
 int waveglow_wino_layer(tts_hip_engine* e, const WgLayerDev& ly, int i, const float* x, float* acts_i, int PR, int BT, int T);
 // timing helpers (engine.hip)

@@ -461,13 +461,14 @@ int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, co
                            int flow, int what, int layer, float* out, int mem) {
     if (!e) return TTS_HIP_EINVAL;
     if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
-    if (!mel || !out || B <= 0 || T <= 0 || precision < 0 || precision > 2 || flow < 0 || flow > 11 || what < 0 || what > 1 ||
-        layer < 0 || layer > 7 || (long long)B * T > 31744)
+    if (!mel || !out || B <= 0 || T <= 0 || precision < 0 || precision > 2 || flow < 0 || flow > 11 || what < 0 || what > 2 ||
+        layer < 0 || layer > 7 || (long long)B * T > 31744 || (what == 2 && precision != 0))
         return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: bad argument");
     if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: bad mem kind %d", mem);
     HIPCHK(e, hipSetDevice(e->device));
     // what 1: the flow's 2 * n_half channels, preceded by the early output that flows 8 and 4 append
-    const int width = what == 0 ? 512 : e->wg.flow[flow].n_rem + (flow % 4 == 0 && flow > 0 ? 2 : 0);
+    // what 2: the conditioning plane (bias included, gate-interleaved columns) that the Winograd form builds for the layer
+    const int width = what == 0 ? 512 : what == 2 ? 1024 : e->wg.flow[flow].n_rem + (flow % 4 == 0 && flow > 0 ? 2 : 0);
     const size_t n_mel = (size_t)B * T * 80, n_z = (size_t)B * T * 32 * 8, n_out = (size_t)B * T * 32 * width;
     const float* d_mel = mel;
     const float* d_z = z;

@@ -144,16 +144,16 @@ __global__ void mel_window_kernel(const float* __restrict__ mel, _Float16* __res
     put_split(dst, lo, i, t - q >= 0 ? mel[(long long)(f - q) * 80 + j] : 0.f);
 }
 
-// test hook (tts_hip_waveglow_probe): phase-major rows m' = p * PR + b * T + t of one layer's gated activations ->
-// natural order [B][T * 32][512] (position l = 32 t + p)
-__global__ void probe_acts_kernel(const float* __restrict__ acts, float* __restrict__ out, int PR, int BT, int T) {
+// test hook (tts_hip_waveglow_probe): phase-major rows m' = p * PR + b * T + t of one layer's gated activations (W = 512) or
+// conditioning plane (W = 1024) -> natural order [B][T * 32][W] (position l = 32 t + p)
+__global__ void probe_acts_kernel(const float* __restrict__ acts, float* __restrict__ out, int PR, int BT, int T, int W) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // one float4 of one position
-    if (idx >= (long long)BT * NPH * (C / 4)) return;
-    const int c = (int)(idx % (C / 4)) * 4;
-    const long long pos = idx / (C / 4);               // b * T * 32 + l
+    if (idx >= (long long)BT * NPH * (W / 4)) return;
+    const int c = (int)(idx % (W / 4)) * 4;
+    const long long pos = idx / (W / 4);               // b * T * 32 + l
     const int p = (int)(pos % NPH);
     const long long f = pos / NPH;                     // b * T + t
-    *reinterpret_cast<f32x4*>(out + pos * C + c) = *reinterpret_cast<const f32x4*>(acts + ((long long)p * PR + f) * C + c);
+    *reinterpret_cast<f32x4*>(out + pos * W + c) = *reinterpret_cast<const f32x4*>(acts + ((long long)p * PR + f) * W + c);
 }
 // the same for the fp16 activation planes, widened to fp32; `lo` (split-fp16 mode, may be null): value = hi + lo
 __global__ void probe_acts16_kernel(const _Float16* __restrict__ acts, const _Float16* __restrict__ lo, float* __restrict__ out,
@@ -523,8 +523,8 @@ void waveglow_free(tts_hip_engine* e) {
     e->wg.wino_U.release();
     e->wg.wino_P.release();
     e->wg.wino_mel.release();
+    e->wg.wino_cond.release();
     e->wg.wino_ready = false;
-    e->wg.wino_legacy_ready = false;
     e->wg.f16_ready = false;
     e->wg.x3_ready = false;
     e->wg.io_mel.release();
@@ -884,7 +884,8 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
     bool row64 = x3 ? pr64 * 1.25 < pr256      // split fp16 has two tile shapes: 64 x 128 (about 25 % more time per row) and 256 x 256
                     : BT <= 512 &&
                       (half ? pr64 * 4 <= pr_big * 3 : pr64 < pr_big);   // fp16: the smaller tile only pays from -25 % rows
-    // fp32: the Winograd form (wn_wino.hip) executes K ~1 090 per output instead of 1 856 in ONE kernel per layer on 64-row tiles.
+    // fp32: the Winograd form (wn_wino.hip) executes K ~910 per output instead of 1 856 (taps 768 in one kernel per layer on 64-row
+    // tiles, conditioning 140 in a kernel of its own ahead of it).
     // It pays from about 150 frames per call (one sentence, measured on one box, Winograd / direct: 100 frames 16.9 / 15.0 ms,
     // 150: 18.3 / 20.9, 200: 19.4 / 26.0, 350: 32.2 / 37.6, 513: 48.5 / 61.2, 800: 64.0 / 84.9; the three-pass form of round 3
     // only paid from 384 frames: its two HBM-bound passes and six-slice launches cost 40 % at 100 frames)
@@ -938,13 +939,14 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
     // fp32 path, 128- / 256-row tiles: layers 1 .. 7 of a flow run in their Winograd form (wn_wino.hip)
     bool wino = wino_size && (!row64 || wg.form_mode != 2);               // (PR is a multiple of 64; form 2: of 128)
     if (wino) {
-        // its operands (6.2 GB of weight planes on first use, 0.7 GB of workspace at config 2) are extra: when the device cannot
-        // hold them -- and only then: any other error is the call's error -- this handle keeps the direct form from now on
-        const bool three_pass = wg.form_mode == 2;
+        // its operands (7.2 GB of weight planes on first use, the conditioning plane -- 0.84 GB at config 2 -- and the mel planes
+        // per call) are extra: when the device cannot hold them -- and only then: any other error is the call's error -- this
+        // handle keeps the direct form from now on
         size_t free_b = 0, total_b = 0;
         HIPCHK(e, hipMemGetInfo(&free_b, &total_b));
-        const size_t need = wg.wino_ready && (!three_pass || wg.wino_legacy_ready) ? 0 : (size_t)(three_pass ? 10 : 7) << 30;
-        int rc = free_b < need ? TTS_HIP_ENOMEM : waveglow_build_wino(e, three_pass);
+        const size_t plane = (size_t)M * 2 * C * 4 > wg.wino_cond.bytes ? (size_t)M * 2 * C * 4 : 0;
+        const size_t need = (wg.wino_ready ? 0 : (size_t)8 << 30) + plane;
+        int rc = free_b < need ? TTS_HIP_ENOMEM : waveglow_build_wino(e);
         bool oom = rc == TTS_HIP_ENOMEM;
         if (!rc) {
             rc = waveglow_wino_begin(e, d_mel, PR, BT, T, wg.form_mode);
@@ -1035,10 +1037,14 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
                     else HIPCHK(e, row64 ? gemm_wn_in_r64(g, st) : tile64 ? gemm_wn_in_64(g, st) : tile128 ? gemm_wn_in_128(g, st) : gemm_wn_in(g, st));
                     timing_end(e);
                 }
-                if (wg.probe_out && wg.probe_what == 0 && wg.probe_flow == k && wg.probe_layer == i) {   // test hook: stop here
-                    const long long n4 = (long long)BT * NPH * (C / 4);
-                    hipLaunchKernelGGL(probe_acts_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, acts_i,
-                                       wg.probe_out, PR, BT, T);
+                if (wg.probe_out && wg.probe_what != 1 && wg.probe_flow == k && wg.probe_layer == i) {   // test hook: stop here
+                    const bool plane = wg.probe_what == 2;                    // the layer's conditioning plane (Winograd form only)
+                    if (plane && !(wino && i > 0))
+                        return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: layer %d of this call has no conditioning plane", i);
+                    const int W = plane ? 2 * C : C;
+                    const long long n4 = (long long)BT * NPH * (W / 4);
+                    hipLaunchKernelGGL(probe_acts_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
+                                       plane ? wg.wino_cond.f() : acts_i, wg.probe_out, PR, BT, T, W);
                     HIPCHK(e, hipGetLastError());
                     return TTS_HIP_OK;
                 }

@@ -563,9 +563,11 @@ class HipEngine:
                        layer: int = 0):
         """Test hook (tts_hip_waveglow_probe): run `waveglow_infer` in `precision` up to flow `flow` and return either the gated
         activations [B, T*32, 512] of its WN layer `layer` (what='acts') or the flow state [B, T*32, n] right after the flow,
-        early output included (what='state'; the reference's audio after that flow)."""
+        early output included (what='state'; the reference's audio after that flow), or the conditioning plane [B, T*32, 1024]
+        of that layer -- sum_q V_q mel[t - q] + b, columns in the gate-interleaved order of the engine's weights -- that the
+        fp32 Winograd form builds (what='cond'; layers 1 - 7 of calls of 144 frames or more)."""
         precs = {'f32': 0, 'f16': 1, 'f16x3': 2}
-        whats = {'acts': 0, 'state': 1}
+        whats = {'acts': 0, 'state': 1, 'cond': 2}
         if precision not in precs or what not in whats:
             raise ValueError(f'precision must be one of {tuple(precs)} and what one of {tuple(whats)}')
         mel = np.ascontiguousarray(mel, dtype=np.float32)
@@ -578,7 +580,7 @@ class HipEngine:
             if z.shape != (B, T * 32, 8):
                 raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {z.shape}')
             zp = z.ctypes.data_as(ctypes.c_void_p)
-        width = 512 if what == 'acts' else (4 if flow >= 8 else 6 if flow >= 4 else 8) + (2 if flow in (4, 8) else 0)
+        width = 512 if what == 'acts' else 1024 if what == 'cond' else (4 if flow >= 8 else 6 if flow >= 4 else 8) + (2 if flow in (4, 8) else 0)
         out = np.empty((B, T * 32, width), dtype=np.float32)
         self._check(self._lib.tts_hip_waveglow_probe(
             self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, zp, float(sigma), precs[precision], int(flow), whats[what],
