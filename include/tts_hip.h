@@ -101,6 +101,27 @@ int tts_hip_random_fill(tts_hip_engine* e, int kind, uint64_t seed, uint64_t off
 int tts_hip_waveglow_infer_seeded(tts_hip_engine* e, const float* mel, int B, int T, uint64_t seed, uint64_t offset,
                                   float sigma, float* audio, int precision, int mem);
 
+/* Per-row streams: seeded output that does not depend on how rows were batched.  Row b owns the stream (keys[b],
+ * offsets[b]); `tts_hip_random_fill_rows` writes out[b * row_stride + i] = element i of that stream -- the element rule of
+ * `tts_hip_random_fill`: word i % 4 of block offsets[b] + i / 4 under key keys[b] -- for i < counts[b] (counts NULL =
+ * row_stride for every row; 0 <= counts[b] <= row_stride) and touches nothing at i >= counts[b].  keys, offsets and counts
+ * are HOST arrays of B entries, read before the call returns; `out` is a DEVICE buffer; enqueued on `stream` (NULL = the
+ * handle's stream) without synchronizing.  B = 1 is `tts_hip_random_fill` bit for bit.
+ * `tts_hip_waveglow_infer_rows_seeded[_async]`: the contract of tts_hip_waveglow_infer_ragged[_async] (packed == 0; lengths
+ * may be NULL) or tts_hip_waveglow_infer_packed[_async] (packed != 0; needs lengths) with the noise drawn inside the engine:
+ * z[b, p, c] = normal element p * 8 + c of row b's stream, only lengths[b] * 256 values per row when lengths are given.  A
+ * row's noise -- and, where a row's arithmetic is its own (lengths given), its audio up to fp32 re-association -- is the
+ * same whichever batch, row position or neighbours it is vocoded with.  Without lengths the rows are a padded batch and
+ * every row still hears its neighbours' padding as in tts_hip_waveglow_infer.                                           */
+int tts_hip_random_fill_rows(tts_hip_engine* e, int kind, const uint64_t* keys, const uint64_t* offsets, int B,
+                             int64_t row_stride, const int64_t* counts, float* out, void* stream);
+int tts_hip_waveglow_infer_rows_seeded(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
+                                       const uint64_t* keys, const uint64_t* offsets, float sigma, float* audio, int precision,
+                                       int packed, int mem);
+int tts_hip_waveglow_infer_rows_seeded_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
+                                             const uint64_t* keys, const uint64_t* offsets, float sigma, float* audio,
+                                             int precision, int packed, void* stream);
+
 /* ---- Tacotron2.infer  (architectures/tacotron2_arch.py:866-925; called at models/tts/tacotron2.py:162)
  * tokens        int32 [B, Tin], 0 = pad
  * speaker       NULL or [B, speaker_embedding_dim]
@@ -153,6 +174,13 @@ int tts_hip_tacotron2_decode_seeded(tts_hip_engine* e, const tts_hip_encoded* en
                                     uint64_t seed, uint64_t offset, int win_len, int win_offset, int precision,
                                     float* mel, float* decoder_output, float* stop_tokens, float* attention,
                                     int32_t* lengths, int32_t* steps_run, int mem, void* stream);
+/* `decode_seeded` with one stream per row (keys / offsets: HOST arrays of B entries, B = the encoded batch's rows): row b's
+ * masks [max_len, 2, 256] are mask elements 0 .. max_len * 512 of stream (keys[b], offsets[b]), so step t of a row reads the
+ * same bits whatever max_len the batch imposes and whichever rows it is decoded with.  All three decoder machines.      */
+int tts_hip_tacotron2_decode_rows_seeded(tts_hip_engine* e, const tts_hip_encoded* encoded, int max_len, int early_stop,
+                                         const uint64_t* keys, const uint64_t* offsets, int win_len, int win_offset,
+                                         int precision, float* mel, float* decoder_output, float* stop_tokens,
+                                         float* attention, int32_t* lengths, int32_t* steps_run, int mem, void* stream);
 /* Runs the encoder for another token batch INTO an existing encoded batch (its device buffer is reused and only grows):
  * what a caller that synthesizes sentence after sentence wants -- no hipMalloc / hipFree per sentence, and the decoder's
  * cached step graphs (keyed by the buffer) survive from one sentence to the next.  Asynchronous like `encode`.        */

@@ -38,6 +38,11 @@ SIGNATURES = {
     'tts_hip_waveglow_infer_f16x3': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_int]),
     'tts_hip_random_fill': (c_int, [c_void_p, c_int, c_uint64, c_uint64, c_void_p, c_int64, c_void_p]),
     'tts_hip_waveglow_infer_seeded': (c_int, [c_void_p, c_void_p, c_int, c_int, c_uint64, c_uint64, c_float, c_void_p, c_int, c_int]),
+    'tts_hip_random_fill_rows': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    'tts_hip_waveglow_infer_rows_seeded': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                                   c_int, c_int, c_int]),
+    'tts_hip_waveglow_infer_rows_seeded_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
+                                                         c_void_p, c_int, c_int, c_void_p]),
     'tts_hip_tacotron2_infer': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     'tts_hip_tacotron2_infer_f16': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
@@ -67,6 +72,8 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'tts_hip_tacotron2_decode_seeded': (c_int, [c_void_p, c_void_p, c_int, c_int, c_uint64, c_uint64, c_int, c_int, c_int, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    'tts_hip_tacotron2_decode_rows_seeded': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'tts_hip_tacotron2_reencode': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     'tts_hip_encoded_free': (c_int, [c_void_p, c_void_p]),
     'tts_hip_kernel_timing': (c_int, [c_void_p, c_int]),

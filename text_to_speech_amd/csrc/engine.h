@@ -279,6 +279,10 @@ void resample_free(tts_hip_engine* e);
 // shared helpers
 // n floats of device-side samples into `out` on `st` (engine.hip: Philox4x32-10; kind = TTS_HIP_RANDOM_*)
 int philox_fill(tts_hip_engine* e, float* out, long long n, uint64_t seed, uint64_t offset, int kind, hipStream_t st);
+// B rows, `row_stride` floats apart: row b = the first counts[b] (null = row_stride) elements of stream (keys[b], offsets[b]);
+// keys / offsets / counts are host arrays, copied into the kernel arguments before the call returns
+int philox_fill_rows(tts_hip_engine* e, float* out, int B, long long row_stride, const uint64_t* keys, const uint64_t* offsets,
+                     const long long* counts, int kind, hipStream_t st);
 const HostTensor* find_tensor(const tts_hip_engine* e, const std::string& name);
 // uploads a host tensor to a fresh device allocation tracked in `allocs`
 int upload(tts_hip_engine* e, const float* src, size_t n, float** dst, std::vector<void*>& allocs);

@@ -102,12 +102,9 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint64_t ctr, uint64_t seed) {
 }
 __device__ __forceinline__ float unit_open(uint32_t x) { return ((float)(x >> 8) + 0.5f) * 5.9604644775390625e-8f; }
 
-// kind 0: standard normals, kind 1: prenet dropout masks.  One thread per Philox block (4 outputs).
-__global__ void philox_fill_kernel(float* __restrict__ out, long long n, uint64_t seed, uint64_t offset, int kind) {
-    const long long blk = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (blk * 4 >= n) return;
-    const Philox4 w = philox4x32_10(offset + (uint64_t)blk, seed);
-    float v[4];
+// The four outputs of one Philox block.  kind 0: standard normals, kind 1: prenet dropout masks.
+__device__ __forceinline__ void philox_block_values(uint64_t ctr, uint64_t seed, int kind, float v[4]) {
+    const Philox4 w = philox4x32_10(ctr, seed);
     if (kind == 0) {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
@@ -121,9 +118,44 @@ __global__ void philox_fill_kernel(float* __restrict__ out, long long n, uint64_
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = (w.x[k] >> 31) ? 2.0f : 0.0f;
     }
+}
+
+// One thread per Philox block (4 outputs).
+__global__ void philox_fill_kernel(float* __restrict__ out, long long n, uint64_t seed, uint64_t offset, int kind) {
+    const long long blk = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (blk * 4 >= n) return;
+    float v[4];
+    philox_block_values(offset + (uint64_t)blk, seed, kind, v);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if (blk * 4 + k < n) out[blk * 4 + k] = v[k];
+}
+
+// Per-row streams: row b = blockIdx.y writes out[b * row_stride + i] = element i of stream (key[b], offset[b]) for
+// i < count[b] -- the element rule of the flat kernel -- and touches nothing behind that.  The table travels by value in the
+// kernel arguments (one launch per kPhiloxRows rows), so the caller's host arrays need not outlive the call.
+constexpr int kPhiloxRows = 32;
+struct PhiloxRows {
+    uint64_t key[kPhiloxRows];
+    uint64_t offset[kPhiloxRows];
+    long long count[kPhiloxRows];
+};
+// vec4: every row base of the launch is 16-byte aligned (out is, and row_stride % 4 == 0)
+__global__ void philox_fill_rows_kernel(float* __restrict__ out, long long row_stride, PhiloxRows rows, int kind, int vec4) {
+    const int b = blockIdx.y;
+    const long long n = rows.count[b];
+    const long long blk = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (blk * 4 >= n) return;
+    float v[4];
+    philox_block_values(rows.offset[b] + (uint64_t)blk, rows.key[b], kind, v);
+    float* dst = out + (long long)b * row_stride + blk * 4;
+    if (vec4 && blk * 4 + 4 <= n) {
+        *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (blk * 4 + k < n) dst[k] = v[k];
+    }
 }
 
 }  // namespace
@@ -133,6 +165,29 @@ int philox_fill(tts_hip_engine* e, float* out, long long n, uint64_t seed, uint6
     const long long blocks = (n + 3) / 4;
     hipLaunchKernelGGL(philox_fill_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, out, n, seed, offset, kind);
     HIPCHK(e, hipGetLastError());
+    return TTS_HIP_OK;
+}
+
+int philox_fill_rows(tts_hip_engine* e, float* out, int B, long long row_stride, const uint64_t* keys, const uint64_t* offsets,
+                     const long long* counts, int kind, hipStream_t st) {
+    for (int b0 = 0; b0 < B; b0 += kPhiloxRows) {
+        const int nb = B - b0 < kPhiloxRows ? B - b0 : kPhiloxRows;
+        PhiloxRows rows{};
+        long long most = 0;
+        for (int r = 0; r < nb; ++r) {
+            rows.key[r] = keys[b0 + r];
+            rows.offset[r] = offsets[b0 + r];
+            rows.count[r] = counts ? counts[b0 + r] : row_stride;
+            if (rows.count[r] > most) most = rows.count[r];
+        }
+        if (most <= 0) continue;
+        float* base = out + (long long)b0 * row_stride;
+        const int vec4 = ((uintptr_t)base % 16 == 0 && row_stride % 4 == 0) ? 1 : 0;
+        const long long blocks = (most + 3) / 4;
+        hipLaunchKernelGGL(philox_fill_rows_kernel, dim3((unsigned)((blocks + 255) / 256), (unsigned)nb), dim3(256), 0, st, base,
+                           row_stride, rows, kind, vec4);
+        HIPCHK(e, hipGetLastError());
+    }
     return TTS_HIP_OK;
 }
 
@@ -517,6 +572,28 @@ int tts_hip_random_fill(tts_hip_engine* e, int kind, uint64_t seed, uint64_t off
     return philox_fill(e, out, (long long)n, seed, offset, kind, stream ? (hipStream_t)stream : e->stream);
 }
 
+// Per-row streams: row b of `out` (row_stride floats apart) = the first counts[b] elements of stream (keys[b], offsets[b]).
+int tts_hip_random_fill_rows(tts_hip_engine* e, int kind, const uint64_t* keys, const uint64_t* offsets, int B,
+                             int64_t row_stride, const int64_t* counts, float* out, void* stream) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (kind != TTS_HIP_RANDOM_NORMAL && kind != TTS_HIP_RANDOM_PRENET_MASK)
+        return set_err(e, TTS_HIP_EINVAL, "random_fill_rows: kind must be 0 (normal) or 1 (prenet mask), got %d", kind);
+    if (!keys || !offsets) return set_err(e, TTS_HIP_EINVAL, "random_fill_rows: keys / offsets is NULL");
+    if (B <= 0) return set_err(e, TTS_HIP_EINVAL, "random_fill_rows: B = %d must be positive", B);
+    if (!out || row_stride < 0) return set_err(e, TTS_HIP_EINVAL, "random_fill_rows: bad argument");
+    std::vector<long long> cnt((size_t)B, (long long)row_stride);
+    if (counts)
+        for (int b = 0; b < B; ++b) {
+            if (counts[b] < 0 || counts[b] > row_stride)
+                return set_err(e, TTS_HIP_EINVAL, "random_fill_rows: counts[%d] = %lld is outside [0, row_stride = %lld]", b,
+                               (long long)counts[b], (long long)row_stride);
+            cnt[b] = (long long)counts[b];
+        }
+    HIPCHK(e, hipSetDevice(e->device));
+    return philox_fill_rows(e, out, B, (long long)row_stride, keys, offsets, cnt.data(), kind,
+                            stream ? (hipStream_t)stream : e->stream);
+}
+
 // WaveGlow.infer with the noise drawn on the device (the reference's default: z = None, deterministic = False).
 int tts_hip_waveglow_infer_seeded(tts_hip_engine* e, const float* mel, int B, int T, uint64_t seed, uint64_t offset,
                                   float sigma, float* audio, int precision, int mem) {
@@ -598,6 +675,95 @@ int tts_hip_waveglow_infer_packed_async(tts_hip_engine* e, const float* mel, int
     int rc = stage_packed(e, B, T, lengths, who, &F, &n_gap);
     if (rc) return rc;
     return waveglow_run_packed(e, mel, B, T, z, sigma, audio, precision, (const int*)e->wg.ragged_info.p, F, n_gap);
+}
+
+// Everything a rows-seeded WaveGlow call can be refused for, checked before the noise is drawn: nothing is launched after
+// an error.  counts[b] = noise values row b needs (lengths[b] * 256, or T * 256 without lengths).
+static int check_rows_seeded(tts_hip_engine* e, const char* who, const float* mel, int B, int T, const int32_t* lengths,
+                             const uint64_t* keys, const uint64_t* offsets, const float* audio, int precision, int packed,
+                             std::vector<long long>* counts) {
+    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "%s: precision must be 0 (f32), 1 (f16) or 2 (f16x3)", who);
+    if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
+    if (!keys || !offsets) return set_err(e, TTS_HIP_EINVAL, "%s: keys / offsets is NULL", who);
+    if (B <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: B = %d must be positive", who, B);
+    if (!mel || !audio || T <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", who);
+    if ((long long)B * T * 32 > (1ll << 30)) return set_err(e, TTS_HIP_EINVAL, "%s: B*T too large", who);
+    if (packed && !lengths) return set_err(e, TTS_HIP_EINVAL, "%s: packed needs lengths, got NULL", who);
+    long long F = 0;
+    int rows = 0;
+    counts->assign((size_t)B, (long long)T * 256);
+    if (lengths)
+        for (int b = 0; b < B; ++b) {
+            if (lengths[b] < 0 || lengths[b] > T)
+                return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d is outside [0, T = %d]", who, b, (int)lengths[b], T);
+            (*counts)[b] = (long long)lengths[b] * 256;
+            F += lengths[b];
+            rows += lengths[b] > 0;
+        }
+    if (packed) {
+        F += rows > 1 ? (long long)TTS_HIP_WG_GAP_FRAMES * (rows - 1) : 0;
+        if (F > kMaxFramesPerRun)
+            return set_err(e, TTS_HIP_EINVAL, "%s: the packed row holds F = %lld frames, above one run's limit (%d); split the "
+                           "batch or use the ragged call", who, F, kMaxFramesPerRun);
+    } else if (T > kMaxFramesPerRun) {
+        return set_err(e, TTS_HIP_EINVAL, "%s: T = %d frames exceeds one run's limit (%d); use windowed inference", who, T,
+                       kMaxFramesPerRun);
+    }
+    return TTS_HIP_OK;
+}
+
+// The ragged / packed calls with row b's noise z[b, p, c] = normal element p * 8 + c of stream (keys[b], offsets[b]), drawn
+// into wg.io_zgen in the batch layout (a packed run reads it through its gather); only a row's real frames are drawn.
+int tts_hip_waveglow_infer_rows_seeded(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
+                                       const uint64_t* keys, const uint64_t* offsets, float sigma, float* audio, int precision,
+                                       int packed, int mem) {
+    const char* who = "waveglow_infer_rows_seeded";
+    if (!e) return TTS_HIP_EINVAL;
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "%s: bad mem kind %d", who, mem);
+    std::vector<long long> counts;
+    int rc = check_rows_seeded(e, who, mel, B, T, lengths, keys, offsets, audio, precision, packed, &counts);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t n_z = (size_t)B * T * 32 * 8, n_mel = (size_t)B * T * 80, n_out = (size_t)B * T * 256;
+    HIPCHK(e, e->wg.io_zgen.ensure(n_z * 4));
+    if ((rc = philox_fill_rows(e, e->wg.io_zgen.f(), B, (long long)T * 256, keys, offsets, counts.data(), TTS_HIP_RANDOM_NORMAL,
+                               e->stream)))
+        return rc;
+    // the generated noise is a device buffer whatever `mem` says about mel / audio
+    if (mem == TTS_HIP_MEM_DEVICE)
+        return waveglow_infer_impl(e, mel, B, T, e->wg.io_zgen.f(), sigma, audio, mem, precision, lengths, packed != 0);
+    HIPCHK(e, e->wg.io_mel.ensure(n_mel * 4));
+    HIPCHK(e, e->wg.io_out.ensure(n_out * 4));
+    HIPCHK(e, hipMemcpyAsync(e->wg.io_mel.p, mel, n_mel * 4, hipMemcpyHostToDevice, e->stream));
+    rc = waveglow_infer_impl(e, e->wg.io_mel.f(), B, T, e->wg.io_zgen.f(), sigma, e->wg.io_out.f(), TTS_HIP_MEM_DEVICE, precision,
+                             lengths, packed != 0);
+    if (rc) return rc;
+    HIPCHK(e, hipMemcpyAsync(audio, e->wg.io_out.p, n_out * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return TTS_HIP_OK;
+}
+
+int tts_hip_waveglow_infer_rows_seeded_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
+                                             const uint64_t* keys, const uint64_t* offsets, float sigma, float* audio,
+                                             int precision, int packed, void* stream) {
+    const char* who = "waveglow_infer_rows_seeded_async";
+    if (!e) return TTS_HIP_EINVAL;
+    std::vector<long long> counts;
+    int rc = check_rows_seeded(e, who, mel, B, T, lengths, keys, offsets, audio, precision, packed, &counts);
+    if (rc) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, e->wg.io_zgen.ensure((size_t)B * T * 32 * 8 * 4));
+    StreamScope scope(e, stream);
+    if ((rc = philox_fill_rows(e, e->wg.io_zgen.f(), B, (long long)T * 256, keys, offsets, counts.data(), TTS_HIP_RANDOM_NORMAL,
+                               e->stream)))
+        return rc;
+    if (packed) {
+        int F = 0, n_gap = 0;
+        if ((rc = stage_packed(e, B, T, lengths, who, &F, &n_gap))) return rc;
+        return waveglow_run_packed(e, mel, B, T, e->wg.io_zgen.f(), sigma, audio, precision, (const int*)e->wg.ragged_info.p, F, n_gap);
+    }
+    if (lengths && (rc = stage_ragged(e, B, T, lengths, kMaxFramesPerRun / T, who))) return rc;
+    return waveglow_run_chunks(e, mel, B, T, lengths, e->wg.io_zgen.f(), sigma, audio, precision);
 }
 
 int tts_hip_mel_stft_async(tts_hip_engine* e, const float* audio, int B, int N, float* mel, void* stream) {

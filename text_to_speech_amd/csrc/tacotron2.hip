@@ -1725,7 +1725,8 @@ static int run_fused(tts_hip_engine* e, DecodeCall c, int* steps) {
 static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, int max_len, int early_stop,
                                  const float* prenet_masks, int win_len, int win_offset, float* mel,
                                  float* decoder_output, float* stop_tokens, float* attention, int32_t* lengths,
-                                 int32_t* steps_run, int mem, bool half_w, const uint64_t* mask_seed = nullptr) {
+                                 int32_t* steps_run, int mem, bool half_w, const uint64_t* mask_seed = nullptr,
+                                 const uint64_t* row_keys = nullptr, const uint64_t* row_offsets = nullptr) {
     Tacotron2Dev& tc = e->taco;
     if (!tc.ready) return set_err(e, TTS_HIP_ENOTREADY, "tacotron2 weights not finalized");
     if (!en || !en->buf.p || en->B <= 0 || max_len <= 0) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode: bad argument");
@@ -1740,7 +1741,7 @@ static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, i
 
     bool backed_off = false;
     const DecMachine planned = choose_decoder_machine(e, B, Tin, &backed_off);
-    const bool with_masks = prenet_masks != nullptr || mask_seed != nullptr;
+    const bool with_masks = prenet_masks != nullptr || mask_seed != nullptr || row_keys != nullptr;
     DecoderWs ws{};
     if ((rc = plan_workspace(e, tc.ws, 4096, [&](Arena& A) { ws = decoder_layout(A, e, planned, B, Tin, max_len, with_masks); })))
         return rc;
@@ -1753,6 +1754,10 @@ static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, i
         HIPCHK(e, hipMemcpyAsync(ws.masks, prenet_masks, RD * 2 * PRE * 4, kin, st));
     } else if (mask_seed) {                                 // drawn on the device, straight into the workspace
         if ((rc = philox_fill(e, ws.masks, (long long)RD * 2 * PRE, mask_seed[0], mask_seed[1], TTS_HIP_RANDOM_PRENET_MASK, st))) return rc;
+    } else if (row_keys) {                                  // row b: elements 0 .. max_len * 512 of its own stream
+        if ((rc = philox_fill_rows(e, ws.masks, B, (long long)max_len * 2 * PRE, row_keys, row_offsets, nullptr,
+                                   TTS_HIP_RANDOM_PRENET_MASK, st)))
+            return rc;
     }
 
     // ---------------- decoder loop: the chosen machine, and the per-step graph from the start when that one gives up
@@ -1856,6 +1861,19 @@ extern "C" int tts_hip_tacotron2_decode_seeded(tts_hip_engine* e, const tts_hip_
     const uint64_t ms[2] = {seed, offset};
     return tacotron2_decode_impl(e, encoded, max_len, early_stop, nullptr, win_len, win_offset, mel, decoder_output, stop_tokens,
                                  attention, lengths, steps_run, mem, precision == 1, ms);
+}
+
+// `decode_seeded` with one stream per row: step t of a row reads the same bits whatever max_len the batch imposes
+extern "C" int tts_hip_tacotron2_decode_rows_seeded(tts_hip_engine* e, const tts_hip_encoded* encoded, int max_len, int early_stop,
+                                                    const uint64_t* keys, const uint64_t* offsets, int win_len, int win_offset,
+                                                    int precision, float* mel, float* decoder_output, float* stop_tokens,
+                                                    float* attention, int32_t* lengths, int32_t* steps_run, int mem, void* stream) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (precision != 0 && precision != 1) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode_rows_seeded: precision must be 0 (f32) or 1 (f16 weights)");
+    if (!keys || !offsets) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode_rows_seeded: keys / offsets is NULL");
+    StreamScope scope(e, stream);
+    return tacotron2_decode_impl(e, encoded, max_len, early_stop, nullptr, win_len, win_offset, mel, decoder_output, stop_tokens,
+                                 attention, lengths, steps_run, mem, precision == 1, nullptr, keys, offsets);
 }
 
 extern "C" int tts_hip_tacotron2_reencode(tts_hip_engine* e, tts_hip_encoded* encoded, const int32_t* tokens, int B, int Tin,

@@ -140,11 +140,15 @@ def _all_gather_rows(dst, row):
         dst[r] = t
 
 
-def synthesize_sharded(tokens, synth_fn, speaker=None, src: int = 0, device=None):
-    """scatter -> `synth_fn(local_tokens, local_speaker) -> (audio [n, S], counts [n])` on every rank -> gather."""
+def synthesize_sharded(tokens, synth_fn, speaker=None, src: int = 0, device=None, with_ids=False):
+    """scatter -> `synth_fn(local_tokens, local_speaker) -> (audio [n, S], counts [n])` on every rank -> gather.
+    `with_ids=True`: `synth_fn(local_tokens, local_speaker, ids)` also gets the global utterance indices of its rows (a list of
+    ints, row order), e.g. to key per-utterance random streams that do not depend on the world size
+    (`TTSPipeline.shard_fn(row_streams=True)`)."""
     local_tok, local_spk, parts = scatter_tokens(tokens, speaker, src=src, device=device)
     if local_tok.shape[0]:
-        audio, counts = synth_fn(local_tok, local_spk)             # numpy arrays or tensors (device tensors stay on the device)
+        extra = ([int(i) for i in parts[dist.get_rank()]],) if with_ids else ()
+        audio, counts = synth_fn(local_tok, local_spk, *extra)     # numpy arrays or tensors (device tensors stay on the device)
     else:
         audio, counts = np.zeros((0, 1), np.float32), np.zeros((0,), np.int64)
     return gather_audio(audio, counts, parts, dst=src, device=device)

@@ -143,6 +143,70 @@ class HipEngine:
             self.synchronize()
         return out
 
+    @staticmethod
+    def _row_tables(row_seeds, B=None, what='row_seeds'):
+        """(keys, offsets) -> two contiguous host uint64 [B] arrays (offsets None or a scalar: that value for every row)."""
+        if not isinstance(row_seeds, (tuple, list)) or len(row_seeds) != 2:
+            raise ValueError(f'{what} must be (keys, offsets), one entry per row')
+        keys, offsets = row_seeds
+        as_u64 = lambda seq: np.ascontiguousarray([int(v) & 0xFFFFFFFFFFFFFFFF for v in np.atleast_1d(np.asarray(seq, dtype=object))],
+                                                  dtype=np.uint64)
+        keys = as_u64(keys)
+        offsets = as_u64([0] * len(keys) if offsets is None else
+                         [offsets] * len(keys) if np.ndim(offsets) == 0 else offsets)
+        if len(keys) == 0 or len(keys) != len(offsets) or (B is not None and len(keys) != B):
+            raise ValueError(f'{what}: need one key and one offset per row'
+                             + (f' ({B} rows)' if B is not None else '') + f', got {len(keys)} and {len(offsets)}')
+        return keys, offsets
+
+    def random_normal_rows(self, row_stride: int, keys, offsets=None, counts=None, stream=None, out=None):
+        """N(0, 1) float32 [B, row_stride] on this engine's GPU with one Philox stream per row (tts_hip_random_fill_rows):
+        row b, element i = element i of `random_normal` under (keys[b], offsets[b]) for i < counts[b] (default row_stride).
+        Elements at i >= counts[b] are not written: they keep what `out` (a float32 CUDA tensor of B * row_stride elements to
+        fill in place) held, or the zeros of a fresh tensor."""
+        return self._random_rows(0, row_stride, keys, offsets, counts, stream, out)
+
+    def random_prenet_masks_rows(self, row_stride: int, keys, offsets=None, counts=None, stream=None, out=None):
+        """Prenet dropout mask values (2.0 with probability 0.5, else 0.0) [B, row_stride], one Philox stream per row, as
+        `random_normal_rows`.  With row_stride = max_len * 512, `.view(B, max_len, 2, 256)` is what
+        `tacotron2_decode(row_mask_seeds=(keys, offsets))` multiplies the prenet by."""
+        return self._random_rows(1, row_stride, keys, offsets, counts, stream, out)
+
+    def _random_rows(self, kind, row_stride, keys, offsets, counts, stream, out):
+        torch = self._torch()
+        dev = torch.device('cuda', self.device)
+        keys, offsets = self._row_tables((keys, offsets))
+        B, row_stride = len(keys), int(row_stride)
+        if row_stride < 0:
+            raise ValueError('row_stride must not be negative')
+        cnt_p = None
+        if counts is not None:
+            cnt = np.ascontiguousarray(np.asarray(counts, dtype=np.int64))
+            if cnt.shape != (B,) or (B and (int(cnt.min()) < 0 or int(cnt.max()) > row_stride)):
+                raise ValueError(f'counts must hold one value in [0, row_stride = {row_stride}] per row, got {cnt.tolist()}')
+            cnt_p = cnt.ctypes.data_as(ctypes.c_void_p)
+        if out is not None:
+            if not _is_torch_cuda(out) or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * row_stride:
+                raise ValueError(f'out must be a contiguous float32 CUDA tensor of {B} x {row_stride} elements')
+            self._check_device(out)
+        if stream is not None:
+            with self._enter_stream(stream):
+                if out is None:
+                    out = torch.zeros((B, row_stride), dtype=torch.float32, device=dev)
+            self._used_on(stream, out)
+            sp = ctypes.c_void_p(int(stream.cuda_stream))
+        else:
+            if out is None:
+                out = torch.zeros((B, row_stride), dtype=torch.float32, device=dev)
+            sp = None
+            self._order_after_torch()
+        self._check(self._lib.tts_hip_random_fill_rows(
+            self._h, kind, keys.ctypes.data_as(ctypes.c_void_p), offsets.ctypes.data_as(ctypes.c_void_p), B, row_stride, cnt_p,
+            ctypes.c_void_p(out.data_ptr()), sp), 'random_fill_rows')
+        if stream is None:
+            self.synchronize()
+        return out
+
     # ------------------------------------------------------------------ weights
     def set_tensor(self, name: str, array) -> None:
         a = np.ascontiguousarray(array, dtype=np.float32)
@@ -179,7 +243,7 @@ class HipEngine:
         return np.ascontiguousarray(arr, dtype=np.int32)
 
     def waveglow_infer(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', stream=None, seed=None, offset: int = 0,
-                       lengths=None, packed: bool = False):
+                       lengths=None, packed: bool = False, row_seeds=None):
         """mel [B, T, 80] (+ optional z [B, T*32, 8]) -> audio [B, T*256].  precision: 'f32' (exact fp32 MFMA), 'f16x3'
         (split fp16: fp32-class accuracy, ~3x faster) or 'f16' (fp16 operands).  `seed` (with z=None): the noise is drawn
         on the device from (seed, offset) -- the reference's default `z=None, deterministic=False`
@@ -192,9 +256,18 @@ class HipEngine:
         batch layout [B, T*32, 8] as without lengths.
         `packed=True` (needs `lengths`): the same results computed as ONE packed row (tts_hip_waveglow_infer_packed) -- the real
         frames of all rows one after another, 4 zero gap frames between two rows -- so the work follows sum(lengths), not
-        B * T.  The noise of `seed` is still drawn in the batch layout: a row gets the values the ragged call gives it."""
+        B * T.  The noise of `seed` is still drawn in the batch layout: a row gets the values the ragged call gives it.
+        `row_seeds=(keys, offsets)` (one pair per row; excludes `z` and `seed`): row b's noise z[b, p, c] is normal element
+        p * 8 + c of its own Philox stream (keys[b], offsets[b]), drawn inside the engine (tts_hip_waveglow_infer_rows_seeded)
+        -- the values `random_normal_rows` gives -- whatever batch the row sits in.  With `lengths` (ragged or packed) a row's
+        arithmetic is its own too, so its audio is that of a one-row call with its key up to fp32 re-association; without
+        `lengths` the batch is a padded one and a row still hears its padding."""
         if packed and lengths is None:
             raise ValueError('packed=True needs lengths (one frame count per row)')
+        if row_seeds is not None:
+            if z is not None or seed is not None:
+                raise ValueError('row_seeds excludes z and seed')
+            return self._waveglow_infer_rows(mel, row_seeds, sigma, precision, stream, lengths, packed)
         rag = self._lib.tts_hip_waveglow_infer_packed if packed else self._lib.tts_hip_waveglow_infer_ragged
         rag_async = (self._lib.tts_hip_waveglow_infer_packed_async if packed
                      else self._lib.tts_hip_waveglow_infer_ragged_async)
@@ -298,14 +371,70 @@ class HipEngine:
                        out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'waveglow_infer')
         return out
 
+    def _waveglow_infer_rows(self, mel, row_seeds, sigma, precision, stream, lengths, packed):
+        pcodes = {'f32': 0, 'f16': 1, 'f16x3': 2}
+        if precision not in pcodes:
+            raise ValueError(f"precision must be one of {tuple(pcodes)}, got {precision!r}")
+        dev = _is_torch_cuda(mel)
+        if dev:
+            torch = self._torch()
+            if mel.dim() != 3 or mel.shape[2] != 80:
+                raise ValueError(f'mel must be [B, T, 80], got {tuple(mel.shape)}')
+            self._check_device(mel)
+        else:
+            if stream is not None:
+                raise ValueError('stream= needs device tensors')
+            mel = np.ascontiguousarray(mel, dtype=np.float32)
+            if mel.ndim != 3 or mel.shape[2] != 80:
+                raise ValueError(f'mel must be [B, T, 80], got {mel.shape}')
+        B, T = int(mel.shape[0]), int(mel.shape[1])
+        keys, offsets = self._row_tables(row_seeds, B)
+        lens = None if lengths is None else self._frame_lengths(lengths, B, T)
+        lens_p = None if lens is None else lens.ctypes.data_as(ctypes.c_void_p)
+        tables = (keys.ctypes.data_as(ctypes.c_void_p), offsets.ctypes.data_as(ctypes.c_void_p))
+        if not dev:
+            out = np.empty((B, T * 256), dtype=np.float32)
+            self._check(self._lib.tts_hip_waveglow_infer_rows_seeded(
+                self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, lens_p, *tables, float(sigma),
+                out.ctypes.data_as(ctypes.c_void_p), pcodes[precision], 1 if packed else 0, MEM_HOST), 'waveglow_infer_rows_seeded')
+            return out
+        if stream is not None:
+            with self._enter_stream(stream):
+                m = mel.to(torch.float32).contiguous()
+                out = torch.empty((B, T * 256), dtype=torch.float32, device=mel.device)
+            self._used_on(stream, mel, m, out)
+            self._check(self._lib.tts_hip_waveglow_infer_rows_seeded_async(
+                self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p, *tables, float(sigma), ctypes.c_void_p(out.data_ptr()),
+                pcodes[precision], 1 if packed else 0, ctypes.c_void_p(int(stream.cuda_stream))), 'waveglow_infer_rows_seeded_async')
+            return out
+        m = mel.to(torch.float32).contiguous()
+        out = torch.empty((B, T * 256), dtype=torch.float32, device=mel.device)
+        self._order_after_torch()
+        self._check(self._lib.tts_hip_waveglow_infer_rows_seeded(
+            self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p, *tables, float(sigma), ctypes.c_void_p(out.data_ptr()),
+            pcodes[precision], 1 if packed else 0, MEM_DEVICE), 'waveglow_infer_rows_seeded')
+        return out
+
     # ------------------------------------------------------------------ Tacotron2
     def tacotron2_infer(self, tokens, speaker=None, max_len: int = 1000, early_stopping: bool = True,
                         prenet_masks=None, attn_mask_win_len=None, attn_mask_offset: int = 0, want_attention=True,
-                        precision: str = 'f32'):
+                        precision: str = 'f32', row_mask_seeds=None):
         """tokens int32 [B, Tin] -> Tacotron2InferenceOutput of numpy arrays (or torch tensors for CUDA tokens).
-        precision 'f16': decoder LSTM weights in fp16 (fp32 accumulate and state)."""
+        precision 'f16': decoder LSTM weights in fp16 (fp32 accumulate and state).
+        `row_mask_seeds=(keys, offsets)` (excludes `prenet_masks`): the prenet dropout masks are drawn on the device, row b
+        from its own stream (encode + `tacotron2_decode(row_mask_seeds=...)`)."""
         if precision not in ('f32', 'f16'):
             raise ValueError(f"precision must be 'f32' or 'f16', got {precision!r}")
+        if row_mask_seeds is not None:
+            if prenet_masks is not None:
+                raise ValueError('pass either prenet_masks or row_mask_seeds, not both')
+            enc = self.tacotron2_encode(tokens, speaker=speaker)
+            try:
+                return self.tacotron2_decode(enc, max_len=max_len, early_stopping=early_stopping,
+                                             attn_mask_win_len=attn_mask_win_len, attn_mask_offset=attn_mask_offset,
+                                             want_attention=want_attention, precision=precision, row_mask_seeds=row_mask_seeds)
+            finally:
+                enc.close()
         fn = self._lib.tts_hip_tacotron2_infer if precision == 'f32' else self._lib.tts_hip_tacotron2_infer_f16
         dev = _is_torch_cuda(tokens)
         if dev:
@@ -404,13 +533,17 @@ class HipEngine:
 
     def tacotron2_decode(self, encoded, max_len: int = 1000, early_stopping: bool = True, prenet_masks=None,
                          attn_mask_win_len=None, attn_mask_offset: int = 0, want_attention=True, precision: str = 'f32',
-                         stream=None, mask_seed=None):
+                         stream=None, mask_seed=None, row_mask_seeds=None):
         """Decoder loop + postnet on an `EncodedBatch`; may be called repeatedly (new dropout masks, other `max_len`).
         `mask_seed` = (seed, offset): the prenet dropout masks are drawn on the device (tts_hip_tacotron2_decode_seeded)
         instead of being passed in.  Returns after `stream` (or the engine's stream) has drained: the loop's length is
-        decided on the GPU."""
-        if mask_seed is not None and prenet_masks is not None:
-            raise ValueError('pass either prenet_masks or mask_seed, not both')
+        decided on the GPU.
+        `row_mask_seeds` = (keys, offsets), one pair per row: row b's masks [max_len, 2, 256] are mask elements
+        0 .. max_len * 512 of its own stream (tts_hip_tacotron2_decode_rows_seeded; `random_prenet_masks_rows` returns the same
+        values), so a row draws the same dropout whichever rows it is decoded with and whatever `max_len` they impose."""
+        if sum(x is not None for x in (mask_seed, prenet_masks, row_mask_seeds)) > 1:
+            raise ValueError('pass only one of prenet_masks, mask_seed and row_mask_seeds')
+        row_tables = None if row_mask_seeds is None else self._row_tables(row_mask_seeds, encoded.B, 'row_mask_seeds')
         if precision not in ('f32', 'f16'):
             raise ValueError(f"precision must be 'f32' or 'f16', got {precision!r}")
         if encoded.engine is not self or encoded.handle is None:
@@ -457,7 +590,13 @@ class HipEngine:
         steps = ctypes.c_int32(0)
         sp = self._order_after_torch(stream) if dev else None
         win = int(attn_mask_win_len) if attn_mask_win_len is not None else 0
-        if mask_seed is not None:
+        if row_tables is not None:
+            self._check(self._lib.tts_hip_tacotron2_decode_rows_seeded(
+                self._h, encoded.handle, max_len, 1 if early_stopping else 0, row_tables[0].ctypes.data_as(ctypes.c_void_p),
+                row_tables[1].ctypes.data_as(ctypes.c_void_p), win, int(attn_mask_offset), 1 if precision == 'f16' else 0,
+                ptr(mel), ptr(dec), ptr(stop), ptr(attn), ptr(lengths), ctypes.cast(ctypes.byref(steps), ctypes.c_void_p),
+                MEM_DEVICE if dev else MEM_HOST, sp), 'tacotron2_decode_rows_seeded')
+        elif mask_seed is not None:
             u64 = lambda v: ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
             self._check(self._lib.tts_hip_tacotron2_decode_seeded(
                 self._h, encoded.handle, max_len, 1 if early_stopping else 0, u64(mask_seed[0]), u64(mask_seed[1]), win,

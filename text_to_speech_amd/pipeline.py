@@ -27,12 +27,13 @@ class TTSPipeline:
         if rank is None:
             import torch.distributed as dist
             rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self._job_seed = self._seed & 0xFFFFFFFFFFFFFFFF       # un-ranked: per-row streams are keyed by the utterance, not the rank
         self._seed = rank_stream(self._seed, rank)
         self._offset = 0                                # running block offset in the engine's device-side Philox stream
 
     def synthesize_tokens(self, tokens, speaker=None, max_length=10.0, deterministic=False, prenet_masks=None, z=None,
                           sigma=1.0, early_stopping=True, round_frames_to=8, on_device=False, reduce_noise=False,
-                          trim_silence=False, ragged=False):
+                          trim_silence=False, ragged=False, row_ids=None):
         """tokens int32 [B, Tin] (0 = pad) -> (list of B float32 waveforms, lengths [B] in frames, steps run).
         `ragged`: the decoder's lengths go to the vocoder (HipEngine.waveglow_infer(lengths=...)) instead of a -11 fill, so
         every waveform is what its sentence gives when vocoded alone; False (default): the reference's batched path, where
@@ -41,10 +42,17 @@ class TTSPipeline:
         samples, sample counts [B] int64 device tensor, steps run).
         `reduce_noise` / `trim_silence`: the reference's waveform clean-up (audio_processing.reduce_noise, trim_silence with
         method 'window') on the device, each row with its own sample count as its length, at RATE Hz; trimming changes the
-        lengths, so it needs host output (on_device=False)."""
+        lengths, so it needs host output (on_device=False).
+        `row_ids` [B] (ints, e.g. the global utterance indices `synthesize_sharded(with_ids=True)` hands a rank; excludes
+        `prenet_masks`, `z` and `deterministic=True`): row b's dropout masks and noise come from streams of its own, keyed by
+        `stream_key(job seed, MASK_STREAM / NOISE_STREAM, row_ids[b], 0, 0)` with the job-wide seed as given (not this rank's
+        `rank_stream`); the running offset is untouched.  An utterance then draws the same values in any batch, on any rank
+        and at any world size; with `ragged=True` its audio is its own as well (up to fp32 re-association), while the padded
+        path (`ragged=False`) keeps hearing the batch's padding."""
         if on_device and trim_silence:
             raise ValueError('trim_silence=True needs on_device=False (trimmed rows have new lengths)')
         import torch
+        from .runtime import MASK_STREAM, NOISE_STREAM, stream_key
         eng = self.engine
         dev = torch.device('cuda', eng.device)
         as_dev = lambda x, dt: (x.to(device=dev, dtype=dt) if torch.is_tensor(x)
@@ -54,7 +62,16 @@ class TTSPipeline:
         n_tok = int((tok != 0).sum(dim=1).max())
         max_len = int(np.float32(n_tok) * np.float32(max_length)) if isinstance(max_length, float) else int(max_length)
         max_len = max(1, max_len)
-        if prenet_masks is None and not deterministic:          # drawn on the device (engine's Philox stream)
+        mask_rows = noise_rows = None
+        if row_ids is not None:
+            if prenet_masks is not None or z is not None or deterministic:
+                raise ValueError('row_ids excludes prenet_masks, z and deterministic=True')
+            ids = [int(i) for i in (row_ids.tolist() if hasattr(row_ids, 'tolist') else row_ids)]
+            if len(ids) != B:
+                raise ValueError(f'row_ids must hold one id per row ({B} rows), got {len(ids)}')
+            mask_rows = ([stream_key(self._job_seed, MASK_STREAM, i) for i in ids], [0] * B)
+            noise_rows = ([stream_key(self._job_seed, NOISE_STREAM, i) for i in ids], [0] * B)
+        elif prenet_masks is None and not deterministic:          # drawn on the device (engine's Philox stream)
             prenet_masks = eng.random_prenet_masks(B, max_len, self._seed, self._offset)
             self._offset += (B * max_len * 512 + 3) // 4
         elif prenet_masks is not None:
@@ -63,7 +80,8 @@ class TTSPipeline:
             speaker = as_dev(speaker, torch.float32)
         out = eng.tacotron2_infer(tok, speaker=speaker, max_len=max_len, early_stopping=early_stopping,
                                   prenet_masks=prenet_masks, want_attention=False,
-                                  precision=self.synthesizer_precision)
+                                  precision=self.synthesizer_precision,
+                                  **({} if mask_rows is None else {'row_mask_seeds': mask_rows}))
         lengths = out.lengths.clamp(min=0)
         steps = eng.last_steps
         T = int(lengths.max())
@@ -80,7 +98,10 @@ class TTSPipeline:
         else:
             valid = torch.arange(T, device=dev)[None, :] < lengths[:, None]
             mel = torch.where(valid[:, :, None], mel, torch.full_like(mel, PAD_MEL_VALUE))
-        if z is None and not deterministic:
+        if noise_rows is not None:
+            audio = eng.waveglow_infer(mel.contiguous(), sigma=sigma, precision=self.vocoder_precision, row_seeds=noise_rows,
+                                       **voc)
+        elif z is None and not deterministic:
             audio = eng.waveglow_infer(mel.contiguous(), sigma=sigma, precision=self.vocoder_precision, seed=self._seed,
                                        offset=self._offset, **voc)
             self._offset += (B * T * 256 + 3) // 4
@@ -105,12 +126,19 @@ class TTSPipeline:
                     for b in range(B)], n, steps
         return [audio_h[b, :int(n[b]) * 256].copy() for b in range(B)], n, steps
 
-    def shard_fn(self, **kwargs):
-        """`synth_fn(local_tokens, local_speaker) -> (audio [n, S] zero padded, sample counts [n])` for
+    def shard_fn(self, row_streams=False, **kwargs):
+        """`row_streams=True`: a three-argument `synth_fn(local_tokens, local_speaker, ids)` for
+        `synthesize_sharded(with_ids=True)` -- the global utterance indices become `synthesize_tokens(row_ids=ids)`, so an
+        utterance gets the same masks and noise at every world size.  Otherwise:
+        `synth_fn(local_tokens, local_speaker) -> (audio [n, S] zero padded, sample counts [n])` for
         `distributed.synthesize_sharded`: this rank's share of the utterances through `synthesize_tokens(**kwargs)`.  Both
         results are DEVICE tensors (the waveforms go from WaveGlow's output buffer straight into the RCCL gather; the only
         device-to-host copy of the job is rank 0's, after the gather)."""
         def synth(local_tokens, local_speaker):
             audio, counts, _ = self.synthesize_tokens(local_tokens, speaker=local_speaker, on_device=True, **kwargs)
             return audio, counts
-        return synth
+
+        def synth_rows(local_tokens, local_speaker, ids):
+            audio, counts, _ = self.synthesize_tokens(local_tokens, speaker=local_speaker, on_device=True, row_ids=ids, **kwargs)
+            return audio, counts
+        return synth_rows if row_streams else synth

@@ -18,6 +18,8 @@ documented Philox4x32-10 stream (include/tts_hip.h, oracle/philox_ref.py), keyed
 offset -- so no host-made tensor crosses PCIe.  The dropout bits and the noise are separate streams of one seed (key = seed
 XOR a purpose constant in the high word: MASK_STREAM / NOISE_STREAM).  Explicit control stays: pass `prenet_masks` / `z`, or
 `deterministic=True`, or `seed=` (that call then starts at offset 0 of that seed's streams and is reproducible).
+Per-row streams (`streams=[...]`, one id per row): every row draws from its own stream, keyed by `stream_key(seed, purpose,
+utterance, part, trial)` at offset 0, so a sentence's masks and noise do not depend on how it was batched.
 """
 from __future__ import annotations
 
@@ -41,6 +43,31 @@ _U64 = (1 << 64) - 1
 def rank_stream(seed: int, rank: int) -> int:
     """Key of rank `rank`'s stream under a job-wide seed: ranks synthesize different shards and must not draw identical noise."""
     return (int(seed) ^ (((int(rank) + 1) * 0x9E3779B97F4A7C15) & _U64)) & _U64 if rank else int(seed) & _U64
+
+
+def _mix64(x: int) -> int:
+    """splitmix64's output function of state x + golden gamma (Steele, Lea, Flood, OOPSLA'14): _mix64(0) is its first output."""
+    x = (int(x) + 0x9E3779B97F4A7C15) & _U64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _U64
+    return x ^ (x >> 31)
+
+
+def stream_key(seed: int, purpose: int, utterance: int = 0, part: int = 0, trial: int = 0) -> int:
+    """Philox key of ONE row's stream: derived from what the row is -- (seed, MASK_STREAM / NOISE_STREAM, utterance number,
+    part of the text, retry) -- not from where it sits in a batch.  The stream always starts at offset 0."""
+    k = _mix64((int(seed) ^ int(purpose)) & _U64)
+    for v in (utterance, part, trial):
+        k = _mix64(k ^ (int(v) & _U64))
+    return k
+
+
+def _row_ids(streams, B, width):
+    """`streams` -> B tuples of `width` ints (a bare int is an utterance number; missing trailing fields are 0)."""
+    ids = [tuple(int(v) for v in (s if isinstance(s, (tuple, list)) else (s,))) for s in streams]
+    if len(ids) != B or any(not 1 <= len(i) <= width for i in ids):
+        raise ValueError(f'streams must hold one id of at most {width} ints per row ({B} rows), got {streams!r}')
+    return [i + (0,) * (width - len(i)) for i in ids]
 
 
 def sample_prenet_masks(rng, B, max_len):
@@ -158,7 +185,13 @@ class HipRuntime(Runtime):
     # ------------------------------------------------------------------ Tacotron2.infer (tacotron2_arch.py:866-925)
     def tacotron2_infer(self, inputs, *, max_length=None, early_stopping=True, attn_mask_offset=0.5,
                         attn_mask_win_len=None, prenet_masks=None, deterministic=False, seed=None, precision=None,
-                        **_ignored):
+                        streams=None, **_ignored):
+        """`streams=[(utterance, part, trial), ...]` (one id per row; excludes `prenet_masks` / `deterministic=True`): row b's
+        dropout masks come from its own stream `stream_key(seed or the runtime's seed, MASK_STREAM, *id)` at offset 0; the
+        runtime's running offset is neither used nor advanced.  A row then draws the same masks in any batch (its mel is its
+        own up to the fp32 re-association between decoder machines)."""
+        if streams is not None and (prenet_masks is not None or deterministic):
+            raise ValueError('streams excludes prenet_masks and deterministic=True')
         if isinstance(inputs, (tuple, list)):
             tokens, speaker = inputs[0], (inputs[1] if len(inputs) > 1 else None)
         else:
@@ -179,8 +212,11 @@ class HipRuntime(Runtime):
         max_len = max(1, max_len)
         if attn_mask_win_len is not None and isinstance(attn_mask_offset, float):   # :894-897
             attn_mask_offset = int(np.float32(attn_mask_win_len) * np.float32(attn_mask_offset))
-        mask_seed = None
-        if prenet_masks is None and not deterministic:
+        mask_seed = row_mask_seeds = None
+        if streams is not None:
+            base = self._seed if seed is None else int(seed)
+            row_mask_seeds = ([stream_key(base, MASK_STREAM, *i) for i in _row_ids(streams, B, 3)], [0] * B)
+        elif prenet_masks is None and not deterministic:
             if seed is not None:
                 mask_seed = ((int(seed) ^ MASK_STREAM) & _U64, 0)
             else:
@@ -196,6 +232,11 @@ class HipRuntime(Runtime):
             spk_np = None if speaker is None else (speaker.detach().cpu().numpy() if _is_torch_cuda(speaker) else np.asarray(speaker))
             key = ('host', tokens.shape, tokens.astype(np.int32).tobytes(),
                    None if spk_np is None else spk_np.astype(np.float32).tobytes())
+        if row_mask_seeds is not None and not hasattr(self.engine, 'tacotron2_encode'):
+            return self.engine.tacotron2_infer(
+                tokens, speaker=speaker, max_len=max_len, early_stopping=bool(early_stopping),
+                attn_mask_win_len=attn_mask_win_len, attn_mask_offset=int(attn_mask_offset or 0),
+                precision=precision or self.synthesizer_precision, row_mask_seeds=row_mask_seeds)
         if not hasattr(self.engine, 'tacotron2_encode'):        # an engine object without the split entry points
             if mask_seed is not None and prenet_masks is None:
                 prenet_masks = sample_prenet_masks(np.random.default_rng(mask_seed[0] + mask_seed[1]), B, max_len)
@@ -221,7 +262,8 @@ class HipRuntime(Runtime):
             return self.engine.tacotron2_decode(
                 self._encoded[1], max_len=max_len, early_stopping=bool(early_stopping), prenet_masks=prenet_masks,
                 attn_mask_win_len=attn_mask_win_len, attn_mask_offset=int(attn_mask_offset or 0),
-                precision=precision or self.synthesizer_precision, mask_seed=mask_seed)
+                precision=precision or self.synthesizer_precision,
+                **({'mask_seed': mask_seed} if row_mask_seeds is None else {'row_mask_seeds': row_mask_seeds}))
         except Exception:
             # a failed decode may have been caused by the encoded batch itself (e.g. the encoder's block exchange timed out and
             # left its status in the buffer): a retry must run the encoder again, not reuse it
@@ -257,13 +299,19 @@ class HipRuntime(Runtime):
 
     # ------------------------------------------------------------------ WaveGlow.infer (waveglow_arch.py:244-306)
     def waveglow_infer(self, mel, z=None, sigma=1.0, deterministic=False, seed=None, precision=None, lengths=None,
-                       packed=False, **_ignored):
+                       packed=False, streams=None, **_ignored):
         """`lengths` [B] (frames of each row that are real): a batch of unequal rows -- every row's audio is that of its own
         frames, zeros behind it (HipEngine.waveglow_infer); the noise is drawn in the batch layout either way.
         `packed=True` (with `lengths`): the same call computed as one packed row; noise values and the running offset are
-        those of the call without it."""
+        those of the call without it.
+        `streams=[(utterance, part), ...]` (one id per row; excludes `z` / `deterministic=True`): row b's noise comes from
+        its own stream `stream_key(seed or the runtime's seed, NOISE_STREAM, utterance, part, 0)` at offset 0; the running
+        offset is neither used nor advanced.  With `lengths` (packed or not) a row's audio is then the same in any batch, up
+        to fp32 re-association; a padded batch (no `lengths`) keeps hearing its padding."""
         if packed and lengths is None:
             raise ValueError('packed=True needs lengths (one frame count per row)')
+        if streams is not None and (z is not None or deterministic):
+            raise ValueError('streams excludes z and deterministic=True')
         dev = _is_torch_cuda(mel)
         if not dev:
             mel = np.asarray(mel, dtype=np.float32)
@@ -271,6 +319,11 @@ class HipRuntime(Runtime):
             mel = mel[None]
         B, T = int(mel.shape[0]), int(mel.shape[1])
         ragged = {} if lengths is None else {'lengths': lengths, 'packed': True} if packed else {'lengths': lengths}
+        if streams is not None:
+            base = self._seed if seed is None else int(seed)
+            keys = [stream_key(base, NOISE_STREAM, *i) for i in _row_ids(streams, B, 2)]
+            return self.engine.waveglow_infer(mel, sigma=float(sigma), precision=precision or self.vocoder_precision,
+                                              row_seeds=(keys, [0] * B), **ragged)
         if z is None and not deterministic:
             if seed is not None:
                 zs, zo = (int(seed) ^ NOISE_STREAM) & _U64, 0
@@ -292,4 +345,4 @@ def build_runtime(runtime, path, *args, **kwargs):
     return _runtimes[runtime](path, *args, **kwargs)
 
 
-__all__ = ['Runtime', 'HipRuntime', 'build_runtime', 'Tacotron2InferenceOutput']
+__all__ = ['Runtime', 'HipRuntime', 'build_runtime', 'Tacotron2InferenceOutput', 'stream_key']

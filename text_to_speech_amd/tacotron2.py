@@ -47,7 +47,10 @@ class Tacotron2:
 
     def infer(self, text, *, embeddings=None, callbacks=None, predicted=None, overwrite=False, return_output=True,
               max_length=10., max_text_length=-1, max_trial=5, min_fpt_ratio=2., max_fpt_ratio=10., vocoder=None,
-              silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, **kwargs):
+              silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, utterance=None, **kwargs):
+        """`utterance` (an int; `predict(sentence_streams=True)` numbers its inputs): every random draw of this text comes
+        from a stream of its own -- part p at trial t decodes with the id (utterance, p, t) and is vocoded with (utterance, p),
+        passed to the models as `streams=[...]` (HipRuntime) -- so with a `seed` the audio does not depend on batching."""
         if isinstance(text, dict):                                   # get_text_from_paragraph (tacotron2.py:369-370)
             text = text['text' if 'text' in text else 'content']
         callbacks = _as_callbacks(callbacks)
@@ -56,16 +59,17 @@ class Tacotron2:
                 apply_callbacks(callbacks, predicted[text], {}, save=False)
             return predicted[text]
         part = self._synthesize(text, embeddings=embeddings, max_length=max_length, max_text_length=max_text_length,
-                                max_trial=max_trial, min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, **kwargs)
+                                max_trial=max_trial, min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio,
+                                utterance=utterance, **kwargs)
         return self._vocode_and_finish(part, callbacks=callbacks, predicted=predicted, return_output=return_output,
                                        vocoder=vocoder, silence_time=silence_time, vocoder_config=vocoder_config,
-                                       reduce_noise=reduce_noise, trim_silence=trim_silence, **kwargs)
+                                       reduce_noise=reduce_noise, trim_silence=trim_silence, utterance=utterance, **kwargs)
 
     # `infer` = `_synthesize` (text -> mels; the autoregressive, latency-bound half) followed by `_vocode_and_finish`
     # (mels -> audio, callbacks; the throughput-bound half).  They are separate so that `stream(overlap=True)` can run
     # the first half of sentence n + 1 while the second half of sentence n is still on the GPU.
     def _synthesize(self, text, *, embeddings=None, max_length=10., max_text_length=-1, max_trial=5, min_fpt_ratio=2.,
-                    max_fpt_ratio=10., **kwargs):
+                    max_fpt_ratio=10., utterance=None, **kwargs):
         if max_text_length == -1:
             splitted = [text]
         elif max_text_length == -2:
@@ -83,12 +87,13 @@ class Tacotron2:
 
         t0 = time.time()
         mels, attention_weights = [], []
-        for inp in encoded:
+        for p, inp in enumerate(encoded):
             length = len(inp)
             success = False
             inputs = inp[None] if embeddings is None else (inp[None], np.asarray(embeddings)[None])
             for trial in range(max_trial):
-                outputs = self.compiled_infer(inputs, max_length=max_length, **kwargs)
+                ids = {} if utterance is None else {'streams': [(int(utterance), p, trial)]}
+                outputs = self.compiled_infer(inputs, max_length=max_length, **ids, **kwargs)
                 n_frames = int(_to_numpy(outputs.lengths)[0])
                 ratio = n_frames / length
                 if min_fpt_ratio < ratio < max_fpt_ratio:
@@ -120,14 +125,15 @@ class Tacotron2:
 
     def _vocode_and_finish(self, part, *, callbacks=None, predicted=None, return_output=True, vocoder=None,
                            silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, pack_vocoder=False,
-                       **kwargs):
+                           utterance=None, **kwargs):
         audios, vocoder_time = None, 0.
         if vocoder is not None:
             t1 = time.time()
             audios = []
-            for mel in part['mel']:
+            for p, mel in enumerate(part['mel']):
                 if mel.shape[0] > 0:
-                    audio = vocoder(mel, **{**kwargs, **vocoder_config})
+                    ids = {} if utterance is None else {'streams': [(int(utterance), p)]}
+                    audio = vocoder(mel, **ids, **{**kwargs, **vocoder_config})
                     if len(audio.shape) == 2:
                         audio = audio[0]
                     audios.append(_to_numpy(audio))
@@ -209,7 +215,7 @@ class Tacotron2:
                         'audio_filename', 'post_processing')
 
     def predict(self, inputs, *, predicted=None, callbacks=None, return_results=True, return_output=None,
-                overlap=False, batch_backlog=None, pack_vocoder=False, **kwargs):
+                overlap=False, batch_backlog=None, pack_vocoder=False, sentence_streams=False, **kwargs):
         """BaseModel.predict (base_model.py:676-711): builds the callbacks unless the caller brings its own `predicted`
         map, then runs `infer` sequentially; returns the result dicts (or the `predicted` entries when a JSON saver is
         active and `return_output` was not forced).
@@ -221,7 +227,12 @@ class Tacotron2:
         decoder; otherwise dropout masks and noise are drawn from the runtime's stream in the batch's layout: the same
         distribution, another realisation than the sequential loop's.  Not combined with `overlap=True`.
         `pack_vocoder=True` (needs `batch_backlog >= 2`): the group's one vocoder call gets `packed=True` -- the same audio,
-        computed on the frames that exist instead of rows x longest row (HipEngine.waveglow_infer)."""
+        computed on the frames that exist instead of rows x longest row (HipEngine.waveglow_infer).
+        `sentence_streams=True`: every input taken from `inputs` gets the next utterance number (from 0; a text served from
+        the cache consumes one too, so grouping cannot shift later sentences) and all its random draws come from streams of
+        its own (`infer(utterance=...)`): with a `seed`, a sentence's dropout masks and noise -- and so its audio, up to fp32
+        re-association between the decoder machines and vocoder layouts -- are the same in the sequential loop, with
+        `overlap=True`, and in any `batch_backlog` grouping (packed or not), from run to run."""
         backlog = batch_backlog is not None and int(batch_backlog) >= 2
         if pack_vocoder and not backlog:
             raise ValueError('pack_vocoder=True needs batch_backlog >= 2 (it packs the vocoder call of a backlog group)')
@@ -245,13 +256,16 @@ class Tacotron2:
         results = []
         if backlog:
             outputs = self._infer_backlog(inputs, int(batch_backlog), predicted=predicted, callbacks=callbacks,
-                                          return_output=return_output, pack_vocoder=bool(pack_vocoder), **kwargs)
+                                          return_output=return_output, pack_vocoder=bool(pack_vocoder),
+                                          sentence_streams=bool(sentence_streams), **kwargs)
         elif overlap and kwargs.get('vocoder') is not None:
             outputs = self._infer_overlapped(inputs, predicted=predicted, callbacks=callbacks,
-                                             return_output=return_output, **kwargs)
+                                             return_output=return_output, sentence_streams=bool(sentence_streams),
+                                             **kwargs)
         else:
             outputs = ((inp, self.infer(inp, predicted=predicted, callbacks=callbacks, return_output=return_output,
-                                        **kwargs)) for inp in inputs)
+                                        **({'utterance': n} if sentence_streams else {}), **kwargs))
+                       for n, inp in enumerate(inputs))
         for inp, output in outputs:
             text = inp['text' if 'text' in inp else 'content'] if isinstance(inp, dict) else inp
             if return_results:
@@ -263,7 +277,8 @@ class Tacotron2:
 
     _synth_kwargs = ('embeddings', 'max_length', 'max_text_length', 'max_trial', 'min_fpt_ratio', 'max_fpt_ratio')
 
-    def _infer_overlapped(self, inputs, *, predicted, callbacks, return_output, overwrite=False, **kwargs):
+    def _infer_overlapped(self, inputs, *, predicted, callbacks, return_output, overwrite=False, sentence_streams=False,
+                          **kwargs):
         """Sentence-level software pipeline: a worker thread runs `_synthesize` for the next input while this thread
         vocodes the previous one.  The synthesizer and the vocoder must sit on different engine handles (two HIP streams;
         calls on one handle are serialised) -- `get_models(..., overlap=True)` builds such a pair.  Measured on MI355X
@@ -278,16 +293,17 @@ class Tacotron2:
 
         def producer():
             try:
-                for inp in inputs:
+                for n, inp in enumerate(inputs):
                     text = inp['text' if 'text' in inp else 'content'] if isinstance(inp, dict) else inp
+                    ids = {'utterance': n} if sentence_streams else {}
                     if predicted and not overwrite and text in predicted:
-                        q.put((inp, text, None, None))
+                        q.put((inp, text, None, None, ids))
                         continue
                     extra = {k: v for k, v in voc_kw.items() if k not in ('vocoder', 'silence_time', 'vocoder_config',
                                                                              'reduce_noise', 'trim_silence')}
-                    q.put((inp, text, self._synthesize(text, **synth_kw, **extra), None))
+                    q.put((inp, text, self._synthesize(text, **synth_kw, **ids, **extra), None, ids))
             except BaseException as exc:                              # noqa: BLE001 -- re-raised in the consumer
-                q.put((None, None, None, exc))
+                q.put((None, None, None, exc, {}))
             finally:
                 q.put(DONE)
 
@@ -298,7 +314,7 @@ class Tacotron2:
                 item = q.get()
                 if item is DONE:
                     break
-                inp, text, part, exc = item
+                inp, text, part, exc, ids = item
                 if exc is not None:
                     raise exc
                 if part is None:                                      # cache hit
@@ -307,7 +323,7 @@ class Tacotron2:
                     yield inp, predicted[text]
                 else:
                     yield inp, self._vocode_and_finish(part, callbacks=callbacks, predicted=predicted,
-                                                       return_output=return_output, **voc_kw)
+                                                       return_output=return_output, **ids, **voc_kw)
         finally:
             while th.is_alive():                                      # drain so that the producer can finish
                 try:
@@ -319,13 +335,15 @@ class Tacotron2:
     def _infer_backlog(self, inputs, k, *, predicted, callbacks, return_output, overwrite=False, embeddings=None,
                        max_length=10., max_text_length=-1, max_trial=5, min_fpt_ratio=2., max_fpt_ratio=10., vocoder=None,
                        silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, pack_vocoder=False,
-                       **kwargs):
+                       sentence_streams=False, **kwargs):
         """`predict(batch_backlog=k)`: yields (input, result) in input order.  Per group of waiting inputs (`_backlog_groups`):
         the parts of all its texts are the rows of 0-padded token batches of at most k rows, one `compiled_infer` call each;
         every row keeps the frame cap, the frame / token ratio test and the retries it would have had alone (rows that fail
         are decoded again together); ONE vocoder call per group with `lengths` = the rows' frame counts, so every waveform is
         that of its own frames (`pack_vocoder`: that call also gets `packed=True`); then each text is finished (`_finish`) in
-        input order."""
+        input order.  `sentence_streams`: inputs are numbered as the groups take them from the source; the row of part p of
+        utterance n decodes with the id (n, p, trial) -- a retried row keeps its id and advances only its own trial -- and is
+        vocoded with (n, p), exactly as the sequential path does."""
         one = dict(predicted=predicted, callbacks=callbacks, return_output=return_output, overwrite=overwrite,
                    embeddings=embeddings, max_length=max_length, max_text_length=max_text_length, max_trial=max_trial,
                    min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, vocoder=vocoder, silence_time=silence_time,
@@ -333,37 +351,43 @@ class Tacotron2:
         finish = dict(callbacks=callbacks, predicted=predicted, return_output=return_output, vocoder=vocoder,
                       silence_time=silence_time, reduce_noise=reduce_noise, trim_silence=trim_silence)
         is_cached = lambda text: bool(predicted) and not overwrite and text in predicted
+        taken = 0
         for group in _backlog_groups(inputs, k, is_cached):
+            number = {text: taken + j for j, (_, text) in enumerate(group)}        # (a group never holds a text twice)
+            taken += len(group)
+            utt = lambda text: {'utterance': number[text]} if sentence_streams else {}
             fresh = [(inp, text) for inp, text in group if not is_cached(text)]
             if len(fresh) <= 1:                                   # no backlog: the sequential path, cache replays included
-                for inp, _ in group:
-                    yield inp, Tacotron2.infer(self, inp, **one)
+                for inp, text in group:
+                    yield inp, Tacotron2.infer(self, inp, **utt(text), **one)
                 continue
             t0 = time.time()
             parts = [self._prepare_text(text, max_text_length, **kwargs) for _, text in fresh]
-            rows = [(ti, enc) for ti, part in enumerate(parts) for enc in part.pop('encoded')]
+            rows = [(ti, enc, p) for ti, part in enumerate(parts) for p, enc in enumerate(part.pop('encoded'))]
+            row_ids = [(number[fresh[ti][1]], p) for ti, _, p in rows] if sentence_streams else None
             decoded = [None] * len(rows)
             for r0 in range(0, len(rows), k):
                 chunk = list(range(r0, min(r0 + k, len(rows))))
                 self._decode_rows(rows, chunk, decoded, embeddings=embeddings, max_length=max_length, max_trial=max_trial,
-                                  min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, **kwargs)
+                                  min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, row_ids=row_ids, **kwargs)
             synth_time = time.time() - t0
-            for (ti, _), (mel, attn) in zip(rows, decoded):
+            for (ti, _, _), (mel, attn) in zip(rows, decoded):
                 parts[ti]['mel'].append(mel)
                 parts[ti]['attention'].append(attn)
             audios, vocoder_time = [None] * len(parts), 0.
             if vocoder is not None:
                 t1 = time.time()
                 audios = [[] for _ in parts]
-                voiced = [(ti, _to_numpy(mel)) for (ti, _), (mel, _) in zip(rows, decoded) if mel.shape[0] > 0]
+                voiced = [(ti, _to_numpy(mel), r) for r, ((ti, _, _), (mel, _)) in enumerate(zip(rows, decoded)) if mel.shape[0] > 0]
                 if voiced:
-                    n_frames = np.asarray([m.shape[0] for _, m in voiced], np.int32)
+                    n_frames = np.asarray([m.shape[0] for _, m, _ in voiced], np.int32)
                     batch = np.zeros((len(voiced), int(n_frames.max()), voiced[0][1].shape[1]), np.float32)
-                    for r, (_, m) in enumerate(voiced):
+                    for r, (_, m, _) in enumerate(voiced):
                         batch[r, :m.shape[0]] = m
                     packed = {'packed': True} if pack_vocoder else {}
-                    audio = _to_numpy(vocoder(batch, lengths=n_frames, **packed, **{**kwargs, **vocoder_config}))
-                    for r, (ti, m) in enumerate(voiced):
+                    ids = {'streams': [row_ids[i] for _, _, i in voiced]} if sentence_streams else {}
+                    audio = _to_numpy(vocoder(batch, lengths=n_frames, **packed, **ids, **{**kwargs, **vocoder_config}))
+                    for r, (ti, m, _) in enumerate(voiced):
                         audios[ti].append(audio[r, :m.shape[0] * 256].copy())
                 vocoder_time = time.time() - t1
             done = {}
@@ -375,7 +399,7 @@ class Tacotron2:
                     part, aud = done[text]
                     yield inp, self._finish(part, aud, vocoder_time / len(fresh), **finish)
                 else:
-                    yield inp, Tacotron2.infer(self, inp, **one)
+                    yield inp, Tacotron2.infer(self, inp, **utt(text), **one)
 
     def _prepare_text(self, text, max_text_length, **kwargs):
         """The host half of `_synthesize` before the decoder: split / clean / encode -> a result-dict stub with `encoded`."""
@@ -395,12 +419,15 @@ class Tacotron2:
         encoded = [np.asarray(enc) for enc in encoded if len(enc) > 0]
         return {'text': text, 'cleaned': cleaned, 'splitted': splitted, 'mel': [], 'attention': [], 'encoded': encoded}
 
-    def _decode_rows(self, rows, chunk, decoded, *, embeddings, max_length, max_trial, min_fpt_ratio, max_fpt_ratio, **kwargs):
+    def _decode_rows(self, rows, chunk, decoded, *, embeddings, max_length, max_trial, min_fpt_ratio, max_fpt_ratio,
+                     row_ids=None, **kwargs):
         """Decodes rows[i] for i in `chunk` as one token batch; decoded[i] = (mel [n_i, 80], attention [n_i, Tin]).  Row i
         ends at min(its length, the cap int(float32(tokens_i) * float32(max_length)) it would have had alone): the runtime
         sizes the loop by the longest row (and the mel of a row cut that way gets the postnet of its own frames, on a HIP
         engine).  Rows outside the frame / token window are decoded again together, up to
-        `max_trial` times in all, and keep their last result, as a sentence alone does."""
+        `max_trial` times in all, and keep their last result, as a sentence alone does.  `row_ids` [(utterance, part)] per row:
+        every call passes `streams=[(utterance, part, trial), ...]` for its rows; a row is in the call of trial t only after
+        failing t times itself, so its own trial advances and the rows that passed are not drawn for again."""
         pending = list(chunk)
         for trial in range(max_trial):
             n_tok = [len(rows[i][1]) for i in pending]
@@ -408,7 +435,8 @@ class Tacotron2:
             for r, i in enumerate(pending):
                 tok[r, :n_tok[r]] = rows[i][1]
             inputs = tok if embeddings is None else (tok, np.repeat(np.asarray(embeddings)[None], len(pending), axis=0))
-            outputs = self.compiled_infer(inputs, max_length=max_length, **kwargs)
+            ids = {} if row_ids is None else {'streams': [(*row_ids[i], trial) for i in pending]}
+            outputs = self.compiled_infer(inputs, max_length=max_length, **ids, **kwargs)
             lengths = _to_numpy(outputs.lengths)
             frames = [int(n) for n in lengths]
             if isinstance(max_length, float):
@@ -449,7 +477,8 @@ class Tacotron2:
         results leave through the callbacks (tacotron2.py:363-367, base_model.py:713)."""
         self.precompile_for_stream(vocoder=vocoder, **{k: v for k, v in kwargs.items()
                                                        if k not in self._callback_kwargs + ('callbacks', 'predicted', 'overlap',
-                                                                                            'batch_backlog', 'pack_vocoder')})
+                                                                                            'batch_backlog', 'pack_vocoder',
+                                                                                            'sentence_streams')})
         kwargs.setdefault('return_output', False)
         kwargs.setdefault('return_results', False)
         # batch_backlog looks at what the queue holds right now, so `predict` gets the queue itself
