@@ -14,7 +14,8 @@
 // columns of ALL SIX products (a wave: 32 x 64 x 6 = 192 accumulator registers).  Its K loop walks the 512 tap columns chunk by
 // chunk: the six INPUT tiles of a chunk arrive by LDS-DMA with per-lane row addresses (phase carries, frame groups, zeros
 // outside an utterance through out-of-range offsets), a product's A fragment is three or four input fragments combined in
-// registers under the other half step's MFMAs, and the epilogue applies the output transform, conditioning plane and gate in registers:
+// registers under the other half step's MFMAs, and the epilogue applies the output transform, conditioning plane (staged through the
+// released LDS by DMA, one tile in flight behind the one being gated) and gate in registers:
 // no U planes, no P planes, no pre-pass or combine launch.  Measured at config 2 on one box: three passes (round 3) 433 ms
 // per step, fused GEMM behind the pre-pass 415, this 401 (direct form 565); the kernel runs the 456 GFLOP a layer executes in
 // 3.62 ms (80 % of the fp32 MFMA peak INCLUDING both transforms and the gate; the per-product GEMM of round 3 alone ran at
@@ -499,7 +500,8 @@ __global__ void wino4_combine_kernel(const float* __restrict__ P, const float* _
     }
 }
 
-// Epilogue of the fused kernels: output transform + conditioning plane + gate in registers (the arithmetic of
+// Epilogue of wino4_fused_kernel (form 3; the default kernel's is wino_gate_store_dma below, same arithmetic): output transform
+// + conditioning plane + gate in registers (the arithmetic of
 // wino4_combine_kernel, written identically), each gated 32 x 32 tile transposed through a wave-private LDS patch (32 x 36
 // floats) so that a lane stores 16 bytes of one acts row.  A wave holds group rows gl0 .. gl0 + 31 of (group) phase block ph and
 // pre-activation columns col0 .. col0 + 63 (tanh half | sigmoid half); lane (li, lh) of an accumulator holds column li of the
@@ -566,6 +568,119 @@ __device__ __forceinline__ void wino_gate_store(const f32x16 (&acc)[6][2], float
             if (jstep < srow >> 20) *reinterpret_cast<f32x4*>(acts + (jb + (srow & 0xfffffu)) * C + ch0) = v;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // patch reads done before the next output overwrites it
+    });
+}
+
+// The same epilogue for wino4_fused2_kernel, with the conditioning tile staged through LDS by DMA instead of fetched into
+// registers (128 four-byte loads per wave in five dependent rounds, each an exposed round trip at two waves per SIMD).  After the
+// K loop the pipeline's LDS is dead; a wave owns 16 KB of it: two slots of one output's tile, 32 rows x 64 columns (256 B:
+// tanh half | sigmoid half).  One DMA instruction fetches four rows -- lane l: 16-byte piece l & 15 of row 4 k + (l >> 4), the
+// row's plane row in the per-lane offset (group_out_pack), a missing output out of range: its rows land as zeros, the value the
+// register path read -- so an output is 8 instructions.  Outputs 0 and 1 are requested at once and output j + 2 when slot j & 1
+// is consumed: one tile is always in flight behind the one being gated.  The gated value overwrites its own (consumed) tanh
+// element, and the rows are read back 16 bytes per lane for the store: no separate transpose patch.  Rows with bit 1 set keep
+// their halves swapped (through the source piece, wino_stage_piece), which spreads the four rows of a ds_read_b128 lane group
+// over all 64 banks; the 4-byte accesses are 32 consecutive floats per half wave either way.
+// Ordering is by count alone (wave-private slots: no barrier).  Every request and every store below is issued unconditionally
+// (stores of missing rows go out of range), so the wave's queue is  t0 t1 | t2 s0 | t3 s1 | s2 | s3  (t = 8 requests, s = 4
+// stores) and the wait for tile j allows the younger ones to stay outstanding.  The compiler's spill stores and reloads
+// (14 registers of outputs 1 and 3, scratch) count on vmcnt too: they only add entries ahead of a wait or drain the queue early,
+// which makes a wait stricter, never weaker -- safe, at the price of some of the overlap in outputs 2 and 3.
+__host__ __device__ constexpr int wino_stage_row(int k, int lane) { return 4 * k + (lane >> 4); }                 // tile row of request k
+__host__ __device__ constexpr int wino_stage_piece(int lane) { return (lane & 15) ^ (((lane >> 5) & 1) << 3); }   // its source piece
+// float offset inside a slot of tile element (row, col) [col < 32: tanh half, else sigmoid half]
+__host__ __device__ constexpr int wino_stage_at(int row, int col) { return row * 64 + (col ^ (((row >> 1) & 1) << 5)); }
+
+__device__ __forceinline__ void wino_gate_store_dma(const f32x16 (&acc)[6][2], float* stage, const float* __restrict__ cond,
+                                                    float* __restrict__ acts, int kind, int d, int ph, int gl0, int col0, int PR,
+                                                    int BT, int T, int lane) {
+    typedef __attribute__((address_space(3))) void* lds_ptr_t;
+    constexpr int TILE = 32 * 64;                                           // floats per slot
+    const int li = lane & 31, lh = lane >> 5, er = lane >> 3, ec4 = (lane & 7) * 4;
+    const int sfr = d / NPH;
+    unsigned drow[8], srow[4];                                              // output rows of the rows this lane requests / stores
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        drow[k] = group_out_pack(kind, gl0 + wino_stage_row(k, lane), sfr, BT, T);
+        __builtin_amdgcn_sched_barrier(0);                                  // (one division's temporaries at a time: register budget)
+    }
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+        srow[qq] = group_out_pack(kind, gl0 + er + 8 * qq, sfr, BT, T);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const unsigned dcol = (unsigned)wino_stage_piece(lane) * 16u;
+    auto request = [&](auto jc) {                                           // the tile of output J -> slot J & 1
+        constexpr int J = decltype(jc)::value;
+        unsigned jstep;
+        const long long jb = group_out_base(kind, ph, J, d, PR, jstep);
+        // plane row jb (block-uniform) goes into the descriptor, the lane's row and piece into a 32-bit offset
+        const __amdgpu_buffer_rsrc_t rc = make_rsrc_uniform(cond + jb * (2 * C) + col0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const unsigned pk = drow[k];
+            const unsigned voff = jstep < pk >> 20 ? (pk & 0xfffffu) * (2 * C * 4) + dcol : OOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rc, (lds_ptr_t)(stage + (J & 1) * TILE + k * 256), 16, voff, 0, 0, 0);
+        }
+    };
+    request(std::integral_constant<int, 0>{});
+    request(std::integral_constant<int, 1>{});
+    static_for<4>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        unsigned jstep;
+        const long long jb = group_out_base(kind, ph, j, d, PR, jstep);
+        float* const mine = stage + (j & 1) * TILE + lh * (4 * 64) + li;    // element (row 4 lh, column li) of the slot
+        // all but the younger requests and stores: tile j has landed
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(j == 0 ? 8 : j == 1 ? 12 : j == 2 ? 16 : 8) : "memory");
+        // (output 0, with all six accumulator sets still live, in two rounds: register budget)
+        constexpr int RB = j == 0 ? 8 : 16;
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += RB) {
+            float ctv[RB], csv[RB];
+#pragma unroll
+            for (int rr = 0; rr < RB; ++rr) {
+                const int r = r0 + rr, row = (r & 3) + 8 * (r >> 2);        // (+ 4 lh: bit 1 of the row is bit 1 of r)
+                ctv[rr] = mine[wino_stage_at(row, 0)];
+                csv[rr] = mine[wino_stage_at(row, 32)];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int rr = 0; rr < RB; ++rr) {
+                const int r = r0 + rr;
+                const float ct = ctv[rr], cs = csv[rr];
+                float tv, sv;
+                if constexpr (j == 0) {
+                    tv = acc[0][0][r] + acc[1][0][r] + acc[2][0][r] + acc[3][0][r] + acc[4][0][r] + ct;
+                    sv = acc[0][1][r] + acc[1][1][r] + acc[2][1][r] + acc[3][1][r] + acc[4][1][r] + cs;
+                } else if constexpr (j == 1) {
+                    tv = acc[1][0][r] - acc[2][0][r] + 2.f * (acc[3][0][r] - acc[4][0][r]) + ct;
+                    sv = acc[1][1][r] - acc[2][1][r] + 2.f * (acc[3][1][r] - acc[4][1][r]) + cs;
+                } else if constexpr (j == 2) {
+                    tv = acc[1][0][r] + acc[2][0][r] + 4.f * (acc[3][0][r] + acc[4][0][r]) + ct;
+                    sv = acc[1][1][r] + acc[2][1][r] + 4.f * (acc[3][1][r] + acc[4][1][r]) + cs;
+                } else {
+                    tv = acc[1][0][r] - acc[2][0][r] + 8.f * (acc[3][0][r] - acc[4][0][r]) + acc[5][0][r] + ct;
+                    sv = acc[1][1][r] - acc[2][1][r] + 8.f * (acc[3][1][r] - acc[4][1][r]) + acc[5][1][r] + cs;
+                }
+                mine[wino_stage_at((r & 3) + 8 * (r >> 2), 0)] = gate_tanh_sigmoid(tv, sv);     // in place of its tanh element
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // wave-private slot: no barrier needed
+        f32x4 v[4];
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq)
+            v[qq] = *reinterpret_cast<const f32x4*>(stage + (j & 1) * TILE + (er + 8 * qq) * 64 + (((er >> 1) & 1) << 5) + ec4);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // the slot is consumed: the next tile may land in it
+        if constexpr (j + 2 < 4) request(std::integral_constant<int, j + 2>{});
+        // (32-bit offset: row * 2 KB stays below the descriptor's 2^31 bytes because waveglow.hip refuses a call whose
+        //  phase-major rows x C x 4 bytes reach 2^31)
+        const __amdgpu_buffer_rsrc_t ra = make_rsrc_uniform(acts + jb * C + (col0 >> 6) * 32);
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {
+            const unsigned pk = srow[qq];
+            const unsigned voff = jstep < pk >> 20 ? (pk & 0xfffffu) * (C * 4) + (unsigned)ec4 * 4u : OOB;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v[qq]), ra, voff, 0, 0);
+        }
     });
 }
 
@@ -749,6 +864,18 @@ struct WinoFused2Args {
     int Mq, phase_rows, kind, d, PR, BT, T;
 };
 
+// Phase measurement for scripts/wino_stamps.py: only in a build made with -DTTS_WINO_STAMPS (csrc/build.sh never passes it).
+// Every block leaves its clock at entry, at the end of its K loop and at its end, and where it ran; the last launch stays.
+#ifdef TTS_WINO_STAMPS
+__device__ unsigned long long g_wino_stamps[4 * 8192];
+#define WINO_STAMP(i)                                                                               \
+    do {                                                                                            \
+        if (tid == 0 && bid < 8192) g_wino_stamps[4 * bid + (i)] = __builtin_amdgcn_s_memtime();    \
+    } while (0)
+#else
+#define WINO_STAMP(i) do { } while (0)
+#endif
+
 __global__ __launch_bounds__(256, 2) void wino4_fused2_kernel(const WinoFused2Args g) {
     constexpr int BM = 64, BN = 128, NBUF = 3, NG = C / 16;                 // NG = 32 chunks of the tap part
     constexpr int XT = BM * 16, XS = 6 * XT, BS = BN * 16;                  // floats: one input tile, one stage of six, one weight tile
@@ -768,6 +895,12 @@ __global__ __launch_bounds__(256, 2) void wino4_fused2_kernel(const WinoFused2Ar
     if (mt >= numMt) return;
     const int m0 = mt * BM, n0 = nt * BN;
     const int ph = m0 / g.phase_rows, fr0 = m0 - ph * g.phase_rows;
+#ifdef TTS_WINO_STAMPS
+    if (tid == 0 && bid < 8192)                                             // HW_ID | XCC_ID << 32
+        g_wino_stamps[4 * bid + 3] = (unsigned long long)__builtin_amdgcn_s_getreg(31 << 11 | 4) |
+                                     (unsigned long long)__builtin_amdgcn_s_getreg(31 << 11 | 20) << 32;
+#endif
+    WINO_STAMP(0);
 
     f32x16 acc[6][2];
 #pragma unroll
@@ -938,9 +1071,12 @@ __global__ __launch_bounds__(256, 2) void wino4_fused2_kernel(const WinoFused2Ar
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+    WINO_STAMP(1);
 
-    // ---- epilogue (as wino4_fused_kernel)
-    wino_gate_store(acc, smem + wave * (32 * 36), g.cond, g.acts, g.kind, g.d, ph, fr0 + wr * 32, n0 + wc * 64, g.PR, g.BT, g.T, lane);
+    // ---- epilogue: every wave owns 16 KB of the released pipeline buffers (64 KB of the block's 72)
+    wino_gate_store_dma(acc, smem + wave * (2 * 32 * 64), g.cond, g.acts, g.kind, g.d, ph, fr0 + wr * 32, n0 + wc * 64, g.PR, g.BT, g.T,
+                        lane);
+    WINO_STAMP(2);
 }
 
 hipError_t launch_wino_fused2(const WinoFused2Args& a, hipStream_t st) {
@@ -953,6 +1089,16 @@ hipError_t launch_wino_fused2(const WinoFused2Args& a, hipStream_t st) {
     hipLaunchKernelGGL(wino4_fused2_kernel, dim3(numMt8 * (2 * C / BN)), dim3(256), lds, st, a);
     return hipGetLastError();
 }
+
+#ifdef TTS_WINO_STAMPS
+}  // namespace
+// the stamps of the last wino4_fused2_kernel launch: n records of {entry, K loop end, end, HW_ID | XCC_ID << 32}
+extern "C" __attribute__((visibility("default"))) int tts_hip_debug_wino_stamps(unsigned long long* out, int n) {
+    if (n < 0 || n > 8192 || hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wino_stamps), (size_t)n * 4 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
+}
+namespace {
+#endif
 
 inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 }  // namespace
