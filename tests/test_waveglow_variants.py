@@ -30,8 +30,9 @@ def _reached():
 # ---- coverage ----------------------------------------------------------------------------------------------------------
 def test_cases_reach_every_wn_gemm_wrapper_and_instantiation():
     """Every `gemm_wn_*` wrapper of gemm_f32.h (both values of a bool argument that picks the instantiation: split fp16's
-    `small`, fp16's `t128`) is reached by some case, and every call site in waveglow.hip / wn_wino.hip names one of them:
-    a new wrapper or call site fails here until the table covers it."""
+    `small`, fp16's `t128`) is reached by some case, and every `gemm_wn_*` name in waveglow.hip (the `kWnKernels` table, where
+    a bool is bound as `bound<wrapper, value>`) / wn_wino.hip (call sites) is one of them: a new wrapper, table entry or call
+    site fails here until the case table covers it."""
     wrappers = re.findall(r'inline hipError_t (gemm_wn_\w+)\(const GemmArgs& \w+, (?:bool (\w+), )?(?:int \w+, )?hipStream_t',
                           _src('gemm_f32.h'))
     assert len(wrappers) >= 20, wrappers
@@ -42,9 +43,17 @@ def test_cases_reach_every_wn_gemm_wrapper_and_instantiation():
     assert expected <= got, sorted(expected - got)
     names = {n for n, _ in wrappers}
     for src in ('waveglow.hip', 'wn_wino.hip'):
-        called = set(re.findall(r'\b(gemm_wn_\w+)\(', _src(src)))
-        assert called and called <= names, sorted(called - names)
-        assert called <= {k.split('(')[0] for k in got}, sorted(called - {k.split('(')[0] for k in got})
+        named = set(re.findall(r'\b(gemm_wn_\w+)\b', _src(src)))
+        assert named and named <= names, sorted(named - names)
+        assert named <= {k.split('(')[0] for k in got}, sorted(named - {k.split('(')[0] for k in got})
+    # the table binds both values of every bool, and names a wrapper with a bool in no other way
+    flags = dict(wrappers)
+    table = _src('waveglow.hip')
+    bound = {(n, v) for n, v in re.findall(r'\bbound<(gemm_wn_\w+), (true|false)>', table)}
+    assert bound == {(n, v) for n in names if flags[n] for v in ('true', 'false')}, sorted(bound)
+    assert not [n for n in re.findall(r'(?<!bound<)\b(gemm_wn_\w+)\b', table) if flags[n]]
+    # every wrapper without a bool that the direct form launches is in the table (gemm_wn_wino*: wn_wino.hip's call sites)
+    assert {n for n in names if not flags[n] and not n.startswith('gemm_wn_wino')} <= set(re.findall(r'\b(gemm_wn_\w+)\b', table))
 
 
 def test_cases_reach_every_winograd_kernel_kind_and_end_fold_instantiation():
@@ -57,7 +66,14 @@ def test_cases_reach_every_winograd_kernel_kind_and_end_fold_instantiation():
         assert {f'{kernel}/{g}' for g in wc.WINO_KINDS} <= got, kernel
     assert {'gemm_wn_wino/phases', 'gemm_wn_wino_128/phases', 'gemm_wn_wino_128/mixed', 'gemm_wn_wino_128/frames',
             'combine'} <= got
-    folds = set(re.findall(r'\((wn_end_fold_kernel<\w+, \w+>)\)', _src('waveglow.hip')))
+    # launch_end_fold: one dispatch over <HALF, SPLIT, MASK>, launched through end_fold<..> and nowhere else
+    src = _src('waveglow.hip')
+    assert len(re.findall(r'hipLaunchKernelGGL\(\(wn_end_fold_kernel<', src)) == 1
+    assert 'hipLaunchKernelGGL((wn_end_fold_kernel<HALF, SPLIT, MASK>)' in src
+    combos = set(re.findall(r'\bend_fold<(true|false), (true|false), (MASK_\w+)>\(', src))
+    assert combos == {(h, s, m) for h, s in (('false', 'false'), ('true', 'false'), ('true', 'true'))
+                      for m in ('MASK_NONE', 'MASK_LENS', 'MASK_FLAGS')}, sorted(combos)
+    folds = {f'wn_end_fold_kernel<{h}, {s}>' for h, s, _ in combos}
     assert len(folds) == 3 and folds <= got, sorted(folds - got)
 
 

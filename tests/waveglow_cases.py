@@ -1,9 +1,11 @@
 """Shared case table of the WaveGlow-variant tests (tests/test_waveglow_variants.py on the CPU, _gpu.py on an MI355X).
 
-`waveglow_run` (csrc/waveglow.hip) picks its WN-layer GEMMs from the frame count B*T, the precision and the form: four
+`waveglow_run` (csrc/waveglow.hip) picks its WN-layer GEMMs from the frame count B*T, the precision and the form (`wg_plan`,
+csrc/wg_plan.h, then the `kWnKernels` table of `WnKernels`): four
 fp32 tile families of the direct form, the Winograd form of layers 1 - 7 (csrc/wn_wino.hip) with its three group kinds and
 two measurement forms, the fp16 and the split-fp16 (f16x3) kernels.  `pick_variant` restates those rules, so a test can
-say which instantiation a call must take and check that the case table reaches every one of them.
+say which instantiation a call must take and check that the case table reaches every one of them; tests/test_wg_plan.py
+compares the restatement with `wg_plan` itself on the CPU.
 
 References come from the numpy oracle in float64, once per case (`flow11_acts`): the gated activations of the 8 WN layers
 of flow 11, the first flow that runs, whose input is exactly sigma * z.
@@ -42,7 +44,7 @@ STATE_END_SCALE = 0.2
 
 PRECISIONS = ('f32', 'f16', 'f16x3')
 FORMS = {'direct': 0, 'winograd': 1, 'winograd-3pass': 2, 'winograd-prepass': 3}    # tts_hip_set_waveglow_form
-WINO_MIN_FRAMES = 144        # waveglow.hip:779 TTS_WINO_MIN_FRAMES
+WINO_MIN_FRAMES = 144        # wg_plan.h TTS_WINO_MIN_FRAMES
 NPH = 32                     # sample groups (positions) per mel frame
 N_LAYERS = 8
 
@@ -61,21 +63,21 @@ def _up(n, m):
 
 
 def frame_groups_per_utt(T):
-    return (T + 15) // 16 * 4                                   # wn_wino.hip:97
+    return (T + 15) // 16 * 4                                   # wn_wino.hip frame_groups_per_utt
 
 
 def mixed_groups_per_utt(T):
-    return (T + 1) // 2                                         # wn_wino.hip:107
+    return (T + 1) // 2                                         # wn_wino.hip mixed_groups_per_utt
 
 
 def group_rows(B, T, form):
-    # wn_wino.hip:996-1003 group_row_tile, frame_group_rows, mixed_group_rows: padded to 64 rows (fused kernels) or 128
+    # wn_wino.hip group_row_tile, frame_group_rows, mixed_group_rows: padded to 64 rows (fused kernels) or 128
     # (form 2's GEMM)
     g = 128 if form == 2 else 64
     return _up(B * frame_groups_per_utt(T), g), _up(B * mixed_groups_per_utt(T), g)
 
 
-WINO_KINDS = ('phases', 'mixed', 'frames')      # layers 1 - 3 (d <= 8), 4 (d = 16), 5 - 7 (d >= 32); wn_wino.hip:1115
+WINO_KINDS = ('phases', 'mixed', 'frames')      # layers 1 - 3 (d <= 8), 4 (d = 16), 5 - 7 (d >= 32); waveglow_wino_layer
 
 
 def pick_variant(B, T, precision, form='winograd') -> Variant:
@@ -83,7 +85,7 @@ def pick_variant(B, T, precision, form='winograd') -> Variant:
     BT = B * T
     half, x3 = precision == 'f16', precision == 'f16x3'
     fm = FORMS[form]
-    # waveglow.hip:767-772: 128-row tiles when they save 5 % of the rows; 64-row tiles for short calls (fp16: from -25 %
+    # wg_plan: 128-row tiles when they save 5 % of the rows; 64-row tiles for short calls (fp16: from -25 %
     # rows; split fp16: 64 x 128 vs 256 x 256, from pr64 * 1.25 < pr256)
     pr256, pr128, pr64 = _up(BT, 256), _up(BT, 128), _up(BT, 64)
     tile128 = pr128 * 1.05 < pr256
@@ -92,37 +94,37 @@ def pick_variant(B, T, precision, form='winograd') -> Variant:
         row64 = pr64 * 1.25 < pr256
     else:
         row64 = BT <= 512 and (pr64 * 4 <= pr_big * 3 if half else pr64 < pr_big)
-    # :779-786 Winograd from 144 fp32 frames; form 2 needs 128-row phase blocks and leaves the 64-row tiles when that pays
+    # wg_plan: Winograd from 144 fp32 frames; form 2 needs 128-row phase blocks and leaves the 64-row tiles when that pays
     wino_size = precision == 'f32' and fm >= 1 and BT >= WINO_MIN_FRAMES
     if wino_size and fm == 2 and row64 and pr128 * 1120.0 * 1.35 < pr64 * 1856.0:
         row64 = False
-    PR = pr64 if row64 else pr128 if tile128 and not x3 else pr256         # :787
-    tile64 = not row64 and tile128 and (NPH * PR // 128) * 8 < 768         # :791
-    wino = wino_size and (not row64 or fm != 2)                            # :807
-    tiles = '64-row' if row64 else '256-row' if x3 else '128x64' if tile64 else '128-row' if tile128 else '256-row'  # :829
-    if x3:                                                                 # :963, :997
+    PR = pr64 if row64 else pr128 if tile128 and not x3 else pr256         # wg_plan: PR
+    tile64 = not row64 and tile128 and (NPH * PR // 128) * 8 < 768         # wg_plan: tile64
+    wino = wino_size and (not row64 or fm != 2)                            # wg_plan: wino_wanted
+    tiles = '64-row' if row64 else '256-row' if x3 else '128x64' if tile64 else '128-row' if tile128 else '256-row'  # tiles
+    if x3:                                                                 # kWnKernels, split fp16 rows
         k = {f'gemm_wn_in0_x3(small={row64})', f'gemm_wn_in_x3(small={row64})', f'gemm_wn_res_x3(small={row64})'}
-    elif half:                                                             # :964-966, :998
+    elif half:                                                             # kWnKernels, fp16 rows
         if row64:
             k = {'gemm_wn_in0_r64h', 'gemm_wn_in_r64h', 'gemm_wn_res_r64h'}
         elif tile64:
             k = {'gemm_wn_in0_64h', 'gemm_wn_in_64h', 'gemm_wn_res_64h'}
         else:
             k = {f'gemm_wn_in0_h(t128={tile128})', f'gemm_wn_in_h(t128={tile128})', 'gemm_wn_res_h'}
-    else:                                                                  # :896-897, :925
+    else:                                                                  # kWnKernels, fp32 rows
         suf = '_r64' if row64 else '_64' if tile64 else '_128' if tile128 else ''
         k = {'gemm_wn_in0' + suf, 'gemm_wn_res' + (suf if row64 or tile64 else '_skip')}
         if not wino:
             k.add('gemm_wn_in' + suf)
-    k.add('wn_end_fold_kernel<%s>' % ('true, true' if x3 else 'true, false' if half else 'false, false'))   # :1008-1016
+    k.add('wn_end_fold_kernel<%s>' % ('true, true' if x3 else 'true, false' if half else 'false, false'))   # launch_end_fold
     groups = None
     if wino:
         groups = group_rows(B, T, fm)
-        if fm == 1:                                                        # wn_wino.hip:1179
+        if fm == 1:                                                        # waveglow_wino_layer: the fused kernel
             k |= {f'fused2/{g}' for g in WINO_KINDS}
-        elif fm == 3:                                                      # :1186 (behind the pre-pass)
+        elif fm == 3:                                                      # ... the same behind the pre-pass
             k |= {f'fused_prepass/{g}' for g in WINO_KINDS}
-        else:                                                              # :1217, :1233, :1245, then the combine pass :1248
+        else:                                                              # ... three GEMMs, then the combine pass
             k |= {'gemm_wn_wino/phases' if PR % 256 == 0 else 'gemm_wn_wino_128/phases', 'gemm_wn_wino_128/mixed',
                   'gemm_wn_wino_128/frames', 'combine'}
     return Variant(tiles, wino, PR, frozenset(k), groups)

@@ -40,12 +40,11 @@ struct WgLayerDev {
     float* in_Bt = nullptr;     // [1024 (tanh/sigmoid interleaved per 128-tile)][3*512 taps] (first layer of a flow: [3*16])
     float* cond_Bt = nullptr;   // [32 phases][1024][320] conditioning conv folded with the upsampling kernel
     float* in_bias = nullptr;   // [1024] in_conv bias + cond bias (+ upsampling bias pushed through), same row order
-    _Float16* in_Bt16 = nullptr;    // fp16 operands of the optional fp16 path (built on first use): [1024][1536] (taps in
-    _Float16* cond_Bt16 = nullptr;  //   chunks of 32), [32][1024][4*96], [512][512]
-    _Float16* rs_Bt16 = nullptr;
-    _Float16* in_Bt_x3 = nullptr;   // split-fp16 mode: the same three matrices as [2 planes][...] (hi, lo), built on first use
-    _Float16* cond_Bt_x3 = nullptr;
-    _Float16* rs_Bt_x3 = nullptr;
+    // fp16 operands, built on first use of a mode: [0] the fp16 path, [1] split fp16, the same three matrices as
+    // [2 planes][...] (hi, lo)
+    _Float16* in_Bt16[2] = {nullptr, nullptr};      // [1024][1536] (taps in chunks of 32)
+    _Float16* cond_Bt16[2] = {nullptr, nullptr};    // [32][1024][4*96]
+    _Float16* rs_Bt16[2] = {nullptr, nullptr};      // [512][512]
     float* wino_G = nullptr;    // Winograd form (wn_wino.hip; built on first use): [6][1024][512] tap combinations and the
     float* wino_W = nullptr;    //   conditioning weight planes [32][7][1024][80] (F(4, 4) along frames)
     float* rs_Bt = nullptr;     // [512][512] residual half of res_skip (layers 0..6)
@@ -65,9 +64,7 @@ struct WaveGlowDev {
     bool ready = false;
     WgFlowDev flow[12];
     std::vector<void*> allocs;
-    DevBuf x, acts, audio, a0p, io_mel, io_z, io_out, io_zgen;
     bool f16_ready = false, x3_ready = false;
-    DevBuf x16, acts16, a0p16, mel16;        // fp16 path: shadow of x, activations, first-layer operand, mel
     int form_mode = 1, last_form = -1;       // tts_hip_set_waveglow_form / tts_hip_last_waveglow_form
     int last_tiles = -1;                     // tts_hip_last_waveglow_tiles: WN GEMM tile family of the last call
     int probe_flow = -1, probe_layer = -1;   // tts_hip_waveglow_probe (test hook): stop after this layer (what 0, 2) or flow
@@ -75,12 +72,23 @@ struct WaveGlowDev {
     float* probe_out = nullptr;              //   [B][T * 32][n] or the layer's conditioning plane [B][T * 32][1024] (what 2;
                                              //   Winograd form only) to this device buffer
     bool wino_ready = false;                 // Winograd form of the fp32 in-layer GEMM (wn_wino.hip)
+    std::vector<int> ragged_info_h;          // host image of ragged_info (staged to the device once per call)
+    // ---- workspace: every DevBuf of this struct is declared here ...
+    DevBuf x, acts, audio, a0p;              // fp32 path (layouts: waveglow.hip)
+    DevBuf x16, acts16, a0p16, mel16;        // fp16 path: shadow of x, activations, first-layer operand, mel
+    DevBuf io_mel, io_z, io_out, io_zgen;    // staging for host callers; the noise of seeded calls
     DevBuf mel_ragged, ragged_info;          // ragged calls: mel copy with cleared tails; [lengths | tail frame list] int32
-    std::vector<int> ragged_info_h;          //   ... and its host image (staged to the device once per call)
     DevBuf packed_z, packed_out;             // packed calls: noise and audio of the one packed row (its mel is mel_ragged, its
                                              //   [segment table | frame flags | gap frames] goes through ragged_info)
     DevBuf wino_U, wino_P, wino_mel;         // mel planes; forms 2 / 3 only: transformed inputs [6][M/4][512], products [6][M/4][1024]
     DevBuf wino_cond;                        // conditioning plane of the current layer [32 PR][1024]
+    // ... and listed here, which is what waveglow_free releases
+    template <class F>
+    void for_each_buf(F f) {
+        for (DevBuf* b : {&x, &acts, &audio, &a0p, &x16, &acts16, &a0p16, &mel16, &io_mel, &io_z, &io_out, &io_zgen, &mel_ragged,
+                          &ragged_info, &packed_z, &packed_out, &wino_U, &wino_P, &wino_mel, &wino_cond})
+            f(*b);
+    }
 };
 
 // ---------------------------------------------------------------- Tacotron2

@@ -28,8 +28,15 @@
 // The 512 -> 512 skip GEMMs (and the whole res_skip conv of the last layer) disappear -- 9.6 % of the WN FLOPs and the
 // read-modify-write of a [M][512] skip buffer per layer -- and are replaced by one [M, 8*512] x [8*512, 2h] product per
 // flow (h <= 4), computed by the HBM-bound wn_end_fold_kernel straight from the stored activations.
+//
+// Host side, in file order: waveglow_free; the load-time algebra above as three host functions and waveglow_finalize, which
+// uploads their results; waveglow_build_half (fp16 operands of either fp16 mode, on first use); the pieces of waveglow_run --
+// the kWnKernels table (precision x tile family of wg_plan.h -> GEMM launchers), ensure_workspace, wn_call / in_layer_args /
+// res_args (one description of the operands for every precision), launch_end_fold, the probe hooks, the Winograd form's
+// out-of-memory fallback -- and waveglow_run itself: one layer loop for every precision, form and mask kind.
 #include "engine.h"
 #include "gemm_f32.h"
+#include "wg_plan.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -510,32 +517,110 @@ int pack_bt(tts_hip_engine* e, const float* d_src, int K, int src_ld, float* dst
 }  // namespace
 
 void waveglow_free(tts_hip_engine* e) {
-    for (void* p : e->wg.allocs) (void)hipFree(p);
-    e->wg.allocs.clear();
-    e->wg.x.release();
-    e->wg.acts.release();
-    e->wg.audio.release();
-    e->wg.a0p.release();
-    e->wg.x16.release();
-    e->wg.acts16.release();
-    e->wg.a0p16.release();
-    e->wg.mel16.release();
-    e->wg.wino_U.release();
-    e->wg.wino_P.release();
-    e->wg.wino_mel.release();
-    e->wg.wino_cond.release();
-    e->wg.wino_ready = false;
-    e->wg.f16_ready = false;
-    e->wg.x3_ready = false;
-    e->wg.io_mel.release();
-    e->wg.io_z.release();
-    e->wg.io_out.release();
-    e->wg.mel_ragged.release();
-    e->wg.ragged_info.release();
-    e->wg.packed_z.release();
-    e->wg.packed_out.release();
-    e->wg.ready = false;
+    WaveGlowDev& wg = e->wg;
+    for (void* p : wg.allocs) (void)hipFree(p);
+    wg.allocs.clear();
+    wg.for_each_buf([](DevBuf& b) { b.release(); });
+    wg.wino_ready = false;
+    wg.f16_ready = false;
+    wg.x3_ready = false;
+    wg.ready = false;
 }
+
+// ---- load-time algebra of waveglow_finalize: host arithmetic in double, no HIP calls
+namespace {
+
+// Start conv composed into the first layer's taps (waveglow_arch.py:108).  w_in [3 taps][512][1024], ws [h][512], bs [512]
+// -> [3 taps][16][1024] for pack_bt: rows j < h: sum_c ws[j][c] * w_in[tap][c][n]; row h: sum_c bs[c] * w_in[tap][c][n];
+// rows > h: 0.
+std::vector<float> compose_start_taps(const float* w_in, const float* ws, const float* bs, int h) {
+    std::vector<float> comp((size_t)3 * 16 * 2 * C, 0.f);
+    std::vector<double> rowacc(2 * C);
+    for (int tap = 0; tap < 3; ++tap)
+        for (int j = 0; j <= h; ++j) {
+            for (int n = 0; n < 2 * C; ++n) rowacc[n] = 0.0;
+            for (int c = 0; c < C; ++c) {
+                const double sv = j < h ? (double)ws[(size_t)j * C + c] : (double)bs[c];
+                const float* wr = w_in + ((size_t)tap * C + c) * 2 * C;
+                for (int n = 0; n < 2 * C; ++n) rowacc[n] += sv * (double)wr[n];
+            }
+            float* dst = comp.data() + ((size_t)tap * 16 + j) * 2 * C;
+            for (int n = 0; n < 2 * C; ++n) dst[n] = (float)rowacc[n];
+        }
+    return comp;
+}
+
+// Skip halves of the 8 res_skip convs folded into the `end` conv we [512][no], be [no]:
+//   wf[i][o][c] = sum_s W_skip_i[c][s] * we[s][o]  ([8][8][512], rows o >= no zero);  bf[o] = sum_i b_skip_i @ we + be[o]
+// wk[i] / bk[i]: kernel [512][rs_full] and bias [rs_full] of layer i, the skip half behind the 512 residual columns
+// (layer 7 has no residual half).
+void fold_skip_into_end(const float* const wk[8], const float* const bk[8], const float* we, const float* be, int no,
+                        std::vector<float>* wf, std::vector<float>* bf) {
+    wf->assign((size_t)8 * 8 * C, 0.f);
+    bf->assign(8, 0.f);
+    std::vector<double> bsum(be, be + no), row(no);
+    for (int i = 0; i < 8; ++i) {
+        const int rs_full = i < 7 ? 2 * C : C, soff = i < 7 ? C : 0;
+        for (int c = 0; c < C; ++c) {
+            for (int o = 0; o < no; ++o) row[o] = 0.0;
+            const float* ws = wk[i] + (size_t)c * rs_full + soff;
+            for (int sidx = 0; sidx < C; ++sidx) {
+                const double wv = ws[sidx];
+                const float* wend = we + (size_t)sidx * no;
+                for (int o = 0; o < no; ++o) row[o] += wv * (double)wend[o];
+            }
+            for (int o = 0; o < no; ++o) (*wf)[((size_t)i * 8 + o) * C + c] = (float)row[o];
+        }
+        for (int sidx = 0; sidx < C; ++sidx)
+            for (int o = 0; o < no; ++o) bsum[o] += (double)bk[i][soff + sidx] * (double)we[(size_t)sidx * no + o];
+    }
+    for (int o = 0; o < no; ++o) (*bf)[o] = (float)bsum[o];
+}
+
+// Invertible1x1Conv.build_inverse (invertible_conv.py:41-47): W = kernel[0]^T, W_inverse = inv(W)^T, and the reverse conv
+// (kernel layout [1][in][out]) computes out = audio @ W_inverse = audio @ inv(kernel[0]^T)^T.
+// kernel [n][n] -> minv[j][c] = inv(W)[c][j]; false when the kernel is singular.
+bool invert_1x1(const float* kernel, int n, std::vector<float>* minv) {
+    std::vector<double> a((size_t)n * 2 * n, 0.0);      // [W | I], W[r][c] = kernel[c][r]
+    for (int r = 0; r < n; ++r) {
+        for (int c = 0; c < n; ++c) a[(size_t)r * 2 * n + c] = (double)kernel[(size_t)c * n + r];
+        a[(size_t)r * 2 * n + n + r] = 1.0;
+    }
+    for (int col = 0; col < n; ++col) {                  // Gauss-Jordan with partial pivoting
+        int piv = col;
+        for (int r = col + 1; r < n; ++r)
+            if (std::fabs(a[(size_t)r * 2 * n + col]) > std::fabs(a[(size_t)piv * 2 * n + col])) piv = r;
+        if (std::fabs(a[(size_t)piv * 2 * n + col]) < 1e-12) return false;
+        if (piv != col)
+            for (int c = 0; c < 2 * n; ++c) std::swap(a[(size_t)piv * 2 * n + c], a[(size_t)col * 2 * n + c]);
+        const double d = a[(size_t)col * 2 * n + col];
+        for (int c = 0; c < 2 * n; ++c) a[(size_t)col * 2 * n + c] /= d;
+        for (int r = 0; r < n; ++r) {
+            if (r == col) continue;
+            const double f = a[(size_t)r * 2 * n + col];
+            if (f != 0.0)
+                for (int c = 0; c < 2 * n; ++c) a[(size_t)r * 2 * n + c] -= f * a[(size_t)col * 2 * n + c];
+        }
+    }
+    minv->resize((size_t)n * n);
+    for (int j = 0; j < n; ++j)
+        for (int c = 0; c < n; ++c) (*minv)[(size_t)j * n + c] = (float)a[(size_t)c * 2 * n + n + j];
+    return true;
+}
+
+// The staging buffers of waveglow_finalize (raw Keras-layout kernels; largest: upsample 1024*80*80 = 6.55 M floats).  However
+// finalize returns they are released, and unless it got to `keep` so is everything it has uploaded.
+struct FinalizeGuard {
+    tts_hip_engine* e;
+    DevBuf stage, stage2, ut, wct;
+    bool keep = false;
+    ~FinalizeGuard() {
+        for (DevBuf* b : {&stage, &stage2, &ut, &wct}) b->release();
+        if (!keep) waveglow_free(e);
+    }
+};
+
+}  // namespace
 
 int waveglow_finalize(tts_hip_engine* e) {
     WaveGlowDev& wg = e->wg;
@@ -549,8 +634,8 @@ int waveglow_finalize(tts_hip_engine* e) {
         return 0;
     };
     int rc;
-    // staging buffers for raw Keras-layout kernels (largest: upsample 1024*80*80 = 6.55 M floats)
-    DevBuf stage, stage2, ut, wct;
+    FinalizeGuard gd{e};
+    DevBuf &stage = gd.stage, &stage2 = gd.stage2, &ut = gd.ut, &wct = gd.wct;
     HIPCHK(e, stage.ensure((size_t)1024 * 80 * 80 * 4));
     HIPCHK(e, stage2.ensure((size_t)1024 * 4 * 2 + 1024));
     HIPCHK(e, ut.ensure((size_t)NPH * KMEL * NCOND * 4));
@@ -559,29 +644,17 @@ int waveglow_finalize(tts_hip_engine* e) {
         HIPCHK(e, hipMemcpyAsync(b.p, t->data.data(), t->numel() * 4, hipMemcpyHostToDevice, e->stream));
         return 0;
     };
-    auto done = [&]() {
-        stage.release();
-        stage2.release();
-        ut.release();
-        wct.release();
-    };
-#define WGCHK(x)          \
-    if ((rc = (x))) {     \
-        done();           \
-        waveglow_free(e); \
-        return rc;        \
-    }
     const HostTensor *t, *t2;
     // ---- transposed-conv upsampling kernel -> per-phase operand UT (only used to fold the conditioning convs below)
-    WGCHK(need("waveglow/upsample/kernel", {1024, 80, 80}, &t));
-    WGCHK(put(stage, t));
+    if ((rc = need("waveglow/upsample/kernel", {1024, 80, 80}, &t))) return rc;
+    if ((rc = put(stage, t))) return rc;
     {
         const long long total = (long long)NPH * KMEL * NCOND;
         hipLaunchKernelGGL(pack_ut_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, stage.f(),
                            ut.f());
         HIPCHK(e, hipGetLastError());
     }
-    WGCHK(need("waveglow/upsample/bias", {80}, &t));
+    if ((rc = need("waveglow/upsample/bias", {80}, &t))) return rc;
     float* d_bup = stage2.f() + 4 * C;              // 80 floats behind the bias staging area
     HIPCHK(e, hipMemcpyAsync(d_bup, t->data.data(), 80 * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -597,48 +670,33 @@ int waveglow_finalize(tts_hip_engine* e) {
         fl.n_rem = n_rem;
         fl.n_half = n_half;
         const std::string p = "waveglow/block-" + std::to_string(k);
-        WGCHK(need(p + "/start_conv/kernel", {1, n_half, C}, &t));
-        WGCHK(upload(e, t->data.data(), t->numel(), &fl.start_w, wg.allocs));
-        WGCHK(need(p + "/start_conv/bias", {C}, &t));
-        WGCHK(upload(e, t->data.data(), t->numel(), &fl.start_b, wg.allocs));
+        const HostTensor *ws, *bs;
+        if ((rc = need(p + "/start_conv/kernel", {1, n_half, C}, &ws))) return rc;
+        if ((rc = upload(e, ws->data.data(), ws->numel(), &fl.start_w, wg.allocs))) return rc;
+        if ((rc = need(p + "/start_conv/bias", {C}, &bs))) return rc;
+        if ((rc = upload(e, bs->data.data(), bs->numel(), &fl.start_b, wg.allocs))) return rc;
+        const float *skip_w[8], *skip_b[8];
         for (int i = 0; i < 8; ++i) {
             WgLayerDev& ly = fl.layer[i];
             const std::string si = std::to_string(i);
             const int kconv = i == 0 ? KCONV0 : KCONV;
-            WGCHK(dev_alloc(e, (size_t)2 * C * kconv, &ly.in_Bt, wg.allocs, false));
-            WGCHK(need(p + "/in_conv-" + si + "/kernel", {3, C, 2 * C}, &t));
+            if ((rc = dev_alloc(e, (size_t)2 * C * kconv, &ly.in_Bt, wg.allocs, false))) return rc;
+            if ((rc = need(p + "/in_conv-" + si + "/kernel", {3, C, 2 * C}, &t))) return rc;
             if (i == 0) {
-                // compose with the start conv (waveglow_arch.py:108): rows j < h: sum_c W_start[j][c] * W_in[tap][c][n];
-                // row h: sum_c b_start[c] * W_in[tap][c][n]; rows > h: 0.  Laid out [3 taps][16][1024] for pack_bt.
-                const HostTensor *ws, *bs;
-                WGCHK(need(p + "/start_conv/kernel", {1, n_half, C}, &ws));
-                WGCHK(need(p + "/start_conv/bias", {C}, &bs));
-                std::vector<float> comp((size_t)3 * 16 * 2 * C, 0.f);
-                std::vector<double> rowacc(2 * C);
-                for (int tap = 0; tap < 3; ++tap)
-                    for (int j = 0; j <= n_half; ++j) {
-                        for (int n = 0; n < 2 * C; ++n) rowacc[n] = 0.0;
-                        for (int c = 0; c < C; ++c) {
-                            const double sv = j < n_half ? (double)ws->data[(size_t)j * C + c] : (double)bs->data[c];
-                            const float* wr = t->data.data() + ((size_t)tap * C + c) * 2 * C;
-                            for (int n = 0; n < 2 * C; ++n) rowacc[n] += sv * (double)wr[n];
-                        }
-                        float* dst = comp.data() + ((size_t)tap * 16 + j) * 2 * C;
-                        for (int n = 0; n < 2 * C; ++n) dst[n] = (float)rowacc[n];
-                    }
+                const std::vector<float> comp = compose_start_taps(t->data.data(), ws->data.data(), bs->data.data(), n_half);
                 HIPCHK(e, hipMemcpyAsync(stage.p, comp.data(), comp.size() * 4, hipMemcpyHostToDevice, e->stream));
                 HIPCHK(e, hipStreamSynchronize(e->stream));
-                WGCHK(pack_bt(e, stage.f(), KCONV0, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1));   // K order tap*16 + j
+                if ((rc = pack_bt(e, stage.f(), KCONV0, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1))) return rc;   // K order tap*16 + j
             } else {
-                WGCHK(put(stage, t));
-                WGCHK(pack_bt(e, stage.f(), 3 * C, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1, WN_TAPS, TTS_WN_BK));
+                if ((rc = put(stage, t))) return rc;
+                if ((rc = pack_bt(e, stage.f(), 3 * C, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1, WN_TAPS, TTS_WN_BK))) return rc;
             }
             HIPCHK(e, hipStreamSynchronize(e->stream));
             // conditioning conv: WcT[n'][k] (gate-permuted rows), then V_{i,p} = WcT @ U_p for the 32 phases
-            WGCHK(need(p + "/cond_layer-" + si + "/kernel", {1, NCOND, 2 * C}, &t));
-            WGCHK(put(stage, t));
-            WGCHK(pack_bt(e, stage.f(), NCOND, 2 * C, wct.f(), 2 * C, NCOND, 0, 1));
-            WGCHK(dev_alloc(e, (size_t)NPH * 2 * C * KMEL, &ly.cond_Bt, wg.allocs, false));
+            if ((rc = need(p + "/cond_layer-" + si + "/kernel", {1, NCOND, 2 * C}, &t))) return rc;
+            if ((rc = put(stage, t))) return rc;
+            if ((rc = pack_bt(e, stage.f(), NCOND, 2 * C, wct.f(), 2 * C, NCOND, 0, 1))) return rc;
+            if ((rc = dev_alloc(e, (size_t)NPH * 2 * C * KMEL, &ly.cond_Bt, wg.allocs, false))) return rc;
             {
                 GemmArgs g{};
                 g.M = 2 * C;
@@ -656,9 +714,9 @@ int waveglow_finalize(tts_hip_engine* e) {
                 g.strideOutZ = (long long)2 * C * KMEL;
                 HIPCHK(e, gemm_small(g, NPH, e->stream));
             }
-            WGCHK(need(p + "/in_conv-" + si + "/bias", {2 * C}, &t));
-            WGCHK(need(p + "/cond_layer-" + si + "/bias", {2 * C}, &t2));
-            WGCHK(dev_alloc(e, 2 * C, &ly.in_bias, wg.allocs, false));
+            if ((rc = need(p + "/in_conv-" + si + "/bias", {2 * C}, &t))) return rc;
+            if ((rc = need(p + "/cond_layer-" + si + "/bias", {2 * C}, &t2))) return rc;
+            if ((rc = dev_alloc(e, 2 * C, &ly.in_bias, wg.allocs, false))) return rc;
             HIPCHK(e, hipMemcpyAsync(stage2.p, t->data.data(), 2 * C * 4, hipMemcpyHostToDevice, e->stream));
             HIPCHK(e, hipMemcpyAsync(stage2.f() + 2 * C, t2->data.data(), 2 * C * 4, hipMemcpyHostToDevice, e->stream));
             hipLaunchKernelGGL(pack_bias_kernel, dim3(4), dim3(256), 0, e->stream, stage2.f(), stage2.f() + 2 * C,
@@ -668,184 +726,325 @@ int waveglow_finalize(tts_hip_engine* e) {
             HIPCHK(e, hipStreamSynchronize(e->stream));
             // res_skip conv: keep only the residual half as a GEMM operand (layers 0..6); the skip half is folded below
             const int rs_full = i < 7 ? 2 * C : C;
-            WGCHK(need(p + "/res_skip_conv-" + si + "/kernel", {1, C, rs_full}, &t));
-            WGCHK(need(p + "/res_skip_conv-" + si + "/bias", {rs_full}, &t2));
+            if ((rc = need(p + "/res_skip_conv-" + si + "/kernel", {1, C, rs_full}, &t))) return rc;
+            if ((rc = need(p + "/res_skip_conv-" + si + "/bias", {rs_full}, &t2))) return rc;
+            skip_w[i] = t->data.data();
+            skip_b[i] = t2->data.data();
             ly.rs_n = i < 7 ? C : 0;
             if (i < 7) {
-                WGCHK(dev_alloc(e, (size_t)C * C, &ly.rs_Bt, wg.allocs, false));
-                WGCHK(put(stage, t));
-                WGCHK(pack_bt(e, stage.f(), C, rs_full, ly.rs_Bt, C, C, 0, 0));      // rows n < 512 = residual outputs
+                if ((rc = dev_alloc(e, (size_t)C * C, &ly.rs_Bt, wg.allocs, false))) return rc;
+                if ((rc = put(stage, t))) return rc;
+                if ((rc = pack_bt(e, stage.f(), C, rs_full, ly.rs_Bt, C, C, 0, 0))) return rc;      // rows n < 512 = residual outputs
                 HIPCHK(e, hipStreamSynchronize(e->stream));
-                WGCHK(upload(e, t2->data.data(), C, &ly.rs_bias, wg.allocs));
+                if ((rc = upload(e, t2->data.data(), C, &ly.rs_bias, wg.allocs))) return rc;
             }
         }
         {
-            // fold: wfold[i][o][c] = sum_s W_skip_i[c][s] * W_end[s][o];  bfold[o] = sum_i b_skip_i @ W_end + b_end
             const HostTensor *we, *be;
-            WGCHK(need(p + "/end_conv/kernel", {1, C, 2 * n_half}, &we));
-            WGCHK(need(p + "/end_conv/bias", {2 * n_half}, &be));
-            const int no = 2 * n_half;
-            std::vector<float> wf((size_t)8 * 8 * C, 0.f), bf(8, 0.f);
-            std::vector<double> bsum(no, 0.0);
-            for (int o = 0; o < no; ++o) bsum[o] = be->data[o];
-            for (int i = 0; i < 8; ++i) {
-                const HostTensor* wk = find_tensor(e, p + "/res_skip_conv-" + std::to_string(i) + "/kernel");
-                const HostTensor* bk = find_tensor(e, p + "/res_skip_conv-" + std::to_string(i) + "/bias");
-                const int rs_full = i < 7 ? 2 * C : C, soff = i < 7 ? C : 0;
-                std::vector<double> row(no);
-                for (int c = 0; c < C; ++c) {
-                    for (int o = 0; o < no; ++o) row[o] = 0.0;
-                    const float* ws = wk->data.data() + (size_t)c * rs_full + soff;
-                    for (int sidx = 0; sidx < C; ++sidx) {
-                        const double wv = ws[sidx];
-                        const float* wend = we->data.data() + (size_t)sidx * no;
-                        for (int o = 0; o < no; ++o) row[o] += wv * (double)wend[o];
-                    }
-                    for (int o = 0; o < no; ++o) wf[((size_t)i * 8 + o) * C + c] = (float)row[o];
-                }
-                for (int sidx = 0; sidx < C; ++sidx)
-                    for (int o = 0; o < no; ++o)
-                        bsum[o] += (double)bk->data[soff + sidx] * (double)we->data[(size_t)sidx * no + o];
-            }
-            for (int o = 0; o < no; ++o) bf[o] = (float)bsum[o];
-            WGCHK(upload(e, wf.data(), wf.size(), &fl.end_w, wg.allocs));
-            WGCHK(upload(e, bf.data(), bf.size(), &fl.end_b, wg.allocs));
+            if ((rc = need(p + "/end_conv/kernel", {1, C, 2 * n_half}, &we))) return rc;
+            if ((rc = need(p + "/end_conv/bias", {2 * n_half}, &be))) return rc;
+            std::vector<float> wf, bf;
+            fold_skip_into_end(skip_w, skip_b, we->data.data(), be->data.data(), 2 * n_half, &wf, &bf);
+            if ((rc = upload(e, wf.data(), wf.size(), &fl.end_w, wg.allocs))) return rc;
+            if ((rc = upload(e, bf.data(), bf.size(), &fl.end_b, wg.allocs))) return rc;
         }
-        // Invertible1x1Conv.build_inverse (invertible_conv.py:41-47): W = kernel[0]^T, W_inverse = inv(W)^T, and the
-        // reverse conv (kernel layout [1][in][out]) computes out = audio @ W_inverse = audio @ inv(kernel[0]^T)^T.
-        WGCHK(need("waveglow/invertible_conv-" + std::to_string(k) + "/conv/kernel", {1, n_rem, n_rem}, &t));
-        {
-            const int n = n_rem;
-            std::vector<double> a((size_t)n * 2 * n, 0.0);      // [W | I], W[r][c] = kernel[c][r]
-            for (int r = 0; r < n; ++r) {
-                for (int c = 0; c < n; ++c) a[(size_t)r * 2 * n + c] = (double)t->data[(size_t)c * n + r];
-                a[(size_t)r * 2 * n + n + r] = 1.0;
-            }
-            for (int col = 0; col < n; ++col) {                  // Gauss-Jordan with partial pivoting
-                int piv = col;
-                for (int r = col + 1; r < n; ++r)
-                    if (std::fabs(a[(size_t)r * 2 * n + col]) > std::fabs(a[(size_t)piv * 2 * n + col])) piv = r;
-                if (std::fabs(a[(size_t)piv * 2 * n + col]) < 1e-12) {
-                    done();
-                    waveglow_free(e);
-                    return set_err(e, TTS_HIP_EINVAL, "invertible_conv-%d kernel is singular", k);
-                }
-                if (piv != col)
-                    for (int c = 0; c < 2 * n; ++c) std::swap(a[(size_t)piv * 2 * n + c], a[(size_t)col * 2 * n + c]);
-                const double d = a[(size_t)col * 2 * n + col];
-                for (int c = 0; c < 2 * n; ++c) a[(size_t)col * 2 * n + c] /= d;
-                for (int r = 0; r < n; ++r) {
-                    if (r == col) continue;
-                    const double f = a[(size_t)r * 2 * n + col];
-                    if (f != 0.0)
-                        for (int c = 0; c < 2 * n; ++c) a[(size_t)r * 2 * n + c] -= f * a[(size_t)col * 2 * n + c];
-                }
-            }
-            std::vector<float> minv((size_t)n * n);              // M[j][c] = inv(W)[c][j]
-            for (int j = 0; j < n; ++j)
-                for (int c = 0; c < n; ++c) minv[(size_t)j * n + c] = (float)a[(size_t)c * 2 * n + n + j];
-            WGCHK(upload(e, minv.data(), minv.size(), &fl.inv, wg.allocs));
-        }
+        if ((rc = need("waveglow/invertible_conv-" + std::to_string(k) + "/conv/kernel", {1, n_rem, n_rem}, &t))) return rc;
+        std::vector<float> minv;
+        if (!invert_1x1(t->data.data(), n_rem, &minv))
+            return set_err(e, TTS_HIP_EINVAL, "invertible_conv-%d kernel is singular", k);
+        if ((rc = upload(e, minv.data(), minv.size(), &fl.inv, wg.allocs))) return rc;
     }
-#undef WGCHK
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    done();
+    gd.keep = true;
     wg.ready = true;
     return TTS_HIP_OK;
 }
 
-// Builds the fp16 GEMM operands from the packed fp32 device copies (once).
-static int waveglow_build_f16(tts_hip_engine* e) {
+// Builds the fp16 GEMM operands of one mode from the packed fp32 device copies (once).  split: every matrix as two planes,
+// hi = fp16(w) and, n elements behind it, lo = fp16(w - hi).
+static int waveglow_build_half(tts_hip_engine* e, bool split) {
     WaveGlowDev& wg = e->wg;
-    if (wg.f16_ready) return TTS_HIP_OK;
+    bool& ready = split ? wg.x3_ready : wg.f16_ready;
+    if (ready) return TTS_HIP_OK;
     hipStream_t st = e->stream;
     auto alloc_h = [&](size_t n, _Float16** out) -> int {
         void* p = nullptr;
-        HIPCHK(e, hipMalloc(&p, n * sizeof(_Float16)));
+        HIPCHK(e, hipMalloc(&p, (split ? 2 : 1) * n * sizeof(_Float16)));
         wg.allocs.push_back(p);
         *out = (_Float16*)p;
         return TTS_HIP_OK;
     };
+    auto lo = [&](_Float16* hi, size_t n) { return split ? hi + n : (_Float16*)nullptr; };
+    auto grid = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
     int rc;
     for (int k = 0; k < 12; ++k)
         for (int i = 0; i < 8; ++i) {
             WgLayerDev& ly = wg.flow[k].layer[i];
             _Float16 *a, *c, *r = nullptr;
-            if (i == 0) {
-                if ((rc = alloc_h((size_t)2 * C * 96, &a))) return rc;
-                hipLaunchKernelGGL(cvt_taps0_kernel, dim3((2 * C * 96 + 255) / 256), dim3(256), 0, st, ly.in_Bt, a);
-            } else {
-                if ((rc = alloc_h((size_t)2 * C * KCONV, &a))) return rc;
-                const long long n = (long long)2 * C * KCONV;
-                hipLaunchKernelGGL(cvt_taps_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ly.in_Bt, a);
-            }
-            if ((rc = alloc_h((size_t)NPH * 2 * C * KMEL, &c))) return rc;
-            {
-                const long long n = (long long)NPH * 2 * C * KMEL;
-                hipLaunchKernelGGL(cvt_half_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ly.cond_Bt, c, n,
-                                   (_Float16*)nullptr);
-            }
+            const size_t na = (size_t)2 * C * (i == 0 ? 96 : KCONV), nc = (size_t)NPH * 2 * C * KMEL, nr = (size_t)C * C;
+            if ((rc = alloc_h(na, &a))) return rc;
+            if (i == 0) hipLaunchKernelGGL(cvt_taps0_kernel, grid(na), dim3(256), 0, st, ly.in_Bt, a, lo(a, na));
+            else hipLaunchKernelGGL(cvt_taps_kernel, grid(na), dim3(256), 0, st, ly.in_Bt, a, lo(a, na));
+            if ((rc = alloc_h(nc, &c))) return rc;
+            hipLaunchKernelGGL(cvt_half_kernel, grid(nc), dim3(256), 0, st, ly.cond_Bt, c, (long long)nc, lo(c, nc));
             if (ly.rs_n) {
-                if ((rc = alloc_h((size_t)C * C, &r))) return rc;
-                hipLaunchKernelGGL(cvt_half_kernel, dim3((C * C + 255) / 256), dim3(256), 0, st, ly.rs_Bt, r, (long long)C * C);
+                if ((rc = alloc_h(nr, &r))) return rc;
+                hipLaunchKernelGGL(cvt_half_kernel, grid(nr), dim3(256), 0, st, ly.rs_Bt, r, (long long)nr, lo(r, nr));
             }
             HIPCHK(e, hipGetLastError());
-            ly.in_Bt16 = a;
-            ly.cond_Bt16 = c;
-            ly.rs_Bt16 = r;
+            ly.in_Bt16[split] = a;
+            ly.cond_Bt16[split] = c;
+            ly.rs_Bt16[split] = r;
         }
     HIPCHK(e, hipStreamSynchronize(st));
-    wg.f16_ready = true;
+    ready = true;
     return TTS_HIP_OK;
 }
 
-// Split-fp16 operands ([2 planes] per matrix: hi = fp16(w), lo = fp16(w - hi)), built once from the packed fp32 copies.
-static int waveglow_build_x3(tts_hip_engine* e) {
+// ---- the pieces of waveglow_run
+namespace {
+
+// The three WN GEMM launchers of a call, chosen once from (precision, tile family).  This table is the only place that names
+// the gemm_wn_* wrappers of gemm_f32.h; the wrappers that take a bool are bound to it here.
+using WnLaunch = hipError_t (*)(const GemmArgs&, hipStream_t);
+template <hipError_t (*F)(const GemmArgs&, bool, hipStream_t), bool V>
+hipError_t bound(const GemmArgs& g, hipStream_t s) {
+    return F(g, V, s);
+}
+struct WnKernels {
+    WnLaunch in0, in, res;      // first layer of a flow (K = 3 taps of a0p), layers 1 .. 7, residual GEMM
+};
+const WnKernels kWnKernels[3][4] = {
+    // fp32                                                                                        WgTiles
+    {{gemm_wn_in0, gemm_wn_in, gemm_wn_res_skip},                                               // WG_T256
+     {gemm_wn_in0_128, gemm_wn_in_128, gemm_wn_res_skip},                                       // WG_T128
+     {gemm_wn_in0_64, gemm_wn_in_64, gemm_wn_res_64},                                           // WG_T128x64
+     {gemm_wn_in0_r64, gemm_wn_in_r64, gemm_wn_res_r64}},                                       // WG_ROW64
+    // fp16: the 128- and 256-row families are one wrapper with a bool t128
+    {{bound<gemm_wn_in0_h, false>, bound<gemm_wn_in_h, false>, gemm_wn_res_h},
+     {bound<gemm_wn_in0_h, true>, bound<gemm_wn_in_h, true>, gemm_wn_res_h},
+     {gemm_wn_in0_64h, gemm_wn_in_64h, gemm_wn_res_64h},
+     {gemm_wn_in0_r64h, gemm_wn_in_r64h, gemm_wn_res_r64h}},
+    // split fp16: two tile shapes, a bool small; wg_plan reports WG_T256 or WG_ROW64 only
+    {{bound<gemm_wn_in0_x3, false>, bound<gemm_wn_in_x3, false>, bound<gemm_wn_res_x3, false>},
+     {bound<gemm_wn_in0_x3, false>, bound<gemm_wn_in_x3, false>, bound<gemm_wn_res_x3, false>},
+     {bound<gemm_wn_in0_x3, false>, bound<gemm_wn_in_x3, false>, bound<gemm_wn_res_x3, false>},
+     {bound<gemm_wn_in0_x3, true>, bound<gemm_wn_in_x3, true>, bound<gemm_wn_res_x3, true>}},
+};
+
+// x, audio and the operands of the call's precision (layouts: the header comment of this file)
+int ensure_workspace(tts_hip_engine* e, const WgPlan& p, int precision) {
     WaveGlowDev& wg = e->wg;
-    if (wg.x3_ready) return TTS_HIP_OK;
-    hipStream_t st = e->stream;
-    auto alloc_h = [&](size_t n, _Float16** out) -> int {
-        void* p = nullptr;
-        HIPCHK(e, hipMalloc(&p, n * sizeof(_Float16)));
-        wg.allocs.push_back(p);
-        *out = (_Float16*)p;
-        return TTS_HIP_OK;
-    };
-    int rc;
-    for (int k = 0; k < 12; ++k)
-        for (int i = 0; i < 8; ++i) {
-            WgLayerDev& ly = wg.flow[k].layer[i];
-            _Float16 *a, *c, *r = nullptr;
-            if (i == 0) {
-                const size_t n = (size_t)2 * C * 96;
-                if ((rc = alloc_h(2 * n, &a))) return rc;
-                hipLaunchKernelGGL(cvt_taps0_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ly.in_Bt, a, a + n);
-            } else {
-                const size_t n = (size_t)2 * C * KCONV;
-                if ((rc = alloc_h(2 * n, &a))) return rc;
-                hipLaunchKernelGGL(cvt_taps_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ly.in_Bt, a, a + n);
-            }
-            {
-                const size_t n = (size_t)NPH * 2 * C * KMEL;
-                if ((rc = alloc_h(2 * n, &c))) return rc;
-                hipLaunchKernelGGL(cvt_half_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ly.cond_Bt, c,
-                                   (long long)n, c + n);
-            }
-            if (ly.rs_n) {
-                const size_t n = (size_t)C * C;
-                if ((rc = alloc_h(2 * n, &r))) return rc;
-                hipLaunchKernelGGL(cvt_half_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ly.rs_Bt, r,
-                                   (long long)n, r + n);
-            }
-            HIPCHK(e, hipGetLastError());
-            ly.in_Bt_x3 = a;
-            ly.cond_Bt_x3 = c;
-            ly.rs_Bt_x3 = r;
-        }
-    HIPCHK(e, hipStreamSynchronize(st));
-    wg.x3_ready = true;
+    const size_t M = (size_t)p.M, NP = (size_t)p.NP;
+    HIPCHK(e, wg.x.ensure(M * C * 4));
+    HIPCHK(e, wg.audio.ensure(M * 8 * 4));
+    if (precision != 0) {
+        HIPCHK(e, wg.x16.ensure(NP * M * C * 2));
+        HIPCHK(e, wg.acts16.ensure(8 * NP * M * C * 2));
+        HIPCHK(e, wg.a0p16.ensure(NP * M * 32 * 2));
+        HIPCHK(e, wg.mel16.ensure(NP * p.BT * KMEL * 2 + 256));
+    } else {
+        HIPCHK(e, wg.acts.ensure(8 * M * C * 4));              // activations of the 8 layers of one flow
+        HIPCHK(e, wg.a0p.ensure(M * 16 * 4));
+    }
     return TTS_HIP_OK;
 }
+
+// One A operand as the GEMM kernels address it: rows of `ld` floats and, in split fp16, the lo plane `plane` floats behind
+// the hi plane.  An fp16 operand is described in these float units too (one unit = 2 halfs), so its ld, k, kpad and the ldb
+// of its weights are half the element counts -- WnCall::unit below is the one place that says so.
+struct WnOperand {
+    const float* p;
+    int ld;
+    long long plane;
+};
+// The operands of one call in its precision
+struct WnCall {
+    WgPlan plan;
+    int precision, T;
+    int unit;                       // elements per float unit: 1 fp32, 2 the fp16 modes
+    WnOperand a0p, x, mel;          // first-layer operand, residual stream (fp16 modes: its shadow), mel frames / windows
+    float* x32;                     // fp32 residual stream (fp16 modes: the master copy)
+    float* acts;                    // gated activations of layer 0; layer i lies i * acts_stride floats behind, with x's plane
+    long long acts_stride;
+    bool split() const { return precision == 2; }
+    float* acts_of(int i) const { return acts + i * acts_stride; }
+    // a weight matrix of the call's precision (the fp16 ones exist once waveglow_build_half has run)
+    const float* weights(const float* f32, _Float16* const (&f16)[2]) const {
+        return precision == 0 ? f32 : (const float*)f16[split()];
+    }
+};
+
+WnCall wn_call(WaveGlowDev& wg, const WgPlan& p, int precision, int T, const float* d_mel) {
+    const bool f16 = precision != 0;
+    const long long pl = precision == 2 ? 1 : 0;       // split fp16: the lo plane lies one whole operand behind the hi plane
+    WnCall c{};
+    c.plan = p;
+    c.precision = precision;
+    c.T = T;
+    c.unit = f16 ? 2 : 1;
+    c.a0p = {f16 ? wg.a0p16.f() : wg.a0p.f(), 16, pl * p.M * 16};            // 16 floats or 32 halfs per row
+    c.x = {f16 ? wg.x16.f() : wg.x.f(), C / c.unit, pl * p.M * C / 2};
+    // fp32: four frames t .. t-3 of 80 floats against the per-phase weights V_{i,p}; fp16: one contiguous 4-frame window
+    c.mel = {f16 ? wg.mel16.f() : d_mel, f16 ? KMEL / 2 : 80, pl * p.BT * KMEL / 2};
+    c.x32 = wg.x.f();
+    c.acts = f16 ? wg.acts16.f() : wg.acts.f();
+    c.acts_stride = p.NP * p.M * C / c.unit;
+    return c;
+}
+
+// In-layer GEMM of layer i: K = 3 taps (of a0p for the first layer: conv(start(a0)) composed at load time, K = 3 x 16 with
+// h + 1 used instead of 3 x 512; of x otherwise) + the folded conditioning, N = 1024, gate epilogue -> acts_of(i)
+GemmArgs in_layer_args(const WnCall& c, const WgLayerDev& ly, int i) {
+    const WgPlan& p = c.plan;
+    const int d = 1 << i, u = c.unit;
+    GemmArgs g{};
+    g.M = (int)p.M;
+    g.N = 2 * C;
+    g.L = c.T;                                 // sequence bounds are tested on the frame index inside a batch item
+    g.phase_rows = p.PR;
+    g.frames = p.BT;
+    g.phase_step = d < 32 ? d : 1;             // taps at +-d groups: another phase block for d < 32, else +-d / 32 frames
+    g.bias = ly.in_bias;
+    g.mode = EPI_GATE;
+    g.split = 2 * C;
+    g.wide_epi = 1;
+    const WnOperand& a = i == 0 ? c.a0p : c.x;
+    for (int tap = 0; tap < 3; ++tap) g.seg[tap] = ASeg{a.p, a.ld, (tap - 1) * d, a.ld, a.ld, SEG_PHASE_TAP, a.plane};
+    const int nmel = c.precision == 0 ? 4 : 1;
+    for (int q = 0; q < nmel; ++q) g.seg[3 + q] = ASeg{c.mel.p, c.mel.ld, -q, c.mel.ld, c.mel.ld, SEG_FRAME, c.mel.plane};
+    g.nseg = 3 + nmel;
+    g.Bt = c.weights(ly.in_Bt, ly.in_Bt16);
+    g.ldb = 3 * a.ld;
+    g.planeB = c.split() ? (long long)2 * C * g.ldb : 0;
+    g.Bt2 = c.weights(ly.cond_Bt, ly.cond_Bt16);
+    g.ldb2 = KMEL / u;
+    g.strideB2p = (long long)2 * C * KMEL / u;
+    g.planeB2 = c.split() ? (long long)NPH * 2 * C * KMEL / 2 : 0;
+    g.ld0 = C;
+    if (c.precision == 0) {
+        g.out0 = c.acts_of(i);
+    } else {
+        g.out0 = c.x32;                        // unused by the gate epilogue (fp16 output below)
+        g.out0h = (_Float16*)c.acts_of(i);
+        g.ld0h = C;
+        g.planeOut = p.M * C;
+    }
+    return g;
+}
+
+// Residual GEMM of layer i < 7: x += acts_i @ W_res + b_res   (skip half folded into wn_end_fold)
+GemmArgs res_args(const WnCall& c, const WgLayerDev& ly, int i) {
+    const int u = c.unit;
+    GemmArgs r{};
+    r.M = (int)c.plan.M;
+    r.N = C;
+    r.L = (int)c.plan.M;
+    r.nseg = 1;
+    r.seg[0] = ASeg{c.acts_of(i), C / u, 0, C / u, C / u, SEG_ROWS, c.x.plane};
+    r.Bt = c.weights(ly.rs_Bt, ly.rs_Bt16);
+    r.ldb = C / u;
+    r.planeB = c.split() ? (long long)C * C / 2 : 0;
+    r.bias = ly.rs_bias;
+    r.mode = EPI_LINEAR;
+    r.act = ACT_NONE;
+    r.split = C;
+    r.out0 = c.x32;                            // fp16 modes: fp32 master of the residual stream (read-modify-write)
+    r.ld0 = C;
+    r.acc0 = 1;
+    r.wide_epi = 1;
+    if (c.precision != 0) {
+        r.out0h = (_Float16*)const_cast<float*>(c.x.p);    // fp16 shadow = operand of the next layer's taps
+        r.ld0h = C;
+        r.planeOut = c.plan.M * C;
+    }
+    return r;
+}
+
+int in_layer_timing_kind(int precision, int i) {
+#ifdef TTS_DEBUG_HOOKS
+    static const bool split_dil = getenv("TTS_TIME_SPLIT_DIL") != nullptr;    // measurement builds: time the fp16 / f16x3
+    if (precision != 0 && i > 0 && split_dil && (1 << i) >= 32) return 2;     // layers with d >= 32 as kind 2
+#endif
+    return i == 0 ? 3 : 0;
+}
+
+// Folded skip / end conv + affine inverse + inverse 1x1 conv of one flow: one of the nine <HALF, SPLIT, MASK> instantiations
+// of wn_end_fold_kernel, with the kernel's arguments `a`
+template <bool HALF, bool SPLIT, int MASK, class... A>
+void end_fold(dim3 grid, hipStream_t st, A... a) {
+    hipLaunchKernelGGL((wn_end_fold_kernel<HALF, SPLIT, MASK>), grid, dim3(256), 0, st, a...);
+}
+template <class... A>
+void launch_end_fold(int precision, int mask, dim3 grid, hipStream_t st, A... a) {
+    switch (precision * 3 + mask) {
+        case 0 * 3 + MASK_NONE: return end_fold<false, false, MASK_NONE>(grid, st, a...);
+        case 0 * 3 + MASK_LENS: return end_fold<false, false, MASK_LENS>(grid, st, a...);
+        case 0 * 3 + MASK_FLAGS: return end_fold<false, false, MASK_FLAGS>(grid, st, a...);
+        case 1 * 3 + MASK_NONE: return end_fold<true, false, MASK_NONE>(grid, st, a...);
+        case 1 * 3 + MASK_LENS: return end_fold<true, false, MASK_LENS>(grid, st, a...);
+        case 1 * 3 + MASK_FLAGS: return end_fold<true, false, MASK_FLAGS>(grid, st, a...);
+        case 2 * 3 + MASK_NONE: return end_fold<true, true, MASK_NONE>(grid, st, a...);
+        case 2 * 3 + MASK_LENS: return end_fold<true, true, MASK_LENS>(grid, st, a...);
+        case 2 * 3 + MASK_FLAGS: return end_fold<true, true, MASK_FLAGS>(grid, st, a...);
+    }
+}
+
+// ---- test hook (tts_hip_waveglow_probe): the call stops at the probed layer or flow and copies what it holds there
+bool probe_wants_layer(const WaveGlowDev& wg, int precision, int k, int i) {
+    // what 0: the gated activations; 2: the layer's conditioning plane, which only the fp32 path has
+    return wg.probe_out && wg.probe_flow == k && wg.probe_layer == i && (precision == 0 ? wg.probe_what != 1 : wg.probe_what == 0);
+}
+int probe_layer(tts_hip_engine* e, const WnCall& c, int i, bool wino_layer) {
+    WaveGlowDev& wg = e->wg;
+    const WgPlan& p = c.plan;
+    const bool plane = wg.probe_what == 2;                    // the layer's conditioning plane (Winograd form only)
+    if (plane && !wino_layer)
+        return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: layer %d of this call has no conditioning plane", i);
+    const int W = plane ? 2 * C : C;
+    const long long n4 = (long long)p.BT * NPH * (W / 4);
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+    if (c.precision == 0) {
+        hipLaunchKernelGGL(probe_acts_kernel, grid, dim3(256), 0, e->stream, plane ? wg.wino_cond.f() : c.acts_of(i),
+                           wg.probe_out, p.PR, p.BT, c.T, W);
+    } else {
+        const _Float16* acts_i = (const _Float16*)c.acts_of(i);
+        hipLaunchKernelGGL(probe_acts16_kernel, grid, dim3(256), 0, e->stream, acts_i,
+                           c.split() ? acts_i + p.M * C : (const _Float16*)nullptr, wg.probe_out, p.PR, p.BT, c.T);
+    }
+    HIPCHK(e, hipGetLastError());
+    return TTS_HIP_OK;
+}
+bool probe_wants_state(const WaveGlowDev& wg, int k) { return wg.probe_out && wg.probe_what == 1 && wg.probe_flow == k; }
+int probe_state(tts_hip_engine* e, const WgPlan& p, const float* state, int natural, int n) {
+    const long long np = (long long)p.BT * NPH;
+    hipLaunchKernelGGL(probe_state_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, e->stream, state, natural,
+                       e->wg.probe_out, n, p.PR, p.BT);
+    HIPCHK(e, hipGetLastError());
+    return TTS_HIP_OK;
+}
+
+// fp32, layers 1 .. 7 in their Winograd form (wn_wino.hip): builds its operands.  They are extra (7.2 GB of weight planes on
+// first use, the conditioning plane -- 0.84 GB at config 2 -- and the mel planes per call): when the device cannot hold them
+// -- and only then: any other error is the call's error -- *wino = false and this handle keeps the direct form from now on
+int wino_begin_or_fall_back(tts_hip_engine* e, const WgPlan& p, const float* d_mel, int T, bool* wino) {
+    WaveGlowDev& wg = e->wg;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(e, hipMemGetInfo(&free_b, &total_b));
+    const size_t plane = (size_t)p.M * 2 * C * 4 > wg.wino_cond.bytes ? (size_t)p.M * 2 * C * 4 : 0;
+    const size_t need = (wg.wino_ready ? 0 : (size_t)8 << 30) + plane;
+    int rc = free_b < need ? TTS_HIP_ENOMEM : waveglow_build_wino(e);
+    if (!rc) rc = waveglow_wino_begin(e, d_mel, p.PR, p.BT, T, wg.form_mode);
+    if (rc && rc != TTS_HIP_ENOMEM) return rc;
+    if (rc) {
+        (void)hipGetLastError();                                      // (clears the sticky out-of-memory status)
+        wg.form_mode = 0;
+        *wino = false;
+    }
+    return TTS_HIP_OK;
+}
+
+}  // namespace
 
 // precision 0: exact fp32 MFMA path.  precision 1: fp16 operands (activations, mel and weights fp16 in HBM), fp32
 // accumulation and fp32 epilogue math, fp32 master copy of the residual stream and of the flow state.  precision 2: split
@@ -859,65 +1058,25 @@ static int waveglow_build_x3(tts_hip_engine* e) {
 // Packed calls (d_flags != null, B = 1, d_lens null): d_flags [T] is non-zero on the real frames of the one row, d_tail lists
 // its n_tail gap frames, and d_mel is already a private copy with zero gap frames (waveglow_run_packed below).  The same
 // argument holds with "gap frame" for "tail frame": nothing in it needs the zero frames to be at the end of a row.
+//
+// The driver: wg_plan (wg_plan.h) says which tile family and form the call takes, kWnKernels which three GEMM launchers that
+// means, wn_call describes the operands of the precision once; the loop below is then the same for every call.
 int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const float* d_z, float sigma, float* d_audio,
                  int precision, const int* d_lens, const int* d_tail, int n_tail, const int* d_flags) {
     WaveGlowDev& wg = e->wg;
-    const bool packed = d_flags != nullptr;
-    const bool ragged = d_lens != nullptr || packed;             // some frames are not real
-    if (packed && (B != 1 || d_lens)) return set_err(e, TTS_HIP_EINVAL, "waveglow_run: a packed run is one row without lengths");
-    const bool half = precision == 1;
-    const bool x3 = precision == 2;
-    if (half) {
-        int rc = waveglow_build_f16(e);
-        if (rc) return rc;
-    }
-    if (x3) {
-        int rc = waveglow_build_x3(e);
-        if (rc) return rc;
-    }
-    const int BT = B * T;                                        // frames
-    // rows per phase block, padded to the M tile: 256-row tiles unless 128-row tiles save at least 5 % of the rows
-    const int pr256 = (BT + 255) / 256 * 256, pr128 = (BT + 127) / 128 * 128, pr64 = (BT + 63) / 64 * 64;
-    bool tile128 = pr128 * 1.05 < pr256;
-    // short utterances (a sentence at batch 1): 64-row tiles when they save padding
-    const int pr_big = tile128 ? pr128 : pr256;
-    bool row64 = x3 ? pr64 * 1.25 < pr256      // split fp16 has two tile shapes: 64 x 128 (about 25 % more time per row) and 256 x 256
-                    : BT <= 512 &&
-                      (half ? pr64 * 4 <= pr_big * 3 : pr64 < pr_big);   // fp16: the smaller tile only pays from -25 % rows
-    // fp32: the Winograd form (wn_wino.hip) executes K ~910 per output instead of 1 856 (taps 768 in one kernel per layer on 64-row
-    // tiles, conditioning 140 in a kernel of its own ahead of it).
-    // It pays from about 150 frames per call (one sentence, measured on one box, Winograd / direct: 100 frames 16.9 / 15.0 ms,
-    // 150: 18.3 / 20.9, 200: 19.4 / 26.0, 350: 32.2 / 37.6, 513: 48.5 / 61.2, 800: 64.0 / 84.9; the three-pass form of round 3
-    // only paid from 384 frames: its two HBM-bound passes and six-slice launches cost 40 % at 100 frames)
-#ifndef TTS_WINO_MIN_FRAMES
-#define TTS_WINO_MIN_FRAMES 144
-#endif
-    const bool wino_size = precision == 0 && wg.form_mode >= 1 && BT >= TTS_WINO_MIN_FRAMES;
-    // the three-pass form (measurement form 2) needs 128-row phase blocks; the fused kernels run on 64-row tiles
-    if (wino_size && wg.form_mode == 2 && row64 && (double)pr128 * 1120.0 * 1.35 < (double)pr64 * 1856.0) {
-        row64 = false;
-        tile128 = pr128 * 1.05 < pr256;
-    }
-    const int PR = row64 ? pr64 : (tile128 && !x3) ? pr128 : pr256;
-    const int NP = x3 ? 2 : 1;                                   // fp16 planes per operand
-    const long long M = (long long)NPH * PR;                     // phase-major rows (incl. padding)
-    // 128 x 128 tiles would leave block slots (3 per CU) empty -> 128 x 64 tiles, twice the blocks
-    const bool tile64 = !row64 && tile128 && (M / 128) * 8 < 768;
+    if (d_flags && (B != 1 || d_lens)) return set_err(e, TTS_HIP_EINVAL, "waveglow_run: a packed run is one row without lengths");
+    const int mask = d_flags ? MASK_FLAGS : d_lens ? MASK_LENS : MASK_NONE;      // which frames are not real
+    const int* mask_info = d_flags ? d_flags : d_lens;
+    if (precision != 0)
+        if (int rc = waveglow_build_half(e, precision == 2)) return rc;
+    const WgPlan plan = wg_plan(B * T, precision, wg.form_mode);
+    const int BT = plan.BT, PR = plan.PR;
+    const long long M = plan.M;
     if ((double)M * C * 4.0 >= 2147483648.0 - 65536.0)
         return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: B*T = %d frames exceeds one call's limit (~32000)", BT);
-    HIPCHK(e, wg.x.ensure((size_t)M * C * 4));
-    HIPCHK(e, wg.audio.ensure((size_t)M * 8 * 4));
-    if (half || x3) {
-        HIPCHK(e, wg.x16.ensure((size_t)NP * M * C * 2));
-        HIPCHK(e, wg.acts16.ensure((size_t)8 * NP * M * C * 2));
-        HIPCHK(e, wg.a0p16.ensure((size_t)NP * M * 32 * 2));
-        HIPCHK(e, wg.mel16.ensure((size_t)NP * BT * KMEL * 2 + 256));
-    } else {
-        HIPCHK(e, wg.acts.ensure((size_t)8 * M * C * 4));      // activations of the 8 layers of one flow
-        HIPCHK(e, wg.a0p.ensure((size_t)M * 16 * 4));
-    }
+    if (int rc = ensure_workspace(e, plan, precision)) return rc;
     hipStream_t st = e->stream;
-    if (ragged && !packed) {                                     // every reader below takes the copy with cleared tails
+    if (mask == MASK_LENS) {                                     // every reader below takes the copy with cleared tails
         HIPCHK(e, wg.mel_ragged.ensure((size_t)BT * 80 * 4));
         const long long n4 = (long long)BT * 20;
         hipLaunchKernelGGL(mel_ragged_copy_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, d_mel,
@@ -927,7 +1086,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
     }
     // x (and its fp16 shadow; after the start conv also the a0p rows) = 0 on the tail rows: store-only, tail bytes only
     auto zero_tail = [&](bool with_a0p) -> int {
-        if (!ragged || n_tail == 0) return TTS_HIP_OK;
+        if (mask == MASK_NONE || n_tail == 0) return TTS_HIP_OK;
         const long long n4 = (long long)NPH * n_tail * (C / 4);
         const bool h16 = precision != 0;
         hipLaunchKernelGGL(wn_zero_tail_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, d_tail, n_tail, PR, M,
@@ -936,46 +1095,27 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         HIPCHK(e, hipGetLastError());
         return TTS_HIP_OK;
     };
-    // fp32 path, 128- / 256-row tiles: layers 1 .. 7 of a flow run in their Winograd form (wn_wino.hip)
-    bool wino = wino_size && (!row64 || wg.form_mode != 2);               // (PR is a multiple of 64; form 2: of 128)
-    if (wino) {
-        // its operands (7.2 GB of weight planes on first use, the conditioning plane -- 0.84 GB at config 2 -- and the mel planes
-        // per call) are extra: when the device cannot hold them -- and only then: any other error is the call's error -- this
-        // handle keeps the direct form from now on
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(e, hipMemGetInfo(&free_b, &total_b));
-        const size_t plane = (size_t)M * 2 * C * 4 > wg.wino_cond.bytes ? (size_t)M * 2 * C * 4 : 0;
-        const size_t need = (wg.wino_ready ? 0 : (size_t)8 << 30) + plane;
-        int rc = free_b < need ? TTS_HIP_ENOMEM : waveglow_build_wino(e);
-        bool oom = rc == TTS_HIP_ENOMEM;
-        if (!rc) {
-            rc = waveglow_wino_begin(e, d_mel, PR, BT, T, wg.form_mode);
-            oom = rc == TTS_HIP_ENOMEM;
-        }
-        if (rc && !oom) return rc;
-        if (rc) {
-            (void)hipGetLastError();                                      // (clears the sticky out-of-memory status)
-            wg.form_mode = 0;
-            wino = false;
-        }
-    }
+    bool wino = plan.wino_wanted;
+    if (wino)
+        if (int rc = wino_begin_or_fall_back(e, plan, d_mel, T, &wino)) return rc;
     wg.last_form = wino ? 1 : 0;
-    wg.last_tiles = row64 ? 3 : x3 ? 0 : tile64 ? 2 : tile128 ? 1 : 0;     // codes: include/tts_hip.h
+    wg.last_tiles = plan.tiles;
+    const WnKernels& kn = kWnKernels[precision][plan.tiles];
+    const WnCall call = wn_call(wg, plan, precision, T, d_mel);
     _Float16* x16 = (_Float16*)wg.x16.p;
-    _Float16* acts16 = (_Float16*)wg.acts16.p;
     _Float16* mel16 = (_Float16*)wg.mel16.p;
 
     const unsigned mb = (unsigned)((M + 255) / 256);
-    if (packed)
+    if (mask == MASK_FLAGS)
         hipLaunchKernelGGL(init_audio_kernel<MASK_FLAGS>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, d_flags, T);
-    else if (ragged)
+    else if (mask == MASK_LENS)
         hipLaunchKernelGGL(init_audio_kernel<MASK_LENS>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, d_lens, T);
     else
         hipLaunchKernelGGL(init_audio_kernel<MASK_NONE>, dim3(mb), dim3(256), 0, st, d_z, sigma, wg.audio.f(), PR, BT, (const int*)nullptr, 1);
-    if (half || x3) {
+    if (precision != 0) {
         const long long n = (long long)BT * KMEL;
         hipLaunchKernelGGL(mel_window_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_mel, mel16,
-                           x3 ? mel16 + n : (_Float16*)nullptr, BT, T);
+                           precision == 2 ? mel16 + n : (_Float16*)nullptr, BT, T);
     }
     HIPCHK(e, hipGetLastError());
 
@@ -986,9 +1126,9 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         {
             const long long n4 = M * (C / 4);
             const dim3 grid((unsigned)((n4 + 255) / 256));
-            if (half || x3)
+            if (precision != 0)
                 hipLaunchKernelGGL(wn_start_kernel<true>, grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
-                                   wg.x.f(), wg.a0p16.p, x16, M, h, x3 ? 1 : 0);
+                                   wg.x.f(), wg.a0p16.p, x16, M, h, precision == 2 ? 1 : 0);
             else
                 hipLaunchKernelGGL(wn_start_kernel<false>, grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
                                    wg.x.f(), wg.a0p.p, (_Float16*)nullptr, M, h);
@@ -997,192 +1137,35 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         }
         for (int i = 0; i < 8; ++i) {
             const WgLayerDev& ly = fl.layer[i];
-            const int d = 1 << i;
-            GemmArgs g{};
-            g.M = (int)M;
-            g.N = 2 * C;
-            g.L = T;                                   // sequence bounds are tested on the frame index inside a batch item
-            g.phase_rows = PR;
-            g.frames = BT;
-            g.phase_step = d < 32 ? d : 1;             // taps at +-d groups: another phase block for d < 32, else +-d / 32 frames
-            g.nseg = 7;
-            g.bias = ly.in_bias;
-            g.mode = EPI_GATE;
-            g.split = 2 * C;
-            g.wide_epi = 1;
-            if (!half && !x3) {
-                if (i == 0) {
-                    // first layer: conv(start(a0)) composed at load time -> K = 3 taps x 16 (h + 1 used) instead of 3 x 512
-                    for (int tap = 0; tap < 3; ++tap) g.seg[tap] = ASeg{wg.a0p.f(), 16, (tap - 1) * d, 16, 16, SEG_PHASE_TAP};
-                    g.ldb = KCONV0;
-                } else {
-                    for (int tap = 0; tap < 3; ++tap) g.seg[tap] = ASeg{wg.x.f(), C, (tap - 1) * d, C, C, SEG_PHASE_TAP};
-                    g.ldb = KCONV;
-                }
-                // folded conditioning: mel frames t, t-1, t-2, t-3 against the per-phase weights V_{i,p}
-                for (int q = 0; q < 4; ++q) g.seg[3 + q] = ASeg{d_mel, 80, -q, 80, 80, SEG_FRAME};
-                g.Bt = ly.in_Bt;
-                g.Bt2 = ly.cond_Bt;
-                g.ldb2 = KMEL;
-                g.strideB2p = (long long)2 * C * KMEL;
-                float* acts_i = wg.acts.f() + (size_t)i * M * C;
-                g.out0 = acts_i;
-                g.ld0 = C;
-                if (wino && i > 0) {
-                    const int rc = waveglow_wino_layer(e, ly, i, wg.x.f(), acts_i, PR, BT, T);
-                    if (rc) return rc;
-                } else {
-                    timing_begin(e, i == 0 ? 3 : 0);
-                    if (i == 0) HIPCHK(e, row64 ? gemm_wn_in0_r64(g, st) : tile64 ? gemm_wn_in0_64(g, st) : tile128 ? gemm_wn_in0_128(g, st) : gemm_wn_in0(g, st));
-                    else HIPCHK(e, row64 ? gemm_wn_in_r64(g, st) : tile64 ? gemm_wn_in_64(g, st) : tile128 ? gemm_wn_in_128(g, st) : gemm_wn_in(g, st));
-                    timing_end(e);
-                }
-                if (wg.probe_out && wg.probe_what != 1 && wg.probe_flow == k && wg.probe_layer == i) {   // test hook: stop here
-                    const bool plane = wg.probe_what == 2;                    // the layer's conditioning plane (Winograd form only)
-                    if (plane && !(wino && i > 0))
-                        return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: layer %d of this call has no conditioning plane", i);
-                    const int W = plane ? 2 * C : C;
-                    const long long n4 = (long long)BT * NPH * (W / 4);
-                    hipLaunchKernelGGL(probe_acts_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
-                                       plane ? wg.wino_cond.f() : acts_i, wg.probe_out, PR, BT, T, W);
-                    HIPCHK(e, hipGetLastError());
-                    return TTS_HIP_OK;
-                }
-                if (i < 7) {             // residual: x += acts_i @ W_res + b_res   (skip half folded into wn_end_fold)
-                    GemmArgs r{};
-                    r.M = (int)M;
-                    r.N = C;
-                    r.L = (int)M;
-                    r.nseg = 1;
-                    r.seg[0] = ASeg{acts_i, C, 0, C, C};
-                    r.Bt = ly.rs_Bt;
-                    r.ldb = C;
-                    r.bias = ly.rs_bias;
-                    r.mode = EPI_LINEAR;
-                    r.act = ACT_NONE;
-                    r.split = C;
-                    r.out0 = wg.x.f();
-                    r.ld0 = C;
-                    r.acc0 = 1;
-                    r.wide_epi = 1;
-                    timing_begin(e, 1);
-                    HIPCHK(e, row64 ? gemm_wn_res_r64(r, st) : tile64 ? gemm_wn_res_64(r, st) : gemm_wn_res_skip(r, st));
-                    timing_end(e);
-                    if (int rc = zero_tail(false)) return rc;
-                }
+            const bool wino_layer = wino && i > 0;
+            if (wino_layer) {
+                if (int rc = waveglow_wino_layer(e, ly, i, wg.x.f(), call.acts_of(i), PR, BT, T)) return rc;
             } else {
-                // fp16 operands, described in float units (one unit = 2 halfs): ld / k / kpad / ldb are halved.  Split mode:
-                // every operand has a second plane (the lo halves) at a fixed offset, loaded next to the first one.
-                const long long plX = x3 ? (long long)M * C / 2 : 0, plA0 = x3 ? (long long)M * 16 : 0,
-                                plMel = x3 ? (long long)BT * KMEL / 2 : 0;
-                g.nseg = 4;                  // 3 taps + one contiguous 4-frame mel window
-                if (i == 0) {
-                    for (int tap = 0; tap < 3; ++tap)
-                        g.seg[tap] = ASeg{(const float*)wg.a0p16.p, 16, (tap - 1) * d, 16, 16, SEG_PHASE_TAP, plA0};
-                    g.ldb = 96 / 2;
-                    g.planeB = x3 ? (long long)2 * C * 96 / 2 : 0;
-                } else {
-                    for (int tap = 0; tap < 3; ++tap)
-                        g.seg[tap] = ASeg{(const float*)x16, C / 2, (tap - 1) * d, C / 2, C / 2, SEG_PHASE_TAP, plX};
-                    g.ldb = KCONV / 2;
-                    g.planeB = x3 ? (long long)2 * C * KCONV / 2 : 0;
-                }
-                g.seg[3] = ASeg{(const float*)mel16, KMEL / 2, 0, KMEL / 2, KMEL / 2, SEG_FRAME, plMel};
-                g.Bt = (const float*)(x3 ? ly.in_Bt_x3 : ly.in_Bt16);
-                g.Bt2 = (const float*)(x3 ? ly.cond_Bt_x3 : ly.cond_Bt16);
-                g.ldb2 = KMEL / 2;
-                g.strideB2p = (long long)2 * C * KMEL / 2;
-                g.planeB2 = x3 ? (long long)NPH * 2 * C * KMEL / 2 : 0;
-                _Float16* acts_i = acts16 + (size_t)i * NP * M * C;
-                g.out0 = wg.x.f();           // unused by the gate epilogue (fp16 output below)
-                g.ld0 = C;
-                g.out0h = acts_i;
-                g.ld0h = C;
-                g.planeOut = (long long)M * C;
-#ifdef TTS_DEBUG_HOOKS
-                static const bool split_dil = getenv("TTS_TIME_SPLIT_DIL") != nullptr;    // measurement builds: time the
-                timing_begin(e, i == 0 ? 3 : (split_dil && d >= 32) ? 2 : 0);             // layers with d >= 32 as kind 2
-#else
-                timing_begin(e, i == 0 ? 3 : 0);
-#endif
-                if (x3) HIPCHK(e, i == 0 ? gemm_wn_in0_x3(g, row64, st) : gemm_wn_in_x3(g, row64, st));
-                else if (row64) HIPCHK(e, i == 0 ? gemm_wn_in0_r64h(g, st) : gemm_wn_in_r64h(g, st));
-                else if (tile64) HIPCHK(e, i == 0 ? gemm_wn_in0_64h(g, st) : gemm_wn_in_64h(g, st));
-                else HIPCHK(e, i == 0 ? gemm_wn_in0_h(g, tile128, st) : gemm_wn_in_h(g, tile128, st));
+                const GemmArgs g = in_layer_args(call, ly, i);
+                timing_begin(e, in_layer_timing_kind(precision, i));
+                HIPCHK(e, (i == 0 ? kn.in0 : kn.in)(g, st));
                 timing_end(e);
-                if (wg.probe_out && wg.probe_what == 0 && wg.probe_flow == k && wg.probe_layer == i) {   // test hook: stop here
-                    const long long n4 = (long long)BT * NPH * (C / 4);
-                    hipLaunchKernelGGL(probe_acts16_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, acts_i,
-                                       x3 ? acts_i + M * C : (const _Float16*)nullptr, wg.probe_out, PR, BT, T);
-                    HIPCHK(e, hipGetLastError());
-                    return TTS_HIP_OK;
-                }
-                if (i < 7) {
-                    GemmArgs r{};
-                    r.M = (int)M;
-                    r.N = C;
-                    r.L = (int)M;
-                    r.nseg = 1;
-                    r.seg[0] = ASeg{(const float*)acts_i, C / 2, 0, C / 2, C / 2, SEG_ROWS, plX};
-                    r.Bt = (const float*)(x3 ? ly.rs_Bt_x3 : ly.rs_Bt16);
-                    r.ldb = C / 2;
-                    r.planeB = x3 ? (long long)C * C / 2 : 0;
-                    r.bias = ly.rs_bias;
-                    r.mode = EPI_LINEAR;
-                    r.act = ACT_NONE;
-                    r.split = C;
-                    r.out0 = wg.x.f();       // fp32 master of the residual stream (read-modify-write)
-                    r.ld0 = C;
-                    r.acc0 = 1;
-                    r.out0h = x16;           // fp16 shadow = operand of the next layer's taps
-                    r.ld0h = C;
-                    r.planeOut = (long long)M * C;
-                    r.wide_epi = 1;
-                    timing_begin(e, 1);
-                    if (x3) HIPCHK(e, gemm_wn_res_x3(r, row64, st));
-                    else HIPCHK(e, row64 ? gemm_wn_res_r64h(r, st) : tile64 ? gemm_wn_res_64h(r, st) : gemm_wn_res_h(r, st));
-                    timing_end(e);
-                    if (int rc = zero_tail(false)) return rc;
-                }
+            }
+            if (probe_wants_layer(wg, precision, k, i)) return probe_layer(e, call, i, wino_layer);   // test hook: stop here
+            if (i < 7) {
+                const GemmArgs r = res_args(call, ly, i);
+                timing_begin(e, 1);
+                HIPCHK(e, kn.res(r, st));
+                timing_end(e);
+                if (int rc = zero_tail(false)) return rc;
             }
         }
         const bool early = (k % 4 == 0) && k > 0;
         float* dst = (k == 0) ? d_audio : wg.audio.f();
         const long long waves = (M + RPW - 1) / RPW;
-        const dim3 grid((unsigned)((waves + 3) / 4));
-#define TTS_END_FOLD(HALF_, SPLIT_, MASK_, acts_, stride_, lo_, info_)                                                     \
-    hipLaunchKernelGGL((wn_end_fold_kernel<HALF_, SPLIT_, MASK_>), grid, dim3(256), 0, st, (const void*)(acts_),          \
-                       (long long)(stride_), fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z, zoff,    \
-                       early ? 2 : 0, sigma, M, h, PR, BT, (long long)(lo_), info_, T)
-        if (packed) {
-            if (x3) TTS_END_FOLD(true, true, MASK_FLAGS, acts16, NP * M * C, M * C, d_flags);
-            else if (half) TTS_END_FOLD(true, false, MASK_FLAGS, acts16, M * C, 0, d_flags);
-            else TTS_END_FOLD(false, false, MASK_FLAGS, wg.acts.p, M * C, 0, d_flags);
-        } else if (ragged) {
-            if (x3) TTS_END_FOLD(true, true, MASK_LENS, acts16, NP * M * C, M * C, d_lens);
-            else if (half) TTS_END_FOLD(true, false, MASK_LENS, acts16, M * C, 0, d_lens);
-            else TTS_END_FOLD(false, false, MASK_LENS, wg.acts.p, M * C, 0, d_lens);
-        } else if (x3)
-            hipLaunchKernelGGL((wn_end_fold_kernel<true, true>), grid, dim3(256), 0, st, (const void*)acts16,
-                               (long long)NP * M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
-                               zoff, early ? 2 : 0, sigma, M, h, PR, BT, (long long)M * C);
-        else if (half)
-            hipLaunchKernelGGL((wn_end_fold_kernel<true, false>), grid, dim3(256), 0, st, (const void*)acts16,
-                               (long long)M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
-                               zoff, early ? 2 : 0, sigma, M, h, PR, BT, 0ll);
-        else
-            hipLaunchKernelGGL((wn_end_fold_kernel<false, false>), grid, dim3(256), 0, st, (const void*)wg.acts.p,
-                               (long long)M * C, fl.end_w, fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z,
-                               zoff, early ? 2 : 0, sigma, M, h, PR, BT);
-#undef TTS_END_FOLD
+        // elements between two layers' activations and (split fp16) from their hi to their lo plane; a call without a mask
+        // passes no frame info and T = 1 (not read)
+        launch_end_fold(precision, mask, dim3((unsigned)((waves + 3) / 4)), st, (const void*)call.acts, plan.NP * M * C, fl.end_w,
+                        fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z, zoff, early ? 2 : 0, sigma, M, h, PR, BT,
+                        precision == 2 ? M * C : 0ll, mask_info, mask == MASK_NONE ? 1 : T);
         HIPCHK(e, hipGetLastError());
-        if (wg.probe_out && wg.probe_what == 1 && wg.probe_flow == k) {          // test hook: the state after this flow
-            const long long n = (long long)BT * NPH;
-            hipLaunchKernelGGL(probe_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)dst,
-                               k == 0 ? 1 : 0, wg.probe_out, 2 * h + (early ? 2 : 0), PR, BT);
-            HIPCHK(e, hipGetLastError());
-            return TTS_HIP_OK;
-        }
+        if (probe_wants_state(wg, k))                            // test hook: the state after this flow
+            return probe_state(e, plan, dst, k == 0 ? 1 : 0, 2 * h + (early ? 2 : 0));
         if (early) zoff += 2;
     }
     return TTS_HIP_OK;
