@@ -342,7 +342,9 @@ int tts_hip_resample_async(tts_hip_engine* e, const float* audio, int B, int N, 
 /* ---- measurement hooks (used by bench.py; no effect on results) -------------------------------------------------
  * Average duration in microseconds of the dominant kernel's launches (HIP events on the engine's stream) since the
  * last reset, and how many launches were timed.  kind: 0 = WaveGlow WN in-layer GEMM (layers 1..7 of a flow: K = 2176),
- * 1 = WN residual GEMM, 2 = Tacotron2 decoder step, 3 = first WN layer of a flow (start conv composed: K = 688).  Timing is off unless enabled (events perturb nothing but cost a few us each).        */
+ * 1 = WN residual GEMM, 2 = Tacotron2 decoder step, 3 = first WN layer of a flow (start conv composed into its taps: direct
+ * form one GEMM of K = 48 + 320; Winograd form the tap operand kernel and wino_layer0_kernel, K = 16 + 140 per output).
+ * Timing is off unless enabled (events perturb nothing but cost a few us each).        */
 int tts_hip_kernel_timing(tts_hip_engine* e, int enable);
 /* Box probe: TFLOP/s a bare v_mfma_f32_32x32x2_f32 loop sustains on this device right now (every CU, 2 waves per SIMD, ~20 ms)
  * and the shader clock (GHz) it holds meanwhile -- what the fp32 MFMA roofline of THIS box is; boxes of one pool differ.    */

@@ -46,7 +46,8 @@ struct WgLayerDev {
     _Float16* cond_Bt16[2] = {nullptr, nullptr};    // [32][1024][4*96]
     _Float16* rs_Bt16[2] = {nullptr, nullptr};      // [512][512]
     float* wino_G = nullptr;    // Winograd form (wn_wino.hip; built on first use): [6][1024][512] tap combinations and the
-    float* wino_W = nullptr;    //   conditioning weight planes [32][7][1024][80] (F(4, 4) along frames)
+    float* wino_W = nullptr;    //   conditioning weight planes [32][7][1024][80] (F(4, 4) along frames; every layer)
+    float* wino_T = nullptr;    //   first layer only (it has no wino_G): its composed taps as one K = 16 chunk, [1024][16]
     float* rs_Bt = nullptr;     // [512][512] residual half of res_skip (layers 0..6)
     float* rs_bias = nullptr;   // [512]
     int rs_n = 0;
@@ -82,11 +83,12 @@ struct WaveGlowDev {
                                              //   [segment table | frame flags | gap frames] goes through ragged_info)
     DevBuf wino_U, wino_P, wino_mel;         // mel planes; forms 2 / 3 only: transformed inputs [6][M/4][512], products [6][M/4][1024]
     DevBuf wino_cond;                        // conditioning plane of the current layer [32 PR][1024]
+    DevBuf wino_taps;                        // tap operand of the current flow's first layer [32 PR][16]
     // ... and listed here, which is what waveglow_free releases
     template <class F>
     void for_each_buf(F f) {
         for (DevBuf* b : {&x, &acts, &audio, &a0p, &x16, &acts16, &a0p16, &mel16, &io_mel, &io_z, &io_out, &io_zgen, &mel_ragged,
-                          &ragged_info, &packed_z, &packed_out, &wino_U, &wino_P, &wino_mel, &wino_cond})
+                          &ragged_info, &packed_z, &packed_out, &wino_U, &wino_P, &wino_mel, &wino_cond, &wino_taps})
             f(*b);
     }
 };
@@ -259,6 +261,7 @@ struct StreamScope {
 int waveglow_build_wino(tts_hip_engine* e);
 int waveglow_wino_begin(tts_hip_engine* e, const float* d_mel, int PR, int BT, int T, int form);
 int waveglow_wino_layer(tts_hip_engine* e, const WgLayerDev& ly, int i, const float* x, float* acts_i, int PR, int BT, int T);
+int waveglow_wino_layer0(tts_hip_engine* e, const WgLayerDev& ly, int h, const float* a0p, float* acts_0, int PR, int BT, int T);
 // timing helpers (engine.hip)
 void timing_begin(tts_hip_engine* e, int kind);
 void timing_end(tts_hip_engine* e);

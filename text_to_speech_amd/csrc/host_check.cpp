@@ -6,8 +6,14 @@
 //        ttsw_check_asan --wg-plan LO HI [STEP]  -- the WaveGlow dispatch (wg_plan.h), one line "BT precision form PR tiles
 // wino_wanted" for every STEP-th (default: every) frame count LO..HI, the three precisions and forms 0..3
 // (tests/test_wg_plan.py compares them with pick_variant).
+//        ttsw_check_asan --wn-taps H T LEN...  -- the tap operand of a flow's first WN layer in the Winograd form (wn_tap_row,
+// wn_tap_of_col, wn_tap_src_col of wg_plan.h, the functions wino_tap_operand_kernel runs) for a call of B = number of LEN rows
+// of T frames, H coupling channels: a model a0p -- column c < H of row m holds 1 + 8 m + c, column H holds 1, rows of frames
+// t >= LEN[b] are zero as after the tail clearing -- goes in, one line of 16 integers per phase-major row comes out, behind a
+// first line "PR" (tests/test_wino_layer0_map.py restates it by positions).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
+#include <vector>
 
 #include "ttsw_host.h"
 #include "wg_plan.h"
@@ -23,7 +29,34 @@ static int print_wg_plans(int lo, int hi, int step) {
     return 0;
 }
 
+static int print_wn_taps(int h, int T, const std::vector<int>& lens) {
+    const int B = (int)lens.size(), BT = B * T;
+    if (h < 1 || h > 4 || T < 1 || B < 1) return 2;
+    const int PR = wg_plan(BT, 0, 1).PR;
+    std::vector<long long> a0p((size_t)32 * PR * 16, 0);
+    for (int m = 0; m < 32 * PR; ++m) {
+        const int f = m % PR;
+        if (f < BT && f % T >= lens[f / T]) continue;                          // a cleared tail row
+        for (int c = 0; c < h; ++c) a0p[(size_t)m * 16 + c] = 1 + 8ll * m + c;
+        a0p[(size_t)m * 16 + h] = 1;
+    }
+    printf("%d\n", PR);
+    for (int m = 0; m < 32 * PR; ++m)
+        for (int k = 0; k < 16; ++k) {
+            const int tap = wn_tap_of_col(k, h);
+            const long long src = tap < 3 ? wn_tap_row(m / PR, m % PR, tap - 1, PR, BT, T) : -1;
+            if (src >= 32ll * PR) return 2;
+            printf("%lld%c", src >= 0 ? a0p[(size_t)src * 16 + wn_tap_src_col(k, h)] : 0ll, k == 15 ? '\n' : ' ');
+        }
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 5 && !strcmp(argv[1], "--wn-taps")) {
+        std::vector<int> lens;
+        for (int i = 4; i < argc; ++i) lens.push_back(atoi(argv[i]));
+        return print_wn_taps(atoi(argv[2]), atoi(argv[3]), lens);
+    }
     if ((argc == 4 || argc == 5) && !strcmp(argv[1], "--wg-plan")) {
         const int step = argc == 5 ? atoi(argv[4]) : 1;
         return step > 0 ? print_wg_plans(atoi(argv[2]), atoi(argv[3]), step) : 2;

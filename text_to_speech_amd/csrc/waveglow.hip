@@ -29,6 +29,9 @@
 // read-modify-write of a [M][512] skip buffer per layer -- and are replaced by one [M, 8*512] x [8*512, 2h] product per
 // flow (h <= 4), computed by the HBM-bound wn_end_fold_kernel straight from the stored activations.
 //
+// fp32 calls of 144 frames or more take the Winograd form (wn_wino.hip) instead of the in-layer GEMMs above: layers 1 .. 7 as
+// F(4,3) along the taps behind a frame-axis F(4,4) conditioning plane, the first layer of a flow on that plane kernel's K loop.
+//
 // Host side, in file order: waveglow_free; the load-time algebra above as three host functions and waveglow_finalize, which
 // uploads their results; waveglow_build_half (fp16 operands of either fp16 mode, on first use); the pieces of waveglow_run --
 // the kWnKernels table (precision x tile family of wg_plan.h -> GEMM launchers), ensure_workspace, wn_call / in_layer_args /
@@ -1024,7 +1027,7 @@ int probe_state(tts_hip_engine* e, const WgPlan& p, const float* state, int natu
     return TTS_HIP_OK;
 }
 
-// fp32, layers 1 .. 7 in their Winograd form (wn_wino.hip): builds its operands.  They are extra (7.2 GB of weight planes on
+// fp32, the layers in their Winograd form (wn_wino.hip): builds its operands.  They are extra (8.1 GB of weight planes on
 // first use, the conditioning plane -- 0.84 GB at config 2 -- and the mel planes per call): when the device cannot hold them
 // -- and only then: any other error is the call's error -- *wino = false and this handle keeps the direct form from now on
 int wino_begin_or_fall_back(tts_hip_engine* e, const WgPlan& p, const float* d_mel, int T, bool* wino) {
@@ -1032,7 +1035,7 @@ int wino_begin_or_fall_back(tts_hip_engine* e, const WgPlan& p, const float* d_m
     size_t free_b = 0, total_b = 0;
     HIPCHK(e, hipMemGetInfo(&free_b, &total_b));
     const size_t plane = (size_t)p.M * 2 * C * 4 > wg.wino_cond.bytes ? (size_t)p.M * 2 * C * 4 : 0;
-    const size_t need = (wg.wino_ready ? 0 : (size_t)8 << 30) + plane;
+    const size_t need = (wg.wino_ready ? 0 : (size_t)9 << 30) + plane;
     int rc = free_b < need ? TTS_HIP_ENOMEM : waveglow_build_wino(e);
     if (!rc) rc = waveglow_wino_begin(e, d_mel, p.PR, p.BT, T, wg.form_mode);
     if (rc && rc != TTS_HIP_ENOMEM) return rc;
@@ -1140,6 +1143,8 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
             const bool wino_layer = wino && i > 0;
             if (wino_layer) {
                 if (int rc = waveglow_wino_layer(e, ly, i, wg.x.f(), call.acts_of(i), PR, BT, T)) return rc;
+            } else if (wino) {                 // first layer of a flow: the plane kernel's K loop, taps and gate in its epilogue
+                if (int rc = waveglow_wino_layer0(e, ly, h, wg.a0p.f(), call.acts_of(0), PR, BT, T)) return rc;
             } else {
                 const GemmArgs g = in_layer_args(call, ly, i);
                 timing_begin(e, in_layer_timing_kind(precision, i));

@@ -49,3 +49,27 @@ inline WgPlan wg_plan(int BT, int precision, int form_mode) {
     p.wino_wanted = wino_size && (!row64 || form_mode != 2);     // form 2 never runs on 64-row blocks (PR: a multiple of 128)
     return p;
 }
+
+// First WN layer of a flow in the Winograd form (wn_wino.hip, wino_layer0_kernel): its three taps act on the neighbouring
+// POSITIONS n - 1, n, n + 1 (n = 32 t + p), i.e. on the phase blocks p - 1, p, p + 1 of the phase-major layout, carried into
+// frame t - 1 / t + 1 at p = 0 / p = 31.  Row of a0p that tap s (-1, 0, +1) of position (phase p, frame row f = b T + t) reads,
+// or -1 when that position lies outside the utterance (or f is a padding row >= BT): the bounds test of the direct form's
+// SEG_PHASE_TAP segments.  Tail frames of a ragged row and gap frames of a packed row need no test: their a0p rows are zero.
+#ifdef __HIPCC__
+#define WG_HOST_DEVICE __host__ __device__
+#else
+#define WG_HOST_DEVICE
+#endif
+WG_HOST_DEVICE inline long long wn_tap_row(int p, int f, int s, int PR, int BT, int T) {
+    if (f >= BT) return -1;
+    const int ps = p + s;
+    const int carry = ps < 0 ? -1 : ps > 31 ? 1 : 0;
+    const int t = f % T + carry;
+    if (t < 0 || t >= T) return -1;
+    return (long long)(ps - 32 * carry) * PR + f + carry;
+}
+// Column k of the 16-float tap operand row for a flow with h coupling channels: [tap -1: a[0..h), v | tap 0 | tap +1 | 0 ..]
+// (v: a0p's constant-1 column, the indicator that carries the start conv's bias) -> tap index 0 .. 2 and a0p column, or
+// tap 3 for the zero columns behind the 3 (h + 1) used ones.
+WG_HOST_DEVICE inline int wn_tap_of_col(int k, int h) { return k < 3 * (h + 1) ? k / (h + 1) : 3; }
+WG_HOST_DEVICE inline int wn_tap_src_col(int k, int h) { return k % (h + 1); }

@@ -31,6 +31,8 @@
 // K = 140 per output in a kernel of its own (wino_cond_kernel, below: one launch per layer ahead of the in-layer kernel), which
 // leaves a plane cond[32 PR][1024] (bias included) that the in-layer kernels add in their epilogue in place of the bias.  A
 // layer executes K = 768 + 140 per output instead of 768 + 320 (dilations 32 / 64: + 200, the earlier F(4, 2) form).
+// The first layer of a flow (taps on the flow's h <= 4 coupling channels) runs on the same K loop, with its taps, bias and gate
+// in the epilogue (wino_layer0_kernel): K = 140 + 16 per output instead of 320 + 48, and no plane.
 //
 // Groups.  Dilation d <= 8 (sample groups): four PHASES p0 + j d of one frame, 8 group phases p0 = (gp / d) 4d + gp % d.
 // d >= 32 (s = d / 32 frames): four FRAMES t0 + j s of one phase.  d = 16: two phases x two frames.  Frame groups are cut per
@@ -42,6 +44,7 @@
 // times less `end` attenuation 6.5e-6 (4.9e-6).  Not bit-identical to the direct form.
 #include "engine.h"
 #include "gemm_f32.h"
+#include "wg_plan.h"
 
 #include <algorithm>
 
@@ -283,10 +286,38 @@ struct WinoCondArgs {
     float* cond;                       // [32 PR][1024]
     int rows;                          // group rows (a multiple of BM)
     int PR, BT, T;
+    // first layer of a flow (wino_layer0_kernel) only: no plane, the gated activations instead
+    const float* taps;                 // tap operand [32 PR][16] (wino_tap_operand_kernel)
+    const float* Wt;                   // tap weights [1024][16], rows in W's order (wino_tap_weights_kernel)
+    float* acts;                       // [32 PR][512]
 };
 
-template <int WR, int WC, int NBUF, int OCC>
-__global__ __launch_bounds__(WR * WC * 64, OCC) void wino_cond_kernel(const WinoCondArgs g) {
+// The first layer of a flow.  Its taps act on the flow's h <= 4 coupling channels (the start conv is composed into them at
+// load time), so its whole pre-activation is the conditioning FIR plus a K <= 15 product per position: the plane kernel's K loop
+// on the layer's own weight planes, and an epilogue that adds the tap term by one K = 16 MFMA chunk per output frame, adds the
+// bias, gates and stores acts -- no plane, no K = 320 + 48 GEMM.
+// Tap operand: one 16-float row per position, [a(n-1)[0..h), v(n-1) | a(n)[0..h), v(n) | a(n+1)[0..h), v(n+1) | 0 ..], copied
+// from the a0p rows of the three positions (wn_tap_row, wg_plan.h; after the tail rows of a0p were cleared), zeros for a
+// neighbour outside the utterance; tap weights: the matching columns of the composed in_Bt [1024][3 x 16].
+__global__ void wino_tap_operand_kernel(const float* __restrict__ a0p, float* __restrict__ taps, int h, int PR, int BT, int T) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)NPH * PR * 16) return;
+    const int k = (int)(idx & 15);
+    const long long m = idx >> 4;
+    const int tap = wn_tap_of_col(k, h);
+    const long long src = tap < 3 ? wn_tap_row((int)(m / PR), (int)(m % PR), tap - 1, PR, BT, T) : -1;
+    taps[idx] = src >= 0 ? a0p[src * 16 + wn_tap_src_col(k, h)] : 0.f;
+}
+__global__ void wino_tap_weights_kernel(const float* __restrict__ in_Bt0, float* __restrict__ Wt, int h) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= 2 * C * 16) return;
+    const int k = idx & 15, tap = wn_tap_of_col(k, h);
+    Wt[idx] = tap < 3 ? in_Bt0[(idx >> 4) * 48 + tap * 16 + wn_tap_src_col(k, h)] : 0.f;
+}
+
+// (the body of both kernels; L0: the first layer of a flow)
+template <int WR, int WC, int NBUF, bool L0>
+__device__ __forceinline__ void wino_cond_body(const WinoCondArgs& g) {
     constexpr int NW = WR * WC, BM = WR * 32, BN = WC * 32;
     constexpr int NPA = BM / 16, NPB = BN / 16, PPW = (NPA + NPB) / NW;     // 16-row DMA pieces: A side, B side, per wave
     static_assert((NPA + NPB) % NW == 0 && PPW <= 4, "the pieces of a tile divide among the waves, one per MFMA of a half step");
@@ -398,32 +429,117 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void wino_cond_kernel(const Wino
     // offset, the output's frame step into the scalar offset; frames past the end of the utterance: out-of-range offset, no store
     const float bv = g.bias[n0 + wc * 32 + li];
     const int* const rt = g.rowtab + m0 + wr * 32 + 4 * lh;
-    const __amdgpu_buffer_rsrc_t ro = make_rsrc_uniform(g.cond + (long long)ph * g.PR * (2 * C) + n0 + wc * 32);
+    if constexpr (!L0) {
+        const __amdgpu_buffer_rsrc_t ro = make_rsrc_uniform(g.cond + (long long)ph * g.PR * (2 * C) + n0 + wc * 32);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int info = rt[(r & 3) + 8 * (r >> 2)];
-        const unsigned voff = ((unsigned)(info & 0xffff) * (2 * C) + li) * 4u;
-        const int nout = info >> 16;
-        const float s12 = acc[1][r] + acc[2][r], d12 = acc[1][r] - acc[2][r];
-        const float s34 = acc[3][r] + acc[4][r], d34 = acc[3][r] - acc[4][r];
-        const float s56 = acc[5][r] + acc[6][r], d56 = acc[5][r] - acc[6][r];
-        float y[4];
-        y[0] = acc[0][r] + s12 + s34 + s56 + bv;
-        y[1] = d12 + 2.f * d34 + 0.5f * d56 + bv;
-        y[2] = s12 + 4.f * s34 + 0.25f * s56 + bv;
-        y[3] = d12 + 8.f * d34 + 0.125f * d56 + bv;
+        for (int r = 0; r < 16; ++r) {
+            const int info = rt[(r & 3) + 8 * (r >> 2)];
+            const unsigned voff = ((unsigned)(info & 0xffff) * (2 * C) + li) * 4u;
+            const int nout = info >> 16;
+            const float s12 = acc[1][r] + acc[2][r], d12 = acc[1][r] - acc[2][r];
+            const float s34 = acc[3][r] + acc[4][r], d34 = acc[3][r] - acc[4][r];
+            const float s56 = acc[5][r] + acc[6][r], d56 = acc[5][r] - acc[6][r];
+            float y[4];
+            y[0] = acc[0][r] + s12 + s34 + s56 + bv;
+            y[1] = d12 + 2.f * d34 + 0.5f * d56 + bv;
+            y[2] = s12 + 4.f * s34 + 0.25f * s56 + bv;
+            y[3] = d12 + 8.f * d34 + 0.125f * d56 + bv;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y[j]), ro, j < nout ? voff : OOB, j * (2 * C * 4), 0);
+        }
+    } else {
+        static_assert(WC == 2, "waves (wr, 0) and (wr, 1) hold the tanh and the sigmoid half of the same 32 channels");
+        // the tap term's operands: as an MFMA A row, lane (li, lh) holds columns 8 lh .. 8 lh + 7 of the operand row of group
+        // row li's frame j (a frame past the utterance, a padding row: zeros through an out-of-range offset), as a B row the
+        // same columns of its own weight row -- K step kk of the chunk is column 8 lh + kk on both sides
+        const int arow = g.rowtab[m0 + wr * 32 + li];
+        const __amdgpu_buffer_rsrc_t rta = make_rsrc_uniform(g.taps + (long long)ph * g.PR * 16);
+        f32x4 ta[4][2], tb[2];
+        auto load_taps = [&](int j) {
+            const unsigned off = j < arow >> 16 ? ((unsigned)(arow & 0xffff) + j) * 64u + lh * 32u : OOB;
+            ta[j][0] = buf_load4(rta, off);
+            ta[j][1] = buf_load4(rta, off + 16u);
+        };
+        load_taps(0);                                                       // (frames 2, 3 once sets 4 .. 6 are free: register budget)
+        load_taps(1);
+        tb[0] = *reinterpret_cast<const f32x4*>(g.Wt + (n0 + wc * 32 + li) * 16 + lh * 8);
+        tb[1] = *reinterpret_cast<const f32x4*>(g.Wt + (n0 + wc * 32 + li) * 16 + lh * 8 + 4);
+        // output transform in place: frames 0 .. 3 into accumulator sets 0 .. 3 (sets 4 .. 6 are free from here on)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float s12 = acc[1][r] + acc[2][r], d12 = acc[1][r] - acc[2][r];
+            const float s34 = acc[3][r] + acc[4][r], d34 = acc[3][r] - acc[4][r];
+            const float s56 = acc[5][r] + acc[6][r], d56 = acc[5][r] - acc[6][r];
+            acc[0][r] = acc[0][r] + s12 + s34 + s56;
+            acc[1][r] = d12 + 2.f * d34 + 0.5f * d56;
+            acc[2][r] = s12 + 4.f * s34 + 0.25f * s56;
+            acc[3][r] = d12 + 8.f * d34 + 0.125f * d56;
+            if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);            // (four rows' temporaries at a time: register budget)
+        }
+        load_taps(2);
+        load_taps(3);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y[j]), ro, j < nout ? voff : OOB, j * (2 * C * 4), 0);
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk)
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ta[j][kk >> 2][kk & 3], tb[kk >> 2][kk & 3], acc[j], 0, 0, 0);
+        // gate: the tanh wave (wc 0) gates frames 0, 1 and hands its frames 2, 3 to the sigmoid wave (wc 1), which hands over
+        // its frames 0, 1 -- 32 values per lane through the released pipeline LDS, register index major (32 consecutive floats
+        // per half wave: no bank conflict).  Every wave has passed its vmcnt(0) before the barrier: no DMA piece (the fetch-
+        // nothing ones land zeros) is still on its way into the LDS that is written here.
+        float* const give = smem + wave * (32 * 64) + lane;
+        const float* const take = smem + (wave ^ 1) * (32 * 64) + lane;
+        __builtin_amdgcn_s_barrier();
+        auto hand_over = [&](auto jc) {                                     // JG: the first of the two frames given away
+            constexpr int JG = decltype(jc)::value;
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) give[(jj * 16 + r) * 64] = acc[JG + jj][r] + bv;
+        };
+        auto gate_store = [&](auto jc) {                                    // JK: the first of the two frames kept
+            constexpr int JK = decltype(jc)::value;
+            const __amdgpu_buffer_rsrc_t ro = make_rsrc_uniform(g.acts + (long long)ph * g.PR * C + (n0 >> 6) * 32);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int info = rt[(r & 3) + 8 * (r >> 2)];
+                const unsigned voff = ((unsigned)(info & 0xffff) * C + li) * 4u;
+                const int nout = info >> 16;
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj) {
+                    const float mine = acc[JK + jj][r] + bv, other = take[(jj * 16 + r) * 64];
+                    const float v = JK == 0 ? gate_tanh_sigmoid(mine, other) : gate_tanh_sigmoid(other, mine);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, JK + jj < nout ? voff : OOB,
+                                                          (JK + jj) * (C * 4), 0);
+                }
+            }
+        };
+        if (wc == 0) hand_over(std::integral_constant<int, 2>{});
+        else hand_over(std::integral_constant<int, 0>{});
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (wc == 0) gate_store(std::integral_constant<int, 0>{});
+        else gate_store(std::integral_constant<int, 2>{});
     }
 }
 
 template <int WR, int WC, int NBUF, int OCC>
+__global__ __launch_bounds__(WR * WC * 64, OCC) void wino_cond_kernel(const WinoCondArgs g) {
+    wino_cond_body<WR, WC, NBUF, false>(g);
+}
+template <int WR, int WC, int NBUF, int OCC>
+__global__ __launch_bounds__(WR * WC * 64, OCC) void wino_layer0_kernel(const WinoCondArgs g) {
+    wino_cond_body<WR, WC, NBUF, true>(g);
+}
+
+template <int WR, int WC, int NBUF, int OCC, bool L0 = false>
 hipError_t launch_wino_cond(const WinoCondArgs& a, hipStream_t st) {
     constexpr int BM = WR * 32, BN = WC * 32;
-    const size_t lds = (size_t)NBUF * (BM + BN) * 16 * sizeof(float);
+    // (first layer: the gate's exchange, 32 floats per lane, needs more than the pipeline's three buffers)
+    const size_t lds = std::max((size_t)NBUF * (BM + BN) * 16, L0 ? (size_t)WR * WC * 32 * 64 : (size_t)0) * sizeof(float);
     if (a.rows % BM != 0) return hipErrorInvalidValue;
-    auto kern = wino_cond_kernel<WR, WC, NBUF, OCC>;
+    auto kern = L0 ? wino_layer0_kernel<WR, WC, NBUF, OCC> : wino_cond_kernel<WR, WC, NBUF, OCC>;
     static PerDeviceOnce attr_set;
     if (hipError_t e = set_max_dyn_lds_once((const void*)kern, lds, attr_set); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)(NPH * (2 * C / BN) * (a.rows / BM))), dim3(WR * WC * 64), lds, st, a);
@@ -1119,9 +1235,9 @@ static inline int mixed_group_rows(int BT, int T, int form) {
 
 static inline int cond_group_rows(int BT, int T) { return ((BT / T) * cond_groups_per_utt(T) + 63) / 64 * 64; }
 
-// Per-layer operands (on the first call that takes this path), for layers 1 .. 7 of every flow: the tap combinations G
-// ([6][1024][512], 12.6 MB) and the conditioning weight planes W ([32][7][1024][80], 73 MB) -- 7.2 GB in all, the same for
-// every form.  A failed allocation frees what this call built.
+// Per-layer operands (on the first call that takes this path): for layers 1 .. 7 of every flow the tap combinations G
+// ([6][1024][512], 12.6 MB), for all eight layers the conditioning weight planes W ([32][7][1024][80], 73 MB), for the first
+// layer its tap weights ([1024][16]) -- 8.1 GB in all, the same for every form.  A failed allocation frees what this call built.
 int waveglow_build_wino(tts_hip_engine* e) {
     WaveGlowDev& wg = e->wg;
     if (wg.wino_ready) return TTS_HIP_OK;
@@ -1131,16 +1247,22 @@ int waveglow_build_wino(tts_hip_engine* e) {
         (void)hipStreamSynchronize(st);
         for (void* p : fresh) (void)hipFree(p);
         for (int k = 0; k < 12; ++k)
-            for (int i = 1; i < 8; ++i) wg.flow[k].layer[i].wino_G = wg.flow[k].layer[i].wino_W = nullptr;
+            for (int i = 0; i < 8; ++i) wg.flow[k].layer[i].wino_G = wg.flow[k].layer[i].wino_W = wg.flow[k].layer[i].wino_T = nullptr;
         return rc;
     };
     for (int k = 0; k < 12; ++k)
-        for (int i = 1; i < 8; ++i) {
+        for (int i = 0; i < 8; ++i) {
             WgLayerDev& ly = wg.flow[k].layer[i];
             const long long nw = (long long)NPH * NPT * 2 * C * NMEL;
             int rc;
-            if ((rc = dev_alloc(e, (size_t)6 * 2 * C * C, &ly.wino_G, fresh, false))) return fail(rc);
-            hipLaunchKernelGGL(wino4_weights_kernel, dim3(blocks_for(2 * C * C)), dim3(256), 0, st, ly.in_Bt, ly.wino_G);
+            if (i == 0) {                                  // (in_Bt of the first layer: the composed taps [1024][3 x 16])
+                if ((rc = dev_alloc(e, (size_t)2 * C * 16, &ly.wino_T, fresh, false))) return fail(rc);
+                hipLaunchKernelGGL(wino_tap_weights_kernel, dim3(blocks_for(2 * C * 16)), dim3(256), 0, st, ly.in_Bt, ly.wino_T,
+                                   wg.flow[k].n_half);
+            } else {
+                if ((rc = dev_alloc(e, (size_t)6 * 2 * C * C, &ly.wino_G, fresh, false))) return fail(rc);
+                hipLaunchKernelGGL(wino4_weights_kernel, dim3(blocks_for(2 * C * C)), dim3(256), 0, st, ly.in_Bt, ly.wino_G);
+            }
             if ((rc = dev_alloc(e, (size_t)nw, &ly.wino_W, fresh, false))) return fail(rc);
             hipLaunchKernelGGL(wino_cond_weights_kernel, dim3(blocks_for(nw)), dim3(256), 0, st, ly.cond_Bt, ly.wino_W);
             if (hipError_t herr = hipGetLastError(); herr != hipSuccess)
@@ -1172,6 +1294,7 @@ int waveglow_wino_begin(tts_hip_engine* e, const float* d_mel, int PR, int BT, i
     if (need_U && (rc = room(wg.wino_U, rows * C * 4))) return rc;
     if (three_pass && (rc = room(wg.wino_P, rows * 2 * C * 4))) return rc;
     if ((rc = room(wg.wino_mel, ((size_t)NPT * PRc * NMEL + PRc) * 4))) return rc;      // [mel planes | row table]
+    if ((rc = room(wg.wino_taps, (size_t)NPH * PR * 16 * 4))) return rc;                // tap operand of a flow's first layer
     // the conditioning plane [32 PR][1024]; its padding rows (frame rows >= BT of a phase) are never written and feed only the
     // padding rows of `acts`: cleared once per allocation so that they hold numbers
     const size_t before = wg.wino_cond.bytes;
@@ -1182,6 +1305,37 @@ int waveglow_wino_begin(tts_hip_engine* e, const float* d_mel, int PR, int BT, i
     hipLaunchKernelGGL(wino_cond_rows_kernel, dim3(blocks_for(PRc)), dim3(256), 0, st, (int*)(wg.wino_mel.f() + (size_t)NPT * PRc * NMEL),
                        PRc, BT, T);
     HIPCHK(e, hipGetLastError());
+    return TTS_HIP_OK;
+}
+
+static WinoCondArgs cond_args(WaveGlowDev& wg, const WgLayerDev& ly, int PR, int BT, int T) {
+    WinoCondArgs c{};
+    c.Z = wg.wino_mel.f();
+    c.W = ly.wino_W;
+    c.bias = ly.in_bias;
+    c.cond = wg.wino_cond.f();
+    c.rows = cond_group_rows(BT, T);
+    c.rowtab = (const int*)(c.Z + (size_t)NPT * c.rows * NMEL);
+    c.PR = PR;
+    c.BT = BT;
+    c.T = T;
+    return c;
+}
+
+// The first layer of a flow with h coupling channels: acts_0 = gate(taps(a0p) + cond + b) from the a0p rows the start kernel
+// wrote (tail rows cleared): the tap operand, then the layer's kernel.  The same launches in every form and tile family.
+int waveglow_wino_layer0(tts_hip_engine* e, const WgLayerDev& ly, int h, const float* a0p, float* acts_0, int PR, int BT, int T) {
+    WaveGlowDev& wg = e->wg;
+    hipStream_t st = e->stream;
+    WinoCondArgs c = cond_args(wg, ly, PR, BT, T);
+    c.taps = wg.wino_taps.f();
+    c.Wt = ly.wino_T;
+    c.acts = acts_0;
+    timing_begin(e, 3);
+    hipLaunchKernelGGL(wino_tap_operand_kernel, dim3(blocks_for((long long)NPH * PR * 16)), dim3(256), 0, st, a0p, wg.wino_taps.f(), h,
+                       PR, BT, T);
+    HIPCHK(e, (launch_wino_cond<2, 2, 3, 3, true>(c, st)));
+    timing_end(e);
     return TTS_HIP_OK;
 }
 
@@ -1196,16 +1350,7 @@ int waveglow_wino_layer(tts_hip_engine* e, const WgLayerDev& ly, int i, const fl
     const int PRq = frame_group_rows(BT, T, wg.form_mode), PRm = mixed_group_rows(BT, T, wg.form_mode);
     const bool phases = d <= 8, mixed = d == 16;
     const long long Mq = phases ? (long long)(NPH / 4) * PR : mixed ? (long long)16 * PRm : (long long)NPH * PRq;
-    WinoCondArgs c{};
-    c.Z = wg.wino_mel.f();
-    c.W = ly.wino_W;
-    c.bias = ly.in_bias;
-    c.cond = wg.wino_cond.f();
-    c.rows = cond_group_rows(BT, T);
-    c.rowtab = (const int*)(c.Z + (size_t)NPT * c.rows * NMEL);
-    c.PR = PR;
-    c.BT = BT;
-    c.T = T;
+    const WinoCondArgs c = cond_args(wg, ly, PR, BT, T);
     const bool no_prepass = wg.form_mode == 1;             // form 1 (default): input transform inside the GEMM's operand reads
     if (!no_prepass) hipLaunchKernelGGL(wino4_prepass_kernel, dim3(blocks_for(Mq * (C / 4))), dim3(256), 0, st, x, U, d, PR, BT, T, Mq);
     if (wg.form_mode != 2) {                               // fused GEMM + output transform + gate (form 2: the three passes)
