@@ -68,7 +68,20 @@ int tts_hip_has_model(const tts_hip_engine* e, const char* model);
  * mel   [B, T, 80]
  * z     NULL (=> zeros: the reference's deterministic=True) or [B, T*32, 8] noise, consumed in the reference's order
  *       (channels 0..3 initial audio, 4..5 early output after flow 8, 6..7 after flow 4)
- * audio [B, T*256] out                                                                                              */
+ * audio [B, T*256] out
+ *
+ * The shared contract of every tts_hip_waveglow_infer* call (this one, _f16, _f16x3, _seeded, _ragged, _packed, _rows_seeded and
+ * the _async forms further down; each comment below only says what its entry adds):
+ *   - `precision`, where a call has the argument: 0 f32 (in the form tts_hip_set_waveglow_form selects), 1 f16, 2 f16x3;
+ *   - a call with `mem` runs on the handle's stream and returns when it has drained; mel, z and audio live where `mem` says.
+ *     An _async call takes device pointers and a `stream` (NULL = the handle's), enqueues and returns without synchronizing.
+ *     `lengths`, `keys` and `offsets` are host arrays in every mode, read before the call returns;
+ *   - a call is refused with TTS_HIP_EINVAL before anything is copied or launched, and the message starts with the name of the
+ *     symbol that was called.  The reasons, first match first: precision outside 0 .. 2; a `mem` that is no TTS_HIP_MEM_*;
+ *     keys or offsets NULL; B <= 0; mel or audio NULL or T <= 0; B * T above 2^25 frames; packed without lengths; a
+ *     lengths[b] outside [0, T]; more frames than one run takes (31744): T of a call that is not packed -- a larger B * T runs
+ *     as slices of whole rows inside the call, a longer single row needs windowed inference -- or F of a packed call;
+ *   - the same arguments give the same bits through every entry point and memory kind that can express them.           */
 int tts_hip_waveglow_infer(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
                            float* audio, int mem);
 /* Same contract with fp16 GEMM operands (the reference's Keras mixed_float16 policy, utils/keras/gpu.py:32-34; BASELINE
@@ -95,7 +108,7 @@ int tts_hip_waveglow_infer_f16x3(tts_hip_engine* e, const float* mel, int B, int
  * oracle/philox_ref.py).  The same (seed, offset) always gives the same values; consecutive calls should advance `offset`
  * by ceil(n / 4).
  * `tts_hip_waveglow_infer_seeded` = WaveGlow.infer(mel, z=None, deterministic=False): z [B, T*32, 8] is generated on the
- * device from (seed, offset) and never crosses PCIe.  precision: 0 f32, 1 f16, 2 f16x3.                               */
+ * device from (seed, offset) and never crosses PCIe.                                                                    */
 enum { TTS_HIP_RANDOM_NORMAL = 0, TTS_HIP_RANDOM_PRENET_MASK = 1 };
 int tts_hip_random_fill(tts_hip_engine* e, int kind, uint64_t seed, uint64_t offset, float* out, int64_t n, void* stream);
 int tts_hip_waveglow_infer_seeded(tts_hip_engine* e, const float* mel, int B, int T, uint64_t seed, uint64_t offset,
@@ -107,8 +120,8 @@ int tts_hip_waveglow_infer_seeded(tts_hip_engine* e, const float* mel, int B, in
  * row_stride for every row; 0 <= counts[b] <= row_stride) and touches nothing at i >= counts[b].  keys, offsets and counts
  * are HOST arrays of B entries, read before the call returns; `out` is a DEVICE buffer; enqueued on `stream` (NULL = the
  * handle's stream) without synchronizing.  B = 1 is `tts_hip_random_fill` bit for bit.
- * `tts_hip_waveglow_infer_rows_seeded[_async]`: the contract of tts_hip_waveglow_infer_ragged[_async] (packed == 0; lengths
- * may be NULL) or tts_hip_waveglow_infer_packed[_async] (packed != 0; needs lengths) with the noise drawn inside the engine:
+ * `tts_hip_waveglow_infer_rows_seeded[_async]`: tts_hip_waveglow_infer_ragged[_async] (packed == 0; lengths may be NULL) or
+ * tts_hip_waveglow_infer_packed[_async] (packed != 0; needs lengths) with the noise drawn inside the engine:
  * z[b, p, c] = normal element p * 8 + c of row b's stream, only lengths[b] * 256 values per row when lengths are given.  A
  * row's noise -- and, where a row's arithmetic is its own (lengths given), its audio up to fp32 re-association -- is the
  * same whichever batch, row position or neighbours it is vocoded with.  Without lengths the rows are a padded batch and
@@ -149,7 +162,7 @@ int tts_hip_tacotron2_infer_f16(tts_hip_engine* e, const int32_t* tokens, int B,
  * (a hipStream_t passed as void*; NULL = the handle's stream), only accept device pointers, enqueue their work and return
  * WITHOUT synchronizing, so a caller can queue transfers, several calls and its own kernels back to back.  A handle still
  * has one workspace per model: two calls on the same handle must be ordered (same stream, or an event between streams).
- * precision: 0 = f32, 1 = f16 operands, 2 = f16x3 (WaveGlow); 0 = f32, 1 = fp16 LSTM weights (Tacotron2).
+ * precision: as the WaveGlow contract above says; 0 = f32, 1 = fp16 LSTM weights (Tacotron2).
  *
  * Tacotron2 in two calls -- Tacotron2Encoder (tacotron2_arch.py:235-333, once per batch) and the decoder loop + postnet
  * (:609-749, :915-917):  `encode` is asynchronous and returns an opaque encoded batch (its own device buffer; free it with
@@ -259,28 +272,24 @@ int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, co
 int tts_hip_last_waveglow_tiles(const tts_hip_engine* e);
 
 /* ---- WaveGlow.infer on a batch of unequal rows
- * mel [B, T, 80], z NULL or [B, T*32, 8], audio [B, T*256] as above; row b holds lengths[b] (0 <= lengths[b] <= T) real
- * frames, lengths NULL = T for every row: then the call IS tts_hip_waveglow_infer* / _async (same kernels, same launches,
- * bit-equal audio).  With lengths, in every precision (0 f32 in the form tts_hip_set_waveglow_form selects, 1 f16, 2 f16x3)
- * and every tile family:
+ * Row b holds lengths[b] (0 <= lengths[b] <= T) real frames; lengths NULL = T for every row: then the call IS
+ * tts_hip_waveglow_infer* / _async (same kernels, same launches, bit-equal audio).  With lengths, in every precision and
+ * every tile family:
  *   - audio[b, :lengths[b]*256] is what a one-row call on mel[b, :lengths[b]], z[b, :lengths[b]*32] returns, up to the fp32
  *     re-association that already separates tile families and forms (a padded row of the calls above is NOT: its WN
  *     convolutions read the padding where the row alone reads zeros, 3e-2 .. 5e-2 RMS on the row's samples);
  *   - audio[b, lengths[b]*256:] = 0 exactly;
  *   - nothing read beyond a row's length: mel[b, lengths[b]:] and z[b, lengths[b]*32:] may hold anything, NaN and Inf
  *     included (e.g. uninitialised padding), and two calls that differ only there return bit-equal audio.
- * `lengths` is host memory in every mode (read during the call); mel, z and audio follow `mem` / live on the device for
- * the _async form, which enqueues on `stream` and returns without synchronizing like tts_hip_waveglow_infer_async.  The
- * B * T limits of the calls above hold (T is what counts, not the lengths: tail frames still occupy rows of the GEMMs).  */
+ * T is what counts towards the limits, not the lengths: tail frames still occupy rows of the GEMMs.                      */
 int tts_hip_waveglow_infer_ragged(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths, const float* z,
                                   float sigma, float* audio, int precision, int mem);
 int tts_hip_waveglow_infer_ragged_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
                                         const float* z, float sigma, float* audio, int precision, void* stream);
 
-/* ---- the same contract, computed as ONE packed row
- * Arguments, memory kinds and results as tts_hip_waveglow_infer_ragged[_async] (lengths must not be NULL): audio[b,
- * :lengths[b]*256] is what a one-row call on the row's own frames returns, audio[b, lengths[b]*256:] = 0 exactly, nothing
- * beyond a row's length is read.  Only the way it is computed differs: the real frames of all rows are laid one after
+/* ---- the same results, computed as ONE packed row
+ * Arguments and results as tts_hip_waveglow_infer_ragged[_async] (lengths must not be NULL).  Only the way it is computed
+ * differs: the real frames of all rows are laid one after
  * another in one row of F = sum(lengths) + TTS_HIP_WG_GAP_FRAMES * (rows with frames - 1) frames, separated by runs of zero
  * "gap" frames that are marked as not real (rows of length 0 take no space and no gap), and that row runs as an ordinary
  * one-row call -- the work follows the frames that exist, not B * max(lengths).  A gather builds the packed mel / z from

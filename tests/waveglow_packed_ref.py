@@ -1,6 +1,7 @@
 """Packed WaveGlow calls restated in numpy and plain Python (shared by tests/test_waveglow_packed*.py).
 
-`packing_plan` is the host plan of tts_hip_waveglow_infer_packed (csrc/engine.hip, stage_packed): the rows that hold frames
+`packing_plan` is the host plan of tts_hip_waveglow_infer_packed (csrc/wg_call.h, wg_call_table; compared with it on the
+CPU by tests/test_wg_call.py): the rows that hold frames
 one after another in ONE row, `gap` zero frames between two of them, rows of length 0 without space and without gap.
 `infer_packed` is oracle.waveglow_ref.infer on such a row with the frames that are not real held at 0 where the engine
 holds them at 0: mel and z, the WN residual stream after the start conv and after every residual sum, the flow state after

@@ -13,6 +13,7 @@
 #include "../../include/tts_hip.h"
 
 #include "ttsw_host.h"      // HostTensor + the TTSW parser (host-only code, also built under ASan / UBSan)
+#include "wg_call.h"        // WgCall: one WaveGlow call, its checks and its staged table (host-only code, likewise)
 
 // Growable device buffer (workspace).  Never shrinks; reallocated only when a larger request arrives.
 struct DevBuf {
@@ -73,7 +74,7 @@ struct WaveGlowDev {
     float* probe_out = nullptr;              //   [B][T * 32][n] or the layer's conditioning plane [B][T * 32][1024] (what 2;
                                              //   Winograd form only) to this device buffer
     bool wino_ready = false;                 // Winograd form of the fp32 in-layer GEMM (wn_wino.hip)
-    std::vector<int> ragged_info_h;          // host image of ragged_info (staged to the device once per call)
+    WgTable call_table;                      // host image of ragged_info (staged to the device once per call), counts
     // ---- workspace: every DevBuf of this struct is declared here ...
     DevBuf x, acts, audio, a0p;              // fp32 path (layouts: waveglow.hip)
     DevBuf x16, acts16, a0p16, mel16;        // fp16 path: shadow of x, activations, first-layer operand, mel

@@ -349,165 +349,110 @@ int tts_hip_has_model(const tts_hip_engine* e, const char* model) {
     return 0;
 }
 
-constexpr int kMaxFramesPerRun = 31744;      // one waveglow_run addresses its activations with 31-bit byte offsets
-
-// Ragged calls: checks `lengths` (host int32 [B], each in [0, T]) and stages [lengths | tail frames] to the device on the
-// current stream, once per call.  The tail frames (b - b0) * T + t, t >= lengths[b], are listed run by run (b0 = first row
-// of the run of `chunkB` rows that holds row b), so that each run finds its own as one contiguous slice.
-static int stage_ragged(tts_hip_engine* e, int B, int T, const int32_t* lengths, int chunkB, const char* who) {
-    long long n_tail = 0;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] < 0 || lengths[b] > T)
-            return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d is outside [0, T = %d]", who, b, (int)lengths[b], T);
-        n_tail += T - lengths[b];
+// Host callers: mel (and z, when given) go through the engine's staging buffers on the current stream.
+static int wg_stage_in(tts_hip_engine* e, const float* mel, const float* z, int B, int T, const float** d_mel, const float** d_z) {
+    const size_t n_mel = (size_t)B * T * 80, n_z = (size_t)B * T * 32 * 8;
+    HIPCHK(e, e->wg.io_mel.ensure(n_mel * 4));
+    HIPCHK(e, hipMemcpyAsync(e->wg.io_mel.p, mel, n_mel * 4, hipMemcpyHostToDevice, e->stream));
+    *d_mel = e->wg.io_mel.f();
+    if (z) {
+        HIPCHK(e, e->wg.io_z.ensure(n_z * 4));
+        HIPCHK(e, hipMemcpyAsync(e->wg.io_z.p, z, n_z * 4, hipMemcpyHostToDevice, e->stream));
+        *d_z = e->wg.io_z.f();
     }
-    std::vector<int>& h = e->wg.ragged_info_h;
-    h.resize((size_t)B + (size_t)n_tail);
-    size_t at = (size_t)B;
-    for (int b = 0; b < B; ++b) {
-        h[b] = lengths[b];
-        for (int t = lengths[b]; t < T; ++t) h[at++] = (b % chunkB) * T + t;
-    }
-    HIPCHK(e, e->wg.ragged_info.ensure(h.size() * sizeof(int)));
-    // (pageable source: the copy has left `h` when the call returns, so the next call may rebuild it)
-    HIPCHK(e, hipMemcpyAsync(e->wg.ragged_info.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
     return TTS_HIP_OK;
 }
 
-// Packed calls: checks `lengths` like stage_ragged, plans the packed row -- the rows that hold frames one after another,
-// TTS_HIP_WG_GAP_FRAMES gap frames between two of them, rows of length 0 take no space and no gap -- and stages
-// [start[B] | len[B] | flags[F] | gap frames] once per call.  flags[f] = 1 + b * T + t on the packed frame that holds frame
-// t of row b (non-zero = real, and the gather's source index), 0 on a gap frame.  The packed row is ONE waveglow_run, so
-// its F frames must fit one run: no slicing, and no silent fall-back to the ragged path.
-static int stage_packed(tts_hip_engine* e, int B, int T, const int32_t* lengths, const char* who, int* F_out, int* n_gap_out) {
-    long long F = 0;
-    int rows = 0;
-    for (int b = 0; b < B; ++b) {
-        if (lengths[b] < 0 || lengths[b] > T)
-            return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d is outside [0, T = %d]", who, b, (int)lengths[b], T);
-        if (lengths[b] > 0) {
-            F += lengths[b];
-            ++rows;
-        }
-    }
-    const long long n_gap = rows > 1 ? (long long)TTS_HIP_WG_GAP_FRAMES * (rows - 1) : 0;
-    F += n_gap;
-    if (F > kMaxFramesPerRun)
-        return set_err(e, TTS_HIP_EINVAL,
-                       "%s: the packed row holds F = %lld frames (%d rows with frames, %d gap frames between two), above one "
-                       "run's limit (%d); split the batch or use the ragged call",
-                       who, F, rows, TTS_HIP_WG_GAP_FRAMES, kMaxFramesPerRun);
-    std::vector<int>& h = e->wg.ragged_info_h;
-    h.assign((size_t)2 * B + (size_t)F + (size_t)n_gap, 0);
-    int* flags = h.data() + 2 * (size_t)B;
-    int* gaps = flags + F;
-    int pos = 0, g = 0;
-    bool first = true;
-    for (int b = 0; b < B; ++b) {
-        h[(size_t)B + b] = lengths[b];
-        if (lengths[b] == 0) continue;                           // (start stays 0: the scatter reads nothing of such a row)
-        if (!first)
-            for (int j = 0; j < TTS_HIP_WG_GAP_FRAMES; ++j) gaps[g++] = pos++;
-        first = false;
-        h[b] = pos;
-        for (int t = 0; t < lengths[b]; ++t) flags[pos++] = 1 + b * T + t;
-    }
-    HIPCHK(e, e->wg.ragged_info.ensure(h.size() * sizeof(int)));
-    // (pageable source: the copy has left `h` when the call returns, so the next call may rebuild it)
-    HIPCHK(e, hipMemcpyAsync(e->wg.ragged_info.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    *F_out = (int)F;
-    *n_gap_out = (int)n_gap;
-    return TTS_HIP_OK;
-}
-
-// runs of whole utterances, each within kMaxFramesPerRun frames; lengths != NULL: staged by stage_ragged with the same chunkB
-static int waveglow_run_chunks(tts_hip_engine* e, const float* d_mel, int B, int T, const int32_t* lengths, const float* d_z,
-                               float sigma, float* d_out, int precision) {
+// runs of whole utterances, each within kMaxFramesPerRun frames; ragged: wg.call_table was built with the same chunkB
+static int waveglow_run_chunks(tts_hip_engine* e, const float* d_mel, int B, int T, bool ragged, const float* d_z, float sigma,
+                               float* d_out, int precision) {
     const int chunkB = kMaxFramesPerRun / T;
     const int* d_info = (const int*)e->wg.ragged_info.p;
     size_t tail_at = (size_t)B;
     for (int b0 = 0; b0 < B; b0 += chunkB) {
         const int nb = B - b0 < chunkB ? B - b0 : chunkB;
-        int n_tail = 0;
-        if (lengths)
-            for (int b = b0; b < b0 + nb; ++b) n_tail += T - lengths[b];
+        const int n_tail = ragged ? e->wg.call_table.run_tails[b0 / chunkB] : 0;
         int rc = waveglow_run(e, d_mel + (size_t)b0 * T * 80, nb, T, d_z ? d_z + (size_t)b0 * T * 32 * 8 : nullptr, sigma,
-                              d_out + (size_t)b0 * T * 256, precision, lengths ? d_info + b0 : nullptr,
-                              lengths ? d_info + tail_at : nullptr, n_tail);
+                              d_out + (size_t)b0 * T * 256, precision, ragged ? d_info + b0 : nullptr,
+                              ragged ? d_info + tail_at : nullptr, n_tail);
         if (rc) return rc;
         tail_at += (size_t)n_tail;
     }
     return TTS_HIP_OK;
 }
 
-static int waveglow_infer_impl(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
-                               float* audio, int mem, int precision, const int32_t* lengths = nullptr, bool packed = false) {
+// Every tts_hip_waveglow_infer* entry point: check, then table, staging, noise and the runs, in that order on one stream.
+static int waveglow_call(tts_hip_engine* e, const WgCall& c) {
     if (!e) return TTS_HIP_EINVAL;
     if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
-    if (!mel || !audio || B <= 0 || T <= 0) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: bad argument");
-    if ((long long)B * T * 32 > (1ll << 30)) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: B*T too large");
-    if (packed && !lengths) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_packed: lengths is NULL");
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: bad mem kind %d", mem);
+    char why[512];
+    if (int rc = wg_call_check(c, why, sizeof why)) return set_err(e, rc, "%s", why);
     HIPCHK(e, hipSetDevice(e->device));
-    int F = 0, n_gap = 0;
-    if (packed) {                                                // planned and checked before anything is copied or launched
-        int rc = stage_packed(e, B, T, lengths, "waveglow_infer_packed", &F, &n_gap);
+    StreamScope scope(e, c.async ? c.stream : nullptr);
+    const int B = c.B, T = c.T;
+    WgTable& tab = e->wg.call_table;
+    if (c.lengths || c.noise == WG_NOISE_ROWS) wg_call_table(B, T, c.lengths, c.packed, c.packed ? B : kMaxFramesPerRun / T, &tab);
+    if (c.lengths) {
+        HIPCHK(e, e->wg.ragged_info.ensure(tab.info.size() * sizeof(int)));
+        // (pageable source: the copy has left the table when the call returns, so the next call may rebuild it)
+        HIPCHK(e, hipMemcpyAsync(e->wg.ragged_info.p, tab.info.data(), tab.info.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    }
+    const size_t n_z = (size_t)B * T * 32 * 8, n_out = (size_t)B * T * 256;
+    const bool host = !c.async && c.mem == TTS_HIP_MEM_HOST;
+    const float* d_mel = c.mel;
+    const float* d_z = c.noise == WG_NOISE_Z ? c.z : nullptr;
+    float* d_out = c.audio;
+    if (host) {
+        if (int rc = wg_stage_in(e, c.mel, d_z, B, T, &d_mel, &d_z)) return rc;
+        HIPCHK(e, e->wg.io_out.ensure(n_out * 4));
+        d_out = e->wg.io_out.f();
+    }
+    if (c.noise != WG_NOISE_Z) {                                 // a device buffer whatever `mem` says about mel / audio
+        HIPCHK(e, e->wg.io_zgen.ensure(n_z * 4));
+        d_z = e->wg.io_zgen.f();
+        int rc = c.noise == WG_NOISE_SEED
+                     ? philox_fill(e, e->wg.io_zgen.f(), (long long)n_z, c.seed, c.offset, TTS_HIP_RANDOM_NORMAL, e->stream)
+                     : philox_fill_rows(e, e->wg.io_zgen.f(), B, (long long)T * 256, c.keys, c.offsets, tab.counts.data(),
+                                        TTS_HIP_RANDOM_NORMAL, e->stream);
         if (rc) return rc;
     }
-    const size_t n_mel = (size_t)B * T * 80, n_z = (size_t)B * T * 32 * 8, n_out = (size_t)B * T * 256;
-    const float* d_mel = mel;
-    const float* d_z = z;
-    float* d_out = audio;
-    if (mem == TTS_HIP_MEM_HOST) {
-        HIPCHK(e, e->wg.io_mel.ensure(n_mel * 4));
-        HIPCHK(e, e->wg.io_out.ensure(n_out * 4));
-        HIPCHK(e, hipMemcpyAsync(e->wg.io_mel.p, mel, n_mel * 4, hipMemcpyHostToDevice, e->stream));
-        d_mel = e->wg.io_mel.f();
-        d_out = e->wg.io_out.f();
-        if (z) {
-            HIPCHK(e, e->wg.io_z.ensure(n_z * 4));
-            HIPCHK(e, hipMemcpyAsync(e->wg.io_z.p, z, n_z * 4, hipMemcpyHostToDevice, e->stream));
-            d_z = e->wg.io_z.f();
-        }
-    } else if (mem != TTS_HIP_MEM_DEVICE) {
-        return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: bad mem kind %d", mem);
-    }
-    // One run addresses its activations with 31-bit byte offsets (<= ~32 k frames).  Utterances are independent, so a
-    // larger batch is processed in slices of whole utterances; a single utterance above the limit is refused (the Python
-    // wrapper's windowed inference, models/tts/waveglow.py:114-142, is the reference's own answer to long mels).
-    // (a packed call is bounded by its F, checked by stage_packed above)
-    if (!packed && T > kMaxFramesPerRun)
-        return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: T = %d frames exceeds one run's limit (%d); use windowed inference",
-                       T, kMaxFramesPerRun);
-    if (packed) {
-        if (int rc = waveglow_run_packed(e, d_mel, B, T, d_z, sigma, d_out, precision, (const int*)e->wg.ragged_info.p, F, n_gap))
-            return rc;
-    } else {
-        if (lengths) {
-            int rc = stage_ragged(e, B, T, lengths, kMaxFramesPerRun / T, "waveglow_infer_ragged");
-            if (rc) return rc;
-        }
-        if (int rc = waveglow_run_chunks(e, d_mel, B, T, lengths, d_z, sigma, d_out, precision)) return rc;
-    }
-    if (mem == TTS_HIP_MEM_HOST)
-        HIPCHK(e, hipMemcpyAsync(audio, d_out, n_out * 4, hipMemcpyDeviceToHost, e->stream));
+    int rc = c.packed ? waveglow_run_packed(e, d_mel, B, T, d_z, c.sigma, d_out, c.precision, (const int*)e->wg.ragged_info.p,
+                                            tab.F, tab.n_gap)
+                      : waveglow_run_chunks(e, d_mel, B, T, c.lengths != nullptr, d_z, c.sigma, d_out, c.precision);
+    if (rc || c.async) return rc;
+    if (host) HIPCHK(e, hipMemcpyAsync(c.audio, d_out, n_out * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return TTS_HIP_OK;
 }
 
+// The part of a WgCall that every entry point fills the same way; z / seed / keys and mem / stream are the entry point's own.
+static WgCall wg_call(const char* who, const float* mel, int B, int T, const int32_t* lengths, bool packed, WgNoise noise,
+                      float sigma, float* audio, int precision, bool async) {
+    WgCall c{};
+    c.who = who, c.mel = mel, c.B = B, c.T = T, c.lengths = lengths, c.packed = packed, c.noise = noise;
+    c.sigma = sigma, c.audio = audio, c.precision = precision, c.async = async;
+    return c;
+}
+
 int tts_hip_waveglow_infer(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
                            float* audio, int mem) {
-    return waveglow_infer_impl(e, mel, B, T, z, sigma, audio, mem, 0);
+    WgCall c = wg_call("tts_hip_waveglow_infer", mel, B, T, nullptr, false, WG_NOISE_Z, sigma, audio, 0, false);
+    c.z = z, c.mem = mem;
+    return waveglow_call(e, c);
 }
 
 int tts_hip_waveglow_infer_f16(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
                                float* audio, int mem) {
-    return waveglow_infer_impl(e, mel, B, T, z, sigma, audio, mem, 1);
+    WgCall c = wg_call("tts_hip_waveglow_infer_f16", mel, B, T, nullptr, false, WG_NOISE_Z, sigma, audio, 1, false);
+    c.z = z, c.mem = mem;
+    return waveglow_call(e, c);
 }
 
 int tts_hip_waveglow_infer_f16x3(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
                                  float* audio, int mem) {
-    return waveglow_infer_impl(e, mel, B, T, z, sigma, audio, mem, 2);
+    WgCall c = wg_call("tts_hip_waveglow_infer_f16x3", mel, B, T, nullptr, false, WG_NOISE_Z, sigma, audio, 2, false);
+    c.z = z, c.mem = mem;
+    return waveglow_call(e, c);
 }
 
 // Test hook: the gated activations of one WN layer (before the res/skip and `end` convolutions) or the flow state after one
@@ -524,21 +469,14 @@ int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, co
     // what 1: the flow's 2 * n_half channels, preceded by the early output that flows 8 and 4 append
     // what 2: the conditioning plane (bias included, gate-interleaved columns) that the Winograd form builds for the layer
     const int width = what == 0 ? 512 : what == 2 ? 1024 : e->wg.flow[flow].n_rem + (flow % 4 == 0 && flow > 0 ? 2 : 0);
-    const size_t n_mel = (size_t)B * T * 80, n_z = (size_t)B * T * 32 * 8, n_out = (size_t)B * T * 32 * width;
+    const size_t n_out = (size_t)B * T * 32 * width;
     const float* d_mel = mel;
     const float* d_z = z;
     struct Scratch : DevBuf {                                   // (DevBuf has no destructor: the engine's buffers live with the handle)
         ~Scratch() { release(); }
     } tmp;
     if (mem == TTS_HIP_MEM_HOST) {
-        HIPCHK(e, e->wg.io_mel.ensure(n_mel * 4));
-        HIPCHK(e, hipMemcpyAsync(e->wg.io_mel.p, mel, n_mel * 4, hipMemcpyHostToDevice, e->stream));
-        d_mel = e->wg.io_mel.f();
-        if (z) {
-            HIPCHK(e, e->wg.io_z.ensure(n_z * 4));
-            HIPCHK(e, hipMemcpyAsync(e->wg.io_z.p, z, n_z * 4, hipMemcpyHostToDevice, e->stream));
-            d_z = e->wg.io_z.f();
-        }
+        if (int rc = wg_stage_in(e, mel, z, B, T, &d_mel, &d_z)) return rc;
         HIPCHK(e, tmp.ensure(n_out * 4));
     }
     HIPCHK(e, e->wg.io_out.ensure((size_t)B * T * 256 * 4));      // the run's audio argument (flow 0's state)
@@ -597,119 +535,47 @@ int tts_hip_random_fill_rows(tts_hip_engine* e, int kind, const uint64_t* keys, 
 // WaveGlow.infer with the noise drawn on the device (the reference's default: z = None, deterministic = False).
 int tts_hip_waveglow_infer_seeded(tts_hip_engine* e, const float* mel, int B, int T, uint64_t seed, uint64_t offset,
                                   float sigma, float* audio, int precision, int mem) {
-    if (!e) return TTS_HIP_EINVAL;
-    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_seeded: precision must be 0 (f32), 1 (f16) or 2 (f16x3)");
-    if (B <= 0 || T <= 0 || (long long)B * T * 32 > (1ll << 30)) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_seeded: bad argument");
-    HIPCHK(e, hipSetDevice(e->device));
-    const size_t n_z = (size_t)B * T * 32 * 8;
-    HIPCHK(e, e->wg.io_zgen.ensure(n_z * 4));
-    int rc = philox_fill(e, e->wg.io_zgen.f(), (long long)n_z, seed, offset, TTS_HIP_RANDOM_NORMAL, e->stream);
-    if (rc) return rc;
-    // the generated noise is a device buffer whatever `mem` says about mel / audio
-    if (mem == TTS_HIP_MEM_DEVICE) return waveglow_infer_impl(e, mel, B, T, e->wg.io_zgen.f(), sigma, audio, mem, precision);
-    if (mem != TTS_HIP_MEM_HOST) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_seeded: bad mem kind %d", mem);
-    const size_t n_mel = (size_t)B * T * 80, n_out = (size_t)B * T * 256;
-    HIPCHK(e, e->wg.io_mel.ensure(n_mel * 4));
-    HIPCHK(e, e->wg.io_out.ensure(n_out * 4));
-    HIPCHK(e, hipMemcpyAsync(e->wg.io_mel.p, mel, n_mel * 4, hipMemcpyHostToDevice, e->stream));
-    rc = waveglow_infer_impl(e, e->wg.io_mel.f(), B, T, e->wg.io_zgen.f(), sigma, e->wg.io_out.f(), TTS_HIP_MEM_DEVICE, precision);
-    if (rc) return rc;
-    HIPCHK(e, hipMemcpyAsync(audio, e->wg.io_out.p, n_out * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return TTS_HIP_OK;
+    WgCall c = wg_call("tts_hip_waveglow_infer_seeded", mel, B, T, nullptr, false, WG_NOISE_SEED, sigma, audio, precision, false);
+    c.seed = seed, c.offset = offset, c.mem = mem;
+    return waveglow_call(e, c);
 }
 
 // Device-pointer variants on a caller stream: enqueue and return (no synchronization).  Same arithmetic as the calls above.
 int tts_hip_waveglow_infer_async(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
                                  float* audio, int precision, void* stream) {
-    return tts_hip_waveglow_infer_ragged_async(e, mel, B, T, nullptr, z, sigma, audio, precision, stream);
+    WgCall c = wg_call("tts_hip_waveglow_infer_async", mel, B, T, nullptr, false, WG_NOISE_Z, sigma, audio, precision, true);
+    c.z = z, c.stream = stream;
+    return waveglow_call(e, c);
 }
 
 // WaveGlow.infer on a batch of unequal rows: lengths[b] frames of row b are real (NULL: the calls above, launch for launch).
 int tts_hip_waveglow_infer_ragged(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths, const float* z,
                                   float sigma, float* audio, int precision, int mem) {
-    if (!e) return TTS_HIP_EINVAL;
-    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_ragged: precision must be 0 (f32), 1 (f16) or 2 (f16x3)");
-    return waveglow_infer_impl(e, mel, B, T, z, sigma, audio, mem, precision, lengths);
+    WgCall c = wg_call("tts_hip_waveglow_infer_ragged", mel, B, T, lengths, false, WG_NOISE_Z, sigma, audio, precision, false);
+    c.z = z, c.mem = mem;
+    return waveglow_call(e, c);
 }
 
 int tts_hip_waveglow_infer_ragged_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
                                         const float* z, float sigma, float* audio, int precision, void* stream) {
-    const char* who = lengths ? "waveglow_infer_ragged_async" : "waveglow_infer_async";
-    if (!e) return TTS_HIP_EINVAL;
-    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "%s: precision must be 0 (f32), 1 (f16) or 2 (f16x3)", who);
-    if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
-    if (!mel || !audio || B <= 0 || T <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", who);
-    if (T > kMaxFramesPerRun)
-        return set_err(e, TTS_HIP_EINVAL, "%s: T = %d frames exceeds one run's limit (%d); use windowed inference", who, T,
-                       kMaxFramesPerRun);
-    HIPCHK(e, hipSetDevice(e->device));
-    StreamScope scope(e, stream);
-    if (lengths) {
-        int rc = stage_ragged(e, B, T, lengths, kMaxFramesPerRun / T, who);
-        if (rc) return rc;
-    }
-    return waveglow_run_chunks(e, mel, B, T, lengths, z, sigma, audio, precision);
+    WgCall c = wg_call("tts_hip_waveglow_infer_ragged_async", mel, B, T, lengths, false, WG_NOISE_Z, sigma, audio, precision, true);
+    c.z = z, c.stream = stream;
+    return waveglow_call(e, c);
 }
 
 // WaveGlow.infer on a batch of unequal rows, computed as ONE packed row (the contract of the ragged calls above)
 int tts_hip_waveglow_infer_packed(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths, const float* z,
                                   float sigma, float* audio, int precision, int mem) {
-    if (!e) return TTS_HIP_EINVAL;
-    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_packed: precision must be 0 (f32), 1 (f16) or 2 (f16x3)");
-    if (!lengths) return set_err(e, TTS_HIP_EINVAL, "waveglow_infer_packed: lengths is NULL");
-    return waveglow_infer_impl(e, mel, B, T, z, sigma, audio, mem, precision, lengths, true);
+    WgCall c = wg_call("tts_hip_waveglow_infer_packed", mel, B, T, lengths, true, WG_NOISE_Z, sigma, audio, precision, false);
+    c.z = z, c.mem = mem;
+    return waveglow_call(e, c);
 }
 
 int tts_hip_waveglow_infer_packed_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
                                         const float* z, float sigma, float* audio, int precision, void* stream) {
-    const char* who = "waveglow_infer_packed_async";
-    if (!e) return TTS_HIP_EINVAL;
-    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "%s: precision must be 0 (f32), 1 (f16) or 2 (f16x3)", who);
-    if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
-    if (!mel || !audio || !lengths || B <= 0 || T <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", who);
-    if ((long long)B * T * 32 > (1ll << 30)) return set_err(e, TTS_HIP_EINVAL, "%s: B*T too large", who);
-    HIPCHK(e, hipSetDevice(e->device));
-    StreamScope scope(e, stream);
-    int F = 0, n_gap = 0;
-    int rc = stage_packed(e, B, T, lengths, who, &F, &n_gap);
-    if (rc) return rc;
-    return waveglow_run_packed(e, mel, B, T, z, sigma, audio, precision, (const int*)e->wg.ragged_info.p, F, n_gap);
-}
-
-// Everything a rows-seeded WaveGlow call can be refused for, checked before the noise is drawn: nothing is launched after
-// an error.  counts[b] = noise values row b needs (lengths[b] * 256, or T * 256 without lengths).
-static int check_rows_seeded(tts_hip_engine* e, const char* who, const float* mel, int B, int T, const int32_t* lengths,
-                             const uint64_t* keys, const uint64_t* offsets, const float* audio, int precision, int packed,
-                             std::vector<long long>* counts) {
-    if (precision < 0 || precision > 2) return set_err(e, TTS_HIP_EINVAL, "%s: precision must be 0 (f32), 1 (f16) or 2 (f16x3)", who);
-    if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
-    if (!keys || !offsets) return set_err(e, TTS_HIP_EINVAL, "%s: keys / offsets is NULL", who);
-    if (B <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: B = %d must be positive", who, B);
-    if (!mel || !audio || T <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", who);
-    if ((long long)B * T * 32 > (1ll << 30)) return set_err(e, TTS_HIP_EINVAL, "%s: B*T too large", who);
-    if (packed && !lengths) return set_err(e, TTS_HIP_EINVAL, "%s: packed needs lengths, got NULL", who);
-    long long F = 0;
-    int rows = 0;
-    counts->assign((size_t)B, (long long)T * 256);
-    if (lengths)
-        for (int b = 0; b < B; ++b) {
-            if (lengths[b] < 0 || lengths[b] > T)
-                return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d is outside [0, T = %d]", who, b, (int)lengths[b], T);
-            (*counts)[b] = (long long)lengths[b] * 256;
-            F += lengths[b];
-            rows += lengths[b] > 0;
-        }
-    if (packed) {
-        F += rows > 1 ? (long long)TTS_HIP_WG_GAP_FRAMES * (rows - 1) : 0;
-        if (F > kMaxFramesPerRun)
-            return set_err(e, TTS_HIP_EINVAL, "%s: the packed row holds F = %lld frames, above one run's limit (%d); split the "
-                           "batch or use the ragged call", who, F, kMaxFramesPerRun);
-    } else if (T > kMaxFramesPerRun) {
-        return set_err(e, TTS_HIP_EINVAL, "%s: T = %d frames exceeds one run's limit (%d); use windowed inference", who, T,
-                       kMaxFramesPerRun);
-    }
-    return TTS_HIP_OK;
+    WgCall c = wg_call("tts_hip_waveglow_infer_packed_async", mel, B, T, lengths, true, WG_NOISE_Z, sigma, audio, precision, true);
+    c.z = z, c.stream = stream;
+    return waveglow_call(e, c);
 }
 
 // The ragged / packed calls with row b's noise z[b, p, c] = normal element p * 8 + c of stream (keys[b], offsets[b]), drawn
@@ -717,53 +583,19 @@ static int check_rows_seeded(tts_hip_engine* e, const char* who, const float* me
 int tts_hip_waveglow_infer_rows_seeded(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
                                        const uint64_t* keys, const uint64_t* offsets, float sigma, float* audio, int precision,
                                        int packed, int mem) {
-    const char* who = "waveglow_infer_rows_seeded";
-    if (!e) return TTS_HIP_EINVAL;
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "%s: bad mem kind %d", who, mem);
-    std::vector<long long> counts;
-    int rc = check_rows_seeded(e, who, mel, B, T, lengths, keys, offsets, audio, precision, packed, &counts);
-    if (rc) return rc;
-    HIPCHK(e, hipSetDevice(e->device));
-    const size_t n_z = (size_t)B * T * 32 * 8, n_mel = (size_t)B * T * 80, n_out = (size_t)B * T * 256;
-    HIPCHK(e, e->wg.io_zgen.ensure(n_z * 4));
-    if ((rc = philox_fill_rows(e, e->wg.io_zgen.f(), B, (long long)T * 256, keys, offsets, counts.data(), TTS_HIP_RANDOM_NORMAL,
-                               e->stream)))
-        return rc;
-    // the generated noise is a device buffer whatever `mem` says about mel / audio
-    if (mem == TTS_HIP_MEM_DEVICE)
-        return waveglow_infer_impl(e, mel, B, T, e->wg.io_zgen.f(), sigma, audio, mem, precision, lengths, packed != 0);
-    HIPCHK(e, e->wg.io_mel.ensure(n_mel * 4));
-    HIPCHK(e, e->wg.io_out.ensure(n_out * 4));
-    HIPCHK(e, hipMemcpyAsync(e->wg.io_mel.p, mel, n_mel * 4, hipMemcpyHostToDevice, e->stream));
-    rc = waveglow_infer_impl(e, e->wg.io_mel.f(), B, T, e->wg.io_zgen.f(), sigma, e->wg.io_out.f(), TTS_HIP_MEM_DEVICE, precision,
-                             lengths, packed != 0);
-    if (rc) return rc;
-    HIPCHK(e, hipMemcpyAsync(audio, e->wg.io_out.p, n_out * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return TTS_HIP_OK;
+    WgCall c = wg_call("tts_hip_waveglow_infer_rows_seeded", mel, B, T, lengths, packed != 0, WG_NOISE_ROWS, sigma, audio,
+                       precision, false);
+    c.keys = keys, c.offsets = offsets, c.mem = mem;
+    return waveglow_call(e, c);
 }
 
 int tts_hip_waveglow_infer_rows_seeded_async(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths,
                                              const uint64_t* keys, const uint64_t* offsets, float sigma, float* audio,
                                              int precision, int packed, void* stream) {
-    const char* who = "waveglow_infer_rows_seeded_async";
-    if (!e) return TTS_HIP_EINVAL;
-    std::vector<long long> counts;
-    int rc = check_rows_seeded(e, who, mel, B, T, lengths, keys, offsets, audio, precision, packed, &counts);
-    if (rc) return rc;
-    HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, e->wg.io_zgen.ensure((size_t)B * T * 32 * 8 * 4));
-    StreamScope scope(e, stream);
-    if ((rc = philox_fill_rows(e, e->wg.io_zgen.f(), B, (long long)T * 256, keys, offsets, counts.data(), TTS_HIP_RANDOM_NORMAL,
-                               e->stream)))
-        return rc;
-    if (packed) {
-        int F = 0, n_gap = 0;
-        if ((rc = stage_packed(e, B, T, lengths, who, &F, &n_gap))) return rc;
-        return waveglow_run_packed(e, mel, B, T, e->wg.io_zgen.f(), sigma, audio, precision, (const int*)e->wg.ragged_info.p, F, n_gap);
-    }
-    if (lengths && (rc = stage_ragged(e, B, T, lengths, kMaxFramesPerRun / T, who))) return rc;
-    return waveglow_run_chunks(e, mel, B, T, lengths, e->wg.io_zgen.f(), sigma, audio, precision);
+    WgCall c = wg_call("tts_hip_waveglow_infer_rows_seeded_async", mel, B, T, lengths, packed != 0, WG_NOISE_ROWS, sigma, audio,
+                       precision, true);
+    c.keys = keys, c.offsets = offsets, c.stream = stream;
+    return waveglow_call(e, c);
 }
 
 int tts_hip_mel_stft_async(tts_hip_engine* e, const float* audio, int B, int N, float* mel, void* stream) {

@@ -11,11 +11,18 @@
 // of T frames, H coupling channels: a model a0p -- column c < H of row m holds 1 + 8 m + c, column H holds 1, rows of frames
 // t >= LEN[b] are zero as after the tail clearing -- goes in, one line of 16 integers per phase-major row comes out, behind a
 // first line "PR" (tests/test_wino_layer0_map.py restates it by positions).
+//        ttsw_check_asan --wg-call T PACKED CHUNKB [KEY=VALUE...] [LEN...]  -- the front end of a WaveGlow call (wg_call.h)
+// for a batch of B = number of LEN rows (no LEN: lengths NULL, B from B=) run as an entry point named "who".  CHUNKB 0:
+// rows per run as the engine derives them.  Settings: B= precision= mem= async=1 noise=0|1|2 (WgNoise) and
+// null=mel,audio,keys,offsets to pass that pointer as NULL.  First line "<status> <message>" of wg_call_check; when the call
+// is accepted: "F n_gap", then the lines "info ...", "run_tails ..." and "counts ..." of wg_call_table
+// (tests/test_wg_call.py compares them with packing_plan and a numpy restatement).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
 
 #include "ttsw_host.h"
+#include "wg_call.h"
 #include "wg_plan.h"
 
 static int print_wg_plans(int lo, int hi, int step) {
@@ -51,7 +58,55 @@ static int print_wn_taps(int h, int T, const std::vector<int>& lens) {
     return 0;
 }
 
+static int print_wg_call(int argc, char** argv) {
+    static float mel, audio;                                                   // never read: the front end only tests pointers
+    static uint64_t keys, offsets;
+    WgCall c{};
+    c.who = "who", c.mel = &mel, c.audio = &audio, c.keys = &keys, c.offsets = &offsets;
+    c.T = atoi(argv[2]), c.packed = atoi(argv[3]) != 0, c.sigma = 1.f;
+    int chunkB = atoi(argv[4]), B = -1;
+    std::vector<int32_t> lens;
+    for (int i = 5; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) {
+            lens.push_back((int32_t)atoi(argv[i]));
+            continue;
+        }
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        const int v = atoi(eq + 1);
+        if (key == "B") B = v;
+        else if (key == "precision") c.precision = v;
+        else if (key == "mem") c.mem = v;
+        else if (key == "async") c.async = v != 0;
+        else if (key == "noise") c.noise = (WgNoise)v;
+        else if (key == "null") {
+            if (strstr(eq, "mel")) c.mel = nullptr;
+            if (strstr(eq, "audio")) c.audio = nullptr;
+            if (strstr(eq, "keys")) c.keys = nullptr;
+            if (strstr(eq, "offsets")) c.offsets = nullptr;
+        } else return 2;
+    }
+    c.lengths = lens.empty() ? nullptr : lens.data();
+    c.B = lens.empty() ? B : (int)lens.size();
+    char why[512] = "";
+    const int rc = wg_call_check(c, why, sizeof why);
+    printf("%d %s\n", rc, why);
+    if (rc) return 0;
+    if (chunkB <= 0) chunkB = c.packed ? c.B : kMaxFramesPerRun / c.T;
+    WgTable t;
+    wg_call_table(c.B, c.T, c.lengths, c.packed, chunkB, &t);
+    printf("%d %d\ninfo", t.F, t.n_gap);
+    for (int v : t.info) printf(" %d", v);
+    printf("\nrun_tails");
+    for (int v : t.run_tails) printf(" %d", v);
+    printf("\ncounts");
+    for (long long v : t.counts) printf(" %lld", v);
+    printf("\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 5 && !strcmp(argv[1], "--wg-call")) return print_wg_call(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wn-taps")) {
         std::vector<int> lens;
         for (int i = 4; i < argc; ++i) lens.push_back(atoi(argv[i]));

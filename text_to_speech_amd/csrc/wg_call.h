@@ -1,0 +1,158 @@
+// wg_call.h -- what one WaveGlow call is, why it may be refused and the int table it stages: pure host code on the caller's
+// arguments (no HIP include; also built with plain g++ under ASan / UBSan by csrc/host_check.cpp, --wg-call, and compared
+// there with tests/waveglow_packed_ref.py::packing_plan and a numpy restatement, tests/test_wg_call.py).  Every
+// tts_hip_waveglow_infer* entry point fills a WgCall and hands it to waveglow_call (engine.hip).
+#pragma once
+#include <stdint.h>
+
+#include <cstdarg>
+#include <cstddef>
+#include <cstdio>
+#include <vector>
+
+#include "../../include/tts_hip.h"
+
+constexpr int kMaxFramesPerRun = 31744;             // one waveglow_run addresses its activations with 31-bit byte offsets
+constexpr long long kMaxGroups = 1ll << 30;         // B * T * 32 groups of 8 samples: what the batch buffers are indexed with
+
+enum WgNoise {
+    WG_NOISE_Z = 0,      // the caller's z (NULL: zeros, the reference's deterministic = True)
+    WG_NOISE_SEED = 1,   // drawn into wg.io_zgen from one stream (seed, offset), batch layout
+    WG_NOISE_ROWS = 2    // drawn into wg.io_zgen from one stream (keys[b], offsets[b]) per row, a row's real frames only
+};
+
+struct WgCall {
+    const char* who;                 // the entry point, as messages name it
+    const float* mel;                // [B, T, 80]
+    int B, T;
+    const int32_t* lengths;          // NULL or host int32 [B]
+    bool packed;                     // one packed row instead of runs of whole rows (needs lengths)
+    WgNoise noise;
+    const float* z;                  // WG_NOISE_Z
+    uint64_t seed, offset;           // WG_NOISE_SEED
+    const uint64_t *keys, *offsets;  // WG_NOISE_ROWS: host uint64 [B]
+    float sigma;
+    float* audio;                    // [B, T * 256]
+    int precision;                   // 0 f32, 1 f16, 2 f16x3
+    bool async;                      // false: `mem` says where mel / z / audio live, runs on the handle's stream, returns drained
+    int mem;                         // true: device pointers, enqueued on `stream` (NULL = the handle's), returns at once
+    void* stream;
+};
+
+// Frames of the packed row: the rows that hold frames one after another, TTS_HIP_WG_GAP_FRAMES gap frames between two of
+// them; rows of length 0 take no space and no gap.  (lengths already checked.)
+inline long long wg_packed_frames(int B, const int32_t* lengths, int* rows_out) {
+    long long F = 0;
+    int rows = 0;
+    for (int b = 0; b < B; ++b)
+        if (lengths[b] > 0) {
+            F += lengths[b];
+            ++rows;
+        }
+    *rows_out = rows;
+    return F + (rows > 1 ? (long long)TTS_HIP_WG_GAP_FRAMES * (rows - 1) : 0);
+}
+
+inline int wg_refuse(char* msg, size_t n, const char* who, const char* fmt, ...) {
+    const int at = snprintf(msg, n, "%s: ", who);
+    va_list ap;
+    va_start(ap, fmt);
+    if (at >= 0 && (size_t)at < n) vsnprintf(msg + at, n - (size_t)at, fmt, ap);
+    va_end(ap);
+    return TTS_HIP_EINVAL;
+}
+
+// Every reason a call is refused for what it asks (a handle without finalized weights is waveglow_call's business), first
+// match wins, in this order: precision, mem kind, keys / offsets, B, mel / audio / T, B * T, packed without lengths,
+// lengths[b], then the one-run limit (F of a packed call, T of any other).  Reads host memory only (lengths); TTS_HIP_OK or
+// TTS_HIP_EINVAL with the reason in `msg`.  Nothing is copied or launched before it has passed.
+inline int wg_call_check(const WgCall& c, char* msg, size_t n) {
+    if (c.precision < 0 || c.precision > 2)
+        return wg_refuse(msg, n, c.who, "precision must be 0 (f32), 1 (f16) or 2 (f16x3), got %d", c.precision);
+    if (!c.async && c.mem != TTS_HIP_MEM_HOST && c.mem != TTS_HIP_MEM_DEVICE)
+        return wg_refuse(msg, n, c.who, "bad mem kind %d", c.mem);
+    if (c.noise == WG_NOISE_ROWS && (!c.keys || !c.offsets)) return wg_refuse(msg, n, c.who, "keys / offsets is NULL");
+    if (c.B <= 0) return wg_refuse(msg, n, c.who, "bad argument: B = %d must be positive", c.B);
+    if (!c.mel || !c.audio || c.T <= 0) return wg_refuse(msg, n, c.who, "bad argument (mel or audio is NULL, or T = %d <= 0)", c.T);
+    if ((long long)c.B * c.T * 32 > kMaxGroups)
+        return wg_refuse(msg, n, c.who, "B*T too large (B = %d, T = %d: above 2^25 frames)", c.B, c.T);
+    if (c.packed && !c.lengths) return wg_refuse(msg, n, c.who, "packed needs lengths, got NULL");
+    if (c.lengths)
+        for (int b = 0; b < c.B; ++b)
+            if (c.lengths[b] < 0 || c.lengths[b] > c.T)
+                return wg_refuse(msg, n, c.who, "lengths[%d] = %d is outside [0, T = %d]", b, (int)c.lengths[b], c.T);
+    // One run addresses its activations with 31-bit byte offsets.  Rows are independent, so a larger batch runs in slices of
+    // whole rows, but a single row above the limit is refused (the Python wrapper's windowed inference is the answer to long
+    // mels); a packed row is ONE run: no slicing, and no silent fall-back to the ragged path.
+    if (c.packed) {
+        int rows = 0;
+        const long long F = wg_packed_frames(c.B, c.lengths, &rows);
+        if (F > kMaxFramesPerRun)
+            return wg_refuse(msg, n, c.who,
+                             "the packed row holds F = %lld frames (%d rows with frames, %d gap frames between two), above one "
+                             "run's limit (%d); split the batch or use the ragged call",
+                             F, rows, TTS_HIP_WG_GAP_FRAMES, kMaxFramesPerRun);
+    } else if (c.T > kMaxFramesPerRun) {
+        return wg_refuse(msg, n, c.who, "T = %d frames exceeds one run's limit (%d); use windowed inference", c.T,
+                         kMaxFramesPerRun);
+    }
+    return TTS_HIP_OK;
+}
+
+// What a call with lengths stages to the device, once, as one int32 table:
+//   ragged: [lengths[B] | tail frames], the tail frames (b - b0) * T + t, t >= lengths[b], listed run by run (b0 = first row
+//           of the run of chunkB rows that holds row b), so that run r finds its own run_tails[r] as one contiguous slice;
+//   packed: [start[B] | len[B] | flags[F] | gap frames[n_gap]], flags[f] = 1 + b * T + t on the packed frame that holds frame
+//           t of row b (non-zero = real, and the gather's source index), 0 on a gap frame; start of an empty row stays 0
+//           (the scatter reads nothing of such a row).
+// counts[b] = noise values row b needs (lengths[b] * 256; T * 256 without lengths, where `info` stays empty).
+struct WgTable {
+    std::vector<int> info;
+    std::vector<int> run_tails;
+    std::vector<long long> counts;
+    int F = 0, n_gap = 0;
+};
+
+// (arguments already passed wg_call_check; chunkB: rows per run, not used by a packed call)
+inline void wg_call_table(int B, int T, const int32_t* lengths, bool packed, int chunkB, WgTable* t) {
+    t->F = t->n_gap = 0;
+    t->info.clear();
+    t->run_tails.clear();
+    t->counts.assign((size_t)B, (long long)T * 256);
+    if (!lengths) return;
+    for (int b = 0; b < B; ++b) t->counts[b] = (long long)lengths[b] * 256;
+    if (packed) {
+        int rows = 0;
+        const long long F = wg_packed_frames(B, lengths, &rows);
+        const long long n_gap = rows > 1 ? (long long)TTS_HIP_WG_GAP_FRAMES * (rows - 1) : 0;
+        t->info.assign((size_t)2 * B + (size_t)F + (size_t)n_gap, 0);
+        int* start = t->info.data();
+        int* len = start + B;
+        int* flags = len + B;
+        int* gaps = flags + F;
+        int pos = 0, g = 0;
+        bool first = true;
+        for (int b = 0; b < B; ++b) {
+            len[b] = lengths[b];
+            if (lengths[b] == 0) continue;
+            if (!first)
+                for (int j = 0; j < TTS_HIP_WG_GAP_FRAMES; ++j) gaps[g++] = pos++;
+            first = false;
+            start[b] = pos;
+            for (int i = 0; i < lengths[b]; ++i) flags[pos++] = 1 + b * T + i;
+        }
+        t->F = (int)F;
+        t->n_gap = (int)n_gap;
+        return;
+    }
+    long long n_tail = 0;
+    for (int b = 0; b < B; ++b) n_tail += T - lengths[b];
+    t->info.resize((size_t)B + (size_t)n_tail);
+    t->run_tails.assign((size_t)((B + chunkB - 1) / chunkB), 0);
+    size_t at = (size_t)B;
+    for (int b = 0; b < B; ++b) {
+        t->info[b] = lengths[b];
+        t->run_tails[b / chunkB] += T - lengths[b];
+        for (int i = lengths[b]; i < T; ++i) t->info[at++] = (b % chunkB) * T + i;
+    }
+}

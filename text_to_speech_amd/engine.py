@@ -113,6 +113,27 @@ class HipEngine:
             if t is not None:
                 t.record_stream(stream)
 
+    def _staged(self, stream, prepare, *inputs):
+        """The two ways a device-tensor call is set up.  `prepare()` converts the inputs and allocates the outputs (a tuple of
+        tensors, None allowed).  stream=None: on torch's current stream, which is then drained (`_order_after_torch`) -> (tensors,
+        None); a torch stream: on that stream (`_enter_stream`), with the caller's `inputs` and the prepared tensors marked as
+        used there (`_used_on`) -> (tensors, the stream's pointer for an _async entry point)."""
+        if stream is None:
+            tensors = prepare()
+            self._order_after_torch()
+            return tensors, None
+        with self._enter_stream(stream):
+            tensors = prepare()
+        self._used_on(stream, *inputs, *tensors)
+        return tensors, ctypes.c_void_p(int(stream.cuda_stream))
+
+    @staticmethod
+    def _ptr(x):
+        """NULL, a device tensor's or a host array's address."""
+        if x is None:
+            return None
+        return ctypes.c_void_p(x.data_ptr()) if hasattr(x, 'data_ptr') else x.ctypes.data_as(ctypes.c_void_p)
+
     # ------------------------------------------------------------------ device-side sampling
     def random_normal(self, shape, seed: int, offset: int = 0, stream=None):
         """N(0, 1) float32 tensor of `shape` on this engine's GPU, drawn on the device (Philox4x32-10 + Box-Muller,
@@ -262,158 +283,79 @@ class HipEngine:
         -- the values `random_normal_rows` gives -- whatever batch the row sits in.  With `lengths` (ragged or packed) a row's
         arithmetic is its own too, so its audio is that of a one-row call with its key up to fp32 re-association; without
         `lengths` the batch is a padded one and a row still hears its padding."""
+        # 1. the arguments
         if packed and lengths is None:
             raise ValueError('packed=True needs lengths (one frame count per row)')
-        if row_seeds is not None:
-            if z is not None or seed is not None:
-                raise ValueError('row_seeds excludes z and seed')
-            return self._waveglow_infer_rows(mel, row_seeds, sigma, precision, stream, lengths, packed)
-        rag = self._lib.tts_hip_waveglow_infer_packed if packed else self._lib.tts_hip_waveglow_infer_ragged
-        rag_async = (self._lib.tts_hip_waveglow_infer_packed_async if packed
-                     else self._lib.tts_hip_waveglow_infer_ragged_async)
-        rag_name = 'waveglow_infer_packed' if packed else 'waveglow_infer_ragged'
-        fns = {'f32': self._lib.tts_hip_waveglow_infer, 'f16': self._lib.tts_hip_waveglow_infer_f16,
-               'f16x3': self._lib.tts_hip_waveglow_infer_f16x3}
-        if precision not in fns:
-            raise ValueError(f"precision must be one of {tuple(fns)}, got {precision!r}")
+        if row_seeds is not None and (z is not None or seed is not None):
+            raise ValueError('row_seeds excludes z and seed')
         if z is not None and seed is not None:
             raise ValueError('pass either z or seed, not both')
-        fn = fns[precision]
-        pcode = {'f32': 0, 'f16': 1, 'f16x3': 2}[precision]
-        u64 = lambda v: ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
-        if _is_torch_cuda(mel):
-            torch = self._torch()
-            if mel.dim() != 3 or mel.shape[2] != 80:
-                raise ValueError(f'mel must be [B, T, 80], got {tuple(mel.shape)}')
-            B, T = int(mel.shape[0]), int(mel.shape[1])
-            if z is not None and tuple(z.shape) != (B, T * 32, 8):
-                raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {tuple(z.shape)}')
-            self._check_device(mel, z)
-            lens = None if lengths is None else self._frame_lengths(lengths, B, T)
-            lens_p = None if lens is None else lens.ctypes.data_as(ctypes.c_void_p)
-
-            def prepared():
-                m = mel.to(torch.float32).contiguous()
-                zz = None if z is None else z.to(device=mel.device, dtype=torch.float32).contiguous()
-                return m, zz, torch.empty((B, T * 256), dtype=torch.float32, device=mel.device)
-
-            if stream is not None:
-                with self._enter_stream(stream):
-                    m, zz, out = prepared()
-                    if zz is None and seed is not None:
-                        zz = torch.empty((B, T * 32, 8), dtype=torch.float32, device=mel.device)
-                        self._check(self._lib.tts_hip_random_fill(self._h, 0, u64(seed), u64(offset),
-                                                                  ctypes.c_void_p(zz.data_ptr()), zz.numel(),
-                                                                  ctypes.c_void_p(int(stream.cuda_stream))), 'random_fill')
-                self._used_on(stream, mel, z, m, zz, out)
-                if lens is not None:
-                    self._check(rag_async(
-                        self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p,
-                        None if zz is None else ctypes.c_void_p(zz.data_ptr()), float(sigma), ctypes.c_void_p(out.data_ptr()),
-                        pcode, ctypes.c_void_p(int(stream.cuda_stream))), rag_name + '_async')
-                    return out
-                self._check(self._lib.tts_hip_waveglow_infer_async(
-                    self._h, ctypes.c_void_p(m.data_ptr()), B, T, None if zz is None else ctypes.c_void_p(zz.data_ptr()),
-                    float(sigma), ctypes.c_void_p(out.data_ptr()), pcode, ctypes.c_void_p(int(stream.cuda_stream))),
-                    'waveglow_infer_async')
-                return out
-            m, zz, out = prepared()
-            if lens is not None and zz is None and seed is not None:
-                zz = torch.empty((B, T * 32, 8), dtype=torch.float32, device=mel.device)
-            self._order_after_torch()
-            if lens is not None:
-                if z is None and seed is not None:       # drawn on the engine's stream, ahead of the call that reads it
-                    self._check(self._lib.tts_hip_random_fill(self._h, 0, u64(seed), u64(offset),
-                                                              ctypes.c_void_p(zz.data_ptr()), zz.numel(), None), 'random_fill')
-                self._check(rag(
-                    self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p, None if zz is None else ctypes.c_void_p(zz.data_ptr()),
-                    float(sigma), ctypes.c_void_p(out.data_ptr()), pcode, MEM_DEVICE), rag_name)
-                return out
-            if zz is None and seed is not None:
-                self._check(self._lib.tts_hip_waveglow_infer_seeded(
-                    self._h, ctypes.c_void_p(m.data_ptr()), B, T, u64(seed), u64(offset), float(sigma),
-                    ctypes.c_void_p(out.data_ptr()), pcode, MEM_DEVICE), 'waveglow_infer_seeded')
-                return out
-            self._check(fn(self._h, ctypes.c_void_p(m.data_ptr()), B, T, None if zz is None else ctypes.c_void_p(zz.data_ptr()),
-                           float(sigma), ctypes.c_void_p(out.data_ptr()), MEM_DEVICE), 'waveglow_infer')
-            return out
-        if stream is not None:
-            raise ValueError('stream= needs device tensors')
-        mel = np.ascontiguousarray(mel, dtype=np.float32)
-        if mel.ndim != 3 or mel.shape[2] != 80:
-            raise ValueError(f'mel must be [B, T, 80], got {mel.shape}')
-        B, T = mel.shape[:2]
-        lens = None if lengths is None else self._frame_lengths(lengths, B, T)
-        zp = None
-        if z is not None:
-            z = np.ascontiguousarray(z, dtype=np.float32)
-            if z.shape != (B, T * 32, 8):
-                raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {z.shape}')
-            zp = z.ctypes.data_as(ctypes.c_void_p)
-        if lens is not None and zp is None and seed is not None:
-            # the noise lives on the device: the mel joins it there (80 floats a frame against the noise's 256)
-            torch = self._torch()
-            dmel = torch.as_tensor(mel, device=torch.device('cuda', self.device))
-            return self.waveglow_infer(dmel, sigma=sigma, precision=precision, seed=seed, offset=offset,
-                                       lengths=lens, packed=packed).cpu().numpy()
-        out = np.empty((B, T * 256), dtype=np.float32)
-        if lens is not None:
-            self._check(rag(
-                self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, lens.ctypes.data_as(ctypes.c_void_p), zp, float(sigma),
-                out.ctypes.data_as(ctypes.c_void_p), pcode, MEM_HOST), rag_name)
-            return out
-        if zp is None and seed is not None:
-            self._check(self._lib.tts_hip_waveglow_infer_seeded(
-                self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, u64(seed), u64(offset), float(sigma),
-                out.ctypes.data_as(ctypes.c_void_p), pcode, MEM_HOST), 'waveglow_infer_seeded')
-            return out
-        self._check(fn(self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, zp, float(sigma),
-                       out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'waveglow_infer')
-        return out
-
-    def _waveglow_infer_rows(self, mel, row_seeds, sigma, precision, stream, lengths, packed):
-        pcodes = {'f32': 0, 'f16': 1, 'f16x3': 2}
-        if precision not in pcodes:
-            raise ValueError(f"precision must be one of {tuple(pcodes)}, got {precision!r}")
+        if precision not in self._WG_PRECISIONS:
+            raise ValueError(f"precision must be one of {tuple(self._WG_PRECISIONS)}, got {precision!r}")
         dev = _is_torch_cuda(mel)
-        if dev:
-            torch = self._torch()
-            if mel.dim() != 3 or mel.shape[2] != 80:
-                raise ValueError(f'mel must be [B, T, 80], got {tuple(mel.shape)}')
-            self._check_device(mel)
-        else:
+        if not dev:
             if stream is not None:
                 raise ValueError('stream= needs device tensors')
             mel = np.ascontiguousarray(mel, dtype=np.float32)
-            if mel.ndim != 3 or mel.shape[2] != 80:
-                raise ValueError(f'mel must be [B, T, 80], got {mel.shape}')
+            z = None if z is None else np.ascontiguousarray(z, dtype=np.float32)
+        if len(mel.shape) != 3 or mel.shape[2] != 80:
+            raise ValueError(f'mel must be [B, T, 80], got {tuple(mel.shape)}')
         B, T = int(mel.shape[0]), int(mel.shape[1])
-        keys, offsets = self._row_tables(row_seeds, B)
+        if z is not None and tuple(z.shape) != (B, T * 32, 8):
+            raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {tuple(z.shape)}')
+        self._check_device(mel, z)
         lens = None if lengths is None else self._frame_lengths(lengths, B, T)
-        lens_p = None if lens is None else lens.ctypes.data_as(ctypes.c_void_p)
-        tables = (keys.ctypes.data_as(ctypes.c_void_p), offsets.ctypes.data_as(ctypes.c_void_p))
-        if not dev:
-            out = np.empty((B, T * 256), dtype=np.float32)
-            self._check(self._lib.tts_hip_waveglow_infer_rows_seeded(
-                self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, lens_p, *tables, float(sigma),
-                out.ctypes.data_as(ctypes.c_void_p), pcodes[precision], 1 if packed else 0, MEM_HOST), 'waveglow_infer_rows_seeded')
-            return out
+        keys, offsets = (None, None) if row_seeds is None else self._row_tables(row_seeds, B)
+        # A batch seed has an entry point of its own for plain synchronous calls only; everywhere else the call is
+        # `random_fill` into a device z, then the z entry point.  Host mel with lengths: the noise lives on the device, so
+        # the mel joins it there (80 floats a frame against the noise's 256) and the audio comes back.
+        fill = seed is not None and (lens is not None or stream is not None)
+        via_device = fill and not dev
+        # 2. + 3. mel, z and the output: host arrays, or device tensors set up for `stream`
+        sp, mem = None, MEM_HOST
+        if dev or via_device:
+            torch = self._torch()
+            if via_device:
+                mel = torch.as_tensor(mel, device=torch.device('cuda', self.device))
+
+            def prepare():
+                m_ = mel.to(torch.float32).contiguous()
+                z_ = None if z is None else z.to(device=mel.device, dtype=torch.float32).contiguous()
+                if fill:
+                    z_ = torch.empty((B, T * 32, 8), dtype=torch.float32, device=mel.device)
+                return m_, z_, torch.empty((B, T * 256), dtype=torch.float32, device=mel.device)
+
+            (m, zz, out), sp = self._staged(stream, prepare, mel, z)
+            mem = MEM_DEVICE
+        else:
+            m, zz, out = mel, z, np.empty((B, T * 256), dtype=np.float32)
+        u64 = lambda v: ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
+        if fill:                                                 # on the stream of the call that reads it, ahead of it
+            self._check(self._lib.tts_hip_random_fill(self._h, 0, u64(seed), u64(offset), self._ptr(zz), zz.numel(), sp),
+                        'random_fill')
+        # 4. + 5. the entry point and its arguments: (h, mel, B, T, <rows and noise>, sigma, audio, precision, ..., mem | stream)
+        noise = 'rows' if row_seeds is not None else 'seed' if seed is not None and not fill else 'z'
+        name = self._WG_ENTRY[noise, 'packed' if packed else 'ragged' if lens is not None else 'plain']
+        pcode = (self._WG_PRECISIONS[precision],)
+        if name == 'waveglow_infer' and stream is None:          # the synchronous plain call has one symbol per precision
+            name, pcode = name + {'f32': '', 'f16': '_f16', 'f16x3': '_f16x3'}[precision], ()
+        if noise == 'rows':
+            mid, last = (self._ptr(lens), self._ptr(keys), self._ptr(offsets)), (1 if packed else 0,)
+        elif noise == 'seed':
+            mid, last = (u64(seed), u64(offset)), ()
+        else:
+            mid, last = ((self._ptr(zz),) if lens is None else (self._ptr(lens), self._ptr(zz))), ()
         if stream is not None:
-            with self._enter_stream(stream):
-                m = mel.to(torch.float32).contiguous()
-                out = torch.empty((B, T * 256), dtype=torch.float32, device=mel.device)
-            self._used_on(stream, mel, m, out)
-            self._check(self._lib.tts_hip_waveglow_infer_rows_seeded_async(
-                self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p, *tables, float(sigma), ctypes.c_void_p(out.data_ptr()),
-                pcodes[precision], 1 if packed else 0, ctypes.c_void_p(int(stream.cuda_stream))), 'waveglow_infer_rows_seeded_async')
-            return out
-        m = mel.to(torch.float32).contiguous()
-        out = torch.empty((B, T * 256), dtype=torch.float32, device=mel.device)
-        self._order_after_torch()
-        self._check(self._lib.tts_hip_waveglow_infer_rows_seeded(
-            self._h, ctypes.c_void_p(m.data_ptr()), B, T, lens_p, *tables, float(sigma), ctypes.c_void_p(out.data_ptr()),
-            pcodes[precision], 1 if packed else 0, MEM_DEVICE), 'waveglow_infer_rows_seeded')
-        return out
+            name += '_async'
+        self._check(getattr(self._lib, 'tts_hip_' + name)(
+            self._h, self._ptr(m), B, T, *mid, float(sigma), self._ptr(out), *pcode, *last, mem if stream is None else sp), name)
+        return out.cpu().numpy() if via_device else out
+
+    _WG_PRECISIONS = {'f32': 0, 'f16': 1, 'f16x3': 2}
+    # (noise, rows) -> entry point, without the tts_hip_ prefix and the _async suffix of a call on a caller's stream
+    _WG_ENTRY = {('z', 'plain'): 'waveglow_infer', ('z', 'ragged'): 'waveglow_infer_ragged', ('z', 'packed'): 'waveglow_infer_packed',
+                 ('seed', 'plain'): 'waveglow_infer_seeded', ('rows', 'plain'): 'waveglow_infer_rows_seeded',
+                 ('rows', 'ragged'): 'waveglow_infer_rows_seeded', ('rows', 'packed'): 'waveglow_infer_rows_seeded'}
 
     # ------------------------------------------------------------------ Tacotron2
     def tacotron2_infer(self, tokens, speaker=None, max_len: int = 1000, early_stopping: bool = True,
@@ -762,20 +704,10 @@ class HipEngine:
                 a_ = a_.contiguous()
                 return a_, torch.empty((int(a_.shape[0]), int(a_.shape[1]) // 256 + 1, 80), dtype=torch.float32, device=a_.device)
 
-            if stream is not None:
-                with self._enter_stream(stream):
-                    a, out = prepared()
-                self._used_on(stream, audio, a, out)
-                B, N = int(a.shape[0]), int(a.shape[1])
-                self._check(self._lib.tts_hip_mel_stft_async(self._h, ctypes.c_void_p(a.data_ptr()), B, N,
-                                                             ctypes.c_void_p(out.data_ptr()), self._order_after_torch(stream)),
-                            'mel_stft_async')
-                return out
-            a, out = prepared()
+            (a, out), sp = self._staged(stream, prepared, audio)
             B, N = int(a.shape[0]), int(a.shape[1])
-            self._order_after_torch()
-            self._check(self._lib.tts_hip_mel_stft(self._h, ctypes.c_void_p(a.data_ptr()), B, N,
-                                                   ctypes.c_void_p(out.data_ptr()), MEM_DEVICE), 'mel_stft')
+            fn, last = ('mel_stft', MEM_DEVICE) if stream is None else ('mel_stft_async', sp)
+            self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(a), B, N, self._ptr(out), last), fn)
             return out
         if stream is not None:
             raise ValueError('stream= needs device tensors')
@@ -853,19 +785,10 @@ class HipEngine:
                 n_ = noise.to(torch.float32).reshape(B, noise_len).contiguous() if noise is not None else None
                 return a_, n_, torch.empty((B, N), dtype=torch.float32, device=a_.device)
 
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-            if stream is not None:
-                with self._enter_stream(stream):
-                    a, n, out = prepared()
-                self._used_on(stream, audio, a, n, out)
-                self._check(self._lib.tts_hip_reduce_noise_async(self._h, ptr(a), B, N, lens_p, ptr(n), noise_len,
-                                                                 int(bool(renormalize)), ptr(out),
-                                                                 self._order_after_torch(stream)), 'reduce_noise_async')
-            else:
-                a, n, out = prepared()
-                self._order_after_torch()
-                self._check(self._lib.tts_hip_reduce_noise(self._h, ptr(a), B, N, lens_p, ptr(n), noise_len,
-                                                           int(bool(renormalize)), ptr(out), MEM_DEVICE), 'reduce_noise')
+            (a, n, out), sp = self._staged(stream, prepared, audio)
+            fn, last = ('reduce_noise', MEM_DEVICE) if stream is None else ('reduce_noise_async', sp)
+            self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(a), B, N, lens_p, self._ptr(n), noise_len,
+                                                            int(bool(renormalize)), self._ptr(out), last), fn)
             return out[0] if one_row else out
         if stream is not None:
             raise ValueError('stream= needs device tensors')
@@ -912,20 +835,14 @@ class HipEngine:
             self._check_device(audio)
             if rate == target_rate and lens is None:
                 return audio.to(torch.float32)
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-            if stream is not None:
-                with self._enter_stream(stream):
-                    a = audio.to(torch.float32).reshape(B, N).contiguous()
-                    out = torch.empty((B, M), dtype=torch.float32, device=a.device)
-                self._used_on(stream, audio, a, out)
-                self._check(self._lib.tts_hip_resample_async(self._h, ptr(a), B, N, lens_p, rate, target_rate, ptr(out), M,
-                                                             self._order_after_torch(stream)), 'resample_async')
-            else:
-                a = audio.to(torch.float32).reshape(B, N).contiguous()
-                out = torch.empty((B, M), dtype=torch.float32, device=a.device)
-                self._order_after_torch()
-                self._check(self._lib.tts_hip_resample(self._h, ptr(a), B, N, lens_p, rate, target_rate, ptr(out), M,
-                                                       MEM_DEVICE), 'resample')
+            def prepared():
+                a_ = audio.to(torch.float32).reshape(B, N).contiguous()
+                return a_, torch.empty((B, M), dtype=torch.float32, device=a_.device)
+
+            (a, out), sp = self._staged(stream, prepared, audio)
+            fn, last = ('resample', MEM_DEVICE) if stream is None else ('resample_async', sp)
+            self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(a), B, N, lens_p, rate, target_rate,
+                                                            self._ptr(out), M, last), fn)
             return out[0] if one_row else out
         if stream is not None:
             raise ValueError('stream= needs device tensors')
