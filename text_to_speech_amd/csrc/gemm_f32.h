@@ -12,8 +12,11 @@
 // A[i][k = lane>>5] / B[k = lane>>5][j]; lane (i, h) therefore feeds k = kb + 4h + kk for kk = 0..3 over four MFMAs.
 // The result is a k-ordered fp32 fmaf chain (bit-exact fp32, no reduced precision).
 //
-// Tile: BM x BN x 32, 256 threads (4 waves, one per SIMD), register-staged double-buffered LDS with +4-float row
-// padding (144-B rows: conflict-free ds_read_b128, MI355X_MICROARCH.md LDS table).
+// Tile: BM x BN x BK, 4 or 8 waves of 64 threads, in one of three pipelines (template parameters PIPE and HALF below):
+//   PIPE_REG        register-staged, double-buffered LDS with +4-float row padding (BK = 32: 144-B rows, conflict-free
+//                   ds_read_b128, MI355X_MICROARCH.md LDS table) -- gemm_big / gemm_small;
+//   PIPE_DMA, fp32  global -> LDS by DMA, three swizzled 64-B-row buffers, K loop rotated by half a step -- the WaveGlow layers;
+//   PIPE_DMA, fp16  the same LDS image, two or three buffers, plain loop -- the fp16 and split-fp16 modes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,31 +25,6 @@
 #include <utility>
 
 #include "dev_util.h"
-
-// Timing ablations of the fp16 loop (TTS_ABL = 1..7; results are garbage when set) only exist in a build made with
-// -DTTS_DEBUG_HOOKS -DTTS_ABL=n; csrc/build.sh never passes either.
-#ifndef TTS_DEBUG_HOOKS
-#undef TTS_ABL
-#endif
-#ifndef TTS_ABL
-#define TTS_ABL 0
-#endif
-// fp16 kernels issue v_mfma_f32_16x16x32_f16 (1) or v_mfma_f32_32x32x16_f16 (0): equal cycles per FLOP, but under load the
-// chip holds a higher clock on the 16x16x32 shape (MI355X_MICROARCH.md, DVFS item 7; measured here: DESIGN.md 4.1b).
-#ifndef TTS_H16
-#define TTS_H16 1
-#endif
-// 8-wave fp16 kernels: only waves 0-3 (one per SIMD) issue the LDS-DMA of a K step; their SIMD partners 4-7 go straight to
-// their operand reads and MFMAs.  An LDS-DMA instruction costs its wave 60-185 issue cycles (MI355X_MICROARCH.md, cycle
-// constants), four per step and wave against 512 cycles of MFMA: with every wave loading, both waves of a SIMD sit in that
-// head together after each barrier and the matrix pipe idles; with one loader per SIMD the partner's MFMAs cover it.
-#ifndef TTS_LOADER4
-#define TTS_LOADER4 1
-#endif
-// fp32 LDS-DMA kernels: K loop rotated by half a step (see "rotated loop" in the kernel).  0 = the plain loop.
-#ifndef TTS_F32_ROT
-#define TTS_F32_ROT 1
-#endif
 
 namespace ttsgemm {
 
@@ -175,12 +153,14 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned by
 // PIPE_REG: tiles are fetched into registers (two stages) and written to a padded, double-buffered LDS image.
 // PIPE_DMA: tiles are fetched straight into LDS (buffer_load ... lds, no VGPR round trip and no ds_write on the LDS
 //           pipe); the LDS image is unpadded 64-B rows, XOR-swizzled through the per-lane SOURCE address (a wave
-//           instruction writes 1 KiB linearly, cdna_hip_programming.md rule 21), triple buffered.
+//           instruction writes 1 KiB linearly, cdna_hip_programming.md rule 21), NBD buffers (fp32: always three).
 enum { PIPE_REG = 0, PIPE_DMA = 1 };
-// HALF: the operands are fp16 (v_mfma_f32_32x32x16_f16, fp32 accumulate).  Everything outside the MFMA call and the
-// epilogue stores works on 4-byte units, so an fp16 operand is described to the kernel in "float units": ld, k, kpad, ldb
-// are HALF the element counts and one 16-byte LDS fragment (4 float units) carries 8 halfs = the K = 16 slice of one
-// MFMA -- the DMA pipeline, the swizzle and the segment addressing are shared with the fp32 kernel.
+// HALF: the operands are fp16 (v_mfma_f32_16x16x32_f16, fp32 accumulate: equal cycles per FLOP to the 32x32x16 shape, but
+// under load the chip holds a higher clock on it -- MI355X_MICROARCH.md, DVFS item 7; measured here: DESIGN.md 4.1b).
+// Everything outside the MFMA call and the epilogue stores works on 4-byte units, so an fp16 operand is described to the
+// kernel in "float units": ld, k, kpad, ldb are HALF the element counts and one 16-byte LDS fragment (4 float units) carries
+// 8 halfs, a quarter of the K = 32 of one MFMA -- the DMA pipeline, the swizzle and the segment addressing are shared with
+// the fp32 kernel.
 // PL = 2 (fp16 only): every operand is a pair of fp16 planes (hi, lo) with v ~= hi + lo (22 significant bits), and a
 // product is the three MFMAs hi*hi + hi*lo + lo*hi accumulated in fp32 -- fp32-class accuracy at 3/16 of the fp32 MFMA cost.
 template <int WR, int WC, int RT, int CT, int BK, int OCC, int TAG, int NI = 0, int PIPE = PIPE_REG, bool HALF = false,
@@ -195,16 +175,22 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
     constexpr int LDSK = DMA ? BK : BK + 4; // LDS row in floats: padded (144 B / 80 B) or swizzled 64 B
     constexpr int NBUF = DMA ? NBD : 2;     // DMA: NBD - 1 tiles in flight
     constexpr int TPR = BK / 4;             // threads (float4) per tile row
-    constexpr int LW = (HALF && WR * WC == 8 && TTS_LOADER4) ? 4 : WR * WC;     // waves that stage tiles
-    constexpr int NT = LW * 64;             // staging threads: all 4 or 8 waves, or the first 4 of 8 (TTS_LOADER4)
+    // 8-wave fp16 kernels: only waves 0-3 (one per SIMD) issue the LDS-DMA of a K step; their SIMD partners 4-7 go straight to
+    // their operand reads and MFMAs.  An LDS-DMA instruction costs its wave 60-185 issue cycles (MI355X_MICROARCH.md, cycle
+    // constants), four per step and wave against 512 cycles of MFMA: with every wave loading, both waves of a SIMD sit in that
+    // head together after each barrier and the matrix pipe idles; with one loader per SIMD the partner's MFMAs cover it.
+    constexpr int LW = (HALF && WR * WC == 8) ? 4 : WR * WC;     // waves that stage tiles
+    constexpr int NT = LW * 64;             // staging threads: all 4 or 8 waves, or the first 4 of 8
     constexpr int RPP = NT / TPR;           // rows staged per pass of the staging threads
     constexpr int PA = BM / RPP;            // float4 loads per thread for the A tile
     constexpr int PB = BN / RPP;
-    // fp32 LDS-DMA kernels run the rotated K loop (below).  There a wave stages CONTIGUOUS rows -- piece p of wave w covers rows
-    // (w * PA + p) * 16 .. + 15 of the tile instead of p * 64 + w * 16 .. -- so that all pieces of one operand side share ONE
+    // fp32 LDS-DMA kernels run the rotated K loop (below); the fp16 ones run the plain DMA loop.  In the rotated loop a wave
+    // stages CONTIGUOUS rows -- piece p of wave w covers rows (w * PA + p) * 16 .. + 15 of the tile instead of
+    // p * 64 + w * 16 .. -- so that all pieces of one operand side share ONE
     // LDS base (one M0 write) and differ in the instruction's immediate offset (p KiB), which the hardware adds to the LDS
     // address AND to the buffer offset: descriptors are based ROT_SH bytes low and the per-lane offsets carry ROT_SH - p KiB.
-    constexpr bool ROT = DMA && !HALF && PL == 1 && NBD == 3 && BK == 16 && TTS_F32_ROT && (!(TTS_ABL) || TTS_ABL >= 9);
+    constexpr bool ROT = DMA && !HALF;
+    static_assert(!ROT || NBD == 3, "the rotated loop requests three LDS buffers up front");
     constexpr int ROT_SH = ROT ? 3072 : 0;
     static_assert(!ROT || (PA <= 4 && PB <= 4), "immediate offsets are 12 bits");
     static_assert(WR * WC == 4 || WR * WC == 8, "4 or 8 waves");
@@ -219,8 +205,8 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WC, wc = wave % WC;
 
-    // XCD-aware tile order: blocks b and b+8 share an XCD (round-robin dispatch), so give the 8 blocks that follow
-    // each other on one XCD the same M tile and consecutive N tiles -> the A panel is fetched into that L2 once.
+    // ---- tile order (XCD-aware): blocks b and b+8 share an XCD (round-robin dispatch), so give the 8 blocks that
+    // follow each other on one XCD the same M tile and consecutive N tiles -> the A panel is fetched into that L2 once.
     const int numNt = (g.N + BN - 1) / BN;
     const int numMt = (g.M + BM - 1) / BM;
     const int bid = blockIdx.x;
@@ -249,19 +235,18 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
 
     const int lrow = (tid & (NT - 1)) / TPR;   // row inside a staging pass (waves >= LW never stage)
     // k offset of this thread's float4.  DMA: LDS slot (row, c') receives global chunk c' ^ ((row >> 2) & 3)
-    //          (H16: c' ^ (-(row >> 2) & 3), the permutation that makes the 16-row x 4-chunk operand reads conflict-free)
-    const int c4 = DMA ? (((tid & 3) ^ ((TTS_H16 && HALF ? -(tid >> 4) : (tid >> 4)) & 3)) * 4) : (tid % TPR) * 4;
+    //          (fp16: c' ^ (-(row >> 2) & 3), the permutation that makes the 16-row x 4-chunk operand reads conflict-free)
+    const int c4 = DMA ? (((tid & 3) ^ ((HALF ? -(tid >> 4) : (tid >> 4)) & 3)) * 4) : (tid % TPR) * 4;
     // tile row that piece p of this thread stages (A / B side), and what its per-lane byte offset carries besides the address
     auto rowA = [&](int p) -> int { return ROT ? (wave * PA + p) * 16 + (lane >> 2) : p * RPP + lrow; };
     auto rowB = [&](int p) -> int { return ROT ? (wave * PB + p) * 16 + (lane >> 2) : p * RPP + lrow; };
     auto adj = [&](int p) -> unsigned { return (unsigned)(ROT_SH - (ROT ? p * 1024 : 0)); };
     const int li = lane & 31, lh = lane >> 5;
-    // Accumulator register r of a 32 x 32 tile holds (row trow(r), column tcol(r)) of the tile.  32x32 MFMA: column =
-    // lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  H16 (four 16x16x32 sub-tiles, registers 4 s .. 4 s + 3 for
+    // Accumulator register r of a 32 x 32 tile holds (row trow(r), column tcol(r)) of the tile.  fp32 (32x32 MFMA): column =
+    // lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  fp16 (four 16x16x32 sub-tiles, registers 4 s .. 4 s + 3 for
     // s = 2 ri + cj): row = 16 ri + 4 (lane >> 4) + (r & 3), column = 16 cj + (lane & 15).
-    constexpr bool H16 = HALF && TTS_H16;
-    auto trow = [&](int r) -> int { return H16 ? 16 * (r >> 3) + 4 * (lane >> 4) + (r & 3) : (r & 3) + 8 * (r >> 2) + 4 * lh; };
-    auto tcol = [&](int r) -> int { return H16 ? 16 * ((r >> 2) & 1) + (lane & 15) : li; };
+    auto trow = [&](int r) -> int { return HALF ? 16 * (r >> 3) + 4 * (lane >> 4) + (r & 3) : (r & 3) + 8 * (r >> 2) + 4 * lh; };
+    auto tcol = [&](int r) -> int { return HALF ? 16 * ((r >> 2) & 1) + (lane & 15) : li; };
 
     // ---- accumulators start from bias (+ the previous output value for read-modify-write epilogues), so the
     //      epilogue is a pure store and the old values are fetched under the first tile's load latency
@@ -273,16 +258,16 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
     float* const outp = (second ? g.out1 : g.out0) + z * g.strideOutZ;
     const long long ldo = second ? g.ld1 : g.ld0;
     const int ncol0 = second ? cbase - g.split : cbase;     // the wave's first output column on that side
-    // 32 x 32 accumulator tiles: one f32x16 per tile (32x32 MFMA), or four f32x4 sub-tiles (H16) -- separate values, so that
+    // 32 x 32 accumulator tiles: one f32x16 per tile (fp32), or four f32x4 sub-tiles (fp16) -- separate values, so that
     // the compiler never has to carry a 16-register tuple through control flow for a 4-register update
-    f32x16 acc[H16 ? 1 : RT][H16 ? 1 : CT];
-    f32x4 accq[H16 ? RT : 1][H16 ? CT : 1][4];
+    f32x16 acc[HALF ? 1 : RT][HALF ? 1 : CT];
+    f32x4 accq[HALF ? RT : 1][HALF ? CT : 1][4];
     auto A = [&](int i, int j, int r) -> float {
-        if constexpr (H16) return accq[i][j][r >> 2][r & 3];
+        if constexpr (HALF) return accq[i][j][r >> 2][r & 3];
         else return acc[i][j][r];
     };
     auto setA = [&](int i, int j, int r, float v) {
-        if constexpr (H16) accq[i][j][r >> 2][r & 3] = v;
+        if constexpr (HALF) accq[i][j][r >> 2][r & 3] = v;
         else acc[i][j][r] = v;
     };
     {
@@ -456,11 +441,6 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
 #pragma unroll
                 for (int p = 0; p < PA; ++p) {
                     bool ok = kok && ((vmaskI[p] >> si) & 1u);
-#if TTS_ABL
-                    // ablation 7: the taps of a layer with dilation >= 32 sit in the tile's own phase block -- price what ONE
-                    // shared activation tile per K chunk would save by making the outer taps' stagings fetch nothing
-                    if (HALF && TTS_ABL == 7 && g.phase_step == 1 && si != 1) ok = false;
-#endif
                     emit(true, p, rsI, ok ? baseI[p] + delta : OOB, (unsigned)(sg0.plane * 4));
                 }
                 if (++si == NI) {
@@ -493,15 +473,12 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
     };
 
     // ---- MFMA on one LDS buffer
-    auto mfma_h = [](f16x8 x, f16x8 y, f32x16 c) -> f32x16 { return __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, c, 0, 0, 0); };
     // 16x16x32: sub-tile s = 2 * ri + cj of a 32 x 32 accumulator tile
     auto mfma_q = [](f16x8 x, f16x8 y, f32x4& c) { c = __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0); };
-    const int xr = (li >> 2) & 3;                    // DMA image: chunk XOR of this lane's operand rows
     auto compute_chunk = [&](int buf, int k8) {
-        if constexpr (H16) {
-            // one call covers the whole 64-byte stage (K = 32 halfs): lane (row q = lane & 15, chunk c = lane >> 4) of a
-            // 16-row operand block reads logical chunk c of its row, stored at slot c ^ (-(q >> 2) & 3)
-            if (k8 != 0) return;
+        if constexpr (HALF) {
+            // fp16: one call (k8 = 0) covers the whole 64-byte stage (K = 32 halfs).  Lane (row q = lane & 15, chunk c = lane >> 4)
+            // of a 16-row operand block reads logical chunk c of its row, stored at slot c ^ (-(q >> 2) & 3)
             const int q16 = lane & 15;
             const int ko = (((lane >> 4) ^ (-(q16 >> 2))) & 3) * 4;
             const float* a = As + buf * PL * BM * LDSK + (wr * RT * 32 + q16) * LDSK + ko;
@@ -548,80 +525,28 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
                         mfma_q(__builtin_bit_cast(f16x8, fa[i][sidx >> 1]), __builtin_bit_cast(f16x8, fb[j][sidx & 1]), accq[i][j][sidx]);
             return;
         }
-        const int koff = DMA ? (((2 * k8 + lh) ^ xr) * 4) : (lh * 4 + k8 * 8);
-        const float* a = As + buf * PL * BM * LDSK + (wr * RT * 32 + li) * LDSK + koff;
-        const float* b = Bs + buf * PL * BN * LDSK + (wc * CT * 32 + li) * LDSK + koff;
-        if constexpr (PL == 2) {
-            f32x4 fa[RT], fal[RT], fb[CT], fbl[CT];
-#pragma unroll
-            for (int i = 0; i < RT; ++i) {
-                fa[i] = *reinterpret_cast<const f32x4*>(a + i * 32 * LDSK);
-                fal[i] = *reinterpret_cast<const f32x4*>(a + (BM + i * 32) * LDSK);
-            }
-#pragma unroll
-            for (int j = 0; j < CT; ++j) {
-                fb[j] = *reinterpret_cast<const f32x4*>(b + j * 32 * LDSK);
-                fbl[j] = *reinterpret_cast<const f32x4*>(b + (BN + j * 32) * LDSK);
-            }
-            // hi*lo and lo*hi first, hi*hi last: the small terms are added before the large one lands in the fp32 sum
-#pragma unroll
-            for (int i = 0; i < RT; ++i)
-#pragma unroll
-                for (int j = 0; j < CT; ++j) {
-                    acc[i][j] = mfma_h(__builtin_bit_cast(f16x8, fal[i]), __builtin_bit_cast(f16x8, fb[j]), acc[i][j]);
-                    acc[i][j] = mfma_h(__builtin_bit_cast(f16x8, fa[i]), __builtin_bit_cast(f16x8, fbl[j]), acc[i][j]);
-                    acc[i][j] = mfma_h(__builtin_bit_cast(f16x8, fa[i]), __builtin_bit_cast(f16x8, fb[j]), acc[i][j]);
-                }
-            return;
-        }
+        // fp32, PIPE_REG image (the rotated loop reads its operands itself): lane (i, h) reads k = 8 k8 + 4 h .. + 3
+        const int koff = lh * 4 + k8 * 8;
+        const float* a = As + buf * BM * LDSK + (wr * RT * 32 + li) * LDSK + koff;
+        const float* b = Bs + buf * BN * LDSK + (wc * CT * 32 + li) * LDSK + koff;
         f32x4 fa[RT], fb[CT];
-#if TTS_ABL == 8 && defined(TTS_ABL_F32)
-        if (!HALF) {                                 // ablation 8: the MFMAs of a K step without their operand reads
 #pragma unroll
-            for (int i = 0; i < RT; ++i) fa[i] = f32x4{1.f, 2.f, 3.f, 4.f} * (float)(lane + i);
-#pragma unroll
-            for (int j = 0; j < CT; ++j) fb[j] = f32x4{1.f, 2.f, 3.f, 4.f} * (float)(lane - j);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int i = 0; i < RT; ++i)
-#pragma unroll
-                    for (int j = 0; j < CT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][kk], fb[j][kk], acc[i][j], 0, 0, 0);
-            return;
-        }
-#endif
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-#if TTS_ABL
-            if (HALF && (TTS_ABL == 5 || TTS_ABL == 6)) { fa[i] = f32x4{1.f, 2.f, 3.f, 4.f} * (float)(i + k8); continue; }   // ablation: no A-side LDS reads
-#endif
-            fa[i] = *reinterpret_cast<const f32x4*>(a + i * 32 * LDSK);
-        }
+        for (int i = 0; i < RT; ++i) fa[i] = *reinterpret_cast<const f32x4*>(a + i * 32 * LDSK);
 #pragma unroll
         for (int j = 0; j < CT; ++j) fb[j] = *reinterpret_cast<const f32x4*>(b + j * 32 * LDSK);
-        if constexpr (HALF) {
-            // lane (row, h) holds k = 8h .. 8h+7 of this 16-wide K slice: exactly the 32x32x16 f16 operand layout
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
             for (int i = 0; i < RT; ++i)
 #pragma unroll
                 for (int j = 0; j < CT; ++j)
-                    acc[i][j] = mfma_h(__builtin_bit_cast(f16x8, fa[i]), __builtin_bit_cast(f16x8, fb[j]), acc[i][j]);
-        } else {
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int i = 0; i < RT; ++i)
-#pragma unroll
-                    for (int j = 0; j < CT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][kk], fb[j][kk], acc[i][j], 0, 0, 0);
-        }
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][kk], fb[j][kk], acc[i][j], 0, 0, 0);
     };
 
     if (nSeq > 0) enter_segment();
     if constexpr (ROT) {
-        // ---- rotated loop (fp32 LDS-DMA kernels).  Measured on the plain loop below (config 2, 5.69 ms per launch, debug
-        // builds with -DTTS_ABL_F32): without the DMA issue 5.19 ms, without the operand reads 5.54, without wait + barrier 5.60,
+        // ---- rotated loop (fp32 LDS-DMA kernels).  Measured on the plain loop below, which these kernels ran before (config 2,
+        // 5.69 ms per launch; ablation builds): without the DMA issue 5.19 ms, without the operand reads 5.54, without wait + barrier 5.60,
         // DMA + barrier alone 1.22 -- a wave issued its 6 DMA pieces, then its operand reads, and only then had MFMAs to offer.
         // Here the step boundary sits in the MIDDLE of a tile's MFMAs: a step = [reads of chunk 1 | MFMAs of chunk 0 | wait +
         // barrier | reads of the NEXT tile's chunk 0 | MFMAs of chunk 1 with the DMA pieces of tile t + 3 issued one per MFMA row
@@ -688,6 +613,7 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsTb, (lds_ptr_t)dst, 16, voff, 0, (q - PA) * 1024, 0);
             }
         };
+        const int xr = (li >> 2) & 3;                    // DMA image: chunk XOR of this lane's operand rows
         auto read_ops = [&](int bufr, int k8, f32x4 (&fa)[RT], f32x4 (&fb)[CT]) {
             const int koff = ((2 * k8 + lh) ^ xr) * 4;
             const float* a = As + bufr * BM * LDSK + (wr * RT * 32 + li) * LDSK + koff;
@@ -731,7 +657,7 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
                 constexpr int grp = decltype(gc)::value;
                 mfma_row(fa1, fb1, grp / RT, grp % RT);
                 if constexpr (grp < LT) {
-                    if (TTS_ABL != 10) issue_piece(gc, buf);     // (ablation 10: the rotated loop without its DMA issue)
+                    issue_piece(gc, buf);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             });
@@ -741,22 +667,16 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
         // the last three steps issued fetch-nothing pieces: they must have written their zeros before the epilogue reuses LDS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else if constexpr (DMA) {
-        // NBUF (3 or 4) LDS buffers.  Step t: issue tile t+NBUF-1's DMA into the buffer read at step t-1 (every wave has
-        // passed the barrier that ended that step), run tile t's MFMAs, then wait until all but the newest NBUF-2 tiles'
-        // DMA have landed (counted vmcnt: tile t+1 is in LDS) and barrier.  No VGPR staging, no ds_write.
-#if TTS_ABL
-        constexpr int LT = PL * ((HALF && (TTS_ABL == 4 || TTS_ABL == 6)) ? PB : PA + PB);
-#else
+        // ---- plain DMA loop (fp16 kernels): NBUF (2 or 3) LDS buffers.  Step t: issue tile t+NBUF-1's DMA into the buffer
+        // read at step t-1 (every wave has passed the barrier that ended that step), run tile t's MFMAs, then wait until all
+        // but the newest NBUF-2 tiles' DMA have landed (counted vmcnt: tile t+1 is in LDS) and barrier.  No VGPR staging, no
+        // ds_write.
         constexpr int LT = PL * (PA + PB);           // DMA instructions per tile per wave
-#endif
         typedef __attribute__((address_space(3))) void* lds_ptr_t;
         auto dma_tile = [&](int buf) {
             fetch_next([&](bool isA, int p, const __amdgpu_buffer_rsrc_t& rs, unsigned voff, unsigned pofs) {
                 // wave-uniform LDS base of this instruction's 16 rows; lane l lands at base + 16 * l
                 float* dst = (isA ? As + buf * PL * BM * LDSK : Bs + buf * PL * BN * LDSK) + (p * RPP + wave * 16) * LDSK;
-#if TTS_ABL
-                if (HALF && (TTS_ABL == 4 || TTS_ABL == 6) && isA) return;       // ablation: no A-side DMA
-#endif
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)dst, 16, voff, 0, 0, 0);
                 if constexpr (PL == 2) {             // the "lo" plane: same rows, second LDS image
                     float* dst2 = dst + (isA ? BM : BN) * LDSK;
@@ -776,30 +696,21 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         int buf = 0, bufn = NBUF - 1;                // buffer of tile t, buffer for tile t + NBUF - 1
-#ifdef TTS_ABL_F32
-        constexpr int ABL = TTS_ABL;                 // measurement builds: the same ablations on the fp32 loop
-#else
-        constexpr int ABL = HALF ? TTS_ABL : 0;      // timing ablations of the fp16 loop (results are garbage when != 0)
-#endif
         for (int t = 0; t < nAll; ++t) {
-            if (ABL != 2 && loader) dma_tile(bufn);
-            if (ABL != 3) {
-#pragma unroll
-                for (int k8 = 0; k8 < BK / 8; ++k8) compute_chunk(buf, k8);
-            }
-            if (ABL != 1) {
-                // tile t + 1 must have landed: tiles t + 2 .. t + NBUF - 1 may stay in flight while they all exist
-                if (t + NBUF - 1 < nAll) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * LT) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
+            if (loader) dma_tile(bufn);
+            compute_chunk(buf, 0);
+            // tile t + 1 must have landed: tiles t + 2 .. t + NBUF - 1 may stay in flight while they all exist
+            if (t + NBUF - 1 < nAll) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * LT) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
             buf = buf == NBUF - 1 ? 0 : buf + 1;
             bufn = bufn == NBUF - 1 ? 0 : bufn + 1;
         }
     } else {
-        // Two register stages: tile t+1 waits in one while tile t+2 is being fetched into the other (prefetch distance
-        // of two K steps).  Step t on LDS buffer `buf`: fetch tile t+2 into the free stage, run all but the last
-        // quarter of the MFMAs of tile t, write tile t+1 to the other LDS buffer, finish the MFMAs, barrier.
+        // ---- register-staged loop (PIPE_REG, fp32).  Two register stages: tile t+1 waits in one while tile t+2 is being
+        // fetched into the other (prefetch distance of two K steps).  Step t on LDS buffer `buf`: fetch tile t+2 into the
+        // free stage, run all but the last quarter of the MFMAs of tile t, write tile t+1 to the other LDS buffer, finish the
+        // MFMAs, barrier.
         f32x4 ra0[PA], rb0[PB], ra1[PA], rb1[PB];
         auto load_next = [&](f32x4 (&ra)[PA], f32x4 (&rb)[PB]) {
             fetch_next([&](bool isA, int p, const __amdgpu_buffer_rsrc_t& rs, unsigned voff, unsigned) {
@@ -834,7 +745,7 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
         }
     }
 
-    // ---------------- epilogue ----------------
+    // ---------------- epilogue: gate (EPI_GATE), wide transpose (wide_epi) or scalar ----------------
     // C/D map of a 32 x 32 tile: trow(r) / tcol(r) (defined with the accumulators above)
     if constexpr (CT % 2 == 0) {
         if (g.mode == EPI_GATE) {
@@ -914,21 +825,10 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
             float* patch = smem + wave * (32 * 36);
             const int prow = lane >> 3, pc4 = (lane & 7) * 4;
             bool accum = second ? g.acc1 : g.acc0;
-#if TTS_ABL == 11 || TTS_ABL == 12
-            // ablations 11 / 12 (timing only): the fp16 residual launch without the fp32 master of x -- 11: no read, no fp32 store
-            // (what an fp16-only residual stream would move); 12: the master as an fp16 (hi, lo) pair (4 B in, 4 B out, no shadow)
-            constexpr bool kNoMaster = HALF && TTS_ABL == 11, kPairMaster = HALF && TTS_ABL == 12;
-            if (kNoMaster) accum = false;
-#else
-            constexpr bool kNoMaster = false, kPairMaster = false;
-#endif
             // read-modify-write: in the HBM-bound fp16 residual launch the old values of ALL this wave's tiles are requested up
             // front (tile by tile they are RT x CT dependent HBM latencies per block): 290 -> 263 - 273 us.  Not in the fp32 and
             // split-fp16 kernels, which are MFMA-bound and lose 1.5 % / gain nothing with 64 more live registers in the epilogue.
-#ifndef TTS_EPI_PREFETCH
-#define TTS_EPI_PREFETCH 1
-#endif
-            constexpr bool kPrefetch = TTS_EPI_PREFETCH && HALF && PL == 1 && RT * CT <= 4;
+            constexpr bool kPrefetch = HALF && PL == 1 && RT * CT <= 4;
             f32x4 oldall[kPrefetch ? RT * CT : 1][4];
             if (kPrefetch && accum) {
 #pragma unroll
@@ -964,18 +864,8 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
 #pragma unroll
                         for (int k = 0; k < 4; ++k) v[k] = act_apply(v[k], g.act);
                         const long long mrow = mrow0 + prow + 8 * q;
-                        if (!kNoMaster && !kPairMaster) *reinterpret_cast<f32x4*>(outp + mrow * ldo + ncol) = v;
+                        *reinterpret_cast<f32x4*>(outp + mrow * ldo + ncol) = v;
                         if constexpr (HALF) {
-                            if (kPairMaster) {                   // (hi, lo) pair written into the fp32 master's bytes: 4 B per element
-                                typedef _Float16 f16x4p __attribute__((ext_vector_type(4)));
-                                const f16x4p hv = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-                                const f16x4p lv = {(_Float16)(v[0] - (float)hv[0]), (_Float16)(v[1] - (float)hv[1]),
-                                                   (_Float16)(v[2] - (float)hv[2]), (_Float16)(v[3] - (float)hv[3])};
-                                _Float16* mp = reinterpret_cast<_Float16*>(outp + mrow * ldo + ncol);
-                                *reinterpret_cast<f16x4p*>(mp) = hv;
-                                *reinterpret_cast<f16x4p*>(mp + 4) = lv;
-                                continue;
-                            }
                             if (g.out0h && !second) {
                                 typedef _Float16 f16x4e __attribute__((ext_vector_type(4)));
                                 const f16x4e hv = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
@@ -1066,96 +956,79 @@ inline hipError_t launch_gemm(const GemmArgs& g, int batch_z, hipStream_t stream
 
 // Tile configurations: BIG = 256x128 (WN layers, upsampling); SMALL = 64x64 (Tacotron2-sized problems).
 enum { TAG_GENERIC = 0, TAG_WN_IN = 1, TAG_WN_RES_SKIP = 2, TAG_WN_IN0 = 3, TAG_WN_WINO = 4 };
-#ifndef TTS_WN_BK
-#define TTS_WN_BK 16
-#define TTS_WN_OCC 2
-#endif
-#ifndef TTS_WN_RT
-#define TTS_WN_WR 4      // 4 x 1 waves, each RT x 4 tiles of 32x32: block tile (128 * RT) x 128
-#define TTS_WN_RT 2
-#endif
-#ifndef TTS_WN_PIPE
-#define TTS_WN_PIPE PIPE_DMA
-#endif
+// Settled choices of the WaveGlow tiles (each was a build option until its measurement was in):
+constexpr int WN_BK = 16;           // K extent of an LDS stage (the LDS-DMA image is 64-byte rows)
+constexpr int WN_OCC = 2;
+constexpr int WN_WR = 4;            // 4 x 1 waves, each RT x 4 tiles of 32x32: block tile (128 * RT) x 128
+constexpr int WN_RT = 2;
+constexpr int WN_PIPE = PIPE_DMA;
+constexpr int WN_RES_RT = 1;        // residual GEMM (N = 512): 128-row tiles -> 6400 blocks, fills the 512 block slots more evenly
+constexpr int WN_RES_OCC = 3;
+constexpr int H_NBUF = 3;           // LDS buffers of the fp16 in-layer GEMM (4 = three tiles in flight was measured no faster:
+                                    // 898 vs 855-885 us)
+constexpr int H_WC = 2;             // fp16 in-layer GEMM: 8 waves, 256 x 256 block tile (the fp16 loop is bound by L2 -> LDS traffic)
+constexpr int HRES_WC = 1;          // fp16 residual GEMM: 4 x 1 waves, 128 x 128 tiles, three blocks per CU
+constexpr int HRES_RT = 1;
+constexpr int HRES_OCC = 3;
 inline hipError_t gemm_big(const GemmArgs& g, int bz, hipStream_t s) { return launch_gemm<4, 1, 2, 4, 32, 1, TAG_GENERIC>(g, bz, s); }
 // WN in-layer GEMM: the three conv taps are interleaved in K (weights packed to match, see pack_bt_kernel)
 constexpr int WN_TAPS = 3;
-inline hipError_t gemm_wn_in(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, TTS_WN_RT, 4, TTS_WN_BK, TTS_WN_OCC, TAG_WN_IN, WN_TAPS, TTS_WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_in(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, WN_RT, 4, WN_BK, WN_OCC, TAG_WN_IN, WN_TAPS, WN_PIPE>(g, 1, s); }
 // 128-row-tile variants: used when padding the phase blocks to 256 rows would waste more work (e.g. batch 1)
-inline hipError_t gemm_wn_in_128(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, 1, 4, TTS_WN_BK, 3, TAG_WN_IN, WN_TAPS, TTS_WN_PIPE>(g, 1, s); }
-inline hipError_t gemm_wn_in0_128(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, 1, 4, TTS_WN_BK, 3, TAG_WN_IN0, WN_TAPS, TTS_WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_in_128(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, 1, 4, WN_BK, 3, TAG_WN_IN, WN_TAPS, WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_in0_128(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, 1, 4, WN_BK, 3, TAG_WN_IN0, WN_TAPS, WN_PIPE>(g, 1, s); }
 // 128 x 64 tiles for short utterances (a few hundred frames at batch 1): twice the blocks, so that every CU gets work
-inline hipError_t gemm_wn_in_64(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, 1, 2, TTS_WN_BK, 4, TAG_WN_IN, WN_TAPS, TTS_WN_PIPE>(g, 1, s); }
-inline hipError_t gemm_wn_in0_64(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, 1, 2, TTS_WN_BK, 4, TAG_WN_IN0, WN_TAPS, TTS_WN_PIPE>(g, 1, s); }
-inline hipError_t gemm_wn_res_64(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, 1, 2, TTS_WN_BK, 4, TAG_WN_RES_SKIP, 0, TTS_WN_PIPE>(g, 1, s); }
-inline hipError_t gemm_wn_in_64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, 1, 2, TTS_WN_BK, 4, TAG_WN_IN, WN_TAPS, PIPE_DMA, true>(g, 1, s); }
-inline hipError_t gemm_wn_in0_64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, 1, 2, TTS_WN_BK, 4, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true>(g, 1, s); }
-inline hipError_t gemm_wn_res_64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, 1, 2, TTS_WN_BK, 4, TAG_WN_RES_SKIP, 0, PIPE_DMA, true>(g, 1, s); }
+inline hipError_t gemm_wn_in_64(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, 1, 2, WN_BK, 4, TAG_WN_IN, WN_TAPS, WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_in0_64(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, 1, 2, WN_BK, 4, TAG_WN_IN0, WN_TAPS, WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_res_64(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, 1, 2, WN_BK, 4, TAG_WN_RES_SKIP, 0, WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_in_64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, 1, 2, WN_BK, 4, TAG_WN_IN, WN_TAPS, PIPE_DMA, true>(g, 1, s); }
+inline hipError_t gemm_wn_in0_64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, 1, 2, WN_BK, 4, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true>(g, 1, s); }
+inline hipError_t gemm_wn_res_64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, 1, 2, WN_BK, 4, TAG_WN_RES_SKIP, 0, PIPE_DMA, true>(g, 1, s); }
 // 64 x 128 tiles (2 x 2 waves): phase blocks are padded to the M tile, so short utterances waste up to BM - 1 frames per
 // phase; 64-row tiles halve that padding (e.g. 170 frames: 192 rows per phase instead of 256)
-inline hipError_t gemm_wn_in_r64(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, TTS_WN_BK, 4, TAG_WN_IN, WN_TAPS, TTS_WN_PIPE>(g, 1, s); }
-inline hipError_t gemm_wn_in0_r64(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, TTS_WN_BK, 4, TAG_WN_IN0, WN_TAPS, TTS_WN_PIPE>(g, 1, s); }
-inline hipError_t gemm_wn_res_r64(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, TTS_WN_BK, 4, TAG_WN_RES_SKIP, 0, TTS_WN_PIPE>(g, 1, s); }
-inline hipError_t gemm_wn_in_r64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, TTS_WN_BK, 4, TAG_WN_IN, WN_TAPS, PIPE_DMA, true>(g, 1, s); }
-inline hipError_t gemm_wn_in0_r64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, TTS_WN_BK, 4, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true>(g, 1, s); }
-inline hipError_t gemm_wn_res_r64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, TTS_WN_BK, 4, TAG_WN_RES_SKIP, 0, PIPE_DMA, true>(g, 1, s); }
+inline hipError_t gemm_wn_in_r64(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, WN_BK, 4, TAG_WN_IN, WN_TAPS, WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_in0_r64(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, WN_BK, 4, TAG_WN_IN0, WN_TAPS, WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_res_r64(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, WN_BK, 4, TAG_WN_RES_SKIP, 0, WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_in_r64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, WN_BK, 4, TAG_WN_IN, WN_TAPS, PIPE_DMA, true>(g, 1, s); }
+inline hipError_t gemm_wn_in0_r64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, WN_BK, 4, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true>(g, 1, s); }
+inline hipError_t gemm_wn_res_r64h(const GemmArgs& g, hipStream_t s) { return launch_gemm<2, 2, 1, 2, WN_BK, 4, TAG_WN_RES_SKIP, 0, PIPE_DMA, true>(g, 1, s); }
 // split-fp16 variants (two fp16 planes per operand, three MFMAs per product), 8 waves.  In-layer GEMM: 256 x 256 block tile
 // with TWO LDS buffers (131 KB; a K step carries 3x the MFMA work of the fp16 kernel, so one tile of prefetch covers the
 // latency: 2 142 us vs 2 429 us for 256 x 128 tiles with three buffers); 64 x 128 tiles for short utterances.
 inline hipError_t gemm_wn_in_x3(const GemmArgs& g, bool small, hipStream_t s) {
-    return small ? launch_gemm<2, 2, 1, 2, TTS_WN_BK, 2, TAG_WN_IN, WN_TAPS, PIPE_DMA, true, 3, 2>(g, 1, s)
-                 : launch_gemm<4, 2, 2, 4, TTS_WN_BK, 1, TAG_WN_IN, WN_TAPS, PIPE_DMA, true, 2, 2>(g, 1, s);
+    return small ? launch_gemm<2, 2, 1, 2, WN_BK, 2, TAG_WN_IN, WN_TAPS, PIPE_DMA, true, 3, 2>(g, 1, s)
+                 : launch_gemm<4, 2, 2, 4, WN_BK, 1, TAG_WN_IN, WN_TAPS, PIPE_DMA, true, 2, 2>(g, 1, s);
 }
-#ifndef TTS_X3_VAR
-#define TTS_X3_VAR 1   // bit 0: 256 x 256 tiles for the first layer of a flow (613 vs 690 us)
-#endif
+// (first layer of a flow: 256 x 256 tiles too, 613 us vs 690 us with 256 x 128 tiles and three buffers)
 inline hipError_t gemm_wn_in0_x3(const GemmArgs& g, bool small, hipStream_t s) {
-    if (!small && (TTS_X3_VAR & 1)) return launch_gemm<4, 2, 2, 4, TTS_WN_BK, 1, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true, 2, 2>(g, 1, s);
-    return small ? launch_gemm<2, 2, 1, 2, TTS_WN_BK, 2, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true, 3, 2>(g, 1, s)
-                 : launch_gemm<4, 2, 2, 2, TTS_WN_BK, 1, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true, 3, 2>(g, 1, s);
+    return small ? launch_gemm<2, 2, 1, 2, WN_BK, 2, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true, 3, 2>(g, 1, s)
+                 : launch_gemm<4, 2, 2, 4, WN_BK, 1, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true, 2, 2>(g, 1, s);
 }
 // residual GEMM (K = 512: short main loop, heavy read-modify-write epilogue): 128 x 128 tiles, 4 waves, two LDS buffers =
 // 64 KB, so two blocks share a CU and one block's epilogue overlaps the other's loop (494 us; 540-570 us with one
 // 256 x 128 block per CU, 584 us with 64 x 128 tiles)
 inline hipError_t gemm_wn_res_x3(const GemmArgs& g, bool small, hipStream_t s) {
-    return small ? launch_gemm<2, 2, 1, 2, TTS_WN_BK, 2, TAG_WN_RES_SKIP, 0, PIPE_DMA, true, 3, 2>(g, 1, s)
-                 : launch_gemm<2, 2, 2, 2, TTS_WN_BK, 2, TAG_WN_RES_SKIP, 0, PIPE_DMA, true, 2, 2>(g, 1, s);
+    return small ? launch_gemm<2, 2, 1, 2, WN_BK, 2, TAG_WN_RES_SKIP, 0, PIPE_DMA, true, 3, 2>(g, 1, s)
+                 : launch_gemm<2, 2, 2, 2, WN_BK, 2, TAG_WN_RES_SKIP, 0, PIPE_DMA, true, 2, 2>(g, 1, s);
 }
 // fp16-operand variants (activations and weights fp16 in HBM, fp32 accumulate): same tiles and pipeline
-#ifndef TTS_H_NBUF
-#define TTS_H_NBUF 3   // LDS buffers of that kernel (4 = three tiles in flight was measured no faster: 898 vs 855-885 us)
-#endif
-#ifndef TTS_H_WC
-#define TTS_H_WC 2     // fp16 in-layer GEMM: 8 waves, 256 x 256 block tile (the fp16 loop is bound by L2 -> LDS traffic)
-#endif
 inline hipError_t gemm_wn_in_h(const GemmArgs& g, bool t128, hipStream_t s) {
-    if (!t128 && TTS_H_WC == 2)
-        return launch_gemm<TTS_WN_WR, 2, TTS_WN_RT, 4, TTS_WN_BK, 1, TAG_WN_IN, WN_TAPS, PIPE_DMA, true, TTS_H_NBUF>(g, 1, s);
-    return t128 ? launch_gemm<TTS_WN_WR, 1, 1, 4, TTS_WN_BK, 3, TAG_WN_IN, WN_TAPS, PIPE_DMA, true>(g, 1, s)
-                : launch_gemm<TTS_WN_WR, 1, TTS_WN_RT, 4, TTS_WN_BK, TTS_WN_OCC, TAG_WN_IN, WN_TAPS, PIPE_DMA, true>(g, 1, s);
+    return t128 ? launch_gemm<WN_WR, 1, 1, 4, WN_BK, 3, TAG_WN_IN, WN_TAPS, PIPE_DMA, true>(g, 1, s)
+                : launch_gemm<WN_WR, H_WC, WN_RT, 4, WN_BK, 1, TAG_WN_IN, WN_TAPS, PIPE_DMA, true, H_NBUF>(g, 1, s);
 }
 inline hipError_t gemm_wn_in0_h(const GemmArgs& g, bool t128, hipStream_t s) {
-    return t128 ? launch_gemm<TTS_WN_WR, 1, 1, 4, TTS_WN_BK, 3, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true>(g, 1, s)
-                : launch_gemm<TTS_WN_WR, 1, TTS_WN_RT, 4, TTS_WN_BK, TTS_WN_OCC, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true>(g, 1, s);
+    return t128 ? launch_gemm<WN_WR, 1, 1, 4, WN_BK, 3, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true>(g, 1, s)
+                : launch_gemm<WN_WR, 1, WN_RT, 4, WN_BK, WN_OCC, TAG_WN_IN0, WN_TAPS, PIPE_DMA, true>(g, 1, s);
 }
-#ifndef TTS_HRES_WC
-#define TTS_HRES_WC 1
-#define TTS_HRES_RT 1
-#define TTS_HRES_OCC 3
-#endif
 inline hipError_t gemm_wn_res_h(const GemmArgs& g, hipStream_t s) {
-    return launch_gemm<TTS_WN_WR, TTS_HRES_WC, TTS_HRES_RT, 4, TTS_WN_BK, TTS_HRES_OCC, TAG_WN_RES_SKIP, 0, PIPE_DMA, true>(g, 1, s);
+    return launch_gemm<WN_WR, HRES_WC, HRES_RT, 4, WN_BK, HRES_OCC, TAG_WN_RES_SKIP, 0, PIPE_DMA, true>(g, 1, s);
 }
 // first layer of a flow (start conv composed into the taps: K = 48 + 320); own TAG so profiles list it separately
-inline hipError_t gemm_wn_in0(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, TTS_WN_RT, 4, TTS_WN_BK, TTS_WN_OCC, TAG_WN_IN0, WN_TAPS, TTS_WN_PIPE>(g, 1, s); }
-#ifndef TTS_WN_RES_RT
-#define TTS_WN_RES_RT 1   // residual GEMM (N = 512): 128-row tiles -> 6400 blocks, fills the 512 block slots more evenly
-#define TTS_WN_RES_OCC 3
-#endif
-inline hipError_t gemm_wn_res_skip(const GemmArgs& g, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, TTS_WN_RES_RT, 4, TTS_WN_BK, TTS_WN_RES_OCC, TAG_WN_RES_SKIP, 0, TTS_WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_in0(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, WN_RT, 4, WN_BK, WN_OCC, TAG_WN_IN0, WN_TAPS, WN_PIPE>(g, 1, s); }
+inline hipError_t gemm_wn_res_skip(const GemmArgs& g, hipStream_t s) { return launch_gemm<WN_WR, 1, WN_RES_RT, 4, WN_BK, WN_RES_OCC, TAG_WN_RES_SKIP, 0, WN_PIPE>(g, 1, s); }
 // Winograd form of the in-layer GEMM (wn_wino.hip): four z slices (one per product) on pair rows, K = 512 + 160 each
-inline hipError_t gemm_wn_wino(const GemmArgs& g, int nz, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, TTS_WN_RT, 4, TTS_WN_BK, TTS_WN_OCC, TAG_WN_WINO, 0, TTS_WN_PIPE>(g, nz, s); }
-inline hipError_t gemm_wn_wino_128(const GemmArgs& g, int nz, hipStream_t s) { return launch_gemm<TTS_WN_WR, 1, 1, 4, TTS_WN_BK, 3, TAG_WN_WINO, 0, TTS_WN_PIPE>(g, nz, s); }
+inline hipError_t gemm_wn_wino(const GemmArgs& g, int nz, hipStream_t s) { return launch_gemm<WN_WR, 1, WN_RT, 4, WN_BK, WN_OCC, TAG_WN_WINO, 0, WN_PIPE>(g, nz, s); }
+inline hipError_t gemm_wn_wino_128(const GemmArgs& g, int nz, hipStream_t s) { return launch_gemm<WN_WR, 1, 1, 4, WN_BK, 3, TAG_WN_WINO, 0, WN_PIPE>(g, nz, s); }
 inline hipError_t gemm_small(const GemmArgs& g, int bz, hipStream_t s) { return launch_gemm<2, 2, 1, 1, 32, 1, TAG_GENERIC>(g, bz, s); }
 
 }  // namespace ttsgemm

@@ -692,7 +692,7 @@ int waveglow_finalize(tts_hip_engine* e) {
                 if ((rc = pack_bt(e, stage.f(), KCONV0, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1))) return rc;   // K order tap*16 + j
             } else {
                 if ((rc = put(stage, t))) return rc;
-                if ((rc = pack_bt(e, stage.f(), 3 * C, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1, WN_TAPS, TTS_WN_BK))) return rc;
+                if ((rc = pack_bt(e, stage.f(), 3 * C, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1, WN_TAPS, WN_BK))) return rc;
             }
             HIPCHK(e, hipStreamSynchronize(e->stream));
             // conditioning conv: WcT[n'][k] (gate-permuted rows), then V_{i,p} = WcT @ U_p for the 32 phases
