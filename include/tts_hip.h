@@ -241,20 +241,27 @@ int tts_hip_last_conv_paths(const tts_hip_engine* e);
  * waveform RMS error against the oracle);
  * form 0: always the direct form;
  * forms 2, 3 (measurement only, same results as form 1): the three-pass form of round 3 (pre-pass, per-product GEMM, combine
- * pass) and the fused GEMM behind the pre-pass.                                                                         */
+ * pass) and the fused GEMM behind the pre-pass.
+ * The Winograd form exists for 512-channel models only: on a 256-channel handle (tts_hip_waveglow_channels) the call is
+ * accepted and has no effect -- every fp32 call takes the direct form.                                                  */
 int tts_hip_set_waveglow_form(tts_hip_engine* e, int form);
 /* Which one the last tts_hip_waveglow_infer* call on this handle used: 1 Winograd, 0 direct, -1 before the first call.  */
 int tts_hip_last_waveglow_form(const tts_hip_engine* e);
+/* n_channels (the WN width C) of this handle's WaveGlow: 512 or 256, fixed by the tensors present at tts_hip_finalize
+ * (waveglow/block-0/start_conv/kernel [1, 4, C]; any other width, or a tensor that disagrees with it, fails finalize with
+ * TTS_HIP_EINVAL).  0 while no WaveGlow is finalized and for a NULL handle.  Handles of both widths may live in one process. */
+int tts_hip_waveglow_channels(const tts_hip_engine* e);
 
 /* Test hook (used by tests/ only; no effect on later calls): runs the fp32 path of tts_hip_waveglow_infer -- in the form
  * selected by tts_hip_set_waveglow_form -- up to WN layer `layer` (0 .. 7) of flow `flow` (flows run 11 .. 0) and copies that
  * layer's gated activations tanh(.) * sigmoid(.) (waveglow_arch.py:19-24,117-127), i.e. the values BEFORE the res/skip and
- * `end` convolutions attenuate an error, to `acts` [B, T*32, 512] in the reference's position order.  B*T <= 31744.       */
+ * `end` convolutions attenuate an error, to `acts` [B, T*32, C] (C = tts_hip_waveglow_channels) in the reference's position
+ * order.  B*T <= 31744.                                                                                                  */
 int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int flow,
                                 int layer, float* acts, int mem);
 /* Test hook, any precision (used by tests/ only; no effect on later calls): runs tts_hip_waveglow_infer in `precision`
  * (0 f32 in the form tts_hip_set_waveglow_form selects, 1 f16, 2 f16x3) up to a stop point of flow `flow` (11 .. 0):
- *   what 0: the gated activations of WN layer `layer` (0 .. 7), as tts_hip_waveglow_probe_acts, to `out` [B, T*32, 512] fp32
+ *   what 0: the gated activations of WN layer `layer` (0 .. 7), as tts_hip_waveglow_probe_acts, to `out` [B, T*32, C] fp32
  *           (f16: the fp16 activations widened; f16x3: hi + lo summed in fp32);
  *   what 1: the flow state right after the flow (affine coupling, inverse 1x1 conv, and the early output that flows 8 and 4
  *           prepend), to `out` [B, T*32, n] with n = 4, 6 (flow 8), 6, 8 (flow 4), 8 for flows 11-9, 8, 7-5, 4, 3-0 --
@@ -262,7 +269,7 @@ int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int 
  *   what 2: (precision 0 only) the conditioning plane that the Winograd form builds for WN layer `layer` (1 .. 7) -- the
  *           layer's conditioning term plus its in-layer bias, columns in the engine's gate-interleaved order (64 j + c: tanh
  *           channel 32 j + c, 64 j + 32 + c: its sigmoid channel) -- to `out` [B, T*32, 1024]; an error when the call does
- *           not take the Winograd form (fewer than 144 frames, form 0).
+ *           not take the Winograd form (fewer than 144 frames, form 0, a 256-channel model).
  * B*T <= 31744.                                                                                                            */
 int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int precision,
                            int flow, int what, int layer, float* out, int mem);

@@ -54,6 +54,7 @@ SIGNATURES = {
     'tts_hip_last_conv_paths': (c_int, [c_void_p]),
     'tts_hip_set_waveglow_form': (c_int, [c_void_p, c_int]),
     'tts_hip_last_waveglow_form': (c_int, [c_void_p]),
+    'tts_hip_waveglow_channels': (c_int, [c_void_p]),
     'tts_hip_waveglow_probe_acts': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_void_p, c_int]),
     'tts_hip_waveglow_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_void_p,
                                        c_int]),

@@ -36,7 +36,9 @@ struct DevBuf {
     float* f() const { return (float*)p; }
 };
 
-// ---------------------------------------------------------------- WaveGlow (fixed reference geometry)
+// ---------------------------------------------------------------- WaveGlow (fixed reference geometry but for the WN width
+// C = WaveGlowDev::channels, 512 or 256; the shapes in the comments below are written for C = 512: 1024 stands for 2 C,
+// 1536 for 3 C; the Winograd operands exist at 512 only)
 struct WgLayerDev {
     float* in_Bt = nullptr;     // [1024 (tanh/sigmoid interleaved per 128-tile)][3*512 taps] (first layer of a flow: [3*16])
     float* cond_Bt = nullptr;   // [32 phases][1024][320] conditioning conv folded with the upsampling kernel
@@ -64,13 +66,14 @@ struct WgFlowDev {
 };
 struct WaveGlowDev {
     bool ready = false;
+    int channels = 0;                        // n_channels of the finalized model (512 or 256; 0 while none is): per handle
     WgFlowDev flow[12];
     std::vector<void*> allocs;
     bool f16_ready = false, x3_ready = false;
     int form_mode = 1, last_form = -1;       // tts_hip_set_waveglow_form / tts_hip_last_waveglow_form
     int last_tiles = -1;                     // tts_hip_last_waveglow_tiles: WN GEMM tile family of the last call
     int probe_flow = -1, probe_layer = -1;   // tts_hip_waveglow_probe (test hook): stop after this layer (what 0, 2) or flow
-    int probe_what = 0;                      //   (what 1) and copy its gated activations [B][T * 32][512], the flow state
+    int probe_what = 0;                      //   (what 1) and copy its gated activations [B][T * 32][C], the flow state
     float* probe_out = nullptr;              //   [B][T * 32][n] or the layer's conditioning plane [B][T * 32][1024] (what 2;
                                              //   Winograd form only) to this device buffer
     bool wino_ready = false;                 // Winograd form of the fp32 in-layer GEMM (wn_wino.hip)

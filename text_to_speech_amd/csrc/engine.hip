@@ -468,7 +468,7 @@ int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, co
     HIPCHK(e, hipSetDevice(e->device));
     // what 1: the flow's 2 * n_half channels, preceded by the early output that flows 8 and 4 append
     // what 2: the conditioning plane (bias included, gate-interleaved columns) that the Winograd form builds for the layer
-    const int width = what == 0 ? 512 : what == 2 ? 1024 : e->wg.flow[flow].n_rem + (flow % 4 == 0 && flow > 0 ? 2 : 0);
+    const int width = what == 0 ? e->wg.channels : what == 2 ? 2 * e->wg.channels : e->wg.flow[flow].n_rem + (flow % 4 == 0 && flow > 0 ? 2 : 0);
     const size_t n_out = (size_t)B * T * 32 * width;
     const float* d_mel = mel;
     const float* d_z = z;
@@ -668,6 +668,8 @@ int tts_hip_set_waveglow_form(tts_hip_engine* e, int form) {
 }
 
 int tts_hip_last_waveglow_form(const tts_hip_engine* e) { return e ? e->wg.last_form : -1; }
+
+int tts_hip_waveglow_channels(const tts_hip_engine* e) { return e && e->wg.ready ? e->wg.channels : 0; }
 
 int tts_hip_last_waveglow_tiles(const tts_hip_engine* e) { return e ? e->wg.last_tiles : -1; }
 

@@ -8,8 +8,10 @@
 // index and PR = B*T rounded up to the 256-row tile.  A conv tap l +- d then stays a constant row shift per tile
 // (phase' = (p +- d) mod 32, frame carry = floor((p +- d) / 32)) and the phase is uniform per tile, which is what the
 // low-rank conditioning below needs.  M' = 32 * PR rows:
-//   x     [M'][512]   WN residual stream, updated in place by the residual GEMM epilogue
-//   acts  [8][M'][512] gated activations tanh * sigmoid of the 8 layers of the current flow (in-layer GEMM epilogue)
+// C = n_channels of the handle's model, 512 or 256 (WaveGlowDev::channels, read from the tensors at finalize); the widths
+// spelled as numbers in the comments below are those of the 512-channel model.
+//   x     [M'][C]     WN residual stream, updated in place by the residual GEMM epilogue
+//   acts  [8][M'][C]  gated activations tanh * sigmoid of the 8 layers of the current flow (in-layer GEMM epilogue)
 //   a0p   [M'][16]    [audio_0 | 1 | 0..]: operand of the first layer of a flow (start conv composed into its taps)
 //   audio [M'][8]     current flow state in the first n_rem columns; the last flow writes the caller's [B][L*8] directly
 // Per flow: start (VALU) -> 8 x { in-layer implicit GEMM (K = 3 taps * 512 + 4 * 80 mel, N = 1024, gate epilogue),
@@ -31,6 +33,11 @@
 //
 // fp32 calls of 144 frames or more take the Winograd form (wn_wino.hip) instead of the in-layer GEMMs above: layers 1 .. 7 as
 // F(4,3) along the taps behind a frame-axis F(4,4) conditioning plane, the first layer of a flow on that plane kernel's K loop.
+// That form is built on N = 1024 planes: a 256-channel model always takes the direct form.
+//
+// Width: the GEMMs take N, K and every stride as run-time values; the VALU kernels of this file whose indexing is built on
+// the width are templates on C, instantiated for 512 and 256 and chosen per call by for_width().  Nothing at file scope
+// depends on a handle's width, so handles of both widths live side by side.
 //
 // Host side, in file order: waveglow_free; the load-time algebra above as three host functions and waveglow_finalize, which
 // uploads their results; waveglow_build_half (fp16 operands of either fp16 mode, on first use); the pieces of waveglow_run --
@@ -43,14 +50,14 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
+#include <utility>
 
 using namespace ttsgemm;
 
 namespace {
 
-constexpr int C = 512;        // n_channels
 constexpr int NCOND = 640;    // n_mel * n_group (reference layout of the conditioning input)
-constexpr int KCONV = 3 * C;  // taps part of the in-layer K
 constexpr int KCONV0 = 3 * 16;// first layer of a flow: taps act on [audio_0 | 1] (16-float rows)
 constexpr int KMEL = 4 * 80;  // folded conditioning: 4 mel frames x 80 channels
 constexpr int NPH = 32;       // phases (sample groups per mel frame)
@@ -60,6 +67,7 @@ constexpr int NPH = 32;       // phases (sample groups per mel frame)
 //       wave's pair of adjacent 32-column MFMA tiles holds matching pre-activations for every N tile >= 64 columns)
 // taps > 1: src is [taps][K/taps][N] and the K axis of dst is tap-interleaved in chunks of `bk`:
 //   dst k = (c / bk) * taps * bk + tap * bk + c % bk     (matches gemm_f32_kernel's NI = taps tile order)
+template <int C>
 __global__ void pack_bt_kernel(const float* __restrict__ src, int K, int src_ld, float* __restrict__ dst, int N,
                                long long ldb, int koff, int perm, int taps, int bk) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,6 +86,7 @@ __global__ void pack_bt_kernel(const float* __restrict__ src, int K, int src_ld,
     dst[(long long)n * ldb + koff + kd] = src[(long long)k * src_ld + sn];
 }
 
+template <int C>
 __global__ void pack_bias_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ dst,
                                  int N, int perm) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -104,6 +113,7 @@ __global__ void pack_ut_kernel(const float* __restrict__ w, float* __restrict__ 
 }
 
 // bias[n] += sum_k WcT[n][k] * b_up[k >> 3]     (upsampling bias pushed through the conditioning conv)
+template <int C>
 __global__ void cond_bias_kernel(const float* __restrict__ wct, const float* __restrict__ b_up, float* __restrict__ bias) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= 2 * C) return;
@@ -126,7 +136,9 @@ __global__ void cvt_half_kernel(const float* __restrict__ src, _Float16* __restr
 }
 // in-layer taps: fp32 [1024][1536] tap-interleaved in chunks of 16 -> fp16 [1024][1536] tap-interleaved in chunks of 32
 // (the fp16 kernel's K step is 32 halfs = 64-byte LDS rows, like 16 floats)
+template <int C>
 __global__ void cvt_taps_kernel(const float* __restrict__ src, _Float16* __restrict__ dst, _Float16* __restrict__ lo = nullptr) {
+    constexpr int KCONV = 3 * C;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)2 * C * KCONV) return;
     const int n = (int)(i / KCONV), r = (int)(i % KCONV);
@@ -135,6 +147,7 @@ __global__ void cvt_taps_kernel(const float* __restrict__ src, _Float16* __restr
     put_split(dst, lo, (long long)n * KCONV + kd, src[(long long)n * KCONV + ks]);
 }
 // first layer of a flow: fp32 [1024][3*16] -> fp16 [1024][3*32] (a0p rows are 32 halfs)
+template <int C>
 __global__ void cvt_taps0_kernel(const float* __restrict__ src, _Float16* __restrict__ dst, _Float16* __restrict__ lo = nullptr) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2 * C * 96) return;
@@ -154,8 +167,8 @@ __global__ void mel_window_kernel(const float* __restrict__ mel, _Float16* __res
     put_split(dst, lo, i, t - q >= 0 ? mel[(long long)(f - q) * 80 + j] : 0.f);
 }
 
-// test hook (tts_hip_waveglow_probe): phase-major rows m' = p * PR + b * T + t of one layer's gated activations (W = 512) or
-// conditioning plane (W = 1024) -> natural order [B][T * 32][W] (position l = 32 t + p)
+// test hook (tts_hip_waveglow_probe): phase-major rows m' = p * PR + b * T + t of one layer's gated activations (W = C) or
+// conditioning plane (W = 1024; Winograd form, 512 channels only) -> natural order [B][T * 32][W] (position l = 32 t + p)
 __global__ void probe_acts_kernel(const float* __restrict__ acts, float* __restrict__ out, int PR, int BT, int T, int W) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // one float4 of one position
     if (idx >= (long long)BT * NPH * (W / 4)) return;
@@ -166,6 +179,7 @@ __global__ void probe_acts_kernel(const float* __restrict__ acts, float* __restr
     *reinterpret_cast<f32x4*>(out + pos * W + c) = *reinterpret_cast<const f32x4*>(acts + ((long long)p * PR + f) * W + c);
 }
 // the same for the fp16 activation planes, widened to fp32; `lo` (split-fp16 mode, may be null): value = hi + lo
+template <int C>
 __global__ void probe_acts16_kernel(const _Float16* __restrict__ acts, const _Float16* __restrict__ lo, float* __restrict__ out,
                                     int PR, int BT, int T) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -239,6 +253,7 @@ __global__ void mel_ragged_copy_kernel(const float* __restrict__ mel, float* __r
 // x16 (fp16 modes, else null): the shadow of x, `planes` planes M * C halfs apart; a0p (null after a residual GEMM):
 // 16 floats per row, or `planes` planes of 32 halfs per row when x16 is given.
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <int C>
 __global__ void wn_zero_tail_kernel(const int* __restrict__ tail, int n_tail, int PR, long long M, float* __restrict__ x,
                                     _Float16* __restrict__ x16, int planes, void* __restrict__ a0p) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -295,7 +310,7 @@ __global__ void packed_scatter_kernel(const float* __restrict__ packed, const in
 // composed with the start conv at load time (the constant 1 carries the start bias through the zero padding).
 // HALF: x stays fp32 (master copy for the residual accumulation) and additionally gets an fp16 shadow x16 (the GEMM
 // operand); a0p is written as 32 halfs per row.
-template <bool HALF>
+template <int C, bool HALF>
 __global__ void wn_start_kernel(const float* __restrict__ audio, const float* __restrict__ w,
                                 const float* __restrict__ b, float* __restrict__ x, void* __restrict__ a0p_v,
                                 _Float16* __restrict__ x16, long long M, int h, int split = 0) {
@@ -348,13 +363,19 @@ __global__ void wn_start_kernel(const float* __restrict__ audio, const float* __
 // Folded skip/end conv + affine inverse + inverse 1x1 conv (+ early-z prepend), RPW positions per wave.
 //   out[m][o] = sum_layer sum_c acts[layer][m][c] * wfold[layer][o][c] + bfold[o]          (waveglow_arch.py:129-141)
 //   audio_1 = (audio_1 - b) / exp(s); audio = [audio_0, audio_1] @ inv; prepend sigma * z_early   (:284-304)
-// Lane l owns channels 4l..4l+3 and 256+4l..256+4l+3 (every wave-level load is one contiguous 1 KiB run); per layer
+// C = 512: lane l owns channels 4l..4l+3 and 256+4l..256+4l+3 (every wave-level load is one contiguous 1 KiB run); per layer
 // the lane's 8x8 slice of wfold sits in registers and is reused for the RPW rows; the RPW*8 partial sums are reduced with the lane-halving exchange (63 shuffles for 64 values).
+// C = 256: a wave still owns RPW whole rows and a lane owns 4 channels of each, 4l..4l+3 (fp32: one float4, the wave-level
+// load is the whole 1 KiB row; fp16 modes: 4 halfs, one 8-byte load per plane), i.e. the second slice (w1 / a1) is absent.
+// The other choice, two rows per wave, would keep 16-byte fp16 loads but needs a second reduction tree (32 lanes per row,
+// 128 values per wave), another row-to-lane map for the masked epilogue and twice the accumulators per lane.  The kernel
+// streams 8 x M x C activations once and is bound by that stream at either width; with one row per wave the reduction,
+// the three MASK modes and the early-z prepend below are the very same code as at 512.
 constexpr int RPW = 8;
 // MASK != MASK_NONE: positions of frames that are not real (beyond their row's length; gap frames of a packed call) store
 // 0 -- the flow state stays 0 there from flow to flow and the last flow gives the zero tail of the output -- and z is not
 // read there.
-template <bool HALF, bool SPLIT = false, int MASK = MASK_NONE>
+template <bool HALF, bool SPLIT = false, int MASK = MASK_NONE, int C = 512>
 __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict__ acts_v, long long layer_stride,
                                                           const float* __restrict__ wfold,
                                                           const float* __restrict__ bfold,
@@ -365,7 +386,10 @@ __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict
                                                           long long lo_plane = 0,
                                                           const int* __restrict__ lens = nullptr, int T = 1) {
     // lo_plane != 0 (split-fp16 mode): activation = hi + lo, lo at + lo_plane halfs
-    // fp16 variants: the folded weights of a layer ([8 outputs][512]: 16 KB, the same for every wave) are staged in LDS once
+    static_assert(C == 512 || C == 256, "wn_end_fold_kernel: 4 or 8 channels per lane");
+    constexpr bool TWO = C == 512;                        // the lane's second slice of 4 channels (w1 / a1)
+    constexpr int WQ = 8 * C / 4 / 256;                   // float4 per thread of a layer's folded weights [8][C]
+    // fp16 variants: the folded weights of a layer ([8 outputs][C]: 16 KB at 512, the same for every wave) are staged in LDS once
     // per block and layer (double buffered; the next layer's rows are requested before this layer's arithmetic).  With
     // 8 consecutive channels per lane a lane's two weight float4 sit 32 B apart, and pulling those slices through the L1
     // per wave cost more than the halved activation stream saved (fp16 0.68 -> 0.42 ms, split 1.14 -> 0.90 ms).
@@ -382,46 +406,47 @@ __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict
     if constexpr (HALF) {
         const f32x4* src = reinterpret_cast<const f32x4*>(wfold);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) reinterpret_cast<f32x4*>(wsm[0])[threadIdx.x + i * 256] = src[threadIdx.x + i * 256];
+        for (int i = 0; i < WQ; ++i) reinterpret_cast<f32x4*>(wsm[0])[threadIdx.x + i * 256] = src[threadIdx.x + i * 256];
         __syncthreads();
     }
     for (int layer = 0; layer < 8; ++layer) {
-        f32x4 w0[8], w1[8], a0[RPW], a1[RPW], wnext[HALF ? 4 : 1];
+        f32x4 w0[8], w1[8], a0[RPW], a1[RPW], wnext[HALF ? WQ : 1];
         if constexpr (HALF) {
             if (layer + 1 < 8) {
                 const f32x4* src = reinterpret_cast<const f32x4*>(wfold + (long long)(layer + 1) * 8 * C);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) wnext[i] = src[threadIdx.x + i * 256];
+                for (int i = 0; i < WQ; ++i) wnext[i] = src[threadIdx.x + i * 256];
             }
         }
         // fp32 activations: lane owns channels 4l..4l+3 and 256+4l..; fp16 activations: channels 8l..8l+7, so that one
-        // 16-byte load per plane and row fetches them
-        const float* wl = HALF ? wsm[layer & 1] + lane * 8 : wfold + ((long long)layer * 8) * C + lane * 4;
+        // 16-byte load per plane and row fetches them (C = 256: channels 4l..4l+3 in every precision)
+        constexpr int CPL = C / 64;                       // channels per lane
+        const float* wl = HALF ? wsm[layer & 1] + lane * CPL : wfold + ((long long)layer * 8) * C + lane * 4;
         constexpr int W1 = HALF ? 4 : C / 2;
 #pragma unroll
         for (int o = 0; o < 8; ++o) {
             w0[o] = *reinterpret_cast<const f32x4*>(wl + o * C);
-            w1[o] = *reinterpret_cast<const f32x4*>(wl + o * C + W1);
+            if constexpr (TWO) w1[o] = *reinterpret_cast<const f32x4*>(wl + o * C + W1);
         }
         if constexpr (HALF) {
             // all loads of the layer first (a run-time test of `lo_plane` between them made the compiler wait for every
             // load before issuing the next: 1.9 ms instead of 0.6 ms), conversions afterwards
-            typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-            f16x8v hv[RPW], lv[SPLIT ? RPW : 1];
+            typedef _Float16 f16xNv __attribute__((ext_vector_type(CPL)));
+            f16xNv hv[RPW], lv[SPLIT ? RPW : 1];
 #pragma unroll
             for (int r = 0; r < RPW; ++r) {
                 const long long m = m0 + r < M ? m0 + r : M - 1;   // clamp: tail rows are computed but never stored
-                const _Float16* al = (const _Float16*)acts_v + layer * layer_stride + m * C + lane * 8;
-                hv[r] = *reinterpret_cast<const f16x8v*>(al);
-                if constexpr (SPLIT) lv[r] = *reinterpret_cast<const f16x8v*>(al + lo_plane);
+                const _Float16* al = (const _Float16*)acts_v + layer * layer_stride + m * C + lane * CPL;
+                hv[r] = *reinterpret_cast<const f16xNv*>(al);
+                if constexpr (SPLIT) lv[r] = *reinterpret_cast<const f16xNv*>(al + lo_plane);
             }
 #pragma unroll
             for (int r = 0; r < RPW; ++r) {
                 a0[r] = f32x4{(float)hv[r][0], (float)hv[r][1], (float)hv[r][2], (float)hv[r][3]};
-                a1[r] = f32x4{(float)hv[r][4], (float)hv[r][5], (float)hv[r][6], (float)hv[r][7]};
+                if constexpr (TWO) a1[r] = f32x4{(float)hv[r][4], (float)hv[r][5], (float)hv[r][6], (float)hv[r][7]};
                 if constexpr (SPLIT) {
                     a0[r] += f32x4{(float)lv[r][0], (float)lv[r][1], (float)lv[r][2], (float)lv[r][3]};
-                    a1[r] += f32x4{(float)lv[r][4], (float)lv[r][5], (float)lv[r][6], (float)lv[r][7]};
+                    if constexpr (TWO) a1[r] += f32x4{(float)lv[r][4], (float)lv[r][5], (float)lv[r][6], (float)lv[r][7]};
                 }
             }
         } else {
@@ -430,7 +455,7 @@ __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict
                 const long long m = m0 + r < M ? m0 + r : M - 1;   // clamp: tail rows are computed but never stored
                 const float* al = (const float*)acts_v + layer * layer_stride + lane * 4;
                 a0[r] = *reinterpret_cast<const f32x4*>(al + m * C);
-                a1[r] = *reinterpret_cast<const f32x4*>(al + m * C + C / 2);
+                if constexpr (TWO) a1[r] = *reinterpret_cast<const f32x4*>(al + m * C + C / 2);
             }
         }
 #pragma unroll
@@ -440,14 +465,16 @@ __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict
                 float p = acc[r * 8 + o];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) p = fmaf(a0[r][j], w0[o][j], p);
+                if constexpr (TWO) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) p = fmaf(a1[r][j], w1[o][j], p);
+                    for (int j = 0; j < 4; ++j) p = fmaf(a1[r][j], w1[o][j], p);
+                }
                 acc[r * 8 + o] = p;
             }
         if constexpr (HALF) {
             if (layer + 1 < 8) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) reinterpret_cast<f32x4*>(wsm[(layer + 1) & 1])[threadIdx.x + i * 256] = wnext[i];
+                for (int i = 0; i < WQ; ++i) reinterpret_cast<f32x4*>(wsm[(layer + 1) & 1])[threadIdx.x + i * 256] = wnext[i];
             }
             __syncthreads();
         }
@@ -508,11 +535,21 @@ __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict
     }
 }
 
-int pack_bt(tts_hip_engine* e, const float* d_src, int K, int src_ld, float* dst, int N, long long ldb, int koff,
+// f(std::integral_constant<int, C>) for a handle's width: the one place that maps the run-time width to the <C> instantiations
+// of the kernels above (finalize admits no other width)
+template <class F>
+void for_width(int C, F f) {
+    if (C == 256) f(std::integral_constant<int, 256>{});
+    else f(std::integral_constant<int, 512>{});
+}
+
+int pack_bt(tts_hip_engine* e, int C, const float* d_src, int K, int src_ld, float* dst, int N, long long ldb, int koff,
             int perm, int taps = 1, int bk = 0) {
     const long long total = (long long)N * K;
-    hipLaunchKernelGGL(pack_bt_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, d_src, K,
-                       src_ld, dst, N, ldb, koff, perm, taps, bk);
+    for_width(C, [&](auto cc) {
+        hipLaunchKernelGGL(pack_bt_kernel<decltype(cc)::value>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream,
+                           d_src, K, src_ld, dst, N, ldb, koff, perm, taps, bk);
+    });
     HIPCHK(e, hipGetLastError());
     return TTS_HIP_OK;
 }
@@ -528,15 +565,16 @@ void waveglow_free(tts_hip_engine* e) {
     wg.f16_ready = false;
     wg.x3_ready = false;
     wg.ready = false;
+    wg.channels = 0;
 }
 
 // ---- load-time algebra of waveglow_finalize: host arithmetic in double, no HIP calls
 namespace {
 
-// Start conv composed into the first layer's taps (waveglow_arch.py:108).  w_in [3 taps][512][1024], ws [h][512], bs [512]
-// -> [3 taps][16][1024] for pack_bt: rows j < h: sum_c ws[j][c] * w_in[tap][c][n]; row h: sum_c bs[c] * w_in[tap][c][n];
+// Start conv composed into the first layer's taps (waveglow_arch.py:108).  w_in [3 taps][C][2 C], ws [h][C], bs [C]
+// -> [3 taps][16][2 C] for pack_bt: rows j < h: sum_c ws[j][c] * w_in[tap][c][n]; row h: sum_c bs[c] * w_in[tap][c][n];
 // rows > h: 0.
-std::vector<float> compose_start_taps(const float* w_in, const float* ws, const float* bs, int h) {
+std::vector<float> compose_start_taps(int C, const float* w_in, const float* ws, const float* bs, int h) {
     std::vector<float> comp((size_t)3 * 16 * 2 * C, 0.f);
     std::vector<double> rowacc(2 * C);
     for (int tap = 0; tap < 3; ++tap)
@@ -553,11 +591,11 @@ std::vector<float> compose_start_taps(const float* w_in, const float* ws, const 
     return comp;
 }
 
-// Skip halves of the 8 res_skip convs folded into the `end` conv we [512][no], be [no]:
-//   wf[i][o][c] = sum_s W_skip_i[c][s] * we[s][o]  ([8][8][512], rows o >= no zero);  bf[o] = sum_i b_skip_i @ we + be[o]
-// wk[i] / bk[i]: kernel [512][rs_full] and bias [rs_full] of layer i, the skip half behind the 512 residual columns
+// Skip halves of the 8 res_skip convs folded into the `end` conv we [C][no], be [no]:
+//   wf[i][o][c] = sum_s W_skip_i[c][s] * we[s][o]  ([8][8][C], rows o >= no zero);  bf[o] = sum_i b_skip_i @ we + be[o]
+// wk[i] / bk[i]: kernel [C][rs_full] and bias [rs_full] of layer i, the skip half behind the C residual columns
 // (layer 7 has no residual half).
-void fold_skip_into_end(const float* const wk[8], const float* const bk[8], const float* we, const float* be, int no,
+void fold_skip_into_end(int C, const float* const wk[8], const float* const bk[8], const float* we, const float* be, int no,
                         std::vector<float>* wf, std::vector<float>* bf) {
     wf->assign((size_t)8 * 8 * C, 0.f);
     bf->assign(8, 0.f);
@@ -628,11 +666,30 @@ struct FinalizeGuard {
 int waveglow_finalize(tts_hip_engine* e) {
     WaveGlowDev& wg = e->wg;
     waveglow_free(e);
+    auto dims_str = [](const std::vector<int64_t>& d) {
+        std::string s = "[";
+        for (size_t i = 0; i < d.size(); ++i) s += (i ? ", " : "") + std::to_string(d[i]);
+        return s + "]";
+    };
+    // the width of this handle's model: what block 0's start conv [1][n_half = 4][C] says; every other tensor must agree
+    int C = 0;
+    {
+        const char* name = "waveglow/block-0/start_conv/kernel";
+        const HostTensor* sc = find_tensor(e, name);
+        if (!sc) return set_err(e, TTS_HIP_ENOTREADY, "missing tensor %s", name);
+        const bool shaped = sc->dims.size() == 3 && sc->dims[0] == 1 && sc->dims[1] == 4;
+        if (!shaped || (sc->dims[2] != 256 && sc->dims[2] != 512))
+            return set_err(e, TTS_HIP_EINVAL, "tensor %s: expected [1, 4, n_channels] with n_channels = 256 or 512 (the supported widths), got %s",
+                           name, dims_str(sc->dims).c_str());
+        C = (int)sc->dims[2];
+    }
+    const int KCONV = 3 * C;                        // taps part of the in-layer K
     auto need = [&](const std::string& name, std::initializer_list<int64_t> dims, const HostTensor** out) -> int {
         const HostTensor* t = find_tensor(e, name);
         if (!t) return set_err(e, TTS_HIP_ENOTREADY, "missing tensor %s", name.c_str());
         if (t->dims != std::vector<int64_t>(dims))
-            return set_err(e, TTS_HIP_EINVAL, "tensor %s has an unexpected shape", name.c_str());
+            return set_err(e, TTS_HIP_EINVAL, "tensor %s has an unexpected shape %s (n_channels = %d by waveglow/block-0/start_conv/kernel)",
+                           name.c_str(), dims_str(t->dims).c_str(), C);
         *out = t;
         return 0;
     };
@@ -686,19 +743,19 @@ int waveglow_finalize(tts_hip_engine* e) {
             if ((rc = dev_alloc(e, (size_t)2 * C * kconv, &ly.in_Bt, wg.allocs, false))) return rc;
             if ((rc = need(p + "/in_conv-" + si + "/kernel", {3, C, 2 * C}, &t))) return rc;
             if (i == 0) {
-                const std::vector<float> comp = compose_start_taps(t->data.data(), ws->data.data(), bs->data.data(), n_half);
+                const std::vector<float> comp = compose_start_taps(C, t->data.data(), ws->data.data(), bs->data.data(), n_half);
                 HIPCHK(e, hipMemcpyAsync(stage.p, comp.data(), comp.size() * 4, hipMemcpyHostToDevice, e->stream));
                 HIPCHK(e, hipStreamSynchronize(e->stream));
-                if ((rc = pack_bt(e, stage.f(), KCONV0, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1))) return rc;   // K order tap*16 + j
+                if ((rc = pack_bt(e, C, stage.f(), KCONV0, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1))) return rc;   // K order tap*16 + j
             } else {
                 if ((rc = put(stage, t))) return rc;
-                if ((rc = pack_bt(e, stage.f(), 3 * C, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1, WN_TAPS, WN_BK))) return rc;
+                if ((rc = pack_bt(e, C, stage.f(), 3 * C, 2 * C, ly.in_Bt, 2 * C, kconv, 0, 1, WN_TAPS, WN_BK))) return rc;
             }
             HIPCHK(e, hipStreamSynchronize(e->stream));
             // conditioning conv: WcT[n'][k] (gate-permuted rows), then V_{i,p} = WcT @ U_p for the 32 phases
             if ((rc = need(p + "/cond_layer-" + si + "/kernel", {1, NCOND, 2 * C}, &t))) return rc;
             if ((rc = put(stage, t))) return rc;
-            if ((rc = pack_bt(e, stage.f(), NCOND, 2 * C, wct.f(), 2 * C, NCOND, 0, 1))) return rc;
+            if ((rc = pack_bt(e, C, stage.f(), NCOND, 2 * C, wct.f(), 2 * C, NCOND, 0, 1))) return rc;
             if ((rc = dev_alloc(e, (size_t)NPH * 2 * C * KMEL, &ly.cond_Bt, wg.allocs, false))) return rc;
             {
                 GemmArgs g{};
@@ -722,9 +779,12 @@ int waveglow_finalize(tts_hip_engine* e) {
             if ((rc = dev_alloc(e, 2 * C, &ly.in_bias, wg.allocs, false))) return rc;
             HIPCHK(e, hipMemcpyAsync(stage2.p, t->data.data(), 2 * C * 4, hipMemcpyHostToDevice, e->stream));
             HIPCHK(e, hipMemcpyAsync(stage2.f() + 2 * C, t2->data.data(), 2 * C * 4, hipMemcpyHostToDevice, e->stream));
-            hipLaunchKernelGGL(pack_bias_kernel, dim3(4), dim3(256), 0, e->stream, stage2.f(), stage2.f() + 2 * C,
-                               ly.in_bias, 2 * C, 1);
-            hipLaunchKernelGGL(cond_bias_kernel, dim3(4), dim3(256), 0, e->stream, wct.f(), d_bup, ly.in_bias);
+            for_width(C, [&](auto cc) {
+                constexpr int CC = decltype(cc)::value;
+                hipLaunchKernelGGL(pack_bias_kernel<CC>, dim3(2 * CC / 256), dim3(256), 0, e->stream, stage2.f(), stage2.f() + 2 * CC,
+                                   ly.in_bias, 2 * CC, 1);
+                hipLaunchKernelGGL(cond_bias_kernel<CC>, dim3(2 * CC / 256), dim3(256), 0, e->stream, wct.f(), d_bup, ly.in_bias);
+            });
             HIPCHK(e, hipGetLastError());
             HIPCHK(e, hipStreamSynchronize(e->stream));
             // res_skip conv: keep only the residual half as a GEMM operand (layers 0..6); the skip half is folded below
@@ -737,7 +797,7 @@ int waveglow_finalize(tts_hip_engine* e) {
             if (i < 7) {
                 if ((rc = dev_alloc(e, (size_t)C * C, &ly.rs_Bt, wg.allocs, false))) return rc;
                 if ((rc = put(stage, t))) return rc;
-                if ((rc = pack_bt(e, stage.f(), C, rs_full, ly.rs_Bt, C, C, 0, 0))) return rc;      // rows n < 512 = residual outputs
+                if ((rc = pack_bt(e, C, stage.f(), C, rs_full, ly.rs_Bt, C, C, 0, 0))) return rc;      // rows n < C = residual outputs
                 HIPCHK(e, hipStreamSynchronize(e->stream));
                 if ((rc = upload(e, t2->data.data(), C, &ly.rs_bias, wg.allocs))) return rc;
             }
@@ -747,7 +807,7 @@ int waveglow_finalize(tts_hip_engine* e) {
             if ((rc = need(p + "/end_conv/kernel", {1, C, 2 * n_half}, &we))) return rc;
             if ((rc = need(p + "/end_conv/bias", {2 * n_half}, &be))) return rc;
             std::vector<float> wf, bf;
-            fold_skip_into_end(skip_w, skip_b, we->data.data(), be->data.data(), 2 * n_half, &wf, &bf);
+            fold_skip_into_end(C, skip_w, skip_b, we->data.data(), be->data.data(), 2 * n_half, &wf, &bf);
             if ((rc = upload(e, wf.data(), wf.size(), &fl.end_w, wg.allocs))) return rc;
             if ((rc = upload(e, bf.data(), bf.size(), &fl.end_b, wg.allocs))) return rc;
         }
@@ -759,6 +819,7 @@ int waveglow_finalize(tts_hip_engine* e) {
     }
     HIPCHK(e, hipStreamSynchronize(e->stream));
     gd.keep = true;
+    wg.channels = C;
     wg.ready = true;
     return TTS_HIP_OK;
 }
@@ -769,6 +830,7 @@ static int waveglow_build_half(tts_hip_engine* e, bool split) {
     WaveGlowDev& wg = e->wg;
     bool& ready = split ? wg.x3_ready : wg.f16_ready;
     if (ready) return TTS_HIP_OK;
+    const int C = wg.channels, KCONV = 3 * C;
     hipStream_t st = e->stream;
     auto alloc_h = [&](size_t n, _Float16** out) -> int {
         void* p = nullptr;
@@ -786,8 +848,11 @@ static int waveglow_build_half(tts_hip_engine* e, bool split) {
             _Float16 *a, *c, *r = nullptr;
             const size_t na = (size_t)2 * C * (i == 0 ? 96 : KCONV), nc = (size_t)NPH * 2 * C * KMEL, nr = (size_t)C * C;
             if ((rc = alloc_h(na, &a))) return rc;
-            if (i == 0) hipLaunchKernelGGL(cvt_taps0_kernel, grid(na), dim3(256), 0, st, ly.in_Bt, a, lo(a, na));
-            else hipLaunchKernelGGL(cvt_taps_kernel, grid(na), dim3(256), 0, st, ly.in_Bt, a, lo(a, na));
+            for_width(C, [&](auto cc) {
+                constexpr int CC = decltype(cc)::value;
+                if (i == 0) hipLaunchKernelGGL(cvt_taps0_kernel<CC>, grid(na), dim3(256), 0, st, ly.in_Bt, a, lo(a, na));
+                else hipLaunchKernelGGL(cvt_taps_kernel<CC>, grid(na), dim3(256), 0, st, ly.in_Bt, a, lo(a, na));
+            });
             if ((rc = alloc_h(nc, &c))) return rc;
             hipLaunchKernelGGL(cvt_half_kernel, grid(nc), dim3(256), 0, st, ly.cond_Bt, c, (long long)nc, lo(c, nc));
             if (ly.rs_n) {
@@ -838,7 +903,7 @@ const WnKernels kWnKernels[3][4] = {
 // x, audio and the operands of the call's precision (layouts: the header comment of this file)
 int ensure_workspace(tts_hip_engine* e, const WgPlan& p, int precision) {
     WaveGlowDev& wg = e->wg;
-    const size_t M = (size_t)p.M, NP = (size_t)p.NP;
+    const size_t M = (size_t)p.M, NP = (size_t)p.NP, C = (size_t)wg.channels;
     HIPCHK(e, wg.x.ensure(M * C * 4));
     HIPCHK(e, wg.audio.ensure(M * 8 * 4));
     if (precision != 0) {
@@ -864,6 +929,7 @@ struct WnOperand {
 // The operands of one call in its precision
 struct WnCall {
     WgPlan plan;
+    int C;                          // n_channels of the handle
     int precision, T;
     int unit;                       // elements per float unit: 1 fp32, 2 the fp16 modes
     WnOperand a0p, x, mel;          // first-layer operand, residual stream (fp16 modes: its shadow), mel frames / windows
@@ -882,7 +948,9 @@ WnCall wn_call(WaveGlowDev& wg, const WgPlan& p, int precision, int T, const flo
     const bool f16 = precision != 0;
     const long long pl = precision == 2 ? 1 : 0;       // split fp16: the lo plane lies one whole operand behind the hi plane
     WnCall c{};
+    const int C = wg.channels;
     c.plan = p;
+    c.C = C;
     c.precision = precision;
     c.T = T;
     c.unit = f16 ? 2 : 1;
@@ -897,10 +965,10 @@ WnCall wn_call(WaveGlowDev& wg, const WgPlan& p, int precision, int T, const flo
 }
 
 // In-layer GEMM of layer i: K = 3 taps (of a0p for the first layer: conv(start(a0)) composed at load time, K = 3 x 16 with
-// h + 1 used instead of 3 x 512; of x otherwise) + the folded conditioning, N = 1024, gate epilogue -> acts_of(i)
+// h + 1 used instead of 3 x C; of x otherwise) + the folded conditioning, N = 2 C, gate epilogue -> acts_of(i)
 GemmArgs in_layer_args(const WnCall& c, const WgLayerDev& ly, int i) {
     const WgPlan& p = c.plan;
-    const int d = 1 << i, u = c.unit;
+    const int d = 1 << i, u = c.unit, C = c.C;
     GemmArgs g{};
     g.M = (int)p.M;
     g.N = 2 * C;
@@ -938,7 +1006,7 @@ GemmArgs in_layer_args(const WnCall& c, const WgLayerDev& ly, int i) {
 
 // Residual GEMM of layer i < 7: x += acts_i @ W_res + b_res   (skip half folded into wn_end_fold)
 GemmArgs res_args(const WnCall& c, const WgLayerDev& ly, int i) {
-    const int u = c.unit;
+    const int u = c.unit, C = c.C;
     GemmArgs r{};
     r.M = (int)c.plan.M;
     r.N = C;
@@ -973,23 +1041,28 @@ int in_layer_timing_kind(int precision, int i) {
 }
 
 // Folded skip / end conv + affine inverse + inverse 1x1 conv of one flow: one of the nine <HALF, SPLIT, MASK> instantiations
-// of wn_end_fold_kernel, with the kernel's arguments `a`
+// of wn_end_fold_kernel of the handle's width, with the kernel's arguments `a`
 template <bool HALF, bool SPLIT, int MASK, class... A>
-void end_fold(dim3 grid, hipStream_t st, A... a) {
-    hipLaunchKernelGGL((wn_end_fold_kernel<HALF, SPLIT, MASK>), grid, dim3(256), 0, st, a...);
+void end_fold(int C, dim3 grid, hipStream_t st, A... a) {
+    if (C == 512) {                 // the kernel's default width: the instantiations a 512-channel model has always run
+        hipLaunchKernelGGL((wn_end_fold_kernel<HALF, SPLIT, MASK>), grid, dim3(256), 0, st, a...);
+    } else {
+        const auto narrow = wn_end_fold_kernel<HALF, SPLIT, MASK, 256>;
+        hipLaunchKernelGGL(narrow, grid, dim3(256), 0, st, a...);
+    }
 }
 template <class... A>
-void launch_end_fold(int precision, int mask, dim3 grid, hipStream_t st, A... a) {
+void launch_end_fold(int C, int precision, int mask, dim3 grid, hipStream_t st, A... a) {
     switch (precision * 3 + mask) {
-        case 0 * 3 + MASK_NONE: return end_fold<false, false, MASK_NONE>(grid, st, a...);
-        case 0 * 3 + MASK_LENS: return end_fold<false, false, MASK_LENS>(grid, st, a...);
-        case 0 * 3 + MASK_FLAGS: return end_fold<false, false, MASK_FLAGS>(grid, st, a...);
-        case 1 * 3 + MASK_NONE: return end_fold<true, false, MASK_NONE>(grid, st, a...);
-        case 1 * 3 + MASK_LENS: return end_fold<true, false, MASK_LENS>(grid, st, a...);
-        case 1 * 3 + MASK_FLAGS: return end_fold<true, false, MASK_FLAGS>(grid, st, a...);
-        case 2 * 3 + MASK_NONE: return end_fold<true, true, MASK_NONE>(grid, st, a...);
-        case 2 * 3 + MASK_LENS: return end_fold<true, true, MASK_LENS>(grid, st, a...);
-        case 2 * 3 + MASK_FLAGS: return end_fold<true, true, MASK_FLAGS>(grid, st, a...);
+        case 0 * 3 + MASK_NONE: return end_fold<false, false, MASK_NONE>(C, grid, st, a...);
+        case 0 * 3 + MASK_LENS: return end_fold<false, false, MASK_LENS>(C, grid, st, a...);
+        case 0 * 3 + MASK_FLAGS: return end_fold<false, false, MASK_FLAGS>(C, grid, st, a...);
+        case 1 * 3 + MASK_NONE: return end_fold<true, false, MASK_NONE>(C, grid, st, a...);
+        case 1 * 3 + MASK_LENS: return end_fold<true, false, MASK_LENS>(C, grid, st, a...);
+        case 1 * 3 + MASK_FLAGS: return end_fold<true, false, MASK_FLAGS>(C, grid, st, a...);
+        case 2 * 3 + MASK_NONE: return end_fold<true, true, MASK_NONE>(C, grid, st, a...);
+        case 2 * 3 + MASK_LENS: return end_fold<true, true, MASK_LENS>(C, grid, st, a...);
+        case 2 * 3 + MASK_FLAGS: return end_fold<true, true, MASK_FLAGS>(C, grid, st, a...);
     }
 }
 
@@ -1001,6 +1074,7 @@ bool probe_wants_layer(const WaveGlowDev& wg, int precision, int k, int i) {
 int probe_layer(tts_hip_engine* e, const WnCall& c, int i, bool wino_layer) {
     WaveGlowDev& wg = e->wg;
     const WgPlan& p = c.plan;
+    const int C = c.C;
     const bool plane = wg.probe_what == 2;                    // the layer's conditioning plane (Winograd form only)
     if (plane && !wino_layer)
         return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: layer %d of this call has no conditioning plane", i);
@@ -1012,8 +1086,10 @@ int probe_layer(tts_hip_engine* e, const WnCall& c, int i, bool wino_layer) {
                            wg.probe_out, p.PR, p.BT, c.T, W);
     } else {
         const _Float16* acts_i = (const _Float16*)c.acts_of(i);
-        hipLaunchKernelGGL(probe_acts16_kernel, grid, dim3(256), 0, e->stream, acts_i,
-                           c.split() ? acts_i + p.M * C : (const _Float16*)nullptr, wg.probe_out, p.PR, p.BT, c.T);
+        for_width(C, [&](auto cc) {
+            hipLaunchKernelGGL(probe_acts16_kernel<decltype(cc)::value>, grid, dim3(256), 0, e->stream, acts_i,
+                               c.split() ? acts_i + p.M * C : (const _Float16*)nullptr, wg.probe_out, p.PR, p.BT, c.T);
+        });
     }
     HIPCHK(e, hipGetLastError());
     return TTS_HIP_OK;
@@ -1032,6 +1108,7 @@ int probe_state(tts_hip_engine* e, const WgPlan& p, const float* state, int natu
 // -- and only then: any other error is the call's error -- *wino = false and this handle keeps the direct form from now on
 int wino_begin_or_fall_back(tts_hip_engine* e, const WgPlan& p, const float* d_mel, int T, bool* wino) {
     WaveGlowDev& wg = e->wg;
+    const int C = 512;                                                // the Winograd form is a 512-channel form (waveglow_run)
     size_t free_b = 0, total_b = 0;
     HIPCHK(e, hipMemGetInfo(&free_b, &total_b));
     const size_t plane = (size_t)p.M * 2 * C * 4 > wg.wino_cond.bytes ? (size_t)p.M * 2 * C * 4 : 0;
@@ -1072,7 +1149,9 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
     const int* mask_info = d_flags ? d_flags : d_lens;
     if (precision != 0)
         if (int rc = waveglow_build_half(e, precision == 2)) return rc;
-    const WgPlan plan = wg_plan(B * T, precision, wg.form_mode);
+    const int C = wg.channels;
+    WgPlan plan = wg_plan(B * T, precision, wg.form_mode);
+    if (C != 512) plan.wino_wanted = false;      // the Winograd form (wn_wino.hip) is built on N = 1024 planes: 512 channels only
     const int BT = plan.BT, PR = plan.PR;
     const long long M = plan.M;
     if ((double)M * C * 4.0 >= 2147483648.0 - 65536.0)
@@ -1092,9 +1171,11 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         if (mask == MASK_NONE || n_tail == 0) return TTS_HIP_OK;
         const long long n4 = (long long)NPH * n_tail * (C / 4);
         const bool h16 = precision != 0;
-        hipLaunchKernelGGL(wn_zero_tail_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, d_tail, n_tail, PR, M,
-                           wg.x.f(), h16 ? (_Float16*)wg.x16.p : (_Float16*)nullptr, precision == 2 ? 2 : 1,
-                           with_a0p ? (h16 ? wg.a0p16.p : wg.a0p.p) : nullptr);
+        for_width(C, [&](auto cc) {
+            hipLaunchKernelGGL(wn_zero_tail_kernel<decltype(cc)::value>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, d_tail,
+                               n_tail, PR, M, wg.x.f(), h16 ? (_Float16*)wg.x16.p : (_Float16*)nullptr, precision == 2 ? 2 : 1,
+                               with_a0p ? (h16 ? wg.a0p16.p : wg.a0p.p) : nullptr);
+        });
         HIPCHK(e, hipGetLastError());
         return TTS_HIP_OK;
     };
@@ -1129,12 +1210,15 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         {
             const long long n4 = M * (C / 4);
             const dim3 grid((unsigned)((n4 + 255) / 256));
-            if (precision != 0)
-                hipLaunchKernelGGL(wn_start_kernel<true>, grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
-                                   wg.x.f(), wg.a0p16.p, x16, M, h, precision == 2 ? 1 : 0);
-            else
-                hipLaunchKernelGGL(wn_start_kernel<false>, grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
-                                   wg.x.f(), wg.a0p.p, (_Float16*)nullptr, M, h);
+            for_width(C, [&](auto cc) {
+                constexpr int CC = decltype(cc)::value;
+                if (precision != 0)
+                    hipLaunchKernelGGL((wn_start_kernel<CC, true>), grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
+                                       wg.x.f(), wg.a0p16.p, x16, M, h, precision == 2 ? 1 : 0);
+                else
+                    hipLaunchKernelGGL((wn_start_kernel<CC, false>), grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
+                                       wg.x.f(), wg.a0p.p, (_Float16*)nullptr, M, h);
+            });
             HIPCHK(e, hipGetLastError());
             if (int rc = zero_tail(true)) return rc;
         }
@@ -1165,7 +1249,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         const long long waves = (M + RPW - 1) / RPW;
         // elements between two layers' activations and (split fp16) from their hi to their lo plane; a call without a mask
         // passes no frame info and T = 1 (not read)
-        launch_end_fold(precision, mask, dim3((unsigned)((waves + 3) / 4)), st, (const void*)call.acts, plan.NP * M * C, fl.end_w,
+        launch_end_fold(C, precision, mask, dim3((unsigned)((waves + 3) / 4)), st, (const void*)call.acts, plan.NP * M * C, fl.end_w,
                         fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z, zoff, early ? 2 : 0, sigma, M, h, PR, BT,
                         precision == 2 ? M * C : 0ll, mask_info, mask == MASK_NONE ? 1 : T);
         HIPCHK(e, hipGetLastError());

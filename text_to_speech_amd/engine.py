@@ -621,7 +621,9 @@ class HipEngine:
 
     def set_waveglow_form(self, form: str) -> None:
         """How the fp32 vocoder evaluates the dilated convolutions of WN layers 1 - 7: 'winograd' (default: minimal filtering
-        along the tap axis, F(4,3), for calls of 144 frames or more) or 'direct' (always three taps).  Both are fp32; they differ by rounding only."""
+        along the tap axis, F(4,3), for calls of 144 frames or more) or 'direct' (always three taps).  Both are fp32; they differ by rounding only.
+        The Winograd form exists for 512-channel models: with a 256-channel one (`waveglow_channels`) the call is accepted and
+        every fp32 call still takes the direct form."""
         # 'winograd-3pass' / 'winograd-prepass': the two earlier stages of the Winograd form (pre-pass + per-product GEMM + combine
         # pass; fused GEMM behind the pre-pass), kept for measurement and as bit-identical cross-checks of the default kernel
         forms = {'direct': 0, 'winograd': 1, 'winograd-3pass': 2, 'winograd-prepass': 3}
@@ -635,6 +637,12 @@ class HipEngine:
         return {1: 'winograd', 0: 'direct'}.get(self._lib.tts_hip_last_waveglow_form(self._h), 'none')
 
     @property
+    def waveglow_channels(self) -> int:
+        """n_channels of this handle's WaveGlow (tts_hip_waveglow_channels): 512 or 256, fixed by the tensors present at
+        `finalize`; 0 while no WaveGlow is finalized."""
+        return int(self._lib.tts_hip_waveglow_channels(self._h))
+
+    @property
     def last_waveglow_tiles(self) -> str:
         """WN GEMM tile family of the last `waveglow_infer` (or probe) call: '64-row', '128x64', '128-row' or '256-row'
         ('none' before the first)."""
@@ -643,10 +651,10 @@ class HipEngine:
     def waveglow_probe(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', flow: int = 11, what: str = 'acts',
                        layer: int = 0):
         """Test hook (tts_hip_waveglow_probe): run `waveglow_infer` in `precision` up to flow `flow` and return either the gated
-        activations [B, T*32, 512] of its WN layer `layer` (what='acts') or the flow state [B, T*32, n] right after the flow,
+        activations [B, T*32, C] (C = `waveglow_channels`) of its WN layer `layer` (what='acts') or the flow state [B, T*32, n] right after the flow,
         early output included (what='state'; the reference's audio after that flow), or the conditioning plane [B, T*32, 1024]
         of that layer -- sum_q V_q mel[t - q] + b, columns in the gate-interleaved order of the engine's weights -- that the
-        fp32 Winograd form builds (what='cond'; layers 1 - 7 of calls of 144 frames or more)."""
+        fp32 Winograd form builds (what='cond'; layers 1 - 7 of calls of 144 frames or more, 512-channel models only)."""
         precs = {'f32': 0, 'f16': 1, 'f16x3': 2}
         whats = {'acts': 0, 'state': 1, 'cond': 2}
         if precision not in precs or what not in whats:
@@ -661,7 +669,8 @@ class HipEngine:
             if z.shape != (B, T * 32, 8):
                 raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {z.shape}')
             zp = z.ctypes.data_as(ctypes.c_void_p)
-        width = 512 if what == 'acts' else 1024 if what == 'cond' else (4 if flow >= 8 else 6 if flow >= 4 else 8) + (2 if flow in (4, 8) else 0)
+        C = self.waveglow_channels
+        width = C if what == 'acts' else 2 * C if what == 'cond' else (4 if flow >= 8 else 6 if flow >= 4 else 8) + (2 if flow in (4, 8) else 0)
         out = np.empty((B, T * 32, width), dtype=np.float32)
         self._check(self._lib.tts_hip_waveglow_probe(
             self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, zp, float(sigma), precs[precision], int(flow), whats[what],
@@ -669,7 +678,7 @@ class HipEngine:
         return out
 
     def waveglow_probe_acts(self, mel, z=None, sigma: float = 1.0, flow: int = 11, layer: int = 1):
-        """Test hook (tts_hip_waveglow_probe_acts): the gated activations [B, T*32, 512] of WN layer `layer` of flow `flow` on
+        """Test hook (tts_hip_waveglow_probe_acts): the gated activations [B, T*32, C] (C = `waveglow_channels`) of WN layer `layer` of flow `flow` on
         the fp32 path, in the form `set_waveglow_form` selects -- the values before the res/skip and `end` convolutions."""
         mel = np.ascontiguousarray(mel, dtype=np.float32)
         if mel.ndim != 3 or mel.shape[2] != 80:
@@ -681,7 +690,7 @@ class HipEngine:
             if z.shape != (B, T * 32, 8):
                 raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {z.shape}')
             zp = z.ctypes.data_as(ctypes.c_void_p)
-        out = np.empty((B, T * 32, 512), dtype=np.float32)
+        out = np.empty((B, T * 32, self.waveglow_channels), dtype=np.float32)
         self._check(self._lib.tts_hip_waveglow_probe_acts(
             self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, zp, float(sigma), int(flow), int(layer),
             out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'waveglow_probe_acts')

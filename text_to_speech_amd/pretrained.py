@@ -81,7 +81,8 @@ _TACOTRON2_REQUIRED = {
 }
 _TACOTRON2_EPS = ('encoder_epsilon', 'postnet_epsilon')          # batch-norm epsilon 1e-5 is folded into the conv weights
 _WAVEGLOW_REQUIRED = {'n_mel_channels': 80, 'n_flows': 12, 'n_group': 8, 'n_early_every': 4, 'n_early_size': 2,
-                      'n_layers': 8, 'n_channels': 512, 'kernel_size': 3}
+                      'n_layers': 8, 'kernel_size': 3}
+_WAVEGLOW_CHANNELS = (256, 512)          # WN widths the engine runs; absent = the engine's default (WaveGlowConfig: 512)
 _MEL_FN_REQUIRED = {'class_name': 'TacotronSTFT', 'sampling_rate': 22050, 'n_mel_channels': 80, 'filter_length': 1024,
                     'hop_length': 256, 'win_length': 1024, 'mel_fmin': 0.0, 'mel_fmax': 8000.0}
 
@@ -102,6 +103,8 @@ def check_hparams(model, hparams, where='config_models.json'):
     implement; absent keys mean the reference's defaults, which are the supported values."""
     required = _TACOTRON2_REQUIRED if model == 'tacotron2' else _WAVEGLOW_REQUIRED
     bad = [f'{k} = {hparams[k]!r} (supported: {v!r})' for k, v in required.items() if k in hparams and not _same(hparams[k], v)]
+    if model == 'waveglow' and 'n_channels' in hparams and not any(_same(hparams['n_channels'], c) for c in _WAVEGLOW_CHANNELS):
+        bad.append(f"n_channels = {hparams['n_channels']!r} (supported: {' or '.join(map(str, _WAVEGLOW_CHANNELS))})")
     if model == 'tacotron2':
         bad += [f'{k} = {hparams[k]!r} (supported: 1e-05)' for k in _TACOTRON2_EPS if k in hparams and not _same(hparams[k], 1e-5)]
         n_spk = hparams.get('encoder_n_speaker', 1)
@@ -211,7 +214,9 @@ def convert_model_dir(model_dir, out=None, cfg=None, force=False):
     if force or not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(ckpt):
         if cfg is None:
             cfg = Tacotron2Config(speaker_embedding_dim=info['speaker_embedding_dim'], vocab_size=info['vocab_size']) \
-                if info['model'] == 'tacotron2' else WaveGlowConfig()
+                if info['model'] == 'tacotron2' else \
+                WaveGlowConfig(n_channels=int(info['hparams']['n_channels'])) if 'n_channels' in info['hparams'] else None
+            # (a WaveGlow directory that does not state its width: the importer takes it from the start conv's shape)
         tensors = from_keras_file(ckpt, info['model'], cfg)
         # several ranks / processes may open a fresh directory at once: each writes its own temporary file and publishes it
         # atomically (a shared name let one writer truncate the file another had just finished)

@@ -11,7 +11,9 @@ module restates those layout rules so a `.pt` state dict can be used directly (S
                     -> kernel [in, 4u], recurrent_kernel [u, 4u], bias [4u]
   BatchNorm1d       weight, bias, running_mean, running_var -> gamma, beta, moving_mean, moving_variance
   weight_norm       weight_g, weight_v -> weight = g * v / ||v||   (norm over every dim but 0)
-  WaveGlow `cond_layer` (fused [8 * 1024, 640, 1]) is split per WN layer.
+  WaveGlow `cond_layer` (fused [8 * 2 * n_channels, 640, 1]) is split per WN layer.
+
+A WaveGlow importer called without a `cfg` takes the WN width (n_channels, 256 or 512) from the first flow's start conv.
 
 No checkpoint ships with this repository (no network); `to_nvidia_*` builds NVIDIA-layout state dicts from the synthetic
 weights so that the mapping is exercised end to end by tests/test_weights_import.py.
@@ -99,8 +101,24 @@ def from_nvidia_tacotron2(state_dict, cfg: Tacotron2Config = Tacotron2Config()):
     return _checked(o, tacotron2_manifest(cfg))
 
 
-def from_nvidia_waveglow(state_dict, cfg: WaveGlowConfig = WaveGlowConfig()):
+WAVEGLOW_CHANNELS = (256, 512)          # WN widths the engine runs (tts_hip_waveglow_channels)
+
+
+def waveglow_cfg_for(n_channels, where):
+    """The WaveGlowConfig of a checkpoint whose first start conv (`where`) is `n_channels` wide; ValueError for a width the
+    engine does not run."""
+    if int(n_channels) not in WAVEGLOW_CHANNELS:
+        raise ValueError(f'{where}: n_channels = {int(n_channels)} (supported: {" or ".join(map(str, WAVEGLOW_CHANNELS))})')
+    return WaveGlowConfig(n_channels=int(n_channels))
+
+
+def from_nvidia_waveglow(state_dict, cfg: WaveGlowConfig | None = None):
+    """NVIDIA WaveGlow state dict -> manifest tensors.  cfg None: the width is that of `WN.0.start.weight` [n_channels, 4, 1]."""
     sd = _strip(state_dict)
+    if cfg is None:
+        if 'WN.0.start.weight' not in sd:
+            raise KeyError('checkpoint has no tensor WN.0.start.weight')
+        cfg = waveglow_cfg_for(sd['WN.0.start.weight'].shape[0], 'WN.0.start.weight')
     o = OrderedDict()
     o['waveglow/upsample/kernel'] = sd['upsample.weight'].transpose(2, 1, 0).copy()       # [in, out, k] -> [k, out, in]
     o['waveglow/upsample/bias'] = sd['upsample.bias']
@@ -201,7 +219,13 @@ def from_keras_variables(named, model: str, cfg=None):
     if model == 'tacotron2':
         manifest = tacotron2_manifest(cfg or Tacotron2Config())
     elif model == 'waveglow':
-        manifest = waveglow_manifest(cfg or WaveGlowConfig())
+        if cfg is None:                      # the width of the first flow's start conv [1, 4, n_channels]
+            start = 'waveglow/block-0/start_conv/kernel'
+            path = next((p for p in named if _keras_target(p, model) == start), None)
+            if path is None:
+                raise KeyError(f'checkpoint has no tensor for {start}')
+            cfg = waveglow_cfg_for(np.shape(named[path])[-1], path)
+        manifest = waveglow_manifest(cfg)
     else:
         raise ValueError(f"model must be 'tacotron2' or 'waveglow', got {model!r}")
     out, origin = {}, {}
@@ -285,11 +309,7 @@ def keras_h5_layout(model: str, cfg=None):
 def from_keras_h5(path, model: str, cfg=None):
     """A Keras 3 `.weights.h5` file of the reference's Tacotron2 / WaveGlow -> manifest tensors (see the note above)."""
     from .hdf5_reader import H5File
-    if model == 'tacotron2':
-        manifest = tacotron2_manifest(cfg or Tacotron2Config())
-    elif model == 'waveglow':
-        manifest = waveglow_manifest(cfg or WaveGlowConfig())
-    else:
+    if model not in ('tacotron2', 'waveglow'):
         raise ValueError(f"model must be 'tacotron2' or 'waveglow', got {model!r}")
     with H5File(path) as f:
         scopes = {}
@@ -297,6 +317,13 @@ def from_keras_h5(path, model: str, cfg=None):
             parts = p.strip('/').split('/')
             if len(parts) >= 2 and parts[-2] == 'vars' and parts[-1].isdigit():
                 scopes.setdefault('/'.join(parts[:-2]), {})[int(parts[-1])] = ds
+        if model == 'waveglow' and cfg is None:  # the width of the first flow's start conv (vars/0: kernel [1, 4, n_channels])
+            cands = next(c for prefix, _, c in keras_h5_layout(model) if prefix == 'waveglow/block-0/start_conv')
+            present = [c for c in cands if c in scopes and 0 in scopes[c]]
+            if len(present) != 1:
+                raise KeyError(f'waveglow/block-0/start_conv: expected exactly one of the H5 groups {cands} (+ /vars), found {present}')
+            cfg = waveglow_cfg_for(scopes[present[0]][0].shape[-1], f'{path}: {present[0]}/vars/0')
+        manifest = tacotron2_manifest(cfg or Tacotron2Config()) if model == 'tacotron2' else waveglow_manifest(cfg)
         out = {}
         for prefix, names, candidates in keras_h5_layout(model, cfg):
             wanted = [n for n in names if f'{prefix}/{n}' in manifest]
