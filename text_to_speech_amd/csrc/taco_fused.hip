@@ -49,14 +49,11 @@ namespace {
 
 constexpr int NBLK = 256;                 // blocks = CUs of an MI355X; 4 units per block
 constexpr int NTHR = 512;                 // 4 LSTM waves + 4 role waves
-#ifndef TTS_FUSED_PF
-#define TTS_FUSED_PF 2
-#endif
-#ifndef TTS_FUSED_PRE
-#define TTS_FUSED_PRE 1
-#endif
-constexpr int PF = TTS_FUSED_PF;          // K slices (4 x 1 KiB per wave) of the weight stream in flight per LSTM wave
-constexpr int PRE_SL = TTS_FUSED_PRE;     // ... of which this many are requested before the operands are staged (barrier #1)
+// The four constants below were build switches until DESIGN 4.3c ("settled switches") had a measurement for each.
+constexpr int PF = 2;                     // K slices (4 x 1 KiB per wave) of the weight stream in flight per LSTM wave; 3: 24.1 -> 27.1 us (batch 8 fp32)
+constexpr int PRE_SL = 1;                 // ... of which this many are requested before the operands are staged (barrier #1); 0 / 1 / 2: 24.3 / 23.9 / 25.0 us
+constexpr int POLL_SLEEP = 4;             // 64-cycle units between two looks of a poll that missed; 1 / 4 / 12 / 30: 24.1 / 24.2 / 24.2 / 25.6 us
+constexpr int QUIET_LEAD = 30;            // a quiet window opens this many 10-ns ticks before the first look; at the publish / 30 / 60: 24.7 / 24.4 / 25.0 us
 constexpr int PRE = 256, RNN = 1024, ATT = 128, NMEL = 80, LOCK = 31;
 constexpr long long SPIN_LIMIT = 1 << 18; // polls (with s_sleep) of one hop before giving up: ~0.1 s
 constexpr int ABORT_TIMEOUT = 2;
@@ -105,7 +102,7 @@ constexpr int FTR_STEPS = 128, FTR_SLOTS = 16;
 #define FTR(kind, slot)                                                                                                   \
     do {                                                                                                                  \
         if (a.trace && lane == 0 && t < FTR_STEPS) {                                                                      \
-            const int tb_ = blk == 0 ? 0 : blk == 80 ? 1 : blk == 200 ? 2 : blk == 255 ? 3 : -1;                          \
+            const int tb_ = trace_block(blk);                                                                             \
             if (tb_ >= 0) a.trace[(((size_t)t * 2 + (kind)) * 4 + tb_) * FTR_SLOTS + (slot)] = (long long)wall_clock64(); \
         }                                                                                                                 \
     } while (0)
@@ -121,6 +118,7 @@ __device__ __forceinline__ int lds_peek(const lds_int* p) { return *(const volat
 __device__ __forceinline__ void lds_poke(lds_int* p, int v) { *(volatile lds_int*)p = v; }
 
 // ---------------------------------------------------------------------------------------------------- wave-level polls
+// Separate from Poller (taco_persist.hip) on purpose: abort checks every 63 / 1 023 polls, own sleep cadence, LDS abort pointer.
 struct WavePoll {
     __amdgpu_buffer_rsrc_t rs;            // the whole exchange area
     int* flags;                           // global: [0] abort code
@@ -153,95 +151,11 @@ struct WavePoll {
         }
         return w;
     }
-    // N pairs per lane straight into registers; `sentinel` (a pair published late) is awaited first with one request per poll
-    // instead of 64 lanes x N, so that waves that arrive early do not hammer the exchange area.
-    template <int N>
-    __device__ __forceinline__ void pairs_to_regs(const unsigned (&entry)[N], unsigned tag, f32x2 (&out)[N], unsigned sentinel) const {
-        wait_pair(sentinel, tag);
-        u32x4 v[N];
-        long long spins = 0;
-        while (true) {
-            asm volatile("" ::: "memory");
-            bool ok = true;
-#pragma unroll
-            for (int i = 0; i < N; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, entry[i] * 8u, 0, 16);
-#pragma unroll
-            for (int i = 0; i < N; ++i) ok = ok && v[i][1] == tag && v[i][3] == tag;
-            if (__all(ok)) break;
-            ++spins;
-            if (spins > SPIN_LIMIT) { give_up(); break; }
-            if (should_stop(spins)) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-#pragma unroll
-        for (int i = 0; i < N; ++i) out[i] = f32x2{bitsf(v[i][0]), bitsf(v[i][2])};
-    }
 };
 
-// LDS-DMA staging: one wave instruction moves 1 KiB (lane l: 16 bytes from `src` + 16 l to `dst` + 16 l) without touching
-// VGPRs.  `dst` must be wave-uniform.  The issuing wave has to drain vmcnt before the barrier that publishes the bytes.
+// destination of an LDS-DMA load (__builtin_amdgcn_raw_ptr_buffer_load_lds): wave-uniform; the issuing wave has to drain vmcnt
+// before the bytes are looked at
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x80000000u, 0x00020000);
-}
-__device__ __forceinline__ void dma_1k(const __amdgpu_buffer_rsrc_t& rs, float* dst, unsigned byte_off, int lane) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)dst, 16, byte_off + 16u * (unsigned)lane, 0, 0, 0);
-}
-
-// Lane-halving reduction of V (16 or 32) per-lane partial sums: in-row DPP steps for lane bits 0..3, bits 4 / 5 through
-// ds_bpermute.  Afterwards every lane holds the wave total of value index bitrev_LOGV(lane & (V - 1)).
-template <int V>
-__device__ __forceinline__ float reduce_v(float (&acc)[V], int lane) {
-    static_assert(V == 16 || V == 32, "V");
-    auto halve = [&](auto S, int half) {
-        const bool hi = (lane >> decltype(S)::value) & 1;
-#pragma unroll
-        for (int i = 0; i < V / 2; ++i) {
-            if (i < half) {
-                float a_lo = acc[i], a_hi = acc[i + half];
-                asm volatile("" : "+v"(a_lo), "+v"(a_hi));      // keeps select(load, load) from becoming an indexed load
-                const float send = hi ? a_lo : a_hi;
-                const float keep = hi ? a_hi : a_lo;
-                acc[i] = keep + row_xor<decltype(S)::value>(send, lane);
-            }
-        }
-    };
-    halve(std::integral_constant<int, 0>{}, V / 2);
-    halve(std::integral_constant<int, 1>{}, V / 4);
-    halve(std::integral_constant<int, 2>{}, V / 8);
-    halve(std::integral_constant<int, 3>{}, V / 16);
-    float v;
-    if constexpr (V == 32) {
-        const bool hi = (lane >> 4) & 1;
-        float a_lo = acc[0], a_hi = acc[1];
-        asm volatile("" : "+v"(a_lo), "+v"(a_hi));
-        const float send = hi ? a_lo : a_hi;
-        const float keep = hi ? a_hi : a_lo;
-        v = keep + __shfl_xor(send, 16, 64);
-    } else {
-        v = acc[0];
-        v += __shfl_xor(v, 16, 64);
-    }
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-template <int V>
-__device__ __forceinline__ int reduced_lane(int idx) {
-    constexpr int LOGV = V == 16 ? 4 : 5;
-    return (int)(__brev((unsigned)idx) >> (32 - LOGV));
-}
-
-template <bool HW>
-struct WT {
-    typedef typename std::conditional<HW, f16x4, f32x4>::type vec;
-    typedef typename std::conditional<HW, _Float16, float>::type el;
-};
-template <bool HW, bool NT>
-__device__ __forceinline__ typename WT<HW>::vec load_w(const void* base, long long elem) {
-    const typename WT<HW>::vec* p = reinterpret_cast<const typename WT<HW>::vec*>((const typename WT<HW>::el*)base + elem);
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
 
 // acc[g * NBT + b] += W[g] . x[b][lane * 4 ..]   for one 256-wide K slice; x rows are `ldx` floats apart in LDS
 template <int NBT, class WV>
@@ -268,31 +182,6 @@ __device__ __forceinline__ void fma_slice(float (&acc)[4 * NBT], const WV& w0, c
     // have to stay above it) and parks the operands in scratch -- the arithmetic must overlap the wait, not follow it
 #pragma unroll
     for (int i = 0; i < 4 * NBT; ++i) asm volatile("" : "+v"(acc[i]));
-}
-
-// role wave: s[b] = row . x[b][cols]   (NI slices of 256 columns; slice i of the row multiplies x columns col[i] ..)
-template <int NBT, int NI>
-__device__ __forceinline__ void role_dots(float (&s)[NBT], const f32x4 (&R)[NI], const float* xs, int ldx, const int (&col)[NI], int lane) {
-#pragma unroll
-    for (int b = 0; b < NBT; ++b) {
-        float acc = 0.f;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + b * ldx + col[i] + lane * 4);
-            acc = fmaf(xv[0], R[i][0], acc);
-            acc = fmaf(xv[1], R[i][1], acc);
-            acc = fmaf(xv[2], R[i][2], acc);
-            acc = fmaf(xv[3], R[i][3], acc);
-        }
-        s[b] = wave_sum(acc);
-    }
-}
-template <int NBT>
-__device__ __forceinline__ float pick_row(const float (&s)[NBT], int lane) {
-    float v = 0.f;
-#pragma unroll
-    for (int b = 0; b < NBT; ++b) v = lane == b ? s[b] : v;
-    return v;
 }
 
 // LSTM tail shared by both kernels: gates and cell update from the reduced sums.
@@ -324,20 +213,6 @@ __device__ __forceinline__ void load_slice(WSlice<HW>& w, const void* base, long
     for (int g = 0; g < 4; ++g) w.g[g] = load_w<HW, NT>(base, (row0 + g) * K + koff + lane * 4);
 }
 
-// Every block stages the same rows at the same moment: starting each block at its own offset keeps the 32 CUs of an XCD from
-// walking the L2 channels in lock step.  (TTS_FUSED_ROT=0: all blocks in the same order.)
-#ifndef TTS_FUSED_ROT
-#define TTS_FUSED_ROT 0
-#endif
-__device__ __forceinline__ int stage_index(int idx, int blk, int total) {
-#if TTS_FUSED_ROT
-    const int r = idx + ((blk >> 3) * 160) % total;      // blocks b, b + 8, ... share an XCD: 32 different offsets, 2.5 KiB apart
-    return r >= total ? r - total : r;
-#else
-    return idx;
-#endif
-}
-
 // ---------------------------------------------------------------------------------------------------- timed polls
 // The 256 blocks run in lock step (entry within ~0.3 us), and every block holds a producer of every hop.  So a consumer
 // does not watch the exchange area while it waits: it spins on an LDS word in which the block's own producer leaves the
@@ -361,9 +236,6 @@ __device__ __forceinline__ void wait_stamp(const WavePoll& P, const lds_int* ts,
     }
     while ((int)((unsigned)wall_clock64() - (unsigned)(v + delay)) < 0) __builtin_amdgcn_s_sleep(1);
 }
-#ifndef TTS_POLL_SLEEP
-#define TTS_POLL_SLEEP 4              // 64-cycle units between two looks of a poll that missed
-#endif
 template <int N>
 __device__ __forceinline__ void poll_pairs(const WavePoll& P, const unsigned (&entry)[N], unsigned tag, f32x2 (&out)[N]) {
     u32x4 v[N];
@@ -379,7 +251,7 @@ __device__ __forceinline__ void poll_pairs(const WavePoll& P, const unsigned (&e
         ++spins;
         if (spins > SPIN_LIMIT) { P.give_up(); break; }
         if (P.should_stop(spins)) break;
-        __builtin_amdgcn_s_sleep(TTS_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(POLL_SLEEP);
     }
 #pragma unroll
     for (int i = 0; i < N; ++i) out[i] = f32x2{bitsf(v[i][0]), bitsf(v[i][2])};
@@ -410,34 +282,22 @@ __device__ __forceinline__ EntryState look_entry(EntryLoads l) {
 }
 
 // Quiet windows (round 4): a hop's price sits in the consumer's memory queue and on a fabric that the weight stream
-// keeps busy.  A role wave raises an LDS counter shortly before its timed first look at a hop (TTS_FUSED_QUIET_LEAD ticks before)
-// and lowers it when its poll has succeeded; the LSTM waves do not request new weight slices while the counter is up (the 256
+// keeps busy.  A role wave raises an LDS counter shortly before its timed first look at a hop (QUIET_LEAD ticks before) and
+// lowers it when its poll has succeeded; the LSTM waves do not request new weight slices while the counter is up (the 256
 // blocks run in lock step, so the whole chip's stream pauses around every hop).  Measured per hop: the hops of kernel Y and the
-// p1 hop of kernel X pay, the p2 hop does not (bits of TTS_FUSED_QUIET).  Bounded wait: the stream resumes on its own after
-// 2 048 looks (~0.1 ms); the tags decide correctness, the counter only delays requests.
-#ifndef TTS_FUSED_QUIET
-#define TTS_FUSED_QUIET 3          // bit 0: the p1 hop of kernel X, bit 2: its p2 hop, bit 1: the hops of kernel Y
-#endif
-#ifndef TTS_FUSED_QUIET_LEAD
-#define TTS_FUSED_QUIET_LEAD 30    // > 0: the window opens this many 10-ns ticks before the first look instead of at the publish
-#endif
-template <int KERNEL>
+// p1 hop of kernel X pay and have a window, the p2 hop of kernel X does not and has none.  Bounded wait: the stream resumes on
+// its own after 2 048 looks (~0.1 ms); the tags decide correctness, the counter only delays requests.
 __device__ __forceinline__ void quiet_begin(lds_int* ctl, int lane) {
-    if constexpr ((TTS_FUSED_QUIET >> KERNEL) & 1)
-        if (lane == 0) __hip_atomic_fetch_add(ctl + 7, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (lane == 0) __hip_atomic_fetch_add(ctl + 7, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-template <int KERNEL>
 __device__ __forceinline__ void quiet_end(lds_int* ctl, int lane) {
-    if constexpr ((TTS_FUSED_QUIET >> KERNEL) & 1)
-        if (lane == 0) __hip_atomic_fetch_add(ctl + 7, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (lane == 0) __hip_atomic_fetch_add(ctl + 7, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 // the delay a role wave sleeps through BEFORE it opens its quiet window
-__device__ __forceinline__ int quiet_pre(int delay) { return TTS_FUSED_QUIET_LEAD > 0 ? max(0, delay - TTS_FUSED_QUIET_LEAD) : 0; }
+__device__ __forceinline__ int quiet_pre(int delay) { return max(0, delay - QUIET_LEAD); }
 __device__ __forceinline__ void stream_gate(const lds_int* ctl) {
-#if TTS_FUSED_QUIET
     int spins = 0;
     while (lds_peek(ctl + 7) > 0 && ++spins < 2048) __builtin_amdgcn_s_sleep(2);
-#endif
 }
 
 // ================================================================================================== kernel X
@@ -532,7 +392,6 @@ __global__ __launch_bounds__(NTHR) void fused_x_kernel(const FusedArgs a, const 
     if (wave == 0) FTR(0, 8);
     if (wave == 4) FTR(0, 0);
 
-
     auto store_staged = [&]() {
 #pragma unroll
         for (int i = 0; i < NS1; ++i) {
@@ -597,7 +456,7 @@ __global__ __launch_bounds__(NTHR) void fused_x_kernel(const FusedArgs a, const 
         if (ctl[0] != 0) return;
         if (s.early_stop && ctl[1] >= B) return;      // every row has fired: the loop ends here, nothing is modified
         fma_slice<NBT>(acc, wl.g[0], wl.g[1], wl.g[2], wl.g[3], p2s, PRE, lane);
-        const float v = reduce_v<V>(acc, lane);
+        const float v = reduce_lanes<V>(acc, lane);
         if (wave == 0) FTR(0, 12);
         lstm_finish<NBT>(v, lane, B, bias4, c_old, a.catt, a.hatt + (size_t)(par ^ 1) * B * RNN, u);
         if (blk == 0 && tid == 0) a.st->exec_t = t + 1;
@@ -609,7 +468,7 @@ __global__ __launch_bounds__(NTHR) void fused_x_kernel(const FusedArgs a, const 
     const int r = wave - 4;
     __builtin_amdgcn_s_setprio(3);                    // the chain is the critical path; the LSTM waves fill the gaps
     WavePoll P;
-    P.rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.xch, 0, 0x80000000u, 0x00020000);
+    P.rs = rsrc_of(a.xch);
     P.flags = a.flags;
     P.abort_s = ctl;
     const bool is_p1 = (r == 0 || r == 3) && step_on, is_p2 = r == 1 && step_on, is_proj = r == 2 && frame_on && blk <= NMEL;
@@ -675,12 +534,12 @@ __global__ __launch_bounds__(NTHR) void fused_x_kernel(const FusedArgs a, const 
         }
         wait_stamp(P, ctl + 2, quiet_pre(a.delay[0]));
         wait_stamp(P, ctl + 3, quiet_pre(a.delay[0]));
-        quiet_begin<0>(ctl, lane);
+        quiet_begin(ctl, lane);
         wait_stamp(P, ctl + 2, a.delay[0]);
         wait_stamp(P, ctl + 3, a.delay[0]);
         f32x2 pv[2 * NBT];
         poll_pairs<2 * NBT>(P, ent, tag, pv);
-        quiet_end<0>(ctl, lane);
+        quiet_end(ctl, lane);
         float sm[NBT];
 #pragma unroll
         for (int b = 0; b < NBT; ++b) {
@@ -702,11 +561,9 @@ __global__ __launch_bounds__(NTHR) void fused_x_kernel(const FusedArgs a, const 
             ent[i] = X.p2 + 2u * (unsigned)(pair[i] < B * PRE / 2 ? pair[i] : 0);
         }
         wait_stamp(P, ctl + 4, quiet_pre(a.delay[1]));
-        quiet_begin<2>(ctl, lane);
         wait_stamp(P, ctl + 4, a.delay[1]);
         f32x2 pv[NQ];
         poll_pairs<NQ>(P, ent, tag, pv);
-        quiet_end<2>(ctl, lane);
 #pragma unroll
         for (int i = 0; i < NQ; ++i)
             if (pair[i] < B * PRE / 2) *reinterpret_cast<f32x2*>(p2s + 2 * pair[i]) = pv[i];
@@ -849,7 +706,6 @@ __global__ __launch_bounds__(NTHR) void fused_y_kernel(const FusedArgs a, const 
     if (wave == 0) FTR(1, 10);
     if (wave == 4) FTR(1, 0);
 
-
     auto store_staged = [&]() {
 #pragma unroll
         for (int i = 0; i < NS1; ++i) {
@@ -908,7 +764,7 @@ __global__ __launch_bounds__(NTHR) void fused_y_kernel(const FusedArgs a, const 
 #pragma unroll
         for (int c = 0; c < NC; ++c)
             fma_slice<NBT>(acc, wlate[c].g[0], wlate[c].g[1], wlate[c].g[2], wlate[c].g[3], xs + RNN + c * 256, KX, lane);
-        const float v = reduce_v<V>(acc, lane);
+        const float v = reduce_lanes<V>(acc, lane);
         lstm_finish<NBT>(v, lane, B, bias4, c_old, a.cdec, a.hdec + (size_t)(par ^ 1) * B * RNN, u);
         if (blk == 0 && tid == 0) a.st->steps_run = t + 1;
         if (wave == 0) FTR(1, 14);
@@ -917,7 +773,7 @@ __global__ __launch_bounds__(NTHR) void fused_y_kernel(const FusedArgs a, const 
     // ---------------------------------------------------------------------------------------------- role waves
     __builtin_amdgcn_s_setprio(3);
     WavePoll P;
-    P.rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.xch, 0, 0x80000000u, 0x00020000);
+    P.rs = rsrc_of(a.xch);
     P.flags = a.flags;
     P.abort_s = ctl;
     store_staged();
@@ -1035,7 +891,7 @@ __global__ __launch_bounds__(NTHR) void fused_y_kernel(const FusedArgs a, const 
         }
         if (g_id < B * Tin) {                         // this wave owns at least one position
             wait_stamp(P, ctl + 2, quiet_pre(a.delay[2]));
-            quiet_begin<1>(ctl, lane);
+            quiet_begin(ctl, lane);
             wait_stamp(P, ctl + 2, a.delay[2]);
             unsigned ent[NPOS];
 #pragma unroll
@@ -1045,7 +901,7 @@ __global__ __launch_bounds__(NTHR) void fused_y_kernel(const FusedArgs a, const 
             }
             f32x2 qv[NPOS];
             poll_pairs<NPOS>(P, ent, tag, qv);
-            quiet_end<1>(ctl, lane);
+            quiet_end(ctl, lane);
             if (r == 0) FTR(1, 4);
 #pragma unroll
             for (int p = 0; p < NPOS; ++p) {
@@ -1081,13 +937,13 @@ __global__ __launch_bounds__(NTHR) void fused_y_kernel(const FusedArgs a, const 
             }
             if (p == 0) {
                 wait_stamp(P, ctl + 2, quiet_pre(a.delay[2]));
-                quiet_begin<1>(ctl, lane);
+                quiet_begin(ctl, lane);
                 wait_stamp(P, ctl + 2, a.delay[2]);
             }
             unsigned ent[1] = {X.q + (unsigned)b * ATT + (unsigned)lane * 2};
             f32x2 qv[1];
             poll_pairs<1>(P, ent, tag, qv);
-            if (p == 0) quiet_end<1>(ctl, lane);
+            if (p == 0) quiet_end(ctl, lane);
             if (r == 0 && p == 0) FTR(1, 4);
             float e = vv[0] * tanh_fast(qv[0][0] + loc[0]);
             e = fmaf(vv[1], tanh_fast(qv[0][1] + loc[1]), e);
@@ -1119,11 +975,11 @@ __global__ __launch_bounds__(NTHR) void fused_y_kernel(const FusedArgs a, const 
             ent[k] = rowe + (unsigned)(tau < X.TinP ? tau : 0);
         }
         wait_stamp(P, ctl + 3, quiet_pre(a.delay[3]));
-        quiet_begin<1>(ctl, lane);
+        quiet_begin(ctl, lane);
         wait_stamp(P, ctl + 3, a.delay[3]);
         f32x2 ev[KT];
         poll_pairs<KT>(P, ent, tag, ev);              // (also drains this wave's LDS-DMA of the memory slice: vmcnt is in order)
-        quiet_end<1>(ctl, lane);
+        quiet_end(ctl, lane);
         if (r == 0) FTR(1, 6);
         // attention window (tacotron2_arch.py:630-638); inclusive upper bound
         int lo = 0, hi = Tin;
@@ -1219,11 +1075,11 @@ __global__ __launch_bounds__(NTHR) void fused_y_kernel(const FusedArgs a, const 
             ent[i] = X.ctx + 2u * (unsigned)(pair[i] < B * ENC / 2 ? pair[i] : 0);
         }
         wait_stamp(P, ctl + 4, quiet_pre(a.delay[4]));
-        quiet_begin<1>(ctl, lane);
+        quiet_begin(ctl, lane);
         wait_stamp(P, ctl + 4, a.delay[4]);
         f32x2 cv[NQ];
         poll_pairs<NQ>(P, ent, tag, cv);
-        quiet_end<1>(ctl, lane);
+        quiet_end(ctl, lane);
 #pragma unroll
         for (int i = 0; i < NQ; ++i)
             if (pair[i] < B * ENC / 2) {

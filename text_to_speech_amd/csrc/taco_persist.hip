@@ -47,7 +47,6 @@ using namespace ttsxch;
 
 namespace {
 
-
 constexpr int NBLK = 256;                 // blocks = CUs of an MI355X; 4 units per block x 256 = 1024 units
 constexpr int PRE = 256, RNN = 1024, ATT = 128, NMEL = 80, LOCK = 31;
 constexpr int PMW = 36;                   // floats per (row, position) of the LDS copy of PM: 16 att | 16 dec | F | proj | pad
@@ -104,7 +103,7 @@ constexpr int TR_STEPS = 256, TR_SLOTS = 20;
 #define TR(slot)                                                                                                  \
     do {                                                                                                          \
         if (a.trace && lane == 0 && t < TR_STEPS) {                                                               \
-            const int tb_ = blk == 0 ? 0 : blk == 80 ? 1 : blk == 200 ? 2 : blk == 255 ? 3 : -1;                  \
+            const int tb_ = trace_block(blk);                                                                     \
             if (tb_ >= 0) a.trace[((size_t)tb_ * TR_STEPS + t) * TR_SLOTS + (slot)] = (long long)wall_clock64(); \
         }                                                                                                         \
     } while (0)
@@ -112,39 +111,8 @@ constexpr int TR_STEPS = 256, TR_SLOTS = 20;
 #define TR(slot) do { } while (0)
 #endif
 
-// Lane-halving reduction of V (= 4, 8 or 16) per-lane partial sums.  Halving step s pairs lane with lane ^ (1 << s) inside
-// its row of 16 (DPP): lanes with bit s clear keep the lower half of the values and receive the partner's, the others the
-// upper half -- so after log2 V steps a lane holds ONE value, index = bit reversal of its low log2 V lane bits.  The rest
-// of the row is folded with rotations (which preserve those bits), the four rows with two ds_bpermute steps.  Every lane
-// whose low bits are bitrev(i) ends up with the wave total of value i.
-template <int V>
-__device__ __forceinline__ float reduce_multi(float (&acc)[V], int lane) {
-    constexpr int LOGV = V == 4 ? 2 : V == 8 ? 3 : 4;
-    auto halve = [&](auto S, int half) {
-        const bool hi = (lane >> decltype(S)::value) & 1;
-#pragma unroll
-        for (int i = 0; i < V / 2; ++i) {
-            if (i < half) {
-                float a_lo = acc[i], a_hi = acc[i + half];
-                asm volatile("" : "+v"(a_lo), "+v"(a_hi));      // keeps select(load, load) from becoming an indexed load
-                const float send = hi ? a_lo : a_hi;
-                const float keep = hi ? a_hi : a_lo;
-                acc[i] = keep + row_xor<decltype(S)::value>(send, lane);
-            }
-        }
-    };
-    halve(std::integral_constant<int, 0>{}, V / 2);
-    halve(std::integral_constant<int, 1>{}, V / 4);
-    if constexpr (LOGV >= 3) halve(std::integral_constant<int, 2>{}, V / 8);
-    if constexpr (LOGV >= 4) halve(std::integral_constant<int, 3>{}, V / 16);
-    float v = acc[0];
-    if constexpr (LOGV == 2) v += dpp<DPP_ROR4>(v);
-    if constexpr (LOGV <= 3) v += dpp<DPP_ROR8>(v);
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-// V = 4 (batch 1): the four totals broadcast to every lane through scalar registers instead (no LDS round trips at all)
+// V = 4 (batch 1) instead of reduce_lanes: the four totals broadcast to every lane through scalar registers (no LDS round
+// trips at all)
 __device__ __forceinline__ void reduce4_bcast(float (&acc)[4], int lane, float& t0, float& t1, float& t2, float& t3) {
     auto halve = [&](auto S, int half) {
         const bool hi = (lane >> decltype(S)::value) & 1;
@@ -168,13 +136,8 @@ __device__ __forceinline__ void reduce4_bcast(float (&acc)[4], int lane, float& 
     t2 = (lane_bcast(v, 1) + lane_bcast(v, 17)) + (lane_bcast(v, 33) + lane_bcast(v, 49));
     t3 = (lane_bcast(v, 3) + lane_bcast(v, 19)) + (lane_bcast(v, 35) + lane_bcast(v, 51));
 }
-// lane that holds value `idx` after reduce_multi<V> (row 0)
-template <int V>
-__device__ __forceinline__ int reduced_lane(int idx) {
-    constexpr int LOGV = V == 4 ? 2 : V == 8 ? 3 : 4;
-    return (int)(__brev((unsigned)idx) >> (32 - LOGV));
-}
 
+// Separate from WavePoll (taco_fused.hip) on purpose: abort checks every 255 / 2 047 polls, own sleep cadence, generic abort pointer.
 struct Poller {
     __amdgpu_buffer_rsrc_t rs;            // the whole exchange area
     int* flags;                           // global: [0] abort code
@@ -364,11 +327,6 @@ __device__ __forceinline__ void gemv_acc(float (&acc)[4 * NBT], const WV (&W)[4]
         }
 }
 
-template <class WV, class EL>
-__device__ __forceinline__ WV load_w(const void* base, long long elem) {
-    return *reinterpret_cast<const WV*>((const EL*)base + elem);
-}
-
 // NBT: batch rows carried (B <= NBT, padded rows compute zeros); KT: ceil(Tin / 64) bound; HW: fp16 LSTM matrices
 template <int NBT, int KT, bool HW>
 __global__ __launch_bounds__(256) void decoder_persist_kernel(const PersistArgs a) {
@@ -376,8 +334,7 @@ __global__ __launch_bounds__(256) void decoder_persist_kernel(const PersistArgs 
     constexpr int TP = KT * 64;                      // padded position count
     constexpr int WS = TP + 32;                      // alignment rows with a 16-entry zero halo on each side
     constexpr int NPOS = (NBT * TP + NBLK - 1) / NBLK;      // (row, position) pairs a wave 3 may own
-    typedef typename std::conditional<HW, f16x4, f32x4>::type wv_t;
-    typedef typename std::conditional<HW, _Float16, float>::type wel_t;
+    typedef typename WT<HW>::vec wv_t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blk = blockIdx.x;
     const int B = a.B, Tin = a.Tin, enc = a.enc, max_len = a.max_len;
@@ -413,12 +370,12 @@ __global__ __launch_bounds__(256) void decoder_persist_kernel(const PersistArgs 
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const long long ra = (long long)(4 * u + g) * a.KA, rd = (long long)(4 * u + g) * a.KD;
-        WA[g][0] = load_w<wv_t, wel_t>(a.Wa, ra + lane * 4);
+        WA[g][0] = load_w<HW, false>(a.Wa, ra + lane * 4);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            WA[g][1 + i] = load_w<wv_t, wel_t>(a.Wa, ra + PRE + enc + i * 256 + lane * 4);
-            WD[g][i] = load_w<wv_t, wel_t>(a.Wd, rd + i * 256 + lane * 4);
-            WD[g][4 + i] = load_w<wv_t, wel_t>(a.Wd, rd + RNN + enc + i * 256 + lane * 4);
+            WA[g][1 + i] = load_w<HW, false>(a.Wa, ra + PRE + enc + i * 256 + lane * 4);
+            WD[g][i] = load_w<HW, false>(a.Wd, rd + i * 256 + lane * 4);
+            WD[g][4 + i] = load_w<HW, false>(a.Wd, rd + RNN + enc + i * 256 + lane * 4);
         }
     }
     const f32x4 biasA = *reinterpret_cast<const f32x4*>(a.ba + 4 * u);
@@ -464,7 +421,7 @@ __global__ __launch_bounds__(256) void decoder_persist_kernel(const PersistArgs 
 
     const Xch X = xch_layout(B, Tin);
     Poller P;
-    P.rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.xch, 0, 0x80000000u, 0x00020000);
+    P.rs = rsrc_of(a.xch);
     P.flags = a.flags;
     P.abort_s = ctl;
     __syncthreads();
@@ -622,7 +579,7 @@ __global__ __launch_bounds__(256) void decoder_persist_kernel(const PersistArgs 
             if constexpr (NBT == 1) {
                 reduce4_bcast(accA, lane, gi, gf, gg, go);
             } else {
-                const float v = reduce_multi<V>(accA, lane);
+                const float v = reduce_lanes<V>(accA, lane);
                 gi = __shfl(v, src_i, 64), gf = __shfl(v, src_f, 64), gg = __shfl(v, src_c, 64), go = __shfl(v, src_o, 64);
             }
             if (writer) {
@@ -764,7 +721,7 @@ __global__ __launch_bounds__(256) void decoder_persist_kernel(const PersistArgs 
             if constexpr (NBT == 1) {
                 reduce4_bcast(accD, lane, gi, gf, gg, go);
             } else {
-                const float v = reduce_multi<V>(accD, lane);
+                const float v = reduce_lanes<V>(accD, lane);
                 gi = __shfl(v, src_i, 64), gf = __shfl(v, src_f, 64), gg = __shfl(v, src_c, 64), go = __shfl(v, src_o, 64);
             }
             if (writer) {
