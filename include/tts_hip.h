@@ -341,6 +341,43 @@ int tts_hip_trim_silence(tts_hip_engine* e, const float* audio, int B, int N, co
                          double threshold, double add_start, double add_end, int mode, int32_t* start, int32_t* end,
                          int mem);
 
+/* ---- silence removal (csrc/silence.hip; no weights needed): the remaining numpy trim methods of
+ * utils/audio/audio_processing.py, sample for sample, with the kept samples compacted on the device.
+ * audio [B, N] -> out [B, N]: row b's kept samples in order, then zeros (out[b, out_lengths[b]:] = 0); out_lengths int32
+ * [B] (follows `mem` / device memory for the _async form; a row may come out empty: 0).  Row b holds lengths[b]
+ * (1 <= lengths[b] <= N) samples, lengths NULL = N for every row; nothing at or beyond lengths[b] is read (it may hold NaN)
+ * and a row's result equals a one-row call on audio[b, :lengths[b]].  `lengths` is host memory in every mode.
+ * method TTS_HIP_SILENCE_RMS (audio_processing.py:100-200): blocks of block_size samples (the last one zero-padded), a block
+ *   is silent when sqrtf(max x*x) < (float)10^(threshold / 20) (threshold in dB); a run of silent blocks [i, j) lasting
+ *   >= min_silence seconds is a silence with bounds s = i * bt, e = min(L / rate, j * bt) seconds (bt = block_size / rate,
+ *   doubles); neighbours closer than min_voice_time seconds merge (0: never); sample bounds are (int)(s * rate) and
+ *   (int)(e * rate), the truncated double products, not i * block_size.  mode 0 start_end, 1 start, 2 end keep one slice
+ *   [a, b): a leading silence is cut to its last replace_by samples, a trailing one (ending within one sample of the row's
+ *   end) to its first replace_by samples; mode 3 remove also cuts every interior silence to replace_by / 2 samples at each
+ *   side.  A row without any silence is returned unchanged in every mode (the reference raises IndexError in modes 0 - 2).
+ *   block_size >= 1 and replace_by >= 0 are in samples.
+ * method TTS_HIP_SILENCE_THRESHOLD (:385-394): m = (float)mean(x) (an fp64 sum rounded once; numpy's fp32 pairwise mean may
+ *   differ from it in the last bit, so a sample within that of the threshold may be judged differently); with idx the samples where fabsf(x - m) >
+ *   (float)threshold, the row keeps [first idx (mode 0, 1) or 0, last idx exclusive (mode 0, 2) or L); no such sample:
+ *   unchanged.  Uses threshold and mode only.
+ * method TTS_HIP_SILENCE_MEAN_WINDOW (:372-383, the reference's 'remove' method): w = (int)(min_silence * rate); conv =
+ *   np.convolve(x * x, ones(w) / (w * threshold), 'same') with fp32 squares and fp64 sums; keeps the samples whose conv >
+ *   min(threshold, mean(conv) / 2).  Uses threshold, min_silence and rate; mode must be 0, 1 or 2 and is ignored.
+ * Parameters a method does not use are ignored.  Refused with TTS_HIP_EINVAL before anything is copied or launched (the
+ * message starts with "remove_silence" / "remove_silence_async"): a method or mode out of range; mode 3 with a method other
+ * than rms; rate <= 0; block_size < 1 or replace_by < 0 (rms); a non-finite or negative threshold, min_silence or
+ * min_voice_time where the method uses it (the rms threshold, in dB, need only be finite); threshold <= 0, w < 1 or a row
+ * shorter than w (mean-window; the reference fails with IndexError there; the message names L and w); out overlapping
+ * audio; B > 65535, N > 2^24 or B * N * 4 >= 2^31.  The call shares the clean-up workspace of the handle (see reduce_noise) and is
+ * enqueued whole, without a host round trip between its stages: the _async form does not synchronize.                   */
+enum { TTS_HIP_SILENCE_RMS = 0, TTS_HIP_SILENCE_THRESHOLD = 1, TTS_HIP_SILENCE_MEAN_WINDOW = 2 };
+int tts_hip_remove_silence(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int method, int mode,
+                           int rate, double threshold, double min_silence, int block_size, int replace_by,
+                           double min_voice_time, float* out, int32_t* out_lengths, int mem);
+int tts_hip_remove_silence_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int method,
+                                 int mode, int rate, double threshold, double min_silence, int block_size, int replace_by,
+                                 double min_voice_time, float* out, int32_t* out_lengths, void* stream);
+
 /* ---- resampling (csrc/resample.hip; no weights needed)
  * scipy.signal.resample(x, int(n / rate * target_rate)) per row (utils/audio/audio_processing.py:30-35), window=None, in
  * fp32 (scipy returns float64).  audio [B, N] -> out [B, M]; M must be (int)((double)N / rate * target_rate) >= 1.  Row b

@@ -86,6 +86,10 @@ SIGNATURES = {
                                            c_void_p]),
     'tts_hip_trim_silence': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_double, c_double, c_double, c_int,
                                      c_void_p, c_void_p, c_int]),
+    'tts_hip_remove_silence': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double, c_double,
+                                       c_int, c_int, c_double, c_void_p, c_void_p, c_int]),
+    'tts_hip_remove_silence_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double,
+                                             c_double, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     'tts_hip_resample': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     'tts_hip_resample_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
 }

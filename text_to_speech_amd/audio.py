@@ -5,8 +5,12 @@ reduce_noise -> normalize again -> trim_silence, in that order.  Normalization i
 resampling, noise reduction and the trim indices run on the GPU (HipEngine.resample / reduce_noise / trim_silence,
 csrc/resample.hip, csrc/audio_proc.hip).  Resampling is opt-in (`resample=True`): by default a file at another rate
 raises, as before.  It differs from the reference in one way: the reference resamples the raw int16 samples in float64
-(scipy.signal.resample), here they become float32 (exactly) and are resampled in fp32 on the device.  The trim methods
-other than 'window' are not provided: asking for them raises.
+(scipy.signal.resample), here they become float32 (exactly) and are resampled in fp32 on the device.
+
+`trim_silence` is the reference's public dispatcher (audio_processing.py:84-98) for one row: method 'window' (the trim
+indices above), 'rms', 'threshold' and 'remove' (HipEngine.remove_silence, csrc/silence.hip: silence mask and compaction on
+the GPU, sample for sample what the reference's numpy gives).  The 'ffmpeg' method shells out to a program and is refused.
+`load_audio` itself still takes method='window' only; trim its result with `trim_silence` for the other methods.
 """
 from __future__ import annotations
 
@@ -51,7 +55,8 @@ def load_audio(data, rate=None, *, engine, normalize=True, reduce_noise=False, t
     resample=False: a file at another rate raises.  resample=True: audio at another rate (the file's header, a dict's
     'rate' entry, or `source_rate=` for raw samples) is resampled to `rate` on `engine` before normalization, as the
     reference does.  Raw samples need `rate`.  kwargs: `noise`, `noise_length` for reduce_noise; `threshold`,
-    `window_length`, `add_start`, `add_end`, `mode` for trim_silence."""
+    `window_length`, `add_start`, `add_end`, `mode` for trim_silence.  Only method='window' is accepted here; for 'rms',
+    'threshold' or 'remove' load without trimming and pass the result to `trim_silence(audio, engine=..., rate=..., method=...)`."""
     if trim_silence and method != 'window':
         raise ValueError(f"trim_silence: only method='window' is implemented (got {method!r})")
     unknown = set(kwargs) - set(_RN_KEYS) - set(_TRIM_KEYS)
@@ -95,6 +100,35 @@ def load_audio(data, rate=None, *, engine, normalize=True, reduce_noise=False, t
         start, end = engine.trim_silence(np.asarray(audio, np.float32), rate, **tr)
         audio = audio[start:end]
     return audio
+
+
+TRIM_METHODS = ('window', 'rms', 'threshold', 'remove')
+_WINDOW_KEYS = ('threshold', 'window_length', 'add_start', 'add_end', 'mode')
+_SILENCE_KEYS = ('mode', 'threshold', 'min_silence', 'block_size', 'replace_by', 'min_voice_time')
+
+
+def trim_silence(audio, *, engine, rate=None, method='window', **kwargs):
+    """audio_processing.trim_silence (:84-98) for one row [n] -> the trimmed float32 row.  'window': engine.trim_silence's
+    indices, sliced (keywords threshold, window_length, add_start, add_end, mode).  'rms' (mode, threshold in dB, min_silence,
+    block_size, replace_by, min_voice_time), 'threshold' (threshold, mode) and 'remove' (the mean-window method: threshold,
+    min_silence): engine.remove_silence, which needs `rate`.  A row in which 'rms' finds no silence comes back unchanged
+    (the reference raises IndexError unless mode is 'remove').  'ffmpeg' and unknown names raise ValueError."""
+    if isinstance(method, bytes):
+        method = method.decode()
+    if method not in TRIM_METHODS:
+        raise ValueError(f'trim_silence: method {method!r} is not supported (supported: {", ".join(TRIM_METHODS)})')
+    allowed = _WINDOW_KEYS if method == 'window' else _SILENCE_KEYS
+    unknown = set(kwargs) - set(allowed)
+    if unknown:
+        raise ValueError(f'trim_silence: unknown arguments {sorted(unknown)} for method {method!r}')
+    audio = audio.detach().cpu().numpy() if hasattr(audio, 'detach') else np.asarray(audio)
+    if audio.ndim != 1:
+        raise ValueError(f'trim_silence: expected one row [n], got shape {audio.shape}')
+    audio = np.asarray(audio, np.float32)
+    if method == 'window':
+        start, end = engine.trim_silence(audio, rate, **kwargs)
+        return audio[start:end]
+    return engine.remove_silence(audio, rate, method=method, **kwargs)
 
 
 MEL_RATE = 22050                    # TacotronSTFT's sampling rate (engine.mel_stft's filterbank)

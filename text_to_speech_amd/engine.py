@@ -900,6 +900,97 @@ class HipEngine:
             return int(start[0]), int(end[0])
         return start, end
 
+    # ------------------------------------------------------------------ silence removal (csrc/silence.hip)
+    _SILENCE_METHODS = {'rms': 0, 'threshold': 1, 'remove': 2}
+    _SILENCE_MODES = {'start_end': 0, 'start': 1, 'end': 2, 'remove': 3}
+    _SILENCE_DEFAULTS = {'rms': (-25, 0.1), 'threshold': (0.1, 0.), 'remove': (0.025, 0.15)}    # threshold, min_silence
+    _SILENCE_MAX = 1 << 24          # samples per row
+
+    def remove_silence(self, audio, rate, lengths=None, method='rms', mode='start_end', threshold=None, min_silence=None,
+                       block_size=0.01, replace_by=0.5, min_voice_time=0.2, stream=None):
+        """The reference's numpy trim methods (utils/audio/audio_processing.py), sample for sample, with the kept samples
+        compacted on the GPU (csrc/silence.hip).  method 'rms' (:100-200; `threshold` in dB, default -25; `min_silence` 0.1 s;
+        `block_size`, `replace_by`: seconds as floats, samples as ints; `min_voice_time` seconds, 0 disables the merging;
+        mode start, end, start_end or remove, which also shortens the pauses inside), 'threshold' (:385-394; `threshold` an
+        amplitude, default 0.1; mode start, end or start_end) or 'remove' (:372-383, the mean-window method; `threshold`
+        0.025, `min_silence` 0.15 s; rows must hold at least int(min_silence * rate) samples).  threshold / min_silence None:
+        the method's reference default.  A row in which the rms method finds no silence is returned unchanged (the reference
+        raises IndexError in the three slice modes).  audio [N] (numpy) -> the kept samples, 1-D; [B, N] -> (out [B, N],
+        out_lengths [B]): row b is the result of a one-row call on audio[b, :lengths[b]] (default N), then zeros.  A CUDA
+        tensor in ([N] or [B, N]) -> CUDA tensors (out, int32 out_lengths) of the input's rank, without synchronization of
+        the lengths; `stream` (torch.cuda.Stream, device tensors only): enqueue there and return without waiting (the
+        clean-up calls share one workspace per engine: the next one must be ordered after it)."""
+        B, N, lens = self._audio_rows(audio, lengths, 'remove_silence')
+        if isinstance(method, bytes):
+            method = method.decode()
+        if isinstance(mode, bytes):
+            mode = mode.decode()
+        if method not in self._SILENCE_METHODS:
+            raise ValueError(f'remove_silence: unknown method {method!r} (supported: {sorted(self._SILENCE_METHODS)})')
+        if mode not in self._SILENCE_MODES:
+            raise ValueError(f'remove_silence: invalid mode {mode!r} (start, end, start_end or remove)')
+        if mode == 'remove' and method != 'rms':
+            raise ValueError(f"remove_silence: mode 'remove' belongs to method 'rms' (got method {method!r})")
+        if rate is None or int(rate) != rate or rate <= 0:
+            raise ValueError(f'remove_silence: rate must be a positive integer (got {rate})')
+        rate = int(rate)
+        d_thr, d_sil = self._SILENCE_DEFAULTS[method]
+        threshold = d_thr if threshold is None else threshold
+        min_silence = d_sil if min_silence is None else min_silence
+        bs = rb = 1
+        if method == 'rms':
+            bs = self._samples(block_size, rate, 'remove_silence: block_size')
+            rb = self._samples(replace_by, rate, 'remove_silence: replace_by')
+            if bs < 1:
+                raise ValueError(f'remove_silence: block_size must be >= 1 sample (got {bs})')
+            if not 0 <= rb < 1 << 31:
+                raise ValueError(f'remove_silence: replace_by must be >= 0 samples (got {rb})')
+            if not np.isfinite(min_voice_time) or min_voice_time < 0:
+                raise ValueError(f'remove_silence: min_voice_time must be finite and >= 0 (got {min_voice_time})')
+            bs = min(bs, 1 << 30)
+        else:
+            min_voice_time = 0.
+        if not np.isfinite(threshold) or (method != 'rms' and threshold < 0):
+            raise ValueError(f'remove_silence: threshold must be finite{"" if method == "rms" else " and >= 0"} (got {threshold})')
+        if not np.isfinite(min_silence) or min_silence < 0:
+            raise ValueError(f'remove_silence: min_silence must be finite and >= 0 (got {min_silence})')
+        if method == 'remove':
+            w = int(min_silence * rate)
+            shortest = N if lens is None else int(lens.min())
+            if threshold <= 0 or w < 1:
+                raise ValueError(f'remove_silence: the mean-window method needs threshold > 0 and a window of w >= 1 samples '
+                                 f'(got threshold {threshold}, w = {w})')
+            if shortest < w:
+                raise ValueError(f'remove_silence: a row of L = {shortest} samples is shorter than the window w = {w}')
+        if B > 65535 or N > self._SILENCE_MAX or B * N * 4 >= 1 << 31:
+            raise ValueError(f'remove_silence: B = {B} x N = {N} too large (B <= 65535, N <= 2^24, B * N * 4 < 2^31)')
+        args = (self._SILENCE_METHODS[method], self._SILENCE_MODES[mode], rate, float(threshold), float(min_silence), bs, rb,
+                float(min_voice_time))
+        lens_p = lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None
+        one_row = len(audio.shape) == 1
+        if _is_torch_cuda(audio):
+            torch = self._torch()
+            self._check_device(audio)
+
+            def prepared():
+                a_ = audio.to(torch.float32).reshape(B, N).contiguous()
+                return (a_, torch.empty((B, N), dtype=torch.float32, device=a_.device),
+                        torch.empty((B,), dtype=torch.int32, device=a_.device))
+
+            (a, out, out_len), sp = self._staged(stream, prepared, audio)
+            fn, last = ('remove_silence', MEM_DEVICE) if stream is None else ('remove_silence_async', sp)
+            self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(a), B, N, lens_p, *args, self._ptr(out),
+                                                            self._ptr(out_len), last), fn)
+            return (out[0], out_len[0]) if one_row else (out, out_len)
+        if stream is not None:
+            raise ValueError('stream= needs device tensors')
+        a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
+        out, out_len = np.empty((B, N), dtype=np.float32), np.empty(B, np.int32)
+        self._check(self._lib.tts_hip_remove_silence(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens_p, *args,
+                                                     out.ctypes.data_as(ctypes.c_void_p),
+                                                     out_len.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'remove_silence')
+        return out[0, :int(out_len[0])].copy() if one_row else (out, out_len)
+
     # ------------------------------------------------------------------ measurement hooks
     def kernel_timing(self, enable: bool) -> None:
         self._check(self._lib.tts_hip_kernel_timing(self._h, 1 if enable else 0), 'kernel_timing')

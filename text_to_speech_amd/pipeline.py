@@ -42,13 +42,17 @@ class TTSPipeline:
         samples, sample counts [B] int64 device tensor, steps run).
         `reduce_noise` / `trim_silence`: the reference's waveform clean-up (audio_processing.reduce_noise, trim_silence with
         method 'window') on the device, each row with its own sample count as its length, at RATE Hz; trimming changes the
-        lengths, so it needs host output (on_device=False).
+        lengths, so it needs host output (on_device=False).  `trim_silence` is a flag here: a dict of `audio.trim_silence`
+        keywords (as `Tacotron2.infer` takes) is refused, not read as True; trim the returned rows with `audio.trim_silence`.
         `row_ids` [B] (ints, e.g. the global utterance indices `synthesize_sharded(with_ids=True)` hands a rank; excludes
         `prenet_masks`, `z` and `deterministic=True`): row b's dropout masks and noise come from streams of its own, keyed by
         `stream_key(job seed, MASK_STREAM / NOISE_STREAM, row_ids[b], 0, 0)` with the job-wide seed as given (not this rank's
         `rank_stream`); the running offset is untouched.  An utterance then draws the same values in any batch, on any rank
         and at any world size; with `ragged=True` its audio is its own as well (up to fp32 re-association), while the padded
         path (`ragged=False`) keeps hearing the batch's padding."""
+        if isinstance(trim_silence, dict):
+            raise ValueError('synthesize_tokens: trim_silence is a flag (method \'window\'); for another method pass the rows '
+                             'to audio.trim_silence(row, engine=..., rate=..., method=...)')
         if on_device and trim_silence:
             raise ValueError('trim_silence=True needs on_device=False (trimmed rows have new lengths)')
         import torch

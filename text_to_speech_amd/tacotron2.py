@@ -108,8 +108,10 @@ class Tacotron2:
                 'synth_time': time.time() - t0}
 
     def _clean_waveform(self, audio, vocoder, reduce_noise, trim_silence):
-        """The reference's waveform clean-up (audio_processing.reduce_noise, trim_silence(method='window')) at self.rate, on
-        the engine of the vocoder that produced `audio` (the synthesizer's only when the vocoder has none).  With
+        """The reference's waveform clean-up (audio_processing.reduce_noise, trim_silence) at self.rate: `trim_silence` True is
+        method 'window' with its defaults, a non-empty dict holds the keywords of `audio.trim_silence` (e.g. {'method': 'rms',
+        'mode': 'remove'}, which also shortens the pauses inside the utterance); an empty dict, like False, trims nothing.
+        It runs on the engine of the vocoder that produced `audio` (the synthesizer's only when the vocoder has none).  With
         `predict(..., overlap=True)` the synthesizer's handle is busy in the producer thread, and calls on one handle must
         be serialised, so the clean-up has to stay on the vocoder's handle, in the thread that vocodes."""
         eng = getattr(getattr(vocoder, 'compiled_infer', None), 'engine', None) or getattr(self.compiled_infer, 'engine', None)
@@ -118,7 +120,10 @@ class Tacotron2:
         audio = np.asarray(audio, np.float32)
         if reduce_noise:
             audio = eng.reduce_noise(audio, self.rate)
-        if trim_silence:
+        if isinstance(trim_silence, dict) and trim_silence:         # {'method': 'rms', 'mode': 'remove', ...}: audio.trim_silence's keywords
+            from .audio import trim_silence as trim_with_method
+            audio = trim_with_method(audio, engine=eng, rate=self.rate, **trim_silence)
+        elif trim_silence and not isinstance(trim_silence, dict):
             start, end = eng.trim_silence(audio, self.rate)
             audio = audio[start:end]
         return audio
