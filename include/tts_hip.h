@@ -321,6 +321,13 @@ int tts_hip_waveglow_infer_packed_async(tts_hip_engine* e, const float* mel, int
 /* ---- TacotronSTFT.mel_spectrogram  (utils/audio/stft.py:242-274,306-314)
  * audio [B, N] (N >= 1024) -> mel [B, N/256 + 1, 80]                                                                */
 int tts_hip_mel_stft(tts_hip_engine* e, const float* audio, int B, int N, float* mel, int mem);
+/* Test hook (no effect on later calls; used by tests/): runs the code of tts_hip_mel_stft, not a copy, on the same
+ * arguments (and refuses the same ones) up to stage `what` and copies that stage's logical extent to `out` (fp32), with
+ * F = N/256 + 1 frames per row --
+ *   what 0: the reflect-padded rows [B, N + 1024]; what 1: the spectrum [B, F, 1026] (real parts of bins 0 .. 512, then
+ *   the imaginary parts at 513 .. 1025); what 2: the magnitudes [B, F, 513]; what 3: the linear mel [B, F, 80], before
+ *   log(max(., 1e-5)).  Any other `what` is TTS_HIP_EINVAL and launches nothing.                                        */
+int tts_hip_mel_stft_probe(tts_hip_engine* e, const float* audio, int B, int N, int what, float* out, int mem);
 
 /* ---- waveform clean-up (csrc/audio_proc.hip; DFT bases built on first use, no weights needed)
  * reduce_noise: utils/audio/noisereducev1.py:175-290 with the defaults utils/audio/audio_processing.py:65-83 uses.

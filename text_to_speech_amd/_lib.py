@@ -15,7 +15,7 @@ LIB_NAME = 'libtts_hip.so'
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 MEM_HOST, MEM_DEVICE = 0, 1
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class HipLibraryError(RuntimeError):
@@ -60,6 +60,7 @@ SIGNATURES = {
                                        c_int]),
     'tts_hip_last_waveglow_tiles': (c_int, [c_void_p]),
     'tts_hip_mel_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]),
+    'tts_hip_mel_stft_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
     'tts_hip_waveglow_infer_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p]),
     'tts_hip_waveglow_infer_ragged': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int]),
     'tts_hip_waveglow_infer_ragged_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int,

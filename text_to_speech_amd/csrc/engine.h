@@ -286,7 +286,8 @@ int tacotron2_finalize(tts_hip_engine* e);
 void tacotron2_free(tts_hip_engine* e);
 
 int melstft_finalize(tts_hip_engine* e);
-int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_mel);
+int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_mel, int stop = -1,
+                const float** stop_out = nullptr);
 void melstft_free(tts_hip_engine* e);
 void audioproc_free(tts_hip_engine* e);
 void resample_free(tts_hip_engine* e);

@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void mfma_probe_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------- C ABI
 extern "C" {
 
-int tts_hip_abi_version(void) { return 11; }
+int tts_hip_abi_version(void) { return 12; }
 
 int tts_hip_create(int device, tts_hip_engine** out) {
     if (!out) return TTS_HIP_EINVAL;
@@ -627,6 +627,35 @@ int tts_hip_mel_stft(tts_hip_engine* e, const float* audio, int B, int N, float*
     int rc = melstft_run(e, d_in, B, N, d_out);
     if (rc) return rc;
     if (mem == TTS_HIP_MEM_HOST) HIPCHK(e, hipMemcpyAsync(mel, d_out, n_out * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return TTS_HIP_OK;
+}
+
+// Test hook: melstft_run on `audio` up to stage `what`, then the stage's logical extent (row padding dropped) to `out`.
+int tts_hip_mel_stft_probe(tts_hip_engine* e, const float* audio, int B, int N, int what, float* out, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (!e->stft.ready) return set_err(e, TTS_HIP_ENOTREADY, "mel_stft not finalized");
+    if (!audio || !out || B <= 0 || N < 1024 || what < 0 || what > 3)
+        return set_err(e, TTS_HIP_EINVAL, "mel_stft_probe: bad argument (N >= 1024, what 0 .. 3)");
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "mel_stft_probe: bad mem kind %d", mem);
+    HIPCHK(e, hipSetDevice(e->device));
+    const int F = N / 256 + 1;
+    const size_t n_in = (size_t)B * N;
+    const float* d_in = audio;
+    if (mem == TTS_HIP_MEM_HOST) {
+        HIPCHK(e, e->stft.io_in.ensure(n_in * 4));
+        HIPCHK(e, hipMemcpyAsync(e->stft.io_in.p, audio, n_in * 4, hipMemcpyHostToDevice, e->stream));
+        d_in = e->stft.io_in.f();
+    }
+    HIPCHK(e, e->stft.io_out.ensure((size_t)B * F * 80 * 4));       // the linear mel lands here (stage 3 only)
+    const float* src = nullptr;
+    if (int rc = melstft_run(e, d_in, B, N, e->stft.io_out.f(), what, &src)) return rc;
+    // (rows, logical width, stored row stride) of the stage, in floats
+    const size_t rows = what == 0 ? (size_t)B : (size_t)B * F;
+    const size_t width = what == 0 ? (size_t)N + 1024 : what == 1 ? 1026 : what == 2 ? 513 : 80;
+    const size_t pitch = what == 0 ? ((size_t)N + 1024 + 3) / 4 * 4 : what == 1 ? 1056 : what == 2 ? 544 : 80;
+    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    HIPCHK(e, hipMemcpy2DAsync(out, width * 4, src, pitch * 4, width * 4, rows, kout, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return TTS_HIP_OK;
 }

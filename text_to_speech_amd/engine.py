@@ -732,6 +732,29 @@ class HipEngine:
                                                out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'mel_stft')
         return out
 
+    _STFT_STAGES = {'padded': 0, 'spectrum': 1, 'magnitude': 2, 'mel_linear': 3}
+
+    def mel_stft_probe(self, audio, what: str = 'spectrum'):
+        """Test hook (tts_hip_mel_stft_probe): run `mel_stft` on audio [N] or [B, N] (host array, N >= 1024: no short-audio
+        pad here) up to a stage and return what it computed there, with F = N // 256 + 1: what='padded' the reflect-padded
+        rows [B, N + 1024], 'spectrum' [B, F, 1026] (real parts of bins 0 .. 512, then the imaginary parts), 'magnitude'
+        [B, F, 513], 'mel_linear' [B, F, 80] (before log(max(., 1e-5)))."""
+        if what not in self._STFT_STAGES:
+            raise ValueError(f'what must be one of {tuple(self._STFT_STAGES)}, got {what!r}')
+        a = np.asarray(audio, dtype=np.float32)
+        if a.ndim == 1:
+            a = a[None]
+        a = np.ascontiguousarray(a)
+        if a.ndim != 2:
+            raise ValueError(f'audio must be [N] or [B, N], got {a.shape}')
+        B, N = a.shape
+        F = N // 256 + 1
+        shape = {'padded': (B, N + 1024), 'spectrum': (B, F, 1026), 'magnitude': (B, F, 513), 'mel_linear': (B, F, 80)}[what]
+        out = np.empty(shape, dtype=np.float32)
+        self._check(self._lib.tts_hip_mel_stft_probe(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, self._STFT_STAGES[what],
+                                                     out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'mel_stft_probe')
+        return out
+
     # ------------------------------------------------------------------ waveform clean-up (csrc/audio_proc.hip)
     _TRIM_MODES = {'start_end': 0, 'start': 1, 'end': 2}
 
