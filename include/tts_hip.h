@@ -347,6 +347,27 @@ int tts_hip_reduce_noise_async(tts_hip_engine* e, const float* audio, int B, int
 int tts_hip_trim_silence(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int window_length,
                          double threshold, double add_start, double add_end, int mode, int32_t* start, int32_t* end,
                          int mem);
+/* Test hooks (no effect on later calls; used by tests/): they run the code of the calls above, not a copy, on the same
+ * arguments (and refuse the same ones).
+ * reduce_noise_probe stops after stage `what` and copies that stage's logical extent to `out` (fp32, follows `mem`), with
+ * Fr = ceil((N + 2560) / 512) frame slots per row, of which row b uses F_b = 1 + (lengths[b] + 512) / 512, and
+ * Frn = ceil((noise_len + 2048) / 512) noise frame slots, of which row b uses 1 + nl_b / 512 (nl_b = noise_len, or
+ * min(noise_len, lengths[b]) for the default clip).  Slots past a row's own frames hold hop-strided reads into the next
+ * row's padded samples up to `gated`, where they become 0 --
+ *   what 0 padded [B, Fr * 512]: 1024 zeros, the row's lengths[b] samples, zeros; 1 noise_padded [B, Frn * 512] likewise;
+ *   2 spectrum [B, Fr, 2050]: real parts of bins 0 .. 1024, then the imaginary parts, before the gate; 3 noise_spectrum
+ *   [B, Frn, 2050]; 4 power_max [2, B]: max |X|^2 over each row's own signal frames, then over its own noise frames;
+ *   5 threshold [B, 1025] in dB; 6 mask [B, Fr, 1025] as 0 / 1 (0 in the slots past F_b); 7 gated [B, Fr, 2050]: the
+ *   spectrum times 1 - smoothed mask (0 in the slots past F_b); 8 frames [B, Fr, 2048]: the windowed inverse-DFT rows before
+ *   the overlap-add.  Any other `what` is TTS_HIP_EINVAL and launches nothing.  The un-normalised output is the ordinary
+ *   call with renormalize = 0.
+ * trim_silence_probe runs the convolution launches of trim_silence and copies conv [B, max(N, W) + 1] (fp64, follows `mem`),
+ *   W = 2 * (window_length / 2): conv[b, :nc_b] = np.convolve(x_b^2, window, 'valid'), nc_b = |lengths[b] - W| + 1; what
+ *   lies at and beyond nc_b is unspecified.                                                                              */
+int tts_hip_reduce_noise_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths,
+                               const float* noise, int noise_len, int what, float* out, int mem);
+int tts_hip_trim_silence_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths,
+                               int window_length, double* conv, int mem);
 
 /* ---- silence removal (csrc/silence.hip; no weights needed): the remaining numpy trim methods of
  * utils/audio/audio_processing.py, sample for sample, with the kept samples compacted on the device.

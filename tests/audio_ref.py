@@ -128,7 +128,12 @@ def trim_window(audio, rate, threshold=0.1, window_length=0.2, add_start=0, add_
     window = np.concatenate([np.linspace(0, 1, window_length // 2),
                              np.linspace(1, 0, window_length // 2)]) / (window_length // 2)
     conv = np.convolve(np.power(audio, 2), window, mode='valid')
-    L = len(audio)
+    return trim_bounds(conv, len(audio), window_length, threshold, add_start, add_end, mode, max_trim_factor)
+
+
+def trim_bounds(conv, L, window_length, threshold=0.1, add_start=0, add_end=1.5, mode='start_end', max_trim_factor=5):
+    """The thresholds and indices of trim_silence_window (audio_processing.py:340-370) from its convolution `conv` of a row
+    of L samples; window_length in samples."""
     start, end = 0, L
     if 'end' in mode:
         th_end = min(threshold, max(np.mean(conv[-window_length:]) * 5, threshold / 50))

@@ -28,7 +28,8 @@ def test_header_and_binding_agree(lib):
     from text_to_speech_amd import _lib
     declared = _declared()
     assert len(declared) >= 14
-    for name in ('tts_hip_mel_stft', 'tts_hip_mel_stft_async', 'tts_hip_mel_stft_probe'):
+    for name in ('tts_hip_mel_stft', 'tts_hip_mel_stft_async', 'tts_hip_mel_stft_probe', 'tts_hip_reduce_noise_probe',
+                 'tts_hip_trim_silence_probe'):
         assert name in declared, name
     assert declared == sorted(_lib.SIGNATURES), 'ctypes SIGNATURES must list exactly the header\'s functions'
 
@@ -39,7 +40,7 @@ def test_every_declared_symbol_is_exported(lib):
 
 
 def test_abi_version_and_null_handle_errors(lib):
-    assert lib.tts_hip_abi_version() == 12
+    assert lib.tts_hip_abi_version() == 13
     assert lib.tts_hip_destroy(None) == -1                       # TTS_HIP_EINVAL, no crash
     assert lib.tts_hip_finalize(None) == -1
     assert lib.tts_hip_has_model(None, b'waveglow') == 0

@@ -73,7 +73,7 @@ def test_rows_calls_are_declared_bound_and_exported():
     declared = set(re.findall(r'\b(tts_hip_\w+)\s*\(', src))
     for name in NEW_CALLS:
         assert name in declared and name in _lib.SIGNATURES and hasattr(lib, name), name
-    assert lib.tts_hip_abi_version() == 12 == _lib.ABI_VERSION
+    assert lib.tts_hip_abi_version() == 13 == _lib.ABI_VERSION
     # a NULL handle is refused before anything else is looked at
     assert lib.tts_hip_random_fill_rows(None, 0, None, None, 1, 4, None, None, None) == -1
     assert lib.tts_hip_waveglow_infer_rows_seeded(None, None, 1, 1, None, None, None, 1.0, None, 0, 0, 0) == -1

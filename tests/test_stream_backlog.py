@@ -238,5 +238,5 @@ def test_ragged_entry_points_are_declared_bound_and_exported():
     for name in ('tts_hip_waveglow_infer_ragged', 'tts_hip_waveglow_infer_ragged_async'):
         assert re.search(r'\bint\s+%s\s*\(' % name, header) and name in _lib.SIGNATURES and hasattr(lib, name)
         assert len(_lib.SIGNATURES[name][1]) == 10
-    assert lib.tts_hip_abi_version() == 12            # additions only
+    assert lib.tts_hip_abi_version() == 13            # additions only
     assert lib.tts_hip_waveglow_infer_ragged(None, None, 1, 1, None, None, ctypes.c_float(1.0), None, 0, 0) == -1

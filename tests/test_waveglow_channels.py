@@ -98,4 +98,4 @@ def test_library_exports_waveglow_channels():
     lib = _lib.load_library()
     assert hasattr(lib, 'tts_hip_waveglow_channels')
     assert lib.tts_hip_waveglow_channels(None) == 0
-    assert lib.tts_hip_abi_version() == 12
+    assert lib.tts_hip_abi_version() == 13

@@ -103,7 +103,7 @@ def test_c_abi_declares_the_packed_calls():
     assert _lib.SIGNATURES['tts_hip_waveglow_infer_packed'] == _lib.SIGNATURES['tts_hip_waveglow_infer_ragged']
     assert _lib.SIGNATURES['tts_hip_waveglow_infer_packed_async'] == _lib.SIGNATURES['tts_hip_waveglow_infer_ragged_async']
     lib = _lib.load_library()
-    assert lib.tts_hip_abi_version() == 12
+    assert lib.tts_hip_abi_version() == 13
     for name in ('tts_hip_waveglow_infer_packed', 'tts_hip_waveglow_infer_packed_async'):
         assert hasattr(lib, name)
     assert lib.tts_hip_waveglow_infer_packed(None, None, 1, 1, None, None, 1.0, None, 0, 0) == -1       # TTS_HIP_EINVAL

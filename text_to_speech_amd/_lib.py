@@ -15,7 +15,7 @@ LIB_NAME = 'libtts_hip.so'
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 MEM_HOST, MEM_DEVICE = 0, 1
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class HipLibraryError(RuntimeError):
@@ -87,6 +87,8 @@ SIGNATURES = {
                                            c_void_p]),
     'tts_hip_trim_silence': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_double, c_double, c_double, c_int,
                                      c_void_p, c_void_p, c_int]),
+    'tts_hip_reduce_noise_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]),
+    'tts_hip_trim_silence_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int]),
     'tts_hip_remove_silence': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double, c_double,
                                        c_int, c_int, c_double, c_void_p, c_void_p, c_int]),
     'tts_hip_remove_silence_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double,

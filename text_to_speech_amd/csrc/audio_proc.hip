@@ -51,6 +51,11 @@ __global__ void audio_pad_rows_kernel(const float* __restrict__ src, long long s
     dst[idx] = v;
 }
 
+// |X|^2 with its two roundings spelled out.  Left to the compiler, re * re + im * im contracts one way in a loop's unrolled
+// body and another way in its remainder, so the same cell gave row maxima one ulp apart under two grid sizes (signal and
+// noise launch), and the two top_db floors that must tie did not.
+__device__ __forceinline__ float power_of(float re, float im) { return __fmaf_rn(re, re, __fmul_rn(im, im)); }
+
 // pmax[b] = max |X|^2 over the row's frames f < F_b (fp32 bit patterns of non-negative values order as unsigned)
 __global__ void audio_power_max_kernel(const float* __restrict__ S, int Fr, const int* __restrict__ fcount,
                                        unsigned* __restrict__ pmax) {
@@ -61,7 +66,7 @@ __global__ void audio_power_max_kernel(const float* __restrict__ S, int Fr, cons
         const long long f = i / NBIN, k = i % NBIN;
         const float* row = S + ((long long)b * Fr + f) * NK;
         const float re = row[k], im = row[NBIN + k];
-        m = fmaxf(m, re * re + im * im);
+        m = fmaxf(m, power_of(re, im));
     }
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     __shared__ float wm[4];
@@ -75,8 +80,9 @@ __global__ void audio_power_max_kernel(const float* __restrict__ S, int Fr, cons
 }
 
 // librosa.amplitude_to_db(|X|, ref=1, amin=1e-20, top_db=80) (noisereducev1.py:66-67): 10 log10(max(p, 1e-40)) clamped in
-// the log domain (1e-40 is an fp32 denormal that flushes to zero), then max(v, rowmax - 80)
-__device__ __forceinline__ float power_db(float p) { return fmaxf(10.f * log10f(p), -400.f); }
+// the log domain (1e-40 is an fp32 denormal that flushes to zero), then max(v, rowmax - 80).  The logarithm is taken in
+// double and rounded once: 10.f * log10f(p) rounds twice on top of log10f's own error, which near -100 dB is 2e-5 dB.
+__device__ __forceinline__ float power_db(float p) { return fmaxf((float)(10.0 * log10((double)p)), -400.f); }
 
 // thresh[b][k] = mean + 1.5 std (population) of the noise clip's dB over its frames (noisereducev1.py:244-247), fp64 sums
 __global__ void audio_noise_thresh_kernel(const float* __restrict__ Sn, int Frn, RowInfo info,
@@ -89,13 +95,13 @@ __global__ void audio_noise_thresh_kernel(const float* __restrict__ Sn, int Frn,
     double s = 0.0;
     for (int f = 0; f < F; ++f) {
         const float re = base[(long long)f * NK + k], im = base[(long long)f * NK + NBIN + k];
-        s += (double)fmaxf(power_db(re * re + im * im), floor_db);
+        s += (double)fmaxf(power_db(power_of(re, im)), floor_db);
     }
     const double mean = s / F;
     double q = 0.0;
     for (int f = 0; f < F; ++f) {
         const float re = base[(long long)f * NK + k], im = base[(long long)f * NK + NBIN + k];
-        const double d = (double)fmaxf(power_db(re * re + im * im), floor_db) - mean;
+        const double d = (double)fmaxf(power_db(power_of(re, im)), floor_db) - mean;
         q += d * d;
     }
     thresh[b * NBIN + k] = (float)(mean + 1.5 * sqrt(q / F));
@@ -110,10 +116,16 @@ __global__ void audio_gate_mask_kernel(const float* __restrict__ S, int Fr, RowI
     if (f < info.frames(b)) {
         const float* row = S + ((long long)b * Fr + f) * NK;
         const float re = row[k], im = row[NBIN + k];
-        const float db = fmaxf(power_db(re * re + im * im), power_db(__uint_as_float(pmax[b])) - 80.f);
+        const float db = fmaxf(power_db(power_of(re, im)), power_db(__uint_as_float(pmax[b])) - 80.f);
         v = db < thresh[b * NBIN + k] ? 1 : 0;
     }
     mask[((long long)b * Fr + f) * NBIN + k] = v;
+}
+
+// probe only: the mask as 0.f / 1.f
+__global__ void audio_mask_f32_kernel(const uint8_t* __restrict__ mask, float* __restrict__ out, long long n) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (float)mask[i];
 }
 
 // X *= 1 - smooth(mask): the 5 x 9 filter outer([1,2,3,2,1]/3, [1,2,3,4,5,4,3,2,1]/5)/15 (noisereducev1.py:81-106) as an
@@ -180,25 +192,26 @@ __device__ double block_sum_d(double v, double* sh) {
     return s;
 }
 
-// normalize_audio(x, max_val=1.) (audio_processing.py:50-62) over the row's own L_b samples: x - mean, / max|x| unless <= 1e-9
+// normalize_audio(x, max_val=1.) (audio_processing.py:50-62) over the row's own L_b samples: x - mean, / max|x| unless <= 1e-9.
+// In double, rounded once (the reference normalises the float64 result of reduce_noise): a mean rounded to fp32 is off by up
+// to 2^-25 |mean|, which the division by m = max|x - mean| turns into 2^-25 |mean| / m of full scale.
 __global__ __launch_bounds__(1024) void audio_renormalize_kernel(float* __restrict__ x, int N, RowInfo info) {
     __shared__ double sh[16];
     const int b = blockIdx.x, L = info.len(b);
     float* r = x + (long long)b * N;
     double s = 0.0;
     for (int t = threadIdx.x; t < L; t += blockDim.x) s += r[t];
-    const float mean = (float)(block_sum_d(s, sh) / L);
-    float m = 0.f;
-    for (int t = threadIdx.x; t < L; t += blockDim.x) m = fmaxf(m, fabsf(r[t] - mean));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    __shared__ float shm[16];
+    const double mean = block_sum_d(s, sh) / L;
+    double m = 0.0;
+    for (int t = threadIdx.x; t < L; t += blockDim.x) m = fmax(m, fabs((double)r[t] - mean));
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+    __shared__ double shm[16];
     __syncthreads();
     if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
     __syncthreads();
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) m = fmaxf(m, shm[i]);
-    const bool scale = m > 1e-9f;
-    const float sc = scale ? 1.f / m : 1.f;
-    for (int t = threadIdx.x; t < L; t += blockDim.x) r[t] = scale ? (r[t] - mean) * sc : r[t] - mean;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) m = fmax(m, shm[i]);
+    const double sc = m > 1e-9 ? 1.0 / m : 1.0;
+    for (int t = threadIdx.x; t < L; t += blockDim.x) r[t] = (float)(((double)r[t] - mean) * sc);
 }
 
 // conv[b][k] = sum_j x[k + j]^2 * w[W - 1 - j], k <= L_b - W (np.convolve 'valid' with L_b >= W; squares rounded to fp32
@@ -435,10 +448,25 @@ hipError_t dft_gemm(const float* A, long long lda, int K, const float* Bt, int N
 
 unsigned blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
 
-// device pointers only; `lengths` / `noise_lens` already validated on the host
+// what a probe copies out: `rows` rows of `width` floats, `pitch` floats apart
+struct RnStage {
+    const float* p;
+    size_t rows, width, pitch;
+};
+
+enum { RN_PADDED, RN_NOISE_PADDED, RN_SPECTRUM, RN_NOISE_SPECTRUM, RN_POWER_MAX, RN_THRESHOLD, RN_MASK, RN_GATED, RN_FRAMES,
+       RN_STAGES };
+
+// device pointers only; `lengths` / `noise_lens` already validated on the host.  stop (tts_hip_reduce_noise_probe): one of
+// RN_* returns right after the launch that completes that stage with *stop_out describing what it wrote (the mask as fp32 in
+// the not yet used frame buffer T; d_out is not touched); -1 runs everything.
 int reduce_noise_run(tts_hip_engine* e, const float* d_audio, int B, int N, const std::vector<int>& lens,
-                     const float* d_noise, int noise_len, int renorm, float* d_out) {
+                     const float* d_noise, int noise_len, int renorm, float* d_out, int stop = -1, RnStage* stop_out = nullptr) {
     AudioProcDev& a = e->aproc;
+    auto stop_at = [&](int stage, const void* p, size_t rows, size_t width, size_t pitch) {
+        if (stop == stage && stop_out) *stop_out = RnStage{(const float*)p, rows, width, pitch};
+        return stop == stage;
+    };
     int rc = audioproc_bases(e);
     if (rc) return rc;
     const RnGeom g = rn_geom(B, N, noise_len);
@@ -476,20 +504,34 @@ int reduce_noise_run(tts_hip_engine* e, const float* d_audio, int B, int N, cons
                            (long long)(d_noise ? noise_len : N), d_info + 2 * B, Q, g.NQ, B, nq);
         HIPCHK(e, hipGetLastError());
     }
+    if (stop_at(RN_PADDED, P, B, g.NP, g.NP) || stop_at(RN_NOISE_PADDED, Q, B, g.NQ, g.NQ)) return TTS_HIP_OK;
     // forward DFTs: frame (b, f) is row b * Fr + f of the hop-strided view of the padded rows
     HIPCHK(e, dft_gemm(P, HOP, NFFT, a.fwd_Bt, NK, B * g.Fr, S, st));
     HIPCHK(e, dft_gemm(Q, HOP, NFFT, a.fwd_Bt, NK, B * g.Frn, Sn, st));
+    if (stop_at(RN_SPECTRUM, S, (size_t)B * g.Fr, 2 * NBIN, NK) || stop_at(RN_NOISE_SPECTRUM, Sn, (size_t)B * g.Frn, 2 * NBIN, NK))
+        return TTS_HIP_OK;
     hipLaunchKernelGGL(audio_power_max_kernel, dim3(64, B), dim3(256), 0, st, S, g.Fr, d_info + B, pmax);
     HIPCHK(e, hipGetLastError());
     hipLaunchKernelGGL(audio_power_max_kernel, dim3(8, B), dim3(256), 0, st, Sn, g.Frn, d_info + 3 * B, pmax + B);
     HIPCHK(e, hipGetLastError());
+    if (stop_at(RN_POWER_MAX, pmax, 1, (size_t)2 * B, (size_t)2 * B)) return TTS_HIP_OK;
     hipLaunchKernelGGL(audio_noise_thresh_kernel, dim3(blocks(NBIN, 256), B), dim3(256), 0, st, Sn, g.Frn, info, pmax + B, thr);
     HIPCHK(e, hipGetLastError());
+    if (stop_at(RN_THRESHOLD, thr, B, NBIN, NBIN)) return TTS_HIP_OK;
     hipLaunchKernelGGL(audio_gate_mask_kernel, dim3(blocks(NBIN, 256), g.Fr, B), dim3(256), 0, st, S, g.Fr, info, pmax, thr, mask);
     HIPCHK(e, hipGetLastError());
+    if (stop == RN_MASK) {
+        const long long n = (long long)B * g.Fr * NBIN;
+        hipLaunchKernelGGL(audio_mask_f32_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, mask, T, n);
+        HIPCHK(e, hipGetLastError());
+        stop_at(RN_MASK, T, (size_t)B * g.Fr, NBIN, NBIN);
+        return TTS_HIP_OK;
+    }
     hipLaunchKernelGGL(audio_gate_apply_kernel, dim3(blocks(NBIN, 256), g.Fr, B), dim3(256), 0, st, S, g.Fr, info, mask);
     HIPCHK(e, hipGetLastError());
+    if (stop_at(RN_GATED, S, (size_t)B * g.Fr, 2 * NBIN, NK)) return TTS_HIP_OK;
     HIPCHK(e, dft_gemm(S, NK, NK, a.inv_Bt, NFFT, B * g.Fr, T, st));
+    if (stop_at(RN_FRAMES, T, (size_t)B * g.Fr, NFFT, NFFT)) return TTS_HIP_OK;
     hipLaunchKernelGGL(audio_overlap_add_kernel, dim3(blocks(N, 256), B), dim3(256), 0, st, T, g.Fr, info, a.win2, d_out, N);
     HIPCHK(e, hipGetLastError());
     if (renorm) {
@@ -532,12 +574,16 @@ int tts_hip_reduce_noise_async(tts_hip_engine* e, const float* audio, int B, int
     return reduce_noise_run(e, audio, B, N, lens, noise, noise_len, renormalize, out);
 }
 
-int tts_hip_reduce_noise(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const float* noise,
-                         int noise_len, int renormalize, float* out, int mem) {
+namespace {
+
+// tts_hip_reduce_noise (what = -1) and tts_hip_reduce_noise_probe (what = a stage, `out` takes that stage) are one call
+int reduce_noise_sync(tts_hip_engine* e, const char* name, const float* audio, int B, int N, const int32_t* lengths,
+                      const float* noise, int noise_len, int renormalize, int what, float* out, int mem) {
     if (!e) return TTS_HIP_EINVAL;
     std::vector<int> lens;
-    if (int rc = rn_check(e, "reduce_noise", audio, B, N, lengths, noise_len, out, lens)) return rc;
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "reduce_noise: bad mem kind %d", mem);
+    if (int rc = rn_check(e, name, audio, B, N, lengths, noise_len, out, lens)) return rc;
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "%s: bad mem kind %d", name, mem);
+    if (what < -1 || what >= RN_STAGES) return set_err(e, TTS_HIP_EINVAL, "%s: no stage %d (0 .. %d)", name, what, RN_STAGES - 1);
     HIPCHK(e, hipSetDevice(e->device));
     AudioProcDev& a = e->aproc;
     const size_t n = (size_t)B * N, nn = noise ? (size_t)B * noise_len : 0;
@@ -555,36 +601,63 @@ int tts_hip_reduce_noise(tts_hip_engine* e, const float* audio, int B, int N, co
         d_noise = noise ? io_noise : nullptr;
         d_out = io_out;
     }
-    int rc = reduce_noise_run(e, d_in, B, N, lens, d_noise, noise_len, renormalize, d_out);
-    if (rc) return rc;
-    if (mem == TTS_HIP_MEM_HOST) HIPCHK(e, hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, e->stream));
+    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    // a probe never produces the ordinary result: d_out (and the io_out staging area, reserved all the same so that both
+    // calls lay the staging buffer out alike) stays unused, and `out` takes the stage straight from the workspace
+    if (what >= 0) {
+        RnStage s{};
+        if (int rc = reduce_noise_run(e, d_in, B, N, lens, d_noise, noise_len, 0, nullptr, what, &s)) return rc;
+        HIPCHK(e, hipMemcpy2DAsync(out, s.width * 4, s.p, s.pitch * 4, s.width * 4, s.rows, kout, e->stream));
+    } else {
+        if (int rc = reduce_noise_run(e, d_in, B, N, lens, d_noise, noise_len, renormalize, d_out)) return rc;
+        if (mem == TTS_HIP_MEM_HOST) HIPCHK(e, hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, e->stream));
+    }
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return TTS_HIP_OK;
 }
 
-int tts_hip_trim_silence(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int window_length,
-                         double threshold, double add_start, double add_end, int mode, int32_t* start, int32_t* end, int mem) {
+}  // namespace
+
+int tts_hip_reduce_noise(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const float* noise,
+                         int noise_len, int renormalize, float* out, int mem) {
+    return reduce_noise_sync(e, "reduce_noise", audio, B, N, lengths, noise, noise_len, renormalize, -1, out, mem);
+}
+
+// Test hook: reduce_noise_run on the same arguments up to stage `what`, then the stage's logical extent to `out`.
+int tts_hip_reduce_noise_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const float* noise,
+                               int noise_len, int what, float* out, int mem) {
+    if (e && what < 0) return set_err(e, TTS_HIP_EINVAL, "reduce_noise_probe: no stage %d (0 .. %d)", what, RN_STAGES - 1);
+    return reduce_noise_sync(e, "reduce_noise_probe", audio, B, N, lengths, noise, noise_len, 0, what, out, mem);
+}
+
+namespace {
+
+// tts_hip_trim_silence (conv_out NULL) and tts_hip_trim_silence_probe (conv_out takes the convolution rows [B][max(N, W) + 1]
+// in place of the thresholds and indices) are one call
+int trim_silence_call(tts_hip_engine* e, const char* name, const float* audio, int B, int N, const int32_t* lengths,
+                      int window_length, double threshold, double add_start, double add_end, int mode, int32_t* start,
+                      int32_t* end, double* conv_out, int mem) {
     if (!e) return TTS_HIP_EINVAL;
-    if (!audio || !start || !end || B <= 0 || N <= 0) return set_err(e, TTS_HIP_EINVAL, "trim_silence: bad argument");
-    if (window_length < 2) return set_err(e, TTS_HIP_EINVAL, "trim_silence: window_length = %d < 2", window_length);
-    if (mode < 0 || mode > 2) return set_err(e, TTS_HIP_EINVAL, "trim_silence: mode %d not 0 (start_end), 1 (start) or 2 (end)", mode);
+    if (!audio || (!conv_out && (!start || !end)) || B <= 0 || N <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", name);
+    if (window_length < 2) return set_err(e, TTS_HIP_EINVAL, "%s: window_length = %d < 2", name, window_length);
+    if (mode < 0 || mode > 2) return set_err(e, TTS_HIP_EINVAL, "%s: mode %d not 0 (start_end), 1 (start) or 2 (end)", name, mode);
     if (!std::isfinite(threshold) || !std::isfinite(add_start) || !std::isfinite(add_end) ||
         add_start < 0 || add_end < 0 || (double)window_length * add_start > 1e9 || (double)window_length * add_end > 1e9)
-        return set_err(e, TTS_HIP_EINVAL, "trim_silence: threshold / margins must be finite, margins >= 0 and not oversized");
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "trim_silence: bad mem kind %d", mem);
+        return set_err(e, TTS_HIP_EINVAL, "%s: threshold / margins must be finite, margins >= 0 and not oversized", name);
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "%s: bad mem kind %d", name, mem);
     const int h = window_length / 2, W = 2 * h, Wp = (W + 3) / 4 * 4;
     std::vector<int> lens(B, N);
     int min_len = N;
     if (lengths)
         for (int b = 0; b < B; ++b) {
             if (lengths[b] < 1 || lengths[b] > N)
-                return set_err(e, TTS_HIP_EINVAL, "trim_silence: lengths[%d] = %d outside [1, N = %d]", b, lengths[b], N);
+                return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d outside [1, N = %d]", name, b, lengths[b], N);
             lens[b] = lengths[b];
             min_len = std::min(min_len, lengths[b]);
         }
     const int Cst = std::max(N, W) + 1;
     if ((long long)B * Cst * 8 >= LIM || (long long)B * N * 4 >= LIM)
-        return set_err(e, TTS_HIP_EINVAL, "trim_silence: B = %d x N = %d too large for 31-bit offsets", B, N);
+        return set_err(e, TTS_HIP_EINVAL, "%s: B = %d x N = %d too large for 31-bit offsets", name, B, N);
     HIPCHK(e, hipSetDevice(e->device));
     AudioProcDev& a = e->aproc;
     hipStream_t st = e->stream;
@@ -630,12 +703,33 @@ int tts_hip_trim_silence(tts_hip_engine* e, const float* audio, int B, int N, co
                            d_w, W, conv, Cst);
         HIPCHK(e, hipGetLastError());
     }
+    const hipMemcpyKind kind = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (conv_out) {
+        HIPCHK(e, hipMemcpyAsync(conv_out, conv, (size_t)B * Cst * 8, kind, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        return TTS_HIP_OK;
+    }
     const TrimParams P{W, window_length, threshold, add_start, add_end, mode};
     hipLaunchKernelGGL(audio_trim_bounds_kernel, dim3(B), dim3(1024), 0, st, conv, Cst, info, P, d_se, d_se + B);
     HIPCHK(e, hipGetLastError());
-    const hipMemcpyKind kind = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     HIPCHK(e, hipMemcpyAsync(start, d_se, (size_t)B * 4, kind, st));
     HIPCHK(e, hipMemcpyAsync(end, d_se + B, (size_t)B * 4, kind, st));
     HIPCHK(e, hipStreamSynchronize(st));
     return TTS_HIP_OK;
+}
+
+}  // namespace
+
+int tts_hip_trim_silence(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int window_length,
+                         double threshold, double add_start, double add_end, int mode, int32_t* start, int32_t* end, int mem) {
+    return trim_silence_call(e, "trim_silence", audio, B, N, lengths, window_length, threshold, add_start, add_end, mode, start,
+                             end, nullptr, mem);
+}
+
+// Test hook: the convolution launches of tts_hip_trim_silence on the same rows, then the rows they wrote to `conv`.
+int tts_hip_trim_silence_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int window_length,
+                               double* conv, int mem) {
+    if (e && !conv) return set_err(e, TTS_HIP_EINVAL, "trim_silence_probe: bad argument");
+    return trim_silence_call(e, "trim_silence_probe", audio, B, N, lengths, window_length, 0.1, 0.0, 0.0, 0, nullptr, nullptr,
+                             conv, mem);
 }

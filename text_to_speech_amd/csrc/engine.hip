@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void mfma_probe_kernel(const float* __restr
 // ------------------------------------------------------------------------------------------- C ABI
 extern "C" {
 
-int tts_hip_abi_version(void) { return 12; }
+int tts_hip_abi_version(void) { return 13; }
 
 int tts_hip_create(int device, tts_hip_engine** out) {
     if (!out) return TTS_HIP_EINVAL;

@@ -836,6 +836,59 @@ class HipEngine:
                     'reduce_noise')
         return out[0] if one_row else out
 
+    _RN_STAGES = {'padded': 0, 'noise_padded': 1, 'spectrum': 2, 'noise_spectrum': 3, 'power_max': 4, 'threshold': 5, 'mask': 6,
+                  'gated': 7, 'frames': 8}
+
+    def reduce_noise_probe(self, audio, rate=None, lengths=None, noise=None, noise_length=0.2, what: str = 'spectrum'):
+        """Test hook (tts_hip_reduce_noise_probe): run `reduce_noise` on the same arguments (host arrays) up to a stage and
+        return what it computed there as float32, with Fr = ceil((N + 2560) / 512) frame slots per row and Frn =
+        ceil((noise_len + 2048) / 512) noise frame slots: 'padded' [B, Fr * 512], 'noise_padded' [B, Frn * 512], 'spectrum'
+        [B, Fr, 2050] (real parts of bins 0 .. 1024, then the imaginary parts; before the gate), 'noise_spectrum'
+        [B, Frn, 2050], 'power_max' [2, B] (signal rows, then noise rows), 'threshold' [B, 1025] dB, 'mask' [B, Fr, 1025] as
+        0 / 1, 'gated' [B, Fr, 2050], 'frames' [B, Fr, 2048] (inverse-DFT rows before the overlap-add).  Always batched."""
+        if what not in self._RN_STAGES:
+            raise ValueError(f'what must be one of {tuple(self._RN_STAGES)}, got {what!r}')
+        audio = np.asarray(audio, dtype=np.float32)
+        B, N, lens = self._audio_rows(audio, lengths, 'reduce_noise_probe')
+        n = None
+        if noise is not None:
+            n = np.ascontiguousarray(np.asarray(noise, dtype=np.float32).reshape(B, -1))
+            noise_len = int(n.shape[1])
+        else:
+            noise_len = self._samples(noise_length, rate, 'reduce_noise_probe: noise_length')
+        if noise_len < 1:
+            raise ValueError(f'reduce_noise_probe: the noise clip must hold at least one sample (got {noise_len})')
+        Fr, Frn = -(-(N + 2560) // 512), -(-(noise_len + 2048) // 512)
+        shape = {'padded': (B, Fr * 512), 'noise_padded': (B, Frn * 512), 'spectrum': (B, Fr, 2050),
+                 'noise_spectrum': (B, Frn, 2050), 'power_max': (2, B), 'threshold': (B, 1025), 'mask': (B, Fr, 1025),
+                 'gated': (B, Fr, 2050), 'frames': (B, Fr, 2048)}[what]
+        a = np.ascontiguousarray(audio.reshape(B, N))
+        out = np.empty(shape, dtype=np.float32)
+        self._check(self._lib.tts_hip_reduce_noise_probe(
+            self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None,
+            n.ctypes.data_as(ctypes.c_void_p) if n is not None else None, noise_len, self._RN_STAGES[what],
+            out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'reduce_noise_probe')
+        return out
+
+    def trim_silence_probe(self, audio, rate=None, lengths=None, window_length=0.2):
+        """Test hook (tts_hip_trim_silence_probe): the convolution launches of `trim_silence` on audio [N] or [B, N] (host
+        array).  Returns conv [B, max(N, W) + 1] float64, W = 2 * (window_length // 2): conv[b, :nc_b] =
+        np.convolve(x_b ** 2, window, 'valid') with nc_b = |lengths[b] - W| + 1, NaN beyond."""
+        audio = np.asarray(audio, dtype=np.float32)
+        B, N, lens = self._audio_rows(audio, lengths, 'trim_silence_probe')
+        wl = self._samples(window_length, rate, 'trim_silence_probe: window_length')
+        if wl < 2:
+            raise ValueError(f'trim_silence_probe: window_length must be >= 2 samples (got {wl})')
+        W = 2 * (wl // 2)
+        a = np.ascontiguousarray(audio.reshape(B, N))
+        conv = np.empty((B, max(N, W) + 1), dtype=np.float64)
+        self._check(self._lib.tts_hip_trim_silence_probe(
+            self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None,
+            wl, conv.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'trim_silence_probe')
+        for b in range(B):
+            conv[b, abs((N if lens is None else int(lens[b])) - W) + 1:] = np.nan
+        return conv
+
     _RESAMPLE_MAX = 1 << 24         # samples per row, in and out (csrc/resample.hip)
 
     def resample(self, audio, rate, target_rate, lengths=None, stream=None):
