@@ -1,0 +1,287 @@
+// audio_call.h -- what the audio front-end calls (mel-STFT, reduce_noise / trim_silence, resample, remove_silence) may be
+// refused for, and the geometry those refusals rest on: pure host code on the caller's arguments (no HIP include; also built
+// with plain g++ under ASan / UBSan by csrc/host_check.cpp, --audio-call, and compared there with a Python restatement,
+// tests/test_audio_call.py).  The .hip files forward the message to set_err; nothing is copied or launched before a check
+// has passed.  Every check is "first match wins" in the order it is written in.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstddef>
+#include <cstdio>
+#include <vector>
+
+#include "../../include/tts_hip.h"
+
+inline int audio_refuse(char* msg, size_t n, const char* who, const char* fmt, ...) {
+    const int at = snprintf(msg, n, "%s: ", who);
+    va_list ap;
+    va_start(ap, fmt);
+    if (at >= 0 && (size_t)at < n) vsnprintf(msg + at, n - (size_t)at, fmt, ap);
+    va_end(ap);
+    return TTS_HIP_EINVAL;
+}
+
+// one row's length: lengths[b] in [1, N]
+inline int audio_row_check(const char* who, int b, int len, int N, char* msg, size_t n) {
+    if (len < 1 || len > N) return audio_refuse(msg, n, who, "lengths[%d] = %d outside [1, N = %d]", b, len, N);
+    return TTS_HIP_OK;
+}
+
+// lens[b] = lengths[b] (NULL: N) for a batch of B rows of N samples, every one in [1, N]; *min_len = the shortest
+inline int audio_rows_check(const char* who, int B, int N, const int32_t* lengths, std::vector<int>& lens, int* min_len, char* msg,
+                            size_t n) {
+    lens.assign(B, N);
+    *min_len = N;
+    if (lengths)
+        for (int b = 0; b < B; ++b) {
+            if (int rc = audio_row_check(who, b, lengths[b], N, msg, n)) return rc;
+            lens[b] = lengths[b];
+            *min_len = std::min(*min_len, lengths[b]);
+        }
+    return TTS_HIP_OK;
+}
+
+// `mem` of a synchronous entry point (an _async one has none: its callers pass TTS_HIP_MEM_DEVICE)
+inline int audio_mem_check(const char* who, int mem, char* msg, size_t n) {
+    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return audio_refuse(msg, n, who, "bad mem kind %d", mem);
+    return TTS_HIP_OK;
+}
+
+inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+inline unsigned blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
+
+// A buffer cut into slices that each start on a 256-byte boundary: take() returns the slice's offset, `o` is the extent
+struct Carve {
+    size_t o = 0;
+    size_t take(size_t bytes) {
+        const size_t at = o;
+        o += al256(bytes);
+        return at;
+    }
+};
+
+constexpr long long kAudioLim = (1ll << 31) - 65536;    // byte extent of any buffer a kernel or GEMM descriptor addresses
+constexpr long long kAudioLim31 = 1ll << 31;            // the same for the kernels that index without a descriptor's slack
+
+// ---------------------------------------------------------------------------------------------- reduce_noise (audio_proc.hip)
+namespace rn {
+constexpr int NFFT = 2048, HOP = 512, HALF = NFFT / 2, NBIN = NFFT / 2 + 1;
+constexpr int NK = 2080;                     // 2 * 1025 DFT rows (real, imaginary) padded to a multiple of 32
+}  // namespace rn
+
+struct RnGeom {
+    int Fr, NP, Frn, NQ;
+    size_t off_info, off_pmax, off_thr, off_P, off_Q, off_S, off_Sn, off_T, off_mask, total;
+};
+
+inline RnGeom rn_geom(int B, int N, int noise_len) {
+    using namespace rn;
+    RnGeom g{};
+    g.Fr = (N + 2560 + HOP - 1) / HOP;          // >= F_b = 1 + (L_b + 512) // 512 for every row; NP = Fr * 512 >= N + 2560
+    g.NP = g.Fr * HOP;
+    g.Frn = (noise_len + NFFT + HOP - 1) / HOP; // >= 1 + noise_len // 512
+    g.NQ = g.Frn * HOP;
+    Carve c;
+    g.off_info = c.take((size_t)4 * B * 4);
+    g.off_pmax = c.take((size_t)2 * B * 4);
+    g.off_thr = c.take((size_t)B * NBIN * 4);
+    g.off_P = c.take(((size_t)B * g.NP + NFFT) * 4);
+    g.off_Q = c.take(((size_t)B * g.NQ + NFFT) * 4);
+    g.off_S = c.take((size_t)B * g.Fr * NK * 4);
+    g.off_Sn = c.take((size_t)B * g.Frn * NK * 4);
+    g.off_T = c.take((size_t)B * g.Fr * NFFT * 4);
+    g.off_mask = c.take((size_t)B * g.Fr * NBIN);
+    g.total = c.o;
+    return g;
+}
+
+// order: pointers / B / N, noise_len, lengths[b], the 31-bit limits, mem kind; fills `lens`
+inline int rn_check(const char* who, const float* audio, int B, int N, const int32_t* lengths, int noise_len, const float* out,
+                    int mem, std::vector<int>& lens, char* msg, size_t n) {
+    using namespace rn;
+    if (!audio || !out || B <= 0 || N <= 0) return audio_refuse(msg, n, who, "bad argument");
+    if (noise_len < 1) return audio_refuse(msg, n, who, "noise_len = %d < 1", noise_len);
+    int min_len;
+    if (int rc = audio_rows_check(who, B, N, lengths, lens, &min_len, msg, n)) return rc;
+    const RnGeom g = rn_geom(B, N, noise_len);
+    const long long biggest = std::max({(long long)B * g.Fr * NK * 4, (long long)B * g.NP * 4 + NFFT * 4,
+                                        (long long)B * g.Frn * NK * 4, (long long)B * g.NQ * 4 + NFFT * 4,
+                                        (long long)B * N * 4, (long long)B * noise_len * 4});
+    if (biggest >= kAudioLim || g.Fr > 65535)
+        return audio_refuse(msg, n, who, "B = %d x N = %d (noise_len %d) too large for 31-bit offsets", B, N, noise_len);
+    return audio_mem_check(who, mem, msg, n);
+}
+
+// ---------------------------------------------------------------------------------------------- trim_silence (audio_proc.hip)
+struct TrimGeom {
+    int W, Wp;          // window taps 2 * (window_length // 2), and rounded up to 4
+    int Cst;            // doubles between two rows of the convolution: max(N, W) + 1
+    int min_len;
+};
+
+// order: pointers / B / N, window_length, mode, threshold / margins, mem kind, lengths[b], the 31-bit limits; fills `lens`.
+// have_out: the entry point's own outputs are there (start and end, or the probe's conv)
+inline int trim_check(const char* who, const float* audio, bool have_out, int B, int N, const int32_t* lengths, int window_length,
+                      double threshold, double add_start, double add_end, int mode, int mem, std::vector<int>& lens, TrimGeom* g,
+                      char* msg, size_t n) {
+    if (!audio || !have_out || B <= 0 || N <= 0) return audio_refuse(msg, n, who, "bad argument");
+    if (window_length < 2) return audio_refuse(msg, n, who, "window_length = %d < 2", window_length);
+    if (mode < 0 || mode > 2) return audio_refuse(msg, n, who, "mode %d not 0 (start_end), 1 (start) or 2 (end)", mode);
+    if (!std::isfinite(threshold) || !std::isfinite(add_start) || !std::isfinite(add_end) ||
+        add_start < 0 || add_end < 0 || (double)window_length * add_start > 1e9 || (double)window_length * add_end > 1e9)
+        return audio_refuse(msg, n, who, "threshold / margins must be finite, margins >= 0 and not oversized");
+    if (int rc = audio_mem_check(who, mem, msg, n)) return rc;
+    const int h = window_length / 2;
+    g->W = 2 * h;
+    g->Wp = (g->W + 3) / 4 * 4;
+    if (int rc = audio_rows_check(who, B, N, lengths, lens, &g->min_len, msg, n)) return rc;
+    g->Cst = std::max(N, g->W) + 1;
+    if ((long long)B * g->Cst * 8 >= kAudioLim || (long long)B * N * 4 >= kAudioLim)
+        return audio_refuse(msg, n, who, "B = %d x N = %d too large for 31-bit offsets", B, N);
+    return TTS_HIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- resample (resample.hip)
+constexpr int RS_MAX_LEN = 1 << 24;                // samples per row, in and out
+
+inline int ilog2(long long v) {
+    int l = 0;
+    while ((1ll << l) < v) ++l;
+    return l;
+}
+
+struct RsLens {
+    int logf, logi;             // log2 of the forward / inverse Bluestein lengths
+};
+
+// L_fwd >= N + N//2, L_inv >= 2M - 1, both at least 64
+inline RsLens rs_lens(int n, int m) { return {std::max(6, ilog2((long long)n + n / 2)), std::max(6, ilog2(2ll * m - 1))}; }
+
+inline int rs_out_len(int n, int rate, int target_rate) { return (int)((double)n / rate * target_rate); }
+
+// order: pointers / B / N, rates, N and M against 2^24, M < 1, M against int(N / rate * target_rate), the 31-bit limits,
+// lengths[b] (and what it resamples to), mem kind; fills the row lengths in and out
+inline int rs_check(const char* who, const float* audio, int B, int N, const int32_t* lengths, int rate, int target_rate,
+                    const float* out, int M, int mem, std::vector<int>& lens, std::vector<int>& mlens, char* msg, size_t n) {
+    if (!audio || !out || B <= 0 || N <= 0) return audio_refuse(msg, n, who, "bad argument");
+    if (rate <= 0 || target_rate <= 0)
+        return audio_refuse(msg, n, who, "rates must be > 0 (rate %d, target_rate %d)", rate, target_rate);
+    if (N > RS_MAX_LEN) return audio_refuse(msg, n, who, "N = %d > 2^24 samples per row", N);
+    const double md = (double)N / rate * target_rate;
+    if (!(md < (double)RS_MAX_LEN + 1))
+        return audio_refuse(msg, n, who, "%d samples at %d -> %d Hz give more than 2^24 samples per row", N, rate, target_rate);
+    const int want = rs_out_len(N, rate, target_rate);
+    if (want < 1) return audio_refuse(msg, n, who, "%d samples at %d -> %d Hz give M = %d < 1", N, rate, target_rate, want);
+    if (M != want) return audio_refuse(msg, n, who, "M = %d, but int(%d / %d * %d) = %d", M, N, rate, target_rate, want);
+    if ((long long)B * M * 4 >= kAudioLim31 || (long long)B * N * 4 >= kAudioLim31)
+        return audio_refuse(msg, n, who, "B = %d x N = %d (M %d) too large for 31-bit offsets", B, N, M);
+    lens.assign(B, N);
+    mlens.assign(B, M);
+    if (lengths)                                            // row by row: a row's own two refusals before the next row's
+        for (int b = 0; b < B; ++b) {
+            if (int rc = audio_row_check(who, b, lengths[b], N, msg, n)) return rc;
+            lens[b] = lengths[b];
+            mlens[b] = rs_out_len(lens[b], rate, target_rate);
+            if (mlens[b] < 1)
+                return audio_refuse(msg, n, who, "lengths[%d] = %d resamples to %d < 1 samples", b, lens[b], mlens[b]);
+        }
+    return audio_mem_check(who, mem, msg, n);
+}
+
+// ---------------------------------------------------------------------------------------------- remove_silence (silence.hip)
+constexpr int SIL_TILE = 2048;               // samples per workgroup of the tile kernels (256 threads x 8 consecutive)
+
+struct SilCall {
+    int B, N, method, mode, rate, bs, rb;
+    double threshold, min_silence, mvt;
+    std::vector<int> lens;
+    int w = 0;                  // mean-window taps
+    int NT = 0, NB = 0, cap = 1;
+    size_t off_info, off_mask, off_cnt, off_off, off_n, off_cut, off_d0, off_d1, off_flag, off_si, off_sj, off_tsum, off_toff,
+        off_P, off_tot, total;
+};
+
+// order: pointers / B / N, method, mode, mode 3 without rms, rate, the size limits, lengths[b], threshold, the rms settings,
+// min_silence, the mean-window settings (a row shorter than the window among them), out overlapping audio, mem kind
+inline int sil_check(const char* who, const float* audio, int B, int N, const int32_t* lengths, int method, int mode, int rate,
+                     double threshold, double min_silence, int block_size, int replace_by, double min_voice_time, const float* out,
+                     const int32_t* out_lengths, int mem, SilCall& c, char* msg, size_t n) {
+    if (!audio || !out || !out_lengths || B <= 0 || N <= 0) return audio_refuse(msg, n, who, "bad argument");
+    if (method < TTS_HIP_SILENCE_RMS || method > TTS_HIP_SILENCE_MEAN_WINDOW)
+        return audio_refuse(msg, n, who, "method %d not 0 (rms), 1 (threshold) or 2 (mean-window)", method);
+    if (mode < 0 || mode > 3)
+        return audio_refuse(msg, n, who, "mode %d not 0 (start_end), 1 (start), 2 (end) or 3 (remove)", mode);
+    if (mode == 3 && method != TTS_HIP_SILENCE_RMS)
+        return audio_refuse(msg, n, who, "mode 3 (remove) belongs to the rms method (got method %d)", method);
+    if (rate <= 0) return audio_refuse(msg, n, who, "rate = %d <= 0", rate);
+    if (B > 65535 || N > (1 << 24) || (long long)B * N * 4 >= kAudioLim31)   // B is a grid dimension of every kernel
+        return audio_refuse(msg, n, who, "B = %d x N = %d too large (B <= 65535, N <= 2^24, B * N * 4 < 2^31)", B, N);
+    int min_len;
+    if (int rc = audio_rows_check(who, B, N, lengths, c.lens, &min_len, msg, n)) return rc;
+    const bool rms = method == TTS_HIP_SILENCE_RMS, mw = method == TTS_HIP_SILENCE_MEAN_WINDOW;
+    if (!std::isfinite(threshold) || (!rms && threshold < 0))
+        return audio_refuse(msg, n, who, "threshold = %g must be finite%s", threshold, rms ? "" : " and >= 0");
+    if (rms) {
+        if (block_size < 1) return audio_refuse(msg, n, who, "block_size = %d < 1", block_size);
+        if (replace_by < 0) return audio_refuse(msg, n, who, "replace_by = %d < 0", replace_by);
+        if (!std::isfinite(min_voice_time) || min_voice_time < 0)
+            return audio_refuse(msg, n, who, "min_voice_time = %g must be finite and >= 0", min_voice_time);
+    }
+    if ((rms || mw) && (!std::isfinite(min_silence) || min_silence < 0))
+        return audio_refuse(msg, n, who, "min_silence = %g must be finite and >= 0", min_silence);
+    if (mw) {
+        if (threshold <= 0) return audio_refuse(msg, n, who, "threshold = %g <= 0 (mean-window)", threshold);
+        const double wd = min_silence * (double)rate;
+        if (wd < 1.0) return audio_refuse(msg, n, who, "window w = (int)(min_silence * rate) = %d < 1", (int)wd);
+        if (std::floor(wd) > (double)min_len)           // also keeps (int)wd in range
+            return audio_refuse(msg, n, who, "a row of L = %d samples is shorter than the window w = %.0f", min_len, std::floor(wd));
+        c.w = (int)wd;
+        if (min_len < c.w)
+            return audio_refuse(msg, n, who, "a row of L = %d samples is shorter than the window w = %d", min_len, c.w);
+    }
+    const char *a0 = (const char*)audio, *o0 = (const char*)out;
+    const size_t bytes = (size_t)B * N * 4;
+    if (a0 < o0 + bytes && o0 < a0 + bytes) return audio_refuse(msg, n, who, "out overlaps audio");
+    if (int rc = audio_mem_check(who, mem, msg, n)) return rc;
+
+    c.B = B;
+    c.N = N;
+    c.method = method;
+    c.mode = mode;
+    c.rate = rate;
+    c.bs = block_size;
+    c.rb = replace_by;
+    c.threshold = threshold;
+    c.min_silence = min_silence;
+    c.mvt = min_voice_time;
+    c.NT = (N + SIL_TILE - 1) / SIL_TILE;
+    if (rms) {
+        // silences per row: each holds >= q blocks (q * bt >= min_silence, taken one short against rounding) and a loud
+        // block parts it from the next
+        c.NB = (int)(((long long)N + c.bs - 1) / c.bs);
+        const double per = min_silence / ((double)c.bs / (double)rate);
+        const long long q = std::max<long long>(1, (per < 1e9 ? (long long)per : 1000000000ll) - 1);
+        c.cap = (int)(c.NB / (q + 1) + 1);
+    }
+    Carve ws;
+    c.off_info = ws.take((size_t)B * 4);
+    c.off_mask = ws.take((size_t)B * N);
+    c.off_cnt = ws.take((size_t)B * c.NT * 4);
+    c.off_off = ws.take((size_t)B * c.NT * 4);
+    c.off_n = ws.take((size_t)B * 4);
+    c.off_cut = ws.take((size_t)B * 4);
+    c.off_d0 = ws.take((size_t)B * c.cap * 4);
+    c.off_d1 = ws.take((size_t)B * c.cap * 4);
+    c.off_flag = ws.take(rms ? (size_t)B * c.NB : 0);
+    c.off_si = ws.take(rms ? (size_t)B * c.cap * 4 : 0);
+    c.off_sj = ws.take(rms ? (size_t)B * c.cap * 4 : 0);
+    c.off_tsum = ws.take(mw ? (size_t)B * c.NT * 8 : 0);
+    c.off_toff = ws.take(mw ? (size_t)B * c.NT * 8 : 0);
+    c.off_P = ws.take(mw ? (size_t)B * ((size_t)N + 1) * 8 : 0);
+    c.off_tot = ws.take(mw ? (size_t)B * 8 : 0);
+    c.total = ws.o;
+    return TTS_HIP_OK;
+}

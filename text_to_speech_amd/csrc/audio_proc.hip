@@ -11,6 +11,7 @@
 // Every row b has its own length L_b <= N; nothing reads across a row's end, and a row's result equals a one-row call on
 // audio[b, :L_b].
 #include "engine.h"
+#include "audio_dev.h"
 #include "gemm_f32.h"
 
 #include <cfloat>
@@ -18,11 +19,10 @@
 #include <cstring>
 
 using namespace ttsgemm;
+using namespace rn;                          // NFFT, HOP, HALF, NBIN, NK (audio_call.h)
 
 namespace {
 
-constexpr int NFFT = 2048, HOP = 512, HALF = NFFT / 2, NBIN = NFFT / 2 + 1;
-constexpr int NK = 2080;                     // 2 * 1025 DFT rows (real, imaginary) padded to a multiple of 32
 constexpr int TRIM_OUT = 1024;               // conv outputs per block of the trim convolution (256 threads x 4)
 constexpr int TRIM_JC = 1024;                // window taps staged in LDS per pass
 
@@ -68,15 +68,9 @@ __global__ void audio_power_max_kernel(const float* __restrict__ S, int Fr, cons
         const float re = row[k], im = row[NBIN + k];
         m = fmaxf(m, power_of(re, im));
     }
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = fmaxf(m, wm[w]);
-        m = fmaxf(m, wm[0]);
-        atomicMax(pmax + b, __float_as_uint(m));
-    }
+    m = block_reduce(m, wm, OpMax());
+    if (threadIdx.x == 0) atomicMax(pmax + b, __float_as_uint(m));
 }
 
 // librosa.amplitude_to_db(|X|, ref=1, amin=1e-20, top_db=80) (noisereducev1.py:66-67): 10 log10(max(p, 1e-40)) clamped in
@@ -181,17 +175,6 @@ __global__ void audio_overlap_add_kernel(const float* __restrict__ T, int Fr, Ro
     out[(long long)b * N + t] = v;
 }
 
-__device__ double block_sum_d(double v, double* sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += sh[i];
-    return s;
-}
-
 // normalize_audio(x, max_val=1.) (audio_processing.py:50-62) over the row's own L_b samples: x - mean, / max|x| unless <= 1e-9.
 // In double, rounded once (the reference normalises the float64 result of reduce_noise): a mean rounded to fp32 is off by up
 // to 2^-25 |mean|, which the division by m = max|x - mean| turns into 2^-25 |mean| / m of full scale.
@@ -201,15 +184,10 @@ __global__ __launch_bounds__(1024) void audio_renormalize_kernel(float* __restri
     float* r = x + (long long)b * N;
     double s = 0.0;
     for (int t = threadIdx.x; t < L; t += blockDim.x) s += r[t];
-    const double mean = block_sum_d(s, sh) / L;
+    const double mean = block_reduce(s, sh, OpAdd()) / L;
     double m = 0.0;
     for (int t = threadIdx.x; t < L; t += blockDim.x) m = fmax(m, fabs((double)r[t] - mean));
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
-    __shared__ double shm[16];
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) m = fmax(m, shm[i]);
+    m = block_reduce(m, sh, OpMax());
     const double sc = m > 1e-9 ? 1.0 / m : 1.0;
     for (int t = threadIdx.x; t < L; t += blockDim.x) r[t] = (float)(((double)r[t] - mean) * sc);
 }
@@ -290,7 +268,7 @@ struct TrimParams {
 __global__ __launch_bounds__(1024) void audio_trim_bounds_kernel(const double* __restrict__ conv, int Cst, RowInfo info,
                                                                  TrimParams P, int* __restrict__ start, int* __restrict__ end) {
     __shared__ double sh[16];
-    __shared__ int shi[2][16];
+    __shared__ int shi[16];
     const int b = blockIdx.x, L = info.len(b);
     const int nc = L >= P.W ? L - P.W + 1 : P.W - L + 1;
     const double* c = conv + (long long)b * Cst;
@@ -302,8 +280,8 @@ __global__ __launch_bounds__(1024) void audio_trim_bounds_kernel(const double* _
         if (i >= e0) se += c[i];
         if (i < s1) ss += c[i];
     }
-    se = block_sum_d(se, sh);
-    ss = block_sum_d(ss, sh);
+    se = block_reduce(se, sh, OpAdd());
+    ss = block_reduce(ss, sh, OpAdd());
     const double th_end = fmin(P.threshold, fmax(se / (nc - e0) * 5.0, P.threshold / 50.0));
     const double th_start = fmin(P.threshold, fmax(ss / s1 * 5.0, P.threshold / 50.0));
     int last = -1, first = 0x7fffffff;
@@ -312,21 +290,9 @@ __global__ __launch_bounds__(1024) void audio_trim_bounds_kernel(const double* _
         if (v > th_end) last = max(last, i);
         if (v > th_start) first = min(first, i);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        last = max(last, __shfl_xor(last, o));
-        first = min(first, __shfl_xor(first, o));
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        shi[0][threadIdx.x >> 6] = last;
-        shi[1][threadIdx.x >> 6] = first;
-    }
-    __syncthreads();
+    last = block_reduce(last, shi, OpMax());
+    first = block_reduce(first, shi, OpMin());
     if (threadIdx.x != 0) return;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) {
-        last = max(last, shi[0][i]);
-        first = min(first, shi[1][i]);
-    }
     long long s = 0, e = L;
     if (do_end && last >= 0) e = std::min<long long>(L, (long long)last + (long long)((double)P.wl * P.add_end));
     if (do_start && first != 0x7fffffff) s = std::max<long long>(0, (long long)first - (long long)((double)P.wl * P.add_start));
@@ -347,8 +313,6 @@ double np_linspace(double a, double z, int num, int i) {
     return y + a;
 }
 
-constexpr long long LIM = (1ll << 31) - 65536;    // byte extent of any buffer a kernel or GEMM descriptor addresses
-
 }  // namespace
 
 void audioproc_free(tts_hip_engine* e) {
@@ -358,7 +322,6 @@ void audioproc_free(tts_hip_engine* e) {
     a.fwd_Bt = a.inv_Bt = nullptr;
     a.win2 = nullptr;
     a.ws.release();
-    a.io.release();
     a.trim_win.release();
     a.trim_wl = -1;
 }
@@ -403,56 +366,10 @@ int audioproc_bases(tts_hip_engine* e) {
     return TTS_HIP_OK;
 }
 
-size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
-struct RnGeom {
-    int Fr, NP, Frn, NQ;
-    size_t off_info, off_pmax, off_thr, off_P, off_Q, off_S, off_Sn, off_T, off_mask, total;
-};
-
-RnGeom rn_geom(int B, int N, int noise_len) {
-    RnGeom g{};
-    g.Fr = (N + 2560 + HOP - 1) / HOP;          // >= F_b = 1 + (L_b + 512) // 512 for every row; NP = Fr * 512 >= N + 2560
-    g.NP = g.Fr * HOP;
-    g.Frn = (noise_len + NFFT + HOP - 1) / HOP; // >= 1 + noise_len // 512
-    g.NQ = g.Frn * HOP;
-    size_t o = 0;
-    g.off_info = o; o += al256((size_t)4 * B * 4);
-    g.off_pmax = o; o += al256((size_t)2 * B * 4);
-    g.off_thr = o; o += al256((size_t)B * NBIN * 4);
-    g.off_P = o; o += al256(((size_t)B * g.NP + NFFT) * 4);
-    g.off_Q = o; o += al256(((size_t)B * g.NQ + NFFT) * 4);
-    g.off_S = o; o += al256((size_t)B * g.Fr * NK * 4);
-    g.off_Sn = o; o += al256((size_t)B * g.Frn * NK * 4);
-    g.off_T = o; o += al256((size_t)B * g.Fr * NFFT * 4);
-    g.off_mask = o; o += al256((size_t)B * g.Fr * NBIN);
-    g.total = o;
-    return g;
-}
-
+// a DFT as one dense product: out[M][Nout] = A (rows lda apart, K wide) x Bt[Nout][K]^T
 hipError_t dft_gemm(const float* A, long long lda, int K, const float* Bt, int Nout, int M, float* out, hipStream_t st) {
-    GemmArgs g{};
-    g.M = M;
-    g.N = Nout;
-    g.L = M;
-    g.nseg = 1;
-    g.seg[0] = ASeg{A, lda, 0, K, K};
-    g.Bt = Bt;
-    g.ldb = K;
-    g.mode = EPI_LINEAR;
-    g.split = Nout;
-    g.out0 = out;
-    g.ld0 = Nout;
-    return gemm_big(g, 1, st);
+    return gemm_big(gemm_linear(A, lda, K, Bt, K, Nout, M, out), 1, st);
 }
-
-unsigned blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
-
-// what a probe copies out: `rows` rows of `width` floats, `pitch` floats apart
-struct RnStage {
-    const float* p;
-    size_t rows, width, pitch;
-};
 
 enum { RN_PADDED, RN_NOISE_PADDED, RN_SPECTRUM, RN_NOISE_SPECTRUM, RN_POWER_MAX, RN_THRESHOLD, RN_MASK, RN_GATED, RN_FRAMES,
        RN_STAGES };
@@ -461,10 +378,10 @@ enum { RN_PADDED, RN_NOISE_PADDED, RN_SPECTRUM, RN_NOISE_SPECTRUM, RN_POWER_MAX,
 // RN_* returns right after the launch that completes that stage with *stop_out describing what it wrote (the mask as fp32 in
 // the not yet used frame buffer T; d_out is not touched); -1 runs everything.
 int reduce_noise_run(tts_hip_engine* e, const float* d_audio, int B, int N, const std::vector<int>& lens,
-                     const float* d_noise, int noise_len, int renorm, float* d_out, int stop = -1, RnStage* stop_out = nullptr) {
+                     const float* d_noise, int noise_len, int renorm, float* d_out, int stop = -1, StageView* stop_out = nullptr) {
     AudioProcDev& a = e->aproc;
     auto stop_at = [&](int stage, const void* p, size_t rows, size_t width, size_t pitch) {
-        if (stop == stage && stop_out) *stop_out = RnStage{(const float*)p, rows, width, pitch};
+        if (stop == stage && stop_out) *stop_out = StageView{p, rows, width, pitch};
         return stop == stage;
     };
     int rc = audioproc_bases(e);
@@ -483,15 +400,16 @@ int reduce_noise_run(tts_hip_engine* e, const float* d_audio, int B, int N, cons
     float* T = (float*)(base + g.off_T);
     uint8_t* mask = (uint8_t*)(base + g.off_mask);
     // row facts: L_b, F_b, noise clip length, noise frames (the default clip is audio[b, :min(noise_len, L_b)])
-    a.info_h.assign((size_t)4 * B, 0);
+    std::vector<int>& info_h = e->audio_info_h;
+    info_h.assign((size_t)4 * B, 0);
     for (int b = 0; b < B; ++b) {
         const int L = lens[b], nl = d_noise ? noise_len : std::min(noise_len, L);
-        a.info_h[b] = L;
-        a.info_h[B + b] = 1 + (L + HOP) / HOP;
-        a.info_h[2 * B + b] = nl;
-        a.info_h[3 * B + b] = 1 + nl / HOP;
+        info_h[b] = L;
+        info_h[B + b] = 1 + (L + HOP) / HOP;
+        info_h[2 * B + b] = nl;
+        info_h[3 * B + b] = 1 + nl / HOP;
     }
-    HIPCHK(e, hipMemcpyAsync(d_info, a.info_h.data(), a.info_h.size() * 4, hipMemcpyHostToDevice, st));
+    if (int rc = stage_row_info(e, d_info)) return rc;
     HIPCHK(e, hipMemsetAsync(pmax, 0, (size_t)2 * B * 4, st));
     const RowInfo info{d_info, B};
     {
@@ -541,34 +459,15 @@ int reduce_noise_run(tts_hip_engine* e, const float* d_audio, int B, int N, cons
     return TTS_HIP_OK;
 }
 
-// host-side validation shared by both entry points; fills `lens`
-int rn_check(tts_hip_engine* e, const char* what, const float* audio, int B, int N, const int32_t* lengths, int noise_len,
-             const float* out, std::vector<int>& lens) {
-    if (!audio || !out || B <= 0 || N <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", what);
-    if (noise_len < 1) return set_err(e, TTS_HIP_EINVAL, "%s: noise_len = %d < 1", what, noise_len);
-    lens.assign(B, N);
-    if (lengths)
-        for (int b = 0; b < B; ++b) {
-            if (lengths[b] < 1 || lengths[b] > N)
-                return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d outside [1, N = %d]", what, b, lengths[b], N);
-            lens[b] = lengths[b];
-        }
-    const RnGeom g = rn_geom(B, N, noise_len);
-    const long long biggest = std::max({(long long)B * g.Fr * NK * 4, (long long)B * g.NP * 4 + NFFT * 4,
-                                        (long long)B * g.Frn * NK * 4, (long long)B * g.NQ * 4 + NFFT * 4,
-                                        (long long)B * N * 4, (long long)B * noise_len * 4});
-    if (biggest >= LIM || g.Fr > 65535)
-        return set_err(e, TTS_HIP_EINVAL, "%s: B = %d x N = %d (noise_len %d) too large for 31-bit offsets", what, B, N, noise_len);
-    return TTS_HIP_OK;
-}
-
 }  // namespace
 
 int tts_hip_reduce_noise_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths,
                                const float* noise, int noise_len, int renormalize, float* out, void* stream) {
     if (!e) return TTS_HIP_EINVAL;
     std::vector<int> lens;
-    if (int rc = rn_check(e, "reduce_noise_async", audio, B, N, lengths, noise_len, out, lens)) return rc;
+    char why[256];
+    if (int rc = rn_check("reduce_noise_async", audio, B, N, lengths, noise_len, out, TTS_HIP_MEM_DEVICE, lens, why, sizeof why))
+        return set_err(e, rc, "%s", why);
     HIPCHK(e, hipSetDevice(e->device));
     StreamScope scope(e, stream);
     return reduce_noise_run(e, audio, B, N, lens, noise, noise_len, renormalize, out);
@@ -581,39 +480,26 @@ int reduce_noise_sync(tts_hip_engine* e, const char* name, const float* audio, i
                       const float* noise, int noise_len, int renormalize, int what, float* out, int mem) {
     if (!e) return TTS_HIP_EINVAL;
     std::vector<int> lens;
-    if (int rc = rn_check(e, name, audio, B, N, lengths, noise_len, out, lens)) return rc;
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "%s: bad mem kind %d", name, mem);
+    char why[256];
+    if (int rc = rn_check(name, audio, B, N, lengths, noise_len, out, mem, lens, why, sizeof why)) return set_err(e, rc, "%s", why);
     if (what < -1 || what >= RN_STAGES) return set_err(e, TTS_HIP_EINVAL, "%s: no stage %d (0 .. %d)", name, what, RN_STAGES - 1);
     HIPCHK(e, hipSetDevice(e->device));
-    AudioProcDev& a = e->aproc;
-    const size_t n = (size_t)B * N, nn = noise ? (size_t)B * noise_len : 0;
-    const float* d_in = audio;
-    const float* d_noise = noise;
-    float* d_out = out;
-    if (mem == TTS_HIP_MEM_HOST) {
-        HIPCHK(e, a.io.ensure(al256(n * 4) * 2 + nn * 4));
-        float* io = a.io.f();
-        float* io_out = (float*)((char*)a.io.p + al256(n * 4));
-        float* io_noise = (float*)((char*)a.io.p + 2 * al256(n * 4));
-        HIPCHK(e, hipMemcpyAsync(io, audio, n * 4, hipMemcpyHostToDevice, e->stream));
-        if (noise) HIPCHK(e, hipMemcpyAsync(io_noise, noise, nn * 4, hipMemcpyHostToDevice, e->stream));
-        d_in = io;
-        d_noise = noise ? io_noise : nullptr;
-        d_out = io_out;
-    }
-    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    // a probe never produces the ordinary result: d_out (and the io_out staging area, reserved all the same so that both
-    // calls lay the staging buffer out alike) stays unused, and `out` takes the stage straight from the workspace
+    const size_t n = (size_t)B * N;
+    AudioStage io(e, mem);
+    const int in = io.in(audio, n * 4), nz = io.in(noise, noise ? (size_t)B * noise_len * 4 : 0);
+    // a probe never produces the ordinary result: `out` takes the stage straight from the workspace
+    const int res = what >= 0 ? -1 : io.out(out, n * 4);
+    if (int rc = io.begin()) return rc;
     if (what >= 0) {
-        RnStage s{};
-        if (int rc = reduce_noise_run(e, d_in, B, N, lens, d_noise, noise_len, 0, nullptr, what, &s)) return rc;
-        HIPCHK(e, hipMemcpy2DAsync(out, s.width * 4, s.p, s.pitch * 4, s.width * 4, s.rows, kout, e->stream));
-    } else {
-        if (int rc = reduce_noise_run(e, d_in, B, N, lens, d_noise, noise_len, renormalize, d_out)) return rc;
-        if (mem == TTS_HIP_MEM_HOST) HIPCHK(e, hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, e->stream));
+        StageView s{};
+        if (int rc = reduce_noise_run(e, io.ptr<const float>(in), B, N, lens, io.ptr<const float>(nz), noise_len, 0, nullptr, what, &s))
+            return rc;
+        if (int rc = copy_stage_out(e, s, out, mem)) return rc;
+    } else if (int rc = reduce_noise_run(e, io.ptr<const float>(in), B, N, lens, io.ptr<const float>(nz), noise_len, renormalize,
+                                         io.ptr<float>(res))) {
+        return rc;
     }
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return TTS_HIP_OK;
+    return io.finish();
 }
 
 }  // namespace
@@ -638,26 +524,13 @@ int trim_silence_call(tts_hip_engine* e, const char* name, const float* audio, i
                       int window_length, double threshold, double add_start, double add_end, int mode, int32_t* start,
                       int32_t* end, double* conv_out, int mem) {
     if (!e) return TTS_HIP_EINVAL;
-    if (!audio || (!conv_out && (!start || !end)) || B <= 0 || N <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", name);
-    if (window_length < 2) return set_err(e, TTS_HIP_EINVAL, "%s: window_length = %d < 2", name, window_length);
-    if (mode < 0 || mode > 2) return set_err(e, TTS_HIP_EINVAL, "%s: mode %d not 0 (start_end), 1 (start) or 2 (end)", name, mode);
-    if (!std::isfinite(threshold) || !std::isfinite(add_start) || !std::isfinite(add_end) ||
-        add_start < 0 || add_end < 0 || (double)window_length * add_start > 1e9 || (double)window_length * add_end > 1e9)
-        return set_err(e, TTS_HIP_EINVAL, "%s: threshold / margins must be finite, margins >= 0 and not oversized", name);
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "%s: bad mem kind %d", name, mem);
-    const int h = window_length / 2, W = 2 * h, Wp = (W + 3) / 4 * 4;
-    std::vector<int> lens(B, N);
-    int min_len = N;
-    if (lengths)
-        for (int b = 0; b < B; ++b) {
-            if (lengths[b] < 1 || lengths[b] > N)
-                return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d outside [1, N = %d]", name, b, lengths[b], N);
-            lens[b] = lengths[b];
-            min_len = std::min(min_len, lengths[b]);
-        }
-    const int Cst = std::max(N, W) + 1;
-    if ((long long)B * Cst * 8 >= LIM || (long long)B * N * 4 >= LIM)
-        return set_err(e, TTS_HIP_EINVAL, "%s: B = %d x N = %d too large for 31-bit offsets", name, B, N);
+    std::vector<int> lens;
+    TrimGeom g{};
+    char why[256];
+    if (int rc = trim_check(name, audio, conv_out || (start && end), B, N, lengths, window_length, threshold, add_start, add_end,
+                            mode, mem, lens, &g, why, sizeof why))
+        return set_err(e, rc, "%s", why);
+    const int h = window_length / 2, W = g.W, Wp = g.Wp, Cst = g.Cst;
     HIPCHK(e, hipSetDevice(e->device));
     AudioProcDev& a = e->aproc;
     hipStream_t st = e->stream;
@@ -678,44 +551,39 @@ int trim_silence_call(tts_hip_engine* e, const char* name, const float* audio, i
         a.trim_wl = window_length;
     }
     const double* d_w = (const double*)a.trim_win.p;
-    const size_t off_conv = 0, off_info = al256((size_t)B * Cst * 8), off_se = off_info + al256((size_t)B * 4),
-                 off_in = off_se + al256((size_t)2 * B * 4), total = off_in + (mem == TTS_HIP_MEM_HOST ? (size_t)B * N * 4 : 0);
-    HIPCHK(e, a.ws.ensure(total));
-    char* base = (char*)a.ws.p;
-    double* conv = (double*)(base + off_conv);
-    int* d_info = (int*)(base + off_info);
-    int* d_se = (int*)(base + off_se);
-    const float* d_in = audio;
-    if (mem == TTS_HIP_MEM_HOST) {
-        HIPCHK(e, hipMemcpyAsync(base + off_in, audio, (size_t)B * N * 4, hipMemcpyHostToDevice, st));
-        d_in = (const float*)(base + off_in);
-    }
-    a.info_h.assign(lens.begin(), lens.end());
-    HIPCHK(e, hipMemcpyAsync(d_info, a.info_h.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    Carve ws;
+    const size_t off_conv = ws.take((size_t)B * Cst * 8), off_info = ws.take((size_t)B * 4);
+    HIPCHK(e, a.ws.ensure(ws.o));
+    double* conv = (double*)((char*)a.ws.p + off_conv);
+    int* d_info = (int*)((char*)a.ws.p + off_info);
+    AudioStage io(e, mem);
+    const int in = io.in(audio, (size_t)B * N * 4);
+    const int s_out = io.out(conv_out ? nullptr : start, (size_t)B * 4), e_out = io.out(conv_out ? nullptr : end, (size_t)B * 4);
+    if (int rc = io.begin()) return rc;
+    const float* d_in = io.ptr<const float>(in);
+    e->audio_info_h.assign(lens.begin(), lens.end());
+    if (int rc = stage_row_info(e, d_info)) return rc;
     const RowInfo info{d_info, B};
     if (N >= W) {
         hipLaunchKernelGGL(audio_trim_conv_kernel, dim3(blocks(N - W + 1, TRIM_OUT), B), dim3(256), 0, st, d_in, N, info,
                            d_w + W, W, Wp, conv, Cst);
         HIPCHK(e, hipGetLastError());
     }
-    if (min_len < W) {
-        hipLaunchKernelGGL(audio_trim_conv_short_kernel, dim3(blocks(W - min_len + 1, 256), B), dim3(256), 0, st, d_in, N, info,
+    if (g.min_len < W) {
+        hipLaunchKernelGGL(audio_trim_conv_short_kernel, dim3(blocks(W - g.min_len + 1, 256), B), dim3(256), 0, st, d_in, N, info,
                            d_w, W, conv, Cst);
         HIPCHK(e, hipGetLastError());
     }
-    const hipMemcpyKind kind = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (conv_out) {
-        HIPCHK(e, hipMemcpyAsync(conv_out, conv, (size_t)B * Cst * 8, kind, st));
-        HIPCHK(e, hipStreamSynchronize(st));
-        return TTS_HIP_OK;
+        HIPCHK(e, hipMemcpyAsync(conv_out, conv, (size_t)B * Cst * 8,
+                                 mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+        return io.finish();
     }
     const TrimParams P{W, window_length, threshold, add_start, add_end, mode};
-    hipLaunchKernelGGL(audio_trim_bounds_kernel, dim3(B), dim3(1024), 0, st, conv, Cst, info, P, d_se, d_se + B);
+    hipLaunchKernelGGL(audio_trim_bounds_kernel, dim3(B), dim3(1024), 0, st, conv, Cst, info, P, io.ptr<int>(s_out),
+                       io.ptr<int>(e_out));
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(start, d_se, (size_t)B * 4, kind, st));
-    HIPCHK(e, hipMemcpyAsync(end, d_se + B, (size_t)B * 4, kind, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    return TTS_HIP_OK;
+    return io.finish();
 }
 
 }  // namespace

@@ -14,6 +14,7 @@
 
 #include "ttsw_host.h"      // HostTensor + the TTSW parser (host-only code, also built under ASan / UBSan)
 #include "wg_call.h"        // WgCall: one WaveGlow call, its checks and its staged table (host-only code, likewise)
+#include "audio_call.h"     // the audio calls' checks and the geometry they rest on (host-only code, likewise)
 
 // Growable device buffer (workspace).  Never shrinks; reallocated only when a larger request arrives.
 struct DevBuf {
@@ -191,12 +192,16 @@ struct Tacotron2Dev {
     hipEvent_t chunk_ev[2] = {nullptr, nullptr};
 };
 
+// ---------------------------------------------------------------- audio front end (mel_stft.hip, audio_proc.hip,
+// resample.hip, silence.hip).  These structs hold weights, tables and per-call workspaces only: what a TTS_HIP_MEM_HOST
+// caller passes in and gets back is staged through the engine's one `audio_io` (AudioStage below), and the per-row int
+// table of a call through `audio_info_h` (stage_row_info).
 struct MelStftDev {
     bool ready = false;
     float* basis_Bt = nullptr;          // [1056 (= 2*513 padded to 33*32)][1024]
     float* mel_Bt = nullptr;            // [80][544]
     std::vector<void*> allocs;
-    DevBuf frames, mag, io_in, io_out;
+    DevBuf frames, mag;
 };
 
 // Waveform clean-up (audio_proc.hip): DFT bases built on first use, no weights
@@ -205,16 +210,14 @@ struct AudioProcDev {
     float* inv_Bt = nullptr;            // [2048][2080] irfft terms x synthesis window
     double* win2 = nullptr;             // [2048] hann^2
     std::vector<void*> allocs;
-    DevBuf ws, io, trim_win;            // workspace, host staging, trim window (+ its reversal) for window length trim_wl
+    DevBuf ws, trim_win;                // workspace, trim window (+ its reversal) for window length trim_wl
     int trim_wl = -1;
-    std::vector<int> info_h;            // per-row facts staged to the device
 };
 
 // Resampling (resample.hip): the W_8192 twiddle table built on first use; the workspace holds, per row, the stage lines
 // (signal and filter: 16 * max(L_fwd, L_inv) bytes) and the kept rfft bins (8 * (N_b // 2 + 1) bytes)
 struct ResampleDev {
-    DevBuf tw, ws, io;                  // twiddles, workspace, host staging
-    std::vector<int> info_h;            // per-row facts staged to the device
+    DevBuf tw, ws;                      // twiddles, workspace
 };
 
 struct TimedLaunch {
@@ -233,6 +236,11 @@ struct tts_hip_engine {
     MelStftDev stft;
     AudioProcDev aproc;
     ResampleDev resamp;
+    // Host staging of every synchronous audio call (AudioStage).  One buffer serves them all: calls on one handle are
+    // serialised by the caller and a synchronous call drains the stream before it returns, so no call finds another's data
+    // still in use here; a call that needs more than its predecessors reallocates it before it copies anything in.
+    DevBuf audio_io;
+    std::vector<int> audio_info_h;      // host image of a call's per-row int table (stage_row_info)
     // timing hooks
     bool timing = false;
     std::vector<TimedLaunch> timed;
@@ -285,9 +293,47 @@ void waveglow_free(tts_hip_engine* e);
 int tacotron2_finalize(tts_hip_engine* e);
 void tacotron2_free(tts_hip_engine* e);
 
+// ---- audio front end
+// What a probe copies out of a workspace: `rows` rows of `width` floats, `pitch` floats apart
+struct StageView {
+    const void* p;
+    size_t rows, width, pitch;
+};
+// the view's logical extent (row padding dropped) to `out`, host or device as `mem` says, on e->stream
+int copy_stage_out(tts_hip_engine* e, const StageView& v, float* out, int mem);
+// e->audio_info_h to d_info on e->stream (pageable source: the copy has left it when the call returns)
+int stage_row_info(tts_hip_engine* e, int* d_info);
+
+// One synchronous audio call's way in and out.  Declare the caller's inputs and outputs, begin(), run on ptr(slot), finish().
+// TTS_HIP_MEM_HOST: begin() carves `audio_io` and copies the inputs in, ptr() is the slot's slice, finish() copies the
+// outputs back; TTS_HIP_MEM_DEVICE: ptr() is the caller's own pointer.  finish() drains e->stream either way.  A NULL
+// input stays NULL; scratch() is a device slice of audio_io whatever `mem` says.
+class AudioStage {
+public:
+    AudioStage(tts_hip_engine* eng, int mem) : e(eng), host(mem == TTS_HIP_MEM_HOST) {}
+    int in(const void* p, size_t bytes) { return add(const_cast<void*>(p), bytes, IN, host && p); }
+    int out(void* p, size_t bytes) { return add(p, bytes, OUT, host && p); }
+    int scratch(size_t bytes) { return add(nullptr, bytes, SCRATCH, true); }
+    int begin();
+    int finish();
+    template <class T>
+    T* ptr(int slot) const { return (T*)(slots[slot].staged ? (char*)e->audio_io.p + slots[slot].off : (char*)slots[slot].user); }
+
+private:
+    enum Kind { IN, OUT, SCRATCH };
+    struct Slot { void* user; size_t bytes, off; Kind kind; bool staged; };
+    int add(void* p, size_t bytes, Kind kind, bool staged) {
+        slots.push_back(Slot{p, bytes, staged ? carve.take(bytes) : 0, kind, staged});
+        return (int)slots.size() - 1;
+    }
+    tts_hip_engine* e;
+    bool host;
+    Carve carve;
+    std::vector<Slot> slots;
+};
+
 int melstft_finalize(tts_hip_engine* e);
-int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_mel, int stop = -1,
-                const float** stop_out = nullptr);
+int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_mel, int stop = -1, StageView* stop_out = nullptr);
 void melstft_free(tts_hip_engine* e);
 void audioproc_free(tts_hip_engine* e);
 void resample_free(tts_hip_engine* e);

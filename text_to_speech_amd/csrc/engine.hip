@@ -191,6 +191,34 @@ int philox_fill_rows(tts_hip_engine* e, float* out, int B, long long row_stride,
     return TTS_HIP_OK;
 }
 
+// ------------------------------------------------------------------------------------------- audio calls: staging
+int AudioStage::begin() {
+    if (carve.o) HIPCHK(e, e->audio_io.ensure(carve.o));
+    for (int i = 0; i < (int)slots.size(); ++i)
+        if (slots[i].staged && slots[i].kind == IN)
+            HIPCHK(e, hipMemcpyAsync(ptr<void>(i), slots[i].user, slots[i].bytes, hipMemcpyHostToDevice, e->stream));
+    return TTS_HIP_OK;
+}
+
+int AudioStage::finish() {
+    for (int i = 0; i < (int)slots.size(); ++i)
+        if (slots[i].staged && slots[i].kind == OUT)
+            HIPCHK(e, hipMemcpyAsync(slots[i].user, ptr<void>(i), slots[i].bytes, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return TTS_HIP_OK;
+}
+
+int copy_stage_out(tts_hip_engine* e, const StageView& v, float* out, int mem) {
+    const hipMemcpyKind kind = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    HIPCHK(e, hipMemcpy2DAsync(out, v.width * 4, v.p, v.pitch * 4, v.width * 4, v.rows, kind, e->stream));
+    return TTS_HIP_OK;
+}
+
+int stage_row_info(tts_hip_engine* e, int* d_info) {
+    HIPCHK(e, hipMemcpyAsync(d_info, e->audio_info_h.data(), e->audio_info_h.size() * 4, hipMemcpyHostToDevice, e->stream));
+    return TTS_HIP_OK;
+}
+
 // Box probe (bench.py): what the fp32 matrix pipe of THIS device sustains right now on a bare v_mfma_f32_32x32x2_f32 loop with
 // the register traffic of the WN GEMMs (8 independent accumulators per wave, 2 waves per SIMD, every CU; scripts/micro/
 // mfma_f32_rate.cpp is the stand-alone version: 155.3 TFLOP/s at 2.398 GHz on the round-3 boxes), and the shader clock it
@@ -268,6 +296,7 @@ int tts_hip_destroy(tts_hip_engine* e) {
     melstft_free(e);
     audioproc_free(e);
     resample_free(e);
+    e->audio_io.release();
     (void)hipStreamDestroy(e->stream);
     delete e;
     return TTS_HIP_OK;
@@ -596,68 +625,6 @@ int tts_hip_waveglow_infer_rows_seeded_async(tts_hip_engine* e, const float* mel
                        precision, true);
     c.keys = keys, c.offsets = offsets, c.stream = stream;
     return waveglow_call(e, c);
-}
-
-int tts_hip_mel_stft_async(tts_hip_engine* e, const float* audio, int B, int N, float* mel, void* stream) {
-    if (!e) return TTS_HIP_EINVAL;
-    if (!e->stft.ready) return set_err(e, TTS_HIP_ENOTREADY, "mel_stft not finalized");
-    if (!audio || !mel || B <= 0 || N < 1024) return set_err(e, TTS_HIP_EINVAL, "mel_stft_async: bad argument (N >= 1024)");
-    HIPCHK(e, hipSetDevice(e->device));
-    StreamScope scope(e, stream);
-    return melstft_run(e, audio, B, N, mel);
-}
-
-int tts_hip_mel_stft(tts_hip_engine* e, const float* audio, int B, int N, float* mel, int mem) {
-    if (!e) return TTS_HIP_EINVAL;
-    if (!e->stft.ready) return set_err(e, TTS_HIP_ENOTREADY, "mel_stft not finalized");
-    if (!audio || !mel || B <= 0 || N < 1024) return set_err(e, TTS_HIP_EINVAL, "mel_stft: bad argument (N >= 1024)");
-    HIPCHK(e, hipSetDevice(e->device));
-    const size_t n_in = (size_t)B * N, n_out = (size_t)B * (N / 256 + 1) * 80;
-    const float* d_in = audio;
-    float* d_out = mel;
-    if (mem == TTS_HIP_MEM_HOST) {
-        HIPCHK(e, e->stft.io_in.ensure(n_in * 4));
-        HIPCHK(e, e->stft.io_out.ensure(n_out * 4));
-        HIPCHK(e, hipMemcpyAsync(e->stft.io_in.p, audio, n_in * 4, hipMemcpyHostToDevice, e->stream));
-        d_in = e->stft.io_in.f();
-        d_out = e->stft.io_out.f();
-    } else if (mem != TTS_HIP_MEM_DEVICE) {
-        return set_err(e, TTS_HIP_EINVAL, "mel_stft: bad mem kind %d", mem);
-    }
-    int rc = melstft_run(e, d_in, B, N, d_out);
-    if (rc) return rc;
-    if (mem == TTS_HIP_MEM_HOST) HIPCHK(e, hipMemcpyAsync(mel, d_out, n_out * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return TTS_HIP_OK;
-}
-
-// Test hook: melstft_run on `audio` up to stage `what`, then the stage's logical extent (row padding dropped) to `out`.
-int tts_hip_mel_stft_probe(tts_hip_engine* e, const float* audio, int B, int N, int what, float* out, int mem) {
-    if (!e) return TTS_HIP_EINVAL;
-    if (!e->stft.ready) return set_err(e, TTS_HIP_ENOTREADY, "mel_stft not finalized");
-    if (!audio || !out || B <= 0 || N < 1024 || what < 0 || what > 3)
-        return set_err(e, TTS_HIP_EINVAL, "mel_stft_probe: bad argument (N >= 1024, what 0 .. 3)");
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "mel_stft_probe: bad mem kind %d", mem);
-    HIPCHK(e, hipSetDevice(e->device));
-    const int F = N / 256 + 1;
-    const size_t n_in = (size_t)B * N;
-    const float* d_in = audio;
-    if (mem == TTS_HIP_MEM_HOST) {
-        HIPCHK(e, e->stft.io_in.ensure(n_in * 4));
-        HIPCHK(e, hipMemcpyAsync(e->stft.io_in.p, audio, n_in * 4, hipMemcpyHostToDevice, e->stream));
-        d_in = e->stft.io_in.f();
-    }
-    HIPCHK(e, e->stft.io_out.ensure((size_t)B * F * 80 * 4));       // the linear mel lands here (stage 3 only)
-    const float* src = nullptr;
-    if (int rc = melstft_run(e, d_in, B, N, e->stft.io_out.f(), what, &src)) return rc;
-    // (rows, logical width, stored row stride) of the stage, in floats
-    const size_t rows = what == 0 ? (size_t)B : (size_t)B * F;
-    const size_t width = what == 0 ? (size_t)N + 1024 : what == 1 ? 1026 : what == 2 ? 513 : 80;
-    const size_t pitch = what == 0 ? ((size_t)N + 1024 + 3) / 4 * 4 : what == 1 ? 1056 : what == 2 ? 544 : 80;
-    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    HIPCHK(e, hipMemcpy2DAsync(out, width * 4, src, pitch * 4, width * 4, rows, kout, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return TTS_HIP_OK;
 }
 
 int tts_hip_kernel_timing(tts_hip_engine* e, int enable) {

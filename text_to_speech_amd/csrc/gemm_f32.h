@@ -107,6 +107,27 @@ struct GemmArgs {
     int mask_out;                   // with rowmask: multiply the pre-activation by the mask and skip altbias
 };
 
+// out[M][Nout] = A x Bt^T with no bias and no activation: A's rows lda floats apart and K wide (K a multiple of 32), Bt
+// [Nout][ldb].  bz > 1 slices: slice z reads A + z * strideAz and writes out + z * strideOutZ.  The caller picks the kernel.
+inline GemmArgs gemm_linear(const float* A, long long lda, int K, const float* Bt, long long ldb, int Nout, int M, float* out,
+                            long long strideAz = 0, long long strideOutZ = 0) {
+    GemmArgs g{};
+    g.M = M;
+    g.N = Nout;
+    g.L = M;
+    g.nseg = 1;
+    g.seg[0] = ASeg{A, lda, 0, K, K};
+    g.strideAz = strideAz;
+    g.Bt = Bt;
+    g.ldb = ldb;
+    g.mode = EPI_LINEAR;
+    g.split = Nout;
+    g.out0 = out;
+    g.ld0 = Nout;
+    g.strideOutZ = strideOutZ;
+    return g;
+}
+
 __device__ __forceinline__ float act_apply(float v, int act) {
     if (act == ACT_RELU) return fmaxf(v, 0.f);
     if (act == ACT_TANH) return tanhf(v);

@@ -1,4 +1,4 @@
-// host_check.cpp -- CPU-only build of the host code that reads untrusted input (ttsw_host.h), for the sanitizers:
+// host_check.cpp -- CPU-only build of the host code that reads untrusted input (ttsw_host.h, the call checks), for the sanitizers:
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all host_check.cpp -o ttsw_check_asan
 // (csrc/build_host_asan.sh; GPU AddressSanitizer is not available on the pool, and this code needs no GPU).
 // usage: ttsw_check_asan [--load] file...   -- one line per file: "<status> <tensors> <floats> <message>"; --load also reads
@@ -17,10 +17,19 @@
 // null=mel,audio,keys,offsets to pass that pointer as NULL.  First line "<status> <message>" of wg_call_check; when the call
 // is accepted: "F n_gap", then the lines "info ...", "run_tails ..." and "counts ..." of wg_call_table
 // (tests/test_wg_call.py compares them with packing_plan and a numpy restatement).
+//        ttsw_check_asan --audio-call KIND [KEY=VALUE...] [LEN...]  -- the front end of an audio call (audio_call.h), KIND one
+// of reduce_noise, trim, resample, silence, for a batch of B = number of LEN rows of N samples (no LEN: lengths NULL, B from
+// B=) run as an entry point named "who".  Settings: B= N= mem= (default 1, device), null=audio,out,lens (out: every output
+// pointer; lens: out_lengths), overlap=1 (out one float behind audio) and the call's own arguments under their C names
+// (noise_len; window_length threshold add_start add_end mode; rate target_rate M; method mode rate threshold min_silence
+// block_size replace_by min_voice_time).  First line "<status> <message>"; when the call is accepted the geometry the check
+// derived: reduce_noise "Fr NP Frn NQ total", trim "W Wp Cst", silence "NT NB cap w total", resample one line
+// "logf logi M_b" per row (tests/test_audio_call.py compares them with a Python restatement).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
 
+#include "audio_call.h"
 #include "ttsw_host.h"
 #include "wg_call.h"
 #include "wg_plan.h"
@@ -105,7 +114,80 @@ static int print_wg_call(int argc, char** argv) {
     return 0;
 }
 
+static int print_audio_call(int argc, char** argv) {
+    // never read: the checks only test and compare the pointers, so two addresses 4 GiB apart stand for the buffers
+    const float* audio = (const float*)(uintptr_t)0x100000000ull;
+    float* out = (float*)(uintptr_t)0x200000000ull;
+    static int32_t out_lengths;
+    const int32_t* lens_out = &out_lengths;
+    const std::string kind = argv[2];
+    std::map<std::string, double> v{{"B", -1}, {"N", 0}, {"mem", TTS_HIP_MEM_DEVICE}, {"noise_len", 1}, {"window_length", 2},
+                                    {"threshold", 0.1}, {"add_start", 0}, {"add_end", 0}, {"mode", 0}, {"rate", 1},
+                                    {"target_rate", 1}, {"M", 0}, {"method", 0}, {"min_silence", 0.1}, {"block_size", 1},
+                                    {"replace_by", 0}, {"min_voice_time", 0}, {"overlap", 0}};
+    std::vector<int32_t> lengths;
+    for (int i = 3; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) {
+            lengths.push_back((int32_t)atoi(argv[i]));
+            continue;
+        }
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        if (key == "null") {
+            if (strstr(eq, "audio")) audio = nullptr;
+            if (strstr(eq, "out")) out = nullptr;
+            if (strstr(eq, "lens")) lens_out = nullptr;
+        } else if (v.count(key)) {
+            v[key] = atof(eq + 1);
+        } else {
+            return 2;
+        }
+    }
+    if (v["overlap"] != 0 && audio) out = const_cast<float*>(audio) + 1;
+    const int32_t* lp = lengths.empty() ? nullptr : lengths.data();
+    const int B = lengths.empty() ? (int)v["B"] : (int)lengths.size(), N = (int)v["N"], mem = (int)v["mem"];
+    char why[256] = "";
+    std::vector<int> lens, mlens;
+    if (kind == "reduce_noise") {
+        const int rc = rn_check("who", audio, B, N, lp, (int)v["noise_len"], out, mem, lens, why, sizeof why);
+        printf("%d %s\n", rc, why);
+        if (rc) return 0;
+        const RnGeom g = rn_geom(B, N, (int)v["noise_len"]);
+        printf("%d %d %d %d %zu\n", g.Fr, g.NP, g.Frn, g.NQ, g.total);
+    } else if (kind == "trim") {
+        TrimGeom g{};
+        const int rc = trim_check("who", audio, out != nullptr, B, N, lp, (int)v["window_length"], v["threshold"], v["add_start"],
+                                  v["add_end"], (int)v["mode"], mem, lens, &g, why, sizeof why);
+        printf("%d %s\n", rc, why);
+        if (rc) return 0;
+        printf("%d %d %d\n", g.W, g.Wp, g.Cst);
+    } else if (kind == "resample") {
+        const int rc = rs_check("who", audio, B, N, lp, (int)v["rate"], (int)v["target_rate"], out, (int)v["M"], mem, lens, mlens,
+                                why, sizeof why);
+        printf("%d %s\n", rc, why);
+        if (rc) return 0;
+        if ((int)lens.size() != B || (int)mlens.size() != B) return 2;
+        for (int b = 0; b < B; ++b) {
+            const RsLens l = rs_lens(lens[b], mlens[b]);
+            printf("%d %d %d\n", l.logf, l.logi, mlens[b]);
+        }
+    } else if (kind == "silence") {
+        SilCall c;
+        const int rc = sil_check("who", audio, B, N, lp, (int)v["method"], (int)v["mode"], (int)v["rate"], v["threshold"],
+                                 v["min_silence"], (int)v["block_size"], (int)v["replace_by"], v["min_voice_time"], out, lens_out,
+                                 mem, c, why, sizeof why);
+        printf("%d %s\n", rc, why);
+        if (rc) return 0;
+        if ((int)c.lens.size() != B) return 2;
+        printf("%d %d %d %d %zu\n", c.NT, c.NB, c.cap, c.w, c.total);
+    } else {
+        return 2;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 3 && !strcmp(argv[1], "--audio-call")) return print_audio_call(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wg-call")) return print_wg_call(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wn-taps")) {
         std::vector<int> lens;

@@ -70,8 +70,6 @@ void melstft_free(tts_hip_engine* e) {
     e->stft.allocs.clear();
     e->stft.frames.release();
     e->stft.mag.release();
-    e->stft.io_in.release();
-    e->stft.io_out.release();
     e->stft.ready = false;
 }
 
@@ -111,13 +109,13 @@ int melstft_finalize(tts_hip_engine* e) {
     return TTS_HIP_OK;
 }
 
-// stop (tts_hip_mel_stft_probe): 0 .. 3 returns right after that stage with *stop_out pointing at what it wrote -- 0 the
+// stop (tts_hip_mel_stft_probe): 0 .. 3 returns right after that stage with *stop_out describing what it wrote -- 0 the
 // reflect-padded rows [B][NP], 1 the spectrum [B * F][NB], 2 the magnitudes [B * F][MAGK], 3 the linear mel [B * F][80]
-// (d_mel itself, before the logarithm); -1 runs everything.
-int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_mel, int stop, const float** stop_out) {
+// (d_mel itself, before the logarithm), each with its logical width beside the stored one; -1 runs everything.
+int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_mel, int stop, StageView* stop_out) {
     MelStftDev& s = e->stft;
-    auto stop_at = [&](int stage, const float* p) {
-        if (stop == stage && stop_out) *stop_out = p;
+    auto stop_at = [&](int stage, const float* p, size_t rows, size_t width, size_t pitch) {
+        if (stop == stage && stop_out) *stop_out = StageView{p, rows, width, pitch};
         return stop == stage;
     };
     const int NP = (N + FL + 3) / 4 * 4;      // padded row stride (16-B aligned rows for the float4 operand loads)
@@ -129,56 +127,68 @@ int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_
     float* ft = padded + (((size_t)B * NP + 63) / 64) * 64;
     {
         const long long n = (long long)B * NP;
-        hipLaunchKernelGGL(reflect_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_audio, padded, N,
-                           B, NP);
+        hipLaunchKernelGGL(reflect_pad_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, d_audio, padded, N, B, NP);
         HIPCHK(e, hipGetLastError());
     }
-    if (stop_at(0, padded)) return TTS_HIP_OK;
-    {   // ft[b][f][r] = sum_n padded[b][f*256 + n] * basis[r][n]
-        GemmArgs g{};
-        g.M = F;
-        g.N = NB;
-        g.L = F;
-        g.nseg = 1;
-        g.seg[0] = ASeg{padded, HOP, 0, FL, FL};
-        g.strideAz = NP;
-        g.Bt = s.basis_Bt;
-        g.ldb = FL;
-        g.mode = EPI_LINEAR;
-        g.split = NB;
-        g.out0 = ft;
-        g.ld0 = NB;
-        g.strideOutZ = (long long)F * NB;
-        HIPCHK(e, gemm_small(g, B, st));
-    }
-    if (stop_at(1, ft)) return TTS_HIP_OK;
+    if (stop_at(0, padded, B, (size_t)N + FL, NP)) return TTS_HIP_OK;
+    // ft[b][f][r] = sum_n padded[b][f*256 + n] * basis[r][n], one z slice per row of the batch
+    HIPCHK(e, gemm_small(gemm_linear(padded, HOP, FL, s.basis_Bt, FL, NB, F, ft, NP, (long long)F * NB), B, st));
+    if (stop_at(1, ft, (size_t)B * F, 2 * CUT, NB)) return TTS_HIP_OK;
     {
         const long long n = (long long)B * F * MAGK;
-        hipLaunchKernelGGL(magnitude_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ft, s.mag.f(),
-                           (long long)B * F);
+        hipLaunchKernelGGL(magnitude_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, ft, s.mag.f(), (long long)B * F);
         HIPCHK(e, hipGetLastError());
     }
-    if (stop_at(2, s.mag.f())) return TTS_HIP_OK;
-    {   // mel[m][j] = sum_c mag[m][c] * mel_basis[j][c]
-        GemmArgs g{};
-        g.M = B * F;
-        g.N = NMEL;
-        g.L = B * F;
-        g.nseg = 1;
-        g.seg[0] = ASeg{s.mag.f(), MAGK, 0, MAGK, MAGK};
-        g.Bt = s.mel_Bt;
-        g.ldb = MAGK;
-        g.mode = EPI_LINEAR;
-        g.split = NMEL;
-        g.out0 = d_mel;
-        g.ld0 = NMEL;
-        HIPCHK(e, gemm_small(g, 1, st));
-    }
-    if (stop_at(3, d_mel)) return TTS_HIP_OK;
+    if (stop_at(2, s.mag.f(), (size_t)B * F, CUT, MAGK)) return TTS_HIP_OK;
+    // mel[m][j] = sum_c mag[m][c] * mel_basis[j][c]
+    HIPCHK(e, gemm_small(gemm_linear(s.mag.f(), MAGK, MAGK, s.mel_Bt, MAGK, NMEL, B * F, d_mel), 1, st));
+    if (stop_at(3, d_mel, (size_t)B * F, NMEL, NMEL)) return TTS_HIP_OK;
     {
         const long long n = (long long)B * F * NMEL;
-        hipLaunchKernelGGL(log_clamp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_mel, n, 1e-5f);
+        hipLaunchKernelGGL(log_clamp_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, d_mel, n, 1e-5f);
         HIPCHK(e, hipGetLastError());
     }
     return TTS_HIP_OK;
+}
+
+int tts_hip_mel_stft_async(tts_hip_engine* e, const float* audio, int B, int N, float* mel, void* stream) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (!e->stft.ready) return set_err(e, TTS_HIP_ENOTREADY, "mel_stft not finalized");
+    if (!audio || !mel || B <= 0 || N < 1024) return set_err(e, TTS_HIP_EINVAL, "mel_stft_async: bad argument (N >= 1024)");
+    HIPCHK(e, hipSetDevice(e->device));
+    StreamScope scope(e, stream);
+    return melstft_run(e, audio, B, N, mel);
+}
+
+int tts_hip_mel_stft(tts_hip_engine* e, const float* audio, int B, int N, float* mel, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (!e->stft.ready) return set_err(e, TTS_HIP_ENOTREADY, "mel_stft not finalized");
+    if (!audio || !mel || B <= 0 || N < 1024) return set_err(e, TTS_HIP_EINVAL, "mel_stft: bad argument (N >= 1024)");
+    char why[256];
+    if (int rc = audio_mem_check("mel_stft", mem, why, sizeof why)) return set_err(e, rc, "%s", why);
+    HIPCHK(e, hipSetDevice(e->device));
+    AudioStage io(e, mem);
+    const int in = io.in(audio, (size_t)B * N * 4), out = io.out(mel, (size_t)B * (N / 256 + 1) * 80 * 4);
+    if (int rc = io.begin()) return rc;
+    if (int rc = melstft_run(e, io.ptr<const float>(in), B, N, io.ptr<float>(out))) return rc;
+    return io.finish();
+}
+
+// Test hook: melstft_run on `audio` up to stage `what`, then the stage's logical extent (row padding dropped) to `out`.
+int tts_hip_mel_stft_probe(tts_hip_engine* e, const float* audio, int B, int N, int what, float* out, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (!e->stft.ready) return set_err(e, TTS_HIP_ENOTREADY, "mel_stft not finalized");
+    if (!audio || !out || B <= 0 || N < 1024 || what < 0 || what > 3)
+        return set_err(e, TTS_HIP_EINVAL, "mel_stft_probe: bad argument (N >= 1024, what 0 .. 3)");
+    char why[256];
+    if (int rc = audio_mem_check("mel_stft_probe", mem, why, sizeof why)) return set_err(e, rc, "%s", why);
+    HIPCHK(e, hipSetDevice(e->device));
+    AudioStage io(e, mem);
+    const int in = io.in(audio, (size_t)B * N * 4);
+    const int mel = io.scratch((size_t)B * (N / 256 + 1) * 80 * 4);      // the linear mel lands here (stage 3 only)
+    if (int rc = io.begin()) return rc;
+    StageView view{};
+    if (int rc = melstft_run(e, io.ptr<const float>(in), B, N, io.ptr<float>(mel), what, &view)) return rc;
+    if (int rc = copy_stage_out(e, view, out, mem)) return rc;
+    return io.finish();
 }

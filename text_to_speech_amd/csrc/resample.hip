@@ -34,8 +34,6 @@ namespace {
 
 constexpr int PMAX = 8192, LOG_PMAX = 13;          // points per workgroup (64 KiB of LDS)
 constexpr int NT = 256;                            // threads per workgroup
-constexpr int RS_MAX_LEN = 1 << 24;                // samples per row, in and out
-constexpr long long LIM31 = 1ll << 31;
 
 enum { LD_PLAIN, LD_FWD_IN, LD_PROD, LD_INV_IN };
 enum { ST_PLAIN, ST_FWD_OUT, ST_INV_OUT };
@@ -251,30 +249,12 @@ __global__ void rs_zero_tail_kernel(float* out, long long M, const int* mlen) {
         out[(size_t)b * M + j] = 0.f;
 }
 
-int ilog2(long long v) {
-    int l = 0;
-    while ((1ll << l) < v) ++l;
-    return l;
-}
-
-struct RsLens {
-    int logf, logi;             // log2 of the forward / inverse Bluestein lengths
-};
-
-// L_fwd >= N + N//2, L_inv >= 2M - 1, both at least 64
-RsLens rs_lens(int n, int m) { return {std::max(6, ilog2((long long)n + n / 2)), std::max(6, ilog2(2ll * m - 1))}; }
-
-int out_len(int n, int rate, int target_rate) { return (int)((double)n / rate * target_rate); }
-
-size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 void resample_free(tts_hip_engine* e) {
     ResampleDev& r = e->resamp;
     r.tw.release();
     r.ws.release();
-    r.io.release();
 }
 
 namespace {
@@ -358,7 +338,7 @@ int resample_run(tts_hip_engine* e, const float* d_in, int B, int N, const std::
         const RsLens l = rs_lens(lens[b], mlens[b]);
         groups[{l.logf, l.logi}].push_back(b);
     }
-    size_t ws = 0;
+    size_t lines = 0;
     std::vector<int> xstride;
     for (auto& g : groups) {
         int xs = 0;
@@ -366,22 +346,24 @@ int resample_run(tts_hip_engine* e, const float* d_in, int B, int N, const std::
         xstride.push_back(xs);
         const size_t G = g.second.size();
         const size_t L = (size_t)1 << std::max(g.first.first, g.first.second);
-        ws = std::max(ws, al256(2 * G * L * 8) + al256(G * (size_t)xs * 8));
+        lines = std::max(lines, al256(2 * G * L * 8) + al256(G * (size_t)xs * 8));
     }
-    const size_t info_bytes = al256((size_t)3 * B * 4);
-    HIPCHK(e, r.ws.ensure(info_bytes + ws));
-    int* d_info = (int*)r.ws.p;
-    char* base = (char*)r.ws.p + info_bytes;
+    Carve ws;
+    const size_t off_info = ws.take((size_t)3 * B * 4), off_lines = ws.take(lines);
+    HIPCHK(e, r.ws.ensure(ws.o));
+    int* d_info = (int*)((char*)r.ws.p + off_info);
+    char* base = (char*)r.ws.p + off_lines;
     // [0, B) N_b, [B, 2B) M_b, [2B, 3B) the batch rows of each group in turn
-    r.info_h.assign((size_t)3 * B, 0);
+    std::vector<int>& info_h = e->audio_info_h;
+    info_h.assign((size_t)3 * B, 0);
     for (int b = 0; b < B; ++b) {
-        r.info_h[b] = lens[b];
-        r.info_h[B + b] = mlens[b];
+        info_h[b] = lens[b];
+        info_h[B + b] = mlens[b];
     }
     int k = 2 * B;
     for (auto& g : groups)
-        for (int b : g.second) r.info_h[k++] = b;
-    HIPCHK(e, hipMemcpyAsync(d_info, r.info_h.data(), r.info_h.size() * 4, hipMemcpyHostToDevice, st));
+        for (int b : g.second) info_h[k++] = b;
+    if (int rc = stage_row_info(e, d_info)) return rc;
     const float2* tw = (const float2*)r.tw.p;
     int first = 2 * B, gi = 0;
     for (auto& g : groups) {
@@ -418,38 +400,6 @@ int resample_run(tts_hip_engine* e, const float* d_in, int B, int N, const std::
     return TTS_HIP_OK;
 }
 
-// host-side validation shared by both entry points; fills the row lengths in and out
-int rs_check(tts_hip_engine* e, const char* what, const float* audio, int B, int N, const int32_t* lengths, int rate,
-             int target_rate, const float* out, int M, std::vector<int>& lens, std::vector<int>& mlens) {
-    if (!audio || !out || B <= 0 || N <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", what);
-    if (rate <= 0 || target_rate <= 0)
-        return set_err(e, TTS_HIP_EINVAL, "%s: rates must be > 0 (rate %d, target_rate %d)", what, rate, target_rate);
-    if (N > RS_MAX_LEN) return set_err(e, TTS_HIP_EINVAL, "%s: N = %d > 2^24 samples per row", what, N);
-    const double md = (double)N / rate * target_rate;
-    if (!(md < (double)RS_MAX_LEN + 1))
-        return set_err(e, TTS_HIP_EINVAL, "%s: %d samples at %d -> %d Hz give more than 2^24 samples per row", what, N, rate,
-                       target_rate);
-    const int want = out_len(N, rate, target_rate);
-    if (want < 1) return set_err(e, TTS_HIP_EINVAL, "%s: %d samples at %d -> %d Hz give M = %d < 1", what, N, rate, target_rate, want);
-    if (M != want)
-        return set_err(e, TTS_HIP_EINVAL, "%s: M = %d, but int(%d / %d * %d) = %d", what, M, N, rate, target_rate, want);
-    if ((long long)B * M * 4 >= LIM31 || (long long)B * N * 4 >= LIM31)
-        return set_err(e, TTS_HIP_EINVAL, "%s: B = %d x N = %d (M %d) too large for 31-bit offsets", what, B, N, M);
-    lens.assign(B, N);
-    mlens.assign(B, M);
-    for (int b = 0; b < B; ++b) {
-        if (lengths) {
-            if (lengths[b] < 1 || lengths[b] > N)
-                return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d outside [1, N = %d]", what, b, lengths[b], N);
-            lens[b] = lengths[b];
-            mlens[b] = out_len(lens[b], rate, target_rate);
-            if (mlens[b] < 1)
-                return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d resamples to %d < 1 samples", what, b, lens[b], mlens[b]);
-        }
-    }
-    return TTS_HIP_OK;
-}
-
 // rate == target_rate: the rows as they are (zero beyond lengths[b]), copies only, nothing launched
 int rs_copy_rows(tts_hip_engine* e, const float* in, int B, int N, const std::vector<int>& lens, float* out, hipMemcpyKind kind,
                  hipStream_t st) {
@@ -472,7 +422,10 @@ int tts_hip_resample_async(tts_hip_engine* e, const float* audio, int B, int N, 
                            int target_rate, float* out, int M, void* stream) {
     if (!e) return TTS_HIP_EINVAL;
     std::vector<int> lens, mlens;
-    if (int rc = rs_check(e, "resample_async", audio, B, N, lengths, rate, target_rate, out, M, lens, mlens)) return rc;
+    char why[256];
+    if (int rc = rs_check("resample_async", audio, B, N, lengths, rate, target_rate, out, M, TTS_HIP_MEM_DEVICE, lens, mlens, why,
+                          sizeof why))
+        return set_err(e, rc, "%s", why);
     HIPCHK(e, hipSetDevice(e->device));
     StreamScope scope(e, stream);
     if (rate == target_rate) return rs_copy_rows(e, audio, B, N, lens, out, hipMemcpyDeviceToDevice, e->stream);
@@ -483,8 +436,9 @@ int tts_hip_resample(tts_hip_engine* e, const float* audio, int B, int N, const 
                      float* out, int M, int mem) {
     if (!e) return TTS_HIP_EINVAL;
     std::vector<int> lens, mlens;
-    if (int rc = rs_check(e, "resample", audio, B, N, lengths, rate, target_rate, out, M, lens, mlens)) return rc;
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "resample: bad mem kind %d", mem);
+    char why[256];
+    if (int rc = rs_check("resample", audio, B, N, lengths, rate, target_rate, out, M, mem, lens, mlens, why, sizeof why))
+        return set_err(e, rc, "%s", why);
     if (rate == target_rate && mem == TTS_HIP_MEM_HOST) return rs_copy_rows(e, audio, B, N, lens, out, hipMemcpyHostToHost, nullptr);
     HIPCHK(e, hipSetDevice(e->device));
     if (rate == target_rate) {
@@ -492,18 +446,9 @@ int tts_hip_resample(tts_hip_engine* e, const float* audio, int B, int N, const 
         HIPCHK(e, hipStreamSynchronize(e->stream));
         return TTS_HIP_OK;
     }
-    ResampleDev& r = e->resamp;
-    const size_t nin = (size_t)B * N, nout = (size_t)B * M;
-    const float* d_in = audio;
-    float* d_out = out;
-    if (mem == TTS_HIP_MEM_HOST) {
-        HIPCHK(e, r.io.ensure(al256(nin * 4) + nout * 4));
-        HIPCHK(e, hipMemcpyAsync(r.io.p, audio, nin * 4, hipMemcpyHostToDevice, e->stream));
-        d_in = r.io.f();
-        d_out = (float*)((char*)r.io.p + al256(nin * 4));
-    }
-    if (int rc = resample_run(e, d_in, B, N, lens, mlens, d_out, M)) return rc;
-    if (mem == TTS_HIP_MEM_HOST) HIPCHK(e, hipMemcpyAsync(out, d_out, nout * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return TTS_HIP_OK;
+    AudioStage io(e, mem);
+    const int in = io.in(audio, (size_t)B * N * 4), res = io.out(out, (size_t)B * M * 4);
+    if (int rc = io.begin()) return rc;
+    if (int rc = resample_run(e, io.ptr<const float>(in), B, N, lens, mlens, io.ptr<float>(res), M)) return rc;
+    return io.finish();
 }

@@ -15,45 +15,14 @@
 // The whole call is enqueued on the stream; no stage reads anything back on the host.  Every row b has its own length
 // L_b <= N; nothing at or beyond L_b is read.
 #include "engine.h"
+#include "audio_dev.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
 
-constexpr int SIL_TILE = 2048;               // samples per workgroup of the tile kernels (256 threads x 8 consecutive)
-constexpr int SIL_PER = 8;
-constexpr long long SIL_LIM = 1ll << 31;
-
-struct OpAdd {
-    template <class T> __device__ static T id() { return T(0); }
-    template <class T> __device__ T operator()(T a, T b) const { return a + b; }
-};
-struct OpMax {
-    template <class T> __device__ static T id() { return T(-1); }      // the scanned values are indices >= 0, or -1
-    template <class T> __device__ T operator()(T a, T b) const { return a > b ? a : b; }
-};
-
-// inclusive scan over the workgroup's threads (<= 1024: 16 waves of 64); `total` = the reduction over all of them.
-// sh holds 16 values; the helper may be called again at once (it ends on a barrier).
-template <class T, class Op>
-__device__ T block_scan(T v, T* sh, T& total, Op op) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const T u = __shfl_up(v, o);
-        if (lane >= o) v = op(u, v);
-    }
-    if (lane == 63) sh[w] = v;
-    __syncthreads();
-    T base = Op::template id<T>(), all = Op::template id<T>();
-    for (int i = 0; i < nw; ++i) {
-        if (i < w) base = op(base, sh[i]);
-        all = op(all, sh[i]);
-    }
-    __syncthreads();
-    total = all;
-    return op(base, v);
-}
+constexpr int SIL_PER = 8;                   // consecutive samples per thread of a SIL_TILE workgroup (audio_call.h)
 
 // ---------------------------------------------------------------------------------------------- shared: scan and compaction
 // off[b][k] = sum of val[b][0..k) over the row's tiles k < ceil(L_b / SIL_TILE), total[b] = their sum (one workgroup per row;
@@ -85,8 +54,7 @@ __global__ __launch_bounds__(256) void sil_tile_count_kernel(const uint8_t* __re
 #pragma unroll
     for (int u = 0; u < SIL_PER; ++u)
         if (t0 + u < L) c += mask[(long long)b * N + t0 + u];
-    int all;
-    block_scan(c, sh, all, OpAdd());
+    const int all = block_reduce(c, sh, OpAdd());
     if (threadIdx.x == 0) cnt[b * NT + blockIdx.x] = all;
 }
 
@@ -164,7 +132,7 @@ __global__ __launch_bounds__(256) void sil_block_flags_kernel(const float* __res
     const float* r = x + (long long)b * N + s0;
     float m = 0.f;
     for (int i = threadIdx.x & 63; i < n; i += 64) m = fmaxf(m, r[i] * r[i]);
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_reduce(m, OpMax());
     if ((threadIdx.x & 63) == 0) flag[(long long)b * P.NB + k] = sqrtf(m) < P.thr ? 1 : 0;
 }
 
@@ -294,9 +262,7 @@ __global__ __launch_bounds__(1024) void sil_threshold_bounds_kernel(const float*
             last = max(last, t);
             first_neg = max(first_neg, L - 1 - t);
         }
-    int last_all, first_all;
-    block_scan(last, shi, last_all, OpMax());
-    block_scan(first_neg, shi, first_all, OpMax());
+    const int last_all = block_reduce(last, shi, OpMax()), first_all = block_reduce(first_neg, shi, OpMax());
     if (threadIdx.x != 0) return;
     int a = 0, cut = L;
     if (last_all >= 0) {
@@ -387,111 +353,6 @@ __global__ void sil_conv_mask_kernel(const double* __restrict__ P, int N, const 
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-unsigned blocks(long long n, int t) { return (unsigned)((n + t - 1) / t); }
-
-struct SilCall {
-    int B, N, method, mode, rate, bs, rb;
-    double threshold, min_silence, mvt;
-    std::vector<int> lens;
-    int w = 0;                  // mean-window taps
-    int NT = 0, NB = 0, cap = 1;
-    size_t off_info, off_mask, off_cnt, off_off, off_n, off_cut, off_d0, off_d1, off_flag, off_si, off_sj, off_tsum, off_toff,
-        off_P, off_tot, total;
-};
-
-int sil_check(tts_hip_engine* e, const char* what, const float* audio, int B, int N, const int32_t* lengths, int method, int mode,
-              int rate, double threshold, double min_silence, int block_size, int replace_by, double min_voice_time,
-              const float* out, const int32_t* out_lengths, SilCall& c) {
-    if (!audio || !out || !out_lengths || B <= 0 || N <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", what);
-    if (method < TTS_HIP_SILENCE_RMS || method > TTS_HIP_SILENCE_MEAN_WINDOW)
-        return set_err(e, TTS_HIP_EINVAL, "%s: method %d not 0 (rms), 1 (threshold) or 2 (mean-window)", what, method);
-    if (mode < 0 || mode > 3)
-        return set_err(e, TTS_HIP_EINVAL, "%s: mode %d not 0 (start_end), 1 (start), 2 (end) or 3 (remove)", what, mode);
-    if (mode == 3 && method != TTS_HIP_SILENCE_RMS)
-        return set_err(e, TTS_HIP_EINVAL, "%s: mode 3 (remove) belongs to the rms method (got method %d)", what, method);
-    if (rate <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: rate = %d <= 0", what, rate);
-    if (B > 65535 || N > (1 << 24) || (long long)B * N * 4 >= SIL_LIM)      // B is a grid dimension of every kernel
-        return set_err(e, TTS_HIP_EINVAL, "%s: B = %d x N = %d too large (B <= 65535, N <= 2^24, B * N * 4 < 2^31)", what, B, N);
-    c.lens.assign(B, N);
-    int min_len = N;
-    if (lengths)
-        for (int b = 0; b < B; ++b) {
-            if (lengths[b] < 1 || lengths[b] > N)
-                return set_err(e, TTS_HIP_EINVAL, "%s: lengths[%d] = %d outside [1, N = %d]", what, b, lengths[b], N);
-            c.lens[b] = lengths[b];
-            min_len = std::min(min_len, lengths[b]);
-        }
-    const bool rms = method == TTS_HIP_SILENCE_RMS, mw = method == TTS_HIP_SILENCE_MEAN_WINDOW;
-    if (!std::isfinite(threshold) || (!rms && threshold < 0))
-        return set_err(e, TTS_HIP_EINVAL, "%s: threshold = %g must be finite%s", what, threshold, rms ? "" : " and >= 0");
-    if (rms) {
-        if (block_size < 1) return set_err(e, TTS_HIP_EINVAL, "%s: block_size = %d < 1", what, block_size);
-        if (replace_by < 0) return set_err(e, TTS_HIP_EINVAL, "%s: replace_by = %d < 0", what, replace_by);
-        if (!std::isfinite(min_voice_time) || min_voice_time < 0)
-            return set_err(e, TTS_HIP_EINVAL, "%s: min_voice_time = %g must be finite and >= 0", what, min_voice_time);
-    }
-    if ((rms || mw) && (!std::isfinite(min_silence) || min_silence < 0))
-        return set_err(e, TTS_HIP_EINVAL, "%s: min_silence = %g must be finite and >= 0", what, min_silence);
-    if (mw) {
-        if (threshold <= 0) return set_err(e, TTS_HIP_EINVAL, "%s: threshold = %g <= 0 (mean-window)", what, threshold);
-        const double wd = min_silence * (double)rate;
-        if (wd < 1.0) return set_err(e, TTS_HIP_EINVAL, "%s: window w = (int)(min_silence * rate) = %d < 1", what, (int)wd);
-        if (std::floor(wd) > (double)min_len)           // also keeps (int)wd in range
-            return set_err(e, TTS_HIP_EINVAL, "%s: a row of L = %d samples is shorter than the window w = %.0f", what, min_len,
-                           std::floor(wd));
-        c.w = (int)wd;
-        if (min_len < c.w)
-            return set_err(e, TTS_HIP_EINVAL, "%s: a row of L = %d samples is shorter than the window w = %d", what, min_len, c.w);
-    }
-    const char *a0 = (const char*)audio, *o0 = (const char*)out;
-    const size_t bytes = (size_t)B * N * 4;
-    if (a0 < o0 + bytes && o0 < a0 + bytes) return set_err(e, TTS_HIP_EINVAL, "%s: out overlaps audio", what);
-
-    c.B = B;
-    c.N = N;
-    c.method = method;
-    c.mode = mode;
-    c.rate = rate;
-    c.bs = block_size;
-    c.rb = replace_by;
-    c.threshold = threshold;
-    c.min_silence = min_silence;
-    c.mvt = min_voice_time;
-    c.NT = (N + SIL_TILE - 1) / SIL_TILE;
-    if (rms) {
-        // silences per row: each holds >= q blocks (q * bt >= min_silence, taken one short against rounding) and a loud
-        // block parts it from the next
-        c.NB = (int)(((long long)N + c.bs - 1) / c.bs);
-        const double per = min_silence / ((double)c.bs / (double)rate);
-        const long long q = std::max<long long>(1, (per < 1e9 ? (long long)per : 1000000000ll) - 1);
-        c.cap = (int)(c.NB / (q + 1) + 1);
-    }
-    size_t o = 0;
-    auto take = [&](size_t bytes_) {
-        const size_t at = o;
-        o += al256(bytes_);
-        return at;
-    };
-    c.off_info = take((size_t)B * 4);
-    c.off_mask = take((size_t)B * N);
-    c.off_cnt = take((size_t)B * c.NT * 4);
-    c.off_off = take((size_t)B * c.NT * 4);
-    c.off_n = take((size_t)B * 4);
-    c.off_cut = take((size_t)B * 4);
-    c.off_d0 = take((size_t)B * c.cap * 4);
-    c.off_d1 = take((size_t)B * c.cap * 4);
-    c.off_flag = take(rms ? (size_t)B * c.NB : 0);
-    c.off_si = take(rms ? (size_t)B * c.cap * 4 : 0);
-    c.off_sj = take(rms ? (size_t)B * c.cap * 4 : 0);
-    c.off_tsum = take(mw ? (size_t)B * c.NT * 8 : 0);
-    c.off_toff = take(mw ? (size_t)B * c.NT * 8 : 0);
-    c.off_P = take(mw ? (size_t)B * ((size_t)N + 1) * 8 : 0);
-    c.off_tot = take(mw ? (size_t)B * 8 : 0);
-    c.total = o;
-    return TTS_HIP_OK;
-}
-
 // device pointers only; everything is enqueued on e->stream
 int sil_run(tts_hip_engine* e, const SilCall& c, const float* d_audio, float* d_out, int* d_out_len) {
     AudioProcDev& a = e->aproc;
@@ -504,8 +365,8 @@ int sil_run(tts_hip_engine* e, const SilCall& c, const float* d_audio, float* d_
     int* cnt = (int*)(base + c.off_cnt);
     int* off = (int*)(base + c.off_off);
     const Intervals iv{(int*)(base + c.off_d0), (int*)(base + c.off_d1), (int*)(base + c.off_n), (int*)(base + c.off_cut), c.cap};
-    a.info_h.assign(c.lens.begin(), c.lens.end());
-    HIPCHK(e, hipMemcpyAsync(lens, a.info_h.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+    e->audio_info_h.assign(c.lens.begin(), c.lens.end());
+    if (int rc = stage_row_info(e, lens)) return rc;
 
     if (c.method == TTS_HIP_SILENCE_RMS) {
         RmsParams P{};
@@ -568,9 +429,10 @@ int tts_hip_remove_silence_async(tts_hip_engine* e, const float* audio, int B, i
                                  double min_voice_time, float* out, int32_t* out_lengths, void* stream) {
     if (!e) return TTS_HIP_EINVAL;
     SilCall c;
-    if (int rc = sil_check(e, "remove_silence_async", audio, B, N, lengths, method, mode, rate, threshold, min_silence, block_size,
-                           replace_by, min_voice_time, out, out_lengths, c))
-        return rc;
+    char why[256];
+    if (int rc = sil_check("remove_silence_async", audio, B, N, lengths, method, mode, rate, threshold, min_silence, block_size,
+                           replace_by, min_voice_time, out, out_lengths, TTS_HIP_MEM_DEVICE, c, why, sizeof why))
+        return set_err(e, rc, "%s", why);
     HIPCHK(e, hipSetDevice(e->device));
     StreamScope scope(e, stream);
     return sil_run(e, c, audio, out, out_lengths);
@@ -581,29 +443,14 @@ int tts_hip_remove_silence(tts_hip_engine* e, const float* audio, int B, int N, 
                            double min_voice_time, float* out, int32_t* out_lengths, int mem) {
     if (!e) return TTS_HIP_EINVAL;
     SilCall c;
-    if (int rc = sil_check(e, "remove_silence", audio, B, N, lengths, method, mode, rate, threshold, min_silence, block_size,
-                           replace_by, min_voice_time, out, out_lengths, c))
-        return rc;
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "remove_silence: bad mem kind %d", mem);
+    char why[256];
+    if (int rc = sil_check("remove_silence", audio, B, N, lengths, method, mode, rate, threshold, min_silence, block_size,
+                           replace_by, min_voice_time, out, out_lengths, mem, c, why, sizeof why))
+        return set_err(e, rc, "%s", why);
     HIPCHK(e, hipSetDevice(e->device));
-    AudioProcDev& a = e->aproc;
-    const size_t n = (size_t)B * N;
-    const float* d_in = audio;
-    float* d_out = out;
-    int* d_len = out_lengths;
-    if (mem == TTS_HIP_MEM_HOST) {
-        HIPCHK(e, a.io.ensure(2 * al256(n * 4) + (size_t)B * 4));
-        float* io_in = a.io.f();
-        d_out = (float*)((char*)a.io.p + al256(n * 4));
-        d_len = (int*)((char*)a.io.p + 2 * al256(n * 4));
-        HIPCHK(e, hipMemcpyAsync(io_in, audio, n * 4, hipMemcpyHostToDevice, e->stream));
-        d_in = io_in;
-    }
-    if (int rc = sil_run(e, c, d_in, d_out, d_len)) return rc;
-    if (mem == TTS_HIP_MEM_HOST) {
-        HIPCHK(e, hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(e, hipMemcpyAsync(out_lengths, d_len, (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
-    }
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-    return TTS_HIP_OK;
+    AudioStage io(e, mem);
+    const int in = io.in(audio, (size_t)B * N * 4), res = io.out(out, (size_t)B * N * 4), len = io.out(out_lengths, (size_t)B * 4);
+    if (int rc = io.begin()) return rc;
+    if (int rc = sil_run(e, c, io.ptr<const float>(in), io.ptr<float>(res), io.ptr<int>(len))) return rc;
+    return io.finish();
 }

@@ -696,6 +696,54 @@ class HipEngine:
             out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'waveglow_probe_acts')
         return out
 
+    # ------------------------------------------------------------------ audio calls on rows
+    def _host_call(self, name, audio, B, N, extra_inputs, make_outputs, args):
+        """tts_hip_<name> on host arrays.  `audio` becomes a contiguous float32 [B, N]; each of `extra_inputs`, (array or None,
+        shape), a contiguous float32 array of that shape or None; `make_outputs(empty)` allocates the outputs with
+        empty(shape, dtype name) and returns them as a tuple; `args(extras, outs)` returns, with every array already turned
+        into its pointer, what the C function takes between (handle, audio, B, N) and the trailing mem kind.  -> the outputs."""
+        def host(x, shape):
+            if x is None:
+                return None
+            x = x.detach().cpu() if hasattr(x, 'detach') else x
+            return np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(shape))
+
+        a = host(audio, (B, N))
+        extras = [host(x, shape) for x, shape in extra_inputs]
+        outs = make_outputs(lambda shape, dtype: np.empty(shape, dtype=dtype))
+        self._check(getattr(self._lib, 'tts_hip_' + name)(self._h, self._ptr(a), B, N,
+                                                          *args([self._ptr(x) for x in extras], [self._ptr(o) for o in outs]),
+                                                          MEM_HOST), name)
+        return outs
+
+    def _rows_call(self, name, audio, B, N, extra_inputs, make_outputs, args, stream):
+        """tts_hip_<name> on numpy-like input (`_host_call`; numpy outputs) or on a CUDA tensor (CUDA outputs): there the same
+        conversions and allocations happen on the device, the call takes TTS_HIP_MEM_DEVICE, or, with `stream`
+        (torch.cuda.Stream, device tensors only), tts_hip_<name>_async is enqueued there and the call returns without waiting
+        (`_staged`).  Arguments as `_host_call`'s."""
+        if not _is_torch_cuda(audio):
+            if stream is not None:
+                raise ValueError('stream= needs device tensors')
+            return self._host_call(name, audio, B, N, extra_inputs, make_outputs, args)
+        torch = self._torch()
+        extra_inputs = [(torch.as_tensor(np.asarray(x, np.float32), device=audio.device)
+                         if x is not None and not _is_torch_cuda(x) else x, shape) for x, shape in extra_inputs]
+        self._check_device(audio, *(x for x, _ in extra_inputs))
+
+        def prepared():
+            a_ = audio.to(torch.float32).reshape(B, N).contiguous()
+            extras = [x.to(torch.float32).reshape(shape).contiguous() if x is not None else None for x, shape in extra_inputs]
+            outs = make_outputs(lambda shape, dtype: torch.empty(shape, dtype=getattr(torch, dtype), device=a_.device))
+            return (a_, *extras, *outs)
+
+        tensors, sp = self._staged(stream, prepared, audio)
+        extras, outs = tensors[1:1 + len(extra_inputs)], tensors[1 + len(extra_inputs):]
+        fn, last = (name, MEM_DEVICE) if stream is None else (name + '_async', sp)
+        self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(tensors[0]), B, N,
+                                                        *args([self._ptr(x) for x in extras], [self._ptr(o) for o in outs]),
+                                                        last), fn)
+        return outs
+
     # ------------------------------------------------------------------ mel-STFT
     def mel_stft(self, audio, stream=None):
         """audio [N] or [B, N] -> mel [B, N // 256 + 1, 80] (the reference's TacotronSTFT()(audio)).  `stream` (torch.cuda.Stream,
@@ -703,34 +751,18 @@ class HipEngine:
         if _is_torch_cuda(audio):
             torch = self._torch()
             self._check_device(audio)
-
-            def prepared():
-                a_ = audio.to(torch.float32)
-                if a_.dim() == 1:
-                    a_ = a_[None]
-                if a_.shape[1] < 1024:
-                    a_ = torch.nn.functional.pad(a_, (0, 1024 - a_.shape[1]))
-                a_ = a_.contiguous()
-                return a_, torch.empty((int(a_.shape[0]), int(a_.shape[1]) // 256 + 1, 80), dtype=torch.float32, device=a_.device)
-
-            (a, out), sp = self._staged(stream, prepared, audio)
-            B, N = int(a.shape[0]), int(a.shape[1])
-            fn, last = ('mel_stft', MEM_DEVICE) if stream is None else ('mel_stft_async', sp)
-            self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(a), B, N, self._ptr(out), last), fn)
-            return out
-        if stream is not None:
-            raise ValueError('stream= needs device tensors')
-        a = np.asarray(audio, dtype=np.float32)
-        if a.ndim == 1:
-            a = a[None]
-        if a.shape[1] < 1024:                     # MelSTFT.__call__ pads short audio (utils/audio/stft.py:113-115)
-            a = np.pad(a, [(0, 0), (0, 1024 - a.shape[1])])
-        a = np.ascontiguousarray(a)
-        B, N = a.shape
-        out = np.empty((B, N // 256 + 1, 80), dtype=np.float32)
-        self._check(self._lib.tts_hip_mel_stft(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N,
-                                               out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'mel_stft')
-        return out
+            a = audio if audio.dim() > 1 else audio[None]
+            if a.shape[1] < 1024:
+                a = torch.nn.functional.pad(a, (0, 1024 - a.shape[1]))
+        else:
+            a = np.asarray(audio, dtype=np.float32)
+            if a.ndim == 1:
+                a = a[None]
+            if a.shape[1] < 1024:                     # MelSTFT.__call__ pads short audio (utils/audio/stft.py:113-115)
+                a = np.pad(a, [(0, 0), (0, 1024 - a.shape[1])])
+        B, N = int(a.shape[0]), int(a.shape[1])
+        return self._rows_call('mel_stft', a, B, N, [], lambda empty: (empty((B, N // 256 + 1, 80), 'float32'),),
+                               lambda extras, outs: (outs[0],), stream)[0]
 
     _STFT_STAGES = {'padded': 0, 'spectrum': 1, 'magnitude': 2, 'mel_linear': 3}
 
@@ -744,16 +776,13 @@ class HipEngine:
         a = np.asarray(audio, dtype=np.float32)
         if a.ndim == 1:
             a = a[None]
-        a = np.ascontiguousarray(a)
         if a.ndim != 2:
             raise ValueError(f'audio must be [N] or [B, N], got {a.shape}')
         B, N = a.shape
         F = N // 256 + 1
         shape = {'padded': (B, N + 1024), 'spectrum': (B, F, 1026), 'magnitude': (B, F, 513), 'mel_linear': (B, F, 80)}[what]
-        out = np.empty(shape, dtype=np.float32)
-        self._check(self._lib.tts_hip_mel_stft_probe(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, self._STFT_STAGES[what],
-                                                     out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'mel_stft_probe')
-        return out
+        return self._host_call('mel_stft_probe', a, B, N, [], lambda empty: (empty(shape, 'float32'),),
+                               lambda extras, outs: (self._STFT_STAGES[what], outs[0]))[0]
 
     # ------------------------------------------------------------------ waveform clean-up (csrc/audio_proc.hip)
     _TRIM_MODES = {'start_end': 0, 'start': 1, 'end': 2}
@@ -804,37 +833,10 @@ class HipEngine:
             noise_len = self._samples(noise_length, rate, 'reduce_noise: noise_length')
         if noise_len < 1:
             raise ValueError(f'reduce_noise: the noise clip must hold at least one sample (got {noise_len})')
-        lens_p = lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None
-        one_row = len(audio.shape) == 1
-        if _is_torch_cuda(audio):
-            torch = self._torch()
-            if noise is not None and not _is_torch_cuda(noise):
-                noise = torch.as_tensor(np.asarray(noise, np.float32), device=audio.device)
-            self._check_device(audio, noise)
-
-            def prepared():
-                a_ = audio.to(torch.float32).reshape(B, N).contiguous()
-                n_ = noise.to(torch.float32).reshape(B, noise_len).contiguous() if noise is not None else None
-                return a_, n_, torch.empty((B, N), dtype=torch.float32, device=a_.device)
-
-            (a, n, out), sp = self._staged(stream, prepared, audio)
-            fn, last = ('reduce_noise', MEM_DEVICE) if stream is None else ('reduce_noise_async', sp)
-            self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(a), B, N, lens_p, self._ptr(n), noise_len,
-                                                            int(bool(renormalize)), self._ptr(out), last), fn)
-            return out[0] if one_row else out
-        if stream is not None:
-            raise ValueError('stream= needs device tensors')
-        a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
-        n = None
-        if noise is not None:
-            n = np.ascontiguousarray(np.asarray(noise.detach().cpu() if hasattr(noise, 'detach') else noise,
-                                                dtype=np.float32).reshape(B, noise_len))
-        out = np.empty((B, N), dtype=np.float32)
-        self._check(self._lib.tts_hip_reduce_noise(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens_p,
-                                                   n.ctypes.data_as(ctypes.c_void_p) if n is not None else None, noise_len,
-                                                   int(bool(renormalize)), out.ctypes.data_as(ctypes.c_void_p), MEM_HOST),
-                    'reduce_noise')
-        return out[0] if one_row else out
+        out, = self._rows_call('reduce_noise', audio, B, N, [(noise, (B, noise_len))], lambda empty: (empty((B, N), 'float32'),),
+                               lambda extras, outs: (self._ptr(lens), extras[0], noise_len, int(bool(renormalize)), outs[0]),
+                               stream)
+        return out[0] if len(audio.shape) == 1 else out
 
     _RN_STAGES = {'padded': 0, 'noise_padded': 1, 'spectrum': 2, 'noise_spectrum': 3, 'power_max': 4, 'threshold': 5, 'mask': 6,
                   'gated': 7, 'frames': 8}
@@ -850,10 +852,8 @@ class HipEngine:
             raise ValueError(f'what must be one of {tuple(self._RN_STAGES)}, got {what!r}')
         audio = np.asarray(audio, dtype=np.float32)
         B, N, lens = self._audio_rows(audio, lengths, 'reduce_noise_probe')
-        n = None
         if noise is not None:
-            n = np.ascontiguousarray(np.asarray(noise, dtype=np.float32).reshape(B, -1))
-            noise_len = int(n.shape[1])
+            noise_len = int(np.asarray(noise).reshape(B, -1).shape[1])
         else:
             noise_len = self._samples(noise_length, rate, 'reduce_noise_probe: noise_length')
         if noise_len < 1:
@@ -862,13 +862,8 @@ class HipEngine:
         shape = {'padded': (B, Fr * 512), 'noise_padded': (B, Frn * 512), 'spectrum': (B, Fr, 2050),
                  'noise_spectrum': (B, Frn, 2050), 'power_max': (2, B), 'threshold': (B, 1025), 'mask': (B, Fr, 1025),
                  'gated': (B, Fr, 2050), 'frames': (B, Fr, 2048)}[what]
-        a = np.ascontiguousarray(audio.reshape(B, N))
-        out = np.empty(shape, dtype=np.float32)
-        self._check(self._lib.tts_hip_reduce_noise_probe(
-            self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None,
-            n.ctypes.data_as(ctypes.c_void_p) if n is not None else None, noise_len, self._RN_STAGES[what],
-            out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'reduce_noise_probe')
-        return out
+        return self._host_call('reduce_noise_probe', audio, B, N, [(noise, (B, noise_len))], lambda empty: (empty(shape, 'float32'),),
+                               lambda extras, outs: (self._ptr(lens), extras[0], noise_len, self._RN_STAGES[what], outs[0]))[0]
 
     def trim_silence_probe(self, audio, rate=None, lengths=None, window_length=0.2):
         """Test hook (tts_hip_trim_silence_probe): the convolution launches of `trim_silence` on audio [N] or [B, N] (host
@@ -880,11 +875,8 @@ class HipEngine:
         if wl < 2:
             raise ValueError(f'trim_silence_probe: window_length must be >= 2 samples (got {wl})')
         W = 2 * (wl // 2)
-        a = np.ascontiguousarray(audio.reshape(B, N))
-        conv = np.empty((B, max(N, W) + 1), dtype=np.float64)
-        self._check(self._lib.tts_hip_trim_silence_probe(
-            self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None,
-            wl, conv.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'trim_silence_probe')
+        conv, = self._host_call('trim_silence_probe', audio, B, N, [], lambda empty: (empty((B, max(N, W) + 1), 'float64'),),
+                                lambda extras, outs: (self._ptr(lens), wl, outs[0]))
         for b in range(B):
             conv[b, abs((N if lens is None else int(lens[b])) - W) + 1:] = np.nan
         return conv
@@ -914,29 +906,16 @@ class HipEngine:
         if B * max(N, M) * 4 >= 1 << 31:
             raise ValueError(f'resample: B = {B} x N = {N} (M {M}) too large for 31-bit offsets')
         one_row = len(audio.shape) == 1
-        lens_p = lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None
-        if _is_torch_cuda(audio):
-            torch = self._torch()
-            self._check_device(audio)
-            if rate == target_rate and lens is None:
-                return audio.to(torch.float32)
-            def prepared():
-                a_ = audio.to(torch.float32).reshape(B, N).contiguous()
-                return a_, torch.empty((B, M), dtype=torch.float32, device=a_.device)
-
-            (a, out), sp = self._staged(stream, prepared, audio)
-            fn, last = ('resample', MEM_DEVICE) if stream is None else ('resample_async', sp)
-            self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(a), B, N, lens_p, rate, target_rate,
-                                                            self._ptr(out), M, last), fn)
-            return out[0] if one_row else out
-        if stream is not None:
-            raise ValueError('stream= needs device tensors')
-        a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
         if rate == target_rate and lens is None:
+            if _is_torch_cuda(audio):
+                self._check_device(audio)
+                return audio.to(self._torch().float32)
+            if stream is not None:
+                raise ValueError('stream= needs device tensors')
+            a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
             return a[0] if one_row else a
-        out = np.empty((B, M), dtype=np.float32)
-        self._check(self._lib.tts_hip_resample(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens_p, rate, target_rate,
-                                               out.ctypes.data_as(ctypes.c_void_p), M, MEM_HOST), 'resample')
+        out, = self._rows_call('resample', audio, B, N, [], lambda empty: (empty((B, M), 'float32'),),
+                               lambda extras, outs: (self._ptr(lens), rate, target_rate, outs[0], M), stream)
         return out[0] if one_row else out
 
     def trim_silence(self, audio, rate=None, lengths=None, threshold=0.1, window_length=0.2, add_start=0, add_end=1.5,
@@ -953,8 +932,7 @@ class HipEngine:
             raise ValueError(f'trim_silence: window_length must be >= 2 samples (got {wl})')
         if not (np.isfinite(threshold) and np.isfinite(add_start) and np.isfinite(add_end)) or add_start < 0 or add_end < 0:
             raise ValueError('trim_silence: threshold and margins must be finite, margins >= 0')
-        lens_p = lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None
-        start, end = np.empty(B, np.int32), np.empty(B, np.int32)
+        lens_p = self._ptr(lens)
         args = (wl, float(threshold), float(add_start), float(add_end), self._TRIM_MODES[mode])
         if _is_torch_cuda(audio):
             torch = self._torch()
@@ -965,13 +943,10 @@ class HipEngine:
             self._check(self._lib.tts_hip_trim_silence(self._h, ctypes.c_void_p(a.data_ptr()), B, N, lens_p, *args,
                                                        ctypes.c_void_p(st.data_ptr()), ctypes.c_void_p(st[1].data_ptr()),
                                                        MEM_DEVICE), 'trim_silence')
-            st = st.cpu().numpy()
-            start[:], end[:] = st[0], st[1]
+            start, end = st.cpu().numpy()
         else:
-            a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
-            self._check(self._lib.tts_hip_trim_silence(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens_p, *args,
-                                                       start.ctypes.data_as(ctypes.c_void_p),
-                                                       end.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'trim_silence')
+            start, end = self._host_call('trim_silence', audio, B, N, [], lambda empty: (empty(B, 'int32'), empty(B, 'int32')),
+                                         lambda extras, outs: (lens_p, *args, outs[0], outs[1]))
         if len(audio.shape) == 1:
             return int(start[0]), int(end[0])
         return start, end
@@ -1042,30 +1017,12 @@ class HipEngine:
             raise ValueError(f'remove_silence: B = {B} x N = {N} too large (B <= 65535, N <= 2^24, B * N * 4 < 2^31)')
         args = (self._SILENCE_METHODS[method], self._SILENCE_MODES[mode], rate, float(threshold), float(min_silence), bs, rb,
                 float(min_voice_time))
-        lens_p = lens.ctypes.data_as(ctypes.c_void_p) if lens is not None else None
-        one_row = len(audio.shape) == 1
-        if _is_torch_cuda(audio):
-            torch = self._torch()
-            self._check_device(audio)
-
-            def prepared():
-                a_ = audio.to(torch.float32).reshape(B, N).contiguous()
-                return (a_, torch.empty((B, N), dtype=torch.float32, device=a_.device),
-                        torch.empty((B,), dtype=torch.int32, device=a_.device))
-
-            (a, out, out_len), sp = self._staged(stream, prepared, audio)
-            fn, last = ('remove_silence', MEM_DEVICE) if stream is None else ('remove_silence_async', sp)
-            self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(a), B, N, lens_p, *args, self._ptr(out),
-                                                            self._ptr(out_len), last), fn)
-            return (out[0], out_len[0]) if one_row else (out, out_len)
-        if stream is not None:
-            raise ValueError('stream= needs device tensors')
-        a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
-        out, out_len = np.empty((B, N), dtype=np.float32), np.empty(B, np.int32)
-        self._check(self._lib.tts_hip_remove_silence(self._h, a.ctypes.data_as(ctypes.c_void_p), B, N, lens_p, *args,
-                                                     out.ctypes.data_as(ctypes.c_void_p),
-                                                     out_len.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'remove_silence')
-        return out[0, :int(out_len[0])].copy() if one_row else (out, out_len)
+        out, out_len = self._rows_call('remove_silence', audio, B, N, [],
+                                       lambda empty: (empty((B, N), 'float32'), empty((B,), 'int32')),
+                                       lambda extras, outs: (self._ptr(lens), *args, outs[0], outs[1]), stream)
+        if len(audio.shape) != 1:
+            return out, out_len
+        return (out[0], out_len[0]) if _is_torch_cuda(audio) else out[0, :int(out_len[0])].copy()
 
     # ------------------------------------------------------------------ measurement hooks
     def kernel_timing(self, enable: bool) -> None:
