@@ -329,6 +329,68 @@ int tts_hip_mel_stft(tts_hip_engine* e, const float* audio, int B, int N, float*
  *   log(max(., 1e-5)).  Any other `what` is TTS_HIP_EINVAL and launches nothing.                                        */
 int tts_hip_mel_stft_probe(tts_hip_engine* e, const float* audio, int B, int N, int what, float* out, int mem);
 
+/* ---- mel plans: any TacotronSTFT configuration and WhisperSTFT (utils/audio/stft.py:101-124, 242-274, 306-314, 350-364)
+ * A plan holds the windowed-DFT basis and the Slaney filterbank of one configuration on the device.  It belongs to the
+ * engine handle it was created on, needs no weights and no tts_hip_finalize, and is freed by tts_hip_mel_fn_free or with
+ * the handle.  `window` is a HOST array of win_length doubles (get_window(name, win_length, fftbins=periodic)), NULL = the
+ * periodic Hann window; it is centred in filter_length (pad_center: (filter_length - win_length) // 2 zeros before it).
+ * tts_hip_mel_stft[_async, _probe] are calls on the handle's default plan: kind Tacotron, 22 050 Hz, 1024 / 256 / 1024,
+ * 80 mels, 0 - 8000 Hz, no pre-emphasis, no normalisation.
+ *
+ * run: audio [B, N] -> mel [B, Fmax, n_mel_channels], Fmax = tts_hip_mel_fn_frames(fn, N).  Row b holds lengths[b]
+ * (1 <= lengths[b] <= N) samples; `lengths` is a HOST array in every mode, NULL = N for every row.  Row b of the result is
+ * what a one-row call on audio[b, :lengths[b]] returns, frames at and beyond tts_hip_mel_fn_frames(fn, lengths[b]) are 0,
+ * and nothing at or beyond lengths[b] is read (it may hold NaN).  Per row of L samples:
+ *   1. L' = max(L, win_length), zeros on the right;
+ *   2. pre_emph > 0: y[0] = x[0], y[i] = x[i] - (float)pre_emph * x[i-1] (one fp32 product, one fp32 difference) on the L'
+ *      samples, so the first padded zero becomes -pre_emph * x[L-1] as in the reference;
+ *   3. numpy 'reflect' padding of filter_length // 2 on each side; F = (L' + 2 * (filter_length // 2) - filter_length)
+ *      // hop_length + 1 frames;
+ *   4. the windowed DFT as a GEMM against cos / -sin rows (phase reduced exactly, rounded to fp32, times the float64 window,
+ *      rounded once), bins 0 .. filter_length // 2;
+ *   5. magnitude sqrt(re^2 + im^2), times the Slaney filterbank of (sampling_rate, filter_length, n_mel_channels, mel_fmin,
+ *      mel_fmax) built in double (librosa.filters.mel defaults);
+ *   6. kind TACOTRON: log(max(., 1e-5)) in double, rounded once; then normalize_mode: PER_FEATURE (x - mean) / std per mel
+ *      channel over the row's own F frames, ALL_FEATURE the same over the row's own F x n_mel cells -- the reference's
+ *      all_feature reduces over the batch too; here a row's result never depends on its neighbours -- population std, 0
+ *      where std is 0, sums / subtraction / division in double and rounded once;
+ *   7. kind WHISPER: the row's last frame is dropped (F - 1 frames come out); log10(max(., 1e-10)) in double, rounded once;
+ *      m = max(x, rowmax - 8.0f) with rowmax the fp32 maximum over the row's own cells; (m + 4.0f) / 4.0f in fp32;
+ *      normalize_mode has no effect.
+ * Refusals (TTS_HIP_EINVAL, first match wins, nothing copied or launched; csrc/audio_call.h) --
+ *   create: NULL cfg / out; kind; normalize_mode; sampling_rate < 1; filter_length outside [2, 4096]; win_length outside
+ *     [1, filter_length]; hop_length < 1; n_mel_channels outside [1, 1024]; not 0 <= mel_fmin < mel_fmax <= sampling_rate / 2;
+ *     pre_emph negative or not finite; a window value that is not finite;
+ *   run / probe: NULL fn / audio / mel, B < 1, N < 1; a lengths[b] outside [1, N]; a row whose L' is not above
+ *     filter_length // 2 (reflect needs it); a Whisper row with F < 2; B > 65535 or one of the call's buffers at 2^31 - 65536
+ *     bytes or more -- the padded rows [B][max(N, win_length) + 2 * (filter_length // 2) (+ up to 6)] fp32, the gathered
+ *     frames [B * F][filter_length up to 32] (hop_length % 4 != 0 only), the spectrum [B * F][2 * bins up to 32], the
+ *     magnitudes [B * F][bins up to 32], the linear mel [B * F][n_mel], audio, with F the frames of N; a bad mem kind; the
+ *     probe's `what` outside 0 .. 4.
+ * All plans of a handle share one workspace: an _async call must be ordered before the next mel call on the handle.
+ * probe (test hook; runs the code of run, not a copy, up to a stage; F = the DFT frames of N, Whisper's last one included):
+ *   what 0 `padded` [B, max(N, win_length) + 2 * (filter_length // 2)] after steps 1 - 3; 1 `spectrum` [B, F, 2 * bins]
+ *   (real parts, then imaginary parts); 2 `magnitude` [B, F, bins]; 3 `mel_linear` [B, F, n_mel]; 4 `mel_log` [B, Fmax,
+ *   n_mel] after the logarithm, before the normalisation / clamp (frames beyond a row's own already 0).  In stages 1 - 3 the
+ *   frames beyond a row's own hold what the zero-padded row gives there.                                                  */
+typedef struct tts_hip_mel_fn tts_hip_mel_fn;
+enum { TTS_HIP_MEL_TACOTRON = 0, TTS_HIP_MEL_WHISPER = 1 };
+enum { TTS_HIP_MEL_NORM_NONE = 0, TTS_HIP_MEL_NORM_PER_FEATURE = 1, TTS_HIP_MEL_NORM_ALL_FEATURE = 2 };
+typedef struct {
+    int kind, sampling_rate, n_mel_channels, filter_length, hop_length, win_length, normalize_mode;
+    double mel_fmin, mel_fmax, pre_emph;
+} tts_hip_mel_config;
+int tts_hip_mel_fn_create(tts_hip_engine* e, const tts_hip_mel_config* cfg, const double* window, tts_hip_mel_fn** out);
+int tts_hip_mel_fn_free(tts_hip_engine* e, tts_hip_mel_fn* fn);
+/* frames a row of n_samples yields (the default plan: max(n, 1024) / 256 + 1); < 0 if run would refuse the row */
+int tts_hip_mel_fn_frames(const tts_hip_mel_fn* fn, int n_samples);
+int tts_hip_mel_fn_run(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                       float* mel, int mem);
+int tts_hip_mel_fn_run_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths,
+                             const tts_hip_mel_fn* fn, float* mel, void* stream);
+int tts_hip_mel_fn_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                         int what, float* out, int mem);
+
 /* ---- waveform clean-up (csrc/audio_proc.hip; DFT bases built on first use, no weights needed)
  * reduce_noise: utils/audio/noisereducev1.py:175-290 with the defaults utils/audio/audio_processing.py:65-83 uses.
  *   audio [B, N] -> out [B, N]; row b has lengths[b] (1 <= lengths[b] <= N) samples, lengths NULL = N for every row, and

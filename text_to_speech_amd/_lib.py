@@ -23,6 +23,13 @@ class HipLibraryError(RuntimeError):
 
 
 # name -> (restype, argtypes); must list exactly the functions include/tts_hip.h declares (checked by the CPU tests)
+class MelConfigC(ctypes.Structure):
+    """tts_hip_mel_config (include/tts_hip.h)."""
+    _fields_ = [('kind', c_int), ('sampling_rate', c_int), ('n_mel_channels', c_int), ('filter_length', c_int),
+                ('hop_length', c_int), ('win_length', c_int), ('normalize_mode', c_int), ('mel_fmin', c_double),
+                ('mel_fmax', c_double), ('pre_emph', c_double)]
+
+
 SIGNATURES = {
     'tts_hip_abi_version': (c_int, []),
     'tts_hip_create': (c_int, [c_int, POINTER(c_void_p)]),
@@ -94,6 +101,12 @@ SIGNATURES = {
     'tts_hip_remove_silence_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double,
                                              c_double, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     'tts_hip_resample': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
+    'tts_hip_mel_fn_create': (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
+    'tts_hip_mel_fn_free': (c_int, [c_void_p, c_void_p]),
+    'tts_hip_mel_fn_frames': (c_int, [c_void_p, c_int]),
+    'tts_hip_mel_fn_run': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]),
+    'tts_hip_mel_fn_run_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tts_hip_mel_fn_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int]),
     'tts_hip_resample_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
 }
 

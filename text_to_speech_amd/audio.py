@@ -134,12 +134,20 @@ def trim_silence(audio, *, engine, rate=None, method='window', **kwargs):
 MEL_RATE = 22050                    # TacotronSTFT's sampling rate (engine.mel_stft's filterbank)
 
 
-def load_mel(data, rate=MEL_RATE, *, engine, resample=False, **kwargs):
-    """audio_io.py:129-144 with TacotronSTFT (engine.mel_stft): load_audio(data, stft_fn.rate, ...) -> mel [T, 80].  Like the
-    reference, the audio is loaded at the STFT's rate: a file at another rate raises unless resample=True, which resamples
-    it on `engine` first."""
+def load_mel(data, rate=MEL_RATE, *, engine, stft_fn=None, resample=False, **kwargs):
+    """audio_io.py:129-144: load_audio(data, stft_fn.rate, ...) -> mel [T, n_mel].  Without `stft_fn` the analysis is the
+    default TacotronSTFT (engine.mel_stft, 22 050 Hz, 80 mels); with one (text_to_speech_amd.stft: any TacotronSTFT
+    configuration or WhisperSTFT) the audio is loaded at `stft_fn.rate` and the mel comes from it on `engine`, and an array
+    [..., stft_fn.n_mel_channels] is taken for a mel and passed through, as the reference does.  Like the reference, the
+    audio is loaded at the STFT's rate: a file at another rate raises unless resample=True, which resamples it on `engine`
+    first."""
     if isinstance(data, dict) and 'mel' in data:
         return data['mel']
+    if stft_fn is not None:
+        if hasattr(data, 'shape') and len(data.shape) >= 2 and data.shape[-1] == stft_fn.n_mel_channels:
+            return data
+        audio = load_audio(data, stft_fn.rate, engine=engine, resample=resample, **kwargs)
+        return stft_fn.bind(engine)(np.asarray(audio, np.float32))[0]
     if rate != MEL_RATE:
         raise ValueError(f'load_mel: the mel-STFT runs at {MEL_RATE} Hz, got rate={rate}')
     audio = load_audio(data, rate, engine=engine, resample=resample, **kwargs)

@@ -285,3 +285,117 @@ inline int sil_check(const char* who, const float* audio, int B, int N, const in
     c.total = ws.o;
     return TTS_HIP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- mel plans (mel_stft.hip)
+// A plan (tts_hip_mel_fn) is a checked tts_hip_mel_config plus the operand widths its tables are padded to; a call derives
+// its frame counts and its one workspace from the plan, B, N and lengths.
+struct MelPlan {
+    int kind, norm, sr, nmel, fl, hop, wl;
+    double fmin, fmax, pre;
+    int half, cut, lpad;        // filter_length // 2, the bins filter_length // 2 + 1, (filter_length - win_length) // 2
+    int K4, Kpad;               // filter_length rounded up to 4 (what a strided frame reads) and to 32 (the K of the tables)
+    int NB, MAGK;               // 2 * cut and cut rounded up to 32: DFT rows / magnitude columns
+    bool gather;                // hop % 4 != 0: frames are materialised [B * Fr][Kpad] instead of read as strided rows
+};
+
+inline int up_to(int v, int m) { return (v + m - 1) / m * m; }
+
+// create -- order: pointers, kind / normalize_mode, sampling_rate, filter_length, win_length, hop_length, n_mel_channels,
+// mel_fmin / mel_fmax, pre_emph, window values; fills `p`
+inline int mel_cfg_check(const char* who, const tts_hip_mel_config* c, const double* window, bool have_out, MelPlan* p, char* msg,
+                         size_t n) {
+    if (!c || !have_out) return audio_refuse(msg, n, who, "bad argument");
+    if (c->kind != TTS_HIP_MEL_TACOTRON && c->kind != TTS_HIP_MEL_WHISPER)
+        return audio_refuse(msg, n, who, "kind %d not 0 (tacotron) or 1 (whisper)", c->kind);
+    if (c->normalize_mode < TTS_HIP_MEL_NORM_NONE || c->normalize_mode > TTS_HIP_MEL_NORM_ALL_FEATURE)
+        return audio_refuse(msg, n, who, "normalize_mode %d not 0 (none), 1 (per_feature) or 2 (all_feature)", c->normalize_mode);
+    if (c->sampling_rate < 1) return audio_refuse(msg, n, who, "sampling_rate = %d < 1", c->sampling_rate);
+    if (c->filter_length < 2 || c->filter_length > 4096)
+        return audio_refuse(msg, n, who, "filter_length = %d outside [2, 4096]", c->filter_length);
+    if (c->win_length < 1 || c->win_length > c->filter_length)
+        return audio_refuse(msg, n, who, "win_length = %d outside [1, filter_length = %d]", c->win_length, c->filter_length);
+    if (c->hop_length < 1) return audio_refuse(msg, n, who, "hop_length = %d < 1", c->hop_length);
+    if (c->n_mel_channels < 1 || c->n_mel_channels > 1024)
+        return audio_refuse(msg, n, who, "n_mel_channels = %d outside [1, 1024]", c->n_mel_channels);
+    if (!(c->mel_fmin >= 0 && c->mel_fmin < c->mel_fmax && c->mel_fmax <= c->sampling_rate / 2.0))
+        return audio_refuse(msg, n, who, "need 0 <= mel_fmin = %g < mel_fmax = %g <= sampling_rate / 2 = %g", c->mel_fmin,
+                            c->mel_fmax, c->sampling_rate / 2.0);
+    if (!std::isfinite(c->pre_emph) || c->pre_emph < 0)
+        return audio_refuse(msg, n, who, "pre_emph = %g must be finite and >= 0", c->pre_emph);
+    if (window)
+        for (int i = 0; i < c->win_length; ++i)
+            if (!std::isfinite(window[i])) return audio_refuse(msg, n, who, "window[%d] is not finite", i);
+    p->kind = c->kind, p->norm = c->normalize_mode, p->sr = c->sampling_rate, p->nmel = c->n_mel_channels;
+    p->fl = c->filter_length, p->hop = c->hop_length, p->wl = c->win_length;
+    p->fmin = c->mel_fmin, p->fmax = c->mel_fmax, p->pre = c->pre_emph;
+    p->half = p->fl / 2, p->cut = p->fl / 2 + 1, p->lpad = (p->fl - p->wl) / 2;
+    p->K4 = up_to(p->fl, 4), p->Kpad = up_to(p->fl, 32);
+    p->NB = up_to(2 * p->cut, 32), p->MAGK = up_to(p->cut, 32);
+    p->gather = p->hop % 4 != 0;
+    return TTS_HIP_OK;
+}
+
+// frames the DFT gives a row of n samples (before Whisper drops the last): L' = max(n, win_length) zero-padded samples,
+// reflect-padded by filter_length // 2 on each side.  0 when reflect cannot pad the row (L' <= filter_length // 2) or n < 1
+inline int mel_dft_frames(const MelPlan& p, int n) {
+    if (n < 1) return 0;
+    const long long lp = std::max(n, p.wl);
+    if (lp <= p.half) return 0;
+    return (int)((lp + 2 * p.half - p.fl) / p.hop + 1);
+}
+
+// frames of the result; < 0 if the row is refused
+inline int mel_out_frames(const MelPlan& p, int n) {
+    const int f = mel_dft_frames(p, n);
+    if (f < 1) return -1;
+    if (p.kind == TTS_HIP_MEL_WHISPER) return f < 2 ? -1 : f - 1;
+    return f;
+}
+
+// One workspace per call.  Named buffers (each below kAudioLim bytes): `padded` [B][NP] the zero-padded, pre-emphasised,
+// reflect-padded rows, PW = max(N, win_length) + 2 * (filter_length // 2) of them logical and NP = PW + K4 - filter_length
+// rounded up to 4 stored; `gathered` [B * Fr][Kpad] (gather plans only); `spectrum` [B * Fr][NB]; `magnitude`
+// [B * Fr][MAGK]; `linear` [B * Fr][n_mel] (Whisper only: the result has one frame less per row); and the caller's audio
+// [B][N] and mel [B][Fout][n_mel]
+struct MelGeom {
+    int Fr, Fout, PW, NP;
+    std::vector<int> lens, fout;            // per row: samples, frames of the result
+    size_t off_info, off_rowmax, off_padded, off_gathered, off_spectrum, off_magnitude, off_linear, total;
+};
+
+// run -- order: pointers / B / N, lengths[b], a row reflect cannot pad, a Whisper row of one frame, the 31-bit limits, mem
+// kind; fills `g`
+inline int mel_call_check(const char* who, const MelPlan* p, const float* audio, int B, int N, const int32_t* lengths,
+                          const float* out, int mem, MelGeom* g, char* msg, size_t n) {
+    if (!p || !audio || !out || B < 1 || N < 1) return audio_refuse(msg, n, who, "bad argument");
+    int min_len;
+    if (int rc = audio_rows_check(who, B, N, lengths, g->lens, &min_len, msg, n)) return rc;
+    g->fout.assign(B, 0);
+    for (int b = 0; b < B; ++b)
+        if (mel_dft_frames(*p, g->lens[b]) < 1)
+            return audio_refuse(msg, n, who, "row %d: max(L = %d, win_length = %d) samples are not more than filter_length // 2 = %d",
+                                b, g->lens[b], p->wl, p->half);
+    for (int b = 0; b < B; ++b) {
+        g->fout[b] = mel_out_frames(*p, g->lens[b]);
+        if (g->fout[b] < 1) return audio_refuse(msg, n, who, "row %d: L = %d samples give one frame, Whisper drops the last", b, g->lens[b]);
+    }
+    g->Fr = mel_dft_frames(*p, N);
+    g->Fout = mel_out_frames(*p, N);
+    const long long PW = (long long)std::max(N, p->wl) + 2 * p->half, NP = (PW + p->K4 - p->fl + 3) / 4 * 4;
+    const long long rows = (long long)B * g->Fr;
+    const long long biggest = std::max({(long long)B * NP * 4 + 256, p->gather ? rows * p->Kpad * 4 : 0, rows * p->NB * 4,
+                                        rows * p->MAGK * 4, rows * p->nmel * 4, (long long)B * N * 4});
+    if (biggest >= kAudioLim || B > 65535)
+        return audio_refuse(msg, n, who, "B = %d x N = %d too large for 31-bit offsets (B <= 65535)", B, N);
+    g->PW = (int)PW, g->NP = (int)NP;
+    Carve c;
+    g->off_info = c.take((size_t)2 * B * 4);
+    g->off_rowmax = c.take((size_t)B * 4);
+    g->off_padded = c.take((size_t)B * NP * 4 + 256);
+    g->off_gathered = c.take(p->gather ? (size_t)rows * p->Kpad * 4 : 0);
+    g->off_spectrum = c.take((size_t)rows * p->NB * 4);
+    g->off_magnitude = c.take((size_t)rows * p->MAGK * 4);
+    g->off_linear = c.take(p->kind == TTS_HIP_MEL_WHISPER ? (size_t)rows * p->nmel * 4 : 0);
+    g->total = c.o;
+    return audio_mem_check(who, mem, msg, n);
+}

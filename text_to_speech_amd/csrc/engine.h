@@ -196,12 +196,18 @@ struct Tacotron2Dev {
 // resample.hip, silence.hip).  These structs hold weights, tables and per-call workspaces only: what a TTS_HIP_MEM_HOST
 // caller passes in and gets back is staged through the engine's one `audio_io` (AudioStage below), and the per-row int
 // table of a call through `audio_info_h` (stage_row_info).
-struct MelStftDev {
-    bool ready = false;
-    float* basis_Bt = nullptr;          // [1056 (= 2*513 padded to 33*32)][1024]
-    float* mel_Bt = nullptr;            // [80][544]
+// One mel plan (tts_hip_mel_fn_create): a checked configuration and its two tables on the device
+struct tts_hip_mel_fn {
+    MelPlan p;
+    float* basis_Bt = nullptr;          // [NB][Kpad] windowed cos rows of bins 0 .. cut - 1, then the -sin rows; zero padded
+    float* mel_Bt = nullptr;            // [n_mel][MAGK] Slaney filterbank, zero padded
     std::vector<void*> allocs;
-    DevBuf frames, mag;
+};
+struct MelStftDev {
+    bool ready = false;                 // the default plan exists (tts_hip_finalize)
+    tts_hip_mel_fn* def = nullptr;      // 1024 / 256 / 1024, 80 mels, 22 050 Hz, 0 - 8000 Hz: what tts_hip_mel_stft runs
+    std::vector<tts_hip_mel_fn*> plans; // the caller's plans still alive
+    DevBuf ws;                          // the one workspace of a call (MelGeom)
 };
 
 // Waveform clean-up (audio_proc.hip): DFT bases built on first use, no weights
@@ -333,7 +339,6 @@ private:
 };
 
 int melstft_finalize(tts_hip_engine* e);
-int melstft_run(tts_hip_engine* e, const float* d_audio, int B, int N, float* d_mel, int stop = -1, StageView* stop_out = nullptr);
 void melstft_free(tts_hip_engine* e);
 void audioproc_free(tts_hip_engine* e);
 void resample_free(tts_hip_engine* e);

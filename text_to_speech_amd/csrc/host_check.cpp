@@ -24,7 +24,12 @@
 // (noise_len; window_length threshold add_start add_end mode; rate target_rate M; method mode rate threshold min_silence
 // block_size replace_by min_voice_time).  First line "<status> <message>"; when the call is accepted the geometry the check
 // derived: reduce_noise "Fr NP Frn NQ total", trim "W Wp Cst", silence "NT NB cap w total", resample one line
-// "logf logi M_b" per row (tests/test_audio_call.py compares them with a Python restatement).
+// "logf logi M_b" per row (tests/test_audio_call.py compares them with a Python restatement).  KIND mel_fn: the plan check
+// and the call check of a mel plan (mel_cfg_check, then mel_call_check); settings mel_kind (the config's kind) sampling_rate n_mel_channels
+// filter_length hop_length win_length normalize_mode mel_fmin mel_fmax pre_emph, window=I:VALUE (an explicit window of ones
+// with window[I] = VALUE; else NULL) and null=cfg,fn,audio,out (fn: the call gets no plan).  First line as above, from
+// whichever check refuses first; accepted: "K4 Kpad NB MAGK gathered", "Fr Fout PW NP total" and "F_b ..." (the result's
+// frames per row), then "mel_fn_frames(N)" (tests/test_mel_fn_call.py).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
@@ -124,7 +129,13 @@ static int print_audio_call(int argc, char** argv) {
     std::map<std::string, double> v{{"B", -1}, {"N", 0}, {"mem", TTS_HIP_MEM_DEVICE}, {"noise_len", 1}, {"window_length", 2},
                                     {"threshold", 0.1}, {"add_start", 0}, {"add_end", 0}, {"mode", 0}, {"rate", 1},
                                     {"target_rate", 1}, {"M", 0}, {"method", 0}, {"min_silence", 0.1}, {"block_size", 1},
-                                    {"replace_by", 0}, {"min_voice_time", 0}, {"overlap", 0}};
+                                    {"replace_by", 0}, {"min_voice_time", 0}, {"overlap", 0}, {"mel_kind", 0},
+                                    {"sampling_rate", 22050}, {"n_mel_channels", 80}, {"filter_length", 1024},
+                                    {"hop_length", 256}, {"win_length", 1024}, {"normalize_mode", 0}, {"mel_fmin", 0},
+                                    {"mel_fmax", 8000}, {"pre_emph", 0}};
+    bool null_cfg = false, null_fn = false;
+    int window_at = -1;
+    double window_value = 1;
     std::vector<int32_t> lengths;
     for (int i = 3; i < argc; ++i) {
         const char* eq = strchr(argv[i], '=');
@@ -137,6 +148,12 @@ static int print_audio_call(int argc, char** argv) {
             if (strstr(eq, "audio")) audio = nullptr;
             if (strstr(eq, "out")) out = nullptr;
             if (strstr(eq, "lens")) lens_out = nullptr;
+            if (strstr(eq, "cfg")) null_cfg = true;
+            if (strstr(eq, "fn")) null_fn = true;
+        } else if (key == "window") {
+            const char* colon = strchr(eq, ':');
+            if (!colon) return 2;
+            window_at = atoi(eq + 1), window_value = atof(colon + 1);
         } else if (v.count(key)) {
             v[key] = atof(eq + 1);
         } else {
@@ -180,6 +197,25 @@ static int print_audio_call(int argc, char** argv) {
         if (rc) return 0;
         if ((int)c.lens.size() != B) return 2;
         printf("%d %d %d %d %zu\n", c.NT, c.NB, c.cap, c.w, c.total);
+    } else if (kind == "mel_fn") {
+        const tts_hip_mel_config cfg{(int)v["mel_kind"], (int)v["sampling_rate"], (int)v["n_mel_channels"], (int)v["filter_length"],
+                                     (int)v["hop_length"], (int)v["win_length"], (int)v["normalize_mode"], v["mel_fmin"],
+                                     v["mel_fmax"], v["pre_emph"]};
+        std::vector<double> window;
+        if (window_at >= 0 && cfg.win_length > 0 && cfg.win_length <= 4096) {
+            window.assign((size_t)cfg.win_length, 1.0);
+            if (window_at < cfg.win_length) window[(size_t)window_at] = window_value;
+        }
+        MelPlan p{};
+        int rc = mel_cfg_check("who", null_cfg ? nullptr : &cfg, window.empty() ? nullptr : window.data(), true, &p, why, sizeof why);
+        MelGeom g;
+        if (!rc) rc = mel_call_check("who", null_fn ? nullptr : &p, audio, B, N, lp, out, mem, &g, why, sizeof why);
+        printf("%d %s\n", rc, why);
+        if (rc) return 0;
+        if ((int)g.lens.size() != B || (int)g.fout.size() != B) return 2;
+        printf("%d %d %d %d %d\n%d %d %d %d %zu\n", p.K4, p.Kpad, p.NB, p.MAGK, (int)p.gather, g.Fr, g.Fout, g.PW, g.NP, g.total);
+        for (int b = 0; b < B; ++b) printf("%d%c", g.fout[b], b == B - 1 ? '\n' : ' ');
+        printf("%d\n", mel_out_frames(p, N));
     } else {
         return 2;
     }

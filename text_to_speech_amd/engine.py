@@ -11,7 +11,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
-from ._lib import HipLibraryError, MEM_DEVICE, MEM_HOST
+from ._lib import HipLibraryError, MelConfigC, MEM_DEVICE, MEM_HOST
 
 # field order of the reference's namedtuple (architectures/tacotron2_arch.py:52-56)
 Tacotron2InferenceOutput = namedtuple(
@@ -22,6 +22,15 @@ KERNEL_WN_IN, KERNEL_WN_RES_SKIP, KERNEL_DECODER_STEP = 0, 1, 2
 
 def _is_torch_cuda(x) -> bool:
     return hasattr(x, 'data_ptr') and hasattr(x, 'is_cuda') and bool(x.is_cuda)
+
+
+class MelFn:
+    """A mel plan of one engine (tts_hip_mel_fn; `HipEngine.mel_fn`).  It is freed when the engine closes."""
+
+    def __init__(self, handle, cfg):
+        self.handle = handle
+        self.n_mel = int(cfg.n_mel_channels)
+        self.geometry = {name: getattr(cfg, name) for name, _ in cfg._fields_}
 
 
 class EncodedBatch:
@@ -58,8 +67,9 @@ class HipEngine:
     # ------------------------------------------------------------------ plumbing
     def close(self):
         if getattr(self, '_h', None):
-            self._lib.tts_hip_destroy(self._h)
+            self._lib.tts_hip_destroy(self._h)          # frees the mel plans with the rest
             self._h = None
+            getattr(self, '_mel_fns', {}).clear()
 
     def __del__(self):
         try:
@@ -783,6 +793,73 @@ class HipEngine:
         shape = {'padded': (B, N + 1024), 'spectrum': (B, F, 1026), 'magnitude': (B, F, 513), 'mel_linear': (B, F, 80)}[what]
         return self._host_call('mel_stft_probe', a, B, N, [], lambda empty: (empty(shape, 'float32'),),
                                lambda extras, outs: (self._STFT_STAGES[what], outs[0]))[0]
+
+    # ------------------------------------------------------------------ mel plans (any TacotronSTFT configuration, WhisperSTFT)
+    _MEL_KINDS = {'tacotron': 0, 'whisper': 1}
+    _MEL_NORMS = {None: 0, 'per_feature': 1, 'all_feature': 2}
+    _MEL_FN_STAGES = {'padded': 0, 'spectrum': 1, 'magnitude': 2, 'mel_linear': 3, 'mel_log': 4}
+
+    def mel_fn(self, config, window=None):
+        """A mel plan (tts_hip_mel_fn_create) for `config` -- a mapping with sampling_rate, n_mel_channels, filter_length,
+        hop_length, win_length, mel_fmin, mel_fmax, and optionally kind ('tacotron' | 'whisper'), normalize_mode (None |
+        'per_feature' | 'all_feature') and pre_emph -- and `window` (float64 [win_length], None = periodic Hann).  Plans are
+        cached by value: the same configuration returns the same `MelFn`.  They live until the engine closes."""
+        cfg = dict(config)
+        kind, norm = cfg.get('kind', 'tacotron'), cfg.get('normalize_mode')
+        if kind not in self._MEL_KINDS or norm not in self._MEL_NORMS:
+            raise ValueError(f'mel_fn: kind must be one of {tuple(self._MEL_KINDS)} and normalize_mode one of '
+                             f'{tuple(self._MEL_NORMS)}, got {kind!r}, {norm!r}')
+        c = MelConfigC(self._MEL_KINDS[kind], int(cfg['sampling_rate']), int(cfg['n_mel_channels']), int(cfg['filter_length']),
+                       int(cfg['hop_length']), int(cfg['win_length']), self._MEL_NORMS[norm], float(cfg['mel_fmin']),
+                       float(cfg['mel_fmax']), float(cfg.get('pre_emph') or 0.0))
+        w = None
+        if window is not None:
+            w = np.ascontiguousarray(window, dtype=np.float64)
+            if w.shape != (c.win_length,):
+                raise ValueError(f'mel_fn: window must be [win_length = {c.win_length}], got {w.shape}')
+        key = (bytes(c), None if w is None else w.tobytes())
+        cache = self.__dict__.setdefault('_mel_fns', {})
+        if key not in cache:
+            h = ctypes.c_void_p()
+            self._check(self._lib.tts_hip_mel_fn_create(self._h, ctypes.byref(c), self._ptr(w), ctypes.byref(h)), 'mel_fn_create')
+            cache[key] = MelFn(h, c)
+        return cache[key]
+
+    def mel_fn_frames(self, plan, n_samples):
+        """Frames a row of `n_samples` yields under `plan`; raises when the plan refuses such a row."""
+        f = self._lib.tts_hip_mel_fn_frames(plan.handle, int(n_samples))
+        if f < 0:
+            raise ValueError(f'mel_fn: a row of {n_samples} samples is refused by this plan')
+        return f
+
+    def mel_fn_run(self, plan, audio, lengths=None, stream=None):
+        """audio [N] or [B, N] -> mel [B, F, n_mel] under `plan` (`mel_fn`), F = mel_fn_frames(plan, N).  Row b holds
+        lengths[b] samples (default N): its frames are what a one-row call on audio[b, :lengths[b]] gives, zero beyond, and
+        nothing behind its length is read.  numpy in -> numpy out; a CUDA tensor in -> a CUDA tensor out; `stream`
+        (torch.cuda.Stream, device tensors only): enqueue there and return without waiting (the plans of an engine share
+        one workspace: the next mel call must be ordered after it)."""
+        B, N, lens = self._audio_rows(audio, lengths, 'mel_fn_run')
+        F = self.mel_fn_frames(plan, N)
+        return self._rows_call('mel_fn_run', audio, B, N, [], lambda empty: (empty((B, F, plan.n_mel), 'float32'),),
+                               lambda extras, outs: (self._ptr(lens), plan.handle, outs[0]), stream)[0]
+
+    def mel_fn_probe(self, plan, audio, what: str = 'spectrum', lengths=None):
+        """Test hook (tts_hip_mel_fn_probe): run `mel_fn_run` on the same arguments (host arrays) up to a stage and return
+        what it computed there, with Fr the DFT frames of N (Whisper's last one included), P = max(N, win_length) +
+        2 * (filter_length // 2) and C = filter_length // 2 + 1: 'padded' [B, P] after the zero pad, the pre-emphasis and
+        the reflect pad; 'spectrum' [B, Fr, 2 C]; 'magnitude' [B, Fr, C]; 'mel_linear' [B, Fr, n_mel]; 'mel_log'
+        [B, F, n_mel] after the logarithm, before the normalisation / clamp."""
+        if what not in self._MEL_FN_STAGES:
+            raise ValueError(f'what must be one of {tuple(self._MEL_FN_STAGES)}, got {what!r}')
+        B, N, lens = self._audio_rows(audio, lengths, 'mel_fn_probe')
+        F = self.mel_fn_frames(plan, N)
+        g = plan.geometry
+        Fr = F + (1 if g['kind'] == 1 else 0)
+        C = g['filter_length'] // 2 + 1
+        shape = {'padded': (B, max(N, g['win_length']) + 2 * (g['filter_length'] // 2)), 'spectrum': (B, Fr, 2 * C),
+                 'magnitude': (B, Fr, C), 'mel_linear': (B, Fr, plan.n_mel), 'mel_log': (B, F, plan.n_mel)}[what]
+        return self._host_call('mel_fn_probe', audio, B, N, [], lambda empty: (empty(shape, 'float32'),),
+                               lambda extras, outs: (self._ptr(lens), plan.handle, self._MEL_FN_STAGES[what], outs[0]))[0]
 
     # ------------------------------------------------------------------ waveform clean-up (csrc/audio_proc.hip)
     _TRIM_MODES = {'start_end': 0, 'start': 1, 'end': 2}

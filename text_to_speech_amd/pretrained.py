@@ -131,7 +131,9 @@ def read_hparams(save_dir, model):
 
 def check_mel_fn(path):
     """`saving/mel_fn.json` (base_audio_model.py:99,208-217: `MelSTFT.get_config()`): the analysis the model was trained on
-    must be the TacotronSTFT the engine's mel-STFT implements."""
+    must be the default TacotronSTFT (1024 / 256 / 1024, 80 mels, 22 050 Hz, 0 - 8000 Hz): the synthesizer and the vocoder
+    are 80-mel / hop-256 models, so a model's own front end stays fixed.  To read such a file as an analysis object of any
+    configuration the engine's mel plans run, use `text_to_speech_amd.stft.MelSTFT.create(path)`."""
     cfg = _load_json(path)
     if not cfg:
         return None
