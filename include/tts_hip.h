@@ -194,6 +194,21 @@ int tts_hip_tacotron2_decode_rows_seeded(tts_hip_engine* e, const tts_hip_encode
                                          const uint64_t* keys, const uint64_t* offsets, int win_len, int win_offset,
                                          int precision, float* mel, float* decoder_output, float* stop_tokens,
                                          float* attention, int32_t* lengths, int32_t* steps_run, int mem, void* stream);
+/* Teacher-forced forward pass of an encoded batch (Tacotron2.call, tacotron2_arch.py:806-849 with :526-607): step t of the
+ * decoder reads frame t of `mel_input` [B, T, 80] -- ALREADY SHIFTED: frame 0 is the zero go-frame, frame t is target frame
+ * t - 1 (models/tts/tacotron2.py:243-259) -- instead of its own previous output.  Every row runs all T steps (no stop test,
+ * no attention window); mel_lengths: HOST int32 [B], each in 1 .. T.  prenet_masks: NULL (deterministic) or [B, T, 2, 256]
+ * multiplicative dropout masks; precision 0 = f32, 1 = fp16 copies of the two decoder LSTM matrices in the loop.
+ * Outputs (any may be NULL): decoder_output [B, T, 80] = where(t <= mel_lengths[b], frame, 0), mel = decoder_output +
+ * postnet(decoder_output) under that mask, stop_tokens [B, T] = sigmoid(gate), unmasked, attention [B, T, Tin].  Frames at
+ * and past a row's length are consumed as given.  mel_input, prenet_masks and the outputs live where `mem` says.
+ * Refused before any GPU work (csrc/taco_forward_call.h; first match wins): precision, mem kind, weights not finalized
+ * (TTS_HIP_ENOTREADY), NULL or foreign encoded batch, NULL mel_input / mel_lengths, T < 1, B * T > 65536, mel_lengths[b]
+ * outside [1, T].  Synchronizes `stream` (NULL: the handle's) before returning, like `decode`; a following
+ * tts_hip_tacotron2_infer* / decode call on the handle is unaffected.                                                   */
+int tts_hip_tacotron2_forward(tts_hip_engine* e, const tts_hip_encoded* encoded, const float* mel_input, int T,
+                              const int32_t* mel_lengths, const float* prenet_masks, int precision, float* mel,
+                              float* decoder_output, float* stop_tokens, float* attention, int mem, void* stream);
 /* Runs the encoder for another token batch INTO an existing encoded batch (its device buffer is reused and only grows):
  * what a caller that synthesizes sentence after sentence wants -- no hipMalloc / hipFree per sentence, and the decoder's
  * cached step graphs (keyed by the buffer) survive from one sentence to the next.  Asynchronous like `encode`.        */

@@ -15,6 +15,7 @@
 #include "ttsw_host.h"      // HostTensor + the TTSW parser (host-only code, also built under ASan / UBSan)
 #include "wg_call.h"        // WgCall: one WaveGlow call, its checks and its staged table (host-only code, likewise)
 #include "audio_call.h"     // the audio calls' checks and the geometry they rest on (host-only code, likewise)
+#include "taco_forward_call.h"      // the teacher-forced Tacotron2 call's check and buffer sizes (host-only code, likewise)
 
 // Growable device buffer (workspace).  Never shrinks; reallocated only when a larger request arrives.
 struct DevBuf {
@@ -124,7 +125,8 @@ struct tts_hip_encoded {
 };
 
 // The three machines that can run the decoder loop; the values are what tts_hip_last_decoder_mode reports.
-enum DecMachine { DEC_STEP_GRAPH = 0, DEC_PERSISTENT = 1, DEC_FUSED = 2 };
+// (DEC_FORWARD only names the chunk graphs of the teacher-forced pass in the graph cache: it is never a last_path.)
+enum DecMachine { DEC_STEP_GRAPH = 0, DEC_PERSISTENT = 1, DEC_FUSED = 2, DEC_FORWARD = 3 };
 
 // Identity of an instantiated decoder-chunk hipGraph: every pointer and scalar its 225 kernel nodes have baked in.
 // ws_layout says which exchange areas the workspace plan sized in (the offset of every later buffer depends on it).
@@ -165,6 +167,7 @@ struct Tacotron2Dev {
     float* bl_rec[2] = {nullptr, nullptr};     // recurrent kernels transposed [1024][256]
     float* prenet_w0 = nullptr;         // [20][256][4]  (k / 4, output, k % 4)
     float* prenet_w1 = nullptr;         // [256][256]
+    float* prenet_w0_Bt = nullptr;      // [256][96]  layer 0 as a GEMM operand (K = 80, zero padded): the forward call's bulk prenet
     LstmDev att, dec;
     float* query_w = nullptr;           // [128][1024]
     float* memory_Bt = nullptr;         // [128][enc]

@@ -30,11 +30,17 @@
 // with window[I] = VALUE; else NULL) and null=cfg,fn,audio,out (fn: the call gets no plan).  First line as above, from
 // whichever check refuses first; accepted: "K4 Kpad NB MAGK gathered", "Fr Fout PW NP total" and "F_b ..." (the result's
 // frames per row), then "mel_fn_frames(N)" (tests/test_mel_fn_call.py).
+//        ttsw_check_asan --taco-forward [KEY=VALUE...] [LEN...]  -- the front end of a teacher-forced Tacotron2 call
+// (taco_forward_call.h) for an encoded batch of B = number of LEN rows (mel_lengths; no LEN: B from B=, every length T).
+// Settings: B= T= Tin= enc= model_enc= precision= mem= ready=0|1 and null=encoded,mel,lens.  First line "<status> <message>"
+// of taco_forward_check; when the call is accepted "frames mel_in prenet gates history proj" of taco_forward_sizes
+// (tests/test_teacher_forced.py compares them with a Python restatement).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
 
 #include "audio_call.h"
+#include "taco_forward_call.h"
 #include "ttsw_host.h"
 #include "wg_call.h"
 #include "wg_plan.h"
@@ -222,7 +228,44 @@ static int print_audio_call(int argc, char** argv) {
     return 0;
 }
 
+static int print_taco_forward(int argc, char** argv) {
+    static float mel;                                                          // never read: the front end only tests the pointer
+    std::map<std::string, int> v{{"B", -1}, {"T", 1}, {"Tin", 8}, {"enc", 512}, {"model_enc", 512}, {"precision", 0},
+                                 {"mem", TTS_HIP_MEM_HOST}, {"ready", 1}};
+    bool null_enc = false, null_mel = false, null_lens = false;
+    std::vector<int32_t> lens;
+    for (int i = 2; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) {
+            lens.push_back((int32_t)atoi(argv[i]));
+            continue;
+        }
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        if (key == "null") {
+            if (strstr(eq, "encoded")) null_enc = true;
+            if (strstr(eq, "mel")) null_mel = true;
+            if (strstr(eq, "lens")) null_lens = true;
+        } else if (v.count(key)) {
+            v[key] = atoi(eq + 1);
+        } else {
+            return 2;
+        }
+    }
+    const int B = lens.empty() ? v["B"] : (int)lens.size();
+    if (lens.empty() && B > 0 && B <= (1 << 20)) lens.assign((size_t)B, (int32_t)v["T"]);
+    const TacoForwardCall c{"who", v["ready"] != 0, !null_enc, B, v["Tin"], v["enc"], v["model_enc"], null_mel ? nullptr : &mel,
+                            v["T"], null_lens || lens.empty() ? nullptr : lens.data(), v["precision"], v["mem"]};
+    char why[256] = "";
+    const int rc = taco_forward_check(c, why, sizeof why);
+    printf("%d %s\n", rc, why);
+    if (rc) return 0;
+    const TacoForwardSizes z = taco_forward_sizes(c.B, c.T, c.enc);
+    printf("%lld %zu %zu %zu %zu %zu\n", z.frames, z.mel_in, z.prenet, z.gates, z.history, z.proj);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--taco-forward")) return print_taco_forward(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "--audio-call")) return print_audio_call(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wg-call")) return print_wg_call(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wn-taps")) {

@@ -15,9 +15,12 @@
 // The step index is `*t0 + j` (j baked into the launch), so 32 steps form one hipGraph that is replayed per chunk;
 // every kernel returns immediately once all rows are finished (device flag), which keeps the reference's
 // "stop as soon as every row has fired" semantics (:625-627) without a host round trip per step.
+// The teacher-forced pass (Tacotron2.call; taco_forward.hip) runs the same cell with the prenet and the projection taken out
+// of the loop: five launches per step, driven from tacotron2_forward_impl below.
 #include "engine.h"
 #include "taco_persist.h"
 #include "taco_fused.h"
+#include "taco_forward.h"
 
 #include <atomic>
 #include <mutex>
@@ -267,14 +270,30 @@ __global__ __launch_bounds__(256) void prenet_kernel(const DecState* __restrict_
 // lane-halving exchange (V - 1 + log2(64 / V) shuffles for V = 4 * NBT values instead of 6 V).
 // HW: the weight rows are fp16 in memory (half the bytes of the stream that bounds this kernel); they are widened to fp32
 // once per register and everything else -- x, accumulation, gates, cell state -- stays fp32.
-template <int KS, int NBT, bool HW>
+// FX: empty for the decode machines (no argument, no code), or the one extra the teacher-forced pass gives a step
+// (tts_hip_tacotron2_forward; rows are b_base + b of a batch whose frame count T is the loop state's max_len):
+//   LstmAddGates  attention LSTM: the packed rows' first 256 columns (the prenet's) are skipped -- K counts the rest -- and
+//                 their product, hoisted out of the loop as G[b * T + t][4 * U], is added to the gate pre-activations;
+//   LstmKeepHist  decoder LSTM: cell_out = [h_new | s1 (the context)] of the step is kept in hist[b * T + t][U + n1].
+struct LstmAddGates { const float* G; int b_base; };
+struct LstmKeepHist { float* hist; int b_base; };
+struct LstmNoFx {};
+__device__ __forceinline__ LstmNoFx first_fx() { return {}; }
+template <class T> __device__ __forceinline__ T first_fx(T v) { return v; }
+
+template <int KS, int NBT, bool HW, class... FX>
 __global__ __launch_bounds__(256) void lstm_step_kernel(const DecState* __restrict__ st, int j,
                                                         const void* __restrict__ Wp_v, const float* __restrict__ bp,
                                                         const float* __restrict__ s0, int n0,
                                                         const float* __restrict__ s1, int n1,
                                                         const float* __restrict__ h_old, float* __restrict__ h_new,
-                                                        float* __restrict__ c_state, int B, int U) {
+                                                        float* __restrict__ c_state, int B, int U, FX... fx) {
+    static_assert(sizeof...(FX) <= 1, "one extra at most");
+    const auto fx0 = first_fx(fx...);
+    typedef typename std::remove_const<decltype(fx0)>::type FX0;
+    constexpr bool ADDG = std::is_same<FX0, LstmAddGates>::value, HIST = std::is_same<FX0, LstmKeepHist>::value;
     constexpr int K = 256 * KS;
+    constexpr int WSKIP = ADDG ? PRE : 0, LDW = K + WSKIP;           // columns skipped / floats between two packed rows
     constexpr int V = 4 * NBT;                                       // partial sums per lane
     constexpr int NX4 = NBT * (K / 4);                               // float4 of x to stage
     constexpr int NST = (NX4 + 255) / 256;                           // staging float4 per thread
@@ -286,12 +305,12 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const DecState* __restri
     typedef typename std::conditional<HW, f16x4, f32x4>::type wvec_t;
     typedef typename std::conditional<HW, _Float16, float>::type wel_t;
     wvec_t wraw[4][KS];
-    const wel_t* wrow = (const wel_t*)Wp_v + (long long)(4 * u) * K + lane * 4;
+    const wel_t* wrow = (const wel_t*)Wp_v + (long long)(4 * u) * LDW + WSKIP + lane * 4;
 #pragma unroll
     for (int gt = 0; gt < 4; ++gt)
 #pragma unroll
         for (int i = 0; i < KS; ++i) {
-            const wvec_t* wp = reinterpret_cast<const wvec_t*>(wrow + (long long)gt * K + i * 256);
+            const wvec_t* wp = reinterpret_cast<const wvec_t*>(wrow + (long long)gt * LDW + i * 256);
             // decoder LSTM (KS >= 10): stream past the L2, so that the attention LSTM's rows -- 1.8 MB per XCD in fp16, the
             // same rows on the same XCD every step -- stay resident in the 4 MB L2 (fp16 mode: 35.1 -> 33.8 us/step;
             // fp32, 3.7 MB per XCD: neutral)
@@ -330,6 +349,11 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const DecState* __restri
     const bool writer = lane < (NBT << SH0) && (lane & ((1 << SH0) - 1)) == 0 && (lane >> SH0) < B;
     const f32x4 bias4 = *reinterpret_cast<const f32x4*>(bp + 4 * u);
     const float c_old = writer ? c_state[(long long)(lane >> SH0) * U + u] : 0.f;
+    f32x4 gadd = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (ADDG) {                       // (a finished loop has no row t: the address is only formed for a live step)
+        if (writer && !done)
+            gadd = *reinterpret_cast<const f32x4*>(fx0.G + ((long long)(fx0.b_base + (lane >> SH0)) * st->max_len + t) * (4ll * U) + 4 * u);
+    }
     // pin the weights: without this the compiler sinks each weight load next to its first use inside the FMA loop
     // (serialising HBM round trips) when register pressure is high (NBT = 8)
 #pragma unroll
@@ -352,6 +376,12 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const DecState* __restri
             if (idx < NX4) *reinterpret_cast<f32x4*>(xs + (idx / (K / 4)) * K + (idx % (K / 4)) * 4) = sv[i];
         }
         __syncthreads();
+        if constexpr (HIST) {                   // block bb < B copies row bb's context out of the staged x
+            const int bb = blockIdx.x;
+            if (bb < B && !done && tid < n1 / 4)
+                *reinterpret_cast<f32x4*>(fx0.hist + ((long long)(fx0.b_base + bb) * st->max_len + t) * (U + n1) + U + tid * 4) =
+                    *reinterpret_cast<const f32x4*>(xs + bb * K + n0 + tid * 4);
+        }
         // Packed accumulation: each (gate, row) sum is kept as an (even-k, odd-k) pair so that one v_pk_fma_f32 takes two
         // adjacent registers of the x float4 and of the weight float4.  x is read from LDS in groups of 4 float4, one
         // group ahead of the FMAs that consume it (explicit double buffer; the compiler barrier keeps it from hoisting
@@ -426,13 +456,25 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const DecState* __restri
         static_assert(SH == SH0, "writer lanes");
         if (!done && writer) {                      // only the final stores depend on the loop state
             const int b = b0 + (lane >> SH);
-            const float ig = sigmoid_exact(gi + bias4[0]);
-            const float fg = sigmoid_exact(gf + bias4[1]);
-            const float cg = tanhf(gg + bias4[2]);
-            const float og = sigmoid_exact(go + bias4[3]);
-            const float cn = fg * c_old + ig * cg;
-            c_state[(long long)b * U + u] = cn;
-            h_new[(long long)b * U + u] = og * tanhf(cn);
+            if constexpr (ADDG || HIST) {           // the same update with the forward call's extra (gadd is zero without ADDG)
+                const float ig = sigmoid_exact(gi + bias4[0] + gadd[0]);
+                const float fg = sigmoid_exact(gf + bias4[1] + gadd[1]);
+                const float cg = tanhf(gg + bias4[2] + gadd[2]);
+                const float og = sigmoid_exact(go + bias4[3] + gadd[3]);
+                const float cn = fg * c_old + ig * cg;
+                const float hn = og * tanhf(cn);
+                c_state[(long long)b * U + u] = cn;
+                h_new[(long long)b * U + u] = hn;
+                if constexpr (HIST) fx0.hist[((long long)(fx0.b_base + b) * st->max_len + t) * (U + n1) + u] = hn;
+            } else {
+                const float ig = sigmoid_exact(gi + bias4[0]);
+                const float fg = sigmoid_exact(gf + bias4[1]);
+                const float cg = tanhf(gg + bias4[2]);
+                const float og = sigmoid_exact(go + bias4[3]);
+                const float cn = fg * c_old + ig * cg;
+                c_state[(long long)b * U + u] = cn;
+                h_new[(long long)b * U + u] = og * tanhf(cn);
+            }
         }
     }
 }
@@ -915,24 +957,26 @@ int conv_gemm(tts_hip_engine* e, const ConvBnDev& cv, const float* x, int ldx, f
     return TTS_HIP_OK;
 }
 
-template <int KS, int NBT, bool HW>
+template <int KS, int NBT, bool HW, class... FX>
 hipError_t launch_lstm(hipStream_t s, const DecState* st, int j, const LstmDev& L, const float* s0, int n0,
-                       const float* s1, int n1, const float* h_old, float* h_new, float* c_state, int B) {
+                       const float* s1, int n1, const float* h_old, float* h_new, float* c_state, int B, FX... fx) {
     const size_t lds = (size_t)NBT * 256 * KS * sizeof(float);
-    auto kern = lstm_step_kernel<KS, NBT, HW>;
+    auto kern = lstm_step_kernel<KS, NBT, HW, FX...>;
     static PerDeviceOnce attr;
     if (hipError_t er = set_max_dyn_lds_once((const void*)kern, lds, attr); er != hipSuccess) return er;
     const void* W = HW ? (const void*)L.W16 : (const void*)L.W;
     hipLaunchKernelGGL(kern, dim3(L.units / 4), dim3(256), lds, s, st, j, W, L.b, s0, n0, s1, n1, h_old, h_new,
-                       c_state, B, L.units);
+                       c_state, B, L.units, fx...);
     return hipGetLastError();
 }
 
-template <int KS, bool HW>
+// (fx: the forward call's extra, whose b_base this loop sets to the chunk's first row)
+template <int KS, bool HW, class... FX>
 hipError_t lstm_by_batch(hipStream_t s, const DecState* st, int j, const LstmDev& L, const float* s0, int n0,
-                         const float* s1, int n1, const float* h_old, float* h_new, float* c_state, int B) {
+                         const float* s1, int n1, const float* h_old, float* h_new, float* c_state, int B, FX... fx) {
     // one launch per chunk of <= 8 batch rows (B > 8 re-streams the weights from L2 / Infinity Cache per chunk)
     for (int b0 = 0; b0 < B; b0 += NB) {
+        ((fx.b_base = b0), ...);
         const int nb = std::min(NB, B - b0);
         const float* a0 = s0 + (size_t)b0 * n0;
         const float* a1 = s1 + (size_t)b0 * n1;
@@ -940,10 +984,10 @@ hipError_t lstm_by_batch(hipStream_t s, const DecState* st, int j, const LstmDev
         float* hn = h_new + (size_t)b0 * L.units;
         float* cs = c_state + (size_t)b0 * L.units;
         hipError_t er;
-        if (nb == 1) er = launch_lstm<KS, 1, HW>(s, st, j, L, a0, n0, a1, n1, ho, hn, cs, nb);
-        else if (nb == 2) er = launch_lstm<KS, 2, HW>(s, st, j, L, a0, n0, a1, n1, ho, hn, cs, nb);
-        else if (nb <= 4) er = launch_lstm<KS, 4, HW>(s, st, j, L, a0, n0, a1, n1, ho, hn, cs, nb);
-        else er = launch_lstm<KS, 8, HW>(s, st, j, L, a0, n0, a1, n1, ho, hn, cs, nb);
+        if (nb == 1) er = launch_lstm<KS, 1, HW>(s, st, j, L, a0, n0, a1, n1, ho, hn, cs, nb, fx...);
+        else if (nb == 2) er = launch_lstm<KS, 2, HW>(s, st, j, L, a0, n0, a1, n1, ho, hn, cs, nb, fx...);
+        else if (nb <= 4) er = launch_lstm<KS, 4, HW>(s, st, j, L, a0, n0, a1, n1, ho, hn, cs, nb, fx...);
+        else er = launch_lstm<KS, 8, HW>(s, st, j, L, a0, n0, a1, n1, ho, hn, cs, nb, fx...);
         if (er != hipSuccess) return er;
     }
     return hipSuccess;
@@ -959,6 +1003,25 @@ hipError_t lstm_dispatch_p(hipStream_t s, const DecState* st, int j, const LstmD
         case 11: return lstm_by_batch<11, HW>(s, st, j, L, s0, n0, s1, n1, h_old, h_new, c_state, B);
         default: return hipErrorInvalidValue;
     }
+}
+
+// The forward call's LSTMs: K = n0 + n1 + units counts the columns the step streams (the attention LSTM's prenet columns
+// are not among them), enc = 512 or 768.
+template <bool HW, class FXT>
+hipError_t lstm_forward_p(hipStream_t s, const DecState* st, int j, const LstmDev& L, const float* s0, int n0,
+                          const float* s1, int n1, const float* h_old, float* h_new, float* c_state, int B, FXT fx) {
+    constexpr int KS0 = std::is_same<FXT, LstmAddGates>::value ? 6 : 10;
+    switch ((n0 + n1 + L.units) / 256 - KS0) {
+        case 0: return lstm_by_batch<KS0, HW>(s, st, j, L, s0, n0, s1, n1, h_old, h_new, c_state, B, fx);
+        case 1: return lstm_by_batch<KS0 + 1, HW>(s, st, j, L, s0, n0, s1, n1, h_old, h_new, c_state, B, fx);
+        default: return hipErrorInvalidValue;
+    }
+}
+template <class FXT>
+hipError_t lstm_forward(hipStream_t s, const DecState* st, int j, const LstmDev& L, const float* s0, int n0,
+                        const float* s1, int n1, const float* h_old, float* h_new, float* c_state, int B, bool half_w, FXT fx) {
+    return half_w ? lstm_forward_p<true>(s, st, j, L, s0, n0, s1, n1, h_old, h_new, c_state, B, fx)
+                  : lstm_forward_p<false>(s, st, j, L, s0, n0, s1, n1, h_old, h_new, c_state, B, fx);
 }
 
 hipError_t lstm_dispatch(hipStream_t s, const DecState* st, int j, const LstmDev& L, const float* s0, int n0,
@@ -1064,6 +1127,7 @@ int tacotron2_finalize(tts_hip_engine* e) {
         TCHK(upload(e, w0p.data(), w0p.size(), &tc.prenet_w0, al));
     }
     TCHK(upload_transposed(e, p1, PRE, PRE, PRE, &tc.prenet_w1, al));
+    TCHK(upload_transposed(e, p0, NMEL, PRE, 96, &tc.prenet_w0_Bt, al));       // [256][96]: the forward call's GEMM operand
     const HostTensor* ak0 = get("decoder/attention_rnn/kernel");
     if (!ak0) { tacotron2_free(e); return set_err(e, TTS_HIP_ENOTREADY, "missing tensor tacotron2/decoder/attention_rnn/kernel"); }
     const int enc = ak0->dims.size() == 2 ? (int)ak0->dims[0] - PRE : -1;    // 512, or 768 with a 256-d speaker embedding
@@ -1411,8 +1475,10 @@ static PostnetBufs postnet_layout(Arena& A, long long RD) {
 static int max_len_bucket(int max_len) { return (max_len + 255) / 256 * 256; }
 
 // The workspace of a decode call whose shape rule picked `machine` (it decides which exchange area is sized in).
+// fwd (the teacher-forced pass): its buffers are laid out too -- the two a chunk graph addresses right behind the histories,
+// the history bucketed like them and the gate term last, so that both start where every call of the bucket finds them.
 static DecoderWs decoder_layout(Arena& A, const tts_hip_engine* e, DecMachine machine, int B, int Tin, int max_len,
-                                bool with_masks) {
+                                bool with_masks, ForwardBufs* fwd = nullptr) {
     const int enc = e->taco.enc_dim;
     const size_t R = (size_t)B * Tin, RB = (size_t)B * max_len_bucket(max_len);
     const bool persist = machine == DEC_PERSISTENT, fused = machine == DEC_FUSED;
@@ -1444,6 +1510,16 @@ static DecoderWs decoder_layout(Arena& A, const tts_hip_engine* e, DecMachine ma
     w.dec_out = A.take<float>(RB * NMEL);
     w.stop_out = A.take<float>(RB);
     w.attn_hist = A.take<float>(RB * Tin);
+    if (fwd) {
+        const TacoForwardSizes z = taco_forward_sizes(B, max_len, enc);
+        fwd->hist = A.take<float>(z.history);
+        fwd->gates = A.take<float>(z.gates);
+        fwd->mel_in = A.take<float>(z.mel_in);
+        fwd->p1 = A.take<float>(z.prenet);
+        fwd->p2 = A.take<float>(z.prenet);
+        fwd->proj = A.take<float>(z.proj);
+        fwd->lengths = A.take<int>(B);
+    }
     w.post = postnet_layout(A, (long long)B * max_len);
     return w;
 }
@@ -1789,6 +1865,123 @@ static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, i
     if ((rc = check_bilstm_status(e, bl_err))) return rc;
     if (steps_run) *steps_run = host_steps;
     return TTS_HIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------- forward
+// The five launches of step j of a chunk of the teacher-forced pass (taco_forward.hip has the semantics and what left the
+// loop): the prenet and the projection of enqueue_step are gone, the attention LSTM adds its hoisted prenet term and the
+// decoder LSTM keeps cell_out.  No rendezvous, no exchange area, no wait of any kind.
+static int enqueue_forward_step(tts_hip_engine* e, const DecodeCall& c, const ForwardBufs& f, int j) {
+    const Tacotron2Dev& tc = e->taco;
+    const DecoderWs& w = c.ws;
+    hipStream_t st = e->stream;
+    DecState* state = (DecState*)w.state;
+    const int B = c.B, Tin = c.Tin, enc = tc.enc_dim;
+    const int par = j & 1;                       // CHUNK is even, so the parity of t equals the parity of j
+    float* hatt_old = w.hatt + (size_t)par * B * ARNN;
+    float* hatt_new = w.hatt + (size_t)(par ^ 1) * B * ARNN;
+    float* hdec_old = w.hdec + (size_t)par * B * DRNN;
+    float* hdec_new = w.hdec + (size_t)(par ^ 1) * B * DRNN;
+    timing_begin(e, 2);
+    HIPCHK(e, lstm_forward(st, state, j, tc.att, w.ctx, enc, (const float*)nullptr, 0, hatt_old, hatt_new, w.catt, B, c.half_w,
+                           LstmAddGates{f.gates, 0}));
+    hipLaunchKernelGGL(query_kernel, dim3(ATT / 2), dim3(256), 0, st, state, j, hatt_new, tc.query_w, w.q, B);
+    HIPCHK(e, hipGetLastError());
+    hipLaunchKernelGGL(energies_kernel, dim3(B, (Tin + EPB - 1) / EPB), dim3(256), 0, st, state, j, w.q, tc.loc_dense, tc.value_w,
+                       c.pm, w.wprev, w.wcum, w.energy, Tin);
+    HIPCHK(e, hipGetLastError());
+    hipLaunchKernelGGL(softmax_ctx_kernel, dim3(B, enc / 32), dim3(256), (size_t)Tin * sizeof(float), st, state, j, w.energy,
+                       c.mask, c.enc_len, 0, 0, w.mainatt + par * B, w.mainatt + (par ^ 1) * B, c.memory, w.wprev, w.wcum, w.ctx,
+                       w.attn_hist, Tin, enc);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, lstm_forward(st, state, j, tc.dec, hatt_new, ARNN, w.ctx, enc, hdec_old, hdec_new, w.cdec, B, c.half_w,
+                           LstmKeepHist{f.hist, 0}));
+    timing_end(e);
+    return TTS_HIP_OK;
+}
+
+static int enqueue_forward_chunk(tts_hip_engine* e, const DecodeCall& c, const ForwardBufs& f) {
+    for (int j = 0; j < CHUNK; ++j)
+        if (int rc = enqueue_forward_step(e, c, f, j)) return rc;
+    hipLaunchKernelGGL(advance_chunk_kernel, dim3(1), dim3(1), 0, e->stream, (DecState*)c.ws.state);
+    HIPCHK(e, hipGetLastError());
+    return TTS_HIP_OK;
+}
+
+// Teacher-forced pass + postnet from an encoded batch, all T steps of every row.  Enqueued on e->stream: bulk prenet and
+// gate term, the chunk graphs back to back (the loop's exit is not data dependent, so nothing is read back between them),
+// bulk projection, postnet, outputs; ONE synchronisation at the end, which also reads the BiLSTM status.  The workspace is
+// the decode call's plan with the forward buffers added, so a following decode call plans, resets and runs as ever.
+static int tacotron2_forward_impl(tts_hip_engine* e, const tts_hip_encoded* en, const float* mel_input, int T,
+                                  const int32_t* mel_lengths, const float* prenet_masks, int precision, float* mel,
+                                  float* decoder_output, float* stop_tokens, float* attention, int mem) {
+    Tacotron2Dev& tc = e->taco;
+    const bool has_enc = en && en->buf.p;
+    const TacoForwardCall fc{"tacotron2_forward", tc.ready, has_enc, has_enc ? en->B : 0, has_enc ? en->Tin : 0,
+                             has_enc ? en->enc : 0, tc.enc_dim, mel_input, T, mel_lengths, precision, mem};
+    char why[256] = "";
+    if (int rc = taco_forward_check(fc, why, sizeof why)) return set_err(e, rc, "%s", why);
+    int rc;
+    const bool half_w = precision == 1;
+    if (half_w && (rc = tacotron2_build_f16(e))) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const int B = en->B, Tin = en->Tin;
+    const size_t RD = (size_t)B * T;
+
+    const bool with_masks = prenet_masks != nullptr;
+    DecoderWs ws{};
+    ForwardBufs f{};
+    if ((rc = plan_workspace(e, tc.ws, 4096, [&](Arena& A) { ws = decoder_layout(A, e, DEC_STEP_GRAPH, B, Tin, T, with_masks, &f); })))
+        return rc;
+    // (the masks are consumed by the bulk prenet: the loop never sees them)
+    const DecodeCall call{B, Tin, T, 0, 0, 0, half_w, en->buf.p, en->memory, en->pm, en->mask, en->enc_len, en->bl_err, nullptr, ws};
+
+    const hipMemcpyKind kin = mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    HIPCHK(e, hipMemcpyAsync(f.mel_in, mel_input, RD * NMEL * 4, kin, st));
+    HIPCHK(e, hipMemcpyAsync(f.lengths, mel_lengths, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (with_masks) HIPCHK(e, hipMemcpyAsync(ws.masks, prenet_masks, RD * 2 * PRE * 4, kin, st));
+
+    if ((rc = forward_bulk_prenet(e, f, (long long)RD, with_masks ? ws.masks : nullptr))) return rc;
+
+    // ---------------- the loop: every state, history and output of the real rows from zero, then the chunks
+    if ((rc = reset_loop_state(e, call))) return rc;
+    bool use_graph = !e->timing;                 // per-step HIP events (tts_hip_kernel_timing) cannot be captured
+    hipGraphExec_t gexec = nullptr;
+    if (use_graph) {
+        // masks in the key: they change where every later buffer of the plan starts
+        const DecGraphKey key{tc.ws.p, call.enc_buf, B, Tin, max_len_bucket(T), with_masks ? 1 : 0, 0, 0, half_w ? 1 : 0,
+                              ws.layout_id, DEC_FORWARD};
+        if ((rc = tc.graphs.get_or_capture(e, key, st, [&] { return enqueue_forward_chunk(e, call, f); }, &gexec))) return rc;
+    }
+    for (int t0 = 0; t0 < T; t0 += CHUNK) {
+        if (use_graph) HIPCHK(e, hipGraphLaunch(gexec, st));
+        else if ((rc = enqueue_forward_chunk(e, call, f))) return rc;
+    }
+
+    // ---------------- projection, gate, mask; postnet + residual
+    if ((rc = forward_project(e, f, B, T, ws.dec_out, ws.stop_out))) return rc;
+    if ((rc = postnet_residual(e, f.lengths, ws.dec_out, B, T, ws.post))) return rc;
+
+    // ---------------- outputs
+    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (mel) HIPCHK(e, hipMemcpyAsync(mel, ws.post.mel, RD * NMEL * 4, kout, st));
+    if (decoder_output) HIPCHK(e, hipMemcpyAsync(decoder_output, ws.dec_out, RD * NMEL * 4, kout, st));
+    if (stop_tokens) HIPCHK(e, hipMemcpyAsync(stop_tokens, ws.stop_out, RD * 4, kout, st));
+    if (attention) HIPCHK(e, hipMemcpyAsync(attention, ws.attn_hist, RD * Tin * 4, kout, st));
+    int bl_err = 0;
+    HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    return check_bilstm_status(e, bl_err);
+}
+
+extern "C" int tts_hip_tacotron2_forward(tts_hip_engine* e, const tts_hip_encoded* encoded, const float* mel_input, int T,
+                                         const int32_t* mel_lengths, const float* prenet_masks, int precision, float* mel,
+                                         float* decoder_output, float* stop_tokens, float* attention, int mem, void* stream) {
+    if (!e) return TTS_HIP_EINVAL;
+    StreamScope scope(e, stream);
+    return tacotron2_forward_impl(e, encoded, mel_input, T, mel_lengths, prenet_masks, precision, mel, decoder_output,
+                                  stop_tokens, attention, mem);
 }
 
 static int tacotron2_infer_impl(tts_hip_engine* e, const int32_t* tokens, int B, int Tin, const float* speaker,

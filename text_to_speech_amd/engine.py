@@ -17,6 +17,9 @@ from ._lib import HipLibraryError, MelConfigC, MEM_DEVICE, MEM_HOST
 Tacotron2InferenceOutput = namedtuple(
     'Tacotron2InferenceOutput', ['decoder_output', 'mel', 'stop_tokens', 'attention_weights', 'lengths'])
 
+# what Tacotron2.call returns (tacotron2_arch.py:849) plus the alignments, which `call` drops
+Tacotron2ForwardOutput = namedtuple('Tacotron2ForwardOutput', ['decoder_output', 'mel', 'stop_tokens', 'attention_weights'])
+
 KERNEL_WN_IN, KERNEL_WN_RES_SKIP, KERNEL_DECODER_STEP = 0, 1, 2
 
 
@@ -562,6 +565,87 @@ class HipEngine:
         self.last_steps = int(steps.value)
         return Tacotron2InferenceOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn,
                                         lengths=lengths)
+
+    def tacotron2_forward(self, tokens, mel_input, mel_lengths=None, speaker=None, prenet_masks=None, seed=None,
+                          offset: int = 0, precision: str = 'f32', stream=None):
+        """Teacher-forced pass (Tacotron2.call; tts_hip_tacotron2_forward): step t of the decoder reads `mel_input[:, t]`
+        instead of its own previous output, every row runs all T steps.  `tokens`: int32 [B, Tin] (0 = pad; with `speaker`
+        [B, E] for a multi-speaker model) or an `EncodedBatch`.  `mel_input` float32 [B, T, 80] is ALREADY SHIFTED: frame 0 is
+        the zero go-frame, frame t is target frame t - 1.  `mel_lengths` [B] (default: T for every row), each in 1 .. T:
+        decoder_output and mel are zero / masked where t > mel_lengths[b]; stop tokens and attention are not masked.
+        Dropout: `prenet_masks` [B, T, 2, 256], or `seed` (the masks of `random_prenet_masks(B, T, seed, offset)`), or
+        neither (deterministic).  numpy in gives numpy out; CUDA tensors in give CUDA tensors out.
+        Repeated calls: pass an `EncodedBatch` (`tacotron2_encode`, re-filled with `into=`) -- the chunk graphs are cached per
+        encoded batch and replayed; a call made from tokens encodes into a fresh buffer, which empties the handle's graph
+        cache (decode graphs included), so it captures its graph anew every time.
+        Returns Tacotron2ForwardOutput(decoder_output [B, T, 80], mel [B, T, 80], stop_tokens [B, T],
+        attention_weights [B, T, Tin]) after `stream` (or the engine's stream) has drained."""
+        if precision not in ('f32', 'f16'):
+            raise ValueError(f"precision must be 'f32' or 'f16', got {precision!r}")
+        if seed is not None and prenet_masks is not None:
+            raise ValueError('pass either prenet_masks or seed, not both')
+        dev = _is_torch_cuda(mel_input)
+        if stream is not None and not dev:
+            raise ValueError('stream= needs device tensors')
+        own = not isinstance(tokens, EncodedBatch)
+        if own:
+            if _is_torch_cuda(tokens) != dev:
+                raise ValueError('tokens and mel_input must both be numpy arrays or both CUDA tensors')
+            encoded = self.tacotron2_encode(tokens, speaker=speaker, stream=stream)
+        else:
+            encoded = tokens
+            if encoded.engine is not self or encoded.handle is None:
+                raise ValueError('this EncodedBatch belongs to another engine or was freed')
+        try:
+            B, Tin = encoded.B, encoded.Tin
+            if len(mel_input.shape) != 3 or int(mel_input.shape[0]) != B or int(mel_input.shape[2]) != 80:
+                raise ValueError(f'mel_input must be [B = {B}, T, 80], got {tuple(mel_input.shape)}')
+            T = int(mel_input.shape[1])
+            lens = np.full((B,), T, np.int32) if mel_lengths is None else np.ascontiguousarray(
+                mel_lengths.detach().cpu().numpy() if hasattr(mel_lengths, 'detach') else mel_lengths, dtype=np.int32)
+            if lens.shape != (B,):
+                raise ValueError(f'mel_lengths must be [B = {B}], got {lens.shape}')
+            if seed is not None:
+                prenet_masks = self.random_prenet_masks(B, T, seed, offset, stream=stream)
+                if not dev:
+                    prenet_masks = prenet_masks.cpu().numpy()
+            scope = None
+            if dev:
+                torch = self._torch()
+                device = torch.device('cuda', self.device)
+                self._check_device(mel_input, prenet_masks)
+                mk = lambda shape: torch.zeros(shape, dtype=torch.float32, device=device)
+                if stream is not None:
+                    scope = self._enter_stream(stream)
+            else:
+                mk = lambda shape: np.zeros(shape, dtype=np.float32)
+
+            def prepare():
+                if dev:
+                    x = mel_input.to(device=device, dtype=torch.float32).contiguous()
+                    m = None if prenet_masks is None else prenet_masks.to(device=device, dtype=torch.float32).contiguous()
+                else:
+                    x = np.ascontiguousarray(mel_input, dtype=np.float32)
+                    m = None if prenet_masks is None else np.ascontiguousarray(prenet_masks, dtype=np.float32)
+                if m is not None and tuple(m.shape) != (B, T, 2, 256):
+                    raise ValueError(f'prenet_masks must be [B, T, 2, 256] = {(B, T, 2, 256)}, got {tuple(m.shape)}')
+                return x, m, mk((B, T, 80)), mk((B, T, 80)), mk((B, T)), mk((B, T, Tin))
+
+            if scope is not None:
+                with scope:
+                    x, m, mel, dec, stop, attn = prepare()
+                self._used_on(stream, mel_input, prenet_masks, x, m, mel, dec, stop, attn)
+            else:
+                x, m, mel, dec, stop, attn = prepare()
+            sp = self._order_after_torch(stream) if dev else None
+            self._check(self._lib.tts_hip_tacotron2_forward(
+                self._h, encoded.handle, self._ptr(x), T, lens.ctypes.data_as(ctypes.c_void_p), self._ptr(m),
+                1 if precision == 'f16' else 0, self._ptr(mel), self._ptr(dec), self._ptr(stop), self._ptr(attn),
+                MEM_DEVICE if dev else MEM_HOST, sp), 'tacotron2_forward')
+        finally:
+            if own:
+                encoded.close()
+        return Tacotron2ForwardOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn)
 
     def set_decoder_mode(self, mode: str) -> None:
         """How the autoregressive decoder loop runs: 'auto' (default: the persistent weight-stationary kernel for 1 - 2 rows,

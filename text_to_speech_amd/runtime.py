@@ -222,16 +222,6 @@ class HipRuntime(Runtime):
             else:
                 mask_seed = ((self._seed ^ MASK_STREAM) & _U64, self._offset)
                 self._offset += (B * max_len * 512 + 3) // 4
-        # encoder reuse (the reference retries a sentence with fresh dropout, models/tts/tacotron2.py:160-179): inputs are
-        # recognised by CONTENT -- host inputs by their bytes, device inputs by comparing them on the device with the runtime's
-        # own copy of the batch that was encoded (an address / version key is not enough: the caching allocator hands the
-        # address of a freed token tensor to the next sentence's tensor of the same shape)
-        if dev:
-            key = self._device_key(tokens, speaker)
-        else:
-            spk_np = None if speaker is None else (speaker.detach().cpu().numpy() if _is_torch_cuda(speaker) else np.asarray(speaker))
-            key = ('host', tokens.shape, tokens.astype(np.int32).tobytes(),
-                   None if spk_np is None else spk_np.astype(np.float32).tobytes())
         if row_mask_seeds is not None and not hasattr(self.engine, 'tacotron2_encode'):
             return self.engine.tacotron2_infer(
                 tokens, speaker=speaker, max_len=max_len, early_stopping=bool(early_stopping),
@@ -244,6 +234,73 @@ class HipRuntime(Runtime):
                 tokens, speaker=speaker, max_len=max_len, early_stopping=bool(early_stopping),
                 prenet_masks=prenet_masks, attn_mask_win_len=attn_mask_win_len, attn_mask_offset=int(attn_mask_offset or 0),
                 precision=precision or self.synthesizer_precision)
+        encoded = self._encoded_batch(tokens, speaker)
+        try:
+            return self.engine.tacotron2_decode(
+                encoded, max_len=max_len, early_stopping=bool(early_stopping), prenet_masks=prenet_masks,
+                attn_mask_win_len=attn_mask_win_len, attn_mask_offset=int(attn_mask_offset or 0),
+                precision=precision or self.synthesizer_precision,
+                **({'mask_seed': mask_seed} if row_mask_seeds is None else {'row_mask_seeds': row_mask_seeds}))
+        except Exception:
+            # a failed decode may have been caused by the encoded batch itself (e.g. the encoder's block exchange timed out and
+            # left its status in the buffer): a retry must run the encoder again, not reuse it
+            self._drop_encoded()
+            raise
+
+    # ------------------------------------------------------------------ Tacotron2.call (tacotron2_arch.py:806-849)
+    def tacotron2_forward(self, inputs, mel_input, mel_lengths=None, *, prenet_masks=None, deterministic=False, seed=None,
+                          precision=None):
+        """Teacher-forced pass: `inputs` as for `tacotron2_infer` (tokens or (tokens, speaker)), `mel_input` [B, T, 80]
+        already shifted (frame 0 the zero go-frame), `mel_lengths` [B].  Dropout as in `tacotron2_infer`: explicit
+        `prenet_masks`, `deterministic=True`, `seed=` (offset 0 of that seed's mask stream) or, by default, the runtime's
+        seed at its running offset, which the call advances by the B * T * 512 values it draws.  The pass runs on the
+        runtime's one kept EncodedBatch, as `tacotron2_infer` does (the encoder runs into it unless it already holds these
+        tokens), so neither call costs the other its cached chunk graphs.  Unknown keywords are an error: a misspelt
+        `deterministic` must not draw dropout unnoticed.  Returns the engine's Tacotron2ForwardOutput."""
+        if isinstance(inputs, (tuple, list)):
+            tokens, speaker = inputs[0], (inputs[1] if len(inputs) > 1 else None)
+        else:
+            tokens, speaker = inputs, None
+        if not _is_torch_cuda(tokens):
+            tokens = np.asarray(tokens)
+        if tokens.ndim == 1:
+            tokens = tokens[None]
+        if len(mel_input.shape) == 2:
+            mel_input = mel_input[None]
+        B, T = int(mel_input.shape[0]), int(mel_input.shape[1])
+        draw = {}
+        if prenet_masks is None and not deterministic:
+            if seed is not None:
+                draw = {'seed': (int(seed) ^ MASK_STREAM) & _U64, 'offset': 0}
+            else:
+                draw = {'seed': (self._seed ^ MASK_STREAM) & _U64, 'offset': self._offset}
+                self._offset += (B * T * 512 + 3) // 4
+        precision = precision or self.synthesizer_precision
+        if not hasattr(self.engine, 'tacotron2_encode'):        # an engine object without the split entry points
+            return self.engine.tacotron2_forward(tokens, mel_input, mel_lengths, speaker=speaker, prenet_masks=prenet_masks,
+                                                 precision=precision, **draw)
+        encoded = self._encoded_batch(tokens, speaker)
+        try:
+            return self.engine.tacotron2_forward(encoded, mel_input, mel_lengths, prenet_masks=prenet_masks,
+                                                 precision=precision, **draw)
+        except Exception:
+            self._drop_encoded()            # as in tacotron2_infer: a retry must run the encoder again
+            raise
+
+    def _encoded_batch(self, tokens, speaker):
+        """The runtime's one EncodedBatch, holding `tokens` (+ `speaker`): kept as it is when it already does, else the
+        encoder runs again INTO it.  Encoder reuse (the reference retries a sentence with fresh dropout,
+        models/tts/tacotron2.py:160-179): inputs are recognised by CONTENT -- host inputs by their bytes, device inputs by
+        comparing them on the device with the runtime's own copy of the batch that was encoded (an address / version key is
+        not enough: the caching allocator hands the address of a freed token tensor to the next sentence's tensor of the same
+        shape)."""
+        dev = _is_torch_cuda(tokens)
+        if dev:
+            key = self._device_key(tokens, speaker)
+        else:
+            spk_np = None if speaker is None else (speaker.detach().cpu().numpy() if _is_torch_cuda(speaker) else np.asarray(speaker))
+            key = ('host', tokens.shape, tokens.astype(np.int32).tobytes(),
+                   None if spk_np is None else spk_np.astype(np.float32).tobytes())
         if self._encoded is not None and (self._encoded[0] is key if dev else self._encoded[0] == key):
             self.encoder_reuses += 1
         elif self._encoded is not None:
@@ -258,17 +315,7 @@ class HipRuntime(Runtime):
                 raise
         else:
             self._encoded = (key, self.engine.tacotron2_encode(tokens, speaker=speaker))
-        try:
-            return self.engine.tacotron2_decode(
-                self._encoded[1], max_len=max_len, early_stopping=bool(early_stopping), prenet_masks=prenet_masks,
-                attn_mask_win_len=attn_mask_win_len, attn_mask_offset=int(attn_mask_offset or 0),
-                precision=precision or self.synthesizer_precision,
-                **({'mask_seed': mask_seed} if row_mask_seeds is None else {'row_mask_seeds': row_mask_seeds}))
-        except Exception:
-            # a failed decode may have been caused by the encoded batch itself (e.g. the encoder's block exchange timed out and
-            # left its status in the buffer): a retry must run the encoder again, not reuse it
-            self._drop_encoded()
-            raise
+        return self._encoded[1]
 
     def _device_key(self, tokens, speaker):
         """Key of a device token batch: the cached key itself when the contents equal the batch it was made from (one tiny

@@ -29,6 +29,27 @@ def _to_numpy(x):
     return x.detach().cpu().numpy() if hasattr(x, 'detach') else np.asarray(x)
 
 
+def attention_durations(attention, length=None):
+    """Per-token durations from the alignments of one utterance: `attention` [T, Tin] -> int64 [Tin], durations[i] = number
+    of frames t < length (default T) whose attention argmax (first index on ties) is token i.  They sum to `length`."""
+    att = _to_numpy(attention)
+    if att.ndim != 2:
+        raise ValueError(f'attention must be [T, Tin], got {att.shape}')
+    n = att.shape[0] if length is None else int(length)
+    if not 0 <= n <= att.shape[0]:
+        raise ValueError(f'length {n} is outside [0, T = {att.shape[0]}]')
+    return np.bincount(att[:n].argmax(axis=1), minlength=att.shape[1]).astype(np.int64)
+
+
+def shift_mel_target(mel):
+    """Decoder input of a teacher-forced pass for the target `mel` [F, 80]: the zero go-frame, then target frames 0 .. F - 2
+    (the reference's prepare_data, models/tts/tacotron2.py:243-259: pad(mel, [(1, 0), (0, 0)])[:-1], length F)."""
+    mel = np.asarray(_to_numpy(mel), dtype=np.float32)
+    if mel.ndim != 2 or mel.shape[0] < 1:
+        raise ValueError(f'mel must be [frames >= 1, n_mel], got {mel.shape}')
+    return np.concatenate([np.zeros((1, mel.shape[1]), np.float32), mel[:-1]], axis=0)
+
+
 class Tacotron2:
     rate = 22050
 
@@ -64,6 +85,36 @@ class Tacotron2:
         return self._vocode_and_finish(part, callbacks=callbacks, predicted=predicted, return_output=return_output,
                                        vocoder=vocoder, silence_time=silence_time, vocoder_config=vocoder_config,
                                        reduce_noise=reduce_noise, trim_silence=trim_silence, utterance=utterance, **kwargs)
+
+    def teacher_forced(self, text, mel=None, audio=None, *, embeddings=None, deterministic=True, **load_kwargs):
+        """The model's mel for exactly the frames of a recording of `text` (Tacotron2.call, teacher forced): `mel` [F, 80]
+        is the target, or `audio` (a file name or a waveform) goes through `audio.load_mel` on the model's engine with
+        `load_kwargs`.  Returns {'text', 'cleaned', 'mel' [F, 80] (ground-truth aligned), 'decoder_output' [F, 80],
+        'stop_tokens' [F], 'attention' [F, Tin], 'durations' [Tin] (frames per token, summing to F)}.  Needs a runtime with
+        `tacotron2_forward` (HipRuntime) behind the model."""
+        forward = getattr(self.compiled_infer, 'tacotron2_forward', None)
+        if forward is None:
+            raise ValueError('teacher_forced needs a runtime with tacotron2_forward (HipRuntime) behind the model')
+        if (mel is None) == (audio is None):
+            raise ValueError('pass exactly one of mel and audio')
+        if mel is None:
+            from .audio import load_mel
+            mel = load_mel(audio, engine=getattr(self.compiled_infer, 'engine', None), **load_kwargs)
+        mel = np.asarray(_to_numpy(mel), dtype=np.float32)
+        if mel.ndim == 3 and mel.shape[0] == 1:
+            mel = mel[0]
+        cleaned = self.clean_text(text)
+        tokens = np.asarray(self.encode_text(cleaned, cleaned=True), dtype=np.int32)
+        if tokens.size == 0:
+            raise ValueError('the text encodes to no token')
+        mel_input = shift_mel_target(mel)
+        n = mel_input.shape[0]
+        inputs = tokens[None] if embeddings is None else (tokens[None], np.asarray(embeddings, np.float32)[None])
+        out = forward(inputs, mel_input[None], np.asarray([n], np.int32), deterministic=deterministic)
+        attention = _to_numpy(out.attention_weights)[0, :n]
+        return {'text': text, 'cleaned': cleaned, 'mel': _to_numpy(out.mel)[0, :n],
+                'decoder_output': _to_numpy(out.decoder_output)[0, :n], 'stop_tokens': _to_numpy(out.stop_tokens)[0, :n],
+                'attention': attention, 'durations': attention_durations(attention, n)}
 
     # `infer` = `_synthesize` (text -> mels; the autoregressive, latency-bound half) followed by `_vocode_and_finish`
     # (mels -> audio, callbacks; the throughput-bound half).  They are separate so that `stream(overlap=True)` can run
@@ -569,6 +620,11 @@ class SV2TTSTacotron2(Tacotron2):
         if embeddings is None or isinstance(embeddings, (int, str, dict)):
             embeddings = self.select_embedding(embeddings)
         return super().infer(text, embeddings=embeddings, **kwargs)
+
+    def teacher_forced(self, text, mel=None, audio=None, *, embeddings=0, **kwargs):
+        if embeddings is None or isinstance(embeddings, (int, str, dict)):
+            embeddings = self.select_embedding(embeddings)
+        return super().teacher_forced(text, mel, audio, embeddings=embeddings, **kwargs)
 
     def _infer_overlapped(self, inputs, *, embeddings=0, **kwargs):
         if embeddings is None or isinstance(embeddings, (int, str, dict)):
