@@ -496,6 +496,20 @@ int tts_hip_resample(tts_hip_engine* e, const float* audio, int B, int N, const 
                      float* out, int M, int mem);
 int tts_hip_resample_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate,
                            int target_rate, float* out, int M, void* stream);
+/* Test hooks (no effect on later calls; used by tests/).
+ * resample_probe takes the arguments of tts_hip_resample (and refuses the same ones; rate == target_rate, which runs no
+ *   transform, as well), forms the same groups and runs the same launches up to the end of the forward chain, and copies what
+ *   stands in the workspace there to `spectrum` [B][N / 2 + 1][2] (fp32 re, im; follows `mem`): row b holds bins
+ *   0 .. lengths[b] / 2 of rfft(audio[b, :lengths[b]]), zeros beyond.
+ * resample_fft_probe runs the complex fp32 FFT every chain is made of on `lines` lines of 2^logL points, `in` -> `out`
+ *   [lines][2^logL][2] (HOST memory, blocking), 6 <= logL <= 25, lines * 2^logL * 8 < 2^31; anything else is TTS_HIP_EINVAL,
+ *   launches nothing and leaves `out` as it was.  Up to 2^13 points a line is transformed in natural order.  Above, the
+ *   forward transform (inverse = 0) of a line in natural order leaves bin k2 + L2 * k1 (L2 = 2^logL / 8192, k2 < L2,
+ *   k1 < 8192) at k2 * 8192 + k1, and the inverse transform (inverse != 0; exponent +, not scaled by 1 / L) takes its
+ *   input in that order and returns the natural one.                                                                     */
+int tts_hip_resample_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate, int target_rate,
+                           float* spectrum, int M, int mem);
+int tts_hip_resample_fft_probe(tts_hip_engine* e, const float* in, int lines, int logL, int inverse, float* out);
 
 /* ---- measurement hooks (used by bench.py; no effect on results) -------------------------------------------------
  * Average duration in microseconds of the dominant kernel's launches (HIP events on the engine's stream) since the

@@ -209,6 +209,15 @@ REFUSALS = [
     ('silence', (), dict(SIL_OK, method=2, min_silence=1e9), ['is shorter than the window w = 22050000000000']),
     ('silence', (), dict(SIL_OK, overlap=1), ['out overlaps audio']),
     ('silence', (), dict(SIL_OK, mem=5), ['bad mem kind 5']),
+    # the FFT probe of the resampling chains (behind the rest: the ids of the cases above stay what they were)
+    ('resample_fft', (), dict(lines=1, logL=6, null='audio'), ['bad argument']),
+    ('resample_fft', (), dict(lines=1, logL=6, null='out'), ['bad argument']),
+    ('resample_fft', (), dict(lines=1, logL=5), ['logL = 5 outside [6, 25]']),
+    ('resample_fft', (), dict(lines=1, logL=26), ['logL = 26 outside [6, 25]']),
+    ('resample_fft', (), dict(lines=0, logL=10), ['lines = 0 < 1']),
+    ('resample_fft', (), dict(lines=-3, logL=10), ['lines = -3 < 1']),
+    ('resample_fft', (), dict(lines=8, logL=25), ['lines = 8 x 2^25 points too large for 31-bit offsets']),
+    ('resample_fft', (), dict(lines=(1 << 31) - 1, logL=25), ['too large for 31-bit offsets']),
 ]
 
 
@@ -243,6 +252,11 @@ def test_the_31_bit_limits_at_the_first_batch_that_crosses_them(checker):
     _refused(checker, 'resample', ['(M 2097152) too large for 31-bit offsets'], B=256, N=1 << 20, rate=1, target_rate=2, M=1 << 21)
     assert _accepted(checker, 'resample', B=255, N=1 << 21, rate=2, target_rate=1, M=1 << 20)
     _refused(checker, 'resample', ['too large for 31-bit offsets'], B=256, N=1 << 21, rate=2, target_rate=1, M=1 << 20)
+    # the FFT probe: lines of 2^logL complex fp32 points, 8 bytes each
+    for logL in (6, 13, 22, 25):
+        most = (LIM31 - 1) // (8 << logL)
+        assert _accepted(checker, 'resample_fft', lines=most, logL=logL) == [[most * (8 << logL)]]
+        _refused(checker, 'resample_fft', [f'lines = {most + 1} x 2^{logL} points too large'], lines=most + 1, logL=logL)
     # remove_silence: the rows, and B as a grid dimension
     assert _accepted(checker, 'silence', **dict(SIL_OK, B=31, N=1 << 24))
     _refused(checker, 'silence', ['B = 32 x N = 16777216 too large'], **dict(SIL_OK, B=32, N=1 << 24))
@@ -265,6 +279,7 @@ def test_refusal_precedence(checker):
       trim_silence    arguments, window_length, mode, threshold / margins, mem kind, lengths[b], 31-bit limits
       resample        arguments, rates, N, M against 2^24, M < 1, M != int(..), 31-bit limits, per row (lengths[b], then what it
                       resamples to), mem kind
+      fft probe       arguments, logL, lines, 31-bit limit
       remove_silence  arguments, method, mode, mode 3 without rms, rate, size limits, lengths[b], threshold, rms settings,
                       min_silence, mean-window settings, out overlaps audio, mem kind"""
     _refused(checker, 'reduce_noise', ['noise_len = 0'], (0, 5), N=100, noise_len=0)
@@ -277,6 +292,8 @@ def test_refusal_precedence(checker):
     _refused(checker, 'resample', ['31-bit'], (0,) * 256, N=1 << 21, rate=2, target_rate=1, M=1 << 20)
     _refused(checker, 'resample', ['lengths[0] = 1 resamples to 0'], (1, 301), N=300, rate=3, target_rate=2, M=200)
     _refused(checker, 'resample', ['lengths[1] = 0'], (300, 0), N=300, rate=3, target_rate=2, M=200, mem=9)
+    _refused(checker, 'resample_fft', ['logL = 30'], lines=0, logL=30)
+    _refused(checker, 'resample_fft', ['lines = 0'], lines=0, logL=25)
     _refused(checker, 'silence', ['mode 3 (remove)'], **dict(SIL_OK, mode=3, method=1, rate=0))
     _refused(checker, 'silence', ['too large'], (0, 5), **dict(SIL_OK, N=(1 << 24) + 1))
     _refused(checker, 'silence', ['lengths[0] = 0'], (0, 5), **dict(SIL_OK, method=2, threshold=0))

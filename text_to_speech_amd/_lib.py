@@ -110,6 +110,8 @@ SIGNATURES = {
     'tts_hip_mel_fn_run_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tts_hip_mel_fn_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int]),
     'tts_hip_resample_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'tts_hip_resample_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
+    'tts_hip_resample_fft_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

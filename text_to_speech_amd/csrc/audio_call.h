@@ -191,6 +191,19 @@ inline int rs_check(const char* who, const float* audio, int B, int N, const int
     return audio_mem_check(who, mem, msg, n);
 }
 
+constexpr int RS_FFT_MIN_LOG = 6, RS_FFT_MAX_LOG = 25;     // transform lengths rs_lens can ask for (N, M <= 2^24)
+
+// tts_hip_resample_fft_probe -- order: pointers, logL, lines, the 31-bit limit of the staged lines
+inline int rs_fft_probe_check(const char* who, const float* in, int lines, int logL, const float* out, char* msg, size_t n) {
+    if (!in || !out) return audio_refuse(msg, n, who, "bad argument");
+    if (logL < RS_FFT_MIN_LOG || logL > RS_FFT_MAX_LOG)
+        return audio_refuse(msg, n, who, "logL = %d outside [%d, %d]", logL, RS_FFT_MIN_LOG, RS_FFT_MAX_LOG);
+    if (lines < 1) return audio_refuse(msg, n, who, "lines = %d < 1", lines);
+    if (((long long)lines << logL) * 8 >= kAudioLim31)
+        return audio_refuse(msg, n, who, "lines = %d x 2^%d points too large for 31-bit offsets", lines, logL);
+    return TTS_HIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- remove_silence (silence.hip)
 constexpr int SIL_TILE = 2048;               // samples per workgroup of the tile kernels (256 threads x 8 consecutive)
 

@@ -24,8 +24,9 @@
 // (noise_len; window_length threshold add_start add_end mode; rate target_rate M; method mode rate threshold min_silence
 // block_size replace_by min_voice_time).  First line "<status> <message>"; when the call is accepted the geometry the check
 // derived: reduce_noise "Fr NP Frn NQ total", trim "W Wp Cst", silence "NT NB cap w total", resample one line
-// "logf logi M_b" per row (tests/test_audio_call.py compares them with a Python restatement).  KIND mel_fn: the plan check
-// and the call check of a mel plan (mel_cfg_check, then mel_call_check); settings mel_kind (the config's kind) sampling_rate n_mel_channels
+// "logf logi M_b" per row (tests/test_audio_call.py compares them with a Python restatement).  KIND resample_fft: the check
+// of tts_hip_resample_fft_probe (settings lines logL, null=audio,out); accepted: the bytes of the staged lines.  KIND
+// mel_fn: the plan check and the call check of a mel plan (mel_cfg_check, then mel_call_check); settings mel_kind (the config's kind) sampling_rate n_mel_channels
 // filter_length hop_length win_length normalize_mode mel_fmin mel_fmax pre_emph, window=I:VALUE (an explicit window of ones
 // with window[I] = VALUE; else NULL) and null=cfg,fn,audio,out (fn: the call gets no plan).  First line as above, from
 // whichever check refuses first; accepted: "K4 Kpad NB MAGK gathered", "Fr Fout PW NP total" and "F_b ..." (the result's
@@ -138,7 +139,7 @@ static int print_audio_call(int argc, char** argv) {
                                     {"replace_by", 0}, {"min_voice_time", 0}, {"overlap", 0}, {"mel_kind", 0},
                                     {"sampling_rate", 22050}, {"n_mel_channels", 80}, {"filter_length", 1024},
                                     {"hop_length", 256}, {"win_length", 1024}, {"normalize_mode", 0}, {"mel_fmin", 0},
-                                    {"mel_fmax", 8000}, {"pre_emph", 0}};
+                                    {"mel_fmax", 8000}, {"pre_emph", 0}, {"lines", 1}, {"logL", 6}};
     bool null_cfg = false, null_fn = false;
     int window_at = -1;
     double window_value = 1;
@@ -194,6 +195,11 @@ static int print_audio_call(int argc, char** argv) {
             const RsLens l = rs_lens(lens[b], mlens[b]);
             printf("%d %d %d\n", l.logf, l.logi, mlens[b]);
         }
+    } else if (kind == "resample_fft") {
+        const int rc = rs_fft_probe_check("who", audio, (int)v["lines"], (int)v["logL"], out, why, sizeof why);
+        printf("%d %s\n", rc, why);
+        if (rc) return 0;
+        printf("%lld\n", ((long long)v["lines"] << (int)v["logL"]) * 8);
     } else if (kind == "silence") {
         SilCall c;
         const int rc = sil_check("who", audio, B, N, lp, (int)v["method"], (int)v["mode"], (int)v["rate"], v["threshold"],

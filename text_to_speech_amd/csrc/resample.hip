@@ -326,9 +326,10 @@ hipError_t rs_fft(RsPass p, int logL, int lines, const float2* tw, hipStream_t s
     return hipGetLastError();
 }
 
-// device pointers only; arguments validated by rs_check
+// device pointers only; arguments validated by rs_check.  spectra (tts_hip_resample_probe; [B][N // 2 + 1] bins, device): every
+// group stops after its forward chain and its rows' bins 0 .. N_b // 2 go there, zeros behind them; d_out is not touched
 int resample_run(tts_hip_engine* e, const float* d_in, int B, int N, const std::vector<int>& lens, const std::vector<int>& mlens,
-                 float* d_out, int M) {
+                 float* d_out, int M, float2* spectra = nullptr) {
     ResampleDev& r = e->resamp;
     if (int rc = rs_twiddles(e)) return rc;
     hipStream_t st = e->stream;
@@ -365,6 +366,8 @@ int resample_run(tts_hip_engine* e, const float* d_in, int B, int N, const std::
         for (int b : g.second) info_h[k++] = b;
     if (int rc = stage_row_info(e, d_info)) return rc;
     const float2* tw = (const float2*)r.tw.p;
+    const size_t sp_ld = (size_t)N / 2 + 1;
+    if (spectra) HIPCHK(e, hipMemsetAsync(spectra, 0, (size_t)B * sp_ld * 8, st));
     int first = 2 * B, gi = 0;
     for (auto& g : groups) {
         const int G = (int)g.second.size(), logf = g.first.first, logi = g.first.second;
@@ -384,12 +387,21 @@ int resample_run(tts_hip_engine* e, const float* d_in, int B, int N, const std::
         // rfft_N: FFT of signal and filter lines, then the inverse FFT of their product -> X (bins 0 .. N_b // 2)
         HIPCHK(e, (rs_fft<LD_FWD_IN, ST_PLAIN, false>(p, logf, 2 * G, tw, st)));
         HIPCHK(e, (rs_fft<LD_PROD, ST_FWD_OUT, true>(p, logf, G, tw, st)));
-        // irfft_M of the fixed-up spectrum: the same chain on L_inv, the stage buffer reused
-        HIPCHK(e, (rs_fft<LD_INV_IN, ST_PLAIN, false>(p, logi, 2 * G, tw, st)));
-        HIPCHK(e, (rs_fft<LD_PROD, ST_INV_OUT, true>(p, logi, G, tw, st)));
+        if (spectra) {                                  // the probe's copy-out, in place of the second chain
+            for (int i = 0; i < G; ++i) {
+                const int b = g.second[i];
+                HIPCHK(e, hipMemcpyAsync(spectra + (size_t)b * sp_ld, p.X + (size_t)i * p.xstride, ((size_t)lens[b] / 2 + 1) * 8,
+                                         hipMemcpyDeviceToDevice, st));
+            }
+        } else {
+            // irfft_M of the fixed-up spectrum: the same chain on L_inv, the stage buffer reused
+            HIPCHK(e, (rs_fft<LD_INV_IN, ST_PLAIN, false>(p, logi, 2 * G, tw, st)));
+            HIPCHK(e, (rs_fft<LD_PROD, ST_INV_OUT, true>(p, logi, G, tw, st)));
+        }
         first += G;
         ++gi;
     }
+    if (spectra) return TTS_HIP_OK;
     bool ragged = false;
     for (int b = 0; b < B; ++b) ragged |= mlens[b] != M;
     if (ragged) {
@@ -451,4 +463,56 @@ int tts_hip_resample(tts_hip_engine* e, const float* audio, int B, int N, const 
     if (int rc = io.begin()) return rc;
     if (int rc = resample_run(e, io.ptr<const float>(in), B, N, lens, mlens, io.ptr<float>(res), M)) return rc;
     return io.finish();
+}
+
+// Test hook: resample_run on the same arguments (the same groups and launches) up to the end of the forward chain, then every
+// row's rfft bins 0 .. N_b // 2 out of the workspace to `spectrum` [B][N // 2 + 1][2].
+int tts_hip_resample_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate, int target_rate,
+                           float* spectrum, int M, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    std::vector<int> lens, mlens;
+    char why[256];
+    if (int rc = rs_check("resample_probe", audio, B, N, lengths, rate, target_rate, spectrum, M, mem, lens, mlens, why, sizeof why))
+        return set_err(e, rc, "%s", why);
+    if (rate == target_rate) return set_err(e, TTS_HIP_EINVAL, "resample_probe: rate == target_rate = %d runs no transform", rate);
+    HIPCHK(e, hipSetDevice(e->device));
+    AudioStage io(e, mem);
+    const int in = io.in(audio, (size_t)B * N * 4), res = io.out(spectrum, (size_t)B * (N / 2 + 1) * 8);
+    if (int rc = io.begin()) return rc;
+    if (int rc = resample_run(e, io.ptr<const float>(in), B, N, lens, mlens, nullptr, M, io.ptr<float2>(res))) return rc;
+    return io.finish();
+}
+
+// Test hook: rs_fft<LD_PLAIN, ST_PLAIN> on `lines` lines of 2^logL complex points, host memory in and out.
+int tts_hip_resample_fft_probe(tts_hip_engine* e, const float* in, int lines, int logL, int inverse, float* out) {
+    if (!e) return TTS_HIP_EINVAL;
+    char why[256];
+    if (int rc = rs_fft_probe_check("resample_fft_probe", in, lines, logL, out, why, sizeof why)) return set_err(e, rc, "%s", why);
+    HIPCHK(e, hipSetDevice(e->device));
+    ResampleDev& r = e->resamp;
+    if (int rc = rs_twiddles(e)) return rc;
+    hipStream_t st = e->stream;
+    const size_t bytes = ((size_t)lines << logL) * 8;
+    Carve ws;
+    const size_t off_info = ws.take(((size_t)lines + 2) * 4), off_lines = ws.take(bytes);
+    HIPCHK(e, r.ws.ensure(ws.o));
+    int* d_info = (int*)((char*)r.ws.p + off_info);
+    // the kernel reads rows / nlen / mlen whatever it loads: every line is "row 0" of one sample in, one out
+    e->audio_info_h.assign((size_t)lines + 2, 0);
+    e->audio_info_h[lines] = e->audio_info_h[lines + 1] = 1;
+    if (int rc = stage_row_info(e, d_info)) return rc;
+    RsPass p{};
+    p.G = lines;
+    p.rows = d_info;
+    p.nlen = d_info + lines;
+    p.mlen = d_info + lines + 1;
+    p.U = (float2*)((char*)r.ws.p + off_lines);
+    HIPCHK(e, hipMemcpyAsync(p.U, in, bytes, hipMemcpyHostToDevice, st));
+    if (inverse)
+        HIPCHK(e, (rs_fft<LD_PLAIN, ST_PLAIN, true>(p, logL, lines, (const float2*)r.tw.p, st)));
+    else
+        HIPCHK(e, (rs_fft<LD_PLAIN, ST_PLAIN, false>(p, logL, lines, (const float2*)r.tw.p, st)));
+    HIPCHK(e, hipMemcpyAsync(out, p.U, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    return TTS_HIP_OK;
 }

@@ -1079,6 +1079,31 @@ class HipEngine:
                                lambda extras, outs: (self._ptr(lens), rate, target_rate, outs[0], M), stream)
         return out[0] if one_row else out
 
+    def resample_probe(self, audio, rate, target_rate, lengths=None):
+        """Test hook (tts_hip_resample_probe): run `resample` on the same arguments (host arrays, rate != target_rate) up to
+        the end of the forward chain -> complex64 [B, N // 2 + 1]: row b holds bins 0 .. lengths[b] // 2 of
+        rfft(audio[b, :lengths[b]]), zeros beyond.  Always batched."""
+        from .audio import resampled_length
+        audio = np.asarray(audio, dtype=np.float32)
+        B, N, lens = self._audio_rows(audio, lengths, 'resample_probe')
+        M = resampled_length(N, int(rate), int(target_rate))
+        out, = self._host_call('resample_probe', audio, B, N, [], lambda empty: (empty((B, N // 2 + 1, 2), 'float32'),),
+                               lambda extras, outs: (self._ptr(lens), int(rate), int(target_rate), outs[0], M))
+        return out.view(np.complex64)[..., 0]
+
+    def resample_fft_probe(self, lines, inverse=False):
+        """Test hook (tts_hip_resample_fft_probe): the complex fp32 FFT of the resampling chains on `lines` [n, 2^logL]
+        (complex64, 6 <= logL <= 25) -> complex64 [n, 2^logL], unscaled.  Up to 2^13 points in natural order; above, the
+        forward transform leaves bin k2 + L2 * k1 (L2 = 2^logL / 8192) at k2 * 8192 + k1 and the inverse takes that order
+        and returns the natural one."""
+        a = np.ascontiguousarray(lines, dtype=np.complex64)
+        if a.ndim != 2 or a.shape[1] < 1 or a.shape[1] & (a.shape[1] - 1):
+            raise ValueError(f'resample_fft_probe: lines must be [n, 2^logL], got {a.shape}')
+        out = np.empty_like(a)
+        self._check(self._lib.tts_hip_resample_fft_probe(self._h, self._ptr(a), int(a.shape[0]), int(a.shape[1]).bit_length() - 1,
+                                                         int(bool(inverse)), self._ptr(out)), 'resample_fft_probe')
+        return out
+
     def trim_silence(self, audio, rate=None, lengths=None, threshold=0.1, window_length=0.2, add_start=0, add_end=1.5,
                      mode='start_end'):
         """Window-method silence trimming (utils/audio/audio_processing.py:274-370: power 2, triangular window, adaptive
