@@ -169,7 +169,19 @@ int tts_hip_tacotron2_infer_f16(tts_hip_engine* e, const int32_t* tokens, int B,
  * tts_hip_encoded_free; several may be alive, e.g. the next sentence's encoder running ahead); `decode` may be called any
  * number of times on it (the retry loop of models/tts/tacotron2.py:160-179 re-runs only the decoder with new dropout
  * masks) and synchronizes `stream` before it returns, because the loop's exit is data dependent and `steps_run` is a host
- * value.  tts_hip_tacotron2_infer == encode + decode.                                                                  */
+ * value.  tts_hip_tacotron2_infer == encode + decode.
+ *
+ * Why a Tacotron2 call is refused (csrc/taco_call.h: the two checks every entry point below and tts_hip_tacotron2_infer* go
+ * through; a NULL handle is TTS_HIP_EINVAL without a message).  Before any GPU work, first match wins, the message is
+ * "<symbol without tts_hip_>: <reason>":
+ *   an encoder run (encode, reencode, probe_encoder, the first half of infer*): bad mem kind; weights not finalized
+ *     (TTS_HIP_ENOTREADY); tokens NULL, B outside [1, 1024] or Tin outside [1, 4096]; a model with speaker embeddings and
+ *     speaker NULL.
+ *   a run on an encoded batch (decode*, forward, the second half of infer*): precision not 0 / 1; bad mem kind; weights not
+ *     finalized (TTS_HIP_ENOTREADY); encoded batch NULL or empty; encoded batch of another width than the handle's weights;
+ *     keys / offsets NULL (decode_rows_seeded), mel_input / mel_lengths NULL (forward); max_len or T < 1; and for forward
+ *     B * T > 65536, then mel_lengths[b] outside [1, T].
+ * infer* passes both checks, in that order, before its encoder is enqueued.                                             */
 typedef struct tts_hip_encoded tts_hip_encoded;
 int tts_hip_waveglow_infer_async(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
                                  float* audio, int precision, void* stream);
@@ -202,10 +214,9 @@ int tts_hip_tacotron2_decode_rows_seeded(tts_hip_engine* e, const tts_hip_encode
  * Outputs (any may be NULL): decoder_output [B, T, 80] = where(t <= mel_lengths[b], frame, 0), mel = decoder_output +
  * postnet(decoder_output) under that mask, stop_tokens [B, T] = sigmoid(gate), unmasked, attention [B, T, Tin].  Frames at
  * and past a row's length are consumed as given.  mel_input, prenet_masks and the outputs live where `mem` says.
- * Refused before any GPU work (csrc/taco_forward_call.h; first match wins): precision, mem kind, weights not finalized
- * (TTS_HIP_ENOTREADY), NULL or foreign encoded batch, NULL mel_input / mel_lengths, T < 1, B * T > 65536, mel_lengths[b]
- * outside [1, T].  Synchronizes `stream` (NULL: the handle's) before returning, like `decode`; a following
- * tts_hip_tacotron2_infer* / decode call on the handle is unaffected.                                                   */
+ * Refused as the block below says; its own limits are B * T <= 65536 and mel_lengths[b] in [1, T].  Synchronizes `stream`
+ * (NULL: the handle's) before returning, like `decode`; a following tts_hip_tacotron2_infer* / decode call on the handle is
+ * unaffected.                                                                                                           */
 int tts_hip_tacotron2_forward(tts_hip_engine* e, const tts_hip_encoded* encoded, const float* mel_input, int T,
                               const int32_t* mel_lengths, const float* prenet_masks, int precision, float* mel,
                               float* decoder_output, float* stop_tokens, float* attention, int mem, void* stream);

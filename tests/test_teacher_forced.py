@@ -1,6 +1,6 @@
 """CPU: the teacher-forced pass (Tacotron2.call) -- its numpy restatement against the free-running oracle, the bound the GPU
-tests use against planted mistakes, the call's front end (csrc/taco_forward_call.h) under ASan / UBSan, and the host logic of
-Tacotron2.teacher_forced.
+tests use against planted mistakes, and the host logic of Tacotron2.teacher_forced.  (The call's front end, csrc/taco_call.h,
+is tested with its siblings in tests/test_taco_call.py.)
 
 Measured here (synth_tacotron2(seed=1234), B = 3, 21 / 14 / 5 tokens, T = 70, mel_lengths 70 / 37 / 1), as dec / stop / attention:
   self-fed restatement vs tacotron2_ref.infer      1.3e-6 / 4.5e-8 / 0.0 (mel 1.6e-6)
@@ -9,9 +9,6 @@ Measured here (synth_tacotron2(seed=1234), B = 3, 21 / 14 / 5 tokens, T = 70, me
   planted: mask < for <=                           0.82 / 0 / 0
   planted: dropout mask of step t - 1              0.41 / 2.0e-2 / 1.0e-1
 """
-import os
-import shutil
-import subprocess
 from collections import namedtuple
 
 import numpy as np
@@ -19,9 +16,6 @@ import pytest
 
 import teacher_forced_ref as tf
 from oracle import tacotron2_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'text_to_speech_amd', 'csrc')
 
 LENS, T, MEL_LENGTHS = (21, 14, 5), 70, (70, 37, 1)
 
@@ -89,77 +83,6 @@ def test_semantics_of_the_restatement(case, refs):
             assert np.any(r32.decoder_output[b, n] != 0)
     assert np.all((r32.stop_tokens > 0) & (r32.stop_tokens < 1))
     np.testing.assert_allclose(r32.attention_weights.sum(-1), 1.0, atol=1e-5)
-
-
-# ------------------------------------------------------------------------------------------------------------ front end
-@pytest.fixture(scope='module')
-def checker():
-    if shutil.which('g++') is None:
-        pytest.skip('no g++')
-    subprocess.run(['bash', os.path.join(CSRC, 'build_host_asan.sh')], check=True, capture_output=True)
-    return os.path.join(CSRC, 'build_host_asan', 'ttsw_check_asan')
-
-
-def _front(exe, *args):
-    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1')
-    r = subprocess.run([exe, '--taco-forward'] + [str(a) for a in args], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0, f'sanitizer report or crash (exit {r.returncode}):\n{r.stderr[-4000:]}'
-    assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr, r.stderr[-4000:]
-    lines = r.stdout.strip().splitlines()
-    rc, _, msg = lines[0].partition(' ')
-    return int(rc), msg, [int(v) for v in lines[1].split()] if len(lines) > 1 else None
-
-
-def _sizes(B, T, enc):
-    frames = B * T
-    return [frames, frames * 80, frames * 256, frames * 4096, B * ((T + 255) // 256 * 256) * (1024 + enc), frames * 81]
-
-
-EINVAL, ENOTREADY = -1, -2
-
-
-def test_front_end_refuses_by_name_before_any_gpu_work(checker):
-    refusals = [
-        (['T=4', 'precision=2', 4, 4], EINVAL, 'precision must be 0 (f32) or 1 (f16 weights), got 2'),
-        (['T=4', 'precision=-1', 4], EINVAL, 'precision must be 0 (f32) or 1 (f16 weights), got -1'),
-        (['T=4', 'mem=7', 4], EINVAL, 'bad mem kind 7'),
-        (['T=4', 'ready=0', 4], ENOTREADY, 'tacotron2 weights not finalized'),
-        (['T=4', 'null=encoded', 4], EINVAL, 'encoded batch is NULL or empty'),
-        (['T=4', 'enc=768', 4], EINVAL, 'encoded batch belongs to other weights (width 768, model 512)'),
-        (['T=4', 'null=mel', 4], EINVAL, 'mel_input or mel_lengths is NULL'),
-        (['T=4', 'null=lens', 4], EINVAL, 'mel_input or mel_lengths is NULL'),
-        (['T=0', 'B=1'], EINVAL, 'T = 0 must be at least 1'),
-        (['T=-3', 'B=1'], EINVAL, 'T = -3 must be at least 1'),
-        (['T=65537', 'B=1'], EINVAL, 'B*T too large (B = 1, T = 65537: above 65536 frames); split the batch'),
-        (['T=8193', 'B=8'], EINVAL, 'B*T too large (B = 8, T = 8193: above 65536 frames); split the batch'),
-        (['T=2147483647', 'B=1024'], EINVAL, 'B*T too large (B = 1024, T = 2147483647: above 65536 frames); split the batch'),
-        (['T=4', 4, 0, 4], EINVAL, 'mel_lengths[1] = 0 is outside [1, T = 4]'),
-        (['T=4', 4, 4, 5], EINVAL, 'mel_lengths[2] = 5 is outside [1, T = 4]'),
-        (['T=4', -1], EINVAL, 'mel_lengths[0] = -1 is outside [1, T = 4]'),
-        # first match wins: precision before everything, the frame limit before the lengths
-        (['T=0', 'precision=3', 'ready=0', 'null=encoded,mel'], EINVAL, 'precision must be 0 (f32) or 1 (f16 weights), got 3'),
-        (['T=65537', 'B=1', 'null=lens'], EINVAL, 'mel_input or mel_lengths is NULL'),
-    ]
-    for args, code, msg in refusals:
-        rc, why, sizes = _front(checker, *args)
-        assert (rc, why) == (code, 'who: ' + msg), (args, rc, why)
-        assert sizes is None
-
-
-def test_front_end_accepts_and_sizes_at_the_limits(checker):
-    for args, (B, T, enc) in [
-        (['T=1', 1], (1, 1, 512)),
-        (['T=33', 33, 17, 1], (3, 33, 512)),
-        (['T=256', 'B=2', 'precision=1', 'mem=1'], (2, 256, 512)),
-        (['T=257', 'B=2', 'enc=768', 'model_enc=768'], (2, 257, 768)),
-        (['T=65536', 'B=1'], (1, 65536, 512)),                       # the frame limit itself: G = 1 GiB
-        (['T=8192', 'B=8', 'enc=768', 'model_enc=768'], (8, 8192, 768)),
-        (['T=64', 'B=1024'], (1024, 64, 512)),
-    ]:
-        rc, why, sizes = _front(checker, *args)
-        assert (rc, why) == (0, ''), (args, rc, why)
-        assert sizes == _sizes(B, T, enc), args
-    assert _sizes(1, 65536, 512)[3] * 4 == 1 << 30
 
 
 # ------------------------------------------------------------------------------------------------------------ host logic

@@ -15,7 +15,7 @@
 #include "ttsw_host.h"      // HostTensor + the TTSW parser (host-only code, also built under ASan / UBSan)
 #include "wg_call.h"        // WgCall: one WaveGlow call, its checks and its staged table (host-only code, likewise)
 #include "audio_call.h"     // the audio calls' checks and the geometry they rest on (host-only code, likewise)
-#include "taco_forward_call.h"      // the teacher-forced Tacotron2 call's check and buffer sizes (host-only code, likewise)
+#include "taco_call.h"      // TacoEncode / TacoRun: the Tacotron2 calls, their checks and the forward pass's buffer sizes (likewise)
 
 // Growable device buffer (workspace).  Never shrinks; reallocated only when a larger request arrives.
 struct DevBuf {

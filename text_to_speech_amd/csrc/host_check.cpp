@@ -31,17 +31,21 @@
 // with window[I] = VALUE; else NULL) and null=cfg,fn,audio,out (fn: the call gets no plan).  First line as above, from
 // whichever check refuses first; accepted: "K4 Kpad NB MAGK gathered", "Fr Fout PW NP total" and "F_b ..." (the result's
 // frames per row), then "mel_fn_frames(N)" (tests/test_mel_fn_call.py).
-//        ttsw_check_asan --taco-forward [KEY=VALUE...] [LEN...]  -- the front end of a teacher-forced Tacotron2 call
-// (taco_forward_call.h) for an encoded batch of B = number of LEN rows (mel_lengths; no LEN: B from B=, every length T).
-// Settings: B= T= Tin= enc= model_enc= precision= mem= ready=0|1 and null=encoded,mel,lens.  First line "<status> <message>"
-// of taco_forward_check; when the call is accepted "frames mel_in prenet gates history proj" of taco_forward_sizes
-// (tests/test_teacher_forced.py compares them with a Python restatement).
+//        ttsw_check_asan --taco-call KIND [KEY=VALUE...] [LEN...]  -- the front end of a Tacotron2 call (taco_call.h) run as an
+// entry point named "who", KIND one of encode, decode, forward, infer (= the encode check, then the decode check on the batch the
+// encoder would fill, as tts_hip_tacotron2_infer* does).  Refused, first match wins -- encode: mem kind, weights not finalized,
+// tokens / B / Tin, speaker; decode and forward: precision, mem kind, weights not finalized, encoded batch, its width, pointers
+// (keys / offsets | mel_input / mel_lengths), max_len | T, and for forward B * T and mel_lengths[b].  Settings: B= Tin= mem=
+// ready=0|1 and null=...; encode: spk_dim=, null=tokens,speaker; decode: max_len= enc= model_enc= precision= masks=0..3
+// (TacoMasks), null=encoded,keys,offsets; forward: T= enc= model_enc= precision=, null=encoded,mel,lens, and the LEN are
+// mel_lengths (no LEN: B from B=, every length T).  First line "<status> <message>"; when a forward call is accepted "frames
+// mel_in prenet gates history proj" of taco_forward_sizes (tests/test_taco_call.py compares them with a Python restatement).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
 
 #include "audio_call.h"
-#include "taco_forward_call.h"
+#include "taco_call.h"
 #include "ttsw_host.h"
 #include "wg_call.h"
 #include "wg_plan.h"
@@ -234,44 +238,57 @@ static int print_audio_call(int argc, char** argv) {
     return 0;
 }
 
-static int print_taco_forward(int argc, char** argv) {
-    static float mel;                                                          // never read: the front end only tests the pointer
-    std::map<std::string, int> v{{"B", -1}, {"T", 1}, {"Tin", 8}, {"enc", 512}, {"model_enc", 512}, {"precision", 0},
-                                 {"mem", TTS_HIP_MEM_HOST}, {"ready", 1}};
-    bool null_enc = false, null_mel = false, null_lens = false;
+static int print_taco_call(int argc, char** argv) {
+    static float mel;                                                          // never read: the front end only tests the pointers
+    static int32_t tokens;
+    static uint64_t keys, offsets;
+    const std::string kind = argv[2];
+    std::map<std::string, int> v{{"B", -1}, {"len", 1}, {"Tin", 8}, {"enc", 512}, {"model_enc", 512}, {"precision", 0},
+                                 {"mem", TTS_HIP_MEM_HOST}, {"ready", 1}, {"spk_dim", 0}, {"masks", 0}};
+    std::string nulls;
     std::vector<int32_t> lens;
-    for (int i = 2; i < argc; ++i) {
+    for (int i = 3; i < argc; ++i) {
         const char* eq = strchr(argv[i], '=');
         if (!eq) {
             lens.push_back((int32_t)atoi(argv[i]));
             continue;
         }
-        const std::string key(argv[i], (size_t)(eq - argv[i]));
-        if (key == "null") {
-            if (strstr(eq, "encoded")) null_enc = true;
-            if (strstr(eq, "mel")) null_mel = true;
-            if (strstr(eq, "lens")) null_lens = true;
-        } else if (v.count(key)) {
-            v[key] = atoi(eq + 1);
-        } else {
-            return 2;
-        }
+        std::string key(argv[i], (size_t)(eq - argv[i]));
+        if (key == "T" || key == "max_len") key = "len";
+        if (key == "null") nulls = eq + 1;
+        else if (v.count(key)) v[key] = atoi(eq + 1);
+        else return 2;
     }
+    const auto null = [&](const char* name) { return nulls.find(name) != std::string::npos; };
     const int B = lens.empty() ? v["B"] : (int)lens.size();
-    if (lens.empty() && B > 0 && B <= (1 << 20)) lens.assign((size_t)B, (int32_t)v["T"]);
-    const TacoForwardCall c{"who", v["ready"] != 0, !null_enc, B, v["Tin"], v["enc"], v["model_enc"], null_mel ? nullptr : &mel,
-                            v["T"], null_lens || lens.empty() ? nullptr : lens.data(), v["precision"], v["mem"]};
+    if (lens.empty() && B > 0 && B <= (1 << 20)) lens.assign((size_t)B, (int32_t)v["len"]);
     char why[256] = "";
-    const int rc = taco_forward_check(c, why, sizeof why);
+    int rc = TTS_HIP_OK;
+    if (kind == "encode" || kind == "infer") {
+        const TacoEncode c{"who", v["ready"] != 0, v["spk_dim"], null("tokens") ? nullptr : &tokens, B, v["Tin"],
+                           null("speaker") ? nullptr : &mel, v["mem"], nullptr};
+        rc = taco_encode_check(c, why, sizeof why);
+    }
+    TacoRun c{};
+    if (kind != "encode" && !rc) {
+        c.who = "who", c.kind = kind == "forward" ? TACO_FORWARD : TACO_DECODE, c.model_ready = v["ready"] != 0;
+        c.has_encoded = kind == "infer" || !null("encoded"), c.B = B, c.Tin = v["Tin"], c.model_enc = v["model_enc"];
+        c.enc = kind == "infer" ? c.model_enc : v["enc"], c.len = v["len"], c.precision = v["precision"], c.mem = v["mem"];
+        c.masks = (TacoMasks)v["masks"], c.prenet_masks = &mel, c.keys = null("keys") ? nullptr : &keys;
+        c.offsets = null("offsets") ? nullptr : &offsets, c.mel_input = null("mel") ? nullptr : &mel;
+        c.mel_lengths = null("lens") || lens.empty() ? nullptr : lens.data();
+        if (kind != "decode" && kind != "forward" && kind != "infer") return 2;
+        rc = taco_run_check(c, why, sizeof why);
+    }
     printf("%d %s\n", rc, why);
-    if (rc) return 0;
-    const TacoForwardSizes z = taco_forward_sizes(c.B, c.T, c.enc);
+    if (rc || kind != "forward") return 0;
+    const TacoForwardSizes z = taco_forward_sizes(c.B, c.len, c.enc);
     printf("%lld %zu %zu %zu %zu %zu\n", z.frames, z.mel_in, z.prenet, z.gates, z.history, z.proj);
     return 0;
 }
 
 int main(int argc, char** argv) {
-    if (argc >= 2 && !strcmp(argv[1], "--taco-forward")) return print_taco_forward(argc, argv);
+    if (argc >= 3 && !strcmp(argv[1], "--taco-call")) return print_taco_call(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "--audio-call")) return print_audio_call(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wg-call")) return print_wg_call(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wn-taps")) {

@@ -1327,21 +1327,21 @@ static void encoded_layout(Arena& A, tts_hip_encoded* o, long long R, int B, int
     o->pm = A.take<float>(R * ATT);
 }
 
+// How a call's tensors travel: in from, and out to, where its `mem` says (a mem kind that passed its check)
+static hipMemcpyKind copy_in(int mem) { return mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice; }
+static hipMemcpyKind copy_out(int mem) { return mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice; }
+
 // tokens -> (mask, lengths, memory, processed memory) in `out` (its own device buffer, so several encoded utterances can
-// be alive); temporaries live in the engine workspace.  Everything is enqueued on e->stream; nothing is synchronized.
+// be alive); temporaries live in the engine workspace.  Everything is enqueued on e->stream; nothing is synchronized.  (The
+// request already passed check_encode.)
 // Test hook (tts_hip_tacotron2_probe_encoder): stop_conv = i (0 .. 2) returns right after encoder conv i with *stop_out
 // pointing at its output [B * Tin][512] in the workspace; -1 runs the whole encoder.
-static int tacotron2_encode_impl(tts_hip_engine* e, const int32_t* tokens, int B, int Tin, const float* speaker, int mem,
-                                 tts_hip_encoded* out, int stop_conv = -1, const float** stop_out = nullptr) {
+static int tacotron2_encode_impl(tts_hip_engine* e, const TacoEncode& c, tts_hip_encoded* out, int stop_conv = -1,
+                                 const float** stop_out = nullptr) {
     Tacotron2Dev& tc = e->taco;
-    if (!tc.ready) return set_err(e, TTS_HIP_ENOTREADY, "tacotron2 weights not finalized");
-    if (!tokens || !out || B <= 0 || Tin <= 0 || Tin > 4096 || B > 1024)
-        return set_err(e, TTS_HIP_EINVAL, "tacotron2_encode: bad argument");
-    if (tc.spk_dim > 0 && !speaker) return set_err(e, TTS_HIP_EINVAL, "tacotron2_encode: this model needs a speaker embedding");
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "bad mem kind %d", mem);
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    const int enc = tc.enc_dim;
+    const int B = c.B, Tin = c.Tin, enc = tc.enc_dim;
     const long long R = (long long)B * Tin;
 
     int rc;
@@ -1353,9 +1353,8 @@ static int tacotron2_encode_impl(tts_hip_engine* e, const int32_t* tokens, int B
     EncoderTmp t{};
     if ((rc = plan_workspace(e, tc.ws, 4096, [&](Arena& A) { t = encoder_tmp_layout(A, R, B, tc.spk_dim); }))) return rc;
 
-    const hipMemcpyKind kin = mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    HIPCHK(e, hipMemcpyAsync(t.tok, tokens, R * 4, kin, st));
-    if (tc.spk_dim) HIPCHK(e, hipMemcpyAsync(t.spk, speaker, (size_t)B * tc.spk_dim * 4, kin, st));
+    HIPCHK(e, hipMemcpyAsync(t.tok, c.tokens, R * 4, copy_in(c.mem), st));
+    if (tc.spk_dim) HIPCHK(e, hipMemcpyAsync(t.spk, c.speaker, (size_t)B * tc.spk_dim * 4, copy_in(c.mem), st));
     HIPCHK(e, hipMemsetAsync(t.blh, 0, blh_u64(B) * 8, st));
     HIPCHK(e, hipMemsetAsync(out->bl_err, 0, 16 * 4, st));
 
@@ -1796,44 +1795,56 @@ static int run_fused(tts_hip_engine* e, DecodeCall c, int* steps) {
     return aborted ? DEC_FALL_BACK : TTS_HIP_OK;
 }
 
+// The results of a run, from the workspace to the caller's outputs that are non-NULL, then the encoder's BiLSTM status word
+// when `read_status` (a decode whose loop already read it does not again), ONE synchronisation of e->stream, the verdict.
+static int copy_results(tts_hip_engine* e, const TacoRun& c, const tts_hip_encoded* en, const DecoderWs& ws, bool read_status) {
+    hipStream_t st = e->stream;
+    const size_t RD = (size_t)en->B * c.len;
+    const hipMemcpyKind kout = copy_out(c.mem);
+    if (c.mel) HIPCHK(e, hipMemcpyAsync(c.mel, ws.post.mel, RD * NMEL * 4, kout, st));
+    if (c.decoder_output) HIPCHK(e, hipMemcpyAsync(c.decoder_output, ws.dec_out, RD * NMEL * 4, kout, st));
+    if (c.stop_tokens) HIPCHK(e, hipMemcpyAsync(c.stop_tokens, ws.stop_out, RD * 4, kout, st));
+    if (c.attention) HIPCHK(e, hipMemcpyAsync(c.attention, ws.attn_hist, RD * en->Tin * 4, kout, st));
+    if (c.lengths) HIPCHK(e, hipMemcpyAsync(c.lengths, ws.lengths, (size_t)en->B * 4, kout, st));
+    int bl_err = 0;
+    if (read_status) HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    return check_bilstm_status(e, bl_err);
+}
+
 // Autoregressive loop + postnet from an encoded batch.  Enqueued on e->stream; synchronizes it before returning (the
-// loop's exit is data dependent and `steps_run` / the BiLSTM status are host values).
-static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, int max_len, int early_stop,
-                                 const float* prenet_masks, int win_len, int win_offset, float* mel,
-                                 float* decoder_output, float* stop_tokens, float* attention, int32_t* lengths,
-                                 int32_t* steps_run, int mem, bool half_w, const uint64_t* mask_seed = nullptr,
-                                 const uint64_t* row_keys = nullptr, const uint64_t* row_offsets = nullptr) {
+// loop's exit is data dependent and `steps_run` / the BiLSTM status are host values).  (The request already passed check_run.)
+static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, const TacoRun& c) {
     Tacotron2Dev& tc = e->taco;
-    if (!tc.ready) return set_err(e, TTS_HIP_ENOTREADY, "tacotron2 weights not finalized");
-    if (!en || !en->buf.p || en->B <= 0 || max_len <= 0) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode: bad argument");
-    if (en->enc != tc.enc_dim) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode: encoded batch belongs to other weights");
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "bad mem kind %d", mem);
     int rc;
+    const bool half_w = c.precision == 1;
     if (half_w && (rc = tacotron2_build_f16(e))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    const int B = en->B, Tin = en->Tin;
+    const int B = en->B, Tin = en->Tin, max_len = c.len;
     const size_t RD = (size_t)B * max_len;           // decoder rows
 
     bool backed_off = false;
     const DecMachine planned = choose_decoder_machine(e, B, Tin, &backed_off);
-    const bool with_masks = prenet_masks != nullptr || mask_seed != nullptr || row_keys != nullptr;
+    const bool with_masks = c.masks != TACO_MASKS_NONE;
     DecoderWs ws{};
     if ((rc = plan_workspace(e, tc.ws, 4096, [&](Arena& A) { ws = decoder_layout(A, e, planned, B, Tin, max_len, with_masks); })))
         return rc;
-    const DecodeCall call{B, Tin, max_len, early_stop ? 1 : 0, win_len, win_offset, half_w, en->buf.p, en->memory, en->pm,
+    const DecodeCall call{B, Tin, max_len, c.early_stop ? 1 : 0, c.win_len, c.win_offset, half_w, en->buf.p, en->memory, en->pm,
                           en->mask, en->enc_len, en->bl_err, with_masks ? ws.masks : nullptr, ws};
 
     // prenet dropout masks always travel through the workspace: a captured graph must not hold a caller's pointer
-    const hipMemcpyKind kin = mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    if (prenet_masks) {
-        HIPCHK(e, hipMemcpyAsync(ws.masks, prenet_masks, RD * 2 * PRE * 4, kin, st));
-    } else if (mask_seed) {                                 // drawn on the device, straight into the workspace
-        if ((rc = philox_fill(e, ws.masks, (long long)RD * 2 * PRE, mask_seed[0], mask_seed[1], TTS_HIP_RANDOM_PRENET_MASK, st))) return rc;
-    } else if (row_keys) {                                  // row b: elements 0 .. max_len * 512 of its own stream
-        if ((rc = philox_fill_rows(e, ws.masks, B, (long long)max_len * 2 * PRE, row_keys, row_offsets, nullptr,
-                                   TTS_HIP_RANDOM_PRENET_MASK, st)))
-            return rc;
+    switch (c.masks) {
+        case TACO_MASKS_NONE: break;
+        case TACO_MASKS_TENSOR: HIPCHK(e, hipMemcpyAsync(ws.masks, c.prenet_masks, RD * 2 * PRE * 4, copy_in(c.mem), st)); break;
+        case TACO_MASKS_SEED:                               // drawn on the device, straight into the workspace
+            if ((rc = philox_fill(e, ws.masks, (long long)RD * 2 * PRE, c.seed, c.offset, TTS_HIP_RANDOM_PRENET_MASK, st))) return rc;
+            break;
+        case TACO_MASKS_ROWS:                               // row b: elements 0 .. max_len * 512 of its own stream
+            if ((rc = philox_fill_rows(e, ws.masks, B, (long long)max_len * 2 * PRE, c.keys, c.offsets, nullptr,
+                                       TTS_HIP_RANDOM_PRENET_MASK, st)))
+                return rc;
+            break;
     }
 
     // ---------------- decoder loop: the chosen machine, and the per-step graph from the start when that one gives up
@@ -1852,18 +1863,9 @@ static int tacotron2_decode_impl(tts_hip_engine* e, const tts_hip_encoded* en, i
     // ---------------- postnet + residual
     if ((rc = postnet_residual(e, ws.lengths, ws.dec_out, B, max_len, ws.post))) return rc;
 
-    // ---------------- outputs
-    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (mel) HIPCHK(e, hipMemcpyAsync(mel, ws.post.mel, RD * NMEL * 4, kout, st));
-    if (decoder_output) HIPCHK(e, hipMemcpyAsync(decoder_output, ws.dec_out, RD * NMEL * 4, kout, st));
-    if (stop_tokens) HIPCHK(e, hipMemcpyAsync(stop_tokens, ws.stop_out, RD * 4, kout, st));
-    if (attention) HIPCHK(e, hipMemcpyAsync(attention, ws.attn_hist, RD * Tin * 4, kout, st));
-    if (lengths) HIPCHK(e, hipMemcpyAsync(lengths, ws.lengths, (size_t)B * 4, kout, st));
-    int bl_err = 0;                                  // the persistent kernel's own synchronisation did not read it
-    if (tc.last_path == DEC_PERSISTENT) HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    if ((rc = check_bilstm_status(e, bl_err))) return rc;
-    if (steps_run) *steps_run = host_steps;
+    // ---------------- outputs (the persistent kernel's own synchronisation did not read the BiLSTM status)
+    if ((rc = copy_results(e, c, en, ws, tc.last_path == DEC_PERSISTENT))) return rc;
+    if (c.steps_run) *c.steps_run = host_steps;
     return TTS_HIP_OK;
 }
 
@@ -1912,24 +1914,18 @@ static int enqueue_forward_chunk(tts_hip_engine* e, const DecodeCall& c, const F
 // gate term, the chunk graphs back to back (the loop's exit is not data dependent, so nothing is read back between them),
 // bulk projection, postnet, outputs; ONE synchronisation at the end, which also reads the BiLSTM status.  The workspace is
 // the decode call's plan with the forward buffers added, so a following decode call plans, resets and runs as ever.
-static int tacotron2_forward_impl(tts_hip_engine* e, const tts_hip_encoded* en, const float* mel_input, int T,
-                                  const int32_t* mel_lengths, const float* prenet_masks, int precision, float* mel,
-                                  float* decoder_output, float* stop_tokens, float* attention, int mem) {
+// (The request already passed check_run.)
+static int tacotron2_forward_impl(tts_hip_engine* e, const tts_hip_encoded* en, const TacoRun& c) {
     Tacotron2Dev& tc = e->taco;
-    const bool has_enc = en && en->buf.p;
-    const TacoForwardCall fc{"tacotron2_forward", tc.ready, has_enc, has_enc ? en->B : 0, has_enc ? en->Tin : 0,
-                             has_enc ? en->enc : 0, tc.enc_dim, mel_input, T, mel_lengths, precision, mem};
-    char why[256] = "";
-    if (int rc = taco_forward_check(fc, why, sizeof why)) return set_err(e, rc, "%s", why);
     int rc;
-    const bool half_w = precision == 1;
+    const bool half_w = c.precision == 1;
     if (half_w && (rc = tacotron2_build_f16(e))) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    const int B = en->B, Tin = en->Tin;
+    const int B = en->B, Tin = en->Tin, T = c.len;
     const size_t RD = (size_t)B * T;
 
-    const bool with_masks = prenet_masks != nullptr;
+    const bool with_masks = c.masks == TACO_MASKS_TENSOR;
     DecoderWs ws{};
     ForwardBufs f{};
     if ((rc = plan_workspace(e, tc.ws, 4096, [&](Arena& A) { ws = decoder_layout(A, e, DEC_STEP_GRAPH, B, Tin, T, with_masks, &f); })))
@@ -1937,10 +1933,9 @@ static int tacotron2_forward_impl(tts_hip_engine* e, const tts_hip_encoded* en, 
     // (the masks are consumed by the bulk prenet: the loop never sees them)
     const DecodeCall call{B, Tin, T, 0, 0, 0, half_w, en->buf.p, en->memory, en->pm, en->mask, en->enc_len, en->bl_err, nullptr, ws};
 
-    const hipMemcpyKind kin = mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    HIPCHK(e, hipMemcpyAsync(f.mel_in, mel_input, RD * NMEL * 4, kin, st));
-    HIPCHK(e, hipMemcpyAsync(f.lengths, mel_lengths, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    if (with_masks) HIPCHK(e, hipMemcpyAsync(ws.masks, prenet_masks, RD * 2 * PRE * 4, kin, st));
+    HIPCHK(e, hipMemcpyAsync(f.mel_in, c.mel_input, RD * NMEL * 4, copy_in(c.mem), st));
+    HIPCHK(e, hipMemcpyAsync(f.lengths, c.mel_lengths, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (with_masks) HIPCHK(e, hipMemcpyAsync(ws.masks, c.prenet_masks, RD * 2 * PRE * 4, copy_in(c.mem), st));
 
     if ((rc = forward_bulk_prenet(e, f, (long long)RD, with_masks ? ws.masks : nullptr))) return rc;
 
@@ -1964,47 +1959,96 @@ static int tacotron2_forward_impl(tts_hip_engine* e, const tts_hip_encoded* en, 
     if ((rc = postnet_residual(e, f.lengths, ws.dec_out, B, T, ws.post))) return rc;
 
     // ---------------- outputs
-    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (mel) HIPCHK(e, hipMemcpyAsync(mel, ws.post.mel, RD * NMEL * 4, kout, st));
-    if (decoder_output) HIPCHK(e, hipMemcpyAsync(decoder_output, ws.dec_out, RD * NMEL * 4, kout, st));
-    if (stop_tokens) HIPCHK(e, hipMemcpyAsync(stop_tokens, ws.stop_out, RD * 4, kout, st));
-    if (attention) HIPCHK(e, hipMemcpyAsync(attention, ws.attn_hist, RD * Tin * 4, kout, st));
-    int bl_err = 0;
-    HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    return check_bilstm_status(e, bl_err);
+    return copy_results(e, c, en, ws, true);
+}
+
+// ---------------------------------------------------------------------------------------------------------- the calls
+// The two checks of taco_call.h, told what a request cannot know: the state of the handle and, for a run, of the encoded
+// batch `en` (NULL from infer, whose run is on the batch its own encoder is about to fill: its facts are the request's).
+// A refusal becomes the handle's error.
+static int check_encode(tts_hip_engine* e, TacoEncode& c) {
+    c.model_ready = e->taco.ready;
+    c.spk_dim = e->taco.spk_dim;
+    char why[256] = "";
+    const int rc = taco_encode_check(c, why, sizeof why);
+    return rc ? set_err(e, rc, "%s", why) : TTS_HIP_OK;
+}
+static int check_run(tts_hip_engine* e, const tts_hip_encoded* en, TacoRun& c) {
+    c.model_ready = e->taco.ready;
+    c.model_enc = e->taco.enc_dim;
+    if (en && en->buf.p) c.has_encoded = true, c.B = en->B, c.Tin = en->Tin, c.enc = en->enc;
+    char why[256] = "";
+    const int rc = taco_run_check(c, why, sizeof why);
+    return rc ? set_err(e, rc, "%s", why) : TTS_HIP_OK;
+}
+
+// The handle's own encoded batch: the one tts_hip_tacotron2_infer* and probe_encoder re-encode into on every call
+static tts_hip_encoded* own_encoded(tts_hip_engine* e) {
+    Tacotron2Dev& tc = e->taco;
+    if (!tc.enc_cache) tc.enc_cache = new (std::nothrow) tts_hip_encoded();
+    if (!tc.enc_cache) set_err(e, TTS_HIP_ENOMEM, "out of host memory");
+    return tc.enc_cache;
+}
+
+// The three drivers every entry point ends in: check, then enqueue on the request's stream.
+static int taco_encode(tts_hip_engine* e, TacoEncode c, tts_hip_encoded* out, int stop_conv = -1, const float** stop_out = nullptr) {
+    if (int rc = check_encode(e, c)) return rc;
+    StreamScope scope(e, c.stream);
+    // (the encoder itself drops every cached graph if `out`'s buffer has to grow; a buffer that stays keeps its graphs: the
+    // next sentence of the same shape bucket replays them)
+    return tacotron2_encode_impl(e, c, out, stop_conv, stop_out);
+}
+static int taco_run(tts_hip_engine* e, const tts_hip_encoded* en, TacoRun c) {
+    if (int rc = check_run(e, en, c)) return rc;
+    StreamScope scope(e, c.stream);
+    return c.kind == TACO_FORWARD ? tacotron2_forward_impl(e, en, c) : tacotron2_decode_impl(e, en, c);
+}
+// encode + decode on the handle's own batch and stream; both requests are checked before the encoder is enqueued
+static int taco_infer(tts_hip_engine* e, TacoEncode enc, TacoRun run) {
+    if (int rc = check_encode(e, enc)) return rc;
+    run.has_encoded = true, run.B = enc.B, run.Tin = enc.Tin, run.enc = e->taco.enc_dim;
+    if (int rc = check_run(e, nullptr, run)) return rc;
+    tts_hip_encoded* en = own_encoded(e);
+    if (!en) return TTS_HIP_ENOMEM;
+    if (int rc = tacotron2_encode_impl(e, enc, en)) return rc;
+    return tacotron2_decode_impl(e, en, run);
+}
+
+static TacoEncode encode_request(const char* who, const int32_t* tokens, int B, int Tin, const float* speaker, int mem, void* stream) {
+    TacoEncode c{};
+    c.who = who, c.tokens = tokens, c.B = B, c.Tin = Tin, c.speaker = speaker, c.mem = mem, c.stream = stream;
+    return c;
+}
+// (the mask source is TACO_MASKS_NONE / TENSOR by `prenet_masks`; the seeded entry points set their own)
+static TacoRun decode_request(const char* who, int max_len, int early_stop, const float* prenet_masks, int win_len, int win_offset,
+                              int precision, float* mel, float* decoder_output, float* stop_tokens, float* attention,
+                              int32_t* lengths, int32_t* steps_run, int mem, void* stream) {
+    TacoRun c{};
+    c.who = who, c.kind = TACO_DECODE, c.len = max_len, c.early_stop = early_stop, c.win_len = win_len, c.win_offset = win_offset;
+    c.precision = precision, c.masks = prenet_masks ? TACO_MASKS_TENSOR : TACO_MASKS_NONE, c.prenet_masks = prenet_masks;
+    c.mel = mel, c.decoder_output = decoder_output, c.stop_tokens = stop_tokens, c.attention = attention;
+    c.lengths = lengths, c.steps_run = steps_run, c.mem = mem, c.stream = stream;
+    return c;
 }
 
 extern "C" int tts_hip_tacotron2_forward(tts_hip_engine* e, const tts_hip_encoded* encoded, const float* mel_input, int T,
                                          const int32_t* mel_lengths, const float* prenet_masks, int precision, float* mel,
                                          float* decoder_output, float* stop_tokens, float* attention, int mem, void* stream) {
     if (!e) return TTS_HIP_EINVAL;
-    StreamScope scope(e, stream);
-    return tacotron2_forward_impl(e, encoded, mel_input, T, mel_lengths, prenet_masks, precision, mel, decoder_output,
-                                  stop_tokens, attention, mem);
-}
-
-static int tacotron2_infer_impl(tts_hip_engine* e, const int32_t* tokens, int B, int Tin, const float* speaker,
-                                int max_len, int early_stop, const float* prenet_masks, int win_len,
-                                int win_offset, float* mel, float* decoder_output, float* stop_tokens,
-                                float* attention, int32_t* lengths, int32_t* steps_run, int mem, bool half_w) {
-    if (!e) return TTS_HIP_EINVAL;
-    if (max_len <= 0) return set_err(e, TTS_HIP_EINVAL, "tacotron2_infer: bad argument");
-    Tacotron2Dev& tc = e->taco;
-    if (!tc.enc_cache) tc.enc_cache = new (std::nothrow) tts_hip_encoded();
-    if (!tc.enc_cache) return set_err(e, TTS_HIP_ENOMEM, "out of host memory");
-    int rc = tacotron2_encode_impl(e, tokens, B, Tin, speaker, mem, tc.enc_cache);
-    if (rc) return rc;
-    return tacotron2_decode_impl(e, tc.enc_cache, max_len, early_stop, prenet_masks, win_len, win_offset, mel,
-                                 decoder_output, stop_tokens, attention, lengths, steps_run, mem, half_w);
+    TacoRun c = decode_request("tacotron2_forward", T, 0, prenet_masks, 0, 0, precision, mel, decoder_output, stop_tokens, attention,
+                               nullptr, nullptr, mem, stream);
+    c.kind = TACO_FORWARD, c.mel_input = mel_input, c.mel_lengths = mel_lengths;
+    return taco_run(e, encoded, c);
 }
 
 extern "C" int tts_hip_tacotron2_infer(tts_hip_engine* e, const int32_t* tokens, int B, int Tin, const float* speaker,
                                        int max_len, int early_stop, const float* prenet_masks, int win_len,
                                        int win_offset, float* mel, float* decoder_output, float* stop_tokens,
                                        float* attention, int32_t* lengths, int32_t* steps_run, int mem) {
-    return tacotron2_infer_impl(e, tokens, B, Tin, speaker, max_len, early_stop, prenet_masks, win_len, win_offset, mel,
-                                decoder_output, stop_tokens, attention, lengths, steps_run, mem, false);
+    if (!e) return TTS_HIP_EINVAL;
+    return taco_infer(e, encode_request("tacotron2_infer", tokens, B, Tin, speaker, mem, nullptr),
+                      decode_request("tacotron2_infer", max_len, early_stop, prenet_masks, win_len, win_offset, 0, mel,
+                                     decoder_output, stop_tokens, attention, lengths, steps_run, mem, nullptr));
 }
 
 extern "C" int tts_hip_tacotron2_infer_f16(tts_hip_engine* e, const int32_t* tokens, int B, int Tin,
@@ -2012,8 +2056,10 @@ extern "C" int tts_hip_tacotron2_infer_f16(tts_hip_engine* e, const int32_t* tok
                                            const float* prenet_masks, int win_len, int win_offset, float* mel,
                                            float* decoder_output, float* stop_tokens, float* attention,
                                            int32_t* lengths, int32_t* steps_run, int mem) {
-    return tacotron2_infer_impl(e, tokens, B, Tin, speaker, max_len, early_stop, prenet_masks, win_len, win_offset, mel,
-                                decoder_output, stop_tokens, attention, lengths, steps_run, mem, true);
+    if (!e) return TTS_HIP_EINVAL;
+    return taco_infer(e, encode_request("tacotron2_infer_f16", tokens, B, Tin, speaker, mem, nullptr),
+                      decode_request("tacotron2_infer_f16", max_len, early_stop, prenet_masks, win_len, win_offset, 1, mel,
+                                     decoder_output, stop_tokens, attention, lengths, steps_run, mem, nullptr));
 }
 
 extern "C" int tts_hip_tacotron2_encode(tts_hip_engine* e, const int32_t* tokens, int B, int Tin, const float* speaker,
@@ -2022,8 +2068,7 @@ extern "C" int tts_hip_tacotron2_encode(tts_hip_engine* e, const int32_t* tokens
     *out = nullptr;
     tts_hip_encoded* en = new (std::nothrow) tts_hip_encoded();
     if (!en) return set_err(e, TTS_HIP_ENOMEM, "out of host memory");
-    StreamScope scope(e, stream);
-    const int rc = tacotron2_encode_impl(e, tokens, B, Tin, speaker, mem, en);
+    const int rc = taco_encode(e, encode_request("tacotron2_encode", tokens, B, Tin, speaker, mem, stream), en);
     if (rc) {
         en->buf.release();
         delete en;
@@ -2038,10 +2083,8 @@ extern "C" int tts_hip_tacotron2_decode(tts_hip_engine* e, const tts_hip_encoded
                                         float* decoder_output, float* stop_tokens, float* attention, int32_t* lengths,
                                         int32_t* steps_run, int mem, void* stream) {
     if (!e) return TTS_HIP_EINVAL;
-    if (precision != 0 && precision != 1) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode: precision must be 0 (f32) or 1 (f16 weights)");
-    StreamScope scope(e, stream);
-    return tacotron2_decode_impl(e, encoded, max_len, early_stop, prenet_masks, win_len, win_offset, mel, decoder_output,
-                                 stop_tokens, attention, lengths, steps_run, mem, precision == 1);
+    return taco_run(e, encoded, decode_request("tacotron2_decode", max_len, early_stop, prenet_masks, win_len, win_offset, precision,
+                                               mel, decoder_output, stop_tokens, attention, lengths, steps_run, mem, stream));
 }
 
 extern "C" int tts_hip_tacotron2_decode_seeded(tts_hip_engine* e, const tts_hip_encoded* encoded, int max_len, int early_stop,
@@ -2049,11 +2092,10 @@ extern "C" int tts_hip_tacotron2_decode_seeded(tts_hip_engine* e, const tts_hip_
                                                float* mel, float* decoder_output, float* stop_tokens, float* attention,
                                                int32_t* lengths, int32_t* steps_run, int mem, void* stream) {
     if (!e) return TTS_HIP_EINVAL;
-    if (precision != 0 && precision != 1) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode_seeded: precision must be 0 (f32) or 1 (f16 weights)");
-    StreamScope scope(e, stream);
-    const uint64_t ms[2] = {seed, offset};
-    return tacotron2_decode_impl(e, encoded, max_len, early_stop, nullptr, win_len, win_offset, mel, decoder_output, stop_tokens,
-                                 attention, lengths, steps_run, mem, precision == 1, ms);
+    TacoRun c = decode_request("tacotron2_decode_seeded", max_len, early_stop, nullptr, win_len, win_offset, precision, mel,
+                               decoder_output, stop_tokens, attention, lengths, steps_run, mem, stream);
+    c.masks = TACO_MASKS_SEED, c.seed = seed, c.offset = offset;
+    return taco_run(e, encoded, c);
 }
 
 // `decode_seeded` with one stream per row: step t of a row reads the same bits whatever max_len the batch imposes
@@ -2062,20 +2104,16 @@ extern "C" int tts_hip_tacotron2_decode_rows_seeded(tts_hip_engine* e, const tts
                                                     int precision, float* mel, float* decoder_output, float* stop_tokens,
                                                     float* attention, int32_t* lengths, int32_t* steps_run, int mem, void* stream) {
     if (!e) return TTS_HIP_EINVAL;
-    if (precision != 0 && precision != 1) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode_rows_seeded: precision must be 0 (f32) or 1 (f16 weights)");
-    if (!keys || !offsets) return set_err(e, TTS_HIP_EINVAL, "tacotron2_decode_rows_seeded: keys / offsets is NULL");
-    StreamScope scope(e, stream);
-    return tacotron2_decode_impl(e, encoded, max_len, early_stop, nullptr, win_len, win_offset, mel, decoder_output, stop_tokens,
-                                 attention, lengths, steps_run, mem, precision == 1, nullptr, keys, offsets);
+    TacoRun c = decode_request("tacotron2_decode_rows_seeded", max_len, early_stop, nullptr, win_len, win_offset, precision, mel,
+                               decoder_output, stop_tokens, attention, lengths, steps_run, mem, stream);
+    c.masks = TACO_MASKS_ROWS, c.keys = keys, c.offsets = offsets;
+    return taco_run(e, encoded, c);
 }
 
 extern "C" int tts_hip_tacotron2_reencode(tts_hip_engine* e, tts_hip_encoded* encoded, const int32_t* tokens, int B, int Tin,
                                           const float* speaker, int mem, void* stream) {
     if (!e || !encoded) return TTS_HIP_EINVAL;
-    StreamScope scope(e, stream);
-    // (the encoder itself drops every cached graph if the buffer has to grow; a buffer that stays keeps its graphs: the next
-    // sentence of the same shape bucket replays them)
-    return tacotron2_encode_impl(e, tokens, B, Tin, speaker, mem, encoded);
+    return taco_encode(e, encode_request("tacotron2_reencode", tokens, B, Tin, speaker, mem, stream), encoded);
 }
 
 extern "C" int tts_hip_encoded_free(tts_hip_engine* e, tts_hip_encoded* encoded) {
@@ -2094,19 +2132,17 @@ extern "C" int tts_hip_tacotron2_probe_encoder(tts_hip_engine* e, const int32_t*
                                                int what, float* out, int mem) {
     if (!e) return TTS_HIP_EINVAL;
     if (!out || what < 0 || what > 4) return set_err(e, TTS_HIP_EINVAL, "tacotron2_probe_encoder: bad argument");
-    Tacotron2Dev& tc = e->taco;
-    if (!tc.enc_cache) tc.enc_cache = new (std::nothrow) tts_hip_encoded();
-    if (!tc.enc_cache) return set_err(e, TTS_HIP_ENOMEM, "out of host memory");
+    tts_hip_encoded* en = own_encoded(e);
+    if (!en) return TTS_HIP_ENOMEM;
     const float* src = nullptr;
-    const int rc = tacotron2_encode_impl(e, tokens, B, Tin, speaker, mem, tc.enc_cache, what <= 2 ? what : -1, &src);
+    const int rc = taco_encode(e, encode_request("tacotron2_probe_encoder", tokens, B, Tin, speaker, mem, nullptr), en,
+                               what <= 2 ? what : -1, &src);
     if (rc) return rc;
-    const tts_hip_encoded* en = tc.enc_cache;
     const int width = what <= 2 ? 512 : what == 3 ? en->enc : ATT;
     if (what == 3) src = en->memory;
     if (what == 4) src = en->pm;
-    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     int bl_err = 0;
-    HIPCHK(e, hipMemcpyAsync(out, src, (size_t)B * Tin * width * 4, kout, e->stream));
+    HIPCHK(e, hipMemcpyAsync(out, src, (size_t)B * Tin * width * 4, copy_out(mem), e->stream));
     if (what >= 3) HIPCHK(e, hipMemcpyAsync(&bl_err, en->bl_err, sizeof bl_err, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return check_bilstm_status(e, bl_err);
@@ -2121,7 +2157,7 @@ extern "C" int tts_hip_tacotron2_probe_postnet(tts_hip_engine* e, const float* f
     if (!tc.ready) return set_err(e, TTS_HIP_ENOTREADY, "tacotron2 weights not finalized");
     if (!frames || !lengths || !out || B <= 0 || B > 1024 || T <= 0 || (long long)B * T > (1 << 18) || what < 0 || what > 5)
         return set_err(e, TTS_HIP_EINVAL, "tacotron2_probe_postnet: bad argument");
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "bad mem kind %d", mem);
+    if (taco_bad_mem(mem)) return set_err(e, TTS_HIP_EINVAL, "tacotron2_probe_postnet: bad mem kind %d", mem);
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = e->stream;
     const long long RD = (long long)B * T;
@@ -2134,14 +2170,12 @@ extern "C" int tts_hip_tacotron2_probe_postnet(tts_hip_engine* e, const float* f
             pb = postnet_layout(A, RD);
         }))
         return rc;
-    const hipMemcpyKind kin = mem == TTS_HIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     HIPCHK(e, hipMemcpyAsync(d_lengths, lengths, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipMemcpyAsync(d_frames, frames, (size_t)RD * NMEL * 4, kin, st));
+    HIPCHK(e, hipMemcpyAsync(d_frames, frames, (size_t)RD * NMEL * 4, copy_in(mem), st));
     const float* src = pb.mel;
     if (int rc = postnet_residual(e, d_lengths, d_frames, B, T, pb, what <= 4 ? what : -1, &src)) return rc;
     const int width = what <= 3 ? 512 : NMEL;
-    const hipMemcpyKind kout = mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    HIPCHK(e, hipMemcpyAsync(out, src, (size_t)RD * width * 4, kout, st));
+    HIPCHK(e, hipMemcpyAsync(out, src, (size_t)RD * width * 4, copy_out(mem), st));
     HIPCHK(e, hipStreamSynchronize(st));
     return TTS_HIP_OK;
 }

@@ -27,6 +27,10 @@ def _is_torch_cuda(x) -> bool:
     return hasattr(x, 'data_ptr') and hasattr(x, 'is_cuda') and bool(x.is_cuda)
 
 
+def _u64(v):
+    return ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
+
+
 class MelFn:
     """A mel plan of one engine (tts_hip_mel_fn; `HipEngine.mel_fn`).  It is freed when the engine closes."""
 
@@ -371,6 +375,66 @@ class HipEngine:
                  ('rows', 'ragged'): 'waveglow_infer_rows_seeded', ('rows', 'packed'): 'waveglow_infer_rows_seeded'}
 
     # ------------------------------------------------------------------ Tacotron2
+    _TACO_PRECISIONS = {'f32': 0, 'f16': 1}
+    # mask source -> (decode entry point without the tts_hip_ prefix, what the call passes where `tacotron2_decode` takes the
+    # masks: ptr = `_ptr`; src = the staged masks | (seed, offset) | the host tables (keys, offsets))
+    _TACO_DECODE = {'tensor': ('tacotron2_decode', lambda ptr, src: (ptr(src),)),
+                    'seed': ('tacotron2_decode_seeded', lambda ptr, src: (_u64(src[0]), _u64(src[1]))),
+                    'rows': ('tacotron2_decode_rows_seeded', lambda ptr, src: (ptr(src[0]), ptr(src[1])))}
+
+    def _taco_precision(self, precision):
+        if precision not in self._TACO_PRECISIONS:
+            raise ValueError(f"precision must be 'f32' or 'f16', got {precision!r}")
+        return self._TACO_PRECISIONS[precision]
+
+    def _check_encoded(self, encoded):
+        if encoded.engine is not self or encoded.handle is None:
+            raise ValueError('this EncodedBatch belongs to another engine or was freed')
+
+    def _f32(self, x, dev):
+        """None, or `x` as contiguous float32: a tensor on this engine's GPU (dev) or a host array."""
+        if x is None:
+            return None
+        if dev:
+            torch = self._torch()
+            return x.to(device=torch.device('cuda', self.device), dtype=torch.float32).contiguous()
+        return np.ascontiguousarray(x, dtype=np.float32)
+
+    def _tokens(self, tokens, dev):
+        """`tokens` as contiguous int32 [B, Tin], where they are (a CUDA tensor if dev, else a host array)."""
+        tok = tokens.to(self._torch().int32).contiguous() if dev else np.ascontiguousarray(tokens, dtype=np.int32)
+        if len(tok.shape) != 2:
+            raise ValueError(f'tokens must be [B, Tin], got {tuple(tok.shape)}')
+        return tok
+
+    @staticmethod
+    def _check_masks(masks, B, T, axis):
+        """Converted prenet masks (or None) must be [B, T, 2, 256]; `axis` names T in the message.  -> masks"""
+        if masks is not None and tuple(masks.shape) != (B, T, 2, 256):
+            raise ValueError(f'prenet_masks must be [B, {axis}, 2, 256] = {(B, T, 2, 256)}, got {tuple(masks.shape)}')
+        return masks
+
+    def _taco_outputs(self, dev, B, T, Tin, want_attention=True, want_lengths=True):
+        """Zero-filled (mel [B, T, 80], dec [B, T, 80], stop [B, T], attn [B, T, Tin] | None, lengths int32 [B] | None): tensors on
+        this engine's GPU (dev) or host arrays."""
+        if dev:
+            torch = self._torch()
+            mk = lambda shape, dt='float32': torch.zeros(shape, dtype=getattr(torch, dt), device=torch.device('cuda', self.device))
+        else:
+            mk = lambda shape, dt='float32': np.zeros(shape, dtype=dt)
+        return (mk((B, T, 80)), mk((B, T, 80)), mk((B, T)), mk((B, T, Tin)) if want_attention else None,
+                mk((B,), 'int32') if want_lengths else None)
+
+    def _taco_staged(self, dev, stream, prepare, *inputs):
+        """`_staged` for a Tacotron2 call -> (what `prepare()` returned, the mem kind, the stream's pointer or None).  Host arrays
+        (not dev) are prepared as they are: nothing of torch's is waited for, and there is no stream to run on."""
+        if not dev:
+            if stream is not None:
+                raise ValueError('stream= needs device tensors')
+            return prepare(), MEM_HOST, None
+        tensors, sp = self._staged(stream, prepare, *inputs)
+        return tensors, MEM_DEVICE, sp
+
     def tacotron2_infer(self, tokens, speaker=None, max_len: int = 1000, early_stopping: bool = True,
                         prenet_masks=None, attn_mask_win_len=None, attn_mask_offset: int = 0, want_attention=True,
                         precision: str = 'f32', row_mask_seeds=None):
@@ -378,8 +442,7 @@ class HipEngine:
         precision 'f16': decoder LSTM weights in fp16 (fp32 accumulate and state).
         `row_mask_seeds=(keys, offsets)` (excludes `prenet_masks`): the prenet dropout masks are drawn on the device, row b
         from its own stream (encode + `tacotron2_decode(row_mask_seeds=...)`)."""
-        if precision not in ('f32', 'f16'):
-            raise ValueError(f"precision must be 'f32' or 'f16', got {precision!r}")
+        pcode = self._taco_precision(precision)
         if row_mask_seeds is not None:
             if prenet_masks is not None:
                 raise ValueError('pass either prenet_masks or row_mask_seeds, not both')
@@ -390,55 +453,27 @@ class HipEngine:
                                              want_attention=want_attention, precision=precision, row_mask_seeds=row_mask_seeds)
             finally:
                 enc.close()
-        fn = self._lib.tts_hip_tacotron2_infer if precision == 'f32' else self._lib.tts_hip_tacotron2_infer_f16
         dev = _is_torch_cuda(tokens)
-        if dev:
-            torch = self._torch()
-            tok = tokens.to(torch.int32).contiguous()
-            B, Tin = int(tok.shape[0]), int(tok.shape[1])
-            device = tok.device
-            mk = lambda shape, dt=None: torch.zeros(shape, dtype=dt or torch.float32, device=device)
-            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-            if speaker is not None:
-                speaker = speaker.to(device=device, dtype=torch.float32).contiguous()
-            if prenet_masks is not None:
-                prenet_masks = prenet_masks.to(device=device, dtype=torch.float32).contiguous()
-            i32 = torch.int32
-        else:
-            tok = np.ascontiguousarray(tokens, dtype=np.int32)
-            if tok.ndim != 2:
-                raise ValueError(f'tokens must be [B, Tin], got {tok.shape}')
-            B, Tin = tok.shape
-            mk = lambda shape, dt=None: np.zeros(shape, dtype=dt or np.float32)
-            ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-            if speaker is not None:
-                speaker = np.ascontiguousarray(speaker, dtype=np.float32)
-            if prenet_masks is not None:
-                prenet_masks = np.ascontiguousarray(prenet_masks, dtype=np.float32)
-            i32 = np.int32
+        self._check_device(tokens)
         max_len = int(max_len)
         if max_len <= 0:
             raise ValueError('max_len must be positive')
-        if prenet_masks is not None and tuple(prenet_masks.shape) != (B, max_len, 2, 256):
-            raise ValueError(f'prenet_masks must be [B, max_len, 2, 256], got {tuple(prenet_masks.shape)}')
-        mel = mk((B, max_len, 80))
-        dec = mk((B, max_len, 80))
-        stop = mk((B, max_len))
-        attn = mk((B, max_len, Tin)) if want_attention else None
-        lengths = mk((B,), i32)
+
+        def prepare():
+            tok = self._tokens(tokens, dev)
+            B, Tin = int(tok.shape[0]), int(tok.shape[1])
+            masks = self._check_masks(self._f32(prenet_masks, dev), B, max_len, 'max_len')
+            return (tok, self._f32(speaker, dev), masks, *self._taco_outputs(dev, B, max_len, Tin, want_attention))
+
+        (tok, spk, masks, mel, dec, stop, attn, lengths), mem, _ = self._taco_staged(dev, None, prepare)
         steps = ctypes.c_int32(0)
-        if dev:
-            self._check_device(tok, speaker, prenet_masks)
-            self._order_after_torch()
-        win = int(attn_mask_win_len) if attn_mask_win_len is not None else 0
-        self._check(fn(
-            self._h, ptr(tok), B, Tin, ptr(speaker), max_len, 1 if early_stopping else 0, ptr(prenet_masks),
-            win, int(attn_mask_offset), ptr(mel), ptr(dec), ptr(stop), ptr(attn), ptr(lengths),
-            ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), MEM_DEVICE if dev else MEM_HOST), 'tacotron2_infer')
-        out = Tacotron2InferenceOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn,
-                                       lengths=lengths)
+        name = 'tacotron2_infer' + ('_f16' if pcode else '')               # one symbol per precision
+        self._check(getattr(self._lib, 'tts_hip_' + name)(
+            self._h, self._ptr(tok), int(tok.shape[0]), int(tok.shape[1]), self._ptr(spk), max_len, 1 if early_stopping else 0,
+            self._ptr(masks), int(attn_mask_win_len or 0), int(attn_mask_offset), *map(self._ptr, (mel, dec, stop, attn, lengths)),
+            ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), mem), 'tacotron2_infer')
         self.last_steps = int(steps.value)
-        return out
+        return Tacotron2InferenceOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn, lengths=lengths)
 
     # ------------------------------------------------------------------ Tacotron2 in two calls
     def tacotron2_encode(self, tokens, speaker=None, stream=None, into=None):
@@ -447,44 +482,21 @@ class HipEngine:
         `EncodedBatch` of this engine to overwrite (tts_hip_tacotron2_reencode: no allocation, the decoder's cached graphs
         stay valid); it is returned."""
         dev = _is_torch_cuda(tokens)
-        if dev:
-            torch = self._torch()
-            self._check_device(tokens, speaker)
-
-            def convert():
-                t_ = tokens.to(torch.int32).contiguous()
-                s_ = None if speaker is None else speaker.to(device=tokens.device, dtype=torch.float32).contiguous()
-                return t_, s_
-
-            if stream is not None:
-                with self._enter_stream(stream):
-                    tok, spk = convert()
-                self._used_on(stream, tokens, speaker, tok, spk)
-            else:
-                tok, spk = convert()
-            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-            sp = self._order_after_torch(stream)
-        else:
-            if stream is not None:
-                raise ValueError('stream= needs device tensors')
-            tok = np.ascontiguousarray(tokens, dtype=np.int32)
-            spk = None if speaker is None else np.ascontiguousarray(speaker, dtype=np.float32)
-            ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-            sp = None
-        if tok.ndim != 2:
-            raise ValueError(f'tokens must be [B, Tin], got {tuple(tok.shape)}')
+        self._check_device(tokens, speaker)
+        (tok, spk), mem, sp = self._taco_staged(dev, stream, lambda: (self._tokens(tokens, dev), self._f32(speaker, dev)),
+                                                tokens, speaker)
+        B, Tin = int(tok.shape[0]), int(tok.shape[1])
         if into is not None:
             if into.engine is not self or into.handle is None:
                 raise ValueError('`into` belongs to another engine or was freed')
-            self._check(self._lib.tts_hip_tacotron2_reencode(self._h, into.handle, ptr(tok), int(tok.shape[0]), int(tok.shape[1]),
-                                                             ptr(spk), MEM_DEVICE if dev else MEM_HOST, sp), 'tacotron2_reencode')
-            into.B, into.Tin, into.on_device, into._keep = int(tok.shape[0]), int(tok.shape[1]), dev, (tok, spk)
+            self._check(self._lib.tts_hip_tacotron2_reencode(self._h, into.handle, self._ptr(tok), B, Tin, self._ptr(spk), mem, sp),
+                        'tacotron2_reencode')
+            into.B, into.Tin, into.on_device, into._keep = B, Tin, dev, (tok, spk)
             return into
         h = ctypes.c_void_p()
-        self._check(self._lib.tts_hip_tacotron2_encode(self._h, ptr(tok), int(tok.shape[0]), int(tok.shape[1]), ptr(spk),
-                                                       MEM_DEVICE if dev else MEM_HOST, sp, ctypes.byref(h)),
+        self._check(self._lib.tts_hip_tacotron2_encode(self._h, self._ptr(tok), B, Tin, self._ptr(spk), mem, sp, ctypes.byref(h)),
                     'tacotron2_encode')
-        return EncodedBatch(self, h, int(tok.shape[0]), int(tok.shape[1]), keep=(tok, spk), on_device=dev)
+        return EncodedBatch(self, h, B, Tin, keep=(tok, spk), on_device=dev)
 
     def tacotron2_decode(self, encoded, max_len: int = 1000, early_stopping: bool = True, prenet_masks=None,
                          attn_mask_win_len=None, attn_mask_offset: int = 0, want_attention=True, precision: str = 'f32',
@@ -492,79 +504,37 @@ class HipEngine:
         """Decoder loop + postnet on an `EncodedBatch`; may be called repeatedly (new dropout masks, other `max_len`).
         `mask_seed` = (seed, offset): the prenet dropout masks are drawn on the device (tts_hip_tacotron2_decode_seeded)
         instead of being passed in.  Returns after `stream` (or the engine's stream) has drained: the loop's length is
-        decided on the GPU.
+        decided on the GPU.  (`stream` only matters for a batch encoded from device tensors.)
         `row_mask_seeds` = (keys, offsets), one pair per row: row b's masks [max_len, 2, 256] are mask elements
         0 .. max_len * 512 of its own stream (tts_hip_tacotron2_decode_rows_seeded; `random_prenet_masks_rows` returns the same
         values), so a row draws the same dropout whichever rows it is decoded with and whatever `max_len` they impose."""
-        if sum(x is not None for x in (mask_seed, prenet_masks, row_mask_seeds)) > 1:
+        given = [k for k, v in (('tensor', prenet_masks), ('seed', mask_seed), ('rows', row_mask_seeds)) if v is not None]
+        if len(given) > 1:
             raise ValueError('pass only one of prenet_masks, mask_seed and row_mask_seeds')
+        source = given[0] if given else 'tensor'
         row_tables = None if row_mask_seeds is None else self._row_tables(row_mask_seeds, encoded.B, 'row_mask_seeds')
-        if precision not in ('f32', 'f16'):
-            raise ValueError(f"precision must be 'f32' or 'f16', got {precision!r}")
-        if encoded.engine is not self or encoded.handle is None:
-            raise ValueError('this EncodedBatch belongs to another engine or was freed')
+        pcode = self._taco_precision(precision)
+        self._check_encoded(encoded)
         B, Tin, dev = encoded.B, encoded.Tin, encoded.on_device
         max_len = int(max_len)
         if max_len <= 0:
             raise ValueError('max_len must be positive')
-        scope = None
-        if dev:
-            torch = self._torch()
-            device = torch.device('cuda', self.device)
-            mk = lambda shape, dt=None: torch.zeros(shape, dtype=dt or torch.float32, device=device)
-            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-            if prenet_masks is not None:
-                self._check_device(prenet_masks)
-            if stream is not None:                   # conversions and zero-filled outputs are ordered on `stream` itself
-                scope = self._enter_stream(stream)
-            i32 = torch.int32
-        else:
-            mk = lambda shape, dt=None: np.zeros(shape, dtype=dt or np.float32)
-            ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-            i32 = np.int32
+        self._check_device(prenet_masks)
 
         def prepare():
-            masks = prenet_masks
-            if masks is not None and dev:
-                masks = masks.to(device=device, dtype=torch.float32).contiguous()
-                if stream is not None:
-                    self._used_on(stream, prenet_masks, masks)
-            elif masks is not None:
-                masks = np.ascontiguousarray(masks, dtype=np.float32)
-            if masks is not None and tuple(masks.shape) != (B, max_len, 2, 256):
-                raise ValueError(f'prenet_masks must be [B, max_len, 2, 256], got {tuple(masks.shape)}')
-            return (masks, mk((B, max_len, 80)), mk((B, max_len, 80)), mk((B, max_len)),
-                    mk((B, max_len, Tin)) if want_attention else None, mk((B,), i32))
+            return (self._check_masks(self._f32(prenet_masks, dev), B, max_len, 'max_len'),
+                    *self._taco_outputs(dev, B, max_len, Tin, want_attention))
 
-        if scope is not None:
-            with scope:                              # (a failing conversion must not leave the caller's stream switched)
-                prenet_masks, mel, dec, stop, attn, lengths = prepare()
-            self._used_on(stream, mel, dec, stop, attn, lengths)
-        else:
-            prenet_masks, mel, dec, stop, attn, lengths = prepare()
+        (masks, mel, dec, stop, attn, lengths), mem, sp = self._taco_staged(dev, stream if dev else None, prepare, prenet_masks)
         steps = ctypes.c_int32(0)
-        sp = self._order_after_torch(stream) if dev else None
-        win = int(attn_mask_win_len) if attn_mask_win_len is not None else 0
-        if row_tables is not None:
-            self._check(self._lib.tts_hip_tacotron2_decode_rows_seeded(
-                self._h, encoded.handle, max_len, 1 if early_stopping else 0, row_tables[0].ctypes.data_as(ctypes.c_void_p),
-                row_tables[1].ctypes.data_as(ctypes.c_void_p), win, int(attn_mask_offset), 1 if precision == 'f16' else 0,
-                ptr(mel), ptr(dec), ptr(stop), ptr(attn), ptr(lengths), ctypes.cast(ctypes.byref(steps), ctypes.c_void_p),
-                MEM_DEVICE if dev else MEM_HOST, sp), 'tacotron2_decode_rows_seeded')
-        elif mask_seed is not None:
-            u64 = lambda v: ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
-            self._check(self._lib.tts_hip_tacotron2_decode_seeded(
-                self._h, encoded.handle, max_len, 1 if early_stopping else 0, u64(mask_seed[0]), u64(mask_seed[1]), win,
-                int(attn_mask_offset), 1 if precision == 'f16' else 0, ptr(mel), ptr(dec), ptr(stop), ptr(attn), ptr(lengths),
-                ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), MEM_DEVICE if dev else MEM_HOST, sp), 'tacotron2_decode_seeded')
-        else:
-            self._check(self._lib.tts_hip_tacotron2_decode(
-                self._h, encoded.handle, max_len, 1 if early_stopping else 0, ptr(prenet_masks), win, int(attn_mask_offset),
-                1 if precision == 'f16' else 0, ptr(mel), ptr(dec), ptr(stop), ptr(attn), ptr(lengths),
-                ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), MEM_DEVICE if dev else MEM_HOST, sp), 'tacotron2_decode')
+        name, mid = self._TACO_DECODE[source]
+        self._check(getattr(self._lib, 'tts_hip_' + name)(
+            self._h, encoded.handle, max_len, 1 if early_stopping else 0,
+            *mid(self._ptr, {'tensor': masks, 'seed': mask_seed, 'rows': row_tables}[source]),
+            int(attn_mask_win_len or 0), int(attn_mask_offset), pcode, *map(self._ptr, (mel, dec, stop, attn, lengths)),
+            ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), mem, sp), name)
         self.last_steps = int(steps.value)
-        return Tacotron2InferenceOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn,
-                                        lengths=lengths)
+        return Tacotron2InferenceOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn, lengths=lengths)
 
     def tacotron2_forward(self, tokens, mel_input, mel_lengths=None, speaker=None, prenet_masks=None, seed=None,
                           offset: int = 0, precision: str = 'f32', stream=None):
@@ -580,8 +550,7 @@ class HipEngine:
         cache (decode graphs included), so it captures its graph anew every time.
         Returns Tacotron2ForwardOutput(decoder_output [B, T, 80], mel [B, T, 80], stop_tokens [B, T],
         attention_weights [B, T, Tin]) after `stream` (or the engine's stream) has drained."""
-        if precision not in ('f32', 'f16'):
-            raise ValueError(f"precision must be 'f32' or 'f16', got {precision!r}")
+        pcode = self._taco_precision(precision)
         if seed is not None and prenet_masks is not None:
             raise ValueError('pass either prenet_masks or seed, not both')
         dev = _is_torch_cuda(mel_input)
@@ -594,8 +563,7 @@ class HipEngine:
             encoded = self.tacotron2_encode(tokens, speaker=speaker, stream=stream)
         else:
             encoded = tokens
-            if encoded.engine is not self or encoded.handle is None:
-                raise ValueError('this EncodedBatch belongs to another engine or was freed')
+            self._check_encoded(encoded)
         try:
             B, Tin = encoded.B, encoded.Tin
             if len(mel_input.shape) != 3 or int(mel_input.shape[0]) != B or int(mel_input.shape[2]) != 80:
@@ -609,39 +577,16 @@ class HipEngine:
                 prenet_masks = self.random_prenet_masks(B, T, seed, offset, stream=stream)
                 if not dev:
                     prenet_masks = prenet_masks.cpu().numpy()
-            scope = None
-            if dev:
-                torch = self._torch()
-                device = torch.device('cuda', self.device)
-                self._check_device(mel_input, prenet_masks)
-                mk = lambda shape: torch.zeros(shape, dtype=torch.float32, device=device)
-                if stream is not None:
-                    scope = self._enter_stream(stream)
-            else:
-                mk = lambda shape: np.zeros(shape, dtype=np.float32)
+            self._check_device(mel_input, prenet_masks)
 
             def prepare():
-                if dev:
-                    x = mel_input.to(device=device, dtype=torch.float32).contiguous()
-                    m = None if prenet_masks is None else prenet_masks.to(device=device, dtype=torch.float32).contiguous()
-                else:
-                    x = np.ascontiguousarray(mel_input, dtype=np.float32)
-                    m = None if prenet_masks is None else np.ascontiguousarray(prenet_masks, dtype=np.float32)
-                if m is not None and tuple(m.shape) != (B, T, 2, 256):
-                    raise ValueError(f'prenet_masks must be [B, T, 2, 256] = {(B, T, 2, 256)}, got {tuple(m.shape)}')
-                return x, m, mk((B, T, 80)), mk((B, T, 80)), mk((B, T)), mk((B, T, Tin))
+                return (self._f32(mel_input, dev), self._check_masks(self._f32(prenet_masks, dev), B, T, 'T'),
+                        *self._taco_outputs(dev, B, T, Tin, want_lengths=False))
 
-            if scope is not None:
-                with scope:
-                    x, m, mel, dec, stop, attn = prepare()
-                self._used_on(stream, mel_input, prenet_masks, x, m, mel, dec, stop, attn)
-            else:
-                x, m, mel, dec, stop, attn = prepare()
-            sp = self._order_after_torch(stream) if dev else None
+            (x, m, mel, dec, stop, attn, _), mem, sp = self._taco_staged(dev, stream, prepare, mel_input, prenet_masks)
             self._check(self._lib.tts_hip_tacotron2_forward(
-                self._h, encoded.handle, self._ptr(x), T, lens.ctypes.data_as(ctypes.c_void_p), self._ptr(m),
-                1 if precision == 'f16' else 0, self._ptr(mel), self._ptr(dec), self._ptr(stop), self._ptr(attn),
-                MEM_DEVICE if dev else MEM_HOST, sp), 'tacotron2_forward')
+                self._h, encoded.handle, self._ptr(x), T, self._ptr(lens), self._ptr(m), pcode,
+                *map(self._ptr, (mel, dec, stop, attn)), mem, sp), 'tacotron2_forward')
         finally:
             if own:
                 encoded.close()
@@ -668,16 +613,12 @@ class HipEngine:
         whats = {'conv1': 0, 'conv2': 1, 'conv3': 2, 'memory': 3, 'processed_memory': 4}
         if what not in whats:
             raise ValueError(f'what must be one of {tuple(whats)}, got {what!r}')
-        tok = np.ascontiguousarray(tokens, dtype=np.int32)
-        if tok.ndim != 2:
-            raise ValueError(f'tokens must be [B, Tin], got {tok.shape}')
+        tok, spk = self._tokens(tokens, False), self._f32(speaker, False)
         B, Tin = tok.shape
-        spk = None if speaker is None else np.ascontiguousarray(speaker, dtype=np.float32)
         width = 512 if whats[what] <= 2 else 128 if what == 'processed_memory' else 512 + (0 if spk is None else spk.shape[1])
         out = np.empty((B, Tin, width), dtype=np.float32)
         self._check(self._lib.tts_hip_tacotron2_probe_encoder(
-            self._h, tok.ctypes.data_as(ctypes.c_void_p), B, Tin, None if spk is None else spk.ctypes.data_as(ctypes.c_void_p),
-            whats[what], out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'tacotron2_probe_encoder')
+            self._h, self._ptr(tok), B, Tin, self._ptr(spk), whats[what], self._ptr(out), MEM_HOST), 'tacotron2_probe_encoder')
         return out
 
     def tacotron2_probe_postnet(self, frames, lengths, what: str = 'mel'):
@@ -688,7 +629,7 @@ class HipEngine:
         whats = {'conv1': 0, 'conv2': 1, 'conv3': 2, 'conv4': 3, 'conv5': 4, 'mel': 5}
         if what not in whats:
             raise ValueError(f'what must be one of {tuple(whats)}, got {what!r}')
-        x = np.ascontiguousarray(frames, dtype=np.float32)
+        x = self._f32(frames, False)
         if x.ndim != 3 or x.shape[2] != 80:
             raise ValueError(f'frames must be [B, T, 80], got {x.shape}')
         B, T = x.shape[:2]
@@ -697,8 +638,7 @@ class HipEngine:
             raise ValueError(f'lengths must be [B] = ({B},), got {lens.shape}')
         out = np.empty((B, T, 512 if whats[what] <= 3 else 80), dtype=np.float32)
         self._check(self._lib.tts_hip_tacotron2_probe_postnet(
-            self._h, x.ctypes.data_as(ctypes.c_void_p), B, T, lens.ctypes.data_as(ctypes.c_void_p), whats[what],
-            out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'tacotron2_probe_postnet')
+            self._h, self._ptr(x), B, T, self._ptr(lens), whats[what], self._ptr(out), MEM_HOST), 'tacotron2_probe_postnet')
         return out
 
     def tacotron2_postnet(self, frames, lengths):
