@@ -56,16 +56,14 @@ class TTSPipeline:
         if on_device and trim_silence:
             raise ValueError('trim_silence=True needs on_device=False (trimmed rows have new lengths)')
         import torch
-        from .runtime import MASK_STREAM, NOISE_STREAM, stream_key
+        from .runtime import MASK_STREAM, NOISE_STREAM, frame_cap, mask_blocks, noise_blocks, stream_key
         eng = self.engine
         dev = torch.device('cuda', eng.device)
         as_dev = lambda x, dt: (x.to(device=dev, dtype=dt) if torch.is_tensor(x)
                                 else torch.as_tensor(np.asarray(x), dtype=dt).to(dev))
         tok = as_dev(tokens, torch.int32)
         B = int(tok.shape[0])
-        n_tok = int((tok != 0).sum(dim=1).max())
-        max_len = int(np.float32(n_tok) * np.float32(max_length)) if isinstance(max_length, float) else int(max_length)
-        max_len = max(1, max_len)
+        max_len = frame_cap(int((tok != 0).sum(dim=1).max()), max_length)
         mask_rows = noise_rows = None
         if row_ids is not None:
             if prenet_masks is not None or z is not None or deterministic:
@@ -77,7 +75,7 @@ class TTSPipeline:
             noise_rows = ([stream_key(self._job_seed, NOISE_STREAM, i) for i in ids], [0] * B)
         elif prenet_masks is None and not deterministic:          # drawn on the device (engine's Philox stream)
             prenet_masks = eng.random_prenet_masks(B, max_len, self._seed, self._offset)
-            self._offset += (B * max_len * 512 + 3) // 4
+            self._offset += mask_blocks(B, max_len)
         elif prenet_masks is not None:
             prenet_masks = as_dev(prenet_masks, torch.float32)
         if speaker is not None:
@@ -108,7 +106,7 @@ class TTSPipeline:
         elif z is None and not deterministic:
             audio = eng.waveglow_infer(mel.contiguous(), sigma=sigma, precision=self.vocoder_precision, seed=self._seed,
                                        offset=self._offset, **voc)
-            self._offset += (B * T * 256 + 3) // 4
+            self._offset += noise_blocks(B, T)
         else:
             if z is not None:
                 z = as_dev(z, torch.float32)[:, :T * 32]

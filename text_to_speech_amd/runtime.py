@@ -70,6 +70,45 @@ def _row_ids(streams, B, width):
     return [i + (0,) * (width - len(i)) for i in ids]
 
 
+def frame_cap(n_tok, max_length, default=None):
+    """Frames the decoder may run for `n_tok` tokens (tacotron2_arch.py:886-897): a float `max_length` is frames per token
+    (the reference's float32 product, truncated), an int is the count itself, None the `default`; never below 1."""
+    if max_length is None:
+        frames = default
+    elif isinstance(max_length, float):
+        frames = int(np.float32(n_tok) * np.float32(max_length))
+    else:
+        frames = int(max_length)
+    return max(1, frames)
+
+
+def mask_blocks(rows, frames):
+    """Philox blocks (4 values each) behind the prenet dropout of `rows` x `frames` decoder steps: 2 layers x 256 units."""
+    return (rows * frames * 512 + 3) // 4
+
+
+def noise_blocks(rows, frames):
+    """Philox blocks behind WaveGlow's noise for `rows` x `frames` mel frames: 256 samples per frame."""
+    return (rows * frames * 256 + 3) // 4
+
+
+# per purpose: (blocks one call draws, fields of a row's `streams` id, the keyword that holds explicit values)
+_DRAWS = {MASK_STREAM: (mask_blocks, 3, 'prenet_masks'), NOISE_STREAM: (noise_blocks, 2, 'z')}
+
+
+def _tokens_and_speaker(inputs):
+    """`inputs` of a Tacotron2 call, tokens or (tokens, speaker) -> (tokens [B, Tin], speaker or None)."""
+    if isinstance(inputs, (tuple, list)):
+        tokens, speaker = inputs[0], (inputs[1] if len(inputs) > 1 else None)
+    else:
+        tokens, speaker = inputs, None
+    if not _is_torch_cuda(tokens):
+        tokens = np.asarray(tokens)
+    if tokens.ndim == 1:
+        tokens = tokens[None]
+    return tokens, speaker
+
+
 def sample_prenet_masks(rng, B, max_len):
     """Multiplicative prenet dropout masks [B, max_len, 2, 256] in {0, 2} (Bernoulli(0.5), scale 1 / (1 - 0.5):
     tacotron2_arch.py:188-203), drawn from the bits of `rng.integers(0, 256, uint8)` -- 6x cheaper on the host than
@@ -190,56 +229,25 @@ class HipRuntime(Runtime):
         dropout masks come from its own stream `stream_key(seed or the runtime's seed, MASK_STREAM, *id)` at offset 0; the
         runtime's running offset is neither used nor advanced.  A row then draws the same masks in any batch (its mel is its
         own up to the fp32 re-association between decoder machines)."""
-        if streams is not None and (prenet_masks is not None or deterministic):
-            raise ValueError('streams excludes prenet_masks and deterministic=True')
-        if isinstance(inputs, (tuple, list)):
-            tokens, speaker = inputs[0], (inputs[1] if len(inputs) > 1 else None)
-        else:
-            tokens, speaker = inputs, None
-        dev = _is_torch_cuda(tokens)
-        if not dev:
-            tokens = np.asarray(tokens)
-        if tokens.ndim == 1:
-            tokens = tokens[None]
+        tokens, speaker = _tokens_and_speaker(inputs)
         B = int(tokens.shape[0])
-        if max_length is None:                      # :886-887 (hparam max_decoder_steps)
-            max_len = self.max_decoder_steps
-        elif isinstance(max_length, float):         # :888-892
-            n_tok = int((tokens != 0).sum(1).max())
-            max_len = int(np.float32(n_tok) * np.float32(max_length))
-        else:
-            max_len = int(max_length)
-        max_len = max(1, max_len)
+        n_tok = int((tokens != 0).sum(1).max()) if isinstance(max_length, float) else None       # :888-892
+        max_len = frame_cap(n_tok, max_length, self.max_decoder_steps)                               # :886-887 (the hparam)
         if attn_mask_win_len is not None and isinstance(attn_mask_offset, float):   # :894-897
             attn_mask_offset = int(np.float32(attn_mask_win_len) * np.float32(attn_mask_offset))
-        mask_seed = row_mask_seeds = None
-        if streams is not None:
-            base = self._seed if seed is None else int(seed)
-            row_mask_seeds = ([stream_key(base, MASK_STREAM, *i) for i in _row_ids(streams, B, 3)], [0] * B)
-        elif prenet_masks is None and not deterministic:
-            if seed is not None:
-                mask_seed = ((int(seed) ^ MASK_STREAM) & _U64, 0)
-            else:
-                mask_seed = ((self._seed ^ MASK_STREAM) & _U64, self._offset)
-                self._offset += (B * max_len * 512 + 3) // 4
-        if row_mask_seeds is not None and not hasattr(self.engine, 'tacotron2_encode'):
-            return self.engine.tacotron2_infer(
-                tokens, speaker=speaker, max_len=max_len, early_stopping=bool(early_stopping),
-                attn_mask_win_len=attn_mask_win_len, attn_mask_offset=int(attn_mask_offset or 0),
-                precision=precision or self.synthesizer_precision, row_mask_seeds=row_mask_seeds)
+        mask_seed, row_mask_seeds = self._draw(MASK_STREAM, B, max_len, prenet_masks, deterministic, seed, streams)
+        run = dict(max_len=max_len, early_stopping=bool(early_stopping), attn_mask_win_len=attn_mask_win_len,
+                   attn_mask_offset=int(attn_mask_offset or 0), precision=precision or self.synthesizer_precision)
         if not hasattr(self.engine, 'tacotron2_encode'):        # an engine object without the split entry points
-            if mask_seed is not None and prenet_masks is None:
+            if row_mask_seeds is not None:
+                return self.engine.tacotron2_infer(tokens, speaker=speaker, row_mask_seeds=row_mask_seeds, **run)
+            if mask_seed is not None:
                 prenet_masks = sample_prenet_masks(np.random.default_rng(mask_seed[0] + mask_seed[1]), B, max_len)
-            return self.engine.tacotron2_infer(
-                tokens, speaker=speaker, max_len=max_len, early_stopping=bool(early_stopping),
-                prenet_masks=prenet_masks, attn_mask_win_len=attn_mask_win_len, attn_mask_offset=int(attn_mask_offset or 0),
-                precision=precision or self.synthesizer_precision)
+            return self.engine.tacotron2_infer(tokens, speaker=speaker, prenet_masks=prenet_masks, **run)
         encoded = self._encoded_batch(tokens, speaker)
         try:
             return self.engine.tacotron2_decode(
-                encoded, max_len=max_len, early_stopping=bool(early_stopping), prenet_masks=prenet_masks,
-                attn_mask_win_len=attn_mask_win_len, attn_mask_offset=int(attn_mask_offset or 0),
-                precision=precision or self.synthesizer_precision,
+                encoded, prenet_masks=prenet_masks, **run,
                 **({'mask_seed': mask_seed} if row_mask_seeds is None else {'row_mask_seeds': row_mask_seeds}))
         except Exception:
             # a failed decode may have been caused by the encoded batch itself (e.g. the encoder's block exchange timed out and
@@ -257,24 +265,12 @@ class HipRuntime(Runtime):
         runtime's one kept EncodedBatch, as `tacotron2_infer` does (the encoder runs into it unless it already holds these
         tokens), so neither call costs the other its cached chunk graphs.  Unknown keywords are an error: a misspelt
         `deterministic` must not draw dropout unnoticed.  Returns the engine's Tacotron2ForwardOutput."""
-        if isinstance(inputs, (tuple, list)):
-            tokens, speaker = inputs[0], (inputs[1] if len(inputs) > 1 else None)
-        else:
-            tokens, speaker = inputs, None
-        if not _is_torch_cuda(tokens):
-            tokens = np.asarray(tokens)
-        if tokens.ndim == 1:
-            tokens = tokens[None]
+        tokens, speaker = _tokens_and_speaker(inputs)
         if len(mel_input.shape) == 2:
             mel_input = mel_input[None]
         B, T = int(mel_input.shape[0]), int(mel_input.shape[1])
-        draw = {}
-        if prenet_masks is None and not deterministic:
-            if seed is not None:
-                draw = {'seed': (int(seed) ^ MASK_STREAM) & _U64, 'offset': 0}
-            else:
-                draw = {'seed': (self._seed ^ MASK_STREAM) & _U64, 'offset': self._offset}
-                self._offset += (B * T * 512 + 3) // 4
+        mask_seed, _ = self._draw(MASK_STREAM, B, T, prenet_masks, deterministic, seed)
+        draw = {} if mask_seed is None else {'seed': mask_seed[0], 'offset': mask_seed[1]}
         precision = precision or self.synthesizer_precision
         if not hasattr(self.engine, 'tacotron2_encode'):        # an engine object without the split entry points
             return self.engine.tacotron2_forward(tokens, mel_input, mel_lengths, speaker=speaker, prenet_masks=prenet_masks,
@@ -286,6 +282,25 @@ class HipRuntime(Runtime):
         except Exception:
             self._drop_encoded()            # as in tacotron2_infer: a retry must run the encoder again
             raise
+
+    def _draw(self, purpose, rows, frames, explicit, deterministic, seed, streams=None):
+        """Where a call's random values (`purpose`: MASK_STREAM / NOISE_STREAM) come from -> (stream, row streams), at most
+        one of them set: row streams ([key per row], [0 per row]) for `streams` ids, keyed by `seed` or the runtime's seed;
+        neither for `explicit` values or `deterministic`; else the stream (key, offset) -- offset 0 of `seed`'s key, or the
+        runtime's key at its running offset, which only this last case advances, by the blocks of `rows` x `frames`."""
+        blocks, id_width, explicit_name = _DRAWS[purpose]
+        if streams is not None:
+            if explicit is not None or deterministic:
+                raise ValueError(f'streams excludes {explicit_name} and deterministic=True')
+            base = self._seed if seed is None else int(seed)
+            return None, ([stream_key(base, purpose, *i) for i in _row_ids(streams, rows, id_width)], [0] * rows)
+        if explicit is not None or deterministic:
+            return None, None
+        if seed is not None:
+            return ((int(seed) ^ purpose) & _U64, 0), None
+        offset = self._offset
+        self._offset += blocks(rows, frames)
+        return ((self._seed ^ purpose) & _U64, offset), None
 
     def _encoded_batch(self, tokens, speaker):
         """The runtime's one EncodedBatch, holding `tokens` (+ `speaker`): kept as it is when it already does, else the
@@ -357,29 +372,16 @@ class HipRuntime(Runtime):
         to fp32 re-association; a padded batch (no `lengths`) keeps hearing its padding."""
         if packed and lengths is None:
             raise ValueError('packed=True needs lengths (one frame count per row)')
-        if streams is not None and (z is not None or deterministic):
-            raise ValueError('streams excludes z and deterministic=True')
-        dev = _is_torch_cuda(mel)
-        if not dev:
+        if not _is_torch_cuda(mel):
             mel = np.asarray(mel, dtype=np.float32)
         if mel.ndim == 2:
             mel = mel[None]
         B, T = int(mel.shape[0]), int(mel.shape[1])
         ragged = {} if lengths is None else {'lengths': lengths, 'packed': True} if packed else {'lengths': lengths}
-        if streams is not None:
-            base = self._seed if seed is None else int(seed)
-            keys = [stream_key(base, NOISE_STREAM, *i) for i in _row_ids(streams, B, 2)]
-            return self.engine.waveglow_infer(mel, sigma=float(sigma), precision=precision or self.vocoder_precision,
-                                              row_seeds=(keys, [0] * B), **ragged)
-        if z is None and not deterministic:
-            if seed is not None:
-                zs, zo = (int(seed) ^ NOISE_STREAM) & _U64, 0
-            else:
-                zs, zo = (self._seed ^ NOISE_STREAM) & _U64, self._offset
-                self._offset += (B * T * 256 + 3) // 4
-            return self.engine.waveglow_infer(mel, sigma=float(sigma), precision=precision or self.vocoder_precision,
-                                              seed=zs, offset=zo, **ragged)
-        return self.engine.waveglow_infer(mel, z=z, sigma=float(sigma), precision=precision or self.vocoder_precision, **ragged)
+        noise, row_seeds = self._draw(NOISE_STREAM, B, T, z, deterministic, seed, streams)
+        draw = ({'row_seeds': row_seeds} if row_seeds is not None else {'z': z} if noise is None
+                else {'seed': noise[0], 'offset': noise[1]})
+        return self.engine.waveglow_infer(mel, sigma=float(sigma), precision=precision or self.vocoder_precision, **draw, **ragged)
 
 
 _runtimes = {'hip': HipRuntime}
@@ -392,4 +394,4 @@ def build_runtime(runtime, path, *args, **kwargs):
     return _runtimes[runtime](path, *args, **kwargs)
 
 
-__all__ = ['Runtime', 'HipRuntime', 'build_runtime', 'Tacotron2InferenceOutput', 'stream_key']
+__all__ = ['Runtime', 'HipRuntime', 'build_runtime', 'Tacotron2InferenceOutput', 'stream_key', 'frame_cap']

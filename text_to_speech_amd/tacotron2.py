@@ -1,6 +1,6 @@
 """Host-side Tacotron2 wrapper and the `tts()` / `stream()` facade.
 
-Restates the host logic of /root/reference/models/tts/tacotron2.py:104-241 (`Tacotron2.infer`: split / clean / encode,
+Restates the host logic of the reference's models/tts/tacotron2.py:104-241 (`Tacotron2.infer`: split / clean / encode,
 per-part batch-1 call, retry while the frame/token ratio is outside (min_fpt_ratio, max_fpt_ratio) up to `max_trial`
 times, slice to `lengths`, vocoder call, concatenation, result dict with keys text, cleaned, splitted, mel, attention,
 audio, rate, time), :276-352 (`get_inference_callbacks`: the `predicted` map / `map.json` cache and the savers),
@@ -20,6 +20,7 @@ import numpy as np
 
 from .callbacks import (AudioSaver, default_audio_format, Callback, FunctionCallback, JSONSaver, QueueCallback, SpectrogramSaver,
                         apply_callbacks, load_json)
+from .runtime import frame_cap
 from .text import CharTokenizer, split_sentences, split_text
 
 logger = logging.getLogger(__name__)
@@ -66,32 +67,37 @@ class Tacotron2:
     def encode_text(self, text, cleaned=False):
         return self.tokenizer.encode(text, cleaned=cleaned)
 
-    def infer(self, text, *, embeddings=None, callbacks=None, predicted=None, overwrite=False, return_output=True,
-              max_length=10., max_text_length=-1, max_trial=5, min_fpt_ratio=2., max_fpt_ratio=10., vocoder=None,
-              silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, utterance=None, **kwargs):
-        """`utterance` (an int; `predict(sentence_streams=True)` numbers its inputs): every random draw of this text comes
+    def infer(self, text, *, callbacks=None, predicted=None, overwrite=False, return_output=True, utterance=None, **kwargs):
+        """One text (or a dict holding it under 'text' / 'content') -> its result dict.  The keywords of the stages
+        (`_stage_kwargs`): `embeddings`, `max_length=10.`, `max_text_length=-1`, `max_trial=5`, `min_fpt_ratio=2.`,
+        `max_fpt_ratio=10.` (`_synthesize`), `vocoder`, `vocoder_config` (`_vocode_parts`), `silence_time=0.15`,
+        `reduce_noise`, `trim_silence` (`_finish`); every other keyword reaches the text cleaner and both models.
+        `utterance` (an int; `predict(sentence_streams=True)` numbers its inputs): every random draw of this text comes
         from a stream of its own -- part p at trial t decodes with the id (utterance, p, t) and is vocoded with (utterance, p),
         passed to the models as `streams=[...]` (HipRuntime) -- so with a `seed` the audio does not depend on batching."""
-        if isinstance(text, dict):                                   # get_text_from_paragraph (tacotron2.py:369-370)
-            text = text['text' if 'text' in text else 'content']
+        kwargs = self._resolve_embeddings(kwargs)
+        text = _input_text(text)                                     # get_text_from_paragraph (tacotron2.py:369-370)
         callbacks = _as_callbacks(callbacks)
-        if predicted and not overwrite and text in predicted:        # cached entry: replay it, nothing is re-saved
-            if callbacks:
-                apply_callbacks(callbacks, predicted[text], {}, save=False)
-            return predicted[text]
-        part = self._synthesize(text, embeddings=embeddings, max_length=max_length, max_text_length=max_text_length,
-                                max_trial=max_trial, min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio,
-                                utterance=utterance, **kwargs)
-        return self._vocode_and_finish(part, callbacks=callbacks, predicted=predicted, return_output=return_output,
-                                       vocoder=vocoder, silence_time=silence_time, vocoder_config=vocoder_config,
-                                       reduce_noise=reduce_noise, trim_silence=trim_silence, utterance=utterance, **kwargs)
+        if _is_cached(text, predicted, overwrite):
+            return _replay(text, predicted, callbacks)
+        decode, vocode, finish = _stage_kwargs(kwargs)
+        part, = self._synthesize([text], [utterance], 1, **decode)
+        return self._finish(part, *self._vocode_parts(part, utterance, **vocode), callbacks=callbacks, predicted=predicted,
+                            return_output=return_output, **finish)
 
-    def teacher_forced(self, text, mel=None, audio=None, *, embeddings=None, deterministic=True, **load_kwargs):
+    def _resolve_embeddings(self, kwargs):
+        """The keywords of a call with `embeddings` resolved to what the synthesizer takes; a resolved vector passes through
+        unchanged, so a path that resolved once per call can hand its keywords to `infer`.  Here: nothing to resolve."""
+        return kwargs
+
+    def teacher_forced(self, text, mel=None, audio=None, *, deterministic=True, **load_kwargs):
         """The model's mel for exactly the frames of a recording of `text` (Tacotron2.call, teacher forced): `mel` [F, 80]
         is the target, or `audio` (a file name or a waveform) goes through `audio.load_mel` on the model's engine with
-        `load_kwargs`.  Returns {'text', 'cleaned', 'mel' [F, 80] (ground-truth aligned), 'decoder_output' [F, 80],
-        'stop_tokens' [F], 'attention' [F, Tin], 'durations' [Tin] (frames per token, summing to F)}.  Needs a runtime with
-        `tacotron2_forward` (HipRuntime) behind the model."""
+        `load_kwargs`; `embeddings=`: the speaker, as for `infer`.  Returns {'text', 'cleaned', 'mel' [F, 80] (ground-truth
+        aligned), 'decoder_output' [F, 80], 'stop_tokens' [F], 'attention' [F, Tin], 'durations' [Tin] (frames per token,
+        summing to F)}.  Needs a runtime with `tacotron2_forward` (HipRuntime) behind the model."""
+        load_kwargs = dict(self._resolve_embeddings(load_kwargs))
+        embeddings = load_kwargs.pop('embeddings', None)
         forward = getattr(self.compiled_infer, 'tacotron2_forward', None)
         if forward is None:
             raise ValueError('teacher_forced needs a runtime with tacotron2_forward (HipRuntime) behind the model')
@@ -116,11 +122,12 @@ class Tacotron2:
                 'decoder_output': _to_numpy(out.decoder_output)[0, :n], 'stop_tokens': _to_numpy(out.stop_tokens)[0, :n],
                 'attention': attention, 'durations': attention_durations(attention, n)}
 
-    # `infer` = `_synthesize` (text -> mels; the autoregressive, latency-bound half) followed by `_vocode_and_finish`
-    # (mels -> audio, callbacks; the throughput-bound half).  They are separate so that `stream(overlap=True)` can run
-    # the first half of sentence n + 1 while the second half of sentence n is still on the GPU.
-    def _synthesize(self, text, *, embeddings=None, max_length=10., max_text_length=-1, max_trial=5, min_fpt_ratio=2.,
-                    max_fpt_ratio=10., utterance=None, **kwargs):
+    # A text goes through four stages: `_prepare_text` (split / clean / encode), `_decode_rows` (tokens -> mels; the
+    # autoregressive, latency-bound half; `_synthesize` is the two together), `_vocode_parts` or `_vocode_group` (mels ->
+    # waveforms; the throughput-bound half) and `_finish` (result, cache entry, callbacks).  `infer`, `_infer_overlapped` and
+    # `_infer_backlog` only decide which text is in which stage when.
+    def _prepare_text(self, text, max_text_length=-1, **kwargs):
+        """Split / clean / encode -> the result-dict stub of `text`, with the token arrays of its parts under `encoded`."""
         if max_text_length == -1:
             splitted = [text]
         elif max_text_length == -2:
@@ -134,29 +141,114 @@ class Tacotron2:
         cleaned = '\n\n'.join(splitted) if len(splitted) > 1 else splitted[0]
         encoded = [self.encode_text(t, cleaned=True) for t in splitted]
         splitted = [splitted[i] for i in range(len(splitted)) if len(encoded[i]) > 0]
-        encoded = [enc for enc in encoded if len(enc) > 0]
+        encoded = [np.asarray(enc) for enc in encoded if len(enc) > 0]
+        return {'text': text, 'cleaned': cleaned, 'splitted': splitted, 'mel': [], 'attention': [], 'encoded': encoded}
 
+    def _synthesize(self, texts, utterances, k, *, embeddings=None, max_length=10., max_text_length=-1, max_trial=5,
+                    min_fpt_ratio=2., max_fpt_ratio=10., **kwargs):
+        """texts -> their result-dict stubs with `mel` / `attention` filled, one entry per part: the parts of all the texts
+        are the rows of token batches of at most `k` rows, one `_decode_rows` each (k = 1: one part per call, the
+        reference's loop).  `utterances`: the texts' numbers for per-row streams, or a None each."""
         t0 = time.time()
-        mels, attention_weights = [], []
-        for p, inp in enumerate(encoded):
-            length = len(inp)
-            success = False
-            inputs = inp[None] if embeddings is None else (inp[None], np.asarray(embeddings)[None])
-            for trial in range(max_trial):
-                ids = {} if utterance is None else {'streams': [(int(utterance), p, trial)]}
-                outputs = self.compiled_infer(inputs, max_length=max_length, **ids, **kwargs)
-                n_frames = int(_to_numpy(outputs.lengths)[0])
-                ratio = n_frames / length
-                if min_fpt_ratio < ratio < max_fpt_ratio:
-                    success = True
-                    break
-                logger.info('Inference failed (lengths : %s, frame/token ratio : %.2f) !', outputs.lengths, ratio)
-            if not success:
-                logger.warning('Inference failed too much time ! Result is probably not perfect')
-            mels.append(outputs.mel[0, :n_frames])
-            attention_weights.append(outputs.attention_weights[0, :n_frames])
-        return {'text': text, 'cleaned': cleaned, 'splitted': splitted, 'mel': mels, 'attention': attention_weights,
-                'synth_time': time.time() - t0}
+        parts = [self._prepare_text(text, max_text_length, **kwargs) for text in texts]
+        rows = [(ti, p, enc) for ti, part in enumerate(parts) for p, enc in enumerate(part.pop('encoded'))]
+        for r0 in range(0, len(rows), k):
+            chunk = rows[r0:r0 + k]
+            row_ids = None if utterances[0] is None else [(int(utterances[ti]), p) for ti, p, _ in chunk]
+            decoded = self._decode_rows([enc for _, _, enc in chunk], row_ids, embeddings=embeddings, max_length=max_length,
+                                        max_trial=max_trial, min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, **kwargs)
+            for (ti, _, _), (mel, attn) in zip(chunk, decoded):
+                parts[ti]['mel'].append(mel)
+                parts[ti]['attention'].append(attn)
+        for part in parts:
+            part['synth_time'] = (time.time() - t0) / len(parts)
+        return parts
+
+    def _decode_rows(self, tokens, row_ids, *, embeddings, max_length, max_trial, min_fpt_ratio, max_fpt_ratio, **kwargs):
+        """Decodes the token arrays `tokens` as the rows of one 0-padded batch -> [(mel [n_i, 80], attention [n_i, Tin])].
+        Row i ends at min(its length, the `frame_cap` it would have had alone): the runtime sizes the loop by the longest row
+        (and the mel of a row cut that way gets the postnet of its own frames, on a HIP engine); for a row decoded alone the
+        runtime's cap is its own.  Rows outside the frame / token window are decoded again together, up to `max_trial` times
+        in all, and keep their last result.  `row_ids` [(utterance, part)] per row, or None: every call passes
+        `streams=[(utterance, part, trial), ...]` for its rows; a row is in the call of trial t only after failing t times
+        itself, so its own trial advances and the rows that passed are not drawn for again."""
+        decoded, pending = [None] * len(tokens), list(range(len(tokens)))
+        for trial in range(max_trial):
+            n_tok = [len(tokens[i]) for i in pending]
+            tok = np.zeros((len(pending), max(n_tok)), dtype=tokens[0].dtype)
+            for r, i in enumerate(pending):
+                tok[r, :n_tok[r]] = tokens[i]
+            inputs = tok if embeddings is None else (tok, np.repeat(np.asarray(embeddings)[None], len(pending), axis=0))
+            ids = {} if row_ids is None else {'streams': [(*row_ids[i], trial) for i in pending]}
+            outputs = self.compiled_infer(inputs, max_length=max_length, **ids, **kwargs)
+            lengths = _to_numpy(outputs.lengths)
+            frames = [int(n) for n in lengths]
+            # (a row decoded alone ends where the synthesizer says, as in the reference's loop: behind HipRuntime that is
+            # within its cap already, and a synthesizer that counts its frames otherwise is not second-guessed)
+            if len(pending) > 1 and max_length is not None:
+                frames = [min(n, frame_cap(t, max_length)) for n, t in zip(frames, n_tok)]
+            mels = {r: outputs.mel[r, :frames[r]] for r in range(len(pending))}
+            # A row cut by its cap: the postnet (five k = 5 convs) of the batch saw the frames the longer loop produced behind
+            # the cut, where the row alone ends.  Its last ~10 frames are computed again from the decoder output, masked there.
+            cut = [r for r in range(len(pending)) if frames[r] < int(lengths[r])]
+            engine = getattr(self.compiled_infer, 'engine', None)
+            if cut and hasattr(engine, 'tacotron2_postnet'):
+                t_cut = max(frames[r] for r in cut)
+                dec = _to_numpy(outputs.decoder_output)[cut, :t_cut]
+                redo = engine.tacotron2_postnet(dec, [frames[r] - 1 for r in cut])
+                for j, r in enumerate(cut):
+                    mels[r] = redo[j, :frames[r]]
+            failed = []
+            for r, i in enumerate(pending):
+                decoded[i] = (mels[r], outputs.attention_weights[r, :frames[r], :n_tok[r]])
+                ratio = frames[r] / n_tok[r]
+                if not min_fpt_ratio < ratio < max_fpt_ratio:
+                    failed.append(i)
+                    logger.info('Inference failed (lengths : %s, frame/token ratio : %.2f) !', lengths[r:r + 1], ratio)
+            pending = failed
+            if not pending:
+                break
+        for _ in pending:
+            logger.warning('Inference failed too much time ! Result is probably not perfect')
+        return decoded
+
+    def _vocode_parts(self, part, utterance=None, *, vocoder=None, vocoder_config={}, **kwargs):
+        """One vocoder call per part of one text, on its 2-D mel -> (the waveforms of the text's non-empty parts, in order;
+        None without a vocoder, seconds spent)."""
+        if vocoder is None:
+            return None, 0.
+        t1 = time.time()
+        audios = []
+        for p, mel in enumerate(part['mel']):
+            if mel.shape[0] > 0:
+                ids = {} if utterance is None else {'streams': [(int(utterance), p)]}
+                audio = vocoder(mel, **ids, **{**kwargs, **vocoder_config})
+                if len(audio.shape) == 2:
+                    audio = audio[0]
+                audios.append(_to_numpy(audio))
+        return audios, time.time() - t1
+
+    def _vocode_group(self, parts, utterances, *, vocoder=None, vocoder_config={}, packed=False, **kwargs):
+        """ONE vocoder call for all the non-empty parts of several texts, as the rows of a 0-padded batch with `lengths` =
+        their frame counts (`packed`: the call also gets `packed=True`), so every waveform is that of its own frames ->
+        (per text what `_vocode_parts` gives, seconds spent)."""
+        if vocoder is None:
+            return [None] * len(parts), 0.
+        t1 = time.time()
+        audios = [[] for _ in parts]
+        voiced = [(ti, p, _to_numpy(mel)) for ti, part in enumerate(parts) for p, mel in enumerate(part['mel'])
+                  if mel.shape[0] > 0]
+        if voiced:
+            n_frames = np.asarray([m.shape[0] for _, _, m in voiced], np.int32)
+            batch = np.zeros((len(voiced), int(n_frames.max()), voiced[0][2].shape[1]), np.float32)
+            for r, (_, _, m) in enumerate(voiced):
+                batch[r, :m.shape[0]] = m
+            ragged = {'packed': True} if packed else {}
+            ids = {} if utterances[0] is None else {'streams': [(int(utterances[ti]), p) for ti, p, _ in voiced]}
+            audio = _to_numpy(vocoder(batch, lengths=n_frames, **ragged, **ids, **{**kwargs, **vocoder_config}))
+            for r, (ti, _, m) in enumerate(voiced):
+                audios[ti].append(audio[r, :m.shape[0] * 256].copy())
+        return audios, time.time() - t1
 
     def _clean_waveform(self, audio, vocoder, reduce_noise, trim_silence):
         """The reference's waveform clean-up (audio_processing.reduce_noise, trim_silence) at self.rate: `trim_silence` True is
@@ -179,28 +271,10 @@ class Tacotron2:
             audio = audio[start:end]
         return audio
 
-    def _vocode_and_finish(self, part, *, callbacks=None, predicted=None, return_output=True, vocoder=None,
-                           silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, pack_vocoder=False,
-                           utterance=None, **kwargs):
-        audios, vocoder_time = None, 0.
-        if vocoder is not None:
-            t1 = time.time()
-            audios = []
-            for p, mel in enumerate(part['mel']):
-                if mel.shape[0] > 0:
-                    ids = {} if utterance is None else {'streams': [(int(utterance), p)]}
-                    audio = vocoder(mel, **ids, **{**kwargs, **vocoder_config})
-                    if len(audio.shape) == 2:
-                        audio = audio[0]
-                    audios.append(_to_numpy(audio))
-            vocoder_time = time.time() - t1
-        return self._finish(part, audios, vocoder_time, callbacks=callbacks, predicted=predicted, return_output=return_output,
-                            vocoder=vocoder, silence_time=silence_time, reduce_noise=reduce_noise, trim_silence=trim_silence)
-
     def _finish(self, part, audios, vocoder_time, *, callbacks=None, predicted=None, return_output=True, vocoder=None,
                 silence_time=0.15, reduce_noise=False, trim_silence=False):
-        """The finishing half of `_vocode_and_finish`: `audios` (the waveforms of the non-empty parts, in order; None without
-        a vocoder) -> concatenation, clean-up, result dict, `predicted` entry, callbacks, return value."""
+        """The last stage: `audios` (the waveforms of the text's non-empty parts, in order; None without a vocoder) ->
+        concatenation, clean-up, result dict, `predicted` entry, callbacks, return value."""
         text, synth_time = part['text'], part.get('synth_time', 0.)
         audio_infos = {}
         if vocoder is not None:
@@ -309,29 +383,24 @@ class Tacotron2:
         if return_output is None:
             return_output = not any(isinstance(cb, JSONSaver) for cb in callbacks)
         kwargs = {k: v for k, v in kwargs.items() if k not in self._callback_kwargs}
+        run = dict(predicted=predicted, callbacks=callbacks, return_output=return_output)
         results = []
-        if backlog:
-            outputs = self._infer_backlog(inputs, int(batch_backlog), predicted=predicted, callbacks=callbacks,
-                                          return_output=return_output, pack_vocoder=bool(pack_vocoder),
-                                          sentence_streams=bool(sentence_streams), **kwargs)
+        if backlog:                                                # (these two resolve the speaker once per call, `infer` per text)
+            outputs = self._infer_backlog(inputs, int(batch_backlog), pack_vocoder=bool(pack_vocoder),
+                                          sentence_streams=bool(sentence_streams), **run, **self._resolve_embeddings(kwargs))
         elif overlap and kwargs.get('vocoder') is not None:
-            outputs = self._infer_overlapped(inputs, predicted=predicted, callbacks=callbacks,
-                                             return_output=return_output, sentence_streams=bool(sentence_streams),
-                                             **kwargs)
+            outputs = self._infer_overlapped(inputs, sentence_streams=bool(sentence_streams), **run,
+                                             **self._resolve_embeddings(kwargs))
         else:
-            outputs = ((inp, self.infer(inp, predicted=predicted, callbacks=callbacks, return_output=return_output,
-                                        **({'utterance': n} if sentence_streams else {}), **kwargs))
+            outputs = ((inp, self.infer(inp, utterance=n if sentence_streams else None, **run, **kwargs))
                        for n, inp in enumerate(inputs))
         for inp, output in outputs:
-            text = inp['text' if 'text' in inp else 'content'] if isinstance(inp, dict) else inp
             if return_results:
-                results.append(output if return_output else predicted[text])
+                results.append(output if return_output else predicted[_input_text(inp)])
         if join_callbacks:
             for cb in callbacks:
                 cb.join()
         return results
-
-    _synth_kwargs = ('embeddings', 'max_length', 'max_text_length', 'max_trial', 'min_fpt_ratio', 'max_fpt_ratio')
 
     def _infer_overlapped(self, inputs, *, predicted, callbacks, return_output, overwrite=False, sentence_streams=False,
                           **kwargs):
@@ -342,24 +411,20 @@ class Tacotron2:
         in fp32; the decoder's launches only get CU slots as WN GEMM blocks retire, so it runs 2.4x / 5.6x slower while a
         vocoder call is in flight, but that time was idle before.  Results keep the input order."""
         import threading
-        synth_kw = {k: kwargs.pop(k) for k in list(kwargs) if k in self._synth_kwargs}
-        voc_kw = dict(kwargs)
+        decode, vocode, finish = _stage_kwargs(kwargs)
         q = _queue.Queue(maxsize=2)
         DONE = object()
 
         def producer():
             try:
                 for n, inp in enumerate(inputs):
-                    text = inp['text' if 'text' in inp else 'content'] if isinstance(inp, dict) else inp
-                    ids = {'utterance': n} if sentence_streams else {}
-                    if predicted and not overwrite and text in predicted:
-                        q.put((inp, text, None, None, ids))
-                        continue
-                    extra = {k: v for k, v in voc_kw.items() if k not in ('vocoder', 'silence_time', 'vocoder_config',
-                                                                             'reduce_noise', 'trim_silence')}
-                    q.put((inp, text, self._synthesize(text, **synth_kw, **ids, **extra), None, ids))
+                    text, number = _input_text(inp), n if sentence_streams else None
+                    part = None                                       # a cached text: the consumer replays it in its turn
+                    if not _is_cached(text, predicted, overwrite):
+                        part, = self._synthesize([text], [number], 1, **decode)
+                    q.put((inp, text, number, part, None))
             except BaseException as exc:                              # noqa: BLE001 -- re-raised in the consumer
-                q.put((None, None, None, exc, {}))
+                q.put((None, None, None, None, exc))
             finally:
                 q.put(DONE)
 
@@ -370,16 +435,14 @@ class Tacotron2:
                 item = q.get()
                 if item is DONE:
                     break
-                inp, text, part, exc, ids = item
+                inp, text, number, part, exc = item
                 if exc is not None:
                     raise exc
-                if part is None:                                      # cache hit
-                    if callbacks:
-                        apply_callbacks(callbacks, predicted[text], {}, save=False)
-                    yield inp, predicted[text]
+                if part is None:
+                    yield inp, _replay(text, predicted, callbacks)
                 else:
-                    yield inp, self._vocode_and_finish(part, callbacks=callbacks, predicted=predicted,
-                                                       return_output=return_output, **ids, **voc_kw)
+                    yield inp, self._finish(part, *self._vocode_parts(part, number, **vocode), callbacks=callbacks,
+                                            predicted=predicted, return_output=return_output, **finish)
         finally:
             while th.is_alive():                                      # drain so that the producer can finish
                 try:
@@ -388,141 +451,37 @@ class Tacotron2:
                     pass
             th.join()
 
-    def _infer_backlog(self, inputs, k, *, predicted, callbacks, return_output, overwrite=False, embeddings=None,
-                       max_length=10., max_text_length=-1, max_trial=5, min_fpt_ratio=2., max_fpt_ratio=10., vocoder=None,
-                       silence_time=0.15, vocoder_config={}, reduce_noise=False, trim_silence=False, pack_vocoder=False,
+    def _infer_backlog(self, inputs, k, *, predicted, callbacks, return_output, overwrite=False, pack_vocoder=False,
                        sentence_streams=False, **kwargs):
         """`predict(batch_backlog=k)`: yields (input, result) in input order.  Per group of waiting inputs (`_backlog_groups`):
         the parts of all its texts are the rows of 0-padded token batches of at most k rows, one `compiled_infer` call each;
         every row keeps the frame cap, the frame / token ratio test and the retries it would have had alone (rows that fail
-        are decoded again together); ONE vocoder call per group with `lengths` = the rows' frame counts, so every waveform is
-        that of its own frames (`pack_vocoder`: that call also gets `packed=True`); then each text is finished (`_finish`) in
-        input order.  `sentence_streams`: inputs are numbered as the groups take them from the source; the row of part p of
-        utterance n decodes with the id (n, p, trial) -- a retried row keeps its id and advances only its own trial -- and is
-        vocoded with (n, p), exactly as the sequential path does."""
-        one = dict(predicted=predicted, callbacks=callbacks, return_output=return_output, overwrite=overwrite,
-                   embeddings=embeddings, max_length=max_length, max_text_length=max_text_length, max_trial=max_trial,
-                   min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, vocoder=vocoder, silence_time=silence_time,
-                   vocoder_config=vocoder_config, reduce_noise=reduce_noise, trim_silence=trim_silence, **kwargs)
-        finish = dict(callbacks=callbacks, predicted=predicted, return_output=return_output, vocoder=vocoder,
-                      silence_time=silence_time, reduce_noise=reduce_noise, trim_silence=trim_silence)
-        is_cached = lambda text: bool(predicted) and not overwrite and text in predicted
+        are decoded again together); ONE vocoder call per group (`_vocode_group`); then each text is finished (`_finish`) in
+        input order.  A group with at most one text to synthesize takes `infer`, cache replays included.
+        `sentence_streams`: inputs are numbered as the groups take them from the source; the row of part p of utterance n
+        decodes with the id (n, p, trial) -- a retried row keeps its id and advances only its own trial -- and is vocoded
+        with (n, p), exactly as the sequential path does."""
+        decode, vocode, finish = _stage_kwargs(kwargs)
+        run = dict(predicted=predicted, callbacks=callbacks, return_output=return_output)
+        is_cached = lambda text: _is_cached(text, predicted, overwrite)
         taken = 0
         for group in _backlog_groups(inputs, k, is_cached):
-            number = {text: taken + j for j, (_, text) in enumerate(group)}        # (a group never holds a text twice)
-            taken += len(group)
-            utt = lambda text: {'utterance': number[text]} if sentence_streams else {}
-            fresh = [(inp, text) for inp, text in group if not is_cached(text)]
-            if len(fresh) <= 1:                                   # no backlog: the sequential path, cache replays included
+            number = {text: taken + j if sentence_streams else None for j, (_, text) in enumerate(group)}
+            taken += len(group)                                   # (a group never holds a text twice)
+            fresh = [text for _, text in group if not is_cached(text)]
+            if len(fresh) <= 1:
                 for inp, text in group:
-                    yield inp, Tacotron2.infer(self, inp, **utt(text), **one)
+                    yield inp, self.infer(inp, utterance=number[text], overwrite=overwrite, **run, **kwargs)
                 continue
-            t0 = time.time()
-            parts = [self._prepare_text(text, max_text_length, **kwargs) for _, text in fresh]
-            rows = [(ti, enc, p) for ti, part in enumerate(parts) for p, enc in enumerate(part.pop('encoded'))]
-            row_ids = [(number[fresh[ti][1]], p) for ti, _, p in rows] if sentence_streams else None
-            decoded = [None] * len(rows)
-            for r0 in range(0, len(rows), k):
-                chunk = list(range(r0, min(r0 + k, len(rows))))
-                self._decode_rows(rows, chunk, decoded, embeddings=embeddings, max_length=max_length, max_trial=max_trial,
-                                  min_fpt_ratio=min_fpt_ratio, max_fpt_ratio=max_fpt_ratio, row_ids=row_ids, **kwargs)
-            synth_time = time.time() - t0
-            for (ti, _, _), (mel, attn) in zip(rows, decoded):
-                parts[ti]['mel'].append(mel)
-                parts[ti]['attention'].append(attn)
-            audios, vocoder_time = [None] * len(parts), 0.
-            if vocoder is not None:
-                t1 = time.time()
-                audios = [[] for _ in parts]
-                voiced = [(ti, _to_numpy(mel), r) for r, ((ti, _, _), (mel, _)) in enumerate(zip(rows, decoded)) if mel.shape[0] > 0]
-                if voiced:
-                    n_frames = np.asarray([m.shape[0] for _, m, _ in voiced], np.int32)
-                    batch = np.zeros((len(voiced), int(n_frames.max()), voiced[0][1].shape[1]), np.float32)
-                    for r, (_, m, _) in enumerate(voiced):
-                        batch[r, :m.shape[0]] = m
-                    packed = {'packed': True} if pack_vocoder else {}
-                    ids = {'streams': [row_ids[i] for _, _, i in voiced]} if sentence_streams else {}
-                    audio = _to_numpy(vocoder(batch, lengths=n_frames, **packed, **ids, **{**kwargs, **vocoder_config}))
-                    for r, (ti, m, _) in enumerate(voiced):
-                        audios[ti].append(audio[r, :m.shape[0] * 256].copy())
-                vocoder_time = time.time() - t1
-            done = {}
-            for (_, text), part, aud in zip(fresh, parts, audios):
-                part['synth_time'] = synth_time / len(fresh)
-                done[text] = (part, aud)
+            numbers = [number[text] for text in fresh]
+            parts = self._synthesize(fresh, numbers, k, **decode)
+            audios, vocoder_time = self._vocode_group(parts, numbers, packed=pack_vocoder, **vocode)
+            done = dict(zip(fresh, zip(parts, audios)))
             for inp, text in group:                               # input order: cache replays between the fresh texts
                 if text in done:
-                    part, aud = done[text]
-                    yield inp, self._finish(part, aud, vocoder_time / len(fresh), **finish)
+                    yield inp, self._finish(*done[text], vocoder_time / len(fresh), **run, **finish)
                 else:
-                    yield inp, Tacotron2.infer(self, inp, **utt(text), **one)
-
-    def _prepare_text(self, text, max_text_length, **kwargs):
-        """The host half of `_synthesize` before the decoder: split / clean / encode -> a result-dict stub with `encoded`."""
-        if max_text_length == -1:
-            splitted = [text]
-        elif max_text_length == -2:
-            splitted = split_sentences(text)
-        else:
-            splitted = split_text(text, max_text_length)
-        splitted = [self.clean_text(sent, **kwargs) for sent in splitted]
-        splitted = [s for s in splitted if any(c.isalnum() for c in s)]
-        if not splitted:
-            splitted = ['']
-        cleaned = '\n\n'.join(splitted) if len(splitted) > 1 else splitted[0]
-        encoded = [self.encode_text(t, cleaned=True) for t in splitted]
-        splitted = [splitted[i] for i in range(len(splitted)) if len(encoded[i]) > 0]
-        encoded = [np.asarray(enc) for enc in encoded if len(enc) > 0]
-        return {'text': text, 'cleaned': cleaned, 'splitted': splitted, 'mel': [], 'attention': [], 'encoded': encoded}
-
-    def _decode_rows(self, rows, chunk, decoded, *, embeddings, max_length, max_trial, min_fpt_ratio, max_fpt_ratio,
-                     row_ids=None, **kwargs):
-        """Decodes rows[i] for i in `chunk` as one token batch; decoded[i] = (mel [n_i, 80], attention [n_i, Tin]).  Row i
-        ends at min(its length, the cap int(float32(tokens_i) * float32(max_length)) it would have had alone): the runtime
-        sizes the loop by the longest row (and the mel of a row cut that way gets the postnet of its own frames, on a HIP
-        engine).  Rows outside the frame / token window are decoded again together, up to
-        `max_trial` times in all, and keep their last result, as a sentence alone does.  `row_ids` [(utterance, part)] per row:
-        every call passes `streams=[(utterance, part, trial), ...]` for its rows; a row is in the call of trial t only after
-        failing t times itself, so its own trial advances and the rows that passed are not drawn for again."""
-        pending = list(chunk)
-        for trial in range(max_trial):
-            n_tok = [len(rows[i][1]) for i in pending]
-            tok = np.zeros((len(pending), max(n_tok)), dtype=rows[pending[0]][1].dtype)
-            for r, i in enumerate(pending):
-                tok[r, :n_tok[r]] = rows[i][1]
-            inputs = tok if embeddings is None else (tok, np.repeat(np.asarray(embeddings)[None], len(pending), axis=0))
-            ids = {} if row_ids is None else {'streams': [(*row_ids[i], trial) for i in pending]}
-            outputs = self.compiled_infer(inputs, max_length=max_length, **ids, **kwargs)
-            lengths = _to_numpy(outputs.lengths)
-            frames = [int(n) for n in lengths]
-            if isinstance(max_length, float):
-                frames = [min(n, max(1, int(np.float32(t) * np.float32(max_length)))) for n, t in zip(frames, n_tok)]
-            elif max_length is not None:
-                frames = [min(n, max(1, int(max_length))) for n in frames]
-            mels = {r: outputs.mel[r, :frames[r]] for r in range(len(pending))}
-            # A row cut by its cap: the postnet (five k = 5 convs) of the batch saw the frames the longer loop produced behind
-            # the cut, where the row alone ends.  Its last ~10 frames are computed again from the decoder output, masked there.
-            cut = [r for r in range(len(pending)) if frames[r] < int(lengths[r])]
-            engine = getattr(self.compiled_infer, 'engine', None)
-            if cut and hasattr(engine, 'tacotron2_postnet'):
-                t_cut = max(frames[r] for r in cut)
-                dec = _to_numpy(outputs.decoder_output)[cut, :t_cut]
-                redo = engine.tacotron2_postnet(dec, [frames[r] - 1 for r in cut])
-                for j, r in enumerate(cut):
-                    mels[r] = redo[j, :frames[r]]
-            failed = []
-            for r, i in enumerate(pending):
-                n_frames = frames[r]
-                decoded[i] = (mels[r], outputs.attention_weights[r, :n_frames, :n_tok[r]])
-                ratio = n_frames / n_tok[r]
-                if not min_fpt_ratio < ratio < max_fpt_ratio:
-                    failed.append(i)
-                    logger.info('Inference failed (lengths : %s, frame/token ratio : %.2f) !', lengths[r:r + 1], ratio)
-            pending = failed
-            if not pending:
-                return
-        for _ in pending:
-            logger.warning('Inference failed too much time ! Result is probably not perfect')
+                    yield inp, _replay(text, predicted, callbacks)
 
     def precompile_for_stream(self, **kwargs):
         for m in (64, 128):                                    # tacotron2.py:354-356 (warm-up of both shape buckets)
@@ -616,25 +575,11 @@ class SV2TTSTacotron2(Tacotron2):
             raise ValueError(f'speaker embedding must have shape ({self.embedding_dim},), got {vec.shape}')
         return vec
 
-    def infer(self, text, *, embeddings=0, **kwargs):
-        if embeddings is None or isinstance(embeddings, (int, str, dict)):
+    def _resolve_embeddings(self, kwargs):
+        embeddings = kwargs.get('embeddings', 0)
+        if embeddings is None or isinstance(embeddings, (int, str, dict)):       # a selector, not the vector itself
             embeddings = self.select_embedding(embeddings)
-        return super().infer(text, embeddings=embeddings, **kwargs)
-
-    def teacher_forced(self, text, mel=None, audio=None, *, embeddings=0, **kwargs):
-        if embeddings is None or isinstance(embeddings, (int, str, dict)):
-            embeddings = self.select_embedding(embeddings)
-        return super().teacher_forced(text, mel, audio, embeddings=embeddings, **kwargs)
-
-    def _infer_overlapped(self, inputs, *, embeddings=0, **kwargs):
-        if embeddings is None or isinstance(embeddings, (int, str, dict)):
-            embeddings = self.select_embedding(embeddings)
-        return super()._infer_overlapped(inputs, embeddings=embeddings, **kwargs)
-
-    def _infer_backlog(self, inputs, k, *, embeddings=0, **kwargs):
-        if embeddings is None or isinstance(embeddings, (int, str, dict)):       # one selection per call, as above
-            embeddings = self.select_embedding(embeddings)
-        return super()._infer_backlog(inputs, k, embeddings=embeddings, **kwargs)
+        return {**kwargs, 'embeddings': embeddings}
 
 
 def _as_callbacks(callbacks):
@@ -668,6 +613,34 @@ def _iterate(stream):
 
 def _input_text(inp):
     return inp['text' if 'text' in inp else 'content'] if isinstance(inp, dict) else inp
+
+
+def _is_cached(text, predicted, overwrite):
+    return bool(predicted) and not overwrite and text in predicted
+
+
+def _replay(text, predicted, callbacks):
+    """A cached text: its entry goes through the callbacks again, nothing is re-saved, and is the result."""
+    if callbacks:
+        apply_callbacks(callbacks, predicted[text], {}, save=False)
+    return predicted[text]
+
+
+_SYNTHESIZE_KWARGS = ('embeddings', 'max_length', 'max_text_length', 'max_trial', 'min_fpt_ratio', 'max_fpt_ratio')
+_VOCODE_KWARGS = ('vocoder', 'vocoder_config')
+_FINISH_KWARGS = ('vocoder', 'silence_time', 'reduce_noise', 'trim_silence')
+
+
+def _stage_kwargs(kwargs):
+    """The keywords of `infer` / `predict`, split once -> those of (`_synthesize`, `_vocode_parts` / `_vocode_group`,
+    `_finish`).  A keyword no stage names (`seed`, `deterministic`, `padding_multiple`, ...) is the models': it goes to the
+    text cleaner and the synthesizer with the first set and to the vocoder with the second, as the reference hands its
+    `**kwargs` on -- so a misspelt stage keyword is handed on like them, not refused.  Each stage's signature holds the
+    defaults of its own keywords (`infer`'s docstring only repeats them)."""
+    named = set(_SYNTHESIZE_KWARGS + _VOCODE_KWARGS + _FINISH_KWARGS)
+    models = {k: v for k, v in kwargs.items() if k not in named}
+    pick = lambda names: {k: kwargs[k] for k in names if k in kwargs}
+    return {**models, **pick(_SYNTHESIZE_KWARGS)}, {**models, **pick(_VOCODE_KWARGS)}, pick(_FINISH_KWARGS)
 
 
 def _backlog_groups(source, k, is_cached=lambda text: False):
