@@ -220,6 +220,32 @@ int tts_hip_tacotron2_decode_rows_seeded(tts_hip_engine* e, const tts_hip_encode
 int tts_hip_tacotron2_forward(tts_hip_engine* e, const tts_hip_encoded* encoded, const float* mel_input, int T,
                               const int32_t* mel_lengths, const float* prenet_masks, int precision, float* mel,
                               float* decoder_output, float* stop_tokens, float* attention, int mem, void* stream);
+/* The reference's TacotronLoss (custom_train_objects/losses/tacotron_loss.py: call, compute_mel_loss) on the outputs of
+ * `forward` and the targets of Tacotron2.prepare_data, per row -- evaluation only, no gradient.  mel_target, decoder_output,
+ * mel: [B, T, 80]; gate_target, stop_tokens: [B, T].  kinds: HOST int32 [n_kinds], 1 .. 4 distinct TTS_HIP_LOSS_* in the
+ * caller's order (the reference's `mel_loss` list).  out: float32 [K, B], K = 2 + 2 n_kinds, rows in the order of the
+ * reference's output_names: loss, one <kind>_mel_loss per kind (on decoder_output), one <kind>_mel_postnet_loss per kind (on
+ * mel), gate_loss.  Per row b:
+ *   mask[t] = 1 - gate_target[b, t] if mask_mel_padding (a float weight on the error, not a branch: targets need not be 0 / 1);
+ *   e = (y - p)^2 (mse kinds) or |y - p| (mae kinds), times w = (y - ymin + 1) / (ymax - ymin + 1) for the weighted kinds,
+ *       ymin / ymax over all T x 80 values of the row's mel_target, padded frames included;
+ *   mel loss = sum_t(mask[t] sum_c e) / (80 sum_t mask[t]), 0 where that divisor is 0 (divide_no_nan); unmasked: sum e / (80 T);
+ *   gate loss = (1 / T) sum_t bce[t] (g finish_weight + (1 - g) not_finish_weight) -- over the padded length T -- with
+ *       bce = max(x, 0) - x g + log1p(exp(-|x|)) if from_logits, else -(g log o + (1 - g) log(1 - o)) on
+ *       o = clip(x, float32(1e-7), float32(1 - 1e-7)) (the engine's stop_tokens are sigmoid outputs: from_logits = 0);
+ *   loss = gate loss + every mel loss + every postnet mel loss.
+ * Specified for finite inputs only (the mask multiplies, so a non-finite value in a masked frame propagates, as in the
+ * reference).  One reduction pass: no floating-point atomics, partial sums in float64, a row's result independent of the
+ * rows beside it (bit for bit at the same T).  The five inputs and `out` live where `mem` says; device pointers to the
+ * three [B, T, 80] arrays must be 16-byte aligned.  Needs no weights: a handle that is not finalized is accepted.  Refused,
+ * first match wins: a NULL pointer, B or T < 1, B * T > 65536, n_kinds outside 1 .. 4, an unknown or repeated kind, a bad
+ * mem kind, a non-finite or negative weight, a misaligned device pointer.  Synchronizes `stream` (NULL: the handle's) before
+ * returning.                                                                                                            */
+enum { TTS_HIP_LOSS_MSE = 0, TTS_HIP_LOSS_MAE = 1, TTS_HIP_LOSS_WEIGHTED_MSE = 2, TTS_HIP_LOSS_WEIGHTED_MAE = 3 };
+int tts_hip_tacotron2_loss(tts_hip_engine* e, const float* mel_target, const float* gate_target, const float* decoder_output,
+                           const float* mel, const float* stop_tokens, int B, int T, const int32_t* kinds, int n_kinds,
+                           int mask_mel_padding, int from_logits, double finish_weight, double not_finish_weight, float* out,
+                           int mem, void* stream);
 /* Runs the encoder for another token batch INTO an existing encoded batch (its device buffer is reused and only grows):
  * what a caller that synthesizes sentence after sentence wants -- no hipMalloc / hipFree per sentence, and the decoder's
  * cached step graphs (keyed by the buffer) survive from one sentence to the next.  Asynchronous like `encode`.        */

@@ -189,6 +189,7 @@ struct Tacotron2Dev {
     std::vector<void*> allocs;
     DevBuf ws;                          // per-call workspace arena
     DevBuf io;                          // staging for host callers
+    DevBuf loss_ws;                     // the one workspace of a loss call (TacoLossLayout, taco_loss.hip)
     tts_hip_encoded* enc_cache = nullptr;                 // encoder output of tts_hip_tacotron2_infer* calls (reused: stable pointers)
     DecGraphCache graphs;                                 // instantiated decoder-chunk graphs, replayed across calls
     void* pinned = nullptr;                               // pinned host ring for the decoder loop's chunk reports (2 x 64 bytes)

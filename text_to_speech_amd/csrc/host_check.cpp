@@ -40,12 +40,19 @@
 // (TacoMasks), null=encoded,keys,offsets; forward: T= enc= model_enc= precision=, null=encoded,mel,lens, and the LEN are
 // mel_lengths (no LEN: B from B=, every length T).  First line "<status> <message>"; when a forward call is accepted "frames
 // mel_in prenet gates history proj" of taco_forward_sizes (tests/test_taco_call.py compares them with a Python restatement).
+//        ttsw_check_asan --taco-loss [KEY=VALUE...] [KIND...]  -- the front end of a TacotronLoss call (taco_loss_call.h) run as an
+// entry point named "who" with the kind codes KIND (TTS_HIP_LOSS_*; n_kinds = their number unless n_kinds= says otherwise: the
+// array always holds at least 4 entries).  Settings: B= T= mem= n_kinds= mask= logits= fw= nfw= (the two weights; nan and inf are
+// understood), null=target,gate,dec,mel,stop,kinds,out and odd=target,dec,mel (that pointer 4 bytes past a 16-byte boundary).
+// First line "<status> <message>"; when the call is accepted "K chunks weighted bytes" of taco_loss_layout
+// (tests/test_taco_loss.py compares them with a Python restatement).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
 
 #include "audio_call.h"
 #include "taco_call.h"
+#include "taco_loss_call.h"
 #include "ttsw_host.h"
 #include "wg_call.h"
 #include "wg_plan.h"
@@ -287,7 +294,49 @@ static int print_taco_call(int argc, char** argv) {
     return 0;
 }
 
+static int print_taco_loss(int argc, char** argv) {
+    // never read: the check only tests the pointers' values
+    const auto at = [](unsigned long long a) { return (const float*)(uintptr_t)a; };
+    std::map<std::string, double> v{{"B", 1}, {"T", 1}, {"mem", TTS_HIP_MEM_HOST}, {"mask", 1}, {"logits", 0},
+                                    {"fw", 1}, {"nfw", 1}};
+    std::string nulls, odd;
+    std::vector<int32_t> kinds;
+    int n_kinds = 0;
+    bool n_given = false;
+    for (int i = 2; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) {
+            kinds.push_back((int32_t)atoi(argv[i]));
+            continue;
+        }
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        if (key == "null") nulls = eq + 1;
+        else if (key == "odd") odd = eq + 1;
+        else if (key == "n_kinds") n_kinds = atoi(eq + 1), n_given = true;
+        else if (v.count(key)) v[key] = atof(eq + 1);
+        else return 2;
+    }
+    if (!n_given) n_kinds = (int)kinds.size();
+    kinds.resize(std::max<size_t>(kinds.size(), kLossMaxKinds), 0);
+    const auto ptr = [&](const char* name, unsigned long long a) {
+        if (nulls.find(name) != std::string::npos) return (const float*)nullptr;
+        return at(odd.find(name) != std::string::npos ? a + 4 : a);
+    };
+    const TacoLossCall c{"who", ptr("target", 0x100000000ull), ptr("gate", 0x200000000ull), ptr("dec", 0x300000000ull),
+                         ptr("mel", 0x400000000ull), ptr("stop", 0x500000000ull), (int)v["B"], (int)v["T"],
+                         nulls.find("kinds") != std::string::npos ? nullptr : kinds.data(), n_kinds, v["mask"] != 0,
+                         v["logits"] != 0, v["fw"], v["nfw"], const_cast<float*>(ptr("out", 0x600000000ull)), (int)v["mem"], nullptr};
+    char why[256] = "";
+    const int rc = taco_loss_check(c, why, sizeof why);
+    printf("%d %s\n", rc, why);
+    if (rc) return 0;
+    const TacoLossLayout l = taco_loss_layout(c);
+    printf("%d %d %d %zu\n", l.K, l.chunks, (int)l.weighted, l.bytes);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--taco-loss")) return print_taco_loss(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "--taco-call")) return print_taco_call(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "--audio-call")) return print_audio_call(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wg-call")) return print_wg_call(argc, argv);

@@ -1060,6 +1060,7 @@ void tacotron2_free(tts_hip_engine* e) {
     }
     e->taco.ws.release();
     e->taco.io.release();
+    e->taco.loss_ws.release();
     e->taco.ready = false;
 }
 

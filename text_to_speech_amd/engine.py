@@ -592,6 +592,46 @@ class HipEngine:
                 encoded.close()
         return Tacotron2ForwardOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn)
 
+    def tacotron2_loss(self, mel_target, gate_target, decoder_output, mel, stop_tokens, *, mel_loss='mse', mask_mel_padding=True,
+                       from_logits=False, finish_weight=1., not_finish_weight=1., stream=None):
+        """The reference's TacotronLoss per sample (tts_hip_tacotron2_loss; the math is pinned in include/tts_hip.h):
+        `mel_target`, `decoder_output`, `mel` [B, T, 80] and `gate_target`, `stop_tokens` [B, T] -> float32 [K, B], K = 2 + 2 x
+        the number of `mel_loss` kinds, rows in the order of `losses.loss_output_names(mel_loss)`: loss, <kind>_mel_loss ...,
+        <kind>_mel_postnet_loss ..., gate_loss.  `mel_loss`: one of 'mse', 'mae', 'weighted_mse', 'weighted_mae' or a list of
+        1 to 4 distinct ones.  `stop_tokens` are probabilities (what `tacotron2_forward` returns) unless `from_logits`.
+        numpy in gives numpy out.  If any input is a CUDA tensor the rest are moved to the GPU and a CUDA tensor comes back:
+        the outputs of `tacotron2_forward` go in as they are, on `stream` (a torch.cuda.Stream) if one is given.  Specified for
+        finite inputs only: the padding mask multiplies the error, so a non-finite value in a masked frame propagates.
+        Returns after `stream` (or the engine's stream) has drained.  Needs no weights."""
+        from .losses import MEL_LOSS_KINDS, mel_loss_kinds
+        kinds = np.asarray([MEL_LOSS_KINDS[k] for k in mel_loss_kinds(mel_loss)], dtype=np.int32)
+        inputs = (mel_target, gate_target, decoder_output, mel, stop_tokens)
+        dev = any(_is_torch_cuda(x) for x in inputs)
+        self._check_device(*inputs)
+        shape = tuple(int(n) for n in mel_target.shape)
+        if len(shape) != 3 or shape[2] != 80:
+            raise ValueError(f'mel_target must be [B, T, 80], got {shape}')
+        B, T = shape[:2]
+        for name, x, want in (('gate_target', gate_target, (B, T)), ('decoder_output', decoder_output, shape), ('mel', mel, shape),
+                              ('stop_tokens', stop_tokens, (B, T))):
+            if tuple(int(n) for n in x.shape) != want:
+                raise ValueError(f'{name} must be {want} beside mel_target {shape}, got {tuple(x.shape)}')
+
+        def prepare():
+            if not dev:
+                return (*(self._f32(x, False) for x in inputs), np.empty((len(kinds) * 2 + 2, B), dtype=np.float32))
+            torch = self._torch()
+            gpu = torch.device('cuda', self.device)
+            xs = [self._f32(x if _is_torch_cuda(x) else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)), True)
+                  for x in inputs]
+            return (*xs, torch.empty((len(kinds) * 2 + 2, B), dtype=torch.float32, device=gpu))
+
+        (y, g, d, m, s, out), mem, sp = self._taco_staged(dev, stream, prepare, *(x for x in inputs if _is_torch_cuda(x)))
+        self._check(self._lib.tts_hip_tacotron2_loss(
+            self._h, *map(self._ptr, (y, g, d, m, s)), B, T, self._ptr(kinds), len(kinds), 1 if mask_mel_padding else 0,
+            1 if from_logits else 0, float(finish_weight), float(not_finish_weight), self._ptr(out), mem, sp), 'tacotron2_loss')
+        return out
+
     def set_decoder_mode(self, mode: str) -> None:
         """How the autoregressive decoder loop runs: 'auto' (default: the persistent weight-stationary kernel for 1 - 2 rows,
         the fused two-kernel step for 3 - 8 rows, whichever applies otherwise), 'persistent' / 'fused' (that machine when the

@@ -257,17 +257,21 @@ class HipRuntime(Runtime):
 
     # ------------------------------------------------------------------ Tacotron2.call (tacotron2_arch.py:806-849)
     def tacotron2_forward(self, inputs, mel_input, mel_lengths=None, *, prenet_masks=None, deterministic=False, seed=None,
-                          precision=None):
+                          precision=None, on_device=False):
         """Teacher-forced pass: `inputs` as for `tacotron2_infer` (tokens or (tokens, speaker)), `mel_input` [B, T, 80]
         already shifted (frame 0 the zero go-frame), `mel_lengths` [B].  Dropout as in `tacotron2_infer`: explicit
         `prenet_masks`, `deterministic=True`, `seed=` (offset 0 of that seed's mask stream) or, by default, the runtime's
         seed at its running offset, which the call advances by the B * T * 512 values it draws.  The pass runs on the
         runtime's one kept EncodedBatch, as `tacotron2_infer` does (the encoder runs into it unless it already holds these
         tokens), so neither call costs the other its cached chunk graphs.  Unknown keywords are an error: a misspelt
-        `deterministic` must not draw dropout unnoticed.  Returns the engine's Tacotron2ForwardOutput."""
+        `deterministic` must not draw dropout unnoticed.  `on_device=True`: host `mel_input` / `prenet_masks` are uploaded
+        first, so the outputs are CUDA tensors that stay on the GPU (what `tacotron2_loss` then reads in place).  Returns the
+        engine's Tacotron2ForwardOutput."""
         tokens, speaker = _tokens_and_speaker(inputs)
         if len(mel_input.shape) == 2:
             mel_input = mel_input[None]
+        if on_device:
+            mel_input, prenet_masks = (self._uploaded(x) for x in (mel_input, prenet_masks))
         B, T = int(mel_input.shape[0]), int(mel_input.shape[1])
         mask_seed, _ = self._draw(MASK_STREAM, B, T, prenet_masks, deterministic, seed)
         draw = {} if mask_seed is None else {'seed': mask_seed[0], 'offset': mask_seed[1]}
@@ -282,6 +286,19 @@ class HipRuntime(Runtime):
         except Exception:
             self._drop_encoded()            # as in tacotron2_infer: a retry must run the encoder again
             raise
+
+    def _uploaded(self, x):
+        """None, a CUDA tensor as it is, or the host array `x` as a float32 tensor on the engine's GPU."""
+        if x is None or _is_torch_cuda(x):
+            return x
+        import torch
+        return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(torch.device('cuda', self.engine.device))
+
+    # ------------------------------------------------------------------ TacotronLoss.call (losses/tacotron_loss.py:115-167)
+    def tacotron2_loss(self, mel_target, gate_target, decoder_output, mel, stop_tokens, **kwargs):
+        """The reference's TacotronLoss per sample on the engine (`HipEngine.tacotron2_loss`, whose keywords these are) ->
+        float32 [K, B].  The outputs of `tacotron2_forward(..., on_device=True)` go in without leaving the GPU."""
+        return self.engine.tacotron2_loss(mel_target, gate_target, decoder_output, mel, stop_tokens, **kwargs)
 
     def _draw(self, purpose, rows, frames, explicit, deterministic, seed, streams=None):
         """Where a call's random values (`purpose`: MASK_STREAM / NOISE_STREAM) come from -> (stream, row streams), at most

@@ -53,6 +53,7 @@ def shift_mel_target(mel):
 
 class Tacotron2:
     rate = 22050
+    pad_mel_value = 0.      # what a batch of mels is padded with (the reference's BaseAudioModel default, base_audio_model.py:37)
 
     def __init__(self, compiled_infer, lang='en', tokenizer=None, pred_dir=None):
         self.compiled_infer = compiled_infer
@@ -103,12 +104,7 @@ class Tacotron2:
             raise ValueError('teacher_forced needs a runtime with tacotron2_forward (HipRuntime) behind the model')
         if (mel is None) == (audio is None):
             raise ValueError('pass exactly one of mel and audio')
-        if mel is None:
-            from .audio import load_mel
-            mel = load_mel(audio, engine=getattr(self.compiled_infer, 'engine', None), **load_kwargs)
-        mel = np.asarray(_to_numpy(mel), dtype=np.float32)
-        if mel.ndim == 3 and mel.shape[0] == 1:
-            mel = mel[0]
+        mel = self._recording_mel(mel, audio, load_kwargs)
         cleaned = self.clean_text(text)
         tokens = np.asarray(self.encode_text(cleaned, cleaned=True), dtype=np.int32)
         if tokens.size == 0:
@@ -121,6 +117,68 @@ class Tacotron2:
         return {'text': text, 'cleaned': cleaned, 'mel': _to_numpy(out.mel)[0, :n],
                 'decoder_output': _to_numpy(out.decoder_output)[0, :n], 'stop_tokens': _to_numpy(out.stop_tokens)[0, :n],
                 'attention': attention, 'durations': attention_durations(attention, n)}
+
+    def _recording_mel(self, mel, audio, load_kwargs):
+        """The target of a teacher-forced pass as float32 [F, 80]: `mel` itself, or `audio` (a file name or a waveform) through
+        `audio.load_mel` on the model's engine with `load_kwargs`."""
+        if mel is None:
+            from .audio import load_mel
+            mel = load_mel(audio, engine=getattr(self.compiled_infer, 'engine', None), **load_kwargs)
+        mel = np.asarray(_to_numpy(mel), dtype=np.float32)
+        if mel.ndim == 3 and mel.shape[0] == 1:
+            mel = mel[0]
+        return mel
+
+    def evaluate(self, items, *, batch_size=8, loss=None, deterministic=True, **load_kwargs):
+        """The reference's TacotronLoss of the model on held-out recordings: `items` is a list of (text, mel [F, 80]) or
+        (text, audio) pairs -- `audio`, a file name or a 1-D waveform, goes through `audio.load_mel` on the model's engine with
+        `load_kwargs`, as in `teacher_forced`; `embeddings=`: the speaker, as for `infer`.  Every item is prepared as the
+        reference's `prepare_data` does (models/tts/tacotron2.py:243-259: target = the mel, input = `shift_mel_target(mel)`,
+        gate = zeros with a final 1); consecutive items form batches of at most `batch_size`, padded with the reference's
+        padding values (`get_dataset_config`, :267-274: tokens with the blank id, mels with `self.pad_mel_value`, gates with
+        1).  Each batch is one ragged `tacotron2_forward` and one `tacotron2_loss` on its outputs, which stay on the GPU: only
+        the [K, B] result comes back.  `loss`: a `losses.TacotronLoss` (default: its defaults).  Returns {'names': its
+        output_names, 'per_item': float32 [K, N] in input order, 'mean': {name: float}}.  Needs a runtime with
+        `tacotron2_forward` and `tacotron2_loss` (HipRuntime) behind the model."""
+        from .losses import TacotronLoss, mean_losses
+        load_kwargs = dict(self._resolve_embeddings(load_kwargs))
+        embeddings = load_kwargs.pop('embeddings', None)
+        runtime = self.compiled_infer
+        if getattr(runtime, 'tacotron2_forward', None) is None or getattr(runtime, 'tacotron2_loss', None) is None:
+            raise ValueError('evaluate needs a runtime with tacotron2_forward and tacotron2_loss (HipRuntime) behind the model')
+        loss = loss or TacotronLoss()
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f'batch_size must be at least 1, got {batch_size}')
+        prepared = []
+        for i, item in enumerate(items):
+            if not isinstance(item, (tuple, list)) or len(item) != 2:
+                raise ValueError(f'items[{i}] must be a (text, mel) or (text, audio) pair')
+            text, recording = item
+            is_mel = not isinstance(recording, str) and len(getattr(recording, 'shape', ())) >= 2
+            mel = self._recording_mel(recording if is_mel else None, None if is_mel else recording, load_kwargs)
+            tokens = np.asarray(self.encode_text(self.clean_text(text), cleaned=True), dtype=np.int32)
+            if tokens.size == 0:
+                raise ValueError(f'items[{i}]: the text encodes to no token')
+            prepared.append((tokens, mel, shift_mel_target(mel)))
+        if not prepared:
+            raise ValueError('evaluate needs at least one item')
+        names = loss.output_names
+        per_item = np.zeros((len(names), len(prepared)), dtype=np.float32)
+        blank, pad = int(self.tokenizer.blank_token_idx), np.float32(self.pad_mel_value)
+        for r0 in range(0, len(prepared), batch_size):
+            rows = prepared[r0:r0 + batch_size]
+            B, Tin, T = len(rows), max(len(t) for t, _, _ in rows), max(len(m) for _, m, _ in rows)
+            tok = np.full((B, Tin), blank, dtype=np.int32)
+            mel_input, target = (np.full((B, T, rows[0][1].shape[1]), pad, dtype=np.float32) for _ in range(2))
+            gate = np.ones((B, T), dtype=np.float32)
+            for r, (tokens, mel, shifted) in enumerate(rows):
+                tok[r, :len(tokens)], mel_input[r, :len(mel)], target[r, :len(mel)], gate[r, :len(mel) - 1] = tokens, shifted, mel, 0.
+            inputs = tok if embeddings is None else (tok, np.repeat(np.asarray(embeddings, np.float32)[None], B, axis=0))
+            out = runtime.tacotron2_forward(inputs, mel_input, np.asarray([len(m) for _, m, _ in rows], np.int32),
+                                            deterministic=deterministic, on_device=True)
+            per_item[:, r0:r0 + B] = _to_numpy(loss([target, gate], out, engine=runtime))
+        return {'names': names, 'per_item': per_item, 'mean': mean_losses(names, per_item)}
 
     # A text goes through four stages: `_prepare_text` (split / clean / encode), `_decode_rows` (tokens -> mels; the
     # autoregressive, latency-bound half; `_synthesize` is the two together), `_vocode_parts` or `_vocode_group` (mels ->
