@@ -81,7 +81,7 @@ struct WaveGlowDev {
     bool wino_ready = false;                 // Winograd form of the fp32 in-layer GEMM (wn_wino.hip)
     WgTable call_table;                      // host image of ragged_info (staged to the device once per call), counts
     // ---- workspace: every DevBuf of this struct is declared here ...
-    DevBuf x, acts, audio, a0p;              // fp32 path (layouts: waveglow.hip)
+    DevBuf x, acts, audio, a0p, endp;        // fp32 path (layouts: waveglow.hip)
     DevBuf x16, acts16, a0p16, mel16;        // fp16 path: shadow of x, activations, first-layer operand, mel
     DevBuf io_mel, io_z, io_out, io_zgen;    // staging for host callers; the noise of seeded calls
     DevBuf mel_ragged, ragged_info;          // ragged calls: mel copy with cleared tails; [lengths | tail frame list] int32
@@ -93,7 +93,7 @@ struct WaveGlowDev {
     // ... and listed here, which is what waveglow_free releases
     template <class F>
     void for_each_buf(F f) {
-        for (DevBuf* b : {&x, &acts, &audio, &a0p, &x16, &acts16, &a0p16, &mel16, &io_mel, &io_z, &io_out, &io_zgen, &mel_ragged,
+        for (DevBuf* b : {&x, &acts, &audio, &a0p, &endp, &x16, &acts16, &a0p16, &mel16, &io_mel, &io_z, &io_out, &io_zgen, &mel_ragged,
                           &ragged_info, &packed_z, &packed_out, &wino_U, &wino_P, &wino_mel, &wino_cond, &wino_taps})
             f(*b);
     }

@@ -105,6 +105,12 @@ struct GemmArgs {
     const uint8_t* rowmask;         // optional [M]: rows with mask 0 produce act(altbias[n]) instead
     const float* altbias;
     int mask_out;                   // with rowmask: multiply the pre-activation by the mask and skip altbias
+    // ---- end partial sums (fp32 TAG_WN_RES_SKIP kernels only; single-output launches, split == N).  Besides its own product
+    // the launch forms, from the A rows it streams anyway, the 8 outputs of the flow's folded skip / end conv as a second
+    // output: out1[m][o] (ld1 = 8, store only) = sum_k A[m][k] * endw[o][k], o < 8, with the layer's folded end weights
+    // endw [8][K], K = 512, passed in `altbias` (such a launch has no row mask).  These words are free in a single-output
+    // launch, so the argument block of every other instantiation keeps its size and layout.
+    int end_sums;
 };
 
 // out[M][Nout] = A x Bt^T with no bias and no activation: A's rows lda floats apart and K wide (K a multiple of 32), Bt
@@ -176,6 +182,14 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned by
 //           pipe); the LDS image is unpadded 64-B rows, XOR-swizzled through the per-lane SOURCE address (a wave
 //           instruction writes 1 KiB linearly, cdna_hip_programming.md rule 21), NBD buffers (fp32: always three).
 enum { PIPE_REG = 0, PIPE_DMA = 1 };
+enum { TAG_GENERIC = 0, TAG_WN_IN = 1, TAG_WN_RES_SKIP = 2, TAG_WN_IN0 = 3, TAG_WN_WINO = 4 };
+// End partial sums (GemmArgs::end_sums) ride the fp32 residual GEMM: N = K = 512, so a block of BN columns owns BN / 64 of the 8
+// outputs and the wave whose columns start at channel 64 o owns output o (CT / 2 per wave).  Their weights sit in an LDS table
+// behind the pipeline buffers, [BN / 64][END_K] floats plus one K step of padding (the loop reads one step ahead).
+constexpr int END_K = 512;
+template <int TAG, int PIPE, bool HALF>
+constexpr bool has_end_partials = TAG == TAG_WN_RES_SKIP && PIPE == PIPE_DMA && !HALF;
+constexpr size_t end_table_bytes(int BN) { return ((size_t)(BN / 64) * END_K + 16) * sizeof(float); }
 // HALF: the operands are fp16 (v_mfma_f32_16x16x32_f16, fp32 accumulate: equal cycles per FLOP to the 32x32x16 shape, but
 // under load the chip holds a higher clock on it -- MI355X_MICROARCH.md, DVFS item 7; measured here: DESIGN.md 4.1b).
 // Everything outside the MFMA call and the epilogue stores works on 4-byte units, so an fp16 operand is described to the
@@ -263,6 +277,9 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
     auto rowB = [&](int p) -> int { return ROT ? (wave * PB + p) * 16 + (lane >> 2) : p * RPP + lrow; };
     auto adj = [&](int p) -> unsigned { return (unsigned)(ROT_SH - (ROT ? p * 1024 : 0)); };
     const int li = lane & 31, lh = lane >> 5;
+    constexpr bool ENDP = has_end_partials<TAG, PIPE, HALF>;
+    constexpr int END_NW = ENDP ? CT / 2 : 1;           // end outputs per wave
+    static_assert(!ENDP || (CT % 2 == 0 && PL == 1), "end partial sums: a wave owns whole outputs");
     // Accumulator register r of a 32 x 32 tile holds (row trow(r), column tcol(r)) of the tile.  fp32 (32x32 MFMA): column =
     // lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5).  fp16 (four 16x16x32 sub-tiles, registers 4 s .. 4 s + 3 for
     // s = 2 ri + cj): row = 16 ri + 4 (lane >> 4) + (r & 3), column = 16 cj + (lane & 15).
@@ -648,6 +665,42 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
 #pragma unroll
             for (int j = 0; j < CT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][kk], fb[j][kk], acc[i][j], 0, 0, 0);
         };
+        // ---- end partial sums.  Lane (li, lh) holds row li of its 32-row block at the logical columns 16 t + 8 k8 + 4 lh + kk,
+        // every (row, k) pair in exactly one lane of a wave row: ep[i][q] is the lane's fmaf chain over its columns in the
+        // order (t, k8, kk) for output o = cbase / 64 + q, the two lh halves are added once after the loop.  That order is the
+        // same in every tile family.  The weights are broadcast ds_read_b128 from the table (vector memory loads in the loop
+        // would enter the counted vmcnt waits below).  With end_sums off the reads and FMAs still run, on whatever the
+        // table's LDS holds, and nothing is stored: the loop stays free of branches.
+        float* const wtab = smem + NBUF * (BM + BN) * LDSK;
+        const float* const wq = wtab + wc * END_NW * END_K + lh * 4;
+        bool endp_on = false;
+        if constexpr (ENDP) endp_on = g.end_sums != 0;
+        float ep[RT][END_NW];
+        f32x4 ew0[END_NW], ew1[END_NW];
+#pragma unroll
+        for (int i = 0; i < RT; ++i)
+#pragma unroll
+            for (int q = 0; q < END_NW; ++q) ep[i][q] = 0.f;
+        auto read_endw = [&](int t, int k8, f32x4 (&w)[END_NW]) {
+#pragma unroll
+            for (int q = 0; q < END_NW; ++q) w[q] = *reinterpret_cast<const f32x4*>(wq + q * END_K + t * 16 + k8 * 8);
+        };
+        auto fma_end = [&](const f32x4 (&fa)[RT], const f32x4 (&w)[END_NW], int kk, int i) {
+#pragma unroll
+            for (int q = 0; q < END_NW; ++q) ep[i][q] = fmaf(fa[i][kk], w[q][kk], ep[i][q]);
+        };
+        if constexpr (ENDP) {
+            // the block's BN / 64 weight rows are contiguous in endw: the table is 2 or 4 DMA pieces of 1 KiB, one per wave,
+            // issued ahead of tile 0's pieces -- the wait that finds tile 0 landed finds them landed, and the barrier behind
+            // it publishes them.  No load of this path passes through a register, so the counted waits see DMA pieces only.
+            constexpr int TP = (BN / 64) * END_K / 256;
+            static_assert(TP <= WR * WC, "one table piece per wave");
+            if (endp_on && wave < TP) {
+                const __amdgpu_buffer_rsrc_t rsE = make_rsrc_uniform(g.altbias + (long long)(n0 / 64) * END_K);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsE, (lds_ptr_t)(wtab + wave * 256), 16, (unsigned)(wave * 1024 + lane * 16),
+                                                         0, 0, 0);
+            }
+        }
         // prologue: all three buffers requested, tile 0 landed, its first chunk in registers
 #pragma unroll
         for (int b = 0; b < 3; ++b) {
@@ -658,14 +711,25 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
         __builtin_amdgcn_s_barrier();
         f32x4 fa0[RT], fb0[CT], fa1[RT], fb1[CT];
         read_ops(0, 0, fa0, fb0);
+        if constexpr (ENDP) read_endw(0, 0, ew0);
         int buf = 0;
         for (int t = 0; t < nAll; ++t) {
             read_ops(buf, 1, fa1, fb1);
+            if constexpr (ENDP) read_endw(t, 1, ew1);
             prepare_next();                              // tile t + 3 (address math only)
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
-                for (int i = 0; i < RT; ++i) mfma_row(fa0, fb0, kk, i);
+                for (int i = 0; i < RT; ++i) {
+                    mfma_row(fa0, fb0, kk, i);
+                    if constexpr (ENDP) fma_end(fa0, ew0, kk, i);
+                }
+            if constexpr (ENDP) {                        // (the chain so far stays on this side of the barrier: left to itself
+#pragma unroll                                           //  hipcc sinks it behind the next reads of fa0, which then need copies)
+                for (int i = 0; i < RT; ++i)
+#pragma unroll
+                    for (int q = 0; q < END_NW; ++q) asm volatile("" : "+v"(ep[i][q]));
+            }
             // every fragment of tile t is in registers; tile t + 1 has landed (tile t + 2 may stay in flight)
             __builtin_amdgcn_sched_barrier(0);           // (keeps the MFMAs above: hipcc would sink them below the barrier)
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LT) : "memory");
@@ -673,10 +737,12 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
             const int bufn1 = buf == 2 ? 0 : buf + 1;
             read_ops(bufn1, 0, fa0, fb0);                // (past the last tile: stale bytes that nothing uses -- an unconditional
                                                          // read keeps hipcc's own lgkmcnt bookkeeping off the MFMAs below)
+            if constexpr (ENDP) read_endw(t + 1, 0, ew0);   // (past the last tile: the table's padding)
             __builtin_amdgcn_sched_barrier(0);           // tile t + 3 -> the buffer of tile t, one piece per MFMA row group
             static_for<4 * RT>([&](auto gc) {
                 constexpr int grp = decltype(gc)::value;
                 mfma_row(fa1, fb1, grp / RT, grp % RT);
+                if constexpr (ENDP) fma_end(fa1, ew1, grp / RT, grp % RT);
                 if constexpr (grp < LT) {
                     issue_piece(gc, buf);
                     __builtin_amdgcn_sched_barrier(0);
@@ -687,6 +753,26 @@ __global__ __launch_bounds__(WR * WC * 64, OCC) void gemm_f32_kernel(const GemmA
         }
         // the last three steps issued fetch-nothing pieces: they must have written their zeros before the epilogue reuses LDS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (ENDP) {
+            if (endp_on) {
+                // lo + hi halves of K (one exchange; both lanes form the same sum), then plain stores by the lh = 0 lanes:
+                // each (row, output) has one writer in the launch, so two runs are equal to the bit.  Store only: every layer
+                // has its own [M][8] slot (a read-modify-write would put a register load among the DMA pieces).
+                const int o0 = cbase / 64;
+#pragma unroll
+                for (int i = 0; i < RT; ++i) {
+                    float sum[END_NW];
+#pragma unroll
+                    for (int q = 0; q < END_NW; ++q) sum[q] = ep[i][q] + __shfl_xor(ep[i][q], 32, 64);
+                    const int row = rbase + i * 32 + li;
+                    if (lh == 0 && row < g.M) {
+                        float* d = g.out1 + (long long)row * 8 + o0;
+#pragma unroll
+                        for (int q = 0; q < END_NW; ++q) d[q] = sum[q];
+                    }
+                }
+            }
+        }
     } else if constexpr (DMA) {
         // ---- plain DMA loop (fp16 kernels): NBUF (2 or 3) LDS buffers.  Step t: issue tile t+NBUF-1's DMA into the buffer
         // read at step t-1 (every wave has passed the barrier that ended that step), run tile t's MFMAs, then wait until all
@@ -945,7 +1031,14 @@ inline hipError_t launch_gemm(const GemmArgs& g, int batch_z, hipStream_t stream
     const int numNt = (g.N + BN - 1) / BN;
     const int numMt = (g.M + BM - 1) / BM;
     const int numMt8 = (numMt + 7) / 8 * 8;
-    const size_t lds = (size_t)NBUF * PL * (BM + BN) * LDSK * sizeof(float);
+    constexpr bool ENDP = has_end_partials<TAG, PIPE, HALF>;
+    const size_t lds = (size_t)NBUF * PL * (BM + BN) * LDSK * sizeof(float) + (ENDP ? end_table_bytes(BN) : 0);
+    if (g.end_sums) {
+        // N = 512 gives every block BN / 64 whole outputs; one A segment of K = 512 is what the table and the loop index
+        if (!ENDP || !g.out1 || g.ld1 != 8 || g.acc1 || !g.altbias || g.rowmask || g.split != g.N || !g.wide_epi || g.N != 512 ||
+            g.nseg != 1 || g.seg[0].k != END_K || g.seg[0].kpad != END_K)
+            return hipErrorInvalidValue;
+    }
     if (g.split < g.N && g.split % BN != 0) return hipErrorInvalidValue;     // output side must be uniform per block
     if (g.phase_rows > 0) {
         // tiles must not straddle phases; the interleaved-tap descriptor spans at most the whole operand (31-bit offsets)
@@ -976,7 +1069,6 @@ inline hipError_t launch_gemm(const GemmArgs& g, int batch_z, hipStream_t stream
 }
 
 // Tile configurations: BIG = 256x128 (WN layers, upsampling); SMALL = 64x64 (Tacotron2-sized problems).
-enum { TAG_GENERIC = 0, TAG_WN_IN = 1, TAG_WN_RES_SKIP = 2, TAG_WN_IN0 = 3, TAG_WN_WINO = 4 };
 // Settled choices of the WaveGlow tiles (each was a build option until its measurement was in):
 constexpr int WN_BK = 16;           // K extent of an LDS stage (the LDS-DMA image is 64-byte rows)
 constexpr int WN_OCC = 2;

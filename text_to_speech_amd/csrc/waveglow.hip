@@ -14,6 +14,7 @@
 //   acts  [8][M'][C]  gated activations tanh * sigmoid of the 8 layers of the current flow (in-layer GEMM epilogue)
 //   a0p   [M'][16]    [audio_0 | 1 | 0..]: operand of the first layer of a flow (start conv composed into its taps)
 //   audio [M'][8]     current flow state in the first n_rem columns; the last flow writes the caller's [B][L*8] directly
+//   endp  [7][M'][8]  fp32, 512 channels: acts_i @ wfold_i for layers i = 0 .. 6, second output of the layer's residual GEMM
 // Per flow: start (VALU) -> 8 x { in-layer implicit GEMM (K = 3 taps * 512 + 4 * 80 mel, N = 1024, gate epilogue),
 // residual GEMM (K = 512, N = 512; not for the last layer) } -> folded skip/end + affine inverse + inverse 1x1 conv.
 //
@@ -29,7 +30,10 @@
 //     end(sum_i skip_i) = sum_i acts_i @ (W_skip_i @ W_end) + (sum_i b_skip_i) @ W_end + b_end .
 // The 512 -> 512 skip GEMMs (and the whole res_skip conv of the last layer) disappear -- 9.6 % of the WN FLOPs and the
 // read-modify-write of a [M][512] skip buffer per layer -- and are replaced by one [M, 8*512] x [8*512, 2h] product per
-// flow (h <= 4), computed by the HBM-bound wn_end_fold_kernel straight from the stored activations.
+// flow (h <= 4), computed by the HBM-bound wn_end_fold_kernel straight from the stored activations -- in the fp16 modes and for
+// 256-channel models.  The fp32 path of a 512-channel model never re-reads them: the residual GEMM of layer i, which streams
+// acts_i as its A operand, also stores the layer's eight partial sums to endp[i] (gemm_f32.h, GemmArgs::end_sums), and
+// wn_end_last_kernel adds the seven slots, layer 7's product (the one layer without a residual GEMM) and the bias.
 //
 // fp32 calls of 144 frames or more take the Winograd form (wn_wino.hip) instead of the in-layer GEMMs above: layers 1 .. 7 as
 // F(4,3) along the taps behind a frame-axis F(4,4) conditioning plane, the first layer of a flow on that plane kernel's K loop.
@@ -535,6 +539,115 @@ __global__ __launch_bounds__(256) void wn_end_fold_kernel(const void* __restrict
     }
 }
 
+
+// fp32, 512 channels: the same on top of the flow's end partial sums.  endp[layer][m][o], layer < 7, already holds acts[layer][m] .
+// wfold[layer][o] -- the residual GEMM of that layer formed it while it streamed those activations (gemm_f32.h,
+// GemmArgs::end_sums) -- so this kernel reads the activations of layer 7 only, the one layer without a residual GEMM:
+// out = ((endp[0] + .. + endp[6]) + acts7 . wfold7) + bfold, in this order.  Lane and row ownership as above.  Rows that
+// store 0 (padding, tails, gap frames) do not read their endp.
+template <int MASK>
+__global__ __launch_bounds__(256) void wn_end_last_kernel(const float* __restrict__ acts7, const float* __restrict__ wfold7,
+                                                          const float* __restrict__ endp, const float* __restrict__ bfold,
+                                                          const float* __restrict__ inv, float* __restrict__ audio_io,
+                                                          float* __restrict__ audio_out, int out_natural,
+                                                          const float* __restrict__ z, int zoff, int n_early, float sigma,
+                                                          long long M, int h, int PR, int BT, const int* __restrict__ lens, int T) {
+    constexpr int C = 512;
+    const int lane = threadIdx.x & 63;
+    const long long m0 = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
+    if (m0 >= M) return;
+    f32x4 w0[8], w1[8], a0[RPW], a1[RPW];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        w0[o] = *reinterpret_cast<const f32x4*>(wfold7 + o * C + lane * 4);
+        w1[o] = *reinterpret_cast<const f32x4*>(wfold7 + o * C + C / 2 + lane * 4);
+    }
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+        const long long m = m0 + r < M ? m0 + r : M - 1;   // clamp: tail rows are computed but never stored
+        a0[r] = *reinterpret_cast<const f32x4*>(acts7 + m * C + lane * 4);
+        a1[r] = *reinterpret_cast<const f32x4*>(acts7 + m * C + C / 2 + lane * 4);
+    }
+    float acc[RPW * 8];                                   // index r * 8 + o
+#pragma unroll
+    for (int r = 0; r < RPW; ++r)
+#pragma unroll
+        for (int o = 0; o < 8; ++o) {
+            float p = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p = fmaf(a0[r][j], w0[o][j], p);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p = fmaf(a1[r][j], w1[o][j], p);
+            acc[r * 8 + o] = p;
+        }
+    // 64 values over 64 lanes, as in wn_end_fold_kernel: afterwards lane l holds the full sum of index l = r * 8 + o
+#pragma unroll
+    for (int half = RPW * 4, msk = 32; half >= 1; half >>= 1, msk >>= 1) {
+        const bool hi = (lane & msk) != 0;
+#pragma unroll
+        for (int i = 0; i < half; ++i) {
+            float a_lo = acc[i], a_hi = acc[i + half];
+            asm volatile("" : "+v"(a_lo), "+v"(a_hi));
+            const float send = hi ? a_lo : a_hi;
+            const float keep = hi ? a_hi : a_lo;
+            acc[i] = keep + __shfl_xor(send, msk, 64);
+        }
+    }
+    const long long m = m0 + (lane >> 3);
+    const int fr = (int)(m % PR);
+    bool real = m < M && fr < BT;
+    if constexpr (MASK != MASK_NONE) real = real && frame_masked_real<MASK>(lens, fr < BT ? fr : 0, T);
+    float part = 0.f;
+    if (real) {
+        float pl[7];
+#pragma unroll
+        for (int layer = 0; layer < 7; ++layer) pl[layer] = endp[(layer * M + m) * 8 + (lane & 7)];
+        part = pl[0];
+#pragma unroll
+        for (int layer = 1; layer < 7; ++layer) part += pl[layer];
+    }
+    const float mine = (part + acc[0]) + bfold[lane & 7];
+    float out[8];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) out[o] = __shfl(mine, (lane & ~7) + o, 64);
+    // from here on the text of wn_end_fold_kernel's last part (kept as a copy: sharing it as a function changes the register
+    // allocation of the nine instantiations of that kernel, which this path leaves as they are)
+    const int cch = 2 * h;
+    const int ph = (int)(m / PR);                              // phase-major row -> (phase, frame)
+    const long long mnat = (long long)fr * NPH + ph;           // natural position index b * L + t * 32 + p
+    if ((lane & 7) == 0 && m < M && fr < BT) {
+        if constexpr (MASK != MASK_NONE) {
+            if (!frame_masked_real<MASK>(lens, fr, T)) {
+                float* dst = audio_out + (out_natural ? mnat : m) * 8;
+                for (int j = 0; j < n_early + cch; ++j) dst[j] = 0.f;
+                return;
+            }
+        }
+        float a[8], y[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) a[j] = j < cch ? audio_io[m * 8 + j] : 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (j < h) y[j] = a[j];
+            else if (j < cch) y[j] = (a[j] - out[j - h]) / expf(out[j]);
+            else y[j] = 0.f;
+        }
+        float res[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            float t = 0.f;
+            if (c < cch) {
+                for (int j = 0; j < cch; ++j) t = fmaf(y[j], inv[j * cch + c], t);
+            }
+            res[c] = t;
+        }
+        float* dst = audio_out + (out_natural ? mnat : m) * 8;
+        for (int j = 0; j < n_early; ++j) dst[j] = z ? sigma * z[mnat * 8 + zoff + j] : 0.f;
+        for (int c = 0; c < cch; ++c) dst[n_early + c] = res[c];
+    }
+}
+
+
 // f(std::integral_constant<int, C>) for a handle's width: the one place that maps the run-time width to the <C> instantiations
 // of the kernels above (finalize admits no other width)
 template <class F>
@@ -914,6 +1027,7 @@ int ensure_workspace(tts_hip_engine* e, const WgPlan& p, int precision) {
     } else {
         HIPCHK(e, wg.acts.ensure(8 * M * C * 4));              // activations of the 8 layers of one flow
         HIPCHK(e, wg.a0p.ensure(M * 16 * 4));
+        HIPCHK(e, wg.endp.ensure(7 * M * 8 * 4));              // end partial sums of layers 0 .. 6 (512 channels only)
     }
     return TTS_HIP_OK;
 }
@@ -936,6 +1050,8 @@ struct WnCall {
     float* x32;                     // fp32 residual stream (fp16 modes: the master copy)
     float* acts;                    // gated activations of layer 0; layer i lies i * acts_stride floats behind, with x's plane
     long long acts_stride;
+    float* endp;                    // [7][M][8] end partial sums of the current flow, one slot per residual GEMM (fp32, 512
+                                    // channels: the table of gemm_f32.h is laid out for K = N = 512); else null
     bool split() const { return precision == 2; }
     float* acts_of(int i) const { return acts + i * acts_stride; }
     // a weight matrix of the call's precision (the fp16 ones exist once waveglow_build_half has run)
@@ -961,6 +1077,7 @@ WnCall wn_call(WaveGlowDev& wg, const WgPlan& p, int precision, int T, const flo
     c.x32 = wg.x.f();
     c.acts = f16 ? wg.acts16.f() : wg.acts.f();
     c.acts_stride = p.NP * p.M * C / c.unit;
+    c.endp = (precision == 0 && C == 512) ? wg.endp.f() : nullptr;
     return c;
 }
 
@@ -1004,8 +1121,9 @@ GemmArgs in_layer_args(const WnCall& c, const WgLayerDev& ly, int i) {
     return g;
 }
 
-// Residual GEMM of layer i < 7: x += acts_i @ W_res + b_res   (skip half folded into wn_end_fold)
-GemmArgs res_args(const WnCall& c, const WgLayerDev& ly, int i) {
+// Residual GEMM of layer i < 7: x += acts_i @ W_res + b_res   (skip half folded into wn_end_fold).  With c.endp the launch
+// also stores endp[i] = acts_i @ wfold_i^T, wfold_i = end_w + i * 8 * C the layer's folded end weights
+GemmArgs res_args(const WnCall& c, const WgLayerDev& ly, int i, const float* end_w) {
     const int u = c.unit, C = c.C;
     GemmArgs r{};
     r.M = (int)c.plan.M;
@@ -1028,6 +1146,12 @@ GemmArgs res_args(const WnCall& c, const WgLayerDev& ly, int i) {
         r.out0h = (_Float16*)const_cast<float*>(c.x.p);    // fp16 shadow = operand of the next layer's taps
         r.ld0h = C;
         r.planeOut = c.plan.M * C;
+    }
+    if (c.endp) {                              // (GemmArgs::end_sums: the second output of a single-output launch)
+        r.end_sums = 1;
+        r.altbias = end_w + (long long)i * 8 * C;
+        r.out1 = c.endp + (long long)i * c.plan.M * 8;
+        r.ld1 = 8;
     }
     return r;
 }
@@ -1237,7 +1361,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
             }
             if (probe_wants_layer(wg, precision, k, i)) return probe_layer(e, call, i, wino_layer);   // test hook: stop here
             if (i < 7) {
-                const GemmArgs r = res_args(call, ly, i);
+                const GemmArgs r = res_args(call, ly, i, fl.end_w);
                 timing_begin(e, 1);
                 HIPCHK(e, kn.res(r, st));
                 timing_end(e);
@@ -1249,9 +1373,22 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         const long long waves = (M + RPW - 1) / RPW;
         // elements between two layers' activations and (split fp16) from their hi to their lo plane; a call without a mask
         // passes no frame info and T = 1 (not read)
-        launch_end_fold(C, precision, mask, dim3((unsigned)((waves + 3) / 4)), st, (const void*)call.acts, plan.NP * M * C, fl.end_w,
-                        fl.end_b, fl.inv, wg.audio.f(), dst, k == 0 ? 1 : 0, d_z, zoff, early ? 2 : 0, sigma, M, h, PR, BT,
-                        precision == 2 ? M * C : 0ll, mask_info, mask == MASK_NONE ? 1 : T);
+        const dim3 egrid((unsigned)((waves + 3) / 4));
+        if (call.endp) {                                         // fp32: layer 7 on top of the residual GEMMs' partial sums
+            auto last = [&](auto kern) {
+                hipLaunchKernelGGL(kern, egrid, dim3(256), 0, st, (const float*)call.acts_of(7), (const float*)(fl.end_w + 7 * 8 * C),
+                                   (const float*)call.endp, (const float*)fl.end_b, (const float*)fl.inv, wg.audio.f(), dst,
+                                   k == 0 ? 1 : 0, d_z, zoff, early ? 2 : 0, sigma, M, h, PR, BT, mask_info,
+                                   mask == MASK_NONE ? 1 : T);
+            };
+            if (mask == MASK_FLAGS) last(wn_end_last_kernel<MASK_FLAGS>);
+            else if (mask == MASK_LENS) last(wn_end_last_kernel<MASK_LENS>);
+            else last(wn_end_last_kernel<MASK_NONE>);
+        } else {
+            launch_end_fold(C, precision, mask, egrid, st, (const void*)call.acts, plan.NP * M * C, fl.end_w, fl.end_b, fl.inv,
+                            wg.audio.f(), dst, k == 0 ? 1 : 0, d_z, zoff, early ? 2 : 0, sigma, M, h, PR, BT,
+                            precision == 2 ? M * C : 0ll, mask_info, mask == MASK_NONE ? 1 : T);
+        }
         HIPCHK(e, hipGetLastError());
         if (probe_wants_state(wg, k))                            // test hook: the state after this flow
             return probe_state(e, plan, dst, k == 0 ? 1 : 0, 2 * h + (early ? 2 : 0));
