@@ -3,7 +3,8 @@
 The three decoder machines -- the persistent kernel (csrc/taco_persist.hip), the fused two-kernel step replayed in 64-step
 chunks (csrc/taco_fused.hip) and the 7-kernel per-step graph replayed in 32-step chunks (csrc/tacotron2.hip) -- are each
 compiled into many template instantiations.  `pick_variant` restates their dispatch rules, so a test can say which
-instantiation a call must take and check that the case table reaches every one of them.
+instantiation a call must take and check that the case table reaches every one of them.  `WINDOW_CASES` run the attention
+window (`Case.win`), which each machine implements on its own, on every machine and precision their shapes allow.
 
 References come from the numpy oracle, once per case and weight rounding (`reference`):
 - 'f32': the oracle as it is;
@@ -24,10 +25,14 @@ MEL_TOL = 1e-3              # north star (BASELINE.json): mel, decoder frames an
 # test_decoder_variants_gpu.py (fp16 calls against the rounded-weight reference, fp32 calls against the fp32 oracle).
 MEL_REG = 3e-5              # frames (decoder_output, mel) and fixed-step stop tokens, max abs: measured 2.71e-6 (mel, b8_len63,
                             # fp16, graph; fp32 worst 2.68e-6, b8_tin256, graph); stop tokens 6.7e-8
+                            # window cases: mel 2.62e-6 (win_stop_b3_64, fp16, fused), frames 1.79e-6 (win_stop_b3_64, fp32,
+                            # persistent), stop tokens 6.7e-8 (win_b3_len66, fp16, persistent)
 ATT_REG = 2.5e-6            # attention weights, RMS of the error / RMS of the reference: measured 2.24e-7 (e768_b1_tin100,
                             # fp16, persistent); max abs 1.64e-7
+                            # window cases: 2.18e-7 (win_stop_b3_64, fp32, persistent); max abs 1.79e-7 (win_b5_tin129, fp32,
+                            # fused: two positions share the mass, so the weights are large)
 STOP_REG = 4e-6             # scripted-stop cases: stop-token bound per unit of the fitted gate's norm (`sensitivity`):
-                            # measured 3.62e-7 (stop_b2_33, fp16, persistent)
+                            # measured 3.62e-7 (stop_b2_33, fp16, persistent); window case 2.30e-7 (win_stop_b3_64, fp16, fused)
 
 GRAPH_CHUNK, FUSED_CHUNK = 32, 64       # tacotron2.hip CHUNK, taco_fused.h FUSED_CHUNK
 N_CU = 256                              # MI355X; both whole-GPU machines need 256 resident blocks
@@ -141,10 +146,16 @@ class Case(NamedTuple):
     enc: int = 512
     targets: Optional[tuple] = None     # scripted stops (tests/stop_script.py): early stopping with these `lengths`
     seed: int = 0
+    win: Optional[tuple] = None         # attention window (win_len, win_off), integers as the C API takes them
 
     @property
     def early_stopping(self):
         return self.targets is not None
+
+    @property
+    def win_kwargs(self):
+        """The window as keyword arguments of `tacotron2_ref.infer` and of `HipEngine.tacotron2_infer` alike."""
+        return {} if self.win is None else dict(attn_mask_win_len=self.win[0], attn_mask_offset=self.win[1])
 
 
 _C = Case
@@ -174,6 +185,26 @@ CASES = (
     _C('stop_b3_64', 3, 100, 129, targets=(31, 63, 33), seed=2),
     _C('stop_b2_33', 2, 150, 100, targets=(32, 31), seed=3),
 )
+# The attention window (win_len, win_off): the arg max of step t's alignment, an integer, decides which energies step t + 1
+# masks -- implemented once per machine.  Seeds and windows are chosen so that the conditions of test_decoder_variants.py
+# hold on the oracle alone: arg-max gap, the window bites, both clamps and the free range occur, the window keeps moving.
+WINDOW_CASES = (
+    # fused NBT 4 / KT 1 and persistent NBT 4; the window still moves across the graph (32) and fused (64) chunk edges; the
+    # row of 20 tokens sits on the upper clamp
+    _C('win_b3_len66', 3, 60, 66, win=(12, 6)),
+    # fused NBT 8 / KT 2 and its fp16 two-positions-per-wave branch; rows of 5 and 11 tokens are shorter than the window (lo < 0)
+    _C('win_b8_tin256', 8, 256, 40, win=(16, 8), seed=1),
+    _C('win_b1_tin512', 1, 512, 40, win=(40, 20), seed=3),                  # persistent KT 8
+    _C('win_b2_tin200', 2, 200, 40, win=(24, 0)),                           # persistent NBT 2 / KT 4, fused KT 2; offset 0
+    _C('win_b1_tin513', 1, 513, 40, win=(24, 8)),                           # graph only: stride-256 loops and their tail
+    _C('win_b11_tin40', 11, 40, 34, win=(8, 2)),                            # graph, two LSTM launches, past its 32-step chunk
+    _C('win_e768_b4_tin100', 4, 100, 66, 768, win=(12, 2)),                 # enc 768: fused ENC 768 and persistent
+    _C('win_e768_b1_tin300', 1, 300, 40, 768, win=(2, 1)),                  # three positions; graph and persistent KT 8
+    _C('win_b5_tin129', 5, 129, 40, win=(1, 0)),                            # two positions (inclusive upper bound); fused NBT 8 / KT 2
+    # scripted stops with the window: finished rows keep moving their arg max until every row has fired
+    _C('win_stop_b3_64', 3, 100, 129, targets=(31, 63, 33), seed=2, win=(12, 6)),
+)
+CASES += WINDOW_CASES
 CASE_BY_NAME = {c.name: c for c in CASES}
 
 
@@ -218,7 +249,7 @@ def scripted(name):
     case = CASE_BY_NAME[name]
     tok, spk, masks = inputs(case)
     return script_stop_tokens(base_weights(case.enc), config(case.enc), tok, list(case.targets), speaker_embedding=spk,
-                              prenet_masks=masks)
+                              prenet_masks=masks, **case.win_kwargs)
 
 
 def weights_key(case):
@@ -238,7 +269,7 @@ def _weights_rounded(key, enc, kind):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(name, kind, zero_speaker=False, max_len=None):
+def _reference(name, kind, zero_speaker=False, max_len=None, windowed=True):
     from oracle import tacotron2_ref
     case = CASE_BY_NAME[name]
     tok, spk, masks = inputs(case)
@@ -247,12 +278,24 @@ def _reference(name, kind, zero_speaker=False, max_len=None):
     T = case.max_len if max_len is None else max_len
     return tacotron2_ref.infer(tok, _weights_rounded(weights_key(case), case.enc, kind), config(case.enc),
                                speaker_embedding=spk, max_length=T, early_stopping=case.early_stopping,
-                               prenet_masks=masks[:, :T])
+                               prenet_masks=masks[:, :T], **(case.win_kwargs if windowed else {}))
 
 
-def reference(case, kind='f32', zero_speaker=False, max_len=None):
-    """Oracle output of `case` with the weights rounded as `kind` says (module docstring); cached per process."""
-    return _reference(case.name, kind, zero_speaker, max_len)
+def reference(case, kind='f32', zero_speaker=False, max_len=None, windowed=True):
+    """Oracle output of `case` with the weights rounded as `kind` says (module docstring); cached per process.
+    `windowed=False` drops the case's attention window."""
+    return _reference(case.name, kind, zero_speaker, max_len, windowed)
+
+
+def window_bounds(case, attention):
+    """(prev, lo, hi), int [B, steps] each, of a window case, from alignments [B, steps, Tin] (tacotron2_arch.py:630-638):
+    `prev` is the arg max of the step before (0 at step 0); the step keeps positions lo <= tau <= hi."""
+    win_len, win_off = case.win
+    am = np.asarray(attention).argmax(-1)
+    prev = np.concatenate([np.zeros((case.B, 1), np.int64), am[:, :-1]], 1)
+    enc_len = np.asarray(lens_of(case))[:, None]
+    center = np.minimum(np.maximum(prev, win_off), enc_len - win_len + win_off)
+    return prev, center - win_off, center - win_off + win_len
 
 
 def machines(case, precision):

@@ -1,7 +1,8 @@
 """CPU half of the decoder-variant matrix (tests/decoder_cases.py): the case table reaches every instantiation of the three
 decoder machines, and every case could fail -- oracle-only controls showing that the regression bounds of
 test_decoder_variants_gpu.py would catch a wrong frame, a wrong chunk edge, a dropped long-input half, a lost speaker
-embedding or an ignored fp16 flag."""
+embedding or an ignored fp16 flag.  For the attention-window cases: the oracle's arg max is decided by a margin far above any
+machine's error, the window changes the frames, both clamps and the free range occur, and the window keeps moving."""
 import numpy as np
 import pytest
 
@@ -112,7 +113,7 @@ def test_consecutive_frames_differ_far_beyond_the_bound(name):
     assert d.min() >= 20 * dc.MEL_REG, (d.min(), np.unravel_index(d.argmin(), d.shape))
 
 
-@pytest.mark.parametrize('name', [c.name for c in dc.CASES if c.Tin > 128])
+@pytest.mark.parametrize('name', [c.name for c in dc.CASES if c.Tin > 128 and c.win is None])     # (a window confines the mass)
 def test_long_inputs_put_attention_past_position_128(name):
     """In rows longer than 128 tokens, the positions >= 128 carry at least 10 % of the attention mass (for 129 - 150
     tokens: at least half of what uniform attention would put there), and dropping them would move the attention far
@@ -187,3 +188,98 @@ def test_scripted_stops_are_realisable(name):
         ref = dc.reference(case, kind)
         assert ref.lengths.tolist() == list(case.targets), (kind, ref.lengths)
     assert max(case.targets) + 1 < case.max_len                          # the loop ends by the stop tokens
+
+
+# ---- the attention window ------------------------------------------------------------------------------------------------------
+WINDOW_IDS = [c.name for c in dc.WINDOW_CASES]
+ARGMAX_GAP = 5e-6               # about 30x the worst attention max-abs error measured on an MI355X (1.8e-7, decoder_cases.ATT_REG)
+# the instantiations each window case is there for: machine -> `Variant.inst` without its HW flag, (NBT, KT, enc) persistent /
+# (NBT, ENC, KT) fused; 'graph': the rows of the call
+WINDOW_REACHES = {
+    'win_b3_len66': {'persistent': (4, 2, 512), 'fused': (4, 512, 1), 'graph': 3},
+    'win_b8_tin256': {'fused': (8, 512, 2), 'graph': 8},
+    'win_b1_tin512': {'persistent': (1, 8, 512), 'graph': 1},
+    'win_b2_tin200': {'persistent': (2, 4, 512), 'fused': (4, 512, 2), 'graph': 2},
+    'win_b1_tin513': {'graph': 1},
+    'win_b11_tin40': {'graph': 11},
+    'win_e768_b4_tin100': {'persistent': (4, 2, 768), 'fused': (4, 768, 1), 'graph': 4},
+    'win_e768_b1_tin300': {'persistent': (1, 8, 768), 'graph': 1},
+    'win_b5_tin129': {'fused': (8, 512, 2), 'graph': 5},
+    'win_stop_b3_64': {'persistent': (4, 2, 512), 'fused': (4, 512, 1), 'graph': 3},
+}
+
+
+def _window(name, kind='f32'):
+    """(case, ref, steps, prev, lo, hi) of a window case on the oracle with weights rounded as `kind`."""
+    case = dc.CASE_BY_NAME[name]
+    ref = dc.reference(case, kind)
+    T = _steps(case, ref)
+    return (case, ref, T, *dc.window_bounds(case, ref.attention_weights[:, :T]))
+
+
+def test_window_cases_reach_their_machines():
+    assert set(WINDOW_REACHES) == set(WINDOW_IDS)
+    for name, want in WINDOW_REACHES.items():
+        case = dc.CASE_BY_NAME[name]
+        for precision in PRECISIONS:
+            got = dict(dc.machines(case, precision))
+            assert set(got) == set(want), (name, precision, sorted(got))        # exactly these machines accept the shape
+            for m, inst in want.items():
+                if m == 'graph':
+                    assert case.B == inst
+                else:
+                    assert got[m].inst == (*inst, precision == 'f16'), (name, m, got[m])
+    assert dc.pick_variant('fused', 8, 256, 512, 'f16').two_pairs                    # the two-positions-per-wave branch
+    assert len(dc.pick_variant('graph', 11, 40, 512, 'f32').inst) == 4               # two LSTM launches (8 + 3 rows) per step
+    assert dc.CASE_BY_NAME['win_b11_tin40'].max_len > dc.GRAPH_CHUNK
+    for name in ('win_b3_len66', 'win_e768_b4_tin100'):
+        assert dc.CASE_BY_NAME[name].max_len > dc.FUSED_CHUNK + 1                    # steps 64 and 65 run in the second chunk
+
+
+@pytest.mark.parametrize('name', WINDOW_IDS)
+def test_window_arg_max_is_decided_with_margin(name):
+    """The arg max, and with it the next window, is discontinuous in the weights: on every reference a machine is compared
+    with, the two largest weights of every (row, step) differ by >= ARGMAX_GAP, so a correct kernel cannot land in another
+    window than the oracle."""
+    for kind in ('f32', 'f16', 'f16_ctx32'):
+        case, ref, T, prev, lo, hi = _window(name, kind)
+        a = np.sort(ref.attention_weights[:, :T].astype(np.float64), axis=-1)
+        gap = float((a[..., -1] - a[..., -2]).min())
+        print(f'{name}: {kind}: smallest arg-max gap {gap:.2e}')
+        assert gap >= ARGMAX_GAP, (kind, gap)
+        # the oracle itself keeps to the window it is asked for
+        tau = np.arange(case.Tin)
+        outside = (tau < lo[..., None]) | (tau > hi[..., None])
+        assert np.all(ref.attention_weights[:, :T][outside] == 0)
+
+
+@pytest.mark.parametrize('name', WINDOW_IDS)
+def test_window_bites(name):
+    """A machine that ignored the window would give the frames of the call without one: >= 1000x MEL_REG away."""
+    case = dc.CASE_BY_NAME[name]
+    d = float(np.abs(dc.reference(case).mel - dc.reference(case, windowed=False).mel).max())
+    print(f'{name}: mel with the window vs without: {d:.2e}')
+    assert d >= 1000 * dc.MEL_REG, d
+
+
+def test_window_cases_cover_both_clamps_and_keep_moving():
+    lower = upper = free = short_rows = 0
+    for name in WINDOW_IDS:
+        case, ref, T, prev, lo, hi = _window(name)
+        win_len, win_off = case.win
+        enc_len = np.asarray(dc.lens_of(case))[:, None]
+        lo_clamp, hi_clamp = prev < win_off, prev > enc_len - win_len + win_off
+        n = (int(lo_clamp.sum()), int(hi_clamp.sum()), int((~lo_clamp & ~hi_clamp).sum()))
+        distinct = [len(set(lo[b])) for b in range(case.B)]
+        print(f'{name}: row-steps on the lower clamp {n[0]}, on the upper {n[1]}, free {n[2]}; distinct window starts per row '
+              f'{distinct}' + ''.join(f'; starts at step {e} {lo[:, e].tolist()}' for e in (32, 64) if e < T))
+        lower, upper, free = lower + n[0], upper + n[1], free + n[2]
+        short_rows += int((enc_len < win_len).sum())
+        if name in ('win_b3_len66', 'win_b8_tin256', 'win_b2_tin200', 'win_b11_tin40'):
+            long_rows = [b for b in range(case.B) if enc_len[b, 0] >= 2 * win_len]
+            assert long_rows and all(distinct[b] >= 3 for b in long_rows), (name, distinct)
+        if name in ('win_b3_len66', 'win_e768_b4_tin100'):
+            assert T > 64 and np.any(lo[:, 64] != lo[:, 0]), (name, lo[:, 0], lo[:, 64])    # still moving in the second fused chunk
+        if name == 'win_b11_tin40':
+            assert np.any(lo[:, 32] != lo[:, 0])                                            # ... and in the second graph chunk
+    assert lower and upper and free and short_rows, (lower, upper, free, short_rows)

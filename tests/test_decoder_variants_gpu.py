@@ -1,5 +1,5 @@
 """GPU half of the decoder-variant matrix (tests/decoder_cases.py): every case on every decoder machine that accepts it, in
-both precisions, against the numpy oracle -- fp32 calls against the fp32 oracle, fp16 calls against the oracle with the
+both precisions (the attention-window cases included), against the numpy oracle -- fp32 calls against the fp32 oracle, fp16 calls against the oracle with the
 same weights rounded to fp16 -- at the north-star bound and at the much tighter regression bounds of decoder_cases.py.
 
 Each call first asserts that the requested machine really ran (a shape the machine does not accept, or an exchange
@@ -42,7 +42,7 @@ def _run(eng, case, machine, precision):
     eng.set_decoder_mode(machine)
     try:
         out = eng.tacotron2_infer(tok, speaker=spk, max_len=case.max_len, early_stopping=case.early_stopping,
-                                  prenet_masks=masks, precision=precision)
+                                  prenet_masks=masks, precision=precision, **case.win_kwargs)
         ran = eng.last_decoder_mode
     finally:
         eng.set_decoder_mode('auto')
@@ -89,6 +89,16 @@ def test_decoder_variant_matches_oracle(engines, name):
             for b in range(case.B):
                 if not np.all(out.attention_weights[b, :, dc.lens_of(case)[b]:] == 0):
                     failures.append(f'{tag}: row {b}: attention on padded positions')
+            if case.win is not None:
+                # exactly zero outside the window that the oracle's arg max of the step before puts around each step
+                _, lo, hi = dc.window_bounds(case, ref.attention_weights[:, :steps])
+                tau = np.arange(case.Tin)
+                outside = (tau < lo[..., None]) | (tau > hi[..., None])
+                bad = np.argwhere(outside & (out.attention_weights[:, :steps] != 0))
+                if len(bad):
+                    b, t, pos = bad[0]
+                    failures.append(f'{tag}: {len(bad)} nonzero weights outside the window, first at row {b} step {t} position '
+                                    f'{pos} (window {lo[b, t]} .. {hi[b, t]})')
             if case.early_stopping:
                 for b, n in enumerate(ref.lengths):
                     d = float(np.abs(out.decoder_output[b, n] - ref.decoder_output[b, n]).max())

@@ -228,3 +228,18 @@ def test_both_checks_equal_their_restatement_on_random_calls(checker):
         seen.add((kind, re.sub(r'-?\d+', '#', why)))
     for kind in ('encode', 'decode', 'forward', 'infer'):                        # the loop reached acceptance and the reasons
         assert (kind, '') in seen and sum(k == kind for k, _ in seen) >= 4, sorted(seen)
+
+
+# ---- the attention window's two integers (HipEngine.tacotron2_infer / tacotron2_decode) -----------------------------------------
+def test_attention_window_is_two_integers_or_an_error():
+    from text_to_speech_amd.engine import attention_window
+    assert attention_window(None, 0) == (0, 0) and attention_window(None, 0.5) == (0, 0) and attention_window(0, 3) == (0, 0)
+    assert attention_window(12, 6) == (12, 6) and attention_window(12, None) == (12, 0) and attention_window(1, 0) == (1, 0)
+    got = attention_window(np.int64(13), np.float32(6.0))                        # whole numbers of any numeric type
+    assert got == (13, 6) and all(type(v) is int for v in got)
+    for offset in (0.5, 0.3, np.float32(6.5)):                                   # the reference's default, passed at this level
+        with pytest.raises(ValueError, match=r'HipRuntime\.tacotron2_infer'):
+            attention_window(12, offset)
+    for win_len in (-1, -12, 2.5):
+        with pytest.raises(ValueError, match='attn_mask_win_len'):
+            attention_window(win_len, 0)

@@ -31,6 +31,21 @@ def _u64(v):
     return ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
 
 
+def attention_window(win_len, offset):
+    """(win_len, win_off) as the ints the C API takes; `None` / 0 window -> (0, 0) (no window).  The offset is in positions
+    here: a fraction of the window (the reference's default 0.5) is resolved by `HipRuntime.tacotron2_infer`."""
+    if win_len is None or win_len == 0:
+        return 0, 0
+    if win_len != int(win_len) or win_len < 0:
+        raise ValueError(f'attn_mask_win_len must be a non-negative integer, got {win_len!r}')
+    if offset is None:
+        offset = 0
+    if offset != int(offset):
+        raise ValueError(f'attn_mask_offset must be a whole number of positions at this level, got {offset!r}: '
+                         'HipRuntime.tacotron2_infer resolves a fraction of the window')
+    return int(win_len), int(offset)
+
+
 class MelFn:
     """A mel plan of one engine (tts_hip_mel_fn; `HipEngine.mel_fn`).  It is freed when the engine closes."""
 
@@ -440,6 +455,7 @@ class HipEngine:
                         precision: str = 'f32', row_mask_seeds=None):
         """tokens int32 [B, Tin] -> Tacotron2InferenceOutput of numpy arrays (or torch tensors for CUDA tokens).
         precision 'f16': decoder LSTM weights in fp16 (fp32 accumulate and state).
+        `attn_mask_win_len` / `attn_mask_offset`: the attention window, both in positions (`attention_window`).
         `row_mask_seeds=(keys, offsets)` (excludes `prenet_masks`): the prenet dropout masks are drawn on the device, row b
         from its own stream (encode + `tacotron2_decode(row_mask_seeds=...)`)."""
         pcode = self._taco_precision(precision)
@@ -453,6 +469,7 @@ class HipEngine:
                                              want_attention=want_attention, precision=precision, row_mask_seeds=row_mask_seeds)
             finally:
                 enc.close()
+        win_len, win_off = attention_window(attn_mask_win_len, attn_mask_offset)
         dev = _is_torch_cuda(tokens)
         self._check_device(tokens)
         max_len = int(max_len)
@@ -470,7 +487,7 @@ class HipEngine:
         name = 'tacotron2_infer' + ('_f16' if pcode else '')               # one symbol per precision
         self._check(getattr(self._lib, 'tts_hip_' + name)(
             self._h, self._ptr(tok), int(tok.shape[0]), int(tok.shape[1]), self._ptr(spk), max_len, 1 if early_stopping else 0,
-            self._ptr(masks), int(attn_mask_win_len or 0), int(attn_mask_offset), *map(self._ptr, (mel, dec, stop, attn, lengths)),
+            self._ptr(masks), win_len, win_off, *map(self._ptr, (mel, dec, stop, attn, lengths)),
             ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), mem), 'tacotron2_infer')
         self.last_steps = int(steps.value)
         return Tacotron2InferenceOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn, lengths=lengths)
@@ -514,6 +531,7 @@ class HipEngine:
         source = given[0] if given else 'tensor'
         row_tables = None if row_mask_seeds is None else self._row_tables(row_mask_seeds, encoded.B, 'row_mask_seeds')
         pcode = self._taco_precision(precision)
+        win_len, win_off = attention_window(attn_mask_win_len, attn_mask_offset)
         self._check_encoded(encoded)
         B, Tin, dev = encoded.B, encoded.Tin, encoded.on_device
         max_len = int(max_len)
@@ -531,7 +549,7 @@ class HipEngine:
         self._check(getattr(self._lib, 'tts_hip_' + name)(
             self._h, encoded.handle, max_len, 1 if early_stopping else 0,
             *mid(self._ptr, {'tensor': masks, 'seed': mask_seed, 'rows': row_tables}[source]),
-            int(attn_mask_win_len or 0), int(attn_mask_offset), pcode, *map(self._ptr, (mel, dec, stop, attn, lengths)),
+            win_len, win_off, pcode, *map(self._ptr, (mel, dec, stop, attn, lengths)),
             ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), mem, sp), name)
         self.last_steps = int(steps.value)
         return Tacotron2InferenceOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn, lengths=lengths)
