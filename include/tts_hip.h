@@ -285,6 +285,27 @@ int tts_hip_tacotron2_probe_postnet(tts_hip_engine* e, const float* frames, int 
  * 3 - 7: postnet convs 1 - 5; a conv that has not run yet reads 0.  -1 before the first conv.                             */
 int tts_hip_last_conv_paths(const tts_hip_engine* e);
 
+/* ---- WaveGlow forward flow: audio -> z and the terms of its log-likelihood (Prenger et al. 2018, section 2; the direction the
+ * published model is trained and scored with, which the reference's `call` does not contain: waveglow_arch.py:241-242).
+ * fp32, at both model widths, in the form tts_hip_set_waveglow_form selects for a call of B * T frames.
+ *   audio [B, T*256], mel [B, T, 80]; `lengths` NULL or host int32 [B] in [0, T] (read before the call returns).
+ *   z [B, T*32, 8] in exactly the layout tts_hip_waveglow_infer* consumes (channels 0..3 the final state, 4..5 what left before
+ *     flow 8, 6..7 what left before flow 4): tts_hip_waveglow_infer(mel, z, sigma = 1) returns the audio.
+ *   stats [3, B], per row over its real positions: stats[0] = sum z^2 (all 8 channels), stats[1] = sum over flows, positions
+ *     and coupling channels of s, stats[2] = lengths[b] * 32 * sum_k log |det kernel_k[0]|.  The negative log-likelihood per
+ *     sample under N(0, sigma^2) is (stats[0] / (2 sigma^2) - stats[1] - stats[2]) / (lengths[b] * 256).
+ *   z or stats may be NULL (not both).  With lengths: audio and mel beyond a row's length are never read by a kernel, z is 0
+ *   there, and a row gets what a call on its own frames gives it (the contract of tts_hip_waveglow_infer_ragged).
+ * The sums use no floating-point atomics and float64 partial sums in a fixed order: repeats are bit-equal.
+ * `mem`, `stream`, and when the call returns: the shared contract of the tts_hip_waveglow_infer* block.  Refused with
+ * TTS_HIP_EINVAL before anything is copied or launched, the message starting with the symbol's name, first match wins: bad
+ * `mem`; B <= 0; audio or mel NULL, or T <= 0; z and stats both NULL; a lengths[b] outside [0, T]; B * T above one run
+ * (31 744 frames: the call is one run, slice the batch by rows).  Armed probe hooks are ignored.                         */
+int tts_hip_waveglow_encode(tts_hip_engine* e, const float* audio, const float* mel, int B, int T, const int32_t* lengths,
+                            float* z, float* stats, int mem);
+int tts_hip_waveglow_encode_async(tts_hip_engine* e, const float* audio, const float* mel, int B, int T, const int32_t* lengths,
+                                  float* z, float* stats, void* stream);
+
 /* How the fp32 WaveGlow path evaluates the k = 3 dilated convolution of WN layers 1 .. 7 (waveglow_arch.py:117-127).
  * form 1 (default): Winograd minimal filtering along the tap axis for calls of 144 frames or more (any utterance length;
  * csrc/wn_wino.hip) -- F(4,3), six products per four outputs: K per output ~800 + 320 instead of 1536 + 320, fp32 operands

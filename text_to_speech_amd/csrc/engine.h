@@ -64,6 +64,8 @@ struct WgFlowDev {
     float* end_w = nullptr;     // [8 layers][8][512] skip halves folded into the end conv (rows >= 2*n_half are zero)
     float* end_b = nullptr;     // [8]
     float* inv = nullptr;       // [n_rem][n_rem]  out = audio @ inv
+    float* fwd = nullptr;       // [n_rem][n_rem]  the kernel itself: out = audio @ fwd (forward flow, wg_encode.hip)
+    double log_det = 0.0;       // log |det fwd|
     WgLayerDev layer[8];
 };
 struct WaveGlowDev {
@@ -90,11 +92,15 @@ struct WaveGlowDev {
     DevBuf wino_U, wino_P, wino_mel;         // mel planes; forms 2 / 3 only: transformed inputs [6][M/4][512], products [6][M/4][1024]
     DevBuf wino_cond;                        // conditioning plane of the current layer [32 PR][1024]
     DevBuf wino_taps;                        // tap operand of the current flow's first layer [32 PR][16]
+    DevBuf enc_ws;                           // forward flow (wg_encode.hip): [sum_j s per position | partial sums of the statistics]
+    DevBuf enc_audio, enc_z;                 // forward flow: a host caller's audio; [z | stats] of a host caller, or whichever of
+                                             //   the two a device caller passed NULL for
     // ... and listed here, which is what waveglow_free releases
     template <class F>
     void for_each_buf(F f) {
         for (DevBuf* b : {&x, &acts, &audio, &a0p, &endp, &x16, &acts16, &a0p16, &mel16, &io_mel, &io_z, &io_out, &io_zgen, &mel_ragged,
-                          &ragged_info, &packed_z, &packed_out, &wino_U, &wino_P, &wino_mel, &wino_cond, &wino_taps})
+                          &ragged_info, &packed_z, &packed_out, &wino_U, &wino_P, &wino_mel, &wino_cond, &wino_taps, &enc_ws, &enc_audio,
+                          &enc_z})
             f(*b);
     }
 };
@@ -298,6 +304,32 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
 // packed call: mel / z / audio in the batch layout, d_info = [start[B] | len[B] | flags[F] | gap frames[n_gap]] (waveglow.hip)
 int waveglow_run_packed(tts_hip_engine* e, const float* d_mel, int B, int T, const float* d_z, float sigma, float* d_audio,
                         int precision, const int* d_info, int F, int n_gap);
+// forward flow, audio -> z and its statistics (fp32; one run: B * T <= kMaxFramesPerRun).  d_z [B, T*32, 8] and d_stats
+// [3, B] are device buffers, both written; d_lens / d_tail / n_tail as for waveglow_run
+int waveglow_encode_run(tts_hip_engine* e, const float* d_audio, const float* d_mel, int B, int T, const int* d_lens,
+                        const int* d_tail, int n_tail, float* d_z, float* d_stats);
+// its position-wise kernels (wg_encode.hip); mask: 0 every frame is real, 1 the first d_lens[b] of each row
+int wg_encode_init(tts_hip_engine* e, const float* d_audio, const float* fwd0, float* state, int PR, int BT, const int* d_lens, int T);
+struct WgEncodeEnd {
+    int C;                          // n_channels of the handle
+    const float* acts;              // gated activations of the flow's eight layers, layer_stride floats apart
+    long long layer_stride;
+    const float *wfold, *bfold;     // the flow's folded skip / end weights
+    float* state;                   // [M][8] phase-major flow state, updated in place
+    float* slog;                    // [M] sum over flows and coupling channels of s, per position
+    int first;                      // flow 0: slog is stored, not added to
+    const float* next;              // the next flow's matrix [n][n], n = 2 h - n_early; null after the last flow
+    float* z;                       // [B, T*32, 8]: the n_early channels that leave go to z[.., zoff ..], the last flow's 4 to z[.., 0 ..]
+    int zoff, n_early;
+    long long M;
+    int h, PR, BT;
+    const int* d_lens;              // null: every frame is real
+    int T;
+};
+int wg_encode_end(tts_hip_engine* e, const WgEncodeEnd& a);
+size_t wg_encode_stats_bytes(int B);    // the partial sums of wg_encode_stats
+int wg_encode_stats(tts_hip_engine* e, const float* d_z, const float* slog, double* part, const int* d_lens, int B, int T, int PR,
+                    double log_det_sum, float* d_stats);
 void waveglow_free(tts_hip_engine* e);
 
 int tacotron2_finalize(tts_hip_engine* e);

@@ -463,6 +463,62 @@ static WgCall wg_call(const char* who, const float* mel, int B, int T, const int
     return c;
 }
 
+// Both tts_hip_waveglow_encode entry points: check, then the lengths table, staging and the one run, on one stream.
+static int waveglow_encode_call(tts_hip_engine* e, const WgEncode& c) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
+    char why[512];
+    if (int rc = wg_encode_check(c, why, sizeof why)) return set_err(e, rc, "%s", why);
+    HIPCHK(e, hipSetDevice(e->device));
+    StreamScope scope(e, c.async ? c.stream : nullptr);
+    WaveGlowDev& wg = e->wg;
+    const int B = c.B, T = c.T;
+    WgTable& tab = wg.call_table;
+    const int* d_lens = nullptr;
+    if (c.lengths) {                                             // [lengths | tail frames] of the one run
+        wg_call_table(B, T, c.lengths, false, B, &tab);
+        HIPCHK(e, wg.ragged_info.ensure(tab.info.size() * sizeof(int)));
+        HIPCHK(e, hipMemcpyAsync(wg.ragged_info.p, tab.info.data(), tab.info.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        d_lens = (const int*)wg.ragged_info.p;
+    }
+    const size_t n_audio = (size_t)B * T * 256, n_mel = (size_t)B * T * 80;
+    const bool host = !c.async && c.mem == TTS_HIP_MEM_HOST;
+    const float *d_audio = c.audio, *d_mel = c.mel;
+    float *d_z = c.z, *d_stats = c.stats;
+    if (host) {
+        HIPCHK(e, wg.enc_audio.ensure(n_audio * 4));
+        HIPCHK(e, wg.io_mel.ensure(n_mel * 4));
+        HIPCHK(e, hipMemcpyAsync(wg.enc_audio.p, c.audio, n_audio * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(e, hipMemcpyAsync(wg.io_mel.p, c.mel, n_mel * 4, hipMemcpyHostToDevice, e->stream));
+        d_audio = wg.enc_audio.f(), d_mel = wg.io_mel.f();
+        d_z = d_stats = nullptr;
+    }
+    if (!d_z || !d_stats) {                                      // the run writes both: [z | stats] it was not given a place for
+        HIPCHK(e, wg.enc_z.ensure((n_audio + 3 * (size_t)B) * 4));
+        if (!d_z) d_z = wg.enc_z.f();
+        if (!d_stats) d_stats = wg.enc_z.f() + n_audio;
+    }
+    int rc = waveglow_encode_run(e, d_audio, d_mel, B, T, d_lens, d_lens ? d_lens + B : nullptr, c.lengths ? tab.run_tails[0] : 0,
+                                 d_z, d_stats);
+    if (rc || c.async) return rc;
+    if (host && c.z) HIPCHK(e, hipMemcpyAsync(c.z, d_z, n_audio * 4, hipMemcpyDeviceToHost, e->stream));
+    if (host && c.stats) HIPCHK(e, hipMemcpyAsync(c.stats, d_stats, 3 * (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return TTS_HIP_OK;
+}
+
+int tts_hip_waveglow_encode(tts_hip_engine* e, const float* audio, const float* mel, int B, int T, const int32_t* lengths, float* z,
+                            float* stats, int mem) {
+    const WgEncode c{"tts_hip_waveglow_encode", audio, mel, B, T, lengths, z, stats, false, mem, nullptr};
+    return waveglow_encode_call(e, c);
+}
+
+int tts_hip_waveglow_encode_async(tts_hip_engine* e, const float* audio, const float* mel, int B, int T, const int32_t* lengths,
+                                  float* z, float* stats, void* stream) {
+    const WgEncode c{"tts_hip_waveglow_encode_async", audio, mel, B, T, lengths, z, stats, true, TTS_HIP_MEM_DEVICE, stream};
+    return waveglow_encode_call(e, c);
+}
+
 int tts_hip_waveglow_infer(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,
                            float* audio, int mem) {
     WgCall c = wg_call("tts_hip_waveglow_infer", mel, B, T, nullptr, false, WG_NOISE_Z, sigma, audio, 0, false);

@@ -17,6 +17,10 @@
 // null=mel,audio,keys,offsets to pass that pointer as NULL.  First line "<status> <message>" of wg_call_check; when the call
 // is accepted: "F n_gap", then the lines "info ...", "run_tails ..." and "counts ..." of wg_call_table
 // (tests/test_wg_call.py compares them with packing_plan and a numpy restatement).
+//        ttsw_check_asan --wg-encode T [KEY=VALUE...] [LEN...]  -- the front end of a forward-flow call (wg_encode_check of
+// wg_call.h) for a batch of B = number of LEN rows (no LEN: lengths NULL, B from B=) run as an entry point named "who".
+// Settings: B= mem= async=1 and null=audio,mel,z,stats.  One line "<status> <message>" (tests/test_waveglow_encode.py compares
+// it with a Python restatement of the refusal order).
 //        ttsw_check_asan --audio-call KIND [KEY=VALUE...] [LEN...]  -- the front end of an audio call (audio_call.h), KIND one
 // of reduce_noise, trim, resample, silence, for a batch of B = number of LEN rows of N samples (no LEN: lengths NULL, B from
 // B=) run as an entry point named "who".  Settings: B= N= mem= (default 1, device), null=audio,out,lens (out: every output
@@ -134,6 +138,35 @@ static int print_wg_call(int argc, char** argv) {
     printf("\ncounts");
     for (long long v : t.counts) printf(" %lld", v);
     printf("\n");
+    return 0;
+}
+
+static int print_wg_encode(int argc, char** argv) {
+    static float audio, mel, z, stats;                                         // never read: the front end only tests pointers
+    WgEncode c{"who", &audio, &mel, -1, atoi(argv[2]), nullptr, &z, &stats, false, 0, nullptr};
+    std::vector<int32_t> lens;
+    for (int i = 3; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) {
+            lens.push_back((int32_t)atoi(argv[i]));
+            continue;
+        }
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        const int v = atoi(eq + 1);
+        if (key == "B") c.B = v;
+        else if (key == "mem") c.mem = v;
+        else if (key == "async") c.async = v != 0;
+        else if (key == "null") {
+            if (strstr(eq, "audio")) c.audio = nullptr;
+            if (strstr(eq, "mel")) c.mel = nullptr;
+            if (strstr(eq, "z")) c.z = nullptr;
+            if (strstr(eq, "stats")) c.stats = nullptr;
+        } else return 2;
+    }
+    if (!lens.empty()) c.lengths = lens.data(), c.B = (int)lens.size();
+    char why[512] = "";
+    const int rc = wg_encode_check(c, why, sizeof why);
+    printf("%d %s\n", rc, why);
     return 0;
 }
 
@@ -340,6 +373,7 @@ int main(int argc, char** argv) {
     if (argc >= 3 && !strcmp(argv[1], "--taco-call")) return print_taco_call(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "--audio-call")) return print_audio_call(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wg-call")) return print_wg_call(argc, argv);
+    if (argc >= 3 && !strcmp(argv[1], "--wg-encode")) return print_wg_encode(argc, argv);
     if (argc >= 5 && !strcmp(argv[1], "--wn-taps")) {
         std::vector<int> lens;
         for (int i = 4; i < argc; ++i) lens.push_back(atoi(argv[i]));

@@ -47,7 +47,9 @@
 // uploads their results; waveglow_build_half (fp16 operands of either fp16 mode, on first use); the pieces of waveglow_run --
 // the kWnKernels table (precision x tile family of wg_plan.h -> GEMM launchers), ensure_workspace, wn_call / in_layer_args /
 // res_args (one description of the operands for every precision), launch_end_fold, the probe hooks, the Winograd form's
-// out-of-memory fallback -- and waveglow_run itself: one layer loop for every precision, form and mask kind.
+// out-of-memory fallback, wn_flow (the WN block of one flow: the one layer loop for every precision, form, mask kind and
+// direction) -- and waveglow_run itself, then waveglow_encode_run: the forward flow (audio -> z, flows ascending) around the same
+// wn_flow, with the position-wise kernels of wg_encode.hip.
 #include "engine.h"
 #include "gemm_f32.h"
 #include "wg_plan.h"
@@ -733,13 +735,15 @@ void fold_skip_into_end(int C, const float* const wk[8], const float* const bk[8
 
 // Invertible1x1Conv.build_inverse (invertible_conv.py:41-47): W = kernel[0]^T, W_inverse = inv(W)^T, and the reverse conv
 // (kernel layout [1][in][out]) computes out = audio @ W_inverse = audio @ inv(kernel[0]^T)^T.
-// kernel [n][n] -> minv[j][c] = inv(W)[c][j]; false when the kernel is singular.
-bool invert_1x1(const float* kernel, int n, std::vector<float>* minv) {
+// kernel [n][n] -> minv[j][c] = inv(W)[c][j]; false when the kernel is singular.  *log_abs_det = log |det kernel| (= that of
+// its transpose W): the sum of log |pivot|, row swaps only change the sign.
+bool invert_1x1(const float* kernel, int n, std::vector<float>* minv, double* log_abs_det) {
     std::vector<double> a((size_t)n * 2 * n, 0.0);      // [W | I], W[r][c] = kernel[c][r]
     for (int r = 0; r < n; ++r) {
         for (int c = 0; c < n; ++c) a[(size_t)r * 2 * n + c] = (double)kernel[(size_t)c * n + r];
         a[(size_t)r * 2 * n + n + r] = 1.0;
     }
+    double logdet = 0.0;
     for (int col = 0; col < n; ++col) {                  // Gauss-Jordan with partial pivoting
         int piv = col;
         for (int r = col + 1; r < n; ++r)
@@ -748,6 +752,7 @@ bool invert_1x1(const float* kernel, int n, std::vector<float>* minv) {
         if (piv != col)
             for (int c = 0; c < 2 * n; ++c) std::swap(a[(size_t)piv * 2 * n + c], a[(size_t)col * 2 * n + c]);
         const double d = a[(size_t)col * 2 * n + col];
+        logdet += std::log(std::fabs(d));
         for (int c = 0; c < 2 * n; ++c) a[(size_t)col * 2 * n + c] /= d;
         for (int r = 0; r < n; ++r) {
             if (r == col) continue;
@@ -759,6 +764,7 @@ bool invert_1x1(const float* kernel, int n, std::vector<float>* minv) {
     minv->resize((size_t)n * n);
     for (int j = 0; j < n; ++j)
         for (int c = 0; c < n; ++c) (*minv)[(size_t)j * n + c] = (float)a[(size_t)c * 2 * n + n + j];
+    *log_abs_det = logdet;
     return true;
 }
 
@@ -926,9 +932,10 @@ int waveglow_finalize(tts_hip_engine* e) {
         }
         if ((rc = need("waveglow/invertible_conv-" + std::to_string(k) + "/conv/kernel", {1, n_rem, n_rem}, &t))) return rc;
         std::vector<float> minv;
-        if (!invert_1x1(t->data.data(), n_rem, &minv))
+        if (!invert_1x1(t->data.data(), n_rem, &minv, &fl.log_det))
             return set_err(e, TTS_HIP_EINVAL, "invertible_conv-%d kernel is singular", k);
         if ((rc = upload(e, minv.data(), minv.size(), &fl.inv, wg.allocs))) return rc;
+        if ((rc = upload(e, t->data.data(), t->numel(), &fl.fwd, wg.allocs))) return rc;      // forward flow: audio @ kernel[0]
     }
     HIPCHK(e, hipStreamSynchronize(e->stream));
     gd.keep = true;
@@ -1248,6 +1255,93 @@ int wino_begin_or_fall_back(tts_hip_engine* e, const WgPlan& p, const float* d_m
     return TTS_HIP_OK;
 }
 
+// Which frames of a call are not real: the mask kind and the list of those frames (waveglow_run)
+struct WnTails {
+    int mask;
+    const int* d_tail;
+    int n_tail;
+};
+// x (and its fp16 shadow; after the start conv also the a0p rows) = 0 on the tail rows: store-only, tail bytes only
+int zero_tail(tts_hip_engine* e, const WnCall& c, const WnTails& t, bool with_a0p) {
+    if (t.mask == MASK_NONE || t.n_tail == 0) return TTS_HIP_OK;
+    WaveGlowDev& wg = e->wg;
+    const long long n4 = (long long)NPH * t.n_tail * (c.C / 4);
+    const bool h16 = c.precision != 0;
+    for_width(c.C, [&](auto cc) {
+        hipLaunchKernelGGL(wn_zero_tail_kernel<decltype(cc)::value>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, e->stream,
+                           t.d_tail, t.n_tail, c.plan.PR, c.plan.M, wg.x.f(), h16 ? (_Float16*)wg.x16.p : (_Float16*)nullptr,
+                           c.precision == 2 ? 2 : 1, with_a0p ? (h16 ? wg.a0p16.p : wg.a0p.p) : nullptr);
+    });
+    HIPCHK(e, hipGetLastError());
+    return TTS_HIP_OK;
+}
+
+// The WN block of flow k on the flow state wg.audio, for either direction: start kernel, the eight layers in the call's form,
+// the residual GEMMs.  Leaves the eight layers' activations (and, with call.endp, the end partial sums) for the direction's
+// boundary kernel.  probes: the inverse direction's test hook may stop the call at a layer (*stopped, with the probe's status
+// as the return value); the forward direction passes false and ignores armed hooks.
+int wn_flow(tts_hip_engine* e, const WnCall& call, const WnKernels& kn, const WgFlowDev& fl, int k, bool wino,
+            const WnTails& tails, bool probes, bool* stopped) {
+    WaveGlowDev& wg = e->wg;
+    hipStream_t st = e->stream;
+    const int C = call.C, precision = call.precision, h = fl.n_half, PR = call.plan.PR, BT = call.plan.BT, T = call.T;
+    const long long M = call.plan.M;
+    *stopped = false;
+    {
+        const long long n4 = M * (C / 4);
+        const dim3 grid((unsigned)((n4 + 255) / 256));
+        for_width(C, [&](auto cc) {
+            constexpr int CC = decltype(cc)::value;
+            if (precision != 0)
+                hipLaunchKernelGGL((wn_start_kernel<CC, true>), grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
+                                   wg.x.f(), wg.a0p16.p, (_Float16*)wg.x16.p, M, h, precision == 2 ? 1 : 0);
+            else
+                hipLaunchKernelGGL((wn_start_kernel<CC, false>), grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
+                                   wg.x.f(), wg.a0p.p, (_Float16*)nullptr, M, h);
+        });
+        HIPCHK(e, hipGetLastError());
+        if (int rc = zero_tail(e, call, tails, true)) return rc;
+    }
+    for (int i = 0; i < 8; ++i) {
+        const WgLayerDev& ly = fl.layer[i];
+        const bool wino_layer = wino && i > 0;
+        if (wino_layer) {
+            if (int rc = waveglow_wino_layer(e, ly, i, wg.x.f(), call.acts_of(i), PR, BT, T)) return rc;
+        } else if (wino) {                 // first layer of a flow: the plane kernel's K loop, taps and gate in its epilogue
+            if (int rc = waveglow_wino_layer0(e, ly, h, wg.a0p.f(), call.acts_of(0), PR, BT, T)) return rc;
+        } else {
+            const GemmArgs g = in_layer_args(call, ly, i);
+            timing_begin(e, in_layer_timing_kind(precision, i));
+            HIPCHK(e, (i == 0 ? kn.in0 : kn.in)(g, st));
+            timing_end(e);
+        }
+        if (probes && probe_wants_layer(wg, precision, k, i)) {      // test hook: stop here
+            *stopped = true;
+            return probe_layer(e, call, i, wino_layer);
+        }
+        if (i < 7) {
+            const GemmArgs r = res_args(call, ly, i, fl.end_w);
+            timing_begin(e, 1);
+            HIPCHK(e, kn.res(r, st));
+            timing_end(e);
+            if (int rc = zero_tail(e, call, tails, false)) return rc;
+        }
+    }
+    return TTS_HIP_OK;
+}
+
+// Ragged calls: private copy of the mel with cleared tails (mel_ragged_copy_kernel) -> *d_mel
+int ragged_mel(tts_hip_engine* e, const float** d_mel, const int* d_lens, int BT, int T) {
+    WaveGlowDev& wg = e->wg;
+    HIPCHK(e, wg.mel_ragged.ensure((size_t)BT * 80 * 4));
+    const long long n4 = (long long)BT * 20;
+    hipLaunchKernelGGL(mel_ragged_copy_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, e->stream, *d_mel,
+                       wg.mel_ragged.f(), d_lens, BT, T);
+    HIPCHK(e, hipGetLastError());
+    *d_mel = wg.mel_ragged.f();
+    return TTS_HIP_OK;
+}
+
 }  // namespace
 
 // precision 0: exact fp32 MFMA path.  precision 1: fp16 operands (activations, mel and weights fp16 in HBM), fp32
@@ -1282,27 +1376,9 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         return set_err(e, TTS_HIP_EINVAL, "waveglow_infer: B*T = %d frames exceeds one call's limit (~32000)", BT);
     if (int rc = ensure_workspace(e, plan, precision)) return rc;
     hipStream_t st = e->stream;
-    if (mask == MASK_LENS) {                                     // every reader below takes the copy with cleared tails
-        HIPCHK(e, wg.mel_ragged.ensure((size_t)BT * 80 * 4));
-        const long long n4 = (long long)BT * 20;
-        hipLaunchKernelGGL(mel_ragged_copy_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, d_mel,
-                           wg.mel_ragged.f(), d_lens, BT, T);
-        HIPCHK(e, hipGetLastError());
-        d_mel = wg.mel_ragged.f();
-    }
-    // x (and its fp16 shadow; after the start conv also the a0p rows) = 0 on the tail rows: store-only, tail bytes only
-    auto zero_tail = [&](bool with_a0p) -> int {
-        if (mask == MASK_NONE || n_tail == 0) return TTS_HIP_OK;
-        const long long n4 = (long long)NPH * n_tail * (C / 4);
-        const bool h16 = precision != 0;
-        for_width(C, [&](auto cc) {
-            hipLaunchKernelGGL(wn_zero_tail_kernel<decltype(cc)::value>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, d_tail,
-                               n_tail, PR, M, wg.x.f(), h16 ? (_Float16*)wg.x16.p : (_Float16*)nullptr, precision == 2 ? 2 : 1,
-                               with_a0p ? (h16 ? wg.a0p16.p : wg.a0p.p) : nullptr);
-        });
-        HIPCHK(e, hipGetLastError());
-        return TTS_HIP_OK;
-    };
+    if (mask == MASK_LENS)                                       // every reader below takes the copy with cleared tails
+        if (int rc = ragged_mel(e, &d_mel, d_lens, BT, T)) return rc;
+    const WnTails tails{mask, d_tail, n_tail};
     bool wino = plan.wino_wanted;
     if (wino)
         if (int rc = wino_begin_or_fall_back(e, plan, d_mel, T, &wino)) return rc;
@@ -1310,7 +1386,6 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
     wg.last_tiles = plan.tiles;
     const WnKernels& kn = kWnKernels[precision][plan.tiles];
     const WnCall call = wn_call(wg, plan, precision, T, d_mel);
-    _Float16* x16 = (_Float16*)wg.x16.p;
     _Float16* mel16 = (_Float16*)wg.mel16.p;
 
     const unsigned mb = (unsigned)((M + 255) / 256);
@@ -1331,43 +1406,9 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
     for (int k = 11; k >= 0; --k) {
         const WgFlowDev& fl = wg.flow[k];
         const int h = fl.n_half;
-        {
-            const long long n4 = M * (C / 4);
-            const dim3 grid((unsigned)((n4 + 255) / 256));
-            for_width(C, [&](auto cc) {
-                constexpr int CC = decltype(cc)::value;
-                if (precision != 0)
-                    hipLaunchKernelGGL((wn_start_kernel<CC, true>), grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
-                                       wg.x.f(), wg.a0p16.p, x16, M, h, precision == 2 ? 1 : 0);
-                else
-                    hipLaunchKernelGGL((wn_start_kernel<CC, false>), grid, dim3(256), 0, st, wg.audio.f(), fl.start_w, fl.start_b,
-                                       wg.x.f(), wg.a0p.p, (_Float16*)nullptr, M, h);
-            });
-            HIPCHK(e, hipGetLastError());
-            if (int rc = zero_tail(true)) return rc;
-        }
-        for (int i = 0; i < 8; ++i) {
-            const WgLayerDev& ly = fl.layer[i];
-            const bool wino_layer = wino && i > 0;
-            if (wino_layer) {
-                if (int rc = waveglow_wino_layer(e, ly, i, wg.x.f(), call.acts_of(i), PR, BT, T)) return rc;
-            } else if (wino) {                 // first layer of a flow: the plane kernel's K loop, taps and gate in its epilogue
-                if (int rc = waveglow_wino_layer0(e, ly, h, wg.a0p.f(), call.acts_of(0), PR, BT, T)) return rc;
-            } else {
-                const GemmArgs g = in_layer_args(call, ly, i);
-                timing_begin(e, in_layer_timing_kind(precision, i));
-                HIPCHK(e, (i == 0 ? kn.in0 : kn.in)(g, st));
-                timing_end(e);
-            }
-            if (probe_wants_layer(wg, precision, k, i)) return probe_layer(e, call, i, wino_layer);   // test hook: stop here
-            if (i < 7) {
-                const GemmArgs r = res_args(call, ly, i, fl.end_w);
-                timing_begin(e, 1);
-                HIPCHK(e, kn.res(r, st));
-                timing_end(e);
-                if (int rc = zero_tail(false)) return rc;
-            }
-        }
+        bool stopped = false;
+        if (int rc = wn_flow(e, call, kn, fl, k, wino, tails, true, &stopped)) return rc;
+        if (stopped) return TTS_HIP_OK;
         const bool early = (k % 4 == 0) && k > 0;
         float* dst = (k == 0) ? d_audio : wg.audio.f();
         const long long waves = (M + RPW - 1) / RPW;
@@ -1395,6 +1436,54 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         if (early) zoff += 2;
     }
     return TTS_HIP_OK;
+}
+
+// Forward flow (fp32): audio [B, T*256] -> z [B, T*32, 8] in the layout waveglow_run consumes, and stats [3][B] (sum z^2, sum s,
+// lens[b] * 32 * sum_k log|det kernel_k|) over each row's real positions.  Same plan, workspace, form and tail handling as
+// waveglow_run, flows ascending; the position-wise kernels are wg_encode.hip's.  The end partial sums of the 512-channel fp32
+// path are not used in this direction (call.endp stays null: the residual GEMMs run plain and wn_end_fwd_kernel reads the
+// eight layers' activations), and armed probe hooks are ignored.
+int waveglow_encode_run(tts_hip_engine* e, const float* d_audio, const float* d_mel, int B, int T, const int* d_lens,
+                        const int* d_tail, int n_tail, float* d_z, float* d_stats) {
+    WaveGlowDev& wg = e->wg;
+    const int C = wg.channels;
+    WgPlan plan = wg_plan(B * T, 0, wg.form_mode);
+    if (C != 512) plan.wino_wanted = false;
+    const int BT = plan.BT, PR = plan.PR;
+    const long long M = plan.M;
+    if ((double)M * C * 4.0 >= 2147483648.0 - 65536.0)
+        return set_err(e, TTS_HIP_EINVAL, "waveglow_encode: B*T = %d frames exceeds one call's limit (~32000)", BT);
+    if (int rc = ensure_workspace(e, plan, 0)) return rc;
+    const size_t part_at = (size_t)M * 4;                        // enc_ws: [slog M floats | partial sums]
+    HIPCHK(e, wg.enc_ws.ensure(part_at + wg_encode_stats_bytes(B)));
+    float* slog = wg.enc_ws.f();
+    if (d_lens)
+        if (int rc = ragged_mel(e, &d_mel, d_lens, BT, T)) return rc;
+    const WnTails tails{d_lens ? MASK_LENS : MASK_NONE, d_tail, n_tail};
+    bool wino = plan.wino_wanted;
+    if (wino)
+        if (int rc = wino_begin_or_fall_back(e, plan, d_mel, T, &wino)) return rc;
+    wg.last_form = wino ? 1 : 0;
+    wg.last_tiles = plan.tiles;
+    const WnKernels& kn = kWnKernels[0][plan.tiles];
+    WnCall call = wn_call(wg, plan, 0, T, d_mel);
+    call.endp = nullptr;
+    if (int rc = wg_encode_init(e, d_audio, wg.flow[0].fwd, wg.audio.f(), PR, BT, d_lens, T)) return rc;
+    double log_det_sum = 0.0;
+    for (int k = 0; k < 12; ++k) {
+        const WgFlowDev& fl = wg.flow[k];
+        bool stopped = false;
+        if (int rc = wn_flow(e, call, kn, fl, k, wino, tails, false, &stopped)) return rc;
+        log_det_sum += fl.log_det;
+        const bool early = k + 1 == 4 || k + 1 == 8;             // the first two channels leave before flows 4 and 8
+        WgEncodeEnd a{};
+        a.C = C, a.acts = call.acts, a.layer_stride = call.acts_stride, a.wfold = fl.end_w, a.bfold = fl.end_b;
+        a.state = wg.audio.f(), a.slog = slog, a.first = k == 0, a.next = k < 11 ? wg.flow[k + 1].fwd : nullptr;
+        a.z = d_z, a.zoff = k + 1 == 4 ? 6 : 4, a.n_early = early ? 2 : 0;
+        a.M = M, a.h = fl.n_half, a.PR = PR, a.BT = BT, a.d_lens = d_lens, a.T = T;
+        if (int rc = wg_encode_end(e, a)) return rc;
+    }
+    return wg_encode_stats(e, d_z, slog, (double*)((char*)wg.enc_ws.p + part_at), d_lens, B, T, PR, log_det_sum, d_stats);
 }
 
 // Packed call: gather the real frames of mel / z [B, T, ..] into one row of F frames (mel_ragged / packed_z), run that row as

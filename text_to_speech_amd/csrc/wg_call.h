@@ -1,7 +1,8 @@
 // wg_call.h -- what one WaveGlow call is, why it may be refused and the int table it stages: pure host code on the caller's
 // arguments (no HIP include; also built with plain g++ under ASan / UBSan by csrc/host_check.cpp, --wg-call, and compared
 // there with tests/waveglow_packed_ref.py::packing_plan and a numpy restatement, tests/test_wg_call.py).  Every
-// tts_hip_waveglow_infer* entry point fills a WgCall and hands it to waveglow_call (engine.hip).
+// tts_hip_waveglow_infer* entry point fills a WgCall and hands it to waveglow_call (engine.hip); the forward flow's two entry
+// points fill a WgEncode (--wg-encode, tests/test_waveglow_encode.py).
 #pragma once
 #include <stdint.h>
 
@@ -96,6 +97,38 @@ inline int wg_call_check(const WgCall& c, char* msg, size_t n) {
         return wg_refuse(msg, n, c.who, "T = %d frames exceeds one run's limit (%d); use windowed inference", c.T,
                          kMaxFramesPerRun);
     }
+    return TTS_HIP_OK;
+}
+
+// One forward-flow call (tts_hip_waveglow_encode[_async], fp32): audio [B, T*256] and mel [B, T, 80] in, z [B, T*32, 8] and
+// stats [3, B] out, either of which may be NULL.
+struct WgEncode {
+    const char* who;                 // the entry point, as messages name it
+    const float *audio, *mel;
+    int B, T;
+    const int32_t* lengths;          // NULL or host int32 [B]
+    float *z, *stats;
+    bool async;                      // as WgCall::async / mem / stream
+    int mem;
+    void* stream;
+};
+
+// Every reason a forward-flow call is refused for what it asks, first match wins, in this order: mem kind, B, audio / mel / T,
+// both outputs NULL, lengths[b], then B * T above one run (the call is one run: no slicing).  Reads host memory only
+// (lengths); nothing is copied or launched before it has passed.
+inline int wg_encode_check(const WgEncode& c, char* msg, size_t n) {
+    if (!c.async && c.mem != TTS_HIP_MEM_HOST && c.mem != TTS_HIP_MEM_DEVICE)
+        return wg_refuse(msg, n, c.who, "bad mem kind %d", c.mem);
+    if (c.B <= 0) return wg_refuse(msg, n, c.who, "bad argument: B = %d must be positive", c.B);
+    if (!c.audio || !c.mel || c.T <= 0) return wg_refuse(msg, n, c.who, "bad argument (audio or mel is NULL, or T = %d <= 0)", c.T);
+    if (!c.z && !c.stats) return wg_refuse(msg, n, c.who, "bad argument: z and stats are both NULL, nothing to compute");
+    if (c.lengths)
+        for (int b = 0; b < c.B; ++b)
+            if (c.lengths[b] < 0 || c.lengths[b] > c.T)
+                return wg_refuse(msg, n, c.who, "lengths[%d] = %d is outside [0, T = %d]", b, (int)c.lengths[b], c.T);
+    if ((long long)c.B * c.T > kMaxFramesPerRun)
+        return wg_refuse(msg, n, c.who, "B * T = %lld frames exceeds one run's limit (%d); encode the batch in slices of rows",
+                         (long long)c.B * c.T, kMaxFramesPerRun);
     return TTS_HIP_OK;
 }
 

@@ -383,6 +383,50 @@ class HipEngine:
             self._h, self._ptr(m), B, T, *mid, float(sigma), self._ptr(out), *pcode, *last, mem if stream is None else sp), name)
         return out.cpu().numpy() if via_device else out
 
+    def waveglow_encode(self, audio, mel, lengths=None, stream=None):
+        """The forward flow, audio [B, T*256] + mel [B, T, 80] -> (z [B, T*32, 8], stats float32 [3, B]), fp32
+        (tts_hip_waveglow_encode): z in the layout `waveglow_infer` consumes, so `waveglow_infer(mel, z=z, sigma=1)` returns the
+        audio; stats[0] = sum z^2, stats[1] = sum of the couplings' s, stats[2] = frames * 32 * sum_k log|det kernel_k| per row,
+        over its real positions -- the row's log-likelihood under N(0, sigma^2) is -(stats[0] / (2 sigma^2)) + stats[1] +
+        stats[2] up to the constant.  `lengths` [B] (ints in [0, T]): a batch of unequal rows -- audio and mel beyond a row's
+        length are never read, z is 0 there and the row gets what a call on its own frames gives it.  numpy in gives numpy out,
+        CUDA tensors in give tensors out; `stream` (a torch.cuda.Stream, device tensors only): enqueue there and return without
+        waiting (tts_hip_waveglow_encode_async).  B * T is limited to one run (31 744 frames)."""
+        dev = _is_torch_cuda(mel)
+        if dev != _is_torch_cuda(audio):
+            raise ValueError('audio and mel must both be host arrays or both be CUDA tensors')
+        if not dev:
+            if stream is not None:
+                raise ValueError('stream= needs device tensors')
+            mel = np.ascontiguousarray(mel, dtype=np.float32)
+            audio = np.ascontiguousarray(audio, dtype=np.float32)
+        if len(mel.shape) != 3 or mel.shape[2] != 80:
+            raise ValueError(f'mel must be [B, T, 80], got {tuple(mel.shape)}')
+        B, T = int(mel.shape[0]), int(mel.shape[1])
+        if tuple(audio.shape) != (B, T * 256):
+            raise ValueError(f'audio must be [B, T*256] = {(B, T * 256)}, got {tuple(audio.shape)}')
+        self._check_device(audio, mel)
+        lens = None if lengths is None else self._frame_lengths(lengths, B, T)
+        sp, mem = None, MEM_HOST
+        if dev:
+            torch = self._torch()
+
+            def prepare():
+                return (audio.to(torch.float32).contiguous(), mel.to(torch.float32).contiguous(),
+                        torch.empty((B, T * 32, 8), dtype=torch.float32, device=mel.device),
+                        torch.empty((3, B), dtype=torch.float32, device=mel.device))
+
+            (a, m, z, stats), sp = self._staged(stream, prepare, audio, mel)
+            mem = MEM_DEVICE
+        else:
+            a, m = audio, mel
+            z, stats = np.empty((B, T * 32, 8), dtype=np.float32), np.empty((3, B), dtype=np.float32)
+        name = 'waveglow_encode' + ('_async' if stream is not None else '')
+        self._check(getattr(self._lib, 'tts_hip_' + name)(
+            self._h, self._ptr(a), self._ptr(m), B, T, self._ptr(lens), self._ptr(z), self._ptr(stats),
+            mem if stream is None else sp), name)
+        return z, stats
+
     _WG_PRECISIONS = {'f32': 0, 'f16': 1, 'f16x3': 2}
     # (noise, rows) -> entry point, without the tts_hip_ prefix and the _async suffix of a call on a caller's stream
     _WG_ENTRY = {('z', 'plain'): 'waveglow_infer', ('z', 'ragged'): 'waveglow_infer_ragged', ('z', 'packed'): 'waveglow_infer_packed',

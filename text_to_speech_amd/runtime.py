@@ -400,6 +400,13 @@ class HipRuntime(Runtime):
                 else {'seed': noise[0], 'offset': noise[1]})
         return self.engine.waveglow_infer(mel, sigma=float(sigma), precision=precision or self.vocoder_precision, **draw, **ragged)
 
+    def waveglow_encode(self, audio, mel, lengths=None, stream=None):
+        """The forward flow of the vocoder, audio [B, T*256] + mel [B, T, 80] -> (z [B, T*32, 8], stats [3, B]), fp32
+        (HipEngine.waveglow_encode); a single utterance ([T*256] with [T, 80]) gets its batch axis."""
+        if len(mel.shape) == 2:
+            audio, mel = audio[None], mel[None]
+        return self.engine.waveglow_encode(audio, mel, lengths=lengths, stream=stream)
+
 
 _runtimes = {'hip': HipRuntime}
 

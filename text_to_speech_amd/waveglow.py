@@ -164,6 +164,104 @@ class WaveGlow:
 
     __call__ = infer
 
+    # ---- the forward flow: audio -> z and its likelihood (the direction the published model is trained and scored with)
+    MAX_RUN_FRAMES = 31744              # B * T of one `waveglow_encode` call (include/tts_hip.h)
+
+    def _encode_runtime(self, what):
+        encode = getattr(self.compiled_infer, 'waveglow_encode', None)
+        if encode is None:
+            raise ValueError(f'{what} needs a runtime with waveglow_encode (HipRuntime) behind the model')
+        return encode
+
+    def _recording(self, audio, mel, load_kwargs):
+        """One recording as (waveform float32 [frames * 256] zero-padded or cut to its mel's frames, mel float32 [frames, 80]):
+        `audio` is a file name (loaded by `audio.load_audio` at the model's rate with `load_kwargs`) or a waveform, taken as it
+        is; `mel` None: the mel of those samples, through `audio.load_mel` on the model's engine."""
+        from .audio import load_audio, load_mel
+        engine = getattr(self.compiled_infer, 'engine', None)
+        if isinstance(audio, (str, bytes, dict)):
+            wave = load_audio(audio, self.rate, engine=engine, **load_kwargs)
+        else:
+            wave = audio
+        wave = np.asarray(_to_numpy(wave), dtype=np.float32).reshape(-1)
+        if mel is None:
+            mel = load_mel(wave, self.rate, engine=engine, normalize=False)      # (of the samples that are encoded)
+        mel = np.asarray(_to_numpy(mel), dtype=np.float32)
+        if mel.ndim == 3 and mel.shape[0] == 1:
+            mel = mel[0]
+        if mel.ndim != 2 or mel.shape[1] != 80:
+            raise ValueError(f'mel must be [frames, 80], got {mel.shape}')
+        n = mel.shape[0] * 256
+        padded = np.zeros(n, dtype=np.float32)
+        padded[:min(n, len(wave))] = wave[:n]
+        return padded, mel
+
+    @staticmethod
+    def _nll(stats, frames, sigma):
+        """[4, N]: nll per sample, sum_z2, sum_log_s, log_det_w from stats [3, N] and the rows' frame counts (0 frames: nll 0)."""
+        stats = np.asarray(stats, dtype=np.float64)
+        frames = np.asarray(frames, dtype=np.float64)
+        total = stats[0] / (2.0 * float(sigma) ** 2) - stats[1] - stats[2]
+        nll = np.where(frames > 0, total / np.maximum(frames * 256.0, 1.0), 0.0)
+        return np.stack([nll, stats[0], stats[1], stats[2]])
+
+    def encode(self, audio, mel=None, **load_kwargs):
+        """A recording's latent under the model: `audio` (a file name or a waveform) and its `mel` [frames, 80] -- None: through
+        `audio.load_mel` on the model's engine, with `load_kwargs` for the file -- go through the forward flow; the audio is
+        zero-padded to frames * 256 samples.  Returns {'z' [frames * 32, 8] (what `infer(mel, z=z[None] * tau)` re-synthesizes
+        from), 'mel' [frames, 80], 'nll' (per sample, sigma = 1, without the constant log(2 pi) / 2), 'sum_z2', 'sum_log_s',
+        'log_det_w'}.  Needs a runtime with `waveglow_encode` (HipRuntime) behind the model."""
+        encode = self._encode_runtime('encode')
+        wave, mel = self._recording(audio, mel, load_kwargs)
+        z, stats = encode(wave[None], mel[None])
+        nll, z2, ls, ld = self._nll(_to_numpy(stats), [mel.shape[0]], 1.0)[:, 0]
+        return {'z': _to_numpy(z)[0], 'mel': mel, 'nll': float(nll), 'sum_z2': float(z2), 'sum_log_s': float(ls),
+                'log_det_w': float(ld)}
+
+    def evaluate(self, items, *, batch_size=8, sigma=1.0, **load_kwargs):
+        """The model's negative log-likelihood on held-out recordings.  `items`: waveforms, file names or (audio, mel) pairs,
+        each prepared as in `encode`.  Consecutive items form ragged batches of at most `batch_size` rows that also fit one run
+        (rows * longest row <= MAX_RUN_FRAMES), padded with zeros and passed with their `lengths`, so every item gets what a
+        call of its own gives it; only the [3, B] statistics come to the host.  Per item
+            nll = (sum_z2 / (2 sigma^2) - sum_log_s - log_det_w) / (frames * 256)      (0 for an empty item)
+        Returns {'names' ('nll', 'sum_z2', 'sum_log_s', 'log_det_w'), 'per_item' float64 [4, N] in input order, 'mean' [4]}."""
+        encode = self._encode_runtime('evaluate')
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f'batch_size must be at least 1, got {batch_size}')
+        if not float(sigma) > 0:
+            raise ValueError(f'sigma must be positive, got {sigma}')
+        names = ('nll', 'sum_z2', 'sum_log_s', 'log_det_w')
+        prepared = []
+        for item in items:
+            audio, mel = item if isinstance(item, tuple) else (item, None)
+            prepared.append(self._recording(audio, mel, load_kwargs))
+        per_item = np.zeros((4, len(prepared)), dtype=np.float64)
+        start = 0
+        while start < len(prepared):
+            stop, longest = start, 0
+            while stop < len(prepared) and stop - start < batch_size:
+                t = max(longest, prepared[stop][1].shape[0])
+                if (stop - start + 1) * max(t, 1) > self.MAX_RUN_FRAMES:
+                    break
+                stop, longest = stop + 1, t
+            if stop == start:
+                raise ValueError(f'item {start} holds {prepared[start][1].shape[0]} frames, above one run\'s limit '
+                                 f'({self.MAX_RUN_FRAMES})')
+            rows = prepared[start:stop]
+            T = max(longest, 1)
+            audio = np.zeros((len(rows), T * 256), dtype=np.float32)
+            mels = np.zeros((len(rows), T, 80), dtype=np.float32)
+            lengths = np.array([m.shape[0] for _, m in rows], dtype=np.int32)
+            for r, (w, m) in enumerate(rows):
+                audio[r, :len(w)] = w
+                mels[r, :m.shape[0]] = m
+            _, stats = encode(audio, mels, lengths=lengths)
+            per_item[:, start:stop] = self._nll(_to_numpy(stats), lengths, sigma)
+            start = stop
+        mean = per_item.mean(axis=1) if len(prepared) else np.zeros(4)
+        return {'names': names, 'per_item': per_item, 'mean': mean}
+
     def infer_exact(self, mel, *, tile_frames=4096, z=None, **kwargs):
         """Long-form vocoding without the approximation of `infer(win_len=...)`: halo tiling, bit-for-bit the samples of
         one run over the whole mel (which one C-ABI call only accepts up to ~31.7 k frames)."""
