@@ -464,6 +464,59 @@ int tts_hip_mel_fn_run_async(tts_hip_engine* e, const float* audio, int B, int N
 int tts_hip_mel_fn_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
                          int what, float* out, int mem);
 
+/* ---- STFT with phase, its inverse, and Griffin-Lim (csrc/stft_inv.hip; utils/audio/stft.py:194-274, the STFT class).
+ * All of these take a Tacotron-kind plan, are refused for a Whisper plan, and build the tables they need on first use.
+ * With cut = filter_length / 2 + 1 bins, half = filter_length / 2:
+ *
+ * transform: audio [B, N], lengths as tts_hip_mel_fn_run -> out0, out1 [B, Fmax, cut], Fmax = tts_hip_mel_fn_frames(fn, N):
+ *   steps 1 - 4 of the mel plan (zero pad, pre-emphasis, reflect pad, windowed DFT), then what = 0: magnitude
+ *   sqrt(re^2 + im^2) and phase atan2f(im, re); what = 1: real and imaginary parts.  Frames at and beyond a row's own are 0.
+ *
+ * inverse: two planes [B, F, cut] (form 0: magnitude and phase, re = m cosf(p), im = m sinf(p); form 1: real and imaginary
+ *   parts) and frames[b] in [1, F] (host array; NULL = F for every row) -> audio [B, F * hop_length].  Per row: time frames
+ *   [re_f, im_f] . inverse_basis (filter_length samples; the windowed pseudo-inverse of stft.py:220-236), overlap-added at
+ *   f * hop_length, y[i] /= ws[i] wherever ws[i] > FLT_MIN with ws[i] = sum_f window^2[i - f * hop_length] over the row's own
+ *   frames, y *= filter_length / hop_length, and half samples dropped at each end: row b holds
+ *   tts_hip_mel_fn_samples(fn, frames[b]) = hop_length * (frames[b] - 1) + filter_length - 2 * half samples, zeros beyond.
+ *   Each output sample sums its frames in frame order (a gather, no atomics): the result is bit-reproducible, nothing
+ *   behind a row's frames is read, and a row never depends on its neighbours.
+ *
+ * griffin_lim: spec [B, F, C] -> audio [B, F * hop_length].  input_kind 0: spec is the linear magnitude S, C = cut;
+ *   1: spec is a Tacotron log-mel, C = n_mel_channels, S = max(0, exp(spec) . Minv) with Minv [n_mel, cut] a host double
+ *   array (whatever `mem` says), NULL = the minimum-norm inverse W^T (W W^T)^-1 of the plan's filterbank (Cholesky in
+ *   double; the call is refused when that fails -- a mel channel without a bin -- and for a plan that normalises).
+ *   With P(re, im) = (re, im) / |(re, im)|, P(0, 0) = (1, 0): p_0 = P(init) (init [B, F, cut, 2]; NULL = (1, 0)),
+ *   t_prev = 0, and n_iters times: x = inverse(S p); Y = transform(x) of the row's own samples (no pre-emphasis: a plan with
+ *   pre_emph > 0 is refused; exactly frames[b] frames); c = Y - momentum / (1 + momentum) * t_prev; t_prev = Y; p = P(c).
+ *   The result is inverse(S p); n_iters = 0 is a single inverse of the initial phase.  The _async form takes device
+ *   pointers (Minv stays a host array) and a stream.
+ *
+ * griffin_lim_probe (test hook): the code of the call, not a copy, stopped at stage `what` of iteration k in [0, n_iters]:
+ *   0 target S [B, F, cut]; 1 operand S p_k [B, F, 2 cut] (real parts, then imaginary parts); 2 frames [B, F, filter_length];
+ *   3 signal [B, hop_length * (F - 1) + filter_length], the reflect-padded row of x_k; 4 spectrum Y_k [B, F, 2 cut];
+ *   5 phasor p_{k+1} [B, F, 2 cut].  The call makes n_iters phase updates and then one more inverse: iteration k = n_iters is
+ *   that last inverse (operand, frames, signal) and takes no transform, so it has no spectrum and no phasor -- stages 4 and 5
+ *   exist for k < n_iters only and are refused at k = n_iters.
+ *
+ * Refusals (TTS_HIP_EINVAL, first match wins, nothing copied or launched): a plan that is not a plan of this handle
+ * (checked first: nothing of a dead plan is read); a NULL pointer; B or F < 1; a frames[b] outside [1, F]; C not the plan's
+ * width for the kind; n_iters < 0; momentum outside [0, 1) or not finite; a Whisper plan; pre_emph > 0 (griffin_lim); a
+ * normalising plan (kind 1); a griffin_lim row whose samples are not more than half (the reflect needs them); a buffer at or
+ * above 2^31 - 65536 bytes; a bad mem kind; a bad `what`, or k outside [0, n_iters]. */
+long long tts_hip_mel_fn_samples(const tts_hip_mel_fn* fn, int frames);
+int tts_hip_stft_transform(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                           int what, float* out0, float* out1, int mem);
+int tts_hip_stft_inverse(tts_hip_engine* e, const float* plane0, int B, int F, const float* plane1, const int32_t* frames,
+                         const tts_hip_mel_fn* fn, int form, float* audio, int mem);
+int tts_hip_griffin_lim(tts_hip_engine* e, const float* spec, int B, int F, int C, const int32_t* frames, const tts_hip_mel_fn* fn,
+                        int input_kind, const double* Minv, const float* init, int n_iters, double momentum, float* audio, int mem);
+int tts_hip_griffin_lim_async(tts_hip_engine* e, const float* spec, int B, int F, int C, const int32_t* frames,
+                              const tts_hip_mel_fn* fn, int input_kind, const double* Minv, const float* init, int n_iters,
+                              double momentum, float* audio, void* stream);
+int tts_hip_griffin_lim_probe(tts_hip_engine* e, const float* spec, int B, int F, int C, const int32_t* frames,
+                              const tts_hip_mel_fn* fn, int input_kind, const double* Minv, const float* init, int n_iters,
+                              double momentum, int k, int what, float* out, int mem);
+
 /* ---- waveform clean-up (csrc/audio_proc.hip; DFT bases built on first use, no weights needed)
  * reduce_noise: utils/audio/noisereducev1.py:175-290 with the defaults utils/audio/audio_processing.py:65-83 uses.
  *   audio [B, N] -> out [B, N]; row b has lengths[b] (1 <= lengths[b] <= N) samples, lengths NULL = N for every row, and
@@ -574,6 +627,8 @@ int tts_hip_resample_fft_probe(tts_hip_engine* e, const float* in, int lines, in
  * last reset, and how many launches were timed.  kind: 0 = WaveGlow WN in-layer GEMM (layers 1..7 of a flow: K = 2176),
  * 1 = WN residual GEMM, 2 = Tacotron2 decoder step, 3 = first WN layer of a flow (start conv composed into its taps: direct
  * form one GEMM of K = 48 + 320; Winograd form the tap operand kernel and wino_layer0_kernel, K = 16 + 140 per output).
+ * A tts_hip_griffin_lim call files the four parts of its iterations under the same kinds: 0 = inverse-frames GEMM, 1 = gather
+ * overlap-add, 2 = forward DFT GEMM (with its gather, where the plan has one), 3 = phase update.
  * Timing is off unless enabled (events perturb nothing but cost a few us each).        */
 int tts_hip_kernel_timing(tts_hip_engine* e, int enable);
 /* Box probe: TFLOP/s a bare v_mfma_f32_32x32x2_f32 loop sustains on this device right now (every CU, 2 waves per SIMD, ~20 ms)

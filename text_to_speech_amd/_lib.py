@@ -113,6 +113,15 @@ SIGNATURES = {
     'tts_hip_mel_fn_run': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     'tts_hip_mel_fn_run_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'tts_hip_mel_fn_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int]),
+    'tts_hip_mel_fn_samples': (c_int64, [c_void_p, c_int]),
+    'tts_hip_stft_transform': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]),
+    'tts_hip_stft_inverse': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
+    'tts_hip_griffin_lim': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                    c_double, c_void_p, c_int]),
+    'tts_hip_griffin_lim_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                          c_int, c_double, c_void_p, c_void_p]),
+    'tts_hip_griffin_lim_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                          c_int, c_double, c_int, c_int, c_void_p, c_int]),
     'tts_hip_resample_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     'tts_hip_resample_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     'tts_hip_resample_fft_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -1,4 +1,4 @@
-// audio_call.h -- what the audio front-end calls (mel-STFT, reduce_noise / trim_silence, resample, remove_silence) may be
+// audio_call.h -- what the audio front-end calls (mel-STFT, STFT inverse / Griffin-Lim, reduce_noise / trim_silence, resample, remove_silence) may be
 // refused for, and the geometry those refusals rest on: pure host code on the caller's arguments (no HIP include; also built
 // with plain g++ under ASan / UBSan by csrc/host_check.cpp, --audio-call, and compared there with a Python restatement,
 // tests/test_audio_call.py).  The .hip files forward the message to set_err; nothing is copied or launched before a check
@@ -411,4 +411,155 @@ inline int mel_call_check(const char* who, const MelPlan* p, const float* audio,
     g->off_linear = c.take(p->kind == TTS_HIP_MEL_WHISPER ? (size_t)rows * p->nmel * 4 : 0);
     g->total = c.o;
     return audio_mem_check(who, mem, msg, n);
+}
+
+// ---------------------------------------------------------------------------------------------- STFT inverse, Griffin-Lim (stft_inv.hip)
+// The Slaney filterbank of a plan in double, [n_mel][cut] (librosa.filters.mel defaults; stft.py:65-72): what plan_build
+// rounds to the fp32 table, and what the mel inversion below starts from.
+inline double mel_hz_to_mel(double f) {
+    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
+    return f >= min_log_hz ? min_log_mel + std::log(f / min_log_hz) / logstep : f / f_sp;
+}
+inline double mel_mel_to_hz(double m) {
+    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
+    return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
+}
+inline void mel_filterbank(const MelPlan& p, std::vector<double>& W) {
+    const double sr = p.sr;
+    std::vector<double> mel_f(p.nmel + 2);
+    const double m0 = mel_hz_to_mel(p.fmin), m1 = mel_hz_to_mel(p.fmax);
+    for (int i = 0; i < p.nmel + 2; ++i) mel_f[i] = mel_mel_to_hz(m0 + (m1 - m0) * i / (p.nmel + 1));
+    W.assign((size_t)p.nmel * p.cut, 0.0);
+    for (int i = 0; i < p.nmel; ++i) {
+        const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
+        for (int c = 0; c < p.cut; ++c) {
+            const double fr = (sr / 2.0) * c / (p.cut - 1);
+            const double lower = (fr - mel_f[i]) / (mel_f[i + 1] - mel_f[i]);
+            const double upper = (mel_f[i + 2] - fr) / (mel_f[i + 2] - mel_f[i + 1]);
+            W[(size_t)i * p.cut + c] = std::fmax(0.0, std::fmin(lower, upper)) * enorm;
+        }
+    }
+}
+
+// Minv [n_mel][cut] = (W W^T)^-1 W, the transpose of the minimum-norm inverse W^T (W W^T)^-1 of the plan's filterbank:
+// spectrum = mel . Minv.  W W^T is factored by Cholesky in double; false when it is not positive definite (a channel
+// without a bin makes a zero row).
+inline bool mel_min_norm_inverse(const MelPlan& p, std::vector<double>& Minv) {
+    std::vector<double> W;
+    mel_filterbank(p, W);
+    const int n = p.nmel, c = p.cut;
+    std::vector<double> G((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double s = 0.0;
+            for (int k = 0; k < c; ++k) s += W[(size_t)i * c + k] * W[(size_t)j * c + k];
+            G[(size_t)i * n + j] = s;
+        }
+    double scale = 0.0;
+    for (int i = 0; i < n; ++i) scale = std::max(scale, G[(size_t)i * n + i]);
+    for (int j = 0; j < n; ++j) {                               // G = L L^T in place (lower triangle)
+        double d = G[(size_t)j * n + j];
+        for (int k = 0; k < j; ++k) d -= G[(size_t)j * n + k] * G[(size_t)j * n + k];
+        if (!(d > 1e-13 * scale)) return false;
+        const double l = std::sqrt(d);
+        G[(size_t)j * n + j] = l;
+        for (int i = j + 1; i < n; ++i) {
+            double s = G[(size_t)i * n + j];
+            for (int k = 0; k < j; ++k) s -= G[(size_t)i * n + k] * G[(size_t)j * n + k];
+            G[(size_t)i * n + j] = s / l;
+        }
+    }
+    Minv = W;                                                   // solve L L^T X = W column by column of W
+    for (int k = 0; k < c; ++k) {
+        for (int i = 0; i < n; ++i) {
+            double s = Minv[(size_t)i * c + k];
+            for (int j = 0; j < i; ++j) s -= G[(size_t)i * n + j] * Minv[(size_t)j * c + k];
+            Minv[(size_t)i * c + k] = s / G[(size_t)i * n + i];
+        }
+        for (int i = n - 1; i >= 0; --i) {
+            double s = Minv[(size_t)i * c + k];
+            for (int j = i + 1; j < n; ++j) s -= G[(size_t)j * n + i] * Minv[(size_t)j * c + k];
+            Minv[(size_t)i * c + k] = s / G[(size_t)i * n + i];
+        }
+    }
+    return true;
+}
+
+// samples `frames` frames overlap-add to, the filter_length // 2 at each end dropped; < 0 for frames < 1
+inline long long stft_samples(const MelPlan& p, int frames) {
+    return frames < 1 ? -1 : (long long)p.hop * (frames - 1) + p.fl - 2 * p.half;
+}
+
+enum { GL_TARGET = 0, GL_OPERAND, GL_FRAMES, GL_SIGNAL, GL_SPECTRUM, GL_PHASOR, GL_STAGES };
+
+// One workspace per call.  `operand` [B * F][NB] the GEMM's A (real parts at columns 0 .. cut - 1, imaginary parts at
+// cut .. 2 cut - 1, zero beyond and in the frames behind a row's own); `tprev` and `phasor` the same shape; `target`
+// [B * F][cut]; `tframes` [B * F][filter_length]; `padded` [B][NP] the reflect-padded rows, PW = hop (F - 1) + filter_length
+// of them logical; `gathered` (gather plans) and `spectrum` as MelGeom's; `expmel` [B * F][EK] and `minv` [cut][EK] (log-mel input).
+struct GlGeom {
+    int B, F, PW, NP, EK;
+    long long Sout;                         // output stride F * hop
+    std::vector<int> frames;                // per row
+    size_t off_info, off_target, off_operand, off_tprev, off_phasor, off_tframes, off_padded, off_gathered, off_spectrum,
+        off_expmel, off_minv, total;
+};
+
+// What tts_hip_stft_inverse (kind < 0: two planes of C = cut) and tts_hip_griffin_lim[_probe] (kind 0 / 1) may be refused
+// for -- order: pointers, B / F, frames[b], C, n_iters, momentum, a Whisper plan, pre_emph, normalisation (kind 1), a row
+// the reflect cannot pad, the 31-bit limits, mem kind, what / k (probe: what >= 0); fills `g`
+inline int stft_inv_check(const char* who, const MelPlan* p, const void* in0, const void* in1, const void* out, int B, int F, int C,
+                          const int32_t* frames, int kind, int n_iters, double momentum, int mem, int what, int k, GlGeom* g,
+                          char* msg, size_t n) {
+    const bool gl = kind >= 0;
+    if (!p || !in0 || !in1 || !out) return audio_refuse(msg, n, who, "bad argument (NULL pointer)");
+    if (B < 1 || F < 1) return audio_refuse(msg, n, who, "B = %d, F = %d: both must be >= 1", B, F);
+    g->frames.assign(B, F);
+    if (frames)
+        for (int b = 0; b < B; ++b) {
+            if (frames[b] < 1 || frames[b] > F) return audio_refuse(msg, n, who, "frames[%d] = %d outside [1, F = %d]", b, frames[b], F);
+            g->frames[b] = frames[b];
+        }
+    if (kind > 1) return audio_refuse(msg, n, who, "input_kind %d not 0 (magnitude) or 1 (log-mel)", kind);
+    const int want = kind == 1 ? p->nmel : p->cut;
+    if (C != want) return audio_refuse(msg, n, who, "C = %d, but the plan's %s is %d", C, kind == 1 ? "n_mel_channels" : "bins", want);
+    if (gl && n_iters < 0) return audio_refuse(msg, n, who, "n_iters = %d < 0", n_iters);
+    if (gl && !(std::isfinite(momentum) && momentum >= 0 && momentum < 1))
+        return audio_refuse(msg, n, who, "momentum = %g outside [0, 1)", momentum);
+    if (p->kind != TTS_HIP_MEL_TACOTRON) return audio_refuse(msg, n, who, "a Whisper plan has no inverse");
+    if (gl && p->pre > 0) return audio_refuse(msg, n, who, "pre_emph = %g > 0 cannot be inverted", p->pre);
+    if (kind == 1 && p->norm != TTS_HIP_MEL_NORM_NONE)
+        return audio_refuse(msg, n, who, "normalize_mode %d is not invertible (log-mel input)", p->norm);
+    if (gl)
+        for (int b = 0; b < B; ++b)
+            if (stft_samples(*p, g->frames[b]) <= p->half)
+                return audio_refuse(msg, n, who, "row %d: %d frames give %lld samples, not more than filter_length // 2 = %d", b,
+                                    g->frames[b], stft_samples(*p, g->frames[b]), p->half);
+    const long long PW = (long long)p->hop * (F - 1) + p->fl, NP = (PW + p->K4 - p->fl + 3) / 4 * 4;
+    const long long rows = (long long)B * F, EK = up_to(p->nmel, 32);
+    const long long biggest = std::max({(long long)B * NP * 4 + 256, rows * p->Kpad * 4, rows * p->NB * 4, rows * p->fl * 4,
+                                        rows * p->hop * 4, rows * C * 4, kind == 1 ? rows * EK * 4 : 0});
+    if (biggest >= kAudioLim || B > 65535)
+        return audio_refuse(msg, n, who, "B = %d x F = %d too large for 31-bit offsets (B <= 65535)", B, F);
+    if (int rc = audio_mem_check(who, mem, msg, n)) return rc;
+    if (what >= 0) {
+        if (what >= GL_STAGES) return audio_refuse(msg, n, who, "no stage %d (0 .. %d)", what, GL_STAGES - 1);
+        if (k < 0 || k > n_iters) return audio_refuse(msg, n, who, "k = %d outside [0, n_iters = %d]", k, n_iters);
+        if (what >= GL_SPECTRUM && k == n_iters)
+            return audio_refuse(msg, n, who, "iteration k = n_iters = %d ends at its signal: no stage %d there", k, what);
+    }
+    g->B = B, g->F = F, g->PW = (int)PW, g->NP = (int)NP, g->EK = (int)EK, g->Sout = (long long)F * p->hop;
+    Carve c;
+    g->off_info = c.take((size_t)B * 4);
+    g->off_target = c.take(gl ? (size_t)rows * p->cut * 4 : 0);
+    g->off_operand = c.take((size_t)rows * p->NB * 4);
+    g->off_tprev = c.take(gl ? (size_t)rows * p->NB * 4 : 0);
+    g->off_phasor = c.take(what == GL_PHASOR ? (size_t)rows * p->NB * 4 : 0);
+    g->off_tframes = c.take((size_t)rows * p->fl * 4);
+    g->off_padded = c.take(gl ? (size_t)B * NP * 4 + 256 : 0);
+    g->off_gathered = c.take(gl && p->gather ? (size_t)rows * p->Kpad * 4 : 0);
+    g->off_spectrum = c.take(gl ? (size_t)rows * p->NB * 4 : 0);
+    g->off_expmel = c.take(kind == 1 ? (size_t)rows * EK * 4 : 0);
+    g->off_minv = c.take(kind == 1 ? (size_t)p->cut * EK * 4 : 0);     // the caller's own Minv, transposed and padded
+    g->total = c.o;
+    return TTS_HIP_OK;
 }

@@ -211,6 +211,12 @@ struct tts_hip_mel_fn {
     MelPlan p;
     float* basis_Bt = nullptr;          // [NB][Kpad] windowed cos rows of bins 0 .. cut - 1, then the -sin rows; zero padded
     float* mel_Bt = nullptr;            // [n_mel][MAGK] Slaney filterbank, zero padded
+    // stft_inv.hip, built on first use
+    float* inv_Bt = nullptr;            // [filter_length][NB] windowed inverse basis: column r < cut the real row of bin r, cut + r the imaginary
+    float* win2 = nullptr;              // [filter_length] the centred window squared
+    float* minv_Bt = nullptr;           // [cut][EK] the filterbank's minimum-norm inverse (log-mel input), zero padded
+    int minv_state = 0;                 //   0 not tried, 1 built, -1 the factorisation failed
+    std::vector<double> win;            // the window centred in filter_length (what the tables were built from)
     std::vector<void*> allocs;
 };
 struct MelStftDev {
@@ -218,6 +224,8 @@ struct MelStftDev {
     tts_hip_mel_fn* def = nullptr;      // 1024 / 256 / 1024, 80 mels, 22 050 Hz, 0 - 8000 Hz: what tts_hip_mel_stft runs
     std::vector<tts_hip_mel_fn*> plans; // the caller's plans still alive
     DevBuf ws;                          // the one workspace of a call (MelGeom)
+    DevBuf inv_ws;                      // the one workspace of an inverse / Griffin-Lim call (GlGeom, stft_inv.hip)
+    std::vector<float> minv_h;          // host image of a caller's Minv while it is staged
 };
 
 // Waveform clean-up (audio_proc.hip): DFT bases built on first use, no weights
@@ -375,6 +383,13 @@ private:
 };
 
 int melstft_finalize(tts_hip_engine* e);
+// mel_stft.hip for stft_inv.hip: the stages mel_fn_exec can stop at, the run itself (device pointers only, the call already
+// checked; stop = -1 runs everything), its DFT product, and "NULL or a plan alive on this handle"
+enum { MEL_PADDED = 0, MEL_SPECTRUM, MEL_MAGNITUDE, MEL_LINEAR, MEL_LOG, MEL_STAGES };
+int mel_fn_exec(tts_hip_engine* e, const tts_hip_mel_fn& fn, const MelGeom& g, const float* d_audio, int B, int N, bool ragged,
+                float* d_mel, int stop = -1, StageView* stop_out = nullptr);
+int mel_dft_gemm(tts_hip_engine* e, const tts_hip_mel_fn& fn, const float* padded, float* gathered, float* ft, int B, int Fr, int NP);
+int mel_plan_check(tts_hip_engine* e, const char* name, const tts_hip_mel_fn* fn);
 void melstft_free(tts_hip_engine* e);
 void audioproc_free(tts_hip_engine* e);
 void resample_free(tts_hip_engine* e);

@@ -35,6 +35,10 @@
 // with window[I] = VALUE; else NULL) and null=cfg,fn,audio,out (fn: the call gets no plan).  First line as above, from
 // whichever check refuses first; accepted: "K4 Kpad NB MAGK gathered", "Fr Fout PW NP total" and "F_b ..." (the result's
 // frames per row), then "mel_fn_frames(N)" (tests/test_mel_fn_call.py).
+// stft_inv: the check of tts_hip_stft_inverse (input_kind=-1) / tts_hip_griffin_lim[_probe] (stft_inv_check) on a plan of the
+// mel_fn settings; settings F C input_kind n_iters momentum what k, the positional values are frames[b]; prints the status
+// line, then "PW NP EK Sout total", the eleven workspace offsets, the rows' sample counts, and with minv=1 whether the
+// filterbank's Cholesky inverse exists and its n_mel * cut values (tests/test_stft_inv.py).
 //        ttsw_check_asan --taco-call KIND [KEY=VALUE...] [LEN...]  -- the front end of a Tacotron2 call (taco_call.h) run as an
 // entry point named "who", KIND one of encode, decode, forward, infer (= the encode check, then the decode check on the batch the
 // encoder would fill, as tts_hip_tacotron2_infer* does).  Refused, first match wins -- encode: mem kind, weights not finalized,
@@ -183,7 +187,8 @@ static int print_audio_call(int argc, char** argv) {
                                     {"replace_by", 0}, {"min_voice_time", 0}, {"overlap", 0}, {"mel_kind", 0},
                                     {"sampling_rate", 22050}, {"n_mel_channels", 80}, {"filter_length", 1024},
                                     {"hop_length", 256}, {"win_length", 1024}, {"normalize_mode", 0}, {"mel_fmin", 0},
-                                    {"mel_fmax", 8000}, {"pre_emph", 0}, {"lines", 1}, {"logL", 6}};
+                                    {"mel_fmax", 8000}, {"pre_emph", 0}, {"lines", 1}, {"logL", 6}, {"F", 0}, {"C", 0},
+                                    {"input_kind", 0}, {"n_iters", 0}, {"momentum", 0}, {"what", -1}, {"k", 0}, {"minv", 0}};
     bool null_cfg = false, null_fn = false;
     int window_at = -1;
     double window_value = 1;
@@ -272,6 +277,32 @@ static int print_audio_call(int argc, char** argv) {
         printf("%d %d %d %d %d\n%d %d %d %d %zu\n", p.K4, p.Kpad, p.NB, p.MAGK, (int)p.gather, g.Fr, g.Fout, g.PW, g.NP, g.total);
         for (int b = 0; b < B; ++b) printf("%d%c", g.fout[b], b == B - 1 ? '\n' : ' ');
         printf("%d\n", mel_out_frames(p, N));
+    } else if (kind == "stft_inv") {
+        // the positional values are frames[b]; N is unused
+        const tts_hip_mel_config cfg{(int)v["mel_kind"], (int)v["sampling_rate"], (int)v["n_mel_channels"], (int)v["filter_length"],
+                                     (int)v["hop_length"], (int)v["win_length"], (int)v["normalize_mode"], v["mel_fmin"],
+                                     v["mel_fmax"], v["pre_emph"]};
+        MelPlan p{};
+        int rc = mel_cfg_check("who", &cfg, nullptr, true, &p, why, sizeof why);
+        GlGeom g;
+        const int F = (int)v["F"], ik = (int)v["input_kind"];
+        if (!rc)
+            rc = stft_inv_check("who", null_fn ? nullptr : &p, audio, audio, out, B, F, (int)v["C"], lp, ik, (int)v["n_iters"],
+                                v["momentum"], mem, (int)v["what"], (int)v["k"], &g, why, sizeof why);
+        printf("%d %s\n", rc, why);
+        if (rc) return 0;
+        if ((int)g.frames.size() != B) return 2;
+        printf("%d %d %d %lld %zu\n", g.PW, g.NP, g.EK, g.Sout, g.total);
+        printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", g.off_info, g.off_target, g.off_operand, g.off_tprev, g.off_phasor,
+               g.off_tframes, g.off_padded, g.off_gathered, g.off_spectrum, g.off_expmel, g.off_minv);
+        for (int b = 0; b < B; ++b) printf("%lld%c", stft_samples(p, g.frames[b]), b == B - 1 ? '\n' : ' ');
+        if (v["minv"] != 0) {
+            std::vector<double> Minv;
+            const bool ok = mel_min_norm_inverse(p, Minv);
+            printf("%d\n", (int)ok);
+            if (ok)
+                for (size_t i = 0; i < Minv.size(); ++i) printf("%.17g\n", Minv[i]);
+        }
     } else {
         return 2;
     }

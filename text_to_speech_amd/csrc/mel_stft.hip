@@ -146,15 +146,6 @@ __global__ void mel_whisper_kernel(float* __restrict__ x, long long n, int Fout,
     x[idx] = (m + 4.0f) / 4.0f;
 }
 
-double hz_to_mel(double f) {
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
-    return f >= min_log_hz ? min_log_mel + std::log(f / min_log_hz) / logstep : f / f_sp;
-}
-double mel_to_hz(double m) {
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = std::log(6.4) / 27.0;
-    return m >= min_log_mel ? min_log_hz * std::exp(logstep * (m - min_log_mel)) : f_sp * m;
-}
-
 void plan_free(tts_hip_mel_fn* fn) {
     if (!fn) return;
     for (void* p : fn->allocs) (void)hipFree(p);
@@ -170,6 +161,7 @@ int plan_build(tts_hip_engine* e, const MelPlan& p, const double* window, tts_hi
     // the window centred in filter_length (librosa.util.pad_center)
     std::vector<double> win(FL, 0.0);
     for (int i = 0; i < p.wl; ++i) win[p.lpad + i] = window ? window[i] : 0.5 - 0.5 * std::cos(2.0 * M_PI * i / p.wl);
+    fn->win = win;
     // windowed DFT rows (stft.py:211-236): rows 0 .. cut - 1 real, cut .. 2 cut - 1 imaginary
     std::vector<float> basis((size_t)p.NB * p.Kpad, 0.f);
     for (int r = 0; r < CUT; ++r)
@@ -182,34 +174,45 @@ int plan_build(tts_hip_engine* e, const MelPlan& p, const double* window, tts_hi
     int rc = upload(e, basis.data(), basis.size(), &fn->basis_Bt, fn->allocs);
     if (rc) return plan_free(fn), rc;
     // Slaney mel filterbank (librosa.filters.mel defaults; stft.py:65-72)
-    const double sr = p.sr;
-    std::vector<double> mel_f(p.nmel + 2);
-    const double m0 = hz_to_mel(p.fmin), m1 = hz_to_mel(p.fmax);
-    for (int i = 0; i < p.nmel + 2; ++i) mel_f[i] = mel_to_hz(m0 + (m1 - m0) * i / (p.nmel + 1));
+    std::vector<double> W;
+    mel_filterbank(p, W);
     std::vector<float> mb((size_t)p.nmel * p.MAGK, 0.f);
-    for (int i = 0; i < p.nmel; ++i) {
-        const double enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-        for (int c = 0; c < CUT; ++c) {
-            const double fr = (sr / 2.0) * c / (CUT - 1);
-            const double lower = (fr - mel_f[i]) / (mel_f[i + 1] - mel_f[i]);
-            const double upper = (mel_f[i + 2] - fr) / (mel_f[i + 2] - mel_f[i + 1]);
-            const double w = std::fmax(0.0, std::fmin(lower, upper));
-            mb[(size_t)i * p.MAGK + c] = (float)(w * enorm);
-        }
-    }
+    for (int i = 0; i < p.nmel; ++i)
+        for (int c = 0; c < CUT; ++c) mb[(size_t)i * p.MAGK + c] = (float)W[(size_t)i * CUT + c];
     rc = upload(e, mb.data(), mb.size(), &fn->mel_Bt, fn->allocs);
     if (rc) return plan_free(fn), rc;
     *out = fn;
     return TTS_HIP_OK;
 }
 
-enum { MEL_PADDED = 0, MEL_SPECTRUM, MEL_MAGNITUDE, MEL_LINEAR, MEL_LOG, MEL_STAGES };
+}  // namespace
+
+// ft[b][f][r] = sum_n padded[b][f * hop + n] * basis[r][n] for the Fr frames of each of B rows, NP floats apart (`gathered`
+// [B * Fr][Kpad]: gather plans only)
+int mel_dft_gemm(tts_hip_engine* e, const tts_hip_mel_fn& fn, const float* padded, float* gathered, float* ft, int B, int Fr, int NP) {
+    const MelPlan& p = fn.p;
+    hipStream_t st = e->stream;
+    const long long rows = (long long)B * Fr;
+    if (p.gather) {
+        const long long n = rows * p.Kpad;
+        hipLaunchKernelGGL(mel_gather_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, padded, gathered, rows, Fr, NP, p.hop, p.fl, p.Kpad);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, gemm_small(gemm_linear(gathered, p.Kpad, p.Kpad, fn.basis_Bt, p.Kpad, p.NB, (int)rows, ft), 1, st));
+    } else {
+        // one z slice per row of the batch.  A frame is read K4 floats wide (inside the row's NP); the tables' columns from
+        // filter_length on are zero
+        GemmArgs a = gemm_linear(padded, p.hop, p.Kpad, fn.basis_Bt, p.Kpad, p.NB, Fr, ft, NP, (long long)Fr * p.NB);
+        a.seg[0].k = p.K4;
+        HIPCHK(e, gemm_small(a, B, st));
+    }
+    return TTS_HIP_OK;
+}
 
 // device pointers only, the call already checked (g).  ragged: the rows' lengths and frame counts go to the device; else
 // every row is N samples and the kernels need no table.  stop (the probes): one of MEL_* returns right after that stage with
 // *stop_out describing what it wrote, each with its logical width beside the stored one; -1 runs everything.
 int mel_fn_exec(tts_hip_engine* e, const tts_hip_mel_fn& fn, const MelGeom& g, const float* d_audio, int B, int N, bool ragged,
-                float* d_mel, int stop = -1, StageView* stop_out = nullptr) {
+                float* d_mel, int stop, StageView* stop_out) {
     const MelPlan& p = fn.p;
     auto stop_at = [&](int stage, const float* ptr, size_t rows, size_t width, size_t pitch) {
         if (stop == stage && stop_out) *stop_out = StageView{ptr, rows, width, pitch};
@@ -242,18 +245,7 @@ int mel_fn_exec(tts_hip_engine* e, const tts_hip_mel_fn& fn, const MelGeom& g, c
         HIPCHK(e, hipGetLastError());
     }
     if (stop_at(MEL_PADDED, padded, B, g.PW, NP)) return TTS_HIP_OK;
-    if (p.gather) {
-        const long long n = rows * p.Kpad;
-        hipLaunchKernelGGL(mel_gather_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, padded, gathered, rows, Fr, NP, p.hop, p.fl, p.Kpad);
-        HIPCHK(e, hipGetLastError());
-        HIPCHK(e, gemm_small(gemm_linear(gathered, p.Kpad, p.Kpad, fn.basis_Bt, p.Kpad, p.NB, (int)rows, ft), 1, st));
-    } else {
-        // ft[b][f][r] = sum_n padded[b][f * hop + n] * basis[r][n], one z slice per row of the batch.  A frame is read K4
-        // floats wide (inside the row's NP); the tables' columns from filter_length on are zero
-        GemmArgs a = gemm_linear(padded, p.hop, p.Kpad, fn.basis_Bt, p.Kpad, p.NB, Fr, ft, NP, (long long)Fr * p.NB);
-        a.seg[0].k = p.K4;
-        HIPCHK(e, gemm_small(a, B, st));
-    }
+    if (int rc = mel_dft_gemm(e, fn, padded, gathered, ft, B, Fr, NP)) return rc;
     if (stop_at(MEL_SPECTRUM, ft, (size_t)rows, 2 * p.cut, p.NB)) return TTS_HIP_OK;
     {
         const long long n = rows * p.MAGK;
@@ -283,17 +275,19 @@ int mel_fn_exec(tts_hip_engine* e, const tts_hip_mel_fn& fn, const MelGeom& g, c
 }
 
 // a plan that is NULL (mel_call_check refuses it) or alive on this handle
-int plan_check(tts_hip_engine* e, const char* name, const tts_hip_mel_fn* fn) {
+int mel_plan_check(tts_hip_engine* e, const char* name, const tts_hip_mel_fn* fn) {
     const auto& plans = e->stft.plans;
     if (!fn || fn == e->stft.def || std::find(plans.begin(), plans.end(), fn) != plans.end()) return TTS_HIP_OK;
     return set_err(e, TTS_HIP_EINVAL, "%s: not a plan of this handle", name);
 }
 
+namespace {
+
 // tts_hip_mel_fn_run (what = -1), tts_hip_mel_fn_probe (what = a stage, `out` takes that stage) and the fixed entry points
 // on the default plan are one call
 int mel_fn_sync(tts_hip_engine* e, const char* name, const tts_hip_mel_fn* fn, const float* audio, int B, int N,
                 const int32_t* lengths, int what, float* out, int mem) {
-    if (int rc = plan_check(e, name, fn)) return rc;
+    if (int rc = mel_plan_check(e, name, fn)) return rc;
     MelGeom g;
     char why[256];
     if (int rc = mel_call_check(name, fn ? &fn->p : nullptr, audio, B, N, lengths, out, mem, &g, why, sizeof why))
@@ -315,7 +309,7 @@ int mel_fn_sync(tts_hip_engine* e, const char* name, const tts_hip_mel_fn* fn, c
 
 int mel_fn_async(tts_hip_engine* e, const char* name, const tts_hip_mel_fn* fn, const float* audio, int B, int N,
                  const int32_t* lengths, float* mel, void* stream) {
-    if (int rc = plan_check(e, name, fn)) return rc;
+    if (int rc = mel_plan_check(e, name, fn)) return rc;
     MelGeom g;
     char why[256];
     if (int rc = mel_call_check(name, fn ? &fn->p : nullptr, audio, B, N, lengths, mel, TTS_HIP_MEM_DEVICE, &g, why, sizeof why))
@@ -333,6 +327,7 @@ void melstft_free(tts_hip_engine* e) {
     for (tts_hip_mel_fn* fn : e->stft.plans) plan_free(fn);
     e->stft.plans.clear();
     e->stft.ws.release();
+    e->stft.inv_ws.release();
     e->stft.ready = false;
 }
 

@@ -1,0 +1,435 @@
+// stft_inv.hip -- the STFT with its phase, its inverse, and Griffin-Lim phase reconstruction on gfx950.
+//
+// Completes the reference's utils/audio/stft.py STFT class (:194-274): `transform` returns magnitude and phase (or real and
+// imaginary parts), and the windowed pseudo-inverse basis the class builds (:220-236) gets the use it was made for -- complex
+// spectrogram -> audio by a frames GEMM and an overlap-add normalised by the summed squared window.  On the two sits
+// Griffin-Lim (with the "fast" momentum term): per iteration one inverse-frames GEMM, one gather overlap-add straight into
+// the reflect-padded rows the forward DFT GEMM reads, that GEMM, and one phasor update -- no atan2 / sin / cos in the loop.
+// All rows of a batch run in one launch per part, driven by frames[b]; nothing is accumulated with atomics, so a row never
+// depends on its neighbours and a repeat gives the same bits.  include/tts_hip.h has the contract, audio_call.h the checks
+// and the geometry (GlGeom), mel_stft.hip the plans and the forward DFT.
+//
+// The inverse basis has a closed form, so no SVD runs here: pinv(scale * [cos; -sin])^T has the rows
+// c_k cos(2 pi k n / N) / (N scale) and -c_k sin(2 pi k n / N) / (N scale), c_0 = 1, c_{N/2} = 1 (N even), else c_k = 2
+// (tests/test_stft_inv.py compares it with scipy's pinv).
+#include "engine.h"
+#include "audio_dev.h"
+#include "gemm_f32.h"
+
+#include <cfloat>
+#include <cmath>
+
+using namespace ttsgemm;
+
+namespace {
+
+// (re, im) / |(re, im)|, (1, 0) at the origin.  Scaled by the larger component first: the squares of a tiny pair neither
+// underflow nor overflow.
+__device__ __forceinline__ void phasor(float re, float im, float& pr, float& pi) {
+    const float m = fmaxf(fabsf(re), fabsf(im));
+    if (!(m > 0.f)) {
+        pr = 1.f, pi = 0.f;
+        return;
+    }
+    const float a = re / m, b = im / m;
+    const float n = sqrtf(a * a + b * b);
+    pr = a / n, pi = b / n;
+}
+
+// transform: out0 / out1 [B][Fout][cut] from the spectrum [B * Fr][NB]; what 0 magnitude and phase, 1 real and imaginary
+// parts; frames at and beyond fo[b] (null: Fout) are 0
+__global__ void stft_polar_kernel(const float* __restrict__ ft, float* __restrict__ out0, float* __restrict__ out1, long long n, int Fr,
+                                  int Fout, int cut, int NB, const int* __restrict__ fo, int what) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const long long cell = idx / cut, b = cell / Fout;
+    const int f = (int)(cell % Fout), c = (int)(idx % cut);
+    float v0 = 0.f, v1 = 0.f;
+    if (f < (fo ? fo[b] : Fout)) {
+        const long long r = b * Fr + f;
+        const float re = ft[r * NB + c], im = ft[r * NB + cut + c];
+        if (what == 0) {
+            v0 = sqrtf(re * re + im * im);
+            v1 = atan2f(im, re);
+        } else {
+            v0 = re, v1 = im;
+        }
+    }
+    out0[idx] = v0;
+    out1[idx] = v1;
+}
+
+// inverse: the GEMM's A operand [B * F][NB] from two planes [B][F][cut]; form 0 magnitude and phase, 1 real and imaginary
+// parts.  Nothing behind a row's own frames is read; those frames and the K padding are 0.
+__global__ void inv_operand_kernel(const float* __restrict__ p0, const float* __restrict__ p1, float* __restrict__ A, long long n, int F,
+                                   int cut, int NB, const int* __restrict__ frames, int form) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const long long r = idx / NB;
+    const int col = (int)(idx % NB), c = col < cut ? col : col - cut;
+    float v = 0.f;
+    if (col < 2 * cut && (int)(r % F) < frames[r / F]) {
+        const float a = p0[r * cut + c], b = p1[r * cut + c];
+        if (form == 0) v = col < cut ? a * cosf(b) : a * sinf(b);
+        else v = col < cut ? a : b;
+    }
+    A[idx] = v;
+}
+
+// One sample of the overlap-add at untrimmed index i of row b (Fb frames): the frames that cover it summed in frame order,
+// divided by the summed squared window where that is above FLT_MIN, times scale
+__device__ __forceinline__ float ola_sample(const float* __restrict__ T, const float* __restrict__ win2, long long row0, int Fb, int i,
+                                            int hop, int fl, float scale) {
+    int f0 = i - fl + 1;
+    f0 = f0 <= 0 ? 0 : (f0 + hop - 1) / hop;
+    const int f1 = min(Fb - 1, i / hop);
+    float acc = 0.f, ws = 0.f;
+    for (int f = f0; f <= f1; ++f) {
+        const int k = i - f * hop;
+        acc += T[(row0 + f) * fl + k];
+        ws += win2[k];
+    }
+    if (ws > FLT_MIN) acc /= ws;
+    return acc * scale;
+}
+
+// The overlap-add as a gather, in one of two layouts.  padded != 0: y [B][NP] (+ 64 floats behind the last row) takes the
+// row's S_b = hop (Fb - 1) + fl - 2 half samples reflect-padded by half on each side -- what the forward DFT reads -- and 0
+// everywhere else.  padded == 0: y [B][pitch] takes the S_b samples and 0 beyond.
+__global__ void ola_kernel(const float* __restrict__ T, const float* __restrict__ win2, float* __restrict__ y, long long n, int B, int F,
+                           int pitch, const int* __restrict__ frames, int hop, int fl, int half, float scale, int padded) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const long long b = idx / pitch;
+    const int p = (int)(idx % pitch);
+    float v = 0.f;
+    if (b < B) {
+        const int Fb = frames[b], S = hop * (Fb - 1) + fl - 2 * half;
+        int s = -1;
+        if (padded) {
+            if (p < S + 2 * half) {
+                s = p - half;
+                if (s < 0) s = -s;
+                if (s >= S) s = 2 * (S - 1) - s;
+            }
+        } else if (p < S) {
+            s = p;
+        }
+        if (s >= 0) v = ola_sample(T, win2, b * F, Fb, s + half, hop, fl, scale);
+    }
+    y[idx] = v;
+}
+
+// log-mel input: E [B * F][EK] = exp(spec [B * F][nmel]) on a row's own frames, 0 beyond and in the K padding
+__global__ void gl_exp_kernel(const float* __restrict__ spec, float* __restrict__ E, long long n, int F, int nmel, int EK,
+                              const int* __restrict__ frames) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const long long r = idx / EK;
+    const int j = (int)(idx % EK);
+    E[idx] = j < nmel && (int)(r % F) < frames[r / F] ? expf(spec[r * nmel + j]) : 0.f;
+}
+
+// target [B * F][cut] = src (clamp: max(0, src)) on a row's own frames, else 0; the first operand S p_0 with p_0 = P(init)
+// (init [B * F][cut][2]; null: (1, 0))
+__global__ void gl_init_kernel(const float* src, float* target, const float* __restrict__ init, float* __restrict__ A, long long n, int F,
+                               int cut, int NB, const int* __restrict__ frames, int clamp) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const long long r = idx / cut;
+    const int c = (int)(idx % cut);
+    float S = 0.f, pr = 1.f, pi = 0.f;
+    if ((int)(r % F) < frames[r / F]) {
+        S = src[idx];
+        if (clamp) S = fmaxf(S, 0.f);
+        if (init) phasor(init[2 * idx], init[2 * idx + 1], pr, pi);
+    }
+    target[idx] = S;
+    A[r * NB + c] = S * pr;
+    A[r * NB + cut + c] = S * pi;
+}
+
+// The phase update: c = Y - alpha t_prev, t_prev = Y, p = P(c), next operand S p (0 behind a row's frames); `ph` (probe
+// only) takes p
+__global__ void gl_phase_kernel(const float* __restrict__ ft, float* __restrict__ tprev, const float* __restrict__ target,
+                                float* __restrict__ A, float* __restrict__ ph, long long n, int F, int cut, int NB,
+                                const int* __restrict__ frames, float alpha) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const long long r = idx / cut;
+    const int c = (int)(idx % cut);
+    const long long ir = r * NB + c, ii = ir + cut;
+    const float yr = ft[ir], yi = ft[ii];
+    const float cr = yr - alpha * tprev[ir], ci = yi - alpha * tprev[ii];
+    tprev[ir] = yr;
+    tprev[ii] = yi;
+    float pr, pi;
+    phasor(cr, ci, pr, pi);
+    const bool own = (int)(r % F) < frames[r / F];
+    const float S = own ? target[idx] : 0.f;
+    A[ir] = S * pr;
+    A[ii] = S * pi;
+    if (ph) ph[ir] = pr, ph[ii] = pi;
+}
+
+// the windowed inverse basis and the squared window of a plan, on first use
+int inv_tables(tts_hip_engine* e, tts_hip_mel_fn* fn) {
+    if (fn->inv_Bt) return TTS_HIP_OK;
+    const MelPlan& p = fn->p;
+    const int N = p.fl;
+    const double scale = (double)p.fl / p.hop;
+    std::vector<float> bt((size_t)N * p.NB, 0.f), w2(N);
+    for (int n = 0; n < N; ++n) {
+        for (int k = 0; k < p.cut; ++k) {
+            const double ck = (k == 0 || 2 * k == N) ? 1.0 : 2.0;
+            const double ang = 2.0 * M_PI * (double)(((long long)k * n) % N) / N;          // exact phase reduction
+            bt[(size_t)n * p.NB + k] = (float)((double)(float)(ck * std::cos(ang) / (N * scale)) * fn->win[n]);
+            bt[(size_t)n * p.NB + p.cut + k] = (float)((double)(float)(-ck * std::sin(ang) / (N * scale)) * fn->win[n]);
+        }
+        w2[n] = (float)(fn->win[n] * fn->win[n]);
+    }
+    if (int rc = upload(e, w2.data(), w2.size(), &fn->win2, fn->allocs)) return rc;
+    return upload(e, bt.data(), bt.size(), &fn->inv_Bt, fn->allocs);
+}
+
+// the plan's own mel inversion, on first use
+int minv_table(tts_hip_engine* e, const char* name, tts_hip_mel_fn* fn) {
+    if (fn->minv_state == 0) {
+        std::vector<double> Minv;
+        if (!mel_min_norm_inverse(fn->p, Minv)) {
+            fn->minv_state = -1;
+        } else {
+            const int EK = up_to(fn->p.nmel, 32), cut = fn->p.cut;
+            std::vector<float> bt((size_t)cut * EK, 0.f);
+            for (int j = 0; j < fn->p.nmel; ++j)
+                for (int c = 0; c < cut; ++c) bt[(size_t)c * EK + j] = (float)Minv[(size_t)j * cut + c];
+            if (int rc = upload(e, bt.data(), bt.size(), &fn->minv_Bt, fn->allocs)) return rc;
+            fn->minv_state = 1;
+        }
+    }
+    if (fn->minv_state < 0)
+        return set_err(e, TTS_HIP_EINVAL, "%s: the plan's filterbank has no minimum-norm inverse (a mel channel without a bin)", name);
+    return TTS_HIP_OK;
+}
+
+struct GlBufs {
+    int* info;
+    float *target, *operand, *tprev, *phasor, *tframes, *padded, *gathered, *spectrum, *expmel, *minv;
+};
+
+int gl_bufs(tts_hip_engine* e, const GlGeom& g, GlBufs* w) {
+    HIPCHK(e, e->stft.inv_ws.ensure(g.total));
+    char* base = (char*)e->stft.inv_ws.p;
+    *w = GlBufs{(int*)(base + g.off_info),        (float*)(base + g.off_target),   (float*)(base + g.off_operand),
+                (float*)(base + g.off_tprev),     (float*)(base + g.off_phasor),   (float*)(base + g.off_tframes),
+                (float*)(base + g.off_padded),    (float*)(base + g.off_gathered), (float*)(base + g.off_spectrum),
+                (float*)(base + g.off_expmel),    (float*)(base + g.off_minv)};
+    e->audio_info_h.assign(g.frames.begin(), g.frames.end());
+    return stage_row_info(e, w->info);
+}
+
+// tframes [B * F][filter_length] = operand x inverse basis
+int inverse_frames(tts_hip_engine* e, const tts_hip_mel_fn& fn, const GlGeom& g, const GlBufs& w) {
+    const MelPlan& p = fn.p;
+    HIPCHK(e, gemm_small(gemm_linear(w.operand, p.NB, p.NB, fn.inv_Bt, p.NB, p.fl, g.B * g.F, w.tframes), 1, e->stream));
+    return TTS_HIP_OK;
+}
+
+int overlap_add(tts_hip_engine* e, const tts_hip_mel_fn& fn, const GlGeom& g, const GlBufs& w, float* y, bool padded) {
+    const MelPlan& p = fn.p;
+    const int pitch = padded ? g.NP : (int)g.Sout;
+    const long long n = (long long)g.B * pitch + (padded ? 64 : 0);
+    hipLaunchKernelGGL(ola_kernel, dim3(blocks(n, 256)), dim3(256), 0, e->stream, w.tframes, fn.win2, y, n, g.B, g.F, pitch, w.info, p.hop,
+                       p.fl, p.half, (float)((double)p.fl / p.hop), padded ? 1 : 0);
+    HIPCHK(e, hipGetLastError());
+    return TTS_HIP_OK;
+}
+
+// device pointers only, the call already checked (g).  stop_k / stop_what >= 0 (the probe): return right after that stage of
+// that iteration with *view describing it.  With tts_hip_kernel_timing on, the four parts of an iteration are timed as kinds
+// 0 (inverse-frames GEMM), 1 (overlap-add), 2 (forward DFT, its gather included) and 3 (phase update)
+int gl_exec(tts_hip_engine* e, tts_hip_mel_fn& fn, const GlGeom& g, const float* d_spec, int kind, const double* Minv,
+            const float* d_init, int n_iters, double momentum, float* d_audio, int stop_k, int stop_what, StageView* view) {
+    const MelPlan& p = fn.p;
+    hipStream_t st = e->stream;
+    GlBufs w;
+    if (int rc = gl_bufs(e, g, &w)) return rc;
+    const long long rows = (long long)g.B * g.F, cells = rows * p.cut;
+    auto stop_at = [&](int it, int stage, const float* ptr, size_t nrows, size_t width, size_t pitch) {
+        const bool hit = stop_what == stage && (stage == GL_TARGET || stop_k == it);
+        if (hit && view) *view = StageView{ptr, nrows, width, pitch};
+        return hit;
+    };
+    HIPCHK(e, hipMemsetAsync(w.tprev, 0, (size_t)rows * p.NB * 4, st));
+    HIPCHK(e, hipMemsetAsync(w.operand, 0, (size_t)rows * p.NB * 4, st));
+    const float* src = d_spec;
+    if (kind == 1) {
+        const float* minv_Bt = fn.minv_Bt;
+        if (Minv) {                                     // the caller's [n_mel][cut] in double -> [cut][EK] fp32
+            e->stft.minv_h.assign((size_t)p.cut * g.EK, 0.f);
+            for (int j = 0; j < p.nmel; ++j)
+                for (int c = 0; c < p.cut; ++c) e->stft.minv_h[(size_t)c * g.EK + j] = (float)Minv[(size_t)j * p.cut + c];
+            HIPCHK(e, hipMemcpyAsync(w.minv, e->stft.minv_h.data(), e->stft.minv_h.size() * 4, hipMemcpyHostToDevice, st));
+            minv_Bt = w.minv;
+        }
+        const long long n = rows * g.EK;
+        hipLaunchKernelGGL(gl_exp_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, d_spec, w.expmel, n, g.F, p.nmel, g.EK, w.info);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, gemm_small(gemm_linear(w.expmel, g.EK, g.EK, minv_Bt, g.EK, p.cut, (int)rows, w.target), 1, st));
+        src = w.target;
+    }
+    hipLaunchKernelGGL(gl_init_kernel, dim3(blocks(cells, 256)), dim3(256), 0, st, src, w.target, d_init, w.operand, cells, g.F, p.cut,
+                       p.NB, w.info, kind == 1 ? 1 : 0);
+    HIPCHK(e, hipGetLastError());
+    if (stop_at(0, GL_TARGET, w.target, (size_t)rows, p.cut, p.cut)) return TTS_HIP_OK;
+    const float alpha = (float)(momentum / (1.0 + momentum));
+    for (int it = 0;; ++it) {
+        if (stop_at(it, GL_OPERAND, w.operand, (size_t)rows, 2 * p.cut, p.NB)) return TTS_HIP_OK;
+        timing_begin(e, 0);
+        if (int rc = inverse_frames(e, fn, g, w)) return rc;
+        timing_end(e);
+        if (stop_at(it, GL_FRAMES, w.tframes, (size_t)rows, p.fl, p.fl)) return TTS_HIP_OK;
+        if (it == n_iters && stop_what != GL_SIGNAL) return overlap_add(e, fn, g, w, d_audio, false);
+        timing_begin(e, 1);
+        if (int rc = overlap_add(e, fn, g, w, w.padded, true)) return rc;
+        timing_end(e);
+        if (stop_at(it, GL_SIGNAL, w.padded, g.B, g.PW, g.NP)) return TTS_HIP_OK;
+        timing_begin(e, 2);
+        if (int rc = mel_dft_gemm(e, fn, w.padded, w.gathered, w.spectrum, g.B, g.F, g.NP)) return rc;
+        timing_end(e);
+        if (stop_at(it, GL_SPECTRUM, w.spectrum, (size_t)rows, 2 * p.cut, p.NB)) return TTS_HIP_OK;
+        float* ph = stop_what == GL_PHASOR && stop_k == it ? w.phasor : nullptr;
+        timing_begin(e, 3);
+        hipLaunchKernelGGL(gl_phase_kernel, dim3(blocks(cells, 256)), dim3(256), 0, st, w.spectrum, w.tprev, w.target, w.operand, ph, cells,
+                           g.F, p.cut, p.NB, w.info, alpha);
+        HIPCHK(e, hipGetLastError());
+        timing_end(e);
+        if (stop_at(it, GL_PHASOR, w.phasor, (size_t)rows, 2 * p.cut, p.NB)) return TTS_HIP_OK;
+    }
+}
+
+// tts_hip_griffin_lim (what = -1), its probe (what = a stage of iteration k) and the _async form (stream, device pointers)
+int gl_call(tts_hip_engine* e, const char* name, const float* spec, int B, int F, int C, const int32_t* frames, const tts_hip_mel_fn* fn,
+            int input_kind, const double* Minv, const float* init, int n_iters, double momentum, int k, int what, float* out, int mem,
+            bool async, void* stream) {
+    if (int rc = mel_plan_check(e, name, fn)) return rc;
+    GlGeom g;
+    char why[256];
+    if (input_kind < 0) return set_err(e, TTS_HIP_EINVAL, "%s: input_kind %d not 0 (magnitude) or 1 (log-mel)", name, input_kind);
+    if (int rc = stft_inv_check(name, fn ? &fn->p : nullptr, spec, spec, out, B, F, C, frames, input_kind, n_iters, momentum, mem, what, k,
+                                &g, why, sizeof why))
+        return set_err(e, rc, "%s", why);
+    tts_hip_mel_fn* plan = const_cast<tts_hip_mel_fn*>(fn);
+    HIPCHK(e, hipSetDevice(e->device));
+    if (input_kind == 1 && !Minv)
+        if (int rc = minv_table(e, name, plan)) return rc;
+    if (int rc = inv_tables(e, plan)) return rc;
+    const size_t rows = (size_t)B * F;
+    if (async) {
+        StreamScope scope(e, stream);
+        return gl_exec(e, *plan, g, spec, input_kind, Minv, init, n_iters, momentum, out, -1, -1, nullptr);
+    }
+    AudioStage io(e, mem);
+    const int in = io.in(spec, rows * C * 4);
+    const int in2 = io.in(init, rows * fn->p.cut * 8);
+    const size_t n_audio = (size_t)B * g.Sout * 4;
+    const int res = what >= 0 ? io.scratch(n_audio) : io.out(out, n_audio);
+    if (int rc = io.begin()) return rc;
+    StageView view{};
+    if (int rc = gl_exec(e, *plan, g, io.ptr<const float>(in), input_kind, Minv, io.ptr<const float>(in2), n_iters, momentum,
+                         io.ptr<float>(res), k, what, &view))
+        return rc;
+    if (what >= 0)
+        if (int rc = copy_stage_out(e, view, out, mem)) return rc;
+    const int rc = io.finish();
+    timing_collect(e);
+    return rc;
+}
+
+}  // namespace
+
+long long tts_hip_mel_fn_samples(const tts_hip_mel_fn* fn, int frames) { return fn ? stft_samples(fn->p, frames) : -1; }
+
+int tts_hip_stft_transform(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                           int what, float* out0, float* out1, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    const char* name = "stft_transform";
+    if (int rc = mel_plan_check(e, name, fn)) return rc;
+    MelGeom g;
+    char why[256];
+    if (!out1) return set_err(e, TTS_HIP_EINVAL, "%s: bad argument", name);
+    if (int rc = mel_call_check(name, fn ? &fn->p : nullptr, audio, B, N, lengths, out0, mem, &g, why, sizeof why))
+        return set_err(e, rc, "%s", why);
+    if (fn->p.kind != TTS_HIP_MEL_TACOTRON) return set_err(e, TTS_HIP_EINVAL, "%s: refused for a Whisper plan", name);
+    if (what < 0 || what > 1) return set_err(e, TTS_HIP_EINVAL, "%s: what %d not 0 (magnitude, phase) or 1 (real, imaginary)", name, what);
+    HIPCHK(e, hipSetDevice(e->device));
+    const MelPlan& p = fn->p;
+    const size_t n_out = (size_t)B * g.Fout * p.cut;
+    AudioStage io(e, mem);
+    const int in = io.in(audio, (size_t)B * N * 4);
+    const int o0 = io.out(out0, n_out * 4), o1 = io.out(out1, n_out * 4);
+    if (int rc = io.begin()) return rc;
+    StageView view{};
+    if (int rc = mel_fn_exec(e, *fn, g, io.ptr<const float>(in), B, N, lengths != nullptr, nullptr, MEL_SPECTRUM, &view)) return rc;
+    // ragged: mel_fn_exec left [lens | fout] at the head of its workspace
+    const int* d_fo = lengths ? (const int*)((const char*)e->stft.ws.p + g.off_info) + B : nullptr;
+    hipLaunchKernelGGL(stft_polar_kernel, dim3(blocks((long long)n_out, 256)), dim3(256), 0, e->stream, (const float*)view.p,
+                       io.ptr<float>(o0), io.ptr<float>(o1), (long long)n_out, g.Fr, g.Fout, p.cut, p.NB, d_fo, what);
+    HIPCHK(e, hipGetLastError());
+    return io.finish();
+}
+
+int tts_hip_stft_inverse(tts_hip_engine* e, const float* plane0, int B, int F, const float* plane1, const int32_t* frames,
+                         const tts_hip_mel_fn* fn, int form, float* audio, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    const char* name = "stft_inverse";
+    if (int rc = mel_plan_check(e, name, fn)) return rc;
+    GlGeom g;
+    char why[256];
+    if (int rc = stft_inv_check(name, fn ? &fn->p : nullptr, plane0, plane1, audio, B, F, fn ? fn->p.cut : 0, frames, -1, 0, 0.0, mem, -1,
+                                0, &g, why, sizeof why))
+        return set_err(e, rc, "%s", why);
+    if (form < 0 || form > 1) return set_err(e, TTS_HIP_EINVAL, "%s: form %d not 0 (magnitude, phase) or 1 (real, imaginary)", name, form);
+    tts_hip_mel_fn* plan = const_cast<tts_hip_mel_fn*>(fn);
+    HIPCHK(e, hipSetDevice(e->device));
+    if (int rc = inv_tables(e, plan)) return rc;
+    const MelPlan& p = fn->p;
+    const size_t n_in = (size_t)B * F * p.cut * 4;
+    AudioStage io(e, mem);
+    const int i0 = io.in(plane0, n_in), i1 = io.in(plane1, n_in);
+    const int res = io.out(audio, (size_t)B * g.Sout * 4);
+    if (int rc = io.begin()) return rc;
+    GlBufs w;
+    if (int rc = gl_bufs(e, g, &w)) return rc;
+    const long long n = (long long)B * F * p.NB;
+    hipLaunchKernelGGL(inv_operand_kernel, dim3(blocks(n, 256)), dim3(256), 0, e->stream, io.ptr<const float>(i0), io.ptr<const float>(i1),
+                       w.operand, n, F, p.cut, p.NB, w.info, form);
+    HIPCHK(e, hipGetLastError());
+    if (int rc = inverse_frames(e, *plan, g, w)) return rc;
+    if (int rc = overlap_add(e, *plan, g, w, io.ptr<float>(res), false)) return rc;
+    return io.finish();
+}
+
+int tts_hip_griffin_lim(tts_hip_engine* e, const float* spec, int B, int F, int C, const int32_t* frames, const tts_hip_mel_fn* fn,
+                        int input_kind, const double* Minv, const float* init, int n_iters, double momentum, float* audio, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    return gl_call(e, "griffin_lim", spec, B, F, C, frames, fn, input_kind, Minv, init, n_iters, momentum, 0, -1, audio, mem, false,
+                   nullptr);
+}
+
+int tts_hip_griffin_lim_async(tts_hip_engine* e, const float* spec, int B, int F, int C, const int32_t* frames,
+                              const tts_hip_mel_fn* fn, int input_kind, const double* Minv, const float* init, int n_iters,
+                              double momentum, float* audio, void* stream) {
+    if (!e) return TTS_HIP_EINVAL;
+    return gl_call(e, "griffin_lim_async", spec, B, F, C, frames, fn, input_kind, Minv, init, n_iters, momentum, 0, -1, audio,
+                   TTS_HIP_MEM_DEVICE, true, stream);
+}
+
+int tts_hip_griffin_lim_probe(tts_hip_engine* e, const float* spec, int B, int F, int C, const int32_t* frames,
+                              const tts_hip_mel_fn* fn, int input_kind, const double* Minv, const float* init, int n_iters,
+                              double momentum, int k, int what, float* out, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (what < 0) return set_err(e, TTS_HIP_EINVAL, "griffin_lim_probe: no stage %d (0 .. %d)", what, GL_STAGES - 1);
+    return gl_call(e, "griffin_lim_probe", spec, B, F, C, frames, fn, input_kind, Minv, init, n_iters, momentum, k, what, out, mem, false,
+                   nullptr);
+}

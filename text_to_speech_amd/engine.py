@@ -987,6 +987,146 @@ class HipEngine:
         return self._host_call('mel_fn_probe', audio, B, N, [], lambda empty: (empty(shape, 'float32'),),
                                lambda extras, outs: (self._ptr(lens), plan.handle, self._MEL_FN_STAGES[what], outs[0]))[0]
 
+    # ------------------------------------------------------------------ STFT with phase, inverse, Griffin-Lim (csrc/stft_inv.hip)
+    def _planes_call(self, name, inputs, make_outputs, args, stream=None):
+        """tts_hip_<name> on arrays of any rank.  `inputs`: (array or None, shape) pairs, the first one never None; all numpy-like
+        -> host call and numpy outputs, the first a CUDA tensor -> device call and CUDA outputs (`stream`: tts_hip_<name>_async
+        enqueued there, `_staged`).  `make_outputs(empty)` as `_host_call`'s; `args(ins, outs)` returns, with every array
+        turned into its pointer, everything the C function takes between the handle and the trailing mem kind / stream."""
+        first = inputs[0][0]
+        if not _is_torch_cuda(first):
+            if stream is not None:
+                raise ValueError('stream= needs device tensors')
+
+            def host(x, shape):
+                if x is None:
+                    return None
+                x = x.detach().cpu() if hasattr(x, 'detach') else x
+                return np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(shape))
+
+            ins = [host(x, shape) for x, shape in inputs]
+            outs = make_outputs(lambda shape, dtype: np.empty(shape, dtype=dtype))
+            self._check(getattr(self._lib, 'tts_hip_' + name)(self._h, *args([self._ptr(x) for x in ins], [self._ptr(o) for o in outs]),
+                                                              MEM_HOST), name)
+            return outs
+        torch = self._torch()
+        inputs = [(torch.as_tensor(np.asarray(x, np.float32), device=first.device) if x is not None and not _is_torch_cuda(x) else x,
+                   shape) for x, shape in inputs]
+        self._check_device(*(x for x, _ in inputs))
+
+        def prepared():
+            ins = [x.to(torch.float32).reshape(shape).contiguous() if x is not None else None for x, shape in inputs]
+            outs = make_outputs(lambda shape, dtype: torch.empty(shape, dtype=getattr(torch, dtype), device=first.device))
+            return (*ins, *outs)
+
+        tensors, sp = self._staged(stream, prepared, *(x for x, _ in inputs))
+        ins, outs = tensors[:len(inputs)], tensors[len(inputs):]
+        fn, last = (name, MEM_DEVICE) if stream is None else (name + '_async', sp)
+        self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, *args([self._ptr(x) for x in ins], [self._ptr(o) for o in outs]), last), fn)
+        return outs
+
+    @staticmethod
+    def _frame_counts(frames, B, F, what):
+        """int32 [B] frame counts in [1, F] (None: None).  Raises before any GPU call."""
+        if frames is None:
+            return None
+        if hasattr(frames, 'detach'):
+            frames = frames.detach().cpu().numpy()
+        fr = np.ascontiguousarray(np.atleast_1d(np.asarray(frames)).astype(np.int64))
+        if fr.shape != (B,):
+            raise ValueError(f'{what}: frames must have shape ({B},), got {fr.shape}')
+        if fr.min() < 1 or fr.max() > F:
+            raise ValueError(f'{what}: frames must lie in [1, {F}]')
+        return fr.astype(np.int32)
+
+    def mel_fn_samples(self, plan, frames):
+        """Samples `frames` frames overlap-add to under `plan`: hop * (frames - 1) + filter_length - 2 * (filter_length // 2)."""
+        n = self._lib.tts_hip_mel_fn_samples(plan.handle, int(frames))
+        if n < 0:
+            raise ValueError(f'mel_fn_samples: frames = {frames} < 1')
+        return int(n)
+
+    def stft_transform(self, plan, audio, lengths=None, polar=True):
+        """audio [N] or [B, N] -> two planes [B, F, filter_length // 2 + 1] under `plan` (Tacotron kind), F =
+        mel_fn_frames(plan, N): (magnitude, phase), or with polar=False (real, imaginary) -- the reference's STFT.transform on
+        the plan's padding and window.  Frames at and beyond a row's own (`lengths`) are 0.  numpy in -> numpy out, a CUDA
+        tensor in -> CUDA tensors out."""
+        B, N, lens = self._audio_rows(audio, lengths, 'stft_transform')
+        F = self.mel_fn_frames(plan, N)
+        C = plan.geometry['filter_length'] // 2 + 1
+        outs = self._planes_call('stft_transform', [(audio, (B, N))],
+                                 lambda empty: (empty((B, F, C), 'float32'), empty((B, F, C), 'float32')),
+                                 lambda ins, outs: (ins[0], B, N, self._ptr(lens), plan.handle, 0 if polar else 1, outs[0], outs[1]))
+        return outs[0], outs[1]
+
+    def stft_inverse(self, plan, plane0, plane1, frames=None, polar=True):
+        """Two planes [F, C] or [B, F, C] (C = filter_length // 2 + 1; magnitude and phase, or with polar=False real and imaginary
+        parts) -> audio [B, F * hop_length]: row b holds mel_fn_samples(plan, frames[b]) samples (default F frames), zeros
+        beyond; nothing behind a row's frames is read."""
+        shape = tuple(plane0.shape)
+        if len(shape) not in (2, 3) or tuple(plane1.shape) != shape:
+            raise ValueError(f'stft_inverse: planes must both be [F, C] or [B, F, C], got {shape} and {tuple(plane1.shape)}')
+        B, F, C = (1, *shape) if len(shape) == 2 else shape
+        B, F, C = int(B), int(F), int(C)
+        if C != plan.geometry['filter_length'] // 2 + 1:
+            raise ValueError(f"stft_inverse: {C} bins, the plan has {plan.geometry['filter_length'] // 2 + 1}")
+        fr = self._frame_counts(frames, B, F, 'stft_inverse')
+        hop = plan.geometry['hop_length']
+        return self._planes_call('stft_inverse', [(plane0, (B, F, C)), (plane1, (B, F, C))],
+                                 lambda empty: (empty((B, F * hop), 'float32'),),
+                                 lambda ins, outs: (ins[0], B, F, ins[1], self._ptr(fr), plan.handle, 0 if polar else 1, outs[0]))[0]
+
+    _GL_KINDS = {'magnitude': 0, 'log_mel': 1}
+    _GL_STAGES = {'target': 0, 'operand': 1, 'frames': 2, 'signal': 3, 'spectrum': 4, 'phasor': 5}
+
+    def _gl_args(self, plan, spec, frames, kind, mel_inverse, init, what):
+        if kind not in self._GL_KINDS:
+            raise ValueError(f'{what}: kind must be one of {tuple(self._GL_KINDS)}, got {kind!r}')
+        shape = tuple(spec.shape)
+        if len(shape) not in (2, 3):
+            raise ValueError(f'{what}: spec must be [F, C] or [B, F, C], got {shape}')
+        B, F, C = (1, *shape) if len(shape) == 2 else shape
+        B, F, C = int(B), int(F), int(C)
+        bins = plan.geometry['filter_length'] // 2 + 1
+        fr = self._frame_counts(frames, B, F, what)
+        minv = None
+        if mel_inverse is not None:
+            minv = np.ascontiguousarray(mel_inverse, dtype=np.float64)
+            if kind != 'log_mel' or minv.shape != (plan.n_mel, bins):
+                raise ValueError(f"{what}: mel_inverse goes with kind='log_mel' and must be [{plan.n_mel}, {bins}]")
+        return B, F, C, bins, fr, minv, [(spec, (B, F, C)), (init, (B, F, bins, 2))]
+
+    def griffin_lim(self, plan, spec, frames=None, kind='magnitude', n_iters=60, momentum=0.99, init=None, mel_inverse=None,
+                    stream=None):
+        """Griffin-Lim phase reconstruction (tts_hip_griffin_lim) under `plan`: spec [F, C] or [B, F, C] -> audio
+        [B, F * hop_length].  kind='magnitude': C = filter_length // 2 + 1 linear magnitudes; 'log_mel': C = n_mel log-mels,
+        turned into magnitudes by max(0, exp(spec) . mel_inverse) (`mel_inverse` float64 [n_mel, bins]; None: the minimum-norm
+        inverse of the plan's filterbank).  `init` [B, F, bins, 2]: the initial phase as (re, im) pairs of any length (None:
+        zero phase).  Row b holds `frames[b]` frames (default F).  `stream` as `mel_fn_run`."""
+        B, F, C, bins, fr, minv, inputs = self._gl_args(plan, spec, frames, kind, mel_inverse, init, 'griffin_lim')
+        hop = plan.geometry['hop_length']
+        keep = (fr, minv)                                                       # host tables stay alive across the call
+        out = self._planes_call('griffin_lim', inputs, lambda empty: (empty((B, F * hop), 'float32'),),
+                                lambda ins, outs: (ins[0], B, F, C, self._ptr(fr), plan.handle, self._GL_KINDS[kind], self._ptr(minv),
+                                                   ins[1], int(n_iters), float(momentum), outs[0]), stream)[0]
+        del keep
+        return out
+
+    def griffin_lim_probe(self, plan, spec, k, what, frames=None, kind='magnitude', n_iters=3, momentum=0.99, init=None,
+                          mel_inverse=None):
+        """Test hook (tts_hip_griffin_lim_probe): run `griffin_lim` on the same arguments (host arrays) up to stage `what` of
+        iteration k and return it: 'target' [B, F, bins]; 'operand', 'spectrum', 'phasor' [B, F, 2 bins] (real parts, then
+        imaginary parts); 'frames' [B, F, filter_length]; 'signal' [B, hop * (F - 1) + filter_length] (the reflect-padded row)."""
+        if what not in self._GL_STAGES:
+            raise ValueError(f'what must be one of {tuple(self._GL_STAGES)}, got {what!r}')
+        B, F, C, bins, fr, minv, inputs = self._gl_args(plan, spec, frames, kind, mel_inverse, init, 'griffin_lim_probe')
+        g = plan.geometry
+        shape = {'target': (B, F, bins), 'frames': (B, F, g['filter_length']),
+                 'signal': (B, g['hop_length'] * (F - 1) + g['filter_length'])}.get(what, (B, F, 2 * bins))
+        return self._planes_call('griffin_lim_probe', inputs, lambda empty: (empty(shape, 'float32'),),
+                                 lambda ins, outs: (ins[0], B, F, C, self._ptr(fr), plan.handle, self._GL_KINDS[kind], self._ptr(minv),
+                                                    ins[1], int(n_iters), float(momentum), int(k), self._GL_STAGES[what], outs[0]))[0]
+
     # ------------------------------------------------------------------ waveform clean-up (csrc/audio_proc.hip)
     _TRIM_MODES = {'start_end': 0, 'start': 1, 'end': 2}
 

@@ -749,16 +749,28 @@ def _backlog_groups(source, k, is_cached=lambda text: False):
 _models = {}
 
 
-def get_models(path='synthetic', device=0, lang='en', overlap=False, **kwargs):
+def get_models(path='synthetic', device=0, lang='en', overlap=False, vocoder=None, **kwargs):
     """(Tacotron2, WaveGlow) pair -- the analogue of models/tts/__init__.py:get_models.  By default both share one engine
     handle; `overlap=True` gives the vocoder its own handle (second HIP stream, second weight copy) so that
-    `stream(..., overlap=True)` can run the two models concurrently."""
+    `stream(..., overlap=True)` can run the two models concurrently.  `vocoder='griffin_lim'`: (Tacotron2, GriffinLim) on the
+    synthesizer's engine -- no WaveGlow weights are needed; Griffin-Lim has no handle of its own to overlap with, so it is
+    refused together with `overlap=True`."""
     from .runtime import HipRuntime, build_runtime
     from .waveglow import WaveGlow
     spk_dim = int(kwargs.get('speaker_embedding_dim', 0) or 0)
     embeddings = kwargs.pop('embeddings', None)
-    key = (path, device, lang, bool(overlap), spk_dim)
-    if key not in _models:
+    if vocoder not in (None, 'griffin_lim'):
+        raise ValueError(f"vocoder must be None (WaveGlow) or 'griffin_lim', got {vocoder!r}")
+    if vocoder and overlap:
+        raise ValueError("vocoder='griffin_lim' runs on the synthesizer's engine: overlap=True does not apply")
+    key = (path, device, lang, bool(overlap), spk_dim) + ((vocoder,) if vocoder else ())
+    if key not in _models and vocoder == 'griffin_lim':
+        from .griffin_lim import GriffinLim
+        synth = build_runtime('hip', path, model='tacotron2', device=device, **kwargs)
+        model = (SV2TTSTacotron2(synth, lang=lang, embedding_dim=spk_dim, embeddings=embeddings) if spk_dim
+                 else Tacotron2(synth, lang=lang))
+        _models[key] = (model, GriffinLim(synth.engine))
+    elif key not in _models:
         synth = build_runtime('hip', path, model='tacotron2', device=device, **kwargs)
         if overlap:
             eng = HipRuntime.load_engine(path, device=device, **kwargs)
@@ -773,11 +785,23 @@ def get_models(path='synthetic', device=0, lang='en', overlap=False, **kwargs):
     return _models[key]
 
 
+def _named_vocoder(model, vocoder):
+    """`vocoder='griffin_lim'` beside a caller's own model: a GriffinLim on that model's engine (nothing is loaded or cached);
+    everything else as it came."""
+    if isinstance(vocoder, str) and vocoder == 'griffin_lim':
+        engine = getattr(getattr(model, 'compiled_infer', None), 'engine', None)
+        if engine is not None:
+            from .griffin_lim import GriffinLim
+            return GriffinLim(engine)
+    return vocoder
+
+
 def tts(text, *, lang='en', model=None, vocoder=None, path='synthetic', device=0, **kwargs):
     """models.tts.tts (models/tts/__init__.py:62-77): one text -> its result dict; a list of texts -> list of dicts."""
-    if model is None or vocoder is None:
-        m, v = get_models(path, device, lang)
-        model, vocoder = model or m, vocoder or v
+    vocoder = _named_vocoder(model, vocoder)
+    if model is None or vocoder is None or isinstance(vocoder, str):
+        m, v = get_models(path, device, lang, vocoder=vocoder if isinstance(vocoder, str) else None)
+        model, vocoder = model or m, v if vocoder is None or isinstance(vocoder, str) else vocoder
     res = model.predict(text, vocoder=vocoder, **kwargs)
     return res[0] if isinstance(text, (str, dict)) else res
 
