@@ -517,6 +517,39 @@ int tts_hip_griffin_lim_probe(tts_hip_engine* e, const float* spec, int B, int F
                               const tts_hip_mel_fn* fn, int input_kind, const double* Minv, const float* init, int n_iters,
                               double momentum, int k, int what, float* out, int mem);
 
+/* ---- WaveGlow denoiser (csrc/stft_inv.hip): spectral subtraction of a model's bias spectrum, the phase kept.
+ * A WaveGlow checkpoint fed a silent mel and no noise still emits a faint tonal hum; the published vocoder ships with a
+ * denoiser that takes the magnitude spectrum of that hum once per model and subtracts strength x it from every frame.
+ *
+ * denoise: audio [B, N], lengths as tts_hip_mel_fn_run, bias [cut] >= 0 (follows `mem`; device memory for the _async form),
+ *   strength >= 0 (used as s = (float)strength) -> out [B, N], under a Tacotron-kind plan:
+ *   X = the transform's spectrum of every row (steps 1 - 4 of the mel plan: what tts_hip_mel_fn_probe returns as stage 1);
+ *   per bin, with m = |X| taken from the pair scaled by its larger component: Y = max(m - s * bias[c], 0) * X / m, Y = 0
+ *   where m = 0 (no atan2 / sin / cos); frames at and beyond a row's own are 0; out = inverse(Y) as tts_hip_stft_inverse
+ *   computes it, cut to the row: row b holds min(lengths[b], tts_hip_mel_fn_samples(fn, frames_b)) samples, frames_b =
+ *   tts_hip_mel_fn_frames(fn, lengths[b]), and zeros beyond.  A vocoder row of frames * 256 samples under the default
+ *   geometry (1024 / 256 / 1024) gets back exactly its samples; a row shorter than win_length is zero-padded by the plan and
+ *   cut back to its length.  Nothing behind a row's length is read, nothing is accumulated with atomics: a row is
+ *   bit-equal to the row called alone and a repeat gives the same bits.  out == audio is allowed for device memory (the
+ *   transform has consumed the audio before the overlap-add writes).  The transform runs in the mel workspace of the
+ *   handle, the inverse in the inverse workspace, with no host round trip between them: the _async form (device pointers,
+ *   a stream) does not synchronize.
+ *
+ * denoise_probe (test hook): the code of the call, not a copy, stopped after stage `what`, with F =
+ *   tts_hip_mel_fn_frames(fn, N): 0 spectrum X [B, F, 2 cut] (real parts, then imaginary parts); 1 the gated operand Y
+ *   [B, F, 2 cut]; 2 time frames [B, F, filter_length].  The call itself is the last stage.
+ *
+ * Refusals (TTS_HIP_EINVAL, first match wins, nothing copied or launched): a plan that is not a plan of this handle; a NULL
+ * plan, audio or out, B or N < 1; a lengths[b] outside [1, N]; a row the reflect cannot pad (as tts_hip_mel_fn_run); a
+ * Whisper plan; bias NULL; strength negative or not finite; a buffer at or above 2^31 - 65536 bytes or B > 65535; a bad
+ * mem kind; a `what` outside 0 .. 2 (probe). */
+int tts_hip_denoise(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                    const float* bias, double strength, float* out, int mem);
+int tts_hip_denoise_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                          const float* bias, double strength, float* out, void* stream);
+int tts_hip_denoise_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                          const float* bias, double strength, int what, float* out, int mem);
+
 /* ---- waveform clean-up (csrc/audio_proc.hip; DFT bases built on first use, no weights needed)
  * reduce_noise: utils/audio/noisereducev1.py:175-290 with the defaults utils/audio/audio_processing.py:65-83 uses.
  *   audio [B, N] -> out [B, N]; row b has lengths[b] (1 <= lengths[b] <= N) samples, lengths NULL = N for every row, and
@@ -628,7 +661,9 @@ int tts_hip_resample_fft_probe(tts_hip_engine* e, const float* in, int lines, in
  * 1 = WN residual GEMM, 2 = Tacotron2 decoder step, 3 = first WN layer of a flow (start conv composed into its taps: direct
  * form one GEMM of K = 48 + 320; Winograd form the tap operand kernel and wino_layer0_kernel, K = 16 + 140 per output).
  * A tts_hip_griffin_lim call files the four parts of its iterations under the same kinds: 0 = inverse-frames GEMM, 1 = gather
- * overlap-add, 2 = forward DFT GEMM (with its gather, where the plan has one), 3 = phase update.
+ * overlap-add, 2 = forward DFT GEMM (with its gather, where the plan has one), 3 = phase update.  A tts_hip_denoise call
+ * files its four parts there too: 2 = forward DFT (padding and gather included), 3 = gate, 0 = inverse-frames GEMM, 1 =
+ * overlap-add.
  * Timing is off unless enabled (events perturb nothing but cost a few us each).        */
 int tts_hip_kernel_timing(tts_hip_engine* e, int enable);
 /* Box probe: TFLOP/s a bare v_mfma_f32_32x32x2_f32 loop sustains on this device right now (every CU, 2 waves per SIMD, ~20 ms)

@@ -122,6 +122,10 @@ SIGNATURES = {
                                           c_int, c_double, c_void_p, c_void_p]),
     'tts_hip_griffin_lim_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                           c_int, c_double, c_int, c_int, c_void_p, c_int]),
+    'tts_hip_denoise': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int]),
+    'tts_hip_denoise_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
+    'tts_hip_denoise_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p,
+                                      c_int]),
     'tts_hip_resample_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     'tts_hip_resample_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     'tts_hip_resample_fft_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -1,4 +1,4 @@
-// audio_call.h -- what the audio front-end calls (mel-STFT, STFT inverse / Griffin-Lim, reduce_noise / trim_silence, resample, remove_silence) may be
+// audio_call.h -- what the audio front-end calls (mel-STFT, STFT inverse / Griffin-Lim, denoise, reduce_noise / trim_silence, resample, remove_silence) may be
 // refused for, and the geometry those refusals rest on: pure host code on the caller's arguments (no HIP include; also built
 // with plain g++ under ASan / UBSan by csrc/host_check.cpp, --audio-call, and compared there with a Python restatement,
 // tests/test_audio_call.py).  The .hip files forward the message to set_err; nothing is copied or launched before a check
@@ -376,6 +376,29 @@ struct MelGeom {
     size_t off_info, off_rowmax, off_padded, off_gathered, off_spectrum, off_magnitude, off_linear, total;
 };
 
+// The frame slots, the padded rows and the one workspace of a call on B rows of N samples -> the bytes of its largest buffer;
+// the widths and offsets of `g` are filled where that lies below kAudioLim
+inline long long mel_geom_layout(const MelPlan& p, int B, int N, MelGeom* g) {
+    g->Fr = mel_dft_frames(p, N);
+    g->Fout = mel_out_frames(p, N);
+    const long long PW = (long long)std::max(N, p.wl) + 2 * p.half, NP = (PW + p.K4 - p.fl + 3) / 4 * 4;
+    const long long rows = (long long)B * g->Fr;
+    const long long biggest = std::max({(long long)B * NP * 4 + 256, p.gather ? rows * p.Kpad * 4 : 0, rows * p.NB * 4,
+                                        rows * p.MAGK * 4, rows * p.nmel * 4, (long long)B * N * 4});
+    if (biggest >= kAudioLim) return biggest;
+    g->PW = (int)PW, g->NP = (int)NP;
+    Carve c;
+    g->off_info = c.take((size_t)2 * B * 4);
+    g->off_rowmax = c.take((size_t)B * 4);
+    g->off_padded = c.take((size_t)B * NP * 4 + 256);
+    g->off_gathered = c.take(p.gather ? (size_t)rows * p.Kpad * 4 : 0);
+    g->off_spectrum = c.take((size_t)rows * p.NB * 4);
+    g->off_magnitude = c.take((size_t)rows * p.MAGK * 4);
+    g->off_linear = c.take(p.kind == TTS_HIP_MEL_WHISPER ? (size_t)rows * p.nmel * 4 : 0);
+    g->total = c.o;
+    return biggest;
+}
+
 // run -- order: pointers / B / N, lengths[b], a row reflect cannot pad, a Whisper row of one frame, the 31-bit limits, mem
 // kind; fills `g`
 inline int mel_call_check(const char* who, const MelPlan* p, const float* audio, int B, int N, const int32_t* lengths,
@@ -392,24 +415,8 @@ inline int mel_call_check(const char* who, const MelPlan* p, const float* audio,
         g->fout[b] = mel_out_frames(*p, g->lens[b]);
         if (g->fout[b] < 1) return audio_refuse(msg, n, who, "row %d: L = %d samples give one frame, Whisper drops the last", b, g->lens[b]);
     }
-    g->Fr = mel_dft_frames(*p, N);
-    g->Fout = mel_out_frames(*p, N);
-    const long long PW = (long long)std::max(N, p->wl) + 2 * p->half, NP = (PW + p->K4 - p->fl + 3) / 4 * 4;
-    const long long rows = (long long)B * g->Fr;
-    const long long biggest = std::max({(long long)B * NP * 4 + 256, p->gather ? rows * p->Kpad * 4 : 0, rows * p->NB * 4,
-                                        rows * p->MAGK * 4, rows * p->nmel * 4, (long long)B * N * 4});
-    if (biggest >= kAudioLim || B > 65535)
+    if (mel_geom_layout(*p, B, N, g) >= kAudioLim || B > 65535)
         return audio_refuse(msg, n, who, "B = %d x N = %d too large for 31-bit offsets (B <= 65535)", B, N);
-    g->PW = (int)PW, g->NP = (int)NP;
-    Carve c;
-    g->off_info = c.take((size_t)2 * B * 4);
-    g->off_rowmax = c.take((size_t)B * 4);
-    g->off_padded = c.take((size_t)B * NP * 4 + 256);
-    g->off_gathered = c.take(p->gather ? (size_t)rows * p->Kpad * 4 : 0);
-    g->off_spectrum = c.take((size_t)rows * p->NB * 4);
-    g->off_magnitude = c.take((size_t)rows * p->MAGK * 4);
-    g->off_linear = c.take(p->kind == TTS_HIP_MEL_WHISPER ? (size_t)rows * p->nmel * 4 : 0);
-    g->total = c.o;
     return audio_mem_check(who, mem, msg, n);
 }
 
@@ -504,6 +511,33 @@ struct GlGeom {
         off_expmel, off_minv, total;
 };
 
+// The one workspace of a call on B rows of F frame slots (kind < 0: the inverse alone; what: the probed stage or -1) -> the
+// bytes of its largest buffer, the caller's planes [B * F][C] and audio [B][F * hop] among them; the widths and offsets of
+// `g` are filled where that lies below kAudioLim
+inline long long gl_geom_layout(const MelPlan& p, int B, int F, int C, int kind, int what, GlGeom* g) {
+    const bool gl = kind >= 0;
+    const long long PW = (long long)p.hop * (F - 1) + p.fl, NP = (PW + p.K4 - p.fl + 3) / 4 * 4;
+    const long long rows = (long long)B * F, EK = up_to(p.nmel, 32);
+    const long long biggest = std::max({(long long)B * NP * 4 + 256, rows * p.Kpad * 4, rows * p.NB * 4, rows * p.fl * 4,
+                                        rows * p.hop * 4, rows * C * 4, kind == 1 ? rows * EK * 4 : 0});
+    if (biggest >= kAudioLim) return biggest;
+    g->B = B, g->F = F, g->PW = (int)PW, g->NP = (int)NP, g->EK = (int)EK, g->Sout = (long long)F * p.hop;
+    Carve c;
+    g->off_info = c.take((size_t)B * 4);
+    g->off_target = c.take(gl ? (size_t)rows * p.cut * 4 : 0);
+    g->off_operand = c.take((size_t)rows * p.NB * 4);
+    g->off_tprev = c.take(gl ? (size_t)rows * p.NB * 4 : 0);
+    g->off_phasor = c.take(what == GL_PHASOR ? (size_t)rows * p.NB * 4 : 0);
+    g->off_tframes = c.take((size_t)rows * p.fl * 4);
+    g->off_padded = c.take(gl ? (size_t)B * NP * 4 + 256 : 0);
+    g->off_gathered = c.take(gl && p.gather ? (size_t)rows * p.Kpad * 4 : 0);
+    g->off_spectrum = c.take(gl ? (size_t)rows * p.NB * 4 : 0);
+    g->off_expmel = c.take(kind == 1 ? (size_t)rows * EK * 4 : 0);
+    g->off_minv = c.take(kind == 1 ? (size_t)p.cut * EK * 4 : 0);       // the caller's own Minv, transposed and padded
+    g->total = c.o;
+    return biggest;
+}
+
 // What tts_hip_stft_inverse (kind < 0: two planes of C = cut) and tts_hip_griffin_lim[_probe] (kind 0 / 1) may be refused
 // for -- order: pointers, B / F, frames[b], C, n_iters, momentum, a Whisper plan, pre_emph, normalisation (kind 1), a row
 // the reflect cannot pad, the 31-bit limits, mem kind, what / k (probe: what >= 0); fills `g`
@@ -534,11 +568,7 @@ inline int stft_inv_check(const char* who, const MelPlan* p, const void* in0, co
             if (stft_samples(*p, g->frames[b]) <= p->half)
                 return audio_refuse(msg, n, who, "row %d: %d frames give %lld samples, not more than filter_length // 2 = %d", b,
                                     g->frames[b], stft_samples(*p, g->frames[b]), p->half);
-    const long long PW = (long long)p->hop * (F - 1) + p->fl, NP = (PW + p->K4 - p->fl + 3) / 4 * 4;
-    const long long rows = (long long)B * F, EK = up_to(p->nmel, 32);
-    const long long biggest = std::max({(long long)B * NP * 4 + 256, rows * p->Kpad * 4, rows * p->NB * 4, rows * p->fl * 4,
-                                        rows * p->hop * 4, rows * C * 4, kind == 1 ? rows * EK * 4 : 0});
-    if (biggest >= kAudioLim || B > 65535)
+    if (gl_geom_layout(*p, B, F, C, kind, what, g) >= kAudioLim || B > 65535)
         return audio_refuse(msg, n, who, "B = %d x F = %d too large for 31-bit offsets (B <= 65535)", B, F);
     if (int rc = audio_mem_check(who, mem, msg, n)) return rc;
     if (what >= 0) {
@@ -547,19 +577,47 @@ inline int stft_inv_check(const char* who, const MelPlan* p, const void* in0, co
         if (what >= GL_SPECTRUM && k == n_iters)
             return audio_refuse(msg, n, who, "iteration k = n_iters = %d ends at its signal: no stage %d there", k, what);
     }
-    g->B = B, g->F = F, g->PW = (int)PW, g->NP = (int)NP, g->EK = (int)EK, g->Sout = (long long)F * p->hop;
-    Carve c;
-    g->off_info = c.take((size_t)B * 4);
-    g->off_target = c.take(gl ? (size_t)rows * p->cut * 4 : 0);
-    g->off_operand = c.take((size_t)rows * p->NB * 4);
-    g->off_tprev = c.take(gl ? (size_t)rows * p->NB * 4 : 0);
-    g->off_phasor = c.take(what == GL_PHASOR ? (size_t)rows * p->NB * 4 : 0);
-    g->off_tframes = c.take((size_t)rows * p->fl * 4);
-    g->off_padded = c.take(gl ? (size_t)B * NP * 4 + 256 : 0);
-    g->off_gathered = c.take(gl && p->gather ? (size_t)rows * p->Kpad * 4 : 0);
-    g->off_spectrum = c.take(gl ? (size_t)rows * p->NB * 4 : 0);
-    g->off_expmel = c.take(kind == 1 ? (size_t)rows * EK * 4 : 0);
-    g->off_minv = c.take(kind == 1 ? (size_t)p->cut * EK * 4 : 0);     // the caller's own Minv, transposed and padded
-    g->total = c.o;
+    return TTS_HIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- denoiser (stft_inv.hip)
+enum { DN_SPECTRUM = 0, DN_OPERAND, DN_FRAMES, DN_STAGES };
+
+// A denoise call is a transform and an inverse on the same frame slots: `fwd` is the transform's geometry (lens, fout = the
+// frames the plan gives each row, its workspace in e->stft.ws), `inv` the inverse's on F = fwd.Fr frame slots (frames = fout,
+// its workspace in e->stft.inv_ws); row b of the result holds keep[b] = min(lens[b], stft_samples(frames[b])) samples
+struct DnGeom {
+    MelGeom fwd;
+    GlGeom inv;
+    std::vector<int> keep;
+};
+
+// What tts_hip_denoise[_async, _probe] may be refused for -- order: pointers / B / N, lengths[b], a row reflect cannot pad,
+// a Whisper plan, bias NULL, strength not finite or negative, the 31-bit limits (of either workspace and of audio [B][N]),
+// mem kind, what (probe: what >= 0; the call itself: -1); fills `g`
+inline int denoise_check(const char* who, const MelPlan* p, const float* audio, int B, int N, const int32_t* lengths, const float* bias,
+                         double strength, const float* out, int mem, int what, DnGeom* g, char* msg, size_t n) {
+    if (!p || !audio || !out || B < 1 || N < 1) return audio_refuse(msg, n, who, "bad argument");
+    int min_len;
+    if (int rc = audio_rows_check(who, B, N, lengths, g->fwd.lens, &min_len, msg, n)) return rc;
+    for (int b = 0; b < B; ++b)
+        if (mel_dft_frames(*p, g->fwd.lens[b]) < 1)
+            return audio_refuse(msg, n, who, "row %d: max(L = %d, win_length = %d) samples are not more than filter_length // 2 = %d",
+                                b, g->fwd.lens[b], p->wl, p->half);
+    if (p->kind != TTS_HIP_MEL_TACOTRON) return audio_refuse(msg, n, who, "refused for a Whisper plan");
+    if (!bias) return audio_refuse(msg, n, who, "bias is NULL");
+    if (!(std::isfinite(strength) && strength >= 0)) return audio_refuse(msg, n, who, "strength = %g must be finite and >= 0", strength);
+    if (B > 65535 || mel_geom_layout(*p, B, N, &g->fwd) >= kAudioLim ||
+        gl_geom_layout(*p, B, g->fwd.Fr, p->cut, -1, -1, &g->inv) >= kAudioLim)
+        return audio_refuse(msg, n, who, "B = %d x N = %d too large for 31-bit offsets (B <= 65535)", B, N);
+    if (int rc = audio_mem_check(who, mem, msg, n)) return rc;
+    if (what >= DN_STAGES) return audio_refuse(msg, n, who, "no stage %d (0 .. %d)", what, DN_STAGES - 1);
+    g->fwd.fout.resize(B);
+    g->keep.resize(B);
+    for (int b = 0; b < B; ++b) {
+        g->fwd.fout[b] = mel_dft_frames(*p, g->fwd.lens[b]);
+        g->keep[b] = (int)std::min<long long>(g->fwd.lens[b], stft_samples(*p, g->fwd.fout[b]));
+    }
+    g->inv.frames = g->fwd.fout;
     return TTS_HIP_OK;
 }

@@ -39,6 +39,10 @@
 // mel_fn settings; settings F C input_kind n_iters momentum what k, the positional values are frames[b]; prints the status
 // line, then "PW NP EK Sout total", the eleven workspace offsets, the rows' sample counts, and with minv=1 whether the
 // filterbank's Cholesky inverse exists and its n_mel * cut values (tests/test_stft_inv.py).
+// denoise: the check of tts_hip_denoise[_probe] (denoise_check) on a plan of the mel_fn settings; settings N strength what and
+// null=audio,out,fn,bias, the positional values are lengths[b]; prints the status line, then "Fr PW NP off_padded off_spectrum
+// total" of the transform's workspace, "F off_operand off_tframes total" of the inverse's, the rows' frames and the samples
+// each row of the result holds (tests/test_denoise.py).
 //        ttsw_check_asan --taco-call KIND [KEY=VALUE...] [LEN...]  -- the front end of a Tacotron2 call (taco_call.h) run as an
 // entry point named "who", KIND one of encode, decode, forward, infer (= the encode check, then the decode check on the batch the
 // encoder would fill, as tts_hip_tacotron2_infer* does).  Refused, first match wins -- encode: mem kind, weights not finalized,
@@ -188,8 +192,9 @@ static int print_audio_call(int argc, char** argv) {
                                     {"sampling_rate", 22050}, {"n_mel_channels", 80}, {"filter_length", 1024},
                                     {"hop_length", 256}, {"win_length", 1024}, {"normalize_mode", 0}, {"mel_fmin", 0},
                                     {"mel_fmax", 8000}, {"pre_emph", 0}, {"lines", 1}, {"logL", 6}, {"F", 0}, {"C", 0},
-                                    {"input_kind", 0}, {"n_iters", 0}, {"momentum", 0}, {"what", -1}, {"k", 0}, {"minv", 0}};
-    bool null_cfg = false, null_fn = false;
+                                    {"input_kind", 0}, {"n_iters", 0}, {"momentum", 0}, {"what", -1}, {"k", 0}, {"minv", 0},
+                                    {"strength", 0.1}};
+    bool null_cfg = false, null_fn = false, null_bias = false;
     int window_at = -1;
     double window_value = 1;
     std::vector<int32_t> lengths;
@@ -206,6 +211,7 @@ static int print_audio_call(int argc, char** argv) {
             if (strstr(eq, "lens")) lens_out = nullptr;
             if (strstr(eq, "cfg")) null_cfg = true;
             if (strstr(eq, "fn")) null_fn = true;
+            if (strstr(eq, "bias")) null_bias = true;
         } else if (key == "window") {
             const char* colon = strchr(eq, ':');
             if (!colon) return 2;
@@ -303,6 +309,24 @@ static int print_audio_call(int argc, char** argv) {
             if (ok)
                 for (size_t i = 0; i < Minv.size(); ++i) printf("%.17g\n", Minv[i]);
         }
+    } else if (kind == "denoise") {
+        const tts_hip_mel_config cfg{(int)v["mel_kind"], (int)v["sampling_rate"], (int)v["n_mel_channels"], (int)v["filter_length"],
+                                     (int)v["hop_length"], (int)v["win_length"], (int)v["normalize_mode"], v["mel_fmin"],
+                                     v["mel_fmax"], v["pre_emph"]};
+        MelPlan p{};
+        int rc = mel_cfg_check("who", &cfg, nullptr, true, &p, why, sizeof why);
+        DnGeom g;
+        if (!rc)
+            rc = denoise_check("who", null_fn ? nullptr : &p, audio, B, N, lp, null_bias ? nullptr : audio, v["strength"], out, mem,
+                               (int)v["what"], &g, why, sizeof why);
+        printf("%d %s\n", rc, why);
+        if (rc) return 0;
+        if ((int)g.fwd.lens.size() != B || (int)g.fwd.fout.size() != B || (int)g.inv.frames.size() != B || (int)g.keep.size() != B)
+            return 2;
+        printf("%d %d %d %zu %zu %zu\n", g.fwd.Fr, g.fwd.PW, g.fwd.NP, g.fwd.off_padded, g.fwd.off_spectrum, g.fwd.total);
+        printf("%d %zu %zu %zu\n", g.inv.F, g.inv.off_operand, g.inv.off_tframes, g.inv.total);
+        for (int b = 0; b < B; ++b) printf("%d%c", g.inv.frames[b], b == B - 1 ? '\n' : ' ');
+        for (int b = 0; b < B; ++b) printf("%d%c", g.keep[b], b == B - 1 ? '\n' : ' ');
     } else {
         return 2;
     }

@@ -6,8 +6,11 @@
 // Griffin-Lim (with the "fast" momentum term): per iteration one inverse-frames GEMM, one gather overlap-add straight into
 // the reflect-padded rows the forward DFT GEMM reads, that GEMM, and one phasor update -- no atan2 / sin / cos in the loop.
 // All rows of a batch run in one launch per part, driven by frames[b]; nothing is accumulated with atomics, so a row never
-// depends on its neighbours and a repeat gives the same bits.  include/tts_hip.h has the contract, audio_call.h the checks
-// and the geometry (GlGeom), mel_stft.hip the plans and the forward DFT.
+// depends on its neighbours and a repeat gives the same bits.  The WaveGlow denoiser (tts_hip_denoise) is one pass of the
+// same parts -- the plan's forward DFT, a gate that lowers every bin's magnitude by strength x the model's bias spectrum and
+// keeps its phase, the inverse-frames GEMM, the gather overlap-add cut to each row's length -- chained without the host.
+// include/tts_hip.h has the contract, audio_call.h the checks and the geometry (GlGeom, DnGeom), mel_stft.hip the plans and
+// the forward DFT.
 //
 // The inverse basis has a closed form, so no SVD runs here: pinv(scale * [cos; -sin])^T has the rows
 // c_k cos(2 pi k n / N) / (N scale) and -c_k sin(2 pi k n / N) / (N scale), c_0 = 1, c_{N/2} = 1 (N even), else c_k = 2
@@ -24,16 +27,17 @@ using namespace ttsgemm;
 namespace {
 
 // (re, im) / |(re, im)|, (1, 0) at the origin.  Scaled by the larger component first: the squares of a tiny pair neither
-// underflow nor overflow.
-__device__ __forceinline__ void phasor(float re, float im, float& pr, float& pi) {
+// underflow nor overflow.  -> |(re, im)| from the scaled pair (the denoiser's gate; Griffin-Lim drops it)
+__device__ __forceinline__ float phasor(float re, float im, float& pr, float& pi) {
     const float m = fmaxf(fabsf(re), fabsf(im));
     if (!(m > 0.f)) {
         pr = 1.f, pi = 0.f;
-        return;
+        return 0.f;
     }
     const float a = re / m, b = im / m;
     const float n = sqrtf(a * a + b * b);
     pr = a / n, pi = b / n;
+    return m * n;
 }
 
 // transform: out0 / out1 [B][Fout][cut] from the spectrum [B * Fr][NB]; what 0 magnitude and phase, 1 real and imaginary
@@ -118,6 +122,44 @@ __global__ void ola_kernel(const float* __restrict__ T, const float* __restrict_
         if (s >= 0) v = ola_sample(T, win2, b * F, Fb, s + half, hop, fl, scale);
     }
     y[idx] = v;
+}
+
+// denoiser: the overlap-add in the caller's own layout y [B][N]: row b takes its first min(lens[b], S_b) samples, 0 beyond
+__global__ void ola_cut_kernel(const float* __restrict__ T, const float* __restrict__ win2, float* __restrict__ y, long long n, int F, int N,
+                               const int* __restrict__ frames, const int* __restrict__ lens, int hop, int fl, int half, float scale) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const long long b = idx / N;
+    const int i = (int)(idx % N), Fb = frames[b];
+    const int keep = min(lens[b], hop * (Fb - 1) + fl - 2 * half);
+    y[idx] = i < keep ? ola_sample(T, win2, b * F, Fb, i + half, hop, fl, scale) : 0.f;
+}
+
+// denoiser: the inverse GEMM's operand A [B * F][NB] from the spectrum ft [B * Fr][NB]: a bin (re, im) of magnitude m keeps
+// its phase and gets the magnitude max(m - s * bias[c], 0); the origin gives 0, as do the frames behind a row's own and the K
+// padding.  n = B * F * (NB - cut) threads: j < cut owns the pair of bin j, j >= cut clears padding column cut + j.
+__global__ void denoise_gate_kernel(const float* __restrict__ ft, const float* __restrict__ bias, float* __restrict__ A, long long n,
+                                    int Fr, int F, int cut, int NB, const int* __restrict__ frames, float s) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const int W = NB - cut, j = (int)(idx % W);
+    const long long r = idx / W, b = r / F;
+    const int f = (int)(r % F);
+    float* row = A + r * NB;
+    if (j >= cut) {
+        row[cut + j] = 0.f;
+        return;
+    }
+    float yr = 0.f, yi = 0.f;
+    if (f < frames[b]) {
+        const float* src = ft + (b * Fr + f) * NB;
+        float pr, pi;
+        const float m = phasor(src[j], src[cut + j], pr, pi);
+        const float gated = fmaxf(m - s * bias[j], 0.f);
+        yr = gated * pr, yi = gated * pi;
+    }
+    row[j] = yr;
+    row[cut + j] = yi;
 }
 
 // log-mel input: E [B * F][EK] = exp(spec [B * F][nmel]) on a row's own frames, 0 beyond and in the K padding
@@ -346,6 +388,75 @@ int gl_call(tts_hip_engine* e, const char* name, const float* spec, int B, int F
     return rc;
 }
 
+// device pointers only, the call already checked (g).  stop >= 0 (the probe): return right after that stage with *view
+// describing it.  With tts_hip_kernel_timing on, the four parts are timed under Griffin-Lim's kinds: 2 (forward DFT: pad,
+// gather where the plan has one, GEMM), 3 (gate), 0 (inverse-frames GEMM) and 1 (overlap-add)
+int dn_exec(tts_hip_engine* e, tts_hip_mel_fn& fn, const DnGeom& g, const float* d_audio, int B, int N, const float* d_bias,
+            float strength, float* d_out, int stop, StageView* view) {
+    const MelPlan& p = fn.p;
+    hipStream_t st = e->stream;
+    const int F = g.inv.F;
+    const long long rows = (long long)B * F;
+    StageView spec{};
+    timing_begin(e, 2);
+    // every row's length goes to the device (lengths NULL: N), so the last kernel can cut to it
+    if (int rc = mel_fn_exec(e, fn, g.fwd, d_audio, B, N, true, nullptr, MEL_SPECTRUM, &spec)) return rc;
+    timing_end(e);
+    if (stop == DN_SPECTRUM) return *view = spec, TTS_HIP_OK;
+    const int* d_lens = (const int*)((const char*)e->stft.ws.p + g.fwd.off_info);
+    GlBufs w;
+    if (int rc = gl_bufs(e, g.inv, &w)) return rc;
+    timing_begin(e, 3);
+    const long long n = rows * (p.NB - p.cut);
+    hipLaunchKernelGGL(denoise_gate_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, (const float*)spec.p, d_bias, w.operand, n, g.fwd.Fr, F,
+                       p.cut, p.NB, w.info, strength);
+    HIPCHK(e, hipGetLastError());
+    timing_end(e);
+    if (stop == DN_OPERAND) return *view = StageView{w.operand, (size_t)rows, (size_t)2 * p.cut, (size_t)p.NB}, TTS_HIP_OK;
+    timing_begin(e, 0);
+    if (int rc = inverse_frames(e, fn, g.inv, w)) return rc;
+    timing_end(e);
+    if (stop == DN_FRAMES) return *view = StageView{w.tframes, (size_t)rows, (size_t)p.fl, (size_t)p.fl}, TTS_HIP_OK;
+    timing_begin(e, 1);
+    const long long cells = (long long)B * N;
+    hipLaunchKernelGGL(ola_cut_kernel, dim3(blocks(cells, 256)), dim3(256), 0, st, w.tframes, fn.win2, d_out, cells, F, N, w.info, d_lens,
+                       p.hop, p.fl, p.half, (float)((double)p.fl / p.hop));
+    HIPCHK(e, hipGetLastError());
+    timing_end(e);
+    return TTS_HIP_OK;
+}
+
+// tts_hip_denoise (what = -1), its probe (what = a stage) and the _async form (stream, device pointers)
+int dn_call(tts_hip_engine* e, const char* name, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+            const float* bias, double strength, int what, float* out, int mem, bool async, void* stream) {
+    if (int rc = mel_plan_check(e, name, fn)) return rc;
+    DnGeom g;
+    char why[256];
+    if (int rc = denoise_check(name, fn ? &fn->p : nullptr, audio, B, N, lengths, bias, strength, out, mem, what, &g, why, sizeof why))
+        return set_err(e, rc, "%s", why);
+    tts_hip_mel_fn* plan = const_cast<tts_hip_mel_fn*>(fn);
+    HIPCHK(e, hipSetDevice(e->device));
+    if (int rc = inv_tables(e, plan)) return rc;
+    if (async) {
+        StreamScope scope(e, stream);
+        return dn_exec(e, *plan, g, audio, B, N, bias, (float)strength, out, -1, nullptr);
+    }
+    const size_t n_audio = (size_t)B * N * 4;
+    AudioStage io(e, mem);
+    const int in = io.in(audio, n_audio), ib = io.in(bias, (size_t)fn->p.cut * 4);
+    const int res = what >= 0 ? io.scratch(n_audio) : io.out(out, n_audio);
+    if (int rc = io.begin()) return rc;
+    StageView view{};
+    if (int rc = dn_exec(e, *plan, g, io.ptr<const float>(in), B, N, io.ptr<const float>(ib), (float)strength, io.ptr<float>(res), what,
+                         &view))
+        return rc;
+    if (what >= 0)
+        if (int rc = copy_stage_out(e, view, out, mem)) return rc;
+    const int rc = io.finish();
+    timing_collect(e);
+    return rc;
+}
+
 }  // namespace
 
 long long tts_hip_mel_fn_samples(const tts_hip_mel_fn* fn, int frames) { return fn ? stft_samples(fn->p, frames) : -1; }
@@ -432,4 +543,23 @@ int tts_hip_griffin_lim_probe(tts_hip_engine* e, const float* spec, int B, int F
     if (what < 0) return set_err(e, TTS_HIP_EINVAL, "griffin_lim_probe: no stage %d (0 .. %d)", what, GL_STAGES - 1);
     return gl_call(e, "griffin_lim_probe", spec, B, F, C, frames, fn, input_kind, Minv, init, n_iters, momentum, k, what, out, mem, false,
                    nullptr);
+}
+
+int tts_hip_denoise(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                    const float* bias, double strength, float* out, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    return dn_call(e, "denoise", audio, B, N, lengths, fn, bias, strength, -1, out, mem, false, nullptr);
+}
+
+int tts_hip_denoise_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                          const float* bias, double strength, float* out, void* stream) {
+    if (!e) return TTS_HIP_EINVAL;
+    return dn_call(e, "denoise_async", audio, B, N, lengths, fn, bias, strength, -1, out, TTS_HIP_MEM_DEVICE, true, stream);
+}
+
+int tts_hip_denoise_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
+                          const float* bias, double strength, int what, float* out, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (what < 0) return set_err(e, TTS_HIP_EINVAL, "denoise_probe: no stage %d (0 .. %d)", what, DN_STAGES - 1);
+    return dn_call(e, "denoise_probe", audio, B, N, lengths, fn, bias, strength, what, out, mem, false, nullptr);
 }

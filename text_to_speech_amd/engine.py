@@ -1127,6 +1127,49 @@ class HipEngine:
                                  lambda ins, outs: (ins[0], B, F, C, self._ptr(fr), plan.handle, self._GL_KINDS[kind], self._ptr(minv),
                                                     ins[1], int(n_iters), float(momentum), int(k), self._GL_STAGES[what], outs[0]))[0]
 
+    # ------------------------------------------------------------------ WaveGlow denoiser (csrc/stft_inv.hip)
+    _DN_STAGES = {'spectrum': 0, 'operand': 1, 'frames': 2}
+
+    def _bias(self, plan, bias, what):
+        bins = plan.geometry['filter_length'] // 2 + 1
+        if tuple(bias.shape) != (bins,):
+            raise ValueError(f'{what}: bias must be [{bins}] (one magnitude per bin of the plan), got {tuple(bias.shape)}')
+        return bins
+
+    def denoise(self, plan, audio, bias, strength=0.1, lengths=None, stream=None, out=None):
+        """Spectral subtraction of a vocoder's bias spectrum (tts_hip_denoise) under `plan` (Tacotron kind): audio [N] or
+        [B, N] -> [B, N], every bin's magnitude lowered by strength * bias[c] and clamped at 0, its phase kept, then the
+        plan's inverse.  Row b holds lengths[b] samples (default N) and gets back min(lengths[b], mel_fn_samples(plan,
+        mel_fn_frames(plan, lengths[b]))) of them, zeros beyond; nothing behind its length is read.  numpy in -> numpy out; a
+        CUDA tensor in -> a CUDA tensor out; `stream` (torch.cuda.Stream, device tensors only): tts_hip_denoise_async is
+        enqueued there and the call returns without waiting.  `out` (device tensors only): a contiguous float32 CUDA tensor
+        [B, N] that takes the result; it may be `audio` itself."""
+        B, N, lens = self._audio_rows(audio, lengths, 'denoise')
+        bins = self._bias(plan, bias, 'denoise')
+        if out is not None:
+            torch = self._torch()
+            if not (_is_torch_cuda(audio) and _is_torch_cuda(out) and out.dtype == torch.float32 and out.is_contiguous()
+                    and tuple(out.shape) == (B, N)):
+                raise ValueError(f'denoise: out must be a contiguous float32 CUDA tensor [{B}, {N}] next to a CUDA input')
+            self._check_device(out)
+        return self._rows_call('denoise', audio, B, N, [(bias, (bins,))],
+                               lambda empty: (empty((B, N), 'float32') if out is None else out,),
+                               lambda extras, outs: (self._ptr(lens), plan.handle, extras[0], float(strength), outs[0]), stream)[0]
+
+    def denoise_probe(self, plan, audio, bias, strength, what, lengths=None):
+        """Test hook (tts_hip_denoise_probe): run `denoise` on the same arguments (host arrays) up to stage `what` and return
+        it, with F = mel_fn_frames(plan, N): 'spectrum' and 'operand' [B, F, 2 bins] (real parts, then imaginary parts),
+        'frames' [B, F, filter_length]."""
+        if what not in self._DN_STAGES:
+            raise ValueError(f'what must be one of {tuple(self._DN_STAGES)}, got {what!r}')
+        B, N, lens = self._audio_rows(audio, lengths, 'denoise_probe')
+        bins = self._bias(plan, bias, 'denoise_probe')
+        F = self.mel_fn_frames(plan, N)
+        shape = (B, F, plan.geometry['filter_length']) if what == 'frames' else (B, F, 2 * bins)
+        return self._host_call('denoise_probe', audio, B, N, [(bias, (bins,))], lambda empty: (empty(shape, 'float32'),),
+                               lambda extras, outs: (self._ptr(lens), plan.handle, extras[0], float(strength),
+                                                     self._DN_STAGES[what], outs[0]))[0]
+
     # ------------------------------------------------------------------ waveform clean-up (csrc/audio_proc.hip)
     _TRIM_MODES = {'start_end': 0, 'start': 1, 'end': 2}
 

@@ -185,6 +185,7 @@ class HipRuntime(Runtime):
         # The reference retries a sentence up to `max_trial` times with fresh prenet dropout (models/tts/tacotron2.py:160-179):
         # the encoder output of the last token batch is kept so that a retry only re-runs the decoder loop.
         self._encoded = None                     # (key, EncodedBatch)
+        self._denoise_stream = None              # torch stream the vocoder and its denoiser share (waveglow_infer)
         self.encoder_reuses = 0
 
     @staticmethod
@@ -378,7 +379,7 @@ class HipRuntime(Runtime):
 
     # ------------------------------------------------------------------ WaveGlow.infer (waveglow_arch.py:244-306)
     def waveglow_infer(self, mel, z=None, sigma=1.0, deterministic=False, seed=None, precision=None, lengths=None,
-                       packed=False, streams=None, **_ignored):
+                       packed=False, streams=None, denoiser_strength=None, **_ignored):
         """`lengths` [B] (frames of each row that are real): a batch of unequal rows -- every row's audio is that of its own
         frames, zeros behind it (HipEngine.waveglow_infer); the noise is drawn in the batch layout either way.
         `packed=True` (with `lengths`): the same call computed as one packed row; noise values and the running offset are
@@ -386,7 +387,13 @@ class HipRuntime(Runtime):
         `streams=[(utterance, part), ...]` (one id per row; excludes `z` / `deterministic=True`): row b's noise comes from
         its own stream `stream_key(seed or the runtime's seed, NOISE_STREAM, utterance, part, 0)` at offset 0; the running
         offset is neither used nor advanced.  With `lengths` (packed or not) a row's audio is then the same in any batch, up
-        to fp32 re-association; a padded batch (no `lengths`) keeps hearing its padding."""
+        to fp32 re-association; a padded batch (no `lengths`) keeps hearing its padding.
+        `denoiser_strength` (None or 0: off, the call is today's): the audio stays on the device and goes through this
+        precision's `Denoiser` there -- `strength` x the vocoder's bias spectrum taken off every frame, each row with
+        lengths[b] * 256 samples as its length -- on one stream with the vocoder, before anything comes to the host; a CUDA
+        mel still gives a CUDA tensor."""
+        if denoiser_strength is not None and not float(denoiser_strength) >= 0:
+            raise ValueError(f'denoiser_strength must be >= 0 (or None), got {denoiser_strength!r}')
         if packed and lengths is None:
             raise ValueError('packed=True needs lengths (one frame count per row)')
         if not _is_torch_cuda(mel):
@@ -398,7 +405,41 @@ class HipRuntime(Runtime):
         noise, row_seeds = self._draw(NOISE_STREAM, B, T, z, deterministic, seed, streams)
         draw = ({'row_seeds': row_seeds} if row_seeds is not None else {'z': z} if noise is None
                 else {'seed': noise[0], 'offset': noise[1]})
-        return self.engine.waveglow_infer(mel, sigma=float(sigma), precision=precision or self.vocoder_precision, **draw, **ragged)
+        precision = precision or self.vocoder_precision
+        if not denoiser_strength:
+            return self.engine.waveglow_infer(mel, sigma=float(sigma), precision=precision, **draw, **ragged)
+        import torch
+        denoiser = self.denoiser(precision)
+        denoiser.bias                                   # the model's bias is taken (once) before anything is enqueued
+        # vocoder and denoiser are enqueued on one stream of the runtime's own (torch's default stream has no handle the engine
+        # could enqueue on); what the caller does next on the current stream waits for it
+        if self._denoise_stream is None:
+            self._denoise_stream = torch.cuda.Stream(self.engine.device)
+        stream, current = self._denoise_stream, torch.cuda.current_stream(self.engine.device)
+        if 'z' in draw:
+            draw['z'] = self._uploaded(draw['z'])
+        audio = self.engine.waveglow_infer(self._uploaded(mel), sigma=float(sigma), precision=precision, stream=stream, **draw, **ragged)
+        samples = None if lengths is None else np.maximum(self.engine._frame_lengths(lengths, B, T).astype(np.int64) * 256, 1)
+        audio = denoiser(audio, float(denoiser_strength), lengths=samples, stream=stream)
+        current.wait_stream(stream)
+        audio.record_stream(current)
+        return audio if _is_torch_cuda(mel) else audio.cpu().numpy()
+
+    def denoiser(self, precision=None):
+        """The `Denoiser` of this runtime's vocoder in `precision` (default: the runtime's): one per precision and engine
+        handle, kept on the engine.  Its bias comes from a call of its own with explicit zero noise: the runtime's running
+        noise offset is neither used nor advanced."""
+        from .denoiser import Denoiser
+        precision = precision or self.vocoder_precision
+        kept = self.engine.__dict__.setdefault('_denoisers', {})
+        if precision not in kept:
+            kept[precision] = Denoiser(self.engine, precision=precision)
+        return kept[precision]
+
+    def denoise(self, audio, strength=0.1, lengths=None, precision=None):
+        """`audio` [N] or [B, N] (a waveform of this runtime's vocoder, e.g. one stitched from several calls) through
+        `denoiser(precision)` -> [B, N]."""
+        return self.denoiser(precision)(audio, strength, lengths=lengths)
 
     def waveglow_encode(self, audio, mel, lengths=None, stream=None):
         """The forward flow of the vocoder, audio [B, T*256] + mel [B, T, 80] -> (z [B, T*32, 8], stats [3, B]), fp32

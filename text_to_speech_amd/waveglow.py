@@ -92,7 +92,10 @@ class WaveGlow:
       * a longer utterance is cut into overlapping windows (`hop_len` frames apart; negative = window minus that many,
         float = fraction of the window), each vocoded alone or all as one batch (`batch=True`), and stitched by dropping
         half of every overlap from each side.  This is the reference's approximation (the vocoder's receptive field is
-        longer than the half-overlap); `infer_exact` is the exact alternative."""
+        longer than the half-overlap); `infer_exact` is the exact alternative.
+    `denoiser_strength` (HipRuntime.waveglow_infer): a direct call passes it on; stitched windows and `infer_exact` vocode without
+    it and denoise the whole waveform once at the end (`HipRuntime.denoise`) -- per-window denoising would change the frames
+    at every seam."""
     rate = 22050
     pad_mel_value = -11.
     runtime = 'hip'
@@ -113,6 +116,14 @@ class WaveGlow:
             return torch.nn.functional.pad(mel, (0, 0, 0, extra), value=self.pad_mel_value)
         return np.pad(np.asarray(mel), [(0, 0), (0, extra), (0, 0)], constant_values=self.pad_mel_value)
 
+    def _denoise_whole(self, audio, strength, precision):
+        """An assembled waveform [N] or [B, N] through the runtime's denoiser, in the shape it came in."""
+        denoise = getattr(self.compiled_infer, 'denoise', None)
+        if denoise is None:
+            raise ValueError('denoiser_strength on an assembled waveform needs a runtime with denoise (HipRuntime) behind the model')
+        out = _to_numpy(denoise(audio, strength, precision=precision))
+        return out[0] if len(audio.shape) == 1 else out
+
     def infer(self, mel, *, win_len=None, hop_len=-64, force_pad=None, batch=False, use_slice=False,
               max_win_len=None, **kwargs):
         if isinstance(mel, str):
@@ -123,6 +134,9 @@ class WaveGlow:
         n_samples = n_frames * 256
         if win_len is None:
             return self.compiled_infer(mel, **kwargs)[:, :n_samples]
+        # with windows the keyword belongs to one call of a whole waveform: a direct call below, or the stitched result
+        strength = kwargs.pop('denoiser_strength', None)
+        direct = {'denoiser_strength': strength} if strength else {}
 
         win_len = self._resolve_window(n_frames, win_len, use_slice, max_win_len)
         kwargs['padding_multiple'] = win_len
@@ -130,10 +144,10 @@ class WaveGlow:
             if force_pad is None:
                 force_pad = self.runtime == 'keras'               # waveglow.py:95 -- False for this runtime
             if not force_pad:
-                return self.compiled_infer(mel)
-            return self.compiled_infer(self._pad_frames(mel, win_len), **kwargs)[:, :n_samples]
+                return self.compiled_infer(mel, **direct)
+            return self.compiled_infer(self._pad_frames(mel, win_len), **kwargs, **direct)[:, :n_samples]
         if mel.shape[0] > 1:
-            return self.compiled_infer(mel, **kwargs)
+            return self.compiled_infer(mel, **kwargs, **direct)
 
         if isinstance(hop_len, float):
             hop_len = int(win_len * hop_len)
@@ -160,7 +174,8 @@ class WaveGlow:
         # reference's output on the same arguments (pinned by tests/golden/host_vectors.json); overlapping windows -- every
         # default -- are seamless.
         ends = [len(p) - t if (i == last or t > 0) else 0 for i, (p, t) in enumerate(zip(pieces, tail))]
-        return np.concatenate([p[h:e] for p, h, e in zip(pieces, head, ends)], axis=-1)
+        stitched = np.concatenate([p[h:e] for p, h, e in zip(pieces, head, ends)], axis=-1)
+        return self._denoise_whole(stitched, strength, kwargs.get('precision')) if strength else stitched
 
     __call__ = infer
 
@@ -264,9 +279,14 @@ class WaveGlow:
 
     def infer_exact(self, mel, *, tile_frames=4096, z=None, **kwargs):
         """Long-form vocoding without the approximation of `infer(win_len=...)`: halo tiling, bit-for-bit the samples of
-        one run over the whole mel (which one C-ABI call only accepts up to ~31.7 k frames)."""
+        one run over the whole mel (which one C-ABI call only accepts up to ~31.7 k frames).  `denoiser_strength`: the tiles
+        are vocoded without it and the whole waveform is denoised once."""
         if isinstance(mel, str):
             mel = np.load(mel)
         if len(mel.shape) == 2:
             mel = mel[None]
-        return infer_tiled(self.compiled_infer, mel, z=z, tile_frames=tile_frames, **kwargs)
+        strength = kwargs.pop('denoiser_strength', None)
+        if strength and kwargs.get('tiles') is not None:
+            raise ValueError('infer_exact: denoiser_strength needs the whole waveform, not a subset of its tiles')
+        audio = infer_tiled(self.compiled_infer, mel, z=z, tile_frames=tile_frames, **kwargs)
+        return self._denoise_whole(audio, strength, kwargs.get('precision')) if strength else audio
