@@ -300,7 +300,8 @@ int tts_hip_last_conv_paths(const tts_hip_engine* e);
  * `mem`, `stream`, and when the call returns: the shared contract of the tts_hip_waveglow_infer* block.  Refused with
  * TTS_HIP_EINVAL before anything is copied or launched, the message starting with the symbol's name, first match wins: bad
  * `mem`; B <= 0; audio or mel NULL, or T <= 0; z and stats both NULL; a lengths[b] outside [0, T]; B * T above one run
- * (31 744 frames: the call is one run, slice the batch by rows).  Armed probe hooks are ignored.                         */
+ * (31 744 frames: the call is one run, slice the batch by rows).  The stop points of tts_hip_waveglow_probe belong to the
+ * inverse direction and never apply here; this direction's test hook is tts_hip_waveglow_encode_probe below.            */
 int tts_hip_waveglow_encode(tts_hip_engine* e, const float* audio, const float* mel, int B, int T, const int32_t* lengths,
                             float* z, float* stats, int mem);
 int tts_hip_waveglow_encode_async(tts_hip_engine* e, const float* audio, const float* mel, int B, int T, const int32_t* lengths,
@@ -346,6 +347,19 @@ int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int 
  * B*T <= 31744.                                                                                                            */
 int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int precision,
                            int flow, int what, int layer, float* out, int mem);
+/* Test hook of the forward direction (used by tests/ only; no state is kept on the handle, so no effect on later calls):
+ * runs tts_hip_waveglow_encode on audio / mel / lengths -- same plan, form and fall-back, same tail handling -- and stops
+ * after the position-wise kernel that ends flow `flow` (0 .. 11; -1: right after the init step audio @ kernel_0):
+ *   what 0: the flow state AS STORED, to `out` [B, T*32, n] in the reference's position order: what flow `flow` + 1 reads,
+ *           i.e. the early channels already gone and that flow's matrix already applied; n = 8 for flows -1 .. 2, 6 for
+ *           3 .. 6, 4 for 7 .. 10.  After flow 11 nothing is stored: `out` [B, T*32, 4] gets z's channels 0 .. 3;
+ *   what 1: the running sum over flows 0 .. `flow` and coupling channels of s, per position, to `out` [B, T*32].
+ * With lengths, `out` is exactly 0 behind a row's length.  tts_hip_last_waveglow_form / _tiles report what ran.  Refused with
+ * TTS_HIP_EINVAL before anything is copied or launched, the message starting with the symbol's name: whatever
+ * tts_hip_waveglow_encode refuses (its two outputs aside), then flow outside [-1, 11], what outside [0, 1], what 1 with
+ * flow -1, out NULL.                                                                                                    */
+int tts_hip_waveglow_encode_probe(tts_hip_engine* e, const float* audio, const float* mel, int B, int T, const int32_t* lengths,
+                                  int flow, int what, float* out, int mem);
 /* WN GEMM tile family the last tts_hip_waveglow_infer* (or probe) call on this handle used for its in-layer (direct form) and
  * residual GEMMs: 3 64-row tiles (64 x 128), 2 128 x 64 tiles, 1 128-row tiles, 0 256-row tiles (fp16: 256 x 256), -1 before
  * the first call.  Split fp16 (f16x3) has two families only: 3 and 0.                                                    */

@@ -74,6 +74,7 @@ SIGNATURES = {
                                                     c_void_p]),
     'tts_hip_waveglow_encode': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int]),
     'tts_hip_waveglow_encode_async': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'tts_hip_waveglow_encode_probe': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int]),
     'tts_hip_waveglow_infer_packed': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int]),
     'tts_hip_waveglow_infer_packed_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int,
                                                     c_void_p]),

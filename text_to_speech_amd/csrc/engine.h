@@ -313,9 +313,10 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
 int waveglow_run_packed(tts_hip_engine* e, const float* d_mel, int B, int T, const float* d_z, float sigma, float* d_audio,
                         int precision, const int* d_info, int F, int n_gap);
 // forward flow, audio -> z and its statistics (fp32; one run: B * T <= kMaxFramesPerRun).  d_z [B, T*32, 8] and d_stats
-// [3, B] are device buffers, both written; d_lens / d_tail / n_tail as for waveglow_run
+// [3, B] are device buffers, both written; d_lens / d_tail / n_tail as for waveglow_run.  probe (test hook, wg_call.h): the
+// same run stops after that flow, copies what the probe asks for to its device buffer `out` and leaves d_stats unwritten
 int waveglow_encode_run(tts_hip_engine* e, const float* d_audio, const float* d_mel, int B, int T, const int* d_lens,
-                        const int* d_tail, int n_tail, float* d_z, float* d_stats);
+                        const int* d_tail, int n_tail, float* d_z, float* d_stats, const WgEncodeProbe* probe = nullptr);
 // its position-wise kernels (wg_encode.hip); mask: 0 every frame is real, 1 the first d_lens[b] of each row
 int wg_encode_init(tts_hip_engine* e, const float* d_audio, const float* fwd0, float* state, int PR, int BT, const int* d_lens, int T);
 struct WgEncodeEnd {

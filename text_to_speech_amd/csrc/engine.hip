@@ -464,11 +464,14 @@ static WgCall wg_call(const char* who, const float* mel, int B, int T, const int
 }
 
 // Both tts_hip_waveglow_encode entry points: check, then the lengths table, staging and the one run, on one stream.
-static int waveglow_encode_call(tts_hip_engine* e, const WgEncode& c) {
+// probe (tts_hip_waveglow_encode_probe): the same staging and the same run, stopped where the probe says; c.z and c.stats
+// are NULL (the run's z goes to the handle's own buffer) and probe->out [n_probe floats] lives where c.mem says.
+static int waveglow_encode_call(tts_hip_engine* e, const WgEncode& c, const WgEncodeProbe* probe = nullptr, size_t n_probe = 0) {
     if (!e) return TTS_HIP_EINVAL;
     if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
     char why[512];
-    if (int rc = wg_encode_check(c, why, sizeof why)) return set_err(e, rc, "%s", why);
+    if (int rc = probe ? wg_encode_probe_check(c, *probe, why, sizeof why) : wg_encode_check(c, why, sizeof why))
+        return set_err(e, rc, "%s", why);
     HIPCHK(e, hipSetDevice(e->device));
     StreamScope scope(e, c.async ? c.stream : nullptr);
     WaveGlowDev& wg = e->wg;
@@ -498,8 +501,28 @@ static int waveglow_encode_call(tts_hip_engine* e, const WgEncode& c) {
         if (!d_z) d_z = wg.enc_z.f();
         if (!d_stats) d_stats = wg.enc_z.f() + n_audio;
     }
+    struct Scratch : DevBuf {                                    // (DevBuf has no destructor: the engine's buffers live with the handle)
+        ~Scratch() { release(); }
+    } tmp;
+    WgEncodeProbe dev_probe{};
+    if (probe) {
+        dev_probe = *probe;
+        if (host) {
+            HIPCHK(e, tmp.ensure(n_probe * 4));
+            dev_probe.out = tmp.f();
+        }
+    }
     int rc = waveglow_encode_run(e, d_audio, d_mel, B, T, d_lens, d_lens ? d_lens + B : nullptr, c.lengths ? tab.run_tails[0] : 0,
-                                 d_z, d_stats);
+                                 d_z, d_stats, probe ? &dev_probe : nullptr);
+    if (probe) {                                                 // always drained: the scratch buffer goes with this frame
+        hipError_t herr = hipSuccess;
+        if (!rc && host) herr = hipMemcpyAsync(probe->out, tmp.p, n_probe * 4, hipMemcpyDeviceToHost, e->stream);
+        const hipError_t serr = hipStreamSynchronize(e->stream);
+        if (rc) return rc;
+        HIPCHK(e, herr);
+        HIPCHK(e, serr);
+        return TTS_HIP_OK;
+    }
     if (rc || c.async) return rc;
     if (host && c.z) HIPCHK(e, hipMemcpyAsync(c.z, d_z, n_audio * 4, hipMemcpyDeviceToHost, e->stream));
     if (host && c.stats) HIPCHK(e, hipMemcpyAsync(c.stats, d_stats, 3 * (size_t)B * 4, hipMemcpyDeviceToHost, e->stream));
@@ -517,6 +540,15 @@ int tts_hip_waveglow_encode_async(tts_hip_engine* e, const float* audio, const f
                                   float* z, float* stats, void* stream) {
     const WgEncode c{"tts_hip_waveglow_encode_async", audio, mel, B, T, lengths, z, stats, true, TTS_HIP_MEM_DEVICE, stream};
     return waveglow_encode_call(e, c);
+}
+
+// Test hook: the forward flow stopped after the init step or one flow; the stored flow state or the running sums of s.
+int tts_hip_waveglow_encode_probe(tts_hip_engine* e, const float* audio, const float* mel, int B, int T, const int32_t* lengths,
+                                  int flow, int what, float* out, int mem) {
+    const WgEncode c{"tts_hip_waveglow_encode_probe", audio, mel, B, T, lengths, nullptr, nullptr, false, mem, nullptr};
+    const WgEncodeProbe probe{flow, what, out};
+    const int n = what == 1 ? 1 : flow <= 2 ? 8 : flow <= 6 ? 6 : 4;         // (after flow 11: z's channels 0 .. 3)
+    return waveglow_encode_call(e, c, &probe, (size_t)(B > 0 && T > 0 ? (long long)B * T * 32 * n : 0));
 }
 
 int tts_hip_waveglow_infer(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma,

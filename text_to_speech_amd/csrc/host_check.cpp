@@ -20,7 +20,8 @@
 //        ttsw_check_asan --wg-encode T [KEY=VALUE...] [LEN...]  -- the front end of a forward-flow call (wg_encode_check of
 // wg_call.h) for a batch of B = number of LEN rows (no LEN: lengths NULL, B from B=) run as an entry point named "who".
 // Settings: B= mem= async=1 and null=audio,mel,z,stats.  One line "<status> <message>" (tests/test_waveglow_encode.py compares
-// it with a Python restatement of the refusal order).
+// it with a Python restatement of the refusal order).  flow= or what= (default 0): the test hook's front end instead
+// (wg_encode_probe_check; null=out for its output; tests/test_waveglow_encode_flows.py).
 //        ttsw_check_asan --audio-call KIND [KEY=VALUE...] [LEN...]  -- the front end of an audio call (audio_call.h), KIND one
 // of reduce_noise, trim, resample, silence, for a batch of B = number of LEN rows of N samples (no LEN: lengths NULL, B from
 // B=) run as an entry point named "who".  Settings: B= N= mem= (default 1, device), null=audio,out,lens (out: every output
@@ -150,8 +151,10 @@ static int print_wg_call(int argc, char** argv) {
 }
 
 static int print_wg_encode(int argc, char** argv) {
-    static float audio, mel, z, stats;                                         // never read: the front end only tests pointers
+    static float audio, mel, z, stats, out;                                    // never read: the front end only tests pointers
     WgEncode c{"who", &audio, &mel, -1, atoi(argv[2]), nullptr, &z, &stats, false, 0, nullptr};
+    WgEncodeProbe probe{0, 0, &out};
+    bool probing = false;
     std::vector<int32_t> lens;
     for (int i = 3; i < argc; ++i) {
         const char* eq = strchr(argv[i], '=');
@@ -164,7 +167,10 @@ static int print_wg_encode(int argc, char** argv) {
         if (key == "B") c.B = v;
         else if (key == "mem") c.mem = v;
         else if (key == "async") c.async = v != 0;
+        else if (key == "flow") probe.flow = v, probing = true;
+        else if (key == "what") probe.what = v, probing = true;
         else if (key == "null") {
+            if (strstr(eq, "out")) probe.out = nullptr;
             if (strstr(eq, "audio")) c.audio = nullptr;
             if (strstr(eq, "mel")) c.mel = nullptr;
             if (strstr(eq, "z")) c.z = nullptr;
@@ -173,7 +179,7 @@ static int print_wg_encode(int argc, char** argv) {
     }
     if (!lens.empty()) c.lengths = lens.data(), c.B = (int)lens.size();
     char why[512] = "";
-    const int rc = wg_encode_check(c, why, sizeof why);
+    const int rc = probing ? wg_encode_probe_check(c, probe, why, sizeof why) : wg_encode_check(c, why, sizeof why);
     printf("%d %s\n", rc, why);
     return 0;
 }

@@ -199,12 +199,14 @@ __global__ void probe_acts16_kernel(const _Float16* __restrict__ acts, const _Fl
     for (int j = 0; j < 4; ++j) v[j] = (float)acts[src + j] + (lo ? (float)lo[src + j] : 0.f);
     *reinterpret_cast<f32x4*>(out + pos * C + c) = v;
 }
-// test hook: the flow state after one flow ([M'][8] phase-major, or [BT * 32][8] natural after flow 0) -> [B][T * 32][n]
-__global__ void probe_state_kernel(const float* __restrict__ audio, int natural, float* __restrict__ out, int n, int PR, int BT) {
+// test hook: the flow state after one flow ([M'][8] phase-major, or [BT * 32][8] natural after flow 0) -> [B][T * 32][n];
+// pitch: floats between two rows of the source (8: the flow state and z; 1: the forward direction's per-position sums)
+__global__ void probe_state_kernel(const float* __restrict__ audio, int natural, float* __restrict__ out, int n, int PR, int BT,
+                                   int pitch) {
     const long long pos = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (pos >= (long long)BT * NPH) return;
     const long long row = natural ? pos : (pos % NPH) * PR + pos / NPH;
-    for (int j = 0; j < n; ++j) out[pos * n + j] = audio[row * 8 + j];
+    for (int j = 0; j < n; ++j) out[pos * n + j] = audio[row * pitch + j];
 }
 
 // Ragged calls (tts_hip_waveglow_infer_ragged): row b = f / T holds lens[b] real frames; frame f is real when f % T < lens[b]
@@ -1226,10 +1228,10 @@ int probe_layer(tts_hip_engine* e, const WnCall& c, int i, bool wino_layer) {
     return TTS_HIP_OK;
 }
 bool probe_wants_state(const WaveGlowDev& wg, int k) { return wg.probe_out && wg.probe_what == 1 && wg.probe_flow == k; }
-int probe_state(tts_hip_engine* e, const WgPlan& p, const float* state, int natural, int n) {
+int probe_state(tts_hip_engine* e, const WgPlan& p, const float* state, int natural, int n, float* out, int pitch = 8) {
     const long long np = (long long)p.BT * NPH;
-    hipLaunchKernelGGL(probe_state_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, e->stream, state, natural,
-                       e->wg.probe_out, n, p.PR, p.BT);
+    hipLaunchKernelGGL(probe_state_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, e->stream, state, natural, out, n,
+                       p.PR, p.BT, pitch);
     HIPCHK(e, hipGetLastError());
     return TTS_HIP_OK;
 }
@@ -1432,7 +1434,7 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
         }
         HIPCHK(e, hipGetLastError());
         if (probe_wants_state(wg, k))                            // test hook: the state after this flow
-            return probe_state(e, plan, dst, k == 0 ? 1 : 0, 2 * h + (early ? 2 : 0));
+            return probe_state(e, plan, dst, k == 0 ? 1 : 0, 2 * h + (early ? 2 : 0), wg.probe_out);
         if (early) zoff += 2;
     }
     return TTS_HIP_OK;
@@ -1442,9 +1444,15 @@ int waveglow_run(tts_hip_engine* e, const float* d_mel, int B, int T, const floa
 // lens[b] * 32 * sum_k log|det kernel_k|) over each row's real positions.  Same plan, workspace, form and tail handling as
 // waveglow_run, flows ascending; the position-wise kernels are wg_encode.hip's.  The end partial sums of the 512-channel fp32
 // path are not used in this direction (call.endp stays null: the residual GEMMs run plain and wn_end_fwd_kernel reads the
-// eight layers' activations), and armed probe hooks are ignored.
+// eight layers' activations), and the inverse direction's armed probe hooks are ignored.
+// probe (tts_hip_waveglow_encode_probe, a test hook): nothing before the stop differs from the plain call; after
+// wn_end_fwd_kernel of flow probe->flow (-1: after encode_init_kernel) the run copies to probe->out, natural position order,
+//   what 0: the stored flow state [B, T*32, n] -- what the next flow reads, that flow's matrix already applied, n = its
+//           channel count; after flow 11 nothing is stored, and the copy is z's channels 0 .. 3;
+//   what 1: slog [B, T*32], the per-position sum of s through that flow
+// and returns; d_stats is not written.
 int waveglow_encode_run(tts_hip_engine* e, const float* d_audio, const float* d_mel, int B, int T, const int* d_lens,
-                        const int* d_tail, int n_tail, float* d_z, float* d_stats) {
+                        const int* d_tail, int n_tail, float* d_z, float* d_stats, const WgEncodeProbe* probe) {
     WaveGlowDev& wg = e->wg;
     const int C = wg.channels;
     WgPlan plan = wg_plan(B * T, 0, wg.form_mode);
@@ -1469,6 +1477,7 @@ int waveglow_encode_run(tts_hip_engine* e, const float* d_audio, const float* d_
     WnCall call = wn_call(wg, plan, 0, T, d_mel);
     call.endp = nullptr;
     if (int rc = wg_encode_init(e, d_audio, wg.flow[0].fwd, wg.audio.f(), PR, BT, d_lens, T)) return rc;
+    if (probe && probe->flow < 0) return probe_state(e, plan, wg.audio.f(), 0, 8, probe->out);
     double log_det_sum = 0.0;
     for (int k = 0; k < 12; ++k) {
         const WgFlowDev& fl = wg.flow[k];
@@ -1482,6 +1491,11 @@ int waveglow_encode_run(tts_hip_engine* e, const float* d_audio, const float* d_
         a.z = d_z, a.zoff = k + 1 == 4 ? 6 : 4, a.n_early = early ? 2 : 0;
         a.M = M, a.h = fl.n_half, a.PR = PR, a.BT = BT, a.d_lens = d_lens, a.T = T;
         if (int rc = wg_encode_end(e, a)) return rc;
+        if (probe && probe->flow == k) {                         // test hook: stop here
+            if (probe->what == 1) return probe_state(e, plan, slog, 0, 1, probe->out, 1);
+            if (k == 11) return probe_state(e, plan, d_z, 1, 4, probe->out);
+            return probe_state(e, plan, wg.audio.f(), 0, 2 * fl.n_half - a.n_early, probe->out);
+        }
     }
     return wg_encode_stats(e, d_z, slog, (double*)((char*)wg.enc_ws.p + part_at), d_lens, B, T, PR, log_det_sum, d_stats);
 }

@@ -116,12 +116,13 @@ struct WgEncode {
 // Every reason a forward-flow call is refused for what it asks, first match wins, in this order: mem kind, B, audio / mel / T,
 // both outputs NULL, lengths[b], then B * T above one run (the call is one run: no slicing).  Reads host memory only
 // (lengths); nothing is copied or launched before it has passed.
-inline int wg_encode_check(const WgEncode& c, char* msg, size_t n) {
+// (outputs = false: the probe below, which has its own one output, skips the check of z / stats.)
+inline int wg_encode_check(const WgEncode& c, char* msg, size_t n, bool outputs = true) {
     if (!c.async && c.mem != TTS_HIP_MEM_HOST && c.mem != TTS_HIP_MEM_DEVICE)
         return wg_refuse(msg, n, c.who, "bad mem kind %d", c.mem);
     if (c.B <= 0) return wg_refuse(msg, n, c.who, "bad argument: B = %d must be positive", c.B);
     if (!c.audio || !c.mel || c.T <= 0) return wg_refuse(msg, n, c.who, "bad argument (audio or mel is NULL, or T = %d <= 0)", c.T);
-    if (!c.z && !c.stats) return wg_refuse(msg, n, c.who, "bad argument: z and stats are both NULL, nothing to compute");
+    if (outputs && !c.z && !c.stats) return wg_refuse(msg, n, c.who, "bad argument: z and stats are both NULL, nothing to compute");
     if (c.lengths)
         for (int b = 0; b < c.B; ++b)
             if (c.lengths[b] < 0 || c.lengths[b] > c.T)
@@ -129,6 +130,23 @@ inline int wg_encode_check(const WgEncode& c, char* msg, size_t n) {
     if ((long long)c.B * c.T > kMaxFramesPerRun)
         return wg_refuse(msg, n, c.who, "B * T = %lld frames exceeds one run's limit (%d); encode the batch in slices of rows",
                          (long long)c.B * c.T, kMaxFramesPerRun);
+    return TTS_HIP_OK;
+}
+
+// Where the forward direction's test hook (tts_hip_waveglow_encode_probe) stops and what it copies: after flow `flow`
+// (-1: after the init step) the flow state as stored (what 0) or the running per-position sum of s (what 1), to `out`.
+struct WgEncodeProbe {
+    int flow, what;
+    float* out;
+};
+// Refused: whatever wg_encode_check refuses of the same audio / mel / B / T / lengths / mem (c.z and c.stats are not looked
+// at), then flow outside -1 .. 11, what outside 0 .. 1, what 1 with flow -1 (no s has been summed yet), out NULL.
+inline int wg_encode_probe_check(const WgEncode& c, const WgEncodeProbe& p, char* msg, size_t n) {
+    if (int rc = wg_encode_check(c, msg, n, false)) return rc;
+    if (p.flow < -1 || p.flow > 11) return wg_refuse(msg, n, c.who, "flow = %d is outside [-1, 11]", p.flow);
+    if (p.what < 0 || p.what > 1) return wg_refuse(msg, n, c.who, "what = %d must be 0 (state) or 1 (slog)", p.what);
+    if (p.what == 1 && p.flow < 0) return wg_refuse(msg, n, c.who, "what = 1 (slog) needs flow >= 0: no s is summed before flow 0");
+    if (!p.out) return wg_refuse(msg, n, c.who, "bad argument: out is NULL");
     return TTS_HIP_OK;
 }
 

@@ -427,6 +427,30 @@ class HipEngine:
             mem if stream is None else sp), name)
         return z, stats
 
+    def waveglow_encode_probe(self, audio, mel, lengths=None, flow: int = 11, what: str = 'state'):
+        """Test hook (tts_hip_waveglow_encode_probe): run `waveglow_encode` on host arrays up to the end of flow `flow` (0 .. 11;
+        -1: the init step audio @ kernel_0 only) and return either the flow state as stored (what='state': [B, T*32, n], what
+        flow `flow` + 1 reads -- early channels gone, its matrix applied; n = 8, 6, 4 for flows -1 .. 2, 3 .. 6, 7 .. 10; after
+        flow 11 z's channels 0 .. 3) or the per-position sum of s through that flow (what='slog': [B, T*32])."""
+        whats = {'state': 0, 'slog': 1}
+        if what not in whats:
+            raise ValueError(f'what must be one of {tuple(whats)}')
+        mel = np.ascontiguousarray(mel, dtype=np.float32)
+        audio = np.ascontiguousarray(audio, dtype=np.float32)
+        if mel.ndim != 3 or mel.shape[2] != 80:
+            raise ValueError(f'mel must be [B, T, 80], got {mel.shape}')
+        B, T = mel.shape[:2]
+        if audio.shape != (B, T * 256):
+            raise ValueError(f'audio must be [B, T*256] = {(B, T * 256)}, got {audio.shape}')
+        lens = None if lengths is None else self._frame_lengths(lengths, B, T)
+        flow = int(flow)
+        shape = (B, T * 32) if what == 'slog' else (B, T * 32, 8 if flow <= 2 else 6 if flow <= 6 else 4)
+        out = np.empty(shape, dtype=np.float32)
+        self._check(self._lib.tts_hip_waveglow_encode_probe(
+            self._h, self._ptr(audio), self._ptr(mel), B, T, self._ptr(lens), flow, whats[what], self._ptr(out), MEM_HOST),
+            'waveglow_encode_probe')
+        return out
+
     _WG_PRECISIONS = {'f32': 0, 'f16': 1, 'f16x3': 2}
     # (noise, rows) -> entry point, without the tts_hip_ prefix and the _async suffix of a call on a caller's stream
     _WG_ENTRY = {('z', 'plain'): 'waveglow_infer', ('z', 'ragged'): 'waveglow_infer_ragged', ('z', 'packed'): 'waveglow_infer_packed',
