@@ -640,6 +640,20 @@ int tts_hip_remove_silence(tts_hip_engine* e, const float* audio, int B, int N, 
 int tts_hip_remove_silence_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int method,
                                  int mode, int rate, double threshold, double min_silence, int block_size, int replace_by,
                                  double min_voice_time, float* out, int32_t* out_lengths, void* stream);
+/* Test hook (no effect on later calls; used by tests/): runs the code of tts_hip_remove_silence, not a copy, on the same
+ * arguments (and refuses the same ones) up to stage `what`, and copies that stage's rows to `out` (follows `mem`), `*width`
+ * elements per row.  `*width` (host memory in every mode) is set by every accepted call; out NULL asks for it alone and
+ * launches nothing.  With NB = ceil(N / block_size) block flags, cap silences and NT = ceil(N / 2048) tiles per row --
+ *   what 0 flags uint8 [B, NB] (rms): 1 = silent block; row b holds ceil(lengths[b] / block_size) of them;
+ *   1 intervals int32 [B, 2 + 2 * cap] (rms, threshold): n, cut, d0[cap], d1[cap] -- the mask keeps t < cut outside every
+ *     [d0[m], d1[m]), m < n (sorted by d0; d1 <= d0: empty); entries at and beyond n are unspecified;
+ *   2 mask uint8 [B, N]: 1 = kept (unspecified at and beyond lengths[b]);
+ *   3 tile_offsets int32 [B, NT]: kept samples before each tile of 2048, for the row's ceil(lengths[b] / 2048) tiles;
+ *   4 prefix fp64 [B, N + 1] (mean-window): P[t] = sum of the fp32 squares x[0 .. t), t <= lengths[b].
+ * A `what` out of range or a stage the method does not have is TTS_HIP_EINVAL and launches nothing.                      */
+int tts_hip_remove_silence_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int method, int mode,
+                                 int rate, double threshold, double min_silence, int block_size, int replace_by,
+                                 double min_voice_time, int what, void* out, int32_t* width, int mem);
 
 /* ---- resampling (csrc/resample.hip; no weights needed)
  * scipy.signal.resample(x, int(n / rate * target_rate)) per row (utils/audio/audio_processing.py:30-35), window=None, in

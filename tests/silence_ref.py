@@ -32,16 +32,35 @@ def rms_block_peaks(x, bs):
     return np.sqrt(sq.reshape(nb, bs).max(axis=1))
 
 
+def rms_flags(x, rate, threshold=-25, block_size=0.01, **_):
+    """1 for every silent block of a row (the last block is zero-padded), uint8."""
+    return (rms_block_peaks(x, _samples(block_size, rate)) < np.float32(10 ** (threshold / 20.0))).astype(np.uint8)
+
+
+def rms_listed(x, rate, threshold=-25, min_silence=0.1, block_size=0.01, **_):
+    """The silent runs [i, j) in blocks that last min_silence, in order: the silences before any merging."""
+    bt = _samples(block_size, rate) / rate
+    silent = rms_flags(x, rate, threshold, block_size)
+    edge = np.diff(np.concatenate([[0], silent.astype(np.int8), [0]]))
+    first, end = np.flatnonzero(edge == 1), np.flatnonzero(edge == -1)         # runs [i, j)
+    assert end.size == 0 or end[-1] <= len(silent)
+    return [(int(i), int(j)) for i, j in zip(first, end) if int(j - i) * bt >= min_silence]
+
+
+def rms_links(listed, L, rate, block_size=0.01, min_voice_time=0.2, **_):
+    """link[k]: listed silence k + 1 starts less than min_voice_time after silence k ends (Python doubles)."""
+    bt = _samples(block_size, rate) / rate
+    sil = [(i * bt, min(L / rate, j * bt)) for i, j in listed]
+    if not min_voice_time:
+        return [False] * max(0, len(sil) - 1)
+    return [sil[k + 1][0] - sil[k][1] < min_voice_time for k in range(len(sil) - 1)]
+
+
 def rms_silences(x, rate, threshold=-25, min_silence=0.1, block_size=0.01, min_voice_time=0.2):
     """The merged silences of a row as (s, e) in seconds (doubles)."""
     L, bs = len(x), _samples(block_size, rate)
     bt = bs / rate
-    silent = rms_block_peaks(x, bs) < np.float32(10 ** (threshold / 20.0))
-    nb = len(silent)
-    edge = np.diff(np.concatenate([[0], silent.astype(np.int8), [0]]))
-    first, end = np.flatnonzero(edge == 1), np.flatnonzero(edge == -1)         # runs [i, j)
-    sil = [(int(i) * bt, min(L / rate, int(j) * bt)) for i, j in zip(first, end) if int(j - i) * bt >= min_silence]
-    assert end.size == 0 or end[-1] <= nb
+    sil = [(i * bt, min(L / rate, j * bt)) for i, j in rms_listed(x, rate, threshold, min_silence, block_size)]
     if min_voice_time and len(sil) > 1:
         link = [sil[k + 1][0] - sil[k][1] < min_voice_time for k in range(len(sil) - 1)]
         merged, k = [], 0
@@ -53,6 +72,45 @@ def rms_silences(x, rate, threshold=-25, min_silence=0.1, block_size=0.01, min_v
             k = t + 1
         sil = merged
     return sil
+
+
+def rms_intervals(x, rate, mode='start_end', threshold=-25, min_silence=0.1, block_size=0.01, replace_by=0.5,
+                  min_voice_time=0.2):
+    """(dropped sample intervals [(d0, d1)] sorted by d0, tail cut): a row keeps t < cut outside every [d0, d1).  Mode
+    remove: one interval per merged silence ((S, S), empty, for the trailing one, which moves the cut, and for one that
+    replace_by covers); the slice modes: the one interval [0, a) and the cut b of the slice [a, b)."""
+    x = np.asarray(x, np.float32)
+    L, rb = len(x), _samples(replace_by, rate)
+    sil = rms_silences(x, rate, threshold, min_silence, block_size, min_voice_time)
+    if mode == 'remove':
+        h, cut, iv = rb // 2, L, []
+        for s, e in sil:
+            S, E = int(s * rate), int(e * rate)
+            if S == 0:
+                iv.append((0, max(0, E - rb)))
+            elif abs(E - L) <= 1:
+                cut = min(cut, L, S + rb)
+                iv.append((S, S))
+            elif S + h < E - h:
+                iv.append((S + h, E - h))
+            else:
+                iv.append((S, S))
+        return iv, cut
+    assert mode in ('start', 'end', 'start_end')
+    a, b = 0, L
+    if sil:
+        if 'end' in mode and abs(sil[-1][1] * rate - L) <= 1:
+            b = min(L, int(sil[-1][0] * rate) + rb)
+        if 'start' in mode and sil[0][0] == 0:
+            a = max(0, int(sil[0][1] * rate) - rb)
+    return [(0, a)], b
+
+
+def interval_mask(L, intervals, cut):
+    keep = np.arange(L) < cut
+    for d0, d1 in intervals:
+        keep[d0:max(d0, d1)] = False
+    return keep.astype(np.uint8)
 
 
 def trim_rms(x, rate, mode='start_end', threshold=-25, min_silence=0.1, block_size=0.01, replace_by=0.5,
@@ -102,6 +160,15 @@ def trim_threshold(x, threshold=0.1, mode='start_end', **_):
     return x[a:b] if a < b else x[:0]
 
 
+def threshold_intervals(x, threshold=0.1, mode='start_end', **_):
+    """The slice [a, b) of trim_threshold as ([(0, a)], b)."""
+    x = np.asarray(x, np.float32)
+    idx = np.flatnonzero(np.abs(x - np.float32(np.mean(x))) > np.float32(threshold))
+    if idx.size == 0:
+        return [(0, 0)], len(x)
+    return [(0, int(idx[0]) if 'start' in mode else 0)], int(idx[-1]) if 'end' in mode else len(x)
+
+
 def threshold_margin(x, threshold=0.1, **_):
     x = np.asarray(x, np.float32)
     d = np.abs(x.astype(np.float64) - float(np.float32(np.mean(x))))
@@ -132,6 +199,36 @@ def mean_window_margin(x, rate, threshold=0.025, min_silence=0.15, **_):
     conv = mean_window_conv(x, rate, threshold, min_silence)
     th = min(threshold, np.mean(conv) / 2)
     return float(np.abs(conv / th - 1).min())
+
+
+def square_prefix(x):
+    """P[t] = sum of the fp32 squares x[0 .. t) for t in [0, L], accumulated in np.longdouble."""
+    x = np.asarray(x, np.float32)
+    return np.concatenate([[np.longdouble(0)], np.cumsum((x * x).astype(np.longdouble))])
+
+
+def mean_window_long(x, rate, threshold=0.025, min_silence=0.15, **_):
+    """(keep mask, margin) of the mean-window method with every sum in np.longdouble: what decides a row so long that the
+    order of an fp64 summation shows in the last digits of its prefix sums."""
+    L, w = len(x), int(min_silence * rate)
+    p = square_prefix(x)
+    i = np.arange(L)
+    hi = np.minimum(L - 1, i + (w - 1) // 2)
+    lo = np.maximum(0, i + (w - 1) // 2 - (w - 1))
+    conv = (p[hi + 1] - p[lo]) * np.longdouble(1.0 / (w * threshold))
+    th = min(np.longdouble(threshold), np.mean(conv) / 2)
+    return (conv > th).astype(np.uint8), float(np.abs(conv / th - 1).min())
+
+
+def keep_mask(method, x, rate, **kw):
+    """uint8 [L]: 1 for the samples `run` keeps."""
+    x = np.asarray(x, np.float32)
+    if method == 'rms':
+        return interval_mask(len(x), *rms_intervals(x, rate, **kw))
+    if method == 'threshold':
+        return interval_mask(len(x), *threshold_intervals(x, **kw))
+    conv = mean_window_conv(x, rate, **kw)
+    return (conv > min(kw.get('threshold', 0.025), np.mean(conv) / 2)).astype(np.uint8)
 
 
 METHODS = {'rms': trim_rms, 'threshold': trim_threshold, 'remove': trim_mean_window}

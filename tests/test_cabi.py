@@ -29,7 +29,7 @@ def test_header_and_binding_agree(lib):
     declared = _declared()
     assert len(declared) >= 14
     for name in ('tts_hip_mel_stft', 'tts_hip_mel_stft_async', 'tts_hip_mel_stft_probe', 'tts_hip_reduce_noise_probe',
-                 'tts_hip_trim_silence_probe'):
+                 'tts_hip_trim_silence_probe', 'tts_hip_remove_silence_probe'):
         assert name in declared, name
     assert declared == sorted(_lib.SIGNATURES), 'ctypes SIGNATURES must list exactly the header\'s functions'
 

@@ -107,6 +107,8 @@ SIGNATURES = {
                                        c_int, c_int, c_double, c_void_p, c_void_p, c_int]),
     'tts_hip_remove_silence_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double,
                                              c_double, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    'tts_hip_remove_silence_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_double,
+                                             c_double, c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_int]),
     'tts_hip_resample': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     'tts_hip_mel_fn_create': (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     'tts_hip_mel_fn_free': (c_int, [c_void_p, c_void_p]),

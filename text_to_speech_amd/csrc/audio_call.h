@@ -299,6 +299,42 @@ inline int sil_check(const char* who, const float* audio, int B, int N, const in
     return TTS_HIP_OK;
 }
 
+// The stages sil_run can stop at (tts_hip_remove_silence_probe): a row of the stage holds `width` elements of `elem` bytes
+enum { SIL_FLAGS = 0, SIL_INTERVALS, SIL_MASK, SIL_TILE_OFFSETS, SIL_PREFIX, SIL_STAGES };
+
+struct SilStage {
+    int width, elem;
+};
+
+// order: width, sil_check's own but for the overlap (`out` NULL asks for the width alone and is no refusal), `what` out of
+// range, a stage the method does not have, out overlapping audio; fills `c` and `s`
+inline int sil_probe_check(const char* who, const float* audio, int B, int N, const int32_t* lengths, int method, int mode, int rate,
+                           double threshold, double min_silence, int block_size, int replace_by, double min_voice_time, int what,
+                           const void* out, const int32_t* width, int mem, SilCall& c, SilStage* s, char* msg, size_t n) {
+    if (!width) return audio_refuse(msg, n, who, "bad argument");
+    // the probe's out has its stage's extent, not the call's B * N floats: sil_check gets the address behind audio in its
+    // place (compared with audio, never read), and the probe's own out is compared below
+    const float* behind = audio && B > 0 && N > 0 ? audio + (size_t)B * N : audio;
+    if (int rc = sil_check(who, audio, B, N, lengths, method, mode, rate, threshold, min_silence, block_size, replace_by,
+                           min_voice_time, behind, width, mem, c, msg, n))
+        return rc;
+    if (what < 0 || what >= SIL_STAGES) return audio_refuse(msg, n, who, "no stage %d (0 .. %d)", what, SIL_STAGES - 1);
+    const bool rms = method == TTS_HIP_SILENCE_RMS, mw = method == TTS_HIP_SILENCE_MEAN_WINDOW;
+    if ((what == SIL_FLAGS && !rms) || (what == SIL_INTERVALS && mw) || (what == SIL_PREFIX && !mw))
+        return audio_refuse(msg, n, who, "method %d has no stage %d", method, what);
+    switch (what) {
+        case SIL_FLAGS: *s = {c.NB, 1}; break;
+        case SIL_INTERVALS: *s = {2 + 2 * c.cap, 4}; break;
+        case SIL_MASK: *s = {N, 1}; break;
+        case SIL_TILE_OFFSETS: *s = {c.NT, 4}; break;
+        default: *s = {N + 1, 8}; break;
+    }
+    const char *a0 = (const char*)audio, *o0 = (const char*)out;
+    const size_t a_bytes = (size_t)B * N * 4, o_bytes = (size_t)B * s->width * s->elem;
+    if (out && a0 < o0 + o_bytes && o0 < a0 + a_bytes) return audio_refuse(msg, n, who, "out overlaps audio");
+    return TTS_HIP_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- mel plans (mel_stft.hip)
 // A plan (tts_hip_mel_fn) is a checked tts_hip_mel_config plus the operand widths its tables are padded to; a call derives
 // its frame counts and its one workspace from the plan, B, N and lengths.

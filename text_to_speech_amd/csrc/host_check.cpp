@@ -29,7 +29,9 @@
 // (noise_len; window_length threshold add_start add_end mode; rate target_rate M; method mode rate threshold min_silence
 // block_size replace_by min_voice_time).  First line "<status> <message>"; when the call is accepted the geometry the check
 // derived: reduce_noise "Fr NP Frn NQ total", trim "W Wp Cst", silence "NT NB cap w total", resample one line
-// "logf logi M_b" per row (tests/test_audio_call.py compares them with a Python restatement).  KIND resample_fft: the check
+// "logf logi M_b" per row (tests/test_audio_call.py compares them with a Python restatement).  KIND silence with probe=1
+// what=STAGE: the check of tts_hip_remove_silence_probe (null=out asks for the width alone, null=lens takes its width
+// away); accepted: a further line "width elem" (tests/test_silence_stages.py).  KIND resample_fft: the check
 // of tts_hip_resample_fft_probe (settings lines logL, null=audio,out); accepted: the bytes of the staged lines.  KIND
 // mel_fn: the plan check and the call check of a mel plan (mel_cfg_check, then mel_call_check); settings mel_kind (the config's kind) sampling_rate n_mel_channels
 // filter_length hop_length win_length normalize_mode mel_fmin mel_fmax pre_emph, window=I:VALUE (an explicit window of ones
@@ -199,7 +201,7 @@ static int print_audio_call(int argc, char** argv) {
                                     {"hop_length", 256}, {"win_length", 1024}, {"normalize_mode", 0}, {"mel_fmin", 0},
                                     {"mel_fmax", 8000}, {"pre_emph", 0}, {"lines", 1}, {"logL", 6}, {"F", 0}, {"C", 0},
                                     {"input_kind", 0}, {"n_iters", 0}, {"momentum", 0}, {"what", -1}, {"k", 0}, {"minv", 0},
-                                    {"strength", 0.1}};
+                                    {"strength", 0.1}, {"probe", 0}};
     bool null_cfg = false, null_fn = false, null_bias = false;
     int window_at = -1;
     double window_value = 1;
@@ -263,13 +265,19 @@ static int print_audio_call(int argc, char** argv) {
         printf("%lld\n", ((long long)v["lines"] << (int)v["logL"]) * 8);
     } else if (kind == "silence") {
         SilCall c;
-        const int rc = sil_check("who", audio, B, N, lp, (int)v["method"], (int)v["mode"], (int)v["rate"], v["threshold"],
-                                 v["min_silence"], (int)v["block_size"], (int)v["replace_by"], v["min_voice_time"], out, lens_out,
-                                 mem, c, why, sizeof why);
+        SilStage s{};
+        const bool probing = v["probe"] != 0;           // lens_out stands for the probe's width
+        const int rc = probing ? sil_probe_check("who", audio, B, N, lp, (int)v["method"], (int)v["mode"], (int)v["rate"],
+                                                 v["threshold"], v["min_silence"], (int)v["block_size"], (int)v["replace_by"],
+                                                 v["min_voice_time"], (int)v["what"], out, lens_out, mem, c, &s, why, sizeof why)
+                               : sil_check("who", audio, B, N, lp, (int)v["method"], (int)v["mode"], (int)v["rate"], v["threshold"],
+                                           v["min_silence"], (int)v["block_size"], (int)v["replace_by"], v["min_voice_time"], out,
+                                           lens_out, mem, c, why, sizeof why);
         printf("%d %s\n", rc, why);
         if (rc) return 0;
         if ((int)c.lens.size() != B) return 2;
         printf("%d %d %d %d %zu\n", c.NT, c.NB, c.cap, c.w, c.total);
+        if (probing) printf("%d %d\n", s.width, s.elem);
     } else if (kind == "mel_fn") {
         const tts_hip_mel_config cfg{(int)v["mel_kind"], (int)v["sampling_rate"], (int)v["n_mel_channels"], (int)v["filter_length"],
                                      (int)v["hop_length"], (int)v["win_length"], (int)v["normalize_mode"], v["mel_fmin"],

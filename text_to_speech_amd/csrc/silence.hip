@@ -12,6 +12,8 @@
 //                same interval list (one leading interval, one tail cut) -> mask
 //   mean-window  fp64 prefix sums of the fp32 squares (the same tile scan) -> box sums as prefix differences -> their mean
 //                -> mask
+// The double-precision decisions of the rms method (link, trailing end) are compiled with fp contraction off: the reference
+// rounds every product before it subtracts, and an fma decides a gap of exactly min_voice_time the other way.
 // The whole call is enqueued on the stream; no stage reads anything back on the host.  Every row b has its own length
 // L_b <= N; nothing at or beyond L_b is read.
 #include "engine.h"
@@ -25,6 +27,30 @@ namespace {
 constexpr int SIL_PER = 8;                   // consecutive samples per thread of a SIL_TILE workgroup (audio_call.h)
 
 // ---------------------------------------------------------------------------------------------- shared: scan and compaction
+// Exclusive sum scan over the workgroup's threads (audio_dev.h's block_scan, shifted by one thread): the sum of the threads
+// before this one, 0 for the first; `total` as block_scan's.  An inclusive value less the thread's own is the same number
+// for integers only: in floating point the difference keeps the rounding of sums that held the own value, which is large
+// against a small sum before it (a quiet start followed by voice).  This one adds non-negative terms only.
+template <class T>
+__device__ T sil_scan_exclusive(T v, T* sh, T& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = __shfl_up(v, o);
+        if (lane >= o) v += u;
+    }
+    if (lane == 63) sh[w] = v;
+    __syncthreads();
+    T base = T(0), all = T(0);
+    for (int i = 0; i < nw; ++i) {
+        if (i < w) base += sh[i];
+        all += sh[i];
+    }
+    __syncthreads();
+    total = all;
+    const T before = __shfl_up(v, 1);
+    return lane == 0 ? base : base + before;
+}
+
 // off[b][k] = sum of val[b][0..k) over the row's tiles k < ceil(L_b / SIL_TILE), total[b] = their sum (one workgroup per row;
 // chunks of blockDim tiles, carried).  Serves the tile counts of the compaction (int) and the tile sums of squares (double).
 template <class T>
@@ -37,8 +63,8 @@ __global__ __launch_bounds__(1024) void sil_row_scan_kernel(const T* __restrict_
         const int k = c0 + threadIdx.x;
         const T v = k < nt ? val[(long long)b * NT + k] : T(0);
         T all;
-        const T inc = block_scan(v, sh, all, OpAdd());
-        if (k < nt) off[(long long)b * NT + k] = carry + (inc - v);
+        const T before = sil_scan_exclusive(v, sh, all);
+        if (k < nt) off[(long long)b * NT + k] = carry + before;
         carry += all;
     }
     if (threadIdx.x == 0 && total) total[b] = carry;
@@ -136,16 +162,46 @@ __global__ __launch_bounds__(256) void sil_block_flags_kernel(const float* __res
     if ((threadIdx.x & 63) == 0) flag[(long long)b * P.NB + k] = sqrtf(m) < P.thr ? 1 : 0;
 }
 
+// The double-precision decisions of the rms method are the reference's Python doubles: every product is rounded before it is
+// subtracted or compared.  Contracted into one fma the product is not, and a voice of exactly min_voice_time (20 blocks of
+// 10 ms at the defaults: 30 * 0.01 - 10 * 0.01 = 0.19999999999999998 < 0.2, but fma(30, 0.01, -0.1) = 0.2) or a silence that
+// ends one sample before the row does is judged the other way.  So they are compiled uncontracted, and the link of a pair
+// (r - 1, r) is one function that both of its threads call: the two cannot disagree whatever the compiler makes of it.
+__device__ __forceinline__ double sil_end_seconds(int j, double bt, double Lr) {
+#pragma clang fp contract(off)
+    const double t = (double)j * bt;
+    return fmin(Lr, t);
+}
+
+// silence (i_next, .) starts less than min_voice_time after silence (., j_prev) ends
+__device__ __forceinline__ bool sil_links(int j_prev, int i_next, double bt, double Lr, double mvt) {
+#pragma clang fp contract(off)
+    const double s = (double)i_next * bt;
+    const double e = sil_end_seconds(j_prev, bt, Lr);
+    const double gap = s - e;
+    return gap < mvt;
+}
+
+// a silence that ends at e seconds ends within one sample of the row's end
+__device__ __forceinline__ bool sil_ends_row(double e, double rate, int L) {
+#pragma clang fp contract(off)
+    const double t = e * rate;
+    const double d = t - (double)L;
+    return fabs(d) <= 1.0;
+}
+
 // One workgroup per row, three passes, each over chunks of blockDim entries with the scans carried from chunk to chunk:
 //   1. over the block flags: a silent run [i, j) ends at k = j - 1; i = 1 + the last loud block before k (max scan); the runs
 //      with (j - i) * bt >= min_silence are numbered (sum scan) and listed in (si, sj)
-//   2. over that list: silence r links to r - 1 when s[r] - e[r - 1] < min_voice_time; every chain of links is one merged
-//      silence, numbered by its head (sum scan): d0 = (int)(s_head * rate), d1 = (int)(e_tail * rate)
+//   2. over that list: silence r links to r - 1 when s[r] - e[r - 1] < min_voice_time (sil_links); every chain of links is
+//      one merged silence, numbered by its head (sum scan): d0 = (int)(s_head * rate), d1 = (int)(e_tail * rate), the tail
+//      being the silence whose successor does not link to it
 //   3. over the merged silences (mode remove): each becomes its dropped interval, in place; the slice modes need the first
 //      and the last only
 __global__ __launch_bounds__(1024) void sil_rms_runs_kernel(const uint8_t* __restrict__ flag, const int* __restrict__ lens,
                                                             RmsParams P, int* __restrict__ si, int* __restrict__ sj,
                                                             Intervals iv) {
+#pragma clang fp contract(off)
     __shared__ int sh[16];
     __shared__ int s_cut, s_last_end;
     const int b = blockIdx.x, L = lens[b], tid = threadIdx.x;
@@ -190,10 +246,10 @@ __global__ __launch_bounds__(1024) void sil_rms_runs_kernel(const uint8_t* __res
         bool link = false, link_next = false;
         if (valid) {
             s = (double)si[r] * P.bt;
-            e = fmin(Lr, (double)sj[r] * P.bt);
+            e = sil_end_seconds(sj[r], P.bt, Lr);
             if (P.mvt != 0.0) {
-                if (r > 0) link = s - fmin(Lr, (double)sj[r - 1] * P.bt) < P.mvt;
-                if (r + 1 < ns) link_next = (double)si[r + 1] * P.bt - e < P.mvt;
+                if (r > 0) link = sil_links(sj[r - 1], si[r], P.bt, Lr, P.mvt);
+                if (r + 1 < ns) link_next = sil_links(sj[r], si[r + 1], P.bt, Lr, P.mvt);
             }
         }
         const int head = valid && !link ? 1 : 0;
@@ -201,7 +257,7 @@ __global__ __launch_bounds__(1024) void sil_rms_runs_kernel(const uint8_t* __res
         const int m = nm + block_scan(head, sh, all, OpAdd()) - 1;
         if (head) d0[m] = (int)(s * P.rate);
         if (valid && !link_next) d1[m] = (int)(e * P.rate);
-        if (valid && r == ns - 1) s_last_end = fabs(e * P.rate - (double)L) <= 1.0 ? 1 : 0;
+        if (valid && r == ns - 1) s_last_end = sil_ends_row(e, P.rate, L) ? 1 : 0;
         nm += all;
     }
     __syncthreads();
@@ -310,7 +366,7 @@ __global__ __launch_bounds__(256) void sil_square_prefix_kernel(const float* __r
         c += q[u];
     }
     double all;
-    double run = toff[b * NT + blockIdx.x] + block_scan(c, sh, all, OpAdd()) - c;
+    double run = toff[b * NT + blockIdx.x] + sil_scan_exclusive(c, sh, all);
     double* p = P + (long long)b * (N + 1);
 #pragma unroll
     for (int u = 0; u < SIL_PER; ++u) {
@@ -353,8 +409,26 @@ __global__ void sil_conv_mask_kernel(const double* __restrict__ P, int N, const 
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-// device pointers only; everything is enqueued on e->stream
-int sil_run(tts_hip_engine* e, const SilCall& c, const float* d_audio, float* d_out, int* d_out_len) {
+// What tts_hip_remove_silence_probe asks of sil_run: stop behind stage `what` and copy its rows to `out` (host or device as
+// `mem` says)
+struct SilProbe {
+    int what;
+    void* out;
+    int mem;
+};
+
+// `rows` rows of `bytes` bytes, `spitch` bytes apart, to rows `dpitch` bytes apart, on e->stream
+int sil_copy_rows(tts_hip_engine* e, const SilProbe& p, size_t at, size_t dpitch, const void* src, size_t spitch, size_t bytes,
+                  size_t rows) {
+    const hipMemcpyKind kind = p.mem == TTS_HIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    HIPCHK(e, hipMemcpy2DAsync((char*)p.out + at, dpitch, src, spitch, bytes, rows, kind, e->stream));
+    return TTS_HIP_OK;
+}
+
+// device pointers only; everything is enqueued on e->stream.  With `probe` the run ends behind that stage.
+int sil_run(tts_hip_engine* e, const SilCall& c, const float* d_audio, float* d_out, int* d_out_len,
+            const SilProbe* probe = nullptr) {
+    const auto stop_at = [&](int stage) { return probe && probe->what == stage; };
     AudioProcDev& a = e->aproc;
     hipStream_t st = e->stream;
     const int B = c.B, N = c.N, NT = c.NT;
@@ -382,6 +456,7 @@ int sil_run(tts_hip_engine* e, const SilCall& c, const float* d_audio, float* d_
         uint8_t* flag = (uint8_t*)(base + c.off_flag);
         hipLaunchKernelGGL(sil_block_flags_kernel, dim3(blocks(c.NB, 4), B), dim3(256), 0, st, d_audio, N, lens, P, flag);
         HIPCHK(e, hipGetLastError());
+        if (stop_at(SIL_FLAGS)) return sil_copy_rows(e, *probe, 0, (size_t)c.NB, flag, (size_t)c.NB, (size_t)c.NB, B);
         hipLaunchKernelGGL(sil_rms_runs_kernel, dim3(B), dim3(1024), 0, st, flag, lens, P, (int*)(base + c.off_si),
                            (int*)(base + c.off_sj), iv);
         HIPCHK(e, hipGetLastError());
@@ -389,6 +464,13 @@ int sil_run(tts_hip_engine* e, const SilCall& c, const float* d_audio, float* d_
         hipLaunchKernelGGL(sil_threshold_bounds_kernel, dim3(B), dim3(1024), 0, st, d_audio, N, lens, (float)c.threshold, c.mode,
                            iv);
         HIPCHK(e, hipGetLastError());
+    }
+    if (stop_at(SIL_INTERVALS)) {               // n, cut, d0[cap], d1[cap] of every row
+        const size_t cap4 = (size_t)c.cap * 4, pitch = 8 + 2 * cap4;
+        if (int rc = sil_copy_rows(e, *probe, 0, pitch, iv.n, 4, 4, B)) return rc;
+        if (int rc = sil_copy_rows(e, *probe, 4, pitch, iv.cut, 4, 4, B)) return rc;
+        if (int rc = sil_copy_rows(e, *probe, 8, pitch, iv.d0, cap4, cap4, B)) return rc;
+        return sil_copy_rows(e, *probe, 8 + cap4, pitch, iv.d1, cap4, cap4, B);
     }
     if (c.method == TTS_HIP_SILENCE_MEAN_WINDOW) {
         double* tsum = (double*)(base + c.off_tsum);
@@ -402,6 +484,10 @@ int sil_run(tts_hip_engine* e, const SilCall& c, const float* d_audio, float* d_
         HIPCHK(e, hipGetLastError());
         hipLaunchKernelGGL(sil_square_prefix_kernel, dim3(NT, B), dim3(256), 0, st, d_audio, N, NT, lens, toff, P);
         HIPCHK(e, hipGetLastError());
+        if (stop_at(SIL_PREFIX)) {
+            const size_t row = ((size_t)N + 1) * 8;
+            return sil_copy_rows(e, *probe, 0, row, P, row, row, B);
+        }
         hipLaunchKernelGGL(sil_conv_sum_kernel, dim3(NT, B), dim3(256), 0, st, P, N, NT, lens, c.w, scale, tsum);
         HIPCHK(e, hipGetLastError());
         hipLaunchKernelGGL(sil_row_scan_kernel<double>, dim3(B), dim3(1024), 0, st, tsum, toff, NT, lens, tot);
@@ -413,10 +499,12 @@ int sil_run(tts_hip_engine* e, const SilCall& c, const float* d_audio, float* d_
         hipLaunchKernelGGL(sil_interval_mask_kernel, dim3(blocks(N, 256), B), dim3(256), 0, st, iv, N, lens, mask);
         HIPCHK(e, hipGetLastError());
     }
+    if (stop_at(SIL_MASK)) return sil_copy_rows(e, *probe, 0, (size_t)N, mask, (size_t)N, (size_t)N, B);
     hipLaunchKernelGGL(sil_tile_count_kernel, dim3(NT, B), dim3(256), 0, st, mask, N, NT, lens, cnt);
     HIPCHK(e, hipGetLastError());
     hipLaunchKernelGGL(sil_row_scan_kernel<int>, dim3(B), dim3(1024), 0, st, cnt, off, NT, lens, d_out_len);
     HIPCHK(e, hipGetLastError());
+    if (stop_at(SIL_TILE_OFFSETS)) return sil_copy_rows(e, *probe, 0, (size_t)NT * 4, off, (size_t)NT * 4, (size_t)NT * 4, B);
     hipLaunchKernelGGL(sil_scatter_kernel, dim3(NT, B), dim3(256), 0, st, d_audio, mask, N, NT, lens, off, d_out_len, d_out);
     HIPCHK(e, hipGetLastError());
     return TTS_HIP_OK;
@@ -452,5 +540,28 @@ int tts_hip_remove_silence(tts_hip_engine* e, const float* audio, int B, int N, 
     const int in = io.in(audio, (size_t)B * N * 4), res = io.out(out, (size_t)B * N * 4), len = io.out(out_lengths, (size_t)B * 4);
     if (int rc = io.begin()) return rc;
     if (int rc = sil_run(e, c, io.ptr<const float>(in), io.ptr<float>(res), io.ptr<int>(len))) return rc;
+    return io.finish();
+}
+
+// Test hook: sil_run on the same rows up to stage `what`, then the rows that stage wrote.  *width (host memory) is set for
+// every accepted call; out NULL asks for it alone.
+int tts_hip_remove_silence_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int method, int mode,
+                                 int rate, double threshold, double min_silence, int block_size, int replace_by,
+                                 double min_voice_time, int what, void* out, int32_t* width, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    SilCall c;
+    SilStage s{};
+    char why[256];
+    if (int rc = sil_probe_check("remove_silence_probe", audio, B, N, lengths, method, mode, rate, threshold, min_silence, block_size,
+                                 replace_by, min_voice_time, what, out, width, mem, c, &s, why, sizeof why))
+        return set_err(e, rc, "%s", why);
+    *width = s.width;
+    if (!out) return TTS_HIP_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    AudioStage io(e, mem);
+    const int in = io.in(audio, (size_t)B * N * 4), res = io.scratch((size_t)B * N * 4), len = io.scratch((size_t)B * 4);
+    if (int rc = io.begin()) return rc;
+    const SilProbe probe{what, out, mem};
+    if (int rc = sil_run(e, c, io.ptr<const float>(in), io.ptr<float>(res), io.ptr<int>(len), &probe)) return rc;
     return io.finish();
 }

@@ -1392,6 +1392,58 @@ class HipEngine:
     _SILENCE_DEFAULTS = {'rms': (-25, 0.1), 'threshold': (0.1, 0.), 'remove': (0.025, 0.15)}    # threshold, min_silence
     _SILENCE_MAX = 1 << 24          # samples per row
 
+    def _silence_call(self, who, audio, rate, lengths, method, mode, threshold, min_silence, block_size, replace_by,
+                      min_voice_time):
+        """(B, N, int32 lengths or None, the C arguments from `method` to `min_voice_time`) of a remove_silence[_probe] call;
+        raises for what the C side refuses, before any GPU call."""
+        B, N, lens = self._audio_rows(audio, lengths, who)
+        if isinstance(method, bytes):
+            method = method.decode()
+        if isinstance(mode, bytes):
+            mode = mode.decode()
+        if method not in self._SILENCE_METHODS:
+            raise ValueError(f'{who}: unknown method {method!r} (supported: {sorted(self._SILENCE_METHODS)})')
+        if mode not in self._SILENCE_MODES:
+            raise ValueError(f'{who}: invalid mode {mode!r} (start, end, start_end or remove)')
+        if mode == 'remove' and method != 'rms':
+            raise ValueError(f"{who}: mode 'remove' belongs to method 'rms' (got method {method!r})")
+        if rate is None or int(rate) != rate or rate <= 0:
+            raise ValueError(f'{who}: rate must be a positive integer (got {rate})')
+        rate = int(rate)
+        d_thr, d_sil = self._SILENCE_DEFAULTS[method]
+        threshold = d_thr if threshold is None else threshold
+        min_silence = d_sil if min_silence is None else min_silence
+        bs = rb = 1
+        if method == 'rms':
+            bs = self._samples(block_size, rate, who + ': block_size')
+            rb = self._samples(replace_by, rate, who + ': replace_by')
+            if bs < 1:
+                raise ValueError(f'{who}: block_size must be >= 1 sample (got {bs})')
+            if not 0 <= rb < 1 << 31:
+                raise ValueError(f'{who}: replace_by must be >= 0 samples (got {rb})')
+            if not np.isfinite(min_voice_time) or min_voice_time < 0:
+                raise ValueError(f'{who}: min_voice_time must be finite and >= 0 (got {min_voice_time})')
+            bs = min(bs, 1 << 30)
+        else:
+            min_voice_time = 0.
+        if not np.isfinite(threshold) or (method != 'rms' and threshold < 0):
+            raise ValueError(f'{who}: threshold must be finite{"" if method == "rms" else " and >= 0"} (got {threshold})')
+        if not np.isfinite(min_silence) or min_silence < 0:
+            raise ValueError(f'{who}: min_silence must be finite and >= 0 (got {min_silence})')
+        if method == 'remove':
+            w = int(min_silence * rate)
+            shortest = N if lens is None else int(lens.min())
+            if threshold <= 0 or w < 1:
+                raise ValueError(f'{who}: the mean-window method needs threshold > 0 and a window of w >= 1 samples '
+                                 f'(got threshold {threshold}, w = {w})')
+            if shortest < w:
+                raise ValueError(f'{who}: a row of L = {shortest} samples is shorter than the window w = {w}')
+        if B > 65535 or N > self._SILENCE_MAX or B * N * 4 >= 1 << 31:
+            raise ValueError(f'{who}: B = {B} x N = {N} too large (B <= 65535, N <= 2^24, B * N * 4 < 2^31)')
+        args = (self._SILENCE_METHODS[method], self._SILENCE_MODES[mode], rate, float(threshold), float(min_silence), bs, rb,
+                float(min_voice_time))
+        return B, N, lens, args
+
     def remove_silence(self, audio, rate, lengths=None, method='rms', mode='start_end', threshold=None, min_silence=None,
                        block_size=0.01, replace_by=0.5, min_voice_time=0.2, stream=None):
         """The reference's numpy trim methods (utils/audio/audio_processing.py), sample for sample, with the kept samples
@@ -1406,58 +1458,39 @@ class HipEngine:
         tensor in ([N] or [B, N]) -> CUDA tensors (out, int32 out_lengths) of the input's rank, without synchronization of
         the lengths; `stream` (torch.cuda.Stream, device tensors only): enqueue there and return without waiting (the
         clean-up calls share one workspace per engine: the next one must be ordered after it)."""
-        B, N, lens = self._audio_rows(audio, lengths, 'remove_silence')
-        if isinstance(method, bytes):
-            method = method.decode()
-        if isinstance(mode, bytes):
-            mode = mode.decode()
-        if method not in self._SILENCE_METHODS:
-            raise ValueError(f'remove_silence: unknown method {method!r} (supported: {sorted(self._SILENCE_METHODS)})')
-        if mode not in self._SILENCE_MODES:
-            raise ValueError(f'remove_silence: invalid mode {mode!r} (start, end, start_end or remove)')
-        if mode == 'remove' and method != 'rms':
-            raise ValueError(f"remove_silence: mode 'remove' belongs to method 'rms' (got method {method!r})")
-        if rate is None or int(rate) != rate or rate <= 0:
-            raise ValueError(f'remove_silence: rate must be a positive integer (got {rate})')
-        rate = int(rate)
-        d_thr, d_sil = self._SILENCE_DEFAULTS[method]
-        threshold = d_thr if threshold is None else threshold
-        min_silence = d_sil if min_silence is None else min_silence
-        bs = rb = 1
-        if method == 'rms':
-            bs = self._samples(block_size, rate, 'remove_silence: block_size')
-            rb = self._samples(replace_by, rate, 'remove_silence: replace_by')
-            if bs < 1:
-                raise ValueError(f'remove_silence: block_size must be >= 1 sample (got {bs})')
-            if not 0 <= rb < 1 << 31:
-                raise ValueError(f'remove_silence: replace_by must be >= 0 samples (got {rb})')
-            if not np.isfinite(min_voice_time) or min_voice_time < 0:
-                raise ValueError(f'remove_silence: min_voice_time must be finite and >= 0 (got {min_voice_time})')
-            bs = min(bs, 1 << 30)
-        else:
-            min_voice_time = 0.
-        if not np.isfinite(threshold) or (method != 'rms' and threshold < 0):
-            raise ValueError(f'remove_silence: threshold must be finite{"" if method == "rms" else " and >= 0"} (got {threshold})')
-        if not np.isfinite(min_silence) or min_silence < 0:
-            raise ValueError(f'remove_silence: min_silence must be finite and >= 0 (got {min_silence})')
-        if method == 'remove':
-            w = int(min_silence * rate)
-            shortest = N if lens is None else int(lens.min())
-            if threshold <= 0 or w < 1:
-                raise ValueError(f'remove_silence: the mean-window method needs threshold > 0 and a window of w >= 1 samples '
-                                 f'(got threshold {threshold}, w = {w})')
-            if shortest < w:
-                raise ValueError(f'remove_silence: a row of L = {shortest} samples is shorter than the window w = {w}')
-        if B > 65535 or N > self._SILENCE_MAX or B * N * 4 >= 1 << 31:
-            raise ValueError(f'remove_silence: B = {B} x N = {N} too large (B <= 65535, N <= 2^24, B * N * 4 < 2^31)')
-        args = (self._SILENCE_METHODS[method], self._SILENCE_MODES[mode], rate, float(threshold), float(min_silence), bs, rb,
-                float(min_voice_time))
+        B, N, lens, args = self._silence_call('remove_silence', audio, rate, lengths, method, mode, threshold, min_silence,
+                                              block_size, replace_by, min_voice_time)
         out, out_len = self._rows_call('remove_silence', audio, B, N, [],
                                        lambda empty: (empty((B, N), 'float32'), empty((B,), 'int32')),
                                        lambda extras, outs: (self._ptr(lens), *args, outs[0], outs[1]), stream)
         if len(audio.shape) != 1:
             return out, out_len
         return (out[0], out_len[0]) if _is_torch_cuda(audio) else out[0, :int(out_len[0])].copy()
+
+    _SILENCE_STAGES = {'flags': (0, 'uint8'), 'intervals': (1, 'int32'), 'mask': (2, 'uint8'), 'tile_offsets': (3, 'int32'),
+                       'prefix': (4, 'float64')}
+
+    def remove_silence_probe(self, audio, rate, what, lengths=None, method='rms', mode='start_end', threshold=None,
+                             min_silence=None, block_size=0.01, replace_by=0.5, min_voice_time=0.2):
+        """Test hook (tts_hip_remove_silence_probe): run `remove_silence` on the same arguments (host arrays) up to a stage
+        and return its rows [B, width], the width being what the C side reports: 'flags' uint8 [B, NB] (rms; 1 = silent
+        block), 'intervals' int32 [B, 2 + 2 * cap] (rms, threshold; n, cut, d0[cap], d1[cap]: the mask keeps t < cut outside
+        every [d0[m], d1[m]), m < n), 'mask' uint8 [B, N], 'tile_offsets' int32 [B, NT] (kept samples before each tile of
+        2048), 'prefix' float64 [B, N + 1] (mean-window; sums of the fp32 squares).  What lies behind a row's own extent
+        (its blocks, its n intervals, its lengths[b] samples, its tiles) is unspecified.  Always batched."""
+        if what not in self._SILENCE_STAGES:
+            raise ValueError(f'what must be one of {tuple(self._SILENCE_STAGES)}, got {what!r}')
+        stage, dtype = self._SILENCE_STAGES[what]
+        audio = np.asarray(audio, dtype=np.float32)
+        B, N, lens, args = self._silence_call('remove_silence_probe', audio, rate, lengths, method, mode, threshold, min_silence,
+                                              block_size, replace_by, min_voice_time)
+        width = ctypes.c_int32(0)
+        tail = lambda out: (self._ptr(lens), *args, stage, out, ctypes.byref(width))
+        audio = np.ascontiguousarray(audio)
+        self._check(self._lib.tts_hip_remove_silence_probe(self._h, self._ptr(audio), B, N, *tail(None), MEM_HOST),
+                    'remove_silence_probe')               # out NULL: the width alone
+        return self._host_call('remove_silence_probe', audio, B, N, [], lambda empty: (empty((B, width.value), dtype),),
+                               lambda extras, outs: tail(outs[0]))[0]
 
     # ------------------------------------------------------------------ measurement hooks
     def kernel_timing(self, enable: bool) -> None:
