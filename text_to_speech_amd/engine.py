@@ -2,6 +2,7 @@
 
 Inputs may be numpy arrays (host buffers: the library stages them over PCIe) or torch CUDA tensors (device buffers:
 passed by pointer, results returned as torch tensors on the same device).  PyTorch is only used to host device memory.
+Every call that takes arrays goes through `HipEngine._call`, which holds the host / device / stream rules.
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ Tacotron2InferenceOutput = namedtuple(
 Tacotron2ForwardOutput = namedtuple('Tacotron2ForwardOutput', ['decoder_output', 'mel', 'stop_tokens', 'attention_weights'])
 
 KERNEL_WN_IN, KERNEL_WN_RES_SKIP, KERNEL_DECODER_STEP = 0, 1, 2
+_INT32 = (-2 ** 31, 2 ** 31 - 1)        # the range of a row table whose entries only the C side checks
 
 
 def _is_torch_cuda(x) -> bool:
@@ -29,6 +31,11 @@ def _is_torch_cuda(x) -> bool:
 
 def _u64(v):
     return ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _dims(x):
+    """The shape of an array, a tensor or a nested sequence as a tuple of ints."""
+    return tuple(int(n) for n in np.shape(x))
 
 
 def attention_window(win_len, offset):
@@ -108,10 +115,6 @@ class HipEngine:
         import torch
         return torch
 
-    def _sync_torch(self):
-        torch = self._torch()
-        torch.cuda.current_stream(self.device).synchronize()
-
     def _check_device(self, *tensors):
         """Device tensors are passed by pointer: they must live on this engine's GPU (a pointer into another GPU's memory
         would be read as garbage or fault)."""
@@ -119,52 +122,108 @@ class HipEngine:
             if t is not None and _is_torch_cuda(t) and t.device.index != self.device:
                 raise ValueError(f'tensor on {t.device} passed to an engine on cuda:{self.device}')
 
-    def _order_after_torch(self, stream=None):
-        """Makes the work this call is about to enqueue wait for what torch has queued so far.  stream=None: the engine's
-        own (non-blocking) stream is used and the call returns after it drained, so torch's current stream on this device
-        is synchronized first (inputs may still be in flight there).  With a torch stream the engine call is enqueued on
-        that very stream: ordering is implicit and nothing is synchronized."""
-        if stream is None:
-            self._sync_torch()
-            return None
-        return ctypes.c_void_p(int(stream.cuda_stream))
-
-    def _enter_stream(self, stream):
-        """Context for the `stream=` paths: `stream` first waits for what torch's current stream has queued (the caller's
-        inputs may still be in flight there), then becomes torch's current stream, so that every conversion, padding and
-        output allocation of the call is ordered on the stream the engine kernels run on."""
-        torch = self._torch()
-        stream.wait_stream(torch.cuda.current_stream(self.device))
-        return torch.cuda.stream(stream)
-
-    @staticmethod
-    def _used_on(stream, *tensors):
-        """Tensors passed to the engine by pointer and read asynchronously on `stream`: tell the caching allocator, so that
-        a temporary freed when the call returns is not handed out again while the kernels still read it."""
-        for t in tensors:
-            if t is not None:
-                t.record_stream(stream)
-
-    def _staged(self, stream, prepare, *inputs):
-        """The two ways a device-tensor call is set up.  `prepare()` converts the inputs and allocates the outputs (a tuple of
-        tensors, None allowed).  stream=None: on torch's current stream, which is then drained (`_order_after_torch`) -> (tensors,
-        None); a torch stream: on that stream (`_enter_stream`), with the caller's `inputs` and the prepared tensors marked as
-        used there (`_used_on`) -> (tensors, the stream's pointer for an _async entry point)."""
-        if stream is None:
-            tensors = prepare()
-            self._order_after_torch()
-            return tensors, None
-        with self._enter_stream(stream):
-            tensors = prepare()
-        self._used_on(stream, *inputs, *tensors)
-        return tensors, ctypes.c_void_p(int(stream.cuda_stream))
-
     @staticmethod
     def _ptr(x):
         """NULL, a device tensor's or a host array's address."""
         if x is None:
             return None
         return ctypes.c_void_p(x.data_ptr()) if hasattr(x, 'data_ptr') else x.ctypes.data_as(ctypes.c_void_p)
+
+    def _call(self, name, inputs, make_outputs, args, stream=None, device=None, twin=True):
+        """tts_hip_<name> on host arrays or on CUDA tensors, synchronously or on a caller's stream -> the outputs.
+
+        `inputs`: (array-like or None, shape or None, dtype name) each; an input becomes a contiguous array of that dtype and
+        shape (None: its own).  `make_outputs(new)` returns the outputs as a tuple (None allowed), allocating with
+        new(shape, dtype='float32', zeros=False) or handing on a caller's `out=` tensor.  `args(ins, outs, (mem, stream
+        pointer))` returns what the C function takes after the handle; arrays and tensors in it are turned into their
+        addresses here, so a host table (lengths, keys, a bias ...) put into it stays referenced until the C call has returned.
+        `twin`: the entry point ends in the mem kind and has an _async twin that ends in the stream (appended here); not
+        `twin`: one entry point, and `args` places the mem kind and the stream pointer itself.
+
+        `device` (default: whether the first input is a CUDA tensor) decides between
+          * a host call: numpy inputs and outputs, TTS_HIP_MEM_HOST; a `stream` is refused before any library call;
+          * a device call: the other inputs are moved to this engine's GPU, every tensor must live there (`_check_device`), the
+            outputs are CUDA tensors.  stream=None: inputs are converted and outputs allocated on torch's current stream,
+            which is then drained (the engine runs on a stream of its own and returns after that drained), and the call takes
+            TTS_HIP_MEM_DEVICE.  A torch.cuda.Stream: it first waits for what torch's current stream has queued (the inputs may
+            still be in flight there), conversion and allocation happen with it as torch's current stream, and the caller's
+            inputs and every prepared tensor are marked as used on it -- the caching allocator must not hand out a temporary
+            freed when this method returns while the kernels still read it; the work is enqueued there and not waited for."""
+        if device is None:
+            device = _is_torch_cuda(inputs[0][0])
+        if not device:
+            if stream is not None:
+                raise ValueError('stream= needs device tensors')
+            def host(x, shape, dt):
+                a = np.asarray(x.detach().cpu() if hasattr(x, 'detach') else x, dtype=dt)
+                return np.ascontiguousarray(a if shape is None else a.reshape(shape))
+
+            ins = [None if x is None else host(x, shape, dt) for x, shape, dt in inputs]
+            outs = make_outputs(lambda shape, dtype='float32', zeros=False: (np.zeros if zeros else np.empty)(shape, dtype=dtype))
+            mem, sp = MEM_HOST, None
+        else:
+            torch = self._torch()
+            gpu = torch.device('cuda', self.device)
+            self._check_device(*(x for x, _, _ in inputs))
+            given = [x if x is None or _is_torch_cuda(x) else torch.as_tensor(np.asarray(x, dtype=dt), device=gpu)
+                     for x, _, dt in inputs]
+
+            def prepare():
+                ins = [None if x is None else (x.to(getattr(torch, dt)) if shape is None else x.to(getattr(torch, dt)).reshape(shape)).contiguous()
+                       for x, (_, shape, dt) in zip(given, inputs)]
+                outs = make_outputs(lambda shape, dtype='float32', zeros=False:
+                                    (torch.zeros if zeros else torch.empty)(shape, dtype=getattr(torch, dtype), device=gpu))
+                self._check_device(*outs)
+                return ins, outs
+
+            current = torch.cuda.current_stream(self.device)
+            mem, sp = MEM_DEVICE, None
+            if stream is None:
+                ins, outs = prepare()
+                current.synchronize()
+            else:
+                stream.wait_stream(current)
+                with torch.cuda.stream(stream):
+                    ins, outs = prepare()
+                for t in (*given, *ins, *outs):
+                    if t is not None:
+                        t.record_stream(stream)
+                sp = ctypes.c_void_p(int(stream.cuda_stream))
+                if twin:
+                    name += '_async'
+        argv = tuple(args(ins, outs, (mem, sp)))
+        if twin:
+            argv += (mem if stream is None else sp,)
+        self._check(getattr(self._lib, 'tts_hip_' + name)(
+            self._h, *(self._ptr(a) if isinstance(a, np.ndarray) or hasattr(a, 'data_ptr') else a for a in argv)), name)
+        return outs
+
+    @staticmethod
+    def _row_table(values, B, lo, hi, what, name):
+        """`values` (any int sequence / array / tensor), the `name` argument of call `what`, as a contiguous host int32 [B] with
+        every entry in [lo, hi].  Raises before any GPU call."""
+        if hasattr(values, 'detach'):
+            values = values.detach().cpu().numpy()
+        arr = np.atleast_1d(np.asarray(values))
+        who = f'{what}: {name}' if what else name
+        if arr.shape != (B,):
+            raise ValueError(f'{who} must hold one value per row, shape ({B},), got {arr.shape}')
+        if arr.dtype.kind not in 'iu':
+            raise ValueError(f'{who} must be integers, got dtype {arr.dtype}')
+        if int(arr.min()) < lo or int(arr.max()) > hi:
+            raise ValueError(f'{who} must lie in [{lo}, {hi}], got {arr.tolist()}')
+        return np.ascontiguousarray(arr, dtype=np.int32)
+
+    @staticmethod
+    def _frame_lengths(lengths, B, T):
+        """`lengths` (any int sequence / array / tensor) as a contiguous host int32 [B] with every entry in [0, T]."""
+        return HipEngine._row_table(lengths, B, 0, T, '', 'lengths')
+
+    @staticmethod
+    def _batched(x, rank):
+        """The dims of `x`, [B, ...] of `rank` axes or one row of it without the batch axis (B = 1); None for any other rank."""
+        shape = _dims(x)
+        return (1, *shape) if len(shape) == rank - 1 else shape if len(shape) == rank else None
 
     # ------------------------------------------------------------------ device-side sampling
     def random_normal(self, shape, seed: int, offset: int = 0, stream=None):
@@ -177,22 +236,10 @@ class HipEngine:
         return self._random(1, (int(B), int(max_len), 2, 256), seed, offset, stream)
 
     def _random(self, kind, shape, seed, offset, stream):
-        torch = self._torch()
-        dev = torch.device('cuda', self.device)
-        u64 = lambda v: ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
-        if stream is not None:
-            with self._enter_stream(stream):
-                out = torch.empty(tuple(shape), dtype=torch.float32, device=dev)
-            sp = ctypes.c_void_p(int(stream.cuda_stream))
-        else:
-            out = torch.empty(tuple(shape), dtype=torch.float32, device=dev)
-            sp = None
-            # the block may have pending readers / writers on torch's current stream (the caching allocator reuses it in that
-            # stream's order only); the fill runs on the engine's own stream
-            self._order_after_torch()
-        self._check(self._lib.tts_hip_random_fill(self._h, kind, u64(seed), u64(offset), ctypes.c_void_p(out.data_ptr()),
-                                                  out.numel(), sp), 'random_fill')
-        if stream is None:
+        out, = self._call('random_fill', [], lambda new: (new(tuple(shape)),),
+                          lambda ins, outs, where: (kind, _u64(seed), _u64(offset), outs[0], outs[0].numel(), where[1]),
+                          stream, device=True, twin=False)
+        if stream is None:                      # the fill ran on the engine's own stream
             self.synchronize()
         return out
 
@@ -226,36 +273,21 @@ class HipEngine:
         return self._random_rows(1, row_stride, keys, offsets, counts, stream, out)
 
     def _random_rows(self, kind, row_stride, keys, offsets, counts, stream, out):
-        torch = self._torch()
-        dev = torch.device('cuda', self.device)
         keys, offsets = self._row_tables((keys, offsets))
         B, row_stride = len(keys), int(row_stride)
         if row_stride < 0:
             raise ValueError('row_stride must not be negative')
-        cnt_p = None
-        if counts is not None:
+        cnt = None
+        if counts is not None:                                   # int64, unlike the other row tables
             cnt = np.ascontiguousarray(np.asarray(counts, dtype=np.int64))
             if cnt.shape != (B,) or (B and (int(cnt.min()) < 0 or int(cnt.max()) > row_stride)):
                 raise ValueError(f'counts must hold one value in [0, row_stride = {row_stride}] per row, got {cnt.tolist()}')
-            cnt_p = cnt.ctypes.data_as(ctypes.c_void_p)
-        if out is not None:
-            if not _is_torch_cuda(out) or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * row_stride:
-                raise ValueError(f'out must be a contiguous float32 CUDA tensor of {B} x {row_stride} elements')
-            self._check_device(out)
-        if stream is not None:
-            with self._enter_stream(stream):
-                if out is None:
-                    out = torch.zeros((B, row_stride), dtype=torch.float32, device=dev)
-            self._used_on(stream, out)
-            sp = ctypes.c_void_p(int(stream.cuda_stream))
-        else:
-            if out is None:
-                out = torch.zeros((B, row_stride), dtype=torch.float32, device=dev)
-            sp = None
-            self._order_after_torch()
-        self._check(self._lib.tts_hip_random_fill_rows(
-            self._h, kind, keys.ctypes.data_as(ctypes.c_void_p), offsets.ctypes.data_as(ctypes.c_void_p), B, row_stride, cnt_p,
-            ctypes.c_void_p(out.data_ptr()), sp), 'random_fill_rows')
+        if out is not None and (not _is_torch_cuda(out) or out.dtype != self._torch().float32 or not out.is_contiguous()
+                                or out.numel() != B * row_stride):
+            raise ValueError(f'out must be a contiguous float32 CUDA tensor of {B} x {row_stride} elements')
+        out, = self._call('random_fill_rows', [], lambda new: (new((B, row_stride), zeros=True) if out is None else out,),
+                          lambda ins, outs, where: (kind, keys, offsets, B, row_stride, cnt, outs[0], where[1]),
+                          stream, device=True, twin=False)
         if stream is None:
             self.synchronize()
         return out
@@ -264,8 +296,7 @@ class HipEngine:
     def set_tensor(self, name: str, array) -> None:
         a = np.ascontiguousarray(array, dtype=np.float32)
         dims = (ctypes.c_int64 * a.ndim)(*a.shape)
-        self._check(self._lib.tts_hip_set_tensor(self._h, name.encode(), a.ctypes.data_as(ctypes.c_void_p), dims,
-                                                 a.ndim), f'set_tensor({name})')
+        self._check(self._lib.tts_hip_set_tensor(self._h, name.encode(), self._ptr(a), dims, a.ndim), f'set_tensor({name})')
 
     def load_state(self, tensors) -> None:
         for k, v in tensors.items():
@@ -281,19 +312,23 @@ class HipEngine:
         return bool(self._lib.tts_hip_has_model(self._h, model.encode()))
 
     # ------------------------------------------------------------------ WaveGlow
-    @staticmethod
-    def _frame_lengths(lengths, B, T):
-        """`lengths` (any int sequence / array / tensor) as a contiguous host int32 [B] with every entry in [0, T]."""
-        if hasattr(lengths, 'detach'):
-            lengths = lengths.detach().cpu().numpy()
-        arr = np.asarray(lengths)
-        if arr.shape != (B,):
-            raise ValueError(f'lengths must hold one frame count per row, shape ({B},), got {arr.shape}')
-        if arr.dtype.kind not in 'iu':
-            raise ValueError(f'lengths must be integers, got dtype {arr.dtype}')
-        if arr.size and (int(arr.min()) < 0 or int(arr.max()) > T):
-            raise ValueError(f'lengths must lie in [0, T = {T}], got {arr.tolist()}')
-        return np.ascontiguousarray(arr, dtype=np.int32)
+    _WG_PRECISIONS = {'f32': 0, 'f16': 1, 'f16x3': 2}
+    # (noise, rows) -> entry point, without the tts_hip_ prefix and the _async suffix of a call on a caller's stream
+    _WG_ENTRY = {('z', 'plain'): 'waveglow_infer', ('z', 'ragged'): 'waveglow_infer_ragged', ('z', 'packed'): 'waveglow_infer_packed',
+                 ('seed', 'plain'): 'waveglow_infer_seeded', ('rows', 'plain'): 'waveglow_infer_rows_seeded',
+                 ('rows', 'ragged'): 'waveglow_infer_rows_seeded', ('rows', 'packed'): 'waveglow_infer_rows_seeded'}
+
+    def _wg_inputs(self, mel, z=None, audio=None, lengths=None):
+        """(B, T, int32 lengths or None) of a WaveGlow call on mel [B, T, 80], z [B, T*32, 8] and / or audio [B, T*256]."""
+        shape = _dims(mel)
+        if len(shape) != 3 or shape[2] != 80:
+            raise ValueError(f'mel must be [B, T, 80], got {shape}')
+        B, T = shape[:2]
+        if z is not None and _dims(z) != (B, T * 32, 8):
+            raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {_dims(z)}')
+        if audio is not None and _dims(audio) != (B, T * 256):
+            raise ValueError(f'audio must be [B, T*256] = {(B, T * 256)}, got {_dims(audio)}')
+        return B, T, None if lengths is None else self._frame_lengths(lengths, B, T)
 
     def waveglow_infer(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', stream=None, seed=None, offset: int = 0,
                        lengths=None, packed: bool = False, row_seeds=None):
@@ -315,7 +350,6 @@ class HipEngine:
         -- the values `random_normal_rows` gives -- whatever batch the row sits in.  With `lengths` (ragged or packed) a row's
         arithmetic is its own too, so its audio is that of a one-row call with its key up to fp32 re-association; without
         `lengths` the batch is a padded one and a row still hears its padding."""
-        # 1. the arguments
         if packed and lengths is None:
             raise ValueError('packed=True needs lengths (one frame count per row)')
         if row_seeds is not None and (z is not None or seed is not None):
@@ -324,63 +358,37 @@ class HipEngine:
             raise ValueError('pass either z or seed, not both')
         if precision not in self._WG_PRECISIONS:
             raise ValueError(f"precision must be one of {tuple(self._WG_PRECISIONS)}, got {precision!r}")
-        dev = _is_torch_cuda(mel)
-        if not dev:
-            if stream is not None:
-                raise ValueError('stream= needs device tensors')
-            mel = np.ascontiguousarray(mel, dtype=np.float32)
-            z = None if z is None else np.ascontiguousarray(z, dtype=np.float32)
-        if len(mel.shape) != 3 or mel.shape[2] != 80:
-            raise ValueError(f'mel must be [B, T, 80], got {tuple(mel.shape)}')
-        B, T = int(mel.shape[0]), int(mel.shape[1])
-        if z is not None and tuple(z.shape) != (B, T * 32, 8):
-            raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {tuple(z.shape)}')
-        self._check_device(mel, z)
-        lens = None if lengths is None else self._frame_lengths(lengths, B, T)
+        B, T, lens = self._wg_inputs(mel, z=z, lengths=lengths)
         keys, offsets = (None, None) if row_seeds is None else self._row_tables(row_seeds, B)
         # A batch seed has an entry point of its own for plain synchronous calls only; everywhere else the call is
         # `random_fill` into a device z, then the z entry point.  Host mel with lengths: the noise lives on the device, so
         # the mel joins it there (80 floats a frame against the noise's 256) and the audio comes back.
         fill = seed is not None and (lens is not None or stream is not None)
-        via_device = fill and not dev
-        # 2. + 3. mel, z and the output: host arrays, or device tensors set up for `stream`
-        sp, mem = None, MEM_HOST
-        if dev or via_device:
-            torch = self._torch()
-            if via_device:
-                mel = torch.as_tensor(mel, device=torch.device('cuda', self.device))
-
-            def prepare():
-                m_ = mel.to(torch.float32).contiguous()
-                z_ = None if z is None else z.to(device=mel.device, dtype=torch.float32).contiguous()
-                if fill:
-                    z_ = torch.empty((B, T * 32, 8), dtype=torch.float32, device=mel.device)
-                return m_, z_, torch.empty((B, T * 256), dtype=torch.float32, device=mel.device)
-
-            (m, zz, out), sp = self._staged(stream, prepare, mel, z)
-            mem = MEM_DEVICE
-        else:
-            m, zz, out = mel, z, np.empty((B, T * 256), dtype=np.float32)
-        u64 = lambda v: ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
-        if fill:                                                 # on the stream of the call that reads it, ahead of it
-            self._check(self._lib.tts_hip_random_fill(self._h, 0, u64(seed), u64(offset), self._ptr(zz), zz.numel(), sp),
-                        'random_fill')
-        # 4. + 5. the entry point and its arguments: (h, mel, B, T, <rows and noise>, sigma, audio, precision, ..., mem | stream)
+        via_device = fill and stream is None and not _is_torch_cuda(mel)
+        # the entry point and its arguments: (h, mel, B, T, <rows and noise>, sigma, audio, precision, ..., mem | stream)
         noise = 'rows' if row_seeds is not None else 'seed' if seed is not None and not fill else 'z'
         name = self._WG_ENTRY[noise, 'packed' if packed else 'ragged' if lens is not None else 'plain']
         pcode = (self._WG_PRECISIONS[precision],)
         if name == 'waveglow_infer' and stream is None:          # the synchronous plain call has one symbol per precision
             name, pcode = name + {'f32': '', 'f16': '_f16', 'f16x3': '_f16x3'}[precision], ()
-        if noise == 'rows':
-            mid, last = (self._ptr(lens), self._ptr(keys), self._ptr(offsets)), (1 if packed else 0,)
-        elif noise == 'seed':
-            mid, last = (u64(seed), u64(offset)), ()
-        else:
-            mid, last = ((self._ptr(zz),) if lens is None else (self._ptr(lens), self._ptr(zz))), ()
-        if stream is not None:
-            name += '_async'
-        self._check(getattr(self._lib, 'tts_hip_' + name)(
-            self._h, self._ptr(m), B, T, *mid, float(sigma), self._ptr(out), *pcode, *last, mem if stream is None else sp), name)
+
+        def args(ins, outs, where):
+            m, zz = ins
+            if fill:                                             # on the stream of the call that reads it, ahead of it
+                zz = outs[1]
+                self._check(self._lib.tts_hip_random_fill(self._h, 0, _u64(seed), _u64(offset), self._ptr(zz), zz.numel(), where[1]),
+                            'random_fill')
+            if noise == 'rows':
+                mid, last = (lens, keys, offsets), (1 if packed else 0,)
+            elif noise == 'seed':
+                mid, last = (_u64(seed), _u64(offset)), ()
+            else:
+                mid, last = ((zz,) if lens is None else (lens, zz)), ()
+            return (m, B, T, *mid, float(sigma), outs[0], *pcode, *last)
+
+        out = self._call(name, [(mel, None, 'float32'), (z, None, 'float32')],
+                         lambda new: (new((B, T * 256)), new((B, T * 32, 8)) if fill else None), args, stream,
+                         device=True if via_device else None)[0]
         return out.cpu().numpy() if via_device else out
 
     def waveglow_encode(self, audio, mel, lengths=None, stream=None):
@@ -392,40 +400,12 @@ class HipEngine:
         length are never read, z is 0 there and the row gets what a call on its own frames gives it.  numpy in gives numpy out,
         CUDA tensors in give tensors out; `stream` (a torch.cuda.Stream, device tensors only): enqueue there and return without
         waiting (tts_hip_waveglow_encode_async).  B * T is limited to one run (31 744 frames)."""
-        dev = _is_torch_cuda(mel)
-        if dev != _is_torch_cuda(audio):
+        if _is_torch_cuda(mel) != _is_torch_cuda(audio):
             raise ValueError('audio and mel must both be host arrays or both be CUDA tensors')
-        if not dev:
-            if stream is not None:
-                raise ValueError('stream= needs device tensors')
-            mel = np.ascontiguousarray(mel, dtype=np.float32)
-            audio = np.ascontiguousarray(audio, dtype=np.float32)
-        if len(mel.shape) != 3 or mel.shape[2] != 80:
-            raise ValueError(f'mel must be [B, T, 80], got {tuple(mel.shape)}')
-        B, T = int(mel.shape[0]), int(mel.shape[1])
-        if tuple(audio.shape) != (B, T * 256):
-            raise ValueError(f'audio must be [B, T*256] = {(B, T * 256)}, got {tuple(audio.shape)}')
-        self._check_device(audio, mel)
-        lens = None if lengths is None else self._frame_lengths(lengths, B, T)
-        sp, mem = None, MEM_HOST
-        if dev:
-            torch = self._torch()
-
-            def prepare():
-                return (audio.to(torch.float32).contiguous(), mel.to(torch.float32).contiguous(),
-                        torch.empty((B, T * 32, 8), dtype=torch.float32, device=mel.device),
-                        torch.empty((3, B), dtype=torch.float32, device=mel.device))
-
-            (a, m, z, stats), sp = self._staged(stream, prepare, audio, mel)
-            mem = MEM_DEVICE
-        else:
-            a, m = audio, mel
-            z, stats = np.empty((B, T * 32, 8), dtype=np.float32), np.empty((3, B), dtype=np.float32)
-        name = 'waveglow_encode' + ('_async' if stream is not None else '')
-        self._check(getattr(self._lib, 'tts_hip_' + name)(
-            self._h, self._ptr(a), self._ptr(m), B, T, self._ptr(lens), self._ptr(z), self._ptr(stats),
-            mem if stream is None else sp), name)
-        return z, stats
+        B, T, lens = self._wg_inputs(mel, audio=audio, lengths=lengths)
+        return self._call('waveglow_encode', [(audio, None, 'float32'), (mel, None, 'float32')],
+                          lambda new: (new((B, T * 32, 8)), new((3, B))),
+                          lambda ins, outs, where: (ins[0], ins[1], B, T, lens, outs[0], outs[1]), stream)
 
     def waveglow_encode_probe(self, audio, mel, lengths=None, flow: int = 11, what: str = 'state'):
         """Test hook (tts_hip_waveglow_encode_probe): run `waveglow_encode` on host arrays up to the end of flow `flow` (0 .. 11;
@@ -435,35 +415,73 @@ class HipEngine:
         whats = {'state': 0, 'slog': 1}
         if what not in whats:
             raise ValueError(f'what must be one of {tuple(whats)}')
-        mel = np.ascontiguousarray(mel, dtype=np.float32)
-        audio = np.ascontiguousarray(audio, dtype=np.float32)
-        if mel.ndim != 3 or mel.shape[2] != 80:
-            raise ValueError(f'mel must be [B, T, 80], got {mel.shape}')
-        B, T = mel.shape[:2]
-        if audio.shape != (B, T * 256):
-            raise ValueError(f'audio must be [B, T*256] = {(B, T * 256)}, got {audio.shape}')
-        lens = None if lengths is None else self._frame_lengths(lengths, B, T)
+        B, T, lens = self._wg_inputs(mel, audio=audio, lengths=lengths)
         flow = int(flow)
         shape = (B, T * 32) if what == 'slog' else (B, T * 32, 8 if flow <= 2 else 6 if flow <= 6 else 4)
-        out = np.empty(shape, dtype=np.float32)
-        self._check(self._lib.tts_hip_waveglow_encode_probe(
-            self._h, self._ptr(audio), self._ptr(mel), B, T, self._ptr(lens), flow, whats[what], self._ptr(out), MEM_HOST),
-            'waveglow_encode_probe')
-        return out
+        return self._call('waveglow_encode_probe', [(audio, None, 'float32'), (mel, None, 'float32')], lambda new: (new(shape),),
+                          lambda ins, outs, where: (ins[0], ins[1], B, T, lens, flow, whats[what], outs[0]))[0]
 
-    _WG_PRECISIONS = {'f32': 0, 'f16': 1, 'f16x3': 2}
-    # (noise, rows) -> entry point, without the tts_hip_ prefix and the _async suffix of a call on a caller's stream
-    _WG_ENTRY = {('z', 'plain'): 'waveglow_infer', ('z', 'ragged'): 'waveglow_infer_ragged', ('z', 'packed'): 'waveglow_infer_packed',
-                 ('seed', 'plain'): 'waveglow_infer_seeded', ('rows', 'plain'): 'waveglow_infer_rows_seeded',
-                 ('rows', 'ragged'): 'waveglow_infer_rows_seeded', ('rows', 'packed'): 'waveglow_infer_rows_seeded'}
+    def waveglow_probe(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', flow: int = 11, what: str = 'acts',
+                       layer: int = 0):
+        """Test hook (tts_hip_waveglow_probe): run `waveglow_infer` in `precision` up to flow `flow` and return either the gated
+        activations [B, T*32, C] (C = `waveglow_channels`) of its WN layer `layer` (what='acts') or the flow state [B, T*32, n] right after the flow,
+        early output included (what='state'; the reference's audio after that flow), or the conditioning plane [B, T*32, 1024]
+        of that layer -- sum_q V_q mel[t - q] + b, columns in the gate-interleaved order of the engine's weights -- that the
+        fp32 Winograd form builds (what='cond'; layers 1 - 7 of calls of 144 frames or more, 512-channel models only)."""
+        whats = {'acts': 0, 'state': 1, 'cond': 2}
+        if precision not in self._WG_PRECISIONS or what not in whats:
+            raise ValueError(f'precision must be one of {tuple(self._WG_PRECISIONS)} and what one of {tuple(whats)}')
+        B, T, _ = self._wg_inputs(mel, z=z)
+        C = self.waveglow_channels
+        width = C if what == 'acts' else 2 * C if what == 'cond' else (4 if flow >= 8 else 6 if flow >= 4 else 8) + (2 if flow in (4, 8) else 0)
+        return self._call('waveglow_probe', [(mel, None, 'float32'), (z, None, 'float32')], lambda new: (new((B, T * 32, width)),),
+                          lambda ins, outs, where: (ins[0], B, T, ins[1], float(sigma), self._WG_PRECISIONS[precision], int(flow),
+                                                    whats[what], int(layer), outs[0]))[0]
+
+    def waveglow_probe_acts(self, mel, z=None, sigma: float = 1.0, flow: int = 11, layer: int = 1):
+        """Test hook (tts_hip_waveglow_probe_acts): the gated activations [B, T*32, C] (C = `waveglow_channels`) of WN layer `layer` of flow `flow` on
+        the fp32 path, in the form `set_waveglow_form` selects -- the values before the res/skip and `end` convolutions."""
+        B, T, _ = self._wg_inputs(mel, z=z)
+        C = self.waveglow_channels
+        return self._call('waveglow_probe_acts', [(mel, None, 'float32'), (z, None, 'float32')], lambda new: (new((B, T * 32, C)),),
+                          lambda ins, outs, where: (ins[0], B, T, ins[1], float(sigma), int(flow), int(layer), outs[0]))[0]
+
+    def set_waveglow_form(self, form: str) -> None:
+        """How the fp32 vocoder evaluates the dilated convolutions of WN layers 1 - 7: 'winograd' (default: minimal filtering
+        along the tap axis, F(4,3), for calls of 144 frames or more) or 'direct' (always three taps).  Both are fp32; they differ by rounding only.
+        The Winograd form exists for 512-channel models: with a 256-channel one (`waveglow_channels`) the call is accepted and
+        every fp32 call still takes the direct form."""
+        # 'winograd-3pass' / 'winograd-prepass': the two earlier stages of the Winograd form (pre-pass + per-product GEMM + combine
+        # pass; fused GEMM behind the pre-pass), kept for measurement and as bit-identical cross-checks of the default kernel
+        forms = {'direct': 0, 'winograd': 1, 'winograd-3pass': 2, 'winograd-prepass': 3}
+        if form not in forms:
+            raise ValueError(f'form must be one of {tuple(forms)}, got {form!r}')
+        self._check(self._lib.tts_hip_set_waveglow_form(self._h, forms[form]), 'set_waveglow_form')
+
+    @property
+    def last_waveglow_form(self) -> str:
+        """'winograd' or 'direct' for the last `waveglow_infer` call on this handle ('none' before the first)."""
+        return {1: 'winograd', 0: 'direct'}.get(self._lib.tts_hip_last_waveglow_form(self._h), 'none')
+
+    @property
+    def waveglow_channels(self) -> int:
+        """n_channels of this handle's WaveGlow (tts_hip_waveglow_channels): 512 or 256, fixed by the tensors present at
+        `finalize`; 0 while no WaveGlow is finalized."""
+        return int(self._lib.tts_hip_waveglow_channels(self._h))
+
+    @property
+    def last_waveglow_tiles(self) -> str:
+        """WN GEMM tile family of the last `waveglow_infer` (or probe) call: '64-row', '128x64', '128-row' or '256-row'
+        ('none' before the first)."""
+        return {3: '64-row', 2: '128x64', 1: '128-row', 0: '256-row'}.get(self._lib.tts_hip_last_waveglow_tiles(self._h), 'none')
 
     # ------------------------------------------------------------------ Tacotron2
     _TACO_PRECISIONS = {'f32': 0, 'f16': 1}
     # mask source -> (decode entry point without the tts_hip_ prefix, what the call passes where `tacotron2_decode` takes the
-    # masks: ptr = `_ptr`; src = the staged masks | (seed, offset) | the host tables (keys, offsets))
-    _TACO_DECODE = {'tensor': ('tacotron2_decode', lambda ptr, src: (ptr(src),)),
-                    'seed': ('tacotron2_decode_seeded', lambda ptr, src: (_u64(src[0]), _u64(src[1]))),
-                    'rows': ('tacotron2_decode_rows_seeded', lambda ptr, src: (ptr(src[0]), ptr(src[1])))}
+    # masks, from src = the staged masks | (seed, offset) | the host tables (keys, offsets))
+    _TACO_DECODE = {'tensor': ('tacotron2_decode', lambda src: (src,)),
+                    'seed': ('tacotron2_decode_seeded', lambda src: (_u64(src[0]), _u64(src[1]))),
+                    'rows': ('tacotron2_decode_rows_seeded', lambda src: tuple(src))}
 
     def _taco_precision(self, precision):
         if precision not in self._TACO_PRECISIONS:
@@ -474,49 +492,25 @@ class HipEngine:
         if encoded.engine is not self or encoded.handle is None:
             raise ValueError('this EncodedBatch belongs to another engine or was freed')
 
-    def _f32(self, x, dev):
-        """None, or `x` as contiguous float32: a tensor on this engine's GPU (dev) or a host array."""
-        if x is None:
-            return None
-        if dev:
-            torch = self._torch()
-            return x.to(device=torch.device('cuda', self.device), dtype=torch.float32).contiguous()
-        return np.ascontiguousarray(x, dtype=np.float32)
-
-    def _tokens(self, tokens, dev):
-        """`tokens` as contiguous int32 [B, Tin], where they are (a CUDA tensor if dev, else a host array)."""
-        tok = tokens.to(self._torch().int32).contiguous() if dev else np.ascontiguousarray(tokens, dtype=np.int32)
-        if len(tok.shape) != 2:
-            raise ValueError(f'tokens must be [B, Tin], got {tuple(tok.shape)}')
-        return tok
+    @staticmethod
+    def _token_dims(tokens):
+        """(B, Tin) of tokens [B, Tin]."""
+        shape = _dims(tokens)
+        if len(shape) != 2:
+            raise ValueError(f'tokens must be [B, Tin], got {shape}')
+        return shape
 
     @staticmethod
     def _check_masks(masks, B, T, axis):
-        """Converted prenet masks (or None) must be [B, T, 2, 256]; `axis` names T in the message.  -> masks"""
-        if masks is not None and tuple(masks.shape) != (B, T, 2, 256):
-            raise ValueError(f'prenet_masks must be [B, {axis}, 2, 256] = {(B, T, 2, 256)}, got {tuple(masks.shape)}')
-        return masks
+        """Prenet masks (or None) must be [B, T, 2, 256]; `axis` names T in the message."""
+        if masks is not None and _dims(masks) != (B, T, 2, 256):
+            raise ValueError(f'prenet_masks must be [B, {axis}, 2, 256] = {(B, T, 2, 256)}, got {_dims(masks)}')
 
-    def _taco_outputs(self, dev, B, T, Tin, want_attention=True, want_lengths=True):
-        """Zero-filled (mel [B, T, 80], dec [B, T, 80], stop [B, T], attn [B, T, Tin] | None, lengths int32 [B] | None): tensors on
-        this engine's GPU (dev) or host arrays."""
-        if dev:
-            torch = self._torch()
-            mk = lambda shape, dt='float32': torch.zeros(shape, dtype=getattr(torch, dt), device=torch.device('cuda', self.device))
-        else:
-            mk = lambda shape, dt='float32': np.zeros(shape, dtype=dt)
-        return (mk((B, T, 80)), mk((B, T, 80)), mk((B, T)), mk((B, T, Tin)) if want_attention else None,
-                mk((B,), 'int32') if want_lengths else None)
-
-    def _taco_staged(self, dev, stream, prepare, *inputs):
-        """`_staged` for a Tacotron2 call -> (what `prepare()` returned, the mem kind, the stream's pointer or None).  Host arrays
-        (not dev) are prepared as they are: nothing of torch's is waited for, and there is no stream to run on."""
-        if not dev:
-            if stream is not None:
-                raise ValueError('stream= needs device tensors')
-            return prepare(), MEM_HOST, None
-        tensors, sp = self._staged(stream, prepare, *inputs)
-        return tensors, MEM_DEVICE, sp
+    @staticmethod
+    def _taco_outputs(new, B, T, Tin, want_attention=True, want_lengths=True):
+        """Zero-filled (mel [B, T, 80], dec [B, T, 80], stop [B, T], attn [B, T, Tin] | None, lengths int32 [B] | None)."""
+        return (new((B, T, 80), zeros=True), new((B, T, 80), zeros=True), new((B, T), zeros=True),
+                new((B, T, Tin), zeros=True) if want_attention else None, new((B,), 'int32', zeros=True) if want_lengths else None)
 
     def tacotron2_infer(self, tokens, speaker=None, max_len: int = 1000, early_stopping: bool = True,
                         prenet_masks=None, attn_mask_win_len=None, attn_mask_offset: int = 0, want_attention=True,
@@ -538,25 +532,18 @@ class HipEngine:
             finally:
                 enc.close()
         win_len, win_off = attention_window(attn_mask_win_len, attn_mask_offset)
-        dev = _is_torch_cuda(tokens)
-        self._check_device(tokens)
         max_len = int(max_len)
         if max_len <= 0:
             raise ValueError('max_len must be positive')
-
-        def prepare():
-            tok = self._tokens(tokens, dev)
-            B, Tin = int(tok.shape[0]), int(tok.shape[1])
-            masks = self._check_masks(self._f32(prenet_masks, dev), B, max_len, 'max_len')
-            return (tok, self._f32(speaker, dev), masks, *self._taco_outputs(dev, B, max_len, Tin, want_attention))
-
-        (tok, spk, masks, mel, dec, stop, attn, lengths), mem, _ = self._taco_staged(dev, None, prepare)
+        B, Tin = self._token_dims(tokens)
+        self._check_masks(prenet_masks, B, max_len, 'max_len')
         steps = ctypes.c_int32(0)
-        name = 'tacotron2_infer' + ('_f16' if pcode else '')               # one symbol per precision
-        self._check(getattr(self._lib, 'tts_hip_' + name)(
-            self._h, self._ptr(tok), int(tok.shape[0]), int(tok.shape[1]), self._ptr(spk), max_len, 1 if early_stopping else 0,
-            self._ptr(masks), win_len, win_off, *map(self._ptr, (mel, dec, stop, attn, lengths)),
-            ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), mem), 'tacotron2_infer')
+        mel, dec, stop, attn, lengths = self._call(
+            'tacotron2_infer' + ('_f16' if pcode else ''),                 # one symbol per precision
+            [(tokens, None, 'int32'), (speaker, None, 'float32'), (prenet_masks, None, 'float32')],
+            lambda new: self._taco_outputs(new, B, max_len, Tin, want_attention),
+            lambda ins, outs, where: (ins[0], B, Tin, ins[1], max_len, 1 if early_stopping else 0, ins[2], win_len, win_off, *outs,
+                                      ctypes.cast(ctypes.byref(steps), ctypes.c_void_p)))
         self.last_steps = int(steps.value)
         return Tacotron2InferenceOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn, lengths=lengths)
 
@@ -566,22 +553,23 @@ class HipEngine:
         the encoder is only enqueued (on `stream`, a torch.cuda.Stream, or on the engine's own stream).  `into`: an
         `EncodedBatch` of this engine to overwrite (tts_hip_tacotron2_reencode: no allocation, the decoder's cached graphs
         stay valid); it is returned."""
-        dev = _is_torch_cuda(tokens)
-        self._check_device(tokens, speaker)
-        (tok, spk), mem, sp = self._taco_staged(dev, stream, lambda: (self._tokens(tokens, dev), self._f32(speaker, dev)),
-                                                tokens, speaker)
-        B, Tin = int(tok.shape[0]), int(tok.shape[1])
-        if into is not None:
-            if into.engine is not self or into.handle is None:
-                raise ValueError('`into` belongs to another engine or was freed')
-            self._check(self._lib.tts_hip_tacotron2_reencode(self._h, into.handle, self._ptr(tok), B, Tin, self._ptr(spk), mem, sp),
-                        'tacotron2_reencode')
-            into.B, into.Tin, into.on_device, into._keep = B, Tin, dev, (tok, spk)
-            return into
-        h = ctypes.c_void_p()
-        self._check(self._lib.tts_hip_tacotron2_encode(self._h, self._ptr(tok), B, Tin, self._ptr(spk), mem, sp, ctypes.byref(h)),
-                    'tacotron2_encode')
-        return EncodedBatch(self, h, B, Tin, keep=(tok, spk), on_device=dev)
+        B, Tin = self._token_dims(tokens)
+        if into is not None and (into.engine is not self or into.handle is None):
+            raise ValueError('`into` belongs to another engine or was freed')
+        h, keep = ctypes.c_void_p(), []
+
+        def args(ins, outs, where):
+            keep.extend(ins)
+            if into is not None:
+                return (into.handle, ins[0], B, Tin, ins[1], *where)
+            return (ins[0], B, Tin, ins[1], *where, ctypes.byref(h))
+
+        self._call('tacotron2_encode' if into is None else 'tacotron2_reencode', [(tokens, None, 'int32'), (speaker, None, 'float32')],
+                   lambda new: (), args, stream, twin=False)
+        if into is None:
+            return EncodedBatch(self, h, B, Tin, keep=tuple(keep), on_device=_is_torch_cuda(tokens))
+        into.B, into.Tin, into.on_device, into._keep = B, Tin, _is_torch_cuda(tokens), tuple(keep)
+        return into
 
     def tacotron2_decode(self, encoded, max_len: int = 1000, early_stopping: bool = True, prenet_masks=None,
                          attn_mask_win_len=None, attn_mask_offset: int = 0, want_attention=True, precision: str = 'f32',
@@ -605,20 +593,15 @@ class HipEngine:
         max_len = int(max_len)
         if max_len <= 0:
             raise ValueError('max_len must be positive')
-        self._check_device(prenet_masks)
-
-        def prepare():
-            return (self._check_masks(self._f32(prenet_masks, dev), B, max_len, 'max_len'),
-                    *self._taco_outputs(dev, B, max_len, Tin, want_attention))
-
-        (masks, mel, dec, stop, attn, lengths), mem, sp = self._taco_staged(dev, stream if dev else None, prepare, prenet_masks)
+        self._check_masks(prenet_masks, B, max_len, 'max_len')
         steps = ctypes.c_int32(0)
         name, mid = self._TACO_DECODE[source]
-        self._check(getattr(self._lib, 'tts_hip_' + name)(
-            self._h, encoded.handle, max_len, 1 if early_stopping else 0,
-            *mid(self._ptr, {'tensor': masks, 'seed': mask_seed, 'rows': row_tables}[source]),
-            win_len, win_off, pcode, *map(self._ptr, (mel, dec, stop, attn, lengths)),
-            ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), mem, sp), name)
+        mel, dec, stop, attn, lengths = self._call(
+            name, [(prenet_masks, None, 'float32')], lambda new: self._taco_outputs(new, B, max_len, Tin, want_attention),
+            lambda ins, outs, where: (encoded.handle, max_len, 1 if early_stopping else 0,
+                                      *mid({'tensor': ins[0], 'seed': mask_seed, 'rows': row_tables}[source]),
+                                      win_len, win_off, pcode, *outs, ctypes.cast(ctypes.byref(steps), ctypes.c_void_p), *where),
+            stream if dev else None, device=dev, twin=False)
         self.last_steps = int(steps.value)
         return Tacotron2InferenceOutput(decoder_output=dec, mel=mel, stop_tokens=stop, attention_weights=attn, lengths=lengths)
 
@@ -652,27 +635,20 @@ class HipEngine:
             self._check_encoded(encoded)
         try:
             B, Tin = encoded.B, encoded.Tin
-            if len(mel_input.shape) != 3 or int(mel_input.shape[0]) != B or int(mel_input.shape[2]) != 80:
-                raise ValueError(f'mel_input must be [B = {B}, T, 80], got {tuple(mel_input.shape)}')
-            T = int(mel_input.shape[1])
-            lens = np.full((B,), T, np.int32) if mel_lengths is None else np.ascontiguousarray(
-                mel_lengths.detach().cpu().numpy() if hasattr(mel_lengths, 'detach') else mel_lengths, dtype=np.int32)
-            if lens.shape != (B,):
-                raise ValueError(f'mel_lengths must be [B = {B}], got {lens.shape}')
+            shape = _dims(mel_input)
+            if len(shape) != 3 or shape[0] != B or shape[2] != 80:
+                raise ValueError(f'mel_input must be [B = {B}, T, 80], got {shape}')
+            T = shape[1]
+            lens = np.full((B,), T, np.int32) if mel_lengths is None else self._row_table(mel_lengths, B, *_INT32, '', 'mel_lengths')
             if seed is not None:
                 prenet_masks = self.random_prenet_masks(B, T, seed, offset, stream=stream)
                 if not dev:
                     prenet_masks = prenet_masks.cpu().numpy()
-            self._check_device(mel_input, prenet_masks)
-
-            def prepare():
-                return (self._f32(mel_input, dev), self._check_masks(self._f32(prenet_masks, dev), B, T, 'T'),
-                        *self._taco_outputs(dev, B, T, Tin, want_lengths=False))
-
-            (x, m, mel, dec, stop, attn, _), mem, sp = self._taco_staged(dev, stream, prepare, mel_input, prenet_masks)
-            self._check(self._lib.tts_hip_tacotron2_forward(
-                self._h, encoded.handle, self._ptr(x), T, self._ptr(lens), self._ptr(m), pcode,
-                *map(self._ptr, (mel, dec, stop, attn)), mem, sp), 'tacotron2_forward')
+            self._check_masks(prenet_masks, B, T, 'T')
+            mel, dec, stop, attn, _ = self._call(
+                'tacotron2_forward', [(mel_input, None, 'float32'), (prenet_masks, None, 'float32')],
+                lambda new: self._taco_outputs(new, B, T, Tin, want_lengths=False),
+                lambda ins, outs, where: (encoded.handle, ins[0], T, lens, ins[1], pcode, *outs[:4], *where), stream, twin=False)
         finally:
             if own:
                 encoded.close()
@@ -692,31 +668,18 @@ class HipEngine:
         from .losses import MEL_LOSS_KINDS, mel_loss_kinds
         kinds = np.asarray([MEL_LOSS_KINDS[k] for k in mel_loss_kinds(mel_loss)], dtype=np.int32)
         inputs = (mel_target, gate_target, decoder_output, mel, stop_tokens)
-        dev = any(_is_torch_cuda(x) for x in inputs)
-        self._check_device(*inputs)
-        shape = tuple(int(n) for n in mel_target.shape)
+        shape = _dims(mel_target)
         if len(shape) != 3 or shape[2] != 80:
             raise ValueError(f'mel_target must be [B, T, 80], got {shape}')
         B, T = shape[:2]
         for name, x, want in (('gate_target', gate_target, (B, T)), ('decoder_output', decoder_output, shape), ('mel', mel, shape),
                               ('stop_tokens', stop_tokens, (B, T))):
-            if tuple(int(n) for n in x.shape) != want:
-                raise ValueError(f'{name} must be {want} beside mel_target {shape}, got {tuple(x.shape)}')
-
-        def prepare():
-            if not dev:
-                return (*(self._f32(x, False) for x in inputs), np.empty((len(kinds) * 2 + 2, B), dtype=np.float32))
-            torch = self._torch()
-            gpu = torch.device('cuda', self.device)
-            xs = [self._f32(x if _is_torch_cuda(x) else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)), True)
-                  for x in inputs]
-            return (*xs, torch.empty((len(kinds) * 2 + 2, B), dtype=torch.float32, device=gpu))
-
-        (y, g, d, m, s, out), mem, sp = self._taco_staged(dev, stream, prepare, *(x for x in inputs if _is_torch_cuda(x)))
-        self._check(self._lib.tts_hip_tacotron2_loss(
-            self._h, *map(self._ptr, (y, g, d, m, s)), B, T, self._ptr(kinds), len(kinds), 1 if mask_mel_padding else 0,
-            1 if from_logits else 0, float(finish_weight), float(not_finish_weight), self._ptr(out), mem, sp), 'tacotron2_loss')
-        return out
+            if _dims(x) != want:
+                raise ValueError(f'{name} must be {want} beside mel_target {shape}, got {_dims(x)}')
+        return self._call('tacotron2_loss', [(x, None, 'float32') for x in inputs], lambda new: (new((len(kinds) * 2 + 2, B)),),
+                          lambda ins, outs, where: (*ins, B, T, kinds, len(kinds), 1 if mask_mel_padding else 0, 1 if from_logits else 0,
+                                                    float(finish_weight), float(not_finish_weight), outs[0], *where),
+                          stream, device=any(_is_torch_cuda(x) for x in inputs), twin=False)[0]
 
     def set_decoder_mode(self, mode: str) -> None:
         """How the autoregressive decoder loop runs: 'auto' (default: the persistent weight-stationary kernel for 1 - 2 rows,
@@ -739,13 +702,11 @@ class HipEngine:
         whats = {'conv1': 0, 'conv2': 1, 'conv3': 2, 'memory': 3, 'processed_memory': 4}
         if what not in whats:
             raise ValueError(f'what must be one of {tuple(whats)}, got {what!r}')
-        tok, spk = self._tokens(tokens, False), self._f32(speaker, False)
-        B, Tin = tok.shape
-        width = 512 if whats[what] <= 2 else 128 if what == 'processed_memory' else 512 + (0 if spk is None else spk.shape[1])
-        out = np.empty((B, Tin, width), dtype=np.float32)
-        self._check(self._lib.tts_hip_tacotron2_probe_encoder(
-            self._h, self._ptr(tok), B, Tin, self._ptr(spk), whats[what], self._ptr(out), MEM_HOST), 'tacotron2_probe_encoder')
-        return out
+        B, Tin = self._token_dims(tokens)
+        width = 512 if whats[what] <= 2 else 128 if what == 'processed_memory' else 512 + (0 if speaker is None else _dims(speaker)[1])
+        return self._call('tacotron2_probe_encoder', [(tokens, None, 'int32'), (speaker, None, 'float32')],
+                          lambda new: (new((B, Tin, width)),),
+                          lambda ins, outs, where: (ins[0], B, Tin, ins[1], whats[what], outs[0]))[0]
 
     def tacotron2_probe_postnet(self, frames, lengths, what: str = 'mel'):
         """Test hook (tts_hip_tacotron2_probe_postnet): run the postnet of `tacotron2_infer` on frames [B, T, 80] in place of
@@ -755,17 +716,14 @@ class HipEngine:
         whats = {'conv1': 0, 'conv2': 1, 'conv3': 2, 'conv4': 3, 'conv5': 4, 'mel': 5}
         if what not in whats:
             raise ValueError(f'what must be one of {tuple(whats)}, got {what!r}')
-        x = self._f32(frames, False)
-        if x.ndim != 3 or x.shape[2] != 80:
-            raise ValueError(f'frames must be [B, T, 80], got {x.shape}')
-        B, T = x.shape[:2]
-        lens = np.ascontiguousarray(lengths, dtype=np.int32)
-        if lens.shape != (B,):
-            raise ValueError(f'lengths must be [B] = ({B},), got {lens.shape}')
-        out = np.empty((B, T, 512 if whats[what] <= 3 else 80), dtype=np.float32)
-        self._check(self._lib.tts_hip_tacotron2_probe_postnet(
-            self._h, self._ptr(x), B, T, self._ptr(lens), whats[what], self._ptr(out), MEM_HOST), 'tacotron2_probe_postnet')
-        return out
+        shape = _dims(frames)
+        if len(shape) != 3 or shape[2] != 80:
+            raise ValueError(f'frames must be [B, T, 80], got {shape}')
+        B, T = shape[:2]
+        lens = self._row_table(lengths, B, *_INT32, '', 'lengths')
+        return self._call('tacotron2_probe_postnet', [(frames, None, 'float32')],
+                          lambda new: (new((B, T, 512 if whats[what] <= 3 else 80)),),
+                          lambda ins, outs, where: (ins[0], B, T, lens, whats[what], outs[0]))[0]
 
     def tacotron2_postnet(self, frames, lengths):
         """Postnet + residual of `tacotron2_infer` on decoder frames [B, T, 80] whose rows end at index lengths[b] (mask
@@ -779,130 +737,21 @@ class HipEngine:
         split per tap; bits 0 - 2 encoder convs 1 - 3, bits 3 - 7 postnet convs 1 - 5; -1 before the first conv."""
         return int(self._lib.tts_hip_last_conv_paths(self._h))
 
-    def set_waveglow_form(self, form: str) -> None:
-        """How the fp32 vocoder evaluates the dilated convolutions of WN layers 1 - 7: 'winograd' (default: minimal filtering
-        along the tap axis, F(4,3), for calls of 144 frames or more) or 'direct' (always three taps).  Both are fp32; they differ by rounding only.
-        The Winograd form exists for 512-channel models: with a 256-channel one (`waveglow_channels`) the call is accepted and
-        every fp32 call still takes the direct form."""
-        # 'winograd-3pass' / 'winograd-prepass': the two earlier stages of the Winograd form (pre-pass + per-product GEMM + combine
-        # pass; fused GEMM behind the pre-pass), kept for measurement and as bit-identical cross-checks of the default kernel
-        forms = {'direct': 0, 'winograd': 1, 'winograd-3pass': 2, 'winograd-prepass': 3}
-        if form not in forms:
-            raise ValueError(f'form must be one of {tuple(forms)}, got {form!r}')
-        self._check(self._lib.tts_hip_set_waveglow_form(self._h, forms[form]), 'set_waveglow_form')
-
-    @property
-    def last_waveglow_form(self) -> str:
-        """'winograd' or 'direct' for the last `waveglow_infer` call on this handle ('none' before the first)."""
-        return {1: 'winograd', 0: 'direct'}.get(self._lib.tts_hip_last_waveglow_form(self._h), 'none')
-
-    @property
-    def waveglow_channels(self) -> int:
-        """n_channels of this handle's WaveGlow (tts_hip_waveglow_channels): 512 or 256, fixed by the tensors present at
-        `finalize`; 0 while no WaveGlow is finalized."""
-        return int(self._lib.tts_hip_waveglow_channels(self._h))
-
-    @property
-    def last_waveglow_tiles(self) -> str:
-        """WN GEMM tile family of the last `waveglow_infer` (or probe) call: '64-row', '128x64', '128-row' or '256-row'
-        ('none' before the first)."""
-        return {3: '64-row', 2: '128x64', 1: '128-row', 0: '256-row'}.get(self._lib.tts_hip_last_waveglow_tiles(self._h), 'none')
-
-    def waveglow_probe(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', flow: int = 11, what: str = 'acts',
-                       layer: int = 0):
-        """Test hook (tts_hip_waveglow_probe): run `waveglow_infer` in `precision` up to flow `flow` and return either the gated
-        activations [B, T*32, C] (C = `waveglow_channels`) of its WN layer `layer` (what='acts') or the flow state [B, T*32, n] right after the flow,
-        early output included (what='state'; the reference's audio after that flow), or the conditioning plane [B, T*32, 1024]
-        of that layer -- sum_q V_q mel[t - q] + b, columns in the gate-interleaved order of the engine's weights -- that the
-        fp32 Winograd form builds (what='cond'; layers 1 - 7 of calls of 144 frames or more, 512-channel models only)."""
-        precs = {'f32': 0, 'f16': 1, 'f16x3': 2}
-        whats = {'acts': 0, 'state': 1, 'cond': 2}
-        if precision not in precs or what not in whats:
-            raise ValueError(f'precision must be one of {tuple(precs)} and what one of {tuple(whats)}')
-        mel = np.ascontiguousarray(mel, dtype=np.float32)
-        if mel.ndim != 3 or mel.shape[2] != 80:
-            raise ValueError(f'mel must be [B, T, 80], got {mel.shape}')
-        B, T = mel.shape[:2]
-        zp = None
-        if z is not None:
-            z = np.ascontiguousarray(z, dtype=np.float32)
-            if z.shape != (B, T * 32, 8):
-                raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {z.shape}')
-            zp = z.ctypes.data_as(ctypes.c_void_p)
-        C = self.waveglow_channels
-        width = C if what == 'acts' else 2 * C if what == 'cond' else (4 if flow >= 8 else 6 if flow >= 4 else 8) + (2 if flow in (4, 8) else 0)
-        out = np.empty((B, T * 32, width), dtype=np.float32)
-        self._check(self._lib.tts_hip_waveglow_probe(
-            self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, zp, float(sigma), precs[precision], int(flow), whats[what],
-            int(layer), out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'waveglow_probe')
-        return out
-
-    def waveglow_probe_acts(self, mel, z=None, sigma: float = 1.0, flow: int = 11, layer: int = 1):
-        """Test hook (tts_hip_waveglow_probe_acts): the gated activations [B, T*32, C] (C = `waveglow_channels`) of WN layer `layer` of flow `flow` on
-        the fp32 path, in the form `set_waveglow_form` selects -- the values before the res/skip and `end` convolutions."""
-        mel = np.ascontiguousarray(mel, dtype=np.float32)
-        if mel.ndim != 3 or mel.shape[2] != 80:
-            raise ValueError(f'mel must be [B, T, 80], got {mel.shape}')
-        B, T = mel.shape[:2]
-        zp = None
-        if z is not None:
-            z = np.ascontiguousarray(z, dtype=np.float32)
-            if z.shape != (B, T * 32, 8):
-                raise ValueError(f'z must be [B, T*32, 8] = {(B, T * 32, 8)}, got {z.shape}')
-            zp = z.ctypes.data_as(ctypes.c_void_p)
-        out = np.empty((B, T * 32, self.waveglow_channels), dtype=np.float32)
-        self._check(self._lib.tts_hip_waveglow_probe_acts(
-            self._h, mel.ctypes.data_as(ctypes.c_void_p), B, T, zp, float(sigma), int(flow), int(layer),
-            out.ctypes.data_as(ctypes.c_void_p), MEM_HOST), 'waveglow_probe_acts')
-        return out
-
     # ------------------------------------------------------------------ audio calls on rows
-    def _host_call(self, name, audio, B, N, extra_inputs, make_outputs, args):
-        """tts_hip_<name> on host arrays.  `audio` becomes a contiguous float32 [B, N]; each of `extra_inputs`, (array or None,
-        shape), a contiguous float32 array of that shape or None; `make_outputs(empty)` allocates the outputs with
-        empty(shape, dtype name) and returns them as a tuple; `args(extras, outs)` returns, with every array already turned
-        into its pointer, what the C function takes between (handle, audio, B, N) and the trailing mem kind.  -> the outputs."""
-        def host(x, shape):
-            if x is None:
-                return None
-            x = x.detach().cpu() if hasattr(x, 'detach') else x
-            return np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(shape))
+    def _audio_rows(self, audio, lengths, what):
+        """(B, N, int32 lengths or None) of a [N] / [B, N] input; every length in [1, N].  Raises before any GPU call."""
+        shape = self._batched(audio, 2)
+        if shape is None:
+            raise ValueError(f'{what}: audio must be [N] or [B, N], got shape {_dims(audio)}')
+        B, N = shape
+        if B < 1 or N < 1:
+            raise ValueError(f'{what}: empty audio {_dims(audio)}')
+        return B, N, None if lengths is None else self._row_table(lengths, B, 1, N, what, 'lengths')
 
-        a = host(audio, (B, N))
-        extras = [host(x, shape) for x, shape in extra_inputs]
-        outs = make_outputs(lambda shape, dtype: np.empty(shape, dtype=dtype))
-        self._check(getattr(self._lib, 'tts_hip_' + name)(self._h, self._ptr(a), B, N,
-                                                          *args([self._ptr(x) for x in extras], [self._ptr(o) for o in outs]),
-                                                          MEM_HOST), name)
-        return outs
-
-    def _rows_call(self, name, audio, B, N, extra_inputs, make_outputs, args, stream):
-        """tts_hip_<name> on numpy-like input (`_host_call`; numpy outputs) or on a CUDA tensor (CUDA outputs): there the same
-        conversions and allocations happen on the device, the call takes TTS_HIP_MEM_DEVICE, or, with `stream`
-        (torch.cuda.Stream, device tensors only), tts_hip_<name>_async is enqueued there and the call returns without waiting
-        (`_staged`).  Arguments as `_host_call`'s."""
-        if not _is_torch_cuda(audio):
-            if stream is not None:
-                raise ValueError('stream= needs device tensors')
-            return self._host_call(name, audio, B, N, extra_inputs, make_outputs, args)
-        torch = self._torch()
-        extra_inputs = [(torch.as_tensor(np.asarray(x, np.float32), device=audio.device)
-                         if x is not None and not _is_torch_cuda(x) else x, shape) for x, shape in extra_inputs]
-        self._check_device(audio, *(x for x, _ in extra_inputs))
-
-        def prepared():
-            a_ = audio.to(torch.float32).reshape(B, N).contiguous()
-            extras = [x.to(torch.float32).reshape(shape).contiguous() if x is not None else None for x, shape in extra_inputs]
-            outs = make_outputs(lambda shape, dtype: torch.empty(shape, dtype=getattr(torch, dtype), device=a_.device))
-            return (a_, *extras, *outs)
-
-        tensors, sp = self._staged(stream, prepared, audio)
-        extras, outs = tensors[1:1 + len(extra_inputs)], tensors[1 + len(extra_inputs):]
-        fn, last = (name, MEM_DEVICE) if stream is None else (name + '_async', sp)
-        self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, self._ptr(tensors[0]), B, N,
-                                                        *args([self._ptr(x) for x in extras], [self._ptr(o) for o in outs]),
-                                                        last), fn)
-        return outs
+    def _audio_call(self, name, audio, B, N, make_outputs, args, stream=None, extra=()):
+        """`_call` for an entry point that begins (handle, audio [B, N], B, N, ...): `args(extras, outs)` returns the rest."""
+        return self._call(name, [(audio, (B, N), 'float32'), *extra], make_outputs,
+                          lambda ins, outs, where: (ins[0], B, N, *args(ins[1:], outs)), stream)
 
     # ------------------------------------------------------------------ mel-STFT
     def mel_stft(self, audio, stream=None):
@@ -921,8 +770,7 @@ class HipEngine:
             if a.shape[1] < 1024:                     # MelSTFT.__call__ pads short audio (utils/audio/stft.py:113-115)
                 a = np.pad(a, [(0, 0), (0, 1024 - a.shape[1])])
         B, N = int(a.shape[0]), int(a.shape[1])
-        return self._rows_call('mel_stft', a, B, N, [], lambda empty: (empty((B, N // 256 + 1, 80), 'float32'),),
-                               lambda extras, outs: (outs[0],), stream)[0]
+        return self._audio_call('mel_stft', a, B, N, lambda new: (new((B, N // 256 + 1, 80)),), lambda extras, outs: (outs[0],), stream)[0]
 
     _STFT_STAGES = {'padded': 0, 'spectrum': 1, 'magnitude': 2, 'mel_linear': 3}
 
@@ -933,15 +781,13 @@ class HipEngine:
         [B, F, 513], 'mel_linear' [B, F, 80] (before log(max(., 1e-5)))."""
         if what not in self._STFT_STAGES:
             raise ValueError(f'what must be one of {tuple(self._STFT_STAGES)}, got {what!r}')
-        a = np.asarray(audio, dtype=np.float32)
-        if a.ndim == 1:
-            a = a[None]
-        if a.ndim != 2:
-            raise ValueError(f'audio must be [N] or [B, N], got {a.shape}')
-        B, N = a.shape
+        shape = self._batched(audio, 2)
+        if shape is None:
+            raise ValueError(f'audio must be [N] or [B, N], got {_dims(audio)}')
+        B, N = shape
         F = N // 256 + 1
         shape = {'padded': (B, N + 1024), 'spectrum': (B, F, 1026), 'magnitude': (B, F, 513), 'mel_linear': (B, F, 80)}[what]
-        return self._host_call('mel_stft_probe', a, B, N, [], lambda empty: (empty(shape, 'float32'),),
+        return self._audio_call('mel_stft_probe', audio, B, N, lambda new: (new(shape),),
                                lambda extras, outs: (self._STFT_STAGES[what], outs[0]))[0]
 
     # ------------------------------------------------------------------ mel plans (any TacotronSTFT configuration, WhisperSTFT)
@@ -990,8 +836,8 @@ class HipEngine:
         one workspace: the next mel call must be ordered after it)."""
         B, N, lens = self._audio_rows(audio, lengths, 'mel_fn_run')
         F = self.mel_fn_frames(plan, N)
-        return self._rows_call('mel_fn_run', audio, B, N, [], lambda empty: (empty((B, F, plan.n_mel), 'float32'),),
-                               lambda extras, outs: (self._ptr(lens), plan.handle, outs[0]), stream)[0]
+        return self._audio_call('mel_fn_run', audio, B, N, lambda new: (new((B, F, plan.n_mel)),),
+                               lambda extras, outs: (lens, plan.handle, outs[0]), stream)[0]
 
     def mel_fn_probe(self, plan, audio, what: str = 'spectrum', lengths=None):
         """Test hook (tts_hip_mel_fn_probe): run `mel_fn_run` on the same arguments (host arrays) up to a stage and return
@@ -1008,61 +854,10 @@ class HipEngine:
         C = g['filter_length'] // 2 + 1
         shape = {'padded': (B, max(N, g['win_length']) + 2 * (g['filter_length'] // 2)), 'spectrum': (B, Fr, 2 * C),
                  'magnitude': (B, Fr, C), 'mel_linear': (B, Fr, plan.n_mel), 'mel_log': (B, F, plan.n_mel)}[what]
-        return self._host_call('mel_fn_probe', audio, B, N, [], lambda empty: (empty(shape, 'float32'),),
-                               lambda extras, outs: (self._ptr(lens), plan.handle, self._MEL_FN_STAGES[what], outs[0]))[0]
+        return self._audio_call('mel_fn_probe', audio, B, N, lambda new: (new(shape),),
+                               lambda extras, outs: (lens, plan.handle, self._MEL_FN_STAGES[what], outs[0]))[0]
 
     # ------------------------------------------------------------------ STFT with phase, inverse, Griffin-Lim (csrc/stft_inv.hip)
-    def _planes_call(self, name, inputs, make_outputs, args, stream=None):
-        """tts_hip_<name> on arrays of any rank.  `inputs`: (array or None, shape) pairs, the first one never None; all numpy-like
-        -> host call and numpy outputs, the first a CUDA tensor -> device call and CUDA outputs (`stream`: tts_hip_<name>_async
-        enqueued there, `_staged`).  `make_outputs(empty)` as `_host_call`'s; `args(ins, outs)` returns, with every array
-        turned into its pointer, everything the C function takes between the handle and the trailing mem kind / stream."""
-        first = inputs[0][0]
-        if not _is_torch_cuda(first):
-            if stream is not None:
-                raise ValueError('stream= needs device tensors')
-
-            def host(x, shape):
-                if x is None:
-                    return None
-                x = x.detach().cpu() if hasattr(x, 'detach') else x
-                return np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(shape))
-
-            ins = [host(x, shape) for x, shape in inputs]
-            outs = make_outputs(lambda shape, dtype: np.empty(shape, dtype=dtype))
-            self._check(getattr(self._lib, 'tts_hip_' + name)(self._h, *args([self._ptr(x) for x in ins], [self._ptr(o) for o in outs]),
-                                                              MEM_HOST), name)
-            return outs
-        torch = self._torch()
-        inputs = [(torch.as_tensor(np.asarray(x, np.float32), device=first.device) if x is not None and not _is_torch_cuda(x) else x,
-                   shape) for x, shape in inputs]
-        self._check_device(*(x for x, _ in inputs))
-
-        def prepared():
-            ins = [x.to(torch.float32).reshape(shape).contiguous() if x is not None else None for x, shape in inputs]
-            outs = make_outputs(lambda shape, dtype: torch.empty(shape, dtype=getattr(torch, dtype), device=first.device))
-            return (*ins, *outs)
-
-        tensors, sp = self._staged(stream, prepared, *(x for x, _ in inputs))
-        ins, outs = tensors[:len(inputs)], tensors[len(inputs):]
-        fn, last = (name, MEM_DEVICE) if stream is None else (name + '_async', sp)
-        self._check(getattr(self._lib, 'tts_hip_' + fn)(self._h, *args([self._ptr(x) for x in ins], [self._ptr(o) for o in outs]), last), fn)
-        return outs
-
-    @staticmethod
-    def _frame_counts(frames, B, F, what):
-        """int32 [B] frame counts in [1, F] (None: None).  Raises before any GPU call."""
-        if frames is None:
-            return None
-        if hasattr(frames, 'detach'):
-            frames = frames.detach().cpu().numpy()
-        fr = np.ascontiguousarray(np.atleast_1d(np.asarray(frames)).astype(np.int64))
-        if fr.shape != (B,):
-            raise ValueError(f'{what}: frames must have shape ({B},), got {fr.shape}')
-        if fr.min() < 1 or fr.max() > F:
-            raise ValueError(f'{what}: frames must lie in [1, {F}]')
-        return fr.astype(np.int32)
-
     def mel_fn_samples(self, plan, frames):
         """Samples `frames` frames overlap-add to under `plan`: hop * (frames - 1) + filter_length - 2 * (filter_length // 2)."""
         n = self._lib.tts_hip_mel_fn_samples(plan.handle, int(frames))
@@ -1078,47 +873,47 @@ class HipEngine:
         B, N, lens = self._audio_rows(audio, lengths, 'stft_transform')
         F = self.mel_fn_frames(plan, N)
         C = plan.geometry['filter_length'] // 2 + 1
-        outs = self._planes_call('stft_transform', [(audio, (B, N))],
-                                 lambda empty: (empty((B, F, C), 'float32'), empty((B, F, C), 'float32')),
-                                 lambda ins, outs: (ins[0], B, N, self._ptr(lens), plan.handle, 0 if polar else 1, outs[0], outs[1]))
-        return outs[0], outs[1]
+        return self._audio_call('stft_transform', audio, B, N, lambda new: (new((B, F, C)), new((B, F, C))),
+                               lambda extras, outs: (lens, plan.handle, 0 if polar else 1, outs[0], outs[1]))
+
+    def _planes(self, x, frames, what, name):
+        """(B, F, C, int32 frame counts in [1, F] or None) of `x`, [F, C] or [B, F, C]."""
+        shape = self._batched(x, 3)
+        if shape is None:
+            raise ValueError(f'{what}: {name} must be [F, C] or [B, F, C], got {_dims(x)}')
+        B, F, C = shape
+        return B, F, C, None if frames is None else self._row_table(frames, B, 1, F, what, 'frames')
 
     def stft_inverse(self, plan, plane0, plane1, frames=None, polar=True):
         """Two planes [F, C] or [B, F, C] (C = filter_length // 2 + 1; magnitude and phase, or with polar=False real and imaginary
         parts) -> audio [B, F * hop_length]: row b holds mel_fn_samples(plan, frames[b]) samples (default F frames), zeros
         beyond; nothing behind a row's frames is read."""
-        shape = tuple(plane0.shape)
-        if len(shape) not in (2, 3) or tuple(plane1.shape) != shape:
-            raise ValueError(f'stft_inverse: planes must both be [F, C] or [B, F, C], got {shape} and {tuple(plane1.shape)}')
-        B, F, C = (1, *shape) if len(shape) == 2 else shape
-        B, F, C = int(B), int(F), int(C)
+        if _dims(plane1) != _dims(plane0):
+            raise ValueError(f'stft_inverse: planes must both be [F, C] or [B, F, C], got {_dims(plane0)} and {_dims(plane1)}')
+        B, F, C, fr = self._planes(plane0, frames, 'stft_inverse', 'planes')
         if C != plan.geometry['filter_length'] // 2 + 1:
             raise ValueError(f"stft_inverse: {C} bins, the plan has {plan.geometry['filter_length'] // 2 + 1}")
-        fr = self._frame_counts(frames, B, F, 'stft_inverse')
-        hop = plan.geometry['hop_length']
-        return self._planes_call('stft_inverse', [(plane0, (B, F, C)), (plane1, (B, F, C))],
-                                 lambda empty: (empty((B, F * hop), 'float32'),),
-                                 lambda ins, outs: (ins[0], B, F, ins[1], self._ptr(fr), plan.handle, 0 if polar else 1, outs[0]))[0]
+        return self._call('stft_inverse', [(plane0, (B, F, C), 'float32'), (plane1, (B, F, C), 'float32')],
+                          lambda new: (new((B, F * plan.geometry['hop_length'])),),
+                          lambda ins, outs, where: (ins[0], B, F, ins[1], fr, plan.handle, 0 if polar else 1, outs[0]))[0]
 
     _GL_KINDS = {'magnitude': 0, 'log_mel': 1}
     _GL_STAGES = {'target': 0, 'operand': 1, 'frames': 2, 'signal': 3, 'spectrum': 4, 'phasor': 5}
 
-    def _gl_args(self, plan, spec, frames, kind, mel_inverse, init, what):
+    def _griffin_lim(self, name, plan, spec, frames, kind, n_iters, momentum, init, mel_inverse, shape, tail=(), stream=None):
+        """tts_hip_griffin_lim or its probe (`tail`: the probe's iteration and stage) -> one output of `shape(B, F, bins)`."""
         if kind not in self._GL_KINDS:
-            raise ValueError(f'{what}: kind must be one of {tuple(self._GL_KINDS)}, got {kind!r}')
-        shape = tuple(spec.shape)
-        if len(shape) not in (2, 3):
-            raise ValueError(f'{what}: spec must be [F, C] or [B, F, C], got {shape}')
-        B, F, C = (1, *shape) if len(shape) == 2 else shape
-        B, F, C = int(B), int(F), int(C)
+            raise ValueError(f'{name}: kind must be one of {tuple(self._GL_KINDS)}, got {kind!r}')
+        B, F, C, fr = self._planes(spec, frames, name, 'spec')
         bins = plan.geometry['filter_length'] // 2 + 1
-        fr = self._frame_counts(frames, B, F, what)
         minv = None
         if mel_inverse is not None:
             minv = np.ascontiguousarray(mel_inverse, dtype=np.float64)
             if kind != 'log_mel' or minv.shape != (plan.n_mel, bins):
-                raise ValueError(f"{what}: mel_inverse goes with kind='log_mel' and must be [{plan.n_mel}, {bins}]")
-        return B, F, C, bins, fr, minv, [(spec, (B, F, C)), (init, (B, F, bins, 2))]
+                raise ValueError(f"{name}: mel_inverse goes with kind='log_mel' and must be [{plan.n_mel}, {bins}]")
+        return self._call(name, [(spec, (B, F, C), 'float32'), (init, (B, F, bins, 2), 'float32')], lambda new: (new(shape(B, F, bins)),),
+                          lambda ins, outs, where: (ins[0], B, F, C, fr, plan.handle, self._GL_KINDS[kind], minv, ins[1], int(n_iters),
+                                                    float(momentum), *tail, outs[0]), stream)[0]
 
     def griffin_lim(self, plan, spec, frames=None, kind='magnitude', n_iters=60, momentum=0.99, init=None, mel_inverse=None,
                     stream=None):
@@ -1127,14 +922,8 @@ class HipEngine:
         turned into magnitudes by max(0, exp(spec) . mel_inverse) (`mel_inverse` float64 [n_mel, bins]; None: the minimum-norm
         inverse of the plan's filterbank).  `init` [B, F, bins, 2]: the initial phase as (re, im) pairs of any length (None:
         zero phase).  Row b holds `frames[b]` frames (default F).  `stream` as `mel_fn_run`."""
-        B, F, C, bins, fr, minv, inputs = self._gl_args(plan, spec, frames, kind, mel_inverse, init, 'griffin_lim')
-        hop = plan.geometry['hop_length']
-        keep = (fr, minv)                                                       # host tables stay alive across the call
-        out = self._planes_call('griffin_lim', inputs, lambda empty: (empty((B, F * hop), 'float32'),),
-                                lambda ins, outs: (ins[0], B, F, C, self._ptr(fr), plan.handle, self._GL_KINDS[kind], self._ptr(minv),
-                                                   ins[1], int(n_iters), float(momentum), outs[0]), stream)[0]
-        del keep
-        return out
+        return self._griffin_lim('griffin_lim', plan, spec, frames, kind, n_iters, momentum, init, mel_inverse,
+                                 lambda B, F, bins: (B, F * plan.geometry['hop_length']), stream=stream)
 
     def griffin_lim_probe(self, plan, spec, k, what, frames=None, kind='magnitude', n_iters=3, momentum=0.99, init=None,
                           mel_inverse=None):
@@ -1143,22 +932,21 @@ class HipEngine:
         imaginary parts); 'frames' [B, F, filter_length]; 'signal' [B, hop * (F - 1) + filter_length] (the reflect-padded row)."""
         if what not in self._GL_STAGES:
             raise ValueError(f'what must be one of {tuple(self._GL_STAGES)}, got {what!r}')
-        B, F, C, bins, fr, minv, inputs = self._gl_args(plan, spec, frames, kind, mel_inverse, init, 'griffin_lim_probe')
         g = plan.geometry
-        shape = {'target': (B, F, bins), 'frames': (B, F, g['filter_length']),
-                 'signal': (B, g['hop_length'] * (F - 1) + g['filter_length'])}.get(what, (B, F, 2 * bins))
-        return self._planes_call('griffin_lim_probe', inputs, lambda empty: (empty(shape, 'float32'),),
-                                 lambda ins, outs: (ins[0], B, F, C, self._ptr(fr), plan.handle, self._GL_KINDS[kind], self._ptr(minv),
-                                                    ins[1], int(n_iters), float(momentum), int(k), self._GL_STAGES[what], outs[0]))[0]
+        return self._griffin_lim('griffin_lim_probe', plan, spec, frames, kind, n_iters, momentum, init, mel_inverse,
+                                 lambda B, F, bins: {'target': (B, F, bins), 'frames': (B, F, g['filter_length']),
+                                                     'signal': (B, g['hop_length'] * (F - 1) + g['filter_length'])
+                                                     }.get(what, (B, F, 2 * bins)), tail=(int(k), self._GL_STAGES[what]))
 
     # ------------------------------------------------------------------ WaveGlow denoiser (csrc/stft_inv.hip)
     _DN_STAGES = {'spectrum': 0, 'operand': 1, 'frames': 2}
 
     def _bias(self, plan, bias, what):
+        """(bias, [bins], dtype) as `_call` takes an input; the bias must hold one magnitude per bin of the plan."""
         bins = plan.geometry['filter_length'] // 2 + 1
-        if tuple(bias.shape) != (bins,):
-            raise ValueError(f'{what}: bias must be [{bins}] (one magnitude per bin of the plan), got {tuple(bias.shape)}')
-        return bins
+        if _dims(bias) != (bins,):
+            raise ValueError(f'{what}: bias must be [{bins}] (one magnitude per bin of the plan), got {_dims(bias)}')
+        return bias, (bins,), 'float32'
 
     def denoise(self, plan, audio, bias, strength=0.1, lengths=None, stream=None, out=None):
         """Spectral subtraction of a vocoder's bias spectrum (tts_hip_denoise) under `plan` (Tacotron kind): audio [N] or
@@ -1169,16 +957,12 @@ class HipEngine:
         enqueued there and the call returns without waiting.  `out` (device tensors only): a contiguous float32 CUDA tensor
         [B, N] that takes the result; it may be `audio` itself."""
         B, N, lens = self._audio_rows(audio, lengths, 'denoise')
-        bins = self._bias(plan, bias, 'denoise')
-        if out is not None:
-            torch = self._torch()
-            if not (_is_torch_cuda(audio) and _is_torch_cuda(out) and out.dtype == torch.float32 and out.is_contiguous()
-                    and tuple(out.shape) == (B, N)):
-                raise ValueError(f'denoise: out must be a contiguous float32 CUDA tensor [{B}, {N}] next to a CUDA input')
-            self._check_device(out)
-        return self._rows_call('denoise', audio, B, N, [(bias, (bins,))],
-                               lambda empty: (empty((B, N), 'float32') if out is None else out,),
-                               lambda extras, outs: (self._ptr(lens), plan.handle, extras[0], float(strength), outs[0]), stream)[0]
+        bias = self._bias(plan, bias, 'denoise')
+        if out is not None and not (_is_torch_cuda(audio) and _is_torch_cuda(out) and out.dtype == self._torch().float32
+                                    and out.is_contiguous() and _dims(out) == (B, N)):
+            raise ValueError(f'denoise: out must be a contiguous float32 CUDA tensor [{B}, {N}] next to a CUDA input')
+        return self._audio_call('denoise', audio, B, N, lambda new: (new((B, N)) if out is None else out,),
+                               lambda extras, outs: (lens, plan.handle, extras[0], float(strength), outs[0]), stream, [bias])[0]
 
     def denoise_probe(self, plan, audio, bias, strength, what, lengths=None):
         """Test hook (tts_hip_denoise_probe): run `denoise` on the same arguments (host arrays) up to stage `what` and return
@@ -1187,34 +971,15 @@ class HipEngine:
         if what not in self._DN_STAGES:
             raise ValueError(f'what must be one of {tuple(self._DN_STAGES)}, got {what!r}')
         B, N, lens = self._audio_rows(audio, lengths, 'denoise_probe')
-        bins = self._bias(plan, bias, 'denoise_probe')
+        bias = self._bias(plan, bias, 'denoise_probe')
         F = self.mel_fn_frames(plan, N)
-        shape = (B, F, plan.geometry['filter_length']) if what == 'frames' else (B, F, 2 * bins)
-        return self._host_call('denoise_probe', audio, B, N, [(bias, (bins,))], lambda empty: (empty(shape, 'float32'),),
-                               lambda extras, outs: (self._ptr(lens), plan.handle, extras[0], float(strength),
-                                                     self._DN_STAGES[what], outs[0]))[0]
+        shape = (B, F, plan.geometry['filter_length']) if what == 'frames' else (B, F, 2 * bias[1][0])
+        return self._audio_call('denoise_probe', audio, B, N, lambda new: (new(shape),),
+                               lambda extras, outs: (lens, plan.handle, extras[0], float(strength), self._DN_STAGES[what], outs[0]),
+                               extra=[bias])[0]
 
     # ------------------------------------------------------------------ waveform clean-up (csrc/audio_proc.hip)
     _TRIM_MODES = {'start_end': 0, 'start': 1, 'end': 2}
-
-    @staticmethod
-    def _audio_rows(audio, lengths, what):
-        """(B, N, int32 lengths or None) of a [N] / [B, N] input; every length in [1, N].  Raises before any GPU call."""
-        if len(audio.shape) not in (1, 2):
-            raise ValueError(f'{what}: audio must be [N] or [B, N], got shape {tuple(audio.shape)}')
-        B, N = (1, int(audio.shape[0])) if len(audio.shape) == 1 else (int(audio.shape[0]), int(audio.shape[1]))
-        if B < 1 or N < 1:
-            raise ValueError(f'{what}: empty audio {tuple(audio.shape)}')
-        if lengths is None:
-            return B, N, None
-        if hasattr(lengths, 'detach'):
-            lengths = lengths.detach().cpu().numpy()
-        lens = np.ascontiguousarray(np.atleast_1d(np.asarray(lengths)).astype(np.int64))
-        if lens.shape != (B,):
-            raise ValueError(f'{what}: lengths must have shape ({B},), got {lens.shape}')
-        if lens.min() < 1 or lens.max() > N:
-            raise ValueError(f'{what}: lengths must lie in [1, {N}]')
-        return B, N, lens.astype(np.int32)
 
     @staticmethod
     def _samples(value, rate, what):
@@ -1243,9 +1008,9 @@ class HipEngine:
             noise_len = self._samples(noise_length, rate, 'reduce_noise: noise_length')
         if noise_len < 1:
             raise ValueError(f'reduce_noise: the noise clip must hold at least one sample (got {noise_len})')
-        out, = self._rows_call('reduce_noise', audio, B, N, [(noise, (B, noise_len))], lambda empty: (empty((B, N), 'float32'),),
-                               lambda extras, outs: (self._ptr(lens), extras[0], noise_len, int(bool(renormalize)), outs[0]),
-                               stream)
+        out, = self._audio_call('reduce_noise', audio, B, N, lambda new: (new((B, N)),),
+                               lambda extras, outs: (lens, extras[0], noise_len, int(bool(renormalize)), outs[0]),
+                               stream, [(noise, (B, noise_len), 'float32')])
         return out[0] if len(audio.shape) == 1 else out
 
     _RN_STAGES = {'padded': 0, 'noise_padded': 1, 'spectrum': 2, 'noise_spectrum': 3, 'power_max': 4, 'threshold': 5, 'mask': 6,
@@ -1260,7 +1025,6 @@ class HipEngine:
         0 / 1, 'gated' [B, Fr, 2050], 'frames' [B, Fr, 2048] (inverse-DFT rows before the overlap-add).  Always batched."""
         if what not in self._RN_STAGES:
             raise ValueError(f'what must be one of {tuple(self._RN_STAGES)}, got {what!r}')
-        audio = np.asarray(audio, dtype=np.float32)
         B, N, lens = self._audio_rows(audio, lengths, 'reduce_noise_probe')
         if noise is not None:
             noise_len = int(np.asarray(noise).reshape(B, -1).shape[1])
@@ -1272,21 +1036,21 @@ class HipEngine:
         shape = {'padded': (B, Fr * 512), 'noise_padded': (B, Frn * 512), 'spectrum': (B, Fr, 2050),
                  'noise_spectrum': (B, Frn, 2050), 'power_max': (2, B), 'threshold': (B, 1025), 'mask': (B, Fr, 1025),
                  'gated': (B, Fr, 2050), 'frames': (B, Fr, 2048)}[what]
-        return self._host_call('reduce_noise_probe', audio, B, N, [(noise, (B, noise_len))], lambda empty: (empty(shape, 'float32'),),
-                               lambda extras, outs: (self._ptr(lens), extras[0], noise_len, self._RN_STAGES[what], outs[0]))[0]
+        return self._audio_call('reduce_noise_probe', audio, B, N, lambda new: (new(shape),),
+                               lambda extras, outs: (lens, extras[0], noise_len, self._RN_STAGES[what], outs[0]),
+                               extra=[(noise, (B, noise_len), 'float32')])[0]
 
     def trim_silence_probe(self, audio, rate=None, lengths=None, window_length=0.2):
         """Test hook (tts_hip_trim_silence_probe): the convolution launches of `trim_silence` on audio [N] or [B, N] (host
         array).  Returns conv [B, max(N, W) + 1] float64, W = 2 * (window_length // 2): conv[b, :nc_b] =
         np.convolve(x_b ** 2, window, 'valid') with nc_b = |lengths[b] - W| + 1, NaN beyond."""
-        audio = np.asarray(audio, dtype=np.float32)
         B, N, lens = self._audio_rows(audio, lengths, 'trim_silence_probe')
         wl = self._samples(window_length, rate, 'trim_silence_probe: window_length')
         if wl < 2:
             raise ValueError(f'trim_silence_probe: window_length must be >= 2 samples (got {wl})')
         W = 2 * (wl // 2)
-        conv, = self._host_call('trim_silence_probe', audio, B, N, [], lambda empty: (empty((B, max(N, W) + 1), 'float64'),),
-                                lambda extras, outs: (self._ptr(lens), wl, outs[0]))
+        conv, = self._audio_call('trim_silence_probe', audio, B, N, lambda new: (new((B, max(N, W) + 1), 'float64'),),
+                                lambda extras, outs: (lens, wl, outs[0]))
         for b in range(B):
             conv[b, abs((N if lens is None else int(lens[b])) - W) + 1:] = np.nan
         return conv
@@ -1316,7 +1080,7 @@ class HipEngine:
         if B * max(N, M) * 4 >= 1 << 31:
             raise ValueError(f'resample: B = {B} x N = {N} (M {M}) too large for 31-bit offsets')
         one_row = len(audio.shape) == 1
-        if rate == target_rate and lens is None:
+        if rate == target_rate and lens is None:            # no library call: the input as float32
             if _is_torch_cuda(audio):
                 self._check_device(audio)
                 return audio.to(self._torch().float32)
@@ -1324,8 +1088,8 @@ class HipEngine:
                 raise ValueError('stream= needs device tensors')
             a = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(B, N))
             return a[0] if one_row else a
-        out, = self._rows_call('resample', audio, B, N, [], lambda empty: (empty((B, M), 'float32'),),
-                               lambda extras, outs: (self._ptr(lens), rate, target_rate, outs[0], M), stream)
+        out, = self._audio_call('resample', audio, B, N, lambda new: (new((B, M)),),
+                               lambda extras, outs: (lens, rate, target_rate, outs[0], M), stream)
         return out[0] if one_row else out
 
     def resample_probe(self, audio, rate, target_rate, lengths=None):
@@ -1333,11 +1097,10 @@ class HipEngine:
         the end of the forward chain -> complex64 [B, N // 2 + 1]: row b holds bins 0 .. lengths[b] // 2 of
         rfft(audio[b, :lengths[b]]), zeros beyond.  Always batched."""
         from .audio import resampled_length
-        audio = np.asarray(audio, dtype=np.float32)
         B, N, lens = self._audio_rows(audio, lengths, 'resample_probe')
         M = resampled_length(N, int(rate), int(target_rate))
-        out, = self._host_call('resample_probe', audio, B, N, [], lambda empty: (empty((B, N // 2 + 1, 2), 'float32'),),
-                               lambda extras, outs: (self._ptr(lens), int(rate), int(target_rate), outs[0], M))
+        out, = self._audio_call('resample_probe', audio, B, N, lambda new: (new((B, N // 2 + 1, 2)),),
+                               lambda extras, outs: (lens, int(rate), int(target_rate), outs[0], M))
         return out.view(np.complex64)[..., 0]
 
     def resample_fft_probe(self, lines, inverse=False):
@@ -1367,21 +1130,11 @@ class HipEngine:
             raise ValueError(f'trim_silence: window_length must be >= 2 samples (got {wl})')
         if not (np.isfinite(threshold) and np.isfinite(add_start) and np.isfinite(add_end)) or add_start < 0 or add_end < 0:
             raise ValueError('trim_silence: threshold and margins must be finite, margins >= 0')
-        lens_p = self._ptr(lens)
-        args = (wl, float(threshold), float(add_start), float(add_end), self._TRIM_MODES[mode])
-        if _is_torch_cuda(audio):
-            torch = self._torch()
-            self._check_device(audio)
-            a = audio.to(torch.float32).reshape(B, N).contiguous()
-            st = torch.empty((2, B), dtype=torch.int32, device=a.device)
-            self._order_after_torch()
-            self._check(self._lib.tts_hip_trim_silence(self._h, ctypes.c_void_p(a.data_ptr()), B, N, lens_p, *args,
-                                                       ctypes.c_void_p(st.data_ptr()), ctypes.c_void_p(st[1].data_ptr()),
-                                                       MEM_DEVICE), 'trim_silence')
-            start, end = st.cpu().numpy()
-        else:
-            start, end = self._host_call('trim_silence', audio, B, N, [], lambda empty: (empty(B, 'int32'), empty(B, 'int32')),
-                                         lambda extras, outs: (lens_p, *args, outs[0], outs[1]))
+        # one int32 [2, B] result (start row, end row): a CUDA input costs one device-to-host copy
+        cuts, = self._audio_call('trim_silence', audio, B, N, lambda new: (new((2, B), 'int32'),),
+                                lambda extras, outs: (lens, wl, float(threshold), float(add_start), float(add_end),
+                                                      self._TRIM_MODES[mode], outs[0][0], outs[0][1]))
+        start, end = cuts.cpu().numpy() if _is_torch_cuda(cuts) else cuts
         if len(audio.shape) == 1:
             return int(start[0]), int(end[0])
         return start, end
@@ -1460,9 +1213,8 @@ class HipEngine:
         clean-up calls share one workspace per engine: the next one must be ordered after it)."""
         B, N, lens, args = self._silence_call('remove_silence', audio, rate, lengths, method, mode, threshold, min_silence,
                                               block_size, replace_by, min_voice_time)
-        out, out_len = self._rows_call('remove_silence', audio, B, N, [],
-                                       lambda empty: (empty((B, N), 'float32'), empty((B,), 'int32')),
-                                       lambda extras, outs: (self._ptr(lens), *args, outs[0], outs[1]), stream)
+        out, out_len = self._audio_call('remove_silence', audio, B, N, lambda new: (new((B, N)), new((B,), 'int32')),
+                                       lambda extras, outs: (lens, *args, outs[0], outs[1]), stream)
         if len(audio.shape) != 1:
             return out, out_len
         return (out[0], out_len[0]) if _is_torch_cuda(audio) else out[0, :int(out_len[0])].copy()
@@ -1481,16 +1233,12 @@ class HipEngine:
         if what not in self._SILENCE_STAGES:
             raise ValueError(f'what must be one of {tuple(self._SILENCE_STAGES)}, got {what!r}')
         stage, dtype = self._SILENCE_STAGES[what]
-        audio = np.asarray(audio, dtype=np.float32)
         B, N, lens, args = self._silence_call('remove_silence_probe', audio, rate, lengths, method, mode, threshold, min_silence,
                                               block_size, replace_by, min_voice_time)
         width = ctypes.c_int32(0)
-        tail = lambda out: (self._ptr(lens), *args, stage, out, ctypes.byref(width))
-        audio = np.ascontiguousarray(audio)
-        self._check(self._lib.tts_hip_remove_silence_probe(self._h, self._ptr(audio), B, N, *tail(None), MEM_HOST),
-                    'remove_silence_probe')               # out NULL: the width alone
-        return self._host_call('remove_silence_probe', audio, B, N, [], lambda empty: (empty((B, width.value), dtype),),
-                               lambda extras, outs: tail(outs[0]))[0]
+        tail = lambda extras, outs: (lens, *args, stage, outs[0] if outs else None, ctypes.byref(width))
+        self._audio_call('remove_silence_probe', audio, B, N, lambda new: (), tail)               # no output: the width alone
+        return self._audio_call('remove_silence_probe', audio, B, N, lambda new: (new((B, width.value), dtype),), tail)[0]
 
     # ------------------------------------------------------------------ measurement hooks
     def kernel_timing(self, enable: bool) -> None:
