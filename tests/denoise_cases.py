@@ -37,19 +37,19 @@ class Case(NamedTuple):
 
     @property
     def geom(self):
-        return SC.BY_NAME[self.base].geom
+        return SC.case_of(self.base).geom
 
     @property
     def F(self):
-        return SC.BY_NAME[self.base].F
+        return SC.case_of(self.base).F
 
     @property
     def n(self):
-        return SC.BY_NAME[self.base].n
+        return SC.case_of(self.base).n
 
     @property
     def signal(self):
-        return SC.BY_NAME[self.base].signal
+        return SC.case_of(self.base).signal
 
     @property
     def s(self):
@@ -61,9 +61,28 @@ CASES = tuple(Case(f'{c.name}_s{s:g}', c.name, s) for c in SC.CASES for s in STR
 BY_NAME = {c.name: c for c in CASES}
 NAMES = tuple(c.name for c in CASES)
 
+# The second table: the tone of each extra geometry of stft_inv_cases (gapped, sparse, long) at strength 0.5.
+EXTRA_STRENGTH = 0.5
+EXTRA_CASES = tuple(Case(f'{gname}_s{EXTRA_STRENGTH:g}', f'{gname}_f{F}_tone', EXTRA_STRENGTH)
+                    for gname, (g, F, _) in SC.EXTRA_GEOMS.items())
+EXTRA_BY_NAME = {c.name: c for c in EXTRA_CASES}
+EXTRA_NAMES = tuple(c.name for c in EXTRA_CASES)
+# BOUNDS' rule geometry by geometry: the operand ten times the float32 numpy distance (beside it;
+# test_denoise.py::test_extra_bounds_lie_above_float32 prints and checks them), the time frames and the audio the STFT
+# inverse's bounds of that geometry.  Measured operand distances: gapped 1.082e-7, sparse 1.203e-7, long 1.109e-7
+EXTRA_BOUNDS = {
+    'gapped': {'operand': 1.1e-6, 'frames': SC.EXTRA_BOUNDS['gapped']['frames'], 'audio': SC.EXTRA_BOUNDS['gapped']['inverse']},
+    'sparse': {'operand': 1.3e-6, 'frames': SC.EXTRA_BOUNDS['sparse']['frames'], 'audio': SC.EXTRA_BOUNDS['sparse']['inverse']},
+    'long': {'operand': 1.2e-6, 'frames': SC.EXTRA_BOUNDS['long']['frames'], 'audio': SC.EXTRA_BOUNDS['long']['inverse']},
+}
+
+
+def case_of(name):
+    return BY_NAME[name] if name in BY_NAME else EXTRA_BY_NAME[name]
+
 
 def audio_of(case):
-    return SC.audio_of(SC.BY_NAME[case.base])
+    return SC.audio_of(SC.case_of(case.base))
 
 
 @functools.lru_cache(maxsize=None)
@@ -80,7 +99,7 @@ def bias_of(g):
 
 def numpy_runner(name, dtype=np.float32, plant=None):
     """runner(what) over a numpy copy of the call in `dtype`, every stage kept."""
-    case = BY_NAME[name]
+    case = case_of(name)
     g, x = case.geom, audio_of(case)
     kept = {'spectrum': R.transform(x, g, dtype)}
     kept['operand'] = D.gate(kept['spectrum'], bias_of(g), case.s, g, None, dtype, plant)
@@ -91,7 +110,7 @@ def numpy_runner(name, dtype=np.float32, plant=None):
 
 def stage_errors(name, runner):
     """{stage: error} of a run against float64 applied to its own previous stage; the audio against float64 on its operand."""
-    case = BY_NAME[name]
+    case = case_of(name)
     g = case.geom
     f64 = lambda a: np.asarray(a, np.float64)
     spec, op, tf, audio = (f64(runner(what)) for what in ('spectrum', 'operand', 'frames', 'audio'))

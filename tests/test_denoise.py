@@ -108,6 +108,37 @@ def test_audio_bound_lies_below_a_missing_cut():
     assert max(e for e, _ in effects) >= 10 * C.BOUNDS['audio']
 
 
+# ---- the second table: gapped, sparse, long --------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', C.EXTRA_NAMES)
+def test_extra_bounds_lie_above_float32(name):
+    gname = name.split('_')[0]
+    bounds = C.EXTRA_BOUNDS[gname]
+    errs = C.stage_errors(name, C.numpy_runner(name))
+    print(name, 'float32 numpy distances', {s: f'{e:.3e}' for s, e in errs.items()}, 'bounds', bounds)
+    assert bounds['operand'] / 12 <= errs['operand'] <= bounds['operand'] / 8           # ten times it, rounded up to two digits
+    for s, e in errs.items():
+        assert e <= bounds[s] / 5, (s, e, bounds[s])
+    # a sample no window covers comes back 0, whatever the gate did
+    case = C.case_of(name)
+    bare = C.SC.uncovered(case.geom, case.F)
+    assert bare.any() == (gname != 'long') and (D.denoise(C.audio_of(case), C.bias_of(case.geom), case.s, case.geom)[0][bare] == 0).all()
+
+
+@pytest.mark.parametrize('plant', D.GATE_MISTAKES)
+@pytest.mark.parametrize('name', C.EXTRA_NAMES)
+def test_extra_operand_bound_lies_below_planted_mistakes(name, plant):
+    """Every gate mistake moves the operand of every extra case by at least ten times its bound -- but the missing clamp on
+    gapped, where no bin of the tone lies under half the bias and nothing clamps."""
+    case = C.case_of(name)
+    share = D.clamped_share(R.transform(C.audio_of(case), case.geom), C.bias_of(case.geom), case.s, case.geom)
+    effect = C.stage_errors(name, C.numpy_runner(name, np.float64, plant))['operand']
+    print(name, plant, f'effect {effect:.3e} clamped {share:.0%}')
+    if plant == 'no_clamp' and share == 0:
+        assert name.startswith('gapped') and effect == 0
+    else:
+        assert effect >= 10 * C.EXTRA_BOUNDS[name.split('_')[0]]['operand'] and effect >= 4e-3
+
+
 # ---- the front end, as a stand-alone program under ASan / UBSan ----------------------------------------------------------
 def _plan(g=R.GEOMS[0], **more):
     return dict(filter_length=g.fl, hop_length=g.hop, win_length=g.wl, n_mel_channels=1, mel_fmax=11025, **more)
@@ -144,6 +175,13 @@ def test_geometry(checker, g):
             lengths[2] = max(1, N - g.hop // 2 - 1)                      # no multiple of the hop
         assert _accepted(checker, 'denoise', lengths, N=N, **_plan(g)) == geometry(g, B, N, lengths), (N, lengths)
         assert _accepted(checker, 'denoise', B=B, N=N, what=2, **_plan(g)) == geometry(g, B, N, ())
+
+
+@pytest.mark.parametrize('gname', ['long', 'sparse'])
+def test_geometry_on_the_extra_plans(checker, gname):
+    """hop > filter_length and filter_length = 2048 through the same stand-alone sweep (gapped refuses the sweep's row of
+    win_length - 1 samples: REFUSALS has that message)."""
+    test_geometry(checker, C.SC.EXTRA_GEOMS[gname][0])
 
 
 OK = dict(B=2, N=40, strength=0.5, **_plan())

@@ -66,6 +66,54 @@ def test_ragged_rows_equal_single_rows(gpu_engine, g, F):
         assert _bits(got[b, :keep], alone[0, :keep]) and (got[b, keep:] == 0).all() and np.abs(got[b, :keep]).max() > 0, (b, L)
 
 
+@pytest.mark.parametrize('name', C.EXTRA_NAMES)
+def test_stage_by_stage_on_the_extra_geometries(gpu_engine, name):
+    """test_stage_by_stage on the second table (gapped, sparse, long) under its own bounds; a sample no window covers is
+    exactly 0 in the audio."""
+    case = C.case_of(name)
+    g, x, bias = case.geom, C.audio_of(case), C.bias_of(case.geom)
+    bounds = C.EXTRA_BOUNDS[name.split('_')[0]]
+    plan = _plan(gpu_engine, g)
+    kept = {what: gpu_engine.denoise_probe(plan, x, bias, case.strength, what) for what in ('spectrum', 'operand', 'frames')}
+    kept['audio'] = gpu_engine.denoise(plan, x, bias, case.strength)
+    assert kept['audio'].shape == x.shape and kept['frames'].shape == (1, case.F, g.fl)
+    assert _bits(kept['spectrum'], gpu_engine.mel_fn_probe(plan, x, 'spectrum'))
+    errs = C.stage_errors(name, kept.__getitem__)
+    print(name, ' '.join(f'{s} {e:.3e}' for s, e in errs.items()))
+    for s, e in errs.items():
+        assert e <= bounds[s], (s, e)
+    bare = SC.uncovered(g, case.F)
+    assert np.isfinite(kept['audio']).all() and (kept['audio'][0, bare] == 0).all() and np.abs(kept['audio'][0, ~bare]).max() > 0
+
+
+def test_ragged_rows_equal_single_rows_on_the_gapped_plan(gpu_engine):
+    """test_ragged_rows_equal_single_rows on (16, 4, 4).  Its lengths of one and two hops are refused there (max(L,
+    win_length) must pass filter_length // 2 = 8), so the two shortest rows are 9 and 12 samples; 33 is no hop multiple.
+    Beside the bits of the row alone: the samples no window covers are exactly 0, the others follow the float64 restatement."""
+    g, F = SC.EXTRA_GEOMS['gapped'][0], 9
+    plan = _plan(gpu_engine, g)
+    N = F * g.hop
+    lengths = [g.half + 1, 3 * g.hop, (F // 2) * g.hop, (F - 1) * g.hop, N, N - g.hop // 2 - 1]
+    rng = np.random.default_rng(F)
+    x = rng.uniform(-0.8, 0.8, (len(lengths), N)).astype(np.float32)
+    for b, L in enumerate(lengths):
+        x[b, L:] = np.nan
+    bias = C.bias_of(g)
+    got = gpu_engine.denoise(plan, x, bias, 0.5, lengths=lengths)
+    assert got.shape == x.shape and np.isfinite(got).all()
+    want = D.denoise(np.nan_to_num(x), bias, float(np.float32(0.5)), g, lengths)
+    for b, L in enumerate(lengths):
+        keep = D.kept_samples(L, g)
+        alone = gpu_engine.denoise(plan, x[b:b + 1, :L], bias, 0.5)
+        assert alone.shape == (1, L) and (alone[0, keep:] == 0).all()
+        assert _bits(got[b, :keep], alone[0, :keep]) and (got[b, keep:] == 0).all() and np.abs(got[b, :keep]).max() > 0, (b, L)
+        bare = SC.uncovered(g, g.frames(L))[:keep]
+        assert bare.any() and (got[b, :keep][bare] == 0).all(), (b, L)
+        err = R.row_error(got[b:b + 1, :keep], want[b:b + 1, :keep])
+        print('gapped ragged', b, L, f'{err:.3e}')
+        assert err <= SC.BOUNDS['inverse'], (b, L, err)
+
+
 def test_repeat_in_place_and_device_input_give_the_same_bits(gpu_engine):
     import torch
     g = R.GEOMS[3]

@@ -62,7 +62,7 @@ def _inverse_distances(plant=None, dtype=np.float32, names=C.NAMES):
     the signal."""
     wi = wr = 0.0
     for name in names:
-        case = C.BY_NAME[name]
+        case = C.case_of(name)
         g, x = case.geom, C.audio_of(case)
         spec = R.transform(x, g, np.float32)
         got = R.inverse(spec, g, None, dtype, plant)
@@ -157,6 +157,130 @@ def test_end_to_end_bounds(name):
     assert C.E2E_BOUNDS[name] / 12 <= d <= C.E2E_BOUNDS[name] / 8
 
 
+# ---- the second table: gapped, sparse, long ------------------------------------------------------------------------------
+_EXTRA = sorted(C.EXTRA_GEOMS)
+
+
+def _extra_names(gname, loud=False):
+    """The cases of a geometry; loud: without the ones whose spectrum is all zero (gapped's impulse falls on a sample whose
+    window is 0 in the one frame that covers it: the plan sees silence)."""
+    names = tuple(n for n in C.EXTRA_NAMES if C.geom_name(n) == gname)
+    return tuple(n for n in names if np.abs(C.target_of(n)).max() > 0) if loud else names
+
+
+@pytest.mark.parametrize('gname', _EXTRA)
+def test_extra_geometries_meet_their_preconditions(gname):
+    """On the reference alone: stft_inv_check takes F, the plan gives samples(F) samples F frames, and the samples no window
+    covers exist on gapped and sparse (with a summed squared window of exactly 0) and not on long."""
+    g, F, signals = C.EXTRA_GEOMS[gname]
+    assert g.samples(F) > g.half and g.frames(g.samples(F)) == F
+    assert g.wl <= g.fl and (gname != 'sparse' or (g.hop > g.fl and g.hop % 4 == 0)) and (gname != 'long' or g.fl > 1024)
+    bare = C.uncovered(g, F)
+    w2 = R.tables(g)[2].astype(np.float64)
+    ws = np.zeros(g.hop * (F - 1) + g.fl)
+    for f in range(F):
+        ws[f * g.hop:f * g.hop + g.fl] += w2
+    kept = ws[g.half:g.half + g.samples(F)]
+    assert np.array_equal(kept <= R.FLT_MIN, bare) and (kept[bare] == 0).all()         # the float32 table agrees, and it is 0
+    print(gname, 'samples', g.samples(F), 'of them uncovered', int(bare.sum()))
+    assert bare.sum() == {'gapped': g.samples(F) // 4, 'sparse': 36, 'long': 0}[gname]
+    for name in _extra_names(gname):
+        case = C.case_of(name)
+        x = C.audio_of(case)
+        back = R.inverse(R.transform(x, g), g)
+        assert (back[0, :case.n][bare] == 0).all()
+        assert R.row_error(back[:, :case.n][:, ~bare], x[:, ~bare]) <= 1e-5       # float32 tables, over sparse's window edge
+    assert _extra_names(gname, loud=True) == tuple(n for n in _extra_names(gname) if n != 'gapped_f9_impulse')
+
+
+@pytest.mark.parametrize('gname', _EXTRA)
+def test_extra_bounds_lie_above_float32(gname):
+    names = _extra_names(gname)
+    worst = _worst(names=names)
+    worst['inverse'], worst['roundtrip'] = _inverse_distances(names=names)
+    bounds = C.EXTRA_BOUNDS[gname]
+    print(gname, 'float32 numpy distances', {s: f'{e:.3e}' for s, e in worst.items()}, 'bounds', bounds)
+    assert ('roundtrip' in bounds) == (gname == 'long') and sorted(set(worst) - {'roundtrip'}) == sorted(set(bounds) - {'roundtrip'})
+    for s, b in bounds.items():
+        if s == 'spectrum':                                     # the forward plan's own bound
+            assert worst[s] <= b / 5
+        elif b == 0:
+            assert worst[s] == 0
+        else:
+            assert b / 12 <= worst[s] <= b / 8, (s, worst[s], b)    # ten times it, rounded up to two digits
+
+
+# ck_edge changes the last bin alone: it cannot show on long's tone, whose last bin holds under 0.4 % of a frame's largest magnitude
+_EXTRA_CANNOT_SHOW = {'ck_edge': ('long_f9_tone',)}
+
+
+@pytest.mark.parametrize('plant', sorted(_SHOWS))
+@pytest.mark.parametrize('gname', _EXTRA)
+def test_extra_bounds_lie_below_planted_mistakes(gname, plant):
+    """As test_bounds_lie_below_planted_mistakes.  P(0, 0) = 0 shows in the phase update where the spectrum is silent (gapped's
+    impulse); on every other case it shows in the first operand, through the zeros of `init`, and is held against that bound."""
+    bounds = C.EXTRA_BOUNDS[gname]
+    loud = tuple(n for n in _extra_names(gname, loud=True) if n not in _EXTRA_CANNOT_SHOW.get(plant, ()))
+    silent = tuple(n for n in _extra_names(gname) if n not in _extra_names(gname, loud=True))
+    if plant == 'reflect_off_by_one':
+        loud = tuple(n for n in loud if not n.endswith('impulse'))
+    groups = [('phasor', silent), ('operand', loud)] if plant == 'p00_zero' else [(_SHOWS[plant], loud)]
+    for stage, names in groups:
+        effects = []
+        for name in names:
+            for m in (C.MOMENTA if plant != 'momentum_from_c' else (0.99,)):
+                init = C.init_of(name)
+                errs = C.stage_errors(name, m, init, C.numpy_runner(name, m, init, np.float64, plant))
+                effects.append((errs[stage], name, m))
+        if effects:
+            print(gname, plant, stage, 'weakest effect', min(effects))
+            assert min(effects)[0] >= 10 * bounds[stage] and min(effects)[0] > 0, min(effects)
+    assert loud
+
+
+@pytest.mark.parametrize('plant', ['no_window', 'ws_from_w', 'no_scale', 'trim_off_by_one', 'ck_edge', 'imag_sign'])
+@pytest.mark.parametrize('gname', _EXTRA)
+def test_extra_inverse_bound_lies_below_planted_mistakes(gname, plant):
+    effects = []
+    for name in _extra_names(gname, loud=True):
+        case = C.case_of(name)
+        g = case.geom
+        spec = R.transform(C.audio_of(case), g)
+        effects.append((R.row_error(R.inverse(spec, g, plant=plant), R.inverse(spec, g)), name))
+    print(gname, plant, 'weakest effect', min(effects))
+    assert min(effects)[0] >= 10 * max(C.EXTRA_BOUNDS[gname]['inverse'], C.EXTRA_BOUNDS[gname].get('roundtrip', 0.0))
+
+
+@pytest.mark.parametrize('name', sorted(C.LOG_MEL_PLANS))
+def test_log_mel_plans(name):
+    """The plans of the ragged log-mel test: no channel is empty and the filterbank has full rank (the plan's own inverse
+    exists), every row passes stft_inv_check, and BOUNDS['target'] lies ten times above the float32 numpy copy's distance
+    from float64 on every row."""
+    g, mel, W, Minv = C.log_mel_rows(name)
+    n_mel = C.LOG_MEL_PLANS[name][3]
+    assert W.shape == (n_mel, g.cut) and (W.max(axis=1) > 0).all() and np.linalg.matrix_rank(W) == n_mel
+    assert g.frames(g.samples(C.LOG_MEL_F)) == C.LOG_MEL_F
+    assert {'mel8': 32, 'mel32': 32, 'mel80': 96}[name] == ceil_div(n_mel, 32) * 32
+    for b, Fb in enumerate(C.LOG_MEL_FRAMES):
+        assert g.samples(Fb) > g.half and np.isnan(mel[b, Fb:]).all() and np.isfinite(mel[b, :Fb]).all()
+        want = R.mel_target(mel[b:b + 1, :Fb], Minv)
+        d = R.target_error(R.mel_target(mel[b:b + 1, :Fb], Minv.astype(np.float32), np.float32), want)
+        print(name, b, f'float32 numpy target {d:.3e}')
+        assert d <= C.BOUNDS['target'] / 10 and want.max() > 0
+        assert R.target_error(R.mel_target(mel[b:b + 1, :Fb], W), want) >= 10 * C.BOUNDS['target']
+
+
+def test_phasor_at_the_ends_of_the_float_range():
+    """The restatement on the pairs the GPU test feeds `init`: unit length, the direction of the pair, (1, 0) at the origin."""
+    pairs = C.phasor_pairs().astype(np.float64)
+    pr, pi = R.phasor(pairs[:, 0], pairs[:, 1])
+    assert np.isfinite(pr).all() and np.isfinite(pi).all() and np.abs(np.hypot(pr, pi) - 1).max() <= 1e-15
+    origin = (pairs == 0).all(axis=1)
+    assert origin.sum() == 2 and (pr[origin] == 1).all() and (pi[origin] == 0).all()
+    ang = np.arctan2(pairs[~origin, 1], pairs[~origin, 0])
+    assert np.abs(pr[~origin] - np.cos(ang)).max() <= 1e-15 and np.abs(pi[~origin] - np.sin(ang)).max() <= 1e-15
+
+
 # ---- the front end, as a stand-alone program under ASan / UBSan ----------------------------------------------------------
 def _plan(fl=16, hop=4, wl=16, **more):
     return dict(filter_length=fl, hop_length=hop, win_length=wl, n_mel_channels=1, mel_fmax=11025, **more)
@@ -185,6 +309,12 @@ def test_geometry(checker, g):
     assert _accepted(checker, 'stft_inv', B=1, F=F, C=g.cut, n_iters=3, what=5, k=2, **s) == geometry(g, 1, F, None, 0, what=5)
     mel = dict(s, n_mel_channels=40, mel_fmax=8000)
     assert _accepted(checker, 'stft_inv', B=2, F=F, C=40, input_kind=1, **mel) == geometry(g, 2, F, None, 1, n_mel=40)
+
+
+@pytest.mark.parametrize('gname', sorted(C.EXTRA_GEOMS))
+def test_geometry_on_the_extra_plans(checker, gname):
+    """hop > filter_length and filter_length = 2048 through the same stand-alone sweep."""
+    test_geometry(checker, C.EXTRA_GEOMS[gname][0])
 
 
 OK = dict(B=2, F=9, C=9, n_iters=3, momentum=0.5, **_plan())

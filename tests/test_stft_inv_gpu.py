@@ -5,6 +5,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import denoise_ref as D
 import stft_inv_cases as C
 import stft_inv_ref as R
 
@@ -124,6 +125,166 @@ def test_loop_stage_by_stage(gpu_engine, name, momentum, with_init):
     audio = gpu_engine.griffin_lim(plan, S, n_iters=C.N_ITERS, momentum=momentum, init=init)
     g = case.geom
     assert _bits(audio[:, :case.n], again[:, g.half:g.half + case.n]) and (audio[:, case.n:] == 0).all()
+
+
+# ---- the second table: plans whose frames leave samples uncovered, and a filter above 1024 -----------------------------------
+@pytest.mark.parametrize('name', C.EXTRA_NAMES)
+def test_inverse_on_the_extra_geometries(gpu_engine, name):
+    """test_inverse_and_round_trip's comparisons under EXTRA_BOUNDS.  Where no window covers a sample (gapped, sparse) there is
+    no round trip: those samples are exactly 0 and the covered ones follow the float64 inverse."""
+    case = C.case_of(name)
+    g, x, bounds = case.geom, C.audio_of(case), C.EXTRA_BOUNDS[C.geom_name(name)]
+    fn = _stft(gpu_engine, g)
+    plan = fn._plan()
+    re, im = gpu_engine.stft_transform(plan, x, polar=False)
+    mag, ph = gpu_engine.stft_transform(plan, x, polar=True)
+    assert re.shape == (1, case.F, g.cut) and np.isfinite(ph).all()
+    spec64 = np.concatenate([re, im], -1).astype(np.float64)
+    e_spec = R.frame_error(spec64, R.transform(x, g), g)
+    got = gpu_engine.stft_inverse(plan, re, im, polar=False)
+    assert got.shape == (1, case.F * g.hop) and gpu_engine.mel_fn_samples(plan, case.F) == case.n
+    polar64 = np.concatenate([mag * np.cos(ph.astype(np.float64)), mag * np.sin(ph.astype(np.float64))], -1)
+    got_p = gpu_engine.stft_inverse(plan, mag, ph, polar=True)
+    bare = C.uncovered(g, case.F)
+    covered = lambda a: np.asarray(a)[:, :case.n][:, ~bare]
+    e_inv = R.row_error(covered(got), covered(R.inverse(spec64, g)))
+    e_pol = R.row_error(covered(got_p), covered(R.inverse(polar64, g)))
+    e_rt = R.row_error(got[:, :case.n], x) if 'roundtrip' in bounds else None
+    print(name, f'spectrum {e_spec:.3e} inverse {e_inv:.3e} polar {e_pol:.3e} round trip {e_rt} uncovered {int(bare.sum())}')
+    assert np.isfinite(got).all() and np.isfinite(got_p).all()
+    assert (got[:, case.n:] == 0).all() and (got_p[:, case.n:] == 0).all()
+    assert (got[0, :case.n][bare] == 0).all() and (got_p[0, :case.n][bare] == 0).all()
+    assert bare.any() == ('roundtrip' not in bounds)
+    assert e_spec <= bounds['spectrum'] and e_inv <= bounds['inverse'] and e_pol <= bounds['inverse']
+    assert e_rt is None or e_rt <= bounds['roundtrip']
+    assert _bits(fn.inverse(np.stack([re, im], -1)), got) and _bits(fn.inverse(mag, ph), got_p)
+
+
+@pytest.mark.parametrize('name', C.EXTRA_NAMES)
+def test_loop_stage_by_stage_on_the_extra_geometries(gpu_engine, name):
+    """test_loop_stage_by_stage at momentum 0.99 with `init`, under EXTRA_BOUNDS; the probed signal is exactly 0 at every
+    sample no window covers, its reflected copies included."""
+    case = C.case_of(name)
+    g, bounds, momentum = case.geom, C.EXTRA_BOUNDS[C.geom_name(name)], 0.99
+    plan = _stft(gpu_engine, g)._plan()
+    S, init = C.target_of(name), C.init_of(name)
+    cache = {}
+
+    def runner(what, k):
+        if (what, k) not in cache:
+            cache[(what, k)] = gpu_engine.griffin_lim_probe(plan, S, k, what, n_iters=C.N_ITERS, momentum=momentum, init=init)
+        return cache[(what, k)]
+
+    assert _bits(runner('target', 0), S)
+    errs = C.stage_errors(name, momentum, init, runner)
+    print(name, momentum, ' '.join(f'{s} {e:.3e}' for s, e in errs.items()))
+    for s, e in errs.items():
+        assert e <= bounds[s], (s, e)
+    bare = np.pad(C.uncovered(g, case.F), g.half, mode='reflect')
+    for k in C.PROBE_KS:
+        sig = runner('signal', k)
+        assert sig.shape == (1, bare.size) and np.isfinite(sig).all() and (sig[0, bare] == 0).all(), k
+    audio = gpu_engine.griffin_lim(plan, S, n_iters=C.N_ITERS, momentum=momentum, init=init)
+    last = runner('signal', C.N_ITERS)
+    assert _bits(audio[:, :case.n], last[:, g.half:g.half + case.n]) and (audio[:, case.n:] == 0).all()
+
+
+_ROWS_GEOMS = {'16_16_4': R.GEOMS[0], '64_48_10': R.GEOMS[2], '1024_1024_256': R.GEOMS[3], 'gapped': C.EXTRA_GEOMS['gapped'][0]}
+
+
+@pytest.mark.parametrize('gname', sorted(_ROWS_GEOMS))
+def test_transform_rows(gpu_engine, gname):
+    """The transform on a batch and on ragged rows: five rows of N = 64 hops hold {1, win_length - 1, win_length, 63 hops - 1,
+    N} samples, NaN behind them (65 frame slots a row: the batch crosses the GEMM's 64-row tile).  On gapped the plan refuses
+    a row of max(L, win_length) <= filter_length // 2 = 8 samples, so its three short rows hold 9, 10 and 12."""
+    from text_to_speech_amd._lib import HipLibraryError
+    g = _ROWS_GEOMS[gname]
+    eng, plan = gpu_engine, _stft(gpu_engine, g)._plan()
+    N = g.hop * 64
+    short = [1, g.wl - 1, g.wl]
+    if gname == 'gapped':
+        with pytest.raises(HipLibraryError, match='not more than filter_length // 2'):
+            eng.stft_transform(plan, np.zeros((3, N), np.float32), lengths=short)
+        short = [g.half + 1, g.half + 2, 3 * g.hop]
+    lengths = short + [g.hop * 63 - 1, N]
+    F = eng.mel_fn_frames(plan, N)
+    assert F == g.frames(N) == 65
+    rng = np.random.default_rng(g.fl + g.hop)
+    clean = rng.uniform(-0.9, 0.9, (5, N)).astype(np.float32)
+    x, x7 = clean.copy(), clean.copy()
+    for b, L in enumerate(lengths):
+        x[b, L:] = np.nan
+        x7[b, L:] = 7.0
+    worst = 0.0
+    for polar in (False, True):
+        p0, p1 = eng.stft_transform(plan, x, lengths=lengths, polar=polar)
+        assert p0.shape == p1.shape == (5, F, g.cut) and np.isfinite(p0).all() and np.isfinite(p1).all()
+        q0, q1 = eng.stft_transform(plan, x7, lengths=lengths, polar=polar)
+        assert _bits(p0, q0) and _bits(p1, q1)
+        for b, L in enumerate(lengths):
+            Fb = eng.mel_fn_frames(plan, L)
+            assert Fb == g.frames(L) and (p0[b, Fb:] == 0).all() and (p1[b, Fb:] == 0).all(), (b, L)
+            a0, a1 = eng.stft_transform(plan, clean[b:b + 1, :L], polar=polar)
+            assert a0.shape == (1, Fb, g.cut) and _bits(p0[b, :Fb], a0[0]) and _bits(p1[b, :Fb], a1[0]), (polar, b, L)
+            if not polar:
+                want = R.transform(D.padded_row(clean[b], L, g), g)
+                err = R.frame_error(np.concatenate([p0[b:b + 1, :Fb], p1[b:b + 1, :Fb]], -1), want, g)
+                worst = max(worst, err)
+                assert err <= C.BOUNDS['spectrum'], (b, L, err)
+        # no lengths: three rows in one call are three calls of one row
+        b0, b1 = eng.stft_transform(plan, clean[:3], polar=polar)
+        for b in range(3):
+            a0, a1 = eng.stft_transform(plan, clean[b:b + 1], polar=polar)
+            assert _bits(b0[b:b + 1], a0) and _bits(b1[b:b + 1], a1), (polar, b)
+    print(gname, f'spectrum of the ragged rows {worst:.3e}')
+
+
+@pytest.mark.parametrize('name', sorted(C.LOG_MEL_PLANS))
+def test_log_mel_input_on_a_ragged_batch(gpu_engine, name):
+    """Log-mel rows of {7, 12, 11} frames, NaN behind them, on plans of 8 (n_mel < 32), 32 (no K padding column) and 80
+    channels: the target is 0 behind a row's frames and max(0, exp(mel) . Minv) inside them, under the plan's own inverse and
+    a caller's; three iterations give finite audio, every row the bits of the row alone."""
+    eng = gpu_engine
+    g, mel, W, Minv = C.log_mel_rows(name)
+    plan = eng.mel_fn(C.log_mel_config(name))
+    frames, F = list(C.LOG_MEL_FRAMES), C.LOG_MEL_F
+    own = eng.griffin_lim_probe(plan, mel, 0, 'target', frames=frames, kind='log_mel', n_iters=0)
+    given = eng.griffin_lim_probe(plan, mel, 0, 'target', frames=frames, kind='log_mel', n_iters=0, mel_inverse=Minv)
+    audio = eng.griffin_lim(plan, mel, frames=frames, kind='log_mel', n_iters=3)
+    assert own.shape == (3, F, g.cut) and audio.shape == (3, F * g.hop) and np.isfinite(audio).all()
+    for b, Fb in enumerate(frames):
+        want = R.mel_target(mel[b:b + 1, :Fb], Minv)
+        e_own, e_given = R.target_error(own[b:b + 1, :Fb], want), R.target_error(given[b:b + 1, :Fb], want)
+        print(name, b, f'target {e_own:.3e} with the caller\'s inverse {e_given:.3e}')
+        assert (own[b, Fb:] == 0).all() and (given[b, Fb:] == 0).all(), b
+        assert e_own <= C.BOUNDS['target'] and e_given <= C.BOUNDS['target'], (b, e_own, e_given)
+        n = g.samples(Fb)
+        alone = eng.griffin_lim(plan, mel[b:b + 1, :Fb], kind='log_mel', n_iters=3)
+        assert _bits(audio[b, :n], alone[0, :n]) and (audio[b, n:] == 0).all() and np.abs(audio[b, :n]).max() > 0, (b, Fb)
+
+
+def test_phasor_at_the_ends_of_the_float_range(gpu_engine):
+    """P(init) on FLT_MIN-sized, subnormal, 3e38-sized and mismatched pairs: with S = 1 the first operand is the phasor.  Every
+    pair has an exact unit answer, so the bound is absolute and unweighted."""
+    g = R.GEOMS[0]
+    plan = _stft(gpu_engine, g)._plan()
+    pairs = C.phasor_pairs()
+    F = 9
+    idx = np.arange(F * g.cut) % len(pairs)
+    init = pairs[idx].reshape(1, F, g.cut, 2)
+    S = np.ones((1, F, g.cut), np.float32)
+    op = gpu_engine.griffin_lim_probe(plan, S, 0, 'operand', n_iters=0, init=init)
+    assert op.shape == (1, F, 2 * g.cut) and np.isfinite(op).all()
+    got_r, got_i = op[0, :, :g.cut].reshape(-1).astype(np.float64), op[0, :, g.cut:].reshape(-1).astype(np.float64)
+    want_r, want_i = R.phasor(pairs[:, 0].astype(np.float64), pairs[:, 1].astype(np.float64))
+    origin = (pairs == 0).all(axis=1)
+    assert origin.sum() == 2 and (want_r[origin] == 1).all() and (want_i[origin] == 0).all()
+    err = np.maximum(np.abs(got_r - want_r[idx]), np.abs(got_i - want_i[idx]))
+    for j, (a, b) in enumerate(pairs):
+        print(f'P({a:.3e}, {b:.3e}) = ({got_r[j]:.9g}, {got_i[j]:.9g}) error {err[idx == j].max():.3e}')
+    assert err.max() <= C.BOUNDS['phasor'], err.max()
+    assert np.abs(np.hypot(got_r, got_i) - 1).max() <= C.BOUNDS['phasor']
+    assert (got_r[origin[idx]] == 1).all() and (got_i[origin[idx]] == 0).all()
 
 
 @pytest.mark.parametrize('g,F', [(R.GEOMS[0], 10), (R.GEOMS[1], 9), (R.GEOMS[2], 12), (R.GEOMS[3], 65)])
