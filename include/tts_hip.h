@@ -246,6 +246,41 @@ int tts_hip_tacotron2_loss(tts_hip_engine* e, const float* mel_target, const flo
                            const float* mel, const float* stop_tokens, int B, int T, const int32_t* kinds, int n_kinds,
                            int mask_mel_padding, int from_logits, double finish_weight, double not_finish_weight, float* out,
                            int mem, void* stream);
+/* Mel-cepstral distortion of two ragged batches of log-mels along a dynamic-time-warping path (MCD-DTW), per row: what a
+ * free-running synthesis is compared with its recording by.  a: [B, Ta, n_mel], b: [B, Tb, n_mel], float32 log-mels; len_a,
+ * len_b: HOST int32 [B], each in 1 .. Ta / 1 .. Tb, NULL = every row full.  Nothing at or behind a row's length is read (a NaN
+ * there reaches no output).  flags: TTS_HIP_DTW_ALIGN | TTS_HIP_DTW_C0.  Per row, la = len_a[b], lb = len_b[b]:
+ *   cepstra   c[r] = sum_k D[r][k] m[k], D the orthonormal DCT-II, D[r][k] = sqrt(2 / n_mel) cos(pi (k + 1/2) r / n_mel), row 0
+ *             divided by sqrt 2; rows 1 .. n_cep are used, rows 0 .. n_cep with TTS_HIP_DTW_C0.  The table is computed on the
+ *             host in float64, rounded once to float32 and kept on the handle per (n_mel, n_cep, c0).  These are the DCT of
+ *             the model's own log-mel, not WORLD / SPTK mel-cepstra.
+ *   distance  d(i, j) = sqrt(sum_r (ca[i][r] - cb[j][r])^2)
+ *   ALIGN     C(0, 0) = d(0, 0); C(i, j) = d(i, j) + min(C(i-1, j-1), C(i-1, j), C(i, j-1)), a missing neighbour = +inf, all
+ *             three steps of unit weight; one float32 add per cell, and min is exact, so C does not depend on how the cells
+ *             are spread over the machine.  The step code of a cell is the argmin: 0 diagonal, 1 from (i-1, j), 2 from
+ *             (i, j-1), ties resolved in that order (cell (0, 0): 0).  cost = C(la-1, lb-1); the path is the backtrack from
+ *             that cell along the step codes, path_len its number of cells.
+ *   no ALIGN  the path is the diagonal (t, t), t < min(la, lb) = path_len; cost = sum_t d(t, t) (float64 sum, rounded once).
+ *   mcd       (10 sqrt 2 / ln 10) cost / path_len, in dB.
+ * stats: float32 [3, B] = cost, path_len, mcd.  path: NULL or int32 [B, Ta + Tb - 1, 2], the pairs (i, j) from (0, 0)
+ * onwards, -1 behind the path's end.  a, b, stats and path live where `mem` says.  A row's results do not depend on the rows
+ * beside it or on `mem`, bit for bit.  Needs no weights.  Refused (TTS_HIP_EINVAL, first match wins, nothing copied or
+ * launched; csrc/mel_dtw_call.h): a NULL a, b or stats; B, Ta or Tb < 1; n_mel outside 2 .. 128; n_cep outside
+ * 1 .. n_mel - 1; unknown flag bits; a bad mem kind; a length outside its range; Ta or Tb > 8192; B * Ta * Tb > 2^25 cells
+ * (the aligned programme keeps 10 bytes per cell: 320 MiB of workspace at the limit); B * (Ta + Tb) > 2^19 frames (cepstra and
+ * a host caller's staged mels, up to 512 bytes per frame each: 256 MiB each at the limit -- the workspace of an accepted call
+ * stays below 840 MiB whatever its shape, path and tables included).  Synchronizes `stream` (NULL: the
+ * handle's) before returning.
+ * Test hook mel_dtw_probe: the same arguments, runs the aligned programme up to the stage `what` and returns it dense, zeros
+ * at and behind the lengths: TTS_HIP_DTW_CEPSTRA_A [B, Ta, R], CEPSTRA_B [B, Tb, R] (R = n_cep, + 1 with C0), DISTANCE, COST,
+ * STEP [B, Ta, Tb] (step codes as float32).  Any other `what` is TTS_HIP_EINVAL, after the mem kind.                       */
+enum { TTS_HIP_DTW_ALIGN = 1, TTS_HIP_DTW_C0 = 2 };
+enum { TTS_HIP_DTW_CEPSTRA_A = 0, TTS_HIP_DTW_CEPSTRA_B = 1, TTS_HIP_DTW_DISTANCE = 2, TTS_HIP_DTW_COST = 3, TTS_HIP_DTW_STEP = 4 };
+int tts_hip_mel_dtw(tts_hip_engine* e, const float* a, const float* b, int B, int Ta, int Tb, int n_mel, const int32_t* len_a,
+                    const int32_t* len_b, int n_cep, int flags, float* stats, int32_t* path, int mem, void* stream);
+int tts_hip_mel_dtw_probe(tts_hip_engine* e, const float* a, const float* b, int B, int Ta, int Tb, int n_mel,
+                          const int32_t* len_a, const int32_t* len_b, int n_cep, int flags, int what, float* out, int mem,
+                          void* stream);
 /* Runs the encoder for another token batch INTO an existing encoded batch (its device buffer is reused and only grows):
  * what a caller that synthesizes sentence after sentence wants -- no hipMalloc / hipFree per sentence, and the decoder's
  * cached step graphs (keyed by the buffer) survive from one sentence to the next.  Asynchronous like `encode`.        */
@@ -691,7 +726,8 @@ int tts_hip_resample_fft_probe(tts_hip_engine* e, const float* in, int lines, in
  * A tts_hip_griffin_lim call files the four parts of its iterations under the same kinds: 0 = inverse-frames GEMM, 1 = gather
  * overlap-add, 2 = forward DFT GEMM (with its gather, where the plan has one), 3 = phase update.  A tts_hip_denoise call
  * files its four parts there too: 2 = forward DFT (padding and gather included), 3 = gate, 0 = inverse-frames GEMM, 1 =
- * overlap-add.
+ * overlap-add.  A tts_hip_mel_dtw call files its launches as 0 = cepstra, 1 = distances, 2 = sweep, 3 = backtrack (without
+ * alignment: the diagonal's reduction).
  * Timing is off unless enabled (events perturb nothing but cost a few us each).        */
 int tts_hip_kernel_timing(tts_hip_engine* e, int enable);
 /* Box probe: TFLOP/s a bare v_mfma_f32_32x32x2_f32 loop sustains on this device right now (every CU, 2 waves per SIMD, ~20 ms)

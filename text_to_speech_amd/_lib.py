@@ -90,6 +90,10 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_int, c_void_p]),
     'tts_hip_tacotron2_loss': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                        c_int, c_int, c_double, c_double, c_void_p, c_int, c_void_p]),
+    'tts_hip_mel_dtw': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                c_void_p, c_int, c_void_p]),
+    'tts_hip_mel_dtw_probe': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_void_p, c_int, c_void_p]),
     'tts_hip_tacotron2_reencode': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     'tts_hip_encoded_free': (c_int, [c_void_p, c_void_p]),
     'tts_hip_kernel_timing': (c_int, [c_void_p, c_int]),

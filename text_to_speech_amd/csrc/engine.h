@@ -244,6 +244,13 @@ struct ResampleDev {
     DevBuf tw, ws;                      // twiddles, workspace
 };
 
+// MCD / DTW (mel_dtw.hip): no weights; the DCT tables built so far, per (n_mel, n_cep, c0), and the one workspace of a call
+struct MelDtwDev {
+    std::map<std::tuple<int, int, int>, float*> dct;      // device [R][n_mel]
+    std::vector<int32_t> lens_h;        // host image of a call's [len_a | len_b] while it is staged
+    DevBuf ws;                          // MelDtwLayout (mel_dtw_call.h)
+};
+
 struct TimedLaunch {
     hipEvent_t a, b;
     int kind;
@@ -260,6 +267,7 @@ struct tts_hip_engine {
     MelStftDev stft;
     AudioProcDev aproc;
     ResampleDev resamp;
+    MelDtwDev dtw;
     // Host staging of every synchronous audio call (AudioStage).  One buffer serves them all: calls on one handle are
     // serialised by the caller and a synchronous call drains the stream before it returns, so no call finds another's data
     // still in use here; a call that needs more than its predecessors reallocates it before it copies anything in.
@@ -394,6 +402,7 @@ int mel_plan_check(tts_hip_engine* e, const char* name, const tts_hip_mel_fn* fn
 void melstft_free(tts_hip_engine* e);
 void audioproc_free(tts_hip_engine* e);
 void resample_free(tts_hip_engine* e);
+void mel_dtw_free(tts_hip_engine* e);
 
 // shared helpers
 // n floats of device-side samples into `out` on `st` (engine.hip: Philox4x32-10; kind = TTS_HIP_RANDOM_*)

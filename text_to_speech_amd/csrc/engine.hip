@@ -296,6 +296,7 @@ int tts_hip_destroy(tts_hip_engine* e) {
     melstft_free(e);
     audioproc_free(e);
     resample_free(e);
+    mel_dtw_free(e);
     e->audio_io.release();
     (void)hipStreamDestroy(e->stream);
     delete e;

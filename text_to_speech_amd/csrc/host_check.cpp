@@ -61,11 +61,18 @@
 // understood), null=target,gate,dec,mel,stop,kinds,out and odd=target,dec,mel (that pointer 4 bytes past a 16-byte boundary).
 // First line "<status> <message>"; when the call is accepted "K chunks weighted bytes" of taco_loss_layout
 // (tests/test_taco_loss.py compares them with a Python restatement).
+//        ttsw_check_asan --mel-dtw [KEY=VALUE...]  -- the front end of an MCD / DTW call (mel_dtw_call.h) run as an entry point named
+// "who".  Settings: B= Ta= Tb= n_mel= n_cep= flags= mem= probe=1 what= (the probe's check) path=0|1 (the call asks for the
+// path), la=N,N,... lb=N,N,... (the length tables; absent: NULL), null=a,b,stats,out and dct=1.  First line "<status>
+// <message>"; when the call is accepted "R W K skew_i aligned" and the thirteen offsets, out_elems and bytes of mel_dtw_layout,
+// and with dct=1 the R * n_mel values of mel_dtw_dct, one per line (tests/test_mel_dtw.py compares them with a Python
+// restatement).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
 
 #include "audio_call.h"
+#include "mel_dtw_call.h"
 #include "taco_call.h"
 #include "taco_loss_call.h"
 #include "ttsw_host.h"
@@ -437,7 +444,57 @@ static int print_taco_loss(int argc, char** argv) {
     return 0;
 }
 
+static int print_mel_dtw(int argc, char** argv) {
+    std::map<std::string, int> v{{"B", 1}, {"Ta", 1}, {"Tb", 1}, {"n_mel", 80}, {"n_cep", 13}, {"flags", TTS_HIP_DTW_ALIGN},
+                                 {"mem", TTS_HIP_MEM_HOST}, {"probe", 0}, {"what", -1}, {"path", 0}, {"dct", 0}};
+    std::string nulls;
+    std::vector<int32_t> la, lb;
+    bool has_la = false, has_lb = false;
+    for (int i = 2; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) return 2;
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        if (key == "null") nulls = eq + 1;
+        else if (key == "la" || key == "lb") {
+            std::vector<int32_t>& t = key == "la" ? la : lb;
+            (key == "la" ? has_la : has_lb) = true;
+            for (const char* p = eq + 1; *p;) {
+                char* end = nullptr;
+                t.push_back((int32_t)strtol(p, &end, 10));
+                if (end == p) return 2;
+                p = *end == ',' ? end + 1 : end;
+            }
+        } else if (v.count(key)) v[key] = atoi(eq + 1);
+        else return 2;
+    }
+    // a table shorter than B would be read past its end by the check: that is the caller's contract, not the check's
+    if ((has_la && (long long)la.size() < v["B"]) || (has_lb && (long long)lb.size() < v["B"])) return 2;
+    // never read: the check only tests the pointers' values
+    const auto ptr = [&](const char* name, unsigned long long a) {      // (whole names: "stats" holds an "a")
+        return ("," + nulls + ",").find(std::string(",") + name + ",") != std::string::npos ? nullptr : (void*)(uintptr_t)a;
+    };
+    const MelDtwCall c{"who", (const float*)ptr("a", 0x100000000ull), (const float*)ptr("b", 0x200000000ull), v["B"], v["Ta"], v["Tb"],
+                       v["n_mel"], has_la ? la.data() : nullptr, has_lb ? lb.data() : nullptr, v["n_cep"], v["flags"],
+                       (float*)ptr("stats", 0x300000000ull), v["path"] ? (int32_t*)(uintptr_t)0x400000000ull : nullptr, v["probe"] != 0,
+                       v["what"], (float*)ptr("out", 0x500000000ull), v["mem"], nullptr};
+    char why[256] = "";
+    const int rc = mel_dtw_check(c, why, sizeof why);
+    printf("%d %s\n", rc, why);
+    if (rc) return 0;
+    const MelDtwLayout l = mel_dtw_layout(c);
+    printf("%d %d %d %d %d\n", l.R, l.W, l.K, (int)l.skew_i, (int)l.aligned);
+    printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", l.in_a, l.in_b, l.lens, l.cep_a, l.cep_b, l.dist, l.step, l.cost,
+           l.final_cost, l.stats, l.path, l.out, l.out_elems, l.bytes);
+    if (v["dct"]) {
+        const std::vector<float> D = mel_dtw_dct(c.n_mel, c.n_cep, (c.flags & TTS_HIP_DTW_C0) != 0);
+        if (D.size() != (size_t)l.R * c.n_mel) return 2;
+        for (float x : D) printf("%.9g\n", x);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--mel-dtw")) return print_mel_dtw(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--taco-loss")) return print_taco_loss(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "--taco-call")) return print_taco_call(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "--audio-call")) return print_audio_call(argc, argv);

@@ -681,6 +681,56 @@ class HipEngine:
                                                     float(finish_weight), float(not_finish_weight), outs[0], *where),
                           stream, device=any(_is_torch_cuda(x) for x in inputs), twin=False)[0]
 
+    # ------------------------------------------------------------------ MCD along a DTW path
+    DTW_ALIGN, DTW_C0 = 1, 2                        # TTS_HIP_DTW_*
+    DTW_STAGES = {'cepstra_a': 0, 'cepstra_b': 1, 'distance': 2, 'cost': 3, 'step': 4}
+
+    def _dtw_request(self, who, a, b, lengths_a, lengths_b, n_cep, include_c0, align):
+        """The checked arguments of a `mel_dtw` / `mel_dtw_probe` call -> (B, Ta, Tb, n_mel, len_a, len_b, n_cep, flags)."""
+        sa, sb = self._batched(a, 3) if len(_dims(a)) == len(_dims(b)) else None, self._batched(b, 3)
+        if sa is None or sb is None or sa[0] != sb[0] or sa[2] != sb[2] or min(sa + sb) < 1:
+            raise ValueError(f'{who}: a and b must be [B, Ta, n_mel] and [B, Tb, n_mel] (or one row of each), got {_dims(a)} and {_dims(b)}')
+        (B, Ta, n_mel), Tb = sa, sb[1]
+        if not 2 <= n_mel <= 128:
+            raise ValueError(f'{who}: n_mel = {n_mel} is outside [2, 128]')
+        if n_cep != int(n_cep) or not 1 <= int(n_cep) <= n_mel - 1:
+            raise ValueError(f'{who}: n_cep = {n_cep!r} is outside [1, n_mel - 1 = {n_mel - 1}]')
+        la = None if lengths_a is None else self._row_table(lengths_a, B, 1, Ta, who, 'lengths_a')
+        lb = None if lengths_b is None else self._row_table(lengths_b, B, 1, Tb, who, 'lengths_b')
+        flags = (self.DTW_ALIGN if align else 0) | (self.DTW_C0 if include_c0 else 0)
+        return B, Ta, Tb, n_mel, la, lb, int(n_cep), flags
+
+    def mel_dtw(self, a, b, lengths_a=None, lengths_b=None, *, n_cep=13, include_c0=False, align=True, return_path=False,
+                stream=None):
+        """Mel-cepstral distortion of log-mels `a` [B, Ta, n_mel] against `b` [B, Tb, n_mel] along their dynamic-time-warping
+        path, per row (tts_hip_mel_dtw; the math is pinned in include/tts_hip.h).  `lengths_a` / `lengths_b` [B], each in
+        1 .. Ta / 1 .. Tb (default: full): nothing at or behind a row's length is read.  The cepstra are rows 1 .. n_cep of the
+        orthonormal DCT-II of a frame (0 .. n_cep with `include_c0`).  `align=False`: no warping, the frames (t, t) below the
+        shorter length.  Returns float32 [3, B] = cost, path length, MCD in dB; with `return_path` also int32
+        [B, Ta + Tb - 1, 2], the pairs (i, j) from (0, 0) onwards and -1 behind the path's end.  One row of each operand
+        without the batch axis is taken as B = 1.  numpy in gives numpy out; if either operand is a CUDA tensor the other is
+        moved to the GPU and CUDA tensors come back, on `stream` (a torch.cuda.Stream) if one is given.  Returns after
+        `stream` (or the engine's stream) has drained.  Needs no weights."""
+        B, Ta, Tb, n_mel, la, lb, n_cep, flags = self._dtw_request('mel_dtw', a, b, lengths_a, lengths_b, n_cep, include_c0, align)
+        outs = self._call('mel_dtw', [(a, (B, Ta, n_mel), 'float32'), (b, (B, Tb, n_mel), 'float32')],
+                          lambda new: (new((3, B)), new((B, Ta + Tb - 1, 2), 'int32') if return_path else None),
+                          lambda ins, outs, where: (*ins, B, Ta, Tb, n_mel, la, lb, n_cep, flags, *outs, *where),
+                          stream, device=_is_torch_cuda(a) or _is_torch_cuda(b), twin=False)
+        return outs if return_path else outs[0]
+
+    def mel_dtw_probe(self, a, b, lengths_a=None, lengths_b=None, *, n_cep=13, include_c0=False, what='cost'):
+        """Test hook (tts_hip_mel_dtw_probe): the aligned programme of `mel_dtw` up to one stage, returned dense with zeros at
+        and behind the lengths: what='cepstra_a' [B, Ta, R] / 'cepstra_b' [B, Tb, R] (R = n_cep, + 1 with `include_c0`),
+        'distance', 'cost', 'step' [B, Ta, Tb] (the step codes 0 diagonal, 1 from (i-1, j), 2 from (i, j-1) as float32)."""
+        if what not in self.DTW_STAGES:
+            raise ValueError(f'what must be one of {tuple(self.DTW_STAGES)}, got {what!r}')
+        B, Ta, Tb, n_mel, la, lb, n_cep, flags = self._dtw_request('mel_dtw_probe', a, b, lengths_a, lengths_b, n_cep, include_c0, True)
+        R = n_cep + (1 if include_c0 else 0)
+        shape = (B, Ta, R) if what == 'cepstra_a' else (B, Tb, R) if what == 'cepstra_b' else (B, Ta, Tb)
+        return self._call('mel_dtw_probe', [(a, (B, Ta, n_mel), 'float32'), (b, (B, Tb, n_mel), 'float32')], lambda new: (new(shape),),
+                          lambda ins, outs, where: (*ins, B, Ta, Tb, n_mel, la, lb, n_cep, flags, self.DTW_STAGES[what], outs[0], *where),
+                          device=_is_torch_cuda(a) or _is_torch_cuda(b), twin=False)[0]
+
     def set_decoder_mode(self, mode: str) -> None:
         """How the autoregressive decoder loop runs: 'auto' (default: the persistent weight-stationary kernel for 1 - 2 rows,
         the fused two-kernel step for 3 - 8 rows, whichever applies otherwise), 'persistent' / 'fused' (that machine when the

@@ -225,14 +225,18 @@ class HipRuntime(Runtime):
     # ------------------------------------------------------------------ Tacotron2.infer (tacotron2_arch.py:866-925)
     def tacotron2_infer(self, inputs, *, max_length=None, early_stopping=True, attn_mask_offset=0.5,
                         attn_mask_win_len=None, prenet_masks=None, deterministic=False, seed=None, precision=None,
-                        streams=None, **_ignored):
-        """`streams=[(utterance, part, trial), ...]` (one id per row; excludes `prenet_masks` / `deterministic=True`): row b's
+                        streams=None, on_device=False, **_ignored):
+        """`on_device=True`: host tokens (and speaker) are uploaded first, so the outputs are CUDA tensors that stay on the GPU
+        (what `mel_dtw` then reads in place).
+        `streams=[(utterance, part, trial), ...]` (one id per row; excludes `prenet_masks` / `deterministic=True`): row b's
         dropout masks come from its own stream `stream_key(seed or the runtime's seed, MASK_STREAM, *id)` at offset 0; the
         runtime's running offset is neither used nor advanced.  A row then draws the same masks in any batch (its mel is its
         own up to the fp32 re-association between decoder machines)."""
         tokens, speaker = _tokens_and_speaker(inputs)
         B = int(tokens.shape[0])
         n_tok = int((tokens != 0).sum(1).max()) if isinstance(max_length, float) else None       # :888-892
+        if on_device:
+            tokens, speaker = self._uploaded(tokens, np.int32), self._uploaded(speaker)
         max_len = frame_cap(n_tok, max_length, self.max_decoder_steps)                               # :886-887 (the hparam)
         if attn_mask_win_len is not None and isinstance(attn_mask_offset, float):   # :894-897
             attn_mask_offset = int(np.float32(attn_mask_win_len) * np.float32(attn_mask_offset))
@@ -288,18 +292,25 @@ class HipRuntime(Runtime):
             self._drop_encoded()            # as in tacotron2_infer: a retry must run the encoder again
             raise
 
-    def _uploaded(self, x):
-        """None, a CUDA tensor as it is, or the host array `x` as a float32 tensor on the engine's GPU."""
+    def _uploaded(self, x, dtype=np.float32):
+        """None, a CUDA tensor as it is, or the host array `x` as a tensor of `dtype` (float32) on the engine's GPU."""
         if x is None or _is_torch_cuda(x):
             return x
         import torch
-        return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(torch.device('cuda', self.engine.device))
+        return torch.as_tensor(np.ascontiguousarray(x, dtype=dtype)).to(torch.device('cuda', self.engine.device))
 
     # ------------------------------------------------------------------ TacotronLoss.call (losses/tacotron_loss.py:115-167)
     def tacotron2_loss(self, mel_target, gate_target, decoder_output, mel, stop_tokens, **kwargs):
         """The reference's TacotronLoss per sample on the engine (`HipEngine.tacotron2_loss`, whose keywords these are) ->
         float32 [K, B].  The outputs of `tacotron2_forward(..., on_device=True)` go in without leaving the GPU."""
         return self.engine.tacotron2_loss(mel_target, gate_target, decoder_output, mel, stop_tokens, **kwargs)
+
+    # ------------------------------------------------------------------ MCD along a DTW path (include/tts_hip.h: tts_hip_mel_dtw)
+    def mel_dtw(self, a, b, lengths_a=None, lengths_b=None, **kwargs):
+        """Mel-cepstral distortion of log-mels `a` [B, Ta, n_mel] against `b` [B, Tb, n_mel] along their DTW path on the engine
+        (`HipEngine.mel_dtw`, whose keywords these are) -> float32 [3, B] (cost, path length, MCD in dB), and the path with
+        `return_path=True`.  The mel of `tacotron2_infer(..., on_device=True)` goes in without leaving the GPU."""
+        return self.engine.mel_dtw(a, b, lengths_a, lengths_b, **kwargs)
 
     def _draw(self, purpose, rows, frames, explicit, deterministic, seed, streams=None):
         """Where a call's random values (`purpose`: MASK_STREAM / NOISE_STREAM) come from -> (stream, row streams), at most

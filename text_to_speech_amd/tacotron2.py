@@ -180,6 +180,68 @@ class Tacotron2:
             per_item[:, r0:r0 + B] = _to_numpy(loss([target, gate], out, engine=runtime))
         return {'names': names, 'per_item': per_item, 'mean': mean_losses(names, per_item)}
 
+    SYNTHESIS_NAMES = ['mcd_dtw', 'path_len', 'frames', 'target_frames', 'frame_ratio', 'stopped']
+
+    def evaluate_synthesis(self, items, *, batch_size=8, max_length=10., n_cep=13, deterministic=True, **load_kwargs):
+        """The model as it is used -- free-running, through its own stop token and attention -- against held-out recordings:
+        mel-cepstral distortion along the DTW path (`metrics`, tts_hip_mel_dtw) of every synthesized mel against its
+        recording's.  `items` as for `evaluate`: (text, mel [F, 80]) or (text, audio) pairs; `embeddings=`: the speaker.
+        Consecutive items form batches of at most `batch_size`: one call of the model's runtime on the 0-padded tokens
+        (`max_length` as for `infer`: a float is frames per token of the longest row), then one `mel_dtw` of the returned mel
+        against the targets padded with `self.pad_mel_value`, with the rows' `lengths` and the targets' frame counts as the
+        length tables.  The mels stay on the GPU: only the lengths and the [3, B] result come to the host.  A row the model
+        gave 0 frames is left out of the DTW call and of the means: mcd_dtw, path_len and frame_ratio NaN, frames 0, stopped 1.
+        Returns {'names': SYNTHESIS_NAMES, 'per_item': float32 [6, N] in input order, 'mean': {name: float} over the rows that
+        produced frames}; `stopped` is 1 where the row ended by its stop token before the batch's frame cap.  Needs a runtime
+        with `mel_dtw` (HipRuntime) behind the model."""
+        load_kwargs = dict(self._resolve_embeddings(load_kwargs))
+        embeddings = load_kwargs.pop('embeddings', None)
+        runtime = self.compiled_infer
+        if getattr(runtime, 'mel_dtw', None) is None or not callable(runtime):
+            raise ValueError('evaluate_synthesis needs a runtime with mel_dtw (HipRuntime) behind the model')
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f'batch_size must be at least 1, got {batch_size}')
+        prepared = []
+        for i, item in enumerate(items):
+            if not isinstance(item, (tuple, list)) or len(item) != 2:
+                raise ValueError(f'items[{i}] must be a (text, mel) or (text, audio) pair')
+            text, recording = item
+            is_mel = not isinstance(recording, str) and len(getattr(recording, 'shape', ())) >= 2
+            mel = self._recording_mel(recording if is_mel else None, None if is_mel else recording, load_kwargs)
+            tokens = np.asarray(self.encode_text(self.clean_text(text), cleaned=True), dtype=np.int32)
+            if tokens.size == 0:
+                raise ValueError(f'items[{i}]: the text encodes to no token')
+            prepared.append((tokens, mel))
+        if not prepared:
+            raise ValueError('evaluate_synthesis needs at least one item')
+        names = self.SYNTHESIS_NAMES
+        per_item = np.full((len(names), len(prepared)), np.nan, dtype=np.float32)
+        pad = np.float32(self.pad_mel_value)
+        for r0 in range(0, len(prepared), batch_size):
+            rows = prepared[r0:r0 + batch_size]
+            B, Tin, T = len(rows), max(len(t) for t, _ in rows), max(len(m) for _, m in rows)
+            tok = np.zeros((B, Tin), dtype=np.int32)
+            target = np.full((B, T, rows[0][1].shape[1]), pad, dtype=np.float32)
+            for r, (tokens, mel) in enumerate(rows):
+                tok[r, :len(tokens)], target[r, :len(mel)] = tokens, mel
+            inputs = tok if embeddings is None else (tok, np.repeat(np.asarray(embeddings, np.float32)[None], B, axis=0))
+            out = runtime(inputs, max_length=max_length, deterministic=deterministic, on_device=True)
+            frames = np.asarray(_to_numpy(out.lengths), dtype=np.int64).reshape(B)
+            wanted = np.asarray([len(m) for _, m in rows], dtype=np.int64)
+            cap = int(out.mel.shape[1])
+            block = per_item[:, r0:r0 + B]
+            block[2], block[3], block[5] = frames, wanted, frames < cap
+            keep = np.flatnonzero(frames > 0)
+            if keep.size:
+                whole = keep.size == B                               # (no copy of the mel when every row produced frames)
+                stats = _to_numpy(runtime.mel_dtw(out.mel if whole else out.mel[keep.tolist()], target if whole else target[keep],
+                                                  frames[keep].astype(np.int32), wanted[keep].astype(np.int32), n_cep=n_cep))
+                block[0, keep], block[1, keep], block[4, keep] = stats[2], stats[1], frames[keep] / wanted[keep]
+        ok = per_item[2] > 0
+        mean = {name: float(per_item[k, ok].astype(np.float64).mean()) if ok.any() else float('nan') for k, name in enumerate(names)}
+        return {'names': list(names), 'per_item': per_item, 'mean': mean}
+
     # A text goes through four stages: `_prepare_text` (split / clean / encode), `_decode_rows` (tokens -> mels; the
     # autoregressive, latency-bound half; `_synthesize` is the two together), `_vocode_parts` or `_vocode_group` (mels ->
     # waveforms; the throughput-bound half) and `_finish` (result, cache entry, callbacks).  `infer`, `_infer_overlapped` and

@@ -277,6 +277,27 @@ class WaveGlow:
         mean = per_item.mean(axis=1) if len(prepared) else np.zeros(4)
         return {'names': names, 'per_item': per_item, 'mean': mean}
 
+    def copy_synthesis(self, mels, *, n_cep=13, **infer_kwargs):
+        """Copy synthesis: every mel of `mels` ([T, 80] each) is vocoded (`infer` with `infer_kwargs`), the audio analysed again
+        with the engine's default mel plan (`mel_stft`), and the input mel compared with the re-analysed one frame by frame --
+        the un-aligned mel-cepstral distortion of `mel_dtw(align=False)` over the frames both have; audio and mels stay on the
+        GPU.  Returns {'names': ['mcd', 'frames'], 'per_item': float32 [2, N] in input order, 'mean': {name: float}}.  Needs a
+        runtime with an `engine` (HipRuntime) behind the model."""
+        engine = getattr(self.compiled_infer, 'engine', None)
+        if getattr(engine, 'mel_dtw', None) is None or getattr(engine, 'mel_stft', None) is None:
+            raise ValueError('copy_synthesis needs a runtime with an engine (HipRuntime) behind the model')
+        upload = getattr(self.compiled_infer, '_uploaded', lambda x: x)
+        names = ['mcd', 'frames']
+        per_item = np.zeros((2, len(mels)), dtype=np.float32)
+        for i, mel in enumerate(mels):
+            if len(mel.shape) != 2:
+                raise ValueError(f'mels[{i}] must be [T, 80], got {tuple(mel.shape)}')
+            mel = upload(mel)[None]
+            stats = _to_numpy(engine.mel_dtw(mel, engine.mel_stft(self.infer(mel, **infer_kwargs)), n_cep=n_cep, align=False))
+            per_item[:, i] = stats[2, 0], stats[1, 0]
+        mean = {name: float(per_item[k].astype(np.float64).mean()) if len(mels) else float('nan') for k, name in enumerate(names)}
+        return {'names': names, 'per_item': per_item, 'mean': mean}
+
     def infer_exact(self, mel, *, tile_frames=4096, z=None, **kwargs):
         """Long-form vocoding without the approximation of `infer(win_len=...)`: halo tiling, bit-for-bit the samples of
         one run over the whole mel (which one C-ABI call only accepts up to ~31.7 k frames).  `denoiser_strength`: the tiles
