@@ -281,6 +281,50 @@ int tts_hip_mel_dtw(tts_hip_engine* e, const float* a, const float* b, int B, in
 int tts_hip_mel_dtw_probe(tts_hip_engine* e, const float* a, const float* b, int B, int Ta, int Tb, int n_mel,
                           const int32_t* len_a, const int32_t* len_b, int n_cep, int flags, int what, float* out, int mem,
                           void* stream);
+/* Pitch of a ragged batch of recordings, YIN (de Cheveigne & Kawahara 2002, steps 1 to 5).  audio: [B, N] float32; lengths:
+ * HOST int32 [B], each in 1 .. N, NULL = every row full; W = win.  Row b has F_b = 1 + lengths[b] / hop frames of the
+ * F = 1 + N / hop the output holds; for 1024 samples or more and hop = 256 that is the frame count of the default mel plan, so
+ * a track lines up with the mel's frames.  Frame t reads x[s + j], j = 0 .. W + tau_max - 1, s = t * hop - W / 2; a sample
+ * outside [0, lengths[b]) reads as 0.  Nothing at or behind a row's length is read (a NaN there reaches no output).
+ *   difference   d(tau) = sum_{j < W} (x[s + j] - x[s + j + tau])^2, tau = 0 .. tau_max: a direct float32 sum of non-negative
+ *                terms in the order of j (no autocorrelation, nothing cancels).
+ *   normalised   S(tau) = sum_{k = 1 .. tau} d(k);  d'(0) = 1;  d'(tau) = d(tau) * tau / S(tau), or 1 where S(tau) = 0
+ *                (silence and DC come out unvoiced).
+ *   pick         the smallest tau in [tau_min, tau_max] with d'(tau) < threshold; then, while tau + 1 <= tau_max and
+ *                d'(tau + 1) < d'(tau), tau advances by one: that is tau*, and the frame is voiced.  If no tau qualifies the
+ *                frame is unvoiced and tau* is the argmin of d' over [tau_min, tau_max], the smallest tau on ties.
+ *   interpolate  a, b, c = d'(tau* - 1), d'(tau*), d'(tau* + 1); if both neighbours lie in [1, tau_max] and a - 2b + c > 0,
+ *                delta = (a - c) / (2 (a - 2b + c)), else 0: computed in double from the three float32 values, as are
+ *                period = tau* + delta and f0 = rate / period, each rounded once to float32.
+ * out: float32 [3, B, F] = f0 in Hz (0 where unvoiced), period in samples (also of unvoiced frames), aperiodicity = d'(tau*)
+ * bit for bit; zeros at and behind F_b.  audio and out live where `mem` says.  A row's results do not depend on the rows
+ * beside it or on `mem`, bit for bit.  Needs no weights.  Refused (TTS_HIP_EINVAL, first match wins, nothing copied or
+ * launched; csrc/pitch_call.h): a NULL audio or out; B or N < 1; rate < 1; hop outside 1 .. win; win outside 2 .. 2048;
+ * tau_min < 1, tau_min >= tau_max or tau_max > 1024; a threshold outside (0, 1]; a bad mem kind; a length outside 1 .. N;
+ * N > 2^24; a buffer of the call at or above 2^31 bytes.  Synchronizes `stream` (NULL: the handle's) before returning.
+ * Test hook pitch_probe: the same arguments, returns the stage `what` dense, zeros at and behind F_b: TTS_HIP_PITCH_DIFF (d)
+ * and TTS_HIP_PITCH_CMND (d') [B, F, tau_max + 1], TTS_HIP_PITCH_PICK [2, B, F] (the voiced flag and tau* as float32).  Any
+ * other `what` is TTS_HIP_EINVAL, after the mem kind; the buffer limit covers the probe's result.                            */
+enum { TTS_HIP_PITCH_DIFF = 0, TTS_HIP_PITCH_CMND = 1, TTS_HIP_PITCH_PICK = 2 };
+int tts_hip_pitch(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate, int hop, int win,
+                  int tau_min, int tau_max, float threshold, float* out, int mem, void* stream);
+int tts_hip_pitch_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate, int hop, int win,
+                        int tau_min, int tau_max, float threshold, int what, float* out, int mem, void* stream);
+/* Two F0 tracks compared along a path, per row: F0 RMSE, voicing error and gross pitch error, the figures reported beside
+ * MCD-DTW.  f0_a: [B, Fa], f0_b: [B, Fb] float32 in Hz; a frame is voiced iff its value is > 0 (a NaN is unvoiced).  len_a,
+ * len_b: HOST int32 [B], each in 1 .. Fa / 1 .. Fb, NULL = every row full.  path: NULL = the diagonal (t, t), t < min(la, lb);
+ * else int32 [B, P, 2] as tts_hip_mel_dtw writes it, living where `mem` says: a row's path ends at its first pair with a
+ * negative index or an index at or beyond its row's frames (i >= la or j >= lb), so a malformed path can shorten a result
+ * but never cause a read out of range.  Over the pairs (i, j) of a row, with c = 1200 log2(f0_a[i] / f0_b[j]) in double:
+ *   stats: float32 [6, B] = pairs; voiced_pairs (both frames voiced); rmse_cents = sqrt(mean c^2) and mean_cents = mean c over
+ *   the voiced pairs (0 where there are none); vuv_errors (exactly one frame voiced); gross_errors (both voiced and
+ *   |c| > gross_cents).  Sums in double, rounded once; counts exact.
+ * A row's results do not depend on the rows beside it or on `mem`, bit for bit.  Refused (TTS_HIP_EINVAL, first match wins;
+ * csrc/pitch_call.h): a NULL f0_a, f0_b or stats; B, Fa or Fb < 1; with a path, P < 1; a gross_cents that is not finite and
+ * positive; a bad mem kind; a length outside its range; Fa or Fb > 8192; with a path, P > Fa + Fb; B * (Fa + Fb) > 2^19.
+ * Synchronizes `stream` (NULL: the handle's) before returning.                                                                */
+int tts_hip_f0_error(tts_hip_engine* e, const float* f0_a, const float* f0_b, int B, int Fa, int Fb, const int32_t* len_a,
+                     const int32_t* len_b, const int32_t* path, int P, float gross_cents, float* stats, int mem, void* stream);
 /* Runs the encoder for another token batch INTO an existing encoded batch (its device buffer is reused and only grows):
  * what a caller that synthesizes sentence after sentence wants -- no hipMalloc / hipFree per sentence, and the decoder's
  * cached step graphs (keyed by the buffer) survive from one sentence to the next.  Asynchronous like `encode`.        */

@@ -94,6 +94,12 @@ SIGNATURES = {
                                 c_void_p, c_int, c_void_p]),
     'tts_hip_mel_dtw_probe': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                       c_void_p, c_int, c_void_p]),
+    'tts_hip_pitch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int,
+                              c_void_p]),
+    'tts_hip_pitch_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                    c_void_p, c_int, c_void_p]),
+    'tts_hip_f0_error': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                 c_void_p, c_int, c_void_p]),
     'tts_hip_tacotron2_reencode': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     'tts_hip_encoded_free': (c_int, [c_void_p, c_void_p]),
     'tts_hip_kernel_timing': (c_int, [c_void_p, c_int]),

@@ -12,7 +12,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 mkdir -p "$bdir"
 objs=()
 pids=()
-for src in engine waveglow wg_encode wn_wino tacotron2 taco_forward taco_loss mel_dtw taco_persist taco_fused mel_stft stft_inv audio_proc resample silence; do
+for src in engine waveglow wg_encode wn_wino tacotron2 taco_forward taco_loss mel_dtw pitch taco_persist taco_fused mel_stft stft_inv audio_proc resample silence; do
   obj="$bdir/$src.o"
   objs+=("$obj")
   stale=0

@@ -251,6 +251,12 @@ struct MelDtwDev {
     DevBuf ws;                          // MelDtwLayout (mel_dtw_call.h)
 };
 
+// Pitch tracks and their comparison (pitch.hip): no weights and no tables, the one workspace of a call
+struct PitchDev {
+    std::vector<int32_t> lens_h;        // host image of a call's length tables while it is staged
+    DevBuf ws;                          // PitchLayout / F0ErrorLayout (pitch_call.h)
+};
+
 struct TimedLaunch {
     hipEvent_t a, b;
     int kind;
@@ -268,6 +274,7 @@ struct tts_hip_engine {
     AudioProcDev aproc;
     ResampleDev resamp;
     MelDtwDev dtw;
+    PitchDev pitch;
     // Host staging of every synchronous audio call (AudioStage).  One buffer serves them all: calls on one handle are
     // serialised by the caller and a synchronous call drains the stream before it returns, so no call finds another's data
     // still in use here; a call that needs more than its predecessors reallocates it before it copies anything in.
@@ -403,6 +410,7 @@ void melstft_free(tts_hip_engine* e);
 void audioproc_free(tts_hip_engine* e);
 void resample_free(tts_hip_engine* e);
 void mel_dtw_free(tts_hip_engine* e);
+void pitch_free(tts_hip_engine* e);
 
 // shared helpers
 // n floats of device-side samples into `out` on `st` (engine.hip: Philox4x32-10; kind = TTS_HIP_RANDOM_*)

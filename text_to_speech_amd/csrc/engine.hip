@@ -297,6 +297,7 @@ int tts_hip_destroy(tts_hip_engine* e) {
     audioproc_free(e);
     resample_free(e);
     mel_dtw_free(e);
+    pitch_free(e);
     e->audio_io.release();
     (void)hipStreamDestroy(e->stream);
     delete e;

@@ -67,12 +67,19 @@
 // <message>"; when the call is accepted "R W K skew_i aligned" and the thirteen offsets, out_elems and bytes of mel_dtw_layout,
 // and with dct=1 the R * n_mel values of mel_dtw_dct, one per line (tests/test_mel_dtw.py compares them with a Python
 // restatement).
+//        ttsw_check_asan --pitch [KEY=VALUE...]  -- the front end of a pitch call or of an F0 comparison (pitch_call.h) run as an
+// entry point named "who".  Settings of a pitch call: B= N= rate= hop= win= tau_min= tau_max= threshold= (nan and inf are
+// understood) mem= probe=1 what= len=N,N,... (the length table; absent: NULL), null=audio,out.  With f0=1 an F0 comparison: B=
+// Fa= Fb= P= path=0|1 gross= mem= la=N,N,... lb=N,N,... null=f0_a,f0_b,stats.  First line "<status> <message>"; when the call is
+// accepted "F threads lens in out out_elems bytes" of pitch_layout, or "lens in_a in_b path stats bytes" of f0_error_layout
+// (tests/test_pitch.py compares them with a Python restatement).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
 
 #include "audio_call.h"
 #include "mel_dtw_call.h"
+#include "pitch_call.h"
 #include "taco_call.h"
 #include "taco_loss_call.h"
 #include "ttsw_host.h"
@@ -493,7 +500,64 @@ static int print_mel_dtw(int argc, char** argv) {
     return 0;
 }
 
+static int print_pitch(int argc, char** argv) {
+    std::map<std::string, long long> v{{"B", 1}, {"N", 4096}, {"rate", 22050}, {"hop", 256}, {"win", 1024}, {"tau_min", 45},
+                                       {"tau_max", 367}, {"mem", TTS_HIP_MEM_HOST}, {"probe", 0}, {"what", -1}, {"f0", 0}, {"Fa", 1},
+                                       {"Fb", 1}, {"P", 1}, {"path", 0}};
+    std::map<std::string, double> f{{"threshold", 0.1}, {"gross", 315.64}};
+    std::map<std::string, std::vector<int32_t>> tables;
+    std::string nulls;
+    for (int i = 2; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) return 2;
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        if (key == "null") nulls = eq + 1;
+        else if (key == "len" || key == "la" || key == "lb") {
+            std::vector<int32_t>& t = tables[key];
+            for (const char* p = eq + 1; *p;) {
+                char* end = nullptr;
+                t.push_back((int32_t)strtol(p, &end, 10));
+                if (end == p) return 2;
+                p = *end == ',' ? end + 1 : end;
+            }
+        } else if (f.count(key)) f[key] = strtod(eq + 1, nullptr);
+        else if (v.count(key)) v[key] = atoll(eq + 1);
+        else return 2;
+    }
+    // a table shorter than B would be read past its end by the check: that is the caller's contract, not the check's
+    for (const auto& kv : tables)
+        if ((long long)kv.second.size() < v["B"]) return 2;
+    const auto table = [&](const char* name) { return tables.count(name) ? tables[name].data() : (const int32_t*)nullptr; };
+    // never read: the checks only test the pointers' values
+    const auto ptr = [&](const char* name, unsigned long long a) {
+        return ("," + nulls + ",").find(std::string(",") + name + ",") != std::string::npos ? nullptr : (void*)(uintptr_t)a;
+    };
+    char why[256] = "";
+    if (v["f0"]) {
+        const F0ErrorCall c{"who", (const float*)ptr("f0_a", 0x100000000ull), (const float*)ptr("f0_b", 0x200000000ull), (int)v["B"],
+                            (int)v["Fa"], (int)v["Fb"], table("la"), table("lb"),
+                            v["path"] ? (const int32_t*)(uintptr_t)0x400000000ull : nullptr, (int)v["P"], (float)f["gross"],
+                            (float*)ptr("stats", 0x300000000ull), (int)v["mem"], nullptr};
+        const int rc = f0_error_check(c, why, sizeof why);
+        printf("%d %s\n", rc, why);
+        if (rc) return 0;
+        const F0ErrorLayout l = f0_error_layout(c);
+        printf("%zu %zu %zu %zu %zu %zu\n", l.lens, l.in_a, l.in_b, l.path, l.stats, l.bytes);
+        return 0;
+    }
+    const PitchCall c{"who", (const float*)ptr("audio", 0x100000000ull), (int)v["B"], (int)v["N"], table("len"), (int)v["rate"],
+                      (int)v["hop"], (int)v["win"], (int)v["tau_min"], (int)v["tau_max"], (float)f["threshold"], v["probe"] != 0,
+                      (int)v["what"], (float*)ptr("out", 0x500000000ull), (int)v["mem"], nullptr};
+    const int rc = pitch_check(c, why, sizeof why);
+    printf("%d %s\n", rc, why);
+    if (rc) return 0;
+    const PitchLayout l = pitch_layout(c);
+    printf("%d %d %zu %zu %zu %zu %zu\n", l.F, l.threads, l.lens, l.in, l.out, l.out_elems, l.bytes);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--pitch")) return print_pitch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--mel-dtw")) return print_mel_dtw(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--taco-loss")) return print_taco_loss(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "--taco-call")) return print_taco_call(argc, argv);

@@ -731,6 +731,99 @@ class HipEngine:
                           lambda ins, outs, where: (*ins, B, Ta, Tb, n_mel, la, lb, n_cep, flags, self.DTW_STAGES[what], outs[0], *where),
                           device=_is_torch_cuda(a) or _is_torch_cuda(b), twin=False)[0]
 
+    # ------------------------------------------------------------------ pitch tracks (YIN) and their comparison
+    PITCH_STAGES = {'difference': 0, 'cmnd': 1, 'pick': 2}      # TTS_HIP_PITCH_*
+    PITCH_MAX_WIN, PITCH_MAX_LAG = 2048, 1024
+    GROSS_CENTS = 1200.0 * float(np.log2(1.2))                  # a gross pitch error: more than 20 % off
+
+    def _pitch_request(self, who, audio, lengths, rate, hop, win, fmin, fmax, threshold):
+        """The checked arguments of a `pitch` / `pitch_probe` call -> (B, N, F, lengths, rate, hop, win, tau_min, tau_max,
+        threshold).  Raises before any library call."""
+        from .pitch import hz_to_lags
+        shape = self._batched(audio, 2)
+        if shape is None or min(shape) < 1:
+            raise ValueError(f'{who}: audio must be [B, N] (or one row [N]), got {_dims(audio)}')
+        B, N = shape
+        for name, v in (('rate', rate), ('hop', hop), ('win', win)):
+            if v != int(v) or int(v) < 1:
+                raise ValueError(f'{who}: {name} = {v!r} must be a positive integer')
+        rate, hop, win = int(rate), int(hop), int(win)
+        if not 2 <= win <= self.PITCH_MAX_WIN:
+            raise ValueError(f'{who}: win = {win} is outside [2, {self.PITCH_MAX_WIN}]')
+        if hop > win:
+            raise ValueError(f'{who}: hop = {hop} is outside [1, win = {win}]')
+        tau_min, tau_max = hz_to_lags(rate, fmin, fmax)
+        if tau_min < 1 or tau_min >= tau_max or tau_max > self.PITCH_MAX_LAG:
+            raise ValueError(f'{who}: fmin = {fmin!r}, fmax = {fmax!r} at rate {rate} give the lags [{tau_min}, {tau_max}]: '
+                             f'need 1 <= tau_min < tau_max <= {self.PITCH_MAX_LAG}')
+        if not 0.0 < float(np.float32(threshold)) <= 1.0:             # as the library receives it: a float32
+            raise ValueError(f'{who}: threshold = {threshold!r} is outside (0, 1] as a float32')
+        if N > 2 ** 24:
+            raise ValueError(f'{who}: N = {N} is above 2^24 samples')
+        lens = None if lengths is None else self._row_table(lengths, B, 1, N, who, 'lengths')
+        return B, N, 1 + N // hop, lens, rate, hop, win, tau_min, tau_max, float(threshold)
+
+    def pitch(self, audio, lengths=None, *, rate=22050, hop=256, win=1024, fmin=60., fmax=500., threshold=0.1, stream=None):
+        """YIN pitch tracks of `audio` [B, N] (tts_hip_pitch; the math is pinned in include/tts_hip.h).  `lengths` [B], each in
+        1 .. N (default: full): nothing at or behind a row's length is read.  Lags tau_min = ceil(rate / fmax) ..
+        tau_max = floor(rate / fmin) are searched (45 .. 367 at the defaults), over windows of `win` samples every `hop`.
+        Returns float32 [3, B, F], F = 1 + N // hop: f0 in Hz (0 where unvoiced), the period in samples, the aperiodicity
+        d'(tau*); zeros at and behind a row's 1 + lengths[b] // hop frames.  For hop = 256 and 1024 samples or more the frames
+        are those of the default mel plan.  One row without the batch axis is taken as B = 1.  numpy in gives numpy out, a
+        CUDA tensor in gives a CUDA tensor out, on `stream` (a torch.cuda.Stream) if one is given.  Returns after `stream` (or
+        the engine's stream) has drained.  Needs no weights."""
+        B, N, F, lens, rate, hop, win, tau_min, tau_max, threshold = self._pitch_request('pitch', audio, lengths, rate, hop, win, fmin,
+                                                                                         fmax, threshold)
+        return self._call('pitch', [(audio, (B, N), 'float32')], lambda new: (new((3, B, F)),),
+                          lambda ins, outs, where: (ins[0], B, N, lens, rate, hop, win, tau_min, tau_max, threshold, outs[0], *where),
+                          stream, twin=False)[0]
+
+    def pitch_probe(self, audio, lengths=None, *, rate=22050, hop=256, win=1024, fmin=60., fmax=500., threshold=0.1, what='cmnd'):
+        """Test hook (tts_hip_pitch_probe): one stage of `pitch`, dense with zeros at and behind a row's frames:
+        what='difference' (d) / 'cmnd' (d') [B, F, tau_max + 1], 'pick' [2, B, F] (the voiced flag and tau* as float32)."""
+        if what not in self.PITCH_STAGES:
+            raise ValueError(f'what must be one of {tuple(self.PITCH_STAGES)}, got {what!r}')
+        B, N, F, lens, rate, hop, win, tau_min, tau_max, threshold = self._pitch_request('pitch_probe', audio, lengths, rate, hop, win,
+                                                                                         fmin, fmax, threshold)
+        shape = (2, B, F) if what == 'pick' else (B, F, tau_max + 1)
+        if int(np.prod(shape)) * 4 >= 2 ** 31:
+            raise ValueError(f'pitch_probe: a result of shape {shape} is 2^31 bytes or more')
+        return self._call('pitch_probe', [(audio, (B, N), 'float32')], lambda new: (new(shape),),
+                          lambda ins, outs, where: (ins[0], B, N, lens, rate, hop, win, tau_min, tau_max, threshold,
+                                                    self.PITCH_STAGES[what], outs[0], *where), twin=False)[0]
+
+    def f0_error(self, f0_a, f0_b, lengths_a=None, lengths_b=None, path=None, *, gross_cents=GROSS_CENTS, stream=None):
+        """F0 tracks `f0_a` [B, Fa] against `f0_b` [B, Fb] (Hz, a frame is voiced iff > 0) along `path` (tts_hip_f0_error):
+        None = the diagonal below the shorter length, else int32 [B, P, 2] as `mel_dtw(return_path=True)` returns it -- a
+        row's path ends at its first pair that is negative or out of the row's frames.  `lengths_*` [B]: the real frames of
+        each row (default: full).  Returns float32 [6, B] = pairs, voiced_pairs, rmse_cents, mean_cents, vuv_errors,
+        gross_errors (both voiced and more than `gross_cents` apart; the default is 20 %).  One row of each operand without
+        the batch axis is taken as B = 1.  numpy in gives numpy out; if any operand is a CUDA tensor the others are moved to the
+        GPU and a CUDA tensor comes back, on `stream` if one is given.  Needs no weights."""
+        sa, sb = self._batched(f0_a, 2) if len(_dims(f0_a)) == len(_dims(f0_b)) else None, self._batched(f0_b, 2)
+        if sa is None or sb is None or sa[0] != sb[0] or min(sa + sb) < 1:
+            raise ValueError(f'f0_error: f0_a and f0_b must be [B, Fa] and [B, Fb] (or one row of each), got {_dims(f0_a)} and {_dims(f0_b)}')
+        (B, Fa), Fb = sa, sb[1]
+        P = 0
+        if path is not None:
+            sp = _dims(path)
+            sp = (1, *sp) if len(sp) == 2 and len(_dims(f0_a)) == 1 else sp
+            if len(sp) != 3 or sp[0] != B or sp[1] < 1 or sp[2] != 2:
+                raise ValueError(f'f0_error: path must be [B = {B}, P, 2], got {_dims(path)}')
+            P = sp[1]
+            if P > Fa + Fb:
+                raise ValueError(f'f0_error: a path of {P} pairs is longer than Fa + Fb = {Fa + Fb}')
+        if not (np.isfinite(np.float32(gross_cents)) and np.float32(gross_cents) > 0):
+            raise ValueError(f'f0_error: gross_cents = {gross_cents!r} must be finite and positive')
+        if Fa > 8192 or Fb > 8192 or B * (Fa + Fb) > 2 ** 19:
+            raise ValueError(f'f0_error: B = {B}, Fa = {Fa}, Fb = {Fb} is above 8192 frames a side or 2^19 frames in all; split the batch')
+        la = None if lengths_a is None else self._row_table(lengths_a, B, 1, Fa, 'f0_error', 'lengths_a')
+        lb = None if lengths_b is None else self._row_table(lengths_b, B, 1, Fb, 'f0_error', 'lengths_b')
+        return self._call('f0_error', [(f0_a, (B, Fa), 'float32'), (f0_b, (B, Fb), 'float32'), (path, None if path is None else (B, P, 2), 'int32')],
+                          lambda new: (new((6, B)),),
+                          lambda ins, outs, where: (ins[0], ins[1], B, Fa, Fb, la, lb, ins[2], P, float(gross_cents), outs[0], *where),
+                          stream, device=any(_is_torch_cuda(x) for x in (f0_a, f0_b, path)), twin=False)[0]
+
     def set_decoder_mode(self, mode: str) -> None:
         """How the autoregressive decoder loop runs: 'auto' (default: the persistent weight-stationary kernel for 1 - 2 rows,
         the fused two-kernel step for 3 - 8 rows, whichever applies otherwise), 'persistent' / 'fused' (that machine when the

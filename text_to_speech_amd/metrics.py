@@ -1,9 +1,13 @@
-"""Objective figures of a synthesis against its recording, computed on the GPU (`HipEngine.mel_dtw`, tts_hip_mel_dtw).
+"""Objective figures of a synthesis against its recording, computed on the GPU (`HipEngine.mel_dtw`, tts_hip_mel_dtw;
+`HipEngine.f0_error`, tts_hip_f0_error).
 
 Mel-cepstral distortion along a dynamic-time-warping path (MCD-DTW): the two mels are not aligned in time, so each frame of
 one is compared with the frame of the other the cheapest monotone path pairs it with.  The cepstra are the orthonormal DCT-II
 of the model's own log-mel (coefficients 1 .. n_cep), not WORLD / SPTK mel-cepstra: figures are comparable between
 checkpoints of one mel configuration, not with published MCD tables.
+
+F0 error: two pitch tracks (`pitch.estimate_f0`) compared along the same path -- the RMSE of the voiced pairs in cents, the
+voicing (V/UV) error rate and the gross pitch error rate (voiced pairs more than 20 % apart).
 """
 from __future__ import annotations
 
@@ -30,3 +34,26 @@ def dtw_path(engine, a, b, lengths_a=None, lengths_b=None, *, n_cep=13, include_
     stats, path = engine.mel_dtw(a, b, lengths_a, lengths_b, n_cep=n_cep, include_c0=include_c0, return_path=True)
     stats, path = _to_numpy(stats), _to_numpy(path)
     return [path[r, :int(stats[1, r])].copy() for r in range(path.shape[0])]
+
+
+F0_STATS = ('pairs', 'voiced_pairs', 'rmse_cents', 'mean_cents', 'vuv_errors', 'gross_errors')
+
+
+def f0_error(engine, f0_a, f0_b, lengths_a=None, lengths_b=None, path=None, **kwargs):
+    """F0 tracks `f0_a` [B, Fa] against `f0_b` [B, Fb] (Hz, voiced iff > 0; `lengths_*`: the real frames of each row) along
+    `path` on `engine`, a `HipEngine` or a `HipRuntime`; `kwargs`: `gross_cents`, `stream`.  `path`: None (the diagonal), the
+    [B, P, 2] array or CUDA tensor of `mel_dtw(return_path=True)` -- taken as it is, it does not leave the GPU -- or the list
+    `dtw_path` returns.  -> a dict of the six F0_STATS, each [B], plus 'vuv_error' = vuv_errors / pairs and 'gross_error' =
+    gross_errors / voiced_pairs (0 where the denominator is): numpy for numpy operands, CUDA tensors if any operand is one."""
+    if isinstance(path, (list, tuple)):
+        P = max(1, max(len(p) for p in path))
+        dense = np.full((len(path), P, 2), -1, np.int32)
+        for r, p in enumerate(path):
+            dense[r, :len(p)] = p
+        path = dense
+    stats = engine.f0_error(f0_a, f0_b, lengths_a, lengths_b, path, **kwargs)
+    out = {name: stats[k] for k, name in enumerate(F0_STATS)}
+    one = stats[0] * 0 + 1
+    out['vuv_error'] = stats[4] / (stats[0] + (stats[0] == 0) * one)
+    out['gross_error'] = stats[5] / (stats[1] + (stats[1] == 0) * one)
+    return out

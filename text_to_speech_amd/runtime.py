@@ -312,6 +312,20 @@ class HipRuntime(Runtime):
         `return_path=True`.  The mel of `tacotron2_infer(..., on_device=True)` goes in without leaving the GPU."""
         return self.engine.mel_dtw(a, b, lengths_a, lengths_b, **kwargs)
 
+    # ------------------------------------------------------------------ pitch (include/tts_hip.h: tts_hip_pitch, tts_hip_f0_error)
+    def pitch(self, audio, lengths=None, **kwargs):
+        """YIN pitch tracks of `audio` [B, N] on the engine (`HipEngine.pitch`, whose keywords these are) -> float32 [3, B, F]
+        (f0 in Hz, period, aperiodicity).  The vocoder's audio on the GPU goes in without leaving it."""
+        return self.engine.pitch(audio, lengths, **kwargs)
+
+    def pitch_probe(self, audio, lengths=None, **kwargs):
+        """Test hook: one stage of `pitch` (`HipEngine.pitch_probe`)."""
+        return self.engine.pitch_probe(audio, lengths, **kwargs)
+
+    def f0_error(self, f0_a, f0_b, lengths_a=None, lengths_b=None, path=None, **kwargs):
+        """Two F0 tracks compared along a path (`HipEngine.f0_error`, whose keywords these are) -> float32 [6, B]."""
+        return self.engine.f0_error(f0_a, f0_b, lengths_a, lengths_b, path, **kwargs)
+
     def _draw(self, purpose, rows, frames, explicit, deterministic, seed, streams=None):
         """Where a call's random values (`purpose`: MASK_STREAM / NOISE_STREAM) come from -> (stream, row streams), at most
         one of them set: row streams ([key per row], [0 per row]) for `streams` ids, keyed by `seed` or the runtime's seed;

@@ -182,7 +182,10 @@ class Tacotron2:
 
     SYNTHESIS_NAMES = ['mcd_dtw', 'path_len', 'frames', 'target_frames', 'frame_ratio', 'stopped']
 
-    def evaluate_synthesis(self, items, *, batch_size=8, max_length=10., n_cep=13, deterministic=True, **load_kwargs):
+    SYNTHESIS_F0_NAMES = ['f0_rmse_cents', 'vuv_error', 'gross_error', 'voiced_pairs']
+
+    def evaluate_synthesis(self, items, *, batch_size=8, max_length=10., n_cep=13, deterministic=True, vocoder=None, pitch=None,
+                           **load_kwargs):
         """The model as it is used -- free-running, through its own stop token and attention -- against held-out recordings:
         mel-cepstral distortion along the DTW path (`metrics`, tts_hip_mel_dtw) of every synthesized mel against its
         recording's.  `items` as for `evaluate`: (text, mel [F, 80]) or (text, audio) pairs; `embeddings=`: the speaker.
@@ -193,29 +196,57 @@ class Tacotron2:
         gave 0 frames is left out of the DTW call and of the means: mcd_dtw, path_len and frame_ratio NaN, frames 0, stopped 1.
         Returns {'names': SYNTHESIS_NAMES, 'per_item': float32 [6, N] in input order, 'mean': {name: float} over the rows that
         produced frames}; `stopped` is 1 where the row ended by its stop token before the batch's frame cap.  Needs a runtime
-        with `mel_dtw` (HipRuntime) behind the model."""
+        with `mel_dtw` (HipRuntime) behind the model.
+        `vocoder` (a `WaveGlow` wrapper; default None: names and values as above): intonation as well.  Every item must then be
+        (text, audio) -- a (text, mel) item raises, there is no recording to track; the recording is loaded once
+        (`audio.load_audio` with `load_kwargs`, `stft_fn` aside) and its mel taken from those samples.  The batch's mels are vocoded in one ragged
+        call (`vocoder.infer(mel, lengths=frames)`), `pitch` (tts_hip_pitch; `pitch`: its keywords, the hop stays 256 so that
+        the tracks share the mels' frames) runs on the vocoded and on the recorded audio, the DTW call also returns its path,
+        and `f0_error` along that path appends SYNTHESIS_F0_NAMES: the F0 RMSE of the voiced pairs in cents, the voicing error
+        rate (of the pairs), the gross pitch error rate (of the voiced pairs; 0 without any) and the voiced pairs.  Audio,
+        tracks and path stay on the GPU; it needs `pitch` and `f0_error` on the runtime as well."""
         load_kwargs = dict(self._resolve_embeddings(load_kwargs))
         embeddings = load_kwargs.pop('embeddings', None)
         runtime = self.compiled_infer
         if getattr(runtime, 'mel_dtw', None) is None or not callable(runtime):
             raise ValueError('evaluate_synthesis needs a runtime with mel_dtw (HipRuntime) behind the model')
+        pitch = dict(pitch or {})
+        if vocoder is not None:
+            if getattr(runtime, 'pitch', None) is None or getattr(runtime, 'f0_error', None) is None:
+                raise ValueError('evaluate_synthesis(vocoder=) needs a runtime with pitch and f0_error (HipRuntime) behind the model')
+            if int(pitch.get('hop', 256)) != 256:
+                raise ValueError(f"evaluate_synthesis: the pitch tracks share the mels' frames, hop must stay 256, got {pitch['hop']!r}")
+        elif pitch:
+            raise ValueError('evaluate_synthesis: pitch= configures the tracker of vocoder=, which is None')
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError(f'batch_size must be at least 1, got {batch_size}')
-        prepared = []
+        prepared, waves = [], []
         for i, item in enumerate(items):
             if not isinstance(item, (tuple, list)) or len(item) != 2:
                 raise ValueError(f'items[{i}] must be a (text, mel) or (text, audio) pair')
             text, recording = item
             is_mel = not isinstance(recording, str) and len(getattr(recording, 'shape', ())) >= 2
-            mel = self._recording_mel(recording if is_mel else None, None if is_mel else recording, load_kwargs)
+            if vocoder is not None and is_mel:
+                raise ValueError(f'items[{i}] is a (text, mel) pair: with vocoder= the pitch of the recording is tracked, pass (text, audio)')
+            if vocoder is not None:
+                # loaded once, with the waveform's keywords only; the mel is that of these very samples, taken as they are
+                from .audio import load_audio
+                audio_kwargs = {k: v for k, v in load_kwargs.items() if k != 'stft_fn'}
+                wave = load_audio(recording, self.rate, engine=getattr(runtime, 'engine', None), **audio_kwargs)
+                wave = np.asarray(_to_numpy(wave), dtype=np.float32).reshape(-1)
+                waves.append(wave)
+                mel_kwargs = {'stft_fn': load_kwargs['stft_fn']} if load_kwargs.get('stft_fn') is not None else {}
+                mel = self._recording_mel(None, wave, dict(mel_kwargs, normalize=False))
+            else:
+                mel = self._recording_mel(recording if is_mel else None, None if is_mel else recording, load_kwargs)
             tokens = np.asarray(self.encode_text(self.clean_text(text), cleaned=True), dtype=np.int32)
             if tokens.size == 0:
                 raise ValueError(f'items[{i}]: the text encodes to no token')
             prepared.append((tokens, mel))
         if not prepared:
             raise ValueError('evaluate_synthesis needs at least one item')
-        names = self.SYNTHESIS_NAMES
+        names = self.SYNTHESIS_NAMES + (self.SYNTHESIS_F0_NAMES if vocoder is not None else [])
         per_item = np.full((len(names), len(prepared)), np.nan, dtype=np.float32)
         pad = np.float32(self.pad_mel_value)
         for r0 in range(0, len(prepared), batch_size):
@@ -233,7 +264,25 @@ class Tacotron2:
             block = per_item[:, r0:r0 + B]
             block[2], block[3], block[5] = frames, wanted, frames < cap
             keep = np.flatnonzero(frames > 0)
-            if keep.size:
+            if keep.size and vocoder is not None:
+                mel = out.mel if keep.size == B else out.mel[keep.tolist()]
+                la, lb = frames[keep].astype(np.int32), wanted[keep].astype(np.int32)
+                stats, path = runtime.mel_dtw(mel, target if keep.size == B else target[keep], la, lb, n_cep=n_cep, return_path=True)
+                stats = _to_numpy(stats)
+                block[0, keep], block[1, keep], block[4, keep] = stats[2], stats[1], frames[keep] / wanted[keep]
+                spoken = [waves[r0 + r] for r in keep]
+                recorded = np.zeros((keep.size, max(len(w) for w in spoken)), dtype=np.float32)
+                for r, w in enumerate(spoken):
+                    recorded[r, :len(w)] = w
+                samples = np.asarray([len(w) for w in spoken], dtype=np.int32)
+                f0_syn = runtime.pitch(vocoder.infer(mel, lengths=la), la * 256, **pitch)[0]
+                f0_rec = runtime.pitch(recorded, samples, **pitch)[0]
+                # a recording below 1024 samples has fewer pitch frames than mel frames: the path ends where the track does
+                f0 = _to_numpy(runtime.f0_error(f0_syn, f0_rec, la, np.minimum(lb, 1 + samples // 256).astype(np.int32), path))
+                block[6, keep], block[9, keep] = f0[2], f0[1]
+                block[7, keep] = f0[4] / np.maximum(f0[0], 1)
+                block[8, keep] = f0[5] / np.maximum(f0[1], 1)
+            elif keep.size:
                 whole = keep.size == B                               # (no copy of the mel when every row produced frames)
                 stats = _to_numpy(runtime.mel_dtw(out.mel if whole else out.mel[keep.tolist()], target if whole else target[keep],
                                                   frames[keep].astype(np.int32), wanted[keep].astype(np.int32), n_cep=n_cep))

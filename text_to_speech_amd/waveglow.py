@@ -298,6 +298,35 @@ class WaveGlow:
         mean = {name: float(per_item[k].astype(np.float64).mean()) if len(mels) else float('nan') for k, name in enumerate(names)}
         return {'names': names, 'per_item': per_item, 'mean': mean}
 
+    RESYNTHESIS_NAMES = ['f0_rmse_cents', 'f0_mean_cents', 'vuv_error', 'gross_error', 'voiced_pairs', 'pairs']
+
+    def resynthesis_f0(self, items, **infer_kwargs):
+        """Does the vocoder keep the pitch?  `items` as for `evaluate`: recordings (waveforms or file names) or (audio, mel)
+        pairs, each prepared by `_recording`.  The mel is vocoded (`infer` with `infer_kwargs`), `pitch` (tts_hip_pitch, the
+        defaults at the model's rate) runs on the recording zero-padded to frames * 256 samples and on the vocoded audio, and
+        `f0_error` compares the two tracks on the diagonal; audio and tracks stay on the GPU.  Returns {'names':
+        RESYNTHESIS_NAMES, 'per_item': float32 [6, N] in input order, 'mean': {name: float}}: the F0 RMSE and the mean
+        deviation of the voiced pairs in cents, the voicing error rate (of the pairs), the gross pitch error rate (more than
+        20 % off; of the voiced pairs, 0 without any), the voiced pairs and the pairs.  Needs a runtime with an `engine`
+        (HipRuntime) behind the model."""
+        engine = getattr(self.compiled_infer, 'engine', None)
+        if getattr(engine, 'pitch', None) is None or getattr(engine, 'f0_error', None) is None:
+            raise ValueError('resynthesis_f0 needs a runtime with an engine (HipRuntime) behind the model')
+        upload = getattr(self.compiled_infer, '_uploaded', lambda x: x)
+        names = self.RESYNTHESIS_NAMES
+        per_item = np.zeros((len(names), len(items)), dtype=np.float32)
+        for i, item in enumerate(items):
+            audio, mel = item if isinstance(item, tuple) else (item, None)
+            wave, mel = self._recording(audio, mel, {})
+            if mel.shape[0] < 1:
+                raise ValueError(f'items[{i}] holds no frame')
+            vocoded = self.infer(upload(mel)[None], **infer_kwargs)
+            f0_rec, f0_voc = engine.pitch(upload(wave)[None], rate=self.rate)[0], engine.pitch(vocoded, rate=self.rate)[0]
+            s = _to_numpy(engine.f0_error(f0_rec, f0_voc))[:, 0]
+            per_item[:, i] = s[2], s[3], s[4] / max(s[0], 1), s[5] / max(s[1], 1), s[1], s[0]
+        mean = {name: float(per_item[k].astype(np.float64).mean()) if len(items) else float('nan') for k, name in enumerate(names)}
+        return {'names': list(names), 'per_item': per_item, 'mean': mean}
+
     def infer_exact(self, mel, *, tile_frames=4096, z=None, **kwargs):
         """Long-form vocoding without the approximation of `infer(win_len=...)`: halo tiling, bit-for-bit the samples of
         one run over the whole mel (which one C-ABI call only accepts up to ~31.7 k frames).  `denoiser_strength`: the tiles
