@@ -643,6 +643,56 @@ int tts_hip_denoise_async(tts_hip_engine* e, const float* audio, int B, int N, c
 int tts_hip_denoise_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const tts_hip_mel_fn* fn,
                           const float* bias, double strength, int what, float* out, int mem);
 
+/* ---- time stretch (csrc/stft_inv.hip): a phase vocoder with identity phase locking (Laroche and Dolson 1999) between the
+ * transform and the inverse of a Tacotron-kind plan.  Only spectral peaks accumulate phase; every other bin keeps the
+ * analysis-phase relation to its nearest peak, so the bins of one partial cannot drift apart when the rate is below 1.
+ *
+ * time_stretch: audio [B, N], lengths as tts_hip_mel_fn_run, rates [B] (HOST doubles in every mode) -> out [B, M].  With
+ *   cut = filter_length / 2 + 1, row b of L_b samples at rate r_b (> 1 faster, < 1 slower):
+ *   1. X_b[f][k], f < F_b = tts_hip_mel_fn_frames(fn, L_b), is the spectrum of steps 1 - 4 of the mel plan (stage 1 of
+ *      tts_hip_mel_fn_probe); X_b[F_b][k] = 0.
+ *   2. T_b is the smallest T with (double)T * r_b >= F_b; for t < T_b: pos = (double)t * r_b, i = floor(pos),
+ *      a = (float)(pos - i).
+ *   3. With c0 = X[i], c1 = X[i+1]: m[t][k] = (1 - a) * |c0[k]| + a * |c1[k]| in fp32, |z| = sqrtf(re * re + im * im), every
+ *      operation rounded on its own (no fused multiply-add): two products, a sum and a square root per magnitude; the
+ *      difference 1 - a, two products and a sum for m.  P(z) = z / |z|, P(0) = (1, 0) (taken from the pair scaled by its
+ *      larger component; its products may be fused).  A[t][k] = P(c1[k] * conj(c0[k])), R[t][k] = P(c0[k] * conj(c0[own[t][k]])).
+ *   4. k is a peak of frame t if m[t][k] > 0, m[t][k] > m[t][k-1], m[t][k] > m[t][k-2], m[t][k] >= m[t][k+1] and
+ *      m[t][k] >= m[t][k+2]; neighbours outside 0 .. cut - 1 count as minus infinity.  own[t][k] is the nearest peak of frame
+ *      t, a tie goes to the lower peak; a frame without a peak (all of its m are 0) has no owners.
+ *   5. U[0][k] = P(X[0][k]); for t >= 1: U[t][k] = P(U[t-1][p] * A[t-1][p] * R[t][k]) with p = own[t][k] (the products in
+ *      that order), and in a frame without peaks U[t][k] = U[t-1][k] * A[t-1][k].  Y[t][k] = m[t][k] * U[t][k].  No atan2,
+ *      sin or cos; the chain re-normalises at every step.
+ *   6. out_b = inverse(Y_b) exactly as tts_hip_stft_inverse computes it for T_b frames.  Row b of out holds S_b =
+ *      llrint((double)L_b / r_b) samples (ties to even): the leading min(S_b, tts_hip_mel_fn_samples(fn, T_b)) come from the
+ *      inverse, everything behind them is 0.  M must equal max_b S_b (and be >= 1).
+ *   tts_hip_time_stretch_samples(fn, n, rate) = S and tts_hip_time_stretch_frames(fn, n, rate) = T of a row of n samples
+ *   (host only); both are negative where the call would refuse the row, the rate or the plan.
+ *   Nothing behind a row's length is read, nothing is accumulated with atomics: a row is bit-equal to the row called alone
+ *   and a repeat gives the same bits.  rate = 1 gives a = 0, A = the analysis phase advance and the input's own phases up to
+ *   rounding: the STFT round trip.  The transform runs in the mel workspace of the handle, the vocoder and the inverse in the
+ *   inverse workspace, with no host round trip: the _async form (device pointers, a stream; lengths and rates stay host
+ *   arrays) does not synchronize.
+ *
+ * time_stretch_probe (test hook): the code of the call, not a copy, stopped after stage `what`, with F =
+ *   tts_hip_mel_fn_frames(fn, N) and T = max_b T_b: 0 spectrum X [B, F, 2 cut] (real parts, then imaginary parts); 1 m
+ *   [B, T, cut]; 2 own as floats [B, T, cut], -1 where a frame has no peak; 3 operand Y [B, T, 2 cut]; 4 time frames
+ *   [B, T, filter_length].  Output frames at and beyond T_b hold m = 0, own = -1, Y = 0.  The call itself is the last stage.
+ *
+ * Refusals (TTS_HIP_EINVAL, first match wins, nothing copied or launched; time_stretch_check in csrc/audio_call.h): a plan
+ * that is not a plan of this handle; a NULL plan, audio, out or rates, B or N < 1; a lengths[b] outside [1, N]; a row the
+ * reflect cannot pad (as tts_hip_mel_fn_run); a Whisper plan; pre_emph > 0 (the inverse does not undo it); a rate that is
+ * not finite or lies outside [0.25, 4]; M not max_b S_b, or that below 1; a buffer at or above 2^31 - 65536 bytes or
+ * B > 65535; a bad mem kind; a `what` outside 0 .. 4 (probe). */
+long long tts_hip_time_stretch_samples(const tts_hip_mel_fn* fn, int n_samples, double rate);
+int tts_hip_time_stretch_frames(const tts_hip_mel_fn* fn, int n_samples, double rate);
+int tts_hip_time_stretch(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const double* rates,
+                         const tts_hip_mel_fn* fn, float* out, int M, int mem);
+int tts_hip_time_stretch_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const double* rates,
+                               const tts_hip_mel_fn* fn, float* out, int M, void* stream);
+int tts_hip_time_stretch_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const double* rates,
+                               const tts_hip_mel_fn* fn, int what, float* out, int M, int mem);
+
 /* ---- waveform clean-up (csrc/audio_proc.hip; DFT bases built on first use, no weights needed)
  * reduce_noise: utils/audio/noisereducev1.py:175-290 with the defaults utils/audio/audio_processing.py:65-83 uses.
  *   audio [B, N] -> out [B, N]; row b has lengths[b] (1 <= lengths[b] <= N) samples, lengths NULL = N for every row, and
@@ -771,7 +821,8 @@ int tts_hip_resample_fft_probe(tts_hip_engine* e, const float* in, int lines, in
  * overlap-add, 2 = forward DFT GEMM (with its gather, where the plan has one), 3 = phase update.  A tts_hip_denoise call
  * files its four parts there too: 2 = forward DFT (padding and gather included), 3 = gate, 0 = inverse-frames GEMM, 1 =
  * overlap-add.  A tts_hip_mel_dtw call files its launches as 0 = cepstra, 1 = distances, 2 = sweep, 3 = backtrack (without
- * alignment: the diagonal's reduction).
+ * alignment: the diagonal's reduction).  A tts_hip_time_stretch call files five parts: 2 = forward DFT, 3 = the vocoder's
+ * parallel pass, 4 = its chain over the frames (the only use of kind 4), 0 = inverse-frames GEMM, 1 = overlap-add.
  * Timing is off unless enabled (events perturb nothing but cost a few us each).        */
 int tts_hip_kernel_timing(tts_hip_engine* e, int enable);
 /* Box probe: TFLOP/s a bare v_mfma_f32_32x32x2_f32 loop sustains on this device right now (every CU, 2 waves per SIMD, ~20 ms)

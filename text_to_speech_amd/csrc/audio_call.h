@@ -1,4 +1,4 @@
-// audio_call.h -- what the audio front-end calls (mel-STFT, STFT inverse / Griffin-Lim, denoise, reduce_noise / trim_silence, resample, remove_silence) may be
+// audio_call.h -- what the audio front-end calls (mel-STFT, STFT inverse / Griffin-Lim, denoise, time_stretch, reduce_noise / trim_silence, resample, remove_silence) may be
 // refused for, and the geometry those refusals rest on: pure host code on the caller's arguments (no HIP include; also built
 // with plain g++ under ASan / UBSan by csrc/host_check.cpp, --audio-call, and compared there with a Python restatement,
 // tests/test_audio_call.py).  The .hip files forward the message to set_err; nothing is copied or launched before a check
@@ -655,5 +655,98 @@ inline int denoise_check(const char* who, const MelPlan* p, const float* audio, 
         g->keep[b] = (int)std::min<long long>(g->fwd.lens[b], stft_samples(*p, g->fwd.fout[b]));
     }
     g->inv.frames = g->fwd.fout;
+    return TTS_HIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- time stretch (stft_inv.hip)
+enum { TS_SPECTRUM = 0, TS_MAGNITUDE, TS_OWNER, TS_OPERAND, TS_FRAMES, TS_STAGES };
+constexpr double kTsRateMin = 0.25, kTsRateMax = 4.0;
+
+inline bool ts_rate_ok(double r) { return std::isfinite(r) && r >= kTsRateMin && r <= kTsRateMax; }
+
+// output frames of F analysis frames at rate r: the smallest T with (double)T * r >= F (the quotient may round either way)
+inline int ts_out_frames(int F, double r) {
+    long long T = (long long)std::ceil((double)F / r);
+    while (T > 1 && (double)(T - 1) * r >= (double)F) --T;
+    while ((double)T * r < (double)F) ++T;
+    return (int)T;
+}
+
+// output samples of a row of n samples at rate r: llrint(n / r), ties to even
+inline long long ts_out_samples(int n, double r) { return std::llrint((double)n / r); }
+
+// frames / samples of a row under a plan; < 0 where time_stretch_check refuses the row or the plan
+inline int ts_row_frames(const MelPlan& p, int n, double r) {
+    if (p.kind != TTS_HIP_MEL_TACOTRON || p.pre > 0 || !ts_rate_ok(r) || mel_dft_frames(p, n) < 1) return -1;
+    return ts_out_frames(mel_dft_frames(p, n), r);
+}
+inline long long ts_row_samples(const MelPlan& p, int n, double r) { return ts_row_frames(p, n, r) < 0 ? -1 : ts_out_samples(n, r); }
+
+// A time-stretch call is a transform on the rows' own frames (`fwd`: lens, fout = F_b, its workspace in e->stft.ws), the
+// vocoder between them, and an inverse on T = max_b T_b frame slots (`inv`: frames = T_b, its workspace in e->stft.inv_ws).
+// Behind the inverse's own buffers that workspace holds the vocoder's: `rowinfo` [B] doubles rates, then [B] int32 S_b;
+// `mag` m [B * T][cut] fp32; `owner` own [B * T][cut] int32 (-1: the frame has no peak); `adv` A[t-1][own[t][k]] and
+// `rel` R[t][k], both [B * T][cut][2] fp32 (re, im).  inv.total covers them.  Row b of the result holds
+// keep[b] = min(S_b, stft_samples(T_b)) samples of the inverse, zeros up to M = max_b S_b.
+struct TsGeom {
+    MelGeom fwd;
+    GlGeom inv;
+    std::vector<double> rates;
+    std::vector<int> S, keep;
+    int M;
+    size_t off_rowinfo, off_mag, off_owner, off_adv, off_rel;
+};
+
+// What tts_hip_time_stretch[_async, _probe] may be refused for -- order: pointers (plan, audio, out, rates) / B / N,
+// lengths[b], a row reflect cannot pad, a Whisper plan, pre_emph > 0, a rate not finite or outside [0.25, 4], M not
+// max_b llrint(L_b / r_b) (or that below 1), the 31-bit limits (either workspace, the vocoder's buffers, audio [B][N] and out
+// [B][M]; B <= 65535), mem kind, what (probe: what >= 0; the call itself: -1); fills `g`
+inline int time_stretch_check(const char* who, const MelPlan* p, const float* audio, int B, int N, const int32_t* lengths,
+                              const double* rates, const float* out, int M, int mem, int what, TsGeom* g, char* msg, size_t n) {
+    if (!p || !audio || !out || !rates || B < 1 || N < 1) return audio_refuse(msg, n, who, "bad argument");
+    int min_len;
+    if (int rc = audio_rows_check(who, B, N, lengths, g->fwd.lens, &min_len, msg, n)) return rc;
+    for (int b = 0; b < B; ++b)
+        if (mel_dft_frames(*p, g->fwd.lens[b]) < 1)
+            return audio_refuse(msg, n, who, "row %d: max(L = %d, win_length = %d) samples are not more than filter_length // 2 = %d",
+                                b, g->fwd.lens[b], p->wl, p->half);
+    if (p->kind != TTS_HIP_MEL_TACOTRON) return audio_refuse(msg, n, who, "refused for a Whisper plan");
+    if (p->pre > 0) return audio_refuse(msg, n, who, "pre_emph = %g > 0 cannot be inverted", p->pre);
+    for (int b = 0; b < B; ++b)
+        if (!ts_rate_ok(rates[b]))
+            return audio_refuse(msg, n, who, "rates[%d] = %g must be finite and lie in [%g, %g]", b, rates[b], kTsRateMin, kTsRateMax);
+    g->rates.assign(rates, rates + B);
+    g->fwd.fout.resize(B);
+    g->inv.frames.resize(B);
+    g->S.resize(B);
+    g->keep.resize(B);
+    long long want = 0;
+    int T = 1;
+    for (int b = 0; b < B; ++b) {
+        g->fwd.fout[b] = mel_dft_frames(*p, g->fwd.lens[b]);
+        g->inv.frames[b] = ts_out_frames(g->fwd.fout[b], rates[b]);
+        T = std::max(T, g->inv.frames[b]);
+        const long long S = ts_out_samples(g->fwd.lens[b], rates[b]);
+        want = std::max(want, S);
+        g->S[b] = (int)S;                                       // <= 4 N
+        g->keep[b] = (int)std::min<long long>(S, stft_samples(*p, g->inv.frames[b]));
+    }
+    if (want < 1) return audio_refuse(msg, n, who, "every row stretches to 0 samples");
+    if (M != want) return audio_refuse(msg, n, who, "M = %d, but max_b llrint(lengths[b] / rates[b]) = %lld", M, want);
+    const long long cells = (long long)B * T * p->cut;
+    if (B > 65535 || mel_geom_layout(*p, B, N, &g->fwd) >= kAudioLim || cells * 8 >= kAudioLim ||
+        gl_geom_layout(*p, B, T, p->cut, -1, -1, &g->inv) >= kAudioLim || (long long)B * M * 4 >= kAudioLim)
+        return audio_refuse(msg, n, who, "B = %d x N = %d (M %d) too large for 31-bit offsets (B <= 65535)", B, N, M);
+    if (int rc = audio_mem_check(who, mem, msg, n)) return rc;
+    if (what >= TS_STAGES) return audio_refuse(msg, n, who, "no stage %d (0 .. %d)", what, TS_STAGES - 1);
+    g->M = M;
+    Carve c;
+    c.o = g->inv.total;
+    g->off_rowinfo = c.take((size_t)B * 12);
+    g->off_mag = c.take((size_t)cells * 4);
+    g->off_owner = c.take((size_t)cells * 4);
+    g->off_adv = c.take((size_t)cells * 8);
+    g->off_rel = c.take((size_t)cells * 8);
+    g->inv.total = c.o;
     return TTS_HIP_OK;
 }

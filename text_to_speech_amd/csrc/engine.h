@@ -284,8 +284,8 @@ struct tts_hip_engine {
     bool timing = false;
     std::vector<TimedLaunch> timed;
     std::vector<TimedLaunch> ev_pool;
-    double time_sum_us[4] = {0, 0, 0, 0};
-    int64_t time_cnt[4] = {0, 0, 0, 0};
+    double time_sum_us[5] = {0, 0, 0, 0, 0};
+    int64_t time_cnt[5] = {0, 0, 0, 0, 0};
 };
 
 int set_err(const tts_hip_engine* e, int code, const char* fmt, ...);

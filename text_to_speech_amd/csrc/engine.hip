@@ -65,7 +65,7 @@ void timing_collect(tts_hip_engine* e) {
     (void)hipStreamSynchronize(e->stream);
     for (auto& t : e->timed) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess && t.kind >= 0 && t.kind < 4) {
+        if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess && t.kind >= 0 && t.kind < 5) {
             e->time_sum_us[t.kind] += 1e3 * ms;
             e->time_cnt[t.kind] += 1;
         }
@@ -721,7 +721,7 @@ int tts_hip_kernel_timing(tts_hip_engine* e, int enable) {
     if (!e) return TTS_HIP_EINVAL;
     timing_collect(e);
     e->timing = enable != 0;
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 5; ++i) {
         e->time_sum_us[i] = 0;
         e->time_cnt[i] = 0;
     }
@@ -729,7 +729,7 @@ int tts_hip_kernel_timing(tts_hip_engine* e, int enable) {
 }
 
 int tts_hip_kernel_time_us(tts_hip_engine* e, int kind, double* avg_us, int64_t* launches) {
-    if (!e || kind < 0 || kind >= 4) return TTS_HIP_EINVAL;
+    if (!e || kind < 0 || kind >= 5) return TTS_HIP_EINVAL;
     timing_collect(e);
     if (avg_us) *avg_us = e->time_cnt[kind] ? e->time_sum_us[kind] / (double)e->time_cnt[kind] : 0.0;
     if (launches) *launches = e->time_cnt[kind];

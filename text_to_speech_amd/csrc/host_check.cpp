@@ -73,6 +73,13 @@
 // Fa= Fb= P= path=0|1 gross= mem= la=N,N,... lb=N,N,... null=f0_a,f0_b,stats.  First line "<status> <message>"; when the call is
 // accepted "F threads lens in out out_elems bytes" of pitch_layout, or "lens in_a in_b path stats bytes" of f0_error_layout
 // (tests/test_pitch.py compares them with a Python restatement).
+//        ttsw_check_asan --time-stretch [KEY=VALUE...] [LEN...]  -- the front end of a time-stretch call (time_stretch_check of
+// audio_call.h) for a batch of B = number of LEN rows of N samples (no LEN: lengths NULL, B from B=) run as an entry point named
+// "who", on a Tacotron-kind plan of filter_length= hop_length= win_length= pre_emph= (mel_kind=1: a Whisper plan).  Settings:
+// B= N= M= mem= what= rates=R,R,... (one value: every row's) and null=fn,audio,out,rates.  First line "<status> <message>"; when
+// the call is accepted "Fr T M", the five offsets of the vocoder's buffers and the inverse workspace's extent, then F_b, T_b,
+// S_b and the kept samples per row.  helpers=1: no check; "frames samples" of ts_row_frames / ts_row_samples per LEN
+// (tests/test_time_stretch.py compares all of it with a Python restatement).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
@@ -556,7 +563,72 @@ static int print_pitch(int argc, char** argv) {
     return 0;
 }
 
+static int print_time_stretch(int argc, char** argv) {
+    // never read: the check only tests the pointers' values
+    const float* audio = (const float*)(uintptr_t)0x100000000ull;
+    float* out = (float*)(uintptr_t)0x200000000ull;
+    std::map<std::string, double> v{{"B", -1}, {"N", 0}, {"M", 0}, {"mem", TTS_HIP_MEM_DEVICE}, {"what", -1}, {"mel_kind", 0},
+                                    {"filter_length", 1024}, {"hop_length", 256}, {"win_length", 1024}, {"pre_emph", 0},
+                                    {"helpers", 0}};
+    std::string nulls;
+    std::vector<int32_t> lengths;
+    std::vector<double> rates;
+    for (int i = 2; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) {
+            lengths.push_back((int32_t)atoi(argv[i]));
+            continue;
+        }
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        if (key == "null") nulls = eq + 1;
+        else if (key == "rates") {
+            for (const char* p = eq + 1; *p;) {
+                char* end = nullptr;
+                rates.push_back(strtod(p, &end));
+                if (end == p) return 2;
+                p = *end == ',' ? end + 1 : end;
+            }
+        } else if (v.count(key)) v[key] = atof(eq + 1);
+        else return 2;
+    }
+    const auto null = [&](const char* name) { return ("," + nulls + ",").find(std::string(",") + name + ",") != std::string::npos; };
+    const int B = lengths.empty() ? (int)v["B"] : (int)lengths.size(), N = (int)v["N"];
+    // a table shorter than B would be read past its end by the check: that is the caller's contract, not the check's
+    if (rates.size() == 1 && B > 1 && B <= (1 << 20)) rates.assign((size_t)B, rates[0]);
+    if (!null("rates") && B > 0 && (long long)rates.size() < B) return 2;
+    const tts_hip_mel_config cfg{(int)v["mel_kind"], 22050, 1, (int)v["filter_length"], (int)v["hop_length"], (int)v["win_length"], 0, 0.0,
+                                 11025.0, v["pre_emph"]};
+    char why[256] = "";
+    MelPlan p{};
+    int rc = mel_cfg_check("who", &cfg, nullptr, true, &p, why, sizeof why);
+    if (!rc && v["helpers"] != 0) {                             // the two host-only helpers, one line "frames samples" per row
+        if (rates.size() < lengths.size()) return 2;
+        printf("0 \n");
+        for (size_t b = 0; b < lengths.size(); ++b)
+            printf("%d %lld\n", ts_row_frames(p, lengths[b], rates[b]), ts_row_samples(p, lengths[b], rates[b]));
+        return 0;
+    }
+    TsGeom g;
+    if (!rc)
+        rc = time_stretch_check("who", null("fn") ? nullptr : &p, null("audio") ? nullptr : audio, B, N,
+                                lengths.empty() ? nullptr : lengths.data(), null("rates") ? nullptr : rates.data(),
+                                null("out") ? nullptr : out, (int)v["M"], (int)v["mem"], (int)v["what"], &g, why, sizeof why);
+    printf("%d %s\n", rc, why);
+    if (rc) return 0;
+    if ((int)g.fwd.lens.size() != B || (int)g.fwd.fout.size() != B || (int)g.inv.frames.size() != B || (int)g.S.size() != B ||
+        (int)g.keep.size() != B || (int)g.rates.size() != B)
+        return 2;
+    printf("%d %d %d\n", g.fwd.Fr, g.inv.F, g.M);
+    printf("%zu %zu %zu %zu %zu %zu\n", g.off_rowinfo, g.off_mag, g.off_owner, g.off_adv, g.off_rel, g.inv.total);
+    for (int b = 0; b < B; ++b) printf("%d%c", g.fwd.fout[b], b == B - 1 ? '\n' : ' ');
+    for (int b = 0; b < B; ++b) printf("%d%c", g.inv.frames[b], b == B - 1 ? '\n' : ' ');
+    for (int b = 0; b < B; ++b) printf("%d%c", g.S[b], b == B - 1 ? '\n' : ' ');
+    for (int b = 0; b < B; ++b) printf("%d%c", g.keep[b], b == B - 1 ? '\n' : ' ');
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--time-stretch")) return print_time_stretch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--pitch")) return print_pitch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--mel-dtw")) return print_mel_dtw(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--taco-loss")) return print_taco_loss(argc, argv);

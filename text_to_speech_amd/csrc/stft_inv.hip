@@ -9,7 +9,10 @@
 // depends on its neighbours and a repeat gives the same bits.  The WaveGlow denoiser (tts_hip_denoise) is one pass of the
 // same parts -- the plan's forward DFT, a gate that lowers every bin's magnitude by strength x the model's bias spectrum and
 // keeps its phase, the inverse-frames GEMM, the gather overlap-add cut to each row's length -- chained without the host.
-// include/tts_hip.h has the contract, audio_call.h the checks and the geometry (GlGeom, DnGeom), mel_stft.hip the plans and
+// Time stretching (tts_hip_time_stretch) puts a phase-locked vocoder (identity phase locking, Laroche and Dolson 1999)
+// between the same transform and inverse: a parallel pass over every output frame (magnitudes, peaks, each bin's nearest
+// peak, the phase factors) and one workgroup per row that walks the frames and carries the synthesis phase in LDS.
+// include/tts_hip.h has the contract, audio_call.h the checks and the geometry (GlGeom, DnGeom, TsGeom), mel_stft.hip the plans and
 // the forward DFT.
 //
 // The inverse basis has a closed form, so no SVD runs here: pinv(scale * [cos; -sin])^T has the rows
@@ -20,7 +23,9 @@
 #include "gemm_f32.h"
 
 #include <cfloat>
+#include <climits>
 #include <cmath>
+#include <cstring>
 
 using namespace ttsgemm;
 
@@ -160,6 +165,199 @@ __global__ void denoise_gate_kernel(const float* __restrict__ ft, const float* _
     }
     row[j] = yr;
     row[cut + j] = yi;
+}
+
+// ---- time stretch: the phase-locked vocoder between the transform and the inverse (include/tts_hip.h has the math)
+// |(re, im)| as the header states it: two products, one sum, one square root, none of them fused
+__device__ __forceinline__ float ts_abs(float re, float im) { return sqrtf(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im))); }
+
+// k is a peak of the frame's magnitudes sm[0 .. cut): positive, above both left neighbours, not below both right ones
+__device__ __forceinline__ bool ts_peak(const float* sm, int k, int cut) {
+    const float v = sm[k];
+    if (!(v > 0.f)) return false;
+    if (k >= 1 && !(v > sm[k - 1])) return false;
+    if (k >= 2 && !(v > sm[k - 2])) return false;
+    if (k + 1 < cut && !(v >= sm[k + 1])) return false;
+    if (k + 2 < cut && !(v >= sm[k + 2])) return false;
+    return true;
+}
+
+// analysis frame i = floor(t * r) and the fraction a = (float)(t * r - i) of output frame t, in double as on the host
+__device__ __forceinline__ int ts_position(int t, double r, float& a) {
+    const double pos = (double)t * r, fl = floor(pos);
+    a = (float)(pos - fl);
+    return (int)fl;
+}
+
+constexpr int TS_THREADS = 256;         // ts_analyse_kernel: one workgroup per output frame
+
+// The parallel pass, one workgroup per (row b, output frame t < T): everything of the vocoder that does not depend on the
+// synthesis phase of frame t - 1.  m[t][k] goes to mag and to LDS; every thread marks the peaks of its run of
+// ceil(cut / 256) consecutive bins; a max-scan from the left over the runs' last peaks and a min-scan from the right over
+// their first peaks give each run the peak before and behind it, and a sweep inside the run the nearest one of every bin
+// (a tie goes down).  Then per bin R[t][k] = P(c0[k] conj(c0[own])) and A[t-1][own] = P(X[i'+1][own] conj(X[i'][own])),
+// i' = floor((t - 1) r), taken straight from the spectrum (own = k in a frame without peaks).  Analysis frames at and beyond
+// fo[b] are 0 and never read; output frames at and beyond frames[b] get m = 0 and own = -1 and nothing else.
+// Dynamic LDS: cut floats (m) + cut ints (the peak before a bin, then its owner).
+__global__ __launch_bounds__(TS_THREADS) void ts_analyse_kernel(const float* __restrict__ ft, const int* __restrict__ fo,
+                                                                const int* __restrict__ frames, const double* __restrict__ rates,
+                                                                float* __restrict__ mag, int* __restrict__ owner,
+                                                                float2* __restrict__ adv, float2* __restrict__ rel, int Fr, int T,
+                                                                int cut, int NB) {
+    extern __shared__ float ts_lds[];
+    float* sm = ts_lds;
+    int* sl = (int*)(ts_lds + cut);
+    __shared__ int sh[16], edge[TS_THREADS];
+    const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
+    const long long cell0 = ((long long)b * T + t) * cut;
+    if (t >= frames[b]) {
+        for (int k = tid; k < cut; k += TS_THREADS) mag[cell0 + k] = 0.f, owner[cell0 + k] = -1;
+        return;
+    }
+    const int Fb = fo[b];
+    const double r = rates[b];
+    float a;
+    const int i = ts_position(t, r, a);                         // i <= Fb - 1: (T_b - 1) r < F_b
+    const float* x0 = ft + ((long long)b * Fr + i) * NB;
+    const float* x1 = x0 + NB;
+    const bool live1 = i + 1 < Fb;
+    const float na = __fsub_rn(1.f, a);
+    for (int k = tid; k < cut; k += TS_THREADS) {
+        const float m0 = ts_abs(x0[k], x0[cut + k]), m1 = live1 ? ts_abs(x1[k], x1[cut + k]) : 0.f;
+        const float m = __fadd_rn(__fmul_rn(na, m0), __fmul_rn(a, m1));
+        sm[k] = m;
+        mag[cell0 + k] = m;
+    }
+    __syncthreads();
+    const int C = (cut + TS_THREADS - 1) / TS_THREADS, k0 = min(cut, tid * C), k1 = min(cut, k0 + C);
+    int last = -1, first = INT_MAX;
+    for (int k = k0; k < k1; ++k)
+        if (ts_peak(sm, k, cut)) {
+            last = k;
+            if (first == INT_MAX) first = k;
+        }
+    int any, none;
+    const int upto = block_scan(last, sh, any, OpMax());        // the last peak in the runs 0 .. tid
+    edge[tid] = upto;
+    __syncthreads();
+    int before = tid ? edge[tid - 1] : -1;
+    __syncthreads();
+    edge[tid] = first;
+    __syncthreads();
+    const int mirrored = edge[TS_THREADS - 1 - tid];
+    const int from = block_scan(mirrored, sh, none, OpMin());   // the first peak in the runs 255 - tid .. 255
+    edge[TS_THREADS - 1 - tid] = from;
+    __syncthreads();
+    int behind = tid + 1 < TS_THREADS ? edge[tid + 1] : INT_MAX;
+    for (int k = k0; k < k1; ++k) {
+        if (ts_peak(sm, k, cut)) before = k;
+        sl[k] = before;
+    }
+    for (int k = k1 - 1; k >= k0; --k) {
+        if (ts_peak(sm, k, cut)) behind = k;
+        const int lo = sl[k];
+        int own = -1;
+        if (any >= 0) own = lo < 0 ? behind : behind == INT_MAX ? lo : (k - lo <= behind - k ? lo : behind);
+        sl[k] = own;
+    }
+    __syncthreads();
+    float ap = 0.f;
+    const int ip = t ? ts_position(t - 1, r, ap) : 0;
+    const float* y0 = ft + ((long long)b * Fr + ip) * NB;
+    const float* y1 = y0 + NB;
+    const bool livep = ip + 1 < Fb;
+    for (int k = tid; k < cut; k += TS_THREADS) {
+        const int own = sl[k], p = own < 0 ? k : own;
+        owner[cell0 + k] = own;
+        float2 R = make_float2(1.f, 0.f), A = make_float2(1.f, 0.f);
+        if (own >= 0) {
+            const float cr = x0[k], ci = x0[cut + k], pr = x0[p], pi = x0[cut + p];
+            phasor(cr * pr + ci * pi, ci * pr - cr * pi, R.x, R.y);
+        }
+        if (t && livep) {
+            const float cr = y1[p], ci = y1[cut + p], pr = y0[p], pi = y0[cut + p];
+            phasor(cr * pr + ci * pi, ci * pr - cr * pi, A.x, A.y);
+        }
+        rel[cell0 + k] = R;
+        adv[cell0 + k] = A;
+    }
+}
+
+constexpr int TS_CHAIN_BINS = 3;        // bins per thread of ts_chain_kernel: 3 x 1024 threads >= 2049 bins
+
+struct TsCell {
+    int own;
+    float m;
+    float2 adv, rel;
+};
+
+__device__ __forceinline__ TsCell ts_cell(const float* __restrict__ mag, const int* __restrict__ owner, const float2* __restrict__ adv,
+                                          const float2* __restrict__ rel, long long at) {
+    return TsCell{owner[at], mag[at], adv[at], rel[at]};
+}
+
+// The sequential pass, one workgroup per row walking its output frames: U[0] = P(X[0]); U[t][k] = P(U[t-1][p] A[t-1][p]
+// R[t][k]), p = own[t][k] -- U[t-1] is gathered from LDS, the other two factors come from the parallel pass -- or
+// U[t-1][k] A[t-1][k] in a frame without peaks; the operand of the inverse takes m[t][k] U[t][k].  U is double-buffered in
+// LDS (2 x cut pairs): frame t reads the buffer frame t - 1 wrote and writes the other one, so one barrier per frame
+// orders both.  Thread j owns the bins j, j + blockDim.x, ... (at most TS_CHAIN_BINS); the cells of frame t + 1 are loaded
+// before the products of frame t, so no global load waits between two barriers.  Rows of A behind frames[b] and its K
+// padding are left as the caller cleared them.
+__global__ __launch_bounds__(1024) void ts_chain_kernel(const float* __restrict__ ft, const int* __restrict__ frames,
+                                                        const float* __restrict__ mag, const int* __restrict__ owner,
+                                                        const float2* __restrict__ adv, const float2* __restrict__ rel,
+                                                        float* __restrict__ A, int Fr, int T, int cut, int NB) {
+    extern __shared__ float2 ts_u[];
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, Tb = frames[b];
+    const long long row0 = (long long)b * T;
+    const float* x0 = ft + (long long)b * Fr * NB;
+    TsCell next[TS_CHAIN_BINS];
+#pragma unroll
+    for (int j = 0; j < TS_CHAIN_BINS; ++j) {
+        const int k = tid + j * nt;
+        if (k >= cut) continue;
+        float2 u;
+        phasor(x0[k], x0[cut + k], u.x, u.y);
+        ts_u[k] = u;
+        const float m = mag[row0 * cut + k];
+        A[row0 * NB + k] = m * u.x;
+        A[row0 * NB + cut + k] = m * u.y;
+        if (Tb > 1) next[j] = ts_cell(mag, owner, adv, rel, (row0 + 1) * cut + k);
+    }
+    __syncthreads();
+    for (int t = 1; t < Tb; ++t) {
+        const float2* prev = ts_u + ((t - 1) & 1) * cut;
+        float2* cur = ts_u + (t & 1) * cut;
+        TsCell c[TS_CHAIN_BINS];
+#pragma unroll
+        for (int j = 0; j < TS_CHAIN_BINS; ++j) {
+            const int k = tid + j * nt;
+            if (k >= cut) continue;
+            c[j] = next[j];
+            if (t + 1 < Tb) next[j] = ts_cell(mag, owner, adv, rel, (row0 + t + 1) * cut + k);
+        }
+#pragma unroll
+        for (int j = 0; j < TS_CHAIN_BINS; ++j) {
+            const int k = tid + j * nt;
+            if (k >= cut) continue;
+            const float2 u = prev[c[j].own < 0 ? k : c[j].own], g = c[j].adv;
+            float2 v = make_float2(u.x * g.x - u.y * g.y, u.x * g.y + u.y * g.x);
+            if (c[j].own >= 0) {
+                const float2 q = c[j].rel;
+                phasor(v.x * q.x - v.y * q.y, v.x * q.y + v.y * q.x, v.x, v.y);
+            }
+            cur[k] = v;
+            A[(row0 + t) * NB + k] = c[j].m * v.x;
+            A[(row0 + t) * NB + cut + k] = c[j].m * v.y;
+        }
+        __syncthreads();
+    }
+}
+
+// probe only: own as floats
+__global__ void ts_owner_float_kernel(const int* __restrict__ owner, float* __restrict__ out, long long n) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n) out[idx] = (float)owner[idx];
 }
 
 // log-mel input: E [B * F][EK] = exp(spec [B * F][nmel]) on a row's own frames, 0 beyond and in the K padding
@@ -457,7 +655,122 @@ int dn_call(tts_hip_engine* e, const char* name, const float* audio, int B, int 
     return rc;
 }
 
+// device pointers only, the call already checked (g).  stop >= 0 (the probe): return right after that stage with *view
+// describing it.  With tts_hip_kernel_timing on, the five parts are timed as kinds 2 (forward DFT: pad, gather where the plan
+// has one, GEMM), 3 (parallel pass), 4 (chain), 0 (inverse-frames GEMM) and 1 (overlap-add)
+int ts_exec(tts_hip_engine* e, tts_hip_mel_fn& fn, const TsGeom& g, const float* d_audio, int B, int N, float* d_out, int stop,
+            StageView* view) {
+    const MelPlan& p = fn.p;
+    hipStream_t st = e->stream;
+    const int T = g.inv.F;
+    const long long rows = (long long)B * T, cells = rows * p.cut;
+    StageView spec{};
+    timing_begin(e, 2);
+    if (int rc = mel_fn_exec(e, fn, g.fwd, d_audio, B, N, true, nullptr, MEL_SPECTRUM, &spec)) return rc;
+    timing_end(e);
+    if (stop == TS_SPECTRUM) return *view = spec, TTS_HIP_OK;
+    const int* d_fo = (const int*)((const char*)e->stft.ws.p + g.fwd.off_info) + B;    // mel_fn_exec left [lens | fout] there
+    GlBufs w;
+    if (int rc = gl_bufs(e, g.inv, &w)) return rc;
+    char* base = (char*)e->stft.inv_ws.p;
+    const double* d_rates = (const double*)(base + g.off_rowinfo);
+    const int* d_S = (const int*)(d_rates + B);
+    float* mag = (float*)(base + g.off_mag);
+    int* owner = (int*)(base + g.off_owner);
+    float2 *adv = (float2*)(base + g.off_adv), *rel = (float2*)(base + g.off_rel);
+    e->audio_info_h.resize((size_t)3 * B);                      // [rates as doubles | S]
+    memcpy(e->audio_info_h.data(), g.rates.data(), (size_t)B * 8);
+    memcpy(e->audio_info_h.data() + 2 * B, g.S.data(), (size_t)B * 4);
+    if (int rc = stage_row_info(e, (int*)(base + g.off_rowinfo))) return rc;
+    HIPCHK(e, hipMemsetAsync(w.operand, 0, (size_t)rows * p.NB * 4, st));
+    timing_begin(e, 3);
+    hipLaunchKernelGGL(ts_analyse_kernel, dim3(T, B), dim3(TS_THREADS), (size_t)p.cut * 8, st, (const float*)spec.p, d_fo, w.info, d_rates,
+                       mag, owner, adv, rel, g.fwd.Fr, T, p.cut, p.NB);
+    HIPCHK(e, hipGetLastError());
+    timing_end(e);
+    if (stop == TS_MAGNITUDE) return *view = StageView{mag, (size_t)rows, (size_t)p.cut, (size_t)p.cut}, TTS_HIP_OK;
+    if (stop == TS_OWNER) {                                     // as floats, in the time frames' buffer (fl >= cut per row)
+        hipLaunchKernelGGL(ts_owner_float_kernel, dim3(blocks(cells, 256)), dim3(256), 0, st, owner, w.tframes, cells);
+        HIPCHK(e, hipGetLastError());
+        return *view = StageView{w.tframes, (size_t)rows, (size_t)p.cut, (size_t)p.cut}, TTS_HIP_OK;
+    }
+    timing_begin(e, 4);
+    const int nt = std::min(1024, up_to(p.cut, 64));
+    hipLaunchKernelGGL(ts_chain_kernel, dim3(B), dim3(nt), (size_t)p.cut * 16, st, (const float*)spec.p, w.info, mag, owner, adv, rel,
+                       w.operand, g.fwd.Fr, T, p.cut, p.NB);
+    HIPCHK(e, hipGetLastError());
+    timing_end(e);
+    if (stop == TS_OPERAND) return *view = StageView{w.operand, (size_t)rows, (size_t)2 * p.cut, (size_t)p.NB}, TTS_HIP_OK;
+    timing_begin(e, 0);
+    if (int rc = inverse_frames(e, fn, g.inv, w)) return rc;
+    timing_end(e);
+    if (stop == TS_FRAMES) return *view = StageView{w.tframes, (size_t)rows, (size_t)p.fl, (size_t)p.fl}, TTS_HIP_OK;
+    timing_begin(e, 1);
+    const long long n = (long long)B * g.M;
+    hipLaunchKernelGGL(ola_cut_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, w.tframes, fn.win2, d_out, n, T, g.M, w.info, d_S, p.hop,
+                       p.fl, p.half, (float)((double)p.fl / p.hop));
+    HIPCHK(e, hipGetLastError());
+    timing_end(e);
+    return TTS_HIP_OK;
+}
+
+// tts_hip_time_stretch (what = -1), its probe (what = a stage) and the _async form (stream, device pointers)
+int ts_call(tts_hip_engine* e, const char* name, const float* audio, int B, int N, const int32_t* lengths, const double* rates,
+            const tts_hip_mel_fn* fn, int what, float* out, int M, int mem, bool async, void* stream) {
+    if (int rc = mel_plan_check(e, name, fn)) return rc;
+    TsGeom g;
+    char why[256];
+    if (int rc = time_stretch_check(name, fn ? &fn->p : nullptr, audio, B, N, lengths, rates, out, M, mem, what, &g, why, sizeof why))
+        return set_err(e, rc, "%s", why);
+    tts_hip_mel_fn* plan = const_cast<tts_hip_mel_fn*>(fn);
+    HIPCHK(e, hipSetDevice(e->device));
+    if (int rc = inv_tables(e, plan)) return rc;
+    if (async) {
+        StreamScope scope(e, stream);
+        return ts_exec(e, *plan, g, audio, B, N, out, -1, nullptr);
+    }
+    const size_t n_out = (size_t)B * M * 4;
+    AudioStage io(e, mem);
+    const int in = io.in(audio, (size_t)B * N * 4);
+    const int res = what >= 0 ? io.scratch(n_out) : io.out(out, n_out);
+    if (int rc = io.begin()) return rc;
+    StageView view{};
+    if (int rc = ts_exec(e, *plan, g, io.ptr<const float>(in), B, N, io.ptr<float>(res), what, &view)) return rc;
+    if (what >= 0)
+        if (int rc = copy_stage_out(e, view, out, mem)) return rc;
+    const int rc = io.finish();
+    timing_collect(e);
+    return rc;
+}
+
 }  // namespace
+
+long long tts_hip_time_stretch_samples(const tts_hip_mel_fn* fn, int n_samples, double rate) {
+    return fn ? ts_row_samples(fn->p, n_samples, rate) : -1;
+}
+
+int tts_hip_time_stretch_frames(const tts_hip_mel_fn* fn, int n_samples, double rate) {
+    return fn ? ts_row_frames(fn->p, n_samples, rate) : -1;
+}
+
+int tts_hip_time_stretch(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const double* rates,
+                         const tts_hip_mel_fn* fn, float* out, int M, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    return ts_call(e, "time_stretch", audio, B, N, lengths, rates, fn, -1, out, M, mem, false, nullptr);
+}
+
+int tts_hip_time_stretch_async(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const double* rates,
+                               const tts_hip_mel_fn* fn, float* out, int M, void* stream) {
+    if (!e) return TTS_HIP_EINVAL;
+    return ts_call(e, "time_stretch_async", audio, B, N, lengths, rates, fn, -1, out, M, TTS_HIP_MEM_DEVICE, true, stream);
+}
+
+int tts_hip_time_stretch_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const double* rates,
+                               const tts_hip_mel_fn* fn, int what, float* out, int M, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (what < 0) return set_err(e, TTS_HIP_EINVAL, "time_stretch_probe: no stage %d (0 .. %d)", what, TS_STAGES - 1);
+    return ts_call(e, "time_stretch_probe", audio, B, N, lengths, rates, fn, what, out, M, mem, false, nullptr);
+}
 
 long long tts_hip_mel_fn_samples(const tts_hip_mel_fn* fn, int frames) { return fn ? stft_samples(fn->p, frames) : -1; }
 

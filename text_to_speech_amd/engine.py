@@ -1121,6 +1121,62 @@ class HipEngine:
                                lambda extras, outs: (lens, plan.handle, extras[0], float(strength), self._DN_STAGES[what], outs[0]),
                                extra=[bias])[0]
 
+    # ------------------------------------------------------------------ time stretch (csrc/stft_inv.hip)
+    _TS_STAGES = {'spectrum': 0, 'magnitude': 1, 'owner': 2, 'operand': 3, 'frames': 4}
+    TIME_STRETCH_RATES = (0.25, 4.0)
+
+    def _stretch_rows(self, plan, audio, rate, lengths, what):
+        """(B, N, lengths or None, float64 rates [B], int32 samples out [B], frames out [B]) of a time-stretch call; `rate` a
+        scalar or one value per row.  Raises before any GPU call."""
+        B, N, lens = self._audio_rows(audio, lengths, what)
+        rates = np.asarray(rate.detach().cpu().numpy() if hasattr(rate, 'detach') else rate, dtype=np.float64)
+        if rates.ndim == 0:
+            rates = np.full(B, float(rates))
+        if rates.shape != (B,):
+            raise ValueError(f'{what}: rate must be a scalar or hold one value per row, shape ({B},), got {rates.shape}')
+        lo, hi = self.TIME_STRETCH_RATES
+        if not (np.isfinite(rates).all() and (rates >= lo).all() and (rates <= hi).all()):
+            raise ValueError(f'{what}: rate must be finite and lie in [{lo}, {hi}], got {rates.tolist()}')
+        rates = np.ascontiguousarray(rates)
+        each = [N] * B if lens is None else lens.tolist()
+        samples = [self._lib.tts_hip_time_stretch_samples(plan.handle, int(n), float(r)) for n, r in zip(each, rates)]
+        frames = [self._lib.tts_hip_time_stretch_frames(plan.handle, int(n), float(r)) for n, r in zip(each, rates)]
+        if min(samples) < 0 or min(frames) < 0:
+            raise ValueError(f'{what}: this plan refuses a row (rows of {each} samples; a Whisper plan, pre_emph > 0 or a row '
+                             'the reflect padding cannot pad)')
+        if max(samples) < 1:
+            raise ValueError(f'{what}: rows of {each} samples at rates {rates.tolist()} stretch to 0 samples')
+        return B, N, lens, rates, np.asarray(samples, np.int32), frames
+
+    def time_stretch(self, plan, audio, rate, lengths=None, stream=None):
+        """Change the tempo of audio [N] or [B, N] without changing its pitch (tts_hip_time_stretch): a phase vocoder with
+        identity phase locking under `plan` (Tacotron kind, no pre-emphasis).  `rate` (a scalar or one value per row, in
+        [0.25, 4]): 2 plays twice as fast.  Row b holds lengths[b] samples (default N).  Returns (out, out_lengths): out
+        [B, max(out_lengths)] ([M] for a one-row [N] input), row b holding out_lengths[b] = round(lengths[b] / rate[b])
+        samples and zeros beyond; out_lengths is a host int32 array [B].  numpy in -> numpy out; a CUDA tensor in -> a CUDA
+        tensor out; `stream` (torch.cuda.Stream, device tensors only): tts_hip_time_stretch_async is enqueued there and the
+        call returns without waiting."""
+        B, N, lens, rates, samples, _ = self._stretch_rows(plan, audio, rate, lengths, 'time_stretch')
+        M = int(samples.max())
+        out, = self._audio_call('time_stretch', audio, B, N, lambda new: (new((B, M)),),
+                                lambda extras, outs: (lens, rates, plan.handle, outs[0], M), stream)
+        return (out[0] if len(_dims(audio)) == 1 else out), samples
+
+    def time_stretch_probe(self, plan, audio, rate, what, lengths=None):
+        """Test hook (tts_hip_time_stretch_probe): run `time_stretch` on the same arguments (host arrays) up to stage `what`
+        and return it, with F = mel_fn_frames(plan, N) and T the most output frames of any row: 'spectrum' [B, F, 2 bins]
+        (real parts, then imaginary parts); 'magnitude' m [B, T, bins]; 'owner' [B, T, bins] as float32, -1 where a frame has
+        no peak; 'operand' Y [B, T, 2 bins]; 'frames' [B, T, filter_length]."""
+        if what not in self._TS_STAGES:
+            raise ValueError(f'what must be one of {tuple(self._TS_STAGES)}, got {what!r}')
+        B, N, lens, rates, samples, frames = self._stretch_rows(plan, audio, rate, lengths, 'time_stretch_probe')
+        bins, T = plan.geometry['filter_length'] // 2 + 1, max(frames)
+        shape = {'spectrum': (B, self.mel_fn_frames(plan, N), 2 * bins), 'magnitude': (B, T, bins), 'owner': (B, T, bins),
+                 'operand': (B, T, 2 * bins), 'frames': (B, T, plan.geometry['filter_length'])}[what]
+        return self._audio_call('time_stretch_probe', audio, B, N, lambda new: (new(shape),),
+                                lambda extras, outs: (lens, rates, plan.handle, self._TS_STAGES[what], outs[0],
+                                                      int(samples.max())))[0]
+
     # ------------------------------------------------------------------ waveform clean-up (csrc/audio_proc.hip)
     _TRIM_MODES = {'start_end': 0, 'start': 1, 'end': 2}
 

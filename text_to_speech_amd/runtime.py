@@ -466,6 +466,12 @@ class HipRuntime(Runtime):
         `denoiser(precision)` -> [B, N]."""
         return self.denoiser(precision)(audio, strength, lengths=lengths)
 
+    def time_stretch(self, audio, rate, lengths=None, plan=None):
+        """`audio` [N] or [B, N] played `rate` times as fast at the same pitch on this runtime's engine
+        (`effects.time_stretch`, default plan 1024 / 256 / 1024) -> (out, out_lengths)."""
+        from .effects import time_stretch
+        return time_stretch(audio, rate, engine=self.engine, plan=plan, lengths=lengths)
+
     def waveglow_encode(self, audio, mel, lengths=None, stream=None):
         """The forward flow of the vocoder, audio [B, T*256] + mel [B, T, 80] -> (z [B, T*32, 8], stats [3, B]), fp32
         (HipEngine.waveglow_encode); a single utterance ([T*256] with [T, 80]) gets its batch axis."""

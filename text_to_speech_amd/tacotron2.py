@@ -72,7 +72,8 @@ class Tacotron2:
         """One text (or a dict holding it under 'text' / 'content') -> its result dict.  The keywords of the stages
         (`_stage_kwargs`): `embeddings`, `max_length=10.`, `max_text_length=-1`, `max_trial=5`, `min_fpt_ratio=2.`,
         `max_fpt_ratio=10.` (`_synthesize`), `vocoder`, `vocoder_config` (`_vocode_parts`), `silence_time=0.15`,
-        `reduce_noise`, `trim_silence` (`_finish`); every other keyword reaches the text cleaner and both models.
+        `reduce_noise`, `trim_silence`, `speed=1.0` (tempo; 1.25 speaks a quarter faster), `pitch_steps=0.0` (semitones)
+        (`_finish`; none of these is part of the `map.json` key); every other keyword reaches the text cleaner and both models.
         `utterance` (an int; `predict(sentence_streams=True)` numbers its inputs): every random draw of this text comes
         from a stream of its own -- part p at trial t decodes with the id (utterance, p, t) and is vocoded with (utterance, p),
         passed to the models as `streams=[...]` (HipRuntime) -- so with a `seed` the audio does not depend on batching."""
@@ -440,15 +441,35 @@ class Tacotron2:
             audio = audio[start:end]
         return audio
 
+    def _apply_effects(self, audio, vocoder, speed, pitch_steps):
+        """`speed` (tempo, `effects.time_stretch`) and then `pitch_steps` (`effects.pitch_shift`) on the concatenated
+        utterance, on the engine `_clean_waveform` would use.  Both must be finite; the engine refuses a speed outside
+        [0.25, 4]."""
+        from . import effects
+        eng = getattr(getattr(vocoder, 'compiled_infer', None), 'engine', None) or getattr(self.compiled_infer, 'engine', None)
+        if eng is None or not hasattr(eng, 'time_stretch'):
+            raise ValueError('speed / pitch_steps need a HIP engine behind the model')
+        audio = np.asarray(audio, np.float32)
+        if speed != 1.0:
+            audio, _ = effects.time_stretch(audio, float(speed), engine=eng)
+        if pitch_steps != 0.0:
+            audio = effects.pitch_shift(audio, float(pitch_steps), engine=eng)
+        return audio
+
     def _finish(self, part, audios, vocoder_time, *, callbacks=None, predicted=None, return_output=True, vocoder=None,
-                silence_time=0.15, reduce_noise=False, trim_silence=False):
+                silence_time=0.15, reduce_noise=False, trim_silence=False, speed=1.0, pitch_steps=0.0):
         """The last stage: `audios` (the waveforms of the text's non-empty parts, in order; None without a vocoder) ->
-        concatenation, clean-up, result dict, `predicted` entry, callbacks, return value."""
+        concatenation, `speed` / `pitch_steps` (`_apply_effects`; the defaults 1.0 and 0.0 call nothing), clean-up, result
+        dict ('time' is the duration after them), `predicted` entry, callbacks, return value.  Like the other keywords of
+        this stage, `speed` and `pitch_steps` are not part of the `map.json` key: a cached text is replayed as it was first
+        made."""
         text, synth_time = part['text'], part.get('synth_time', 0.)
         audio_infos = {}
         if vocoder is not None:
             if len(audios) > 0:
                 audios = audios[0] if len(audios) == 1 else np.concatenate(audios, axis=0)
+                if (speed != 1.0 or pitch_steps != 0.0) and len(audios) > 0:
+                    audios = self._apply_effects(audios, vocoder, speed, pitch_steps)
                 if (reduce_noise or trim_silence) and len(audios) > 0:
                     audios = self._clean_waveform(audios, vocoder, reduce_noise, trim_silence)
                 audio_infos = {'audio': audios, 'rate': self.rate, 'time': len(audios) / self.rate}
@@ -797,7 +818,7 @@ def _replay(text, predicted, callbacks):
 
 _SYNTHESIZE_KWARGS = ('embeddings', 'max_length', 'max_text_length', 'max_trial', 'min_fpt_ratio', 'max_fpt_ratio')
 _VOCODE_KWARGS = ('vocoder', 'vocoder_config')
-_FINISH_KWARGS = ('vocoder', 'silence_time', 'reduce_noise', 'trim_silence')
+_FINISH_KWARGS = ('vocoder', 'silence_time', 'reduce_noise', 'trim_silence', 'speed', 'pitch_steps')
 
 
 def _stage_kwargs(kwargs):
