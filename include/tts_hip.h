@@ -426,6 +426,23 @@ int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int 
  * B*T <= 31744.                                                                                                            */
 int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int precision,
                            int flow, int what, int layer, float* out, int mem);
+/* The same test hook for calls with row lengths (used by tests/ only; no effect on later calls); the two symbols above are
+ * calls of this one with lengths NULL and packed 0, bit for bit.  `lengths`: NULL or host int32 [B] in [0, T].
+ *   lengths, packed 0: the ONE run of tts_hip_waveglow_infer_ragged on these arguments (the same table, staged the same way),
+ *     stopped at the probe; `out` [B, T*32, W] in the batch layout, W as above.  what 1: `out` is exactly 0 behind a row's
+ *     length.  what 0 and 2: what lies behind a row's length is whatever the run computed there -- NOT SPECIFIED.
+ *   packed != 0 (needs lengths): the gather of tts_hip_waveglow_infer_packed, then its one-row run with per-frame flags,
+ *     stopped at the probe; there is no scatter.  `out` [F*32, W] in the packed row's OWN layout, F = sum(lengths) +
+ *     TTS_HIP_WG_GAP_FRAMES * (rows with frames - 1): row b's frames start at frame sum over the rows before it that hold
+ *     frames of (their length + the gap).  what 1: `out` is exactly 0 on gap frames; what 0 and 2: not specified there.  F = 0:
+ *     nothing is written.
+ * mel and z behind a row's length are never read.  Refused with TTS_HIP_EINVAL before anything is copied or launched, the
+ * message starting with the symbol's name (also for the two symbols above), first match wins (csrc/wg_call.h,
+ * wg_probe_check): whatever tts_hip_waveglow_infer_ragged / _packed refuses of the same mel / B / T / lengths / packed /
+ * precision / mem, then flow outside [0, 11], what outside [0, 2], layer outside [0, 7], what 2 with precision != 0, B * T
+ * (packed: F) above one run (31 744 frames: the probe does not slice), out NULL.                                          */
+int tts_hip_waveglow_probe_rows(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths, int packed,
+                                const float* z, float sigma, int precision, int flow, int what, int layer, float* out, int mem);
 /* Test hook of the forward direction (used by tests/ only; no state is kept on the handle, so no effect on later calls):
  * runs tts_hip_waveglow_encode on audio / mel / lengths -- same plan, form and fall-back, same tail handling -- and stops
  * after the position-wise kernel that ends flow `flow` (0 .. 11; -1: right after the init step audio @ kernel_0):

@@ -224,6 +224,8 @@ CASES = {
     'waveglow_probe': lambda e: e.waveglow_probe(MEL, flow=3, layer=2),
     'waveglow_probe_state_z': lambda e: e.waveglow_probe(MEL, z=Z, precision='f16x3', flow=4, what='state'),
     'waveglow_probe_cond': lambda e: e.waveglow_probe(MEL, z=Z, what='cond', layer=1),
+    'waveglow_probe_lengths': lambda e: e.waveglow_probe(MEL, z=Z, precision='f16', flow=8, what='state', lengths=[4, 2]),
+    'waveglow_probe_packed': lambda e: e.waveglow_probe(MEL, lengths=np.asarray([3, 2]), packed=True, layer=5),
     'waveglow_probe_acts': lambda e: e.waveglow_probe_acts(MEL),
     'waveglow_probe_acts_z': lambda e: e.waveglow_probe_acts(MEL, z=Z, sigma=0.5, flow=2, layer=3),
     # ---- Tacotron2
@@ -336,6 +338,8 @@ REFUSALS = {
     'waveglow_encode_audio': (lambda e: e.waveglow_encode(WAV[:, :-1], MEL), r'audio must be \[B, T\*256\]'),
     'waveglow_encode_probe_mel': (lambda e: e.waveglow_encode_probe(WAV, MEL[0]), r'mel must be \[B, T, 80\]'),
     'waveglow_probe_z': (lambda e: e.waveglow_probe(MEL, z=Z[:1]), r'z must be \[B, T\*32, 8\]'),
+    'waveglow_probe_packed_alone': (lambda e: e.waveglow_probe(MEL, packed=True), 'packed=True needs lengths'),
+    'waveglow_probe_lengths_range': (lambda e: e.waveglow_probe(MEL, lengths=[5, 2]), r'lengths must lie in \[0, '),
     'waveglow_probe_acts_mel': (lambda e: e.waveglow_probe_acts(MEL[0]), r'mel must be \[B, T, 80\]'),
     'tacotron2_infer_tokens': (lambda e: e.tacotron2_infer(TOKENS[0]), r'tokens must be \[B, Tin\]'),
     'tacotron2_infer_masks': (lambda e: e.tacotron2_infer(TOKENS, max_len=8, prenet_masks=masks(7, 8)),

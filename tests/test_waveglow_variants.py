@@ -1,7 +1,10 @@
 """CPU half of the WaveGlow-variant matrix (tests/waveglow_cases.py): the case table reaches every WN GEMM instantiation and
 every Winograd kernel kind that `waveglow_run` can launch, `pick_variant` restates the dispatch rules at their edges, and
 every bound of test_waveglow_variants_gpu.py could fail -- oracle-only controls showing that a tap leaking across an
-utterance end, a conditioning frame off by one, an ignored fp16 flag and a small error in the `end` conv would be caught."""
+utterance end, a conditioning frame off by one, an ignored fp16 flag and a small error in the `end` conv would be caught.
+The same for calls with row lengths (RAGGED_CASES / PACKED_CASES, tests/test_waveglow_rows_gpu.py): the tables reach every
+tile family and every MASK_LENS / MASK_FLAGS instantiation, and each mistake a mask can make -- x not zeroed somewhere, a mask
+one frame too long, a gap one frame too short, an uncleared gap mel, an unmasked z or state tail -- would be caught."""
 import os
 import re
 
@@ -237,6 +240,239 @@ def test_control_an_end_conv_error_of_1e4_moves_the_post_flow_state_beyond_its_b
         print(f'end conv x (1 + 1e-4): state after flow {k}: rel {e["rel"]:.2e} max_rel {e["max_rel"]:.2e}')
         for p in ('f32', 'f16x3'):
             assert e['rel'] > wc.STATE_REL[p] and e['max_rel'] > wc.STATE_MAX_REL[p], (k, p)
+
+
+# ---- calls with row lengths: coverage ------------------------------------------------------------------------------------
+def _rows_seen(cases):
+    return {(p, f, v.tiles, v.wino) for c in cases for p, f in wc.runs(c) for v in [wc.rows_variant(c, p, f)]}
+
+
+@pytest.mark.parametrize('table', ['ragged', 'packed'])
+def test_rows_cases_reach_every_tile_family_and_the_winograd_form_on_each(table):
+    cases = wc.RAGGED_CASES if table == 'ragged' else wc.PACKED_CASES
+    seen = _rows_seen(cases)
+    for fam in ('64-row', '128x64', '128-row', '256-row'):
+        assert any(s[0] == 'f32' and s[2] == fam and not s[3] for s in seen), fam
+        assert ('f16', 'winograd', fam, False) in seen, fam
+    assert {('f16x3', 'winograd', fam, False) for fam in ('64-row', '256-row')} <= seen
+    for fam in ('64-row', '128-row', '256-row'):
+        assert ('f32', 'winograd', fam, True) in seen, fam
+    if table == 'packed':
+        assert all(set(c.forms) == {'winograd', 'direct'} and c.packed and c.frames == sum(c.lengths) + wc.GAP * (
+            sum(n > 0 for n in c.lengths) - 1) for c in cases)
+        assert any(c.T > 10 * max(c.lengths) for c in cases)        # the gather's source index is not the packed index
+    else:
+        assert ('f32', 'winograd-3pass', '256-row', True) in seen and ('f32', 'winograd-3pass', '128-row', True) in seen
+        assert {'gemm_wn_wino/phases', 'gemm_wn_wino_128/phases'} <= {
+            k for c in cases for f in c.forms for k in wc.rows_variant(c, 'f32', f).kernels}
+    # every table: a row of length 0, 1, T and T - 1 (T > 1: not the same row as the one of length 0), an odd length
+    for want in ('zero', 'one', 'T', 'T-1', 'odd'):
+        assert any({'zero': n == 0, 'one': n == 1, 'T': n == c.T, 'T-1': n == c.T - 1 and c.T > 2, 'odd': n % 2 == 1}[want]
+                   for c in cases for n in c.lengths), (table, want)
+    pads = {(wc.rows_variant(c, p, f).PR - c.frames, wc.rows_variant(c, p, f).tiles) for c in cases for p, f in wc.runs(c)}
+    assert (127, '128-row') in pads and (63, '64-row') in pads or table == 'packed' and (1, '128-row') in pads
+
+
+def test_rows_cases_reach_every_masked_instantiation_named_in_the_source():
+    """init_audio_kernel<MASK_*>, wn_end_last_kernel<MASK_*> and end_fold<HALF, SPLIT, MASK_*> for MASK_LENS and MASK_FLAGS:
+    every one that waveglow.hip names is launched by some case of the tables (fp32 end_fold: the 256-channel cases), and the
+    tables name none that the source does not have."""
+    src = _src('waveglow.hip')
+    named = {f'{k}<{m}>' for k, m in re.findall(r'\b(init_audio_kernel|wn_end_last_kernel)<(MASK_LENS|MASK_FLAGS)>', src)}
+    named |= {f'end_fold<{h}, {s}, {m}>' for h, s, m in
+              re.findall(r'\bend_fold<(true|false), (true|false), (MASK_LENS|MASK_FLAGS)>\(', src)}
+    assert len(named) == 2 + 2 + 6, sorted(named)
+    got = set()
+    for c in wc.ROWS_CASES:
+        for p in wc.PRECISIONS:
+            got |= wc.mask_kernels(c, p)
+    for name in wc.ROWS_256_CASES:
+        got |= wc.mask_kernels(wc.ROWS_CASE_BY_NAME[name], 'f32', channels=256)
+    assert got == named, (sorted(named - got), sorted(got - named))
+    # one launch site per kind, picked by the run's mask alone: a packed run takes MASK_FLAGS, a ragged one MASK_LENS
+    assert 'const int mask = d_flags ? MASK_FLAGS : d_lens ? MASK_LENS : MASK_NONE;' in src
+    assert 'c.endp = (precision == 0 && C == 512) ? wg.endp.f() : nullptr;' in src
+    for names in (wc.ROWS_LATER_FLOW_CASES, wc.ROWS_STATE_CASES, wc.ROWS_COND_CASES, wc.ROWS_256_CASES):
+        assert set(names) <= set(wc.ROWS_CASE_BY_NAME)
+    assert all(wc.rows_variant(wc.ROWS_CASE_BY_NAME[n], 'f32').wino for n in wc.ROWS_COND_CASES)
+    from waveglow_packed_ref import header_gap_frames
+    assert wc.GAP == header_gap_frames()
+
+
+# ---- calls with row lengths: oracle-only controls --------------------------------------------------------------------------
+CTRL_ROWS = wc.RowsCase('ctrl_r3x13', 3, 13, (13, 5, 9))
+CTRL_PACKED = CTRL_ROWS._replace(name='ctrl_p35', packed=True)
+
+
+_SOLO = {}
+
+
+def _solo_acts(case, mel, z):
+    """Per row: the oracle's flow-11 activations on the row's own frames (one computation per set of rows)."""
+    key = (case.B, case.T, case.lengths, case.packed)          # (what seeds rows_inputs)
+    if key not in _SOLO:
+        _SOLO[key] = _solo_acts_of(case, mel, z)
+    return _SOLO[key]
+
+
+def _solo_acts_of(case, mel, z):
+    return [wc.flow_acts(z[b:b + 1, :n * wc.NPH, :2], wc.spect_of(mel[b:b + 1, :n], wc.weights64()), 11)
+            for b, n in enumerate(case.lengths)]
+
+
+def _run_layout(case, mel, z, gap=wc.GAP, fill=None):
+    """(mel [R, F, 80], z [R, F*32, 8], real [R, F]) of the one run: the padded batch, or the packed row with `gap` frames
+    between two rows; gap frames hold `fill`'s values (a generator: the engine gathers nothing there, the control puts numbers)."""
+    if not case.packed:
+        return mel, z, np.arange(case.T)[None, :] < np.asarray(case.lengths)[:, None]
+    from waveglow_packed_ref import packing_plan
+    plan = packing_plan(case.lengths, case.T, gap)
+    F = plan['F']
+    pm, pz = fill.uniform(-11.5, 1.2, (1, F, 80)), fill.standard_normal((1, F * wc.NPH, 8))
+    for b, n in enumerate(case.lengths):
+        at = plan['starts'][b]
+        pm[0, at:at + n], pz[0, at * wc.NPH:(at + n) * wc.NPH] = mel[b, :n], z[b, :n * wc.NPH]
+    return pm, pz, (np.asarray(plan['flags']) != 0)[None, :]
+
+
+def _masked_acts(mel, z, real, unmasked=(), clear_mel=True, mask_z=True):
+    """Flow 11's activations of the masked oracle on one run (float64)."""
+    from waveglow_packed_ref import wn_block_masked
+    keep = real.astype(np.float64)
+    mel = np.asarray(mel, np.float64) * (keep[:, :, None] if clear_mel else 1.0)
+    pos = np.repeat(keep, wc.NPH, axis=1)[:, :, None]
+    a0 = np.asarray(z, np.float64)[:, :, :2] * (pos if mask_z else 1.0)
+    acts = []
+    wn_block_masked(a0, wc.spect_of(mel, wc.weights64()), wc.weights64(), 'waveglow/block-11', pos, collect=acts,
+                    unmasked=unmasked)
+    return acts
+
+
+def _worst_per_row(case, acts, solo, starts=None):
+    """Worst of every metric over rows and layers, each row against the oracle on its own frames."""
+    worst = {'rel': 0.0, 'edge': 0.0, 'abs': 0.0}
+    case = case if starts is None else _Starts(case, starts)
+    for b, n in enumerate(case.lengths):
+        if n:
+            for layer in range(wc.N_LAYERS):
+                out = acts[layer][0] if case.packed else acts[layer]
+                e = wc.act_errors(wc.row_of(case, out, b), solo[b][layer], n, 1 << layer)
+                worst = {k: max(worst[k], e[k]) for k in worst}
+    return worst
+
+
+class _Starts:
+    """A packed case whose rows start elsewhere (the 3-gap-frame control)."""
+
+    def __init__(self, case, starts):
+        self.packed, self.lengths, self.starts = case.packed, case.lengths, starts
+
+
+def _exceeds(e, factor, precisions):
+    return all(any(e[k] >= factor * bound[p] for k, bound in (('rel', wc.ACTS_REL), ('edge', wc.ACTS_EDGE_REL),
+                                                              ('abs', wc.ACTS_ABS))) for p in precisions)
+
+
+@pytest.mark.parametrize('case', [CTRL_ROWS, CTRL_PACKED], ids=lambda c: c.name)
+def test_control_masked_oracle_on_the_run_is_the_solo_oracle_per_row(case):
+    """Lengths (13, 5, 9): x zeroed after the start conv and after every residual sum -- and nothing else, neither the mel
+    tail cleared nor the z tail masked -- gives every row what it computes alone, to float64 rounding (measured: no bit
+    differs).  So the activations cannot see those two mistakes: the state controls below do.  A packed row is different
+    in one respect: the transposed-conv upsampling looks three frames BACK, so what the mel holds on a gap frame reaches the
+    first frames of the row behind it -- there an uncleared mel is a planted mistake of the next test, not of this one."""
+    mel, z = wc.rows_inputs(case, nan=False)
+    solo = _solo_acts(case, mel, z)
+    rm, rz, real = _run_layout(case, mel, z, fill=np.random.default_rng(3))
+    for kw in ({}, dict(mask_z=False)) + (() if case.packed else (dict(clear_mel=False),)):
+        e = _worst_per_row(case, _masked_acts(rm, rz, real, **kw), solo)
+        print(f'{case.name} masked oracle {kw}: rel {e["rel"]:.1e} edge {e["edge"]:.1e} abs {e["abs"]:.1e}')
+        assert e['rel'] <= 1e-13 and e['edge'] <= 1e-13 and e['abs'] <= 1e-12
+
+
+PLANTED = [('start', dict(unmasked=('start',))), ('res0', dict(unmasked=(0,))), ('res3', dict(unmasked=(3,))),
+           ('res6', dict(unmasked=(6,))), ('long', dict(longer=1)), ('gap_mel', dict(clear_mel=False))]
+
+
+# (behind a row's length nothing looks at the mel -- the upsampling is causal -- so 'gap_mel' is a mistake of the packed row only)
+PLANTED_RUNS = [(c, n, m) for c in (CTRL_ROWS, CTRL_PACKED) for n, m in PLANTED if n != 'gap_mel' or c.packed]
+
+
+@pytest.mark.parametrize('case,name,mistake', PLANTED_RUNS, ids=[f'{c.name}-{n}' for c, n, _ in PLANTED_RUNS])
+def test_control_a_planted_mask_mistake_breaks_the_per_row_bounds(case, name, mistake):
+    """One mistake at a time in the masked oracle -- x not zeroed after the start conv, or after residual sum 0 / 3 / 6, or a
+    mask one frame too long -- moves some row beyond the bounds of waveglow_cases in at least one metric, by a factor 100 for
+    f32 and f16x3 and by 3 for f16.  Measured worst over rows and layers, lengths (13, 5, 9) in a [3, 13] batch with this
+    module's inputs (rel / edge / abs): start 1.8e-3 / 1.7e-2 / 1.1e-1; res0 1.6e-2 / 1.0e-1 / 0.83; res3 4.1e-2 / 9.3e-2 /
+    1.1; res6 1.0e-1 / 1.0e-1 / 1.1; one frame too long 2.0e-1 / 3.2e-1 / 1.9.  The same rows packed with 4 gap frames (gap
+    frames holding numbers): start 2.9e-3 / 2.6e-2 / 1.4e-1; res0 2.0e-2 / 1.3e-1 / 0.95; res3 4.3e-2 / 9.7e-2 / 0.91; res6
+    1.6e-1 / 1.6e-1 / 1.3; too long 2.9e-1 / 3.0e-1 / 1.9; and, packed only, the mel not cleared on the gap frames 8.0e-1 /
+    9.1e-1 / 2.0.  The smallest ratio to a bound is the start conv's: edge 1.7e-2 = 680 x the fp32 bound, 1100 x f16x3's,
+    8.5 x fp16's (abs 1.1e-1 = 3.7 x fp16's)."""
+    mel, z = wc.rows_inputs(case, nan=False)
+    solo = _solo_acts(case, mel, z)
+    rm, rz, real = _run_layout(case, mel, z, fill=np.random.default_rng(3))
+    kw = dict(mistake)
+    if kw.pop('longer', 0):
+        grown = real.copy()
+        grown[:, 1:] |= real[:, :-1]                                # every row one frame longer (into its tail or its gap)
+        real = grown
+    e = _worst_per_row(case, _masked_acts(rm, rz, real, **kw), solo)
+    print(f'{case.name} {name}: rel {e["rel"]:.1e} edge {e["edge"]:.1e} abs {e["abs"]:.1e}')
+    assert _exceeds(e, 100, ('f32', 'f16x3')) and _exceeds(e, 3, ('f16',)), e
+
+
+def test_control_three_gap_frames_break_the_per_row_bounds():
+    """The packed row built with 3 gap frames instead of 4 and otherwise correct: the d = 128 taps of layer 7 reach 4 frames,
+    across the gap into the neighbouring row.  Measured (lengths (13, 5, 9)): rel 2.6e-1 / edge 2.6e-1 / abs 1.9 (130 x fp16's
+    edge bound); with 4 frames the control above holds bit for bit."""
+    from waveglow_packed_ref import packing_plan
+    case = CTRL_PACKED
+    mel, z = wc.rows_inputs(case, nan=False)
+    solo = _solo_acts(case, mel, z)
+    rm, rz, real = _run_layout(case, mel, z, gap=3, fill=np.random.default_rng(3))
+    e = _worst_per_row(case, _masked_acts(rm, rz, real), solo, starts=packing_plan(case.lengths, case.T, 3)['starts'])
+    print(f'3 gap frames: rel {e["rel"]:.1e} edge {e["edge"]:.1e} abs {e["abs"]:.1e}')
+    assert _exceeds(e, 100, ('f32', 'f16x3')) and _exceeds(e, 3, ('f16',)), e
+
+
+# (twelve flows in float64, three times over: the smallest rows that have a tail, a gap and a row that fills its T)
+CTRL_STATE = wc.RowsCase('ctrl_r3x3', 3, 3, (3, 1, 2))
+
+
+@pytest.mark.parametrize('case', [CTRL_STATE, CTRL_STATE._replace(name='ctrl_p14', packed=True)], ids=lambda c: c.name)
+def test_control_an_unmasked_tail_leaves_state_behind_a_length(case):
+    """The state checks: with z masked in the init step and the state cleared by every flow's end kernel, the state after
+    flows 11, 8, 4 and 0 is exactly 0 on every frame that is not real and the row's own state on the others; z not masked,
+    or the end kernel not clearing, leaves non-zero state there -- which the activations above cannot show."""
+    from oracle import waveglow_ref
+    from waveglow_packed_ref import infer_packed
+    mel, z = wc.rows_inputs(case, nan=False)
+    rm, rz, real = _run_layout(case, mel, z, fill=np.random.default_rng(3))
+    w = wc.weights64(wc.STATE_END_SCALE)
+    good, no_z, no_end = {}, {}, {}
+    infer_packed(rm, rz, real, w, wc.config(), dtype=np.float64, states=good)
+    infer_packed(rm, rz, real, w, wc.config(), dtype=np.float64, states=no_z, mask_z=False)
+    infer_packed(rm, rz, real, w, wc.config(), dtype=np.float64, states=no_end, mask_state=False)
+    for k in (11, 8, 4, 0):
+        layout = lambda s: s[k][0] if case.packed else s[k]
+        assert not wc.not_real(case, layout(good)).any(), k
+        assert wc.not_real(case, layout(no_end)).any(), k
+        # the early outputs that flows 8 and 4 prepend are z's: they show an unmasked z even where the state was cleared
+        assert wc.not_real(case, layout(no_z)).any() == (k in (8, 4)), k
+    # the real positions: every row against the same arithmetic on its own frames (no frame masked), and the last row --
+    # behind a tail, or behind a gap -- against the oracle's own intermediates as well
+    for b, n in enumerate(case.lengths):
+        own_mel, own_z = mel[b:b + 1, :n].astype(np.float64), z[b:b + 1, :n * wc.NPH].astype(np.float64)
+        alone = {}
+        infer_packed(own_mel, own_z, np.ones((1, n)), w, wc.config(), dtype=np.float64, states=alone)
+        if b == case.B - 1:
+            _, inter = waveglow_ref.infer(own_mel, wc.weights(wc.STATE_END_SCALE), wc.config(), z=own_z, sigma=1.0,
+                                          dtype=np.float64, return_intermediates=True)
+        for k in (11, 8, 4, 0):
+            got = wc.row_of(case, good[k][0] if case.packed else good[k], b)
+            for ref in (alone[k],) + ((inter[f'audio_after_flow_{k}'],) if b == case.B - 1 else ()):
+                e = wc.state_errors(got, ref)                       # (float64 rounding: the matrix products block by shape)
+                assert e['rel'] <= 1e-12 and e['max_rel'] <= 1e-12, (b, k, e)
 
 
 def test_edge_windows_and_state_widths():

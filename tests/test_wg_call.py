@@ -190,3 +190,112 @@ def test_refusal_precedence(checker):
     assert 'B*T too large' in _call(checker, MAX_FRAMES + 1, True, 0, B=1 << 20)[1]
     assert 'packed needs lengths' in _call(checker, MAX_FRAMES + 1, True, 0, B=2)[1]
     assert 'lengths[0] = -3' in _call(checker, MAX_FRAMES + 1, False, 0, (-3, 1))[1]
+
+
+# ---- the inverse direction's test hook (tts_hip_waveglow_probe_rows): wg_probe_check ---------------------------------------
+def probe_refusal(T, packed, lengths, B, precision=0, mem=0, flow=0, what=0, layer=0, null=''):
+    """The first reason wg_probe_check gives, as a substring of its message (None: accepted), restated from
+    include/tts_hip.h: the reasons of the ragged / packed call for the same mel / B / T / lengths / packed / precision / mem
+    (its audio pointer is not looked at), then flow, what, layer, what 2 outside fp32, B * T above one run, out NULL."""
+    B = len(lengths) if lengths else B
+    if not 0 <= precision <= 2:
+        return 'precision must be'
+    if mem not in (0, 1):
+        return f'bad mem kind {mem}'
+    if B <= 0:
+        return f'B = {B} must be positive'
+    if 'mel' in null or T <= 0:
+        return 'mel or audio is NULL, or T'
+    if B * T * 32 > 1 << 30:
+        return 'B*T too large'
+    if packed and not lengths:
+        return 'packed needs lengths'
+    for b, n in enumerate(lengths):
+        if not 0 <= n <= T:
+            return f'lengths[{b}] = {n} is outside'
+    if packed:
+        rows = sum(n > 0 for n in lengths)
+        if sum(lengths) + header_gap_frames() * max(rows - 1, 0) > MAX_FRAMES:
+            return 'the packed row holds F = '
+    elif T > MAX_FRAMES:
+        return 'windowed inference'
+    if not 0 <= flow <= 11:
+        return f'flow = {flow} is outside [0, 11]'
+    if not 0 <= what <= 2:
+        return f'what = {what} must be'
+    if not 0 <= layer <= 7:
+        return f'layer = {layer} is outside [0, 7]'
+    if what == 2 and precision != 0:
+        return f'what = 2 (cond) needs precision 0 (f32), got {precision}'
+    if not packed and B * T > MAX_FRAMES:
+        return f'B * T = {B * T} frames exceeds one run'
+    if 'out' in null:
+        return 'out is NULL'
+    return None
+
+
+def _probe(exe, T, packed, lengths=(), B=-1, **kw):
+    """(status, message) of the C++ check and the restatement's needle for the same request."""
+    settings = dict(kw)
+    if not lengths:
+        settings['B'] = B
+    settings.setdefault('flow', 0)                    # (any of flow= / what= / layer= selects the probe's check)
+    rc, msg, _ = _call(exe, T, packed, 0, lengths, **settings)
+    return rc, msg, probe_refusal(T, packed, lengths, B, **kw)
+
+
+PROBE_REQUESTS = [
+    # accepted: a plain call, a ragged one, a packed one, the limits themselves
+    (6, 0, (), dict(B=3)), (6, 0, (6, 0, 3), dict(flow=11, what=1, layer=7)), (6, 1, (6, 0, 3), dict(precision=2, what=0)),
+    (6, 0, (), dict(B=2, what=2, layer=7)), (MAX_FRAMES // 4, 0, (), dict(B=4)), (FULL, 1, (FULL, FULL), {}),
+    (40000, 1, (3, 2), {}),                           # T alone does not limit a packed probe either
+    (6, 0, (), dict(B=3, null='audio')),              # the probe has no audio argument: that pointer is not looked at
+    # the call's own reasons, in the call's order
+    (6, 0, (), dict(B=3, precision=3)), (6, 0, (), dict(B=3, mem=7)), (6, 0, (), dict(B=0)), (6, 0, (), dict(B=3, null='mel')),
+    (0, 0, (), dict(B=3)), (16384, 0, (), dict(B=MAX_BT // 16384 + 1)), (6, 1, (), dict(B=3)), (6, 0, (6, 7, 3), {}),
+    (6, 1, (6, 2, -1), {}), (MAX_FRAMES + 1, 0, (), dict(B=1)), (FULL + 1, 1, (FULL, FULL + 1), {}),
+    # the probe's own
+    (6, 0, (), dict(B=3, flow=-1)), (6, 0, (), dict(B=3, flow=12)), (6, 0, (), dict(B=3, what=-1)), (6, 0, (), dict(B=3, what=3)),
+    (6, 0, (), dict(B=3, layer=-1)), (6, 0, (), dict(B=3, layer=8)), (6, 0, (), dict(B=3, what=2, precision=1)),
+    (6, 0, (6, 1, 2), dict(what=2, precision=2)), (MAX_FRAMES // 4 + 1, 0, (), dict(B=4)),
+    (MAX_FRAMES // 2 + 1, 0, (5, 7), {}),              # a ragged probe is one run of B * T frames whatever the lengths
+    (6, 0, (), dict(B=3, null='out')), (6, 1, (6, 0, 3), dict(null='out')),
+]
+
+
+@pytest.mark.parametrize('T,packed,lengths,kw', PROBE_REQUESTS)
+def test_probe_check_equals_the_restatement(checker, T, packed, lengths, kw):
+    rc, msg, want = _probe(checker, T, packed, lengths, **kw)
+    if want is None:
+        assert rc == 0, msg
+    else:
+        assert rc == -1 and msg.startswith('who: ') and want in msg, (msg, want)
+
+
+def test_probe_check_every_kind_of_refusal_is_in_the_table(checker):
+    wants = {probe_refusal(T, packed, lengths, kw.get('B', -1), **{k: v for k, v in kw.items() if k != 'B'})
+             for T, packed, lengths, kw in PROBE_REQUESTS}
+    reasons = ['precision must be', 'bad mem kind', 'must be positive', 'mel or audio is NULL', 'B*T too large', 'packed needs lengths',
+               'lengths[', 'the packed row holds', 'windowed inference', 'flow = ', 'what = 3', 'layer = ', 'what = 2 (cond)',
+               'exceeds one run', 'out is NULL']
+    assert None in wants and all(any(w and r in w for w in wants) for r in reasons)
+
+
+def test_probe_check_precedence_on_random_requests(checker):
+    """Several things wrong at once: the first match in the documented order is the one reported."""
+    rng = np.random.default_rng(13)
+    pick = lambda values, p_first: values[0] if rng.random() < p_first else values[int(rng.integers(1, len(values)))]
+    seen = set()
+    for _ in range(250):
+        T = pick([6, 0, MAX_FRAMES + 1], 0.8)
+        packed = int(rng.random() < 0.3)
+        lengths = pick([(), (6, 0, 3), (6, 7, 3), (-1, 2)], 0.4)
+        kw = dict(B=pick([3, 0, MAX_FRAMES], 0.7), precision=pick([0, 1, 2, 3, -1], 0.5), mem=pick([0, 1, 5], 0.5),
+                  flow=pick([11, 0, -1, 12], 0.6), what=pick([0, 1, 2, 3], 0.4), layer=pick([0, 7, 8, -2], 0.6),
+                  null=pick(['', 'out', 'mel', 'mel,out'], 0.6))
+        if not kw['null']:
+            del kw['null']
+        rc, msg, want = _probe(checker, T, packed, lengths, **kw)
+        seen.add(want)
+        assert (rc == 0 and want is None) or (rc == -1 and want is not None and want in msg), (T, packed, lengths, kw, msg, want)
+    assert None in seen and len(seen) >= 12

@@ -3,8 +3,9 @@ four frames, F(4,4) along frames) against a float64 evaluation of the reference'
 cond_layer(regroup(upsample(mel))) + in-layer bias, reached through the probe hook (`waveglow_probe(what='cond')`).
 
 Shapes: partial last groups (3 x 131 frames), utterances shorter than one group of four frames in a call that takes the
-Winograd form (48 x 3), and the three group kinds' tile families (256 frames).  The probe hook takes no row lengths, so the
-ragged property is checked at the call's output: frames past a row's length share a group with its last real frames, and
+Winograd form (48 x 3), and the three group kinds' tile families (256 frames).  The plane of a run with row lengths (ragged
+or packed, through `waveglow_probe(.., lengths=)`) is compared row by row in tests/test_waveglow_rows_gpu.py; here the ragged
+property is checked once more at the call's output: frames past a row's length share a group with its last real frames, and
 NaN there changes no bit of the audio.
 """
 import numpy as np

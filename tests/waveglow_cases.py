@@ -24,6 +24,16 @@ import numpy as np
 #   f32    rel 1.93e-6 (b1_t193, Winograd)  edge 2.34e-6 (b1_t193, Winograd)  abs 6.41e-5 (b5_t77, Winograd)
 #   f16x3  rel 1.55e-6 (b1_t257)            edge 1.43e-6                      abs 2.66e-5 (b3_t64)
 #   f16    rel 8.03e-4 (b1_t193)            edge 7.57e-4 (b2_t128)            abs 1.18e-2 (b1_t383)
+# The same metrics for runs with row lengths (test_waveglow_rows_gpu.py: MASK_LENS / MASK_FLAGS kernels, zeroed tails, the
+# packed row's gather), PER ROW against the oracle on the row's own frames, worst over rows, layers and cases:
+#   ragged f32    rel 2.43e-6 (r16x9, Winograd)  edge 2.46e-6 (r16x9, Winograd)  abs 4.04e-5 (r3x171, Winograd)
+#          f16x3  rel 1.54e-6 (r1x193)           edge 1.44e-6 (r5x13)            abs 2.11e-5 (r2x128)
+#          f16    rel 8.01e-4 (r1x193)           edge 7.60e-4 (r5x77)            abs 1.08e-2 (r2x128)
+#   packed f32    rel 2.04e-6 (p193, Winograd)   edge 2.35e-6 (p175, Winograd)   abs 3.91e-5 (p383, Winograd)
+#          f16x3  rel 1.55e-6 (p383)             edge 1.44e-6 (p108)             abs 2.27e-5 (p193)
+#          f16    rel 8.04e-4 (p175)             edge 7.67e-4 (p108)             abs 1.08e-2 (p383)
+# (flows 7 and 3 from the GPU's own state: f32 2.23e-6 / 2.27e-6 / 3.31e-5, f16x3 1.54e-6 / 1.44e-6 / 2.03e-5, f16 8.05e-4 /
+# 7.60e-4 / 1.07e-2.)  No bound is new: a masked row is held to what the unmasked matrix is held to.
 # fp32 and f16x3 bounds: about 10x those (the fp32 'rel' bound is tests/test_waveglow_gpu.py's ACTS_REL_TOL).  The fp16
 # error is the rounding of the operands themselves, the same in every run (rel 5.8e-4 - 8.0e-4 over every fp16 probe): its
 # bounds are 2.5x the worst, 10x would pass errors that are large for an fp16 product.
@@ -38,6 +48,8 @@ F16_FLOOR = 2e-4
 # Measured worst over flows 11, 8, 4, 0 (after flow 0 in every precision): f32 1.48e-6 / 1.78e-6, f16x3 1.77e-6 / 2.18e-6,
 # f16 8.41e-4 / 1.19e-3.  Bounds 10x (fp16: 2.5x); a 1e-4 relative error of the `end` conv output moves the state after
 # flow 11 by 4.0e-5 / 6.3e-5 already (oracle-only control).
+# With row lengths, per row: f32 2.13e-6 / 2.87e-6 (p14, r5x13), f16x3 1.78e-6 / 3.29e-6 (p108), f16 9.58e-4 / 2.13e-3 (r5x13;
+# a one-frame row's maximum over 32 positions); and exactly 0 on every frame that is not real.
 STATE_REL = {'f32': 1.5e-5, 'f16x3': 1.8e-5, 'f16': 2.5e-3}
 STATE_MAX_REL = {'f32': 1.8e-5, 'f16x3': 2.2e-5, 'f16': 3e-3}
 STATE_END_SCALE = 0.2
@@ -178,6 +190,148 @@ def runs(case):
     return [('f32', f) for f in case.forms] + [('f16', 'winograd'), ('f16x3', 'winograd')]
 
 
+# ---- cases with row lengths --------------------------------------------------------------------------------------------
+# Ragged (`lengths=`) and packed (`packed=True`) calls take the MASK_LENS / MASK_FLAGS instantiation of every position-wise
+# kernel, wn_zero_tail_kernel behind the start conv and every residual GEMM, the cleared mel copy and (packed) the gather.
+# A ragged call is one run of B x T frames; a packed call one row of F frames (packing_plan): `pick_variant(B, T, ..)` and
+# `pick_variant(1, F, ..)` say what they take.  Every row goes against the oracle on ITS OWN frames (mel[b:b+1, :n],
+# z[b:b+1, :n*32]: the contract of tts_hip_waveglow_infer_ragged), with the row's own ends as edge windows.
+GAP = 4                      # include/tts_hip.h TTS_HIP_WG_GAP_FRAMES (tests/test_waveglow_packed.py compares)
+
+
+class RowsCase(NamedTuple):
+    name: str
+    B: int
+    T: int
+    lengths: tuple
+    forms: tuple = ('winograd',)
+    packed: bool = False
+
+    @property
+    def starts(self):
+        """First frame of every row in the probe's output: b * T in the batch layout, the packing plan's in the packed row."""
+        if not self.packed:
+            return tuple(b * self.T for b in range(self.B))
+        from waveglow_packed_ref import packing_plan
+        return tuple(packing_plan(self.lengths, self.T, GAP)['starts'])
+
+    @property
+    def frames(self):
+        """Frames of the one run: B * T, or F of the packed row."""
+        if not self.packed:
+            return self.B * self.T
+        rows = sum(n > 0 for n in self.lengths)
+        return sum(self.lengths) + GAP * max(rows - 1, 0)
+
+    @property
+    def run_shape(self):
+        return (1, self.frames) if self.packed else (self.B, self.T)
+
+
+def _ragged(B, T, lengths, forms=('winograd',)):
+    assert len(lengths) == B and max(lengths) <= T
+    return RowsCase(f'r{B}x{T}', B, T, tuple(lengths), forms, False)
+
+
+def _packed(lengths, forms=('winograd', 'direct'), T=None):
+    c = RowsCase('', len(lengths), max(lengths) if T is None else T, tuple(lengths), forms, True)
+    return c._replace(name=f'p{c.frames}')
+
+
+RAGGED_CASES = (
+    # 64-row in every precision; rows shorter than the d = 64 / 128 reach, and an empty row
+    _ragged(4, 3, (3, 1, 0, 2)),
+    # 65 frames: 128 x 64 tiles for fp32 and fp16; split fp16 64-row, padded by 63
+    _ragged(5, 13, (13, 5, 9, 1, 12)),
+    # 144 frames, the Winograd start on 64-row tiles (PR 192); lengths that split frame groups of 16 and mixed groups of 2
+    _ragged(16, 9, (9, 0, 1, 8, 3, 9, 2, 7, 4, 9, 5, 6, 9, 1, 0, 9), _ALL),
+    # 256-row, fp16 and split fp16 256 x 256; a tail inside the one row
+    _ragged(1, 193, (150,), ('winograd', 'direct')),
+    # 256 frames, no padding rows; form 2 takes gemm_wn_wino
+    _ragged(2, 128, (128, 50), _ALL),
+    # 300 frames: fp32 64-row PR 320; form 2 and fp16 128-row PR 384
+    _ragged(4, 75, (75, 0, 31, 74), _ALL),
+    # 385 frames: fp32 64-row PR 448; fp16 and split fp16 256-row PR 512
+    _ragged(5, 77, (77, 40, 1, 76, 33)),
+    # 513 frames: fp32 and fp16 128-row PR 640, padded by 127; split fp16 64-row PR 576
+    _ragged(3, 171, (171, 100, 37), _ALL),
+)
+PACKED_CASES = (
+    # F = 14, 64-row; T = 300, well above every length: the gather's source index b * T + t is not the packed index
+    _packed((3, 0, 1, 2), T=300),
+    _packed((30, 1, 45, 20)),                 # F = 108, 128 x 64
+    _packed((100, 37, 30)),                   # F = 175, Winograd on 64-row; the oracle rows of tests/test_waveglow_packed_gpu.py
+    _packed((120, 1, 64)),                    # F = 193, 256-row; a one-frame row between two gaps
+    _packed((200, 77, 98)),                   # F = 383, 128-row padded by one
+    _packed((171, 100, 37, 193)),             # F = 513, 128-row PR 640
+    # added for the coverage test's rule "a row of length T and one of T - 1 in every table" (above, T is max(lengths) and no
+    # row has T - 1 frames, or T = 300): F = 9, 64-row
+    _packed((2, 3)),
+)
+ROWS_CASES = RAGGED_CASES + PACKED_CASES
+ROWS_CASE_BY_NAME = {c.name: c for c in ROWS_CASES}
+assert len(ROWS_CASE_BY_NAME) == len(ROWS_CASES)
+# flows 7 and 3 (the a0p rows of 3 and 4 coupling channels and their constant-1 column, which zero_tail(.., with_a0p) clears)
+ROWS_LATER_FLOW_CASES = ('r4x3', 'r5x13', 'r16x9', 'p14', 'p175')
+ROWS_STATE_CASES = ('r4x3', 'r5x13', 'p14', 'p108')
+ROWS_COND_CASES = ('r16x9', 'r3x171', 'p175', 'p513')
+ROWS_256_CASES = ('r4x3', 'p14')             # on a 256-channel handle, fp32: end_fold<false, false, MASK_*>
+
+
+def rows_variant(case, precision, form='winograd'):
+    return pick_variant(*case.run_shape, precision, form)
+
+
+def mask_kernels(case, precision, channels=512):
+    """The MASK_LENS / MASK_FLAGS instantiations of the position-wise kernels a call with lengths launches (waveglow_run):
+    init_audio_kernel, and at every flow's end wn_end_last_kernel (fp32 at 512 channels, on the residual GEMMs' partial sums)
+    or end_fold<HALF, SPLIT, ..>."""
+    m = 'MASK_FLAGS' if case.packed else 'MASK_LENS'
+    if precision == 'f32' and channels == 512:
+        end = f'wn_end_last_kernel<{m}>'
+    else:
+        end = 'end_fold<%s, %s>' % ('true, true' if precision == 'f16x3' else 'true, false' if precision == 'f16' else
+                                    'false, false', m)
+    return {f'init_audio_kernel<{m}>', end}
+
+
+def rows_inputs(case, nan=True):
+    """(mel [B, T, 80], z [B, T*32, 8]) by the recipe of `inputs`, seeded by the case; behind every length NaN (no reference
+    may depend on it), or with nan=False the recipe's own values (the oracle-only controls, where a leak must show as a number)."""
+    rng = np.random.default_rng(900 + 7 * case.B + case.T + 1000 * sum(case.lengths) + case.packed)
+    mel = rng.uniform(-11.5, 1.2, (case.B, case.T, 80)).astype(np.float32)
+    z = rng.standard_normal((case.B, case.T * NPH, 8)).astype(np.float32)
+    if nan:
+        for b, n in enumerate(case.lengths):
+            mel[b, n:] = np.nan
+            z[b, n * NPH:] = np.nan
+    return mel, z
+
+
+def row_inputs(case, b):
+    """Row b's own frames: (mel [1, n, 80], z [1, n*32, 8])."""
+    mel, z = rows_inputs(case)
+    n = case.lengths[b]
+    return np.ascontiguousarray(mel[b:b + 1, :n]), np.ascontiguousarray(z[b:b + 1, :n * NPH])
+
+
+def row_of(case, out, b):
+    """Row b's real positions [1, n*32, W] of a probe's output: [B, T*32, W] (ragged) or [F*32, W] (packed)."""
+    n = case.lengths[b]
+    if case.packed:
+        at = case.starts[b] * NPH
+        return out[None, at:at + n * NPH]
+    return out[b:b + 1, :n * NPH]
+
+
+def not_real(case, out):
+    """Every position of a probe's output that belongs to no real frame: behind the lengths, or on the gap frames."""
+    real = np.zeros(case.frames * NPH, bool)
+    for b, n in enumerate(case.lengths):
+        real[case.starts[b] * NPH:(case.starts[b] + n) * NPH] = True
+    return out.reshape(case.frames * NPH, -1)[~real]
+
+
 def inputs(case):
     """(mel [B, T, 80], z [B, T*32, 8]) float32, the value ranges of tests/test_waveglow_gpu.py."""
     rng = np.random.default_rng(500 + 7 * case.B + case.T + case.seed)
@@ -250,6 +404,31 @@ def _states(name, end_scale):
 def states(case, end_scale=STATE_END_SCALE):
     """Oracle flow state after flows 11, 8, 4 and 0 (float64), cached per process."""
     return _states(case.name, end_scale)
+
+
+@functools.lru_cache(maxsize=None)
+def _row_flow11_acts(name, b):
+    mel, z = row_inputs(ROWS_CASE_BY_NAME[name], b)
+    return tuple(flow_acts(z[:, :, :n_half_of(11)], spect_of(mel, weights64()), 11))
+
+
+def row_flow11_acts(case, b):
+    """Oracle activations of the 8 layers of flow 11 of row b ALONE (its own frames), cached per (case, row)."""
+    return _row_flow11_acts(case.name, b)
+
+
+@functools.lru_cache(maxsize=None)
+def _row_states(name, b, end_scale):
+    from oracle import waveglow_ref
+    mel, z = row_inputs(ROWS_CASE_BY_NAME[name], b)
+    _, inter = waveglow_ref.infer(mel.astype(np.float64), weights(end_scale), config(), z=z.astype(np.float64), sigma=1.0,
+                                  dtype=np.float64, return_intermediates=True)
+    return {k: inter[f'audio_after_flow_{k}'] for k in (11, 8, 4, 0)}
+
+
+def row_states(case, b, end_scale=STATE_END_SCALE):
+    """Oracle flow state of row b ALONE after flows 11, 8, 4 and 0 (float64), cached per (case, row)."""
+    return _row_states(case.name, b, end_scale)
 
 
 # ---- metrics -----------------------------------------------------------------------------------------------------------

@@ -45,18 +45,26 @@ def packing_plan(lengths, T, gap):
     return {'starts': starts, 'F': len(flags), 'flags': flags, 'gaps': gaps}
 
 
-def wn_block_masked(a0, spect, w, prefix, real, n_layers=8, n_channels=512):
-    """oracle.waveglow_ref.wn_block with the residual stream x times `real` after the start conv and each residual sum."""
-    x = (a0 @ w[f'{prefix}/start_conv/kernel'][0] + w[f'{prefix}/start_conv/bias']) * real
+def wn_block_masked(a0, spect, w, prefix, real, n_layers=8, n_channels=512, collect=None, unmasked=()):
+    """oracle.waveglow_ref.wn_block with the residual stream x times `real` after the start conv and each residual sum.
+    `collect` (a list): gets the gated activations of every layer.  `unmasked`: the places where x is NOT multiplied -- 'start',
+    or the index of a residual sum -- for the controls of tests/test_waveglow_variants.py that plant exactly that mistake."""
+    x = a0 @ w[f'{prefix}/start_conv/kernel'][0] + w[f'{prefix}/start_conv/bias']
+    if 'start' not in unmasked:
+        x = x * real
     output = None
     for i in range(n_layers):
         in_act = R.conv1d_dilated_same(x, w[f'{prefix}/in_conv-{i}/kernel'], w[f'{prefix}/in_conv-{i}/bias'], 2 ** i)
         cond = spect @ w[f'{prefix}/cond_layer-{i}/kernel'][0] + w[f'{prefix}/cond_layer-{i}/bias']
         s = in_act + cond
         acts = np.tanh(s[..., :n_channels]) * R._sigmoid(s[..., n_channels:])
+        if collect is not None:
+            collect.append(acts)
         rs = acts @ w[f'{prefix}/res_skip_conv-{i}/kernel'][0] + w[f'{prefix}/res_skip_conv-{i}/bias']
         if i < n_layers - 1:
-            x = (rs[..., :n_channels] + x) * real
+            x = rs[..., :n_channels] + x
+            if i not in unmasked:
+                x = x * real
             skip = rs[..., n_channels:]
         else:
             skip = rs
@@ -64,16 +72,20 @@ def wn_block_masked(a0, spect, w, prefix, real, n_layers=8, n_channels=512):
     return output @ w[f'{prefix}/end_conv/kernel'][0] + w[f'{prefix}/end_conv/bias']
 
 
-def infer_packed(mel, z, flags, w, cfg, dtype=np.float32):
+def infer_packed(mel, z, flags, w, cfg, dtype=np.float32, states=None, mask_z=True, mask_state=True):
     """mel [1, F, 80], z [1, F * 32, 8], flags [F] (non-zero = real) -> audio [F * 256]; what mel / z hold on a frame that is
-    not real does not enter."""
-    w = {k: v.astype(dtype) for k, v in w.items() if k.startswith('waveglow/')}
+    not real does not enter.  Works on any [B, F] batch with flags [B, F] as well (a ragged call: flags = t < lengths[b]).
+    `states` (a dict): gets the flow state after flows 11, 8, 4 and 0, early outputs included.  mask_z / mask_state = False:
+    z, or the state after every flow, is NOT cleared on the frames that are not real -- planted mistakes for the controls of
+    tests/test_waveglow_variants.py."""
+    w = {k: np.asarray(v, dtype) for k, v in w.items() if k.startswith('waveglow/')}
     keep = (np.asarray(flags) != 0).astype(dtype)
-    mel = np.where(keep[None, :, None] != 0, np.asarray(mel, dtype), dtype(0))
+    keep = keep[None] if keep.ndim == 1 else keep
+    mel = np.where(keep[:, :, None] != 0, np.asarray(mel, dtype), dtype(0))
     spect = R.regroup(R.upsample(mel, w['waveglow/upsample/kernel'], w['waveglow/upsample/bias'], cfg.upsample_stride),
                       cfg.n_group)
-    real = np.repeat(keep, spect.shape[1] // len(keep))[None, :, None]
-    z = np.where(real != 0, np.asarray(z, dtype), dtype(0))
+    real = np.repeat(keep, spect.shape[1] // keep.shape[1], axis=1)[:, :, None]
+    z = np.where(real != 0, np.asarray(z, dtype), dtype(0)) if mask_z else np.asarray(z, dtype)
     n_rem = cfg.n_remaining_channels
     audio, z = z[:, :, :n_rem], z[:, :, n_rem:]
     for k in reversed(range(cfg.n_flows)):
@@ -82,8 +94,11 @@ def infer_packed(mel, z, flags, w, cfg, dtype=np.float32):
         out = wn_block_masked(a0, spect, w, f'waveglow/block-{k}', real, cfg.n_layers, cfg.n_channels)
         a1 = (a1 - out[:, :, :n_half]) / np.exp(out[:, :, n_half:])
         audio = np.concatenate([a0, a1], axis=2) @ R.inv1x1_reverse_matrix(w[f'waveglow/invertible_conv-{k}/conv/kernel'])
-        audio = audio * real
+        if mask_state:
+            audio = audio * real
         if k % cfg.n_early_every == 0 and k > 0:
             audio = np.concatenate([z[:, :, :cfg.n_early_size], audio], axis=2)
             z = z[:, :, cfg.n_early_size:]
+        if states is not None and k in (11, 8, 4, 0):
+            states[k] = audio
     return audio.reshape(-1)

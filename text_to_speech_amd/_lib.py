@@ -65,6 +65,8 @@ SIGNATURES = {
     'tts_hip_waveglow_probe_acts': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_void_p, c_int]),
     'tts_hip_waveglow_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_int, c_int, c_int, c_void_p,
                                        c_int]),
+    'tts_hip_waveglow_probe_rows': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_int, c_int,
+                                            c_int, c_void_p, c_int]),
     'tts_hip_last_waveglow_tiles': (c_int, [c_void_p]),
     'tts_hip_mel_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]),
     'tts_hip_mel_stft_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int]),

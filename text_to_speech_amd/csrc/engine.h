@@ -76,7 +76,7 @@ struct WaveGlowDev {
     bool f16_ready = false, x3_ready = false;
     int form_mode = 1, last_form = -1;       // tts_hip_set_waveglow_form / tts_hip_last_waveglow_form
     int last_tiles = -1;                     // tts_hip_last_waveglow_tiles: WN GEMM tile family of the last call
-    int probe_flow = -1, probe_layer = -1;   // tts_hip_waveglow_probe (test hook): stop after this layer (what 0, 2) or flow
+    int probe_flow = -1, probe_layer = -1;   // tts_hip_waveglow_probe[_rows] (test hook): stop after this layer (what 0, 2) or flow
     int probe_what = 0;                      //   (what 1) and copy its gated activations [B][T * 32][C], the flow state
     float* probe_out = nullptr;              //   [B][T * 32][n] or the layer's conditioning plane [B][T * 32][1024] (what 2;
                                              //   Winograd form only) to this device buffer

@@ -574,21 +574,31 @@ int tts_hip_waveglow_infer_f16x3(tts_hip_engine* e, const float* mel, int B, int
     return waveglow_call(e, c);
 }
 
-// Test hook: the gated activations of one WN layer (before the res/skip and `end` convolutions) or the flow state after one
-// flow, natural position order, in any precision.
-int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int precision,
-                           int flow, int what, int layer, float* out, int mem) {
+// Test hook: the gated activations of one WN layer (before the res/skip and `end` convolutions), its conditioning plane or
+// the flow state after one flow, natural position order, in any precision -- of a call without lengths, of the one run of a
+// ragged call (the table and its staging are waveglow_call's) or of the packed row behind waveglow_run_packed's gather.
+static int waveglow_probe_call(tts_hip_engine* e, const char* who, const float* mel, int B, int T, const int32_t* lengths,
+                               bool packed, const float* z, float sigma, int precision, const WgProbe& p, int mem) {
     if (!e) return TTS_HIP_EINVAL;
     if (!e->wg.ready) return set_err(e, TTS_HIP_ENOTREADY, "waveglow weights not finalized");
-    if (!mel || !out || B <= 0 || T <= 0 || precision < 0 || precision > 2 || flow < 0 || flow > 11 || what < 0 || what > 2 ||
-        layer < 0 || layer > 7 || (long long)B * T > 31744 || (what == 2 && precision != 0))
-        return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: bad argument");
-    if (mem != TTS_HIP_MEM_HOST && mem != TTS_HIP_MEM_DEVICE) return set_err(e, TTS_HIP_EINVAL, "waveglow_probe: bad mem kind %d", mem);
+    WgCall c = wg_call(who, mel, B, T, lengths, packed, WG_NOISE_Z, sigma, nullptr, precision, false);
+    c.z = z, c.mem = mem;
+    char why[512];
+    if (int rc = wg_probe_check(c, p, why, sizeof why)) return set_err(e, rc, "%s", why);
     HIPCHK(e, hipSetDevice(e->device));
+    WgTable& tab = e->wg.call_table;
+    if (lengths) {                                               // one run: every row (ragged) or the one packed row
+        wg_call_table(B, T, lengths, packed, B, &tab);
+        HIPCHK(e, e->wg.ragged_info.ensure(tab.info.size() * sizeof(int)));
+        HIPCHK(e, hipMemcpyAsync(e->wg.ragged_info.p, tab.info.data(), tab.info.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    }
     // what 1: the flow's 2 * n_half channels, preceded by the early output that flows 8 and 4 append
     // what 2: the conditioning plane (bias included, gate-interleaved columns) that the Winograd form builds for the layer
+    const int flow = p.flow, what = p.what;
     const int width = what == 0 ? e->wg.channels : what == 2 ? 2 * e->wg.channels : e->wg.flow[flow].n_rem + (flow % 4 == 0 && flow > 0 ? 2 : 0);
-    const size_t n_out = (size_t)B * T * 32 * width;
+    const size_t frames = packed ? (size_t)tab.F : (size_t)B * T;
+    const size_t n_out = frames * 32 * width;
+    if (!n_out) return TTS_HIP_OK;                               // a packed row without a frame: `out` holds nothing
     const float* d_mel = mel;
     const float* d_z = z;
     struct Scratch : DevBuf {                                   // (DevBuf has no destructor: the engine's buffers live with the handle)
@@ -600,15 +610,18 @@ int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, co
     }
     HIPCHK(e, e->wg.io_out.ensure((size_t)B * T * 256 * 4));      // the run's audio argument (flow 0's state)
     e->wg.probe_flow = flow;
-    e->wg.probe_layer = layer;
+    e->wg.probe_layer = p.layer;
     e->wg.probe_what = what;
-    e->wg.probe_out = mem == TTS_HIP_MEM_HOST ? tmp.f() : out;
-    int rc = waveglow_run(e, d_mel, B, T, d_z, sigma, e->wg.io_out.f(), precision);
+    e->wg.probe_out = mem == TTS_HIP_MEM_HOST ? tmp.f() : p.out;
+    const int* d_info = (const int*)e->wg.ragged_info.p;
+    int rc = packed    ? waveglow_run_packed(e, d_mel, B, T, d_z, sigma, e->wg.io_out.f(), precision, d_info, tab.F, tab.n_gap)
+             : lengths ? waveglow_run(e, d_mel, B, T, d_z, sigma, e->wg.io_out.f(), precision, d_info, d_info + B, tab.run_tails[0])
+                       : waveglow_run(e, d_mel, B, T, d_z, sigma, e->wg.io_out.f(), precision);
     e->wg.probe_out = nullptr;
     e->wg.probe_flow = e->wg.probe_layer = -1;
     e->wg.probe_what = 0;
     hipError_t herr = hipSuccess;
-    if (!rc && mem == TTS_HIP_MEM_HOST) herr = hipMemcpyAsync(out, tmp.p, n_out * 4, hipMemcpyDeviceToHost, e->stream);
+    if (!rc && mem == TTS_HIP_MEM_HOST) herr = hipMemcpyAsync(p.out, tmp.p, n_out * 4, hipMemcpyDeviceToHost, e->stream);
     const hipError_t serr = hipStreamSynchronize(e->stream);
     if (rc) return rc;
     HIPCHK(e, herr);
@@ -616,9 +629,22 @@ int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, co
     return TTS_HIP_OK;
 }
 
+int tts_hip_waveglow_probe_rows(tts_hip_engine* e, const float* mel, int B, int T, const int32_t* lengths, int packed,
+                                const float* z, float sigma, int precision, int flow, int what, int layer, float* out, int mem) {
+    return waveglow_probe_call(e, "tts_hip_waveglow_probe_rows", mel, B, T, lengths, packed != 0, z, sigma, precision,
+                               WgProbe{flow, what, layer, out}, mem);
+}
+
+int tts_hip_waveglow_probe(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int precision,
+                           int flow, int what, int layer, float* out, int mem) {
+    return waveglow_probe_call(e, "tts_hip_waveglow_probe", mel, B, T, nullptr, false, z, sigma, precision,
+                               WgProbe{flow, what, layer, out}, mem);
+}
+
 int tts_hip_waveglow_probe_acts(tts_hip_engine* e, const float* mel, int B, int T, const float* z, float sigma, int flow,
                                 int layer, float* acts, int mem) {
-    return tts_hip_waveglow_probe(e, mel, B, T, z, sigma, 0, flow, 0, layer, acts, mem);
+    return waveglow_probe_call(e, "tts_hip_waveglow_probe_acts", mel, B, T, nullptr, false, z, sigma, 0,
+                               WgProbe{flow, 0, layer, acts}, mem);
 }
 
 int tts_hip_random_fill(tts_hip_engine* e, int kind, uint64_t seed, uint64_t offset, float* out, int64_t n, void* stream) {

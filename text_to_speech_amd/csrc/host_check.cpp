@@ -16,7 +16,8 @@
 // rows per run as the engine derives them.  Settings: B= precision= mem= async=1 noise=0|1|2 (WgNoise) and
 // null=mel,audio,keys,offsets to pass that pointer as NULL.  First line "<status> <message>" of wg_call_check; when the call
 // is accepted: "F n_gap", then the lines "info ...", "run_tails ..." and "counts ..." of wg_call_table
-// (tests/test_wg_call.py compares them with packing_plan and a numpy restatement).
+// (tests/test_wg_call.py compares them with packing_plan and a numpy restatement).  flow= what= or layer= (default 0): the
+// inverse direction's test hook instead (wg_probe_check; null=out for its output, c.audio is not looked at); the same lines.
 //        ttsw_check_asan --wg-encode T [KEY=VALUE...] [LEN...]  -- the front end of a forward-flow call (wg_encode_check of
 // wg_call.h) for a batch of B = number of LEN rows (no LEN: lengths NULL, B from B=) run as an entry point named "who".
 // Settings: B= mem= async=1 and null=audio,mel,z,stats.  One line "<status> <message>" (tests/test_waveglow_encode.py compares
@@ -127,8 +128,10 @@ static int print_wn_taps(int h, int T, const std::vector<int>& lens) {
 }
 
 static int print_wg_call(int argc, char** argv) {
-    static float mel, audio;                                                   // never read: the front end only tests pointers
+    static float mel, audio, out;                                              // never read: the front end only tests pointers
     static uint64_t keys, offsets;
+    WgProbe probe{0, 0, 0, &out};
+    bool probing = false;
     WgCall c{};
     c.who = "who", c.mel = &mel, c.audio = &audio, c.keys = &keys, c.offsets = &offsets;
     c.T = atoi(argv[2]), c.packed = atoi(argv[3]) != 0, c.sigma = 1.f;
@@ -147,7 +150,11 @@ static int print_wg_call(int argc, char** argv) {
         else if (key == "mem") c.mem = v;
         else if (key == "async") c.async = v != 0;
         else if (key == "noise") c.noise = (WgNoise)v;
+        else if (key == "flow") probe.flow = v, probing = true;
+        else if (key == "what") probe.what = v, probing = true;
+        else if (key == "layer") probe.layer = v, probing = true;
         else if (key == "null") {
+            if (strstr(eq, "out")) probe.out = nullptr;
             if (strstr(eq, "mel")) c.mel = nullptr;
             if (strstr(eq, "audio")) c.audio = nullptr;
             if (strstr(eq, "keys")) c.keys = nullptr;
@@ -157,7 +164,7 @@ static int print_wg_call(int argc, char** argv) {
     c.lengths = lens.empty() ? nullptr : lens.data();
     c.B = lens.empty() ? B : (int)lens.size();
     char why[512] = "";
-    const int rc = wg_call_check(c, why, sizeof why);
+    const int rc = probing ? wg_probe_check(c, probe, why, sizeof why) : wg_call_check(c, why, sizeof why);
     printf("%d %s\n", rc, why);
     if (rc) return 0;
     if (chunkB <= 0) chunkB = c.packed ? c.B : kMaxFramesPerRun / c.T;

@@ -1521,6 +1521,7 @@ int waveglow_run_packed(tts_hip_engine* e, const float* d_mel, int B, int T, con
         int rc = waveglow_run(e, wg.mel_ragged.f(), 1, F, d_z ? wg.packed_z.f() : nullptr, sigma, wg.packed_out.f(), precision,
                               nullptr, d_flags + F, n_gap, d_flags);
         if (rc) return rc;
+        if (wg.probe_out) return TTS_HIP_OK;                     // test hook: an armed probe stopped the run, no audio to scatter
     }
     // (no real frame at all: the scatter reads nothing of `packed` and stores the zeros)
     const long long n4 = (long long)B * T * 64;

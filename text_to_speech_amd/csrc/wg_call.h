@@ -1,7 +1,8 @@
 // wg_call.h -- what one WaveGlow call is, why it may be refused and the int table it stages: pure host code on the caller's
 // arguments (no HIP include; also built with plain g++ under ASan / UBSan by csrc/host_check.cpp, --wg-call, and compared
 // there with tests/waveglow_packed_ref.py::packing_plan and a numpy restatement, tests/test_wg_call.py).  Every
-// tts_hip_waveglow_infer* entry point fills a WgCall and hands it to waveglow_call (engine.hip); the forward flow's two entry
+// tts_hip_waveglow_infer* entry point fills a WgCall and hands it to waveglow_call (engine.hip); the inverse direction's test
+// hooks fill a WgCall and a WgProbe (wg_probe_check; --wg-call with flow= / what= / layer=); the forward flow's two entry
 // points fill a WgEncode (--wg-encode, tests/test_waveglow_encode.py).
 #pragma once
 #include <stdint.h>
@@ -67,14 +68,15 @@ inline int wg_refuse(char* msg, size_t n, const char* who, const char* fmt, ...)
 // match wins, in this order: precision, mem kind, keys / offsets, B, mel / audio / T, B * T, packed without lengths,
 // lengths[b], then the one-run limit (F of a packed call, T of any other).  Reads host memory only (lengths); TTS_HIP_OK or
 // TTS_HIP_EINVAL with the reason in `msg`.  Nothing is copied or launched before it has passed.
-inline int wg_call_check(const WgCall& c, char* msg, size_t n) {
+// (audio = false: the probe below, which has its own one output, skips the test of c.audio.)
+inline int wg_call_check(const WgCall& c, char* msg, size_t n, bool audio = true) {
     if (c.precision < 0 || c.precision > 2)
         return wg_refuse(msg, n, c.who, "precision must be 0 (f32), 1 (f16) or 2 (f16x3), got %d", c.precision);
     if (!c.async && c.mem != TTS_HIP_MEM_HOST && c.mem != TTS_HIP_MEM_DEVICE)
         return wg_refuse(msg, n, c.who, "bad mem kind %d", c.mem);
     if (c.noise == WG_NOISE_ROWS && (!c.keys || !c.offsets)) return wg_refuse(msg, n, c.who, "keys / offsets is NULL");
     if (c.B <= 0) return wg_refuse(msg, n, c.who, "bad argument: B = %d must be positive", c.B);
-    if (!c.mel || !c.audio || c.T <= 0) return wg_refuse(msg, n, c.who, "bad argument (mel or audio is NULL, or T = %d <= 0)", c.T);
+    if (!c.mel || (audio && !c.audio) || c.T <= 0) return wg_refuse(msg, n, c.who, "bad argument (mel or audio is NULL, or T = %d <= 0)", c.T);
     if ((long long)c.B * c.T * 32 > kMaxGroups)
         return wg_refuse(msg, n, c.who, "B*T too large (B = %d, T = %d: above 2^25 frames)", c.B, c.T);
     if (c.packed && !c.lengths) return wg_refuse(msg, n, c.who, "packed needs lengths, got NULL");
@@ -97,6 +99,31 @@ inline int wg_call_check(const WgCall& c, char* msg, size_t n) {
         return wg_refuse(msg, n, c.who, "T = %d frames exceeds one run's limit (%d); use windowed inference", c.T,
                          kMaxFramesPerRun);
     }
+    return TTS_HIP_OK;
+}
+
+// Where the inverse direction's test hook (tts_hip_waveglow_probe_rows and the two older symbols that call it) stops and what
+// it copies to `out`: what 0 the gated activations of WN layer `layer` of flow `flow`, 1 the flow state after flow `flow`,
+// 2 that layer's conditioning plane (fp32 only).
+struct WgProbe {
+    int flow, what, layer;
+    float* out;
+};
+// Refused: whatever wg_call_check refuses of the same mel / B / T / lengths / packed / precision / mem (c.audio is not looked
+// at), then flow outside 0 .. 11, what outside 0 .. 2, layer outside 0 .. 7, what 2 in another precision than fp32, more
+// frames than one run holds (B * T; a packed row's F was wg_call_check's last reason already: the probe is one run, it does
+// not slice), out NULL.
+inline int wg_probe_check(const WgCall& c, const WgProbe& p, char* msg, size_t n) {
+    if (int rc = wg_call_check(c, msg, n, false)) return rc;
+    if (p.flow < 0 || p.flow > 11) return wg_refuse(msg, n, c.who, "flow = %d is outside [0, 11]", p.flow);
+    if (p.what < 0 || p.what > 2) return wg_refuse(msg, n, c.who, "what = %d must be 0 (acts), 1 (state) or 2 (cond)", p.what);
+    if (p.layer < 0 || p.layer > 7) return wg_refuse(msg, n, c.who, "layer = %d is outside [0, 7]", p.layer);
+    if (p.what == 2 && c.precision != 0)
+        return wg_refuse(msg, n, c.who, "what = 2 (cond) needs precision 0 (f32), got %d: only fp32 builds the plane", c.precision);
+    if (!c.packed && (long long)c.B * c.T > kMaxFramesPerRun)
+        return wg_refuse(msg, n, c.who, "B * T = %lld frames exceeds one run's limit (%d); the probe is one run",
+                         (long long)c.B * c.T, kMaxFramesPerRun);
+    if (!p.out) return wg_refuse(msg, n, c.who, "bad argument: out is NULL");
     return TTS_HIP_OK;
 }
 

@@ -422,21 +422,36 @@ class HipEngine:
                           lambda ins, outs, where: (ins[0], ins[1], B, T, lens, flow, whats[what], outs[0]))[0]
 
     def waveglow_probe(self, mel, z=None, sigma: float = 1.0, precision: str = 'f32', flow: int = 11, what: str = 'acts',
-                       layer: int = 0):
+                       layer: int = 0, lengths=None, packed: bool = False):
         """Test hook (tts_hip_waveglow_probe): run `waveglow_infer` in `precision` up to flow `flow` and return either the gated
         activations [B, T*32, C] (C = `waveglow_channels`) of its WN layer `layer` (what='acts') or the flow state [B, T*32, n] right after the flow,
         early output included (what='state'; the reference's audio after that flow), or the conditioning plane [B, T*32, 1024]
         of that layer -- sum_q V_q mel[t - q] + b, columns in the gate-interleaved order of the engine's weights -- that the
-        fp32 Winograd form builds (what='cond'; layers 1 - 7 of calls of 144 frames or more, 512-channel models only)."""
+        fp32 Winograd form builds (what='cond'; layers 1 - 7 of calls of 144 frames or more, 512-channel models only).
+        `lengths` [B] (tts_hip_waveglow_probe_rows): the one run of `waveglow_infer(.., lengths=)` stopped there, same shapes; the
+        state is 0 behind a row's length, activations and planes are not specified there.  `packed=True` (needs `lengths`):
+        the packed row of `waveglow_infer(.., lengths=, packed=True)` stopped there, in the packed row's OWN layout [F*32, width]
+        (F frames: the rows that hold frames one after another, 4 gap frames between two; no scatter), state 0 on gap frames."""
         whats = {'acts': 0, 'state': 1, 'cond': 2}
         if precision not in self._WG_PRECISIONS or what not in whats:
             raise ValueError(f'precision must be one of {tuple(self._WG_PRECISIONS)} and what one of {tuple(whats)}')
-        B, T, _ = self._wg_inputs(mel, z=z)
+        if packed and lengths is None:
+            raise ValueError('packed=True needs lengths (one frame count per row)')
+        B, T, lens = self._wg_inputs(mel, z=z, lengths=lengths)
         C = self.waveglow_channels
         width = C if what == 'acts' else 2 * C if what == 'cond' else (4 if flow >= 8 else 6 if flow >= 4 else 8) + (2 if flow in (4, 8) else 0)
-        return self._call('waveglow_probe', [(mel, None, 'float32'), (z, None, 'float32')], lambda new: (new((B, T * 32, width)),),
-                          lambda ins, outs, where: (ins[0], B, T, ins[1], float(sigma), self._WG_PRECISIONS[precision], int(flow),
-                                                    whats[what], int(layer), outs[0]))[0]
+        if lens is None:
+            return self._call('waveglow_probe', [(mel, None, 'float32'), (z, None, 'float32')], lambda new: (new((B, T * 32, width)),),
+                              lambda ins, outs, where: (ins[0], B, T, ins[1], float(sigma), self._WG_PRECISIONS[precision], int(flow),
+                                                        whats[what], int(layer), outs[0]))[0]
+        if packed:                                               # wg_packed_frames (csrc/wg_call.h)
+            rows = int((lens > 0).sum())
+            shape = ((int(lens.sum()) + 4 * max(rows - 1, 0)) * 32, width)
+        else:
+            shape = (B, T * 32, width)
+        return self._call('waveglow_probe_rows', [(mel, None, 'float32'), (z, None, 'float32')], lambda new: (new(shape),),
+                          lambda ins, outs, where: (ins[0], B, T, lens, 1 if packed else 0, ins[1], float(sigma),
+                                                    self._WG_PRECISIONS[precision], int(flow), whats[what], int(layer), outs[0]))[0]
 
     def waveglow_probe_acts(self, mel, z=None, sigma: float = 1.0, flow: int = 11, layer: int = 1):
         """Test hook (tts_hip_waveglow_probe_acts): the gated activations [B, T*32, C] (C = `waveglow_channels`) of WN layer `layer` of flow `flow` on
