@@ -310,6 +310,51 @@ int tts_hip_pitch(tts_hip_engine* e, const float* audio, int B, int N, const int
                   int tau_min, int tau_max, float threshold, float* out, int mem, void* stream);
 int tts_hip_pitch_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate, int hop, int win,
                         int tau_min, int tau_max, float threshold, int what, float* out, int mem, void* stream);
+/* Pitch of a ragged batch of recordings, probabilistic YIN (Mauch & Dixon 2014; the Boltzmann prior over the trough index is
+ * left out): every trough of d' is a pitch candidate with a probability, and a Viterbi decode over pitch bins x {voiced,
+ * unvoiced} chooses the track and the voicing.  Frames, d and d' are those of tts_hip_pitch, bit for bit.
+ *   troughs      lag tau in [tau_min, tau_max] is a trough when d'(tau) < d'(tau - 1) (d'(0) = 1) and (tau = tau_max or
+ *                d'(tau) <= d'(tau + 1)).
+ *   thresholds   s_i = float32(i) / float32(n_thresh), i = 1 .. n_thresh; prior: HOST float32 [n_thresh], the mass of each
+ *                threshold; cum(k) = prior[0] + ... + prior[k - 1] in double, rounded once to float32.
+ *   probability  troughs by ascending lag, m = the smallest d' of the troughs before (+inf for the first): a trough with
+ *                d' < m takes p = the prior of the thresholds with d' < s_i <= m, computed as cum(#{s_i <= m}) - cum(#{s_i <=
+ *                d'}) in float32 (comparisons in float32 on the float32 d'); any other trough p = 0.  The trough of smallest d'
+ *                (smallest lag on ties) adds no_trough_prob * cum(#{s_i <= d'}), product and sum rounded to float32.
+ *   period, bin  a trough's delta is the interpolation of tts_hip_pitch (so |delta| <= 1/2), period = tau + delta, f = rate /
+ *                period, pos = 12 bps log2(f / fmin), all in double; bin = clip(floor(pos + 1/2), 0, n_bins - 1).
+ *   observation  obs[t, j] = the sum of p over the troughs of bin j by ascending lag in float32; cand[t, j] = float32(period)
+ *                of the bin's trough of largest p (smallest lag on ties), 0 if the bin has none.  v_t = min(sum_j obs[t, j],
+ *                1) (a fixed tree of float32 sums).  log-observations: log(max(obs[t, j], 2^-100)) of voiced state j, log(max((1 -
+ *                v_t) / n_bins, 2^-100)) of every unvoiced state.
+ *   states       0 .. n_bins - 1 voiced, n_bins .. 2 n_bins - 1 unvoiced.  Bins i -> j: w = max(0, max_step + 1 - |i - j|)
+ *                over the sum of w over the bins j of the range; times 1 - switch_prob where voicing is kept, switch_prob where it
+ *                changes.  The tables log w, log norm(i), log(1 - switch_prob), log(switch_prob) are computed in double and
+ *                rounded once.  The initial distribution is uniform and dropped.
+ *   decode       delta_0(j) = logobs_0(j); delta_t(j) = logobs_t(j) + max_i [((delta_{t-1}(i) - log norm(i)) + log w(i, j)) +
+ *                log keep-or-switch] in float32, the smallest predecessor index on ties; after every frame the frame's maximum
+ *                is subtracted.  The last state is the argmax (smallest index on ties); the path follows the stored
+ *                predecessors.  Only a row's own F_b frames are decoded.
+ * out: float32 [3, B, F] = f0 in Hz (0 where the decoded state is unvoiced; else rate / cand[t, j] of the decoded bin j, or
+ * the bin's centre fmin 2^(j / (12 bps)) where the bin has no candidate; computed in double, rounded once), the same pitch of
+ * the decoded bin whether voiced or not, v_t; zeros at and behind F_b.  audio and out live where `mem` says.  A row's results
+ * do not depend on the rows beside it or on `mem`, bit for bit: no floating-point atomics.  Needs no weights.  Refused
+ * (TTS_HIP_EINVAL, first match wins, nothing copied or launched; csrc/pitch_call.h): everything tts_hip_pitch refuses, in its
+ * order; n_bins outside 1 .. 1024; bps outside 1 .. 100; max_step outside 1 .. n_bins; n_thresh outside 1 .. 1024; a NULL prior;
+ * a prior entry that is not finite or negative; switch_prob outside (0, 1); no_trough_prob outside [0, 1]; fmin not finite and
+ * positive; a buffer of the call (out, the observations, the uint16 backpointers [B, F, 2 n_bins]) at or above 2^31 bytes.
+ * Synchronizes `stream` (NULL: the handle's) before returning.
+ * Test hook pyin_probe: the same arguments, returns the stage `what` dense, zeros at and behind F_b: TTS_HIP_PYIN_TROUGH (p per
+ * lag) [B, F, tau_max + 1], TTS_HIP_PYIN_OBS [2, B, F, n_bins] (obs, cand), TTS_HIP_PYIN_DELTA [B, F, 2 n_bins] (after the
+ * frame's maximum is subtracted), TTS_HIP_PYIN_BACK [B, F, 2 n_bins] (the predecessor state as float32; frame 0: the state
+ * itself), TTS_HIP_PYIN_PATH [B, F] (the decoded state as float32).  Any other `what` is TTS_HIP_EINVAL, after fmin.          */
+enum { TTS_HIP_PYIN_TROUGH = 0, TTS_HIP_PYIN_OBS = 1, TTS_HIP_PYIN_DELTA = 2, TTS_HIP_PYIN_BACK = 3, TTS_HIP_PYIN_PATH = 4 };
+int tts_hip_pyin(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate, int hop, int win,
+                 int tau_min, int tau_max, const float* prior, int n_thresh, float no_trough_prob, double fmin, int bps, int n_bins,
+                 int max_step, float switch_prob, float* out, int mem, void* stream);
+int tts_hip_pyin_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, int rate, int hop, int win,
+                       int tau_min, int tau_max, const float* prior, int n_thresh, float no_trough_prob, double fmin, int bps,
+                       int n_bins, int max_step, float switch_prob, int what, float* out, int mem, void* stream);
 /* Two F0 tracks compared along a path, per row: F0 RMSE, voicing error and gross pitch error, the figures reported beside
  * MCD-DTW.  f0_a: [B, Fa], f0_b: [B, Fb] float32 in Hz; a frame is voiced iff its value is > 0 (a NaN is unvoiced).  len_a,
  * len_b: HOST int32 [B], each in 1 .. Fa / 1 .. Fb, NULL = every row full.  path: NULL = the diagonal (t, t), t < min(la, lb);

@@ -100,6 +100,10 @@ SIGNATURES = {
                               c_void_p]),
     'tts_hip_pitch_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
                                     c_void_p, c_int, c_void_p]),
+    'tts_hip_pyin': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float,
+                             c_double, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
+    'tts_hip_pyin_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float,
+                                   c_double, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p]),
     'tts_hip_f0_error': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float,
                                  c_void_p, c_int, c_void_p]),
     'tts_hip_tacotron2_reencode': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),

@@ -254,7 +254,8 @@ struct MelDtwDev {
 // Pitch tracks and their comparison (pitch.hip): no weights and no tables, the one workspace of a call
 struct PitchDev {
     std::vector<int32_t> lens_h;        // host image of a call's length tables while it is staged
-    DevBuf ws;                          // PitchLayout / F0ErrorLayout (pitch_call.h)
+    std::vector<float> tables_h;        // host image of a pYIN call's cumulative prior and transition tables (pyin_tables)
+    DevBuf ws;                          // PitchLayout / PyinLayout / F0ErrorLayout (pitch_call.h)
 };
 
 struct TimedLaunch {

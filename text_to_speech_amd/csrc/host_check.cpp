@@ -74,6 +74,12 @@
 // Fa= Fb= P= path=0|1 gross= mem= la=N,N,... lb=N,N,... null=f0_a,f0_b,stats.  First line "<status> <message>"; when the call is
 // accepted "F threads lens in out out_elems bytes" of pitch_layout, or "lens in_a in_b path stats bytes" of f0_error_layout
 // (tests/test_pitch.py compares them with a Python restatement).
+//        ttsw_check_asan --pyin [KEY=VALUE...]  -- the front end of a probabilistic-YIN call (pyin_check, pyin_layout and pyin_tables
+// of pitch_call.h) run as an entry point named "who".  Settings: those of a pitch call but threshold=, and n_bins= bps= max_step=
+// n_thresh= prior=P,P,... (absent: 1 / n_thresh each; nan and inf are understood) switch= no_trough= fmin= probe=1 what=
+// null=audio,out,prior and tables=1.  First line "<status> <message>"; when the call is accepted "F threads vit_threads" and the
+// ten offsets, out_elems and bytes of pyin_layout, and with tables=1 the cumulative prior and the transition tables, one value
+// a line (tests/test_pyin.py compares them with a Python restatement).
 //        ttsw_check_asan --time-stretch [KEY=VALUE...] [LEN...]  -- the front end of a time-stretch call (time_stretch_check of
 // audio_call.h) for a batch of B = number of LEN rows of N samples (no LEN: lengths NULL, B from B=) run as an entry point named
 // "who", on a Tacotron-kind plan of filter_length= hop_length= win_length= pre_emph= (mel_kind=1: a Whisper plan).  Settings:
@@ -570,6 +576,62 @@ static int print_pitch(int argc, char** argv) {
     return 0;
 }
 
+static int print_pyin(int argc, char** argv) {
+    std::map<std::string, long long> v{{"B", 1}, {"N", 4096}, {"rate", 22050}, {"hop", 256}, {"win", 1024}, {"tau_min", 45},
+                                       {"tau_max", 367}, {"mem", TTS_HIP_MEM_HOST}, {"probe", 0}, {"what", -1}, {"n_bins", 368},
+                                       {"bps", 10}, {"max_step", 51}, {"n_thresh", 4}, {"tables", 0}};
+    std::map<std::string, double> f{{"switch", 0.01}, {"no_trough", 0.01}, {"fmin", 60.0}};
+    std::vector<int32_t> len;
+    std::vector<float> prior;
+    bool have_prior = false;
+    std::string nulls;
+    for (int i = 2; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) return 2;
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        if (key == "null") nulls = eq + 1;
+        else if (key == "len" || key == "prior") {
+            have_prior |= key == "prior";
+            for (const char* p = eq + 1; *p;) {
+                char* end = nullptr;
+                if (key == "len") len.push_back((int32_t)strtol(p, &end, 10));
+                else prior.push_back((float)strtod(p, &end));
+                if (end == p) return 2;
+                p = *end == ',' ? end + 1 : end;
+            }
+        } else if (f.count(key)) f[key] = strtod(eq + 1, nullptr);
+        else if (v.count(key)) v[key] = atoll(eq + 1);
+        else return 2;
+    }
+    const auto null = [&](const char* name) { return ("," + nulls + ",").find(std::string(",") + name + ",") != std::string::npos; };
+    // tables shorter than the check reads would be read past their end: that is the caller's contract, not the check's
+    if (!len.empty() && (long long)len.size() < v["B"]) return 2;
+    const long long n_thresh = v["n_thresh"];
+    if (!have_prior && n_thresh >= 1 && n_thresh <= kPyinMaxThresh) prior.assign((size_t)n_thresh, 1.f / (float)n_thresh);
+    if (!null("prior") && n_thresh >= 1 && n_thresh <= kPyinMaxThresh && (long long)prior.size() < n_thresh) return 2;
+    // audio and out are never read: the checks only test the pointers' values
+    const PyinCall c{PitchCall{"who", null("audio") ? nullptr : (const float*)(uintptr_t)0x100000000ull, (int)v["B"], (int)v["N"],
+                               len.empty() ? nullptr : len.data(), (int)v["rate"], (int)v["hop"], (int)v["win"], (int)v["tau_min"],
+                               (int)v["tau_max"], 0.5f, false, -1, null("out") ? nullptr : (float*)(uintptr_t)0x500000000ull, (int)v["mem"],
+                               nullptr},
+                     null("prior") ? nullptr : prior.data(), (int)n_thresh, (float)f["no_trough"], f["fmin"], (int)v["bps"], (int)v["n_bins"],
+                     (int)v["max_step"], (float)f["switch"], v["probe"] != 0, (int)v["what"]};
+    char why[256] = "";
+    const int rc = pyin_check(c, why, sizeof why);
+    printf("%d %s\n", rc, why);
+    if (rc) return 0;
+    const PyinLayout l = pyin_layout(c);
+    printf("%d %d %d %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", l.F, l.threads, l.vit_threads, l.lens, l.in, l.out, l.cum, l.tables,
+           l.obs, l.cand, l.vprob, l.back, l.path, l.out_elems, l.bytes);
+    if (v["tables"]) {                                          // the host tables, one value a line: cum, then the transition tables
+        std::vector<float> cum((size_t)c.n_thresh + 1), tab((size_t)c.max_step + 1 + c.n_bins + 2);
+        pyin_tables(c, cum.data(), tab.data());
+        for (float x : cum) printf("%.9g\n", x);
+        for (float x : tab) printf("%.9g\n", x);
+    }
+    return 0;
+}
+
 static int print_time_stretch(int argc, char** argv) {
     // never read: the check only tests the pointers' values
     const float* audio = (const float*)(uintptr_t)0x100000000ull;
@@ -637,6 +699,7 @@ static int print_time_stretch(int argc, char** argv) {
 int main(int argc, char** argv) {
     if (argc >= 2 && !strcmp(argv[1], "--time-stretch")) return print_time_stretch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--pitch")) return print_pitch(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "--pyin")) return print_pyin(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--mel-dtw")) return print_mel_dtw(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--taco-loss")) return print_taco_loss(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "--taco-call")) return print_taco_call(argc, argv);

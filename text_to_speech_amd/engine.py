@@ -807,6 +807,76 @@ class HipEngine:
                           lambda ins, outs, where: (ins[0], B, N, lens, rate, hop, win, tau_min, tau_max, threshold,
                                                     self.PITCH_STAGES[what], outs[0], *where), twin=False)[0]
 
+    PYIN_STAGES = {'trough': 0, 'obs': 1, 'delta': 2, 'back': 3, 'path': 4}      # TTS_HIP_PYIN_*
+    PYIN_MAX_BINS, PYIN_MAX_BPS, PYIN_MAX_THRESHOLDS = 1024, 100, 1024
+
+    def _pyin_request(self, who, audio, lengths, rate, hop, win, fmin, fmax, bins_per_semitone, beta, n_thresholds, max_transition_rate,
+                      switch_prob, no_trough_prob, prior=None, n_bins=None, max_step=None):
+        """The checked arguments of a `pyin` / `pyin_probe` call -> (B, N, F, the C arguments from `lengths` to `switch_prob`,
+        tau_max, n_bins).  `prior`: a table of its own in place of `beta_prior(*beta, n_thresholds)`; `n_bins`, `max_step`: those in
+        place of what `pitch.pyin_geometry` gives.  Raises before any library call."""
+        from .pitch import beta_prior, pyin_geometry
+        B, N, F, lens, rate, hop, win, tau_min, tau_max, _ = self._pitch_request(who, audio, lengths, rate, hop, win, fmin, fmax, 0.5)
+        if bins_per_semitone != int(bins_per_semitone) or not 1 <= int(bins_per_semitone) <= self.PYIN_MAX_BPS:
+            raise ValueError(f'{who}: bins_per_semitone = {bins_per_semitone!r} must be an integer in [1, {self.PYIN_MAX_BPS}]')
+        geometry = pyin_geometry(rate, hop, fmin, fmax, int(bins_per_semitone), max_transition_rate)
+        n_bins = geometry[0] if n_bins is None else int(n_bins)
+        max_step = min(geometry[1], n_bins) if max_step is None else int(max_step)
+        if not 1 <= max_step <= n_bins and 1 <= n_bins <= self.PYIN_MAX_BINS:
+            raise ValueError(f'{who}: max_step = {max_step} is outside [1, n_bins = {n_bins}]')
+        if not 1 <= n_bins <= self.PYIN_MAX_BINS:
+            raise ValueError(f'{who}: fmin = {fmin!r}, fmax = {fmax!r} at {bins_per_semitone} bins a semitone give {n_bins} bins: '
+                             f'need 1 .. {self.PYIN_MAX_BINS}')
+        if prior is None:
+            if n_thresholds != int(n_thresholds) or not 1 <= int(n_thresholds) <= self.PYIN_MAX_THRESHOLDS:
+                raise ValueError(f'{who}: n_thresholds = {n_thresholds!r} must be an integer in [1, {self.PYIN_MAX_THRESHOLDS}]')
+            prior = beta_prior(int(beta[0]), int(beta[1]), int(n_thresholds)) if tuple(beta) == (int(beta[0]), int(beta[1])) else None
+            if prior is None:
+                raise ValueError(f'{who}: beta = {beta!r} must be two integers')
+        prior = np.ascontiguousarray(np.asarray(prior, dtype=np.float64).reshape(-1), dtype=np.float32)
+        if not 1 <= len(prior) <= self.PYIN_MAX_THRESHOLDS or not (np.isfinite(prior).all() and (prior >= 0).all()):
+            raise ValueError(f'{who}: the prior must hold 1 .. {self.PYIN_MAX_THRESHOLDS} finite entries that are not negative')
+        if not 0.0 < float(np.float32(switch_prob)) < 1.0:
+            raise ValueError(f'{who}: switch_prob = {switch_prob!r} is outside (0, 1) as a float32')
+        if not 0.0 <= float(np.float32(no_trough_prob)) <= 1.0:
+            raise ValueError(f'{who}: no_trough_prob = {no_trough_prob!r} is outside [0, 1]')
+        if B * F * 2 * n_bins * 2 >= 2 ** 31 or B * F * n_bins * 4 >= 2 ** 31:
+            raise ValueError(f'{who}: B = {B}, F = {F}, n_bins = {n_bins}: observations or backpointers of 2^31 bytes or more; split the batch')
+        c_args = (lens, rate, hop, win, tau_min, tau_max, prior, len(prior), float(no_trough_prob), float(fmin), int(bins_per_semitone),
+                  n_bins, max_step, float(switch_prob))
+        return B, N, F, c_args, tau_max, n_bins
+
+    def pyin(self, audio, lengths=None, *, rate=22050, hop=256, win=1024, fmin=60., fmax=500., bins_per_semitone=10, beta=(2, 18),
+             n_thresholds=100, max_transition_rate=35.92, switch_prob=0.01, no_trough_prob=0.01, prior=None, n_bins=None, max_step=None, stream=None):
+        """Probabilistic-YIN pitch tracks of `audio` [B, N] (tts_hip_pyin; the math is pinned in include/tts_hip.h): every trough
+        of the frames' d' (those of `pitch`, bit for bit) is a candidate whose probability sums the Beta(`beta`) prior over
+        `n_thresholds` thresholds, and a Viterbi decode over `bins_per_semitone` pitch bins a semitone from `fmin` to `fmax`,
+        voiced and unvoiced, chooses track and voicing; a step of the track is at most `max_transition_rate` octaves a second
+        (`pitch.pyin_geometry`), voicing changes with `switch_prob`.  Returns float32 [3, B, F], F = 1 + N // hop: f0 in Hz (0
+        where the decoded state is unvoiced), the pitch of the decoded bin whether voiced or not, the voiced probability; zeros
+        at and behind a row's frames.  `prior` (a table of threshold masses), `n_bins` and `max_step` replace what `beta` and the
+        geometry give.  Operands, `lengths` and `stream` as for `pitch`.  Needs no weights."""
+        B, N, F, c_args, _, _ = self._pyin_request('pyin', audio, lengths, rate, hop, win, fmin, fmax, bins_per_semitone, beta,
+                                                   n_thresholds, max_transition_rate, switch_prob, no_trough_prob, prior, n_bins, max_step)
+        return self._call('pyin', [(audio, (B, N), 'float32')], lambda new: (new((3, B, F)),),
+                          lambda ins, outs, where: (ins[0], B, N, *c_args, outs[0], *where), stream, twin=False)[0]
+
+    def pyin_probe(self, audio, lengths=None, *, rate=22050, hop=256, win=1024, fmin=60., fmax=500., bins_per_semitone=10, beta=(2, 18),
+                   n_thresholds=100, max_transition_rate=35.92, switch_prob=0.01, no_trough_prob=0.01, prior=None, n_bins=None, max_step=None,
+                   what='obs'):
+        """Test hook (tts_hip_pyin_probe): one stage of `pyin`, dense with zeros at and behind a row's frames: what='trough' (p
+        per lag) [B, F, tau_max + 1], 'obs' [2, B, F, n_bins] (obs, cand), 'delta' / 'back' [B, F, 2 n_bins], 'path' [B, F]."""
+        if what not in self.PYIN_STAGES:
+            raise ValueError(f'what must be one of {tuple(self.PYIN_STAGES)}, got {what!r}')
+        B, N, F, c_args, tau_max, n_bins = self._pyin_request('pyin_probe', audio, lengths, rate, hop, win, fmin, fmax, bins_per_semitone,
+                                                              beta, n_thresholds, max_transition_rate, switch_prob, no_trough_prob, prior,
+                                                              n_bins, max_step)
+        shape = {'trough': (B, F, tau_max + 1), 'obs': (2, B, F, n_bins), 'path': (B, F)}.get(what, (B, F, 2 * n_bins))
+        if int(np.prod(shape)) * 4 >= 2 ** 31:
+            raise ValueError(f'pyin_probe: a result of shape {shape} is 2^31 bytes or more')
+        return self._call('pyin_probe', [(audio, (B, N), 'float32')], lambda new: (new(shape),),
+                          lambda ins, outs, where: (ins[0], B, N, *c_args, self.PYIN_STAGES[what], outs[0], *where), twin=False)[0]
+
     def f0_error(self, f0_a, f0_b, lengths_a=None, lengths_b=None, path=None, *, gross_cents=GROSS_CENTS, stream=None):
         """F0 tracks `f0_a` [B, Fa] against `f0_b` [B, Fb] (Hz, a frame is voiced iff > 0) along `path` (tts_hip_f0_error):
         None = the diagonal below the shorter length, else int32 [B, P, 2] as `mel_dtw(return_path=True)` returns it -- a

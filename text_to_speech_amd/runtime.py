@@ -322,6 +322,15 @@ class HipRuntime(Runtime):
         """Test hook: one stage of `pitch` (`HipEngine.pitch_probe`)."""
         return self.engine.pitch_probe(audio, lengths, **kwargs)
 
+    def pyin(self, audio, lengths=None, **kwargs):
+        """Probabilistic-YIN pitch tracks of `audio` [B, N] on the engine (`HipEngine.pyin`, whose keywords these are) -> float32
+        [3, B, F]: f0 (0 where unvoiced), the decoded bin's pitch, the voiced probability."""
+        return self.engine.pyin(audio, lengths, **kwargs)
+
+    def pyin_probe(self, audio, lengths=None, **kwargs):
+        """Test hook: one stage of `pyin` (`HipEngine.pyin_probe`)."""
+        return self.engine.pyin_probe(audio, lengths, **kwargs)
+
     def f0_error(self, f0_a, f0_b, lengths_a=None, lengths_b=None, path=None, **kwargs):
         """Two F0 tracks compared along a path (`HipEngine.f0_error`, whose keywords these are) -> float32 [6, B]."""
         return self.engine.f0_error(f0_a, f0_b, lengths_a, lengths_b, path, **kwargs)

@@ -186,7 +186,7 @@ class Tacotron2:
     SYNTHESIS_F0_NAMES = ['f0_rmse_cents', 'vuv_error', 'gross_error', 'voiced_pairs']
 
     def evaluate_synthesis(self, items, *, batch_size=8, max_length=10., n_cep=13, deterministic=True, vocoder=None, pitch=None,
-                           **load_kwargs):
+                           f0_method='yin', f0_config=None, **load_kwargs):
         """The model as it is used -- free-running, through its own stop token and attention -- against held-out recordings:
         mel-cepstral distortion along the DTW path (`metrics`, tts_hip_mel_dtw) of every synthesized mel against its
         recording's.  `items` as for `evaluate`: (text, mel [F, 80]) or (text, audio) pairs; `embeddings=`: the speaker.
@@ -205,20 +205,27 @@ class Tacotron2:
         the tracks share the mels' frames) runs on the vocoded and on the recorded audio, the DTW call also returns its path,
         and `f0_error` along that path appends SYNTHESIS_F0_NAMES: the F0 RMSE of the voiced pairs in cents, the voicing error
         rate (of the pairs), the gross pitch error rate (of the voiced pairs; 0 without any) and the voiced pairs.  Audio,
-        tracks and path stay on the GPU; it needs `pitch` and `f0_error` on the runtime as well."""
+        tracks and path stay on the GPU; it needs `pitch` and `f0_error` on the runtime as well.  `f0_method='pyin'` tracks both
+        with `pyin` (tts_hip_pyin) in place of `pitch`; `f0_config`: the tracker's keywords, on top of `pitch=`."""
+        from .pitch import F0_METHODS, track_f0
+        if f0_method not in F0_METHODS:
+            raise ValueError(f'evaluate_synthesis: f0_method must be one of {F0_METHODS}, got {f0_method!r}')
         load_kwargs = dict(self._resolve_embeddings(load_kwargs))
         embeddings = load_kwargs.pop('embeddings', None)
         runtime = self.compiled_infer
         if getattr(runtime, 'mel_dtw', None) is None or not callable(runtime):
             raise ValueError('evaluate_synthesis needs a runtime with mel_dtw (HipRuntime) behind the model')
-        pitch = dict(pitch or {})
+        pitch = dict(pitch or {}, **(f0_config or {}))
         if vocoder is not None:
-            if getattr(runtime, 'pitch', None) is None or getattr(runtime, 'f0_error', None) is None:
-                raise ValueError('evaluate_synthesis(vocoder=) needs a runtime with pitch and f0_error (HipRuntime) behind the model')
+            tracker = 'pitch' if f0_method == 'yin' else 'pyin'
+            if getattr(runtime, tracker, None) is None or getattr(runtime, 'f0_error', None) is None:
+                raise ValueError(f'evaluate_synthesis(vocoder=) needs a runtime with {tracker} and f0_error (HipRuntime) behind the model')
             if int(pitch.get('hop', 256)) != 256:
                 raise ValueError(f"evaluate_synthesis: the pitch tracks share the mels' frames, hop must stay 256, got {pitch['hop']!r}")
         elif pitch:
             raise ValueError('evaluate_synthesis: pitch= configures the tracker of vocoder=, which is None')
+        elif f0_method != 'yin':
+            raise ValueError('evaluate_synthesis: f0_method= chooses the tracker of vocoder=, which is None')
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError(f'batch_size must be at least 1, got {batch_size}')
@@ -276,8 +283,8 @@ class Tacotron2:
                 for r, w in enumerate(spoken):
                     recorded[r, :len(w)] = w
                 samples = np.asarray([len(w) for w in spoken], dtype=np.int32)
-                f0_syn = runtime.pitch(vocoder.infer(mel, lengths=la), la * 256, **pitch)[0]
-                f0_rec = runtime.pitch(recorded, samples, **pitch)[0]
+                f0_syn = track_f0(runtime, f0_method, vocoder.infer(mel, lengths=la), la * 256, **pitch)[0]
+                f0_rec = track_f0(runtime, f0_method, recorded, samples, **pitch)[0]
                 # a recording below 1024 samples has fewer pitch frames than mel frames: the path ends where the track does
                 f0 = _to_numpy(runtime.f0_error(f0_syn, f0_rec, la, np.minimum(lb, 1 + samples // 256).astype(np.int32), path))
                 block[6, keep], block[9, keep] = f0[2], f0[1]

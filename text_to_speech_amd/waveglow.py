@@ -300,7 +300,7 @@ class WaveGlow:
 
     RESYNTHESIS_NAMES = ['f0_rmse_cents', 'f0_mean_cents', 'vuv_error', 'gross_error', 'voiced_pairs', 'pairs']
 
-    def resynthesis_f0(self, items, **infer_kwargs):
+    def resynthesis_f0(self, items, f0_method='yin', f0_config=None, **infer_kwargs):
         """Does the vocoder keep the pitch?  `items` as for `evaluate`: recordings (waveforms or file names) or (audio, mel)
         pairs, each prepared by `_recording`.  The mel is vocoded (`infer` with `infer_kwargs`), `pitch` (tts_hip_pitch, the
         defaults at the model's rate) runs on the recording zero-padded to frames * 256 samples and on the vocoded audio, and
@@ -308,10 +308,13 @@ class WaveGlow:
         RESYNTHESIS_NAMES, 'per_item': float32 [6, N] in input order, 'mean': {name: float}}: the F0 RMSE and the mean
         deviation of the voiced pairs in cents, the voicing error rate (of the pairs), the gross pitch error rate (more than
         20 % off; of the voiced pairs, 0 without any), the voiced pairs and the pairs.  Needs a runtime with an `engine`
-        (HipRuntime) behind the model."""
+        (HipRuntime) behind the model.  `f0_method='pyin'` tracks both with `pyin` (tts_hip_pyin) in place of `pitch`;
+        `f0_config`: further keywords of the tracker (the rate stays the model's)."""
+        from .pitch import track_f0
         engine = getattr(self.compiled_infer, 'engine', None)
         if getattr(engine, 'pitch', None) is None or getattr(engine, 'f0_error', None) is None:
             raise ValueError('resynthesis_f0 needs a runtime with an engine (HipRuntime) behind the model')
+        f0_config = dict(f0_config or {}, rate=self.rate)
         upload = getattr(self.compiled_infer, '_uploaded', lambda x: x)
         names = self.RESYNTHESIS_NAMES
         per_item = np.zeros((len(names), len(items)), dtype=np.float32)
@@ -321,7 +324,8 @@ class WaveGlow:
             if mel.shape[0] < 1:
                 raise ValueError(f'items[{i}] holds no frame')
             vocoded = self.infer(upload(mel)[None], **infer_kwargs)
-            f0_rec, f0_voc = engine.pitch(upload(wave)[None], rate=self.rate)[0], engine.pitch(vocoded, rate=self.rate)[0]
+            f0_rec = track_f0(engine, f0_method, upload(wave)[None], **f0_config)[0]
+            f0_voc = track_f0(engine, f0_method, vocoded, **f0_config)[0]
             s = _to_numpy(engine.f0_error(f0_rec, f0_voc))[:, 0]
             per_item[:, i] = s[2], s[3], s[4] / max(s[0], 1), s[5] / max(s[1], 1), s[1], s[0]
         mean = {name: float(per_item[k].astype(np.float64).mean()) if len(items) else float('nan') for k, name in enumerate(names)}
