@@ -755,6 +755,64 @@ int tts_hip_time_stretch_async(tts_hip_engine* e, const float* audio, int B, int
 int tts_hip_time_stretch_probe(tts_hip_engine* e, const float* audio, int B, int N, const int32_t* lengths, const double* rates,
                                const tts_hip_mel_fn* fn, int what, float* out, int M, int mem);
 
+/* ---- formant match (csrc/stft_inv.hip): the spectral envelope of one signal put onto another, the phases kept.
+ * A pitch shift by resampling moves the vocal-tract resonances along with the harmonics; this call multiplies the shifted
+ * signal's spectrum, on the same frame grid, by the ratio of the original's cepstrally smoothed envelope to its own.  Warping
+ * the source envelope along frequency moves the formants with or without a pitch change.
+ *
+ * formant_match: audio [B, N] (the signal to correct), source [B, N] or NULL = the audio itself (the signal whose envelope is
+ *   wanted; both follow `mem`, device memory for the _async form), lengths as tts_hip_mel_fn_run (they hold for both signals),
+ *   warps [B] (HOST doubles in every mode, in [0.5, 2]; NULL = 1 for every row), the lifter cut Q = `lifter`,
+ *   max_gain_db in (0, 60] -> out [B, N], under a Tacotron-kind plan.  With cut = filter_length / 2 + 1, n = filter_length,
+ *   F_b = tts_hip_mel_fn_frames(fn, lengths[b]):
+ *   1. X_b, Y_b are the spectra of source and audio: steps 1 - 4 of the mel plan (stage 1 of tts_hip_mel_fn_probe).  With
+ *      source NULL there is one transform and X = Y.
+ *   2. lx[f][k] = logf(max(|X[f][k]|, 1e-5f)) and ly the same from Y, |z| = sqrtf(re * re + im * im) with every operation
+ *      rounded on its own (as step 3 of the time stretch); 1e-5 is the clip of the mel plan's logarithm.
+ *   3. Sx = lx . L and Sy = ly . L with the liftering table L [cut, cut], L[j][k] = (w_j / n) * sum_{q = 0 .. Q} v_q
+ *      cos(2 pi q j / n) cos(2 pi q k / n), w_0 = w_{cut-1} = 1 and v_0 = 1, every other weight 2: the real cepstrum of the even
+ *      extension of a row, cut after quefrency Q, transformed back.  L is built on the host in double at first use for a
+ *      (plan, Q), rounded once to fp32 and kept with the plan's tables (a call with another Q rebuilds it); both products are
+ *      one fp32 GEMM over the 2 * B * F stacked rows, K = cut padded to a multiple of 32.
+ *   4. Per row, beta = warps[b], per bin k: pos = (double)k / beta, i = floor(pos), a = (float)(pos - i);
+ *      E[f][k] = (1 - a) * Sx[f][i] + a * Sx[f][i + 1] - Sy[f][k] in fp32, no fused multiply-add (the difference 1 - a, two
+ *      products, a sum, a difference); where i >= cut - 1 the top bin is held: Sx[f][cut - 1] - Sy[f][k].  beta = 1 gives
+ *      a = 0 and E = Sx - Sy exactly.
+ *   5. g = expf(min(max(E, -G), G)), G = (float)(max_gain_db * ln(10) / 20).
+ *   6. Per frame e0 = sum_k |Y[f][k]|^2 and e1 = sum_k (g[f][k] |Y[f][k]|)^2 over the cut bins, fp32, in a fixed order (one
+ *      workgroup per frame, no atomics; products and sums not fused); s = sqrtf(e0 / e1), s = 1 where e1 == 0;
+ *      gain = g * s.  The mean-log envelope of a higher-pitched voice sits lower between its sparser harmonics; s removes
+ *      that bias and keeps every frame's energy.
+ *   7. Y' = gain * Y, both components; frames at and beyond F_b are 0.
+ *   8. out = inverse(Y') exactly as tts_hip_denoise finishes: row b holds min(lengths[b], tts_hip_mel_fn_samples(fn, F_b))
+ *      samples and zeros beyond.
+ *   source NULL with warps 1 gives E = 0, gain = 1 and Y' = Y bit for bit: the STFT round trip.  Nothing behind a row's
+ *   length is read, in either signal; nothing is accumulated with atomics: a row is bit-equal to the row called alone and a
+ *   repeat gives the same bits.  The transforms run one after the other in the mel workspace of the handle (the source's
+ *   log-magnitudes are taken before the audio's transform runs; the audio's spectrum stays there until step 7), everything
+ *   else in the inverse workspace, with no host round trip: the _async form (device pointers, a stream; lengths and warps
+ *   stay host arrays) does not synchronize once the tables of the (plan, Q) exist.
+ *
+ * formant_match_probe (test hook): the code of the call, not a copy, stopped after stage `what`, with F =
+ *   tts_hip_mel_fn_frames(fn, N): 0 logmag [2, B, F, cut] (source, then audio); 1 envelope [2, B, F, cut] (Sx, then Sy);
+ *   2 gain [B, F, cut] after step 6; 3 operand Y' [B, F, 2 cut] (real parts, then imaginary parts); 4 time frames
+ *   [B, F, filter_length].  Frames at and beyond F_b are 0 in every stage.  The call itself is the last stage.
+ *
+ * Refusals (TTS_HIP_EINVAL, first match wins, nothing copied or launched; formant_match_check in csrc/audio_call.h): a plan
+ * that is not a plan of this handle; a NULL plan, audio or out, B or N < 1; a lengths[b] outside [1, N]; a row the reflect
+ * cannot pad (as tts_hip_mel_fn_run); a Whisper plan; pre_emph > 0 (the inverse does not undo it); a warp that is not finite
+ * or lies outside [0.5, 2]; Q outside [1, filter_length / 2 - 1]; max_gain_db not finite, not above 0 or above 60; a buffer
+ * at or above 2^31 - 65536 bytes (the 2 * B * F stacked rows included) or B > 65535; a bad mem kind; a `what` outside 0 .. 4
+ * (probe). */
+int tts_hip_formant_match(tts_hip_engine* e, const float* audio, const float* source, int B, int N, const int32_t* lengths,
+                          const tts_hip_mel_fn* fn, const double* warps, int lifter, double max_gain_db, float* out, int mem);
+int tts_hip_formant_match_async(tts_hip_engine* e, const float* audio, const float* source, int B, int N, const int32_t* lengths,
+                                const tts_hip_mel_fn* fn, const double* warps, int lifter, double max_gain_db, float* out,
+                                void* stream);
+int tts_hip_formant_match_probe(tts_hip_engine* e, const float* audio, const float* source, int B, int N, const int32_t* lengths,
+                                const tts_hip_mel_fn* fn, const double* warps, int lifter, double max_gain_db, int what, float* out,
+                                int mem);
+
 /* ---- waveform clean-up (csrc/audio_proc.hip; DFT bases built on first use, no weights needed)
  * reduce_noise: utils/audio/noisereducev1.py:175-290 with the defaults utils/audio/audio_processing.py:65-83 uses.
  *   audio [B, N] -> out [B, N]; row b has lengths[b] (1 <= lengths[b] <= N) samples, lengths NULL = N for every row, and
@@ -884,7 +942,9 @@ int tts_hip_resample_fft_probe(tts_hip_engine* e, const float* in, int lines, in
  * files its four parts there too: 2 = forward DFT (padding and gather included), 3 = gate, 0 = inverse-frames GEMM, 1 =
  * overlap-add.  A tts_hip_mel_dtw call files its launches as 0 = cepstra, 1 = distances, 2 = sweep, 3 = backtrack (without
  * alignment: the diagonal's reduction).  A tts_hip_time_stretch call files five parts: 2 = forward DFT, 3 = the vocoder's
- * parallel pass, 4 = its chain over the frames (the only use of kind 4), 0 = inverse-frames GEMM, 1 = overlap-add.
+ * parallel pass, 4 = its chain over the frames, 0 = inverse-frames GEMM, 1 = overlap-add.  A tts_hip_formant_match call files
+ * its parts as 2 = forward DFT (one launch group per transform: two with a source), 3 = log-magnitudes and the envelope GEMM,
+ * 4 = the gain kernel (kind 4 has these two uses), 0 = inverse-frames GEMM, 1 = overlap-add.
  * Timing is off unless enabled (events perturb nothing but cost a few us each).        */
 int tts_hip_kernel_timing(tts_hip_engine* e, int enable);
 /* Box probe: TFLOP/s a bare v_mfma_f32_32x32x2_f32 loop sustains on this device right now (every CU, 2 waves per SIMD, ~20 ms)

@@ -152,6 +152,12 @@ SIGNATURES = {
                                            c_void_p]),
     'tts_hip_time_stretch_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                            c_int]),
+    'tts_hip_formant_match': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                                      c_void_p, c_int]),
+    'tts_hip_formant_match_async': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                                            c_void_p, c_void_p]),
+    'tts_hip_formant_match_probe': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_double,
+                                            c_int, c_void_p, c_int]),
     'tts_hip_resample_async': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     'tts_hip_resample_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
     'tts_hip_resample_fft_probe': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -1,4 +1,4 @@
-// audio_call.h -- what the audio front-end calls (mel-STFT, STFT inverse / Griffin-Lim, denoise, time_stretch, reduce_noise / trim_silence, resample, remove_silence) may be
+// audio_call.h -- what the audio front-end calls (mel-STFT, STFT inverse / Griffin-Lim, denoise, time_stretch, formant_match, reduce_noise / trim_silence, resample, remove_silence) may be
 // refused for, and the geometry those refusals rest on: pure host code on the caller's arguments (no HIP include; also built
 // with plain g++ under ASan / UBSan by csrc/host_check.cpp, --audio-call, and compared there with a Python restatement,
 // tests/test_audio_call.py).  The .hip files forward the message to set_err; nothing is copied or launched before a check
@@ -747,6 +747,103 @@ inline int time_stretch_check(const char* who, const MelPlan* p, const float* au
     g->off_owner = c.take((size_t)cells * 4);
     g->off_adv = c.take((size_t)cells * 8);
     g->off_rel = c.take((size_t)cells * 8);
+    g->inv.total = c.o;
+    return TTS_HIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- formant match (stft_inv.hip)
+enum { FM_LOGMAG = 0, FM_ENVELOPE, FM_GAIN, FM_OPERAND, FM_FRAMES, FM_STAGES };
+constexpr double kFmWarpMin = 0.5, kFmWarpMax = 2.0, kFmGainDbMax = 60.0;
+
+inline bool fm_warp_ok(double w) { return std::isfinite(w) && w >= kFmWarpMin && w <= kFmWarpMax; }
+
+// The liftering table of a plan, L [cut][cut] in double: L[j][k] = (w_j / n) sum_{q <= Q} v_q cos(2 pi q j / n) cos(2 pi q k / n),
+// w_0 = w_{cut-1} = 1 and v_0 = 1, every other weight 2 -- the real cepstrum of the even extension of a row of cut values, cut
+// after quefrency Q, transformed back (smoothed = row . L).  The phases are reduced exactly (q k mod n).
+inline void fm_lifter_table(int fl, int Q, std::vector<double>& L) {
+    const int cut = fl / 2 + 1;
+    std::vector<double> C((size_t)(Q + 1) * cut);
+    for (int q = 0; q <= Q; ++q)
+        for (int k = 0; k < cut; ++k) C[(size_t)q * cut + k] = std::cos(2.0 * M_PI * (double)(((long long)q * k) % fl) / fl);
+    L.assign((size_t)cut * cut, 0.0);
+    for (int j = 0; j < cut; ++j) {
+        double* row = L.data() + (size_t)j * cut;
+        for (int q = 0; q <= Q; ++q) {
+            const double c = (q ? 2.0 : 1.0) * C[(size_t)q * cut + j];
+            const double* cq = C.data() + (size_t)q * cut;
+            for (int k = 0; k < cut; ++k) row[k] += c * cq[k];
+        }
+        const double w = ((j == 0 || j == cut - 1) ? 1.0 : 2.0) / fl;
+        for (int k = 0; k < cut; ++k) row[k] *= w;
+    }
+}
+
+// A formant-match call is one or two transforms on the rows' own frames (`fwd`: lens, fout = F_b, its workspace in
+// e->stft.ws, which holds the audio's spectrum Y from the last transform to the gain kernel) and an inverse on F = fwd.Fr
+// frame slots (`inv`: frames = F_b, its workspace in e->stft.inv_ws).  Behind the inverse's own buffers that workspace holds
+// `warps` [B] doubles; `logmag` [2 * B * F][MAGK] fp32, the envelope GEMM's A operand (the source's rows, then the audio's;
+// zero in the K padding and in the frames behind a row's own); `env` [2 * B * F][cut] fp32, Sx then Sy; and for the probe's
+// stage FM_GAIN `gain` [B * F][cut].  inv.total covers them.  Row b of the result holds keep[b] = min(lens[b],
+// stft_samples(F_b)) samples.
+struct FmGeom {
+    MelGeom fwd;
+    GlGeom inv;
+    std::vector<double> warps;
+    std::vector<int> keep;
+    int Q;
+    float G;                                // the clamp of the log gain, (float)(max_gain_db * ln(10) / 20)
+    size_t off_warps, off_logmag, off_env, off_gain;
+};
+
+// What tts_hip_formant_match[_async, _probe] may be refused for -- order: pointers (plan, audio, out) / B / N, lengths[b], a
+// row reflect cannot pad, a Whisper plan, pre_emph > 0, a warp not finite or outside [0.5, 2] (warps NULL: 1 for every row),
+// Q outside [1, filter_length / 2 - 1], max_gain_db not finite, not above 0 or above 60, the 31-bit limits (either workspace,
+// the 2 * B * F stacked rows of the envelope GEMM, audio and out [B][N]; B <= 65535), mem kind, what (probe: what >= 0; the
+// call itself: -1); fills `g`.  `source` may be NULL (the audio itself) and is not looked at here.
+inline int formant_match_check(const char* who, const MelPlan* p, const float* audio, int B, int N, const int32_t* lengths,
+                               const double* warps, int Q, double max_gain_db, const float* out, int mem, int what, FmGeom* g,
+                               char* msg, size_t n) {
+    if (!p || !audio || !out || B < 1 || N < 1) return audio_refuse(msg, n, who, "bad argument");
+    int min_len;
+    if (int rc = audio_rows_check(who, B, N, lengths, g->fwd.lens, &min_len, msg, n)) return rc;
+    for (int b = 0; b < B; ++b)
+        if (mel_dft_frames(*p, g->fwd.lens[b]) < 1)
+            return audio_refuse(msg, n, who, "row %d: max(L = %d, win_length = %d) samples are not more than filter_length // 2 = %d",
+                                b, g->fwd.lens[b], p->wl, p->half);
+    if (p->kind != TTS_HIP_MEL_TACOTRON) return audio_refuse(msg, n, who, "refused for a Whisper plan");
+    if (p->pre > 0) return audio_refuse(msg, n, who, "pre_emph = %g > 0 cannot be inverted", p->pre);
+    g->warps.assign(B, 1.0);
+    if (warps)
+        for (int b = 0; b < B; ++b) {
+            if (!fm_warp_ok(warps[b]))
+                return audio_refuse(msg, n, who, "warps[%d] = %g must be finite and lie in [%g, %g]", b, warps[b], kFmWarpMin, kFmWarpMax);
+            g->warps[b] = warps[b];
+        }
+    if (Q < 1 || Q > p->fl / 2 - 1) return audio_refuse(msg, n, who, "lifter Q = %d outside [1, filter_length / 2 - 1 = %d]", Q, p->fl / 2 - 1);
+    if (!(std::isfinite(max_gain_db) && max_gain_db > 0 && max_gain_db <= kFmGainDbMax))
+        return audio_refuse(msg, n, who, "max_gain_db = %g must be finite and lie in (0, %g]", max_gain_db, kFmGainDbMax);
+    const long long big = mel_geom_layout(*p, B, N, &g->fwd);
+    const long long rows2 = 2ll * B * g->fwd.Fr;
+    if (B > 65535 || big >= kAudioLim || rows2 * p->MAGK * 4 >= kAudioLim ||
+        gl_geom_layout(*p, B, g->fwd.Fr, p->cut, -1, -1, &g->inv) >= kAudioLim)
+        return audio_refuse(msg, n, who, "B = %d x N = %d too large for 31-bit offsets (B <= 65535)", B, N);
+    if (int rc = audio_mem_check(who, mem, msg, n)) return rc;
+    if (what >= FM_STAGES) return audio_refuse(msg, n, who, "no stage %d (0 .. %d)", what, FM_STAGES - 1);
+    g->Q = Q;
+    g->G = (float)(max_gain_db * std::log(10.0) / 20.0);
+    g->fwd.fout.resize(B);
+    g->keep.resize(B);
+    for (int b = 0; b < B; ++b) {
+        g->fwd.fout[b] = mel_dft_frames(*p, g->fwd.lens[b]);
+        g->keep[b] = (int)std::min<long long>(g->fwd.lens[b], stft_samples(*p, g->fwd.fout[b]));
+    }
+    g->inv.frames = g->fwd.fout;
+    Carve c;
+    c.o = g->inv.total;
+    g->off_warps = c.take((size_t)B * 8);
+    g->off_logmag = c.take((size_t)rows2 * p->MAGK * 4);
+    g->off_env = c.take((size_t)rows2 * p->cut * 4);
+    g->off_gain = c.take(what == FM_GAIN ? (size_t)(rows2 / 2) * p->cut * 4 : 0);
     g->inv.total = c.o;
     return TTS_HIP_OK;
 }

@@ -216,6 +216,8 @@ struct tts_hip_mel_fn {
     float* win2 = nullptr;              // [filter_length] the centred window squared
     float* minv_Bt = nullptr;           // [cut][EK] the filterbank's minimum-norm inverse (log-mel input), zero padded
     int minv_state = 0;                 //   0 not tried, 1 built, -1 the factorisation failed
+    float* lift_Bt = nullptr;           // [cut][MAGK] the liftering table of tts_hip_formant_match: row k holds L[.][k], zero padded
+    int lift_Q = 0;                     //   the cut it was built for (0: not built); a call with another Q rebuilds it
     std::vector<double> win;            // the window centred in filter_length (what the tables were built from)
     std::vector<void*> allocs;
 };

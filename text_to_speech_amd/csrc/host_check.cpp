@@ -87,6 +87,13 @@
 // the call is accepted "Fr T M", the five offsets of the vocoder's buffers and the inverse workspace's extent, then F_b, T_b,
 // S_b and the kept samples per row.  helpers=1: no check; "frames samples" of ts_row_frames / ts_row_samples per LEN
 // (tests/test_time_stretch.py compares all of it with a Python restatement).
+//        ttsw_check_asan --formant-match [KEY=VALUE...] [LEN...]  -- the front end of a formant-match call (formant_match_check of
+// audio_call.h) for a batch of B = number of LEN rows of N samples (no LEN: lengths NULL, B from B=) run as an entry point named
+// "who", on a plan as --time-stretch takes it.  Settings: B= N= Q= max_gain_db= mem= what= warps=W,W,... (one value: every
+// row's; absent: warps NULL) and null=fn,audio,out.  First line "<status> <message>"; when the call is accepted "Fr Q" and the
+// bits of the fp32 clamp G, the four offsets of the call's own buffers and the inverse workspace's extent, then F_b and the kept
+// samples per row.  table=1: no check; the liftering table fm_lifter_table(filter_length, Q), one value a line
+// (tests/test_formant.py compares all of it with a Python restatement).
 // Exit status 0 unless a sanitizer aborts the process.
 #include <cstdlib>
 #include <vector>
@@ -696,7 +703,76 @@ static int print_time_stretch(int argc, char** argv) {
     return 0;
 }
 
+static int print_formant_match(int argc, char** argv) {
+    // never read: the check only tests the pointers' values
+    const float* audio = (const float*)(uintptr_t)0x100000000ull;
+    float* out = (float*)(uintptr_t)0x200000000ull;
+    std::map<std::string, double> v{{"B", -1}, {"N", 0}, {"Q", 33}, {"max_gain_db", 24}, {"mem", TTS_HIP_MEM_DEVICE}, {"what", -1},
+                                    {"mel_kind", 0}, {"filter_length", 1024}, {"hop_length", 256}, {"win_length", 1024},
+                                    {"pre_emph", 0}, {"table", 0}};
+    std::string nulls;
+    std::vector<int32_t> lengths;
+    std::vector<double> warps;
+    bool have_warps = false;
+    for (int i = 2; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (!eq) {
+            lengths.push_back((int32_t)atoi(argv[i]));
+            continue;
+        }
+        const std::string key(argv[i], (size_t)(eq - argv[i]));
+        if (key == "null") nulls = eq + 1;
+        else if (key == "warps") {
+            have_warps = true;
+            for (const char* p = eq + 1; *p;) {
+                char* end = nullptr;
+                warps.push_back(strtod(p, &end));
+                if (end == p) return 2;
+                p = *end == ',' ? end + 1 : end;
+            }
+        } else if (v.count(key)) v[key] = atof(eq + 1);
+        else return 2;
+    }
+    const auto null = [&](const char* name) { return ("," + nulls + ",").find(std::string(",") + name + ",") != std::string::npos; };
+    const int B = lengths.empty() ? (int)v["B"] : (int)lengths.size(), N = (int)v["N"];
+    // a table shorter than B would be read past its end by the check: that is the caller's contract, not the check's
+    if (warps.size() == 1 && B > 1 && B <= (1 << 20)) warps.assign((size_t)B, warps[0]);
+    if (have_warps && B > 0 && (long long)warps.size() < B) return 2;
+    const tts_hip_mel_config cfg{(int)v["mel_kind"], 22050, 1, (int)v["filter_length"], (int)v["hop_length"], (int)v["win_length"], 0, 0.0,
+                                 11025.0, v["pre_emph"]};
+    char why[256] = "";
+    MelPlan p{};
+    int rc = mel_cfg_check("who", &cfg, nullptr, true, &p, why, sizeof why);
+    if (!rc && v["table"] != 0) {                               // the liftering table alone, one value a line
+        const int Q = (int)v["Q"];
+        if (Q < 0 || Q > p.fl) return 2;
+        std::vector<double> L;
+        fm_lifter_table(p.fl, Q, L);
+        printf("0 \n");
+        for (double x : L) printf("%.17g\n", x);
+        return 0;
+    }
+    FmGeom g;
+    if (!rc)
+        rc = formant_match_check("who", null("fn") ? nullptr : &p, null("audio") ? nullptr : audio, B, N,
+                                 lengths.empty() ? nullptr : lengths.data(), have_warps ? warps.data() : nullptr, (int)v["Q"],
+                                 v["max_gain_db"], null("out") ? nullptr : out, (int)v["mem"], (int)v["what"], &g, why, sizeof why);
+    printf("%d %s\n", rc, why);
+    if (rc) return 0;
+    if ((int)g.fwd.lens.size() != B || (int)g.fwd.fout.size() != B || (int)g.inv.frames.size() != B || (int)g.keep.size() != B ||
+        (int)g.warps.size() != B)
+        return 2;
+    uint32_t gbits;
+    memcpy(&gbits, &g.G, 4);
+    printf("%d %d %u\n", g.fwd.Fr, g.Q, gbits);
+    printf("%zu %zu %zu %zu %zu\n", g.off_warps, g.off_logmag, g.off_env, g.off_gain, g.inv.total);
+    for (int b = 0; b < B; ++b) printf("%d%c", g.inv.frames[b], b == B - 1 ? '\n' : ' ');
+    for (int b = 0; b < B; ++b) printf("%d%c", g.keep[b], b == B - 1 ? '\n' : ' ');
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && !strcmp(argv[1], "--formant-match")) return print_formant_match(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--time-stretch")) return print_time_stretch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--pitch")) return print_pitch(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "--pyin")) return print_pyin(argc, argv);

@@ -12,7 +12,10 @@
 // Time stretching (tts_hip_time_stretch) puts a phase-locked vocoder (identity phase locking, Laroche and Dolson 1999)
 // between the same transform and inverse: a parallel pass over every output frame (magnitudes, peaks, each bin's nearest
 // peak, the phase factors) and one workgroup per row that walks the frames and carries the synthesis phase in LDS.
-// include/tts_hip.h has the contract, audio_call.h the checks and the geometry (GlGeom, DnGeom, TsGeom), mel_stft.hip the plans and
+// Formant matching (tts_hip_formant_match) puts the ratio of two cepstrally smoothed envelopes there: the log-magnitudes of a
+// source's and the audio's spectra, one GEMM against a liftering table, and one workgroup per frame that turns the ratio into
+// an energy-keeping gain on the audio's spectrum.
+// include/tts_hip.h has the contract, audio_call.h the checks and the geometry (GlGeom, DnGeom, TsGeom, FmGeom), mel_stft.hip the plans and
 // the forward DFT.
 //
 // The inverse basis has a closed form, so no SVD runs here: pinv(scale * [cos; -sin])^T has the rows
@@ -358,6 +361,82 @@ __global__ __launch_bounds__(1024) void ts_chain_kernel(const float* __restrict_
 __global__ void ts_owner_float_kernel(const int* __restrict__ owner, float* __restrict__ out, long long n) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < n) out[idx] = (float)owner[idx];
+}
+
+// ---- formant match: the cepstral envelopes of source and audio and their ratio as a gain on the audio's spectrum
+// (include/tts_hip.h has the math)
+// The envelope GEMM's A operand, rows [B * F][CK] of logf(max(|X|, 1e-5f)) from the spectrum ft [B * F][NB]: 0 in the frames
+// behind a row's own and in the K padding.  `twin` (source NULL: X = Y) takes the same values.
+__global__ void fm_logmag_kernel(const float* __restrict__ ft, float* __restrict__ A, float* __restrict__ twin, long long n, int F,
+                                 int cut, int NB, int CK, const int* __restrict__ frames) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const long long r = idx / CK;
+    const int c = (int)(idx % CK);
+    float v = 0.f;
+    if (c < cut && (int)(r % F) < frames[r / F]) {
+        const float* src = ft + r * NB;
+        v = logf(fmaxf(ts_abs(src[c], src[cut + c]), 1e-5f));
+    }
+    A[idx] = v;
+    if (twin) twin[idx] = v;
+}
+
+constexpr int FM_THREADS = 256;         // fm_gain_kernel: one workgroup per frame
+
+// Steps 4 - 7, one workgroup per (frame f, row b): the source's envelope Sx = env[b * F + f] read at k / beta (linear
+// interpolation, the top bin held; no fused multiply-add, so beta = 1 gives Sx itself), the log gain E = that - Sy (Sy =
+// env[rows + b * F + f]) clamped to +-G, g = expf(E), the frame's energies e0 = sum |Y|^2 and e1 = sum (g |Y|)^2 in a fixed
+// order (each thread its bins k = tid, tid + 256, ... in turn, then block_reduce), and the operand row gain * Y with gain =
+// g * sqrtf(e0 / e1) (e1 == 0: g).  Frames at and beyond frames[b] and the K padding are written 0.  gain_out (probe only)
+// [B * F][cut].  Dynamic LDS: cut floats (g).
+__global__ __launch_bounds__(FM_THREADS) void fm_gain_kernel(const float* __restrict__ ft, const float* __restrict__ env,
+                                                             const int* __restrict__ frames, const double* __restrict__ warps,
+                                                             float* __restrict__ A, float* __restrict__ gain_out, long long rows,
+                                                             int F, int cut, int NB, float G) {
+    extern __shared__ float fm_g[];
+    __shared__ float sh[16];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const long long r = (long long)b * F + f;
+    float* row = A + r * NB;
+    if (f >= frames[b]) {
+        for (int k = tid; k < NB; k += FM_THREADS) row[k] = 0.f;
+        if (gain_out)
+            for (int k = tid; k < cut; k += FM_THREADS) gain_out[r * cut + k] = 0.f;
+        return;
+    }
+    const float* Sx = env + r * cut;
+    const float* Sy = env + (rows + r) * cut;
+    const float* y = ft + r * NB;
+    const double beta = warps[b];
+    float e0 = 0.f, e1 = 0.f;
+    for (int k = tid; k < cut; k += FM_THREADS) {
+        const double pos = (double)k / beta, fl = floor(pos);
+        const int i = (int)fl;                                  // <= 2 (cut - 1)
+        float sx;
+        if (i >= cut - 1) {
+            sx = Sx[cut - 1];
+        } else {
+            const float a = (float)(pos - fl);
+            sx = __fadd_rn(__fmul_rn(__fsub_rn(1.f, a), Sx[i]), __fmul_rn(a, Sx[i + 1]));
+        }
+        const float E = __fsub_rn(sx, Sy[k]);
+        const float g = expf(fminf(fmaxf(E, -G), G));
+        const float m = ts_abs(y[k], y[cut + k]), gm = __fmul_rn(g, m);
+        e0 = __fadd_rn(e0, __fmul_rn(m, m));
+        e1 = __fadd_rn(e1, __fmul_rn(gm, gm));
+        fm_g[k] = g;
+    }
+    e0 = block_reduce(e0, sh, OpAdd{});
+    e1 = block_reduce(e1, sh, OpAdd{});
+    const float s = e1 == 0.f ? 1.f : sqrtf(e0 / e1);
+    for (int k = tid; k < cut; k += FM_THREADS) {               // a thread reads back the g of its own bins only
+        const float gain = __fmul_rn(fm_g[k], s);
+        row[k] = gain * y[k];
+        row[cut + k] = gain * y[cut + k];
+        if (gain_out) gain_out[r * cut + k] = gain;
+    }
+    for (int k = 2 * cut + tid; k < NB; k += FM_THREADS) row[k] = 0.f;
 }
 
 // log-mel input: E [B * F][EK] = exp(spec [B * F][nmel]) on a row's own frames, 0 beyond and in the K padding
@@ -743,7 +822,144 @@ int ts_call(tts_hip_engine* e, const char* name, const float* audio, int B, int 
     return rc;
 }
 
+// the liftering table of a plan for the cut Q, on first use; a call with another Q rebuilds it in place
+int lift_table(tts_hip_engine* e, tts_hip_mel_fn* fn, int Q) {
+    if (fn->lift_Q == Q) return TTS_HIP_OK;
+    const MelPlan& p = fn->p;
+    std::vector<double> L;
+    fm_lifter_table(p.fl, Q, L);
+    std::vector<float> bt((size_t)p.cut * p.MAGK, 0.f);         // Bt [N = cut][K = MAGK]: row k holds L[.][k]
+    for (int j = 0; j < p.cut; ++j)
+        for (int k = 0; k < p.cut; ++k) bt[(size_t)k * p.MAGK + j] = (float)L[(size_t)j * p.cut + k];
+    if (!fn->lift_Bt)
+        if (int rc = dev_alloc(e, bt.size(), &fn->lift_Bt, fn->allocs, false)) return rc;
+    fn->lift_Q = 0;
+    HIPCHK(e, hipDeviceSynchronize());                          // an earlier call may still read the table of another Q
+    HIPCHK(e, hipMemcpy(fn->lift_Bt, bt.data(), bt.size() * sizeof(float), hipMemcpyHostToDevice));
+    fn->lift_Q = Q;
+    return TTS_HIP_OK;
+}
+
+// device pointers only, the call already checked (g); d_source null: the audio itself.  stop >= 0 (the probe): return right
+// after that stage with *view describing it.  With tts_hip_kernel_timing on, the parts are timed as kinds 2 (forward DFT: pad,
+// gather where the plan has one, GEMM; twice with a source), 3 (log-magnitudes and the envelope GEMM), 4 (gain), 0
+// (inverse-frames GEMM) and 1 (overlap-add)
+int fm_exec(tts_hip_engine* e, tts_hip_mel_fn& fn, const FmGeom& g, const float* d_audio, const float* d_source, int B, int N,
+            float* d_out, int stop, StageView* view) {
+    const MelPlan& p = fn.p;
+    hipStream_t st = e->stream;
+    const int F = g.inv.F, CK = p.MAGK;
+    const long long rows = (long long)B * F, n = rows * CK;
+    GlBufs w;
+    if (int rc = gl_bufs(e, g.inv, &w)) return rc;
+    char* base = (char*)e->stft.inv_ws.p;
+    const double* d_warps = (const double*)(base + g.off_warps);
+    float *logmag = (float*)(base + g.off_logmag), *env = (float*)(base + g.off_env), *gain = (float*)(base + g.off_gain);
+    e->audio_info_h.resize((size_t)2 * B);                      // the warps as doubles
+    memcpy(e->audio_info_h.data(), g.warps.data(), (size_t)B * 8);
+    if (int rc = stage_row_info(e, (int*)(base + g.off_warps))) return rc;
+    StageView spec{};
+    if (d_source) {                                             // the mel workspace holds one spectrum at a time
+        timing_begin(e, 2);
+        if (int rc = mel_fn_exec(e, fn, g.fwd, d_source, B, N, true, nullptr, MEL_SPECTRUM, &spec)) return rc;
+        timing_end(e);
+        timing_begin(e, 3);
+        hipLaunchKernelGGL(fm_logmag_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, (const float*)spec.p, logmag, (float*)nullptr, n, F,
+                           p.cut, p.NB, CK, w.info);
+        HIPCHK(e, hipGetLastError());
+        timing_end(e);
+    }
+    timing_begin(e, 2);
+    if (int rc = mel_fn_exec(e, fn, g.fwd, d_audio, B, N, true, nullptr, MEL_SPECTRUM, &spec)) return rc;
+    timing_end(e);
+    const float* Y = (const float*)spec.p;                      // stays in the mel workspace until the gain kernel has read it
+    const int* d_lens = (const int*)((const char*)e->stft.ws.p + g.fwd.off_info);
+    timing_begin(e, 3);
+    hipLaunchKernelGGL(fm_logmag_kernel, dim3(blocks(n, 256)), dim3(256), 0, st, Y, logmag + n, d_source ? (float*)nullptr : logmag, n,
+                       F, p.cut, p.NB, CK, w.info);
+    HIPCHK(e, hipGetLastError());
+    timing_end(e);
+    if (stop == FM_LOGMAG) return *view = StageView{logmag, (size_t)(2 * rows), (size_t)p.cut, (size_t)CK}, TTS_HIP_OK;
+    timing_begin(e, 3);
+    HIPCHK(e, gemm_small(gemm_linear(logmag, CK, CK, fn.lift_Bt, CK, p.cut, (int)(2 * rows), env), 1, st));
+    timing_end(e);
+    if (stop == FM_ENVELOPE) return *view = StageView{env, (size_t)(2 * rows), (size_t)p.cut, (size_t)p.cut}, TTS_HIP_OK;
+    timing_begin(e, 4);
+    hipLaunchKernelGGL(fm_gain_kernel, dim3(F, B), dim3(FM_THREADS), (size_t)p.cut * 4, st, Y, env, w.info, d_warps, w.operand,
+                       stop == FM_GAIN ? gain : (float*)nullptr, rows, F, p.cut, p.NB, g.G);
+    HIPCHK(e, hipGetLastError());
+    timing_end(e);
+    if (stop == FM_GAIN) return *view = StageView{gain, (size_t)rows, (size_t)p.cut, (size_t)p.cut}, TTS_HIP_OK;
+    if (stop == FM_OPERAND) return *view = StageView{w.operand, (size_t)rows, (size_t)2 * p.cut, (size_t)p.NB}, TTS_HIP_OK;
+    timing_begin(e, 0);
+    if (int rc = inverse_frames(e, fn, g.inv, w)) return rc;
+    timing_end(e);
+    if (stop == FM_FRAMES) return *view = StageView{w.tframes, (size_t)rows, (size_t)p.fl, (size_t)p.fl}, TTS_HIP_OK;
+    timing_begin(e, 1);
+    const long long cells = (long long)B * N;
+    hipLaunchKernelGGL(ola_cut_kernel, dim3(blocks(cells, 256)), dim3(256), 0, st, w.tframes, fn.win2, d_out, cells, F, N, w.info, d_lens,
+                       p.hop, p.fl, p.half, (float)((double)p.fl / p.hop));
+    HIPCHK(e, hipGetLastError());
+    timing_end(e);
+    return TTS_HIP_OK;
+}
+
+// tts_hip_formant_match (what = -1), its probe (what = a stage) and the _async form (stream, device pointers)
+int fm_call(tts_hip_engine* e, const char* name, const float* audio, const float* source, int B, int N, const int32_t* lengths,
+            const tts_hip_mel_fn* fn, const double* warps, int Q, double max_gain_db, int what, float* out, int mem, bool async,
+            void* stream) {
+    if (int rc = mel_plan_check(e, name, fn)) return rc;
+    FmGeom g;
+    char why[256];
+    if (int rc = formant_match_check(name, fn ? &fn->p : nullptr, audio, B, N, lengths, warps, Q, max_gain_db, out, mem, what, &g, why,
+                                     sizeof why))
+        return set_err(e, rc, "%s", why);
+    tts_hip_mel_fn* plan = const_cast<tts_hip_mel_fn*>(fn);
+    HIPCHK(e, hipSetDevice(e->device));
+    if (int rc = inv_tables(e, plan)) return rc;
+    if (int rc = lift_table(e, plan, Q)) return rc;
+    if (async) {
+        StreamScope scope(e, stream);
+        return fm_exec(e, *plan, g, audio, source, B, N, out, -1, nullptr);
+    }
+    const size_t n_audio = (size_t)B * N * 4;
+    AudioStage io(e, mem);
+    const int in = io.in(audio, n_audio), is = io.in(source, n_audio);
+    const int res = what >= 0 ? io.scratch(n_audio) : io.out(out, n_audio);
+    if (int rc = io.begin()) return rc;
+    StageView view{};
+    if (int rc = fm_exec(e, *plan, g, io.ptr<const float>(in), io.ptr<const float>(is), B, N, io.ptr<float>(res), what, &view)) return rc;
+    if (what >= 0)
+        if (int rc = copy_stage_out(e, view, out, mem)) return rc;
+    const int rc = io.finish();
+    timing_collect(e);
+    return rc;
+}
+
 }  // namespace
+
+int tts_hip_formant_match(tts_hip_engine* e, const float* audio, const float* source, int B, int N, const int32_t* lengths,
+                          const tts_hip_mel_fn* fn, const double* warps, int lifter, double max_gain_db, float* out, int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    return fm_call(e, "formant_match", audio, source, B, N, lengths, fn, warps, lifter, max_gain_db, -1, out, mem, false, nullptr);
+}
+
+int tts_hip_formant_match_async(tts_hip_engine* e, const float* audio, const float* source, int B, int N, const int32_t* lengths,
+                                const tts_hip_mel_fn* fn, const double* warps, int lifter, double max_gain_db, float* out,
+                                void* stream) {
+    if (!e) return TTS_HIP_EINVAL;
+    return fm_call(e, "formant_match_async", audio, source, B, N, lengths, fn, warps, lifter, max_gain_db, -1, out, TTS_HIP_MEM_DEVICE,
+                   true, stream);
+}
+
+int tts_hip_formant_match_probe(tts_hip_engine* e, const float* audio, const float* source, int B, int N, const int32_t* lengths,
+                                const tts_hip_mel_fn* fn, const double* warps, int lifter, double max_gain_db, int what, float* out,
+                                int mem) {
+    if (!e) return TTS_HIP_EINVAL;
+    if (what < 0) return set_err(e, TTS_HIP_EINVAL, "formant_match_probe: no stage %d (0 .. %d)", what, FM_STAGES - 1);
+    return fm_call(e, "formant_match_probe", audio, source, B, N, lengths, fn, warps, lifter, max_gain_db, what, out, mem, false,
+                   nullptr);
+}
 
 long long tts_hip_time_stretch_samples(const tts_hip_mel_fn* fn, int n_samples, double rate) {
     return fn ? ts_row_samples(fn->p, n_samples, rate) : -1;

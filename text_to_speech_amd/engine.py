@@ -1262,6 +1262,69 @@ class HipEngine:
                                 lambda extras, outs: (lens, rates, plan.handle, self._TS_STAGES[what], outs[0],
                                                       int(samples.max())))[0]
 
+    # ------------------------------------------------------------------ formant match (csrc/stft_inv.hip)
+    _FM_STAGES = {'logmag': 0, 'envelope': 1, 'gain': 2, 'operand': 3, 'frames': 4}
+    FORMANT_WARPS = (0.5, 2.0)
+    FORMANT_MAX_GAIN_DB = 60.0
+
+    @staticmethod
+    def default_lifter(plan):
+        """The lifter cut used when none is given: max(1, round(0.0015 * sampling_rate)) -- 1.5 ms, 33 at 22 050 Hz, below the
+        period of a 600 Hz voice -- clipped to [1, filter_length // 2 - 1]."""
+        g = plan.geometry
+        return int(min(max(1, int(round(0.0015 * g['sampling_rate']))), max(1, g['filter_length'] // 2 - 1)))
+
+    def _formant_rows(self, plan, audio, source, warp, lifter, max_gain_db, lengths, what):
+        """(B, N, lengths or None, the source as `_call` takes an input, float64 warps [B], Q, max_gain_db) of a formant-match
+        call; `warp` a scalar or one value per row.  Raises before any GPU call."""
+        B, N, lens = self._audio_rows(audio, lengths, what)
+        if source is not None and self._batched(source, 2) != (B, N):
+            raise ValueError(f'{what}: source must have the shape of audio, [{B}, {N}] (or [{N}]), got {_dims(source)}')
+        warps = np.asarray(warp.detach().cpu().numpy() if hasattr(warp, 'detach') else warp, dtype=np.float64)
+        if warps.ndim == 0:
+            warps = np.full(B, float(warps))
+        if warps.shape != (B,):
+            raise ValueError(f'{what}: warp must be a scalar or hold one value per row, shape ({B},), got {warps.shape}')
+        lo, hi = self.FORMANT_WARPS
+        if not (np.isfinite(warps).all() and (warps >= lo).all() and (warps <= hi).all()):
+            raise ValueError(f'{what}: warp must be finite and lie in [{lo}, {hi}], got {warps.tolist()}')
+        top = plan.geometry['filter_length'] // 2 - 1
+        Q = self.default_lifter(plan) if lifter is None else lifter
+        if int(Q) != Q or not 1 <= int(Q) <= top:
+            raise ValueError(f'{what}: lifter must be an integer in [1, filter_length // 2 - 1 = {top}], got {lifter!r}')
+        if not (np.isfinite(max_gain_db) and 0 < max_gain_db <= self.FORMANT_MAX_GAIN_DB):
+            raise ValueError(f'{what}: max_gain_db must lie in (0, {self.FORMANT_MAX_GAIN_DB:g}], got {max_gain_db!r}')
+        return B, N, lens, (source, (B, N), 'float32'), np.ascontiguousarray(warps), int(Q), float(max_gain_db)
+
+    def formant_match(self, plan, audio, source=None, *, warp=1.0, lifter=None, max_gain_db=24.0, lengths=None, stream=None):
+        """Give audio [N] or [B, N] the spectral envelope of `source` (same shape; None: the audio itself) and keep its own
+        phases and pitch (tts_hip_formant_match) under `plan` (Tacotron kind, no pre-emphasis): both signals' log-magnitude
+        spectra are smoothed by cepstral liftering (quefrencies up to `lifter`; None: `default_lifter(plan)`), the audio's
+        spectrum is multiplied by exp of their difference, clamped to +-`max_gain_db` and scaled so that every frame keeps
+        its energy, then the plan's inverse.  `warp` (a scalar or one value per row, in [0.5, 2]) reads the source envelope
+        at k / warp: above 1 the formants move up.  Row b holds lengths[b] samples (default N) in both signals and gets back
+        what `denoise` gives a row, zeros beyond.  numpy in -> numpy out; a CUDA tensor in -> a CUDA tensor out; `stream`
+        (torch.cuda.Stream, device tensors only): tts_hip_formant_match_async is enqueued there and the call returns without
+        waiting."""
+        B, N, lens, src, warps, Q, db = self._formant_rows(plan, audio, source, warp, lifter, max_gain_db, lengths, 'formant_match')
+        return self._call('formant_match', [(audio, (B, N), 'float32'), src], lambda new: (new((B, N)),),
+                          lambda ins, outs, where: (ins[0], ins[1], B, N, lens, plan.handle, warps, Q, db, outs[0]), stream)[0]
+
+    def formant_match_probe(self, plan, audio, source, what, *, warp=1.0, lifter=None, max_gain_db=24.0, lengths=None):
+        """Test hook (tts_hip_formant_match_probe): run `formant_match` on the same arguments (host arrays) up to stage `what`
+        and return it, with F = mel_fn_frames(plan, N): 'logmag' and 'envelope' [2, B, F, bins] (source, then audio); 'gain'
+        [B, F, bins]; 'operand' [B, F, 2 bins] (real parts, then imaginary parts); 'frames' [B, F, filter_length]."""
+        if what not in self._FM_STAGES:
+            raise ValueError(f'what must be one of {tuple(self._FM_STAGES)}, got {what!r}')
+        B, N, lens, src, warps, Q, db = self._formant_rows(plan, audio, source, warp, lifter, max_gain_db, lengths,
+                                                           'formant_match_probe')
+        bins, F = plan.geometry['filter_length'] // 2 + 1, self.mel_fn_frames(plan, N)
+        shape = {'logmag': (2, B, F, bins), 'envelope': (2, B, F, bins), 'gain': (B, F, bins), 'operand': (B, F, 2 * bins),
+                 'frames': (B, F, plan.geometry['filter_length'])}[what]
+        return self._call('formant_match_probe', [(audio, (B, N), 'float32'), src], lambda new: (new(shape),),
+                          lambda ins, outs, where: (ins[0], ins[1], B, N, lens, plan.handle, warps, Q, db, self._FM_STAGES[what],
+                                                    outs[0]))[0]
+
     # ------------------------------------------------------------------ waveform clean-up (csrc/audio_proc.hip)
     _TRIM_MODES = {'start_end': 0, 'start': 1, 'end': 2}
 

@@ -481,6 +481,18 @@ class HipRuntime(Runtime):
         from .effects import time_stretch
         return time_stretch(audio, rate, engine=self.engine, plan=plan, lengths=lengths)
 
+    def pitch_shift(self, audio, n_steps, lengths=None, plan=None, **kwargs):
+        """`audio` [N] or [B, N] raised by `n_steps` semitones at the same duration on this runtime's engine
+        (`effects.pitch_shift`; `preserve_formants=True` keeps the voice's spectral envelope, `formant_steps` moves it)."""
+        from .effects import pitch_shift
+        return pitch_shift(audio, n_steps, engine=self.engine, plan=plan, lengths=lengths, **kwargs)
+
+    def formant_shift(self, audio, n_steps, lengths=None, plan=None, **kwargs):
+        """`audio` [N] or [B, N] with its formants moved by `n_steps` semitones, pitch and duration kept
+        (`effects.formant_shift`, default plan 1024 / 256 / 1024)."""
+        from .effects import formant_shift
+        return formant_shift(audio, n_steps, engine=self.engine, plan=plan, lengths=lengths, **kwargs)
+
     def waveglow_encode(self, audio, mel, lengths=None, stream=None):
         """The forward flow of the vocoder, audio [B, T*256] + mel [B, T, 80] -> (z [B, T*32, 8], stats [3, B]), fp32
         (HipEngine.waveglow_encode); a single utterance ([T*256] with [T, 80]) gets its batch axis."""

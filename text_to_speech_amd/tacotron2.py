@@ -72,7 +72,9 @@ class Tacotron2:
         """One text (or a dict holding it under 'text' / 'content') -> its result dict.  The keywords of the stages
         (`_stage_kwargs`): `embeddings`, `max_length=10.`, `max_text_length=-1`, `max_trial=5`, `min_fpt_ratio=2.`,
         `max_fpt_ratio=10.` (`_synthesize`), `vocoder`, `vocoder_config` (`_vocode_parts`), `silence_time=0.15`,
-        `reduce_noise`, `trim_silence`, `speed=1.0` (tempo; 1.25 speaks a quarter faster), `pitch_steps=0.0` (semitones)
+        `reduce_noise`, `trim_silence`, `speed=1.0` (tempo; 1.25 speaks a quarter faster), `pitch_steps=0.0` (semitones),
+        `preserve_formants=False` (the shifted voice keeps its spectral envelope), `formant_steps=0.0` (semitones the envelope
+        itself moves by: the apparent size of the speaker)
         (`_finish`; none of these is part of the `map.json` key); every other keyword reaches the text cleaner and both models.
         `utterance` (an int; `predict(sentence_streams=True)` numbers its inputs): every random draw of this text comes
         from a stream of its own -- part p at trial t decodes with the id (utterance, p, t) and is vocoded with (utterance, p),
@@ -448,10 +450,11 @@ class Tacotron2:
             audio = audio[start:end]
         return audio
 
-    def _apply_effects(self, audio, vocoder, speed, pitch_steps):
-        """`speed` (tempo, `effects.time_stretch`) and then `pitch_steps` (`effects.pitch_shift`) on the concatenated
-        utterance, on the engine `_clean_waveform` would use.  Both must be finite; the engine refuses a speed outside
-        [0.25, 4]."""
+    def _apply_effects(self, audio, vocoder, speed, pitch_steps, preserve_formants=False, formant_steps=0.0):
+        """`speed` (tempo, `effects.time_stretch`) and then `pitch_steps` (`effects.pitch_shift`, which takes
+        `preserve_formants` and `formant_steps`; without a pitch change `formant_steps` is `effects.formant_shift`) on the
+        concatenated utterance, on the engine `_clean_waveform` would use.  All must be finite; the engine refuses a speed
+        outside [0.25, 4] and formant steps beyond an octave."""
         from . import effects
         eng = getattr(getattr(vocoder, 'compiled_infer', None), 'engine', None) or getattr(self.compiled_infer, 'engine', None)
         if eng is None or not hasattr(eng, 'time_stretch'):
@@ -459,24 +462,29 @@ class Tacotron2:
         audio = np.asarray(audio, np.float32)
         if speed != 1.0:
             audio, _ = effects.time_stretch(audio, float(speed), engine=eng)
-        if pitch_steps != 0.0:
+        if formant_steps != 0.0 or (preserve_formants and pitch_steps != 0.0):
+            audio = effects.pitch_shift(audio, float(pitch_steps), engine=eng, preserve_formants=bool(preserve_formants),
+                                        formant_steps=float(formant_steps))
+        elif pitch_steps != 0.0:
             audio = effects.pitch_shift(audio, float(pitch_steps), engine=eng)
         return audio
 
     def _finish(self, part, audios, vocoder_time, *, callbacks=None, predicted=None, return_output=True, vocoder=None,
-                silence_time=0.15, reduce_noise=False, trim_silence=False, speed=1.0, pitch_steps=0.0):
+                silence_time=0.15, reduce_noise=False, trim_silence=False, speed=1.0, pitch_steps=0.0, preserve_formants=False,
+                formant_steps=0.0):
         """The last stage: `audios` (the waveforms of the text's non-empty parts, in order; None without a vocoder) ->
-        concatenation, `speed` / `pitch_steps` (`_apply_effects`; the defaults 1.0 and 0.0 call nothing), clean-up, result
-        dict ('time' is the duration after them), `predicted` entry, callbacks, return value.  Like the other keywords of
-        this stage, `speed` and `pitch_steps` are not part of the `map.json` key: a cached text is replayed as it was first
-        made."""
+        concatenation, `speed` / `pitch_steps` / `preserve_formants` / `formant_steps` (`_apply_effects`; the defaults 1.0,
+        0.0, False and 0.0 call nothing, and `preserve_formants` alone changes nothing), clean-up, result dict ('time' is the
+        duration after them), `predicted` entry, callbacks, return value.  Like the other keywords of this stage, `speed`,
+        `pitch_steps`, `preserve_formants` and `formant_steps` are not part of the `map.json` key: a cached text is replayed
+        as it was first made."""
         text, synth_time = part['text'], part.get('synth_time', 0.)
         audio_infos = {}
         if vocoder is not None:
             if len(audios) > 0:
                 audios = audios[0] if len(audios) == 1 else np.concatenate(audios, axis=0)
-                if (speed != 1.0 or pitch_steps != 0.0) and len(audios) > 0:
-                    audios = self._apply_effects(audios, vocoder, speed, pitch_steps)
+                if (speed != 1.0 or pitch_steps != 0.0 or formant_steps != 0.0) and len(audios) > 0:
+                    audios = self._apply_effects(audios, vocoder, speed, pitch_steps, preserve_formants, formant_steps)
                 if (reduce_noise or trim_silence) and len(audios) > 0:
                     audios = self._clean_waveform(audios, vocoder, reduce_noise, trim_silence)
                 audio_infos = {'audio': audios, 'rate': self.rate, 'time': len(audios) / self.rate}
@@ -825,7 +833,8 @@ def _replay(text, predicted, callbacks):
 
 _SYNTHESIZE_KWARGS = ('embeddings', 'max_length', 'max_text_length', 'max_trial', 'min_fpt_ratio', 'max_fpt_ratio')
 _VOCODE_KWARGS = ('vocoder', 'vocoder_config')
-_FINISH_KWARGS = ('vocoder', 'silence_time', 'reduce_noise', 'trim_silence', 'speed', 'pitch_steps')
+_FINISH_KWARGS = ('vocoder', 'silence_time', 'reduce_noise', 'trim_silence', 'speed', 'pitch_steps', 'preserve_formants',
+                  'formant_steps')
 
 
 def _stage_kwargs(kwargs):
